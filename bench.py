@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- IPM iterations/sec on the headline workload of BASELINE.json (dense 4096x8192 fp64 LP).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`)
 
 A "step" is one complete `InteriorPoint::solve` (mod.rs:199-240) of the rank's LP: the whole hot path
@@ -35,6 +35,11 @@ Extra objects on the JSON line:
   roofline.traffic / mfma_busy_pmc come from a separate rocprofv3 --pmc run (counters cannot be read from inside this
                  process) whose summary is committed under profiles/ WITH a hash of lp_amd/csrc at collection time:
                  they are reported only while that hash still matches the sources ("recorded, not measured in this run").
+
+--dump-outputs DIR: after the run, rank 0 writes what the timed path returned in its LAST timed step as DIR/<name>.npy
+(float64): x (the solution, or the gathered block of all ranks), fun, iterations, status; c4: one row / entry per member.
+The default run adds the same for its c2 / c4 measurements as c2_<name> / c4_<name>.  The inputs are seeded (synth.planted_lp),
+so two builds run with the same arguments can be compared output by output.
 """
 from __future__ import annotations
 
@@ -68,6 +73,22 @@ def csrc_hash() -> str:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
     return h.hexdigest()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, outputs, np):
+    """--dump-outputs: every output of the last timed step as d/<name>.npy in float64."""
+    if d is None:
+        return
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def cpu_baseline(A, b, c, m, n):
@@ -116,8 +137,10 @@ def cpu_baseline(A, b, c, m, n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 5; c2: 200)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64)")
     ap.add_argument("--m", type=int, default=4096)
     ap.add_argument("--n", type=int, default=8192)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -129,8 +152,10 @@ def main():
     args = ap.parse_args()
     if args.workload == "c2":
         args.m, args.n = 512, 1024
-        if args.steps == 5:
-            args.steps = 200           # a C2 solve is ~2 ms: keep the timed region near half a second
+    if args.steps is None:
+        args.steps = 200 if args.workload == "c2" else 5   # a C2 solve is ~2 ms: keep the timed region near half a second
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # STDOUT carries exactly one line, the JSON result.  Libraries that print to file descriptor 1 on their own (RCCL's
     # version banner under NCCL_DEBUG=VERSION, warnings) are sent to stderr for the lifetime of the process.
@@ -167,16 +192,18 @@ def main():
     if args.workload == "c4":
         return bench_c4(args, rank, local_rank, world, dist, dev, np, torch, lp_amd, synth)
     env = (rank, local_rank, world, dist, dev, np, torch, lp_amd, synth)
-    out = measure_single(args.m, args.n, args.steps, args.warmup, args.workload == "c2",
-                         world == 1 and not args.no_cpu_baseline, *env)
+    out, outputs = measure_single(args.m, args.n, args.steps, args.warmup, args.workload == "c2",
+                                  world == 1 and not args.no_cpu_baseline, *env)
     nbad = 0
     if args.workload == "c3" and (args.m, args.n) == (4096, 8192) and not args.only_headline:
         # The other two single-node configs of BASELINE.json, measured in the SAME run (short; after the headline's timed
         # region), so that the driver's default invocation records them too: c2 = config 2 (one 512x1024 LP per GPU, HBM
         # roofline of the passes over A), c4 = config 4 (32 LPs of 1024x2048 per GPU as one lockstep batch, LP/s, whole-solve
         # MFMA fraction, parity of every member against the oracle's envelope).  `value` above stays the headline's.
-        c2 = measure_single(512, 1024, 100, 5, True, False, *env)
-        c4, nbad = measure_c4(3, 1, *env)
+        c2, c2_outputs = measure_single(512, 1024, 100, 5, True, False, *env)
+        c4, nbad, c4_outputs = measure_c4(3, 1, *env)
+        outputs.update({"c2_" + k: v for k, v in c2_outputs.items()})
+        outputs.update({"c4_" + k: v for k, v in c4_outputs.items()})
         if rank == 0:
             keep = ("metric", "value", "unit", "ms_per_step", "config", "roofline")
             out["c2"] = {k: c2[k] for k in keep}
@@ -187,6 +214,7 @@ def main():
             out["c4"]["parity_rank0"] = c4["parity_rank0"]
             out["c4"]["parity_failed_members_any_rank"] = c4["parity_failed_members_any_rank"]
     if rank == 0:
+        dump_outputs(args.dump_outputs, outputs, np)
         emit(out)
     if dist is not None:
         dist.barrier()
@@ -197,8 +225,8 @@ def main():
 
 
 def measure_single(m, n, steps, warmup, c2, want_cpu_baseline, rank, local_rank, world, dist, dev, np, torch, lp_amd, synth):
-    """One independent m x n LP per GPU (seed = rank): the headline protocol (C3) and BASELINE config 2.  Returns the result
-    dict on rank 0 (None elsewhere)."""
+    """One independent m x n LP per GPU (seed = rank): the headline protocol (C3) and BASELINE config 2.  Returns (the result
+    dict on rank 0 (None elsewhere), the outputs of the last timed step)."""
     A, b, c, xstar = synth.planted_lp(rank, m, n)        # one independent LP per rank (seed = rank)
     ctx = lp_amd.Context(local_rank)
     ctx.upload_arrays(A, b, c)                           # one-time H2D, outside the timed region
@@ -243,6 +271,8 @@ def measure_single(m, n, steps, warmup, c2, want_cpu_baseline, rank, local_rank,
         gemv_passes += pt["gemv_passes"]
     barrier()
     dt = time.perf_counter() - t0
+    # what the last timed step returned, before the solves below overwrite x_dev
+    outputs = {"x": (gathered if dist is not None else x_dev).cpu().numpy(), "fun": fun, "iterations": its, "status": 0}
     # per-phase breakdown: one more solve with every phase bracketed by events, OUTSIDE the timed region
     ctx.set_profiling(1)
     ctx.solve_raw(opts, x_dev_ptr=x_dev.data_ptr())
@@ -280,7 +310,7 @@ def measure_single(m, n, steps, warmup, c2, want_cpu_baseline, rank, local_rank,
     else:
         dt_max, iters_total = dt, float(iters_local)
     if rank != 0:
-        return None
+        return None, outputs
     flops_per_launch = float(m) * (m + 1) * n                     # lower triangle of A.D.A^T
     avg_ms = adat_ms / max(adat_launches, 1)
     achieved = flops_per_launch / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
@@ -343,7 +373,7 @@ def measure_single(m, n, steps, warmup, c2, want_cpu_baseline, rank, local_rank,
         out["unbracketed"] = unbracketed
     if want_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(A, b, c, m, n)
-    return out
+    return out, outputs
 
 
 def measure_c4(steps, warmup, rank, local_rank, world, dist, dev, np, torch, lp_amd, synth):
@@ -353,7 +383,8 @@ def measure_c4(steps, warmup, rank, local_rank, world, dist, dev, np, torch, lp_
     committed oracle fixture (tests/golden/c4_members.npz): after the timed region every member of this rank is compared
     with the oracle's OWN ENVELOPE on that LP (component-wise [min, max] of the oracle's x over its run on the LP as
     generated and four runs with permuted columns) widened by 1e-6, and its iteration count with the counts the oracle
-    produced.  Returns (result dict for rank 0, number of members of THIS rank that fail that check)."""
+    produced.  Returns (result dict for rank 0, number of members of ANY rank that fail that check, the outputs of the last
+    timed step)."""
     per_rank, m, n = 32, 1024, 2048
     seeds = [rank * per_rank + s for s in range(per_rank)]
     probs = [synth.planted_lp(s, m, n) for s in seeds]
@@ -387,6 +418,9 @@ def measure_c4(steps, warmup, rank, local_rank, world, dist, dev, np, torch, lp_
     dt = time.perf_counter() - t0
     its = sum(r[2] for r in res)
     x_host = xs.cpu().numpy()
+    outputs = {"x": gathered.cpu().numpy() if dist is not None else x_host,
+               "fun": [np.nan if r[1] is None else r[1] for r in res],
+               "iterations": [r[2] for r in res], "status": [r[0] for r in res]}
     err = max(float(np.abs(x_host[k] - p[3]).max()) for k, p in enumerate(probs))
     # per-phase device times of one more lockstep solve (HIP events on the solver's stream), outside the timed region
     ctx.set_profiling(1)
@@ -451,12 +485,13 @@ def measure_c4(steps, warmup, rank, local_rank, world, dist, dev, np, torch, lp_
                      "adat_achieved": adat_tf, "adat_frac": adat_tf / PEAK_FP64_MFMA_TFLOPS, "adat_launch_ms": phase["adat_ms"]},
         "phase_ms_per_lockstep_iteration": phase,
         "parity_rank0": parity, "parity_failed_members_any_rank": nbad_any}
-    return out, nbad_any
+    return out, nbad_any, outputs
 
 
 def bench_c4(args, rank, local_rank, world, dist, dev, np, torch, lp_amd, synth):
-    out, nbad = measure_c4(args.steps, args.warmup, rank, local_rank, world, dist, dev, np, torch, lp_amd, synth)
+    out, nbad, outputs = measure_c4(args.steps, args.warmup, rank, local_rank, world, dist, dev, np, torch, lp_amd, synth)
     if rank == 0:
+        dump_outputs(args.dump_outputs, outputs, np)
         emit(out)
     if dist is not None:
         dist.barrier()

@@ -16,11 +16,13 @@ def test_every_declared_symbol_is_exported(built):
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)          # declarations only, not prose
     declared = set(re.findall(r"\b(lpipm_[a-z0-9_]+)\s*\(", hdr))
     assert declared, "header parse failed"
+    # _capi.lib() first: it imports torch before the library, so that this process keeps one HIP runtime (torch's);
+    # a bare CDLL here would pull in the system one and break torch's device use in the tests that follow
+    _capi.lib()
     lib = C.CDLL(_capi.LIB_PATH)
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/lpipm.h but not exported"
     assert declared == set(_capi.SYMBOLS), declared ^ set(_capi.SYMBOLS)
-    _capi.lib()
 
 
 def test_struct_layouts_match_header(built):

@@ -155,6 +155,25 @@ def test_bench_distributed_code_path_on_one_rank(built):
         assert r["n_gpus"] == 1 and r["value"] > 0
 
 
+def test_bench_steps_and_dumped_outputs(built, tmp_path):
+    """bench.py --steps is the number of timed steps (c2 has its own default, not an override) and --dump-outputs writes
+    what the last timed step returned: c2's LP is the seed-0 512x1024 one of the committed oracle fixture."""
+    import json
+    import subprocess
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c2", "--steps", "5",
+                          "--warmup", "0", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert r["steps"] == 5 and r["ms_per_step"] > 0
+    got = {k: np.load(tmp_path / f"{k}.npy") for k in ("x", "fun", "iterations", "status")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    g = np.load(os.path.join(ROOT, "tests", "golden", "planted_512x1024_s0.npz"))
+    assert got["status"] == 0 and got["iterations"] == int(g["iterations"])
+    assert got["x"].shape == (1024,) and np.abs(got["x"] - g["x_slack"]).max() <= 1e-6
+    assert abs(float(got["fun"]) - float(g["fun"])) <= 1e-6 * max(1.0, abs(float(g["fun"])))
+
+
 def _worker_two_ways(rank, world, port, q, seed, m, n):
     """The same column-split solve twice: group-by-group reduction of M behind the running A.D.A^T launch (default) and the
     one-block reduction after it (LPIPM_ADAT_UNITS=0: the round-2 path)."""
