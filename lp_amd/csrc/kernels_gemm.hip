@@ -521,7 +521,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 //   consumer : the workgroup whose add completed the tile (told by the value the add returned) -> that lane's
 //              agent-scope acquire + s_waitcnt vmcnt(0) -> workgroup barrier -> EVERY load of the slabs is an sc1 load.
 // The finished tile of M is stored write-through as well when group words are signalled: its readers are other
-// kernels (the factorisation's chain, on another stream) that start while this launch is still running -- their
+// kernels (the column-split reduction of M, on another stream) that start while this launch is still running -- their
 // kernel-start acquire drops stale lines, but nothing would write this XCD's dirty lines back before this launch ends.
 constexpr int AUX_SC1 = 16;
 struct UnitsK {

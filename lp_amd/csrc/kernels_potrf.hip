@@ -621,7 +621,7 @@ long long* g_diag_stamps = nullptr;  // debug: device buffer of 8 cycle stamps f
 // passes over the trailing matrix (at K = 128 that update is bound by the C-tile traffic, 16 flop/B).
 constexpr int OUTER = POTRF_OUTER;
 
-hipError_t potrf_clear_info(int32_t* info, hipStream_t st, const Batch& bt) {
+static hipError_t potrf_clear_info(int32_t* info, hipStream_t st, const Batch& bt) {
     // (a finished LP of a batch has its info word cleared too: its status record already holds the value)
     info = (int32_t*)((char*)info + (size_t)bt.first * (size_t)bt.stride);
     return bt.count == 1 ? hipMemsetAsync(info, 0, sizeof(int32_t), st)
@@ -630,8 +630,8 @@ hipError_t potrf_clear_info(int32_t* info, hipStream_t st, const Batch& bt) {
 
 // The dependent chain of one outer panel [J0, J1) of 128-blocks: diag(j) -> panel solve(j) (all rows below) -> update
 // of the rest of the outer panel's columns (K = 128, few tiles).
-hipError_t potrf_panel_chain(double* M, int64_t ld, int mp, const FactorPlan& plan, int32_t* info, hipStream_t st,
-                             const Batch& bt, int J0, int J1) {
+static hipError_t potrf_panel_chain(double* M, int64_t ld, int mp, const FactorPlan& plan, int32_t* info, hipStream_t st,
+                                    const Batch& bt, int J0, int J1) {
     hipError_t e;
     const int nb = mp / NB;
     for (int j = J0; j < J1; ++j) {
@@ -704,13 +704,10 @@ static hipError_t trailing_update_columns(double* M, int64_t ld, int nb, hipStre
     u.nwg = u.ntiles;
     return launch_gemm_nt(u, st);
 }
-hipError_t potrf_trailing_update(double* M, int64_t ld, int mp, hipStream_t st, const Batch& bt, int J0, int J1) {
-    return trailing_update_columns(M, ld, mp / NB, st, bt, J0, J1, J1, mp / NB);
-}
 
 // inverses of the diagonal super-blocks from the 128-block inverses: doubling levels, each a
 // grouped launch of stage A (T^T = Inv11^T.L21^T) then stage B (Inv21 = -Inv22.T and its transpose)
-hipError_t potrf_superblock_inverses(const FactorPlan& plan, hipStream_t st, const Batch& bt) {
+static hipError_t potrf_superblock_inverses(const FactorPlan& plan, hipStream_t st, const Batch& bt) {
     for (const auto& stg : plan.stages) {
         hipError_t e = launch_gemm_grouped(plan.descs_dev + stg.first, stg.second, st, bt, plan.merge_edge);
         if (e != hipSuccess) return e;

@@ -134,8 +134,8 @@ int gemm_streamk_nwg(int ntiles, int KT, int num_cu);
 // at every chunk boundary, whatever the decomposition (no separate fix-up launch; the bits of M do not depend on the
 // workgroup count, on `upc`, or on who arrives last).  A non-persistent grid, one unit per workgroup, dispatched in list
 // order: with a column-group-major list the groups of M complete one after the other WHILE the launch runs, and the
-// workgroup that completes a group's last tile bumps that group's word -- what the factorisation's chain waits for
-// (solver.hip, enqueue_factor_grouped).
+// workgroup that completes a group's last tile bumps that group's word -- what the column-split reduction of M waits for
+// (solver.hip, enqueue_head).
 struct AdatUnitsArgs {
     const double* A; int64_t lda;     // P = Q = A
     const double* s;                  // dinv (per-k scale)
@@ -218,13 +218,7 @@ struct PotrfLookahead {
 hipError_t launch_potrf(double* M, int64_t ld, int mp, const FactorPlan& plan, int32_t* info, hipStream_t st,
                         const Batch& bt = Batch{}, const PotrfLookahead* la = nullptr, bool clear_info = true);
 
-// The pieces of launch_potrf, for the factorisation that runs beside A.D.A^T (solver.hip, enqueue_factor_overlapped):
-constexpr int POTRF_OUTER = 4;   // 128-blocks per outer panel
-hipError_t potrf_clear_info(int32_t* info, hipStream_t st, const Batch& bt);
-hipError_t potrf_panel_chain(double* M, int64_t ld, int mp, const FactorPlan& plan, int32_t* info, hipStream_t st,
-                             const Batch& bt, int J0, int J1);
-hipError_t potrf_trailing_update(double* M, int64_t ld, int mp, hipStream_t st, const Batch& bt, int J0, int J1);
-hipError_t potrf_superblock_inverses(const FactorPlan& plan, hipStream_t st, const Batch& bt);
+constexpr int POTRF_OUTER = 4;   // 128-blocks per outer panel (also the width of the column groups of A.D.A^T, solver.hip)
 
 // ---------------------------------------------------------------- triangular solves (kernels_trsv.hip)
 // R[r] <- L^-T L^-1 R[r], r < nrhs (1|2); R is nrhs x mp (row stride mp); Yscratch: nrhs x mp.

@@ -79,18 +79,7 @@ struct lpipm_ctx {
                                          // launch leaves them zero itself; launches with group words do not)
     unsigned int* wait_timeout = nullptr;   // arena: set by a wait kernel that gave up (a producer that never ran)
     unsigned int* timeout_host = nullptr;   // pinned mirror, read with the status record
-    // factorisation beside A.D.A^T (enqueue_factor_grouped): CU-masked streams, column groups of the tile list
-    hipStream_t st_a = nullptr, st_b = nullptr, st_u = nullptr;
-    double* ws_upd = nullptr;            // stream-K slabs of the left-looking updates (they run beside A.D.A^T: own buffer)
-    size_t ws_upd_slabs = 0;
-    unsigned int* sk_claim_upd = nullptr;
-    hipEvent_t ev_adat_done = nullptr;
-    int overlap_cus = 0;                 // CUs per XCC reserved for the chain stream (0: no masked streams)
-    bool overlap = false;                // this problem can be factorised beside its A.D.A^T (geometry)
-    bool factor_in_head = false;         // ... and the current solve does so (Cholesky arm, no column split, no graph replay)
-    uint64_t overlap_sections = 0;       // profiling: sections enqueued in this solve
     std::vector<int> grp_off, grp_nt;    // tile sub-list of every column group (outer panel of the factorisation)
-    hipEvent_t ev_fork = nullptr;
     PotrfLookahead la;                   // trailing updates of one factorisation beside the next panel's chain (launch_potrf)
     // a lockstep batch as two half-batches driven by two host threads on two streams (solve_lockstep): views of this
     // context that share its arena (every pointer is LP 0's; a view's launches cover the LPs [bt.first, bt.first + B))
@@ -98,7 +87,6 @@ struct lpipm_ctx {
     int halves_env = 1;                  // LPIPM_HALVES=0: one stream for the whole batch
     bool pred_done = false;              // the last residual launch also ran the next iteration's k_pred_setup
     std::vector<lpipm_ctx*> halves;
-    std::vector<hipEvent_t> ev_ready, ev_chain, ev_adat;
     int refine = 0;              // set from the environment by lpipm_create.  0 (default): plain solves; LPIPM_REFINE=2: every
                                  //   solve of every iteration refined; =1: only from mu / mu_0 <= refine_below() on.
                                  //   Built because ~1 % of the C4 members took a poor last step (alpha 0.987 for 0.99995) and
@@ -109,7 +97,7 @@ struct lpipm_ctx {
     bool refine_now = false;     // the iteration being enqueued refines its solves (host mirror of the LPs' skip_refine words)
     int2* tile_list = nullptr;
     int2* tile_list_grp = nullptr;      // the same tiles grouped by column group (behind tile_list in one allocation)
-    size_t ws_slabs = 0;                // stream-K slabs (TILE x TILE doubles each) the A.D.A^T / update launches may need
+    size_t ws_slabs = 0;                // stream-K slabs (TILE x TILE doubles each) the A.D.A^T launches may need
     unsigned int* sk_claim = nullptr;   // claim word of the dynamic stream-K chunks of A.D.A^T
     int ntiles = 0, adat_nwg = 1;
     VecArgs va{};
@@ -137,11 +125,6 @@ struct lpipm_ctx {
     std::vector<lpipm_ctx*> workers;
     int batch_concurrency = 0;   // 0 = auto
     int lockstep_max = -1;       // lpipm_solve_batch: -1 auto, 0 never group same-shape members, > 0 largest group
-    // captured iteration (hipGraph): one executable graph per (ip, options) key, valid while the buffers live
-    struct IterGraph { int ip; int refine; double alpha0, tol; hipGraphExec_t exec; };
-    std::vector<IterGraph> graphs;
-    int use_graph = -1;          // -1: decide from the environment at first use
-    bool no_speculate = false;
     // n-split mode (one LP split by columns over ranks; BASELINE config C5): the collective is the caller's
     bool colsplit = false;
     int rank = 0, world = 1;
@@ -157,14 +140,6 @@ struct lpipm_ctx {
 
 static void destroy_views(lpipm_ctx* c);      // half-batch views of a lockstep batch (solve_lockstep)
 namespace lpipm { lpipm_ctx_device lpipm_ctx_device_of(lpipm_ctx* c) { return lpipm_ctx_device{c->device, c->st}; } }
-
-// The factorisation beside A.D.A^T (enqueue_factor_grouped) unless LPIPM_OVERLAP says otherwise: see lpipm_create.
-constexpr bool OVERLAP_DEFAULT = false;
-
-static void drop_graphs(lpipm_ctx* c) {
-    for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
-    c->graphs.clear();
-}
 
 // Cross-rank reduction of `count` doubles at a device pointer, ordered after everything enqueued on the ctx's stream
 // so far.  Default contract: the stream is drained first and the callee returns when the result is in place.
@@ -230,14 +205,6 @@ static void prof_collect(lpipm_ctx* c, size_t upto = (size_t)-1) {
         c->mark_tags[i - upto] = c->mark_tags[i];
     }
     c->nmarks -= upto;
-}
-
-// A.D.A^T time of one completed side-by-side section (its events have completed): the one launch on the throughput stream
-static void prof_collect_overlap(lpipm_ctx* c, uint64_t section) {
-    if (!c->profiling || !c->factor_in_head) return;
-    hipEvent_t* ev = c->ev_adat.data() + (section & 1) * 2;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) c->tag_ms[T_ADAT] += ms;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -322,7 +289,7 @@ extern "C" int lpipm_create(int device, lpipm_ctx** out) {
     // exist only for a refining context: 134 MB at C3, 2 GB at m = 16384, per member of a lockstep batch)
     { const char* e = lp_knob("LPIPM_REFINE"); c->refine = !e ? 0 : (e[0] == '2' ? 2 : (e[0] == '1' ? 1 : 0)); }
     // LPIPM_ADAT_UNITS: 0 = the round-2 kernel everywhere, 2 = the units kernel for single LPs too (measurement / test knob);
-    // default 1 = units kernel for lockstep batches and for the side-by-side factorisation, round-2 kernel for a single LP
+    // default 1 = units kernel for lockstep batches and for the column-split reduction, round-2 kernel for a single LP
     // (measured per launch, units vs round-2: 512x1024 0.042 / 0.045 ms, 1024x2048 0.102 / 0.097, 2048x4096 0.469 / 0.458,
     // 4096x8192 2.47 / 2.39 standalone and 2.32 / 2.25 inside a solve; C4 lockstep shard 1732 vs 1674 LP/s)
     { const char* e = lp_knob("LPIPM_ADAT_UNITS"); c->units_env = !e ? 1 : (e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1)); }
@@ -334,35 +301,6 @@ extern "C" int lpipm_create(int device, lpipm_ctx** out) {
     }
     *c->timeout_host = 0;
     std::memset(c->status_host, 0, sizeof(StatusRec));
-    // CU-masked streams for the factorisation that runs beside A.D.A^T (enqueue_factor_grouped).  Mask bit i is CU i/8 of
-    // XCC i%8 (scripts/diag/cu_mask_probe.cpp; an XCC with no bit set would be unrestricted): the chain stream (st_b) gets
-    // CUs 0..R-1 of every XCC -- a diagonal-block kernel needs a whole CU's LDS, and on a chip full of A.D.A^T workgroups it
-    // would wait for one --, the throughput streams (st_a: the one A.D.A^T launch; st_u: the left-looking updates that run
-    // beside it) the rest.  LPIPM_OVERLAP=0 switches the scheme off, LPIPM_OVERLAP_CUS=R sets R (default 4).  Only on the
-    // 8 x 32 CU layout it was measured on.
-    {
-        const char* on = lp_knob("LPIPM_OVERLAP");
-        int R = 4;
-        if (const char* e = lp_knob("LPIPM_OVERLAP_CUS")) { const int v = atoi(e); if (v >= 1 && v <= 16) R = v; }
-        if (OVERLAP_DEFAULT ? !(on && on[0] == '0') : (on && on[0] == '1')) if (c->num_cu == 256 && c->units_env) {
-            uint32_t ma[8], mb[8];
-            for (int w = 0; w < 8; ++w) { ma[w] = 0; mb[w] = 0; }
-            for (int i = 0; i < 256; ++i) ((i / 8) < R ? mb : ma)[i / 32] |= 1u << (i % 32);
-            if (hipExtStreamCreateWithCUMask(&c->st_a, 8, ma) == hipSuccess &&
-                hipExtStreamCreateWithCUMask(&c->st_u, 8, ma) == hipSuccess &&
-                hipExtStreamCreateWithCUMask(&c->st_b, 8, mb) == hipSuccess &&
-                hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&c->ev_adat_done, hipEventDisableTiming) == hipSuccess) {
-                c->overlap_cus = R;
-            } else {
-                (void)hipGetLastError();
-                if (c->st_a) (void)hipStreamDestroy(c->st_a);
-                if (c->st_u) (void)hipStreamDestroy(c->st_u);
-                if (c->st_b) (void)hipStreamDestroy(c->st_b);
-                c->st_a = c->st_b = c->st_u = nullptr;
-            }
-        }
-    }
     // Side stream for the look-ahead of the factorisation's trailing updates (launch_potrf; used from m = 4096, see there for
     // the measurements; LPIPM_LOOKAHEAD=0 switches it off, =1 lowers the threshold to m = 1536).  CU-masked (bit i = CU i/8 of XCC i%8): the first R CUs of every XCC stay free for the chain
     // stream's kernels -- the diagonal-block kernel needs a CU to itself (150 KB of LDS) and would otherwise wait for a
@@ -405,7 +343,6 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     destroy_views(c);
     (void)hipSetDevice(c->device);
     if (c->st) (void)hipStreamSynchronize(c->st);
-    drop_graphs(c);
     if (c->arena) (void)hipFree(c->arena);
     if (c->tile_list) (void)hipFree(c->tile_list);
     free_list(c->kallocs);
@@ -419,17 +356,9 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
     if (c->ev_end) (void)hipEventDestroy(c->ev_end);
     if (c->ev_status) (void)hipEventDestroy(c->ev_status);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    for (hipEvent_t e : c->ev_ready) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_chain) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_adat) (void)hipEventDestroy(e);
     if (c->la.side) { (void)hipStreamSynchronize(c->la.side); (void)hipStreamDestroy(c->la.side); }
     for (hipEvent_t e : c->la.ev_chain) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->la.ev_rest) (void)hipEventDestroy(e);
-    if (c->st_a) { (void)hipStreamSynchronize(c->st_a); (void)hipStreamDestroy(c->st_a); }
-    if (c->st_u) { (void)hipStreamSynchronize(c->st_u); (void)hipStreamDestroy(c->st_u); }
-    if (c->st_b) { (void)hipStreamSynchronize(c->st_b); (void)hipStreamDestroy(c->st_b); }
-    if (c->ev_adat_done) (void)hipEventDestroy(c->ev_adat_done);
     if (c->timeout_host) (void)hipHostFree(c->timeout_host);
     if (c->status_host) (void)hipHostFree(c->status_host);
     if (c->x_pinned) (void)hipHostFree(c->x_pinned);
@@ -441,9 +370,8 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
 // renumbered so that 64 consecutive tiles run on one XCD (one L2): full off-diagonal 8x8 super-blocks
 // come first, each exactly one such chunk (16 row panels of A feed 64 tiles); the triangular
 // diagonal super-blocks (36 tiles each) follow and are the ones that straddle chunk boundaries.
-// The same tiles ordered for the factorisation that runs beside A.D.A^T: column group g (tile columns 4g .. 4g+3, one
-// outer panel of the factorisation) is one contiguous sub-list; inside it row by row, so that consecutive stream-K
-// claims of one k-range share a row panel of A.
+// The same tiles ordered for the column-split reduction of M (enqueue_head): column group g (tile columns 4g .. 4g+3, one
+// outer panel of the factorisation) is one contiguous sub-list; inside it row by row.
 static std::vector<int2> adat_tile_order_grouped(int nt, std::vector<int>& off, std::vector<int>& cnt) {
     std::vector<int2> v;
     off.clear(); cnt.clear();
@@ -532,7 +460,7 @@ static void plan_adat(lpipm_ctx* c, int count) {
     // 0.55 GB at C3, 38 MB per member at C4) -- up to 4 GiB per LP, beyond that (m = 16384: 34 GB) the round-2 kernel
     c->cpt = adat_units_cpt(c->npa);
     c->units = c->units_env != 0 && (size_t)c->ntiles * c->cpt * TILE * TILE * sizeof(double) <= ((size_t)4 << 30) &&
-               (count > 1 || c->units_env == 2 || c->st_a != nullptr || c->cpt == 1 || c->ntiles <= 16 || c->ntiles * c->cpt >= 256);
+               (count > 1 || c->units_env == 2 || c->cpt == 1 || c->ntiles <= 16 || c->ntiles * c->cpt >= 256);
     // (tiny single LPs -- up to 16 tiles -- : one launch and one memset less, 0.042 vs 0.045 ms at 512x1024;
     //  a single LP with few tiles AND several chunks -- 1000x5000: 36 tiles x 3 -- keeps the round-2 kernel: one workgroup per
     //  tile adding the slabs at the end of a launch that never filled the chip costs more than the 16-way fix-up launch,
@@ -590,17 +518,14 @@ static int layout_problem(lpipm_ctx* c, Arena& ar, bool build) {
     c->gs = ar.take<double>(8);
     c->xout = ar.take<double>(np);
     c->sk_claim = ar.take<unsigned int>(1);
-    c->sk_claim_upd = ar.take<unsigned int>(1);
     // arrival counters of the units kernel: one word per tile, then one per column group; cleared by ONE memset per launch
     // (a block of its own, a multiple of 16 bytes)
     c->cnt_bytes = (size_t)round_up(((size_t)c->ntiles + 64) * sizeof(unsigned int), 16);
     c->tile_cnt = (unsigned int*)ar.take<uint4>(c->cnt_bytes / 16);
     c->grp_cnt = c->tile_cnt + c->ntiles;
     c->wait_timeout = ar.take<unsigned int>(4);
-    // chunk slabs of A.D.A^T (units kernel: every chunk of every tile; round-2 kernel: the stream-K remainder tiles), and
-    // those of the left-looking updates that run beside it
+    // chunk slabs of A.D.A^T (units kernel: every chunk of every tile; round-2 kernel: the stream-K remainder tiles)
     c->ws = ar.take<double>(c->ws_slabs * TILE * TILE);
-    c->ws_upd = ar.take<double>(c->ws_upd_slabs * TILE * TILE);
     return LPIPM_OK;
 }
 
@@ -628,7 +553,6 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
             if (row[j] != ((i == j) ? 1.0 : 0.0)) { n_slack = 0; break; }
     }
     LP_HIP(hipSetDevice(c->device));
-    drop_graphs(c);   // kernel arguments depend on m, n, n_slack and the buffers
     destroy_views(c); // half-batch views copy the geometry and the buffers
     const uint64_t nx = n - n_slack;
     const int mp = (int)round_up(m, NB), np = (int)round_up(n, BK), npa = (int)round_up(nx, BK);
@@ -659,40 +583,14 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
             }
         }
         c->nunits = (int)units.size();
-        // Factorisation beside A.D.A^T: single LP, big enough that A.D.A^T can hide the factorisation's chain
-        c->overlap = count == 1 && c->st_a != nullptr && mp >= 2048 && c->units && c->cpt > 1 && nt <= 64 * POTRF_OUTER;
         const bool grouped_reduce = count == 1 && c->world > 1 && c->units && nt <= 64 * POTRF_OUTER;
         std::vector<int2> grouped;
-        c->ws_upd_slabs = 0;
-        if (grouped_reduce && !c->overlap) {       // column-group-major unit list for the pipelined reduction of M (enqueue_head)
+        if (grouped_reduce) {       // column-group-major unit list for the pipelined reduction of M (enqueue_head)
             grouped = adat_tile_order_grouped(nt, c->grp_off, c->grp_nt);
             for (size_t g = 0; g < c->grp_nt.size(); ++g) {
                 std::vector<int> grp((size_t)c->grp_nt[g]);
                 for (int t = 0; t < c->grp_nt[g]; ++t) grp[(size_t)t] = c->grp_off[g] + t;
                 deal_units(grp, c->cpt, 1, units_grp);
-            }
-        }
-        if (c->overlap) {
-            grouped = adat_tile_order_grouped(nt, c->grp_off, c->grp_nt);
-            const int wg_cus = c->num_cu - 8 * c->overlap_cus;
-            for (size_t g = 0; g < c->grp_nt.size(); ++g) {
-                std::vector<int> grp((size_t)c->grp_nt[g]);        // group-major; inside a group dealt to the XCDs, chunk-major
-                for (int t = 0; t < c->grp_nt[g]; ++t) grp[(size_t)t] = c->grp_off[g] + t;
-                deal_units(grp, c->cpt, 1, units_grp);
-                const int ku = (int)g * POTRF_OUTER * NB / BK;      // contraction of the left-looking update of group g
-                const size_t s2 = ku ? gemm_streamk_slabs(c->grp_nt[g], ku, gemm_streamk_nwg(c->grp_nt[g], ku, wg_cus)) : 0;
-                if (s2 > c->ws_upd_slabs) c->ws_upd_slabs = s2;
-            }
-            while (c->ev_ready.size() < c->grp_nt.size()) {
-                hipEvent_t e1, e2;
-                LP_HIP(hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-                LP_HIP(hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-                c->ev_ready.push_back(e1); c->ev_chain.push_back(e2);
-            }
-            while (c->ev_adat.size() < 4) {     // {begin, end} x 2: the head of iteration k+1 is enqueued before iteration k's times are read
-                hipEvent_t e3;
-                LP_HIP(hipEventCreate(&e3));
-                c->ev_adat.push_back(e3);
             }
         }
         c->nunits_grp = (int)units_grp.size();
@@ -861,77 +759,6 @@ static hipError_t run_adat(lpipm_ctx* c, const Batch& bt) {
     return hipGetLastError();
 }
 
-// The normal equations AND their Cholesky factor, the factorisation running beside A.D.A^T (single LP, m >= 2048).
-// Why: the factorisation is a chain of 32 (m = 4096) dependent steps -- one 128 x 128 diagonal block on ONE CU, its panel
-// solve, the update of the next block -- with 1-30 of 256 CUs busy for 1.4 of its 1.9 ms.  It is given other work to hide
-// behind, the 2.3 ms of A.D.A^T:
-//   * A.D.A^T is ONE launch of (tile, chunk) units in COLUMN-GROUP-MAJOR order (group g = tile columns 4g .. 4g+3 = one
-//     outer panel of the factorisation) on the throughput stream st_a (CU mask: all but R CUs per XCC).  The workgroup that
-//     completes a tile stores it write-through and bumps its group's word; group g is complete when that word reaches the
-//     group's tile count -- long before the launch ends (round 2 cut A.D.A^T into eight stream-K launches with eight tails
-//     and eight fix-ups: 2.84 + 0.25 ms against 2.35, and lost);
-//   * the factorisation is left-looking at the outer-panel level: before panel g is factorised, its column group gets the
-//     updates of all panels before it in ONE product (K = 512 g, stream-K, alpha = -1, beta = 1) on st_u -- a second stream
-//     with the throughput mask, so the update's workgroups take slots between A.D.A^T's units, which are still being
-//     dispatched -- behind a one-wave kernel that waits for the group's word (launch_wait_count);
-//   * inside a panel the chain is what it was (potrf_panel_chain), on the chain stream st_b (CU mask: the R reserved CUs
-//     per XCC: a diagonal-block kernel needs a whole CU's LDS);
-//   * events: panel g-1 done (st_b -> st_u), group g updated (st_u -> st_b).
-// The results are those of the same factorisation run alone (fixed summation orders everywhere).
-static int enqueue_factor_grouped(lpipm_ctx* c, const Batch& bt) {
-    hipStream_t sm = c->st, sa = c->st_a, su = c->st_u, sb = c->st_b;
-    const int ng = (int)c->grp_nt.size();
-    const int wg_cus = c->num_cu - 8 * c->overlap_cus;
-    // the words the other streams poll are cleared BEFORE they are released (a wait kernel that ran ahead of the memset
-    // would see the previous iteration's full counts)
-    LP_HIP(clear_unit_counters(c, bt, sm));
-    c->cnt_dirty = true;
-    LP_HIP(hipEventRecord(c->ev_fork, sm));
-    LP_HIP(hipStreamWaitEvent(sa, c->ev_fork, 0));
-    LP_HIP(hipStreamWaitEvent(su, c->ev_fork, 0));
-    LP_HIP(hipStreamWaitEvent(sb, c->ev_fork, 0));
-    LP_HIP(potrf_clear_info(c->va.potrf_info, sb, bt));
-    const bool timed = c->profiling != 0;
-    hipEvent_t* ev = c->ev_adat.data() + (c->overlap_sections & 1) * 2;   // {begin, end} of this section's launch
-    {   // throughput stream: the whole of A.D.A^T, group by group
-        AdatUnitsArgs a = adat_units_args(c, bt);
-        a.tile_list = c->tile_list_grp; a.unit_list = c->unit_list_grp; a.nunits = c->nunits_grp;
-        a.grp_cnt = c->grp_cnt;
-        if (timed) LP_HIP(hipEventRecord(ev[0], sa));
-        LP_HIP(launch_adat_units(a, sa));
-        if (timed) LP_HIP(hipEventRecord(ev[1], sa));
-        LP_HIP(hipEventRecord(c->ev_adat_done, sa));
-    }
-    for (int g = 0; g < ng; ++g) {
-        const int J0 = g * POTRF_OUTER, J1 = J0 + POTRF_OUTER < c->mp / NB ? J0 + POTRF_OUTER : c->mp / NB;
-        hipStream_t sg = g == 0 ? sb : su;           // group 0 needs no update: the chain stream waits for it itself
-        if (g > 0) LP_HIP(hipStreamWaitEvent(su, c->ev_chain[g - 1], 0));
-        LP_HIP(launch_wait_count(c->grp_cnt + g, (unsigned)c->grp_nt[g], bt.done, c->wait_timeout, sg));
-        if (c->ns > J0 * NB) {                       // + diag(D_slack) on the group's diagonal blocks (before the update, as alone)
-            const int r0 = J0 * NB, cnt = (c->ns < J1 * NB ? c->ns : J1 * NB) - r0;
-            LP_HIP(launch_slack_diag(cnt, c->nx, c->va.dinv + r0, c->M + (size_t)r0 * (c->mp + 1), c->mp, sg, bt));
-            if (c->refine > 0) LP_HIP(launch_slack_diag(cnt, c->nx, c->va.dinv + r0, c->M0 + (size_t)r0 * (c->mp + 1), c->mp, sg, bt));
-        }
-        if (g > 0) {   // ... minus what the panels before it contribute: C -= L[rows, 0:K) . L[cols, 0:K)^T
-            GemmArgs u{};
-            u.P = c->M; u.ldp = c->mp; u.Q = c->M; u.ldq = c->mp; u.s = nullptr;
-            u.C = c->M; u.ldc = c->mp; u.K = J0 * NB; u.alpha = -1.0; u.beta = 1.0;
-            u.ntiles = c->grp_nt[g]; u.tiles_lower = 1; u.tile_list = c->tile_list_grp + c->grp_off[g];
-            u.diag_pad_from = -1; u.ws = c->ws_upd; u.batch = bt; u.sk_claim = c->sk_claim_upd; u.streamk = 1;
-            u.nwg = gemm_streamk_nwg(u.ntiles, u.K / BK, wg_cus);
-            LP_HIP(launch_gemm_nt(u, su));
-            LP_HIP(hipEventRecord(c->ev_ready[g], su));
-            LP_HIP(hipStreamWaitEvent(sb, c->ev_ready[g], 0));
-        }
-        LP_HIP(potrf_panel_chain(c->M, c->mp, c->mp, c->plan, c->va.potrf_info, sb, bt, J0, J1));
-        LP_HIP(hipEventRecord(c->ev_chain[g], sb));
-    }
-    LP_HIP(hipStreamWaitEvent(sm, c->ev_chain[ng - 1], 0));
-    LP_HIP(hipStreamWaitEvent(sm, c->ev_adat_done, 0));        // (complete by then: every group word was waited for)
-    LP_HIP(potrf_superblock_inverses(c->plan, sm, bt));
-    return LPIPM_OK;
-}
-
 // v = M^-1 r through the Cholesky factor (newton_equations.rs:151-169); optionally (LPIPM_REFINE, see lpipm_ctx::refine)
 // with one step of iterative refinement against the matrix itself:  v0 = L^-T L^-1 r;  rho = r - M.v0 (doubled
 // precision, one read of the lower triangle);  v = v0 + L^-T L^-1 rho.  R: nrhs x mp, in/out.
@@ -966,10 +793,9 @@ static int enqueue_residuals(lpipm_ctx* c, int is_init, int ip_next, double tol)
         LP_HIP(ctx_gemv_t(c, 1, v.y, c->bt));
     }
     prof_mark(c, T_GEMV);
-    // small LPs: the launch goes on with the next iteration's Dinv / r_hat set-up (enqueue_head then skips it); not under graph
-    // replay, where the head must be the same launches every time
+    // small LPs: the launch goes on with the next iteration's Dinv / r_hat set-up (enqueue_head then skips it)
     v.status_seq = (int)(++c->seq_counter & 0x7fffffffu);
-    const bool with_pred = !c->colsplit && vec_fused(v) && c->use_graph != 1;
+    const bool with_pred = !c->colsplit && vec_fused(v);
     LP_TRY(vec_residuals(v, is_init, ip_next, tol, c->st, c->colsplit ? &xr : nullptr, with_pred));
     c->pred_done = with_pred;
     LP_HIP(hipGetLastError());
@@ -1017,7 +843,7 @@ static int copy_status(lpipm_ctx* c) {
     else if (c->B == 1) LP_HIP(hipMemcpyAsync(c->status_host, (const char*)c->va.status + (size_t)c->bt.first * c->bstride, sizeof(StatusRec), hipMemcpyDeviceToHost, c->st));
     else LP_HIP(hipMemcpy2DAsync(c->status_host, sizeof(StatusRec), (const char*)c->va.status + (size_t)c->bt.first * c->bstride, c->bstride,
                                  sizeof(StatusRec), (size_t)c->B, hipMemcpyDeviceToHost, c->st));
-    if (c->factor_in_head || (c->colsplit && c->grouped_reduce))   // a wait kernel that gave up (its producer never ran) says so here
+    if (c->colsplit && c->grouped_reduce)   // a wait kernel that gave up (its producer never ran) says so here
         LP_HIP(hipMemcpyAsync(c->timeout_host, c->wait_timeout, sizeof(unsigned int), hipMemcpyDeviceToHost, c->st));
     return LPIPM_OK;
 }
@@ -1036,13 +862,6 @@ static int enqueue_head(lpipm_ctx* c) {
     prof_mark(c, T_VEC);
     if (c->pred_done) c->pred_done = false;       // the residual launch in front of this head has done it (enqueue_residuals)
     else vec_pred_setup(vh, st);
-    if (c->factor_in_head) {   // A.D.A^T and the Cholesky factorisation side by side (newton_equations.rs:55-57, :129-131)
-        prof_mark(c, T_VEC);
-        LP_TRY(enqueue_factor_grouped(c, c->bt_head));
-        prof_mark(c, T_POTRF);
-        c->overlap_sections++;
-        return LPIPM_OK;
-    }
     prof_mark(c, T_VEC, true);
     if (c->colsplit && c->world > 1 && c->grouped_reduce && c->st_c) {
         // n-split, M = sum_g A_g D_g A_g^T, PIPELINED: one A.D.A^T launch in column-group-major order on the solver's stream;
@@ -1085,8 +904,8 @@ static int enqueue_head(lpipm_ctx* c) {
     return LPIPM_OK;
 }
 
-// The look-ahead of launch_potrf needs a second stream: not while a graph is being captured on the solver's stream.
-static const PotrfLookahead* lookahead(lpipm_ctx* c) { return (c->la.side && c->use_graph != 1) ? &c->la : nullptr; }
+// The look-ahead of launch_potrf, if the side stream it needs was created (lpipm_create).
+static const PotrfLookahead* lookahead(lpipm_ctx* c) { return c->la.side ? &c->la : nullptr; }
 
 // The rest of the iteration, ending with the status record on its way to the host and ev_status behind it.
 static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
@@ -1096,10 +915,9 @@ static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
     const XRank* xr = c->colsplit ? &xr_ : nullptr;
     const Batch& bt = c->bt;
     const bool chol = o->solver_type == LPIPM_SOLVER_CHOLESKY;
-    if (c->factor_in_head) {}                                                             // factorised beside A.D.A^T
     // (no clearing of the pivot-failure word: k_blind_start and every k_scalar_indicators leave it zero)
-    else if (chol) LP_HIP(launch_potrf(c->M, c->mp, c->mp, c->plan, v.potrf_info, st, bt, lookahead(c), false));   // :129-131
-    else           LP_HIP(launch_qr_factor(c->M, c->mp, c->mp, c->tau, v.potrf_info, st));   // :133-149
+    if (chol) LP_HIP(launch_potrf(c->M, c->mp, c->mp, c->plan, v.potrf_info, st, bt, lookahead(c), false));   // :129-131
+    else      LP_HIP(launch_qr_factor(c->M, c->mp, c->mp, c->tau, v.potrf_info, st));        // :133-149
     prof_mark(c, T_POTRF);
     // predictor: both sym_solve calls of solve_newton_equations (:187-188) in one pass each
     if (!c->colsplit) {
@@ -1155,32 +973,6 @@ static int enqueue_iteration(lpipm_ctx* c, int ip, const lpipm_opts* o) {
     return enqueue_tail(c, ip, o);
 }
 
-// The ~100 launches of one iteration replayed as one hipGraph launch: the sequence and every argument
-// are the same from iteration to iteration (only `ip` differs, on the first one).  Capturing does not
-// execute anything, so the first use of a key costs one capture + instantiate and then runs the graph.
-static int run_iteration(lpipm_ctx* c, int ip, const lpipm_opts* o) {
-    const bool graphable = c->use_graph == 1 && !c->profiling && !c->colsplit && o->solver_type == LPIPM_SOLVER_CHOLESKY;
-    if (!graphable) return enqueue_iteration(c, ip, o);
-    for (auto& g : c->graphs)
-        if (g.ip == ip && g.refine == (int)c->refine_now && g.alpha0 == o->alpha0 && g.tol == o->tol) {
-            LP_HIP(hipGraphLaunch(g.exec, c->st));
-            return LPIPM_OK;
-        }
-    LP_HIP(hipStreamBeginCapture(c->st, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_iteration(c, ip, o);
-    hipGraph_t graph = nullptr;
-    const hipError_t e = hipStreamEndCapture(c->st, &graph);
-    if (rc != LPIPM_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    LP_HIP(e);
-    hipGraphExec_t exec = nullptr;
-    const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    LP_HIP(ei);
-    c->graphs.push_back({ip, (int)c->refine_now, o->alpha0, o->tol, exec});
-    LP_HIP(hipGraphLaunch(exec, c->st));
-    return LPIPM_OK;
-}
-
 static void print_row(double alpha, const StatusRec& s) {  // mod.rs:228 + indicators.rs:25-33
     printf("%.8f\t%.8f\t%.8f\t%.8f\t%.8f\t%8.3f\n", alpha, s.rho_p, s.rho_d, s.rho_g, s.rho_mu, s.obj);
 }
@@ -1198,14 +990,6 @@ static int solve_impl(lpipm_ctx* c, const lpipm_opts* o, double* x_host, void* x
     LP_HIP(hipSetDevice(c->device));
     VecArgs& v = c->va;
     hipStream_t st = c->st;
-    if (c->use_graph < 0) {   // measurement knobs: LPIPM_GRAPH=1 (hipGraph replay), LPIPM_SPECULATE=0 (no early head)
-        const char* g = lp_knob("LPIPM_GRAPH");
-        c->use_graph = (g && g[0] == '1') ? 1 : 0;
-        const char* sp = lp_knob("LPIPM_SPECULATE");
-        c->no_speculate = sp && sp[0] == '0';
-    }
-    c->factor_in_head = c->overlap && !c->colsplit && c->use_graph != 1 && o->solver_type == LPIPM_SOLVER_CHOLESKY;
-    c->overlap_sections = 0;
     for (int t = 0; t < T_NTAGS; ++t) c->tag_ms[t] = 0.0;
     c->times = lpipm_phase_times{};
     c->nmarks = 0;
@@ -1234,18 +1018,17 @@ static int solve_impl(lpipm_ctx* c, const lpipm_opts* o, double* x_host, void* x
     int ret = LPIPM_ITERATION_LIMIT;
     uint64_t iteration = 0;
     // the head of iteration k+1 goes out before the status of iteration k is read (see enqueue_head); not when the
-    // iteration is replayed as a graph or contains host-side collectives
-    const bool speculate = c->use_graph != 1 && !c->colsplit && !c->no_speculate;
+    // iteration contains host-side collectives
+    const bool speculate = !c->colsplit;
     // (with every phase bracketed -- profiling 1 -- the last mark of an iteration is recorded BEHIND the indicators kernel and
     //  has to have completed when it is read: the event wait stays; profiling 2's two marks sit in front of it)
     c->spin_status = speculate && c->va.status_pinned != nullptr && c->profiling != 1;
     bool head_out = false;
     for (iteration = 1; iteration <= o->max_iter; ++iteration) {   // mod.rs:213
         if (!speculate) {
-            LP_TRY(run_iteration(c, ip, o));
+            LP_TRY(enqueue_iteration(c, ip, o));
             LP_HIP(hipStreamSynchronize(st));
             prof_collect(c);
-            prof_collect_overlap(c, c->overlap_sections - 1);
         } else {
             if (!head_out) LP_TRY(enqueue_head(c));
             LP_TRY(enqueue_tail(c, ip, o));
@@ -1254,10 +1037,9 @@ static int solve_impl(lpipm_ctx* c, const lpipm_opts* o, double* x_host, void* x
             if (head_out) LP_TRY(enqueue_head(c));
             LP_TRY(wait_status(c, nullptr, 1));
             prof_collect(c, marks);
-            prof_collect_overlap(c, c->overlap_sections - (head_out ? 2 : 1));
         }
         ++adat_launches;
-        if ((c->factor_in_head || (c->colsplit && c->grouped_reduce)) && *c->timeout_host != 0) {
+        if (c->colsplit && c->grouped_reduce && *c->timeout_host != 0) {
             g_err_detail = "a column group of A.D.A^T did not complete within the wait kernel's bound";
             LP_HIP(hipStreamSynchronize(st));
             return LPIPM_ERR_HIP;
@@ -1308,10 +1090,6 @@ static int solve_impl(lpipm_ctx* c, const lpipm_opts* o, double* x_host, void* x
         (void)hipEventElapsedTime(&ms, c->ev_begin, c->ev_end);
         c->times.total_ms = ms;
         c->times.adat_ms = c->tag_ms[T_ADAT]; c->times.potrf_ms = c->tag_ms[T_POTRF];
-        if (c->factor_in_head && c->profiling == 1) {   // T_POTRF spans the whole side-by-side section: what A.D.A^T does not hide
-            c->times.potrf_ms = c->tag_ms[T_POTRF] - c->tag_ms[T_ADAT];
-            if (c->times.potrf_ms < 0.0) c->times.potrf_ms = 0.0;
-        }
         c->times.trsv_ms = c->tag_ms[T_TRSV]; c->times.gemv_ms = c->tag_ms[T_GEMV];
         c->times.vec_ms = c->tag_ms[T_VEC];
         c->times.adat_launches = adat_launches; c->times.iterations = iteration;
@@ -1354,10 +1132,10 @@ static lpipm_ctx* make_view(const lpipm_ctx* c, int first, int count) {
     lpipm_ctx* v = new lpipm_ctx(*c);
     v->is_view = true;
     v->cnt_dirty = true;
-    v->halves.clear(); v->workers.clear(); v->graphs.clear(); v->kallocs.clear();
+    v->halves.clear(); v->workers.clear(); v->kallocs.clear();
     v->events.clear(); v->mark_tags.clear(); v->nmarks = 0;
-    v->ev_ready.clear(); v->ev_chain.clear(); v->ev_adat.clear(); v->la = PotrfLookahead{};
-    v->st = nullptr; v->st_a = v->st_b = v->st_u = nullptr; v->ev_fork = v->ev_adat_done = nullptr; v->overlap = false;
+    v->la = PotrfLookahead{};
+    v->st = nullptr;
     v->ev_begin = v->ev_end = v->ev_status = nullptr; v->status_host = nullptr; v->timeout_host = nullptr;
     v->x_pinned = nullptr; v->x_pinned_cap = 0;
     v->mpack = nullptr; v->kM = v->kM0 = v->kR = v->kY = nullptr; v->kmp = 0; v->kplan = FactorPlan{};
@@ -1450,7 +1228,6 @@ static int solve_lockstep_one(lpipm_ctx* c, const lpipm_opts* o, const XOut& xo,
     const int B = c->B;
     VecArgs& v = c->va;
     hipStream_t st = c->st;
-    c->factor_in_head = false;
     // profiling (lpipm_set_profiling): the same event marks as a single solve; a phase's time is that of the whole batch's launch
     for (int t = 0; t < T_NTAGS; ++t) c->tag_ms[t] = 0.0;
     c->times = lpipm_phase_times{};
@@ -2037,7 +1814,6 @@ extern "C" int lpipm_k_iteration(lpipm_ctx* c, const lpipm_opts* o, int ip, doub
     VecArgs& v = c->va;
     hipStream_t st = c->st;
     c->refine_now = c->refine == 2;
-    c->factor_in_head = false;
     vec_blind_start(v, st);                                   // clears done / flags; the iterate is overwritten next
     LP_HIP(hipMemcpyAsync(v.x, x, c->n * sizeof(double), hipMemcpyHostToDevice, st));
     LP_HIP(hipMemcpyAsync(v.y, y, c->m * sizeof(double), hipMemcpyHostToDevice, st));

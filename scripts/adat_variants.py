@@ -1,6 +1,6 @@
-"""A.D.A^T kernel variants and the side-by-side factorisation, on the GPU box:
+"""A.D.A^T kernel variants, on the GPU box:
    python scripts/adat_variants.py            -> per-launch ms of k_adat (units kernel vs round-2 kernel, bit comparison),
-                                                 solve it/s at C3 with LPIPM_OVERLAP on/off, C4 lockstep LP/s both kernels."""
+                                                 solve it/s at C3 with both kernels, C4 lockstep LP/s both kernels."""
 import os, sys, time
 os.environ["LPIPM_EXPERIMENTAL"] = "1"      # the library reads its measurement knobs only with the master switch on
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,7 +21,7 @@ def adat(m, n, reps=10):
     d = np.random.default_rng(1).uniform(0.1, 3.0, n)
     out = {}
     for name, env in (("units", {"LPIPM_ADAT_UNITS": 2}), ("round2", {"LPIPM_ADAT_UNITS": 0})):
-        cx = ctx_with(LPIPM_OVERLAP=0, **env)
+        cx = ctx_with(**env)
         cx.upload_arrays(A, b, c)
         cx.k_adat(d, 2)
         M, ms = cx.k_adat(d, reps)
@@ -76,11 +76,9 @@ if "adat" in what:
     for (m, n) in ((512, 1024), (1024, 2048), (2048, 4096), (4096, 8192), (1000, 5000), (3000, 3500), (2048, 16384), (6144, 12288)):
         adat(m, n)
 if "c3" in what:
-    x0 = solve(4096, 8192, 5, LPIPM_OVERLAP=0, LPIPM_ADAT_UNITS=0)
-    x1 = solve(4096, 8192, 5, LPIPM_OVERLAP=0)
-    x2 = solve(4096, 8192, 5, LPIPM_OVERLAP=1)
-    x3 = solve(4096, 8192, 5, LPIPM_OVERLAP=1, LPIPM_OVERLAP_CUS=2)
-    print("c3: |x_units - x_round2|", np.abs(x1 - x0).max(), " |x_overlap - x_units|", np.abs(x2 - x1).max(), np.abs(x3 - x1).max(), flush=True)
+    x0 = solve(4096, 8192, 5, LPIPM_ADAT_UNITS=0)
+    x1 = solve(4096, 8192, 5)
+    print("c3: |x_units - x_round2|", np.abs(x1 - x0).max(), flush=True)
 if "c4" in what:
     a = lockstep(32, 1024, 2048, 5, LPIPM_ADAT_UNITS=0)
     b = lockstep(32, 1024, 2048, 5)
@@ -88,7 +86,6 @@ if "c4" in what:
 if "c4only" in what:
     lockstep(32, 1024, 2048, 5)
 if "c2" in what:
-    solve(512, 1024, 50, LPIPM_OVERLAP=0, LPIPM_ADAT_UNITS=0)
-    solve(512, 1024, 50, LPIPM_OVERLAP=0)
-    solve(2048, 4096, 10, LPIPM_OVERLAP=0)
-    solve(2048, 4096, 10, LPIPM_OVERLAP=1)
+    solve(512, 1024, 50, LPIPM_ADAT_UNITS=0)
+    solve(512, 1024, 50)
+    solve(2048, 4096, 10)

@@ -117,11 +117,9 @@ int main() {
         CHECK(lpipm_k_symv_residual(ctx, ms_, S.data(), 2, V.data(), R0.data(), Rho.data()) == 0);
     }
     lpipm_destroy(ctx);
-    // refined solves (LPIPM_REFINE=2) and the factorisation beside A.D.A^T (LPIPM_OVERLAP=1): both are decided when a
-    // context is created / first solves
+    // refined solves (LPIPM_REFINE=2): decided when a context is created
     setenv("LPIPM_EXPERIMENTAL", "1", 1);     // the library reads its measurement knobs only with the master switch on
     setenv("LPIPM_REFINE", "2", 1);
-    setenv("LPIPM_OVERLAP", "1", 1);
     {
         lpipm_ctx* c2 = nullptr;
         CHECK(lpipm_create(0, &c2) == 0);
@@ -130,7 +128,7 @@ int main() {
         std::vector<double> x(p.n); double fun; uint64_t it;
         CHECK(lpipm_solve(c2, &o, x.data(), &fun, &it, nullptr) == 0);
         CHECK(maxerr(x, p.xs) < 1e-5);
-        LP q = make(3, 2048, 2304);                       // big enough for the side-by-side schedule
+        LP q = make(3, 2048, 2304);
         CHECK(lpipm_upload(c2, q.m, q.n, q.A.data(), q.n, q.b.data(), q.c.data(), 0.0) == 0);
         std::vector<double> xq(q.n);
         CHECK(lpipm_solve(c2, &o, xq.data(), &fun, &it, nullptr) == 0);

@@ -370,31 +370,6 @@ def test_c5_shape_on_one_gpu(ctx):
     ctx.upload_arrays(A[:128, :256].copy(), b[:128].copy(), c[:256].copy())      # release the 7 GiB of buffers
 
 
-def test_graph_replay_is_bit_identical(built, monkeypatch):
-    """LPIPM_GRAPH=1 replays each iteration's launches as one hipGraph: same kernels, same arguments, same
-    order => bit-identical iterates (measured gain ~1 %: the dependent-dispatch latency is on the GPU side)."""
-    import lp_amd
-    from lp_amd import synth
-    A, b, c = synth.planted_lp(2, 200, 520)[:3]
-    o = lp_amd.InteriorPoint.default().opts()
-    plain = lp_amd.Context(0)
-    plain.upload_arrays(A, b, c)
-    r0 = plain.solve_raw(o, want_log=True)
-    plain.close()
-    monkeypatch.setenv("LPIPM_EXPERIMENTAL", "1")
-    monkeypatch.setenv("LPIPM_GRAPH", "1")
-    g = lp_amd.Context(0)
-    g.upload_arrays(A, b, c)
-    r1 = g.solve_raw(o, want_log=True)
-    r2 = g.solve_raw(o, want_log=True)          # second solve reuses the instantiated graph
-    g.upload_arrays(A * 2.0, b * 2.0, c)        # re-upload drops the graphs; the scaled LP has the same solution
-    r3 = g.solve_raw(o)
-    g.close()
-    assert r0[0] == r1[0] == r2[0] == r3[0] == 0 and r0[3] == r1[3] == r2[3]
-    assert np.array_equal(r0[1], r1[1]) and np.array_equal(r0[1], r2[1]) and r0[4] == r1[4] == r2[4]
-    assert np.abs(r3[1] - r0[1]).max() < 1e-6
-
-
 @pytest.mark.parametrize("m,n,ip", [(200, 520, False), (512, 1024, False), (1000, 1024, True), (300, 900, True), (7, 13, False)])
 def test_fused_vector_stage_is_bit_identical(built, monkeypatch, m, n, ip):
     """Up to 1024 rows / columns the runs of vector kernels between the passes over A are ONE single-workgroup launch each
@@ -562,25 +537,3 @@ def test_awkward_shapes_match_oracle(ctx, m, n):
     assert rc == ref["status"] == 0 and it == ref["iterations"]
     assert np.abs(x - ref["x_slack"]).max() <= 1e-6
     assert abs(fun - ref["fun"]) <= 1e-6 * max(1.0, abs(ref["fun"]))
-
-
-def test_factorisation_beside_adat_matches_golden(built, monkeypatch):
-    """The opt-in schedule LPIPM_OVERLAP=1 (solver.hip enqueue_factor_overlapped: A.D.A^T in column groups on one
-    CU-masked stream, the left-looking factorisation's chain on another): same iterations and x as the committed
-    oracle vector of the headline LP, and the same bits run to run."""
-    import os
-    import lp_amd as lp
-    from lp_amd import synth
-    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "planted_4096x8192_s1.npz"))
-    A, b, c, _ = synth.planted_lp(1, 4096, 8192)
-    monkeypatch.setenv("LPIPM_EXPERIMENTAL", "1")
-    monkeypatch.setenv("LPIPM_OVERLAP", "1")
-    ctx = lp.Context(0)                       # the streams are created with the context
-    ctx.upload_arrays(A, b, c)
-    o = lp.InteriorPoint.default().opts()
-    rc, x, fun, it, _ = ctx.solve_raw(o)
-    rc2, x2, _, it2, _ = ctx.solve_raw(o)
-    ctx.close()
-    assert rc == 0 and it == int(g["iterations"])
-    assert np.abs(x - g["x_slack"]).max() <= X_TOL
-    assert rc2 == 0 and it2 == it and np.array_equal(x, x2)
