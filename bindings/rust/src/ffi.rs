@@ -84,6 +84,14 @@ extern "C" {
         ctx: *mut lpipm_ctx, opts: *const lpipm_opts, x_slack_out: *const *mut f64, fun_out: *mut f64,
         iterations_out: *mut u64, status_out: *mut i32,
     ) -> c_int;
+    // A lockstep batch whose members share ONE constraint matrix (member i = (A, b[i], c[i], c0[i])): A resident once,
+    // every pass over it serving the whole batch; solved with lpipm_solve_lockstep, members bit-identical to single solves.
+    pub fn lpipm_upload_lockstep_shared(
+        ctx: *mut lpipm_ctx, count: u64, m: u64, n: u64, a: *const f64, lda: u64, b: *const *const f64,
+        c: *const *const f64, c0: *const f64,
+    ) -> c_int;
+    // Device bytes held for the resident problem(s): arenas + shared matrix + factor workspace.
+    pub fn lpipm_get_resident_bytes(ctx: *const lpipm_ctx, bytes_out: *mut u64) -> c_int;
 
     // One LP split by columns over ranks (BASELINE config 5): the caller supplies the all-reduce
     // (e.g. ncclAllReduce on `stream`); op 0 = sum, 1 = min.

@@ -186,6 +186,16 @@ int lpipm_solve_lockstep(lpipm_ctx* ctx, const lpipm_opts* opts, double* const* 
  * without a host round trip.  Rows of members without a solution (Infeasible, ...) are left untouched. */
 int lpipm_solve_lockstep_device(lpipm_ctx* ctx, const lpipm_opts* opts, void* x_dev_out, uint64_t row_stride,
                                 double* fun_out, uint64_t* iterations_out, int32_t* status_out);
+/* Lockstep batch of `count` LPs that share ONE constraint matrix A (m x n row-major, lda >= n): member i is
+ * (A, b[i], c[i], c0[i]).  A is copied to the device once and is not part of any member's arena; every pass over A
+ * serves the whole batch.  Solve with lpipm_solve_lockstep / lpipm_solve_lockstep_device, exactly as after
+ * lpipm_upload_lockstep: each member comes out bit-identical to lpipm_upload + lpipm_solve of (A, b[i], c[i], c0[i]).
+ * Validation and return codes as lpipm_upload_lockstep (dense slack form, no n_slack hint; Cholesky arm only). */
+int lpipm_upload_lockstep_shared(lpipm_ctx* ctx, uint64_t count, uint64_t m, uint64_t n, const double* A, uint64_t lda,
+                                 const double* const* b, const double* const* c, const double* c0 /* nullable */);
+/* Device bytes the context holds for its resident problem(s) (arenas + shared matrix + factor workspace); 0 before any
+ * upload. */
+int lpipm_get_resident_bytes(const lpipm_ctx* ctx, uint64_t* bytes_out);
 /* lpipm_solve_batch with device-resident results: member i's x / tau goes to x_dev_out + i * row_stride doubles
  * (row_stride >= max n[i]); everything else as lpipm_solve_batch. */
 int lpipm_solve_batch_device(lpipm_ctx* ctx, uint64_t count, const uint64_t* m, const uint64_t* n,

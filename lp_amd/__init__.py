@@ -308,6 +308,32 @@ class Context:
         self.m, self.n = m, n
         return self
 
+    def upload_lockstep_shared(self, A, bs, cs, c0s=None):
+        """`len(bs)` LPs that share ONE constraint matrix A, resident at once (lpipm_upload_lockstep_shared): member i is
+        (A, bs[i], cs[i], c0s[i]).  A is held once on the device and each pass over it serves the whole batch; solve with
+        solve_lockstep / solve_lockstep_device -- every member bit-identical to solving it alone."""
+        A = _f64(A); bs = [_f64(b) for b in bs]; cs = [_f64(c) for c in cs]
+        K = len(bs)
+        if A.ndim != 2 or K < 1 or len(cs) != K or (c0s is not None and len(c0s) != K):
+            raise IncompatibleInputDimensions()
+        m, n = A.shape
+        for b, c in zip(bs, cs):
+            if b.shape != (m,) or c.shape != (n,):
+                raise IncompatibleInputDimensions()
+        dp = C.POINTER(C.c_double)
+        arr = lambda lst: (dp * K)(*[_p(a) for a in lst])
+        c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
+        _raise_for(_capi.lib().lpipm_upload_lockstep_shared(self._h, K, m, n, _p(A), n, arr(bs), arr(cs), c0))
+        self._lock = (K, m, n, A, bs, cs)
+        self.m, self.n = m, n
+        return self
+
+    def resident_bytes(self) -> int:
+        """Device bytes held for the resident problem(s): arenas + shared matrix + factor workspace."""
+        out = C.c_uint64(0)
+        _raise_for(_capi.lib().lpipm_get_resident_bytes(self._h, C.byref(out)))
+        return int(out.value)
+
     def solve_lockstep(self, opts: "_capi.Opts"):
         """-> list of (status, x_slack | None, fun, iterations), one per LP of the last upload_lockstep"""
         K, m, n = self._lock[:3]

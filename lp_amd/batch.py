@@ -86,3 +86,25 @@ def solve_batch_sharded(problems, opts=None, ctx=None, group=None, device=None, 
         out.append(dict(status=status, x_slack=row[:n].copy() if has_x else None,
                         fun=float(row[n_max]) if has_x else None, iterations=int(row[n_max + 1])))
     return out
+
+
+def solve_shared_matrix(A, bs, cs, c0s=None, opts=None, ctx=None, max_group=32):
+    """LPs that share ONE constraint matrix A (scenario sweeps: only b, c and c0 vary), member i = (A, bs[i], cs[i], c0s[i]).
+    The members go through lockstep groups of at most `max_group` on one context (lpipm_upload_lockstep_shared: A resident
+    once, every pass over it serving the whole group).  Returns a list of dicts {status, x_slack, fun, iterations} in member
+    order, as solve_batch_sharded does."""
+    import lp_amd
+    count = len(bs)
+    if len(cs) != count or (c0s is not None and len(c0s) != count):
+        raise lp_amd.IncompatibleInputDimensions()
+    if max_group < 1:
+        raise lp_amd.InvalidParameter("max_group must be >= 1")
+    ctx = ctx or lp_amd.default_context(0)
+    opts = opts or lp_amd.InteriorPoint.default().opts()
+    out = []
+    for k0 in range(0, count, max_group):
+        k1 = min(k0 + max_group, count)
+        ctx.upload_lockstep_shared(A, bs[k0:k1], cs[k0:k1], None if c0s is None else c0s[k0:k1])
+        for st, x, fun, it in ctx.solve_lockstep(opts):
+            out.append(dict(status=st, x_slack=x, fun=fun, iterations=it))
+    return out

@@ -71,11 +71,14 @@ struct GemmK {
     int sk;                   // stream-K unit in k-tiles (== kc up to KT = 256: one canonical chunking for every tile)
     double* C2;               // nullable: the final value of every tile is stored here too (same ldc)
     BatchK bk;
+    long long pq_stride;      // bytes between the members' P and Q: bk.stride, or 0 for the A a batch shares
 };
 // LP blockIdx.z of a lockstep batch: per-LP pointers shifted (the tile list is shared)
 __device__ __forceinline__ GemmK batch_shift(const GemmK& p0) {
     GemmK p = p0;
-    p.P = batch_ptr(p0.P, p0.bk); p.Q = batch_ptr(p0.Q, p0.bk); p.s = batch_ptr(p0.s, p0.bk);
+    const long long pq = batch_lp(p0.bk) * p0.pq_stride;
+    p.P = p0.P ? (const double*)((const char*)p0.P + pq) : p0.P; p.Q = p0.Q ? (const double*)((const char*)p0.Q + pq) : p0.Q;
+    p.s = batch_ptr(p0.s, p0.bk);
     p.C = batch_ptr(p0.C, p0.bk); p.ws = batch_ptr(p0.ws, p0.bk); p.sk_claim = batch_ptr(p0.sk_claim, p0.bk);
     p.C2 = batch_ptr(p0.C2, p0.bk);
     return p;
@@ -541,12 +544,14 @@ struct UnitsK {
     unsigned int* grp_cnt;
     int grp_w;
     BatchK bk;
+    long long astride;        // bytes between the members' A: bk.stride, or 0 for the A a batch shares
 };
 template <bool GRP>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemm_nt_units_kernel(const UnitsK p0) {
     if (batch_done(p0.bk)) return;
     UnitsK p = p0;
-    p.A = batch_ptr(p0.A, p0.bk); p.s = batch_ptr(p0.s, p0.bk); p.C = batch_ptr(p0.C, p0.bk); p.C2 = batch_ptr(p0.C2, p0.bk);
+    p.A = (const double*)((const char*)p0.A + batch_lp(p0.bk) * p0.astride);
+    p.s = batch_ptr(p0.s, p0.bk); p.C = batch_ptr(p0.C, p0.bk); p.C2 = batch_ptr(p0.C2, p0.bk);
     p.slabs = batch_ptr(p0.slabs, p0.bk); p.tile_cnt = batch_ptr(p0.tile_cnt, p0.bk); p.grp_cnt = batch_ptr(p0.grp_cnt, p0.bk);
     __shared__ __attribute__((aligned(16))) double ldsA[2][TILE][LDS_STRIDE];
     __shared__ __attribute__((aligned(16))) double ldsB[2][TILE][LDS_STRIDE];
@@ -975,6 +980,7 @@ hipError_t launch_gemm_nt(const GemmArgs& a, hipStream_t st) {
     k.C = a.C; k.ldc = a.ldc; k.KT = a.K / BK; k.alpha = a.alpha; k.beta = a.beta;
     k.ntiles = a.ntiles; k.tiles_lower = a.tiles_lower; k.ntj = a.ntj; k.tile_list = a.tile_list;
     k.diag_pad_from = a.diag_pad_from; k.ws = a.ws; k.nwg = a.nwg; k.bk = batch_k(a.batch);
+    k.pq_stride = a.shared_a ? 0 : k.bk.stride;
     k.sk_claim = a.sk_claim; k.kc = 0; k.sk = SK_CHUNK; k.C2 = a.C2;
     const int B = a.batch.count;
     if (a.ntiles <= 0 || k.KT <= 0) return hipSuccess;
@@ -1061,6 +1067,7 @@ hipError_t launch_adat_units(const AdatUnitsArgs& a, hipStream_t st) {
     k.ntiles = a.ntiles; k.tile_list = a.tile_list; k.unit_list = a.unit_list; k.nunits = a.nunits; k.upc = a.upc;
     k.diag_pad_from = a.diag_pad_from; k.slabs = a.slabs; k.tile_cnt = a.tile_cnt;
     k.grp_cnt = a.grp_cnt; k.grp_w = a.grp_w > 0 ? a.grp_w : 1; k.bk = batch_k(a.batch);
+    k.astride = a.shared_a ? 0 : k.bk.stride;
     const int B = a.batch.count;
     const bool xm = B >= 8 && B % 8 == 0;                  // one LP per XCD at a time (see BatchK)
     k.bk.xcd_major = xm ? 1 : 0;

@@ -117,6 +117,7 @@ struct GemmArgs {
     double*       C2;           // stream-K launches whose tiles are all split (ntiles < nwg): final values stored here too
     int           tile_edge;    // whole-tile launches: 0/128 -> 128x128 tiles, 64 -> 64x64, 32 -> 32 rows x 128 cols, 3232 -> 32x32
     Batch         batch;        // lockstep batch (every pointer above except tile_list is per LP)
+    bool          shared_a = false;   // P and Q are ONE matrix the whole batch shares (member stride 0; lpipm_upload_lockstep_shared)
 };
 // Launches the main kernel and, when tiles are split into stream-K chunks, the deterministic fix-up pass.
 hipError_t launch_gemm_nt(const GemmArgs& a, hipStream_t st);
@@ -152,6 +153,7 @@ struct AdatUnitsArgs {
     unsigned int* grp_cnt;            // nullable: completed tiles per column group (tj / grp_w), zeroed likewise
     int grp_w;
     Batch batch;
+    bool shared_a = false;            // A is ONE matrix the whole batch shares (member stride 0; lpipm_upload_lockstep_shared)
 };
 int adat_units_cpt(int K);            // chunks per tile for a contraction of K columns
 int adat_units_chunking(int K, int* kc, int* nbig, int* ks);   // ... and their boundaries (kernels_gemm.hip)
@@ -249,6 +251,17 @@ hipError_t launch_gemv_t(const double* A, int64_t lda, int mp, int np, int nrhs,
 int gemv_dual_chunks(int np);
 hipError_t launch_gemv_dual(const double* A, int64_t lda, int mp, int np, const double* W, const double* V, double* AxPart,
                             double* Upart, int64_t slab, hipStream_t st, const Batch& bt = Batch{});
+// ---- the same three passes over ONE matrix A that every member of the batch shares (lpipm_upload_lockstep_shared): A is
+// not offset by the member (the other operands are); each A element a wave loads serves a GROUP of members before the next
+// one is read (gridDim.z = groups), so a pass reads A ceil(count / group) times instead of count times.  Every output is
+// summed exactly as the single-member kernel above sums it (same lane striding and butterfly, same row slabs, same chunk
+// slabs): a member's bits do not depend on whether A is shared.  Finished members are skipped and their outputs untouched.
+hipError_t launch_gemv_n_shared(const double* A, int64_t lda, int m, int np, int nrhs, const double* W, int64_t ldw,
+                                const double* add0, const double* add1, double* Y, int64_t ldy, hipStream_t st, const Batch& bt);
+hipError_t launch_gemv_t_shared(const double* A, int64_t lda, int mp, int np, int nrhs, const double* V, int64_t ldv,
+                                double* Upart, hipStream_t st, int64_t slab, const Batch& bt);
+hipError_t launch_gemv_dual_shared(const double* A, int64_t lda, int mp, int np, const double* W, const double* V,
+                                   double* AxPart, double* Upart, int64_t slab, hipStream_t st, const Batch& bt);
 // Rho[q] = R0[q] - M.V[q] (q < nrhs) for a symmetric mp x mp M whose LOWER triangle is stored (one read of it);
 // slabs: symv_slab_doubles(mp) doubles of scratch.  The residual of the refinement step of the Cholesky solve.
 size_t symv_slab_doubles(int mp);

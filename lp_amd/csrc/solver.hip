@@ -55,6 +55,12 @@ struct lpipm_ctx {
     char* arena = nullptr;
     size_t arena_bytes = 0, bstride = 0;
     int B = 1;
+    // lpipm_upload_lockstep_shared: ONE A for the whole batch, outside the arenas (mp x npa, zeros beyond n and m); every
+    // pass over A serves all members (the *_shared GEMV launches, A.D.A^T with A's member stride 0)
+    bool shared_a = false;
+    double* a_shared = nullptr;          // owned by the context (a view shares its parent's)
+    size_t a_shared_bytes = 0;
+    size_t list_bytes = 0;               // tile / unit lists (own allocation)
     Batch bt;                    // what the solve path hands to every launcher (count, stride, done flags)
     Batch bt_head;               // same with the done test always on: the speculatively enqueued head of an iteration
     hipEvent_t ev_status = nullptr;   // recorded behind the status copy of an iteration
@@ -344,6 +350,7 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->st) (void)hipStreamSynchronize(c->st);
     if (c->arena) (void)hipFree(c->arena);
+    if (c->a_shared) (void)hipFree(c->a_shared);
     if (c->tile_list) (void)hipFree(c->tile_list);
     free_list(c->kallocs);
     if (c->mpack) (void)hipFree(c->mpack);
@@ -485,7 +492,7 @@ static void bind_status_pinned(lpipm_ctx* c, bool allow);
 static int layout_problem(lpipm_ctx* c, Arena& ar, bool build) {
     VecArgs& v = c->va;
     const size_t mp = (size_t)c->mp, np = (size_t)c->np;
-    c->A = ar.take<double>(mp * c->npa);
+    c->A = c->shared_a ? nullptr : ar.take<double>(mp * c->npa);     // a shared A has its own allocation (upload_impl)
     v.b = ar.take<double>(mp); v.c = ar.take<double>(np);
     v.x = ar.take<double>(np); v.y = ar.take<double>(mp); v.z = ar.take<double>(np);
     v.dinv = ar.take<double>(np); v.xs = ar.take<double>(np); v.r1 = ar.take<double>(np); v.rD = ar.take<double>(np);
@@ -535,18 +542,20 @@ static int layout_problem(lpipm_ctx* c, Arena& ar, bool build) {
 // structure is then true by construction (lpipm_upload_ub_eq).
 struct UploadParts { uint64_t m_ub; const double* A_ub; uint64_t lda_ub; const double* b_ub;
                      const double* A_eq; uint64_t lda_eq; const double* b_eq; };
+// shared: A[0] is the one matrix of all `count` LPs (lpipm_upload_lockstep_shared; A holds one entry).
 static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const double* const* A, uint64_t lda,
                        const double* const* b, const double* const* cc, const double* c0, uint64_t n_slack,
-                       const UploadParts* parts = nullptr) {
+                       const UploadParts* parts = nullptr, bool shared = false) {
     if (!c || count < 1 || !cc) return LPIPM_ERR_BAD_ARGUMENT;
     if (!parts && (!A || !b || lda < n)) return LPIPM_ERR_BAD_ARGUMENT;
     for (int i = 0; i < count; ++i)
-        if (!cc[i] || (!parts && (!A[i] || !b[i]))) return LPIPM_ERR_BAD_ARGUMENT;
+        if (!cc[i] || (!parts && ((!shared && !A[i]) || !b[i]))) return LPIPM_ERR_BAD_ARGUMENT;
+    if (shared && (parts || !A[0])) return LPIPM_ERR_BAD_ARGUMENT;
     if (m == 0) return LPIPM_UNCONSTRAINED;  // linear_program.rs:134-136
     if (n == 0 || m > (1u << 20) || n > (1u << 24) || n_slack > n || n_slack > m) return LPIPM_ERR_BAD_ARGUMENT;
     // The hint is only used if the last n_slack columns really are [I; 0] (ProblemBuilder::build
     // guarantees it, linear_program.rs:147-156); anything else is treated as a dense matrix.
-    if (!parts && (n_slack == n || count > 1)) n_slack = 0;
+    if (!parts && (n_slack == n || count > 1 || shared)) n_slack = 0;
     for (uint64_t i = 0; i < m && n_slack && !parts; ++i) {
         const double* row = A[0] + i * lda + (n - n_slack);
         for (uint64_t j = 0; j < n_slack; ++j)
@@ -557,9 +566,11 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
     const uint64_t nx = n - n_slack;
     const int mp = (int)round_up(m, NB), np = (int)round_up(n, BK), npa = (int)round_up(nx, BK);
     hipStream_t st = c->st;
-    if (!c->has_problem || mp != c->mp || np != c->np || npa != c->npa || count != c->B) {
+    if (!c->has_problem || mp != c->mp || np != c->np || npa != c->npa || count != c->B || shared != c->shared_a) {
         LP_HIP(hipStreamSynchronize(st));
         if (c->arena) { LP_HIP(hipFree(c->arena)); c->arena = nullptr; }
+        if (c->a_shared) { LP_HIP(hipFree(c->a_shared)); c->a_shared = nullptr; c->a_shared_bytes = 0; }
+        c->shared_a = shared;
         if (c->tile_list) { LP_HIP(hipFree(c->tile_list)); c->tile_list = nullptr; }
         factor_plan_destroy(c->plan);
         c->has_problem = false;
@@ -604,7 +615,14 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
         Arena real;
         real.base = c->arena;
         LP_TRY(layout_problem(c, real, true));
-        LP_HIP(hipMalloc((void**)&c->tile_list, (order.size() + grouped.size() + units.size() + units_grp.size() + 1) * sizeof(int2)));
+        if (shared) {              // the one A of the batch: mp x npa like an arena's, zero padding
+            c->a_shared_bytes = (size_t)mp * (size_t)npa * sizeof(double);
+            LP_HIP(hipMalloc((void**)&c->a_shared, c->a_shared_bytes));
+            LP_HIP(hipMemsetAsync(c->a_shared, 0, c->a_shared_bytes, st));
+            c->A = c->a_shared;
+        }
+        c->list_bytes = (order.size() + grouped.size() + units.size() + units_grp.size() + 1) * sizeof(int2);
+        LP_HIP(hipMalloc((void**)&c->tile_list, c->list_bytes));
         LP_HIP(hipMemcpyAsync(c->tile_list, order.data(), order.size() * sizeof(int2), hipMemcpyHostToDevice, st));
         c->tile_list_grp = c->tile_list + order.size();
         c->unit_list = c->tile_list_grp + grouped.size();
@@ -630,6 +648,7 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
         // same padded geometry: clear the whole state, so no stale (possibly non-finite) value of a
         // previous problem can sit in a padding lane
         LP_HIP(hipMemsetAsync(c->arena, 0, c->arena_bytes, st));
+        if (c->a_shared) LP_HIP(hipMemsetAsync(c->a_shared, 0, c->a_shared_bytes, st));   // (a smaller m or n than before)
     }
     c->m = m; c->n = n;
     c->ns = (int)n_slack; c->nx = (int)nx;
@@ -659,10 +678,14 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
         LP_HIP(hipMemcpyAsync((void*)c->va.c, cc[0], nx * sizeof(double), hipMemcpyHostToDevice, st));
         LP_HIP(hipMemcpyAsync((void*)(c->va.S + S_C0), &c0v[0], sizeof(double), hipMemcpyHostToDevice, st));
     }
+    if (shared)
+        LP_HIP(hipMemcpy2DAsync(c->A, (size_t)npa * sizeof(double), A[0], (size_t)lda * sizeof(double),
+                                (size_t)nx * sizeof(double), (size_t)m, hipMemcpyHostToDevice, st));
     for (int i = 0; i < count && !parts; ++i) {
         const size_t off = (size_t)i * c->bstride;
-        LP_HIP(hipMemcpy2DAsync((char*)c->A + off, (size_t)npa * sizeof(double), A[i], (size_t)lda * sizeof(double),
-                                (size_t)nx * sizeof(double), (size_t)m, hipMemcpyHostToDevice, st));
+        if (!shared)
+            LP_HIP(hipMemcpy2DAsync((char*)c->A + off, (size_t)npa * sizeof(double), A[i], (size_t)lda * sizeof(double),
+                                    (size_t)nx * sizeof(double), (size_t)m, hipMemcpyHostToDevice, st));
         LP_HIP(hipMemcpyAsync((char*)c->va.b + off, b[i], m * sizeof(double), hipMemcpyHostToDevice, st));
         LP_HIP(hipMemcpyAsync((char*)c->va.c + off, cc[i], n * sizeof(double), hipMemcpyHostToDevice, st));
         LP_HIP(hipMemcpyAsync((char*)(c->va.S + S_C0) + off, &c0v[i], sizeof(double), hipMemcpyHostToDevice, st));
@@ -700,12 +723,14 @@ extern "C" int lpipm_upload_ub_eq(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const
 static hipError_t ctx_gemv_n(lpipm_ctx* c, int nrhs, const double* W, const double* add0, const double* add1, double* Y,
                              const Batch& bt) {
     ++c->gemv_passes;
+    if (c->shared_a) return launch_gemv_n_shared(c->A, c->npa, (int)c->m, c->npa, nrhs, W, c->np, add0, add1, Y, c->mp, c->st, bt);
     hipError_t e = launch_gemv_n(c->A, c->npa, (int)c->m, c->npa, nrhs, W, c->np, add0, add1, Y, c->mp, c->st, 1.0, bt);
     if (e != hipSuccess) return e;
     return launch_slack_n(c->ns, c->nx, nrhs, W, c->np, Y, c->mp, c->st, bt);
 }
 static hipError_t ctx_gemv_t(lpipm_ctx* c, int nrhs, const double* V, const Batch& bt) {
     ++c->gemv_passes;
+    if (c->shared_a) return launch_gemv_t_shared(c->A, c->npa, c->mp, c->npa, nrhs, V, c->mp, c->ATpart, c->st, c->np, bt);
     hipError_t e = launch_gemv_t(c->A, c->npa, c->mp, c->npa, nrhs, V, c->mp, c->ATpart, c->st, c->np, bt);
     if (e != hipSuccess) return e;
     return launch_slack_t(c->ns, c->nx, nrhs, c->nsplit, V, c->mp, c->ATpart, c->np, c->st, bt);
@@ -720,6 +745,7 @@ static GemmArgs adat_args(lpipm_ctx* c, const Batch& bt) {
     g.ntiles = c->ntiles; g.tiles_lower = 1; g.ntj = 0; g.tile_list = c->tile_list;
     g.diag_pad_from = (int)c->m; g.ws = c->ws; g.nwg = c->adat_nwg; g.batch = bt; g.sk_claim = c->sk_claim; g.streamk = 1;
     g.C2 = (c->refine > 0 && gemm_streamk_split(c->npa / BK)) ? c->M0 : nullptr;    // only the refined solves need M itself
+    g.shared_a = c->shared_a;
     return g;
 }
 static AdatUnitsArgs adat_units_args(lpipm_ctx* c, const Batch& bt) {
@@ -728,7 +754,7 @@ static AdatUnitsArgs adat_units_args(lpipm_ctx* c, const Batch& bt) {
     a.C2 = (c->refine > 0 && c->cpt > 1) ? c->M0 : nullptr;                // only the refined solves need M itself
     a.ntiles = c->ntiles; a.tile_list = c->tile_list; a.unit_list = c->unit_list; a.nunits = c->nunits; a.upc = c->upc;
     a.diag_pad_from = (int)c->m; a.slabs = c->ws; a.tile_cnt = c->tile_cnt;
-    a.grp_cnt = nullptr; a.grp_w = POTRF_OUTER; a.batch = bt;
+    a.grp_cnt = nullptr; a.grp_w = POTRF_OUTER; a.batch = bt; a.shared_a = c->shared_a;
     return a;
 }
 // clears the arrival counters (tiles and groups) of every LP of the batch
@@ -783,7 +809,8 @@ static int enqueue_residuals(lpipm_ctx* c, int is_init, int ip_next, double tol)
     if (!(c->colsplit && c->world > 1)) {       // both products in one read of A
         ++c->gemv_passes;
         v.ax_chunks = gemv_dual_chunks(c->npa);
-        LP_HIP(launch_gemv_dual(c->A, c->npa, c->mp, c->npa, v.x, v.y, v.Ax, c->ATpart, c->np, c->st, c->bt));
+        if (c->shared_a) LP_HIP(launch_gemv_dual_shared(c->A, c->npa, c->mp, c->npa, v.x, v.y, v.Ax, c->ATpart, c->np, c->st, c->bt));
+        else             LP_HIP(launch_gemv_dual(c->A, c->npa, c->mp, c->npa, v.x, v.y, v.Ax, c->ATpart, c->np, c->st, c->bt));
         LP_HIP(launch_slack_n(c->ns, c->nx, 1, v.x, c->np, v.Ax, c->mp, c->st, c->bt));          // into chunk slab 0
         LP_HIP(launch_slack_t(c->ns, c->nx, 1, c->nsplit, v.y, c->mp, c->ATpart, c->np, c->st, c->bt));
     } else {
@@ -1314,6 +1341,16 @@ extern "C" int lpipm_upload_lockstep(lpipm_ctx* c, uint64_t count, uint64_t m, u
                                      const double* const* b, const double* const* cc, const double* c0) {
     if (count < 1 || count > 4096) return LPIPM_ERR_BAD_ARGUMENT;
     return upload_impl(c, (int)count, m, n, A, n, b, cc, c0, 0);
+}
+extern "C" int lpipm_upload_lockstep_shared(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* A, uint64_t lda,
+                                            const double* const* b, const double* const* cc, const double* c0) {
+    if (count < 1 || count > 4096 || !A) return LPIPM_ERR_BAD_ARGUMENT;
+    return upload_impl(c, (int)count, m, n, &A, lda, b, cc, c0, 0, nullptr, true);
+}
+extern "C" int lpipm_get_resident_bytes(const lpipm_ctx* c, uint64_t* bytes_out) {
+    if (!c || !bytes_out) return LPIPM_ERR_BAD_ARGUMENT;
+    *bytes_out = c->has_problem ? (uint64_t)(c->arena_bytes + c->a_shared_bytes + c->list_bytes) : 0;
+    return LPIPM_OK;
 }
 extern "C" int lpipm_solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, double* const* x_slack_out, double* fun_out,
                                     uint64_t* iterations_out, int32_t* status_out) {

@@ -22,6 +22,26 @@ def planted_lp(seed: int, m: int, n: int):
     return A, b, c, xs
 
 
+def planted_scenarios(seed: int, m: int, n: int, count: int):
+    """One planted constraint matrix with `count` scenarios on it: A is planted_lp(seed, m, n)'s; scenario i draws its own
+    basis (m of the n columns), x*_i (1 + U[0,1) on the basis), y*_i ~ N(0, 1) and z*_i (1 + U[0,1) off the basis), so
+    b_i = A x*_i and c_i = A^T y*_i + z*_i have the known, strictly complementary optimum x*_i.
+    -> (A[m,n], bs[count][m], cs[count][n], xstars[count][n])."""
+    if m > n:
+        raise ValueError("planted_scenarios needs m <= n")
+    A = planted_lp(seed, m, n)[0]
+    rng = np.random.default_rng([seed, m, n, count])
+    bs, cs, xs = [], [], []
+    for _ in range(count):
+        basis = rng.permutation(n)[:m]
+        x, z = np.zeros(n), 1.0 + rng.random(n)
+        x[basis] = 1.0 + rng.random(m)
+        z[basis] = 0.0
+        y = rng.standard_normal(m)
+        bs.append(A @ x); cs.append(A.T @ y + z); xs.append(x)
+    return A, bs, cs, xs
+
+
 class _Rng:
     """splitmix64 -> xoshiro256**, Box-Muller; scalar Python, for small cross-checks only."""
 
