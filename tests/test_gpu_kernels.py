@@ -71,14 +71,16 @@ def test_potrf_and_solve(ctx, m):
 
 
 def test_potrf_reports_nonpositive_pivot(ctx):
-    """A failed factorisation must surface (newton_equations.rs:59-63 -> NumericalProblem)."""
+    """A failed factorisation must surface (newton_equations.rs:59-63 -> NumericalProblem), with info = 1 + the index of
+    the first non-positive pivot (include/lpipm.h): pivots 0..149 are those of a positive definite matrix, and pivot 150
+    is -1 - |L[150, :150]|^2 < 0, so 151 is the only correct value."""
     m = 200
     rng = np.random.default_rng(7)
     B = rng.standard_normal((m, m + 5))
     M = B @ B.T
     M[150, 150] = -1.0
     _, info, _ = ctx.k_potrf(M)
-    assert 1 <= info <= 151
+    assert info == 151, info
 
 
 def test_potrf_is_bitwise_reproducible(ctx):
