@@ -1063,7 +1063,7 @@ hipError_t launch_adat_units(const AdatUnitsArgs& a, hipStream_t st) {
     if (k.cpt == 1) k.kc = 0;
     if (a.upc > 1 && k.nbig != k.cpt) return hipErrorInvalidValue;     // several chunks per unit: uniform chunking only
     if (k.cpt > 1 && (!a.slabs || !a.tile_cnt)) return hipErrorInvalidValue;
-    if (k.cpt > 256) return hipErrorInvalidValue;          // a tile's slabs are one 32-bit buffer
+    if (k.cpt > ADAT_UNITS_MAX_CPT) return hipErrorInvalidValue;   // a tile's slabs are one 32-bit buffer
     k.ntiles = a.ntiles; k.tile_list = a.tile_list; k.unit_list = a.unit_list; k.nunits = a.nunits; k.upc = a.upc;
     k.diag_pad_from = a.diag_pad_from; k.slabs = a.slabs; k.tile_cnt = a.tile_cnt;
     k.grp_cnt = a.grp_cnt; k.grp_w = a.grp_w > 0 ? a.grp_w : 1; k.bk = batch_k(a.batch);

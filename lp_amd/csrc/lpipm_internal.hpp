@@ -156,6 +156,7 @@ struct AdatUnitsArgs {
     bool shared_a = false;            // A is ONE matrix the whole batch shares (member stride 0; lpipm_upload_lockstep_shared)
 };
 int adat_units_cpt(int K);            // chunks per tile for a contraction of K columns
+constexpr int ADAT_UNITS_MAX_CPT = 256;   // most chunks per tile the units kernel takes (a tile's slabs are one 32-bit buffer)
 int adat_units_chunking(int K, int* kc, int* nbig, int* ks);   // ... and their boundaries (kernels_gemm.hip)
 hipError_t launch_adat_units(const AdatUnitsArgs& a, hipStream_t st);
 // One wave that returns when *cnt >= target (or when *done != 0, or after a bounded number of polls, which sets *timeout):

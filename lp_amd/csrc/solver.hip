@@ -465,8 +465,10 @@ static void plan_adat(lpipm_ctx* c, int count) {
     c->ws_slabs = gemm_streamk_slabs(c->ntiles, c->npa / BK, c->adat_nwg);
     // A.D.A^T as (tile, chunk) units: every chunk sum goes through its own slab (ntiles x cpt slabs of 128 KiB per LP:
     // 0.55 GB at C3, 38 MB per member at C4) -- up to 4 GiB per LP, beyond that (m = 16384: 34 GB) the round-2 kernel
+    // -- and only up to ADAT_UNITS_MAX_CPT chunks per tile (npa up to ~256000 columns): longer rows take the round-2 kernel too
     c->cpt = adat_units_cpt(c->npa);
-    c->units = c->units_env != 0 && (size_t)c->ntiles * c->cpt * TILE * TILE * sizeof(double) <= ((size_t)4 << 30) &&
+    const bool units_fit = c->cpt <= ADAT_UNITS_MAX_CPT;
+    c->units = c->units_env != 0 && units_fit && (size_t)c->ntiles * c->cpt * TILE * TILE * sizeof(double) <= ((size_t)4 << 30) &&
                (count > 1 || c->units_env == 2 || c->cpt == 1 || c->ntiles <= 16 || c->ntiles * c->cpt >= 256);
     // (tiny single LPs -- up to 16 tiles -- : one launch and one memset less, 0.042 vs 0.045 ms at 512x1024;
     //  a single LP with few tiles AND several chunks -- 1000x5000: 36 tiles x 3 -- keeps the round-2 kernel: one workgroup per
@@ -475,7 +477,7 @@ static void plan_adat(lpipm_ctx* c, int count) {
     //  2048x16384 1.30 vs 1.60 -- carries no spill and leaves out the blocks above the diagonal of the diagonal tiles)
     // one LP split by columns over ranks: the units kernel signals M's column groups one by one, and each group's cross-rank
     // sum runs behind the rest of the launch (enqueue_head); its slabs may take up to 32 GiB there (C5: 17 GB per rank)
-    if (count == 1 && c->world > 1 && c->units_env != 0 && nt <= 64 * POTRF_OUTER &&
+    if (count == 1 && c->world > 1 && c->units_env != 0 && units_fit && nt <= 64 * POTRF_OUTER &&
         (size_t)c->ntiles * c->cpt * TILE * TILE * sizeof(double) <= ((size_t)32 << 30)) c->units = true;
     // a single LP: one chunk per unit (parallelism, and column groups that complete while the launch runs); a lockstep
     // batch: two chunks per unit -- whole tiles (one unit = all chunks, its own workgroup adds its slabs) leave the last of
