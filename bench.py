@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- IPM iterations/sec on the headline workload of BASELINE.json (dense 4096x8192 fp64 LP).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`)
 
 A "step" is one complete `InteriorPoint::solve` (mod.rs:199-240) of the rank's LP: the whole hot path
@@ -11,22 +11,31 @@ Weak scaling: every rank owns ONE independent LP of the same shape (seed = rank)
 one per GPU with no data-path collective -- and the timed region ends with the single RCCL
 all-gather of the solutions.  value = IPM iterations of all ranks / max-over-ranks wall time.
 
+A plain run does only what `value` needs: it sets up, runs the W warm-up and K timed steps, writes the outputs of the
+last timed step if --dump-outputs is given and prints the JSON line (with the `roofline` object, whose figures come from
+the events recorded inside the timed region).  On the default workload --dump-outputs also runs the short c2 and c4
+steps, for their outputs alone.  --full adds, after the timed region, everything else the benchmark
+measures or checks: the per-phase breakdown, the unbracketed pass, the distance to the planted optimum, the CPU baselines,
+the c4 parity check and, on the default workload, the c2 and c4 measurements.  The timed steps are the same in both.
+
 `--workload c2` (optional): BASELINE config 2 -- one 512x1024 LP per GPU ("GEMV-bound, HBM roofline check"), same
 protocol; its `roofline` object is the HBM one: the passes over A (GEMV-N / GEMV-T), algorithmic bytes 8mn per pass /
 the average pass duration from HIP events on the solver's stream inside the timed region, against 8 TB/s.
 `--workload c4` (optional): BASELINE config 4 -- 32 independent 1024x2048 LPs per GPU as one lockstep batch with
-resident inputs, value in LP/s; same timing protocol; its `roofline` is the whole-solve MFMA fraction (+ the batched
-A.D.A^T launch's own); exits non-zero if a member lies outside the oracle's own envelope on that LP widened by 1e-6 or
-takes an iteration count the oracle never produced (tests/golden/make_envelopes.py).
-The DEFAULT run (no --workload) measures the headline C3 and then, briefly, c2 and c4 as well: they are appended to the
-one JSON line as the objects "c2" and "c4" (`value` stays the headline's); --only-headline skips them.
+resident inputs, value in LP/s; same timing protocol; its `roofline` is the whole-solve MFMA fraction (+ with --full the
+batched A.D.A^T launch's own); with --full it exits non-zero if a member lies outside the oracle's own envelope on that
+LP widened by 1e-6 or takes an iteration count the oracle never produced (tests/golden/make_envelopes.py).
+With --full the default workload (no --workload) measures the headline C3 and then, briefly, c2 and c4 as well: they are
+appended to the one JSON line as the objects "c2" and "c4" (`value` stays the headline's); --only-headline skips them.
 
-Extra objects on the JSON line:
+Objects on the JSON line besides the headline figures:
   roofline     : the dominant kernel (A.D.A^T, MFMA-bound): algorithmic flops m(m+1)n per launch /
                  its average launch duration from HIP events recorded on the solver's own stream
                  INSIDE the timed region (2 events per iteration, bracketing that kernel and its fix-up);
-                 peak = 78.6 TFLOP/s dense fp64 MFMA.  The per-phase breakdown comes from one extra,
-                 untimed solve with every phase bracketed.
+                 peak = 78.6 TFLOP/s dense fp64 MFMA.
+  --full only:
+  phase_ms_per_iteration : from one extra, untimed solve with every phase bracketed.
+  unbracketed  : the timed steps once more with no HIP event recorded inside a solve (`value` stays the bracketed run).
   cpu_baseline : rank 0, N == 1 only: the single-threaded C restatement of the reference (oracle/, kind "port") timed
                  on this box's host for the first TWO IPM iterations of the same LP (two runs, max_iter 1 and 2: the
                  second iteration's time is the difference; the op count does not depend on the iterate), plus
@@ -38,8 +47,9 @@ Extra objects on the JSON line:
 
 --dump-outputs DIR: after the run, rank 0 writes what the timed path returned in its LAST timed step as DIR/<name>.npy
 (float64): x (the solution, or the gathered block of all ranks), fun, iterations, status; c4: one row / entry per member.
-The default run adds the same for its c2 / c4 measurements as c2_<name> / c4_<name>.  The inputs are seeded (synth.planted_lp),
-so two builds run with the same arguments can be compared output by output.
+The default workload adds the same for its c2 / c4 steps as c2_<name> / c4_<name> (with or without --full; not with
+--only-headline).  The inputs are seeded (synth.planted_lp), so two builds run with the same arguments can be compared
+output by output.
 """
 from __future__ import annotations
 
@@ -140,11 +150,17 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default 5; c2: 200)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
-                    help="write the outputs of the last timed step as DIR/<name>.npy (float64)")
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64); on the default workload also "
+                         "those of the short c2 / c4 steps")
     ap.add_argument("--m", type=int, default=4096)
     ap.add_argument("--n", type=int, default=8192)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--only-headline", action="store_true", help="skip the short c2 / c4 measurements appended to the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check everything beyond the headline figure: per-phase "
+                         "breakdown, unbracketed pass, planted-optimum distance, CPU baselines, c4 parity, and on the "
+                         "default workload the c2 / c4 measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--only-headline", action="store_true",
+                    help="with --full: skip the short c2 / c4 measurements appended to the default workload")
     ap.add_argument("--workload", choices=("c3", "c2", "c4"), default="c3",
                     help="c3 (default, the BASELINE metric): one 4096x8192 LP per GPU; c2: one 512x1024 LP per GPU (HBM "
                          "roofline on the GEMV passes); c4: a shard of 32 independent 1024x2048 LPs per GPU as one lockstep "
@@ -192,19 +208,21 @@ def main():
     if args.workload == "c4":
         return bench_c4(args, rank, local_rank, world, dist, dev, np, torch, lp_amd, synth)
     env = (rank, local_rank, world, dist, dev, np, torch, lp_amd, synth)
-    out, outputs = measure_single(args.m, args.n, args.steps, args.warmup, args.workload == "c2",
-                                  world == 1 and not args.no_cpu_baseline, *env)
+    out, outputs = measure_single(args.m, args.n, args.steps, args.warmup, args.workload == "c2", args.full,
+                                  args.full and world == 1 and not args.no_cpu_baseline, *env)
     nbad = 0
-    if args.workload == "c3" and (args.m, args.n) == (4096, 8192) and not args.only_headline:
+    if ((args.full or args.dump_outputs is not None) and args.workload == "c3" and (args.m, args.n) == (4096, 8192)
+            and not args.only_headline):
         # The other two single-node configs of BASELINE.json, measured in the SAME run (short; after the headline's timed
-        # region), so that the driver's default invocation records them too: c2 = config 2 (one 512x1024 LP per GPU, HBM
-        # roofline of the passes over A), c4 = config 4 (32 LPs of 1024x2048 per GPU as one lockstep batch, LP/s, whole-solve
-        # MFMA fraction, parity of every member against the oracle's envelope).  `value` above stays the headline's.
-        c2, c2_outputs = measure_single(512, 1024, 100, 5, True, False, *env)
-        c4, nbad, c4_outputs = measure_c4(3, 1, *env)
+        # region), so that a --full run records them too: c2 = config 2 (one 512x1024 LP per GPU, HBM roofline of the
+        # passes over A), c4 = config 4 (32 LPs of 1024x2048 per GPU as one lockstep batch, LP/s, whole-solve MFMA
+        # fraction, parity of every member against the oracle's envelope).  `value` above stays the headline's.
+        # --dump-outputs without --full runs their steps too, for the c2_ / c4_ outputs alone (no object on the line).
+        c2, c2_outputs = measure_single(512, 1024, 100, 5, True, args.full, False, *env)
+        c4, nbad, c4_outputs = measure_c4(3, 1, args.full, *env)
         outputs.update({"c2_" + k: v for k, v in c2_outputs.items()})
         outputs.update({"c4_" + k: v for k, v in c4_outputs.items()})
-        if rank == 0:
+        if rank == 0 and args.full:
             keep = ("metric", "value", "unit", "ms_per_step", "config", "roofline")
             out["c2"] = {k: c2[k] for k in keep}
             out["c2"]["phase_ms_per_iteration"] = c2["phase_ms_per_iteration"]
@@ -224,9 +242,11 @@ def main():
         sys.exit(1)
 
 
-def measure_single(m, n, steps, warmup, c2, want_cpu_baseline, rank, local_rank, world, dist, dev, np, torch, lp_amd, synth):
-    """One independent m x n LP per GPU (seed = rank): the headline protocol (C3) and BASELINE config 2.  Returns (the result
-    dict on rank 0 (None elsewhere), the outputs of the last timed step)."""
+def measure_single(m, n, steps, warmup, c2, full, want_cpu_baseline, rank, local_rank, world, dist, dev, np, torch, lp_amd,
+                   synth):
+    """One independent m x n LP per GPU (seed = rank): the headline protocol (C3) and BASELINE config 2.  full: the untimed
+    phase breakdown, unbracketed pass and planted-optimum distance after the timed region.  Returns (the result dict on
+    rank 0 (None elsewhere), the outputs of the last timed step)."""
     A, b, c, xstar = synth.planted_lp(rank, m, n)        # one independent LP per rank (seed = rank)
     ctx = lp_amd.Context(local_rank)
     ctx.upload_arrays(A, b, c)                           # one-time H2D, outside the timed region
@@ -257,7 +277,6 @@ def measure_single(m, n, steps, warmup, c2, want_cpu_baseline, rank, local_rank,
     adat_launches = 0
     gemv_ms = 0.0
     gemv_passes = 0
-    phase = {k: 0.0 for k in ("adat_ms", "potrf_ms", "trsv_ms", "gemv_ms", "vec_ms", "total_ms")}
     iters_local = 0
     barrier()
     t0 = time.perf_counter()
@@ -273,18 +292,18 @@ def measure_single(m, n, steps, warmup, c2, want_cpu_baseline, rank, local_rank,
     dt = time.perf_counter() - t0
     # what the last timed step returned, before the solves below overwrite x_dev
     outputs = {"x": (gathered if dist is not None else x_dev).cpu().numpy(), "fun": fun, "iterations": its, "status": 0}
-    # per-phase breakdown: one more solve with every phase bracketed by events, OUTSIDE the timed region
-    ctx.set_profiling(1)
-    ctx.solve_raw(opts, x_dev_ptr=x_dev.data_ptr())
-    pt = ctx.phase_times()
-    phase = {k: pt[k] for k in phase}
-    phase_iters = max(int(pt["iterations"]), 1)
-    ctx.set_profiling(0)
-    # config 2 is a chain of ~30 launches of 5-30 us per iteration: the event brackets of its phase split cost a visible share
-    # of it (at C3 the two events around A.D.A^T cost ~0.2 %).  The same steps once more with no event recorded at all
-    # (every rank runs them: the step holds the gather); `value` stays the bracketed measurement above
-    unbracketed = None
-    if True:
+    phase = unbracketed = err = None
+    if full:
+        # per-phase breakdown: one more solve with every phase bracketed by events, OUTSIDE the timed region
+        ctx.set_profiling(1)
+        ctx.solve_raw(opts, x_dev_ptr=x_dev.data_ptr())
+        pt = ctx.phase_times()
+        phase = {k: pt[k] for k in ("adat_ms", "potrf_ms", "trsv_ms", "gemv_ms", "vec_ms", "total_ms")}
+        phase_iters = max(int(pt["iterations"]), 1)
+        ctx.set_profiling(0)
+        # config 2 is a chain of ~30 launches of 5-30 us per iteration: the event brackets of its phase split cost a visible
+        # share of it (at C3 the two events around A.D.A^T cost ~0.2 %).  The same steps once more with no event recorded at
+        # all (every rank runs them: the step holds the gather); `value` stays the bracketed measurement above
         barrier()
         t1 = time.perf_counter()
         its_u = 0
@@ -295,9 +314,8 @@ def measure_single(m, n, steps, warmup, c2, want_cpu_baseline, rank, local_rank,
         unbracketed = {"value": its_u / dt_u, "unit": "iterations/s (this rank)", "ms_per_step": dt_u * 1e3 / steps,
                        "ms_per_iteration": dt_u * 1e3 / max(its_u, 1),
                        "note": "the same steps with profiling off: no HIP event recorded inside a solve"}
-
-    # parity guard on what was just timed: the planted vertex is the known answer
-    err = float((x_dev.cpu().numpy() - xstar).__abs__().max())
+        # parity guard on what was just solved: the planted vertex is the known answer
+        err = float((x_dev.cpu().numpy() - xstar).__abs__().max())
     ctx.close()
 
     if dist is not None:
@@ -364,11 +382,13 @@ def measure_single(m, n, steps, warmup, c2, want_cpu_baseline, rank, local_rank,
         "data": "synthetic",
         "config": {"workload": f"{'C3' if (m, n) == (4096, 8192) else ('C2' if (m, n) == (512, 1024) else 'custom')}: random dense planted LP m={m} n={n} fp64, one independent LP per GPU "
                                f"(seed = rank), reference default options, A resident in HBM",
-                   "m": m, "n": n, "iterations_per_solve": iters_local / steps,
-                   "max_abs_err_vs_planted_optimum": err},
+                   "m": m, "n": n, "iterations_per_solve": iters_local / steps},
         "roofline": roofline,
-        "phase_ms_per_iteration": {k: v / phase_iters for k, v in phase.items()},
     }
+    if err is not None:
+        out["config"]["max_abs_err_vs_planted_optimum"] = err
+    if phase is not None:
+        out["phase_ms_per_iteration"] = {k: v / phase_iters for k, v in phase.items()}
     if unbracketed is not None:
         out["unbracketed"] = unbracketed
     if want_cpu_baseline:
@@ -376,15 +396,15 @@ def measure_single(m, n, steps, warmup, c2, want_cpu_baseline, rank, local_rank,
     return out, outputs
 
 
-def measure_c4(steps, warmup, rank, local_rank, world, dist, dev, np, torch, lp_amd, synth):
+def measure_c4(steps, warmup, full, rank, local_rank, world, dist, dev, np, torch, lp_amd, synth):
     """BASELINE config 4: 32 independent 1024x2048 LPs per GPU (256 over 8), solved as ONE lockstep batch with the inputs
     resident in HBM; every x / tau goes device to device into the rank's packed block and ONE all-gather (RCCL) of those
     blocks ends the step.  value = LPs of all ranks / max-over-ranks wall time.  The members are the seeds of the
-    committed oracle fixture (tests/golden/c4_members.npz): after the timed region every member of this rank is compared
-    with the oracle's OWN ENVELOPE on that LP (component-wise [min, max] of the oracle's x over its run on the LP as
-    generated and four runs with permuted columns) widened by 1e-6, and its iteration count with the counts the oracle
-    produced.  Returns (result dict for rank 0, number of members of ANY rank that fail that check, the outputs of the last
-    timed step)."""
+    committed oracle fixture (tests/golden/c4_members.npz): with `full`, after the timed region every member of this rank
+    is compared with the oracle's OWN ENVELOPE on that LP (component-wise [min, max] of the oracle's x over its run on the
+    LP as generated and four runs with permuted columns) widened by 1e-6, and its iteration count with the counts the
+    oracle produced.  Returns (result dict for rank 0, number of members of ANY rank that fail that check (0 without
+    `full`), the outputs of the last timed step)."""
     per_rank, m, n = 32, 1024, 2048
     seeds = [rank * per_rank + s for s in range(per_rank)]
     probs = [synth.planted_lp(s, m, n) for s in seeds]
@@ -421,15 +441,54 @@ def measure_c4(steps, warmup, rank, local_rank, world, dist, dev, np, torch, lp_
     outputs = {"x": gathered.cpu().numpy() if dist is not None else x_host,
                "fun": [np.nan if r[1] is None else r[1] for r in res],
                "iterations": [r[2] for r in res], "status": [r[0] for r in res]}
-    err = max(float(np.abs(x_host[k] - p[3]).max()) for k, p in enumerate(probs))
-    # per-phase device times of one more lockstep solve (HIP events on the solver's stream), outside the timed region
-    ctx.set_profiling(1)
-    ctx.solve_lockstep_device(opts, xs.data_ptr(), n)
-    pt = ctx.phase_times()
-    ctx.set_profiling(0)
-    batch_its = max(int(pt["iterations"]), 1)
-    phase = {k: pt[k] / batch_its for k in ("adat_ms", "potrf_ms", "trsv_ms", "gemv_ms", "vec_ms", "total_ms")}
-    # parity against the committed oracle vectors of exactly these members
+    err = phase = parity = None
+    nbad = 0
+    if full:
+        err = max(float(np.abs(x_host[k] - p[3]).max()) for k, p in enumerate(probs))
+        # per-phase device times of one more lockstep solve (HIP events on the solver's stream), outside the timed region
+        ctx.set_profiling(1)
+        ctx.solve_lockstep_device(opts, xs.data_ptr(), n)
+        pt = ctx.phase_times()
+        ctx.set_profiling(0)
+        batch_its = max(int(pt["iterations"]), 1)
+        phase = {k: pt[k] / batch_its for k in ("adat_ms", "potrf_ms", "trsv_ms", "gemv_ms", "vec_ms", "total_ms")}
+        parity, nbad = c4_parity(x_host, res, seeds, m, n, np)
+    if dist is not None:
+        t = torch.tensor([dt, float(nbad)], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt, nbad_any = float(t[0]), int(t[1])
+    else:
+        nbad_any = nbad
+    ctx.close()
+    lps = world * per_rank * steps / dt
+    it_per_lp = its / per_rank
+    # whole-solve MFMA fraction: the flops the path HAS to do in matrix form (A.D.A^T lower triangle + Cholesky) per LP-iteration
+    flop_it = float(m) * (m + 1) * n + float(m) ** 3 / 3.0
+    whole = lps / world * it_per_lp * flop_it / 1e12
+    out = {
+        "metric": "independent LPs solved per second, batch of 1024x2048 fp64 LPs sharded 32 per GPU", "value": lps,
+        "unit": "LP/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": dt * 1e3 / steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"C4: {world * per_rank} independent planted LPs m={m} n={n} fp64, {per_rank} per GPU as one lockstep batch, "
+                               "inputs resident in HBM, solutions device to device into the packed block, one all-gather",
+                   "iterations_per_lp": it_per_lp},
+        "roofline": {"kernel": "whole solve of the shard (A.D.A^T + Cholesky flops of every LP-iteration / wall time per GPU)",
+                     "bound": "mfma", "achieved": whole, "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s",
+                     "frac": whole / PEAK_FP64_MFMA_TFLOPS, "traffic": None}}
+    if full:
+        adat_tf = per_rank * float(m) * (m + 1) * n / (phase["adat_ms"] * 1e-3) / 1e12 if phase["adat_ms"] > 0 else 0.0
+        out["config"]["max_abs_err_vs_planted_optimum"] = err
+        out["roofline"]["kernel"] += ("; adat_* = the batched A.D.A^T launch alone (32 LPs per launch, HIP events on the "
+                                      "solver's stream)")
+        out["roofline"].update(adat_achieved=adat_tf, adat_frac=adat_tf / PEAK_FP64_MFMA_TFLOPS, adat_launch_ms=phase["adat_ms"])
+        out["phase_ms_per_lockstep_iteration"] = phase
+        out["parity_rank0"] = parity
+        out["parity_failed_members_any_rank"] = nbad_any
+    return out, nbad_any, outputs
+
+
+def c4_parity(x_host, res, seeds, m, n, np):
+    """The members of this rank against the committed oracle fixture (measure_c4).  -> (parity record, failing members)."""
     parity = {"checked": False}
     gold = os.path.join(ROOT, "tests", "golden", "c4_members.npz")
     nbad = 0
@@ -458,38 +517,12 @@ def measure_c4(steps, warmup, rank, local_rank, world, dist, dev, np, torch, lp_
                       "largest_excess_over_oracle_envelope": float(excess.max()),
                       "members_outside_envelope_plus_1e-6_parity_unpinned": unpinned,
                       "failed_members": bad}
-    if dist is not None:
-        t = torch.tensor([dt, float(nbad)], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt, nbad_any = float(t[0]), int(t[1])
-    else:
-        nbad_any = nbad
-    ctx.close()
-    lps = world * per_rank * steps / dt
-    it_per_lp = its / per_rank
-    # whole-solve MFMA fraction: the flops the path HAS to do in matrix form (A.D.A^T lower triangle + Cholesky) per LP-iteration
-    flop_it = float(m) * (m + 1) * n + float(m) ** 3 / 3.0
-    whole = lps / world * it_per_lp * flop_it / 1e12
-    adat_tf = per_rank * float(m) * (m + 1) * n / (phase["adat_ms"] * 1e-3) / 1e12 if phase["adat_ms"] > 0 else 0.0
-    out = {
-        "metric": "independent LPs solved per second, batch of 1024x2048 fp64 LPs sharded 32 per GPU", "value": lps,
-        "unit": "LP/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": dt * 1e3 / steps,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"C4: {world * per_rank} independent planted LPs m={m} n={n} fp64, {per_rank} per GPU as one lockstep batch, "
-                               "inputs resident in HBM, solutions device to device into the packed block, one all-gather",
-                   "iterations_per_lp": it_per_lp, "max_abs_err_vs_planted_optimum": err},
-        "roofline": {"kernel": "whole solve of the shard (A.D.A^T + Cholesky flops of every LP-iteration / wall time per GPU); "
-                               "adat_* = the batched A.D.A^T launch alone (32 LPs per launch, HIP events on the solver's stream)",
-                     "bound": "mfma", "achieved": whole, "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s",
-                     "frac": whole / PEAK_FP64_MFMA_TFLOPS, "traffic": None,
-                     "adat_achieved": adat_tf, "adat_frac": adat_tf / PEAK_FP64_MFMA_TFLOPS, "adat_launch_ms": phase["adat_ms"]},
-        "phase_ms_per_lockstep_iteration": phase,
-        "parity_rank0": parity, "parity_failed_members_any_rank": nbad_any}
-    return out, nbad_any, outputs
+    return parity, nbad
 
 
 def bench_c4(args, rank, local_rank, world, dist, dev, np, torch, lp_amd, synth):
-    out, nbad, outputs = measure_c4(args.steps, args.warmup, rank, local_rank, world, dist, dev, np, torch, lp_amd, synth)
+    out, nbad, outputs = measure_c4(args.steps, args.warmup, args.full, rank, local_rank, world, dist, dev, np, torch, lp_amd,
+                                    synth)
     if rank == 0:
         dump_outputs(args.dump_outputs, outputs, np)
         emit(out)

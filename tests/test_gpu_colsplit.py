@@ -142,22 +142,27 @@ def test_c5_two_ranks_on_one_gpu_at_c3_size_matches_golden(built):
 
 
 def test_bench_distributed_code_path_on_one_rank(built):
-    """bench.py's N > 1 code path (init_process_group nccl = RCCL, barrier, all-gather, max-over-ranks) on ONE rank."""
+    """bench.py's N > 1 code path (init_process_group nccl = RCCL, barrier, all-gather, max-over-ranks) on ONE rank, with
+    --full: the untimed passes after the timed region (phase breakdown, unbracketed steps, c4 parity) run under it too."""
     import json
     import subprocess
     env = dict(os.environ, LPIPM_BENCH_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(29500 + (os.getpid() * 13) % 2000))
-    for extra in (["--m", "512", "--n", "1024", "--steps", "3", "--no-cpu-baseline"], ["--workload", "c4", "--steps", "1"]):
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--warmup", "1"] + extra,
+    for extra, full_keys in ((["--m", "512", "--n", "1024", "--steps", "3", "--no-cpu-baseline"],
+                              ("phase_ms_per_iteration", "unbracketed")),
+                             (["--workload", "c4", "--steps", "1"], ("phase_ms_per_lockstep_iteration", "parity_rank0"))):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--warmup", "1", "--full"] + extra,
                              capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
         assert out.returncode == 0, out.stderr[-2000:]
         r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
         assert r["n_gpus"] == 1 and r["value"] > 0
+        assert all(k in r for k in full_keys), sorted(r)
 
 
 def test_bench_steps_and_dumped_outputs(built, tmp_path):
     """bench.py --steps is the number of timed steps (c2 has its own default, not an override) and --dump-outputs writes
-    what the last timed step returned: c2's LP is the seed-0 512x1024 one of the committed oracle fixture."""
+    what the last timed step returned: c2's LP is the seed-0 512x1024 one of the committed oracle fixture.  Without --full
+    the run measures nothing after its timed region."""
     import json
     import subprocess
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c2", "--steps", "5",
@@ -166,12 +171,37 @@ def test_bench_steps_and_dumped_outputs(built, tmp_path):
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert r["steps"] == 5 and r["ms_per_step"] > 0
+    assert not {"phase_ms_per_iteration", "unbracketed", "cpu_baseline", "c2", "c4"} & set(r), sorted(r)
+    assert "max_abs_err_vs_planted_optimum" not in r["config"]
     got = {k: np.load(tmp_path / f"{k}.npy") for k in ("x", "fun", "iterations", "status")}
     assert all(a.dtype == np.float64 for a in got.values())
     g = np.load(os.path.join(ROOT, "tests", "golden", "planted_512x1024_s0.npz"))
     assert got["status"] == 0 and got["iterations"] == int(g["iterations"])
     assert got["x"].shape == (1024,) and np.abs(got["x"] - g["x_slack"]).max() <= 1e-6
     assert abs(float(got["fun"]) - float(g["fun"])) <= 1e-6 * max(1.0, abs(float(g["fun"])))
+
+
+def test_bench_plain_default_run_dumps_every_output(built, tmp_path):
+    """A plain run of the default workload with --dump-outputs writes the headline's outputs and those of the short c2 / c4
+    steps, as a --full run does, while its line carries no object of the --full run."""
+    import json
+    import subprocess
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert r["steps"] == 1 and r["ms_per_step"] > 0
+    assert not {"phase_ms_per_iteration", "unbracketed", "cpu_baseline", "c2", "c4"} & set(r), sorted(r)
+    names = ("x", "fun", "iterations", "status")
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(f"{p}{k}.npy" for p in ("", "c2_", "c4_") for k in names)
+    got = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["x"].shape == (8192,) and got["c2_x"].shape == (1024,) and got["c4_x"].shape == (32, 2048)
+    assert got["status"] == 0 and got["c2_status"] == 0 and (got["c4_status"] == 0).all()
+    g3 = np.load(os.path.join(ROOT, "tests", "golden", "planted_4096x8192_s0.npz"))
+    g2 = np.load(os.path.join(ROOT, "tests", "golden", "planted_512x1024_s0.npz"))
+    assert int(got["iterations"]) in set(int(v) for v in g3["iterations_all"])
+    assert got["c2_iterations"] == int(g2["iterations"])
 
 
 def _worker_two_ways(rank, world, port, q, seed, m, n):
