@@ -737,6 +737,16 @@ static hipError_t ctx_gemv_t(lpipm_ctx* c, int nrhs, const double* V, const Batc
     if (e != hipSuccess) return e;
     return launch_slack_t(c->ns, c->nx, nrhs, c->nsplit, V, c->mp, c->ATpart, c->np, c->st, bt);
 }
+// both in one read of A: chunk slabs of A.w into AxPart (gemv_dual_chunks(npa) of them), row-split slabs of A^T.v into ATpart
+static hipError_t ctx_gemv_dual(lpipm_ctx* c, const double* W, const double* V, double* AxPart, const Batch& bt) {
+    ++c->gemv_passes;
+    hipError_t e = c->shared_a ? launch_gemv_dual_shared(c->A, c->npa, c->mp, c->npa, W, V, AxPart, c->ATpart, c->np, c->st, bt)
+                               : launch_gemv_dual(c->A, c->npa, c->mp, c->npa, W, V, AxPart, c->ATpart, c->np, c->st, bt);
+    if (e != hipSuccess) return e;
+    e = launch_slack_n(c->ns, c->nx, 1, W, c->np, AxPart, c->mp, c->st, bt);          // into chunk slab 0
+    if (e != hipSuccess) return e;
+    return launch_slack_t(c->ns, c->nx, 1, c->nsplit, V, c->mp, c->ATpart, c->np, c->st, bt);
+}
 
 // M = A . diag(dinv) . A^T, lower tiles (newton_equations.rs:54-57); a second copy of it goes to M0 (the matrix the
 // refined Cholesky solves take their residuals against: M itself is factorised in place)
@@ -809,12 +819,8 @@ static int enqueue_residuals(lpipm_ctx* c, int is_init, int ip_next, double tol)
     // A.x and A^T.y at the current point (residual.rs:23,25)
     XRank xr{xrank_fn, c};
     if (!(c->colsplit && c->world > 1)) {       // both products in one read of A
-        ++c->gemv_passes;
         v.ax_chunks = gemv_dual_chunks(c->npa);
-        if (c->shared_a) LP_HIP(launch_gemv_dual_shared(c->A, c->npa, c->mp, c->npa, v.x, v.y, v.Ax, c->ATpart, c->np, c->st, c->bt));
-        else             LP_HIP(launch_gemv_dual(c->A, c->npa, c->mp, c->npa, v.x, v.y, v.Ax, c->ATpart, c->np, c->st, c->bt));
-        LP_HIP(launch_slack_n(c->ns, c->nx, 1, v.x, c->np, v.Ax, c->mp, c->st, c->bt));          // into chunk slab 0
-        LP_HIP(launch_slack_t(c->ns, c->nx, 1, c->nsplit, v.y, c->mp, c->ATpart, c->np, c->st, c->bt));
+        LP_HIP(ctx_gemv_dual(c, v.x, v.y, v.Ax, c->bt));
     } else {
         v.ax_chunks = 1;
         LP_HIP(ctx_gemv_n(c, 1, v.x, nullptr, nullptr, v.Ax, c->bt));
@@ -1888,9 +1894,7 @@ extern "C" int lpipm_k_gemv_dual(lpipm_ctx* c, const double* w, const double* v,
     LP_HIP(hipMemcpyAsync(va.R, v, c->m * sizeof(double), hipMemcpyHostToDevice, c->st));
     const int nch = gemv_dual_chunks(c->npa);
     LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int {
-        LP_HIP(launch_gemv_dual(c->A, c->npa, c->mp, c->npa, va.W, va.R, va.Ax, c->ATpart, c->np, c->st));
-        LP_HIP(launch_slack_n(c->ns, c->nx, 1, va.W, c->np, va.Ax, c->mp, c->st));
-        LP_HIP(launch_slack_t(c->ns, c->nx, 1, c->nsplit, va.R, c->mp, c->ATpart, c->np, c->st));
+        LP_HIP(ctx_gemv_dual(c, va.W, va.R, va.Ax, Batch{}));
         return LPIPM_OK;
     }));
     // the consumers' folds, on the host: chunk slabs of A.w, row-block slabs of A^T.v, in index order

@@ -42,6 +42,27 @@ def planted_scenarios(seed: int, m: int, n: int, count: int):
     return A, bs, cs, xs
 
 
+def spread_scenarios(seed: int, m: int, n: int, spreads):
+    """planted_scenarios with magnitudes spread over decades: scenario i draws x*_i on its basis and z*_i off it as
+    10^(s_i U(-1, 1)) with s_i = spreads[i] (s = 0: all ones), so the members of one batch on one A need very different
+    iteration counts (256 x 1100: 3-4 iterations at s = 0, about 30 at s = 3; the CPU oracle's counts).  The optimum x*_i
+    stays known and strictly complementary, but the distance a solver ends from it grows with s.
+    -> (A[m,n], bs[len(spreads)][m], cs[len(spreads)][n], xstars[len(spreads)][n])."""
+    if m > n:
+        raise ValueError("spread_scenarios needs m <= n")
+    A = planted_lp(seed, m, n)[0]
+    bs, cs, xs = [], [], []
+    for i, s in enumerate(spreads):
+        rng = np.random.default_rng([seed, m, n, i, int(round(1000 * float(s)))])
+        basis = rng.permutation(n)[:m]
+        x, z = np.zeros(n), 10.0 ** (float(s) * rng.uniform(-1.0, 1.0, n))
+        x[basis] = 10.0 ** (float(s) * rng.uniform(-1.0, 1.0, m))
+        z[basis] = 0.0
+        y = rng.standard_normal(m)
+        bs.append(A @ x); cs.append(A.T @ y + z); xs.append(x)
+    return A, bs, cs, xs
+
+
 class _Rng:
     """splitmix64 -> xoshiro256**, Box-Muller; scalar Python, for small cross-checks only."""
 

@@ -107,6 +107,27 @@ def test_synth_generator_c_vs_python_mirror(built):
     assert not np.array_equal(A3, synth.planted_lp(0, 5, 9)[0])
 
 
+def test_synth_spread_scenarios_are_planted(built):
+    """spread_scenarios: planted_lp's A, each member feasible at its x*, strictly complementary (z* = 0 exactly on the basis),
+    magnitudes inside 10^(+-s), and a member does not depend on the others' spreads."""
+    from lp_amd import synth
+    m, n, spreads = 12, 30, [0.0, 1.0, 3.0]
+    A, bs, cs, xs = synth.spread_scenarios(5, m, n, spreads)
+    assert np.array_equal(A, synth.planted_lp(5, m, n)[0])
+    for s, b, c, x in zip(spreads, bs, cs, xs):
+        basis = x > 0
+        assert basis.sum() == m and np.array_equal(A @ x, b)
+        y = np.linalg.lstsq(A[:, basis].T, c[basis], rcond=None)[0]           # z* = 0 on the basis determines y*
+        z = c - A.T @ y
+        assert np.abs(z[basis]).max() < 1e-9 and z[~basis].min() > 0.5 * 10.0 ** -s
+        assert 10.0 ** -s <= x[basis].min() and x[basis].max() <= 10.0 ** s
+    assert np.ptp(xs[0][xs[0] > 0]) == 0.0 and np.ptp(xs[2][xs[2] > 0]) > 10.0
+    _, bs2, cs2, _ = synth.spread_scenarios(5, m, n, [2.0, 1.0])
+    assert np.array_equal(bs2[1], bs[1]) and np.array_equal(cs2[1], cs[1])
+    with pytest.raises(ValueError):
+        synth.spread_scenarios(5, 9, 5, [0.0])
+
+
 def test_no_gpu_means_loud_failure(built):
     """The product path must fail loudly when there is no usable device -- never fall back."""
     import lp_amd as lp
