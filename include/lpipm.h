@@ -252,7 +252,11 @@ int lpipm_k_gemv_t(lpipm_ctx* ctx, int nrhs, const double* V, double* U, int rep
  * (feasible_point.rs:110-152: residuals, normal equations + factor, Rhat::predictor / corrector, Delta::compute twice,
  * update_gamma), the step length (mod.rs:216-221, feasible_point.rs:53-72) and do_step (:76-106).
  * In/out: x[n], y[m], z[n], *tau, *kappa.  Out: the corrector's direction d_x[n], d_y[m], d_z[n],
- * d_tk = {d_tau, d_kappa}, *alpha, *info (pivot failure as lpipm_k_potrf).  Differential tests of the vector stage. */
+ * d_tk = {d_tau, d_kappa}, *alpha, *info (pivot failure as lpipm_k_potrf).  Differential tests of the vector stage.
+ * On a column-split context (lpipm_upload_nsplit) every rank must call it together: x, z, d_x, d_z are the rank's
+ * slices of n_local elements; y[m], tau, kappa and every other output are replicated, bit-identical on all ranks.
+ * A group wait of the pipelined reduction of M that gave up is reported as in lpipm_solve (LPIPM_ERR_HIP).
+ * A lockstep batch is refused (LPIPM_ERR_UNSUPPORTED). */
 int lpipm_k_iteration(lpipm_ctx* ctx, const lpipm_opts* opts, int ip, double* x, double* y, double* z, double* tau,
                       double* kappa, double* d_x, double* d_y, double* d_z, double* d_tk, double* alpha_out,
                       int32_t* info_out);

@@ -471,7 +471,8 @@ static void plan_adat(lpipm_ctx* c, int count) {
     c->units = c->units_env != 0 && units_fit && (size_t)c->ntiles * c->cpt * TILE * TILE * sizeof(double) <= ((size_t)4 << 30) &&
                (count > 1 || c->units_env == 2 || c->cpt == 1 || c->ntiles <= 16 || c->ntiles * c->cpt >= 256);
     // (tiny single LPs -- up to 16 tiles -- : one launch and one memset less, 0.042 vs 0.045 ms at 512x1024;
-    //  a single LP with few tiles AND several chunks -- 1000x5000: 36 tiles x 3 -- keeps the round-2 kernel: one workgroup per
+    //  a single LP with few tiles AND several chunks under 256 units -- 700x1500: 21 tiles x 6, 1009x1100: 36 tiles x 5; not
+    //  1000x5000, whose 36 tiles x 11 chunks are 396 units -- keeps the round-2 kernel: one workgroup per
     //  tile adding the slabs at the end of a launch that never filled the chip costs more than the 16-way fix-up launch,
     //  0.196 vs 0.151 ms; everywhere else the units kernel is level or ahead -- 4096x8192 2.206 vs 2.22 ms inside a solve,
     //  2048x16384 1.30 vs 1.60 -- carries no spill and leaves out the blocks above the diagonal of the diagonal tiles)
@@ -904,7 +905,9 @@ static int enqueue_head(lpipm_ctx* c) {
         // kernel waits for that word, the group's tiles are packed, summed over the ranks (the caller's all-reduce) and
         // unpacked -- while the launch goes on with the next groups.  After the last tile only the last group's sum is
         // left (C5: 1/32 .. 1/8 of the 1.08 GB that round 2 reduced in one block after the launch).  Element-wise sums:
-        // the same values as one reduction of the whole triangle.
+        // the same values as one reduction of the whole triangle -- bit for bit with two ranks; with three or more only if
+        // the caller's all-reduce sums an element's terms in an order that does not depend on where the element sits in
+        // the buffer (a ring all-reduce such as gloo's does not: last-bit differences between the two ways).
         hipStream_t sc = c->st_c;
         const Batch& bt = c->bt_head;
         LP_HIP(clear_unit_counters(c, bt, st));
@@ -1854,7 +1857,9 @@ extern "C" int lpipm_k_iteration(lpipm_ctx* c, const lpipm_opts* o, int ip, doub
                                  int32_t* info_out) {
     if (!c || !o || !x || !y || !z || !tau || !kappa || !d_x || !d_y || !d_z || !d_tk || !alpha_out) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->has_problem) return LPIPM_ERR_NO_PROBLEM;
-    if (c->B != 1 || c->colsplit) return LPIPM_ERR_UNSUPPORTED;
+    if (c->B != 1) return LPIPM_ERR_UNSUPPORTED;
+    // (a column-split context: x, z, d_x, d_z are this rank's slices, everything else is replicated, and every rank must
+    //  call together -- enqueue_residuals / enqueue_iteration contain the cross-rank reductions)
     LP_HIP(hipSetDevice(c->device));
     VecArgs& v = c->va;
     hipStream_t st = c->st;
@@ -1877,6 +1882,10 @@ extern "C" int lpipm_k_iteration(lpipm_ctx* c, const lpipm_opts* o, int ip, doub
     LP_HIP(hipMemcpyAsync(d_y, v.dy, c->m * sizeof(double), hipMemcpyDeviceToHost, st));
     LP_HIP(hipMemcpyAsync(d_z, v.dz, c->n * sizeof(double), hipMemcpyDeviceToHost, st));
     LP_HIP(hipStreamSynchronize(st));
+    if (c->colsplit && c->grouped_reduce && *c->timeout_host != 0) {   // as solve_impl: a group wait that gave up is an error
+        g_err_detail = "a column group of A.D.A^T did not complete within the wait kernel's bound";
+        return LPIPM_ERR_HIP;
+    }
     *tau = sc[S_TAU]; *kappa = sc[S_KAPPA]; d_tk[0] = sc[S_DTAU]; d_tk[1] = sc[S_DKAPPA]; *alpha_out = sc[S_ALPHA];
     if (info_out) *info_out = c->status_host->potrf_info;
     return LPIPM_OK;

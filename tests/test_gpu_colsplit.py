@@ -66,8 +66,11 @@ def test_column_split_matches_oracle_and_single(ctx, world, seed, m, n, align):
         assert abs(fun - ref["fun"]) <= 1e-6 * max(1.0, abs(ref["fun"]))
         assert fun == got[0][4] and rows == got[0][6]              # replicated scalars are bit-identical across ranks
         x[lo:lo + len(xs)] = xs
-        # per iteration: M, 2 x (A w), 6 scalar groups; plus the residual / final ones
-        assert calls >= 9 * it
+        # one column group of M at these sizes (m <= 512).  Per iteration: M, 2 x (A.W), {c.p, c.u, NaN flag}, c.u, 2 x the
+        # ratio-test minima, A.x and the four residual scalars = 9 calls; A.x and the scalars at the starting point; c.(x/tau)
+        # for the final x (enqueue_head / enqueue_tail / enqueue_residuals / vec_final_x; test_gpu_colsplit_at_scale.py
+        # derives the general count and the bytes)
+        assert calls == 2 + 9 * it + 1 and (calls, nbytes) == got[0][7:9]
     assert not np.isnan(x).any()
     assert np.abs(x - ref["x_slack"]).max() <= 1e-6
     assert np.abs(x - x1).max() <= 1e-6
@@ -91,7 +94,9 @@ def test_column_split_world_one_is_the_plain_solve(ctx):
 
 
 def test_column_split_infeasible_agrees_on_all_ranks(ctx):
-    """Control flow (status decisions) must be identical on every rank or the collectives would deadlock."""
+    """The Infeasible exit through the n-split entry points with world = 1: no callback, reductions local.  With 2 and 3
+    ranks, where status decisions that differ between ranks would leave a rank waiting in a collective, every exit is run
+    by test_gpu_colsplit_at_scale.py::test_exits_agree_on_all_ranks."""
     import lp_amd
     A = np.array([[1.0, 1.0, 1.0, 1.0]]); b = np.array([-1.0]); c = np.ones(4)
     ctx.set_collective(0, 1, None)
