@@ -43,10 +43,37 @@ const char* lp_knob(const char* name) {
 }  // namespace lpipm
 enum { T_VEC = 0, T_ADAT, T_POTRF, T_TRSV, T_GEMV, T_NTAGS };
 
-struct lpipm_ctx {
-    int device = 0;
+namespace {   // the parts of a context: local to this file
+// How the A.D.A^T launch of a geometry is cut up (plan_adat).
+struct AdatPlan {
+    int ntiles = 0, adat_nwg = 1;
+    size_t ws_slabs = 0;                 // stream-K slabs (TILE x TILE doubles each) the A.D.A^T launches may need
+    bool units = false;                  // this problem runs the units kernel (geometry: the slabs fit the budget)
+    int cpt = 1, upc = 1;                // chunks per tile, chunks per unit
+};
+
+// What one stream of solver work owns on the host: a context has one, and so has each of its half-batch views.  Made by
+// stream_res_create, released by stream_res_destroy; nobody else creates or frees a member.
+struct StreamRes {
     hipStream_t st = nullptr;
-    int num_cu = 256;
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    hipEvent_t ev_status = nullptr;    // recorded behind the status copy of an iteration
+    std::vector<hipEvent_t> events;    // phase marks (prof_mark), created as they are needed
+    std::vector<int> mark_tags;
+    size_t nmarks = 0;
+    StatusRec* status_host = nullptr;  // pinned, status_cap records
+    size_t status_cap = 0;
+    unsigned int* timeout_host = nullptr;   // pinned mirror of Problem::wait_timeout, read with the status record
+    double* x_pinned = nullptr;        // pinned bounce buffer of the solution (a D2H copy into the caller's pageable array takes
+    size_t x_pinned_cap = 0;           //   the runtime's staged path: ~40 us more per solve than pinned + memcpy)
+    uint32_t seq_counter = 0;          // sequence numbers of the status records (VecArgs::status_seq)
+    bool spin_status = false;          // this solve waits for an iteration by watching the records' sequence words (wait_status)
+};
+
+// The resident problem: geometry, device pointers and launch arguments.  Every pointer points into an allocation of the
+// context that uploaded it (arena, a_shared, tile_list; the factor plan), so a plain copy of this struct shares the device
+// state and owns nothing: that is what a half-batch view holds (make_view).
+struct Problem {
     bool has_problem = false;
     uint64_t m = 0, n = 0;
     int mp = 0, np = 0, nblk = 1, nsplit = 1;
@@ -58,34 +85,45 @@ struct lpipm_ctx {
     // lpipm_upload_lockstep_shared: ONE A for the whole batch, outside the arenas (mp x npa, zeros beyond n and m); every
     // pass over A serves all members (the *_shared GEMV launches, A.D.A^T with A's member stride 0)
     bool shared_a = false;
-    double* a_shared = nullptr;          // owned by the context (a view shares its parent's)
+    double* a_shared = nullptr;
     size_t a_shared_bytes = 0;
     size_t list_bytes = 0;               // tile / unit lists (own allocation)
     Batch bt;                    // what the solve path hands to every launcher (count, stride, done flags)
     Batch bt_head;               // same with the done test always on: the speculatively enqueued head of an iteration
-    hipEvent_t ev_status = nullptr;   // recorded behind the status copy of an iteration
-    std::vector<void*> kallocs;  // buffers of the stand-alone kernel entry points
-    // problem + state + work
-    FactorPlan plan, kplan;
-    double *tau = nullptr, *ktau = nullptr;   // Householder scalars of the QR arms
+    const FactorPlan* factor = nullptr;  // lpipm_ctx::plan of the uploading context
+    double* tau = nullptr;               // Householder scalars of the QR arms
     double *A = nullptr, *M = nullptr, *ws = nullptr, *Y = nullptr, *ATpart = nullptr, *xout = nullptr;
     double *M0 = nullptr, *R0 = nullptr, *Rho = nullptr, *symv_ws = nullptr;   // refinement of the Cholesky solve
     // A.D.A^T as (tile, chunk) units with an in-launch combine (launch_adat_units; kernels_gemm.hip)
-    int units_env = 1;                   // LPIPM_ADAT_UNITS=0: the round-2 kernel (data-parallel tiles + stream-K + fix-up launch)
-    bool units = false;                  // this problem runs the units kernel (geometry: the slabs fit the budget)
     bool grouped_reduce = false;         // column split over ranks: M is reduced group by group behind the running launch
-    int cpt = 1, upc = 1;                // chunks per tile, chunks per unit
     int nunits = 0, nunits_grp = 0;
     int2* unit_list = nullptr;           // (tile, first chunk) in dispatch order: chunk-major over the XCD-aware tile order
     int2* unit_list_grp = nullptr;       // column-group-major (tile indices into tile_list_grp): groups complete one after the other
     unsigned int* tile_cnt = nullptr;    // arena: arrival counters of the tiles, then the group words (one memset clears both)
     unsigned int* grp_cnt = nullptr;
     size_t cnt_bytes = 0;
+    unsigned int* wait_timeout = nullptr;   // arena: set by a wait kernel that gave up (a producer that never ran)
+    std::vector<int> grp_off, grp_nt;    // tile sub-list of every column group (outer panel of the factorisation)
+    int2* tile_list = nullptr;
+    int2* tile_list_grp = nullptr;      // the same tiles grouped by column group (behind tile_list in one allocation)
+    unsigned int* sk_claim = nullptr;   // claim word of the dynamic stream-K chunks of A.D.A^T
+    double* gs = nullptr;        // 8 doubles: sums / minima that must be reduced across ranks (n-split mode)
+    VecArgs va{};
+};
+}  // namespace
+
+struct lpipm_ctx {
+    int device = 0;
+    int num_cu = 256;
+    StreamRes rs;
+    Problem p;
+    AdatPlan ap;
+    std::vector<void*> kallocs;  // buffers of the stand-alone kernel entry points
+    FactorPlan plan, kplan;
+    double* ktau = nullptr;
+    int units_env = 1;                   // LPIPM_ADAT_UNITS=0: the round-2 kernel (data-parallel tiles + stream-K + fix-up launch)
     bool cnt_dirty = true;               // the arrival words may be non-zero: the next plain units launch clears them first (a plain
                                          // launch leaves them zero itself; launches with group words do not)
-    unsigned int* wait_timeout = nullptr;   // arena: set by a wait kernel that gave up (a producer that never ran)
-    unsigned int* timeout_host = nullptr;   // pinned mirror, read with the status record
-    std::vector<int> grp_off, grp_nt;    // tile sub-list of every column group (outer panel of the factorisation)
     PotrfLookahead la;                   // trailing updates of one factorisation beside the next panel's chain (launch_potrf)
     // a lockstep batch as two half-batches driven by two host threads on two streams (solve_lockstep): views of this
     // context that share its arena (every pointer is LP 0's; a view's launches cover the LPs [bt.first, bt.first + B))
@@ -101,18 +139,6 @@ struct lpipm_ctx {
                                  //   d_tau is ill-determined in fp64 (tests/golden/make_c4_members.py, margin()): the oracle
                                  //   does the same under a permutation of its columns.  Refinement costs 7-20 % and is off.
     bool refine_now = false;     // the iteration being enqueued refines its solves (host mirror of the LPs' skip_refine words)
-    int2* tile_list = nullptr;
-    int2* tile_list_grp = nullptr;      // the same tiles grouped by column group (behind tile_list in one allocation)
-    size_t ws_slabs = 0;                // stream-K slabs (TILE x TILE doubles each) the A.D.A^T launches may need
-    unsigned int* sk_claim = nullptr;   // claim word of the dynamic stream-K chunks of A.D.A^T
-    int ntiles = 0, adat_nwg = 1;
-    VecArgs va{};
-    StatusRec* status_host = nullptr;  // pinned, status_cap records
-    uint32_t seq_counter = 0;          // sequence numbers of the status records (VecArgs::status_seq)
-    bool spin_status = false;          // this solve waits for an iteration by watching the records' sequence words (wait_status)
-    double* x_pinned = nullptr;        // pinned bounce buffer of the solution (a D2H copy into the caller's pageable array takes
-    size_t x_pinned_cap = 0;           //   the runtime's staged path: ~40 us more per solve than pinned + memcpy)
-    size_t status_cap = 0;
     // stand-alone potrf/solve buffers
     double *kM = nullptr, *kM0 = nullptr, *kR = nullptr, *kY = nullptr;
     int32_t* kinfo = nullptr;
@@ -120,10 +146,6 @@ struct lpipm_ctx {
     bool kchol_valid = false;
     // profiling
     int profiling = 0;           // 0 off, 1 every phase, 2 only the A.D.A^T launches (2 events per iteration)
-    std::vector<hipEvent_t> events;
-    std::vector<int> mark_tags;
-    size_t nmarks = 0;
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     double tag_ms[T_NTAGS] = {0, 0, 0, 0, 0};
     uint64_t gemv_passes = 0;
     lpipm_phase_times times{};
@@ -137,7 +159,6 @@ struct lpipm_ctx {
     lpipm_allreduce_fn coll = nullptr;
     void* coll_user = nullptr;
     bool coll_on_stream = false;  // the callback enqueues the reduction on the ctx's stream itself (no drain before the call)
-    double* gs = nullptr;        // 8 doubles: sums / minima that must be reduced across ranks
     hipStream_t st_c = nullptr;  // communication stream: the column groups of M are packed, reduced and unpacked here, behind the
     hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;   //   group words of the A.D.A^T launch that is still running on the solver's stream
     double* mpack = nullptr;     // contiguous image of the lower block-triangle of M for its all-reduce
@@ -145,7 +166,7 @@ struct lpipm_ctx {
 };
 
 static void destroy_views(lpipm_ctx* c);      // half-batch views of a lockstep batch (solve_lockstep)
-namespace lpipm { lpipm_ctx_device lpipm_ctx_device_of(lpipm_ctx* c) { return lpipm_ctx_device{c->device, c->st}; } }
+namespace lpipm { lpipm_ctx_device lpipm_ctx_device_of(lpipm_ctx* c) { return lpipm_ctx_device{c->device, c->rs.st}; } }
 
 // Cross-rank reduction of `count` doubles at a device pointer, ordered after everything enqueued on the ctx's stream
 // so far.  Default contract: the stream is drained first and the callee returns when the result is in place.
@@ -155,7 +176,7 @@ namespace lpipm { lpipm_ctx_device lpipm_ctx_device_of(lpipm_ctx* c) { return lp
 static int ctx_allreduce(lpipm_ctx* c, double* ptr, uint64_t count, int op, hipStream_t on = nullptr) {
     if (!c->colsplit || c->world <= 1) return LPIPM_OK;
     if (!c->coll) return LPIPM_ERR_BAD_ARGUMENT;
-    hipStream_t st = on ? on : c->st;             // (the M groups are reduced on the communication stream, see enqueue_head)
+    hipStream_t st = on ? on : c->rs.st;             // (the M groups are reduced on the communication stream, see enqueue_head)
     if (!c->coll_on_stream) LP_HIP(hipStreamSynchronize(st));
     if (c->coll(c->coll_user, ptr, count, op, (void*)st) != 0) {
         g_err_detail = "the all-reduce callback of lpipm_set_collective reported a failure";
@@ -184,33 +205,70 @@ static int dalloc(std::vector<void*>& list, std::vector<size_t>* sizes, T** out,
 }
 #define LP_TRY(expr) do { int rc__ = (expr); if (rc__ != LPIPM_OK) return rc__; } while (0)
 
+// ---- StreamRes: created for `count` status records, its status array grown, destroyed -- here and nowhere else
+static void stream_res_destroy(StreamRes& r) {
+    if (r.st) (void)hipStreamSynchronize(r.st);
+    for (hipEvent_t e : r.events) (void)hipEventDestroy(e);
+    if (r.ev_begin) (void)hipEventDestroy(r.ev_begin);
+    if (r.ev_end) (void)hipEventDestroy(r.ev_end);
+    if (r.ev_status) (void)hipEventDestroy(r.ev_status);
+    if (r.timeout_host) (void)hipHostFree(r.timeout_host);
+    if (r.status_host) (void)hipHostFree(r.status_host);
+    if (r.x_pinned) (void)hipHostFree(r.x_pinned);
+    if (r.st) (void)hipStreamDestroy(r.st);
+    r = StreamRes{};
+}
+// At least `count` zeroed status records (coherent and mapped: the kernels write them directly, bind_status_pinned).
+static int stream_res_grow_status(StreamRes& r, size_t count) {
+    if (count <= r.status_cap) return LPIPM_OK;
+    if (r.status_host) (void)hipHostFree(r.status_host);
+    r.status_host = nullptr; r.status_cap = 0;
+    LP_HIP(hipHostMalloc((void**)&r.status_host, count * sizeof(StatusRec), hipHostMallocCoherent | hipHostMallocMapped));
+    std::memset(r.status_host, 0, count * sizeof(StatusRec));
+    r.status_cap = count;
+    return LPIPM_OK;
+}
+static int stream_res_create(StreamRes& r, size_t count) {
+    if (hipStreamCreateWithFlags(&r.st, hipStreamNonBlocking) != hipSuccess || stream_res_grow_status(r, count) != LPIPM_OK ||
+        hipHostMalloc((void**)&r.timeout_host, sizeof(unsigned int)) != hipSuccess ||
+        hipEventCreate(&r.ev_begin) != hipSuccess || hipEventCreate(&r.ev_end) != hipSuccess ||
+        hipEventCreateWithFlags(&r.ev_status, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        stream_res_destroy(r);
+        g_err_detail = "failed to create stream / pinned status / events";
+        return LPIPM_ERR_HIP;
+    }
+    *r.timeout_host = 0;
+    return LPIPM_OK;
+}
+
 static void prof_mark(lpipm_ctx* c, int tag, bool adat_bracket = false) {
     if (!c->profiling || (c->profiling == 2 && !adat_bracket)) return;
-    if (c->nmarks == c->events.size()) {
+    if (c->rs.nmarks == c->rs.events.size()) {
         hipEvent_t e;
         if (hipEventCreate(&e) != hipSuccess) return;
-        c->events.push_back(e);
-        c->mark_tags.push_back(0);
+        c->rs.events.push_back(e);
+        c->rs.mark_tags.push_back(0);
     }
-    c->mark_tags[c->nmarks] = tag;
-    (void)hipEventRecord(c->events[c->nmarks], c->st);
-    ++c->nmarks;
+    c->rs.mark_tags[c->rs.nmarks] = tag;
+    (void)hipEventRecord(c->rs.events[c->rs.nmarks], c->rs.st);
+    ++c->rs.nmarks;
 }
 // Adds up the intervals between the first `upto` marks (all of them by default); call when those events have
 // completed.  Later marks (the speculatively enqueued head of the next iteration) move to the front.
 static void prof_collect(lpipm_ctx* c, size_t upto = (size_t)-1) {
     if (!c->profiling) return;
-    if (upto > c->nmarks) upto = c->nmarks;
+    if (upto > c->rs.nmarks) upto = c->rs.nmarks;
     for (size_t i = 1; i < upto; ++i) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c->events[i - 1], c->events[i]) == hipSuccess)
-            c->tag_ms[c->mark_tags[i]] += ms;
+        if (hipEventElapsedTime(&ms, c->rs.events[i - 1], c->rs.events[i]) == hipSuccess)
+            c->tag_ms[c->rs.mark_tags[i]] += ms;
     }
-    for (size_t i = upto; i < c->nmarks; ++i) {
-        std::swap(c->events[i - upto], c->events[i]);
-        c->mark_tags[i - upto] = c->mark_tags[i];
+    for (size_t i = upto; i < c->rs.nmarks; ++i) {
+        std::swap(c->rs.events[i - upto], c->rs.events[i]);
+        c->rs.mark_tags[i - upto] = c->rs.mark_tags[i];
     }
-    c->nmarks -= upto;
+    c->rs.nmarks -= upto;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -282,31 +340,20 @@ extern "C" int lpipm_create(int device, lpipm_ctx** out) {
     c->device = device;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->num_cu = prop.multiProcessorCount;
-    if (hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess ||
-        hipHostMalloc((void**)&c->status_host, sizeof(StatusRec), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
-        hipEventCreate(&c->ev_begin) != hipSuccess || hipEventCreate(&c->ev_end) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_status, hipEventDisableTiming) != hipSuccess) {
-        g_err_detail = "failed to create stream / pinned status / events";
+    if (stream_res_create(c->rs, 1) != LPIPM_OK) {
         delete c;
         return LPIPM_ERR_HIP;
     }
-    c->status_cap = 1;
     // LPIPM_REFINE (see lpipm_ctx::refine) is read ONCE, here: the arena layout depends on it (M0, R0, Rho and the symv slabs
     // exist only for a refining context: 134 MB at C3, 2 GB at m = 16384, per member of a lockstep batch)
     { const char* e = lp_knob("LPIPM_REFINE"); c->refine = !e ? 0 : (e[0] == '2' ? 2 : (e[0] == '1' ? 1 : 0)); }
-    // LPIPM_ADAT_UNITS: 0 = the round-2 kernel everywhere, 2 = the units kernel for single LPs too (measurement / test knob);
-    // default 1 = units kernel for lockstep batches and for the column-split reduction, round-2 kernel for a single LP
-    // (measured per launch, units vs round-2: 512x1024 0.042 / 0.045 ms, 1024x2048 0.102 / 0.097, 2048x4096 0.469 / 0.458,
+    // LPIPM_ADAT_UNITS: 0 = the round-2 kernel everywhere, 2 = the units kernel for every single LP whose slabs fit (measurement /
+    // test knob); default 1 = units kernel for lockstep batches, for the column-split reduction and for most single LPs, the
+    // 4096x8192 headline included -- plan_adat has the rule, its exceptions (few tiles with several chunks) and the figures
+    // (first measured per launch, units vs round-2: 512x1024 0.042 / 0.045 ms, 1024x2048 0.102 / 0.097, 2048x4096 0.469 / 0.458,
     // 4096x8192 2.47 / 2.39 standalone and 2.32 / 2.25 inside a solve; C4 lockstep shard 1732 vs 1674 LP/s)
     { const char* e = lp_knob("LPIPM_ADAT_UNITS"); c->units_env = !e ? 1 : (e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1)); }
     { const char* e = lp_knob("LPIPM_HALVES"); c->halves_env = (e && e[0] == '0') ? 0 : 1; }
-    if (hipHostMalloc((void**)&c->timeout_host, sizeof(unsigned int)) != hipSuccess) {
-        g_err_detail = "failed to allocate the pinned time-out word";
-        lpipm_destroy(c);
-        return LPIPM_ERR_HIP;
-    }
-    *c->timeout_host = 0;
-    std::memset(c->status_host, 0, sizeof(StatusRec));
     // Side stream for the look-ahead of the factorisation's trailing updates (launch_potrf; used from m = 4096, see there for
     // the measurements; LPIPM_LOOKAHEAD=0 switches it off, =1 lowers the threshold to m = 1536).  CU-masked (bit i = CU i/8 of XCC i%8): the first R CUs of every XCC stay free for the chain
     // stream's kernels -- the diagonal-block kernel needs a CU to itself (150 KB of LDS) and would otherwise wait for a
@@ -348,10 +395,10 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     c->workers.clear();
     destroy_views(c);
     (void)hipSetDevice(c->device);
-    if (c->st) (void)hipStreamSynchronize(c->st);
-    if (c->arena) (void)hipFree(c->arena);
-    if (c->a_shared) (void)hipFree(c->a_shared);
-    if (c->tile_list) (void)hipFree(c->tile_list);
+    if (c->rs.st) (void)hipStreamSynchronize(c->rs.st);      // before the buffers go
+    if (c->p.arena) (void)hipFree(c->p.arena);
+    if (c->p.a_shared) (void)hipFree(c->p.a_shared);
+    if (c->p.tile_list) (void)hipFree(c->p.tile_list);
     free_list(c->kallocs);
     if (c->mpack) (void)hipFree(c->mpack);
     if (c->st_c) { (void)hipStreamSynchronize(c->st_c); (void)hipStreamDestroy(c->st_c); }
@@ -359,17 +406,10 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     if (c->ev_c1) (void)hipEventDestroy(c->ev_c1);
     factor_plan_destroy(c->plan);
     factor_plan_destroy(c->kplan);
-    for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
-    if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
-    if (c->ev_end) (void)hipEventDestroy(c->ev_end);
-    if (c->ev_status) (void)hipEventDestroy(c->ev_status);
     if (c->la.side) { (void)hipStreamSynchronize(c->la.side); (void)hipStreamDestroy(c->la.side); }
     for (hipEvent_t e : c->la.ev_chain) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->la.ev_rest) (void)hipEventDestroy(e);
-    if (c->timeout_host) (void)hipHostFree(c->timeout_host);
-    if (c->status_host) (void)hipHostFree(c->status_host);
-    if (c->x_pinned) (void)hipHostFree(c->x_pinned);
-    if (c->st) (void)hipStreamDestroy(c->st);
+    stream_res_destroy(c->rs);
     delete c;
 }
 
@@ -445,31 +485,33 @@ static void deal_units(const std::vector<int>& tiles, int cpt, int upc, std::vec
                 out.push_back(i < own[x].size() ? make_int2(own[x][i], q * upc) : make_int2(-1, 0));
 }
 
-// How the A.D.A^T launch of this geometry is cut up (a function of mp, npa, the batch count and the CU count alone).
-static void plan_adat(lpipm_ctx* c, int count) {
-    const int nt = c->mp / TILE;
-    c->ntiles = nt * (nt + 1) / 2;
+// How the A.D.A^T launch of a geometry is cut up: a function of mp, npa, the batch count, the CU count, the number of ranks
+// of a column split (world; it matters for a single LP only) and the value of LPIPM_ADAT_UNITS -- and of nothing else.
+static AdatPlan plan_adat(int mp, int npa, int count, int num_cu, int world, int units_env) {
+    AdatPlan a;
+    const int nt = mp / TILE;
+    a.ntiles = nt * (nt + 1) / 2;
     // workgroups per LP of the round-2 A.D.A^T launch (LPIPM_ADAT_UNITS=0, and contractions whose slabs would not fit):
     // stream-K over the chip's share of one LP; a batch that fills the chip with whole tiles needs no k-split
-    if (count == 1) c->adat_nwg = gemm_streamk_nwg(c->ntiles, c->npa / BK, c->num_cu);
-    else if ((long long)count * c->ntiles >= 2LL * c->num_cu) {
+    if (count == 1) a.adat_nwg = gemm_streamk_nwg(a.ntiles, npa / BK, num_cu);
+    else if ((long long)count * a.ntiles >= 2LL * num_cu) {
         // more tiles than resident workgroups: each LP gets its share of the 2*CUs slots and stream-K
         // balances its tiles over them (no tail round of a few leftover tiles)
-        c->adat_nwg = 2 * c->num_cu / count;
-        if (c->adat_nwg < 1) c->adat_nwg = 1;
-        if (c->adat_nwg > c->ntiles) c->adat_nwg = c->ntiles;
+        a.adat_nwg = 2 * num_cu / count;
+        if (a.adat_nwg < 1) a.adat_nwg = 1;
+        if (a.adat_nwg > a.ntiles) a.adat_nwg = a.ntiles;
     } else {
-        c->adat_nwg = gemm_streamk_nwg(c->ntiles, c->npa / BK, c->num_cu / count);
-        if (c->adat_nwg < c->ntiles) c->adat_nwg = c->ntiles;
+        a.adat_nwg = gemm_streamk_nwg(a.ntiles, npa / BK, num_cu / count);
+        if (a.adat_nwg < a.ntiles) a.adat_nwg = a.ntiles;
     }
-    c->ws_slabs = gemm_streamk_slabs(c->ntiles, c->npa / BK, c->adat_nwg);
+    a.ws_slabs = gemm_streamk_slabs(a.ntiles, npa / BK, a.adat_nwg);
     // A.D.A^T as (tile, chunk) units: every chunk sum goes through its own slab (ntiles x cpt slabs of 128 KiB per LP:
     // 0.55 GB at C3, 38 MB per member at C4) -- up to 4 GiB per LP, beyond that (m = 16384: 34 GB) the round-2 kernel
     // -- and only up to ADAT_UNITS_MAX_CPT chunks per tile (npa up to ~256000 columns): longer rows take the round-2 kernel too
-    c->cpt = adat_units_cpt(c->npa);
-    const bool units_fit = c->cpt <= ADAT_UNITS_MAX_CPT;
-    c->units = c->units_env != 0 && units_fit && (size_t)c->ntiles * c->cpt * TILE * TILE * sizeof(double) <= ((size_t)4 << 30) &&
-               (count > 1 || c->units_env == 2 || c->cpt == 1 || c->ntiles <= 16 || c->ntiles * c->cpt >= 256);
+    a.cpt = adat_units_cpt(npa);
+    const bool units_fit = a.cpt <= ADAT_UNITS_MAX_CPT;
+    a.units = units_env != 0 && units_fit && (size_t)a.ntiles * a.cpt * TILE * TILE * sizeof(double) <= ((size_t)4 << 30) &&
+               (count > 1 || units_env == 2 || a.cpt == 1 || a.ntiles <= 16 || a.ntiles * a.cpt >= 256);
     // (tiny single LPs -- up to 16 tiles -- : one launch and one memset less, 0.042 vs 0.045 ms at 512x1024;
     //  a single LP with few tiles AND several chunks under 256 units -- 700x1500: 21 tiles x 6, 1009x1100: 36 tiles x 5; not
     //  1000x5000, whose 36 tiles x 11 chunks are 396 units -- keeps the round-2 kernel: one workgroup per
@@ -478,24 +520,27 @@ static void plan_adat(lpipm_ctx* c, int count) {
     //  2048x16384 1.30 vs 1.60 -- carries no spill and leaves out the blocks above the diagonal of the diagonal tiles)
     // one LP split by columns over ranks: the units kernel signals M's column groups one by one, and each group's cross-rank
     // sum runs behind the rest of the launch (enqueue_head); its slabs may take up to 32 GiB there (C5: 17 GB per rank)
-    if (count == 1 && c->world > 1 && c->units_env != 0 && units_fit && nt <= 64 * POTRF_OUTER &&
-        (size_t)c->ntiles * c->cpt * TILE * TILE * sizeof(double) <= ((size_t)32 << 30)) c->units = true;
+    if (count == 1 && world > 1 && units_env != 0 && units_fit && nt <= 64 * POTRF_OUTER &&
+        (size_t)a.ntiles * a.cpt * TILE * TILE * sizeof(double) <= ((size_t)32 << 30)) a.units = true;
     // a single LP: one chunk per unit (parallelism, and column groups that complete while the launch runs); a lockstep
     // batch: two chunks per unit -- whole tiles (one unit = all chunks, its own workgroup adds its slabs) leave the last of
     // 2.25 rounds of tiles a quarter full (C4 shard: 1633 LP/s, against 1706 with one chunk per unit, 1533 / 1521 / 1521 at
     // 2 / 1 / 4 chunks on a slower box)
-    c->upc = count == 1 ? 1 : (c->cpt < 2 ? c->cpt : 2);
-    { int kc, nbig, ks; if (adat_units_chunking(c->npa, &kc, &nbig, &ks) != nbig) c->upc = 1; }   // non-uniform chunks: one per unit
-    if (c->units && c->ws_slabs < (size_t)c->ntiles * c->cpt) c->ws_slabs = (size_t)c->ntiles * c->cpt;
+    a.upc = count == 1 ? 1 : (a.cpt < 2 ? a.cpt : 2);
+    { int kc, nbig, ks; if (adat_units_chunking(npa, &kc, &nbig, &ks) != nbig) a.upc = 1; }   // non-uniform chunks: one per unit
+    if (a.units && a.ws_slabs < (size_t)a.ntiles * a.cpt) a.ws_slabs = (size_t)a.ntiles * a.cpt;
+    return a;
 }
 
 // Per-LP device state: one pass over a measuring arena sizes it, a second pass over the real one places it.
 // Every LP of a lockstep batch gets the same layout, `bstride` bytes after the previous LP's.
 static void bind_status_pinned(lpipm_ctx* c, bool allow);
-static int layout_problem(lpipm_ctx* c, Arena& ar, bool build) {
-    VecArgs& v = c->va;
-    const size_t mp = (size_t)c->mp, np = (size_t)c->np;
-    c->A = c->shared_a ? nullptr : ar.take<double>(mp * c->npa);     // a shared A has its own allocation (upload_impl)
+// In: p's geometry (mp, np, npa, nsplit, B, shared_a), the A.D.A^T plan and whether the context refines its solves.  Out: p's
+// device pointers and `plan`, the factor plan they refer to.
+static int layout_problem(Problem& p, FactorPlan& plan, const AdatPlan& ap, int refine, Arena& ar, bool build, hipStream_t st) {
+    VecArgs& v = p.va;
+    const size_t mp = (size_t)p.mp, np = (size_t)p.np;
+    p.A = p.shared_a ? nullptr : ar.take<double>(mp * p.npa);     // a shared A has its own allocation (upload_impl)
     v.b = ar.take<double>(mp); v.c = ar.take<double>(np);
     v.x = ar.take<double>(np); v.y = ar.take<double>(mp); v.z = ar.take<double>(np);
     v.dinv = ar.take<double>(np); v.xs = ar.take<double>(np); v.r1 = ar.take<double>(np); v.rD = ar.take<double>(np);
@@ -505,37 +550,38 @@ static int layout_problem(lpipm_ctx* c, Arena& ar, bool build) {
     // chunk slabs of A.x: sized by the count the launches use (the STORED columns npa -- gemv_dual_chunks is not monotone:
     // 256-column chunks below 4096 columns, 1024-column chunks from there on, so np's count can be the smaller one)
     {
-        const int ch_a = gemv_dual_chunks(c->npa), ch_n = gemv_dual_chunks((int)np);
+        const int ch_a = gemv_dual_chunks(p.npa), ch_n = gemv_dual_chunks((int)np);
         v.Ax = ar.take<double>(mp * (size_t)(ch_a > ch_n ? ch_a : ch_n));
     }
     v.W = ar.take<double>(2 * np); v.R = ar.take<double>(2 * mp);
-    c->Y = ar.take<double>(2 * mp);
-    c->ATpart = ar.take<double>((size_t)c->nsplit * 2 * np);
-    v.ATpart = c->ATpart;
+    p.Y = ar.take<double>(2 * mp);
+    p.ATpart = ar.take<double>((size_t)p.nsplit * 2 * np);
+    v.ATpart = p.ATpart;
     v.S = ar.take<double>(64); v.red = ar.take<double>((size_t)RED_SLOTS * RED_STRIDE);
     v.status = ar.take<StatusRec>(1);
     v.potrf_info = ar.take<int32_t>(1); v.flags = ar.take<int>(1); v.done = ar.take<int>(1);
     v.skip_refine = ar.take<int>(1);
-    c->M = ar.take<double>(mp * mp);
-    LP_HIP(factor_plan_create(c->plan, c->M, c->mp, c->mp, ar, build, c->st, super_for(c->mp), merge_edge_for(c->B)));
-    c->M0 = c->R0 = c->Rho = c->symv_ws = nullptr;
-    if (c->refine > 0) {     // only the refined solves read the matrix itself
-        c->M0 = ar.take<double>(mp * mp);
-        c->R0 = ar.take<double>(2 * mp); c->Rho = ar.take<double>(2 * mp);
-        c->symv_ws = ar.take<double>(symv_slab_doubles(c->mp));
+    p.M = ar.take<double>(mp * mp);
+    LP_HIP(factor_plan_create(plan, p.M, p.mp, p.mp, ar, build, st, super_for(p.mp), merge_edge_for(p.B)));
+    p.factor = &plan;
+    p.M0 = p.R0 = p.Rho = p.symv_ws = nullptr;
+    if (refine > 0) {     // only the refined solves read the matrix itself
+        p.M0 = ar.take<double>(mp * mp);
+        p.R0 = ar.take<double>(2 * mp); p.Rho = ar.take<double>(2 * mp);
+        p.symv_ws = ar.take<double>(symv_slab_doubles(p.mp));
     }
-    c->tau = ar.take<double>(mp);
-    c->gs = ar.take<double>(8);
-    c->xout = ar.take<double>(np);
-    c->sk_claim = ar.take<unsigned int>(1);
+    p.tau = ar.take<double>(mp);
+    p.gs = ar.take<double>(8);
+    p.xout = ar.take<double>(np);
+    p.sk_claim = ar.take<unsigned int>(1);
     // arrival counters of the units kernel: one word per tile, then one per column group; cleared by ONE memset per launch
     // (a block of its own, a multiple of 16 bytes)
-    c->cnt_bytes = (size_t)round_up(((size_t)c->ntiles + 64) * sizeof(unsigned int), 16);
-    c->tile_cnt = (unsigned int*)ar.take<uint4>(c->cnt_bytes / 16);
-    c->grp_cnt = c->tile_cnt + c->ntiles;
-    c->wait_timeout = ar.take<unsigned int>(4);
+    p.cnt_bytes = (size_t)round_up(((size_t)ap.ntiles + 64) * sizeof(unsigned int), 16);
+    p.tile_cnt = (unsigned int*)ar.take<uint4>(p.cnt_bytes / 16);
+    p.grp_cnt = p.tile_cnt + ap.ntiles;
+    p.wait_timeout = ar.take<unsigned int>(4);
     // chunk slabs of A.D.A^T (units kernel: every chunk of every tile; round-2 kernel: the stream-K remainder tiles)
-    c->ws = ar.take<double>(c->ws_slabs * TILE * TILE);
+    p.ws = ar.take<double>(ap.ws_slabs * TILE * TILE);
     return LPIPM_OK;
 }
 
@@ -565,136 +611,130 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
             if (row[j] != ((i == j) ? 1.0 : 0.0)) { n_slack = 0; break; }
     }
     LP_HIP(hipSetDevice(c->device));
-    destroy_views(c); // half-batch views copy the geometry and the buffers
+    destroy_views(c); // half-batch views hold copies of the geometry and of the device pointers
     const uint64_t nx = n - n_slack;
     const int mp = (int)round_up(m, NB), np = (int)round_up(n, BK), npa = (int)round_up(nx, BK);
-    hipStream_t st = c->st;
-    if (!c->has_problem || mp != c->mp || np != c->np || npa != c->npa || count != c->B || shared != c->shared_a) {
+    hipStream_t st = c->rs.st;
+    if (!c->p.has_problem || mp != c->p.mp || np != c->p.np || npa != c->p.npa || count != c->p.B || shared != c->p.shared_a) {
         LP_HIP(hipStreamSynchronize(st));
-        if (c->arena) { LP_HIP(hipFree(c->arena)); c->arena = nullptr; }
-        if (c->a_shared) { LP_HIP(hipFree(c->a_shared)); c->a_shared = nullptr; c->a_shared_bytes = 0; }
-        c->shared_a = shared;
-        if (c->tile_list) { LP_HIP(hipFree(c->tile_list)); c->tile_list = nullptr; }
+        if (c->p.arena) { LP_HIP(hipFree(c->p.arena)); c->p.arena = nullptr; }
+        if (c->p.a_shared) { LP_HIP(hipFree(c->p.a_shared)); c->p.a_shared = nullptr; c->p.a_shared_bytes = 0; }
+        c->p.shared_a = shared;
+        if (c->p.tile_list) { LP_HIP(hipFree(c->p.tile_list)); c->p.tile_list = nullptr; }
         factor_plan_destroy(c->plan);
-        c->has_problem = false;
-        c->mp = mp; c->np = np; c->npa = npa; c->B = count;
-        c->nsplit = mp / GEMVT_ROWS;
+        c->p.has_problem = false;
+        c->p.mp = mp; c->p.np = np; c->p.npa = npa; c->p.B = count;
+        c->p.nsplit = mp / GEMVT_ROWS;
         const uint64_t big = m > n ? m : n;
-        c->nblk = (int)((big + 255) / 256);
-        if (c->nblk > RED_STRIDE) c->nblk = RED_STRIDE;
+        c->p.nblk = (int)((big + 255) / 256);
+        if (c->p.nblk > RED_STRIDE) c->p.nblk = RED_STRIDE;
         const int nt = mp / TILE;
         std::vector<int2> order = adat_tile_order(nt);
-        plan_adat(c, count);
+        c->ap = plan_adat(mp, npa, count, c->num_cu, c->world, c->units_env);
         std::vector<int2> units, units_grp;
-        if (c->units) {
+        if (c->ap.units) {
             if (count == 1) {
-                std::vector<int> all((size_t)c->ntiles);
-                for (int t = 0; t < c->ntiles; ++t) all[(size_t)t] = t;
-                deal_units(all, c->cpt, c->upc, units);
+                std::vector<int> all((size_t)c->ap.ntiles);
+                for (int t = 0; t < c->ap.ntiles; ++t) all[(size_t)t] = t;
+                deal_units(all, c->ap.cpt, c->ap.upc, units);
             } else {                                               // a batch: an LP's units all run on one XCD (xcd-major grid)
-                for (int q = 0; q < c->cpt; q += c->upc)
-                    for (int t = 0; t < c->ntiles; ++t) units.push_back(make_int2(t, q));
+                for (int q = 0; q < c->ap.cpt; q += c->ap.upc)
+                    for (int t = 0; t < c->ap.ntiles; ++t) units.push_back(make_int2(t, q));
             }
         }
-        c->nunits = (int)units.size();
-        const bool grouped_reduce = count == 1 && c->world > 1 && c->units && nt <= 64 * POTRF_OUTER;
+        c->p.nunits = (int)units.size();
+        const bool grouped_reduce = count == 1 && c->world > 1 && c->ap.units && nt <= 64 * POTRF_OUTER;
         std::vector<int2> grouped;
         if (grouped_reduce) {       // column-group-major unit list for the pipelined reduction of M (enqueue_head)
-            grouped = adat_tile_order_grouped(nt, c->grp_off, c->grp_nt);
-            for (size_t g = 0; g < c->grp_nt.size(); ++g) {
-                std::vector<int> grp((size_t)c->grp_nt[g]);
-                for (int t = 0; t < c->grp_nt[g]; ++t) grp[(size_t)t] = c->grp_off[g] + t;
-                deal_units(grp, c->cpt, 1, units_grp);
+            grouped = adat_tile_order_grouped(nt, c->p.grp_off, c->p.grp_nt);
+            for (size_t g = 0; g < c->p.grp_nt.size(); ++g) {
+                std::vector<int> grp((size_t)c->p.grp_nt[g]);
+                for (int t = 0; t < c->p.grp_nt[g]; ++t) grp[(size_t)t] = c->p.grp_off[g] + t;
+                deal_units(grp, c->ap.cpt, 1, units_grp);
             }
         }
-        c->nunits_grp = (int)units_grp.size();
-        c->grouped_reduce = grouped_reduce && c->nunits_grp > 0;
+        c->p.nunits_grp = (int)units_grp.size();
+        c->p.grouped_reduce = grouped_reduce && c->p.nunits_grp > 0;
         Arena measure;
-        LP_TRY(layout_problem(c, measure, false));
-        c->bstride = round_up(measure.off, 4096);
-        c->arena_bytes = c->bstride * (size_t)count;
-        LP_HIP(hipMalloc((void**)&c->arena, c->arena_bytes));
-        LP_HIP(hipMemsetAsync(c->arena, 0, c->arena_bytes, st));
+        LP_TRY(layout_problem(c->p, c->plan, c->ap, c->refine, measure, false, st));
+        c->p.bstride = round_up(measure.off, 4096);
+        c->p.arena_bytes = c->p.bstride * (size_t)count;
+        LP_HIP(hipMalloc((void**)&c->p.arena, c->p.arena_bytes));
+        LP_HIP(hipMemsetAsync(c->p.arena, 0, c->p.arena_bytes, st));
         Arena real;
-        real.base = c->arena;
-        LP_TRY(layout_problem(c, real, true));
+        real.base = c->p.arena;
+        LP_TRY(layout_problem(c->p, c->plan, c->ap, c->refine, real, true, st));
         if (shared) {              // the one A of the batch: mp x npa like an arena's, zero padding
-            c->a_shared_bytes = (size_t)mp * (size_t)npa * sizeof(double);
-            LP_HIP(hipMalloc((void**)&c->a_shared, c->a_shared_bytes));
-            LP_HIP(hipMemsetAsync(c->a_shared, 0, c->a_shared_bytes, st));
-            c->A = c->a_shared;
+            c->p.a_shared_bytes = (size_t)mp * (size_t)npa * sizeof(double);
+            LP_HIP(hipMalloc((void**)&c->p.a_shared, c->p.a_shared_bytes));
+            LP_HIP(hipMemsetAsync(c->p.a_shared, 0, c->p.a_shared_bytes, st));
+            c->p.A = c->p.a_shared;
         }
-        c->list_bytes = (order.size() + grouped.size() + units.size() + units_grp.size() + 1) * sizeof(int2);
-        LP_HIP(hipMalloc((void**)&c->tile_list, c->list_bytes));
-        LP_HIP(hipMemcpyAsync(c->tile_list, order.data(), order.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-        c->tile_list_grp = c->tile_list + order.size();
-        c->unit_list = c->tile_list_grp + grouped.size();
-        c->unit_list_grp = c->unit_list + units.size();
+        c->p.list_bytes = (order.size() + grouped.size() + units.size() + units_grp.size() + 1) * sizeof(int2);
+        LP_HIP(hipMalloc((void**)&c->p.tile_list, c->p.list_bytes));
+        LP_HIP(hipMemcpyAsync(c->p.tile_list, order.data(), order.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+        c->p.tile_list_grp = c->p.tile_list + order.size();
+        c->p.unit_list = c->p.tile_list_grp + grouped.size();
+        c->p.unit_list_grp = c->p.unit_list + units.size();
         if (!grouped.empty())
-            LP_HIP(hipMemcpyAsync(c->tile_list_grp, grouped.data(), grouped.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+            LP_HIP(hipMemcpyAsync(c->p.tile_list_grp, grouped.data(), grouped.size() * sizeof(int2), hipMemcpyHostToDevice, st));
         if (!units.empty())
-            LP_HIP(hipMemcpyAsync(c->unit_list, units.data(), units.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+            LP_HIP(hipMemcpyAsync(c->p.unit_list, units.data(), units.size() * sizeof(int2), hipMemcpyHostToDevice, st));
         if (!units_grp.empty())
-            LP_HIP(hipMemcpyAsync(c->unit_list_grp, units_grp.data(), units_grp.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+            LP_HIP(hipMemcpyAsync(c->p.unit_list_grp, units_grp.data(), units_grp.size() * sizeof(int2), hipMemcpyHostToDevice, st));
         LP_HIP(hipStreamSynchronize(st));  // the lists must outlive the copies
-        if ((size_t)count > c->status_cap) {
-            if (c->status_host) (void)hipHostFree(c->status_host);
-            c->status_host = nullptr; c->status_cap = 0;
-            LP_HIP(hipHostMalloc((void**)&c->status_host, (size_t)count * sizeof(StatusRec), hipHostMallocCoherent | hipHostMallocMapped));
-            std::memset(c->status_host, 0, (size_t)count * sizeof(StatusRec));
-            c->status_cap = (size_t)count;
-        }
-        VecArgs& v = c->va;
-        v.np = np; v.mp = mp; v.nblk = c->nblk; v.nsplit = c->nsplit;
-        v.bcount = count; v.bstride = (long long)c->bstride; v.bfirst = 0; v.refine_below = refine_below();
+        LP_TRY(stream_res_grow_status(c->rs, (size_t)count));
+        VecArgs& v = c->p.va;
+        v.np = np; v.mp = mp; v.nblk = c->p.nblk; v.nsplit = c->p.nsplit;
+        v.bcount = count; v.bstride = (long long)c->p.bstride; v.bfirst = 0; v.refine_below = refine_below();
     } else {
         // same padded geometry: clear the whole state, so no stale (possibly non-finite) value of a
         // previous problem can sit in a padding lane
-        LP_HIP(hipMemsetAsync(c->arena, 0, c->arena_bytes, st));
-        if (c->a_shared) LP_HIP(hipMemsetAsync(c->a_shared, 0, c->a_shared_bytes, st));   // (a smaller m or n than before)
+        LP_HIP(hipMemsetAsync(c->p.arena, 0, c->p.arena_bytes, st));
+        if (c->p.a_shared) LP_HIP(hipMemsetAsync(c->p.a_shared, 0, c->p.a_shared_bytes, st));   // (a smaller m or n than before)
     }
-    c->m = m; c->n = n;
-    c->ns = (int)n_slack; c->nx = (int)nx;
-    c->va.n = (int)n; c->va.m = (int)m;
-    c->va.n_total = (long long)n; c->va.gs = nullptr; c->colsplit = false;   // lpipm_upload_nsplit overrides
+    c->p.m = m; c->p.n = n;
+    c->p.ns = (int)n_slack; c->p.nx = (int)nx;
+    c->p.va.n = (int)n; c->p.va.m = (int)m;
+    c->p.va.n_total = (long long)n; c->p.va.gs = nullptr; c->colsplit = false;   // lpipm_upload_nsplit overrides
     // A single LP's loop ends on the host, so its kernels need not test the done word (one dependent load
     // less at the start of ~100 short kernels) -- except the head of an iteration, which is enqueued before
     // the host has seen the previous status.  In a batch every kernel tests it.
-    c->bt = Batch{count, (long long)c->bstride, count > 1 ? c->va.done : nullptr};
-    c->bt_head = Batch{count, (long long)c->bstride, c->va.done};
-    c->va.done_chk = c->bt.done;
+    c->p.bt = Batch{count, (long long)c->p.bstride, count > 1 ? c->p.va.done : nullptr};
+    c->p.bt_head = Batch{count, (long long)c->p.bstride, c->p.va.done};
+    c->p.va.done_chk = c->p.bt.done;
     std::vector<double> c0v((size_t)count, 0.0);          // must outlive the asynchronous copies below
     for (int i = 0; i < count; ++i) c0v[i] = c0 ? c0[i] : 0.0;
     if (parts) {   // rows of A_ub, then rows of A_eq; b likewise; c = [c; 0] (the arena is zero)
         const uint64_t m_ub = parts->m_ub, m_eq = m - m_ub;
         if (m_ub) {
-            LP_HIP(hipMemcpy2DAsync(c->A, (size_t)npa * sizeof(double), parts->A_ub, (size_t)parts->lda_ub * sizeof(double),
+            LP_HIP(hipMemcpy2DAsync(c->p.A, (size_t)npa * sizeof(double), parts->A_ub, (size_t)parts->lda_ub * sizeof(double),
                                     (size_t)nx * sizeof(double), (size_t)m_ub, hipMemcpyHostToDevice, st));
-            LP_HIP(hipMemcpyAsync((void*)c->va.b, parts->b_ub, m_ub * sizeof(double), hipMemcpyHostToDevice, st));
+            LP_HIP(hipMemcpyAsync((void*)c->p.va.b, parts->b_ub, m_ub * sizeof(double), hipMemcpyHostToDevice, st));
         }
         if (m_eq) {
-            LP_HIP(hipMemcpy2DAsync(c->A + (size_t)m_ub * npa, (size_t)npa * sizeof(double), parts->A_eq,
+            LP_HIP(hipMemcpy2DAsync(c->p.A + (size_t)m_ub * npa, (size_t)npa * sizeof(double), parts->A_eq,
                                     (size_t)parts->lda_eq * sizeof(double), (size_t)nx * sizeof(double), (size_t)m_eq,
                                     hipMemcpyHostToDevice, st));
-            LP_HIP(hipMemcpyAsync((void*)(c->va.b + m_ub), parts->b_eq, m_eq * sizeof(double), hipMemcpyHostToDevice, st));
+            LP_HIP(hipMemcpyAsync((void*)(c->p.va.b + m_ub), parts->b_eq, m_eq * sizeof(double), hipMemcpyHostToDevice, st));
         }
-        LP_HIP(hipMemcpyAsync((void*)c->va.c, cc[0], nx * sizeof(double), hipMemcpyHostToDevice, st));
-        LP_HIP(hipMemcpyAsync((void*)(c->va.S + S_C0), &c0v[0], sizeof(double), hipMemcpyHostToDevice, st));
+        LP_HIP(hipMemcpyAsync((void*)c->p.va.c, cc[0], nx * sizeof(double), hipMemcpyHostToDevice, st));
+        LP_HIP(hipMemcpyAsync((void*)(c->p.va.S + S_C0), &c0v[0], sizeof(double), hipMemcpyHostToDevice, st));
     }
     if (shared)
-        LP_HIP(hipMemcpy2DAsync(c->A, (size_t)npa * sizeof(double), A[0], (size_t)lda * sizeof(double),
+        LP_HIP(hipMemcpy2DAsync(c->p.A, (size_t)npa * sizeof(double), A[0], (size_t)lda * sizeof(double),
                                 (size_t)nx * sizeof(double), (size_t)m, hipMemcpyHostToDevice, st));
     for (int i = 0; i < count && !parts; ++i) {
-        const size_t off = (size_t)i * c->bstride;
+        const size_t off = (size_t)i * c->p.bstride;
         if (!shared)
-            LP_HIP(hipMemcpy2DAsync((char*)c->A + off, (size_t)npa * sizeof(double), A[i], (size_t)lda * sizeof(double),
+            LP_HIP(hipMemcpy2DAsync((char*)c->p.A + off, (size_t)npa * sizeof(double), A[i], (size_t)lda * sizeof(double),
                                     (size_t)nx * sizeof(double), (size_t)m, hipMemcpyHostToDevice, st));
-        LP_HIP(hipMemcpyAsync((char*)c->va.b + off, b[i], m * sizeof(double), hipMemcpyHostToDevice, st));
-        LP_HIP(hipMemcpyAsync((char*)c->va.c + off, cc[i], n * sizeof(double), hipMemcpyHostToDevice, st));
-        LP_HIP(hipMemcpyAsync((char*)(c->va.S + S_C0) + off, &c0v[i], sizeof(double), hipMemcpyHostToDevice, st));
+        LP_HIP(hipMemcpyAsync((char*)c->p.va.b + off, b[i], m * sizeof(double), hipMemcpyHostToDevice, st));
+        LP_HIP(hipMemcpyAsync((char*)c->p.va.c + off, cc[i], n * sizeof(double), hipMemcpyHostToDevice, st));
+        LP_HIP(hipMemcpyAsync((char*)(c->p.va.S + S_C0) + off, &c0v[i], sizeof(double), hipMemcpyHostToDevice, st));
     }
     LP_HIP(hipStreamSynchronize(st));   // the caller's arrays and c0v are free again from here
-    c->has_problem = true;
+    c->p.has_problem = true;
     c->cnt_dirty = true;
     bind_status_pinned(c, true);
     return LPIPM_OK;
@@ -726,75 +766,75 @@ extern "C" int lpipm_upload_ub_eq(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const
 static hipError_t ctx_gemv_n(lpipm_ctx* c, int nrhs, const double* W, const double* add0, const double* add1, double* Y,
                              const Batch& bt) {
     ++c->gemv_passes;
-    if (c->shared_a) return launch_gemv_n_shared(c->A, c->npa, (int)c->m, c->npa, nrhs, W, c->np, add0, add1, Y, c->mp, c->st, bt);
-    hipError_t e = launch_gemv_n(c->A, c->npa, (int)c->m, c->npa, nrhs, W, c->np, add0, add1, Y, c->mp, c->st, 1.0, bt);
+    if (c->p.shared_a) return launch_gemv_n_shared(c->p.A, c->p.npa, (int)c->p.m, c->p.npa, nrhs, W, c->p.np, add0, add1, Y, c->p.mp, c->rs.st, bt);
+    hipError_t e = launch_gemv_n(c->p.A, c->p.npa, (int)c->p.m, c->p.npa, nrhs, W, c->p.np, add0, add1, Y, c->p.mp, c->rs.st, 1.0, bt);
     if (e != hipSuccess) return e;
-    return launch_slack_n(c->ns, c->nx, nrhs, W, c->np, Y, c->mp, c->st, bt);
+    return launch_slack_n(c->p.ns, c->p.nx, nrhs, W, c->p.np, Y, c->p.mp, c->rs.st, bt);
 }
 static hipError_t ctx_gemv_t(lpipm_ctx* c, int nrhs, const double* V, const Batch& bt) {
     ++c->gemv_passes;
-    if (c->shared_a) return launch_gemv_t_shared(c->A, c->npa, c->mp, c->npa, nrhs, V, c->mp, c->ATpart, c->st, c->np, bt);
-    hipError_t e = launch_gemv_t(c->A, c->npa, c->mp, c->npa, nrhs, V, c->mp, c->ATpart, c->st, c->np, bt);
+    if (c->p.shared_a) return launch_gemv_t_shared(c->p.A, c->p.npa, c->p.mp, c->p.npa, nrhs, V, c->p.mp, c->p.ATpart, c->rs.st, c->p.np, bt);
+    hipError_t e = launch_gemv_t(c->p.A, c->p.npa, c->p.mp, c->p.npa, nrhs, V, c->p.mp, c->p.ATpart, c->rs.st, c->p.np, bt);
     if (e != hipSuccess) return e;
-    return launch_slack_t(c->ns, c->nx, nrhs, c->nsplit, V, c->mp, c->ATpart, c->np, c->st, bt);
+    return launch_slack_t(c->p.ns, c->p.nx, nrhs, c->p.nsplit, V, c->p.mp, c->p.ATpart, c->p.np, c->rs.st, bt);
 }
 // both in one read of A: chunk slabs of A.w into AxPart (gemv_dual_chunks(npa) of them), row-split slabs of A^T.v into ATpart
 static hipError_t ctx_gemv_dual(lpipm_ctx* c, const double* W, const double* V, double* AxPart, const Batch& bt) {
     ++c->gemv_passes;
-    hipError_t e = c->shared_a ? launch_gemv_dual_shared(c->A, c->npa, c->mp, c->npa, W, V, AxPart, c->ATpart, c->np, c->st, bt)
-                               : launch_gemv_dual(c->A, c->npa, c->mp, c->npa, W, V, AxPart, c->ATpart, c->np, c->st, bt);
+    hipError_t e = c->p.shared_a ? launch_gemv_dual_shared(c->p.A, c->p.npa, c->p.mp, c->p.npa, W, V, AxPart, c->p.ATpart, c->p.np, c->rs.st, bt)
+                               : launch_gemv_dual(c->p.A, c->p.npa, c->p.mp, c->p.npa, W, V, AxPart, c->p.ATpart, c->p.np, c->rs.st, bt);
     if (e != hipSuccess) return e;
-    e = launch_slack_n(c->ns, c->nx, 1, W, c->np, AxPart, c->mp, c->st, bt);          // into chunk slab 0
+    e = launch_slack_n(c->p.ns, c->p.nx, 1, W, c->p.np, AxPart, c->p.mp, c->rs.st, bt);          // into chunk slab 0
     if (e != hipSuccess) return e;
-    return launch_slack_t(c->ns, c->nx, 1, c->nsplit, V, c->mp, c->ATpart, c->np, c->st, bt);
+    return launch_slack_t(c->p.ns, c->p.nx, 1, c->p.nsplit, V, c->p.mp, c->p.ATpart, c->p.np, c->rs.st, bt);
 }
 
 // M = A . diag(dinv) . A^T, lower tiles (newton_equations.rs:54-57); a second copy of it goes to M0 (the matrix the
 // refined Cholesky solves take their residuals against: M itself is factorised in place)
 static GemmArgs adat_args(lpipm_ctx* c, const Batch& bt) {
     GemmArgs g{};
-    g.P = c->A; g.ldp = c->npa; g.Q = c->A; g.ldq = c->npa; g.s = c->va.dinv;
-    g.C = c->M; g.ldc = c->mp; g.K = c->npa; g.alpha = 1.0; g.beta = 0.0;
-    g.ntiles = c->ntiles; g.tiles_lower = 1; g.ntj = 0; g.tile_list = c->tile_list;
-    g.diag_pad_from = (int)c->m; g.ws = c->ws; g.nwg = c->adat_nwg; g.batch = bt; g.sk_claim = c->sk_claim; g.streamk = 1;
-    g.C2 = (c->refine > 0 && gemm_streamk_split(c->npa / BK)) ? c->M0 : nullptr;    // only the refined solves need M itself
-    g.shared_a = c->shared_a;
+    g.P = c->p.A; g.ldp = c->p.npa; g.Q = c->p.A; g.ldq = c->p.npa; g.s = c->p.va.dinv;
+    g.C = c->p.M; g.ldc = c->p.mp; g.K = c->p.npa; g.alpha = 1.0; g.beta = 0.0;
+    g.ntiles = c->ap.ntiles; g.tiles_lower = 1; g.ntj = 0; g.tile_list = c->p.tile_list;
+    g.diag_pad_from = (int)c->p.m; g.ws = c->p.ws; g.nwg = c->ap.adat_nwg; g.batch = bt; g.sk_claim = c->p.sk_claim; g.streamk = 1;
+    g.C2 = (c->refine > 0 && gemm_streamk_split(c->p.npa / BK)) ? c->p.M0 : nullptr;    // only the refined solves need M itself
+    g.shared_a = c->p.shared_a;
     return g;
 }
 static AdatUnitsArgs adat_units_args(lpipm_ctx* c, const Batch& bt) {
     AdatUnitsArgs a{};
-    a.A = c->A; a.lda = c->npa; a.s = c->va.dinv; a.C = c->M; a.ldc = c->mp; a.K = c->npa;
-    a.C2 = (c->refine > 0 && c->cpt > 1) ? c->M0 : nullptr;                // only the refined solves need M itself
-    a.ntiles = c->ntiles; a.tile_list = c->tile_list; a.unit_list = c->unit_list; a.nunits = c->nunits; a.upc = c->upc;
-    a.diag_pad_from = (int)c->m; a.slabs = c->ws; a.tile_cnt = c->tile_cnt;
-    a.grp_cnt = nullptr; a.grp_w = POTRF_OUTER; a.batch = bt; a.shared_a = c->shared_a;
+    a.A = c->p.A; a.lda = c->p.npa; a.s = c->p.va.dinv; a.C = c->p.M; a.ldc = c->p.mp; a.K = c->p.npa;
+    a.C2 = (c->refine > 0 && c->ap.cpt > 1) ? c->p.M0 : nullptr;                // only the refined solves need M itself
+    a.ntiles = c->ap.ntiles; a.tile_list = c->p.tile_list; a.unit_list = c->p.unit_list; a.nunits = c->p.nunits; a.upc = c->ap.upc;
+    a.diag_pad_from = (int)c->p.m; a.slabs = c->p.ws; a.tile_cnt = c->p.tile_cnt;
+    a.grp_cnt = nullptr; a.grp_w = POTRF_OUTER; a.batch = bt; a.shared_a = c->p.shared_a;
     return a;
 }
 // clears the arrival counters (tiles and groups) of every LP of the batch
 static hipError_t clear_unit_counters(lpipm_ctx* c, const Batch& bt, hipStream_t st) {
-    char* p = (char*)c->tile_cnt + (size_t)bt.first * (size_t)bt.stride;
-    return bt.count == 1 ? hipMemsetAsync(p, 0, c->cnt_bytes, st)
-                         : hipMemset2DAsync(p, (size_t)bt.stride, 0, c->cnt_bytes, (size_t)bt.count, st);
+    char* p = (char*)c->p.tile_cnt + (size_t)bt.first * (size_t)bt.stride;
+    return bt.count == 1 ? hipMemsetAsync(p, 0, c->p.cnt_bytes, st)
+                         : hipMemset2DAsync(p, (size_t)bt.stride, 0, c->p.cnt_bytes, (size_t)bt.count, st);
 }
 static hipError_t run_adat(lpipm_ctx* c, const Batch& bt) {
     hipError_t e;
     bool second_copy;
-    if (c->units) {
+    if (c->ap.units) {
         const AdatUnitsArgs a = adat_units_args(c, bt);
-        if (c->cpt > 1 && c->cnt_dirty && (e = clear_unit_counters(c, bt, c->st)) != hipSuccess) return e;
-        if ((e = launch_adat_units(a, c->st)) != hipSuccess) return e;
+        if (c->ap.cpt > 1 && c->cnt_dirty && (e = clear_unit_counters(c, bt, c->rs.st)) != hipSuccess) return e;
+        if ((e = launch_adat_units(a, c->rs.st)) != hipSuccess) return e;
         c->cnt_dirty = false;            // the last arriver of every tile has put its word back to zero
         second_copy = a.C2 != nullptr;
     } else {
         const GemmArgs g = adat_args(c, bt);
-        if ((e = launch_gemm_nt(g, c->st)) != hipSuccess) return e;
+        if ((e = launch_gemm_nt(g, c->rs.st)) != hipSuccess) return e;
         second_copy = g.C2 != nullptr;
     }
-    e = launch_slack_diag(c->ns, c->nx, c->va.dinv, c->M, c->mp, c->st, bt);   // + diag(D_slack)
+    e = launch_slack_diag(c->p.ns, c->p.nx, c->p.va.dinv, c->p.M, c->p.mp, c->rs.st, bt);   // + diag(D_slack)
     if (e != hipSuccess) return e;
     if (c->refine <= 0) return hipSuccess;
-    if (second_copy) return launch_slack_diag(c->ns, c->nx, c->va.dinv, c->M0, c->mp, c->st, bt);
-    vec_copy_lower(c->M, c->M0, c->mp, c->mp, c->st, bt);     // short contraction: one store per tile, copied afterwards
+    if (second_copy) return launch_slack_diag(c->p.ns, c->p.nx, c->p.va.dinv, c->p.M0, c->p.mp, c->rs.st, bt);
+    vec_copy_lower(c->p.M, c->p.M0, c->p.mp, c->p.mp, c->rs.st, bt);     // short contraction: one store per tile, copied afterwards
     return hipGetLastError();
 }
 
@@ -802,37 +842,37 @@ static hipError_t run_adat(lpipm_ctx* c, const Batch& bt) {
 // with one step of iterative refinement against the matrix itself:  v0 = L^-T L^-1 r;  rho = r - M.v0 (doubled
 // precision, one read of the lower triangle);  v = v0 + L^-T L^-1 rho.  R: nrhs x mp, in/out.
 static int chol_solve_refined(lpipm_ctx* c, int nrhs, double* R, const Batch& bt) {
-    hipStream_t st = c->st;
-    if (!c->refine_now) { LP_HIP(launch_chol_solve(c->M, c->mp, c->plan, nrhs, R, c->Y, st, bt)); return LPIPM_OK; }
+    hipStream_t st = c->rs.st;
+    if (!c->refine_now) { LP_HIP(launch_chol_solve(c->p.M, c->p.mp, *c->p.factor, nrhs, R, c->p.Y, st, bt)); return LPIPM_OK; }
     // the refinement's launches skip an LP whose own word says so (a finished one, or one that does not need it yet)
-    const Batch br = c->refine == 2 ? bt : Batch{bt.count, bt.stride, c->va.skip_refine, bt.first};
-    vec_rows_copy(c->mp, nrhs, c->R0, R, st, br);
-    LP_HIP(launch_chol_solve(c->M, c->mp, c->plan, nrhs, R, c->Y, st, bt));
-    LP_HIP(launch_symv_residual(c->M0, c->mp, c->mp, nrhs, R, c->mp, c->R0, c->mp, c->Rho, c->mp, c->symv_ws, st, br));
-    LP_HIP(launch_chol_solve(c->M, c->mp, c->plan, nrhs, c->Rho, c->Y, st, br));
-    vec_rows_add(c->mp, nrhs, R, c->Rho, st, br);
+    const Batch br = c->refine == 2 ? bt : Batch{bt.count, bt.stride, c->p.va.skip_refine, bt.first};
+    vec_rows_copy(c->p.mp, nrhs, c->p.R0, R, st, br);
+    LP_HIP(launch_chol_solve(c->p.M, c->p.mp, *c->p.factor, nrhs, R, c->p.Y, st, bt));
+    LP_HIP(launch_symv_residual(c->p.M0, c->p.mp, c->p.mp, nrhs, R, c->p.mp, c->p.R0, c->p.mp, c->p.Rho, c->p.mp, c->p.symv_ws, st, br));
+    LP_HIP(launch_chol_solve(c->p.M, c->p.mp, *c->p.factor, nrhs, c->p.Rho, c->p.Y, st, br));
+    vec_rows_add(c->p.mp, nrhs, R, c->p.Rho, st, br);
     LP_HIP(hipGetLastError());
     return LPIPM_OK;
 }
 
 static int enqueue_residuals(lpipm_ctx* c, int is_init, int ip_next, double tol) {
-    VecArgs& v = c->va;
+    VecArgs& v = c->p.va;
     // A.x and A^T.y at the current point (residual.rs:23,25)
     XRank xr{xrank_fn, c};
     if (!(c->colsplit && c->world > 1)) {       // both products in one read of A
-        v.ax_chunks = gemv_dual_chunks(c->npa);
-        LP_HIP(ctx_gemv_dual(c, v.x, v.y, v.Ax, c->bt));
+        v.ax_chunks = gemv_dual_chunks(c->p.npa);
+        LP_HIP(ctx_gemv_dual(c, v.x, v.y, v.Ax, c->p.bt));
     } else {
         v.ax_chunks = 1;
-        LP_HIP(ctx_gemv_n(c, 1, v.x, nullptr, nullptr, v.Ax, c->bt));
-        LP_TRY(ctx_allreduce(c, v.Ax, c->m, 0));          // n-split: A.x = sum over ranks of A_g.x_g
-        LP_HIP(ctx_gemv_t(c, 1, v.y, c->bt));
+        LP_HIP(ctx_gemv_n(c, 1, v.x, nullptr, nullptr, v.Ax, c->p.bt));
+        LP_TRY(ctx_allreduce(c, v.Ax, c->p.m, 0));          // n-split: A.x = sum over ranks of A_g.x_g
+        LP_HIP(ctx_gemv_t(c, 1, v.y, c->p.bt));
     }
     prof_mark(c, T_GEMV);
     // small LPs: the launch goes on with the next iteration's Dinv / r_hat set-up (enqueue_head then skips it)
-    v.status_seq = (int)(++c->seq_counter & 0x7fffffffu);
+    v.status_seq = (int)(++c->rs.seq_counter & 0x7fffffffu);
     const bool with_pred = !c->colsplit && vec_fused(v);
-    LP_TRY(vec_residuals(v, is_init, ip_next, tol, c->st, c->colsplit ? &xr : nullptr, with_pred));
+    LP_TRY(vec_residuals(v, is_init, ip_next, tol, c->rs.st, c->colsplit ? &xr : nullptr, with_pred));
     c->pred_done = with_pred;
     LP_HIP(hipGetLastError());
     return LPIPM_OK;
@@ -847,18 +887,18 @@ static int enqueue_residuals(lpipm_ctx* c, int is_init, int ip_next, double tol)
 static void bind_status_pinned(lpipm_ctx* c, bool allow) {
     void* dp = nullptr;
     const char* e = lp_knob("LPIPM_STATUS_COPY");
-    const bool on = allow && !(e && e[0] == '1') && c->status_host && hipHostGetDevicePointer(&dp, c->status_host, 0) == hipSuccess;
+    const bool on = allow && !(e && e[0] == '1') && c->rs.status_host && hipHostGetDevicePointer(&dp, c->rs.status_host, 0) == hipSuccess;
     (void)hipGetLastError();
-    c->va.status_pinned = on ? (StatusRec*)dp : nullptr;
+    c->p.va.status_pinned = on ? (StatusRec*)dp : nullptr;
 }
-// Waits until the records of the LPs `idx[0 .. count)` (nullptr: record 0) carry the sequence number of the last residual
+// Waits until the records of the LPs `idx[0 .. count)` carry the sequence number of the last residual
 // launch.  Spins on the pinned records (bounded: ~10 s, then the stream is drained and the records are checked once more).
 static int wait_status(lpipm_ctx* c, const int* idx, int count) {
-    if (!c->spin_status) { LP_HIP(hipEventSynchronize(c->ev_status)); return LPIPM_OK; }
-    const int32_t want = (int32_t)c->va.status_seq;
+    if (!c->rs.spin_status) { LP_HIP(hipEventSynchronize(c->rs.ev_status)); return LPIPM_OK; }
+    const int32_t want = (int32_t)c->p.va.status_seq;
     auto arrived = [&]() {
         for (int k = 0; k < count; ++k) {
-            const StatusRec* r = c->status_host + (idx ? idx[k] : 0);
+            const StatusRec* r = c->rs.status_host + idx[k];
             if (__atomic_load_n(&r->pad_, __ATOMIC_ACQUIRE) != want) return false;
         }
         return true;
@@ -869,18 +909,18 @@ static int wait_status(lpipm_ctx* c, const int* idx, int count) {
         __builtin_ia32_pause();
         if ((spins & 0xffffu) == 0xffffu && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) break;
     }
-    LP_HIP(hipStreamSynchronize(c->st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
     if (arrived()) return LPIPM_OK;
     g_err_detail = "the status record of an iteration never reached the host";
     return LPIPM_ERR_HIP;
 }
 static int copy_status(lpipm_ctx* c) {
-    if (c->va.status_pinned) {}          // written by the kernels themselves
-    else if (c->B == 1) LP_HIP(hipMemcpyAsync(c->status_host, (const char*)c->va.status + (size_t)c->bt.first * c->bstride, sizeof(StatusRec), hipMemcpyDeviceToHost, c->st));
-    else LP_HIP(hipMemcpy2DAsync(c->status_host, sizeof(StatusRec), (const char*)c->va.status + (size_t)c->bt.first * c->bstride, c->bstride,
-                                 sizeof(StatusRec), (size_t)c->B, hipMemcpyDeviceToHost, c->st));
-    if (c->colsplit && c->grouped_reduce)   // a wait kernel that gave up (its producer never ran) says so here
-        LP_HIP(hipMemcpyAsync(c->timeout_host, c->wait_timeout, sizeof(unsigned int), hipMemcpyDeviceToHost, c->st));
+    if (c->p.va.status_pinned) {}          // written by the kernels themselves
+    else if (c->p.B == 1) LP_HIP(hipMemcpyAsync(c->rs.status_host, (const char*)c->p.va.status + (size_t)c->p.bt.first * c->p.bstride, sizeof(StatusRec), hipMemcpyDeviceToHost, c->rs.st));
+    else LP_HIP(hipMemcpy2DAsync(c->rs.status_host, sizeof(StatusRec), (const char*)c->p.va.status + (size_t)c->p.bt.first * c->p.bstride, c->p.bstride,
+                                 sizeof(StatusRec), (size_t)c->p.B, hipMemcpyDeviceToHost, c->rs.st));
+    if (c->colsplit && c->p.grouped_reduce)   // a wait kernel that gave up (its producer never ran) says so here
+        LP_HIP(hipMemcpyAsync(c->rs.timeout_host, c->p.wait_timeout, sizeof(unsigned int), hipMemcpyDeviceToHost, c->rs.st));
     return LPIPM_OK;
 }
 
@@ -892,14 +932,14 @@ static int copy_status(lpipm_ctx* c) {
 // next instead of idling through the read-back, and if the LP turns out to be finished the two kernels return
 // at once.
 static int enqueue_head(lpipm_ctx* c) {
-    hipStream_t st = c->st;
-    VecArgs vh = c->va;
-    vh.done_chk = c->bt_head.done;
+    hipStream_t st = c->rs.st;
+    VecArgs vh = c->p.va;
+    vh.done_chk = c->p.bt_head.done;
     prof_mark(c, T_VEC);
     if (c->pred_done) c->pred_done = false;       // the residual launch in front of this head has done it (enqueue_residuals)
     else vec_pred_setup(vh, st);
     prof_mark(c, T_VEC, true);
-    if (c->colsplit && c->world > 1 && c->grouped_reduce && c->st_c) {
+    if (c->colsplit && c->world > 1 && c->p.grouped_reduce && c->st_c) {
         // n-split, M = sum_g A_g D_g A_g^T, PIPELINED: one A.D.A^T launch in column-group-major order on the solver's stream;
         // the workgroup that completes a group's last tile bumps the group's word; on the communication stream a one-wave
         // kernel waits for that word, the group's tiles are packed, summed over the ranks (the caller's all-reduce) and
@@ -909,34 +949,34 @@ static int enqueue_head(lpipm_ctx* c) {
         // the caller's all-reduce sums an element's terms in an order that does not depend on where the element sits in
         // the buffer (a ring all-reduce such as gloo's does not: last-bit differences between the two ways).
         hipStream_t sc = c->st_c;
-        const Batch& bt = c->bt_head;
+        const Batch& bt = c->p.bt_head;
         LP_HIP(clear_unit_counters(c, bt, st));
         c->cnt_dirty = true;
         LP_HIP(hipEventRecord(c->ev_c0, st));
         LP_HIP(hipStreamWaitEvent(sc, c->ev_c0, 0));
         AdatUnitsArgs a = adat_units_args(c, bt);
-        a.tile_list = c->tile_list_grp; a.unit_list = c->unit_list_grp; a.nunits = c->nunits_grp; a.upc = 1;
-        a.grp_cnt = c->grp_cnt; a.C2 = nullptr;
+        a.tile_list = c->p.tile_list_grp; a.unit_list = c->p.unit_list_grp; a.nunits = c->p.nunits_grp; a.upc = 1;
+        a.grp_cnt = c->p.grp_cnt; a.C2 = nullptr;
         LP_HIP(launch_adat_units(a, st));
-        for (size_t g = 0; g < c->grp_nt.size(); ++g) {
-            double* slice = c->mpack + (size_t)c->grp_off[g] * TILE * TILE;
-            LP_HIP(launch_wait_count(c->grp_cnt + g, (unsigned)c->grp_nt[g], bt.done, c->wait_timeout, sc));
-            vec_pack_tiles(c->M, c->mp, c->tile_list_grp + c->grp_off[g], c->grp_nt[g], slice, 0, sc);
-            LP_TRY(ctx_allreduce(c, slice, (uint64_t)c->grp_nt[g] * TILE * TILE, 0, sc));
-            vec_pack_tiles(c->M, c->mp, c->tile_list_grp + c->grp_off[g], c->grp_nt[g], slice, 1, sc);
+        for (size_t g = 0; g < c->p.grp_nt.size(); ++g) {
+            double* slice = c->mpack + (size_t)c->p.grp_off[g] * TILE * TILE;
+            LP_HIP(launch_wait_count(c->p.grp_cnt + g, (unsigned)c->p.grp_nt[g], bt.done, c->p.wait_timeout, sc));
+            vec_pack_tiles(c->p.M, c->p.mp, c->p.tile_list_grp + c->p.grp_off[g], c->p.grp_nt[g], slice, 0, sc);
+            LP_TRY(ctx_allreduce(c, slice, (uint64_t)c->p.grp_nt[g] * TILE * TILE, 0, sc));
+            vec_pack_tiles(c->p.M, c->p.mp, c->p.tile_list_grp + c->p.grp_off[g], c->p.grp_nt[g], slice, 1, sc);
         }
         LP_HIP(hipEventRecord(c->ev_c1, sc));
         LP_HIP(hipStreamWaitEvent(st, c->ev_c1, 0));
-        if (c->refine > 0) vec_copy_lower(c->M, c->M0, c->mp, c->mp, st, c->bt_head);   // the summed matrix, for the refined solves
+        if (c->refine > 0) vec_copy_lower(c->p.M, c->p.M0, c->p.mp, c->p.mp, st, c->p.bt_head);   // the summed matrix, for the refined solves
         prof_mark(c, T_ADAT, true);
         return LPIPM_OK;
     }
-    LP_HIP(run_adat(c, c->bt_head));                                       // newton_equations.rs:55-57
+    LP_HIP(run_adat(c, c->p.bt_head));                                       // newton_equations.rs:55-57
     if (c->colsplit && c->world > 1) {                                     // n-split: M = sum_g A_g D_g A_g^T
-        vec_pack_lower(c->M, c->mp, c->mp, c->mpack, 0, st);
+        vec_pack_lower(c->p.M, c->p.mp, c->p.mp, c->mpack, 0, st);
         LP_TRY(ctx_allreduce(c, c->mpack, c->mpack_count, 0));
-        vec_pack_lower(c->M, c->mp, c->mp, c->mpack, 1, st);
-        if (c->refine > 0) vec_copy_lower(c->M, c->M0, c->mp, c->mp, st, c->bt_head);   // the summed matrix, for the refined solves
+        vec_pack_lower(c->p.M, c->p.mp, c->p.mp, c->mpack, 1, st);
+        if (c->refine > 0) vec_copy_lower(c->p.M, c->p.M0, c->p.mp, c->p.mp, st, c->p.bt_head);   // the summed matrix, for the refined solves
     }
     prof_mark(c, T_ADAT, true);
     return LPIPM_OK;
@@ -947,27 +987,27 @@ static const PotrfLookahead* lookahead(lpipm_ctx* c) { return c->la.side ? &c->l
 
 // The rest of the iteration, ending with the status record on its way to the host and ev_status behind it.
 static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
-    VecArgs& v = c->va;
-    hipStream_t st = c->st;
+    VecArgs& v = c->p.va;
+    hipStream_t st = c->rs.st;
     XRank xr_{xrank_fn, c};
     const XRank* xr = c->colsplit ? &xr_ : nullptr;
-    const Batch& bt = c->bt;
+    const Batch& bt = c->p.bt;
     const bool chol = o->solver_type == LPIPM_SOLVER_CHOLESKY;
     // (no clearing of the pivot-failure word: k_blind_start and every k_scalar_indicators leave it zero)
-    if (chol) LP_HIP(launch_potrf(c->M, c->mp, c->mp, c->plan, v.potrf_info, st, bt, lookahead(c), false));   // :129-131
-    else      LP_HIP(launch_qr_factor(c->M, c->mp, c->mp, c->tau, v.potrf_info, st));        // :133-149
+    if (chol) LP_HIP(launch_potrf(c->p.M, c->p.mp, c->p.mp, *c->p.factor, v.potrf_info, st, bt, lookahead(c), false));   // :129-131
+    else      LP_HIP(launch_qr_factor(c->p.M, c->p.mp, c->p.mp, c->p.tau, v.potrf_info, st));        // :133-149
     prof_mark(c, T_POTRF);
     // predictor: both sym_solve calls of solve_newton_equations (:187-188) in one pass each
     if (!c->colsplit) {
         LP_HIP(ctx_gemv_n(c, 2, v.W, v.b, v.rP, v.R, bt));  // :220
     } else {   // the addend r2 enters once, after the cross-rank sum of the column-split products
         LP_HIP(ctx_gemv_n(c, 2, v.W, nullptr, nullptr, v.R, bt));
-        LP_TRY(ctx_allreduce(c, v.R, (uint64_t)2 * c->mp, 0));
-        vec_add_rows((int)c->m, 2, v.R, c->mp, v.b, v.rP, st);
+        LP_TRY(ctx_allreduce(c, v.R, (uint64_t)2 * c->p.mp, 0));
+        vec_add_rows((int)c->p.m, 2, v.R, c->p.mp, v.b, v.rP, st);
     }
     prof_mark(c, T_GEMV);
     if (chol) LP_TRY(chol_solve_refined(c, 2, v.R, bt));                                    // :221, :154
-    else      LP_HIP(launch_qr_solve(c->M, c->mp, c->mp, c->tau, 2, v.R, v.potrf_info, st));   // :155-166
+    else      LP_HIP(launch_qr_solve(c->p.M, c->p.mp, c->p.mp, c->p.tau, 2, v.R, v.potrf_info, st));   // :155-166
     prof_mark(c, T_TRSV);
     LP_HIP(ctx_gemv_t(c, 2, v.R, bt));              // :223
     prof_mark(c, T_GEMV);
@@ -983,12 +1023,12 @@ static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
         LP_HIP(ctx_gemv_n(c, 1, v.W, v.rP2, nullptr, v.R, bt));
     } else {
         LP_HIP(ctx_gemv_n(c, 1, v.W, nullptr, nullptr, v.R, bt));
-        LP_TRY(ctx_allreduce(c, v.R, c->mp, 0));
-        vec_add_rows((int)c->m, 1, v.R, c->mp, v.rP2, nullptr, st);
+        LP_TRY(ctx_allreduce(c, v.R, c->p.mp, 0));
+        vec_add_rows((int)c->p.m, 1, v.R, c->p.mp, v.rP2, nullptr, st);
     }
     prof_mark(c, T_GEMV);
     if (chol) LP_TRY(chol_solve_refined(c, 1, v.R, bt));
-    else      LP_HIP(launch_qr_solve(c->M, c->mp, c->mp, c->tau, 1, v.R, v.potrf_info, st));
+    else      LP_HIP(launch_qr_solve(c->p.M, c->p.mp, c->p.mp, c->p.tau, 1, v.R, v.potrf_info, st));
     prof_mark(c, T_TRSV);
     LP_HIP(ctx_gemv_t(c, 1, v.R, bt));
     prof_mark(c, T_GEMV);
@@ -1002,7 +1042,7 @@ static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
     LP_TRY(enqueue_residuals(c, 0, 0, o->tol));   // mod.rs:225
     LP_TRY(copy_status(c));
     prof_mark(c, T_VEC);
-    if (!c->spin_status) LP_HIP(hipEventRecord(c->ev_status, st));
+    if (!c->rs.spin_status) LP_HIP(hipEventRecord(c->rs.ev_status, st));
     return LPIPM_OK;
 }
 
@@ -1015,54 +1055,98 @@ static void print_row(double alpha, const StatusRec& s) {  // mod.rs:228 + indic
     printf("%.8f\t%.8f\t%.8f\t%.8f\t%.8f\t%8.3f\n", alpha, s.rho_p, s.rho_d, s.rho_g, s.rho_mu, s.obj);
 }
 
-static int solve_impl(lpipm_ctx* c, const lpipm_opts* o, double* x_host, void* x_dev, double* fun_out,
-                      uint64_t* iters_out, lpipm_iter_row* log) {
+// Where the solutions go: per-member host pointers, or rows of one device buffer.
+struct XOut {
+    double* const* host = nullptr;
+    char* dev = nullptr;
+    size_t stride_bytes = 0;
+    bool valid() const { return host || dev; }
+};
+
+// The return code a status record stands for, -1 while the LP goes on iterating.
+static int status_code(const StatusRec& s) {
+    // EquationSolverType::build failure (newton_equations.rs:58-63) and the NaN check on p, q
+    // (:190-194) both surface as NumericalProblem from get_delta (mod.rs:215)
+    if (s.potrf_info != 0 || (s.flags & FLAG_NAN_PQ)) return LPIPM_NUMERICAL_PROBLEM;
+    if (s.status == ST_OPTIMAL) return LPIPM_OK;               // mod.rs:231
+    if (s.status == ST_INFEASIBLE) return LPIPM_INFEASIBLE;    // :232
+    if (s.status == ST_UNBOUNDED) return LPIPM_UNBOUNDED;      // :233
+    return -1;
+}
+static bool has_x(int code) { return code == LPIPM_OK || code == LPIPM_ITERATION_LIMIT; }
+
+// The interior-point loop (solve_normal_form, mod.rs:199-240) for the B >= 1 LPs that c -- a context or a half-batch view --
+// covers; member i's return code, objective (NAN without a solution) and iteration count go to status_out[i], fun_out[i]
+// and its_out[i], its solution to row rows[i] of xo (row i when rows is null).
+// batch == false: the one LP of lpipm_solve / lpipm_solve_device (any solver arm, column split, `disp` table, iteration log).
+// batch == true, a lockstep batch: B LPs of one shape resident at once (upload_impl with count = B), every launch of the
+// iteration covering all of them (gridDim.z = B).  The ~100 dependent launches per iteration -- the
+// latency floor of a small LP -- are then paid once per B LPs.  LPs finish at different iterations:
+// k_scalar_indicators sets an LP's `done` word on the conditions that end the reference's loop
+// (mod.rs:215, :231-233) and every later kernel skips it, so its iterate stays what it was; the host
+// mirrors the same decisions from the status records to count iterations and pick the return codes.
+static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XOut& xo, const uint64_t* rows, double* fun_out,
+                         uint64_t* its_out, int32_t* status_out, lpipm_iter_row* log) {
     if (!c || !o) return LPIPM_ERR_BAD_ARGUMENT;
     // InteriorPointBuilder::build, mod.rs:118-128
     if (!(o->alpha0 > 0.0) || !(o->alpha0 < 1.0)) return LPIPM_INVALID_PARAMETER;
     if (!(o->tol > 0.0)) return LPIPM_INVALID_PARAMETER;
-    if (o->solver_type < 0 || o->solver_type > 2) return LPIPM_INVALID_PARAMETER;
-    if (!c->has_problem) return LPIPM_ERR_NO_PROBLEM;
-    if (c->B != 1) return LPIPM_ERR_BAD_ARGUMENT;   // a lockstep batch is solved by solve_lockstep
-    if (o->solver_type != LPIPM_SOLVER_CHOLESKY && c->mp > 16384) return LPIPM_ERR_UNSUPPORTED;  // QR solve keeps the rhs in LDS
+    if (batch) {
+        if (o->solver_type != LPIPM_SOLVER_CHOLESKY) return LPIPM_ERR_UNSUPPORTED;      // the QR arms are single-LP
+        if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+        if (c->colsplit) return LPIPM_ERR_UNSUPPORTED;
+    } else {
+        if (o->solver_type < 0 || o->solver_type > 2) return LPIPM_INVALID_PARAMETER;
+        if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+        if (c->p.B != 1) return LPIPM_ERR_BAD_ARGUMENT;   // a lockstep batch is solved by solve_lockstep
+        if (o->solver_type != LPIPM_SOLVER_CHOLESKY && c->p.mp > 16384) return LPIPM_ERR_UNSUPPORTED;  // QR solve keeps the rhs in LDS
+    }
     LP_HIP(hipSetDevice(c->device));
-    VecArgs& v = c->va;
-    hipStream_t st = c->st;
+    const int B = c->p.B;
+    VecArgs& v = c->p.va;
+    StreamRes& rs = c->rs;
+    hipStream_t st = rs.st;
+    // profiling (lpipm_set_profiling): a phase's time is that of the launch, which covers all B members
     for (int t = 0; t < T_NTAGS; ++t) c->tag_ms[t] = 0.0;
     c->times = lpipm_phase_times{};
-    c->nmarks = 0;
+    rs.nmarks = 0;
     c->gemv_passes = 0;
-    uint64_t adat_launches = 0;
-    if (c->profiling) LP_HIP(hipEventRecord(c->ev_begin, st));
+    uint64_t loop_iterations = 0;
+    if (c->profiling) LP_HIP(hipEventRecord(rs.ev_begin, st));
 
     vec_blind_start(v, st);                               // feasible_point.rs:24-31
     prof_mark(c, T_VEC);
     LP_TRY(enqueue_residuals(c, 1, o->ip ? 1 : 0, o->tol));  // feasible_point.rs:32, mod.rs:206
-    LP_TRY(copy_status(c));
+    if (!batch) LP_TRY(copy_status(c));                   // (only a single LP's starting record is ever read, below)
     prof_mark(c, T_VEC);
-    // the host needs the starting point's indicators only for the `disp` table, for the selective refinement's first decision
-    // and for the phase marks: otherwise the first iteration is enqueued without a round trip to the host (~25 us per solve)
-    const bool need_start_row = o->disp || c->refine == 1 || c->profiling == 1;   // (profiling 2 brackets A.D.A^T only: no mark yet)
-    if (need_start_row) {
+    // A single LP: the host needs the starting point's indicators only for the `disp` table, for the selective refinement's
+    // first decision and for the phase marks: otherwise the first iteration is enqueued without a round trip to the host
+    // (~25 us per solve; profiling 2 brackets A.D.A^T only: no mark yet).  A batch: nothing of the starting point is read by
+    // the host; it waits here whenever it profiles.
+    const bool wait_start = batch ? c->profiling != 0 : (o->disp || c->refine == 1 || c->profiling == 1);
+    if (wait_start) {
         LP_HIP(hipStreamSynchronize(st));
         prof_collect(c);
     }
-    if (o->disp) {                                        // mod.rs:208-211
+    if (!batch && o->disp) {                              // mod.rs:208-211
         printf("alpha     \trho_p     \trho_d     \trho_g     \trho_mu    \tobj       \n");
-        print_row(1.0, *c->status_host);
+        print_row(1.0, *rs.status_host);
     }
-    c->refine_now = c->refine == 2 || (c->refine == 1 && c->status_host->rho_mu <= refine_below());
-    int ip = o->ip ? 1 : 0;
-    int ret = LPIPM_ITERATION_LIMIT;
-    uint64_t iteration = 0;
+    // (selective mode: at the starting point mu / mu_0 = 1, so no member of a batch refines its first iteration)
+    c->refine_now = c->refine == 2 || (!batch && c->refine == 1 && rs.status_host->rho_mu <= refine_below());
     // the head of iteration k+1 goes out before the status of iteration k is read (see enqueue_head); not when the
     // iteration contains host-side collectives
     const bool speculate = !c->colsplit;
-    // (with every phase bracketed -- profiling 1 -- the last mark of an iteration is recorded BEHIND the indicators kernel and
-    //  has to have completed when it is read: the event wait stays; profiling 2's two marks sit in front of it)
-    c->spin_status = speculate && c->va.status_pinned != nullptr && c->profiling != 1;
+    // (a single LP with every phase bracketed -- profiling 1 -- : the last mark of an iteration is recorded BEHIND the indicators
+    //  kernel and has to have completed when it is read: the event wait stays; profiling 2's two marks sit in front of it.  A
+    //  batch keeps the event wait in both profiling modes.)
+    rs.spin_status = speculate && v.status_pinned != nullptr && (batch ? !c->profiling : c->profiling != 1);
+    std::vector<int> ret((size_t)B, -1), act((size_t)B);        // -1: still iterating; act[0 .. running): those members, ascending
+    std::vector<uint64_t> its((size_t)B, 0);
+    for (int i = 0; i < B; ++i) act[(size_t)i] = i;
+    int running = B, ip = o->ip ? 1 : 0;
     bool head_out = false;
-    for (iteration = 1; iteration <= o->max_iter; ++iteration) {   // mod.rs:213
+    for (uint64_t iteration = 1; iteration <= o->max_iter && running > 0; ++iteration) {   // mod.rs:213
         if (!speculate) {
             LP_TRY(enqueue_iteration(c, ip, o));
             LP_HIP(hipStreamSynchronize(st));
@@ -1070,81 +1154,115 @@ static int solve_impl(lpipm_ctx* c, const lpipm_opts* o, double* x_host, void* x
         } else {
             if (!head_out) LP_TRY(enqueue_head(c));
             LP_TRY(enqueue_tail(c, ip, o));
-            const size_t marks = c->nmarks;
+            const size_t marks = rs.nmarks;
             head_out = iteration < o->max_iter;
-            if (head_out) LP_TRY(enqueue_head(c));
-            LP_TRY(wait_status(c, nullptr, 1));
+            if (head_out) LP_TRY(enqueue_head(c));       // next iteration's A.D.A^T, before this one's status is read
+            // the members that were still running when this iteration was enqueued write a record; the others are skipped
+            LP_TRY(wait_status(c, act.data(), running));
             prof_collect(c, marks);
         }
-        ++adat_launches;
-        if (c->colsplit && c->grouped_reduce && *c->timeout_host != 0) {
+        ++loop_iterations;
+        if (c->colsplit && c->p.grouped_reduce && *rs.timeout_host != 0) {
             g_err_detail = "a column group of A.D.A^T did not complete within the wait kernel's bound";
             LP_HIP(hipStreamSynchronize(st));
             return LPIPM_ERR_HIP;
         }
-        const StatusRec s = *c->status_host;
-        // EquationSolverType::build failure (newton_equations.rs:58-63) and the NaN check on p, q
-        // (:190-194) both surface as NumericalProblem from get_delta (mod.rs:215)
-        if (s.potrf_info != 0 || (s.flags & FLAG_NAN_PQ)) { ret = LPIPM_NUMERICAL_PROBLEM; break; }
-        c->refine_now = c->refine == 2 || (c->refine == 1 && s.rho_mu <= refine_below());   // the next iteration's solves
         ip = 0;                                                    // mod.rs:223
-        if (o->disp) print_row(s.alpha, s);
-        if (log) {
-            lpipm_iter_row& r = log[iteration - 1];
-            r.alpha = s.alpha; r.rho_p = s.rho_p; r.rho_d = s.rho_d; r.rho_A = s.rho_A;
-            r.rho_g = s.rho_g; r.rho_mu = s.rho_mu; r.obj = s.obj;
-        }
-        if (s.status == ST_OPTIMAL) { ret = LPIPM_OK; break; }             // mod.rs:231
-        if (s.status == ST_INFEASIBLE) { ret = LPIPM_INFEASIBLE; break; }   // :232
-        if (s.status == ST_UNBOUNDED) { ret = LPIPM_UNBOUNDED; break; }     // :233
-    }
-    if (ret == LPIPM_ITERATION_LIMIT) iteration = o->max_iter;
-    if (ret == LPIPM_OK || ret == LPIPM_ITERATION_LIMIT) {
-        XRank xrf{xrank_fn, c};
-        LP_TRY(vec_final_x(v, c->xout, st, c->colsplit ? &xrf : nullptr));   // mod.rs:231/238, :165
-        LP_HIP(hipGetLastError());
-        if (x_dev) LP_HIP(hipMemcpyAsync(x_dev, c->xout, c->n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        if (x_host) {   // through a pinned buffer: truly asynchronous, one synchronisation for x and the status record
-            if (c->x_pinned_cap < c->n) {
-                if (c->x_pinned) (void)hipHostFree(c->x_pinned);
-                c->x_pinned = nullptr; c->x_pinned_cap = 0;
-                LP_HIP(hipHostMalloc((void**)&c->x_pinned, c->n * sizeof(double)));
-                c->x_pinned_cap = c->n;
+        // the refinement launches of the next iteration are enqueued if ANY running member asks for them; which members
+        // they touch is each member's own device word (k_scalar_indicators), the same decision as when it is solved alone
+        bool any_refines = false;
+        int still = 0;
+        for (int k = 0; k < running; ++k) {
+            const int i = act[(size_t)k];
+            const StatusRec s = rs.status_host[i];
+            const int code = status_code(s);
+            if (!batch && code != LPIPM_NUMERICAL_PROBLEM) {       // (get_delta fails before the row of its iteration exists)
+                if (o->disp) print_row(s.alpha, s);
+                if (log) {
+                    lpipm_iter_row& r = log[iteration - 1];
+                    r.alpha = s.alpha; r.rho_p = s.rho_p; r.rho_d = s.rho_d; r.rho_A = s.rho_A;
+                    r.rho_g = s.rho_g; r.rho_mu = s.rho_mu; r.obj = s.obj;
+                }
             }
-            LP_HIP(hipMemcpyAsync(c->x_pinned, c->xout, c->n * sizeof(double), hipMemcpyDeviceToHost, st));
+            if (code >= 0) { ret[(size_t)i] = code; its[(size_t)i] = iteration; continue; }
+            act[(size_t)still++] = i;
+            any_refines = any_refines || (c->refine == 1 && s.rho_mu <= refine_below());
+        }
+        running = still;
+        c->refine_now = c->refine == 2 || any_refines;
+    }
+    for (int i = 0; i < B; ++i)
+        if (ret[(size_t)i] < 0) { ret[(size_t)i] = LPIPM_ITERATION_LIMIT; its[(size_t)i] = o->max_iter; }   // mod.rs:237-239
+    // x (mod.rs:231/238, :165): one launch for every LP of a batch; none for a single LP that has no solution
+    double* bounced = nullptr;
+    if (batch || has_x(ret[0])) {
+        XRank xrf{xrank_fn, c};
+        LP_TRY(vec_final_x(v, c->p.xout, st, c->colsplit ? &xrf : nullptr));
+        LP_HIP(hipGetLastError());
+        const size_t xbytes = c->p.n * sizeof(double);
+        for (int i = 0; i < B; ++i) {
+            if (!has_x(ret[(size_t)i])) continue;
+            const uint64_t row = rows ? rows[i] : (uint64_t)i;
+            const char* src = (const char*)c->p.xout + (size_t)(c->p.bt.first + i) * c->p.bstride;
+            if (xo.dev) LP_HIP(hipMemcpyAsync(xo.dev + row * xo.stride_bytes, src, xbytes, hipMemcpyDeviceToDevice, st));
+            else if (!xo.host[row]) continue;
+            else if (batch) LP_HIP(hipMemcpyAsync(xo.host[row], src, xbytes, hipMemcpyDeviceToHost, st));
+            else {   // a single LP: through a pinned buffer -- truly asynchronous, one synchronisation for x and the status record
+                if (rs.x_pinned_cap < c->p.n) {
+                    if (rs.x_pinned) (void)hipHostFree(rs.x_pinned);
+                    rs.x_pinned = nullptr; rs.x_pinned_cap = 0;
+                    LP_HIP(hipHostMalloc((void**)&rs.x_pinned, xbytes));
+                    rs.x_pinned_cap = c->p.n;
+                }
+                LP_HIP(hipMemcpyAsync(rs.x_pinned, src, xbytes, hipMemcpyDeviceToHost, st));
+                bounced = xo.host[row];
+            }
         }
         LP_TRY(copy_status(c));
-        if (c->profiling) LP_HIP(hipEventRecord(c->ev_end, st));
-        LP_HIP(hipStreamSynchronize(st));
-        if (x_host) std::memcpy(x_host, c->x_pinned, c->n * sizeof(double));
-        if (fun_out) *fun_out = c->status_host->obj;
-    } else {
-        if (c->profiling) LP_HIP(hipEventRecord(c->ev_end, st));
-        LP_HIP(hipStreamSynchronize(st));
     }
-    if (iters_out) *iters_out = iteration;
+    if (c->profiling) LP_HIP(hipEventRecord(rs.ev_end, st));
+    LP_HIP(hipStreamSynchronize(st));
+    if (bounced) std::memcpy(bounced, rs.x_pinned, c->p.n * sizeof(double));
     if (c->profiling) {
         float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, c->ev_begin, c->ev_end);
+        (void)hipEventElapsedTime(&ms, rs.ev_begin, rs.ev_end);
         c->times.total_ms = ms;
         c->times.adat_ms = c->tag_ms[T_ADAT]; c->times.potrf_ms = c->tag_ms[T_POTRF];
         c->times.trsv_ms = c->tag_ms[T_TRSV]; c->times.gemv_ms = c->tag_ms[T_GEMV];
         c->times.vec_ms = c->tag_ms[T_VEC];
-        c->times.adat_launches = adat_launches; c->times.iterations = iteration;
+        c->times.adat_launches = loop_iterations;      // launches of the kernel (each covers all B members)
+        c->times.iterations = loop_iterations;         // iterations of the loop (= the slowest member's count)
         // the speculatively enqueued head of the iteration after the last holds no GEMV pass: every counted pass ran
         c->times.gemv_passes = c->gemv_passes;
     }
-    return ret;
+    for (int i = 0; i < B; ++i) {
+        status_out[i] = ret[(size_t)i];
+        if (fun_out) fun_out[i] = has_x(ret[(size_t)i]) ? rs.status_host[i].obj : NAN;
+        if (its_out) its_out[i] = its[(size_t)i];
+    }
+    return LPIPM_OK;
 }
 
+// One LP: the return code is the LP's own, and fun_out stays untouched when it has no solution.
+static int solve_single(lpipm_ctx* c, const lpipm_opts* o, double* x_host, void* x_dev, double* fun_out,
+                        uint64_t* iters_out, lpipm_iter_row* log) {
+    XOut xo; xo.host = &x_host; xo.dev = (char*)x_dev;
+    double fun = NAN;
+    uint64_t its = 0;
+    int32_t code = LPIPM_OK;
+    LP_TRY(solve_members(c, o, false, xo, nullptr, &fun, &its, &code, log));
+    if (fun_out && has_x(code)) *fun_out = fun;
+    if (iters_out) *iters_out = its;
+    return code;
+}
 extern "C" int lpipm_solve(lpipm_ctx* c, const lpipm_opts* o, double* x_slack_out, double* fun_out,
                            uint64_t* iterations_out, lpipm_iter_row* log) {
     if (!x_slack_out) return LPIPM_ERR_BAD_ARGUMENT;
-    return solve_impl(c, o, x_slack_out, nullptr, fun_out, iterations_out, log);
+    return solve_single(c, o, x_slack_out, nullptr, fun_out, iterations_out, log);
 }
 extern "C" int lpipm_solve_device(lpipm_ctx* c, const lpipm_opts* o, void* x_dev_out, double* fun_out,
                                   uint64_t* iterations_out, lpipm_iter_row* log) {
-    return solve_impl(c, o, nullptr, x_dev_out, fun_out, iterations_out, log);
+    return solve_single(c, o, nullptr, x_dev_out, fun_out, iterations_out, log);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1152,70 +1270,28 @@ extern "C" int lpipm_solve_device(lpipm_ctx* c, const lpipm_opts* o, void* x_dev
 static void destroy_views(lpipm_ctx* c) {
     for (lpipm_ctx* v : c->halves) {
         (void)hipSetDevice(v->device);
-        if (v->st) { (void)hipStreamSynchronize(v->st); (void)hipStreamDestroy(v->st); }
-        for (hipEvent_t e : v->events) (void)hipEventDestroy(e);
-        if (v->ev_begin) (void)hipEventDestroy(v->ev_begin);
-        if (v->ev_end) (void)hipEventDestroy(v->ev_end);
-        if (v->ev_status) (void)hipEventDestroy(v->ev_status);
-        if (v->status_host) (void)hipHostFree(v->status_host);
-        if (v->timeout_host) (void)hipHostFree(v->timeout_host);
-        v->plan = FactorPlan{};            // shares the parent's descriptors: never destroyed here
+        stream_res_destroy(v->rs);         // all that a view owns
         delete v;
     }
     c->halves.clear();
 }
-// A view of the LPs [first, first + count) of c's resident batch: the same device state (every pointer stays LP 0's), its own
-// stream, events and pinned status records.
+// A view of the LPs [first, first + count) of c's resident batch: a copy of the problem (the same device state: every pointer
+// stays LP 0's) and of the A.D.A^T plan, and its own stream, events and pinned status records.
 static lpipm_ctx* make_view(const lpipm_ctx* c, int first, int count) {
-    lpipm_ctx* v = new lpipm_ctx(*c);
+    lpipm_ctx* v = new lpipm_ctx();
+    if (stream_res_create(v->rs, (size_t)count) != LPIPM_OK) { delete v; return nullptr; }
     v->is_view = true;
-    v->cnt_dirty = true;
-    v->halves.clear(); v->workers.clear(); v->kallocs.clear();
-    v->events.clear(); v->mark_tags.clear(); v->nmarks = 0;
-    v->la = PotrfLookahead{};
-    v->st = nullptr;
-    v->ev_begin = v->ev_end = v->ev_status = nullptr; v->status_host = nullptr; v->timeout_host = nullptr;
-    v->x_pinned = nullptr; v->x_pinned_cap = 0;
-    v->mpack = nullptr; v->kM = v->kM0 = v->kR = v->kY = nullptr; v->kmp = 0; v->kplan = FactorPlan{};
-    v->profiling = 0;
-    v->B = count;
-    v->bt = Batch{count, (long long)c->bstride, c->va.done, first};
-    v->bt_head = v->bt;
-    v->va.bcount = count; v->va.bfirst = first; v->va.done_chk = c->va.done;
-    v->status_cap = (size_t)count;
-    if (hipStreamCreateWithFlags(&v->st, hipStreamNonBlocking) != hipSuccess ||
-        hipHostMalloc((void**)&v->status_host, (size_t)count * sizeof(StatusRec), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
-        hipHostMalloc((void**)&v->timeout_host, sizeof(unsigned int)) != hipSuccess ||
-        hipEventCreate(&v->ev_begin) != hipSuccess || hipEventCreate(&v->ev_end) != hipSuccess ||
-        hipEventCreateWithFlags(&v->ev_status, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        lpipm_ctx tmp_owner;               // release what was made
-        tmp_owner.halves.push_back(v);
-        destroy_views(&tmp_owner);
-        return nullptr;
-    }
-    *v->timeout_host = 0;
-    std::memset(v->status_host, 0, (size_t)count * sizeof(StatusRec));
-    v->seq_counter = 0; v->spin_status = false;
-    bind_status_pinned(v, c->va.status_pinned != nullptr);
+    v->device = c->device; v->num_cu = c->num_cu; v->refine = c->refine;
+    v->ap = c->ap;
+    v->p = c->p;
+    v->p.B = count;
+    v->p.bt = Batch{count, (long long)c->p.bstride, c->p.va.done, first};
+    v->p.bt_head = v->p.bt;
+    v->p.va.bcount = count; v->p.va.bfirst = first; v->p.va.done_chk = c->p.va.done;
+    bind_status_pinned(v, c->p.va.status_pinned != nullptr);
     return v;
 }
 
-// Lockstep batch: B LPs of one shape resident at once (upload_impl with count = B), every launch of the
-// iteration covering all of them (gridDim.z = B).  The ~100 dependent launches per iteration -- the
-// latency floor of a small LP -- are then paid once per B LPs.  LPs finish at different iterations:
-// k_scalar_indicators sets an LP's `done` word on the conditions that end the reference's loop
-// (mod.rs:215, :231-233) and every later kernel skips it, so its iterate stays what it was; the host
-// mirrors the same decisions from the status records to count iterations and pick the return codes.
-// Where the solutions of a batch go: per-member host pointers, or rows of one device buffer.
-struct XOut {
-    double* const* host = nullptr;
-    char* dev = nullptr;
-    size_t stride_bytes = 0;
-    bool valid() const { return host || dev; }
-};
-static int solve_lockstep_one(lpipm_ctx* c, const lpipm_opts* o, const XOut& xo, const uint64_t* rows, double* fun_out,
-                              uint64_t* its_out, int32_t* status_out);
 // A batch of at least 16 members is solved as TWO half-batches, each by its own host thread on its own stream (views of the
 // context): the halves drift out of phase, and one half's A.D.A^T (MFMA-bound, fills the chip) runs beside the other half's
 // factorisation chain, solves and passes over A (latency- and HBM-bound).  Every member goes through exactly the kernels
@@ -1225,127 +1301,34 @@ static int solve_lockstep_one(lpipm_ctx* c, const lpipm_opts* o, const XOut& xo,
 static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const XOut& xo, const uint64_t* rows, double* fun_out,
                           uint64_t* its_out, int32_t* status_out) {
     if (!c || !o || !xo.valid() || !status_out) return LPIPM_ERR_BAD_ARGUMENT;
-    if (c->is_view || !c->halves_env || c->profiling || c->B < 16 || !c->has_problem || c->colsplit)
-        return solve_lockstep_one(c, o, xo, rows, fun_out, its_out, status_out);
+    if (c->is_view || !c->halves_env || c->profiling || c->p.B < 16 || !c->p.has_problem || c->colsplit)
+        return solve_members(c, o, true, xo, rows, fun_out, its_out, status_out, nullptr);
     LP_HIP(hipSetDevice(c->device));
     if (c->halves.empty()) {
-        const int h = c->B / 2;
+        const int h = c->p.B / 2;
         lpipm_ctx* a = make_view(c, 0, h);
-        lpipm_ctx* b = a ? make_view(c, h, c->B - h) : nullptr;
+        lpipm_ctx* b = a ? make_view(c, h, c->p.B - h) : nullptr;
         if (!a || !b) {
             if (a) { c->halves.push_back(a); destroy_views(c); }
-            return solve_lockstep_one(c, o, xo, rows, fun_out, its_out, status_out);
+            return solve_members(c, o, true, xo, rows, fun_out, its_out, status_out, nullptr);
         }
         c->halves.push_back(a); c->halves.push_back(b);
     }
-    LP_HIP(hipStreamSynchronize(c->st));         // the upload (or whatever else the caller enqueued) precedes both halves
+    LP_HIP(hipStreamSynchronize(c->rs.st));         // the upload (or whatever else the caller enqueued) precedes both halves
     int rc[2] = {LPIPM_OK, LPIPM_OK};
     // a view numbers its members from 0: member i of half k is member first + i of the batch
     std::vector<uint64_t> ident;
-    if (!rows) { ident.resize((size_t)c->B); for (int i = 0; i < c->B; ++i) ident[(size_t)i] = (uint64_t)i; rows = ident.data(); }
+    if (!rows) { ident.resize((size_t)c->p.B); for (int i = 0; i < c->p.B; ++i) ident[(size_t)i] = (uint64_t)i; rows = ident.data(); }
     auto run = [&](int k) {
         lpipm_ctx* v = c->halves[(size_t)k];
-        const int f = v->bt.first;
-        rc[k] = solve_lockstep_one(v, o, xo, rows + f, fun_out ? fun_out + f : nullptr, its_out ? its_out + f : nullptr, status_out + f);
+        const int f = v->p.bt.first;
+        rc[k] = solve_members(v, o, true, xo, rows + f, fun_out ? fun_out + f : nullptr, its_out ? its_out + f : nullptr,
+                              status_out + f, nullptr);
     };
     std::thread other(run, 1);
     run(0);
     other.join();
     return rc[0] != LPIPM_OK ? rc[0] : rc[1];
-}
-
-static int solve_lockstep_one(lpipm_ctx* c, const lpipm_opts* o, const XOut& xo, const uint64_t* rows, double* fun_out,
-                              uint64_t* its_out, int32_t* status_out) {
-    if (!c || !o || !xo.valid() || !status_out) return LPIPM_ERR_BAD_ARGUMENT;
-    if (!(o->alpha0 > 0.0) || !(o->alpha0 < 1.0)) return LPIPM_INVALID_PARAMETER;   // mod.rs:118-128
-    if (!(o->tol > 0.0)) return LPIPM_INVALID_PARAMETER;
-    if (o->solver_type != LPIPM_SOLVER_CHOLESKY) return LPIPM_ERR_UNSUPPORTED;      // the QR arms are single-LP
-    if (!c->has_problem) return LPIPM_ERR_NO_PROBLEM;
-    if (c->colsplit) return LPIPM_ERR_UNSUPPORTED;
-    LP_HIP(hipSetDevice(c->device));
-    const int B = c->B;
-    VecArgs& v = c->va;
-    hipStream_t st = c->st;
-    // profiling (lpipm_set_profiling): the same event marks as a single solve; a phase's time is that of the whole batch's launch
-    for (int t = 0; t < T_NTAGS; ++t) c->tag_ms[t] = 0.0;
-    c->times = lpipm_phase_times{};
-    c->nmarks = 0;
-    c->gemv_passes = 0;
-    uint64_t batch_iterations = 0;
-    if (c->profiling) LP_HIP(hipEventRecord(c->ev_begin, st));
-    vec_blind_start(v, st);                                                  // feasible_point.rs:24-31
-    prof_mark(c, T_VEC);
-    LP_TRY(enqueue_residuals(c, 1, o->ip ? 1 : 0, o->tol));                  // feasible_point.rs:32, mod.rs:206
-    prof_mark(c, T_VEC);
-    if (c->profiling) {                  // (nothing of the starting point is read by the host otherwise)
-        LP_HIP(hipStreamSynchronize(st));
-        prof_collect(c);
-    }
-    std::vector<int> ret((size_t)B, -1);                                     // -1: still iterating
-    std::vector<uint64_t> its((size_t)B, 0);
-    int running = B, ip = o->ip ? 1 : 0;
-    bool head_out = false;
-    c->spin_status = c->va.status_pinned != nullptr && !c->profiling;
-    c->refine_now = c->refine == 2;      // (selective mode) at the starting point mu / mu_0 = 1: no member refines its first iteration
-    for (uint64_t iteration = 1; iteration <= o->max_iter && running > 0; ++iteration) {   // mod.rs:213
-        if (!head_out) LP_TRY(enqueue_head(c));
-        LP_TRY(enqueue_tail(c, ip, o));
-        const size_t marks = c->nmarks;
-        head_out = iteration < o->max_iter;
-        if (head_out) LP_TRY(enqueue_head(c));       // next iteration's A.D.A^T, before this one's status is read
-        {   // the members that were still running when this iteration was enqueued write a record; the others are skipped
-            std::vector<int> act;
-            for (int i = 0; i < B; ++i) if (ret[i] < 0) act.push_back(i);
-            LP_TRY(wait_status(c, act.data(), (int)act.size()));
-        }
-        prof_collect(c, marks);
-        ++batch_iterations;
-        ip = 0;                                                              // mod.rs:223
-        for (int i = 0; i < B; ++i) {
-            if (ret[i] >= 0) continue;
-            const StatusRec& s = c->status_host[i];
-            if (s.potrf_info != 0 || (s.flags & FLAG_NAN_PQ)) ret[i] = LPIPM_NUMERICAL_PROBLEM;   // mod.rs:215
-            else if (s.status == ST_OPTIMAL) ret[i] = LPIPM_OK;              // mod.rs:231
-            else if (s.status == ST_INFEASIBLE) ret[i] = LPIPM_INFEASIBLE;   // :232
-            else if (s.status == ST_UNBOUNDED) ret[i] = LPIPM_UNBOUNDED;     // :233
-            if (ret[i] >= 0) { its[i] = iteration; --running; }
-        }
-        // the refinement launches of the next iteration are enqueued if ANY running member asks for them; which members
-        // they touch is each member's own device word (k_scalar_indicators), the same decision as when it is solved alone
-        c->refine_now = c->refine == 2;
-        for (int i = 0; i < B && c->refine == 1 && !c->refine_now; ++i)
-            if (ret[i] < 0 && c->status_host[i].rho_mu <= refine_below()) c->refine_now = true;
-    }
-    for (int i = 0; i < B; ++i)
-        if (ret[i] < 0) { ret[i] = LPIPM_ITERATION_LIMIT; its[i] = o->max_iter; }   // mod.rs:237-239
-    LP_TRY(vec_final_x(v, c->xout, st, nullptr));                            // mod.rs:231/238, :165 (every LP)
-    LP_TRY(copy_status(c));
-    for (int i = 0; i < B; ++i) {     // rows[i]: member i's row in the caller's numbering (identity when null)
-        if (ret[i] != LPIPM_OK && ret[i] != LPIPM_ITERATION_LIMIT) continue;
-        const uint64_t row = rows ? rows[i] : (uint64_t)i;
-        const char* src = (const char*)c->xout + (size_t)(c->bt.first + i) * c->bstride;
-        if (xo.dev) LP_HIP(hipMemcpyAsync(xo.dev + row * xo.stride_bytes, src, c->n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        else if (xo.host[row]) LP_HIP(hipMemcpyAsync(xo.host[row], src, c->n * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    if (c->profiling) LP_HIP(hipEventRecord(c->ev_end, st));
-    LP_HIP(hipStreamSynchronize(st));
-    if (c->profiling) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, c->ev_begin, c->ev_end);
-        c->times.total_ms = ms;
-        c->times.adat_ms = c->tag_ms[T_ADAT]; c->times.potrf_ms = c->tag_ms[T_POTRF];
-        c->times.trsv_ms = c->tag_ms[T_TRSV]; c->times.gemv_ms = c->tag_ms[T_GEMV]; c->times.vec_ms = c->tag_ms[T_VEC];
-        c->times.adat_launches = batch_iterations;     // launches of the batched kernel (each covers all B members)
-        c->times.iterations = batch_iterations;        // lockstep iterations of the batch (= the slowest member's count)
-        c->times.gemv_passes = c->gemv_passes;
-    }
-    for (int i = 0; i < B; ++i) {
-        status_out[i] = ret[i];
-        const bool has_x = ret[i] == LPIPM_OK || ret[i] == LPIPM_ITERATION_LIMIT;
-        if (fun_out) fun_out[i] = has_x ? c->status_host[i].obj : NAN;
-        if (its_out) its_out[i] = its[i];
-    }
-    return LPIPM_OK;
 }
 
 extern "C" int lpipm_upload_lockstep(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* const* A,
@@ -1360,7 +1343,7 @@ extern "C" int lpipm_upload_lockstep_shared(lpipm_ctx* c, uint64_t count, uint64
 }
 extern "C" int lpipm_get_resident_bytes(const lpipm_ctx* c, uint64_t* bytes_out) {
     if (!c || !bytes_out) return LPIPM_ERR_BAD_ARGUMENT;
-    *bytes_out = c->has_problem ? (uint64_t)(c->arena_bytes + c->a_shared_bytes + c->list_bytes) : 0;
+    *bytes_out = c->p.has_problem ? (uint64_t)(c->p.arena_bytes + c->p.a_shared_bytes + c->p.list_bytes) : 0;
     return LPIPM_OK;
 }
 extern "C" int lpipm_solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, double* const* x_slack_out, double* fun_out,
@@ -1370,22 +1353,22 @@ extern "C" int lpipm_solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, double* c
 }
 extern "C" int lpipm_solve_lockstep_device(lpipm_ctx* c, const lpipm_opts* o, void* x_dev_out, uint64_t row_stride,
                                            double* fun_out, uint64_t* iterations_out, int32_t* status_out) {
-    if (!c || !x_dev_out || row_stride < c->n) return LPIPM_ERR_BAD_ARGUMENT;
+    if (!c || !x_dev_out || row_stride < c->p.n) return LPIPM_ERR_BAD_ARGUMENT;
     XOut xo; xo.dev = (char*)x_dev_out; xo.stride_bytes = row_stride * sizeof(double);
     return solve_lockstep(c, o, xo, nullptr, fun_out, iterations_out, status_out);
 }
 
-// Bytes one member of a lockstep batch of this shape occupies: the real layout (a measuring pass of layout_problem on a
-// scratch context carrying only the geometry), not a formula that drifts from it.
+// Bytes one member of a lockstep batch of this shape occupies: the real layout (plan_adat and a measuring pass of
+// layout_problem over the bare geometry), not a formula that drifts from it.
 static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, uint64_t m, uint64_t n) {
-    lpipm_ctx t;
-    t.num_cu = c->num_cu; t.refine = c->refine; t.B = 32;
+    Problem t;
+    t.B = 32;
     t.mp = (int)round_up(m, NB); t.np = (int)round_up(n, BK); t.npa = t.np;
     t.nsplit = t.mp / GEMVT_ROWS;
-    t.units_env = c->units_env;
-    plan_adat(&t, t.B);
+    const AdatPlan ap = plan_adat(t.mp, t.npa, t.B, c->num_cu, c->world, c->units_env);
+    FactorPlan fp;
     Arena measure;
-    if (layout_problem(&t, measure, false) != LPIPM_OK) return (size_t)-1;
+    if (layout_problem(t, fp, ap, c->refine, measure, false, nullptr) != LPIPM_OK) return (size_t)-1;
     return (size_t)round_up(measure.off, 4096);
 }
 
@@ -1418,7 +1401,7 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             // resident: one being solved, the next one being uploaded)
             size_t free_b = 0, total_b = 0;
             LP_HIP(hipMemGetInfo(&free_b, &total_b));
-            free_b += c->arena_bytes;                // the current arena is released before the next one is made
+            free_b += c->p.arena_bytes;                // the current arena is released before the next one is made
             const double per_lp = (double)lockstep_bytes_per_lp(c, m[i], n[i]);     // the real arena layout of one member
             size_t chunk;
             if (c->lockstep_max > 0) chunk = (size_t)c->lockstep_max;
@@ -1520,7 +1503,7 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             double fun = NAN;
             uint64_t it = 0;
             if (rc == LPIPM_OK)
-                rc = xo.dev ? solve_impl(w, &opts, nullptr, xo.dev + i * xo.stride_bytes, &fun, &it, nullptr)
+                rc = xo.dev ? solve_single(w, &opts, nullptr, xo.dev + i * xo.stride_bytes, &fun, &it, nullptr)
                             : lpipm_solve(w, &opts, xo.host[i], &fun, &it, nullptr);
             status_out[i] = rc;
             if (fun_out) fun_out[i] = fun;
@@ -1583,7 +1566,7 @@ extern "C" int lpipm_upload_nsplit(lpipm_ctx* c, uint64_t m, uint64_t n_total, u
     const int rc = lpipm_upload_slack(c, m, n_local, A_local, lda, b, c_local, c0, 0);
     if (rc != LPIPM_OK) return rc;
     if (c->world > 1) {
-        const size_t need = (size_t)c->mp * ((size_t)c->mp + 128) / 2;
+        const size_t need = (size_t)c->p.mp * ((size_t)c->p.mp + 128) / 2;
         if (need != c->mpack_count) {
             if (c->mpack) { LP_HIP(hipFree(c->mpack)); c->mpack = nullptr; c->mpack_count = 0; }
             LP_HIP(hipMalloc((void**)&c->mpack, need * sizeof(double)));
@@ -1600,8 +1583,8 @@ extern "C" int lpipm_upload_nsplit(lpipm_ctx* c, uint64_t m, uint64_t n_total, u
         }
     }
     c->colsplit = true;
-    c->va.n_total = (long long)n_total;
-    c->va.gs = c->gs;
+    c->p.va.n_total = (long long)n_total;
+    c->p.va.gs = c->p.gs;
     return LPIPM_OK;
 }
 
@@ -1623,12 +1606,12 @@ static int timed_repeats(lpipm_ctx* c, int repeats, double* ms_out, F&& body) {
     if (repeats < 1) repeats = 1;
     float total = 0.f;
     for (int r = 0; r < repeats; ++r) {
-        LP_HIP(hipEventRecord(c->ev_begin, c->st));
+        LP_HIP(hipEventRecord(c->rs.ev_begin, c->rs.st));
         LP_TRY(body());
-        LP_HIP(hipEventRecord(c->ev_end, c->st));
-        LP_HIP(hipStreamSynchronize(c->st));
+        LP_HIP(hipEventRecord(c->rs.ev_end, c->rs.st));
+        LP_HIP(hipStreamSynchronize(c->rs.st));
         float ms = 0.f;
-        LP_HIP(hipEventElapsedTime(&ms, c->ev_begin, c->ev_end));
+        LP_HIP(hipEventElapsedTime(&ms, c->rs.ev_begin, c->rs.ev_end));
         total += ms;
     }
     if (ms_out) *ms_out = total / repeats;
@@ -1637,35 +1620,35 @@ static int timed_repeats(lpipm_ctx* c, int repeats, double* ms_out, F&& body) {
 
 extern "C" int lpipm_k_adat(lpipm_ctx* c, const double* dinv, double* M_out, int repeats, double* ms_out) {
     if (!c || !dinv || !M_out) return LPIPM_ERR_BAD_ARGUMENT;
-    if (!c->has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
     LP_HIP(hipSetDevice(c->device));
-    LP_HIP(hipMemcpyAsync(c->va.dinv, dinv, c->n * sizeof(double), hipMemcpyHostToDevice, c->st));
+    LP_HIP(hipMemcpyAsync(c->p.va.dinv, dinv, c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
     LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int { LP_HIP(run_adat(c, Batch{})); return LPIPM_OK; }));
-    LP_HIP(hipMemcpy2DAsync(M_out, c->m * sizeof(double), c->M, (size_t)c->mp * sizeof(double),
-                            c->m * sizeof(double), c->m, hipMemcpyDeviceToHost, c->st));
-    LP_HIP(hipStreamSynchronize(c->st));
+    LP_HIP(hipMemcpy2DAsync(M_out, c->p.m * sizeof(double), c->p.M, (size_t)c->p.mp * sizeof(double),
+                            c->p.m * sizeof(double), c->p.m, hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
 }
 
 static int kbuf_ensure(lpipm_ctx* c, int mp) {
     if (c->kmp == mp) return LPIPM_OK;
-    LP_HIP(hipStreamSynchronize(c->st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
     free_list(c->kallocs);
     factor_plan_destroy(c->kplan);
     c->kmp = 0;
-    LP_TRY(dalloc(c->kallocs, nullptr, &c->kM, (size_t)mp * mp, c->st));
-    LP_TRY(dalloc(c->kallocs, nullptr, &c->kM0, (size_t)mp * mp, c->st));
-    LP_TRY(dalloc(c->kallocs, nullptr, &c->kR, (size_t)2 * mp, c->st));
-    LP_TRY(dalloc(c->kallocs, nullptr, &c->kY, (size_t)2 * mp, c->st));
-    LP_TRY(dalloc(c->kallocs, nullptr, &c->kinfo, 1, c->st));
-    LP_TRY(dalloc(c->kallocs, nullptr, &c->ktau, (size_t)mp, c->st));
+    LP_TRY(dalloc(c->kallocs, nullptr, &c->kM, (size_t)mp * mp, c->rs.st));
+    LP_TRY(dalloc(c->kallocs, nullptr, &c->kM0, (size_t)mp * mp, c->rs.st));
+    LP_TRY(dalloc(c->kallocs, nullptr, &c->kR, (size_t)2 * mp, c->rs.st));
+    LP_TRY(dalloc(c->kallocs, nullptr, &c->kY, (size_t)2 * mp, c->rs.st));
+    LP_TRY(dalloc(c->kallocs, nullptr, &c->kinfo, 1, c->rs.st));
+    LP_TRY(dalloc(c->kallocs, nullptr, &c->ktau, (size_t)mp, c->rs.st));
     Arena measure;
-    LP_HIP(factor_plan_create(c->kplan, c->kM, mp, mp, measure, false, c->st, super_for(mp), merge_edge_for(1)));
+    LP_HIP(factor_plan_create(c->kplan, c->kM, mp, mp, measure, false, c->rs.st, super_for(mp), merge_edge_for(1)));
     char* kar = nullptr;
-    LP_TRY(dalloc(c->kallocs, nullptr, &kar, measure.off + 256, c->st));   // zeroed
+    LP_TRY(dalloc(c->kallocs, nullptr, &kar, measure.off + 256, c->rs.st));   // zeroed
     Arena real;
     real.base = kar;
-    LP_HIP(factor_plan_create(c->kplan, c->kM, mp, mp, real, true, c->st, super_for(mp), merge_edge_for(1)));
+    LP_HIP(factor_plan_create(c->kplan, c->kM, mp, mp, real, true, c->rs.st, super_for(mp), merge_edge_for(1)));
     c->kmp = mp;
     return LPIPM_OK;
 }
@@ -1678,23 +1661,23 @@ extern "C" int lpipm_k_potrf(lpipm_ctx* c, uint64_t m, double* M_inout, int32_t*
     LP_TRY(kbuf_ensure(c, mp));
     // padded pristine copy: [[M, 0], [0, I]]
     std::vector<double> pad((size_t)(mp - m), 1.0);
-    LP_HIP(hipMemsetAsync(c->kM0, 0, (size_t)mp * mp * sizeof(double), c->st));
+    LP_HIP(hipMemsetAsync(c->kM0, 0, (size_t)mp * mp * sizeof(double), c->rs.st));
     LP_HIP(hipMemcpy2DAsync(c->kM0, (size_t)mp * sizeof(double), M_inout, m * sizeof(double), m * sizeof(double),
-                            m, hipMemcpyHostToDevice, c->st));
+                            m, hipMemcpyHostToDevice, c->rs.st));
     if (mp > (int)m)
         LP_HIP(hipMemcpy2DAsync(c->kM0 + m * mp + m, (size_t)(mp + 1) * sizeof(double), pad.data(), sizeof(double),
-                                sizeof(double), mp - m, hipMemcpyHostToDevice, c->st));
-    LP_HIP(hipStreamSynchronize(c->st));
+                                sizeof(double), mp - m, hipMemcpyHostToDevice, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
     if (repeats < 1) repeats = 1;
     float total = 0.f;
     for (int r = 0; r < repeats; ++r) {
-        LP_HIP(hipMemcpyAsync(c->kM, c->kM0, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToDevice, c->st));
-        LP_HIP(hipEventRecord(c->ev_begin, c->st));
-        LP_HIP(launch_potrf(c->kM, mp, mp, c->kplan, c->kinfo, c->st, Batch{}, lookahead(c)));
-        LP_HIP(hipEventRecord(c->ev_end, c->st));
-        LP_HIP(hipStreamSynchronize(c->st));
+        LP_HIP(hipMemcpyAsync(c->kM, c->kM0, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToDevice, c->rs.st));
+        LP_HIP(hipEventRecord(c->rs.ev_begin, c->rs.st));
+        LP_HIP(launch_potrf(c->kM, mp, mp, c->kplan, c->kinfo, c->rs.st, Batch{}, lookahead(c)));
+        LP_HIP(hipEventRecord(c->rs.ev_end, c->rs.st));
+        LP_HIP(hipStreamSynchronize(c->rs.st));
         float ms = 0.f;
-        LP_HIP(hipEventElapsedTime(&ms, c->ev_begin, c->ev_end));
+        LP_HIP(hipEventElapsedTime(&ms, c->rs.ev_begin, c->rs.ev_end));
         total += ms;
     }
     if (ms_out) *ms_out = total / repeats;
@@ -1703,9 +1686,9 @@ extern "C" int lpipm_k_potrf(lpipm_ctx* c, uint64_t m, double* M_inout, int32_t*
         if (hipMalloc((void**)&d, sizeof(h)) == hipSuccess) {
             g_diag_stamps = d;
             (void)hipMemset(d, 0, sizeof(h));
-            (void)hipMemcpyAsync(c->kM, c->kM0, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToDevice, c->st);
-            (void)launch_potrf(c->kM, mp, mp, c->kplan, c->kinfo, c->st);
-            (void)hipStreamSynchronize(c->st);
+            (void)hipMemcpyAsync(c->kM, c->kM0, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToDevice, c->rs.st);
+            (void)launch_potrf(c->kM, mp, mp, c->kplan, c->kinfo, c->rs.st);
+            (void)hipStreamSynchronize(c->rs.st);
             g_diag_stamps = nullptr;
             (void)hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
             (void)hipFree(d);
@@ -1719,10 +1702,10 @@ extern "C" int lpipm_k_potrf(lpipm_ctx* c, uint64_t m, double* M_inout, int32_t*
         }
     }
     int32_t info = 0;
-    LP_HIP(hipMemcpyAsync(&info, c->kinfo, sizeof(int32_t), hipMemcpyDeviceToHost, c->st));
+    LP_HIP(hipMemcpyAsync(&info, c->kinfo, sizeof(int32_t), hipMemcpyDeviceToHost, c->rs.st));
     LP_HIP(hipMemcpy2DAsync(M_inout, m * sizeof(double), c->kM, (size_t)mp * sizeof(double), m * sizeof(double), m,
-                            hipMemcpyDeviceToHost, c->st));
-    LP_HIP(hipStreamSynchronize(c->st));
+                            hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
     if (info_out) *info_out = info;
     c->kchol_valid = true;
     return LPIPM_OK;
@@ -1737,21 +1720,21 @@ extern "C" int lpipm_k_chol_solve(lpipm_ctx* c, uint64_t m, int nrhs, const doub
     if (repeats < 1) repeats = 1;
     float total = 0.f;
     for (int r = 0; r < repeats; ++r) {
-        LP_HIP(hipMemsetAsync(c->kR, 0, (size_t)2 * mp * sizeof(double), c->st));
+        LP_HIP(hipMemsetAsync(c->kR, 0, (size_t)2 * mp * sizeof(double), c->rs.st));
         LP_HIP(hipMemcpy2DAsync(c->kR, (size_t)mp * sizeof(double), R, m * sizeof(double), m * sizeof(double), nrhs,
-                                hipMemcpyHostToDevice, c->st));
-        LP_HIP(hipEventRecord(c->ev_begin, c->st));
-        LP_HIP(launch_chol_solve(c->kM, mp, c->kplan, nrhs, c->kR, c->kY, c->st));
-        LP_HIP(hipEventRecord(c->ev_end, c->st));
-        LP_HIP(hipStreamSynchronize(c->st));
+                                hipMemcpyHostToDevice, c->rs.st));
+        LP_HIP(hipEventRecord(c->rs.ev_begin, c->rs.st));
+        LP_HIP(launch_chol_solve(c->kM, mp, c->kplan, nrhs, c->kR, c->kY, c->rs.st));
+        LP_HIP(hipEventRecord(c->rs.ev_end, c->rs.st));
+        LP_HIP(hipStreamSynchronize(c->rs.st));
         float ms = 0.f;
-        LP_HIP(hipEventElapsedTime(&ms, c->ev_begin, c->ev_end));
+        LP_HIP(hipEventElapsedTime(&ms, c->rs.ev_begin, c->rs.ev_end));
         total += ms;
     }
     if (ms_out) *ms_out = total / repeats;
     LP_HIP(hipMemcpy2DAsync(V, m * sizeof(double), c->kR, (size_t)mp * sizeof(double), m * sizeof(double), nrhs,
-                            hipMemcpyDeviceToHost, c->st));
-    LP_HIP(hipStreamSynchronize(c->st));
+                            hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
 }
 
@@ -1765,15 +1748,15 @@ extern "C" int lpipm_k_symv_residual(lpipm_ctx* c, uint64_t m, const double* M, 
     // every failure leaves through the one exit below, which frees both buffers
     hipError_t e = hipMalloc((void**)&ws, symv_slab_doubles(mp) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&vbuf, (size_t)6 * mp * sizeof(double));
-    if (e == hipSuccess) e = hipMemsetAsync(vbuf, 0, (size_t)6 * mp * sizeof(double), c->st);
-    if (e == hipSuccess) e = hipMemsetAsync(c->kM0, 0, (size_t)mp * mp * sizeof(double), c->st);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(c->kM0, (size_t)mp * sizeof(double), M, m * sizeof(double), m * sizeof(double), m, hipMemcpyHostToDevice, c->st);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(vbuf, (size_t)mp * sizeof(double), V, m * sizeof(double), m * sizeof(double), nrhs, hipMemcpyHostToDevice, c->st);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(vbuf + 2 * mp, (size_t)mp * sizeof(double), R0, m * sizeof(double), m * sizeof(double), nrhs, hipMemcpyHostToDevice, c->st);
-    if (e == hipSuccess) e = launch_symv_residual(c->kM0, mp, mp, nrhs, vbuf, mp, vbuf + 2 * mp, mp, vbuf + 4 * mp, mp, ws, c->st);
+    if (e == hipSuccess) e = hipMemsetAsync(vbuf, 0, (size_t)6 * mp * sizeof(double), c->rs.st);
+    if (e == hipSuccess) e = hipMemsetAsync(c->kM0, 0, (size_t)mp * mp * sizeof(double), c->rs.st);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(c->kM0, (size_t)mp * sizeof(double), M, m * sizeof(double), m * sizeof(double), m, hipMemcpyHostToDevice, c->rs.st);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(vbuf, (size_t)mp * sizeof(double), V, m * sizeof(double), m * sizeof(double), nrhs, hipMemcpyHostToDevice, c->rs.st);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(vbuf + 2 * mp, (size_t)mp * sizeof(double), R0, m * sizeof(double), m * sizeof(double), nrhs, hipMemcpyHostToDevice, c->rs.st);
+    if (e == hipSuccess) e = launch_symv_residual(c->kM0, mp, mp, nrhs, vbuf, mp, vbuf + 2 * mp, mp, vbuf + 4 * mp, mp, ws, c->rs.st);
     if (e == hipSuccess)
-        e = hipMemcpy2DAsync(Rho, m * sizeof(double), vbuf + 4 * mp, (size_t)mp * sizeof(double), m * sizeof(double), nrhs, hipMemcpyDeviceToHost, c->st);
-    const hipError_t es = hipStreamSynchronize(c->st);      // also on failure: nothing may still use the buffers freed next
+        e = hipMemcpy2DAsync(Rho, m * sizeof(double), vbuf + 4 * mp, (size_t)mp * sizeof(double), m * sizeof(double), nrhs, hipMemcpyDeviceToHost, c->rs.st);
+    const hipError_t es = hipStreamSynchronize(c->rs.st);      // also on failure: nothing may still use the buffers freed next
     if (e == hipSuccess) e = es;
     if (ws) (void)hipFree(ws);
     if (vbuf) (void)hipFree(vbuf);
@@ -1788,26 +1771,26 @@ extern "C" int lpipm_k_qr_solve(lpipm_ctx* c, uint64_t m, const double* M, int n
     const int mp = (int)round_up(m, NB);
     LP_TRY(kbuf_ensure(c, mp));
     std::vector<double> pad((size_t)(mp - m), 1.0);
-    LP_HIP(hipMemsetAsync(c->kM, 0, (size_t)mp * mp * sizeof(double), c->st));
+    LP_HIP(hipMemsetAsync(c->kM, 0, (size_t)mp * mp * sizeof(double), c->rs.st));
     LP_HIP(hipMemcpy2DAsync(c->kM, (size_t)mp * sizeof(double), M, m * sizeof(double), m * sizeof(double), m,
-                            hipMemcpyHostToDevice, c->st));
+                            hipMemcpyHostToDevice, c->rs.st));
     if (mp > (int)m)
         LP_HIP(hipMemcpy2DAsync(c->kM + m * mp + m, (size_t)(mp + 1) * sizeof(double), pad.data(), sizeof(double),
-                                sizeof(double), mp - m, hipMemcpyHostToDevice, c->st));
-    LP_HIP(hipMemsetAsync(c->kR, 0, (size_t)2 * mp * sizeof(double), c->st));
+                                sizeof(double), mp - m, hipMemcpyHostToDevice, c->rs.st));
+    LP_HIP(hipMemsetAsync(c->kR, 0, (size_t)2 * mp * sizeof(double), c->rs.st));
     LP_HIP(hipMemcpy2DAsync(c->kR, (size_t)mp * sizeof(double), R, m * sizeof(double), m * sizeof(double), nrhs,
-                            hipMemcpyHostToDevice, c->st));
-    LP_HIP(hipEventRecord(c->ev_begin, c->st));
-    LP_HIP(launch_qr_factor(c->kM, mp, mp, c->ktau, c->kinfo, c->st));
-    LP_HIP(launch_qr_solve(c->kM, mp, mp, c->ktau, nrhs, c->kR, c->kinfo, c->st));
-    LP_HIP(hipEventRecord(c->ev_end, c->st));
+                            hipMemcpyHostToDevice, c->rs.st));
+    LP_HIP(hipEventRecord(c->rs.ev_begin, c->rs.st));
+    LP_HIP(launch_qr_factor(c->kM, mp, mp, c->ktau, c->kinfo, c->rs.st));
+    LP_HIP(launch_qr_solve(c->kM, mp, mp, c->ktau, nrhs, c->kR, c->kinfo, c->rs.st));
+    LP_HIP(hipEventRecord(c->rs.ev_end, c->rs.st));
     int32_t info = 0;
-    LP_HIP(hipMemcpyAsync(&info, c->kinfo, sizeof(int32_t), hipMemcpyDeviceToHost, c->st));
+    LP_HIP(hipMemcpyAsync(&info, c->kinfo, sizeof(int32_t), hipMemcpyDeviceToHost, c->rs.st));
     LP_HIP(hipMemcpy2DAsync(V, m * sizeof(double), c->kR, (size_t)mp * sizeof(double), m * sizeof(double), nrhs,
-                            hipMemcpyDeviceToHost, c->st));
-    LP_HIP(hipStreamSynchronize(c->st));
+                            hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
     float ms = 0.f;
-    LP_HIP(hipEventElapsedTime(&ms, c->ev_begin, c->ev_end));
+    LP_HIP(hipEventElapsedTime(&ms, c->rs.ev_begin, c->rs.ev_end));
     if (ms_out) *ms_out = ms;
     if (info_out) *info_out = info;
     c->kchol_valid = false;   // kM no longer holds a Cholesky factor: lpipm_k_chol_solve needs a new lpipm_k_potrf
@@ -1816,35 +1799,35 @@ extern "C" int lpipm_k_qr_solve(lpipm_ctx* c, uint64_t m, const double* M, int n
 
 extern "C" int lpipm_k_gemv_n(lpipm_ctx* c, int nrhs, const double* W, double* Y, int repeats, double* ms_out) {
     if (!c || !W || !Y || (nrhs != 1 && nrhs != 2)) return LPIPM_ERR_BAD_ARGUMENT;
-    if (!c->has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
     LP_HIP(hipSetDevice(c->device));
-    LP_HIP(hipMemcpy2DAsync(c->va.W, (size_t)c->np * sizeof(double), W, c->n * sizeof(double), c->n * sizeof(double),
-                            nrhs, hipMemcpyHostToDevice, c->st));
+    LP_HIP(hipMemcpy2DAsync(c->p.va.W, (size_t)c->p.np * sizeof(double), W, c->p.n * sizeof(double), c->p.n * sizeof(double),
+                            nrhs, hipMemcpyHostToDevice, c->rs.st));
     LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int {
-        LP_HIP(ctx_gemv_n(c, nrhs, c->va.W, nullptr, nullptr, c->va.R, Batch{}));
+        LP_HIP(ctx_gemv_n(c, nrhs, c->p.va.W, nullptr, nullptr, c->p.va.R, Batch{}));
         return LPIPM_OK;
     }));
-    LP_HIP(hipMemcpy2DAsync(Y, c->m * sizeof(double), c->va.R, (size_t)c->mp * sizeof(double), c->m * sizeof(double),
-                            nrhs, hipMemcpyDeviceToHost, c->st));
-    LP_HIP(hipStreamSynchronize(c->st));
+    LP_HIP(hipMemcpy2DAsync(Y, c->p.m * sizeof(double), c->p.va.R, (size_t)c->p.mp * sizeof(double), c->p.m * sizeof(double),
+                            nrhs, hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
 }
 
 extern "C" int lpipm_k_gemv_t(lpipm_ctx* c, int nrhs, const double* V, double* U, int repeats, double* ms_out) {
     if (!c || !V || !U || (nrhs != 1 && nrhs != 2)) return LPIPM_ERR_BAD_ARGUMENT;
-    if (!c->has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
     LP_HIP(hipSetDevice(c->device));
-    LP_HIP(hipMemsetAsync(c->va.R, 0, (size_t)2 * c->mp * sizeof(double), c->st));
-    LP_HIP(hipMemcpy2DAsync(c->va.R, (size_t)c->mp * sizeof(double), V, c->m * sizeof(double), c->m * sizeof(double),
-                            nrhs, hipMemcpyHostToDevice, c->st));
+    LP_HIP(hipMemsetAsync(c->p.va.R, 0, (size_t)2 * c->p.mp * sizeof(double), c->rs.st));
+    LP_HIP(hipMemcpy2DAsync(c->p.va.R, (size_t)c->p.mp * sizeof(double), V, c->p.m * sizeof(double), c->p.m * sizeof(double),
+                            nrhs, hipMemcpyHostToDevice, c->rs.st));
     LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int {
-        LP_HIP(ctx_gemv_t(c, nrhs, c->va.R, Batch{}));
-        LP_HIP(launch_gemv_t_reduce(c->ATpart, c->nsplit, nrhs, c->np, c->va.W, c->np, c->st));
+        LP_HIP(ctx_gemv_t(c, nrhs, c->p.va.R, Batch{}));
+        LP_HIP(launch_gemv_t_reduce(c->p.ATpart, c->p.nsplit, nrhs, c->p.np, c->p.va.W, c->p.np, c->rs.st));
         return LPIPM_OK;
     }));
-    LP_HIP(hipMemcpy2DAsync(U, c->n * sizeof(double), c->va.W, (size_t)c->np * sizeof(double), c->n * sizeof(double),
-                            nrhs, hipMemcpyDeviceToHost, c->st));
-    LP_HIP(hipStreamSynchronize(c->st));
+    LP_HIP(hipMemcpy2DAsync(U, c->p.n * sizeof(double), c->p.va.W, (size_t)c->p.np * sizeof(double), c->p.n * sizeof(double),
+                            nrhs, hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
 }
 
@@ -1856,18 +1839,18 @@ extern "C" int lpipm_k_iteration(lpipm_ctx* c, const lpipm_opts* o, int ip, doub
                                  double* kappa, double* d_x, double* d_y, double* d_z, double* d_tk, double* alpha_out,
                                  int32_t* info_out) {
     if (!c || !o || !x || !y || !z || !tau || !kappa || !d_x || !d_y || !d_z || !d_tk || !alpha_out) return LPIPM_ERR_BAD_ARGUMENT;
-    if (!c->has_problem) return LPIPM_ERR_NO_PROBLEM;
-    if (c->B != 1) return LPIPM_ERR_UNSUPPORTED;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (c->p.B != 1) return LPIPM_ERR_UNSUPPORTED;
     // (a column-split context: x, z, d_x, d_z are this rank's slices, everything else is replicated, and every rank must
     //  call together -- enqueue_residuals / enqueue_iteration contain the cross-rank reductions)
     LP_HIP(hipSetDevice(c->device));
-    VecArgs& v = c->va;
-    hipStream_t st = c->st;
+    VecArgs& v = c->p.va;
+    hipStream_t st = c->rs.st;
     c->refine_now = c->refine == 2;
     vec_blind_start(v, st);                                   // clears done / flags; the iterate is overwritten next
-    LP_HIP(hipMemcpyAsync(v.x, x, c->n * sizeof(double), hipMemcpyHostToDevice, st));
-    LP_HIP(hipMemcpyAsync(v.y, y, c->m * sizeof(double), hipMemcpyHostToDevice, st));
-    LP_HIP(hipMemcpyAsync(v.z, z, c->n * sizeof(double), hipMemcpyHostToDevice, st));
+    LP_HIP(hipMemcpyAsync(v.x, x, c->p.n * sizeof(double), hipMemcpyHostToDevice, st));
+    LP_HIP(hipMemcpyAsync(v.y, y, c->p.m * sizeof(double), hipMemcpyHostToDevice, st));
+    LP_HIP(hipMemcpyAsync(v.z, z, c->p.n * sizeof(double), hipMemcpyHostToDevice, st));
     const double tk[2] = {*tau, *kappa};
     LP_HIP(hipMemcpyAsync(v.S + S_TAU, &tk[0], sizeof(double), hipMemcpyHostToDevice, st));
     LP_HIP(hipMemcpyAsync(v.S + S_KAPPA, &tk[1], sizeof(double), hipMemcpyHostToDevice, st));
@@ -1875,44 +1858,44 @@ extern "C" int lpipm_k_iteration(lpipm_ctx* c, const lpipm_opts* o, int ip, doub
     LP_TRY(enqueue_iteration(c, ip ? 1 : 0, o));
     double sc[S_COUNT];
     LP_HIP(hipMemcpyAsync(sc, v.S, sizeof(sc), hipMemcpyDeviceToHost, st));
-    LP_HIP(hipMemcpyAsync(x, v.x, c->n * sizeof(double), hipMemcpyDeviceToHost, st));
-    LP_HIP(hipMemcpyAsync(y, v.y, c->m * sizeof(double), hipMemcpyDeviceToHost, st));
-    LP_HIP(hipMemcpyAsync(z, v.z, c->n * sizeof(double), hipMemcpyDeviceToHost, st));
-    LP_HIP(hipMemcpyAsync(d_x, v.dx, c->n * sizeof(double), hipMemcpyDeviceToHost, st));
-    LP_HIP(hipMemcpyAsync(d_y, v.dy, c->m * sizeof(double), hipMemcpyDeviceToHost, st));
-    LP_HIP(hipMemcpyAsync(d_z, v.dz, c->n * sizeof(double), hipMemcpyDeviceToHost, st));
+    LP_HIP(hipMemcpyAsync(x, v.x, c->p.n * sizeof(double), hipMemcpyDeviceToHost, st));
+    LP_HIP(hipMemcpyAsync(y, v.y, c->p.m * sizeof(double), hipMemcpyDeviceToHost, st));
+    LP_HIP(hipMemcpyAsync(z, v.z, c->p.n * sizeof(double), hipMemcpyDeviceToHost, st));
+    LP_HIP(hipMemcpyAsync(d_x, v.dx, c->p.n * sizeof(double), hipMemcpyDeviceToHost, st));
+    LP_HIP(hipMemcpyAsync(d_y, v.dy, c->p.m * sizeof(double), hipMemcpyDeviceToHost, st));
+    LP_HIP(hipMemcpyAsync(d_z, v.dz, c->p.n * sizeof(double), hipMemcpyDeviceToHost, st));
     LP_HIP(hipStreamSynchronize(st));
-    if (c->colsplit && c->grouped_reduce && *c->timeout_host != 0) {   // as solve_impl: a group wait that gave up is an error
+    if (c->colsplit && c->p.grouped_reduce && *c->rs.timeout_host != 0) {   // as solve_members: a group wait that gave up is an error
         g_err_detail = "a column group of A.D.A^T did not complete within the wait kernel's bound";
         return LPIPM_ERR_HIP;
     }
     *tau = sc[S_TAU]; *kappa = sc[S_KAPPA]; d_tk[0] = sc[S_DTAU]; d_tk[1] = sc[S_DKAPPA]; *alpha_out = sc[S_ALPHA];
-    if (info_out) *info_out = c->status_host->potrf_info;
+    if (info_out) *info_out = c->rs.status_host->potrf_info;
     return LPIPM_OK;
 }
 
 extern "C" int lpipm_k_gemv_dual(lpipm_ctx* c, const double* w, const double* v, double* Aw_out, double* ATv_out, int repeats,
                                  double* ms_out) {
     if (!c || !w || !v || !Aw_out || !ATv_out) return LPIPM_ERR_BAD_ARGUMENT;
-    if (!c->has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
     LP_HIP(hipSetDevice(c->device));
-    VecArgs& va = c->va;
-    LP_HIP(hipMemsetAsync(va.W, 0, (size_t)c->np * sizeof(double), c->st));
-    LP_HIP(hipMemsetAsync(va.R, 0, (size_t)c->mp * sizeof(double), c->st));
-    LP_HIP(hipMemcpyAsync(va.W, w, c->n * sizeof(double), hipMemcpyHostToDevice, c->st));
-    LP_HIP(hipMemcpyAsync(va.R, v, c->m * sizeof(double), hipMemcpyHostToDevice, c->st));
-    const int nch = gemv_dual_chunks(c->npa);
+    VecArgs& va = c->p.va;
+    LP_HIP(hipMemsetAsync(va.W, 0, (size_t)c->p.np * sizeof(double), c->rs.st));
+    LP_HIP(hipMemsetAsync(va.R, 0, (size_t)c->p.mp * sizeof(double), c->rs.st));
+    LP_HIP(hipMemcpyAsync(va.W, w, c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
+    LP_HIP(hipMemcpyAsync(va.R, v, c->p.m * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
+    const int nch = gemv_dual_chunks(c->p.npa);
     LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int {
         LP_HIP(ctx_gemv_dual(c, va.W, va.R, va.Ax, Batch{}));
         return LPIPM_OK;
     }));
     // the consumers' folds, on the host: chunk slabs of A.w, row-block slabs of A^T.v, in index order
-    std::vector<double> ax((size_t)nch * c->mp), at((size_t)c->nsplit * c->np);
-    LP_HIP(hipMemcpyAsync(ax.data(), va.Ax, ax.size() * sizeof(double), hipMemcpyDeviceToHost, c->st));
-    LP_HIP(hipMemcpyAsync(at.data(), c->ATpart, at.size() * sizeof(double), hipMemcpyDeviceToHost, c->st));
-    LP_HIP(hipStreamSynchronize(c->st));
-    for (uint64_t i = 0; i < c->m; ++i) { double s = 0.0; for (int ch = 0; ch < nch; ++ch) s += ax[(size_t)ch * c->mp + i]; Aw_out[i] = s; }
-    for (uint64_t j = 0; j < c->n; ++j) { double s = 0.0; for (int sp = 0; sp < c->nsplit; ++sp) s += at[(size_t)sp * c->np + j]; ATv_out[j] = s; }
+    std::vector<double> ax((size_t)nch * c->p.mp), at((size_t)c->p.nsplit * c->p.np);
+    LP_HIP(hipMemcpyAsync(ax.data(), va.Ax, ax.size() * sizeof(double), hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(hipMemcpyAsync(at.data(), c->p.ATpart, at.size() * sizeof(double), hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
+    for (uint64_t i = 0; i < c->p.m; ++i) { double s = 0.0; for (int ch = 0; ch < nch; ++ch) s += ax[(size_t)ch * c->p.mp + i]; Aw_out[i] = s; }
+    for (uint64_t j = 0; j < c->p.n; ++j) { double s = 0.0; for (int sp = 0; sp < c->p.nsplit; ++sp) s += at[(size_t)sp * c->p.np + j]; ATv_out[j] = s; }
     return LPIPM_OK;
 }
 
@@ -1923,7 +1906,7 @@ extern "C" int lpipm_k_mfma_f64_probe(lpipm_ctx* c, int iters, double* tflops_ou
     double* sink = nullptr;
     LP_HIP(hipMalloc((void**)&sink, (size_t)blocks * 256 * sizeof(double)));
     double ms = 0.0;
-    int rc = timed_repeats(c, 3, &ms, [&]() -> int { LP_HIP(launch_mfma_probe(iters, sink, blocks, c->st)); return LPIPM_OK; });
+    int rc = timed_repeats(c, 3, &ms, [&]() -> int { LP_HIP(launch_mfma_probe(iters, sink, blocks, c->rs.st)); return LPIPM_OK; });
     (void)hipFree(sink);
     if (rc != LPIPM_OK) return rc;
     // per wave and loop trip: 16 independent accumulators x one 16x16x4 MFMA = 16 * 2048 flop

@@ -229,9 +229,11 @@ def test_gemv_dual_one_read_of_A(ctx, m, n):
 @pytest.mark.parametrize("m,n", [(100, 130), (512, 1024), (640, 3000), (1024, 4096), (1000, 5000), (2048, 9000)])
 def test_adat_units_kernel_single_lp(built, monkeypatch, m, n):
     """The (tile, chunk) units kernel with its in-launch last-arriver combine (gemm_nt_units_kernel: what lockstep batches and
-    the column-split reduction run) forced onto a single LP (LPIPM_ADAT_UNITS=2): against numpy, bit-identical to the
-    default single-LP kernel up to n = 4096 (one canonical chunking for both), and bit-reproducible over 5 launches (the
-    combine is done by whichever workgroup arrives last: the sums must not depend on who that is)."""
+    the column-split reduction run, and by default most single LPs too) forced onto every single LP (LPIPM_ADAT_UNITS=2):
+    against numpy, bit-identical to what a default context launches for the shape (plan_adat: the units kernel itself, or
+    the round-2 kernel for few tiles with several chunks) up to n = 4096 (one canonical chunking for both), and
+    bit-reproducible over 5 launches (the combine is done by whichever workgroup arrives last: the sums must not depend on
+    who that is)."""
     import lp_amd
     from lp_amd import synth
     A, b, c, _ = synth.planted_lp(3, m, n)
