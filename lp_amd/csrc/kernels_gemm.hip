@@ -105,6 +105,14 @@ __device__ __forceinline__ void tile_coords(const GemmK& p, int t, int& ti, int&
 }
 
 
+template <int MTM, int MTN>
+__device__ __forceinline__ void acc_clear(d4 (&acc)[MTM][MTN]) {
+#pragma unroll
+    for (int mi = 0; mi < MTM; ++mi)
+#pragma unroll
+        for (int nj = 0; nj < MTN; ++nj) acc[mi][nj] = (d4){0.0, 0.0, 0.0, 0.0};
+}
+
 // acc(128x128 tile, 64 doubles per lane) += sum over k-tiles [kb, ke) of P-panel . (s o Q-panel)^T
 // Pp / Qp point at this thread's first staging element (row srow, column scol of the panels).
 // MTM x MTN = 16x16 MFMA tiles per wave (2x2 waves per workgroup): workgroup tile = 32*MTM x 32*MTN.
@@ -370,12 +378,7 @@ __device__ __forceinline__ void tile_pass_w8(double (*ldsA)[TILE][LDS_STRIDE], d
         if (more) lstore(cur ^ 1);
         asm volatile("" :: "v"(pf0), "v"(pf1));            // the touch loads have landed (and their registers are free) from here
         flush(first, !more);
-        if (more) {
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                for (int nj = 0; nj < 2; ++nj) acc[mi][nj] = (d4){0.0, 0.0, 0.0, 0.0};
-        }
+        if (more) acc_clear(acc);
         first = false;
         __syncthreads();
         cur ^= 1;
@@ -407,12 +410,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int g = p.bk.xcd_major ? (int)blockIdx.y : xcd_remap(blockIdx.x, gridDim.x);
     const int KT = p.KT;
     const int ntiles_dp = (p.ntiles / p.nwg) * p.nwg;
-    auto zero = [](d4 (&acc)[4][2]) {
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int nj = 0; nj < 2; ++nj) acc[mi][nj] = (d4){0.0, 0.0, 0.0, 0.0};
-    };
     // C tile (ti, tj) as a buffer; this lane's element of MFMA block (mi, nj), register r sits at
     //   offC + ((mi*16 + 4r)*ldc + nj*16) * 8   (wave-uniform second term)
     const unsigned rowC = (unsigned)(p.ldc * (long long)sizeof(double));
@@ -472,7 +469,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         int ti, tj;
         tile_coords(p, tile, ti, tj);
         d4 acc[4][2];
-        zero(acc);
+        acc_clear(acc);
         tile_pass_w8<SCALE>(ldsA, ldsB, p_rsrc(ti), p64, q_rsrc(tj), q64, Sr, offP, offQ, offS, 0, KT, acc, srow, scol, wr, wc, fr, fq,
                             p.kc, [&](bool first, bool last) {
                                 if (first) store_tile(acc, ti, tj); else add_tile(acc, ti, tj, last && p.C2 != nullptr);
@@ -498,7 +495,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         int ti, tj;
         tile_coords(p, ntiles_dp + rt, ti, tj);
         d4 acc[4][2];
-        zero(acc);
+        acc_clear(acc);
         tile_pass_w8<SCALE>(ldsA, ldsB, p_rsrc(ti), p64, q_rsrc(tj), q64, Sr, offP, offQ, offS, kb, ke, acc, srow, scol, wr, wc, fr, fq,
                             0, [&](bool, bool) {
             if (cpt == 1) { store_tile(acc, ti, tj); return; }   // the chunk is the whole tile
@@ -580,10 +577,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     constexpr unsigned SLAB_BYTES = (unsigned)(TILE * TILE * sizeof(double));
     const __amdgpu_buffer_rsrc_t Wr = make_rsrc(p.slabs + (long long)tile * p.cpt * (TILE * TILE), (unsigned)p.cpt * SLAB_BYTES);
     d4 acc[4][2];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int nj = 0; nj < 2; ++nj) acc[mi][nj] = (d4){0.0, 0.0, 0.0, 0.0};
+    acc_clear(acc);
     // chunk boundaries: nbig chunks of kc k-tiles, the rest of the contraction in pieces of ks
     auto chunk_begin = [&](int q) { const int b0 = q <= p.nbig ? q * p.kc : p.nbig * p.kc + (q - p.nbig) * p.ks; return b0 < KT ? b0 : KT; };
     const int kb = chunk_begin(q0), ke = chunk_begin(q1);
@@ -718,10 +712,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_tile_kernel(const GemmK p0) {
     int ti, tj;
     tile_coords(p, blockIdx.x, ti, tj);
     d4 acc[MTM][MTN];
-#pragma unroll
-    for (int mi = 0; mi < MTM; ++mi)
-#pragma unroll
-        for (int nj = 0; nj < MTN; ++nj) acc[mi][nj] = (d4){0.0, 0.0, 0.0, 0.0};
+    acc_clear(acc);
     tile_mainloop<false, MTM, MTN>(ldsA, ldsB, p.P + (long long)(ti * TM + srow) * p.ldp + scol, p.ldp,
                                    p.Q + (long long)(tj * TN + srow) * p.ldq + scol, p.ldq, nullptr, 0, p.KT, acc,
                                    srow, scol, wr, wc, fr, fq);
@@ -754,10 +745,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_tile_k128_kernel(const GemmK p
         for (int r = 0; r < MTN; ++r) pb[kt][r] = *(const d2*)(Qp + (long long)(32 * r) * p.ldq + kt * BK);
     }
     d4 acc[MTM][MTN];
-#pragma unroll
-    for (int mi = 0; mi < MTM; ++mi)
-#pragma unroll
-        for (int nj = 0; nj < MTN; ++nj) acc[mi][nj] = (d4){0.0, 0.0, 0.0, 0.0};
+    acc_clear(acc);
 #pragma unroll
     for (int kt = 0; kt < KT8; ++kt) {
         const int buf = kt & 1;
@@ -815,7 +803,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_rows32_k128_kernel(const GemmK
         for (int r = 0; r < 2; ++r) pb[kt][r] = *(const d2*)(Qp + (long long)(64 * r) * p.ldq + kt * BK);
     }
     d4 acc[1][2];
-    acc[0][0] = acc[0][1] = (d4){0.0, 0.0, 0.0, 0.0};
+    acc_clear(acc);
 #pragma unroll
     for (int kt = 0; kt < KT8; ++kt) {
         const int buf = kt & 1;
@@ -842,60 +830,27 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_rows32_k128_kernel(const GemmK
 
 // Grouped GEMM: every workgroup takes its own descriptor (operands, k-range, alpha): the doubling
 // levels of the super-block triangular inverse are a few such launches over many small products.
-__global__ __launch_bounds__(256, 2) void gemm_nt_grouped_kernel(const GemmTileDesc* __restrict__ descs, BatchK bk) {
+// Output tiles of 32 * MT rows and columns:
+//   MT = 4 (128x128): flop-bound stages, 2 resident workgroups per CU.
+//   MT = 2 (64x64, 4 resident workgroups per CU): a merge stage of one LP is a few dozen 128x128 tiles on 512 slots and
+//          each tile's k-loop is pure latency, so quartering the tiles quarters the stage's duration; the triangular
+//          k-ranges are also tighter at 64 granularity.
+//   MT = 1 (32x32): the merge stages of one LP are one round of tiles each, so a stage lasts as long as its longest k-loop,
+//          and a quarter-size tile has the shortest MFMA chain and the tightest triangular k-range.
+template <int MT>
+__global__ __launch_bounds__(256, MT == 4 ? 2 : 4) void gemm_nt_grouped_kernel(const GemmTileDesc* __restrict__ descs, BatchK bk) {
     if (batch_done(bk)) return;
-    __shared__ __attribute__((aligned(16))) double ldsA[2][TILE][LDS_STRIDE];
-    __shared__ __attribute__((aligned(16))) double ldsB[2][TILE][LDS_STRIDE];
+    __shared__ __attribute__((aligned(16))) double ldsA[2][32 * MT][LDS_STRIDE];
+    __shared__ __attribute__((aligned(16))) double ldsB[2][32 * MT][LDS_STRIDE];
     TILE_THREAD_IDS
     GemmTileDesc d = descs[blockIdx.x];
     d.P = batch_ptr(d.P, bk); d.Q = batch_ptr(d.Q, bk); d.C = batch_ptr(d.C, bk);
-    d4 acc[4][4];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int nj = 0; nj < 4; ++nj) acc[mi][nj] = (d4){0.0, 0.0, 0.0, 0.0};
-    tile_mainloop<false, 4, 4>(ldsA, ldsB, d.P + (long long)srow * d.ldp + scol, d.ldp, d.Q + (long long)srow * d.ldq + scol,
-                         d.ldq, nullptr, d.kt_begin, d.kt_end, acc, srow, scol, wr, wc, fr, fq);
-    double* cb = d.C + (long long)(wr * 64 + fq) * d.ldc + (wc * 64 + fr);
-    tile_store<4, 4>(cb, d.ldc, acc, d.alpha, 0.0, false, 0, -1, fr, fq);
-}
-
-// The same with 64x64 output tiles (4 resident workgroups per CU): a merge stage of one LP is a few dozen
-// 128x128 tiles on 512 slots and each tile's k-loop is pure latency, so quartering the tiles quarters the
-// stage's duration; the triangular k-ranges are also tighter at 64 granularity.
-__global__ __launch_bounds__(256, 4) void gemm_nt_grouped64_kernel(const GemmTileDesc* __restrict__ descs, BatchK bk) {
-    if (batch_done(bk)) return;
-    __shared__ __attribute__((aligned(16))) double ldsA[2][64][LDS_STRIDE];
-    __shared__ __attribute__((aligned(16))) double ldsB[2][64][LDS_STRIDE];
-    TILE_THREAD_IDS
-    GemmTileDesc d = descs[blockIdx.x];
-    d.P = batch_ptr(d.P, bk); d.Q = batch_ptr(d.Q, bk); d.C = batch_ptr(d.C, bk);
-    d4 acc[2][2];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int nj = 0; nj < 2; ++nj) acc[mi][nj] = (d4){0.0, 0.0, 0.0, 0.0};
-    tile_mainloop<false, 2, 2>(ldsA, ldsB, d.P + (long long)srow * d.ldp + scol, d.ldp, d.Q + (long long)srow * d.ldq + scol,
-                               d.ldq, nullptr, d.kt_begin, d.kt_end, acc, srow, scol, wr, wc, fr, fq);
-    double* cb = d.C + (long long)(wr * 32 + fq) * d.ldc + (wc * 32 + fr);
-    tile_store<2, 2>(cb, d.ldc, acc, d.alpha, 0.0, false, 0, -1, fr, fq);
-}
-
-// And with 32x32 output tiles: the merge stages of one LP are one round of tiles each, so a stage lasts as long as its longest
-// k-loop, and a quarter-size tile has the shortest MFMA chain and the tightest triangular k-range.
-__global__ __launch_bounds__(256, 4) void gemm_nt_grouped32_kernel(const GemmTileDesc* __restrict__ descs, BatchK bk) {
-    if (batch_done(bk)) return;
-    __shared__ __attribute__((aligned(16))) double ldsA[2][32][LDS_STRIDE];
-    __shared__ __attribute__((aligned(16))) double ldsB[2][32][LDS_STRIDE];
-    TILE_THREAD_IDS
-    GemmTileDesc d = descs[blockIdx.x];
-    d.P = batch_ptr(d.P, bk); d.Q = batch_ptr(d.Q, bk); d.C = batch_ptr(d.C, bk);
-    d4 acc[1][1];
-    acc[0][0] = (d4){0.0, 0.0, 0.0, 0.0};
-    tile_mainloop<false, 1, 1>(ldsA, ldsB, d.P + (long long)srow * d.ldp + scol, d.ldp, d.Q + (long long)srow * d.ldq + scol,
-                               d.ldq, nullptr, d.kt_begin, d.kt_end, acc, srow, scol, wr, wc, fr, fq);
-    double* cb = d.C + (long long)(wr * 16 + fq) * d.ldc + (wc * 16 + fr);
-    tile_store<1, 1>(cb, d.ldc, acc, d.alpha, 0.0, false, 0, -1, fr, fq);
+    d4 acc[MT][MT];
+    acc_clear(acc);
+    tile_mainloop<false, MT, MT>(ldsA, ldsB, d.P + (long long)srow * d.ldp + scol, d.ldp, d.Q + (long long)srow * d.ldq + scol,
+                                 d.ldq, nullptr, d.kt_begin, d.kt_end, acc, srow, scol, wr, wc, fr, fq);
+    double* cb = d.C + (long long)(wr * (16 * MT) + fq) * d.ldc + (wc * (16 * MT) + fr);
+    tile_store<MT, MT>(cb, d.ldc, acc, d.alpha, 0.0, false, 0, -1, fr, fq);
 }
 
 // Adds the chunk slabs of every stream-K (remainder) tile in chunk order.  grid = remainder tiles x FIX_SPLIT:
@@ -986,13 +941,16 @@ hipError_t launch_gemm_nt(const GemmArgs& a, hipStream_t st) {
     if (a.ntiles <= 0 || k.KT <= 0) return hipSuccess;
     if (!a.streamk) {   // one whole tile per workgroup
         if (a.nwg != a.ntiles || a.s || a.diag_pad_from >= 0) return hipErrorInvalidValue;
-        if (a.tile_edge == 64 && k.KT == 8)      hipLaunchKernelGGL((gemm_nt_tile_k128_kernel<2, 2>), dim3(a.ntiles, 1, B), dim3(256), 0, st, k);
-        else if (a.tile_edge == 32 && k.KT == 8) hipLaunchKernelGGL(gemm_nt_rows32_k128_kernel, dim3(a.ntiles, 1, B), dim3(512), 0, st, k);
-        else if (a.tile_edge == 3232 && k.KT == 8) hipLaunchKernelGGL((gemm_nt_tile_k128_kernel<1, 1>), dim3(a.ntiles, 1, B), dim3(256), 0, st, k);
-        else if (a.tile_edge == 64) hipLaunchKernelGGL((gemm_nt_tile_kernel<2, 2>), dim3(a.ntiles, 1, B), dim3(256), 0, st, k);
-        else if (a.tile_edge == 3232) hipLaunchKernelGGL((gemm_nt_tile_kernel<1, 1>), dim3(a.ntiles, 1, B), dim3(256), 0, st, k);
-        else if (a.tile_edge == 32) hipLaunchKernelGGL((gemm_nt_tile_kernel<1, 4>), dim3(a.ntiles, 1, B), dim3(256), 0, st, k);
-        else                        hipLaunchKernelGGL((gemm_nt_tile_kernel<4, 4>), dim3(a.ntiles, 1, B), dim3(256), 0, st, k);
+        const dim3 grid(a.ntiles, 1, B);
+        const TileShape shape = a.tile_shape;
+        const bool k128 = k.KT == 8;    // the K = 128 specialisations (128x128 has none)
+        if (shape == TileShape::T64x64 && k128)       hipLaunchKernelGGL((gemm_nt_tile_k128_kernel<2, 2>), grid, dim3(256), 0, st, k);
+        else if (shape == TileShape::T32x128 && k128) hipLaunchKernelGGL(gemm_nt_rows32_k128_kernel, grid, dim3(512), 0, st, k);
+        else if (shape == TileShape::T32x32 && k128)  hipLaunchKernelGGL((gemm_nt_tile_k128_kernel<1, 1>), grid, dim3(256), 0, st, k);
+        else if (shape == TileShape::T64x64)          hipLaunchKernelGGL((gemm_nt_tile_kernel<2, 2>), grid, dim3(256), 0, st, k);
+        else if (shape == TileShape::T32x32)          hipLaunchKernelGGL((gemm_nt_tile_kernel<1, 1>), grid, dim3(256), 0, st, k);
+        else if (shape == TileShape::T32x128)         hipLaunchKernelGGL((gemm_nt_tile_kernel<1, 4>), grid, dim3(256), 0, st, k);
+        else                                          hipLaunchKernelGGL((gemm_nt_tile_kernel<4, 4>), grid, dim3(256), 0, st, k);
         return hipGetLastError();
     }
     // canonical chunked summation (see the head of this file).  Data-parallel tiles take beta at their first chunk and
@@ -1084,9 +1042,10 @@ hipError_t launch_wait_count(const unsigned int* cnt, unsigned int target, const
 
 hipError_t launch_gemm_grouped(const GemmTileDesc* descs_dev, int ntiles, hipStream_t st, const Batch& bt, int edge) {
     if (ntiles <= 0) return hipSuccess;
-    if (edge == 32)      hipLaunchKernelGGL(gemm_nt_grouped32_kernel, dim3(ntiles, 1, bt.count), dim3(256), 0, st, descs_dev, batch_k(bt));
-    else if (edge == 64) hipLaunchKernelGGL(gemm_nt_grouped64_kernel, dim3(ntiles, 1, bt.count), dim3(256), 0, st, descs_dev, batch_k(bt));
-    else            hipLaunchKernelGGL(gemm_nt_grouped_kernel, dim3(ntiles, 1, bt.count), dim3(256), 0, st, descs_dev, batch_k(bt));
+    const dim3 grid(ntiles, 1, bt.count);
+    if (edge == 32)      hipLaunchKernelGGL(gemm_nt_grouped_kernel<1>, grid, dim3(256), 0, st, descs_dev, batch_k(bt));
+    else if (edge == 64) hipLaunchKernelGGL(gemm_nt_grouped_kernel<2>, grid, dim3(256), 0, st, descs_dev, batch_k(bt));
+    else                 hipLaunchKernelGGL(gemm_nt_grouped_kernel<4>, grid, dim3(256), 0, st, descs_dev, batch_k(bt));
     return hipGetLastError();
 }
 

@@ -14,92 +14,147 @@ namespace lpipm {
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 
-// rows per wave: 2 for the passes over A (more bytes in flight per wave), 1 for short matrices (the blocks of the
-// triangular solves: 1024 rows would otherwise occupy only half of the CUs)
+// ------------------------------------------------------------------------------------------------
+// Every pass over A is written once, for a GROUP of SG members of a lockstep batch (gridDim.z counts groups).
+//   SHARED == false: every member owns its A, the group is the member (SG == 1) and A is offset by the arena stride like
+//                    every other operand -- the ordinary (batched or single) pass.
+//   SHARED == true : ONE matrix A that the whole batch shares (lpipm_upload_lockstep_shared).  A is never offset; a wave
+//                    loads an element of A once and applies it to every member of its group, so a pass reads A
+//                    ceil(count / SG) times instead of count times.  W / V / add / outputs are offset per member.
+// A member's output is summed the same way whatever the group size -- the same lane striding, the same expressions, the
+// same butterfly / row slabs / chunk slabs in the same order -- so a member comes out with the bits it has when it owns
+// its A.  A member whose done word is set is computed on its (frozen) inputs and its output discarded: nothing of it is
+// written; a group whose members are all done returns at once.  Members past the batch end (the last group) stand on the
+// group's last member, never stored.
+template <int SG>
+__device__ __forceinline__ bool group_load(const BatchK& bk, int count, long long (&off)[SG], bool (&live)[SG]) {
+    const int g0 = (int)blockIdx.z * SG, ng = count - g0 < SG ? count - g0 : SG;
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < SG; ++j) {
+        off[j] = ((long long)bk.first + g0 + (j < ng ? j : ng - 1)) * bk.stride;
+        live[j] = j < ng && !(bk.done && *(const int*)((const char*)bk.done + off[j]) != 0);
+        any |= live[j];
+    }
+    return any;
+}
+static inline int group_count(int count, int sg) { return (count + sg - 1) / sg; }
+// a member's operand: `off` bytes behind member 0's (A, W, V and the outputs are never null; the addends may be)
+template <typename T> __device__ __forceinline__ T* shift(T* p, long long off) { return (T*)((char*)p + off); }
+template <typename T> __device__ __forceinline__ const T* shift(const T* p, long long off) { return (const T*)((const char*)p + off); }
+__device__ __forceinline__ const double* shift_nullable(const double* p, long long off) { return p ? shift(p, off) : p; }
 
-// One wave computes GN_ROWS_PER_WAVE row dot products; np (padded row length) is a multiple of 16,
-// W is zero beyond the true n, so the 128-wide strides need a tail guard only on np.
-template <int NRHS, int GN_ROWS_PER_WAVE>
-__global__ __launch_bounds__(256) void gemv_n_kernel(const double* __restrict__ A, long long lda, int m,
-                                                     int np, const double* __restrict__ W, long long ldw,
-                                                     const double* add0,
-                                                     const double* add1,
-                                                     double* Y, long long ldy, double alpha, BatchK bk) {
-    if (batch_done(bk)) return;
-    A = batch_ptr(A, bk); W = batch_ptr(W, bk); add0 = batch_ptr(add0, bk); add1 = batch_ptr(add1, bk);
-    Y = batch_ptr(Y, bk);
+constexpr int SG_N = 4;      // members per group of gemv_n (acc: SG_N x rows x NRHS doubles, W: SG_N x NRHS pairs per step)
+constexpr int SG_T = 8;      // members per group of gemv_t (their V slabs in LDS, acc: SG_T x NRHS pairs)
+
+// One wave computes RPW row dot products per member (a row's sum does not depend on RPW); np (padded row length) is a
+// multiple of 16, W is zero beyond the true n, so the 128-wide strides need a tail guard only on np.
+template <int NRHS, int RPW, int SG, bool SHARED>
+__global__ __launch_bounds__(256) void gemv_n_kernel(const double* __restrict__ A, long long lda, int m, int np,
+                                                     const double* __restrict__ W, long long ldw, const double* add0,
+                                                     const double* add1, double* Y, long long ldy, double alpha,
+                                                     int count, BatchK bk) {
+    static_assert(SHARED || SG == 1, "members that own their A are groups of one");
+    long long off[SG];
+    bool live[SG];
+    if (!group_load<SG>(bk, count, off, live)) return;
+    if (!SHARED) A = shift(A, off[0]);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr int GN_ROWS_PER_WG = 4 * GN_ROWS_PER_WAVE;
-    const int row0 = blockIdx.x * GN_ROWS_PER_WG + wave * GN_ROWS_PER_WAVE;
+    const int row0 = blockIdx.x * 4 * RPW + wave * RPW;
     if (row0 >= m) return;
-    double acc[GN_ROWS_PER_WAVE][NRHS];
+    double acc[SG][RPW][NRHS];
 #pragma unroll
-    for (int r = 0; r < GN_ROWS_PER_WAVE; ++r)
+    for (int j = 0; j < SG; ++j)
 #pragma unroll
-        for (int q = 0; q < NRHS; ++q) acc[r][q] = 0.0;
+        for (int r = 0; r < RPW; ++r)
+#pragma unroll
+            for (int q = 0; q < NRHS; ++q) acc[j][r][q] = 0.0;
     const double* a0 = A + (long long)row0 * lda;
     for (int k = 2 * lane; k < np; k += 128) {
-        d2 wv[NRHS];
+        d2 wv[SG][NRHS];
 #pragma unroll
-        for (int q = 0; q < NRHS; ++q) wv[q] = *(const d2*)(W + (long long)q * ldw + k);
+        for (int j = 0; j < SG; ++j)
 #pragma unroll
-        for (int r = 0; r < GN_ROWS_PER_WAVE; ++r) {
+            for (int q = 0; q < NRHS; ++q) wv[j][q] = *(const d2*)(shift(W, off[j]) + (long long)q * ldw + k);
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) {
             // rows past m (only in the last workgroup) re-read row m-1; their result is not stored
             const int rr = row0 + r < m ? r : 0;
             const d2 av = *(const d2*)(a0 + (long long)rr * lda + k);
 #pragma unroll
-            for (int q = 0; q < NRHS; ++q) acc[r][q] += av[0] * wv[q][0] + av[1] * wv[q][1];
+            for (int j = 0; j < SG; ++j)
+#pragma unroll
+                for (int q = 0; q < NRHS; ++q) acc[j][r][q] += av[0] * wv[j][q][0] + av[1] * wv[j][q][1];
         }
     }
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
+    for (int off_ = 32; off_ >= 1; off_ >>= 1)
 #pragma unroll
-        for (int r = 0; r < GN_ROWS_PER_WAVE; ++r)
+        for (int j = 0; j < SG; ++j)
 #pragma unroll
-            for (int q = 0; q < NRHS; ++q) acc[r][q] += __shfl_xor(acc[r][q], off, 64);
+            for (int r = 0; r < RPW; ++r)
+#pragma unroll
+                for (int q = 0; q < NRHS; ++q) acc[j][r][q] += __shfl_xor(acc[j][r][q], off_, 64);
     if (lane == 0) {
 #pragma unroll
-        for (int r = 0; r < GN_ROWS_PER_WAVE; ++r) {
-            if (row0 + r >= m) continue;
+        for (int j = 0; j < SG; ++j) {
+            if (!live[j]) continue;
 #pragma unroll
-            for (int q = 0; q < NRHS; ++q) {
-                const double* add = q == 0 ? add0 : add1;
-                const double base = add ? add[row0 + r] : 0.0;
-                Y[(long long)q * ldy + row0 + r] = base + alpha * acc[r][q];
+            for (int r = 0; r < RPW; ++r) {
+                if (row0 + r >= m) continue;
+#pragma unroll
+                for (int q = 0; q < NRHS; ++q) {
+                    const double* add = shift_nullable(q == 0 ? add0 : add1, off[j]);
+                    const double base = add ? add[row0 + r] : 0.0;
+                    shift(Y, off[j])[(long long)q * ldy + row0 + r] = base + alpha * acc[j][r][q];
+                }
             }
         }
     }
 }
 
-// grid = (np / 512 rounded up, mp / GEMVT_ROWS).  Each thread owns two adjacent columns and walks
-// GEMVT_ROWS rows; the row split s = blockIdx.y writes its slab Upart[s][q][:].
-template <int NRHS>
+// grid = (np / 512 rounded up, mp / GEMVT_ROWS, groups).  Each thread owns two adjacent columns and walks
+// GEMVT_ROWS rows; the row split s = blockIdx.y writes its slab Upart[s][q][:] of every live member.
+template <int NRHS, int SG, bool SHARED>
 __global__ __launch_bounds__(256) void gemv_t_kernel(const double* __restrict__ A, long long lda, int np,
                                                      const double* __restrict__ V, long long ldv,
-                                                     double* __restrict__ Upart, long long slab, BatchK bk) {
-    if (batch_done(bk)) return;
-    A = batch_ptr(A, bk); V = batch_ptr(V, bk); Upart = batch_ptr(Upart, bk);
-    __shared__ double vs[NRHS][GEMVT_ROWS];
+                                                     double* __restrict__ Upart, long long slab, int count, BatchK bk) {
+    static_assert(SHARED || SG == 1, "members that own their A are groups of one");
+    long long off[SG];
+    bool live[SG];
+    if (!group_load<SG>(bk, count, off, live)) return;
+    if (!SHARED) A = shift(A, off[0]);
+    __shared__ double vs[SG][NRHS][GEMVT_ROWS];
     const int tid = threadIdx.x;
     const int col = (blockIdx.x * 256 + tid) * 2;
     const int row0 = blockIdx.y * GEMVT_ROWS;
-    for (int e = tid; e < NRHS * GEMVT_ROWS; e += 256)
-        vs[e / GEMVT_ROWS][e % GEMVT_ROWS] = V[(long long)(e / GEMVT_ROWS) * ldv + row0 + e % GEMVT_ROWS];
+    for (int e = tid; e < SG * NRHS * GEMVT_ROWS; e += 256) {
+        const int j = e / (NRHS * GEMVT_ROWS), q = (e / GEMVT_ROWS) % NRHS, r = e % GEMVT_ROWS;
+        vs[j][q][r] = shift(V, off[j])[(long long)q * ldv + row0 + r];
+    }
     __syncthreads();
     if (col >= np) return;
-    d2 acc[NRHS];
+    d2 acc[SG][NRHS];
 #pragma unroll
-    for (int q = 0; q < NRHS; ++q) acc[q] = (d2){0.0, 0.0};
+    for (int j = 0; j < SG; ++j)
+#pragma unroll
+        for (int q = 0; q < NRHS; ++q) acc[j][q] = (d2){0.0, 0.0};
     const double* ap = A + (long long)row0 * lda + col;
 #pragma unroll 8
     for (int r = 0; r < GEMVT_ROWS; ++r) {
         const d2 av = *(const d2*)(ap + (long long)r * lda);
 #pragma unroll
-        for (int q = 0; q < NRHS; ++q) acc[q] += av * vs[q][r];
+        for (int j = 0; j < SG; ++j)
+#pragma unroll
+            for (int q = 0; q < NRHS; ++q) acc[j][q] += av * vs[j][q][r];
     }
 #pragma unroll
-    for (int q = 0; q < NRHS; ++q)
-        *(d2*)(Upart + ((long long)blockIdx.y * NRHS + q) * slab + col) = acc[q];
+    for (int j = 0; j < SG; ++j) {
+        if (!live[j]) continue;
+#pragma unroll
+        for (int q = 0; q < NRHS; ++q)
+            *(d2*)(shift(Upart, off[j]) + ((long long)blockIdx.y * NRHS + q) * slab + col) = acc[j][q];
+    }
 }
 
 __global__ __launch_bounds__(256) void gemv_t_reduce_kernel(const double* __restrict__ Upart, int nsplit,
@@ -121,31 +176,37 @@ __global__ __launch_bounds__(256) void gemv_t_reduce_kernel(const double* __rest
 //   per 128-column step:
 //     row part     AxPart[ch][r]  = sum_{c in chunk} A(r,c) w[c]      (wave reduction per row)
 //     column part  Upart[rb][c]   = sum_{r in block} A(r,c) v[r]      (lane accumulators, the 4 waves added in order)
-//   the consumers (k_residuals) add the chunk slabs / the row-block slabs in index order.
-template <int CW>
+//   the consumers (k_residuals) add the chunk slabs / the row-block slabs in index order.  For a group of SG members:
+//   the same units, waves, row groups and slabs; the 4-wave column combine runs member after member through one LDS buffer.
+template <int CW, int SG, bool SHARED>
 __global__ __launch_bounds__(256) void gemv_dual_kernel(const double* __restrict__ A, long long lda, int np,
                                                         const double* __restrict__ W, const double* __restrict__ V,
                                                         double* __restrict__ AxPart, long long mp,
-                                                        double* __restrict__ Upart, long long slab, BatchK bk) {
-    if (batch_done(bk)) return;
-    A = batch_ptr(A, bk); W = batch_ptr(W, bk); V = batch_ptr(V, bk); AxPart = batch_ptr(AxPart, bk); Upart = batch_ptr(Upart, bk);
+                                                        double* __restrict__ Upart, long long slab, int count, BatchK bk) {
+    static_assert(SHARED || SG == 1, "members that own their A are groups of one");
+    long long off[SG];
+    bool live[SG];
+    if (!group_load<SG>(bk, count, off, live)) return;
+    if (!SHARED) A = shift(A, off[0]);
     constexpr int NS = CW / 128;
     const int ch = blockIdx.x, rb = blockIdx.y;
     const int r0 = rb * GEMVT_ROWS, c0 = ch * CW;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __shared__ double vrow[GEMVT_ROWS];
+    __shared__ double vrow[SG][GEMVT_ROWS];
     __shared__ double csum[4][CW];
-    for (int e = threadIdx.x; e < GEMVT_ROWS; e += 256) vrow[e] = V[r0 + e];
-    d2 wc[NS], cacc[NS];
+    for (int e = threadIdx.x; e < SG * GEMVT_ROWS; e += 256) vrow[e / GEMVT_ROWS][e % GEMVT_ROWS] = shift(V, off[e / GEMVT_ROWS])[r0 + e % GEMVT_ROWS];
+    d2 wc[SG][NS], cacc[SG][NS];
 #pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int col = c0 + s * 128 + 2 * lane;
-        wc[s] = col < np ? *(const d2*)(W + col) : (d2){0.0, 0.0};
-        cacc[s] = (d2){0.0, 0.0};
-    }
+    for (int j = 0; j < SG; ++j)
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int col = c0 + s * 128 + 2 * lane;
+            wc[j][s] = col < np ? *(const d2*)(shift(W, off[j]) + col) : (d2){0.0, 0.0};
+            cacc[j][s] = (d2){0.0, 0.0};
+        }
     __syncthreads();
     // RG rows per trip: their loads are all issued before any is used (RG * NS 16-byte loads in flight per lane) and
-    // the RG row sums go through the shuffle butterfly together
+    // the RG row sums go through the shuffle butterfly together (the rows a wave takes fix the column sums)
     constexpr int RG = NS >= 8 ? 2 : 4;
     for (int rr0 = wave * RG; rr0 < GEMVT_ROWS; rr0 += 4 * RG) {
         d2 a[RG][NS];
@@ -156,39 +217,58 @@ __global__ __launch_bounds__(256) void gemv_dual_kernel(const double* __restrict
             for (int s = 0; s < NS; ++s)
                 a[g][s] = c0 + s * 128 + 2 * lane < np ? *(const d2*)(row + s * 128) : (d2){0.0, 0.0};
         }
-        double racc[RG];
+        double racc[SG][RG];
 #pragma unroll
-        for (int g = 0; g < RG; ++g) {
-            const double vr = vrow[rr0 + g];
-            racc[g] = 0.0;
+        for (int j = 0; j < SG; ++j)
 #pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                racc[g] += a[g][s][0] * wc[s][0] + a[g][s][1] * wc[s][1];
-                cacc[s] += a[g][s] * vr;
+            for (int g = 0; g < RG; ++g) {
+                const double vr = vrow[j][rr0 + g];
+                racc[j][g] = 0.0;
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    racc[j][g] += a[g][s][0] * wc[j][s][0] + a[g][s][1] * wc[j][s][1];
+                    cacc[j][s] += a[g][s] * vr;
+                }
             }
-        }
 #pragma unroll
-        for (int off = 32; off >= 1; off >>= 1)
+        for (int off_ = 32; off_ >= 1; off_ >>= 1)
 #pragma unroll
-            for (int g = 0; g < RG; ++g) racc[g] += __shfl_xor(racc[g], off, 64);
+            for (int j = 0; j < SG; ++j)
+#pragma unroll
+                for (int g = 0; g < RG; ++g) racc[j][g] += __shfl_xor(racc[j][g], off_, 64);
         if (lane == 0) {
 #pragma unroll
-            for (int g = 0; g < RG; ++g) AxPart[(long long)ch * mp + r0 + rr0 + g] = racc[g];
+            for (int j = 0; j < SG; ++j) {
+                if (!live[j]) continue;
+#pragma unroll
+                for (int g = 0; g < RG; ++g) shift(AxPart, off[j])[(long long)ch * mp + r0 + rr0 + g] = racc[j][g];
+            }
         }
     }
 #pragma unroll
-    for (int s = 0; s < NS; ++s) *(d2*)&csum[wave][s * 128 + 2 * lane] = cacc[s];
-    __syncthreads();
-    for (int e = threadIdx.x; e < CW; e += 256)
-        if (c0 + e < np) Upart[(long long)rb * slab + c0 + e] = ((csum[0][e] + csum[1][e]) + csum[2][e]) + csum[3][e];
+    for (int j = 0; j < SG; ++j) {
+        if (j > 0) __syncthreads();                                 // the previous member's combine has read the buffer
+#pragma unroll
+        for (int s = 0; s < NS; ++s) *(d2*)&csum[wave][s * 128 + 2 * lane] = cacc[j][s];
+        __syncthreads();
+        if (live[j])
+            for (int e = threadIdx.x; e < CW; e += 256)
+                if (c0 + e < np)
+                    shift(Upart, off[j])[(long long)rb * slab + c0 + e] = ((csum[0][e] + csum[1][e]) + csum[2][e]) + csum[3][e];
+    }
 }
 int gemv_dual_chunks(int np) { return np >= 4096 ? (np + 1023) / 1024 : (np + 255) / 256; }
 hipError_t launch_gemv_dual(const double* A, int64_t lda, int mp, int np, const double* W, const double* V, double* AxPart,
-                            double* Upart, int64_t slab, hipStream_t st, const Batch& bt) {
+                            double* Upart, int64_t slab, hipStream_t st, const Batch& bt, bool shared_a) {
     if (slab <= 0) slab = np;
-    const dim3 grid(gemv_dual_chunks(np), mp / GEMVT_ROWS, bt.count);
-    if (np >= 4096) hipLaunchKernelGGL(gemv_dual_kernel<1024>, grid, dim3(256), 0, st, A, (long long)lda, np, W, V, AxPart, (long long)mp, Upart, (long long)slab, batch_k(bt));
-    else            hipLaunchKernelGGL(gemv_dual_kernel<256>, grid, dim3(256), 0, st, A, (long long)lda, np, W, V, AxPart, (long long)mp, Upart, (long long)slab, batch_k(bt));
+    // a shared A: 1024-column chunks hold 8 column pairs per lane and member: 2 members per group; 256-column chunks: 4
+    const int sg = !shared_a ? 1 : np >= 4096 ? 2 : 4;
+    const dim3 grid(gemv_dual_chunks(np), mp / GEMVT_ROWS, group_count(bt.count, sg));
+#define GD_LAUNCH(CW, SG, SH) hipLaunchKernelGGL((gemv_dual_kernel<CW, SG, SH>), grid, dim3(256), 0, st, A, (long long)lda, np, W, V, \
+                                                 AxPart, (long long)mp, Upart, (long long)slab, bt.count, batch_k(bt))
+    if (np >= 4096) { if (shared_a) GD_LAUNCH(1024, 2, true); else GD_LAUNCH(1024, 1, false); }
+    else            { if (shared_a) GD_LAUNCH(256, 4, true);  else GD_LAUNCH(256, 1, false); }
+#undef GD_LAUNCH
     return hipGetLastError();
 }
 
@@ -352,276 +432,33 @@ hipError_t launch_symv_residual(const double* M, int64_t ld, int mp, int nrhs, c
 
 hipError_t launch_gemv_n(const double* A, int64_t lda, int m, int np, int nrhs, const double* W,
                          int64_t ldw, const double* add0, const double* add1, double* Y, int64_t ldy,
-                         hipStream_t st, double alpha, const Batch& bt) {
-    // rows per wave (a row's sum is the same whatever the count): 1 while the launch would otherwise leave CUs empty, 2 from
-    // 2048 rows over the whole batch (every wave re-reads W from L2; C4 lockstep: solves 0.199 -> 0.187 ms, passes 0.527 ->
-    // 0.521 per iteration; 4 rows per wave: the same)
-    const int rpw = (long long)m * bt.count <= 2048 ? 1 : 2;
-    const dim3 grid((m + 4 * rpw - 1) / (4 * rpw), 1, bt.count);
-#define GN_LAUNCH(NR, RPW) hipLaunchKernelGGL((gemv_n_kernel<NR, RPW>), grid, dim3(256), 0, st, A, (long long)lda, m, np, W, \
-                                              (long long)ldw, add0, add1, Y, (long long)ldy, alpha, batch_k(bt))
-    if (nrhs == 1) { if (rpw == 1) GN_LAUNCH(1, 1); else GN_LAUNCH(1, 2); }
-    else           { if (rpw == 1) GN_LAUNCH(2, 1); else GN_LAUNCH(2, 2); }
+                         hipStream_t st, double alpha, const Batch& bt, bool shared_a) {
+    const int groups = group_count(bt.count, shared_a ? SG_N : 1);
+    // rows per wave (a row's sum is the same whatever the count): 1 while the launch would otherwise leave CUs empty (the
+    // blocks of the triangular solves: 1024 rows at 2 per wave would occupy only half of the CUs); from 2048 rows over all
+    // groups, 2 (every wave re-reads W from L2; C4 lockstep: solves 0.199 -> 0.187 ms, passes 0.527 -> 0.521 per iteration;
+    // 4 rows per wave: the same) or, with a shared A, 4 (W is re-read per wave from L2: more rows per wave, fewer re-reads)
+    const int rpw = (long long)m * groups <= 2048 ? 1 : shared_a ? 4 : 2;
+    const dim3 grid((m + 4 * rpw - 1) / (4 * rpw), 1, groups);
+#define GN_LAUNCH(NR, RPW, SG, SH) hipLaunchKernelGGL((gemv_n_kernel<NR, RPW, SG, SH>), grid, dim3(256), 0, st, A, (long long)lda, m, np, \
+                                                      W, (long long)ldw, add0, add1, Y, (long long)ldy, alpha, bt.count, batch_k(bt))
+#define GN_BY_NRHS(RPW, SG, SH) do { if (nrhs == 1) GN_LAUNCH(1, RPW, SG, SH); else GN_LAUNCH(2, RPW, SG, SH); } while (0)
+    if (!shared_a) { if (rpw == 1) GN_BY_NRHS(1, 1, false);   else GN_BY_NRHS(2, 1, false); }
+    else           { if (rpw == 1) GN_BY_NRHS(1, SG_N, true); else GN_BY_NRHS(4, SG_N, true); }
+#undef GN_BY_NRHS
 #undef GN_LAUNCH
     return hipGetLastError();
 }
 
 hipError_t launch_gemv_t(const double* A, int64_t lda, int mp, int np, int nrhs, const double* V,
-                         int64_t ldv, double* Upart, hipStream_t st, int64_t slab, const Batch& bt) {
+                         int64_t ldv, double* Upart, hipStream_t st, int64_t slab, const Batch& bt, bool shared_a) {
     if (slab <= 0) slab = np;
-    dim3 grid((np / 2 + 255) / 256, mp / GEMVT_ROWS, bt.count);
-    if (nrhs == 1)
-        hipLaunchKernelGGL(gemv_t_kernel<1>, grid, dim3(256), 0, st, A, (long long)lda, np, V, (long long)ldv, Upart, (long long)slab, batch_k(bt));
-    else
-        hipLaunchKernelGGL(gemv_t_kernel<2>, grid, dim3(256), 0, st, A, (long long)lda, np, V, (long long)ldv, Upart, (long long)slab, batch_k(bt));
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------
-// Passes over ONE matrix A that the whole batch shares (lpipm_upload_lockstep_shared).  gridDim.z counts GROUPS of SG
-// members: a wave loads an element of A once and applies it to every member of its group, so a pass reads A
-// ceil(count / SG) times instead of count times.  A is never offset by the member; W / V / add / outputs are, by the arena
-// stride.  Each member's output is summed exactly as the single-member kernel above sums it -- the same lane striding, the
-// same expressions, the same butterfly / row slabs / chunk slabs in the same order -- so a member comes out with the bits
-// it has when it owns its A.  A member whose done word is set is computed on its (frozen) inputs and its output discarded:
-// nothing of it is written.  Members past the batch end (the last group) stand on the group's last member, never stored.
-struct SharedGroup {
-    template <int SG>
-    __device__ __forceinline__ static bool load(const BatchK& bk, int count, long long (&off)[SG], bool (&live)[SG]) {
-        const int g0 = (int)blockIdx.z * SG, ng = count - g0 < SG ? count - g0 : SG;
-        bool any = false;
-#pragma unroll
-        for (int j = 0; j < SG; ++j) {
-            off[j] = ((long long)bk.first + g0 + (j < ng ? j : ng - 1)) * bk.stride;
-            live[j] = j < ng && !(bk.done && *(const int*)((const char*)bk.done + off[j]) != 0);
-            any |= live[j];
-        }
-        return any;
-    }
-};
-template <typename T> __device__ __forceinline__ T* shift(T* p, long long off) { return p ? (T*)((char*)p + off) : p; }
-template <typename T> __device__ __forceinline__ const T* shift(const T* p, long long off) { return p ? (const T*)((const char*)p + off) : p; }
-
-constexpr int SG_N = 4;      // members per group of gemv_n (acc: SG_N x rows x NRHS doubles, W: SG_N x NRHS pairs per step)
-constexpr int SG_T = 8;      // members per group of gemv_t (their V slabs in LDS, acc: SG_T x NRHS pairs)
-
-// gemv_n_kernel for a group: RPW rows per wave (a row's sum does not depend on RPW)
-template <int NRHS, int RPW>
-__global__ __launch_bounds__(256) void gemv_n_shared_kernel(const double* __restrict__ A, long long lda, int m, int np,
-                                                            const double* __restrict__ W, long long ldw, const double* add0,
-                                                            const double* add1, double* Y, long long ldy, double alpha,
-                                                            int count, BatchK bk) {
-    long long off[SG_N];
-    bool live[SG_N];
-    if (!SharedGroup::load<SG_N>(bk, count, off, live)) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int row0 = blockIdx.x * 4 * RPW + wave * RPW;
-    if (row0 >= m) return;
-    double acc[SG_N][RPW][NRHS];
-#pragma unroll
-    for (int j = 0; j < SG_N; ++j)
-#pragma unroll
-        for (int r = 0; r < RPW; ++r)
-#pragma unroll
-            for (int q = 0; q < NRHS; ++q) acc[j][r][q] = 0.0;
-    const double* a0 = A + (long long)row0 * lda;
-    for (int k = 2 * lane; k < np; k += 128) {
-        d2 wv[SG_N][NRHS];
-#pragma unroll
-        for (int j = 0; j < SG_N; ++j)
-#pragma unroll
-            for (int q = 0; q < NRHS; ++q) wv[j][q] = *(const d2*)(shift(W, off[j]) + (long long)q * ldw + k);
-#pragma unroll
-        for (int r = 0; r < RPW; ++r) {
-            const int rr = row0 + r < m ? r : 0;
-            const d2 av = *(const d2*)(a0 + (long long)rr * lda + k);
-#pragma unroll
-            for (int j = 0; j < SG_N; ++j)
-#pragma unroll
-                for (int q = 0; q < NRHS; ++q) acc[j][r][q] += av[0] * wv[j][q][0] + av[1] * wv[j][q][1];
-        }
-    }
-#pragma unroll
-    for (int off_ = 32; off_ >= 1; off_ >>= 1)
-#pragma unroll
-        for (int j = 0; j < SG_N; ++j)
-#pragma unroll
-            for (int r = 0; r < RPW; ++r)
-#pragma unroll
-                for (int q = 0; q < NRHS; ++q) acc[j][r][q] += __shfl_xor(acc[j][r][q], off_, 64);
-    if (lane == 0) {
-#pragma unroll
-        for (int j = 0; j < SG_N; ++j) {
-            if (!live[j]) continue;
-#pragma unroll
-            for (int r = 0; r < RPW; ++r) {
-                if (row0 + r >= m) continue;
-#pragma unroll
-                for (int q = 0; q < NRHS; ++q) {
-                    const double* add = shift(q == 0 ? add0 : add1, off[j]);
-                    const double base = add ? add[row0 + r] : 0.0;
-                    shift(Y, off[j])[(long long)q * ldy + row0 + r] = base + alpha * acc[j][r][q];
-                }
-            }
-        }
-    }
-}
-
-// gemv_t_kernel for a group: grid = (np / 512 rounded up, mp / GEMVT_ROWS, groups)
-template <int NRHS>
-__global__ __launch_bounds__(256) void gemv_t_shared_kernel(const double* __restrict__ A, long long lda, int np,
-                                                            const double* __restrict__ V, long long ldv,
-                                                            double* __restrict__ Upart, long long slab, int count, BatchK bk) {
-    long long off[SG_T];
-    bool live[SG_T];
-    if (!SharedGroup::load<SG_T>(bk, count, off, live)) return;
-    __shared__ double vs[SG_T][NRHS][GEMVT_ROWS];
-    const int tid = threadIdx.x;
-    const int col = (blockIdx.x * 256 + tid) * 2;
-    const int row0 = blockIdx.y * GEMVT_ROWS;
-    for (int e = tid; e < SG_T * NRHS * GEMVT_ROWS; e += 256) {
-        const int j = e / (NRHS * GEMVT_ROWS), q = (e / GEMVT_ROWS) % NRHS, r = e % GEMVT_ROWS;
-        vs[j][q][r] = shift(V, off[j])[(long long)q * ldv + row0 + r];
-    }
-    __syncthreads();
-    if (col >= np) return;
-    d2 acc[SG_T][NRHS];
-#pragma unroll
-    for (int j = 0; j < SG_T; ++j)
-#pragma unroll
-        for (int q = 0; q < NRHS; ++q) acc[j][q] = (d2){0.0, 0.0};
-    const double* ap = A + (long long)row0 * lda + col;
-#pragma unroll 8
-    for (int r = 0; r < GEMVT_ROWS; ++r) {
-        const d2 av = *(const d2*)(ap + (long long)r * lda);
-#pragma unroll
-        for (int j = 0; j < SG_T; ++j)
-#pragma unroll
-            for (int q = 0; q < NRHS; ++q) acc[j][q] += av * vs[j][q][r];
-    }
-#pragma unroll
-    for (int j = 0; j < SG_T; ++j) {
-        if (!live[j]) continue;
-#pragma unroll
-        for (int q = 0; q < NRHS; ++q)
-            *(d2*)(shift(Upart, off[j]) + ((long long)blockIdx.y * NRHS + q) * slab + col) = acc[j][q];
-    }
-}
-
-// gemv_dual_kernel for a group of SG members: the same units, waves, row groups and slabs; the 4-wave column combine runs
-// member after member through one LDS buffer
-template <int CW, int SG>
-__global__ __launch_bounds__(256) void gemv_dual_shared_kernel(const double* __restrict__ A, long long lda, int np,
-                                                               const double* __restrict__ W, const double* __restrict__ V,
-                                                               double* __restrict__ AxPart, long long mp,
-                                                               double* __restrict__ Upart, long long slab, int count, BatchK bk) {
-    long long off[SG];
-    bool live[SG];
-    if (!SharedGroup::load<SG>(bk, count, off, live)) return;
-    constexpr int NS = CW / 128;
-    const int ch = blockIdx.x, rb = blockIdx.y;
-    const int r0 = rb * GEMVT_ROWS, c0 = ch * CW;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __shared__ double vrow[SG][GEMVT_ROWS];
-    __shared__ double csum[4][CW];
-    for (int e = threadIdx.x; e < SG * GEMVT_ROWS; e += 256) vrow[e / GEMVT_ROWS][e % GEMVT_ROWS] = shift(V, off[e / GEMVT_ROWS])[r0 + e % GEMVT_ROWS];
-    d2 wc[SG][NS], cacc[SG][NS];
-#pragma unroll
-    for (int j = 0; j < SG; ++j)
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int col = c0 + s * 128 + 2 * lane;
-            wc[j][s] = col < np ? *(const d2*)(shift(W, off[j]) + col) : (d2){0.0, 0.0};
-            cacc[j][s] = (d2){0.0, 0.0};
-        }
-    __syncthreads();
-    constexpr int RG = NS >= 8 ? 2 : 4;      // rows per trip: as gemv_dual_kernel (the rows a wave takes fix the column sums)
-    for (int rr0 = wave * RG; rr0 < GEMVT_ROWS; rr0 += 4 * RG) {
-        d2 a[RG][NS];
-#pragma unroll
-        for (int g = 0; g < RG; ++g) {
-            const double* row = A + (long long)(r0 + rr0 + g) * lda + c0 + 2 * lane;
-#pragma unroll
-            for (int s = 0; s < NS; ++s)
-                a[g][s] = c0 + s * 128 + 2 * lane < np ? *(const d2*)(row + s * 128) : (d2){0.0, 0.0};
-        }
-        double racc[SG][RG];
-#pragma unroll
-        for (int j = 0; j < SG; ++j)
-#pragma unroll
-            for (int g = 0; g < RG; ++g) {
-                const double vr = vrow[j][rr0 + g];
-                racc[j][g] = 0.0;
-#pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    racc[j][g] += a[g][s][0] * wc[j][s][0] + a[g][s][1] * wc[j][s][1];
-                    cacc[j][s] += a[g][s] * vr;
-                }
-            }
-#pragma unroll
-        for (int off_ = 32; off_ >= 1; off_ >>= 1)
-#pragma unroll
-            for (int j = 0; j < SG; ++j)
-#pragma unroll
-                for (int g = 0; g < RG; ++g) racc[j][g] += __shfl_xor(racc[j][g], off_, 64);
-        if (lane == 0) {
-#pragma unroll
-            for (int j = 0; j < SG; ++j) {
-                if (!live[j]) continue;
-#pragma unroll
-                for (int g = 0; g < RG; ++g) shift(AxPart, off[j])[(long long)ch * mp + r0 + rr0 + g] = racc[j][g];
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < SG; ++j) {
-        if (j > 0) __syncthreads();                                 // the previous member's combine has read the buffer
-#pragma unroll
-        for (int s = 0; s < NS; ++s) *(d2*)&csum[wave][s * 128 + 2 * lane] = cacc[j][s];
-        __syncthreads();
-        if (live[j])
-            for (int e = threadIdx.x; e < CW; e += 256)
-                if (c0 + e < np)
-                    shift(Upart, off[j])[(long long)rb * slab + c0 + e] = ((csum[0][e] + csum[1][e]) + csum[2][e]) + csum[3][e];
-    }
-}
-
-static inline int shared_groups(int count, int sg) { return (count + sg - 1) / sg; }
-hipError_t launch_gemv_n_shared(const double* A, int64_t lda, int m, int np, int nrhs, const double* W, int64_t ldw,
-                                const double* add0, const double* add1, double* Y, int64_t ldy, hipStream_t st, const Batch& bt) {
-    const int groups = shared_groups(bt.count, SG_N);
-    // rows per wave: 4 when the launch has rows enough to fill the chip with them (W is re-read per wave from L2: more rows
-    // per wave, fewer re-reads), else 1
-    const int rpw = (long long)m * groups <= 2048 ? 1 : 4;
-    const dim3 grid((m + 4 * rpw - 1) / (4 * rpw), 1, groups);
-#define GNS_LAUNCH(NR, RPW) hipLaunchKernelGGL((gemv_n_shared_kernel<NR, RPW>), grid, dim3(256), 0, st, A, (long long)lda, m, np, W, \
-                                               (long long)ldw, add0, add1, Y, (long long)ldy, 1.0, bt.count, batch_k(bt))
-    if (nrhs == 1) { if (rpw == 1) GNS_LAUNCH(1, 1); else GNS_LAUNCH(1, 4); }
-    else           { if (rpw == 1) GNS_LAUNCH(2, 1); else GNS_LAUNCH(2, 4); }
-#undef GNS_LAUNCH
-    return hipGetLastError();
-}
-hipError_t launch_gemv_t_shared(const double* A, int64_t lda, int mp, int np, int nrhs, const double* V, int64_t ldv,
-                                double* Upart, hipStream_t st, int64_t slab, const Batch& bt) {
-    if (slab <= 0) slab = np;
-    const dim3 grid((np / 2 + 255) / 256, mp / GEMVT_ROWS, shared_groups(bt.count, SG_T));
-    if (nrhs == 1)
-        hipLaunchKernelGGL(gemv_t_shared_kernel<1>, grid, dim3(256), 0, st, A, (long long)lda, np, V, (long long)ldv, Upart, (long long)slab, bt.count, batch_k(bt));
-    else
-        hipLaunchKernelGGL(gemv_t_shared_kernel<2>, grid, dim3(256), 0, st, A, (long long)lda, np, V, (long long)ldv, Upart, (long long)slab, bt.count, batch_k(bt));
-    return hipGetLastError();
-}
-hipError_t launch_gemv_dual_shared(const double* A, int64_t lda, int mp, int np, const double* W, const double* V,
-                                   double* AxPart, double* Upart, int64_t slab, hipStream_t st, const Batch& bt) {
-    if (slab <= 0) slab = np;
-    // 1024-column chunks hold 8 column pairs per lane and member: 2 members per group; 256-column chunks: 4
-    if (np >= 4096) {
-        const dim3 grid(gemv_dual_chunks(np), mp / GEMVT_ROWS, shared_groups(bt.count, 2));
-        hipLaunchKernelGGL((gemv_dual_shared_kernel<1024, 2>), grid, dim3(256), 0, st, A, (long long)lda, np, W, V, AxPart, (long long)mp, Upart, (long long)slab, bt.count, batch_k(bt));
-    } else {
-        const dim3 grid(gemv_dual_chunks(np), mp / GEMVT_ROWS, shared_groups(bt.count, 4));
-        hipLaunchKernelGGL((gemv_dual_shared_kernel<256, 4>), grid, dim3(256), 0, st, A, (long long)lda, np, W, V, AxPart, (long long)mp, Upart, (long long)slab, bt.count, batch_k(bt));
-    }
+    const dim3 grid((np / 2 + 255) / 256, mp / GEMVT_ROWS, group_count(bt.count, shared_a ? SG_T : 1));
+#define GT_LAUNCH(NR, SG, SH) hipLaunchKernelGGL((gemv_t_kernel<NR, SG, SH>), grid, dim3(256), 0, st, A, (long long)lda, np, V, \
+                                                 (long long)ldv, Upart, (long long)slab, bt.count, batch_k(bt))
+    if (!shared_a) { if (nrhs == 1) GT_LAUNCH(1, 1, false);   else GT_LAUNCH(2, 1, false); }
+    else           { if (nrhs == 1) GT_LAUNCH(1, SG_T, true); else GT_LAUNCH(2, SG_T, true); }
+#undef GT_LAUNCH
     return hipGetLastError();
 }
 

@@ -652,7 +652,7 @@ static hipError_t potrf_panel_chain(double* M, int64_t ld, int mp, const FactorP
         t.C = panel; t.ldc = ld; t.K = NB; t.alpha = 1.0; t.beta = 0.0;
         // few tiles -> latency-bound: 32-row x 128-col tiles put 4x as many CUs on the panel, and a
         // workgroup still owns whole rows, so the product may overwrite its own input
-        t.tile_edge = 32;
+        t.tile_shape = TileShape::T32x128;
         t.ntiles = 4 * rem; t.tiles_lower = 0; t.ntj = 1; t.tile_list = nullptr;
         t.diag_pad_from = -1; t.ws = nullptr; t.nwg = t.ntiles; t.batch = bt;
         e = launch_gemm_nt(t, st);
@@ -666,7 +666,7 @@ static hipError_t potrf_panel_chain(double* M, int64_t ld, int mp, const FactorP
             c.C = M + (o + NB) * ld + (o + NB); c.ldc = ld; c.K = NB; c.alpha = -1.0; c.beta = 1.0;
             // 32x32 tiles: 16x as many workgroups as 128x128 ones, 32 MFMAs per wave; the launch is one round of tiles on the
             // chain (factorisation at m = 4096: 1998 us with 64x64 tiles, 1942 with 32x64, 1903 with 32x32)
-            c.tile_edge = 3232; c.tiles_lower = 0; c.ntj = 4 * ncols; c.ntiles = (4 * rem) * (4 * ncols);
+            c.tile_shape = TileShape::T32x32; c.tiles_lower = 0; c.ntj = 4 * ncols; c.ntiles = (4 * rem) * (4 * ncols);
             c.tile_list = nullptr; c.diag_pad_from = -1; c.ws = nullptr; c.nwg = c.ntiles; c.batch = bt;
             e = launch_gemm_nt(c, st);
             if (e != hipSuccess) return e;
@@ -691,15 +691,15 @@ static hipError_t trailing_update_columns(double* M, int64_t ld, int nb, hipStre
     if (C1 < nb) {
         // a band of columns: rectangular grid of 32x32 tiles, rows C0..nb x columns C0..C1 (the few tiles above the diagonal
         // are computed too and never read); it sits on the chain, and a 32x32 tile is the shortest MFMA chain there is
-        u.tile_edge = 3232; u.tiles_lower = 0; u.ntj = 4 * (C1 - C0); u.ntiles = (4 * remT) * (4 * (C1 - C0));
+        u.tile_shape = TileShape::T32x32; u.tiles_lower = 0; u.ntj = 4 * (C1 - C0); u.ntiles = (4 * remT) * (4 * (C1 - C0));
     } else {
         u.tiles_lower = 1; u.ntj = 0;
         // up to 16 trailing blocks (at most one round of 64x64 tiles) 32x32 tiles: the launch lasts as long as the busiest CU's
         // tiles, and a quarter-size tile is a quarter-length MFMA chain (m = 4096: 1889 -> 1858 us, m = 2048: 772 -> 745);
         // 64x64 tiles (4 workgroups per CU) until the 128x128 ones would fill the chip's 512 slots about twice
-        if (remT <= 16)                        { u.tile_edge = 3232; u.ntiles = (4 * remT) * (4 * remT + 1) / 2; }
-        else if (remT * (remT + 1) / 2 < 1024) { u.tile_edge = 64; u.ntiles = (2 * remT) * (2 * remT + 1) / 2; }
-        else                                   { u.tile_edge = 128; u.ntiles = remT * (remT + 1) / 2; }
+        if (remT <= 16)                        { u.tile_shape = TileShape::T32x32; u.ntiles = (4 * remT) * (4 * remT + 1) / 2; }
+        else if (remT * (remT + 1) / 2 < 1024) { u.tile_shape = TileShape::T64x64; u.ntiles = (2 * remT) * (2 * remT + 1) / 2; }
+        else                                   { u.tile_shape = TileShape::T128x128; u.ntiles = remT * (remT + 1) / 2; }
     }
     u.nwg = u.ntiles;
     return launch_gemm_nt(u, st);

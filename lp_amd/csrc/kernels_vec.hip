@@ -346,6 +346,10 @@ __device__ __forceinline__ double scalar_amin(const VecArgs& a, int mslot) {    
     const double ax = fold_min(a.red, mslot, a.nblk, 1.0), az = fold_min(a.red, mslot + 1, a.nblk, 1.0);
     return amin_from(a, ax, az, a.S[S_DTAU], a.S[S_DKAPPA]);
 }
+// gamma is needed ROUNDED (it is stored and multiplies mu), but where the compiler contracts, eta = 1 - gamma is formed from
+// the UNROUNDED last product of gamma (one fma: -(1-alpha)^2 * min(0.1, 1-alpha) + 1).  Every consumer of gamma and eta
+// goes through this function for that reason: a second statement of the same expressions, compiled in another kernel,
+// need not contract alike, and then two paths would be one rounding apart in eta.
 struct CorrScal { double alpha, gamma, eta, tk; };
 __device__ __forceinline__ CorrScal corr_from(const VecArgs& a, double amin, int ip, double d_tau, double d_kappa) {   // feasible_point.rs:134-136,156-165; rhat.rs:51-74
     const double* S = a.S;
@@ -361,6 +365,20 @@ __device__ __forceinline__ CorrScal corr_from(const VecArgs& a, double amin, int
 }
 __device__ __forceinline__ CorrScal scalar_corr(const VecArgs& a, double amin, int ip) {
     return corr_from(a, amin, ip, a.S[S_DTAU], a.S[S_DKAPPA]);
+}
+// what the corrector's set-up leaves in S (ONE thread); rg = S[S_RG], read by the caller before anything of S is written
+__device__ __forceinline__ void store_corr(double* S, const CorrScal& c, double rg) {
+    S[S_ALPHA_PRED] = c.alpha; S[S_GAMMA] = c.gamma; S[S_ETA] = c.eta;
+    S[S_RHAT_G] = rg * c.eta;                                         // rhat.rs:71
+    S[S_RHAT_TK] = c.tk;
+}
+// tau / kappa part of do_step (feasible_point.rs:76-106)
+struct TauKappa { double tau, kappa; };
+__device__ __forceinline__ TauKappa step_tau_kappa(const VecArgs& a, double d_tau, double d_kappa, double alpha, int ip) {
+    double tau = a.S[S_TAU] + d_tau * alpha;
+    double kappa = a.S[S_KAPPA] + d_kappa * alpha;
+    if (ip) { tau = fmax(tau, 1.0); kappa = fmax(kappa, 1.0); }
+    return TauKappa{tau, kappa};
 }
 
 // delta.rs:29-32 (d_tau) and :38 (d_kappa).  phase 0: predictor (all four dots fresh);
@@ -378,13 +396,9 @@ __global__ void k_scalar_dtau(VecArgs a, int phase) {
         cp = a.S[S_CP]; bq = a.S[S_BQ];
     }
     if (threadIdx.x != 0) return;
-    double* S = a.S;
-    const double tau = S[S_TAU], kappa = S[S_KAPPA];
-    const double d_tau = (S[S_RHAT_G] + 1.0 / tau * S[S_RHAT_TK] - (-cu + bv)) /
-                         (1.0 / tau * kappa + (-cp + bq));
-    const double d_kappa = 1.0 / tau * (S[S_RHAT_TK] - kappa * d_tau);
-    S[S_CP] = cp; S[S_BQ] = bq;
-    S[S_DTAU] = d_tau; S[S_DKAPPA] = d_kappa;
+    const DtauOut o = dtau_from(a, cp, cu, bq, bv);
+    a.S[S_CP] = o.cp; a.S[S_BQ] = o.bq;
+    a.S[S_DTAU] = o.d_tau; a.S[S_DKAPPA] = o.d_kappa;
 }
 
 // delta.rs:33-37 + the folds of get_step_size (feasible_point.rs:54-62).
@@ -429,31 +443,10 @@ __global__ void k_scalar_alpha(VecArgs a, int phase, int ip, double alpha0) {
     const int nblk = a.nblk;
     const double ax = a.gs ? a.gs[0] : fold_min(a.red, 0, nblk, 1.0), az = a.gs ? a.gs[1] : fold_min(a.red, 1, nblk, 1.0);
     if (threadIdx.x != 0) return;
-    double* S = a.S;
-    const double tau = S[S_TAU], kappa = S[S_KAPPA], d_tau = S[S_DTAU], d_kappa = S[S_DKAPPA];
-    const double at = d_tau < 0.0 ? fmin(1.0, tau / -d_tau) : 1.0;
-    const double ak = d_kappa < 0.0 ? fmin(1.0, kappa / -d_kappa) : 1.0;
-    const double amin = fmin(fmin(fmin(fmin(1.0, ax), at), az), ak);
-    if (phase == 0) {
-        const double alpha = amin * 1.0;                              // feasible_point.rs:134
-        const double mu = S[S_MU];
-        double gamma;
-        if (ip) gamma = 10.0;                                         // :158-160
-        else gamma = (1.0 - alpha) * (1.0 - alpha) * fmin(0.1, 1.0 - alpha);  // :163-164
-        const double eta = ip ? 1.0 : 1.0 - gamma;                    // :136
-        double tk;
-        if (ip) {                                                     // rhat.rs:52,57-59
-            const double alpha_2 = alpha * alpha;
-            tk = (1.0 - alpha) * gamma * mu - tau * kappa - alpha_2 * d_tau * d_kappa;
-        } else {                                                      // rhat.rs:65
-            tk = gamma * mu - tau * kappa - d_tau * d_kappa;
-        }
-        S[S_ALPHA_PRED] = alpha; S[S_GAMMA] = gamma; S[S_ETA] = eta;
-        S[S_RHAT_G] = S[S_RG] * eta;                                  // rhat.rs:71
-        S[S_RHAT_TK] = tk;
-    } else {
-        S[S_ALPHA] = ip ? 1.0 : amin * alpha0;                        // mod.rs:216-221
-    }
+    const double d_tau = a.S[S_DTAU], d_kappa = a.S[S_DKAPPA];
+    const double amin = amin_from(a, ax, az, d_tau, d_kappa);
+    if (phase == 0) store_corr(a.S, corr_from(a, amin, ip, d_tau, d_kappa), a.S[S_RG]);
+    else a.S[S_ALPHA] = ip ? 1.0 : amin * alpha0;                     // mod.rs:216-221
 }
 
 // Rhat::corrector vector parts (rhat.rs:51-56 / :62-64, :69-70) and the r1 / Dinv*r1 of the
@@ -484,11 +477,7 @@ __global__ __launch_bounds__(256) void k_corr_setup(VecArgs a, int ip) {
     if (FOLD) {     // k_scalar_alpha(phase 0) folded in
         const CorrScal c = scalar_corr(a, scalar_amin(a, 4), ip);
         gamma = c.gamma; eta = c.eta; alpha = c.alpha;
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            a.S[S_ALPHA_PRED] = c.alpha; a.S[S_GAMMA] = c.gamma; a.S[S_ETA] = c.eta;
-            a.S[S_RHAT_G] = a.S[S_RG] * c.eta;                           // rhat.rs:71
-            a.S[S_RHAT_TK] = c.tk;
-        }
+        if (blockIdx.x == 0 && threadIdx.x == 0) store_corr(a.S, c, a.S[S_RG]);
     } else { gamma = a.S[S_GAMMA]; eta = a.S[S_ETA]; alpha = a.S[S_ALPHA_PRED]; }
     body_corr_setup(a, plain_thread(), ip, gamma, eta, alpha, mu);
 }
@@ -519,13 +508,9 @@ __global__ __launch_bounds__(256) void k_step(VecArgs a, int ip, double alpha0) 
 __global__ void k_step_scalars(VecArgs a, int ip) {
     if (!vbatch(a, true)) return;
     if (threadIdx.x != 0) return;
-    double* S = a.S;
-    const double alpha = S[S_ALPHA];
-    double tau = S[S_TAU] + S[S_DTAU] * alpha;
-    double kappa = S[S_KAPPA] + S[S_DKAPPA] * alpha;
-    if (ip) { tau = fmax(tau, 1.0); kappa = fmax(kappa, 1.0); }
-    S[S_TAU] = tau;
-    S[S_KAPPA] = kappa;
+    const TauKappa tk = step_tau_kappa(a, a.S[S_DTAU], a.S[S_DKAPPA], a.S[S_ALPHA], ip);
+    a.S[S_TAU] = tk.tau;
+    a.S[S_KAPPA] = tk.kappa;
 }
 
 // ---------------------------------------------------------------- fused vector stage (one workgroup per LP)
@@ -607,9 +592,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_fused_predictor(VecArgs a, in
     __syncthreads();                                       // every read of S above precedes the writes below
     if (threadIdx.x == 0) {
         a.S[S_DTAU] = o.d_tau; a.S[S_DKAPPA] = o.d_kappa; a.S[S_CP] = o.cp; a.S[S_BQ] = o.bq;
-        a.S[S_ALPHA_PRED] = c.alpha; a.S[S_GAMMA] = c.gamma; a.S[S_ETA] = c.eta;
-        a.S[S_RHAT_G] = rg * c.eta;                        // rhat.rs:71
-        a.S[S_RHAT_TK] = c.tk;
+        store_corr(a.S, c, rg);
     }
     for (int r = 0; r < rounds; ++r) {
         const VThread t = fused_thread(a, r);
@@ -643,13 +626,11 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_fused_corrector(VecArgs a, in
     double mins[2];
     fused_total<2, true>(sm2b, a.nblk, mins);
     const double alpha = ip ? 1.0 : amin_from(a, mins[0], mins[1], o.d_tau, o.d_kappa) * alpha0;
-    double tau = a.S[S_TAU] + o.d_tau * alpha;             // k_step_scalars
-    double kappa = a.S[S_KAPPA] + o.d_kappa * alpha;
-    if (ip) { tau = fmax(tau, 1.0); kappa = fmax(kappa, 1.0); }
+    const TauKappa tk = step_tau_kappa(a, o.d_tau, o.d_kappa, alpha, ip);    // k_step_scalars
     __syncthreads();                                       // every read of S above precedes the writes below
     if (threadIdx.x == 0) {
         a.S[S_DTAU] = o.d_tau; a.S[S_DKAPPA] = o.d_kappa; a.S[S_ALPHA] = alpha;
-        a.S[S_TAU] = tau; a.S[S_KAPPA] = kappa;
+        a.S[S_TAU] = tk.tau; a.S[S_KAPPA] = tk.kappa;
     }
     for (int r = 0; r < rounds; ++r) {
         const VThread t = fused_thread(a, r);

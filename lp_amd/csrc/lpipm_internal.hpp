@@ -95,6 +95,8 @@ struct Arena {
 //   A.D.A^T            (P = Q = A, s = x/z, lower tiles, stream-K over n)   newton_equations.rs:55-57
 //   trailing update    (P = Q = L21, alpha=-1, beta=1, lower tiles)         Cholesky, :129-131
 //   TRSM as GEMM       (P = A21, Q = inv(L11), rectangular tiles)
+// output tile of a whole-tile launch (rows x columns); tile indices count in these units
+enum class TileShape { T128x128, T64x64, T32x128, T32x32 };
 struct GemmArgs {
     const double* P; int64_t ldp;
     const double* Q; int64_t ldq;
@@ -115,7 +117,7 @@ struct GemmArgs {
                                 //   (workgroups that finish their data-parallel tiles early take more of them); slabs are
                                 //   indexed by chunk, so the sums do not depend on who computed what
     double*       C2;           // stream-K launches whose tiles are all split (ntiles < nwg): final values stored here too
-    int           tile_edge;    // whole-tile launches: 0/128 -> 128x128 tiles, 64 -> 64x64, 32 -> 32 rows x 128 cols, 3232 -> 32x32
+    TileShape     tile_shape;   // whole-tile launches (a value-initialised GemmArgs has 128x128)
     Batch         batch;        // lockstep batch (every pointer above except tile_list is per LP)
     bool          shared_a = false;   // P and Q are ONE matrix the whole batch shares (member stride 0; lpipm_upload_lockstep_shared)
 };
@@ -238,31 +240,27 @@ hipError_t launch_qr_solve(const double* M, int64_t ld, int mp, const double* ta
                            int32_t* info, hipStream_t st);
 
 // ---------------------------------------------------------------- GEMV (kernels_gemv.hip)
+// The three passes over A.  shared_a (as in GemmArgs, AdatUnitsArgs): A is ONE matrix that every member of the batch shares
+// (lpipm_upload_lockstep_shared) and is not offset by the member (the other operands are); each A element a wave loads
+// serves a GROUP of members before the next one is read (gridDim.z = groups), so a pass reads A ceil(count / group) times
+// instead of count times.  Every output is summed the same way whatever the group (same lane striding and butterfly, same
+// row slabs, same chunk slabs): a member's bits do not depend on whether A is shared.  Finished members are skipped and
+// their outputs untouched.
 // Y[r][i] = (add[r] ? add[r][i] : 0) + alpha * sum_k A[i][k] * W[r][k],   i < m, k < np
 hipError_t launch_gemv_n(const double* A, int64_t lda, int m, int np, int nrhs, const double* W,
                          int64_t ldw, const double* add0, const double* add1, double* Y, int64_t ldy,
-                         hipStream_t st, double alpha = 1.0, const Batch& bt = Batch{});
+                         hipStream_t st, double alpha = 1.0, const Batch& bt = Batch{}, bool shared_a = false);
 // Upart[s][r][k] = sum_{i in row split s} A[i][k] * V[r][i];  consumers sum the splits in order.
 constexpr int GEMVT_ROWS = 128;
 // np: columns processed (multiple of 2); slab: stride between slabs (0 = np)
 hipError_t launch_gemv_t(const double* A, int64_t lda, int mp, int np, int nrhs, const double* V,
-                         int64_t ldv, double* Upart, hipStream_t st, int64_t slab = 0, const Batch& bt = Batch{});
+                         int64_t ldv, double* Upart, hipStream_t st, int64_t slab = 0, const Batch& bt = Batch{},
+                         bool shared_a = false);
 // One read of A for both products of the residual pair: AxPart[ch][i] = sum over column chunk ch of A[i][k] W[k]
 // (gemv_dual_chunks(np) slabs of mp doubles: consumers add them in order) and the row-split slabs of A^T.V as gemv_t.
 int gemv_dual_chunks(int np);
 hipError_t launch_gemv_dual(const double* A, int64_t lda, int mp, int np, const double* W, const double* V, double* AxPart,
-                            double* Upart, int64_t slab, hipStream_t st, const Batch& bt = Batch{});
-// ---- the same three passes over ONE matrix A that every member of the batch shares (lpipm_upload_lockstep_shared): A is
-// not offset by the member (the other operands are); each A element a wave loads serves a GROUP of members before the next
-// one is read (gridDim.z = groups), so a pass reads A ceil(count / group) times instead of count times.  Every output is
-// summed exactly as the single-member kernel above sums it (same lane striding and butterfly, same row slabs, same chunk
-// slabs): a member's bits do not depend on whether A is shared.  Finished members are skipped and their outputs untouched.
-hipError_t launch_gemv_n_shared(const double* A, int64_t lda, int m, int np, int nrhs, const double* W, int64_t ldw,
-                                const double* add0, const double* add1, double* Y, int64_t ldy, hipStream_t st, const Batch& bt);
-hipError_t launch_gemv_t_shared(const double* A, int64_t lda, int mp, int np, int nrhs, const double* V, int64_t ldv,
-                                double* Upart, hipStream_t st, int64_t slab, const Batch& bt);
-hipError_t launch_gemv_dual_shared(const double* A, int64_t lda, int mp, int np, const double* W, const double* V,
-                                   double* AxPart, double* Upart, int64_t slab, hipStream_t st, const Batch& bt);
+                            double* Upart, int64_t slab, hipStream_t st, const Batch& bt = Batch{}, bool shared_a = false);
 // Rho[q] = R0[q] - M.V[q] (q < nrhs) for a symmetric mp x mp M whose LOWER triangle is stored (one read of it);
 // slabs: symv_slab_doubles(mp) doubles of scratch.  The residual of the refinement step of the Cholesky solve.
 size_t symv_slab_doubles(int mp);

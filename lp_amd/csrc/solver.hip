@@ -766,23 +766,20 @@ extern "C" int lpipm_upload_ub_eq(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const
 static hipError_t ctx_gemv_n(lpipm_ctx* c, int nrhs, const double* W, const double* add0, const double* add1, double* Y,
                              const Batch& bt) {
     ++c->gemv_passes;
-    if (c->p.shared_a) return launch_gemv_n_shared(c->p.A, c->p.npa, (int)c->p.m, c->p.npa, nrhs, W, c->p.np, add0, add1, Y, c->p.mp, c->rs.st, bt);
-    hipError_t e = launch_gemv_n(c->p.A, c->p.npa, (int)c->p.m, c->p.npa, nrhs, W, c->p.np, add0, add1, Y, c->p.mp, c->rs.st, 1.0, bt);
-    if (e != hipSuccess) return e;
+    hipError_t e = launch_gemv_n(c->p.A, c->p.npa, (int)c->p.m, c->p.npa, nrhs, W, c->p.np, add0, add1, Y, c->p.mp, c->rs.st, 1.0, bt, c->p.shared_a);
+    if (e != hipSuccess || c->p.shared_a) return e;      // (no slack launch behind a shared A)
     return launch_slack_n(c->p.ns, c->p.nx, nrhs, W, c->p.np, Y, c->p.mp, c->rs.st, bt);
 }
 static hipError_t ctx_gemv_t(lpipm_ctx* c, int nrhs, const double* V, const Batch& bt) {
     ++c->gemv_passes;
-    if (c->p.shared_a) return launch_gemv_t_shared(c->p.A, c->p.npa, c->p.mp, c->p.npa, nrhs, V, c->p.mp, c->p.ATpart, c->rs.st, c->p.np, bt);
-    hipError_t e = launch_gemv_t(c->p.A, c->p.npa, c->p.mp, c->p.npa, nrhs, V, c->p.mp, c->p.ATpart, c->rs.st, c->p.np, bt);
-    if (e != hipSuccess) return e;
+    hipError_t e = launch_gemv_t(c->p.A, c->p.npa, c->p.mp, c->p.npa, nrhs, V, c->p.mp, c->p.ATpart, c->rs.st, c->p.np, bt, c->p.shared_a);
+    if (e != hipSuccess || c->p.shared_a) return e;      // (no slack launch behind a shared A)
     return launch_slack_t(c->p.ns, c->p.nx, nrhs, c->p.nsplit, V, c->p.mp, c->p.ATpart, c->p.np, c->rs.st, bt);
 }
 // both in one read of A: chunk slabs of A.w into AxPart (gemv_dual_chunks(npa) of them), row-split slabs of A^T.v into ATpart
 static hipError_t ctx_gemv_dual(lpipm_ctx* c, const double* W, const double* V, double* AxPart, const Batch& bt) {
     ++c->gemv_passes;
-    hipError_t e = c->p.shared_a ? launch_gemv_dual_shared(c->p.A, c->p.npa, c->p.mp, c->p.npa, W, V, AxPart, c->p.ATpart, c->p.np, c->rs.st, bt)
-                               : launch_gemv_dual(c->p.A, c->p.npa, c->p.mp, c->p.npa, W, V, AxPart, c->p.ATpart, c->p.np, c->rs.st, bt);
+    hipError_t e = launch_gemv_dual(c->p.A, c->p.npa, c->p.mp, c->p.npa, W, V, AxPart, c->p.ATpart, c->p.np, c->rs.st, bt, c->p.shared_a);
     if (e != hipSuccess) return e;
     e = launch_slack_n(c->p.ns, c->p.nx, 1, W, c->p.np, AxPart, c->p.mp, c->rs.st, bt);          // into chunk slab 0
     if (e != hipSuccess) return e;

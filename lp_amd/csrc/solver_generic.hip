@@ -341,7 +341,6 @@ template <typename T> __global__ __launch_bounds__(VT) void kv_epi(GVec<T> a, in
 // step length (mod.rs:216-221) and do_step (feasible_point.rs:76-106).
 template <typename T> __global__ __launch_bounds__(VT) void kv_delta(GVec<T> a, int phase, int ip, T alpha0) {
     __shared__ T red[VT];
-    __shared__ T sh[4];
     GScal<T>& S = *a.S;
     T cu = 0, bv = 0, cp = 0, bq = 0;
     for (int j = threadIdx.x; j < a.n; j += VT) { cu += a.c[j] * a.u[j]; cp += a.c[j] * a.p[j]; }
@@ -402,7 +401,6 @@ template <typename T> __global__ __launch_bounds__(VT) void kv_delta(GVec<T> a, 
             S.tau = tn; S.kappa = kn; S.alpha = alpha;
         }
     }
-    (void)sh;
 }
 // x / tau (mod.rs:231,238) and fun = c.x + c0 (mod.rs:165, linear_program.rs:61-63)
 template <typename T> __global__ __launch_bounds__(VT) void kv_final(GVec<T> a, T* xout, T* fun) {
@@ -595,16 +593,16 @@ static int generic_solve(lpipm_ctx_device dev, uint64_t m64, uint64_t n64, const
 
 using namespace lpipm;
 
-// interior_point/mod.rs:161-168 for F = f32 (src/float.rs:42-43).  Host arrays in, host arrays out; the problem is uploaded,
-// solved and released inside the call (the f32 instantiation keeps no state in the context).  log (nullable): max_iter rows.
-extern "C" int lpipm_solve_f32(lpipm_ctx* ctx, uint64_t m, uint64_t n, const float* A, uint64_t lda, const float* b, const float* c,
-                               float c0, const lpipm_opts* opts, float* x_slack_out, float* fun_out, uint64_t* iterations_out,
-                               lpipm_iter_row_f32* log) {
+// Host arrays in, host arrays out; the problem is uploaded, solved and released inside the call (the generic instantiations
+// keep no state in the context).  log (nullable): max_iter rows.
+template <typename T, typename Row>
+static int solve_entry(lpipm_ctx* ctx, uint64_t m, uint64_t n, const T* A, uint64_t lda, const T* b, const T* c, T c0,
+                       const lpipm_opts* opts, T* x_slack_out, T* fun_out, uint64_t* iterations_out, Row* log) {
     if (!ctx) return LPIPM_ERR_BAD_ARGUMENT;
-    std::vector<generic::GStatus<float>> rows(log && opts ? (size_t)opts->max_iter : 0);
+    std::vector<generic::GStatus<T>> rows(log && opts ? (size_t)opts->max_iter : 0);
     uint64_t its = 0;
-    const int rc = generic::generic_solve<float>(lpipm_ctx_device_of(ctx), m, n, A, lda, b, c, c0, opts, x_slack_out, fun_out, &its,
-                                                 rows.empty() ? nullptr : rows.data());
+    const int rc = generic::generic_solve<T>(lpipm_ctx_device_of(ctx), m, n, A, lda, b, c, c0, opts, x_slack_out, fun_out, &its,
+                                             rows.empty() ? nullptr : rows.data());
     if (iterations_out) *iterations_out = its;
     for (uint64_t i = 0; log && i < its && i < rows.size() && rc != LPIPM_NUMERICAL_PROBLEM; ++i) {
         const auto& r = rows[i];
@@ -614,20 +612,16 @@ extern "C" int lpipm_solve_f32(lpipm_ctx* ctx, uint64_t m, uint64_t n, const flo
     return rc;
 }
 
+// interior_point/mod.rs:161-168 for F = f32 (src/float.rs:42-43)
+extern "C" int lpipm_solve_f32(lpipm_ctx* ctx, uint64_t m, uint64_t n, const float* A, uint64_t lda, const float* b, const float* c,
+                               float c0, const lpipm_opts* opts, float* x_slack_out, float* fun_out, uint64_t* iterations_out,
+                               lpipm_iter_row_f32* log) {
+    return solve_entry(ctx, m, n, A, lda, b, c, c0, opts, x_slack_out, fun_out, iterations_out, log);
+}
+
 // Test hook: the same generic kernels with T = double (see the head of this file).
 extern "C" int lpipm_k_generic_solve_f64(lpipm_ctx* ctx, uint64_t m, uint64_t n, const double* A, uint64_t lda, const double* b,
                                          const double* c, double c0, const lpipm_opts* opts, double* x_slack_out, double* fun_out,
                                          uint64_t* iterations_out, lpipm_iter_row* log) {
-    if (!ctx) return LPIPM_ERR_BAD_ARGUMENT;
-    std::vector<generic::GStatus<double>> rows(log && opts ? (size_t)opts->max_iter : 0);
-    uint64_t its = 0;
-    const int rc = generic::generic_solve<double>(lpipm_ctx_device_of(ctx), m, n, A, lda, b, c, c0, opts, x_slack_out, fun_out, &its,
-                                                  rows.empty() ? nullptr : rows.data());
-    if (iterations_out) *iterations_out = its;
-    for (uint64_t i = 0; log && i < its && i < rows.size() && rc != LPIPM_NUMERICAL_PROBLEM; ++i) {
-        const auto& r = rows[i];
-        log[i].alpha = r.alpha; log[i].rho_p = r.rho_p; log[i].rho_d = r.rho_d; log[i].rho_A = r.rho_A;
-        log[i].rho_g = r.rho_g; log[i].rho_mu = r.rho_mu; log[i].obj = r.obj;
-    }
-    return rc;
+    return solve_entry(ctx, m, n, A, lda, b, c, c0, opts, x_slack_out, fun_out, iterations_out, log);
 }

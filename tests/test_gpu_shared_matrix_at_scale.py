@@ -1,6 +1,6 @@
-"""Lockstep batches on ONE shared constraint matrix (lpipm_upload_lockstep_shared) at every variant of the three shared
-passes over A (gemv_n_shared_kernel, gemv_t_shared_kernel, gemv_dual_shared_kernel) and every layout of their member
-groups.  Which branch a case reaches follows from the host-side rules, mirrored in _plan() and asserted by each test:
+"""Lockstep batches on ONE shared constraint matrix (lpipm_upload_lockstep_shared) at every variant of the three passes
+over a shared A (the SHARED instantiations of gemv_n_kernel, gemv_t_kernel, gemv_dual_kernel) and every layout of their
+member groups.  Which branch a case reaches follows from the host-side rules, mirrored in _plan() and asserted by each test:
 
   mp = m rounded up to 128, npa = n rounded up to 16; a batch of 16 or more runs as two half-batch views of B / 2 and
   B - B / 2 members (the second with first != 0), and every rule below sees the VIEW's count;
@@ -38,15 +38,16 @@ the hooks on a single upload, and within oracle.vector_checks.check_gemv's compo
 reference.
 
 That the file bites: six changes to kernels_gemv.hip, each built and run once on an MI355X against the shared-matrix tests
-that existed before (tests/test_gpu_shared_matrix.py, the only other file that uploads a shared matrix) and against this file:
+that existed before (tests/test_gpu_shared_matrix.py, the only other file that uploads a shared matrix) and against this
+file (a record of that run; the kernels and launchers are named as they are named now):
 
   change                                                              before          this file
-  1 launch_gemv_dual_shared, 1024 branch: groups of 4 in the grid      passes          5 fail (dual x 4, 2100 x 4200)
-  2 gemv_dual_shared_kernel<1024, 2>: RG forced to 4                   passes          12 fail (those 5, 7 dual hooks)
+  1 launch_gemv_dual, shared 1024 branch: groups of 4 in the grid      passes          5 fail (dual x 4, 2100 x 4200)
+  2 gemv_dual_kernel<1024, 2, true>: RG forced to 4                    passes          12 fail (those 5, 7 dual hooks)
   3 the same kernel: column sub-slab NS - 1 left out of cacc (NS = 8)  passes          12 fail (the same 12)
-  4 gemv_n_shared_kernel: if (row0 + RPW > m) return                   passes          2 fail (RPW test at m = 1009 and 527)
-  5 gemv_t_shared_kernel: the store loop stops at SG_T - 1             3 of 10 fail    7 fail (RPW x 4, layouts, staggered x 2)
-  6 SharedGroup::load: the member after a finished one not live        7 of 10 fail    3 fail (staggered x 2, 1000 x 5000)
+  4 gemv_n_kernel, groups of 4: if (row0 + RPW > m) return             passes          2 fail (RPW test at m = 1009 and 527)
+  5 gemv_t_kernel, groups of 8: the store loop stops at SG_T - 1       3 of 10 fail    7 fail (RPW x 4, layouts, staggered x 2)
+  6 group_load: the member after a finished one not live               7 of 10 fail    3 fail (staggered x 2, 1000 x 5000)
 
 Wall time of this file on an MI355X box (16 CPUs): 53 s, against 74 s for tests/test_gpu_vector_stage_at_scale.py in the
 same run of the suite (WALL_TIME below).
@@ -80,7 +81,7 @@ def _views(count):
 
 
 def _plan(m, n, count=1):
-    """The host-side launch rules (upload_impl, plan_adat, launch_gemv_*_shared, adat_units_chunking) for one VIEW of
+    """The host-side launch rules (upload_impl, plan_adat, launch_gemv_* with shared_a, adat_units_chunking) for one VIEW of
     `count` members."""
     mp, npa = _up(m, 128), _up(n, 16)
     KT = npa // 16
@@ -213,7 +214,7 @@ def _default_opts():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# launch_gemv_dual_shared, npa >= 4096: gemv_dual_shared_kernel<1024, 2>
+# launch_gemv_dual with shared_a, npa >= 4096: gemv_dual_kernel<1024, 2, true>
 DUAL_SHAPES = [(333, 4100, 11), (512, 4096, 12), (300, 9000, 13), (1000, 5000, 115)]
 
 
@@ -243,7 +244,7 @@ def test_dual_pass_1024_columns_groups_of_two(ctx, m, n, seed):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# launch_gemv_n_shared: 4 rows per wave with a row tail, and 1 row per wave, on one A
+# launch_gemv_n with shared_a: 4 rows per wave with a row tail, and 1 row per wave, on one A
 RPW_SHAPES = [(700, 1500, 121, 13), (1009, 1100, 22, 9), (516, 1100, 23, 13), (527, 1200, 124, 13)]
 
 
@@ -291,7 +292,7 @@ def test_super_blocks_2100x4200(ctx):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# SharedGroup::load: every short last group, one view and two
+# group_load: every short last group, one view and two
 LAYOUT_COUNTS = (7, 9, 10, 15, 16, 17, 23, 27, 33)
 
 
@@ -423,7 +424,7 @@ HOOK_SHAPES = [(m, n) for m, n, _ in DUAL_SHAPES] + [(m, n) for m, n, _, _ in RP
 @pytest.mark.parametrize("m,n", HOOK_SHAPES)
 def test_gemv_hooks_on_shared_upload(built, m, n):
     """lpipm_k_gemv_n / _t / _dual on a context uploaded with upload_lockstep_shared (count 1 and count 5) run
-    gemv_n_shared_kernel / gemv_t_shared_kernel / gemv_dual_shared_kernel: bit-equal to the hooks on a single upload of the
+    the SHARED instantiations of gemv_n_kernel / gemv_t_kernel / gemv_dual_kernel: bit-equal to the hooks on a single upload of the
     same A, and inside the componentwise bound 2 k u |A| |w| of the extended-precision reference."""
     import lp_amd
     from lp_amd import synth

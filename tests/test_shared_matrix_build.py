@@ -1,12 +1,22 @@
-"""Build-time properties of the passes over a shared constraint matrix (kernels_gemv.hip, *_shared_kernel): every
+"""Build-time properties of the passes over A (kernels_gemv.hip: gemv_n_kernel, gemv_t_kernel, gemv_dual_kernel, each
+one template for members that own their A -- groups of one -- and for groups of members that share one A): every
 instantiation exists and carries NO VGPR / SGPR spill and no scratch -- a group of members is held in registers, and a
-spill would put a scratch round trip into every step of a pass that exists to save memory traffic.  Read from hipcc's own
-resource-usage remarks; no GPU needed."""
+spill would put a scratch round trip into every step of a pass that exists to save memory traffic -- and keeps at least
+the waves per SIMD it was written for.  Read from hipcc's own resource-usage remarks; no GPU needed."""
 import os
 import re
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# template arguments as they stand in the mangled name -> least waves per SIMD
+#   gemv_n_kernel<NRHS, RPW, SG, SHARED>, gemv_t_kernel<NRHS, SG, SHARED>, gemv_dual_kernel<CW, SG, SHARED>
+WAVES_PER_SIMD = {
+    "gemv_n_kernel": {(1, 1, 1, 0): 8, (1, 2, 1, 0): 8, (2, 1, 1, 0): 8, (2, 2, 1, 0): 8,
+                      (1, 1, 4, 1): 8, (1, 4, 4, 1): 7, (2, 1, 4, 1): 7, (2, 4, 4, 1): 3},
+    "gemv_t_kernel": {(1, 1, 0): 8, (2, 1, 0): 8, (1, 8, 1): 6, (2, 8, 1): 3},
+    "gemv_dual_kernel": {(1024, 1, 0): 3, (256, 1, 0): 5, (1024, 2, 1): 2, (256, 4, 1): 2},
+}
 
 
 def test_shared_matrix_kernels_have_no_spills():
@@ -15,13 +25,17 @@ def test_shared_matrix_kernels_have_no_spills():
                           "-Rpass-analysis=kernel-resource-usage", src, "-o", os.devnull],
                          capture_output=True, text=True, cwd=os.path.dirname(src)).stderr
     blocks = re.split(r"remark: Function Name: ", out)
-    names = {"gemv_n_shared_kernel": 4, "gemv_t_shared_kernel": 2, "gemv_dual_shared_kernel": 2}
-    for name, count in names.items():
-        found = [b for b in blocks[1:] if name in b.splitlines()[0]]
-        assert len(found) == count, (name, [b.splitlines()[0] for b in blocks[1:]])
-        for b in found:
+    for name, floors in WAVES_PER_SIMD.items():
+        found = {}
+        for b in blocks[1:]:
+            m = re.match(r"_ZN5lpipm\d+" + name + r"I((?:L[ib]\d+E)+)E", b)
+            if m:
+                found[tuple(int(v) for v in re.findall(r"L[ib](\d+)E", m.group(1)))] = b
+        assert sorted(found) == sorted(floors), (name, [b.splitlines()[0] for b in blocks[1:]])
+        for args, b in found.items():
             get = lambda key: int(re.search(key + r": (\d+)", b).group(1))
             assert get(r"VGPRs Spill") == 0 and get(r"SGPRs Spill") == 0 and get(r"ScratchSize \[bytes/lane\]") == 0, b
+            assert get(r"Occupancy \[waves/SIMD\]") >= floors[args], (name, args, b)
 
 
 def test_planted_scenarios_have_their_planted_optimum():
