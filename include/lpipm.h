@@ -64,7 +64,10 @@ typedef struct { double alpha, rho_p, rho_d, rho_A, rho_g, rho_mu, obj; } lpipm_
 typedef struct { float alpha, rho_p, rho_d, rho_A, rho_g, rho_mu, obj; } lpipm_iter_row_f32;
 
 /* Device time per phase of the LAST lpipm_solve on this ctx, from HIP events on the ctx's stream
- * (only filled while profiling is on; recording events costs a few us per phase). */
+ * (only filled while profiling is on; recording events costs a few us per phase).  The marks sit on the ctx's stream: what a
+ * large single LP runs beside the factorisation's chain on the look-ahead's side stream (trailing updates, merges of the
+ * super-block inverses, the predictor's pass over A and the first forward steps of its solve) falls inside the
+ * factorisation's interval and is counted in potrf_ms; gemv_passes still counts that pass. */
 typedef struct {
     double   adat_ms;      /* sum over iterations of the A.D.A^T kernel launches       */
     double   potrf_ms;     /* Cholesky factorisation (+ diagonal-block inverses)        */

@@ -716,7 +716,7 @@ static hipError_t potrf_superblock_inverses(const FactorPlan& plan, hipStream_t 
 }
 
 hipError_t launch_potrf(double* M, int64_t ld, int mp, const FactorPlan& plan, int32_t* info, hipStream_t st,
-                        const Batch& bt, const PotrfLookahead* la, bool clear_info) {
+                        const Batch& bt, const PotrfLookahead* la, bool clear_info, PotrfBeside* beside) {
     hipError_t e = clear_info ? potrf_clear_info(info, st, bt) : hipSuccess;   // (the solver's iteration keeps the word clean itself)
     if (e != hipSuccess) return e;
     const int nb = mp / NB;
@@ -732,6 +732,31 @@ hipError_t launch_potrf(double* M, int64_t ld, int mp, const FactorPlan& plan, i
     const int npanel = (nb + OUTER - 1) / OUTER;
     const bool ahead = la && la->side && bt.count == 1 && (int)la->ev_chain.size() >= npanel && nb >= 3 * OUTER && nb >= la->min_nb;
     int pending = -1;                            // panel whose rest-update the chain stream has not waited for yet
+    // Beside the chain, behind each rest-update (so the chain never waits for them; the side stream idles for most of a
+    // panel's chain: its rest-updates take 131, 95, 67, 45 us and less in windows of ~190 us at m = 4096): the merges of the
+    // super-block inverses whose inputs that panel completed, and the caller's own work (PotrfBeside).  They read block
+    // columns of L and 128-block inverses of finished panels only and write the off-diagonal blocks of the super-block
+    // inverses and each merge's own slice of the workspace, which nothing on the chain touches.
+    std::vector<size_t> issued(plan.stages.size(), 0);   // descriptors of each stage already on the side stream
+    int sb_next = 0, last_side = -1;
+    const bool join = ahead && la->ev_join;
+    auto beside_panel = [&](int pnl) -> hipError_t {
+        hipError_t e2;
+        for (const MergeGroup& g : plan.groups) {
+            if (g.panel > pnl || (size_t)(g.first - plan.stages[g.stage].first) < issued[g.stage]) continue;
+            if ((e2 = launch_gemm_grouped(plan.descs_dev + g.first, g.count, la->side, bt, plan.merge_edge)) != hipSuccess) return e2;
+            issued[g.stage] += (size_t)g.count;
+        }
+        if (!beside || !beside->at) return hipSuccess;
+        if (beside->calls == 0) { ++beside->calls; if ((e2 = beside->at(beside->self, -1, la->side)) != hipSuccess) return e2; }
+        for (; sb_next < (int)plan.sbs.size(); ++sb_next) {
+            const SuperBlock& s = plan.sbs[sb_next];
+            if (((s.row0 + s.size) / NB - 1) / OUTER > pnl) break;
+            ++beside->calls;
+            if ((e2 = beside->at(beside->self, sb_next, la->side)) != hipSuccess) return e2;
+        }
+        return hipSuccess;
+    };
     for (int J0 = 0, pnl = 0; J0 < nb; J0 += OUTER, ++pnl) {
         const int J1 = J0 + OUTER < nb ? J0 + OUTER : nb;
         if ((e = potrf_panel_chain(M, ld, mp, plan, info, st, bt, J0, J1)) != hipSuccess) return e;
@@ -747,13 +772,25 @@ hipError_t launch_potrf(double* M, int64_t ld, int mp, const FactorPlan& plan, i
             if ((e = trailing_update_columns(M, ld, nb, la->side, bt, J0, J1, J2, nb)) != hipSuccess) return e;
             if ((e = hipEventRecord(la->ev_rest[pnl], la->side)) != hipSuccess) return e;
             pending = pnl;
+            if (join) { if ((e = beside_panel(pnl)) != hipSuccess) return e; last_side = pnl; }
         } else {
             if (pending >= 0) { if ((e = hipStreamWaitEvent(st, la->ev_rest[pending], 0)) != hipSuccess) return e; pending = -1; }
             if ((e = trailing_update_columns(M, ld, nb, st, bt, J0, J1, J1, nb)) != hipSuccess) return e;
         }
     }
     if (pending >= 0 && (e = hipStreamWaitEvent(st, la->ev_rest[pending], 0)) != hipSuccess) return e;
-    return potrf_superblock_inverses(plan, st, bt);
+    if (last_side < 0) return potrf_superblock_inverses(plan, st, bt);
+    // one join behind the last thing the side stream got, then what is left of every stage (its tail: panels ascend inside a
+    // stage), in the order of the serial schedule
+    if ((e = hipEventRecord(la->ev_join, la->side)) != hipSuccess) return e;
+    if ((e = hipStreamWaitEvent(st, la->ev_join, 0)) != hipSuccess) return e;
+    for (size_t i = 0; i < plan.stages.size(); ++i) {
+        const int left = plan.stages[i].second - (int)issued[i];
+        if (left <= 0) continue;
+        e = launch_gemm_grouped(plan.descs_dev + plan.stages[i].first + issued[i], left, st, bt, plan.merge_edge);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace lpipm

@@ -84,6 +84,16 @@ hipError_t factor_plan_create(FactorPlan& plan, const double* L, int64_t ld, int
 
     std::vector<GemmTileDesc> descs;
     plan.stages.clear();
+    plan.groups.clear();
+    // a stage's descriptors stay in merge order -- super-block by super-block, left to right, so the chain step after which
+    // a merge's inputs are final (block hi - 1 of its super-block) never decreases along a stage -- and the stage is cut
+    // where the outer panel of that step changes
+    auto count_in_group = [&](const Merge& m) {
+        const int panel = (plan.sbs[m.sb].row0 / NB + m.hi - 1) / POTRF_OUTER, stage = (int)plan.stages.size();
+        if (plan.groups.empty() || plan.groups.back().stage != stage || plan.groups.back().panel != panel)
+            plan.groups.push_back(MergeGroup{(int)descs.size(), 0, stage, panel});
+        return &plan.groups.back();
+    };
     const int KPB = NB / BK;   // k-tiles per 128-block
     for (int lvl = 1; lvl <= maxlvl; ++lvl) {
         // stage A: T^T (s1 x s2) = Inv11^T . L21^T ; Inv11^T is upper triangular: k >= row tile
@@ -92,6 +102,8 @@ hipError_t factor_plan_create(FactorPlan& plan, const double* L, int64_t ld, int
             if (m.level != lvl) continue;
             const SuperBlock& s = plan.sbs[m.sb];
             const int n1 = m.mid - m.lo, n2 = m.hi - m.mid;
+            MergeGroup* grp = count_in_group(m);
+            grp->count += (n1 * SUB) * (n2 * SUB);
             for (int tj = 0; tj < n1 * SUB; ++tj)           // sub-tile indices: rows of T^T, columns of T^T
                 for (int ti = 0; ti < n2 * SUB; ++ti) {
                     GemmTileDesc d{};
@@ -116,6 +128,8 @@ hipError_t factor_plan_create(FactorPlan& plan, const double* L, int64_t ld, int
             const SuperBlock& s = plan.sbs[m.sb];
             const int n1 = m.mid - m.lo, n2 = m.hi - m.mid;
             double* TT = tws + m.toff;
+            MergeGroup* grp = count_in_group(m);
+            grp->count += 2 * (n1 * SUB) * (n2 * SUB);
             for (int ti = 0; ti < n2 * SUB; ++ti)
                 for (int tj = 0; tj < n1 * SUB; ++tj) {
                     GemmTileDesc d{};   // Inv21(ti,tj) = -sum_k Inv22[ti][k] T^T[tj][k]
@@ -156,6 +170,7 @@ void factor_plan_destroy(FactorPlan& plan) {
     if (plan.descs_dev) (void)hipFree(plan.descs_dev);   // the inverse storage belongs to the arena
     plan.sbs.clear();
     plan.stages.clear();
+    plan.groups.clear();
     plan.descs_dev = nullptr;
     plan.tpart = nullptr;
     plan.mp = 0;
@@ -188,12 +203,13 @@ __global__ __launch_bounds__(256) void trsv_fold_kernel(double* __restrict__ y, 
 }
 
 hipError_t launch_chol_solve(const double* L, int64_t ld, const FactorPlan& plan, int nrhs, double* R,
-                             double* Y, hipStream_t st, const Batch& bt) {
+                             double* Y, hipStream_t st, const Batch& bt, const SolveSteps& steps) {
     const int mp = plan.mp;
     hipError_t e;
     const int nsb = (int)plan.sbs.size();
+    const int k1 = steps.fwd_end < 0 || steps.fwd_end > nsb ? nsb : steps.fwd_end;
     // forward: L y = r
-    for (int k = 0; k < nsb; ++k) {
+    for (int k = steps.fwd_begin; k < k1; ++k) {
         const SuperBlock& s = plan.sbs[k];
         e = launch_gemv_n(s.inv, s.size, s.size, s.size, nrhs, R + s.row0, mp, nullptr, nullptr, Y + s.row0, mp, st, 1.0, bt);
         if (e != hipSuccess) return e;
@@ -205,6 +221,7 @@ hipError_t launch_chol_solve(const double* L, int64_t ld, const FactorPlan& plan
             if (e != hipSuccess) return e;
         }
     }
+    if (!steps.backward) return hipSuccess;
     // backward: L^T v = y   (solution written over R)
     for (int k = nsb - 1; k >= 0; --k) {
         const SuperBlock& s = plan.sbs[k];

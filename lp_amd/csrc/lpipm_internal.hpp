@@ -187,6 +187,9 @@ struct SuperBlock {
     double* inv;             // size x size row-major: inv(L_ss)   (lower triangular, zeros above)
     double* invT;            // size x size row-major: inv(L_ss)^T (upper triangular, zeros below)
 };
+// A stage's descriptors whose inputs become final with one outer panel of the factorisation: the 128-block inverses the
+// merge of blocks [lo, hi) reads and L[mid..hi, lo..mid] are final once chain step hi - 1 has run.
+struct MergeGroup { int first, count, stage, panel; };
 struct FactorPlan {
     int mp = 0;
     int merge_edge = 128;    // output tile edge of the merge GEMMs (32 / 64: latency-bound, 128: flop-bound)
@@ -196,6 +199,7 @@ struct FactorPlan {
     std::vector<SuperBlock> sbs;
     GemmTileDesc* descs_dev = nullptr;           // grouped-GEMM tiles of all merge stages (own allocation, shared by a batch)
     std::vector<std::pair<int, int>> stages;     // (first descriptor, count) per launch, in order
+    std::vector<MergeGroup> groups;              // the stages cut by outer panel (stage by stage, panels ascending inside one)
     double* tpart = nullptr;                     // gemv_t slabs of the backward sweep
     // 128-block k of the factorisation -> where its inverse / transposed inverse go, and their ld
     double* blk_inv(int k) const;
@@ -218,17 +222,33 @@ void factor_plan_destroy(FactorPlan& plan);
 struct PotrfLookahead {
     hipStream_t side = nullptr;
     std::vector<hipEvent_t> ev_chain, ev_rest;
+    hipEvent_t ev_join = nullptr;   // behind the last thing the side stream was given
     int min_nb = 32;         // 128-blocks from which the look-ahead is used (default: m >= 4096; LPIPM_LOOKAHEAD=1: 12)
 };
+// With the look-ahead on, the side stream idles for most of every outer panel's chain.  Behind each rest-update it also gets
+// the merges of the super-block inverses whose inputs that panel completed (FactorPlan::groups), and what the caller
+// attaches here: work that needs nothing but finished panels.  `at` enqueues on `side` and is called once with sb = -1 behind
+// the first rest-update, then with sb = k as soon as the inverse of super-block k is enqueued there (k ascending; block
+// columns of L up to the end of that super-block are final).  Never called when the look-ahead does not apply;
+// `calls` counts the calls made.
+struct PotrfBeside {
+    hipError_t (*at)(void* self, int sb, hipStream_t side) = nullptr;
+    void* self = nullptr;
+    int calls = 0;
+};
 hipError_t launch_potrf(double* M, int64_t ld, int mp, const FactorPlan& plan, int32_t* info, hipStream_t st,
-                        const Batch& bt = Batch{}, const PotrfLookahead* la = nullptr, bool clear_info = true);
+                        const Batch& bt = Batch{}, const PotrfLookahead* la = nullptr, bool clear_info = true,
+                        PotrfBeside* beside = nullptr);
 
 constexpr int POTRF_OUTER = 4;   // 128-blocks per outer panel (also the width of the column groups of A.D.A^T, solver.hip)
 
 // ---------------------------------------------------------------- triangular solves (kernels_trsv.hip)
 // R[r] <- L^-T L^-1 R[r], r < nrhs (1|2); R is nrhs x mp (row stride mp); Yscratch: nrhs x mp.
+// steps: the forward steps [fwd_begin, fwd_end) (fwd_end < 0: to the last one; the steps before fwd_begin have been run by
+// an earlier call on the same R and Yscratch), then the backward sweep unless `backward` is false.
+struct SolveSteps { int fwd_begin = 0, fwd_end = -1; bool backward = true; };
 hipError_t launch_chol_solve(const double* L, int64_t ld, const FactorPlan& plan, int nrhs, double* R,
-                             double* Yscratch, hipStream_t st, const Batch& bt = Batch{});
+                             double* Yscratch, hipStream_t st, const Batch& bt = Batch{}, const SolveSteps& steps = SolveSteps{});
 
 // ---------------------------------------------------------------- QR arms (kernels_qr.hip)
 // EquationSolverType::{Inverse, LeastSquares}: Householder QR of the full mp x mp matrix whose LOWER

@@ -375,8 +375,10 @@ extern "C" int lpipm_create(int device, lpipm_ctx** out) {
                 e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
                 if (e == hipSuccess) (i < NEV ? c->la.ev_chain : c->la.ev_rest).push_back(ev);
             }
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&c->la.ev_join, hipEventDisableTiming);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
+                if (c->la.ev_join) { (void)hipEventDestroy(c->la.ev_join); c->la.ev_join = nullptr; }
                 for (hipEvent_t ev : c->la.ev_chain) (void)hipEventDestroy(ev);
                 for (hipEvent_t ev : c->la.ev_rest) (void)hipEventDestroy(ev);
                 c->la.ev_chain.clear(); c->la.ev_rest.clear();
@@ -409,6 +411,7 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     if (c->la.side) { (void)hipStreamSynchronize(c->la.side); (void)hipStreamDestroy(c->la.side); }
     for (hipEvent_t e : c->la.ev_chain) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->la.ev_rest) (void)hipEventDestroy(e);
+    if (c->la.ev_join) (void)hipEventDestroy(c->la.ev_join);
     stream_res_destroy(c->rs);
     delete c;
 }
@@ -764,11 +767,12 @@ extern "C" int lpipm_upload_ub_eq(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const
 // Y = add + A.W and Upart = row-split slabs of A^T.V on the stored structural columns, plus the
 // identity block of the slack columns
 static hipError_t ctx_gemv_n(lpipm_ctx* c, int nrhs, const double* W, const double* add0, const double* add1, double* Y,
-                             const Batch& bt) {
+                             const Batch& bt, hipStream_t on = nullptr) {
+    hipStream_t st = on ? on : c->rs.st;
     ++c->gemv_passes;
-    hipError_t e = launch_gemv_n(c->p.A, c->p.npa, (int)c->p.m, c->p.npa, nrhs, W, c->p.np, add0, add1, Y, c->p.mp, c->rs.st, 1.0, bt, c->p.shared_a);
+    hipError_t e = launch_gemv_n(c->p.A, c->p.npa, (int)c->p.m, c->p.npa, nrhs, W, c->p.np, add0, add1, Y, c->p.mp, st, 1.0, bt, c->p.shared_a);
     if (e != hipSuccess || c->p.shared_a) return e;      // (no slack launch behind a shared A)
-    return launch_slack_n(c->p.ns, c->p.nx, nrhs, W, c->p.np, Y, c->p.mp, c->rs.st, bt);
+    return launch_slack_n(c->p.ns, c->p.nx, nrhs, W, c->p.np, Y, c->p.mp, st, bt);
 }
 static hipError_t ctx_gemv_t(lpipm_ctx* c, int nrhs, const double* V, const Batch& bt) {
     ++c->gemv_passes;
@@ -982,6 +986,22 @@ static int enqueue_head(lpipm_ctx* c) {
 // The look-ahead of launch_potrf, if the side stream it needs was created (lpipm_create).
 static const PotrfLookahead* lookahead(lpipm_ctx* c) { return c->la.side ? &c->la : nullptr; }
 
+// What the predictor does beside the factorisation's chain, on the look-ahead's side stream (PotrfBeside): its pass A.W needs
+// W of k_pred_setup only, and forward step k of its solve needs that right-hand side, the inverse of super-block k and block
+// columns of L that are final by then.  R, Y and tpart belong to the solves alone; nothing of the factorisation touches them.
+struct PredictorBeside {
+    lpipm_ctx* c;
+    int fwd_done = 0;            // forward steps [0, fwd_done) of the predictor's solve are enqueued
+    static hipError_t at(void* self, int sb, hipStream_t side) {
+        PredictorBeside* b = (PredictorBeside*)self;
+        lpipm_ctx* c = b->c;
+        VecArgs& v = c->p.va;
+        if (sb < 0) return ctx_gemv_n(c, 2, v.W, v.b, v.rP, v.R, c->p.bt, side);     // :220
+        b->fwd_done = sb + 1;
+        return launch_chol_solve(c->p.M, c->p.mp, *c->p.factor, 2, v.R, c->p.Y, side, c->p.bt, SolveSteps{sb, sb + 1, false});
+    }
+};
+
 // The rest of the iteration, ending with the status record on its way to the host and ev_status behind it.
 static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
     VecArgs& v = c->p.va;
@@ -991,11 +1011,18 @@ static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
     const Batch& bt = c->p.bt;
     const bool chol = o->solver_type == LPIPM_SOLVER_CHOLESKY;
     // (no clearing of the pivot-failure word: k_blind_start and every k_scalar_indicators leave it zero)
-    if (chol) LP_HIP(launch_potrf(c->p.M, c->p.mp, c->p.mp, *c->p.factor, v.potrf_info, st, bt, lookahead(c), false));   // :129-131
+    // a single LP whose factorisation runs with the look-ahead: the predictor's pass and the first forward steps of its
+    // solve go beside the chain (launch_potrf decides whether the look-ahead applies; the serial order otherwise)
+    PredictorBeside pb{c};
+    PotrfBeside beside{PredictorBeside::at, &pb};
+    const bool may_beside = chol && !c->colsplit && bt.count == 1 && c->refine <= 0;
+    if (chol) LP_HIP(launch_potrf(c->p.M, c->p.mp, c->p.mp, *c->p.factor, v.potrf_info, st, bt, lookahead(c), false,
+                                  may_beside ? &beside : nullptr));   // :129-131
     else      LP_HIP(launch_qr_factor(c->p.M, c->p.mp, c->p.mp, c->p.tau, v.potrf_info, st));        // :133-149
     prof_mark(c, T_POTRF);
     // predictor: both sym_solve calls of solve_newton_equations (:187-188) in one pass each
-    if (!c->colsplit) {
+    if (beside.calls > 0) {}                                // the pass ran beside the factorisation
+    else if (!c->colsplit) {
         LP_HIP(ctx_gemv_n(c, 2, v.W, v.b, v.rP, v.R, bt));  // :220
     } else {   // the addend r2 enters once, after the cross-rank sum of the column-split products
         LP_HIP(ctx_gemv_n(c, 2, v.W, nullptr, nullptr, v.R, bt));
@@ -1003,7 +1030,8 @@ static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
         vec_add_rows((int)c->p.m, 2, v.R, c->p.mp, v.b, v.rP, st);
     }
     prof_mark(c, T_GEMV);
-    if (chol) LP_TRY(chol_solve_refined(c, 2, v.R, bt));                                    // :221, :154
+    if (beside.calls > 0) LP_HIP(launch_chol_solve(c->p.M, c->p.mp, *c->p.factor, 2, v.R, c->p.Y, st, bt, SolveSteps{pb.fwd_done, -1, true}));
+    else if (chol) LP_TRY(chol_solve_refined(c, 2, v.R, bt));                               // :221, :154
     else      LP_HIP(launch_qr_solve(c->p.M, c->p.mp, c->p.mp, c->p.tau, 2, v.R, v.potrf_info, st));   // :155-166
     prof_mark(c, T_TRSV);
     LP_HIP(ctx_gemv_t(c, 2, v.R, bt));              // :223
