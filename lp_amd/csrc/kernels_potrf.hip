@@ -648,13 +648,12 @@ static hipError_t potrf_panel_chain(double* M, int64_t ld, int mp, const FactorP
         if (rem <= 0) break;
         double* panel = M + (o + NB) * ld + o;   // rows below block j, column block j
         GemmArgs t{};
-        t.P = panel; t.ldp = ld; t.Q = linv; t.ldq = ldinv; t.s = nullptr;
+        t.P = panel; t.ldp = ld; t.Q = linv; t.ldq = ldinv;
         t.C = panel; t.ldc = ld; t.K = NB; t.alpha = 1.0; t.beta = 0.0;
         // few tiles -> latency-bound: 32-row x 128-col tiles put 4x as many CUs on the panel, and a
         // workgroup still owns whole rows, so the product may overwrite its own input
         t.tile_shape = TileShape::T32x128;
-        t.ntiles = 4 * rem; t.tiles_lower = 0; t.ntj = 1; t.tile_list = nullptr;
-        t.diag_pad_from = -1; t.ws = nullptr; t.nwg = t.ntiles; t.batch = bt;
+        t.ntiles = 4 * rem; t.tiles_lower = 0; t.ntj = 1; t.batch = bt;
         e = launch_gemm_nt(t, st);
         if (e != hipSuccess) return e;
         const int ncols = J1 - j - 1;            // column blocks of the outer panel right of j
@@ -662,12 +661,12 @@ static hipError_t potrf_panel_chain(double* M, int64_t ld, int mp, const FactorP
             // rows j+1..nb x columns j+1..J1-1 -= L[rows, j] . L[cols, j]^T  (rectangular grid of tiles; the few tiles
             // above the diagonal are computed too and never read)
             GemmArgs c{};
-            c.P = panel; c.ldp = ld; c.Q = panel; c.ldq = ld; c.s = nullptr;
+            c.P = panel; c.ldp = ld; c.Q = panel; c.ldq = ld;
             c.C = M + (o + NB) * ld + (o + NB); c.ldc = ld; c.K = NB; c.alpha = -1.0; c.beta = 1.0;
             // 32x32 tiles: 16x as many workgroups as 128x128 ones, 32 MFMAs per wave; the launch is one round of tiles on the
             // chain (factorisation at m = 4096: 1998 us with 64x64 tiles, 1942 with 32x64, 1903 with 32x32)
             c.tile_shape = TileShape::T32x32; c.tiles_lower = 0; c.ntj = 4 * ncols; c.ntiles = (4 * rem) * (4 * ncols);
-            c.tile_list = nullptr; c.diag_pad_from = -1; c.ws = nullptr; c.nwg = c.ntiles; c.batch = bt;
+            c.batch = bt;
             e = launch_gemm_nt(c, st);
             if (e != hipSuccess) return e;
         }
@@ -685,8 +684,7 @@ static hipError_t trailing_update_columns(double* M, int64_t ld, int nb, hipStre
     const int64_t oJ0 = (int64_t)J0 * NB, oC0 = (int64_t)C0 * NB;
     const int remT = nb - C0;                    // block rows from C0 down
     GemmArgs u{};
-    u.s = nullptr; u.ldp = ld; u.ldq = ld; u.ldc = ld; u.K = (J1 - J0) * NB; u.alpha = -1.0; u.beta = 1.0;
-    u.tile_list = nullptr; u.diag_pad_from = -1; u.ws = nullptr; u.batch = bt;
+    u.ldp = ld; u.ldq = ld; u.ldc = ld; u.K = (J1 - J0) * NB; u.alpha = -1.0; u.beta = 1.0; u.batch = bt;
     u.P = M + oC0 * ld + oJ0; u.Q = u.P; u.C = M + oC0 * ld + oC0;
     if (C1 < nb) {
         // a band of columns: rectangular grid of 32x32 tiles, rows C0..nb x columns C0..C1 (the few tiles above the diagonal
@@ -701,7 +699,6 @@ static hipError_t trailing_update_columns(double* M, int64_t ld, int nb, hipStre
         else if (remT * (remT + 1) / 2 < 1024) { u.tile_shape = TileShape::T64x64; u.ntiles = (2 * remT) * (2 * remT + 1) / 2; }
         else                                   { u.tile_shape = TileShape::T128x128; u.ntiles = remT * (remT + 1) / 2; }
     }
-    u.nwg = u.ntiles;
     return launch_gemm_nt(u, st);
 }
 

@@ -90,77 +90,92 @@ struct Arena {
 };
 
 // ---------------------------------------------------------------- NT GEMM (kernels_gemm.hip)
-// C(tile ti,tj) = beta*C + alpha * sum_k P[ti*128+r][k] * s[k] * Q[tj*128+c][k]
-// Row-major operands with K contiguous ("NT"): this one MFMA kernel serves
-//   A.D.A^T            (P = Q = A, s = x/z, lower tiles, stream-K over n)   newton_equations.rs:55-57
+// C(tile ti,tj) = beta*C + alpha * sum_k P[ti*TM+r][k] * Q[tj*TN+c][k], one whole output tile per workgroup.
+// Row-major operands with K contiguous ("NT"): the launches of the factorisation
 //   trailing update    (P = Q = L21, alpha=-1, beta=1, lower tiles)         Cholesky, :129-131
 //   TRSM as GEMM       (P = A21, Q = inv(L11), rectangular tiles)
-// output tile of a whole-tile launch (rows x columns); tile indices count in these units
+// output tile of a launch (rows x columns); tile indices count in these units
 enum class TileShape { T128x128, T64x64, T32x128, T32x32 };
 struct GemmArgs {
     const double* P; int64_t ldp;
     const double* Q; int64_t ldq;
-    const double* s;            // nullable: per-k scale applied to the Q panel while staging
     double*       C; int64_t ldc;
     int           K;            // multiple of BK
     double        alpha, beta;
-    int           ntiles;
+    int           ntiles;       // == workgroups per LP
     int           tiles_lower;  // 1: tile index -> lower triangle (row-major), 0: rectangular
     int           ntj;          // rectangular: number of tile columns
-    const int2*   tile_list;    // nullable: explicit (ti,tj) order (device pointer)
-    int           diag_pad_from;// rows/cols >= this on the diagonal are written as 1.0 (-1: off)
-    int           streamk;      // 1: the A.D.A^T kernel (data-parallel tiles + claimed stream-K chunks, canonical chunked
-                                //    summation; alpha = 1, beta = 0); 0: whole-tile kernels, nwg == ntiles
-    double*       ws;           // stream-K chunk slabs: gemm_streamk_slabs() tiles of TILE*TILE doubles
-    int           nwg;          // workgroups launched per LP
-    unsigned int* sk_claim;     // stream-K: the device word through which the chunks of the remainder tiles are claimed
-                                //   (workgroups that finish their data-parallel tiles early take more of them); slabs are
-                                //   indexed by chunk, so the sums do not depend on who computed what
-    double*       C2;           // stream-K launches whose tiles are all split (ntiles < nwg): final values stored here too
-    TileShape     tile_shape;   // whole-tile launches (a value-initialised GemmArgs has 128x128)
-    Batch         batch;        // lockstep batch (every pointer above except tile_list is per LP)
-    bool          shared_a = false;   // P and Q are ONE matrix the whole batch shares (member stride 0; lpipm_upload_lockstep_shared)
+    TileShape     tile_shape;   // (a value-initialised GemmArgs has 128x128)
+    Batch         batch;        // lockstep batch (every pointer above is per LP)
 };
-// Launches the main kernel and, when tiles are split into stream-K chunks, the deterministic fix-up pass.
 hipError_t launch_gemm_nt(const GemmArgs& a, hipStream_t st);
-// stream-K geometry: canonical chunk (k-tiles) for a contraction of KT k-tiles, workgroup count for ntiles x KT
-// work on num_cu CUs, and the number of TILE x TILE slabs ws must hold for a given workgroup count
-int gemm_streamk_chunk(int KT);
-size_t gemm_streamk_slabs(int ntiles, int KT, int nwg);
-bool gemm_streamk_split(int KT);     // contraction long enough to be cut into chunks (only then can GemmArgs::C2 be used)
-int gemm_streamk_nwg(int ntiles, int KT, int num_cu);
-// ---- A.D.A^T as (tile, chunk) UNITS with an in-launch combine (kernels_gemm.hip, gemm_nt_units_kernel) --------------
-// The contraction of every lower tile is cut into the canonical chunks (gemm_streamk_chunk); a workgroup computes `upc`
-// consecutive chunks of ONE tile, writes each chunk sum to that chunk's slab (write-through stores: nothing to wait for),
-// and adds the number of chunks it did to the tile's arrival counter.  The workgroup whose add completes the tile adds the
-// tile's slabs IN CHUNK ORDER and stores the tile -- the same sums in the same order as a single running pass that flushes
-// at every chunk boundary, whatever the decomposition (no separate fix-up launch; the bits of M do not depend on the
-// workgroup count, on `upc`, or on who arrives last).  A non-persistent grid, one unit per workgroup, dispatched in list
-// order: with a column-group-major list the groups of M complete one after the other WHILE the launch runs, and the
-// workgroup that completes a group's last tile bumps that group's word -- what the column-split reduction of M waits for
-// (solver.hip, enqueue_head).
-struct AdatUnitsArgs {
-    const double* A; int64_t lda;     // P = Q = A
-    const double* s;                  // dinv (per-k scale)
-    double* C; int64_t ldc;           // M
-    double* C2;                       // nullable second copy
-    int K;                            // columns (multiple of BK)
-    int ntiles;
-    const int2* tile_list;            // (ti, tj) per tile, device
-    const int2* unit_list;            // (tile index, first chunk) per unit in dispatch order, device; tile < 0: padding (no-op)
-    int nunits, upc;
-    int diag_pad_from;
-    double* slabs;                    // ntiles * cpt slabs of TILE*TILE doubles
-    unsigned int* tile_cnt;           // ntiles arrival counters, ZEROED before the launch (by the caller, in stream order)
-    unsigned int* grp_cnt;            // nullable: completed tiles per column group (tj / grp_w), zeroed likewise
-    int grp_w;
-    Batch batch;
-    bool shared_a = false;            // A is ONE matrix the whole batch shares (member stride 0; lpipm_upload_lockstep_shared)
+
+// ---------------------------------------------------------------- A.D.A^T (kernels_adat.hip)
+// M = A . diag(dinv) . A^T, lower 128x128 tiles (newton_equations.rs:54-57).  The module owns everything from the geometry
+// to the written M: how a launch is cut up and which of its two kernels runs it (the plan), the device words and slabs the
+// kernels need (AdatRes: a part of every LP's arena, and the tile / unit lists), and the launch.
+// The plan: a function of mp, npa, the batch count, the CU count, the number of ranks of a column split (world; it matters
+// for a single LP only) and the value of LPIPM_ADAT_UNITS -- and of nothing else.  Needs no device.
+struct AdatPlan {
+    int ntiles = 0;
+    bool units = false;                  // the (tile, chunk) units kernel with its in-launch combine; else the round-2 kernel
+                                         //   (data-parallel tiles + claimed stream-K chunks + fix-up launch)
+    int cpt = 1, upc = 1;                // canonical chunks per tile, chunks per unit
+    int nwg = 1;                         // round-2 kernel: workgroups per LP
+    size_t slabs = 0;                    // chunk slabs (TILE x TILE doubles each) per LP, whichever kernel
+    bool grouped = false;                // one LP split by columns over ranks: a second, column-group-major order whose launch
+                                         //   signals M's column groups (POTRF_OUTER tile columns each) one by one
 };
-int adat_units_cpt(int K);            // chunks per tile for a contraction of K columns
-constexpr int ADAT_UNITS_MAX_CPT = 256;   // most chunks per tile the units kernel takes (a tile's slabs are one 32-bit buffer)
-int adat_units_chunking(int K, int* kc, int* nbig, int* ks);   // ... and their boundaries (kernels_gemm.hip)
-hipError_t launch_adat_units(const AdatUnitsArgs& a, hipStream_t st);
+AdatPlan plan_adat(int mp, int npa, int count, int num_cu, int world, int units_env);
+// What the launches of one resident problem use on the device.  A plain copy shares it and owns nothing (a half-batch view).
+struct AdatRes {
+    // per LP, in the arena (adat_take)
+    unsigned int* claim = nullptr;       // round-2 kernel: the word through which the stream-K chunks are claimed
+    unsigned int* counters = nullptr;    // units kernel: arrival words of the tiles, then the group words: one clearable block
+    size_t counter_bytes = 0;
+    unsigned int* group_words = nullptr;
+    unsigned int* wait_timeout = nullptr;   // set by a wait kernel that gave up (a producer that never ran)
+    double* slabs = nullptr;
+    bool counters_dirty = true;          // the counters may be non-zero: the next plain units launch clears them first (a plain
+                                         //   launch leaves them zero itself; launches that signal groups do not)
+    // shared by the LPs of a batch: ONE allocation (adat_lists_create), tile orders and unit lists
+    int2* tiles = nullptr;               // XCD-aware order, then the same tiles column-group-major (plan.grouped)
+    int2* tiles_grouped = nullptr;
+    int2* units = nullptr;               // (tile, first chunk) in dispatch order, per order
+    int2* units_grouped = nullptr;
+    int nunits = 0, nunits_grouped = 0;
+    size_t list_bytes = 0;
+    std::vector<int> group_first, group_ntiles;   // tile sub-list of every column group
+    int ngroups() const { return (int)group_ntiles.size(); }
+};
+// Takes the claim word, the counter block, the time-out word and the slabs of one LP from its arena.
+void adat_take(AdatRes& r, const AdatPlan& plan, Arena& arena);
+// Builds and uploads the lists (synchronises st); destroy frees them.  Counters start dirty.
+hipError_t adat_lists_create(AdatRes& r, const AdatPlan& plan, int mp, int count, hipStream_t st);
+void adat_lists_destroy(AdatRes& r);
+// Column group g of a grouped plan, for the consumer of a signalling launch: its tiles (device sub-list, and where they
+// start in the grouped order) and the word that reaches `ntiles` when all of them are stored.
+struct AdatGroup { const int2* tiles; int first, ntiles; const unsigned int* word; };
+inline AdatGroup adat_group(const AdatRes& r, int g) {
+    return AdatGroup{r.tiles_grouped + r.group_first[(size_t)g], r.group_first[(size_t)g], r.group_ntiles[(size_t)g], r.group_words + g};
+}
+struct AdatLaunch {
+    const double* A; int64_t lda;        // mp x K, row-major
+    const double* dinv;                  // per-column scale
+    double* M; int64_t ldm;
+    double* M2;                          // nullable second copy of M (same ld)
+    int K;                               // columns (multiple of BK)
+    int diag_pad_from;                   // rows/cols >= this on the diagonal are written as 1.0
+    Batch batch;
+    bool shared_a = false;               // A is ONE matrix the whole batch shares (member stride 0; lpipm_upload_lockstep_shared)
+};
+// Picks the kernel and the unit list, clears the counters when they may be non-zero, launches.  signal_groups (grouped plans):
+// column-group-major order, one chunk per unit, and the workgroup that completes a group's last tile bumps the group's word;
+// `armed` (nullable) is recorded between the clear and the launch: what a consumer on another stream waits for before it
+// polls the words.  *second_copy: whether M2 was written by the launch (only a contraction of several chunks can; never
+// when groups are signalled) -- if not, the caller copies.
+hipError_t launch_adat(const AdatPlan& plan, AdatRes& r, const AdatLaunch& a, bool signal_groups, hipStream_t st,
+                       bool* second_copy, hipEvent_t armed = nullptr);
 // One wave that returns when *cnt >= target (or when *done != 0, or after a bounded number of polls, which sets *timeout):
 // the device-side wait of a stream for a group word of a running launch on another stream.
 hipError_t launch_wait_count(const unsigned int* cnt, unsigned int target, const int* done, unsigned int* timeout, hipStream_t st);
@@ -240,7 +255,7 @@ hipError_t launch_potrf(double* M, int64_t ld, int mp, const FactorPlan& plan, i
                         const Batch& bt = Batch{}, const PotrfLookahead* la = nullptr, bool clear_info = true,
                         PotrfBeside* beside = nullptr);
 
-constexpr int POTRF_OUTER = 4;   // 128-blocks per outer panel (also the width of the column groups of A.D.A^T, solver.hip)
+constexpr int POTRF_OUTER = 4;   // 128-blocks per outer panel (also the width of the column groups of A.D.A^T, kernels_adat.hip)
 
 // ---------------------------------------------------------------- triangular solves (kernels_trsv.hip)
 // R[r] <- L^-T L^-1 R[r], r < nrhs (1|2); R is nrhs x mp (row stride mp); Yscratch: nrhs x mp.
@@ -260,7 +275,7 @@ hipError_t launch_qr_solve(const double* M, int64_t ld, int mp, const double* ta
                            int32_t* info, hipStream_t st);
 
 // ---------------------------------------------------------------- GEMV (kernels_gemv.hip)
-// The three passes over A.  shared_a (as in GemmArgs, AdatUnitsArgs): A is ONE matrix that every member of the batch shares
+// The three passes over A.  shared_a (as in AdatLaunch): A is ONE matrix that every member of the batch shares
 // (lpipm_upload_lockstep_shared) and is not offset by the member (the other operands are); each A element a wave loads
 // serves a GROUP of members before the next one is read (gridDim.z = groups), so a pass reads A ceil(count / group) times
 // instead of count times.  Every output is summed the same way whatever the group (same lane striding and butterfly, same

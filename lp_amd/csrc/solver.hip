@@ -44,14 +44,6 @@ const char* lp_knob(const char* name) {
 enum { T_VEC = 0, T_ADAT, T_POTRF, T_TRSV, T_GEMV, T_NTAGS };
 
 namespace {   // the parts of a context: local to this file
-// How the A.D.A^T launch of a geometry is cut up (plan_adat).
-struct AdatPlan {
-    int ntiles = 0, adat_nwg = 1;
-    size_t ws_slabs = 0;                 // stream-K slabs (TILE x TILE doubles each) the A.D.A^T launches may need
-    bool units = false;                  // this problem runs the units kernel (geometry: the slabs fit the budget)
-    int cpt = 1, upc = 1;                // chunks per tile, chunks per unit
-};
-
 // What one stream of solver work owns on the host: a context has one, and so has each of its half-batch views.  Made by
 // stream_res_create, released by stream_res_destroy; nobody else creates or frees a member.
 struct StreamRes {
@@ -63,7 +55,7 @@ struct StreamRes {
     size_t nmarks = 0;
     StatusRec* status_host = nullptr;  // pinned, status_cap records
     size_t status_cap = 0;
-    unsigned int* timeout_host = nullptr;   // pinned mirror of Problem::wait_timeout, read with the status record
+    unsigned int* timeout_host = nullptr;   // pinned mirror of AdatRes::wait_timeout, read with the status record
     double* x_pinned = nullptr;        // pinned bounce buffer of the solution (a D2H copy into the caller's pageable array takes
     size_t x_pinned_cap = 0;           //   the runtime's staged path: ~40 us more per solve than pinned + memcpy)
     uint32_t seq_counter = 0;          // sequence numbers of the status records (VecArgs::status_seq)
@@ -71,8 +63,9 @@ struct StreamRes {
 };
 
 // The resident problem: geometry, device pointers and launch arguments.  Every pointer points into an allocation of the
-// context that uploaded it (arena, a_shared, tile_list; the factor plan), so a plain copy of this struct shares the device
-// state and owns nothing: that is what a half-batch view holds (make_view).
+// context that uploaded it (arena, a_shared, the factor plan; the tile and unit lists belong to `adat`, made by
+// adat_lists_create and freed by adat_lists_destroy), so a plain copy of this struct shares the device state and owns
+// nothing: that is what a half-batch view holds (make_view).
 struct Problem {
     bool has_problem = false;
     uint64_t m = 0, n = 0;
@@ -87,26 +80,14 @@ struct Problem {
     bool shared_a = false;
     double* a_shared = nullptr;
     size_t a_shared_bytes = 0;
-    size_t list_bytes = 0;               // tile / unit lists (own allocation)
     Batch bt;                    // what the solve path hands to every launcher (count, stride, done flags)
     Batch bt_head;               // same with the done test always on: the speculatively enqueued head of an iteration
     const FactorPlan* factor = nullptr;  // lpipm_ctx::plan of the uploading context
     double* tau = nullptr;               // Householder scalars of the QR arms
-    double *A = nullptr, *M = nullptr, *ws = nullptr, *Y = nullptr, *ATpart = nullptr, *xout = nullptr;
+    double *A = nullptr, *M = nullptr, *Y = nullptr, *ATpart = nullptr, *xout = nullptr;
     double *M0 = nullptr, *R0 = nullptr, *Rho = nullptr, *symv_ws = nullptr;   // refinement of the Cholesky solve
-    // A.D.A^T as (tile, chunk) units with an in-launch combine (launch_adat_units; kernels_gemm.hip)
-    bool grouped_reduce = false;         // column split over ranks: M is reduced group by group behind the running launch
-    int nunits = 0, nunits_grp = 0;
-    int2* unit_list = nullptr;           // (tile, first chunk) in dispatch order: chunk-major over the XCD-aware tile order
-    int2* unit_list_grp = nullptr;       // column-group-major (tile indices into tile_list_grp): groups complete one after the other
-    unsigned int* tile_cnt = nullptr;    // arena: arrival counters of the tiles, then the group words (one memset clears both)
-    unsigned int* grp_cnt = nullptr;
-    size_t cnt_bytes = 0;
-    unsigned int* wait_timeout = nullptr;   // arena: set by a wait kernel that gave up (a producer that never ran)
-    std::vector<int> grp_off, grp_nt;    // tile sub-list of every column group (outer panel of the factorisation)
-    int2* tile_list = nullptr;
-    int2* tile_list_grp = nullptr;      // the same tiles grouped by column group (behind tile_list in one allocation)
-    unsigned int* sk_claim = nullptr;   // claim word of the dynamic stream-K chunks of A.D.A^T
+    AdatRes adat;                // what the A.D.A^T launches use on the device (kernels_adat.hip); adat.ngroups() > 0: one LP split by
+                                 //   columns over ranks, M is reduced column group by column group behind the running launch
     double* gs = nullptr;        // 8 doubles: sums / minima that must be reduced across ranks (n-split mode)
     VecArgs va{};
 };
@@ -121,9 +102,7 @@ struct lpipm_ctx {
     std::vector<void*> kallocs;  // buffers of the stand-alone kernel entry points
     FactorPlan plan, kplan;
     double* ktau = nullptr;
-    int units_env = 1;                   // LPIPM_ADAT_UNITS=0: the round-2 kernel (data-parallel tiles + stream-K + fix-up launch)
-    bool cnt_dirty = true;               // the arrival words may be non-zero: the next plain units launch clears them first (a plain
-                                         // launch leaves them zero itself; launches with group words do not)
+    int units_env = 1;                   // LPIPM_ADAT_UNITS=0: the round-2 kernel (data-parallel tiles + fix-up launch) everywhere
     PotrfLookahead la;                   // trailing updates of one factorisation beside the next panel's chain (launch_potrf)
     // a lockstep batch as two half-batches driven by two host threads on two streams (solve_lockstep): views of this
     // context that share its arena (every pointer is LP 0's; a view's launches cover the LPs [bt.first, bt.first + B))
@@ -400,7 +379,7 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     if (c->rs.st) (void)hipStreamSynchronize(c->rs.st);      // before the buffers go
     if (c->p.arena) (void)hipFree(c->p.arena);
     if (c->p.a_shared) (void)hipFree(c->p.a_shared);
-    if (c->p.tile_list) (void)hipFree(c->p.tile_list);
+    adat_lists_destroy(c->p.adat);
     free_list(c->kallocs);
     if (c->mpack) (void)hipFree(c->mpack);
     if (c->st_c) { (void)hipStreamSynchronize(c->st_c); (void)hipStreamDestroy(c->st_c); }
@@ -414,38 +393,6 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     if (c->la.ev_join) (void)hipEventDestroy(c->la.ev_join);
     stream_res_destroy(c->rs);
     delete c;
-}
-
-// Order in which the lower-triangular 128x128 tiles of M are handed to workgroups.  Workgroups are
-// renumbered so that 64 consecutive tiles run on one XCD (one L2): full off-diagonal 8x8 super-blocks
-// come first, each exactly one such chunk (16 row panels of A feed 64 tiles); the triangular
-// diagonal super-blocks (36 tiles each) follow and are the ones that straddle chunk boundaries.
-// The same tiles ordered for the column-split reduction of M (enqueue_head): column group g (tile columns 4g .. 4g+3, one
-// outer panel of the factorisation) is one contiguous sub-list; inside it row by row.
-static std::vector<int2> adat_tile_order_grouped(int nt, std::vector<int>& off, std::vector<int>& cnt) {
-    std::vector<int2> v;
-    off.clear(); cnt.clear();
-    for (int g = 0; g * POTRF_OUTER < nt; ++g) {
-        off.push_back((int)v.size());
-        const int c0 = g * POTRF_OUTER, c1 = c0 + POTRF_OUTER < nt ? c0 + POTRF_OUTER : nt;
-        for (int ti = c0; ti < nt; ++ti)
-            for (int tj = c0; tj < c1 && tj <= ti; ++tj) v.push_back(make_int2(ti, tj));
-        cnt.push_back((int)v.size() - off.back());
-    }
-    return v;
-}
-static std::vector<int2> adat_tile_order(int nt) {
-    std::vector<int2> v;
-    v.reserve((size_t)nt * (nt + 1) / 2);
-    const int ns = (nt + 7) / 8;
-    auto emit = [&](int SI, int SJ) {
-        for (int ti = SI * 8; ti < nt && ti < SI * 8 + 8; ++ti)
-            for (int tj = SJ * 8; tj < SJ * 8 + 8 && tj <= ti; ++tj) v.push_back(make_int2(ti, tj));
-    };
-    for (int SI = 0; SI < ns; ++SI)
-        for (int SJ = 0; SJ < SI; ++SJ) emit(SI, SJ);
-    for (int SI = 0; SI < ns; ++SI) emit(SI, SI);
-    return v;
 }
 
 // Output tile edge of the inverse-merge GEMMs: 64 (a stage of one LP is a few dozen latency-bound tiles: factorisation
@@ -465,74 +412,6 @@ static int merge_edge_for(int) {
     // 4096: 1865 -> 1854; the lockstep C4 batch is indifferent: 1745 LP/s either way)
     if (const char* e = lp_knob("LPIPM_MERGE_EDGE")) { const int v = atoi(e); return (v == 128 || v == 64) ? v : 32; }
     return 32;
-}
-
-// The unit list of a single LP's A.D.A^T launch, dealt to the XCDs.  Workgroup b of a launch runs on XCD b % 8 (round-robin
-// dispatch), so entry b of the list belongs to XCD b % 8: every XCD gets its OWN tiles (full rounds of 512 tiles: 64
-// consecutive tiles of the order = one 8 x 8 super-block sharing 16 row panels of A; the rest in contiguous eighths) and
-// walks them chunk by chunk -- the workgroups resident on one XCD (one L2) are one k-range of neighbouring tiles for the
-// whole launch, like the data-parallel phase of the round-2 kernel.  Shorter lists are padded with no-op entries.
-// tiles: indices into the launch's tile list, in its order; chunks q0, q0 + upc, ... < cpt per tile.
-static void deal_units(const std::vector<int>& tiles, int cpt, int upc, std::vector<int2>& out) {
-    std::vector<int> own[8];
-    const int nt = (int)tiles.size(), full = nt / 512 * 512, rest = nt - full;
-    for (int i = 0; i < full; ++i) own[(i % 512) / 64].push_back(tiles[(size_t)i]);
-    for (int x = 0; x < 8; ++x)
-        for (int i = full + (int)((long long)rest * x / 8); i < full + (int)((long long)rest * (x + 1) / 8); ++i) own[x].push_back(tiles[(size_t)i]);
-    size_t longest = 0;
-    for (int x = 0; x < 8; ++x) longest = own[x].size() > longest ? own[x].size() : longest;
-    const int nq = (cpt + upc - 1) / upc;
-    for (int q = 0; q < nq; ++q)                           // chunk-major inside an XCD's list
-        for (size_t i = 0; i < longest; ++i)
-            for (int x = 0; x < 8; ++x)
-                out.push_back(i < own[x].size() ? make_int2(own[x][i], q * upc) : make_int2(-1, 0));
-}
-
-// How the A.D.A^T launch of a geometry is cut up: a function of mp, npa, the batch count, the CU count, the number of ranks
-// of a column split (world; it matters for a single LP only) and the value of LPIPM_ADAT_UNITS -- and of nothing else.
-static AdatPlan plan_adat(int mp, int npa, int count, int num_cu, int world, int units_env) {
-    AdatPlan a;
-    const int nt = mp / TILE;
-    a.ntiles = nt * (nt + 1) / 2;
-    // workgroups per LP of the round-2 A.D.A^T launch (LPIPM_ADAT_UNITS=0, and contractions whose slabs would not fit):
-    // stream-K over the chip's share of one LP; a batch that fills the chip with whole tiles needs no k-split
-    if (count == 1) a.adat_nwg = gemm_streamk_nwg(a.ntiles, npa / BK, num_cu);
-    else if ((long long)count * a.ntiles >= 2LL * num_cu) {
-        // more tiles than resident workgroups: each LP gets its share of the 2*CUs slots and stream-K
-        // balances its tiles over them (no tail round of a few leftover tiles)
-        a.adat_nwg = 2 * num_cu / count;
-        if (a.adat_nwg < 1) a.adat_nwg = 1;
-        if (a.adat_nwg > a.ntiles) a.adat_nwg = a.ntiles;
-    } else {
-        a.adat_nwg = gemm_streamk_nwg(a.ntiles, npa / BK, num_cu / count);
-        if (a.adat_nwg < a.ntiles) a.adat_nwg = a.ntiles;
-    }
-    a.ws_slabs = gemm_streamk_slabs(a.ntiles, npa / BK, a.adat_nwg);
-    // A.D.A^T as (tile, chunk) units: every chunk sum goes through its own slab (ntiles x cpt slabs of 128 KiB per LP:
-    // 0.55 GB at C3, 38 MB per member at C4) -- up to 4 GiB per LP, beyond that (m = 16384: 34 GB) the round-2 kernel
-    // -- and only up to ADAT_UNITS_MAX_CPT chunks per tile (npa up to ~256000 columns): longer rows take the round-2 kernel too
-    a.cpt = adat_units_cpt(npa);
-    const bool units_fit = a.cpt <= ADAT_UNITS_MAX_CPT;
-    a.units = units_env != 0 && units_fit && (size_t)a.ntiles * a.cpt * TILE * TILE * sizeof(double) <= ((size_t)4 << 30) &&
-               (count > 1 || units_env == 2 || a.cpt == 1 || a.ntiles <= 16 || a.ntiles * a.cpt >= 256);
-    // (tiny single LPs -- up to 16 tiles -- : one launch and one memset less, 0.042 vs 0.045 ms at 512x1024;
-    //  a single LP with few tiles AND several chunks under 256 units -- 700x1500: 21 tiles x 6, 1009x1100: 36 tiles x 5; not
-    //  1000x5000, whose 36 tiles x 11 chunks are 396 units -- keeps the round-2 kernel: one workgroup per
-    //  tile adding the slabs at the end of a launch that never filled the chip costs more than the 16-way fix-up launch,
-    //  0.196 vs 0.151 ms; everywhere else the units kernel is level or ahead -- 4096x8192 2.206 vs 2.22 ms inside a solve,
-    //  2048x16384 1.30 vs 1.60 -- carries no spill and leaves out the blocks above the diagonal of the diagonal tiles)
-    // one LP split by columns over ranks: the units kernel signals M's column groups one by one, and each group's cross-rank
-    // sum runs behind the rest of the launch (enqueue_head); its slabs may take up to 32 GiB there (C5: 17 GB per rank)
-    if (count == 1 && world > 1 && units_env != 0 && units_fit && nt <= 64 * POTRF_OUTER &&
-        (size_t)a.ntiles * a.cpt * TILE * TILE * sizeof(double) <= ((size_t)32 << 30)) a.units = true;
-    // a single LP: one chunk per unit (parallelism, and column groups that complete while the launch runs); a lockstep
-    // batch: two chunks per unit -- whole tiles (one unit = all chunks, its own workgroup adds its slabs) leave the last of
-    // 2.25 rounds of tiles a quarter full (C4 shard: 1633 LP/s, against 1706 with one chunk per unit, 1533 / 1521 / 1521 at
-    // 2 / 1 / 4 chunks on a slower box)
-    a.upc = count == 1 ? 1 : (a.cpt < 2 ? a.cpt : 2);
-    { int kc, nbig, ks; if (adat_units_chunking(npa, &kc, &nbig, &ks) != nbig) a.upc = 1; }   // non-uniform chunks: one per unit
-    if (a.units && a.ws_slabs < (size_t)a.ntiles * a.cpt) a.ws_slabs = (size_t)a.ntiles * a.cpt;
-    return a;
 }
 
 // Per-LP device state: one pass over a measuring arena sizes it, a second pass over the real one places it.
@@ -576,15 +455,7 @@ static int layout_problem(Problem& p, FactorPlan& plan, const AdatPlan& ap, int 
     p.tau = ar.take<double>(mp);
     p.gs = ar.take<double>(8);
     p.xout = ar.take<double>(np);
-    p.sk_claim = ar.take<unsigned int>(1);
-    // arrival counters of the units kernel: one word per tile, then one per column group; cleared by ONE memset per launch
-    // (a block of its own, a multiple of 16 bytes)
-    p.cnt_bytes = (size_t)round_up(((size_t)ap.ntiles + 64) * sizeof(unsigned int), 16);
-    p.tile_cnt = (unsigned int*)ar.take<uint4>(p.cnt_bytes / 16);
-    p.grp_cnt = p.tile_cnt + ap.ntiles;
-    p.wait_timeout = ar.take<unsigned int>(4);
-    // chunk slabs of A.D.A^T (units kernel: every chunk of every tile; round-2 kernel: the stream-K remainder tiles)
-    p.ws = ar.take<double>(ap.ws_slabs * TILE * TILE);
+    adat_take(p.adat, ap, ar);
     return LPIPM_OK;
 }
 
@@ -623,7 +494,7 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
         if (c->p.arena) { LP_HIP(hipFree(c->p.arena)); c->p.arena = nullptr; }
         if (c->p.a_shared) { LP_HIP(hipFree(c->p.a_shared)); c->p.a_shared = nullptr; c->p.a_shared_bytes = 0; }
         c->p.shared_a = shared;
-        if (c->p.tile_list) { LP_HIP(hipFree(c->p.tile_list)); c->p.tile_list = nullptr; }
+        adat_lists_destroy(c->p.adat);
         factor_plan_destroy(c->plan);
         c->p.has_problem = false;
         c->p.mp = mp; c->p.np = np; c->p.npa = npa; c->p.B = count;
@@ -631,33 +502,7 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
         const uint64_t big = m > n ? m : n;
         c->p.nblk = (int)((big + 255) / 256);
         if (c->p.nblk > RED_STRIDE) c->p.nblk = RED_STRIDE;
-        const int nt = mp / TILE;
-        std::vector<int2> order = adat_tile_order(nt);
         c->ap = plan_adat(mp, npa, count, c->num_cu, c->world, c->units_env);
-        std::vector<int2> units, units_grp;
-        if (c->ap.units) {
-            if (count == 1) {
-                std::vector<int> all((size_t)c->ap.ntiles);
-                for (int t = 0; t < c->ap.ntiles; ++t) all[(size_t)t] = t;
-                deal_units(all, c->ap.cpt, c->ap.upc, units);
-            } else {                                               // a batch: an LP's units all run on one XCD (xcd-major grid)
-                for (int q = 0; q < c->ap.cpt; q += c->ap.upc)
-                    for (int t = 0; t < c->ap.ntiles; ++t) units.push_back(make_int2(t, q));
-            }
-        }
-        c->p.nunits = (int)units.size();
-        const bool grouped_reduce = count == 1 && c->world > 1 && c->ap.units && nt <= 64 * POTRF_OUTER;
-        std::vector<int2> grouped;
-        if (grouped_reduce) {       // column-group-major unit list for the pipelined reduction of M (enqueue_head)
-            grouped = adat_tile_order_grouped(nt, c->p.grp_off, c->p.grp_nt);
-            for (size_t g = 0; g < c->p.grp_nt.size(); ++g) {
-                std::vector<int> grp((size_t)c->p.grp_nt[g]);
-                for (int t = 0; t < c->p.grp_nt[g]; ++t) grp[(size_t)t] = c->p.grp_off[g] + t;
-                deal_units(grp, c->ap.cpt, 1, units_grp);
-            }
-        }
-        c->p.nunits_grp = (int)units_grp.size();
-        c->p.grouped_reduce = grouped_reduce && c->p.nunits_grp > 0;
         Arena measure;
         LP_TRY(layout_problem(c->p, c->plan, c->ap, c->refine, measure, false, st));
         c->p.bstride = round_up(measure.off, 4096);
@@ -673,19 +518,7 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
             LP_HIP(hipMemsetAsync(c->p.a_shared, 0, c->p.a_shared_bytes, st));
             c->p.A = c->p.a_shared;
         }
-        c->p.list_bytes = (order.size() + grouped.size() + units.size() + units_grp.size() + 1) * sizeof(int2);
-        LP_HIP(hipMalloc((void**)&c->p.tile_list, c->p.list_bytes));
-        LP_HIP(hipMemcpyAsync(c->p.tile_list, order.data(), order.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-        c->p.tile_list_grp = c->p.tile_list + order.size();
-        c->p.unit_list = c->p.tile_list_grp + grouped.size();
-        c->p.unit_list_grp = c->p.unit_list + units.size();
-        if (!grouped.empty())
-            LP_HIP(hipMemcpyAsync(c->p.tile_list_grp, grouped.data(), grouped.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-        if (!units.empty())
-            LP_HIP(hipMemcpyAsync(c->p.unit_list, units.data(), units.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-        if (!units_grp.empty())
-            LP_HIP(hipMemcpyAsync(c->p.unit_list_grp, units_grp.data(), units_grp.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-        LP_HIP(hipStreamSynchronize(st));  // the lists must outlive the copies
+        LP_HIP(adat_lists_create(c->p.adat, c->ap, mp, count, st));    // (drains st)
         LP_TRY(stream_res_grow_status(c->rs, (size_t)count));
         VecArgs& v = c->p.va;
         v.np = np; v.mp = mp; v.nblk = c->p.nblk; v.nsplit = c->p.nsplit;
@@ -738,7 +571,7 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
     }
     LP_HIP(hipStreamSynchronize(st));   // the caller's arrays and c0v are free again from here
     c->p.has_problem = true;
-    c->cnt_dirty = true;
+    c->p.adat.counters_dirty = true;
     bind_status_pinned(c, true);
     return LPIPM_OK;
 }
@@ -792,50 +625,22 @@ static hipError_t ctx_gemv_dual(lpipm_ctx* c, const double* W, const double* V, 
 
 // M = A . diag(dinv) . A^T, lower tiles (newton_equations.rs:54-57); a second copy of it goes to M0 (the matrix the
 // refined Cholesky solves take their residuals against: M itself is factorised in place)
-static GemmArgs adat_args(lpipm_ctx* c, const Batch& bt) {
-    GemmArgs g{};
-    g.P = c->p.A; g.ldp = c->p.npa; g.Q = c->p.A; g.ldq = c->p.npa; g.s = c->p.va.dinv;
-    g.C = c->p.M; g.ldc = c->p.mp; g.K = c->p.npa; g.alpha = 1.0; g.beta = 0.0;
-    g.ntiles = c->ap.ntiles; g.tiles_lower = 1; g.ntj = 0; g.tile_list = c->p.tile_list;
-    g.diag_pad_from = (int)c->p.m; g.ws = c->p.ws; g.nwg = c->ap.adat_nwg; g.batch = bt; g.sk_claim = c->p.sk_claim; g.streamk = 1;
-    g.C2 = (c->refine > 0 && gemm_streamk_split(c->p.npa / BK)) ? c->p.M0 : nullptr;    // only the refined solves need M itself
-    g.shared_a = c->p.shared_a;
-    return g;
-}
-static AdatUnitsArgs adat_units_args(lpipm_ctx* c, const Batch& bt) {
-    AdatUnitsArgs a{};
-    a.A = c->p.A; a.lda = c->p.npa; a.s = c->p.va.dinv; a.C = c->p.M; a.ldc = c->p.mp; a.K = c->p.npa;
-    a.C2 = (c->refine > 0 && c->ap.cpt > 1) ? c->p.M0 : nullptr;                // only the refined solves need M itself
-    a.ntiles = c->ap.ntiles; a.tile_list = c->p.tile_list; a.unit_list = c->p.unit_list; a.nunits = c->p.nunits; a.upc = c->ap.upc;
-    a.diag_pad_from = (int)c->p.m; a.slabs = c->p.ws; a.tile_cnt = c->p.tile_cnt;
-    a.grp_cnt = nullptr; a.grp_w = POTRF_OUTER; a.batch = bt; a.shared_a = c->p.shared_a;
+static AdatLaunch adat_launch(lpipm_ctx* c, const Batch& bt) {
+    AdatLaunch a{};
+    a.A = c->p.A; a.lda = c->p.npa; a.dinv = c->p.va.dinv; a.M = c->p.M; a.ldm = c->p.mp;
+    a.M2 = c->refine > 0 ? c->p.M0 : nullptr;                                // only the refined solves need M itself
+    a.K = c->p.npa; a.diag_pad_from = (int)c->p.m; a.batch = bt; a.shared_a = c->p.shared_a;
     return a;
 }
-// clears the arrival counters (tiles and groups) of every LP of the batch
-static hipError_t clear_unit_counters(lpipm_ctx* c, const Batch& bt, hipStream_t st) {
-    char* p = (char*)c->p.tile_cnt + (size_t)bt.first * (size_t)bt.stride;
-    return bt.count == 1 ? hipMemsetAsync(p, 0, c->p.cnt_bytes, st)
-                         : hipMemset2DAsync(p, (size_t)bt.stride, 0, c->p.cnt_bytes, (size_t)bt.count, st);
-}
 static hipError_t run_adat(lpipm_ctx* c, const Batch& bt) {
-    hipError_t e;
-    bool second_copy;
-    if (c->ap.units) {
-        const AdatUnitsArgs a = adat_units_args(c, bt);
-        if (c->ap.cpt > 1 && c->cnt_dirty && (e = clear_unit_counters(c, bt, c->rs.st)) != hipSuccess) return e;
-        if ((e = launch_adat_units(a, c->rs.st)) != hipSuccess) return e;
-        c->cnt_dirty = false;            // the last arriver of every tile has put its word back to zero
-        second_copy = a.C2 != nullptr;
-    } else {
-        const GemmArgs g = adat_args(c, bt);
-        if ((e = launch_gemm_nt(g, c->rs.st)) != hipSuccess) return e;
-        second_copy = g.C2 != nullptr;
-    }
+    bool second_copy = false;
+    hipError_t e = launch_adat(c->ap, c->p.adat, adat_launch(c, bt), false, c->rs.st, &second_copy);
+    if (e != hipSuccess) return e;
     e = launch_slack_diag(c->p.ns, c->p.nx, c->p.va.dinv, c->p.M, c->p.mp, c->rs.st, bt);   // + diag(D_slack)
     if (e != hipSuccess) return e;
     if (c->refine <= 0) return hipSuccess;
     if (second_copy) return launch_slack_diag(c->p.ns, c->p.nx, c->p.va.dinv, c->p.M0, c->p.mp, c->rs.st, bt);
-    vec_copy_lower(c->p.M, c->p.M0, c->p.mp, c->p.mp, c->rs.st, bt);     // short contraction: one store per tile, copied afterwards
+    vec_copy_lower(c->p.M, c->p.M0, c->p.mp, c->p.mp, c->rs.st, bt);     // the launch could not write it: copied afterwards
     return hipGetLastError();
 }
 
@@ -920,8 +725,8 @@ static int copy_status(lpipm_ctx* c) {
     else if (c->p.B == 1) LP_HIP(hipMemcpyAsync(c->rs.status_host, (const char*)c->p.va.status + (size_t)c->p.bt.first * c->p.bstride, sizeof(StatusRec), hipMemcpyDeviceToHost, c->rs.st));
     else LP_HIP(hipMemcpy2DAsync(c->rs.status_host, sizeof(StatusRec), (const char*)c->p.va.status + (size_t)c->p.bt.first * c->p.bstride, c->p.bstride,
                                  sizeof(StatusRec), (size_t)c->p.B, hipMemcpyDeviceToHost, c->rs.st));
-    if (c->colsplit && c->p.grouped_reduce)   // a wait kernel that gave up (its producer never ran) says so here
-        LP_HIP(hipMemcpyAsync(c->rs.timeout_host, c->p.wait_timeout, sizeof(unsigned int), hipMemcpyDeviceToHost, c->rs.st));
+    if (c->colsplit && c->p.adat.ngroups() > 0)   // a wait kernel that gave up (its producer never ran) says so here
+        LP_HIP(hipMemcpyAsync(c->rs.timeout_host, c->p.adat.wait_timeout, sizeof(unsigned int), hipMemcpyDeviceToHost, c->rs.st));
     return LPIPM_OK;
 }
 
@@ -940,7 +745,7 @@ static int enqueue_head(lpipm_ctx* c) {
     if (c->pred_done) c->pred_done = false;       // the residual launch in front of this head has done it (enqueue_residuals)
     else vec_pred_setup(vh, st);
     prof_mark(c, T_VEC, true);
-    if (c->colsplit && c->world > 1 && c->p.grouped_reduce && c->st_c) {
+    if (c->colsplit && c->world > 1 && c->p.adat.ngroups() > 0 && c->st_c) {
         // n-split, M = sum_g A_g D_g A_g^T, PIPELINED: one A.D.A^T launch in column-group-major order on the solver's stream;
         // the workgroup that completes a group's last tile bumps the group's word; on the communication stream a one-wave
         // kernel waits for that word, the group's tiles are packed, summed over the ranks (the caller's all-reduce) and
@@ -951,20 +756,16 @@ static int enqueue_head(lpipm_ctx* c) {
         // the buffer (a ring all-reduce such as gloo's does not: last-bit differences between the two ways).
         hipStream_t sc = c->st_c;
         const Batch& bt = c->p.bt_head;
-        LP_HIP(clear_unit_counters(c, bt, st));
-        c->cnt_dirty = true;
-        LP_HIP(hipEventRecord(c->ev_c0, st));
+        // (the launch arms ev_c0 once the group words are zero, in front of its kernel)
+        LP_HIP(launch_adat(c->ap, c->p.adat, adat_launch(c, bt), true, st, nullptr, c->ev_c0));
         LP_HIP(hipStreamWaitEvent(sc, c->ev_c0, 0));
-        AdatUnitsArgs a = adat_units_args(c, bt);
-        a.tile_list = c->p.tile_list_grp; a.unit_list = c->p.unit_list_grp; a.nunits = c->p.nunits_grp; a.upc = 1;
-        a.grp_cnt = c->p.grp_cnt; a.C2 = nullptr;
-        LP_HIP(launch_adat_units(a, st));
-        for (size_t g = 0; g < c->p.grp_nt.size(); ++g) {
-            double* slice = c->mpack + (size_t)c->p.grp_off[g] * TILE * TILE;
-            LP_HIP(launch_wait_count(c->p.grp_cnt + g, (unsigned)c->p.grp_nt[g], bt.done, c->p.wait_timeout, sc));
-            vec_pack_tiles(c->p.M, c->p.mp, c->p.tile_list_grp + c->p.grp_off[g], c->p.grp_nt[g], slice, 0, sc);
-            LP_TRY(ctx_allreduce(c, slice, (uint64_t)c->p.grp_nt[g] * TILE * TILE, 0, sc));
-            vec_pack_tiles(c->p.M, c->p.mp, c->p.tile_list_grp + c->p.grp_off[g], c->p.grp_nt[g], slice, 1, sc);
+        for (int g = 0; g < c->p.adat.ngroups(); ++g) {
+            const AdatGroup grp = adat_group(c->p.adat, g);
+            double* slice = c->mpack + (size_t)grp.first * TILE * TILE;
+            LP_HIP(launch_wait_count(grp.word, (unsigned)grp.ntiles, bt.done, c->p.adat.wait_timeout, sc));
+            vec_pack_tiles(c->p.M, c->p.mp, grp.tiles, grp.ntiles, slice, 0, sc);
+            LP_TRY(ctx_allreduce(c, slice, (uint64_t)grp.ntiles * TILE * TILE, 0, sc));
+            vec_pack_tiles(c->p.M, c->p.mp, grp.tiles, grp.ntiles, slice, 1, sc);
         }
         LP_HIP(hipEventRecord(c->ev_c1, sc));
         LP_HIP(hipStreamWaitEvent(st, c->ev_c1, 0));
@@ -1187,7 +988,7 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XO
             prof_collect(c, marks);
         }
         ++loop_iterations;
-        if (c->colsplit && c->p.grouped_reduce && *rs.timeout_host != 0) {
+        if (c->colsplit && c->p.adat.ngroups() > 0 && *rs.timeout_host != 0) {
             g_err_detail = "a column group of A.D.A^T did not complete within the wait kernel's bound";
             LP_HIP(hipStreamSynchronize(st));
             return LPIPM_ERR_HIP;
@@ -1309,6 +1110,7 @@ static lpipm_ctx* make_view(const lpipm_ctx* c, int first, int count) {
     v->device = c->device; v->num_cu = c->num_cu; v->refine = c->refine;
     v->ap = c->ap;
     v->p = c->p;
+    v->p.adat.counters_dirty = true;     // whatever the parent's state: this view's stream has not launched yet
     v->p.B = count;
     v->p.bt = Batch{count, (long long)c->p.bstride, c->p.va.done, first};
     v->p.bt_head = v->p.bt;
@@ -1368,7 +1170,7 @@ extern "C" int lpipm_upload_lockstep_shared(lpipm_ctx* c, uint64_t count, uint64
 }
 extern "C" int lpipm_get_resident_bytes(const lpipm_ctx* c, uint64_t* bytes_out) {
     if (!c || !bytes_out) return LPIPM_ERR_BAD_ARGUMENT;
-    *bytes_out = c->p.has_problem ? (uint64_t)(c->p.arena_bytes + c->p.a_shared_bytes + c->p.list_bytes) : 0;
+    *bytes_out = c->p.has_problem ? (uint64_t)(c->p.arena_bytes + c->p.a_shared_bytes + c->p.adat.list_bytes) : 0;
     return LPIPM_OK;
 }
 extern "C" int lpipm_solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, double* const* x_slack_out, double* fun_out,
@@ -1890,7 +1692,7 @@ extern "C" int lpipm_k_iteration(lpipm_ctx* c, const lpipm_opts* o, int ip, doub
     LP_HIP(hipMemcpyAsync(d_y, v.dy, c->p.m * sizeof(double), hipMemcpyDeviceToHost, st));
     LP_HIP(hipMemcpyAsync(d_z, v.dz, c->p.n * sizeof(double), hipMemcpyDeviceToHost, st));
     LP_HIP(hipStreamSynchronize(st));
-    if (c->colsplit && c->p.grouped_reduce && *c->rs.timeout_host != 0) {   // as solve_members: a group wait that gave up is an error
+    if (c->colsplit && c->p.adat.ngroups() > 0 && *c->rs.timeout_host != 0) {   // as solve_members: a group wait that gave up is an error
         g_err_detail = "a column group of A.D.A^T did not complete within the wait kernel's bound";
         return LPIPM_ERR_HIP;
     }

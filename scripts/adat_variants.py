@@ -73,7 +73,8 @@ def lockstep(K, m, n, reps, **env):
 
 what = sys.argv[1:] or ["adat", "c3", "c4", "c2"]
 if "adat" in what:
-    for (m, n) in ((512, 1024), (1024, 2048), (2048, 4096), (4096, 8192), (1000, 5000), (3000, 3500), (2048, 16384), (6144, 12288)):
+    for (m, n) in ((512, 1024), (1024, 2048), (2048, 4096), (4096, 8192), (1000, 5000), (3000, 3500), (2048, 16384), (6144, 12288),
+                   (700, 1500), (1009, 1100)):      # the single-LP shapes that take the round-2 kernel by default
         adat(m, n)
 if "c3" in what:
     x0 = solve(4096, 8192, 5, LPIPM_ADAT_UNITS=0)

@@ -158,12 +158,12 @@ def test_product_never_imports_oracle():
 
 
 def test_units_kernel_has_no_spills_and_four_waves_per_simd():
-    """Build-time property of the A.D.A^T units kernel (kernels_gemm.hip, gemm_nt_units_kernel): 4 waves per SIMD (two
+    """Build-time property of the A.D.A^T units kernel (kernels_adat.hip, gemm_nt_units_kernel): 4 waves per SIMD (two
     512-thread workgroups per CU) with NO VGPR / SGPR spill and no scratch -- at 128 VGPRs a spill inside the main loop puts
     an s_waitcnt vmcnt(0) in front of the prefetch it has just issued.  Read from hipcc's own resource-usage remarks."""
     import re
     import subprocess
-    src = os.path.join(ROOT, "lp_amd", "csrc", "kernels_gemm.hip")
+    src = os.path.join(ROOT, "lp_amd", "csrc", "kernels_adat.hip")
     out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++20", "--offload-arch=gfx950", "--cuda-device-only", "-c",
                           "-Rpass-analysis=kernel-resource-usage", src, "-o", os.devnull],
                          capture_output=True, text=True, cwd=os.path.dirname(src)).stderr

@@ -12,7 +12,7 @@ identical LP in which only summation orders change; tests/golden/make_envelopes.
 on 5 not even about the iteration count.
 
 The two paths must agree with each other BIT FOR BIT: an LP goes through the same kernels with the same summation
-orders alone and as a batch member (canonical chunked summation in A.D.A^T, kernels_gemm.hip; super-block width a
+orders alone and as a batch member (canonical chunked summation in A.D.A^T, kernels_adat.hip; super-block width a
 function of m alone, solver.hip)."""
 import os
 

@@ -11,7 +11,7 @@ plain references (oracle/factor_checks.py).  Which branch each shape reaches fol
                       [0,4)+[4,7), [4,6)+[6,7)); 40 padded rows
   16384  16384 / 128  the C5 factor: probe checks only
 
-  A.D.A^T, single LP, default knobs (plan_adat, launch_gemm_nt): the round-2 kernel (gemm_nt_streamk_w8_kernel) and its
+  A.D.A^T, single LP, default knobs (plan_adat, launch_adat): the round-2 kernel (gemm_nt_streamk_w8_kernel) and its
   fix-up (gemm_nt_fixup_kernel) where the units kernel is not taken --
   (768, 2048)    21 tiles x 8 chunks < 256 units: round-2, every tile stream-K, KT = 128 <= 256
   (1025, 1100)   45 tiles x 5 chunks < 256 units: round-2, every tile stream-K, KT = 69
@@ -216,7 +216,7 @@ def _adat_check(cx, A, d):
 @pytest.mark.parametrize("m,n", [(768, 2048), (1025, 1100)])
 def test_adat_round2_default_small(ctx, built, monkeypatch, m, n):
     """The round-2 kernel with its fix-up at KT <= 256 (the default for these shapes): against numpy, and bit-identical to
-    the units kernel (LPIPM_ADAT_UNITS=2) -- the head of kernels_gemm.hip: M's bits do not depend on the decomposition."""
+    the units kernel (LPIPM_ADAT_UNITS=2) -- the head of kernels_adat.hip: M's bits do not depend on the decomposition."""
     import lp_amd
     rng = np.random.default_rng(m * n)
     A = rng.standard_normal((m, n))

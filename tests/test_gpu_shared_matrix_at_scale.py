@@ -81,7 +81,7 @@ def _views(count):
 
 
 def _plan(m, n, count=1):
-    """The host-side launch rules (upload_impl, plan_adat, launch_gemv_* with shared_a, adat_units_chunking) for one VIEW of
+    """The host-side launch rules (upload_impl, plan_adat, launch_gemv_* with shared_a, units_chunking) for one VIEW of
     `count` members."""
     mp, npa = _up(m, 128), _up(n, 16)
     KT = npa // 16
@@ -231,7 +231,7 @@ def test_dual_pass_1024_columns_groups_of_two(ctx, m, n, seed):
     if (m, n) == (512, 4096):
         assert p["uniform"] and p["cpt"] == 16 and _plan(m, n, 5)["upc"] == 2
     if (m, n) == (1000, 5000):
-        # 36 tiles x 11 chunks: 8 row slabs of the dual pass times 5 chunk slabs.  (With the chunking of adat_units_chunking
+        # 36 tiles x 11 chunks: 8 row slabs of the dual pass times 5 chunk slabs.  (With the chunking of units_chunking
         # a single LP of this shape has 396 units and takes the units kernel too; the shapes where the single LP takes the
         # stream-K kernel with its fix-up and the batch the units kernel are 700 x 1500 and 1009 x 1100 below.)
         assert p["ntiles"] == 36 and p["cpt"] == 11 and not p["single_streamk"] and p["row_slabs"] == 8
