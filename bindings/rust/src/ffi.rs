@@ -90,6 +90,28 @@ extern "C" {
         ctx: *mut lpipm_ctx, count: u64, m: u64, n: u64, a: *const f64, lda: u64, b: *const *const f64,
         c: *const *const f64, c0: *const f64,
     ) -> c_int;
+    // The same batches with the structural hint of lpipm_upload_slack (linear_program.rs:145-161): the slack block [I; 0]
+    // of the `ub` rows is verified, then neither stored nor multiplied; members bit-identical to lpipm_upload_slack + lpipm_solve.
+    pub fn lpipm_upload_lockstep_slack(
+        ctx: *mut lpipm_ctx, count: u64, m: u64, n: u64, a: *const *const f64, b: *const *const f64,
+        c: *const *const f64, c0: *const f64, n_slack: u64,
+    ) -> c_int;
+    pub fn lpipm_upload_lockstep_shared_slack(
+        ctx: *mut lpipm_ctx, count: u64, m: u64, n: u64, a: *const f64, lda: u64, b: *const *const f64,
+        c: *const *const f64, c0: *const f64, n_slack: u64,
+    ) -> c_int;
+    // Device-side assembly of a shared-matrix batch: the ub / eq blocks once, b[i] = [b_ub_i; b_eq_i], c[i] = n structural costs.
+    pub fn lpipm_upload_lockstep_shared_ub_eq(
+        ctx: *mut lpipm_ctx, count: u64, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, m_eq: u64, a_eq: *const f64,
+        lda_eq: u64, b: *const *const f64, c: *const *const f64, c0: *const f64,
+    ) -> c_int;
+    // lpipm_solve_batch with a per-member hint (n_slack nullable); exactly one of x_slack_out and x_dev_out is non-null.
+    pub fn lpipm_solve_batch_slack(
+        ctx: *mut lpipm_ctx, count: u64, m: *const u64, n: *const u64, n_slack: *const u64, a: *const *const f64,
+        b: *const *const f64, c: *const *const f64, c0: *const f64, opts: *const lpipm_opts,
+        x_slack_out: *const *mut f64, x_dev_out: *mut c_void, row_stride: u64, fun_out: *mut f64,
+        iterations_out: *mut u64, status_out: *mut i32,
+    ) -> c_int;
     // Device bytes held for the resident problem(s): arenas + shared matrix + factor workspace.
     pub fn lpipm_get_resident_bytes(ctx: *const lpipm_ctx, bytes_out: *mut u64) -> c_int;
 

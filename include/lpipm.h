@@ -175,13 +175,21 @@ int lpipm_set_collective_on_stream(lpipm_ctx* ctx, int on);
 int lpipm_upload_nsplit(lpipm_ctx* ctx, uint64_t m, uint64_t n_total, uint64_t n_local, const double* A_local,
                         uint64_t lda, const double* b, const double* c_local, double c0);
 
-/* Lockstep batch: `count` LPs of ONE shape (m x n, dense) resident on the device at once; every kernel launch of
+/* Lockstep batch: `count` LPs of ONE shape (m x n; dense, or with the slack hint of lpipm_upload_lockstep_slack) resident on the device at once; every kernel launch of
  * the iteration covers all of them, so the ~100 dependent launches per iteration are paid once per batch
  * instead of once per LP.  lpipm_upload_lockstep replaces the context's problem; lpipm_solve_lockstep returns
  * per-LP status (0 / LinearProgramError variants), fun, iterations and x / tau, exactly as `count` calls of
  * lpipm_solve would (Cholesky arm only: LPIPM_ERR_UNSUPPORTED otherwise).  A[i]: m x n row-major, lda = n. */
 int lpipm_upload_lockstep(lpipm_ctx* ctx, uint64_t count, uint64_t m, uint64_t n, const double* const* A,
                           const double* const* b, const double* const* c, const double* c0 /* nullable */);
+/* lpipm_upload_lockstep with the structural hint of lpipm_upload_slack (n_slack, linear_program.rs:161): the last n_slack
+ * columns of EVERY member are the slack block [I; 0] of its `ub` rows (linear_program.rs:145-161) and are then neither
+ * copied nor multiplied.  The hint is verified on every member; if one member's columns are not [I; 0] the whole upload is
+ * treated as dense (and still returns Ok); n_slack == n is ignored.  Each member comes out bit-identical to
+ * lpipm_upload_slack (same hint) + lpipm_solve of that member alone.  n_slack = 0: exactly lpipm_upload_lockstep. */
+int lpipm_upload_lockstep_slack(lpipm_ctx* ctx, uint64_t count, uint64_t m, uint64_t n, const double* const* A,
+                                const double* const* b, const double* const* c, const double* c0 /* nullable */,
+                                uint64_t n_slack);
 int lpipm_solve_lockstep(lpipm_ctx* ctx, const lpipm_opts* opts, double* const* x_slack_out, double* fun_out,
                          uint64_t* iterations_out, int32_t* status_out);
 /* The same with the solutions left in HBM: x / tau of LP i goes to the DEVICE row x_dev_out + i * row_stride doubles
@@ -193,9 +201,25 @@ int lpipm_solve_lockstep_device(lpipm_ctx* ctx, const lpipm_opts* opts, void* x_
  * (A, b[i], c[i], c0[i]).  A is copied to the device once and is not part of any member's arena; every pass over A
  * serves the whole batch.  Solve with lpipm_solve_lockstep / lpipm_solve_lockstep_device, exactly as after
  * lpipm_upload_lockstep: each member comes out bit-identical to lpipm_upload + lpipm_solve of (A, b[i], c[i], c0[i]).
- * Validation and return codes as lpipm_upload_lockstep (dense slack form, no n_slack hint; Cholesky arm only). */
+ * Validation and return codes as lpipm_upload_lockstep (Cholesky arm only).  This entry takes A as a dense matrix; the
+ * two below keep its slack block structural. */
 int lpipm_upload_lockstep_shared(lpipm_ctx* ctx, uint64_t count, uint64_t m, uint64_t n, const double* A, uint64_t lda,
                                  const double* const* b, const double* const* c, const double* c0 /* nullable */);
+/* lpipm_upload_lockstep_shared with the structural hint of lpipm_upload_slack (linear_program.rs:145-161): the one shared A
+ * is given with its n_slack slack columns [I; 0], which are verified and then neither copied nor multiplied (a matrix
+ * without them is treated as dense; n_slack == n is ignored).  Each member bit-identical to lpipm_upload_slack (same hint) +
+ * lpipm_solve of (A, b[i], c[i], c0[i]).  n_slack = 0: exactly lpipm_upload_lockstep_shared. */
+int lpipm_upload_lockstep_shared_slack(lpipm_ctx* ctx, uint64_t count, uint64_t m, uint64_t n, const double* A, uint64_t lda,
+                                       const double* const* b, const double* const* c, const double* c0 /* nullable */,
+                                       uint64_t n_slack);
+/* Device-side assembly (as lpipm_upload_ub_eq; ProblemBuilder::build, linear_program.rs:145-161) of a shared-matrix batch:
+ * the ub / eq blocks are given once (either may be absent: row count 0, pointer NULL; both absent -> LPIPM_UNCONSTRAINED).
+ * b[i] = [b_ub_i; b_eq_i] (m_ub + m_eq doubles), c[i] = the n structural costs.  No (m_ub+m_eq) x (n+m_ub) host matrix
+ * exists anywhere.  x of lpipm_solve_lockstep has n + m_ub entries, slack values last; each member bit-identical to
+ * lpipm_upload_ub_eq + lpipm_solve of that member alone. */
+int lpipm_upload_lockstep_shared_ub_eq(lpipm_ctx* ctx, uint64_t count, uint64_t n, uint64_t m_ub, const double* A_ub,
+                                       uint64_t lda_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq,
+                                       const double* const* b, const double* const* c, const double* c0 /* nullable */);
 /* Device bytes the context holds for its resident problem(s) (arenas + shared matrix + factor workspace); 0 before any
  * upload. */
 int lpipm_get_resident_bytes(const lpipm_ctx* ctx, uint64_t* bytes_out);
@@ -206,6 +230,16 @@ int lpipm_solve_batch_device(lpipm_ctx* ctx, uint64_t count, const uint64_t* m, 
                              const double* c0 /* nullable */, const lpipm_opts* opts, void* x_dev_out,
                              uint64_t row_stride, double* fun_out /* nullable */, uint64_t* iterations_out /* nullable */,
                              int32_t* status_out);
+/* lpipm_solve_batch / lpipm_solve_batch_device with a per-member structural hint (n_slack nullable = all 0; semantics of
+ * lpipm_upload_slack, linear_program.rs:145-161).  Each member's hint is verified first; members are then grouped into
+ * lockstep batches by (m, n, the hint that holds), and members solved one at a time are uploaded with their hint.
+ * Exactly one of x_slack_out (host rows, as lpipm_solve_batch) and x_dev_out (+ row_stride, as lpipm_solve_batch_device)
+ * is non-null.  Each member bit-identical to lpipm_upload_slack (its hint) + lpipm_solve. */
+int lpipm_solve_batch_slack(lpipm_ctx* ctx, uint64_t count, const uint64_t* m, const uint64_t* n, const uint64_t* n_slack,
+                            const double* const* A, const double* const* b, const double* const* c,
+                            const double* c0 /* nullable */, const lpipm_opts* opts, double* const* x_slack_out,
+                            void* x_dev_out, uint64_t row_stride, double* fun_out, uint64_t* iterations_out,
+                            int32_t* status_out);
 /* lpipm_solve_batch groups members of equal shape into lockstep batches: max_group -1 = auto (default: chunks
  * of up to 32 within the memory budget, the upload of one chunk overlapping the solve of the previous one), 0 = never, > 0 = largest group. */
 int lpipm_set_batch_lockstep(lpipm_ctx* ctx, int max_group);

@@ -222,6 +222,12 @@ class EquationSolverType(enum.IntEnum):
     LeastSquares = 2
 
 
+def _batch_hints(problems):
+    """The n_slack hints of [(A, b, c, c0[, n_slack]), ...] as a C array, or None when no member carries one."""
+    ns = [int(p[4]) if len(p) > 4 and p[4] else 0 for p in problems]
+    return (C.c_uint64 * len(ns))(*ns) if any(ns) else None
+
+
 # ------------------------------------------------------------------------------ device context
 class Context:
     """One lpipm_ctx: device buffers + stream of one (thread, device).  `InteriorPoint.solve` keeps one
@@ -290,8 +296,11 @@ class Context:
         self.m, self.n = m, nl
         return self
 
-    def upload_lockstep(self, As, bs, cs, c0s=None):
-        """`len(As)` LPs of one shape resident at once (lpipm_upload_lockstep); solve with solve_lockstep."""
+    def upload_lockstep(self, As, bs, cs, c0s=None, n_slack=0):
+        """`len(As)` LPs of one shape resident at once (lpipm_upload_lockstep); solve with solve_lockstep.
+        n_slack > 0 (lpipm_upload_lockstep_slack): the last n_slack columns of every member are the slack block [I; 0] of its
+        `ub` rows, verified and then neither stored nor multiplied -- every member bit-identical to upload_arrays(..., n_slack)
+        + solve_raw of that member alone."""
         As = [_f64(A) for A in As]; bs = [_f64(b) for b in bs]; cs = [_f64(c) for c in cs]
         K = len(As)
         if K < 1 or len(bs) != K or len(cs) != K:
@@ -303,15 +312,20 @@ class Context:
         dp = C.POINTER(C.c_double)
         arr = lambda lst: (dp * K)(*[_p(a) for a in lst])
         c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
-        _raise_for(_capi.lib().lpipm_upload_lockstep(self._h, K, m, n, arr(As), arr(bs), arr(cs), c0))
+        if n_slack:
+            _raise_for(_capi.lib().lpipm_upload_lockstep_slack(self._h, K, m, n, arr(As), arr(bs), arr(cs), c0, int(n_slack)))
+        else:
+            _raise_for(_capi.lib().lpipm_upload_lockstep(self._h, K, m, n, arr(As), arr(bs), arr(cs), c0))
         self._lock = (K, m, n, As, bs, cs)      # keep the host arrays alive only for the duration of the call chain
         self.m, self.n = m, n
         return self
 
-    def upload_lockstep_shared(self, A, bs, cs, c0s=None):
+    def upload_lockstep_shared(self, A, bs, cs, c0s=None, n_slack=0):
         """`len(bs)` LPs that share ONE constraint matrix A, resident at once (lpipm_upload_lockstep_shared): member i is
         (A, bs[i], cs[i], c0s[i]).  A is held once on the device and each pass over it serves the whole batch; solve with
-        solve_lockstep / solve_lockstep_device -- every member bit-identical to solving it alone."""
+        solve_lockstep / solve_lockstep_device -- every member bit-identical to solving it alone.
+        n_slack > 0 (lpipm_upload_lockstep_shared_slack): the last n_slack columns of A are its slack block [I; 0], verified
+        and then neither stored nor multiplied, as upload_arrays(..., n_slack) does for one LP."""
         A = _f64(A); bs = [_f64(b) for b in bs]; cs = [_f64(c) for c in cs]
         K = len(bs)
         if A.ndim != 2 or K < 1 or len(cs) != K or (c0s is not None and len(c0s) != K):
@@ -323,9 +337,40 @@ class Context:
         dp = C.POINTER(C.c_double)
         arr = lambda lst: (dp * K)(*[_p(a) for a in lst])
         c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
-        _raise_for(_capi.lib().lpipm_upload_lockstep_shared(self._h, K, m, n, _p(A), n, arr(bs), arr(cs), c0))
+        if n_slack:
+            _raise_for(_capi.lib().lpipm_upload_lockstep_shared_slack(self._h, K, m, n, _p(A), n, arr(bs), arr(cs), c0,
+                                                                      int(n_slack)))
+        else:
+            _raise_for(_capi.lib().lpipm_upload_lockstep_shared(self._h, K, m, n, _p(A), n, arr(bs), arr(cs), c0))
         self._lock = (K, m, n, A, bs, cs)
         self.m, self.n = m, n
+        return self
+
+    def upload_lockstep_shared_ub_eq(self, A_ub, A_eq, bs, cs, c0s=None):
+        """`len(bs)` inequality-form LPs over ONE pair of blocks (lpipm_upload_lockstep_shared_ub_eq): member i is
+        min cs[i]'x st A_ub x <= bs[i][:m_ub], A_eq x == bs[i][m_ub:], x >= 0.  Either block may be None.  The blocks go to
+        the device once, as they are; the slack block is never formed.  solve_lockstep then returns x with n + m_ub entries,
+        slack values last -- every member bit-identical to Context.upload(Problem...ub().eq().build()) + solve_raw."""
+        bs = [_f64(b) for b in bs]; cs = [_f64(c) for c in cs]
+        K = len(bs)
+        if K < 1 or len(cs) != K or (c0s is not None and len(c0s) != K) or cs[0].ndim != 1:
+            raise IncompatibleInputDimensions()
+        n = cs[0].shape[0]
+        A_ub = _f64(A_ub) if A_ub is not None else np.zeros((0, n))
+        A_eq = _f64(A_eq) if A_eq is not None else np.zeros((0, n))
+        if A_ub.ndim != 2 or A_eq.ndim != 2 or A_ub.shape[1] != n or A_eq.shape[1] != n:
+            raise IncompatibleInputDimensions()
+        m_ub, m_eq = A_ub.shape[0], A_eq.shape[0]
+        for b, c in zip(bs, cs):
+            if b.shape != (m_ub + m_eq,) or c.shape != (n,):
+                raise IncompatibleInputDimensions()
+        dp = C.POINTER(C.c_double)
+        arr = lambda lst: (dp * K)(*[_p(a) for a in lst])
+        c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
+        _raise_for(_capi.lib().lpipm_upload_lockstep_shared_ub_eq(self._h, K, n, m_ub, _p(A_ub) if m_ub else None, n, m_eq,
+                                                                  _p(A_eq) if m_eq else None, n, arr(bs), arr(cs), c0))
+        self._lock = (K, m_ub + m_eq, n + m_ub, None, bs, cs)
+        self.m, self.n = m_ub + m_eq, n + m_ub
         return self
 
     def resident_bytes(self) -> int:
@@ -363,7 +408,8 @@ class Context:
 
     def solve_batch_device(self, problems, opts: "_capi.Opts", x_dev_ptr: int, row_stride: int):
         """lpipm_solve_batch_device over [(A, b, c, c0), ...]: member i's x / tau goes to the device row
-        x_dev_ptr + i * row_stride doubles.  -> list of (status, fun | None, iterations)"""
+        x_dev_ptr + i * row_stride doubles.  A fifth tuple element is the member's n_slack hint (lpipm_solve_batch_slack).
+        -> list of (status, fun | None, iterations)"""
         K = len(problems)
         if K == 0:
             return []
@@ -376,14 +422,20 @@ class Context:
         m = (C.c_uint64 * K)(*[A.shape[0] for A in As]); n = (C.c_uint64 * K)(*[A.shape[1] for A in As])
         c0 = (C.c_double * K)(*[float(p[3]) if len(p) > 3 else 0.0 for p in problems])
         fun = (C.c_double * K)(); its = (C.c_uint64 * K)(); st = (C.c_int32 * K)()
-        rc = _capi.lib().lpipm_solve_batch_device(self._h, K, m, n, arr(As), arr(bs), arr(cs), c0, C.byref(opts),
-                                                  C.c_void_p(int(x_dev_ptr)), int(row_stride), fun, its, st)
+        ns = _batch_hints(problems)
+        if ns is not None:
+            rc = _capi.lib().lpipm_solve_batch_slack(self._h, K, m, n, ns, arr(As), arr(bs), arr(cs), c0, C.byref(opts), None,
+                                                     C.c_void_p(int(x_dev_ptr)), int(row_stride), fun, its, st)
+        else:
+            rc = _capi.lib().lpipm_solve_batch_device(self._h, K, m, n, arr(As), arr(bs), arr(cs), c0, C.byref(opts),
+                                                      C.c_void_p(int(x_dev_ptr)), int(row_stride), fun, its, st)
         if rc != _capi.OK:
             _raise_for(rc)
         return [(int(st[i]), fun[i] if st[i] in (_capi.OK, _capi.ITERATION_LIMIT) else None, int(its[i])) for i in range(K)]
 
     def solve_batch(self, problems, opts: "_capi.Opts"):
         """lpipm_solve_batch over [(A, b, c, c0), ...] (any mix of shapes; equal shapes run as lockstep batches).
+        A fifth tuple element is the member's n_slack hint (lpipm_solve_batch_slack): its slack block stays structural.
         -> list of (status, x_slack | None, fun | None, iterations)"""
         K = len(problems)
         if K == 0:
@@ -398,7 +450,12 @@ class Context:
         m = (C.c_uint64 * K)(*[A.shape[0] for A in As]); n = (C.c_uint64 * K)(*[A.shape[1] for A in As])
         c0 = (C.c_double * K)(*[float(p[3]) if len(p) > 3 else 0.0 for p in problems])
         fun = (C.c_double * K)(); its = (C.c_uint64 * K)(); st = (C.c_int32 * K)()
-        rc = _capi.lib().lpipm_solve_batch(self._h, K, m, n, arr(As), arr(bs), arr(cs), c0, C.byref(opts), arr(xs), fun, its, st)
+        ns = _batch_hints(problems)
+        if ns is not None:
+            rc = _capi.lib().lpipm_solve_batch_slack(self._h, K, m, n, ns, arr(As), arr(bs), arr(cs), c0, C.byref(opts), arr(xs),
+                                                     None, 0, fun, its, st)
+        else:
+            rc = _capi.lib().lpipm_solve_batch(self._h, K, m, n, arr(As), arr(bs), arr(cs), c0, C.byref(opts), arr(xs), fun, its, st)
         if rc != _capi.OK:
             _raise_for(rc)
         out = []

@@ -28,7 +28,7 @@ def shard_range(count: int, world: int, rank: int) -> range:
 
 
 def solve_batch_sharded(problems, opts=None, ctx=None, group=None, device=None, solve_fn=None):
-    """problems: sequence of (A, b, c, c0) -- every rank passes the same list (or at least its shard
+    """problems: sequence of (A, b, c, c0) or (A, b, c, c0, n_slack) -- every rank passes the same list (or at least its shard
     at the right indices).  Returns, on EVERY rank, a list of dicts {status, x_slack, fun, iterations}
     in problem order.  `solve_fn(A, b, c, c0, None) -> (status, x | None, fun, iterations)` replaces the
     library call in the CPU-rank tests."""
@@ -59,7 +59,7 @@ def solve_batch_sharded(problems, opts=None, ctx=None, group=None, device=None, 
         device = device or torch.device("cpu")
         host = np.zeros((rows, n_max + 3))
         for slot, i in enumerate(mine):
-            A, b, c, c0 = problems[i]
+            A, b, c, c0 = problems[i][:4]
             n = np.asarray(c).shape[0]
             rc, x, fun, it = solve_fn(A, b, c, c0, None)
             if x is not None:
@@ -88,11 +88,12 @@ def solve_batch_sharded(problems, opts=None, ctx=None, group=None, device=None, 
     return out
 
 
-def solve_shared_matrix(A, bs, cs, c0s=None, opts=None, ctx=None, max_group=32):
+def solve_shared_matrix(A, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, n_slack=0):
     """LPs that share ONE constraint matrix A (scenario sweeps: only b, c and c0 vary), member i = (A, bs[i], cs[i], c0s[i]).
     The members go through lockstep groups of at most `max_group` on one context (lpipm_upload_lockstep_shared: A resident
     once, every pass over it serving the whole group).  Returns a list of dicts {status, x_slack, fun, iterations} in member
-    order, as solve_batch_sharded does."""
+    order, as solve_batch_sharded does.  n_slack: the last n_slack columns of A are its slack block [I; 0], kept structural
+    (lpipm_upload_lockstep_shared_slack)."""
     import lp_amd
     count = len(bs)
     if len(cs) != count or (c0s is not None and len(c0s) != count):
@@ -104,7 +105,29 @@ def solve_shared_matrix(A, bs, cs, c0s=None, opts=None, ctx=None, max_group=32):
     out = []
     for k0 in range(0, count, max_group):
         k1 = min(k0 + max_group, count)
-        ctx.upload_lockstep_shared(A, bs[k0:k1], cs[k0:k1], None if c0s is None else c0s[k0:k1])
+        ctx.upload_lockstep_shared(A, bs[k0:k1], cs[k0:k1], None if c0s is None else c0s[k0:k1], n_slack=n_slack)
+        for st, x, fun, it in ctx.solve_lockstep(opts):
+            out.append(dict(status=st, x_slack=x, fun=fun, iterations=it))
+    return out
+
+
+def solve_shared_ub_eq(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_group=32):
+    """Inequality-form LPs over ONE pair of blocks (right-hand-side and cost sweeps over A_ub x <= b_ub, A_eq x == b_eq):
+    member i = (bs[i] = [b_ub_i; b_eq_i], cs[i] = the n structural costs, c0s[i]); either block may be None.  Lockstep groups
+    of at most `max_group` on one context through lpipm_upload_lockstep_shared_ub_eq: the blocks resident once, the slack
+    block never formed on the host or the device.  Returns what solve_shared_matrix returns; x_slack has n + m_ub entries."""
+    import lp_amd
+    count = len(bs)
+    if len(cs) != count or (c0s is not None and len(c0s) != count):
+        raise lp_amd.IncompatibleInputDimensions()
+    if max_group < 1:
+        raise lp_amd.InvalidParameter("max_group must be >= 1")
+    ctx = ctx or lp_amd.default_context(0)
+    opts = opts or lp_amd.InteriorPoint.default().opts()
+    out = []
+    for k0 in range(0, count, max_group):
+        k1 = min(k0 + max_group, count)
+        ctx.upload_lockstep_shared_ub_eq(A_ub, A_eq, bs[k0:k1], cs[k0:k1], None if c0s is None else c0s[k0:k1])
         for st, x, fun, it in ctx.solve_lockstep(opts):
             out.append(dict(status=st, x_slack=x, fun=fun, iterations=it))
     return out

@@ -485,6 +485,19 @@ __global__ __launch_bounds__(256) void slack_t_kernel(int ns, int nx, int nrhs, 
     for (int q = 0; q < nrhs; ++q)
         Upart[((long long)sp * nrhs + q) * slab + nx + i] = sp == 0 ? V[q * ldv + i] : 0.0;
 }
+// The dual pass's two slack terms in ONE launch behind gemv_dual (it sits on every iteration's chain): grid.y = row splits as
+// slack_t_kernel with one vector, and the blocks of split 0 also add w[nx + i] into chunk slab 0 of A.w as slack_n_kernel.
+// The same values from the same operands as those two launches, in one place each.
+__global__ __launch_bounds__(256) void slack_dual_kernel(int ns, int nx, const double* __restrict__ W,
+                                                         const double* __restrict__ V, double* __restrict__ AxPart,
+                                                         double* __restrict__ Upart, long long slab, BatchK bk) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= ns || batch_done(bk)) return;
+    W = batch_ptr(W, bk); V = batch_ptr(V, bk); AxPart = batch_ptr(AxPart, bk); Upart = batch_ptr(Upart, bk);
+    const int sp = blockIdx.y;
+    Upart[(long long)sp * slab + nx + i] = sp == 0 ? V[i] : 0.0;
+    if (sp == 0) AxPart[i] += W[nx + i];
+}
 __global__ __launch_bounds__(256) void slack_diag_kernel(int ns, int nx, const double* __restrict__ d,
                                                          double* __restrict__ M, long long ldm, BatchK bk) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -504,6 +517,13 @@ hipError_t launch_slack_t(int ns, int nx, int nrhs, int nsplit, const double* V,
     if (ns <= 0) return hipSuccess;
     hipLaunchKernelGGL(slack_t_kernel, dim3((ns + 255) / 256, nsplit, bt.count), dim3(256), 0, st, ns, nx, nrhs, V, (long long)ldv,
                        Upart, (long long)slab, batch_k(bt));
+    return hipGetLastError();
+}
+hipError_t launch_slack_dual(int ns, int nx, int nsplit, const double* W, const double* V, double* AxPart, double* Upart,
+                             int64_t slab, hipStream_t st, const Batch& bt) {
+    if (ns <= 0) return hipSuccess;
+    hipLaunchKernelGGL(slack_dual_kernel, dim3((ns + 255) / 256, nsplit, bt.count), dim3(256), 0, st, ns, nx, W, V, AxPart, Upart,
+                       (long long)slab, batch_k(bt));
     return hipGetLastError();
 }
 hipError_t launch_slack_diag(int ns, int nx, const double* d, double* M, int64_t ldm, hipStream_t st, const Batch& bt) {

@@ -306,6 +306,9 @@ hipError_t launch_slack_n(int ns, int nx, int nrhs, const double* W, int64_t ldw
                           const Batch& bt = Batch{});
 hipError_t launch_slack_t(int ns, int nx, int nrhs, int nsplit, const double* V, int64_t ldv, double* Upart, int64_t slab,
                           hipStream_t st, const Batch& bt = Batch{});
+// both slack terms of the dual pass in one launch: slack_n into chunk slab 0 of AxPart and slack_t (one vector) into Upart
+hipError_t launch_slack_dual(int ns, int nx, int nsplit, const double* W, const double* V, double* AxPart, double* Upart,
+                             int64_t slab, hipStream_t st, const Batch& bt = Batch{});
 hipError_t launch_slack_diag(int ns, int nx, const double* d, double* M, int64_t ldm, hipStream_t st,
                              const Batch& bt = Batch{});
 // U[r][k] = sum_s Upart[s][r][k]   (stand-alone reduce; the solver fuses this into its consumers)

@@ -459,31 +459,43 @@ static int layout_problem(Problem& p, FactorPlan& plan, const AdatPlan& ap, int 
     return LPIPM_OK;
 }
 
+// Whether the last n_slack columns of every one of the `count` m x n matrices are [I; 0] (n_slack == n: not a hint).
+static bool slack_hint_holds(int count, uint64_t m, uint64_t n, const double* const* A, uint64_t lda, uint64_t n_slack) {
+    if (n_slack == 0 || n_slack == n) return false;
+    for (int k = 0; k < count; ++k)
+        for (uint64_t i = 0; i < m; ++i) {
+            const double* row = A[k] + i * lda + (n - n_slack);
+            for (uint64_t j = 0; j < n_slack; ++j)
+                if (row[j] != ((i == j) ? 1.0 : 0.0)) return false;
+        }
+    return true;
+}
+
 // count LPs of one geometry (count == 1: the ordinary upload).  A/b/cc/c0: one entry per LP.
-// `parts` (count == 1 only): the rows come as two blocks of nx = n - n_slack columns -- m_ub rows of A_ub, then
-// m - m_ub rows of A_eq -- with b split the same way and c holding only the nx structural costs; the slack
-// structure is then true by construction (lpipm_upload_ub_eq).
+// n_slack: the structural hint of lpipm_upload_slack, for every member alike.  It is verified on every member (on the one
+// matrix of a shared batch); if any member's last n_slack columns are not [I; 0] the whole upload is dense.
+// hint_verified: the caller has done that check on these very matrices (batch_impl) and it is not repeated.
+// `parts` (count == 1, or shared): the rows come as two blocks of nx = n - n_slack columns -- m_ub rows of A_ub, then
+// m - m_ub rows of A_eq -- and c holds only the nx structural costs; the slack structure is then true by construction.
+// count == 1: b split the same way, in parts (lpipm_upload_ub_eq).  shared: the blocks are the batch's one matrix and
+// b[i] = [b_ub_i; b_eq_i] comes per member (lpipm_upload_lockstep_shared_ub_eq).
 struct UploadParts { uint64_t m_ub; const double* A_ub; uint64_t lda_ub; const double* b_ub;
                      const double* A_eq; uint64_t lda_eq; const double* b_eq; };
 // shared: A[0] is the one matrix of all `count` LPs (lpipm_upload_lockstep_shared; A holds one entry).
 static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const double* const* A, uint64_t lda,
                        const double* const* b, const double* const* cc, const double* c0, uint64_t n_slack,
-                       const UploadParts* parts = nullptr, bool shared = false) {
+                       const UploadParts* parts = nullptr, bool shared = false, bool hint_verified = false) {
     if (!c || count < 1 || !cc) return LPIPM_ERR_BAD_ARGUMENT;
     if (!parts && (!A || !b || lda < n)) return LPIPM_ERR_BAD_ARGUMENT;
+    if (parts && (shared ? !b : count != 1)) return LPIPM_ERR_BAD_ARGUMENT;
     for (int i = 0; i < count; ++i)
-        if (!cc[i] || (!parts && ((!shared && !A[i]) || !b[i]))) return LPIPM_ERR_BAD_ARGUMENT;
-    if (shared && (parts || !A[0])) return LPIPM_ERR_BAD_ARGUMENT;
+        if (!cc[i] || (!parts && !shared && !A[i]) || (b && !b[i])) return LPIPM_ERR_BAD_ARGUMENT;
+    if (shared && !parts && !A[0]) return LPIPM_ERR_BAD_ARGUMENT;
     if (m == 0) return LPIPM_UNCONSTRAINED;  // linear_program.rs:134-136
     if (n == 0 || m > (1u << 20) || n > (1u << 24) || n_slack > n || n_slack > m) return LPIPM_ERR_BAD_ARGUMENT;
     // The hint is only used if the last n_slack columns really are [I; 0] (ProblemBuilder::build
     // guarantees it, linear_program.rs:147-156); anything else is treated as a dense matrix.
-    if (!parts && (n_slack == n || count > 1 || shared)) n_slack = 0;
-    for (uint64_t i = 0; i < m && n_slack && !parts; ++i) {
-        const double* row = A[0] + i * lda + (n - n_slack);
-        for (uint64_t j = 0; j < n_slack; ++j)
-            if (row[j] != ((i == j) ? 1.0 : 0.0)) { n_slack = 0; break; }
-    }
+    if (!parts && !hint_verified && !slack_hint_holds(shared ? 1 : count, m, n, A, lda, n_slack)) n_slack = 0;
     LP_HIP(hipSetDevice(c->device));
     destroy_views(c); // half-batch views hold copies of the geometry and of the device pointers
     const uint64_t nx = n - n_slack;
@@ -541,32 +553,30 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
     c->p.va.done_chk = c->p.bt.done;
     std::vector<double> c0v((size_t)count, 0.0);          // must outlive the asynchronous copies below
     for (int i = 0; i < count; ++i) c0v[i] = c0 ? c0[i] : 0.0;
-    if (parts) {   // rows of A_ub, then rows of A_eq; b likewise; c = [c; 0] (the arena is zero)
+    if (parts) {   // rows of A_ub, then rows of A_eq (into the single LP's arena or the batch's one matrix); a single LP's b likewise
         const uint64_t m_ub = parts->m_ub, m_eq = m - m_ub;
         if (m_ub) {
             LP_HIP(hipMemcpy2DAsync(c->p.A, (size_t)npa * sizeof(double), parts->A_ub, (size_t)parts->lda_ub * sizeof(double),
                                     (size_t)nx * sizeof(double), (size_t)m_ub, hipMemcpyHostToDevice, st));
-            LP_HIP(hipMemcpyAsync((void*)c->p.va.b, parts->b_ub, m_ub * sizeof(double), hipMemcpyHostToDevice, st));
+            if (!shared) LP_HIP(hipMemcpyAsync((void*)c->p.va.b, parts->b_ub, m_ub * sizeof(double), hipMemcpyHostToDevice, st));
         }
         if (m_eq) {
             LP_HIP(hipMemcpy2DAsync(c->p.A + (size_t)m_ub * npa, (size_t)npa * sizeof(double), parts->A_eq,
                                     (size_t)parts->lda_eq * sizeof(double), (size_t)nx * sizeof(double), (size_t)m_eq,
                                     hipMemcpyHostToDevice, st));
-            LP_HIP(hipMemcpyAsync((void*)(c->p.va.b + m_ub), parts->b_eq, m_eq * sizeof(double), hipMemcpyHostToDevice, st));
+            if (!shared) LP_HIP(hipMemcpyAsync((void*)(c->p.va.b + m_ub), parts->b_eq, m_eq * sizeof(double), hipMemcpyHostToDevice, st));
         }
-        LP_HIP(hipMemcpyAsync((void*)c->p.va.c, cc[0], nx * sizeof(double), hipMemcpyHostToDevice, st));
-        LP_HIP(hipMemcpyAsync((void*)(c->p.va.S + S_C0), &c0v[0], sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    if (shared)
+    } else if (shared)
         LP_HIP(hipMemcpy2DAsync(c->p.A, (size_t)npa * sizeof(double), A[0], (size_t)lda * sizeof(double),
                                 (size_t)nx * sizeof(double), (size_t)m, hipMemcpyHostToDevice, st));
-    for (int i = 0; i < count && !parts; ++i) {
+    const uint64_t nc = parts ? nx : n;        // parts: c = [c; 0], and the arena is zero
+    for (int i = 0; i < count; ++i) {
         const size_t off = (size_t)i * c->p.bstride;
-        if (!shared)
+        if (!shared && !parts)
             LP_HIP(hipMemcpy2DAsync((char*)c->p.A + off, (size_t)npa * sizeof(double), A[i], (size_t)lda * sizeof(double),
                                     (size_t)nx * sizeof(double), (size_t)m, hipMemcpyHostToDevice, st));
-        LP_HIP(hipMemcpyAsync((char*)c->p.va.b + off, b[i], m * sizeof(double), hipMemcpyHostToDevice, st));
-        LP_HIP(hipMemcpyAsync((char*)c->p.va.c + off, cc[i], n * sizeof(double), hipMemcpyHostToDevice, st));
+        if (b) LP_HIP(hipMemcpyAsync((char*)c->p.va.b + off, b[i], m * sizeof(double), hipMemcpyHostToDevice, st));
+        LP_HIP(hipMemcpyAsync((char*)c->p.va.c + off, cc[i], nc * sizeof(double), hipMemcpyHostToDevice, st));
         LP_HIP(hipMemcpyAsync((char*)(c->p.va.S + S_C0) + off, &c0v[i], sizeof(double), hipMemcpyHostToDevice, st));
     }
     LP_HIP(hipStreamSynchronize(st));   // the caller's arrays and c0v are free again from here
@@ -604,13 +614,13 @@ static hipError_t ctx_gemv_n(lpipm_ctx* c, int nrhs, const double* W, const doub
     hipStream_t st = on ? on : c->rs.st;
     ++c->gemv_passes;
     hipError_t e = launch_gemv_n(c->p.A, c->p.npa, (int)c->p.m, c->p.npa, nrhs, W, c->p.np, add0, add1, Y, c->p.mp, st, 1.0, bt, c->p.shared_a);
-    if (e != hipSuccess || c->p.shared_a) return e;      // (no slack launch behind a shared A)
+    if (e != hipSuccess) return e;
     return launch_slack_n(c->p.ns, c->p.nx, nrhs, W, c->p.np, Y, c->p.mp, st, bt);
 }
 static hipError_t ctx_gemv_t(lpipm_ctx* c, int nrhs, const double* V, const Batch& bt) {
     ++c->gemv_passes;
     hipError_t e = launch_gemv_t(c->p.A, c->p.npa, c->p.mp, c->p.npa, nrhs, V, c->p.mp, c->p.ATpart, c->rs.st, c->p.np, bt, c->p.shared_a);
-    if (e != hipSuccess || c->p.shared_a) return e;      // (no slack launch behind a shared A)
+    if (e != hipSuccess) return e;
     return launch_slack_t(c->p.ns, c->p.nx, nrhs, c->p.nsplit, V, c->p.mp, c->p.ATpart, c->p.np, c->rs.st, bt);
 }
 // both in one read of A: chunk slabs of A.w into AxPart (gemv_dual_chunks(npa) of them), row-split slabs of A^T.v into ATpart
@@ -618,9 +628,8 @@ static hipError_t ctx_gemv_dual(lpipm_ctx* c, const double* W, const double* V, 
     ++c->gemv_passes;
     hipError_t e = launch_gemv_dual(c->p.A, c->p.npa, c->p.mp, c->p.npa, W, V, AxPart, c->p.ATpart, c->p.np, c->rs.st, bt, c->p.shared_a);
     if (e != hipSuccess) return e;
-    e = launch_slack_n(c->p.ns, c->p.nx, 1, W, c->p.np, AxPart, c->p.mp, c->rs.st, bt);          // into chunk slab 0
-    if (e != hipSuccess) return e;
-    return launch_slack_t(c->p.ns, c->p.nx, 1, c->p.nsplit, V, c->p.mp, c->p.ATpart, c->p.np, c->rs.st, bt);
+    // the slack terms of both products in one launch: w_s into chunk slab 0, v into row-split slab 0 (zeros into the others)
+    return launch_slack_dual(c->p.ns, c->p.nx, c->p.nsplit, W, V, AxPart, c->p.ATpart, c->p.np, c->rs.st, bt);
 }
 
 // M = A . diag(dinv) . A^T, lower tiles (newton_equations.rs:54-57); a second copy of it goes to M0 (the matrix the
@@ -1160,13 +1169,32 @@ static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const XOut& xo, con
 
 extern "C" int lpipm_upload_lockstep(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* const* A,
                                      const double* const* b, const double* const* cc, const double* c0) {
+    return lpipm_upload_lockstep_slack(c, count, m, n, A, b, cc, c0, 0);
+}
+extern "C" int lpipm_upload_lockstep_slack(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* const* A,
+                                           const double* const* b, const double* const* cc, const double* c0, uint64_t n_slack) {
     if (count < 1 || count > 4096) return LPIPM_ERR_BAD_ARGUMENT;
-    return upload_impl(c, (int)count, m, n, A, n, b, cc, c0, 0);
+    return upload_impl(c, (int)count, m, n, A, n, b, cc, c0, n_slack);
 }
 extern "C" int lpipm_upload_lockstep_shared(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* A, uint64_t lda,
                                             const double* const* b, const double* const* cc, const double* c0) {
+    return lpipm_upload_lockstep_shared_slack(c, count, m, n, A, lda, b, cc, c0, 0);
+}
+extern "C" int lpipm_upload_lockstep_shared_slack(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* A, uint64_t lda,
+                                                  const double* const* b, const double* const* cc, const double* c0,
+                                                  uint64_t n_slack) {
     if (count < 1 || count > 4096 || !A) return LPIPM_ERR_BAD_ARGUMENT;
-    return upload_impl(c, (int)count, m, n, &A, lda, b, cc, c0, 0, nullptr, true);
+    return upload_impl(c, (int)count, m, n, &A, lda, b, cc, c0, n_slack, nullptr, true);
+}
+extern "C" int lpipm_upload_lockstep_shared_ub_eq(lpipm_ctx* c, uint64_t count, uint64_t n, uint64_t m_ub, const double* A_ub,
+                                                  uint64_t lda_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq,
+                                                  const double* const* b, const double* const* cc, const double* c0) {
+    if (count < 1 || count > 4096) return LPIPM_ERR_BAD_ARGUMENT;
+    if (!b || !cc) return LPIPM_ERR_BAD_ARGUMENT;
+    if (m_ub + m_eq == 0) return LPIPM_UNCONSTRAINED;                       // linear_program.rs:134-136
+    if (n == 0 || (m_ub && (!A_ub || lda_ub < n)) || (m_eq && (!A_eq || lda_eq < n))) return LPIPM_ERR_BAD_ARGUMENT;
+    const UploadParts parts{m_ub, A_ub, lda_ub, nullptr, A_eq, lda_eq, nullptr};
+    return upload_impl(c, (int)count, m_ub + m_eq, n + m_ub, nullptr, 0, b, cc, c0, m_ub, &parts, true);
 }
 extern "C" int lpipm_get_resident_bytes(const lpipm_ctx* c, uint64_t* bytes_out) {
     if (!c || !bytes_out) return LPIPM_ERR_BAD_ARGUMENT;
@@ -1187,10 +1215,11 @@ extern "C" int lpipm_solve_lockstep_device(lpipm_ctx* c, const lpipm_opts* o, vo
 
 // Bytes one member of a lockstep batch of this shape occupies: the real layout (plan_adat and a measuring pass of
 // layout_problem over the bare geometry), not a formula that drifts from it.
-static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, uint64_t m, uint64_t n) {
+// n_slack: the member's (verified) structural hint -- its slack columns are not resident.
+static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, uint64_t m, uint64_t n, uint64_t n_slack) {
     Problem t;
     t.B = 32;
-    t.mp = (int)round_up(m, NB); t.np = (int)round_up(n, BK); t.npa = t.np;
+    t.mp = (int)round_up(m, NB); t.np = (int)round_up(n, BK); t.npa = (int)round_up(n - n_slack, BK);
     t.nsplit = t.mp / GEMVT_ROWS;
     const AdatPlan ap = plan_adat(t.mp, t.npa, t.B, c->num_cu, c->world, c->units_env);
     FactorPlan fp;
@@ -1207,21 +1236,35 @@ static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, uint64_t m, uint64_t n) 
 //     each driven by its own host thread -- solve different members at the same time; independent
 //     streams need no cross-stream synchronisation.  Members are handed out through an atomic counter.
 // Every member's result depends only on its own inputs.
-static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uint64_t* n,
+// n_slack (nullable = all 0): member i's structural hint (lpipm_upload_slack).  Each is verified here first; members are
+// grouped by the hint that holds as well as by shape, and both upload paths pass it on.
+static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uint64_t* n, const uint64_t* n_slack,
                       const double* const* A, const double* const* b, const double* const* cc,
                       const double* c0, const lpipm_opts* o, const XOut& xo,
                       double* fun_out, uint64_t* iterations_out, int32_t* status_out) {
     if (!c || !o || (count && (!m || !n || !A || !b || !cc || !xo.valid() || !status_out)))
         return LPIPM_ERR_BAD_ARGUMENT;
+    // the hint that holds, per member: verified here, once (the uploads below are told so).  A hint larger than the member's
+    // n or m is that member's error, as it is lpipm_upload_slack's: the member is refused here and takes no further part.
+    std::vector<uint64_t> ns(count, 0);
+    std::vector<char> taken(count, 0);              // in a lockstep group, or refused
+    for (uint64_t i = 0; i < count && n_slack; ++i) {
+        if (m[i] == 0 || n_slack[i] == 0 || !A[i]) continue;          // (Unconstrained / a null A: the upload's answer)
+        if (n_slack[i] > n[i] || n_slack[i] > m[i]) {
+            taken[i] = 1;
+            status_out[i] = LPIPM_ERR_BAD_ARGUMENT;
+            if (fun_out) fun_out[i] = NAN;
+            if (iterations_out) iterations_out[i] = 0;
+        } else if (slack_hint_holds(1, m[i], n[i], &A[i], n[i], n_slack[i])) ns[i] = n_slack[i];
+    }
     std::vector<uint64_t> rest;                      // members left to the one-by-one path
     if (c->lockstep_max != 0 && o->solver_type == LPIPM_SOLVER_CHOLESKY) {
         LP_HIP(hipSetDevice(c->device));
-        std::vector<char> taken(count, 0);
         for (uint64_t i = 0; i < count; ++i) {
             if (taken[i]) continue;
             std::vector<uint64_t> grp;
             for (uint64_t j = i; j < count; ++j)
-                if (!taken[j] && m[j] == m[i] && n[j] == n[i]) grp.push_back(j);
+                if (!taken[j] && m[j] == m[i] && n[j] == n[i] && ns[j] == ns[i]) grp.push_back(j);
             if (grp.size() < 2) continue;
             for (uint64_t j : grp) taken[j] = 1;
             // chunk size: the configured maximum, and what fits in ~60 % of the free memory (two chunks are
@@ -1229,7 +1272,7 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             size_t free_b = 0, total_b = 0;
             LP_HIP(hipMemGetInfo(&free_b, &total_b));
             free_b += c->p.arena_bytes;                // the current arena is released before the next one is made
-            const double per_lp = (double)lockstep_bytes_per_lp(c, m[i], n[i]);     // the real arena layout of one member
+            const double per_lp = (double)lockstep_bytes_per_lp(c, m[i], n[i], ns[i]);     // the real arena layout of one member
             size_t chunk;
             if (c->lockstep_max > 0) chunk = (size_t)c->lockstep_max;
             else if (grp.size() > 32) chunk = 32;
@@ -1268,7 +1311,8 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             }
             auto upload_chunk = [&](lpipm_ctx* w, const Chunk& ch) -> int {
                 (void)hipSetDevice(w->device);
-                return upload_impl(w, (int)ch.g, m[i], n[i], ch.A.data(), n[i], ch.b.data(), ch.c.data(), ch.c0.data(), 0);
+                return upload_impl(w, (int)ch.g, m[i], n[i], ch.A.data(), n[i], ch.b.data(), ch.c.data(), ch.c0.data(), ns[i],
+                                   nullptr, false, true);
             };
             int rc_up = chunks.empty() ? LPIPM_OK : upload_chunk(pipe[0], chunks[0]);
             for (size_t q = 0; q < chunks.size(); ++q) {
@@ -1298,7 +1342,8 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
         for (uint64_t i = 0; i < count; ++i)
             if (!taken[i]) rest.push_back(i);
     } else {
-        for (uint64_t i = 0; i < count; ++i) rest.push_back(i);
+        for (uint64_t i = 0; i < count; ++i)
+            if (!taken[i]) rest.push_back(i);
     }
     if (rest.empty()) return LPIPM_OK;
     int nworkers = c->batch_concurrency;
@@ -1326,7 +1371,8 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             const uint64_t k = next.fetch_add(1);
             if (k >= rest.size() || fatal.load() != LPIPM_OK) break;
             const uint64_t i = rest[k];
-            int rc = lpipm_upload(w, m[i], n[i], A[i], n[i], b[i], cc[i], c0 ? c0[i] : 0.0);
+            const double c0i = c0 ? c0[i] : 0.0;
+            int rc = upload_impl(w, 1, m[i], n[i], &A[i], n[i], &b[i], &cc[i], &c0i, ns[i], nullptr, false, true);
             double fun = NAN;
             uint64_t it = 0;
             if (rc == LPIPM_OK)
@@ -1350,7 +1396,7 @@ extern "C" int lpipm_solve_batch(lpipm_ctx* c, uint64_t count, const uint64_t* m
                                  const double* c0, const lpipm_opts* o, double* const* x_slack_out,
                                  double* fun_out, uint64_t* iterations_out, int32_t* status_out) {
     XOut xo; xo.host = x_slack_out;
-    return batch_impl(c, count, m, n, A, b, cc, c0, o, xo, fun_out, iterations_out, status_out);
+    return batch_impl(c, count, m, n, nullptr, A, b, cc, c0, o, xo, fun_out, iterations_out, status_out);
 }
 extern "C" int lpipm_solve_batch_device(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uint64_t* n,
                                         const double* const* A, const double* const* b, const double* const* cc,
@@ -1360,7 +1406,22 @@ extern "C" int lpipm_solve_batch_device(lpipm_ctx* c, uint64_t count, const uint
     for (uint64_t i = 0; i < count && n; ++i)
         if (n[i] > row_stride) return LPIPM_ERR_BAD_ARGUMENT;
     XOut xo; xo.dev = (char*)x_dev_out; xo.stride_bytes = row_stride * sizeof(double);
-    return batch_impl(c, count, m, n, A, b, cc, c0, o, xo, fun_out, iterations_out, status_out);
+    return batch_impl(c, count, m, n, nullptr, A, b, cc, c0, o, xo, fun_out, iterations_out, status_out);
+}
+
+extern "C" int lpipm_solve_batch_slack(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uint64_t* n, const uint64_t* n_slack,
+                                       const double* const* A, const double* const* b, const double* const* cc,
+                                       const double* c0, const lpipm_opts* o, double* const* x_slack_out, void* x_dev_out,
+                                       uint64_t row_stride, double* fun_out, uint64_t* iterations_out, int32_t* status_out) {
+    if ((x_slack_out != nullptr) == (x_dev_out != nullptr)) return LPIPM_ERR_BAD_ARGUMENT;
+    XOut xo;
+    if (x_slack_out) xo.host = x_slack_out;
+    else {
+        for (uint64_t i = 0; i < count && n; ++i)
+            if (n[i] > row_stride) return LPIPM_ERR_BAD_ARGUMENT;
+        xo.dev = (char*)x_dev_out; xo.stride_bytes = row_stride * sizeof(double);
+    }
+    return batch_impl(c, count, m, n, n_slack, A, b, cc, c0, o, xo, fun_out, iterations_out, status_out);
 }
 
 extern "C" int lpipm_set_batch_lockstep(lpipm_ctx* c, int max_group) {
