@@ -75,7 +75,7 @@ typedef struct {
     double   gemv_ms;      /* passes over A (GEMV-N / GEMV-T)                           */
     double   vec_ms;       /* O(n) vector / scalar kernels + status read-back          */
     double   total_ms;     /* first kernel to last kernel of the solve                 */
-    uint64_t adat_launches;
+    uint64_t adat_launches; /* A.D.A^T launches made: `iterations`, less one when iteration 1 started from the kept factor */
     uint64_t iterations;
     uint64_t gemv_passes;  /* passes over A inside gemv_ms (a 2-vector pass reads A once and counts once) */
 } lpipm_phase_times;
@@ -127,6 +127,26 @@ int lpipm_upload_slack(lpipm_ctx* ctx, uint64_t m, uint64_t n, const double* A, 
 int lpipm_upload_ub_eq(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub,
                        const double* b_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq, const double* b_eq,
                        const double* c, double c0);
+
+/* New b and c for the resident problem of lpipm_upload / lpipm_upload_slack: b[m] and c[n] in that upload's own form (c with
+ * its slack entries).  A stays where it is, so a sweep over right-hand sides or costs, or a sequence of LPs over one
+ * constraint matrix, pays for the upload of A once -- and, with it, for the first iteration's factor (below), which depends
+ * on A alone and is kept.  The next lpipm_solve is bit-identical to lpipm_upload(A, b, c) + lpipm_solve; c0 stays.
+ * LPIPM_ERR_NO_PROBLEM without an upload; LPIPM_ERR_UNSUPPORTED after lpipm_upload_ub_eq (its b and c come in parts), for a
+ * lockstep batch and for a column-split context. */
+int lpipm_update_vectors(lpipm_ctx* ctx, const double* b, const double* c);
+
+/* Every solve starts from x = z = 1 (feasible_point.rs:24-31), so the normal matrix of its first iteration is A.A^T (+ I on
+ * the rows of a structural slack block): that matrix, its Cholesky factor, the inverses of the factor's diagonal blocks and
+ * the pivot-failure word are functions of A alone.  The Cholesky arm keeps them per upload -- a single LP's, and every
+ * member's of a lockstep batch -- and every solve after the first on the same upload starts from them instead of running
+ * A.D.A^T and the factorisation again.  No result changes by a bit.  Any upload drops what is kept.  Not used by the QR arms,
+ * column-split contexts, lpipm_solve_f32 and lpipm_solve_batch (which uploads on every call).
+ * Cost per resident LP, with mp = m rounded up to 128 and s_k the widths of the diagonal super-blocks (512 each up to
+ * mp = 2048, 1024 beyond; the last one what is left of mp):  8 mp^2 + 16 sum_k s_k^2 + 4096 bytes (lpipm_get_resident_bytes
+ * counts them).  on = 0 gives that memory back: the kept factor is no longer used from the next solve on, and the buffers go
+ * (or, with on = 1 again, come back) with the next upload.  Default: on. */
+int lpipm_set_first_factor_cache(lpipm_ctx* ctx, int on);
 
 /* InteriorPoint::solve_normal_form + the `fun` of solve (mod.rs:199-240, :165).
  *   x_slack_out[n] : x / tau  (mod.rs:231); ALSO filled for LPIPM_ITERATION_LIMIT (mod.rs:237-239)

@@ -277,6 +277,22 @@ class Context:
         self.m, self.n = m, n
         return self
 
+    def update_vectors(self, b, c):
+        """New b and c for the resident single LP of upload_arrays (lpipm_update_vectors), in that upload's own form; A --
+        and the first iteration's factor kept with it -- stays.  The next solve_raw is bit-identical to a fresh
+        upload_arrays(A, b, c) + solve_raw."""
+        b, c = _f64(b), _f64(c)
+        if b.shape != (self.m,) or c.shape != (self.n,):
+            raise IncompatibleInputDimensions()
+        _raise_for(_capi.lib().lpipm_update_vectors(self._h, _p(b), _p(c)))
+        return self
+
+    def set_first_factor_cache(self, on: bool = True):
+        """Whether the first iteration's factor (a function of A alone) is kept per upload and reused by every later solve
+        on it (lpipm_set_first_factor_cache; default on).  Off gives its memory back at the next upload."""
+        _raise_for(_capi.lib().lpipm_set_first_factor_cache(self._h, int(bool(on))))
+        return self
+
     def set_collective(self, rank: int, world: int, collective):
         """`collective.cfn` is an lpipm_allreduce_fn thunk (lp_amd.colsplit.TorchCollective); kept alive here."""
         self._collective = collective

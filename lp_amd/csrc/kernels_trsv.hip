@@ -55,7 +55,7 @@ int plan_merges(int sb, int lo, int hi, std::vector<Merge>& out, size_t& tcursor
 }  // namespace
 
 hipError_t factor_plan_create(FactorPlan& plan, const double* L, int64_t ld, int mp, Arena& arena, bool build,
-                              hipStream_t st, int super_w, int merge_edge) {
+                              hipStream_t st, int super_w, int merge_edge, const FactorPlan* scratch_of) {
     factor_plan_destroy(plan);
     plan.mp = mp;
     plan.super_w = super_w;
@@ -77,9 +77,10 @@ hipError_t factor_plan_create(FactorPlan& plan, const double* L, int64_t ld, int
         const int lvl = plan_merges((int)i, 0, plan.sbs[i].size / NB, merges, tcursor);
         if (lvl > maxlvl) maxlvl = lvl;
     }
-    double* tws = arena.take<double>(tcursor);
+    double* tws = scratch_of ? scratch_of->tws : arena.take<double>(tcursor);
+    plan.tws = tws;
     // slabs of the backward sweep's transposed panel products: (rows below / 128) x 2 rhs x SUPER
-    plan.tpart = arena.take<double>((size_t)(mp / GEMVT_ROWS + 1) * 2 * super_w);
+    plan.tpart = scratch_of ? scratch_of->tpart : arena.take<double>((size_t)(mp / GEMVT_ROWS + 1) * 2 * super_w);
     if (!build) return hipSuccess;
 
     std::vector<GemmTileDesc> descs;
@@ -173,6 +174,7 @@ void factor_plan_destroy(FactorPlan& plan) {
     plan.groups.clear();
     plan.descs_dev = nullptr;
     plan.tpart = nullptr;
+    plan.tws = nullptr;
     plan.mp = 0;
 }
 

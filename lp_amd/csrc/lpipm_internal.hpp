@@ -216,6 +216,7 @@ struct FactorPlan {
     std::vector<std::pair<int, int>> stages;     // (first descriptor, count) per launch, in order
     std::vector<MergeGroup> groups;              // the stages cut by outer panel (stage by stage, panels ascending inside one)
     double* tpart = nullptr;                     // gemv_t slabs of the backward sweep
+    double* tws = nullptr;                       // workspace of the merges (T^T of every merge)
     // 128-block k of the factorisation -> where its inverse / transposed inverse go, and their ld
     double* blk_inv(int k) const;
     double* blk_invT(int k) const;
@@ -224,8 +225,10 @@ struct FactorPlan {
 // Takes the inverse storage for an mp x mp factor living at (L, ld) from the arena (which must be zeroed:
 // the never-written halves of the triangular inverses are read as zeros) and, when `build`, uploads the
 // merge descriptors.  build == false: sizing pass over a measuring arena, nothing is allocated.
+// scratch_of (nullable): a plan of the same mp, widths and arena that is never in use at the same time as this one; the new
+// plan then takes only the inverse storage from the arena and works in that plan's merge workspace and gemv_t slabs.
 hipError_t factor_plan_create(FactorPlan& plan, const double* L, int64_t ld, int mp, Arena& arena, bool build, hipStream_t st,
-                              int super_w = SUPER, int merge_edge = 128);
+                              int super_w = SUPER, int merge_edge = 128, const FactorPlan* scratch_of = nullptr);
 void factor_plan_destroy(FactorPlan& plan);
 
 // ---------------------------------------------------------------- Cholesky (kernels_potrf.hip)

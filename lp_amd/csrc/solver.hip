@@ -86,6 +86,13 @@ struct Problem {
     double* tau = nullptr;               // Householder scalars of the QR arms
     double *A = nullptr, *M = nullptr, *Y = nullptr, *ATpart = nullptr, *xout = nullptr;
     double *M0 = nullptr, *R0 = nullptr, *Rho = nullptr, *symv_ws = nullptr;   // refinement of the Cholesky solve
+    // The first iteration's factor (see lpipm_ctx::first_valid): a second M with a second factor plan's inverses and a copy
+    // of the pivot-failure word, at the end of every LP's arena.  keep: this layout has them.
+    bool keep = false;
+    double* M1 = nullptr;
+    const FactorPlan* factor1 = nullptr; // lpipm_ctx::plan1 of the uploading context
+    int32_t* info1 = nullptr;
+    bool from_parts = false;     // uploaded as ub / eq blocks (lpipm_upload_ub_eq): b and c are not in the caller's slack form
     AdatRes adat;                // what the A.D.A^T launches use on the device (kernels_adat.hip); adat.ngroups() > 0: one LP split by
                                  //   columns over ranks, M is reduced column group by column group behind the running launch
     double* gs = nullptr;        // 8 doubles: sums / minima that must be reduced across ranks (n-split mode)
@@ -102,6 +109,17 @@ struct lpipm_ctx {
     std::vector<void*> kallocs;  // buffers of the stand-alone kernel entry points
     FactorPlan plan, kplan;
     double* ktau = nullptr;
+    // Iteration 1 of every solve starts from x = z = 1 (k_blind_start), so its dinv is exactly 1 and its normal matrix is
+    // A.A^T (+ I on the slack rows): that matrix, its factor, the inverses and the pivot-failure word depend on A alone.  The
+    // Cholesky arm of a resident problem therefore factors iteration 1 into a second set of buffers (Problem::M1, plan1, info1)
+    // and every later solve on the same upload starts from them instead of running A.D.A^T and the factorisation again.
+    FactorPlan plan1;
+    bool first_cache = true;     // lpipm_set_first_factor_cache
+    bool first_valid = false;    // M1 / plan1 / info1 hold iteration 1 of this upload (every member's); dropped by any upload.  A
+                                 //   half-batch view holds the parent's value for the length of one solve
+    bool first_done = false;     // the last solve of this context (or view) got through its iteration 1
+    bool on_first = false;       // the iteration being enqueued works in M1 / plan1 ...
+    bool skip_factor = false;    //   ... which already hold its factor: no A.D.A^T, no factorisation
     int units_env = 1;                   // LPIPM_ADAT_UNITS=0: the round-2 kernel (data-parallel tiles + fix-up launch) everywhere
     PotrfLookahead la;                   // trailing updates of one factorisation beside the next panel's chain (launch_potrf)
     // a lockstep batch as two half-batches driven by two host threads on two streams (solve_lockstep): views of this
@@ -386,6 +404,7 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     if (c->ev_c0) (void)hipEventDestroy(c->ev_c0);
     if (c->ev_c1) (void)hipEventDestroy(c->ev_c1);
     factor_plan_destroy(c->plan);
+    factor_plan_destroy(c->plan1);
     factor_plan_destroy(c->kplan);
     if (c->la.side) { (void)hipStreamSynchronize(c->la.side); (void)hipStreamDestroy(c->la.side); }
     for (hipEvent_t e : c->la.ev_chain) (void)hipEventDestroy(e);
@@ -417,9 +436,19 @@ static int merge_edge_for(int) {
 // Per-LP device state: one pass over a measuring arena sizes it, a second pass over the real one places it.
 // Every LP of a lockstep batch gets the same layout, `bstride` bytes after the previous LP's.
 static void bind_status_pinned(lpipm_ctx* c, bool allow);
-// In: p's geometry (mp, np, npa, nsplit, B, shared_a), the A.D.A^T plan and whether the context refines its solves.  Out: p's
-// device pointers and `plan`, the factor plan they refer to.
-static int layout_problem(Problem& p, FactorPlan& plan, const AdatPlan& ap, int refine, Arena& ar, bool build, hipStream_t st) {
+// In: p's geometry (mp, np, npa, nsplit, B, shared_a), the A.D.A^T plan, whether the context refines its solves and whether
+// the first iteration's factor is kept (`keep`).  Out: p's device pointers and `plan` (and `plan1`), the factor plans they
+// refer to.
+// The kept factor is the last block of an LP's arena, on 4096-byte bounds: mp x mp doubles of M, two s x s inverses per
+// diagonal super-block of width s, and one page for the pivot-failure word -- first_factor_bytes(mp) in all, a function of mp
+// alone.  Its plan works in the first plan's merge workspace and gemv_t slabs: the two are never in use at the same time.
+static size_t first_factor_bytes(int mp, int super_w) {
+    size_t bytes = (size_t)mp * mp * sizeof(double) + 4096;
+    for (int r0 = 0; r0 < mp; r0 += super_w) { const size_t s = (size_t)(mp - r0 < super_w ? mp - r0 : super_w); bytes += 2 * s * s * sizeof(double); }
+    return bytes;
+}
+static int layout_problem(Problem& p, FactorPlan& plan, FactorPlan& plan1, const AdatPlan& ap, int refine, bool keep, Arena& ar,
+                          bool build, hipStream_t st) {
     VecArgs& v = p.va;
     const size_t mp = (size_t)p.mp, np = (size_t)p.np;
     p.A = p.shared_a ? nullptr : ar.take<double>(mp * p.npa);     // a shared A has its own allocation (upload_impl)
@@ -456,6 +485,18 @@ static int layout_problem(Problem& p, FactorPlan& plan, const AdatPlan& ap, int 
     p.gs = ar.take<double>(8);
     p.xout = ar.take<double>(np);
     adat_take(p.adat, ap, ar);
+    p.keep = keep;
+    p.M1 = nullptr; p.factor1 = nullptr; p.info1 = nullptr;
+    if (keep) {
+        ar.off = (size_t)round_up(ar.off, 4096);
+        const size_t begin = ar.off;
+        p.M1 = ar.take<double>(mp * mp);
+        LP_HIP(factor_plan_create(plan1, p.M1, p.mp, p.mp, ar, build, st, super_for(p.mp), merge_edge_for(p.B), &plan));
+        p.factor1 = &plan1;
+        p.info1 = ar.take<int32_t>(1);
+        ar.off = (size_t)round_up(ar.off, 4096);
+        if (ar.off - begin != first_factor_bytes(p.mp, super_for(p.mp))) return LPIPM_ERR_BAD_ARGUMENT;   // (the documented size)
+    } else factor_plan_destroy(plan1);
     return LPIPM_OK;
 }
 
@@ -484,7 +525,7 @@ struct UploadParts { uint64_t m_ub; const double* A_ub; uint64_t lda_ub; const d
 // shared: A[0] is the one matrix of all `count` LPs (lpipm_upload_lockstep_shared; A holds one entry).
 static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const double* const* A, uint64_t lda,
                        const double* const* b, const double* const* cc, const double* c0, uint64_t n_slack,
-                       const UploadParts* parts = nullptr, bool shared = false, bool hint_verified = false) {
+                       const UploadParts* parts = nullptr, bool shared = false, bool hint_verified = false, bool keep_ok = true) {
     if (!c || count < 1 || !cc) return LPIPM_ERR_BAD_ARGUMENT;
     if (!parts && (!A || !b || lda < n)) return LPIPM_ERR_BAD_ARGUMENT;
     if (parts && (shared ? !b : count != 1)) return LPIPM_ERR_BAD_ARGUMENT;
@@ -498,16 +539,21 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
     if (!parts && !hint_verified && !slack_hint_holds(shared ? 1 : count, m, n, A, lda, n_slack)) n_slack = 0;
     LP_HIP(hipSetDevice(c->device));
     destroy_views(c); // half-batch views hold copies of the geometry and of the device pointers
+    c->first_valid = false;   // whatever is kept belongs to the matrix that is being replaced
+    // keep_ok == false: an upload that is solved once (lpipm_solve_batch) or never through the kept factor (column split)
+    const bool keep = keep_ok && c->first_cache && c->refine <= 0;
     const uint64_t nx = n - n_slack;
     const int mp = (int)round_up(m, NB), np = (int)round_up(n, BK), npa = (int)round_up(nx, BK);
     hipStream_t st = c->rs.st;
-    if (!c->p.has_problem || mp != c->p.mp || np != c->p.np || npa != c->p.npa || count != c->p.B || shared != c->p.shared_a) {
+    if (!c->p.has_problem || mp != c->p.mp || np != c->p.np || npa != c->p.npa || count != c->p.B || shared != c->p.shared_a ||
+        keep != c->p.keep) {
         LP_HIP(hipStreamSynchronize(st));
         if (c->p.arena) { LP_HIP(hipFree(c->p.arena)); c->p.arena = nullptr; }
         if (c->p.a_shared) { LP_HIP(hipFree(c->p.a_shared)); c->p.a_shared = nullptr; c->p.a_shared_bytes = 0; }
         c->p.shared_a = shared;
         adat_lists_destroy(c->p.adat);
         factor_plan_destroy(c->plan);
+        factor_plan_destroy(c->plan1);
         c->p.has_problem = false;
         c->p.mp = mp; c->p.np = np; c->p.npa = npa; c->p.B = count;
         c->p.nsplit = mp / GEMVT_ROWS;
@@ -516,14 +562,14 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
         if (c->p.nblk > RED_STRIDE) c->p.nblk = RED_STRIDE;
         c->ap = plan_adat(mp, npa, count, c->num_cu, c->world, c->units_env);
         Arena measure;
-        LP_TRY(layout_problem(c->p, c->plan, c->ap, c->refine, measure, false, st));
+        LP_TRY(layout_problem(c->p, c->plan, c->plan1, c->ap, c->refine, keep, measure, false, st));
         c->p.bstride = round_up(measure.off, 4096);
         c->p.arena_bytes = c->p.bstride * (size_t)count;
         LP_HIP(hipMalloc((void**)&c->p.arena, c->p.arena_bytes));
         LP_HIP(hipMemsetAsync(c->p.arena, 0, c->p.arena_bytes, st));
         Arena real;
         real.base = c->p.arena;
-        LP_TRY(layout_problem(c->p, c->plan, c->ap, c->refine, real, true, st));
+        LP_TRY(layout_problem(c->p, c->plan, c->plan1, c->ap, c->refine, keep, real, true, st));
         if (shared) {              // the one A of the batch: mp x npa like an arena's, zero padding
             c->p.a_shared_bytes = (size_t)mp * (size_t)npa * sizeof(double);
             LP_HIP(hipMalloc((void**)&c->p.a_shared, c->p.a_shared_bytes));
@@ -543,6 +589,7 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
     }
     c->p.m = m; c->p.n = n;
     c->p.ns = (int)n_slack; c->p.nx = (int)nx;
+    c->p.from_parts = parts != nullptr;
     c->p.va.n = (int)n; c->p.va.m = (int)m;
     c->p.va.n_total = (long long)n; c->p.va.gs = nullptr; c->colsplit = false;   // lpipm_upload_nsplit overrides
     // A single LP's loop ends on the host, so its kernels need not test the done word (one dependent load
@@ -634,9 +681,21 @@ static hipError_t ctx_gemv_dual(lpipm_ctx* c, const double* W, const double* V, 
 
 // M = A . diag(dinv) . A^T, lower tiles (newton_equations.rs:54-57); a second copy of it goes to M0 (the matrix the
 // refined Cholesky solves take their residuals against: M itself is factorised in place)
+// The matrix and the factor plan of the iteration being enqueued: the kept first factor's in iteration 1 of a solve that
+// uses it (lpipm_ctx::on_first), the working ones otherwise.
+static double* cur_M(const lpipm_ctx* c) { return c->on_first ? c->p.M1 : c->p.M; }
+static const FactorPlan& cur_factor(const lpipm_ctx* c) { return c->on_first ? *c->p.factor1 : *c->p.factor; }
+// The pivot-failure words of the LPs this context covers, between the solver's word and its kept copy (device to device).
+static hipError_t copy_info(lpipm_ctx* c, int32_t* dst, const int32_t* src) {
+    const size_t off = (size_t)c->p.bt.first * c->p.bstride;
+    char* d = (char*)dst + off;
+    const char* s = (const char*)src + off;
+    return c->p.B == 1 ? hipMemcpyAsync(d, s, sizeof(int32_t), hipMemcpyDeviceToDevice, c->rs.st)
+                       : hipMemcpy2DAsync(d, c->p.bstride, s, c->p.bstride, sizeof(int32_t), (size_t)c->p.B, hipMemcpyDeviceToDevice, c->rs.st);
+}
 static AdatLaunch adat_launch(lpipm_ctx* c, const Batch& bt) {
     AdatLaunch a{};
-    a.A = c->p.A; a.lda = c->p.npa; a.dinv = c->p.va.dinv; a.M = c->p.M; a.ldm = c->p.mp;
+    a.A = c->p.A; a.lda = c->p.npa; a.dinv = c->p.va.dinv; a.M = cur_M(c); a.ldm = c->p.mp;
     a.M2 = c->refine > 0 ? c->p.M0 : nullptr;                                // only the refined solves need M itself
     a.K = c->p.npa; a.diag_pad_from = (int)c->p.m; a.batch = bt; a.shared_a = c->p.shared_a;
     return a;
@@ -645,7 +704,7 @@ static hipError_t run_adat(lpipm_ctx* c, const Batch& bt) {
     bool second_copy = false;
     hipError_t e = launch_adat(c->ap, c->p.adat, adat_launch(c, bt), false, c->rs.st, &second_copy);
     if (e != hipSuccess) return e;
-    e = launch_slack_diag(c->p.ns, c->p.nx, c->p.va.dinv, c->p.M, c->p.mp, c->rs.st, bt);   // + diag(D_slack)
+    e = launch_slack_diag(c->p.ns, c->p.nx, c->p.va.dinv, cur_M(c), c->p.mp, c->rs.st, bt);   // + diag(D_slack)
     if (e != hipSuccess) return e;
     if (c->refine <= 0) return hipSuccess;
     if (second_copy) return launch_slack_diag(c->p.ns, c->p.nx, c->p.va.dinv, c->p.M0, c->p.mp, c->rs.st, bt);
@@ -658,7 +717,7 @@ static hipError_t run_adat(lpipm_ctx* c, const Batch& bt) {
 // precision, one read of the lower triangle);  v = v0 + L^-T L^-1 rho.  R: nrhs x mp, in/out.
 static int chol_solve_refined(lpipm_ctx* c, int nrhs, double* R, const Batch& bt) {
     hipStream_t st = c->rs.st;
-    if (!c->refine_now) { LP_HIP(launch_chol_solve(c->p.M, c->p.mp, *c->p.factor, nrhs, R, c->p.Y, st, bt)); return LPIPM_OK; }
+    if (!c->refine_now) { LP_HIP(launch_chol_solve(cur_M(c), c->p.mp, cur_factor(c), nrhs, R, c->p.Y, st, bt)); return LPIPM_OK; }
     // the refinement's launches skip an LP whose own word says so (a finished one, or one that does not need it yet)
     const Batch br = c->refine == 2 ? bt : Batch{bt.count, bt.stride, c->p.va.skip_refine, bt.first};
     vec_rows_copy(c->p.mp, nrhs, c->p.R0, R, st, br);
@@ -754,6 +813,7 @@ static int enqueue_head(lpipm_ctx* c) {
     if (c->pred_done) c->pred_done = false;       // the residual launch in front of this head has done it (enqueue_residuals)
     else vec_pred_setup(vh, st);
     prof_mark(c, T_VEC, true);
+    if (c->skip_factor) return LPIPM_OK;          // iteration 1 on a kept factor: its M is already there, factored
     if (c->colsplit && c->world > 1 && c->p.adat.ngroups() > 0 && c->st_c) {
         // n-split, M = sum_g A_g D_g A_g^T, PIPELINED: one A.D.A^T launch in column-group-major order on the solver's stream;
         // the workgroup that completes a group's last tile bumps the group's word; on the communication stream a one-wave
@@ -808,7 +868,7 @@ struct PredictorBeside {
         VecArgs& v = c->p.va;
         if (sb < 0) return ctx_gemv_n(c, 2, v.W, v.b, v.rP, v.R, c->p.bt, side);     // :220
         b->fwd_done = sb + 1;
-        return launch_chol_solve(c->p.M, c->p.mp, *c->p.factor, 2, v.R, c->p.Y, side, c->p.bt, SolveSteps{sb, sb + 1, false});
+        return launch_chol_solve(cur_M(c), c->p.mp, cur_factor(c), 2, v.R, c->p.Y, side, c->p.bt, SolveSteps{sb, sb + 1, false});
     }
 };
 
@@ -826,10 +886,14 @@ static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
     PredictorBeside pb{c};
     PotrfBeside beside{PredictorBeside::at, &pb};
     const bool may_beside = chol && !c->colsplit && bt.count == 1 && c->refine <= 0;
-    if (chol) LP_HIP(launch_potrf(c->p.M, c->p.mp, c->p.mp, *c->p.factor, v.potrf_info, st, bt, lookahead(c), false,
-                                  may_beside ? &beside : nullptr));   // :129-131
-    else      LP_HIP(launch_qr_factor(c->p.M, c->p.mp, c->p.mp, c->p.tau, v.potrf_info, st));        // :133-149
-    prof_mark(c, T_POTRF);
+    if (c->skip_factor) LP_HIP(copy_info(c, v.potrf_info, c->p.info1));   // the kept factor's pivot failure, if it had one
+    else {
+        if (chol) LP_HIP(launch_potrf(cur_M(c), c->p.mp, c->p.mp, cur_factor(c), v.potrf_info, st, bt, lookahead(c), false,
+                                      may_beside ? &beside : nullptr));   // :129-131
+        else      LP_HIP(launch_qr_factor(c->p.M, c->p.mp, c->p.mp, c->p.tau, v.potrf_info, st));        // :133-149
+        if (c->on_first) LP_HIP(copy_info(c, c->p.info1, v.potrf_info));  // kept with the factor it belongs to
+        prof_mark(c, T_POTRF);
+    }
     // predictor: both sym_solve calls of solve_newton_equations (:187-188) in one pass each
     if (beside.calls > 0) {}                                // the pass ran beside the factorisation
     else if (!c->colsplit) {
@@ -840,7 +904,7 @@ static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
         vec_add_rows((int)c->p.m, 2, v.R, c->p.mp, v.b, v.rP, st);
     }
     prof_mark(c, T_GEMV);
-    if (beside.calls > 0) LP_HIP(launch_chol_solve(c->p.M, c->p.mp, *c->p.factor, 2, v.R, c->p.Y, st, bt, SolveSteps{pb.fwd_done, -1, true}));
+    if (beside.calls > 0) LP_HIP(launch_chol_solve(cur_M(c), c->p.mp, cur_factor(c), 2, v.R, c->p.Y, st, bt, SolveSteps{pb.fwd_done, -1, true}));
     else if (chol) LP_TRY(chol_solve_refined(c, 2, v.R, bt));                               // :221, :154
     else      LP_HIP(launch_qr_solve(c->p.M, c->p.mp, c->p.mp, c->p.tau, 2, v.R, v.potrf_info, st));   // :155-166
     prof_mark(c, T_TRSV);
@@ -981,14 +1045,25 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XO
     for (int i = 0; i < B; ++i) act[(size_t)i] = i;
     int running = B, ip = o->ip ? 1 : 0;
     bool head_out = false;
+    // The kept first factor (lpipm_ctx::first_valid): the Cholesky arm of a resident problem whose layout has the buffers.
+    // Iteration 1 works in them; when they are valid it neither forms nor factors its matrix.  The flag is down from here
+    // until iteration 1 has completed, so a solve that fails before that leaves nothing that counts as kept.
+    const bool use_first = o->solver_type == LPIPM_SOLVER_CHOLESKY && c->first_cache && c->p.keep && !c->colsplit && c->refine <= 0;
+    const bool replay = use_first && c->first_valid;
+    c->first_done = false;
+    if (use_first) c->first_valid = false;
     for (uint64_t iteration = 1; iteration <= o->max_iter && running > 0; ++iteration) {   // mod.rs:213
+        c->on_first = use_first && iteration == 1;
+        c->skip_factor = c->on_first && replay;
         if (!speculate) {
             LP_TRY(enqueue_iteration(c, ip, o));
+            c->on_first = c->skip_factor = false;
             LP_HIP(hipStreamSynchronize(st));
             prof_collect(c);
         } else {
             if (!head_out) LP_TRY(enqueue_head(c));
             LP_TRY(enqueue_tail(c, ip, o));
+            c->on_first = c->skip_factor = false;
             const size_t marks = rs.nmarks;
             head_out = iteration < o->max_iter;
             if (head_out) LP_TRY(enqueue_head(c));       // next iteration's A.D.A^T, before this one's status is read
@@ -997,6 +1072,7 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XO
             prof_collect(c, marks);
         }
         ++loop_iterations;
+        if (iteration == 1) { c->first_done = true; if (use_first) c->first_valid = true; }
         if (c->colsplit && c->p.adat.ngroups() > 0 && *rs.timeout_host != 0) {
             g_err_detail = "a column group of A.D.A^T did not complete within the wait kernel's bound";
             LP_HIP(hipStreamSynchronize(st));
@@ -1065,7 +1141,8 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XO
         c->times.adat_ms = c->tag_ms[T_ADAT]; c->times.potrf_ms = c->tag_ms[T_POTRF];
         c->times.trsv_ms = c->tag_ms[T_TRSV]; c->times.gemv_ms = c->tag_ms[T_GEMV];
         c->times.vec_ms = c->tag_ms[T_VEC];
-        c->times.adat_launches = loop_iterations;      // launches of the kernel (each covers all B members)
+        // launches of the kernel (each covers all B members): iteration 1 on a kept factor made none
+        c->times.adat_launches = loop_iterations - (replay && loop_iterations > 0 ? 1 : 0);
         c->times.iterations = loop_iterations;         // iterations of the loop (= the slowest member's count)
         // the speculatively enqueued head of the iteration after the last holds no GEMV pass: every counted pass ran
         c->times.gemv_passes = c->gemv_passes;
@@ -1151,6 +1228,11 @@ static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const XOut& xo, con
         c->halves.push_back(a); c->halves.push_back(b);
     }
     LP_HIP(hipStreamSynchronize(c->rs.st));         // the upload (or whatever else the caller enqueued) precedes both halves
+    // the kept first factor: the halves work with the parent's switch and validity, and it is valid afterwards only if both
+    // got through their iteration 1 and returned Ok
+    const bool use_first = c->first_cache && c->p.keep;
+    for (lpipm_ctx* v : c->halves) { v->first_cache = c->first_cache; v->first_valid = c->first_valid; }
+    if (use_first) c->first_valid = false;
     int rc[2] = {LPIPM_OK, LPIPM_OK};
     // a view numbers its members from 0: member i of half k is member first + i of the batch
     std::vector<uint64_t> ident;
@@ -1164,6 +1246,7 @@ static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const XOut& xo, con
     std::thread other(run, 1);
     run(0);
     other.join();
+    if (use_first && rc[0] == LPIPM_OK && rc[1] == LPIPM_OK && c->halves[0]->first_done && c->halves[1]->first_done) c->first_valid = true;
     return rc[0] != LPIPM_OK ? rc[0] : rc[1];
 }
 
@@ -1216,15 +1299,15 @@ extern "C" int lpipm_solve_lockstep_device(lpipm_ctx* c, const lpipm_opts* o, vo
 // Bytes one member of a lockstep batch of this shape occupies: the real layout (plan_adat and a measuring pass of
 // layout_problem over the bare geometry), not a formula that drifts from it.
 // n_slack: the member's (verified) structural hint -- its slack columns are not resident.
-static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, uint64_t m, uint64_t n, uint64_t n_slack) {
+static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, uint64_t m, uint64_t n, uint64_t n_slack, bool keep) {
     Problem t;
     t.B = 32;
     t.mp = (int)round_up(m, NB); t.np = (int)round_up(n, BK); t.npa = (int)round_up(n - n_slack, BK);
     t.nsplit = t.mp / GEMVT_ROWS;
     const AdatPlan ap = plan_adat(t.mp, t.npa, t.B, c->num_cu, c->world, c->units_env);
-    FactorPlan fp;
+    FactorPlan fp, fp1;
     Arena measure;
-    if (layout_problem(t, fp, ap, c->refine, measure, false, nullptr) != LPIPM_OK) return (size_t)-1;
+    if (layout_problem(t, fp, fp1, ap, c->refine, keep && c->first_cache && c->refine <= 0, measure, false, nullptr) != LPIPM_OK) return (size_t)-1;
     return (size_t)round_up(measure.off, 4096);
 }
 
@@ -1272,7 +1355,8 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             size_t free_b = 0, total_b = 0;
             LP_HIP(hipMemGetInfo(&free_b, &total_b));
             free_b += c->p.arena_bytes;                // the current arena is released before the next one is made
-            const double per_lp = (double)lockstep_bytes_per_lp(c, m[i], n[i], ns[i]);     // the real arena layout of one member
+            // the real arena layout of one member (no kept first factor: a chunk is uploaded, solved once and replaced)
+            const double per_lp = (double)lockstep_bytes_per_lp(c, m[i], n[i], ns[i], false);
             size_t chunk;
             if (c->lockstep_max > 0) chunk = (size_t)c->lockstep_max;
             else if (grp.size() > 32) chunk = 32;
@@ -1312,7 +1396,7 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             auto upload_chunk = [&](lpipm_ctx* w, const Chunk& ch) -> int {
                 (void)hipSetDevice(w->device);
                 return upload_impl(w, (int)ch.g, m[i], n[i], ch.A.data(), n[i], ch.b.data(), ch.c.data(), ch.c0.data(), ns[i],
-                                   nullptr, false, true);
+                                   nullptr, false, true, false);
             };
             int rc_up = chunks.empty() ? LPIPM_OK : upload_chunk(pipe[0], chunks[0]);
             for (size_t q = 0; q < chunks.size(); ++q) {
@@ -1372,7 +1456,7 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             if (k >= rest.size() || fatal.load() != LPIPM_OK) break;
             const uint64_t i = rest[k];
             const double c0i = c0 ? c0[i] : 0.0;
-            int rc = upload_impl(w, 1, m[i], n[i], &A[i], n[i], &b[i], &cc[i], &c0i, ns[i], nullptr, false, true);
+            int rc = upload_impl(w, 1, m[i], n[i], &A[i], n[i], &b[i], &cc[i], &c0i, ns[i], nullptr, false, true, false);
             double fun = NAN;
             uint64_t it = 0;
             if (rc == LPIPM_OK)
@@ -1451,7 +1535,7 @@ extern "C" int lpipm_set_collective_on_stream(lpipm_ctx* c, int on) {
 extern "C" int lpipm_upload_nsplit(lpipm_ctx* c, uint64_t m, uint64_t n_total, uint64_t n_local, const double* A_local,
                                    uint64_t lda, const double* b, const double* c_local, double c0) {
     if (!c || n_local == 0 || n_local > n_total) return LPIPM_ERR_BAD_ARGUMENT;
-    const int rc = lpipm_upload_slack(c, m, n_local, A_local, lda, b, c_local, c0, 0);
+    const int rc = upload_impl(c, 1, m, n_local, &A_local, lda, &b, &c_local, &c0, 0, nullptr, false, false, false);
     if (rc != LPIPM_OK) return rc;
     if (c->world > 1) {
         const size_t need = (size_t)c->p.mp * ((size_t)c->p.mp + 128) / 2;
@@ -1473,6 +1557,24 @@ extern "C" int lpipm_upload_nsplit(lpipm_ctx* c, uint64_t m, uint64_t n_total, u
     c->colsplit = true;
     c->p.va.n_total = (long long)n_total;
     c->p.va.gs = c->p.gs;
+    return LPIPM_OK;
+}
+
+extern "C" int lpipm_set_first_factor_cache(lpipm_ctx* c, int on) {
+    if (!c) return LPIPM_ERR_BAD_ARGUMENT;
+    c->first_cache = on != 0;     // the buffers come and go with the next upload (upload_impl); off stops their use at once
+    return LPIPM_OK;
+}
+
+extern "C" int lpipm_update_vectors(lpipm_ctx* c, const double* b, const double* cc) {
+    if (!c || !b || !cc) return LPIPM_ERR_BAD_ARGUMENT;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (c->p.B != 1 || c->colsplit || c->p.from_parts) return LPIPM_ERR_UNSUPPORTED;
+    LP_HIP(hipSetDevice(c->device));
+    // (the padding beyond m and n stays zero; A, and with it the kept first factor, is not touched)
+    LP_HIP(hipMemcpyAsync((void*)c->p.va.b, b, c->p.m * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
+    LP_HIP(hipMemcpyAsync((void*)c->p.va.c, cc, c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));   // the caller's arrays are free again from here
     return LPIPM_OK;
 }
 
