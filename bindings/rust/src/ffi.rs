@@ -105,6 +105,14 @@ extern "C" {
         ctx: *mut lpipm_ctx, count: u64, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, m_eq: u64, a_eq: *const f64,
         lda_eq: u64, b: *const *const f64, c: *const *const f64, c0: *const f64,
     ) -> c_int;
+    // New b / c / c0 (each nullable: stays) for every member of the resident lockstep batch, in its upload's own form; A and
+    // the kept first factor stay.  _device: packed row blocks on the device, member i at b_dev + i * ldb doubles.
+    pub fn lpipm_update_lockstep_vectors(
+        ctx: *mut lpipm_ctx, count: u64, b: *const *const f64, c: *const *const f64, c0: *const f64,
+    ) -> c_int;
+    pub fn lpipm_update_lockstep_vectors_device(
+        ctx: *mut lpipm_ctx, count: u64, b_dev: *const c_void, ldb: u64, c_dev: *const c_void, ldc: u64, c0: *const f64,
+    ) -> c_int;
     // lpipm_solve_batch with a per-member hint (n_slack nullable); exactly one of x_slack_out and x_dev_out is non-null.
     pub fn lpipm_solve_batch_slack(
         ctx: *mut lpipm_ctx, count: u64, m: *const u64, n: *const u64, n_slack: *const u64, a: *const *const f64,

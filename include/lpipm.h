@@ -75,7 +75,9 @@ typedef struct {
     double   gemv_ms;      /* passes over A (GEMV-N / GEMV-T)                           */
     double   vec_ms;       /* O(n) vector / scalar kernels + status read-back          */
     double   total_ms;     /* first kernel to last kernel of the solve                 */
-    uint64_t adat_launches; /* A.D.A^T launches made: `iterations`, less one when iteration 1 started from the kept factor */
+    uint64_t adat_launches; /* A.D.A^T launches made: `iterations`, less one when iteration 1 started from the kept factor, plus
+                             * the one that builds a shared-matrix batch's factor ahead of its first solve (its time and
+                             * the factorisation's are in adat_ms and potrf_ms of that solve) */
     uint64_t iterations;
     uint64_t gemv_passes;  /* passes over A inside gemv_ms (a 2-vector pass reads A once and counts once) */
 } lpipm_phase_times;
@@ -136,16 +138,41 @@ int lpipm_upload_ub_eq(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const double* 
  * lockstep batch and for a column-split context. */
 int lpipm_update_vectors(lpipm_ctx* ctx, const double* b, const double* c);
 
+/* New b, c and (optionally) c0 for EVERY member of the resident lockstep batch, whichever lpipm_upload_lockstep* made it, in
+ * that upload's own form: b[i][m] and c[i][n] (c with its slack entries); after lpipm_upload_lockstep_shared_ub_eq
+ * b[i] = [b_ub_i; b_eq_i] and c[i] = the n structural costs (the slack costs stay 0).  b or c may be NULL as a whole: those
+ * vectors stay (a right-hand-side sweep sends no costs); c0 == NULL: the constants stay.  A, the layout, the half-batch views
+ * and the kept first factor(s) are not touched, and the padding beyond m and n stays zero: the next lpipm_solve_lockstep[_device]
+ * is bit-identical to a fresh upload of the same members followed by a solve.  The host arrays are staged in one pinned block
+ * of the context, sent with one copy and distributed by one kernel launch; the call returns when they are free again.
+ * The _device variant reads packed row blocks that are already on the device, on the context's stream (they must be
+ * complete when it is called): member i's b at b_dev + i * ldb doubles (ldb >= m), its c at c_dev + i * ldc (ldc >= the
+ * length of c[i] above); c0 stays a host array.  A scenario generator on the GPU never touches the host.
+ * LPIPM_ERR_NO_PROBLEM without an upload; LPIPM_ERR_BAD_ARGUMENT for a null context, b and c both NULL, count other than
+ * the resident member count, or ldb / ldc too small; LPIPM_ERR_UNSUPPORTED for a column-split context and after the
+ * single-LP lpipm_upload_ub_eq (as lpipm_update_vectors).  The staging block (count * (m + n + 1) doubles on each side) is
+ * not part of lpipm_get_resident_bytes. */
+int lpipm_update_lockstep_vectors(lpipm_ctx* ctx, uint64_t count, const double* const* b /* nullable */,
+                                  const double* const* c /* nullable */, const double* c0 /* nullable: stays */);
+int lpipm_update_lockstep_vectors_device(lpipm_ctx* ctx, uint64_t count, const void* b_dev /* nullable */, uint64_t ldb,
+                                         const void* c_dev /* nullable */, uint64_t ldc,
+                                         const double* c0 /* host, nullable: stays */);
+
 /* Every solve starts from x = z = 1 (feasible_point.rs:24-31), so the normal matrix of its first iteration is A.A^T (+ I on
  * the rows of a structural slack block): that matrix, its Cholesky factor, the inverses of the factor's diagonal blocks and
  * the pivot-failure word are functions of A alone.  The Cholesky arm keeps them per upload -- a single LP's, and every
- * member's of a lockstep batch -- and every solve after the first on the same upload starts from them instead of running
- * A.D.A^T and the factorisation again.  No result changes by a bit.  Any upload drops what is kept.  Not used by the QR arms,
+ * member's of a lockstep batch whose members own their matrices -- and every solve after the first on the same upload starts
+ * from them instead of running A.D.A^T and the factorisation again.  A shared-matrix batch (lpipm_upload_lockstep_shared*)
+ * keeps ONE set next to its one A: it is formed and factored once, ahead of the first solve after the upload, and every
+ * member of every solve, the first included, starts from it; in that iteration each block of the factor and of its inverses
+ * is read once per group of members.  No result changes by a bit.  Any upload drops what is kept.  Not used by the QR arms,
  * column-split contexts, lpipm_solve_f32 and lpipm_solve_batch (which uploads on every call).
- * Cost per resident LP, with mp = m rounded up to 128 and s_k the widths of the diagonal super-blocks (512 each up to
- * mp = 2048, 1024 beyond; the last one what is left of mp):  8 mp^2 + 16 sum_k s_k^2 + 4096 bytes (lpipm_get_resident_bytes
- * counts them).  on = 0 gives that memory back: the kept factor is no longer used from the next solve on, and the buffers go
- * (or, with on = 1 again, come back) with the next upload.  Default: on. */
+ * Cost per resident LP -- once per shared-matrix batch, which adds a vector of ones over the padded columns (8 np bytes
+ * rounded up to 4096, np = n rounded up to 16) --, with mp = m rounded up to 128 and s_k the widths of the diagonal
+ * super-blocks (512 each up to mp = 2048, 1024 beyond; the last one what is left of mp):  8 mp^2 + 16 sum_k s_k^2 + 4096
+ * bytes (lpipm_get_resident_bytes counts them).  on = 0 gives that memory back: the kept factor is no longer used from the
+ * next solve on, and the buffers go (or, with on = 1 again, come back) with the next upload; a shared-matrix batch uploaded
+ * with on = 0 has no shared set, and every member forms and factors its own iteration 1.  Default: on. */
 int lpipm_set_first_factor_cache(lpipm_ctx* ctx, int on);
 
 /* InteriorPoint::solve_normal_form + the `fun` of solve (mod.rs:199-240, :165).
@@ -240,8 +267,8 @@ int lpipm_upload_lockstep_shared_slack(lpipm_ctx* ctx, uint64_t count, uint64_t 
 int lpipm_upload_lockstep_shared_ub_eq(lpipm_ctx* ctx, uint64_t count, uint64_t n, uint64_t m_ub, const double* A_ub,
                                        uint64_t lda_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq,
                                        const double* const* b, const double* const* c, const double* c0 /* nullable */);
-/* Device bytes the context holds for its resident problem(s) (arenas + shared matrix + factor workspace); 0 before any
- * upload. */
+/* Device bytes the context holds for its resident problem(s) (arenas + shared matrix with the batch's one kept first factor +
+ * factor workspace); 0 before any upload. */
 int lpipm_get_resident_bytes(const lpipm_ctx* ctx, uint64_t* bytes_out);
 /* lpipm_solve_batch with device-resident results: member i's x / tau goes to x_dev_out + i * row_stride doubles
  * (row_stride >= max n[i]); everything else as lpipm_solve_batch. */

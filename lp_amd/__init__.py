@@ -287,6 +287,44 @@ class Context:
         _raise_for(_capi.lib().lpipm_update_vectors(self._h, _p(b), _p(c)))
         return self
 
+    def _lockstep_form(self):
+        """(members, len(b[i]), len(c[i])) of the resident lockstep batch, in its upload's own form."""
+        lock = getattr(self, "_lock", None)
+        if lock is None:
+            raise BackendError("no lockstep batch is resident on this context")
+        K, m, n, _, _, cs = lock
+        return K, m, cs[0].shape[0]                # (after upload_lockstep_shared_ub_eq: the structural costs only)
+
+    def update_lockstep_vectors(self, bs=None, cs=None, c0s=None):
+        """New b, c and c0 for every member of the resident lockstep batch (lpipm_update_lockstep_vectors), in the form of the
+        upload_lockstep* that made it; None leaves those vectors (or constants) as they are.  A stays, and so does the first
+        iteration's factor kept with it: the next solve_lockstep is bit-identical to a fresh upload of the same members."""
+        K, m, nc = self._lockstep_form()
+        bs = None if bs is None else [_f64(b) for b in bs]
+        cs = None if cs is None else [_f64(c) for c in cs]
+        if ((bs is not None and (len(bs) != K or any(b.shape != (m,) for b in bs)))
+                or (cs is not None and (len(cs) != K or any(c.shape != (nc,) for c in cs)))
+                or (c0s is not None and len(c0s) != K)):
+            raise IncompatibleInputDimensions()
+        dp = C.POINTER(C.c_double)
+        arr = lambda lst: None if lst is None else (dp * K)(*[_p(a) for a in lst])
+        c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
+        _raise_for(_capi.lib().lpipm_update_lockstep_vectors(self._h, K, arr(bs), arr(cs), c0))
+        return self
+
+    def update_lockstep_vectors_device(self, b_ptr, ldb, c_ptr, ldc, c0s=None):
+        """update_lockstep_vectors from packed row blocks already on the device (lpipm_update_lockstep_vectors_device):
+        member i's b at b_ptr + i * ldb doubles, its c at c_ptr + i * ldc; a null (0 / None) pointer leaves those vectors.
+        The blocks are read on the context's stream: whatever wrote them must have completed."""
+        K = self._lockstep_form()[0]
+        if c0s is not None and len(c0s) != K:
+            raise IncompatibleInputDimensions()
+        c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
+        _raise_for(_capi.lib().lpipm_update_lockstep_vectors_device(
+            self._h, K, C.c_void_p(int(b_ptr)) if b_ptr else None, int(ldb), C.c_void_p(int(c_ptr)) if c_ptr else None,
+            int(ldc), c0))
+        return self
+
     def set_first_factor_cache(self, on: bool = True):
         """Whether the first iteration's factor (a function of A alone) is kept per upload and reused by every later solve
         on it (lpipm_set_first_factor_cache; default on).  Off gives its memory back at the next upload."""

@@ -45,6 +45,8 @@ SYMBOLS = {
     "lpipm_upload_slack": (C.c_int, [_vp, _u64, _u64, _dp, _u64, _dp, _dp, C.c_double, _u64]),
     "lpipm_upload_ub_eq": (C.c_int, [_vp, _u64, _u64, _dp, _u64, _dp, _u64, _dp, _u64, _dp, _dp, C.c_double]),
     "lpipm_update_vectors": (C.c_int, [_vp, _dp, _dp]),
+    "lpipm_update_lockstep_vectors": (C.c_int, [_vp, _u64, _dpp, _dpp, _dp]),
+    "lpipm_update_lockstep_vectors_device": (C.c_int, [_vp, _u64, _vp, _u64, _vp, _u64, _dp]),
     "lpipm_set_first_factor_cache": (C.c_int, [_vp, C.c_int]),
     "lpipm_solve": (C.c_int, [_vp, C.POINTER(Opts), _dp, _dp, C.POINTER(_u64), C.POINTER(IterRow)]),
     "lpipm_solve_device": (C.c_int, [_vp, C.POINTER(Opts), _vp, _dp, C.POINTER(_u64), C.POINTER(IterRow)]),

@@ -131,3 +131,52 @@ def solve_shared_ub_eq(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_gr
         for st, x, fun, it in ctx.solve_lockstep(opts):
             out.append(dict(status=st, x_slack=x, fun=fun, iterations=it))
     return out
+
+
+def sweep_chunks(count: int, max_group: int):
+    """The equal chunks of a sweep: k = ceil(count / max_group) chunks of g = ceil(count / k) members, as lists of member
+    indices.  The last chunk is filled up to g with repeats of its own last member (at most k - 1 of them in all), so
+    every chunk after the first replaces the vectors of a resident batch of g instead of uploading a shorter one.
+    -> (g, [indices of chunk 0, ...]); the first `count` indices in order are 0 .. count - 1."""
+    if count < 1 or max_group < 1:
+        return 0, []
+    k = -(-count // max_group)
+    g = -(-count // k)
+    chunks = [list(range(q * g, min((q + 1) * g, count))) for q in range(k)]
+    chunks[-1] += [chunks[-1][-1]] * (g - len(chunks[-1]))
+    return g, chunks
+
+
+def _sweep(upload, bs, cs, c0s, opts, ctx, max_group):
+    import lp_amd
+    count = len(bs)
+    if len(cs) != count or (c0s is not None and len(c0s) != count):
+        raise lp_amd.IncompatibleInputDimensions()
+    if max_group < 1:
+        raise lp_amd.InvalidParameter("max_group must be >= 1")
+    ctx = ctx or lp_amd.default_context(0)
+    opts = opts or lp_amd.InteriorPoint.default().opts()
+    out = []
+    for q, idx in enumerate(sweep_chunks(count, max_group)[1]):
+        pick = lambda seq: None if seq is None else [seq[i] for i in idx]
+        if q == 0:
+            upload(ctx, pick(bs), pick(cs), pick(c0s))
+        else:
+            ctx.update_lockstep_vectors(pick(bs), pick(cs), pick(c0s))
+        res = ctx.solve_lockstep(opts)
+        for st, x, fun, it in res[:count - len(out)]:          # (the padding's results are dropped)
+            out.append(dict(status=st, x_slack=x, fun=fun, iterations=it))
+    return out
+
+
+def sweep_shared_matrix(A, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, n_slack=0):
+    """solve_shared_matrix for a sweep of more than one group: ONE upload_lockstep_shared (the first chunk), then
+    update_lockstep_vectors for every later chunk -- A goes to the device once, and its first iteration's factor is formed
+    once for the whole sweep.  The chunks are equal (sweep_chunks).  Returns what solve_shared_matrix returns, bit for bit."""
+    return _sweep(lambda cx, b, c, c0: cx.upload_lockstep_shared(A, b, c, c0, n_slack=n_slack), bs, cs, c0s, opts, ctx, max_group)
+
+
+def sweep_shared_ub_eq(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_group=32):
+    """solve_shared_ub_eq as a sweep: one upload_lockstep_shared_ub_eq, then update_lockstep_vectors per later chunk (bs[i] =
+    [b_ub_i; b_eq_i], cs[i] = the n structural costs).  Returns what solve_shared_ub_eq returns, bit for bit."""
+    return _sweep(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_eq(A_ub, A_eq, b, c, c0), bs, cs, c0s, opts, ctx, max_group)

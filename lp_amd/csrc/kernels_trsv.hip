@@ -205,7 +205,10 @@ __global__ __launch_bounds__(256) void trsv_fold_kernel(double* __restrict__ y, 
 }
 
 hipError_t launch_chol_solve(const double* L, int64_t ld, const FactorPlan& plan, int nrhs, double* R,
-                             double* Y, hipStream_t st, const Batch& bt, const SolveSteps& steps) {
+                             double* Y, hipStream_t st, const Batch& bt, const SolveSteps& steps, bool shared_factor) {
+    // shared_factor: L, inv and invT are ONE factor for the whole batch and get no member offset; every mat-vec of the sweep
+    // then runs as the shared-matrix group template (a block of the factor is read once per group of members).  R, Y and
+    // the slabs stay per member, and a member's sums are those of the group of one.
     const int mp = plan.mp;
     hipError_t e;
     const int nsb = (int)plan.sbs.size();
@@ -213,13 +216,13 @@ hipError_t launch_chol_solve(const double* L, int64_t ld, const FactorPlan& plan
     // forward: L y = r
     for (int k = steps.fwd_begin; k < k1; ++k) {
         const SuperBlock& s = plan.sbs[k];
-        e = launch_gemv_n(s.inv, s.size, s.size, s.size, nrhs, R + s.row0, mp, nullptr, nullptr, Y + s.row0, mp, st, 1.0, bt);
+        e = launch_gemv_n(s.inv, s.size, s.size, s.size, nrhs, R + s.row0, mp, nullptr, nullptr, Y + s.row0, mp, st, 1.0, bt, shared_factor);
         if (e != hipSuccess) return e;
         const int below = mp - (s.row0 + s.size);
         if (below > 0) {
             double* rb = R + s.row0 + s.size;
             e = launch_gemv_n(L + (size_t)(s.row0 + s.size) * ld + s.row0, ld, below, s.size, nrhs, Y + s.row0, mp, rb,
-                              rb + mp, rb, mp, st, -1.0, bt);
+                              rb + mp, rb, mp, st, -1.0, bt, shared_factor);
             if (e != hipSuccess) return e;
         }
     }
@@ -230,13 +233,13 @@ hipError_t launch_chol_solve(const double* L, int64_t ld, const FactorPlan& plan
         const int below = mp - (s.row0 + s.size);
         if (below > 0) {
             e = launch_gemv_t(L + (size_t)(s.row0 + s.size) * ld + s.row0, ld, below, s.size, nrhs,
-                              R + s.row0 + s.size, mp, plan.tpart, st, 0, bt);
+                              R + s.row0 + s.size, mp, plan.tpart, st, 0, bt, shared_factor);
             if (e != hipSuccess) return e;
             hipLaunchKernelGGL(trsv_fold_kernel, dim3((s.size + 255) / 256, 1, bt.count), dim3(256), 0, st, Y + s.row0,
                                (long long)mp, plan.tpart, below / GEMVT_ROWS, nrhs, s.size, batch_k(bt));
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
-        e = launch_gemv_n(s.invT, s.size, s.size, s.size, nrhs, Y + s.row0, mp, nullptr, nullptr, R + s.row0, mp, st, 1.0, bt);
+        e = launch_gemv_n(s.invT, s.size, s.size, s.size, nrhs, Y + s.row0, mp, nullptr, nullptr, R + s.row0, mp, st, 1.0, bt, shared_factor);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -819,6 +819,28 @@ void vec_copy_lower(const double* M, double* M0, long long ld, int mp, hipStream
     hipLaunchKernelGGL(k_copy_lower, dim3(mp, mp / 128, bt.count), dim3(64), 0, st, M, M0, ld, batch_k(bt));
 }
 
+// Rows of packed blocks into the members' arenas: segment s = blockIdx.y writes src[z * ld + i] (i < len) to element i of
+// member z's dst.  grid (element block, segment, member); a null dst, or a block past a segment's length, does nothing.
+// Plain loads and stores, no done test: it replaces the inputs of members that have finished.  ld == 0: one row for all.
+template <typename T>
+__global__ __launch_bounds__(256) void k_scatter_rows(ScatterRows<T> a, BatchK bk) {
+    const ScatterSeg<T> s = a.seg[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (!s.dst || i >= s.len) return;
+    batch_ptr(s.dst, bk)[i] = s.src[(long long)blockIdx.z * s.ld + i];
+}
+template <typename T>
+void vec_scatter_rows(const ScatterRows<T>& a, hipStream_t st, const Batch& bt) {
+    int len = 0, nseg = 0;
+    for (int s = 0; s < SCATTER_SEGS; ++s)
+        if (a.seg[s].dst) { nseg = s + 1; if (a.seg[s].len > len) len = a.seg[s].len; }
+    if (nseg == 0 || len <= 0) return;
+    const Batch all{bt.count, bt.stride, nullptr, bt.first};
+    hipLaunchKernelGGL(k_scatter_rows<T>, dim3((len + 255) / 256, nseg, bt.count), dim3(256), 0, st, a, batch_k(all));
+}
+template void vec_scatter_rows<double>(const ScatterRows<double>&, hipStream_t, const Batch&);
+template void vec_scatter_rows<int32_t>(const ScatterRows<int32_t>&, hipStream_t, const Batch&);
+
 void vec_add_rows(int m, int nrhs, double* Y, long long ldy, const double* add0, const double* add1, hipStream_t st) {
     hipLaunchKernelGGL(k_add_rows, dim3((m + 255) / 256), dim3(256), 0, st, m, nrhs, Y, ldy, add0, add1);
 }

@@ -265,8 +265,11 @@ constexpr int POTRF_OUTER = 4;   // 128-blocks per outer panel (also the width o
 // steps: the forward steps [fwd_begin, fwd_end) (fwd_end < 0: to the last one; the steps before fwd_begin have been run by
 // an earlier call on the same R and Yscratch), then the backward sweep unless `backward` is false.
 struct SolveSteps { int fwd_begin = 0, fwd_end = -1; bool backward = true; };
+// shared_factor: the factor and the plan's inverses belong to the whole batch (a shared-matrix batch's kept first factor):
+// they are not offset by the member, and each step runs as the shared group template of launch_gemv_n / launch_gemv_t.
 hipError_t launch_chol_solve(const double* L, int64_t ld, const FactorPlan& plan, int nrhs, double* R,
-                             double* Yscratch, hipStream_t st, const Batch& bt = Batch{}, const SolveSteps& steps = SolveSteps{});
+                             double* Yscratch, hipStream_t st, const Batch& bt = Batch{}, const SolveSteps& steps = SolveSteps{},
+                             bool shared_factor = false);
 
 // ---------------------------------------------------------------- QR arms (kernels_qr.hip)
 // EquationSolverType::{Inverse, LeastSquares}: Householder QR of the full mp x mp matrix whose LOWER

@@ -92,6 +92,10 @@ struct Problem {
     double* M1 = nullptr;
     const FactorPlan* factor1 = nullptr; // lpipm_ctx::plan1 of the uploading context
     int32_t* info1 = nullptr;
+    // A shared-matrix batch keeps ONE such set for all its members, behind A in a_shared (layout_shared_factor), built once
+    // from `ones` -- iteration 1's dinv, exact 1.0 over the np columns -- ahead of the first solve (ensure_shared_factor).
+    bool shared_factor = false;
+    double* ones = nullptr;
     bool from_parts = false;     // uploaded as ub / eq blocks (lpipm_upload_ub_eq): b and c are not in the caller's slack form
     AdatRes adat;                // what the A.D.A^T launches use on the device (kernels_adat.hip); adat.ngroups() > 0: one LP split by
                                  //   columns over ranks, M is reduced column group by column group behind the running launch
@@ -120,6 +124,14 @@ struct lpipm_ctx {
     bool first_done = false;     // the last solve of this context (or view) got through its iteration 1
     bool on_first = false;       // the iteration being enqueued works in M1 / plan1 ...
     bool skip_factor = false;    //   ... which already hold its factor: no A.D.A^T, no factorisation
+    // what building a shared-matrix batch's one factor took, until the solve it preceded reports it (lpipm_phase_times)
+    double build_adat_ms = 0.0, build_potrf_ms = 0.0;
+    uint64_t build_launches = 0;
+    // lpipm_update_lockstep_vectors: the members' new b, c and c0 packed in one pinned block, and its image on the device.
+    // Made on first use, grown when a call needs more, freed by lpipm_destroy; nobody else touches them.
+    double* stage_host = nullptr;
+    double* stage_dev = nullptr;
+    size_t stage_cap = 0;        // doubles, each side
     int units_env = 1;                   // LPIPM_ADAT_UNITS=0: the round-2 kernel (data-parallel tiles + fix-up launch) everywhere
     PotrfLookahead la;                   // trailing updates of one factorisation beside the next panel's chain (launch_potrf)
     // a lockstep batch as two half-batches driven by two host threads on two streams (solve_lockstep): views of this
@@ -397,6 +409,8 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     if (c->rs.st) (void)hipStreamSynchronize(c->rs.st);      // before the buffers go
     if (c->p.arena) (void)hipFree(c->p.arena);
     if (c->p.a_shared) (void)hipFree(c->p.a_shared);
+    if (c->stage_dev) (void)hipFree(c->stage_dev);
+    if (c->stage_host) (void)hipHostFree(c->stage_host);
     adat_lists_destroy(c->p.adat);
     free_list(c->kallocs);
     if (c->mpack) (void)hipFree(c->mpack);
@@ -486,8 +500,10 @@ static int layout_problem(Problem& p, FactorPlan& plan, FactorPlan& plan1, const
     p.xout = ar.take<double>(np);
     adat_take(p.adat, ap, ar);
     p.keep = keep;
-    p.M1 = nullptr; p.factor1 = nullptr; p.info1 = nullptr;
-    if (keep) {
+    p.shared_factor = keep && p.shared_a;      // one set for the batch, outside the arenas (layout_shared_factor)
+    p.M1 = nullptr; p.factor1 = nullptr; p.info1 = nullptr; p.ones = nullptr;
+    if (p.shared_factor) {}
+    else if (keep) {
         ar.off = (size_t)round_up(ar.off, 4096);
         const size_t begin = ar.off;
         p.M1 = ar.take<double>(mp * mp);
@@ -497,6 +513,22 @@ static int layout_problem(Problem& p, FactorPlan& plan, FactorPlan& plan1, const
         ar.off = (size_t)round_up(ar.off, 4096);
         if (ar.off - begin != first_factor_bytes(p.mp, super_for(p.mp))) return LPIPM_ERR_BAD_ARGUMENT;   // (the documented size)
     } else factor_plan_destroy(plan1);
+    return LPIPM_OK;
+}
+// The one kept first factor of a shared-matrix batch (p.shared_factor), from `sh`: the batch's shared allocation behind A.
+// The same block as an arena's -- first_factor_bytes(mp) on 4096-byte bounds -- then the vector of ones, np doubles rounded
+// up to 4096 bytes.  The plan's inverses are the batch's; its merge workspace and gemv_t slabs stay the first plan's, per member.
+static int layout_shared_factor(Problem& p, const FactorPlan& plan, FactorPlan& plan1, Arena& sh, bool build, hipStream_t st) {
+    sh.off = (size_t)round_up(sh.off, 4096);
+    const size_t begin = sh.off;
+    p.M1 = sh.take<double>((size_t)p.mp * p.mp);
+    LP_HIP(factor_plan_create(plan1, p.M1, p.mp, p.mp, sh, build, st, super_for(p.mp), merge_edge_for(p.B), &plan));
+    p.factor1 = &plan1;
+    p.info1 = sh.take<int32_t>(1);
+    sh.off = (size_t)round_up(sh.off, 4096);
+    if (sh.off - begin != first_factor_bytes(p.mp, super_for(p.mp))) return LPIPM_ERR_BAD_ARGUMENT;   // (the documented size)
+    p.ones = sh.take<double>((size_t)p.np);
+    sh.off = (size_t)round_up(sh.off, 4096);
     return LPIPM_OK;
 }
 
@@ -570,11 +602,18 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
         Arena real;
         real.base = c->p.arena;
         LP_TRY(layout_problem(c->p, c->plan, c->plan1, c->ap, c->refine, keep, real, true, st));
-        if (shared) {              // the one A of the batch: mp x npa like an arena's, zero padding
-            c->p.a_shared_bytes = (size_t)mp * (size_t)npa * sizeof(double);
+        if (shared) {              // the one A of the batch: mp x npa like an arena's, zero padding; behind it the one kept factor
+            const size_t a_bytes = (size_t)mp * (size_t)npa * sizeof(double);
+            Arena sh_measure;
+            sh_measure.off = a_bytes;
+            if (c->p.shared_factor) LP_TRY(layout_shared_factor(c->p, c->plan, c->plan1, sh_measure, false, st));
+            c->p.a_shared_bytes = sh_measure.off;
             LP_HIP(hipMalloc((void**)&c->p.a_shared, c->p.a_shared_bytes));
             LP_HIP(hipMemsetAsync(c->p.a_shared, 0, c->p.a_shared_bytes, st));
             c->p.A = c->p.a_shared;
+            Arena sh;
+            sh.base = (char*)c->p.a_shared; sh.off = a_bytes;
+            if (c->p.shared_factor) LP_TRY(layout_shared_factor(c->p, c->plan, c->plan1, sh, true, st));
         }
         LP_HIP(adat_lists_create(c->p.adat, c->ap, mp, count, st));    // (drains st)
         LP_TRY(stream_res_grow_status(c->rs, (size_t)count));
@@ -600,6 +639,8 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
     c->p.va.done_chk = c->p.bt.done;
     std::vector<double> c0v((size_t)count, 0.0);          // must outlive the asynchronous copies below
     for (int i = 0; i < count; ++i) c0v[i] = c0 ? c0[i] : 0.0;
+    const std::vector<double> onesv(c->p.shared_factor ? (size_t)np : 0, 1.0);
+    if (c->p.shared_factor) LP_HIP(hipMemcpyAsync(c->p.ones, onesv.data(), onesv.size() * sizeof(double), hipMemcpyHostToDevice, st));
     if (parts) {   // rows of A_ub, then rows of A_eq (into the single LP's arena or the batch's one matrix); a single LP's b likewise
         const uint64_t m_ub = parts->m_ub, m_eq = m - m_ub;
         if (m_ub) {
@@ -626,7 +667,7 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
         LP_HIP(hipMemcpyAsync((char*)c->p.va.c + off, cc[i], nc * sizeof(double), hipMemcpyHostToDevice, st));
         LP_HIP(hipMemcpyAsync((char*)(c->p.va.S + S_C0) + off, &c0v[i], sizeof(double), hipMemcpyHostToDevice, st));
     }
-    LP_HIP(hipStreamSynchronize(st));   // the caller's arrays and c0v are free again from here
+    LP_HIP(hipStreamSynchronize(st));   // the caller's arrays, c0v and onesv are free again from here
     c->p.has_problem = true;
     c->p.adat.counters_dirty = true;
     bind_status_pinned(c, true);
@@ -685,8 +726,16 @@ static hipError_t ctx_gemv_dual(lpipm_ctx* c, const double* W, const double* V, 
 // uses it (lpipm_ctx::on_first), the working ones otherwise.
 static double* cur_M(const lpipm_ctx* c) { return c->on_first ? c->p.M1 : c->p.M; }
 static const FactorPlan& cur_factor(const lpipm_ctx* c) { return c->on_first ? *c->p.factor1 : *c->p.factor; }
+static bool cur_shared(const lpipm_ctx* c) { return c->on_first && c->p.shared_factor; }   // one factor for the whole batch
 // The pivot-failure words of the LPs this context covers, between the solver's word and its kept copy (device to device).
+// A shared-matrix batch's one kept word goes to every LP (the other direction does not exist: the build wrote it).
 static hipError_t copy_info(lpipm_ctx* c, int32_t* dst, const int32_t* src) {
+    if (c->p.shared_factor && src == c->p.info1) {
+        ScatterRows<int32_t> w;
+        w.seg[0].dst = dst; w.seg[0].src = src; w.seg[0].ld = 0; w.seg[0].len = 1;
+        vec_scatter_rows(w, c->rs.st, c->p.bt);
+        return hipGetLastError();
+    }
     const size_t off = (size_t)c->p.bt.first * c->p.bstride;
     char* d = (char*)dst + off;
     const char* s = (const char*)src + off;
@@ -717,7 +766,7 @@ static hipError_t run_adat(lpipm_ctx* c, const Batch& bt) {
 // precision, one read of the lower triangle);  v = v0 + L^-T L^-1 rho.  R: nrhs x mp, in/out.
 static int chol_solve_refined(lpipm_ctx* c, int nrhs, double* R, const Batch& bt) {
     hipStream_t st = c->rs.st;
-    if (!c->refine_now) { LP_HIP(launch_chol_solve(cur_M(c), c->p.mp, cur_factor(c), nrhs, R, c->p.Y, st, bt)); return LPIPM_OK; }
+    if (!c->refine_now) { LP_HIP(launch_chol_solve(cur_M(c), c->p.mp, cur_factor(c), nrhs, R, c->p.Y, st, bt, SolveSteps{}, cur_shared(c))); return LPIPM_OK; }
     // the refinement's launches skip an LP whose own word says so (a finished one, or one that does not need it yet)
     const Batch br = c->refine == 2 ? bt : Batch{bt.count, bt.stride, c->p.va.skip_refine, bt.first};
     vec_rows_copy(c->p.mp, nrhs, c->p.R0, R, st, br);
@@ -868,7 +917,7 @@ struct PredictorBeside {
         VecArgs& v = c->p.va;
         if (sb < 0) return ctx_gemv_n(c, 2, v.W, v.b, v.rP, v.R, c->p.bt, side);     // :220
         b->fwd_done = sb + 1;
-        return launch_chol_solve(cur_M(c), c->p.mp, cur_factor(c), 2, v.R, c->p.Y, side, c->p.bt, SolveSteps{sb, sb + 1, false});
+        return launch_chol_solve(cur_M(c), c->p.mp, cur_factor(c), 2, v.R, c->p.Y, side, c->p.bt, SolveSteps{sb, sb + 1, false}, cur_shared(c));
     }
 };
 
@@ -904,7 +953,7 @@ static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
         vec_add_rows((int)c->p.m, 2, v.R, c->p.mp, v.b, v.rP, st);
     }
     prof_mark(c, T_GEMV);
-    if (beside.calls > 0) LP_HIP(launch_chol_solve(cur_M(c), c->p.mp, cur_factor(c), 2, v.R, c->p.Y, st, bt, SolveSteps{pb.fwd_done, -1, true}));
+    if (beside.calls > 0) LP_HIP(launch_chol_solve(cur_M(c), c->p.mp, cur_factor(c), 2, v.R, c->p.Y, st, bt, SolveSteps{pb.fwd_done, -1, true}, cur_shared(c)));
     else if (chol) LP_TRY(chol_solve_refined(c, 2, v.R, bt));                               // :221, :154
     else      LP_HIP(launch_qr_solve(c->p.M, c->p.mp, c->p.mp, c->p.tau, 2, v.R, v.potrf_info, st));   // :155-166
     prof_mark(c, T_TRSV);
@@ -948,6 +997,55 @@ static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
 static int enqueue_iteration(lpipm_ctx* c, int ip, const lpipm_opts* o) {
     LP_TRY(enqueue_head(c));
     return enqueue_tail(c, ip, o);
+}
+
+// The one kept first factor of a shared-matrix batch (Problem::shared_factor): M1 = A.A^T (+ I on the structural slack rows)
+// by ONE A.D.A^T launch for a batch of one member with dinv = the vector of ones, then its factorisation with the merges of
+// the inverses, on the serial schedule every member of a batch goes through.  Formed once it equals what each member would
+// have formed (the library is deterministic and a member's bits do not depend on its place in a batch).  Run by the parent
+// context on its own stream, ahead of the first Cholesky-arm solve after an upload and before any half-batch view is
+// dispatched, so two host threads never race to build it; the flag is up only when the build has completed.  The launch uses
+// member 0's slabs and counters (through a copy of the A.D.A^T resources: the context's own dirty mark covers every member).
+static int ensure_shared_factor(lpipm_ctx* c, const lpipm_opts* o) {
+    if (!c || !o || !c->p.has_problem || !c->p.shared_factor || c->first_valid) return LPIPM_OK;
+    if (o->solver_type != LPIPM_SOLVER_CHOLESKY || !c->first_cache || c->colsplit || c->refine > 0) return LPIPM_OK;
+    if (c->is_view) { g_err_detail = "a half-batch view found the shared first factor unbuilt"; return LPIPM_ERR_HIP; }
+    LP_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->rs.st;
+    const Batch one{1, (long long)c->p.bstride, nullptr, 0};
+    const bool timed = c->profiling != 0;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    auto drop_events = [&]() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
+    if (timed)
+        for (hipEvent_t& e : ev)
+            if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); drop_events(); g_err_detail = "failed to create events"; return LPIPM_ERR_HIP; }
+    auto enqueue = [&]() -> int {
+        if (timed) LP_HIP(hipEventRecord(ev[0], st));
+        AdatRes res = c->p.adat;
+        res.counters_dirty = true;
+        AdatLaunch a{};
+        a.A = c->p.A; a.lda = c->p.npa; a.dinv = c->p.ones; a.M = c->p.M1; a.ldm = c->p.mp; a.M2 = nullptr;
+        a.K = c->p.npa; a.diag_pad_from = (int)c->p.m; a.batch = one; a.shared_a = true;
+        LP_HIP(launch_adat(c->ap, res, a, false, st, nullptr));
+        LP_HIP(launch_slack_diag(c->p.ns, c->p.nx, c->p.ones, c->p.M1, c->p.mp, st, one));   // + I on the slack rows
+        if (timed) LP_HIP(hipEventRecord(ev[1], st));
+        LP_HIP(launch_potrf(c->p.M1, c->p.mp, c->p.mp, *c->p.factor1, c->p.info1, st, one, nullptr, true, nullptr));
+        if (timed) LP_HIP(hipEventRecord(ev[2], st));
+        LP_HIP(hipStreamSynchronize(st));
+        return LPIPM_OK;
+    };
+    const int rc = enqueue();
+    if (rc == LPIPM_OK && timed) {
+        float a_ms = 0.f, p_ms = 0.f;
+        (void)hipEventElapsedTime(&a_ms, ev[0], ev[1]);
+        (void)hipEventElapsedTime(&p_ms, ev[1], ev[2]);
+        c->build_adat_ms = a_ms; c->build_potrf_ms = p_ms;
+    }
+    drop_events();
+    LP_TRY(rc);
+    c->build_launches = 1;
+    c->first_valid = true;
+    return LPIPM_OK;
 }
 
 static void print_row(double alpha, const StatusRec& s) {  // mod.rs:228 + indicators.rs:25-33
@@ -1001,6 +1099,7 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XO
         if (o->solver_type != LPIPM_SOLVER_CHOLESKY && c->p.mp > 16384) return LPIPM_ERR_UNSUPPORTED;  // QR solve keeps the rhs in LDS
     }
     LP_HIP(hipSetDevice(c->device));
+    LP_TRY(ensure_shared_factor(c, o));                   // (a view finds it built: solve_lockstep)
     const int B = c->p.B;
     VecArgs& v = c->p.va;
     StreamRes& rs = c->rs;
@@ -1048,10 +1147,13 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XO
     // The kept first factor (lpipm_ctx::first_valid): the Cholesky arm of a resident problem whose layout has the buffers.
     // Iteration 1 works in them; when they are valid it neither forms nor factors its matrix.  The flag is down from here
     // until iteration 1 has completed, so a solve that fails before that leaves nothing that counts as kept.
+    // A shared-matrix batch's one factor is complete before any solve reads it (ensure_shared_factor) and no solve writes it:
+    // every member of every solve replays it, the first solve included, and its flag stays up.
     const bool use_first = o->solver_type == LPIPM_SOLVER_CHOLESKY && c->first_cache && c->p.keep && !c->colsplit && c->refine <= 0;
     const bool replay = use_first && c->first_valid;
+    if (use_first && c->p.shared_factor && !replay) { g_err_detail = "the shared first factor is not built"; return LPIPM_ERR_HIP; }
     c->first_done = false;
-    if (use_first) c->first_valid = false;
+    if (use_first && !c->p.shared_factor) c->first_valid = false;
     for (uint64_t iteration = 1; iteration <= o->max_iter && running > 0; ++iteration) {   // mod.rs:213
         c->on_first = use_first && iteration == 1;
         c->skip_factor = c->on_first && replay;
@@ -1138,15 +1240,17 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XO
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, rs.ev_begin, rs.ev_end);
         c->times.total_ms = ms;
-        c->times.adat_ms = c->tag_ms[T_ADAT]; c->times.potrf_ms = c->tag_ms[T_POTRF];
+        // (with what building the shared first factor ahead of this solve took, if it was built)
+        c->times.adat_ms = c->tag_ms[T_ADAT] + c->build_adat_ms; c->times.potrf_ms = c->tag_ms[T_POTRF] + c->build_potrf_ms;
         c->times.trsv_ms = c->tag_ms[T_TRSV]; c->times.gemv_ms = c->tag_ms[T_GEMV];
         c->times.vec_ms = c->tag_ms[T_VEC];
         // launches of the kernel (each covers all B members): iteration 1 on a kept factor made none
-        c->times.adat_launches = loop_iterations - (replay && loop_iterations > 0 ? 1 : 0);
+        c->times.adat_launches = loop_iterations - (replay && loop_iterations > 0 ? 1 : 0) + c->build_launches;
         c->times.iterations = loop_iterations;         // iterations of the loop (= the slowest member's count)
         // the speculatively enqueued head of the iteration after the last holds no GEMV pass: every counted pass ran
         c->times.gemv_passes = c->gemv_passes;
     }
+    c->build_adat_ms = c->build_potrf_ms = 0.0; c->build_launches = 0;    // reported (or not asked for)
     for (int i = 0; i < B; ++i) {
         status_out[i] = ret[(size_t)i];
         if (fun_out) fun_out[i] = has_x(ret[(size_t)i]) ? rs.status_host[i].obj : NAN;
@@ -1227,10 +1331,12 @@ static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const XOut& xo, con
         }
         c->halves.push_back(a); c->halves.push_back(b);
     }
+    LP_TRY(ensure_shared_factor(c, o));             // one factor for the batch: built here, once, before both halves
+    c->build_adat_ms = c->build_potrf_ms = 0.0; c->build_launches = 0;   // (nothing is profiled on this path)
     LP_HIP(hipStreamSynchronize(c->rs.st));         // the upload (or whatever else the caller enqueued) precedes both halves
     // the kept first factor: the halves work with the parent's switch and validity, and it is valid afterwards only if both
-    // got through their iteration 1 and returned Ok
-    const bool use_first = c->first_cache && c->p.keep;
+    // got through their iteration 1 and returned Ok (a shared-matrix batch's one factor is only read: it stays valid)
+    const bool use_first = c->first_cache && c->p.keep && !c->p.shared_factor;
     for (lpipm_ctx* v : c->halves) { v->first_cache = c->first_cache; v->first_valid = c->first_valid; }
     if (use_first) c->first_valid = false;
     int rc[2] = {LPIPM_OK, LPIPM_OK};
@@ -1576,6 +1682,65 @@ extern "C" int lpipm_update_vectors(lpipm_ctx* c, const double* b, const double*
     LP_HIP(hipMemcpyAsync((void*)c->p.va.c, cc, c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));   // the caller's arrays are free again from here
     return LPIPM_OK;
+}
+
+// At least `count` doubles in the context's pinned staging block and in its device image.
+static int stage_grow(lpipm_ctx* c, size_t count) {
+    if (count <= c->stage_cap) return LPIPM_OK;
+    LP_HIP(hipStreamSynchronize(c->rs.st));
+    if (c->stage_host) { (void)hipHostFree(c->stage_host); c->stage_host = nullptr; }
+    if (c->stage_dev) { (void)hipFree(c->stage_dev); c->stage_dev = nullptr; }
+    c->stage_cap = 0;
+    LP_HIP(hipHostMalloc((void**)&c->stage_host, count * sizeof(double)));
+    LP_HIP(hipMalloc((void**)&c->stage_dev, count * sizeof(double)));
+    c->stage_cap = count;
+    return LPIPM_OK;
+}
+// New b / c / c0 for every member of the resident batch.  host: per-member arrays, staged (with c0) in the pinned block,
+// sent with one copy and distributed from its device image; otherwise b_dev / c_dev are the caller's packed device blocks and
+// only c0 is staged.  One scatter launch either way.  A, the layout, the views and whatever factor is kept stay as they are.
+static int update_lockstep_impl(lpipm_ctx* c, uint64_t count, const double* const* b, const double* const* cc, bool host,
+                                const double* b_dev, uint64_t ldb, const double* c_dev, uint64_t ldc, const double* c0) {
+    if (!c) return LPIPM_ERR_BAD_ARGUMENT;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (c->colsplit || (c->p.from_parts && !c->p.shared_a)) return LPIPM_ERR_UNSUPPORTED;
+    const bool has_b = host ? b != nullptr : b_dev != nullptr, has_c = host ? cc != nullptr : c_dev != nullptr;
+    if ((!has_b && !has_c) || count != (uint64_t)c->p.B) return LPIPM_ERR_BAD_ARGUMENT;
+    const size_t B = (size_t)c->p.B, m = (size_t)c->p.m;
+    const size_t nc = c->p.from_parts ? (size_t)c->p.nx : (size_t)c->p.n;      // parts: c = [c; 0], the slack costs stay 0
+    if (host) {
+        for (size_t i = 0; i < B; ++i)
+            if ((has_b && !b[i]) || (has_c && !cc[i])) return LPIPM_ERR_BAD_ARGUMENT;
+    } else if ((has_b && ldb < m) || (has_c && ldc < nc)) return LPIPM_ERR_BAD_ARGUMENT;
+    LP_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->rs.st;
+    // the staged block: [b rows | c rows | c0], each part only if it is sent from the host
+    const size_t nb_st = host && has_b ? B * m : 0, nc_st = host && has_c ? B * nc : 0, n0_st = c0 ? B : 0;
+    const size_t total = nb_st + nc_st + n0_st;
+    if (total) {
+        LP_TRY(stage_grow(c, total));
+        double* h = c->stage_host;
+        for (size_t i = 0; i < B && nb_st; ++i) std::memcpy(h + i * m, b[i], m * sizeof(double));
+        for (size_t i = 0; i < B && nc_st; ++i) std::memcpy(h + nb_st + i * nc, cc[i], nc * sizeof(double));
+        if (n0_st) std::memcpy(h + nb_st + nc_st, c0, B * sizeof(double));
+        LP_HIP(hipMemcpyAsync(c->stage_dev, h, total * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    ScatterRows<double> w;
+    if (has_b) { w.seg[0].dst = (double*)c->p.va.b; w.seg[0].src = host ? c->stage_dev : b_dev; w.seg[0].ld = (long long)(host ? m : ldb); w.seg[0].len = (int)m; }
+    if (has_c) { w.seg[1].dst = (double*)c->p.va.c; w.seg[1].src = host ? c->stage_dev + nb_st : c_dev; w.seg[1].ld = (long long)(host ? nc : ldc); w.seg[1].len = (int)nc; }
+    if (c0)    { w.seg[2].dst = c->p.va.S + S_C0; w.seg[2].src = c->stage_dev + nb_st + nc_st; w.seg[2].ld = 1; w.seg[2].len = 1; }
+    vec_scatter_rows(w, st, Batch{c->p.B, (long long)c->p.bstride, nullptr, 0});
+    LP_HIP(hipGetLastError());
+    LP_HIP(hipStreamSynchronize(st));   // the staging block (and with it the caller's arrays) is free again from here
+    return LPIPM_OK;
+}
+extern "C" int lpipm_update_lockstep_vectors(lpipm_ctx* c, uint64_t count, const double* const* b, const double* const* cc,
+                                             const double* c0) {
+    return update_lockstep_impl(c, count, b, cc, true, nullptr, 0, nullptr, 0, c0);
+}
+extern "C" int lpipm_update_lockstep_vectors_device(lpipm_ctx* c, uint64_t count, const void* b_dev, uint64_t ldb,
+                                                    const void* c_dev, uint64_t ldc, const double* c0) {
+    return update_lockstep_impl(c, count, nullptr, nullptr, false, (const double*)b_dev, ldb, (const double*)c_dev, ldc, c0);
 }
 
 extern "C" int lpipm_set_profiling(lpipm_ctx* c, int on) {

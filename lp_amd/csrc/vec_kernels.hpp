@@ -94,6 +94,13 @@ void vec_pack_tiles(double* M, long long ld, const int2* tiles, int ntiles, doub
 void vec_rows_copy(int mp, int nrhs, double* dst, const double* src, hipStream_t st, const Batch& bt = Batch{});
 void vec_rows_add(int mp, int nrhs, double* dst, const double* src, hipStream_t st, const Batch& bt = Batch{});
 void vec_copy_lower(const double* M, double* M0, long long ld, int mp, hipStream_t st, const Batch& bt = Batch{});
+// Up to SCATTER_SEGS packed row blocks into the arenas in one launch: member z of the launch gets src[z * ld .. + len) at its
+// dst (dst is LP 0's pointer; ld in elements, 0 = the same row for every member).  A segment with a null dst is skipped.
+// Members are written whether finished or not (lpipm_update_lockstep_vectors; the shared first factor's pivot word).
+constexpr int SCATTER_SEGS = 3;
+template <typename T> struct ScatterSeg { T* dst = nullptr; const T* src = nullptr; long long ld = 0; int len = 0; };
+template <typename T> struct ScatterRows { ScatterSeg<T> seg[SCATTER_SEGS]; };
+template <typename T> void vec_scatter_rows(const ScatterRows<T>& a, hipStream_t st, const Batch& bt);
 
 
 }  // namespace lpipm
