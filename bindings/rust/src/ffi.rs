@@ -122,6 +122,10 @@ extern "C" {
     ) -> c_int;
     // Device bytes held for the resident problem(s): arenas + shared matrix + factor workspace.
     pub fn lpipm_get_resident_bytes(ctx: *const lpipm_ctx, bytes_out: *mut u64) -> c_int;
+    // Power-of-two row / column equilibration of every later upload (passes 1..64; 0 = off, the default), and the int32
+    // exponents in use for a resident member: row_exp_out[m], col_exp_out[n].  x comes back in the caller's units.
+    pub fn lpipm_set_scaling(ctx: *mut lpipm_ctx, passes: c_int) -> c_int;
+    pub fn lpipm_get_scaling(ctx: *const lpipm_ctx, member: u64, row_exp_out: *mut i32, col_exp_out: *mut i32) -> c_int;
 
     // One LP split by columns over ranks (BASELINE config 5): the caller supplies the all-reduce
     // (e.g. ncclAllReduce on `stream`); op 0 = sum, 1 = min.

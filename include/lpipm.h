@@ -175,6 +175,30 @@ int lpipm_update_lockstep_vectors_device(lpipm_ctx* ctx, uint64_t count, const v
  * with on = 0 has no shared set, and every member forms and factors its own iteration 1.  Default: on. */
 int lpipm_set_first_factor_cache(lpipm_ctx* ctx, int on);
 
+/* Power-of-two row and column equilibration of the resident matrix, for problems that mix units (the reference has none; it
+ * leaves a comment slot, mod.rs:164).  With integer exponents kr[i], kc[j], all zero at the start, and X the stored structural
+ * block of A (the slack columns of a verified hint or of an *_ub_eq upload are not part of it), one pass takes
+ * S_ij = |ldexp(X_ij, kr[i] + kc[j])| from the original X_ij, the row and column maxima of S (NaNs ignored), and for every
+ * finite maximum a > 0 with frexp(a) = (f, e) adds -(e floordiv 2) to that row's or column's exponent; a maximum in [0.5, 2)
+ * stays.  After the last pass A_ij <- ldexp(A_ij, kr[i] + kc[j]), b_i <- ldexp(b_i, kr[i]), c_j <- ldexp(c_j, kc[j]) on the
+ * device; the slack column of `ub` row i gets kc = -kr[i], so its entry stays exactly 1 and the block [I; 0] stays unstored.
+ * The solve then runs unchanged on the scaled problem: it is bit-identical to an ordinary solve of the same LP scaled on the
+ * host with these exponents (powers of two: exact), and x_j / tau is returned as ldexp(x_j / tau, kc[j]) to every
+ * destination.  `fun` is computed from the scaled vectors (the same number); the iteration log, the `disp` table and `tol`
+ * refer to the SCALED problem.  The kept first factor is that of the scaled matrix; lpipm_update_vectors and
+ * lpipm_update_lockstep_vectors[_device] scale the new b and c with the kept exponents.  A lockstep batch whose members own
+ * their matrices has one set of exponents per member, a shared-matrix batch one set.  lpipm_solve_batch* passes the switch on
+ * to every member.  The lpipm_k_* entries that work on the uploaded problem see the scaled one.  lpipm_solve_f32 ignores the
+ * switch; lpipm_upload_nsplit with scaling on returns LPIPM_ERR_UNSUPPORTED.  The exponents (4 (mp + np) bytes per set) and the
+ * slabs of the maxima pass live in an allocation of their own, made only while scaling is on (lpipm_get_resident_bytes
+ * counts it).
+ * passes = 0: off (default).  1..64: that many equilibration passes at every later upload on this ctx.  Takes effect
+ * with the next upload, like lpipm_set_first_factor_cache.  > 64 or < 0: LPIPM_ERR_BAD_ARGUMENT. */
+int lpipm_set_scaling(lpipm_ctx* ctx, int passes);
+/* The exponents in use for resident member `member` (0 for a single LP and for a shared-matrix batch): row_exp_out[m],
+ * col_exp_out[n] (int32; n counts slack columns too).  All zero when scaling is off.  LPIPM_ERR_NO_PROBLEM before an upload. */
+int lpipm_get_scaling(const lpipm_ctx* ctx, uint64_t member, int32_t* row_exp_out, int32_t* col_exp_out);
+
 /* InteriorPoint::solve_normal_form + the `fun` of solve (mod.rs:199-240, :165).
  *   x_slack_out[n] : x / tau  (mod.rs:231); ALSO filled for LPIPM_ITERATION_LIMIT (mod.rs:237-239)
  *   fun_out        : c . x_slack + c0  (linear_program.rs:61-63)
@@ -268,7 +292,7 @@ int lpipm_upload_lockstep_shared_ub_eq(lpipm_ctx* ctx, uint64_t count, uint64_t 
                                        uint64_t lda_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq,
                                        const double* const* b, const double* const* c, const double* c0 /* nullable */);
 /* Device bytes the context holds for its resident problem(s) (arenas + shared matrix with the batch's one kept first factor +
- * factor workspace); 0 before any upload. */
+ * factor workspace, and the exponent block of lpipm_set_scaling while scaling is on); 0 before any upload. */
 int lpipm_get_resident_bytes(const lpipm_ctx* ctx, uint64_t* bytes_out);
 /* lpipm_solve_batch with device-resident results: member i's x / tau goes to x_dev_out + i * row_stride doubles
  * (row_stride >= max n[i]); everything else as lpipm_solve_batch. */

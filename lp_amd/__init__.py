@@ -331,6 +331,21 @@ class Context:
         _raise_for(_capi.lib().lpipm_set_first_factor_cache(self._h, int(bool(on))))
         return self
 
+    def set_scaling(self, passes: int = 8):
+        """Power-of-two row and column equilibration of every later upload on this context (lpipm_set_scaling): `passes`
+        passes (1..64), 0 = off (the default).  Solutions come back in the caller's units; the iteration log and `tol` refer
+        to the scaled problem."""
+        _raise_for(_capi.lib().lpipm_set_scaling(self._h, int(passes)))
+        return self
+
+    def scaling(self, member: int = 0):
+        """-> (row_exp, col_exp): the int32 exponents in use for resident member `member` (lpipm_get_scaling; one set for a
+        single LP and for a shared-matrix batch).  All zero when scaling is off."""
+        kr, kc = np.zeros(self.m, dtype=np.int32), np.zeros(self.n, dtype=np.int32)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        _raise_for(_capi.lib().lpipm_get_scaling(self._h, int(member), ip(kr), ip(kc)))
+        return kr, kc
+
     def set_collective(self, rank: int, world: int, collective):
         """`collective.cfn` is an lpipm_allreduce_fn thunk (lp_amd.colsplit.TorchCollective); kept alive here."""
         self._collective = collective

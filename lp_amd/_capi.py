@@ -48,6 +48,8 @@ SYMBOLS = {
     "lpipm_update_lockstep_vectors": (C.c_int, [_vp, _u64, _dpp, _dpp, _dp]),
     "lpipm_update_lockstep_vectors_device": (C.c_int, [_vp, _u64, _vp, _u64, _vp, _u64, _dp]),
     "lpipm_set_first_factor_cache": (C.c_int, [_vp, C.c_int]),
+    "lpipm_set_scaling": (C.c_int, [_vp, C.c_int]),
+    "lpipm_get_scaling": (C.c_int, [_vp, _u64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lpipm_solve": (C.c_int, [_vp, C.POINTER(Opts), _dp, _dp, C.POINTER(_u64), C.POINTER(IterRow)]),
     "lpipm_solve_device": (C.c_int, [_vp, C.POINTER(Opts), _vp, _dp, C.POINTER(_u64), C.POINTER(IterRow)]),
     "lpipm_solve_batch": (C.c_int, [_vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _dpp, _dpp, _dpp, _dp,

@@ -321,6 +321,29 @@ hipError_t launch_slack_diag(int ns, int nx, const double* d, double* M, int64_t
 hipError_t launch_gemv_t_reduce(const double* Upart, int nsplit, int nrhs, int np, double* U,
                                 int64_t ldu, hipStream_t st);
 
+// ---------------------------------------------------------------- equilibration (kernels_scale.hip)
+// Power-of-two row and column scaling of the resident matrix (lpipm_set_scaling): int32 exponents kr[mp], kc[np] per exponent
+// set -- one set per member of a batch whose members own their matrices, ONE for a single LP and for a shared-matrix batch
+// (estride 0) -- and the slabs of the maxima pass, all in one allocation of the context that exists only while scaling is on.
+struct ScaleBuf {
+    int32_t* kr = nullptr;       // set 0's row exponents; set z's are estride elements * z further
+    int32_t* kc = nullptr;
+    long long estride = 0;
+    double* rslab = nullptr;     // [set][column chunk][mp] row maxima of a chunk of columns
+    double* cslab = nullptr;     // [set][row block][npa] column maxima of a block of rows
+    int sets = 0;
+};
+size_t scale_buf_bytes(int mp, int np, int npa, int sets);
+ScaleBuf scale_buf_place(void* base, int mp, int np, int npa, int sets);   // base: scale_buf_bytes, exponents zeroed
+// `passes` passes of maxima + exponent update over the stored block(s) A (mp x npa, of which m x nx count; ns structural
+// slack columns), then the scaling of A in place.  bt: the matrices, one per exponent set (count == 1 for a shared one).
+hipError_t launch_equilibrate(const ScaleBuf& s, double* A, int m, int mp, int nx, int npa, int ns, int passes, hipStream_t st,
+                              const Batch& bt);
+// b[i] <- ldexp(b[i], kr[i]) (i < m), c[j] <- ldexp(c[j], kc[j]) (j < nc) for every member of bt; b or c may be null.
+hipError_t launch_scale_vectors(const ScaleBuf& s, double* b, int m, double* c, int nc, hipStream_t st, const Batch& bt);
+// x[j] <- ldexp(x[j], kc[j]) (j < n) for every member of bt: the scaled problem's solution in the caller's units.
+hipError_t launch_unscale_x(const ScaleBuf& s, double* x, int n, hipStream_t st, const Batch& bt);
+
 // ---------------------------------------------------------------- probe (kernels_probe.hip)
 hipError_t launch_mfma_probe(int iters, double* sink, int blocks, hipStream_t st);
 

@@ -97,6 +97,12 @@ struct Problem {
     bool shared_factor = false;
     double* ones = nullptr;
     bool from_parts = false;     // uploaded as ub / eq blocks (lpipm_upload_ub_eq): b and c are not in the caller's slack form
+    // Equilibration (lpipm_set_scaling): the exponents and the maxima slabs, in an allocation of their own that exists only
+    // for a problem uploaded with scaling on.  scale_passes > 0: the resident A, b and c are the scaled ones.
+    int scale_passes = 0;
+    void* scale_mem = nullptr;
+    size_t scale_bytes = 0;
+    ScaleBuf sc;
     AdatRes adat;                // what the A.D.A^T launches use on the device (kernels_adat.hip); adat.ngroups() > 0: one LP split by
                                  //   columns over ranks, M is reduced column group by column group behind the running launch
     double* gs = nullptr;        // 8 doubles: sums / minima that must be reduced across ranks (n-split mode)
@@ -119,6 +125,7 @@ struct lpipm_ctx {
     // and every later solve on the same upload starts from them instead of running A.D.A^T and the factorisation again.
     FactorPlan plan1;
     bool first_cache = true;     // lpipm_set_first_factor_cache
+    int scaling = 0;             // lpipm_set_scaling: equilibration passes of every later upload (0: none)
     bool first_valid = false;    // M1 / plan1 / info1 hold iteration 1 of this upload (every member's); dropped by any upload.  A
                                  //   half-batch view holds the parent's value for the length of one solve
     bool first_done = false;     // the last solve of this context (or view) got through its iteration 1
@@ -409,6 +416,7 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     if (c->rs.st) (void)hipStreamSynchronize(c->rs.st);      // before the buffers go
     if (c->p.arena) (void)hipFree(c->p.arena);
     if (c->p.a_shared) (void)hipFree(c->p.a_shared);
+    if (c->p.scale_mem) (void)hipFree(c->p.scale_mem);
     if (c->stage_dev) (void)hipFree(c->stage_dev);
     if (c->stage_host) (void)hipHostFree(c->stage_host);
     adat_lists_destroy(c->p.adat);
@@ -544,6 +552,26 @@ static bool slack_hint_holds(int count, uint64_t m, uint64_t n, const double* co
     return true;
 }
 
+// The exponent block of the upload being made: `sets` exponent sets for the padded geometry when the context scales, none
+// otherwise (what a previous upload left is freed).  Exponents start at zero.
+static int scale_setup(lpipm_ctx* c, int mp, int np, int npa, int sets) {
+    Problem& p = c->p;
+    const size_t need = c->scaling > 0 ? scale_buf_bytes(mp, np, npa, sets) : 0;
+    if (need != p.scale_bytes) {
+        LP_HIP(hipStreamSynchronize(c->rs.st));
+        if (p.scale_mem) { LP_HIP(hipFree(p.scale_mem)); p.scale_mem = nullptr; }
+        p.scale_bytes = 0;
+        if (need) LP_HIP(hipMalloc(&p.scale_mem, need));
+        p.scale_bytes = need;
+    }
+    p.scale_passes = c->scaling;
+    p.sc = ScaleBuf{};
+    if (!need) return LPIPM_OK;
+    LP_HIP(hipMemsetAsync(p.scale_mem, 0, need, c->rs.st));
+    p.sc = scale_buf_place(p.scale_mem, mp, np, npa, sets);
+    return LPIPM_OK;
+}
+
 // count LPs of one geometry (count == 1: the ordinary upload).  A/b/cc/c0: one entry per LP.
 // n_slack: the structural hint of lpipm_upload_slack, for every member alike.  It is verified on every member (on the one
 // matrix of a shared batch); if any member's last n_slack columns are not [I; 0] the whole upload is dense.
@@ -626,6 +654,8 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
         LP_HIP(hipMemsetAsync(c->p.arena, 0, c->p.arena_bytes, st));
         if (c->p.a_shared) LP_HIP(hipMemsetAsync(c->p.a_shared, 0, c->p.a_shared_bytes, st));   // (a smaller m or n than before)
     }
+    c->p.has_problem = false;     // until this upload is complete
+    LP_TRY(scale_setup(c, mp, np, npa, shared ? 1 : count));
     c->p.m = m; c->p.n = n;
     c->p.ns = (int)n_slack; c->p.nx = (int)nx;
     c->p.from_parts = parts != nullptr;
@@ -666,6 +696,12 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
         if (b) LP_HIP(hipMemcpyAsync((char*)c->p.va.b + off, b[i], m * sizeof(double), hipMemcpyHostToDevice, st));
         LP_HIP(hipMemcpyAsync((char*)c->p.va.c + off, cc[i], nc * sizeof(double), hipMemcpyHostToDevice, st));
         LP_HIP(hipMemcpyAsync((char*)(c->p.va.S + S_C0) + off, &c0v[i], sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (c->p.scale_passes > 0) {   // equilibrate what was just copied: the solves see the scaled problem only
+        const Batch members{count, (long long)c->p.bstride, nullptr, 0};
+        LP_HIP(launch_equilibrate(c->p.sc, c->p.A, (int)m, mp, (int)nx, npa, (int)n_slack, c->p.scale_passes, st,
+                                  shared ? Batch{} : members));
+        LP_HIP(launch_scale_vectors(c->p.sc, (double*)c->p.va.b, (int)m, (double*)c->p.va.c, (int)n, st, members));
     }
     LP_HIP(hipStreamSynchronize(st));   // the caller's arrays, c0v and onesv are free again from here
     c->p.has_problem = true;
@@ -1212,6 +1248,9 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XO
         XRank xrf{xrank_fn, c};
         LP_TRY(vec_final_x(v, c->p.xout, st, c->colsplit ? &xrf : nullptr));
         LP_HIP(hipGetLastError());
+        // a scaled problem's x back in the caller's units (fun is the scaled vectors' product: the same number)
+        if (c->p.scale_passes > 0)
+            LP_HIP(launch_unscale_x(c->p.sc, c->p.xout, (int)c->p.n, st, Batch{B, (long long)c->p.bstride, nullptr, c->p.bt.first}));
         const size_t xbytes = c->p.n * sizeof(double);
         for (int i = 0; i < B; ++i) {
             if (!has_x(ret[(size_t)i])) continue;
@@ -1387,7 +1426,7 @@ extern "C" int lpipm_upload_lockstep_shared_ub_eq(lpipm_ctx* c, uint64_t count, 
 }
 extern "C" int lpipm_get_resident_bytes(const lpipm_ctx* c, uint64_t* bytes_out) {
     if (!c || !bytes_out) return LPIPM_ERR_BAD_ARGUMENT;
-    *bytes_out = c->p.has_problem ? (uint64_t)(c->p.arena_bytes + c->p.a_shared_bytes + c->p.adat.list_bytes) : 0;
+    *bytes_out = c->p.has_problem ? (uint64_t)(c->p.arena_bytes + c->p.a_shared_bytes + c->p.adat.list_bytes + c->p.scale_bytes) : 0;
     return LPIPM_OK;
 }
 extern "C" int lpipm_solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, double* const* x_slack_out, double* fun_out,
@@ -1501,6 +1540,7 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             }
             auto upload_chunk = [&](lpipm_ctx* w, const Chunk& ch) -> int {
                 (void)hipSetDevice(w->device);
+                w->scaling = c->scaling;
                 return upload_impl(w, (int)ch.g, m[i], n[i], ch.A.data(), n[i], ch.b.data(), ch.c.data(), ch.c0.data(), ns[i],
                                    nullptr, false, true, false);
             };
@@ -1555,6 +1595,7 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
     std::atomic<int> fatal{LPIPM_OK};
     auto run = [&](lpipm_ctx* w) {
         (void)hipSetDevice(w->device);
+        w->scaling = c->scaling;
         lpipm_opts opts = *o;
         opts.disp = 0;   // interleaved tables from concurrent members would be unreadable
         for (;;) {
@@ -1641,6 +1682,7 @@ extern "C" int lpipm_set_collective_on_stream(lpipm_ctx* c, int on) {
 extern "C" int lpipm_upload_nsplit(lpipm_ctx* c, uint64_t m, uint64_t n_total, uint64_t n_local, const double* A_local,
                                    uint64_t lda, const double* b, const double* c_local, double c0) {
     if (!c || n_local == 0 || n_local > n_total) return LPIPM_ERR_BAD_ARGUMENT;
+    if (c->scaling > 0) return LPIPM_ERR_UNSUPPORTED;      // row maxima of a column split would need the collective
     const int rc = upload_impl(c, 1, m, n_local, &A_local, lda, &b, &c_local, &c0, 0, nullptr, false, false, false);
     if (rc != LPIPM_OK) return rc;
     if (c->world > 1) {
@@ -1672,6 +1714,28 @@ extern "C" int lpipm_set_first_factor_cache(lpipm_ctx* c, int on) {
     return LPIPM_OK;
 }
 
+extern "C" int lpipm_set_scaling(lpipm_ctx* c, int passes) {
+    if (!c || passes < 0 || passes > 64) return LPIPM_ERR_BAD_ARGUMENT;
+    c->scaling = passes;          // the exponents come and go with the next upload (upload_impl)
+    return LPIPM_OK;
+}
+extern "C" int lpipm_get_scaling(const lpipm_ctx* c, uint64_t member, int32_t* row_exp_out, int32_t* col_exp_out) {
+    if (!c || !row_exp_out || !col_exp_out) return LPIPM_ERR_BAD_ARGUMENT;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (member >= (uint64_t)c->p.B) return LPIPM_ERR_BAD_ARGUMENT;
+    if (c->p.scale_passes <= 0) {
+        std::memset(row_exp_out, 0, c->p.m * sizeof(int32_t));
+        std::memset(col_exp_out, 0, c->p.n * sizeof(int32_t));
+        return LPIPM_OK;
+    }
+    LP_HIP(hipSetDevice(c->device));
+    const long long off = (long long)member * c->p.sc.estride;   // (one set for a shared-matrix batch: estride 0)
+    LP_HIP(hipMemcpyAsync(row_exp_out, c->p.sc.kr + off, c->p.m * sizeof(int32_t), hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(hipMemcpyAsync(col_exp_out, c->p.sc.kc + off, c->p.n * sizeof(int32_t), hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
+    return LPIPM_OK;
+}
+
 extern "C" int lpipm_update_vectors(lpipm_ctx* c, const double* b, const double* cc) {
     if (!c || !b || !cc) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
@@ -1680,6 +1744,8 @@ extern "C" int lpipm_update_vectors(lpipm_ctx* c, const double* b, const double*
     // (the padding beyond m and n stays zero; A, and with it the kept first factor, is not touched)
     LP_HIP(hipMemcpyAsync((void*)c->p.va.b, b, c->p.m * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
     LP_HIP(hipMemcpyAsync((void*)c->p.va.c, cc, c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
+    if (c->p.scale_passes > 0)                // the kept exponents: A, and its kept factor, are the scaled ones
+        LP_HIP(launch_scale_vectors(c->p.sc, (double*)c->p.va.b, (int)c->p.m, (double*)c->p.va.c, (int)c->p.n, c->rs.st, Batch{}));
     LP_HIP(hipStreamSynchronize(c->rs.st));   // the caller's arrays are free again from here
     return LPIPM_OK;
 }
@@ -1731,6 +1797,9 @@ static int update_lockstep_impl(lpipm_ctx* c, uint64_t count, const double* cons
     if (c0)    { w.seg[2].dst = c->p.va.S + S_C0; w.seg[2].src = c->stage_dev + nb_st + nc_st; w.seg[2].ld = 1; w.seg[2].len = 1; }
     vec_scatter_rows(w, st, Batch{c->p.B, (long long)c->p.bstride, nullptr, 0});
     LP_HIP(hipGetLastError());
+    if (c->p.scale_passes > 0)                // only what was just replaced, with the kept exponents
+        LP_HIP(launch_scale_vectors(c->p.sc, has_b ? (double*)c->p.va.b : nullptr, (int)m, has_c ? (double*)c->p.va.c : nullptr, (int)nc,
+                                    st, Batch{c->p.B, (long long)c->p.bstride, nullptr, 0}));
     LP_HIP(hipStreamSynchronize(st));   // the staging block (and with it the caller's arrays) is free again from here
     return LPIPM_OK;
 }
