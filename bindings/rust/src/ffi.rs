@@ -57,6 +57,11 @@ extern "C" {
         ctx: *mut lpipm_ctx, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, b_ub: *const f64, m_eq: u64,
         a_eq: *const f64, lda_eq: u64, b_eq: *const f64, c: *const f64, c0: f64,
     ) -> c_int;
+    /// The tall inequality form: `ub` rows only, many more rows than columns; lpipm_solve then factors the n x n reduced
+    /// system K = X^T W_s X + E_x instead of the m_ub x m_ub normal matrix (Cholesky arm only; see include/lpipm.h).
+    pub fn lpipm_upload_ub_tall(
+        ctx: *mut lpipm_ctx, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, b_ub: *const f64, c: *const f64, c0: f64,
+    ) -> c_int;
     pub fn lpipm_solve(
         ctx: *mut lpipm_ctx, opts: *const lpipm_opts, x_slack_out: *mut f64, fun_out: *mut f64,
         iterations_out: *mut u64, log: *mut lpipm_iter_row,

@@ -130,6 +130,29 @@ int lpipm_upload_ub_eq(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const double* 
                        const double* b_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq, const double* b_eq,
                        const double* c, double c0);
 
+/* The tall inequality form: a pure-`ub` LP, min c^T x, A_ub.x <= b_ub, x >= 0, with many more rows than columns (cover and
+ * resource models, L1 / L-infinity fits, scenario cuts, discretised semi-infinite constraints).  Arguments as lpipm_upload_ub_eq
+ * without its `eq` block.  The slack form is A = [X I], X = A_ub (m_ub x n), and its normal matrix X.D_x.X^T + D_s has one row
+ * per constraint; after this upload lpipm_solve / lpipm_solve_device factor instead the n x n SPD matrix
+ *   K = X^T.diag(W_s).X + diag(E_x),   W_s = z_s / x_s (slack part of the iterate),   E_x = z_x / x_x (structural part),
+ * and sym_solve(r1, r2) (newton_equations.rs:214-225), r1 = [r1_x; r1_s], reads
+ *   t = W_s*r2 + r1_s;  g = X^T.t - r1_x;  u_x = K^-1 g;  u_s = r2 - X.u_x;  v = W_s*u_s + r1_s;  u = [u_x; u_s]
+ * -- the same Newton system, so every solve agrees with lpipm_upload_ub_eq on the same LP to rounding (same status and
+ * iteration count on every test; no bit-identity).  K is built by the A.D.A^T kernels from a resident transpose of X (written
+ * once per upload, after the equilibration of lpipm_set_scaling, which works as for any upload: both copies carry the same
+ * exponents) and factored by the Cholesky chain; nothing the context holds grows as m_ub^2 (lpipm_get_resident_bytes counts the
+ * transpose).  x_slack_out has n + m_ub entries, slack values last; return codes, fun, the iteration log, the `disp` table and
+ * the phase times are as after lpipm_upload_ub_eq (K's build in adat_ms, its factorisation in potrf_ms; a failed pivot of K is
+ * LPIPM_NUMERICAL_PROBLEM, as a failed pivot of M is).  m_ub = 0: LPIPM_UNCONSTRAINED.
+ * Scope.  Cholesky arm only: lpipm_solve with solver_type 1 or 2 returns LPIPM_ERR_UNSUPPORTED, and so do
+ * lpipm_update_vectors (as after lpipm_upload_ub_eq), this upload on a context of a column split (lpipm_set_collective with
+ * world > 1) or with the opt-in refined solves, and lpipm_k_adat (there is no M; lpipm_k_tall_normal returns K).  The first
+ * iteration's factor is not kept (as for the QR arms).  `eq` rows (the reduced system is then a saddle point, not SPD) and
+ * lockstep or shared-matrix batches of tall LPs are not built.  lpipm_k_iteration, lpipm_k_gemv_n, lpipm_k_gemv_t and
+ * lpipm_k_gemv_dual work as on any other upload. */
+int lpipm_upload_ub_tall(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub, const double* b_ub,
+                         const double* c, double c0);
+
 /* New b and c for the resident problem of lpipm_upload / lpipm_upload_slack: b[m] and c[n] in that upload's own form (c with
  * its slack entries).  A stays where it is, so a sweep over right-hand sides or costs, or a sequence of LPs over one
  * constraint matrix, pays for the upload of A once -- and, with it, for the first iteration's factor (below), which depends
@@ -333,7 +356,16 @@ int lpipm_get_phase_times(const lpipm_ctx* ctx, lpipm_phase_times* out);
 /* newton_equations.rs:54-57:  M = A . diag(dinv) . A^T.  dinv[n]; M_out m x m row-major, LOWER
  * triangle valid (the strict upper triangle is unspecified).  `ms_out` (nullable) gets the device
  * time of the kernel launch(es) averaged over `repeats` (>= 1) back-to-back launches. */
-int lpipm_k_adat(lpipm_ctx* ctx, const double* dinv, double* M_out, int repeats, double* ms_out);
+int lpipm_k_adat(lpipm_ctx* ctx, const double* dinv, double* M_out, int repeats, double* ms_out);   /* tall upload: LPIPM_ERR_UNSUPPORTED */
+/* On a tall upload (lpipm_upload_ub_tall), with nx its structural columns, m its rows, n = nx + m and dinv[n] = x / z:
+ * K_out (nx x nx row-major, LOWER triangle valid) = X^T.diag(1 / dinv_s).X + diag(1 / dinv_x).  Any other upload:
+ * LPIPM_ERR_UNSUPPORTED. */
+int lpipm_k_tall_normal(lpipm_ctx* ctx, const double* dinv, double* K_out);
+/* The reduced sym_solve (newton_equations.rs:214-225) on a tall upload at the given dinv[n], for nrhs (1|2) right-hand sides:
+ * R1 nrhs x n, R2 nrhs x m -> U_out nrhs x n, V_out nrhs x m, with M.V = R2 + A.(dinv * R1), U = dinv * (A^T.V - R1) in exact
+ * arithmetic.  info_out (nullable): pivot failure of K as lpipm_k_potrf.  The iterate of the context is overwritten. */
+int lpipm_k_tall_sym_solve(lpipm_ctx* ctx, const double* dinv, int nrhs, const double* R1, const double* R2, double* U_out,
+                           double* V_out, int32_t* info_out);
 /* newton_equations.rs:129-131: in-place lower Cholesky of the m x m row-major matrix M (lower
  * triangle read, lower triangle written).  info_out: 0, or k+1 for the first non-positive pivot. */
 int lpipm_k_potrf(lpipm_ctx* ctx, uint64_t m, double* M_inout, int32_t* info_out, int repeats,

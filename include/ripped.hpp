@@ -200,6 +200,10 @@ public:
                o_.solver_type == r.o_.solver_type && o_.disp == r.o_.disp;
     }
     const lpipm_opts& opts() const { return o_; }
+    // Opt-in (not in the reference): a problem built from `ub` rows only is uploaded in the tall inequality form
+    // (lpipm_upload_ub_tall) -- the solve factors the n x n reduced system instead of the m_ub x m_ub normal matrix.  For LPs
+    // with many more rows than columns; Cholesky arm only.  Problems with `eq` rows are solved as before.
+    InteriorPoint& tall_form(bool on = true) { tall_ = on; return *this; }
 
     // mod.rs:161-168.  One context (stream + device buffers) per call keeps `solve(&self)` stateless
     // and re-entrant like the reference; callers that solve many problems can hold an lpipm_ctx.
@@ -208,6 +212,11 @@ public:
         raise_for(lpipm_create(device_, &ctx));
         struct Guard { lpipm_ctx* c; ~Guard() { lpipm_destroy(c); } } guard{ctx};
         const Matrix& A = problem.A();
+        if (tall_ && problem.n_slack() == A.rows && problem.n_slack() < A.cols)
+            // `ub` rows only: A = [X I], X = the first cols - n_slack columns (lda = cols); the slack costs are zero
+            raise_for(lpipm_upload_ub_tall(ctx, A.cols - problem.n_slack(), A.rows, A.data.data(), A.cols, problem.b().data(),
+                                           problem.c().data(), problem.c0()));
+        else
         // n_slack tells the backend that the last columns are the [I; 0] slack block (linear_program.rs:147-161)
         raise_for(lpipm_upload_slack(ctx, A.rows, A.cols, A.data.data(), A.cols, problem.b().data(),
                                      problem.c().data(), problem.c0(), problem.n_slack()));
@@ -239,6 +248,7 @@ public:
 private:
     lpipm_opts o_;
     int device_;
+    bool tall_ = false;
 };
 
 inline InteriorPoint InteriorPointBuilder::build() const {

@@ -253,7 +253,19 @@ class Context:
         except Exception:
             pass
 
-    def upload(self, problem: Problem, use_slack_structure: bool = True):
+    def upload(self, problem: Problem, use_slack_structure: bool = True, tall: bool = False):
+        """tall=True: the tall inequality form (lpipm_upload_ub_tall) -- a Problem with `ub` rows only, usually many more of
+        them than columns; the solves then factor the n x n reduced system instead of the m x m normal matrix."""
+        if tall:
+            parts = getattr(problem, "_parts", None)
+            if parts is None or parts[0].shape[0] == 0 or parts[2].shape[0] != 0:
+                raise ValueError("tall=True needs a Problem built from `ub` rows only")
+            A_ub, b_ub, _, _, c = parts
+            A_ub, b_ub, c = _f64(A_ub), _f64(b_ub), _f64(c)
+            m_ub, n = A_ub.shape[0], c.shape[0]
+            _raise_for(_capi.lib().lpipm_upload_ub_tall(self._h, n, m_ub, _p(A_ub), n, _p(b_ub), _p(c), float(problem.c0())))
+            self.m, self.n = m_ub, n + m_ub
+            return self
         if use_slack_structure and getattr(problem, "_parts", None) is not None:
             # device-side assembly: the ub / eq blocks as given, no host slack matrix (lpipm_upload_ub_eq)
             A_ub, b_ub, A_eq, b_eq, c = problem._parts
@@ -603,6 +615,29 @@ class Context:
         ms = C.c_double(0)
         _raise_for(_capi.lib().lpipm_k_adat(self._h, _p(dinv), _p(M), repeats, C.byref(ms)))
         return M, ms.value
+
+    def k_tall_normal(self, dinv):
+        """K = X^T diag(1/dinv_s) X + diag(1/dinv_x) of the tall upload (lower triangle valid)."""
+        dinv = _f64(dinv)
+        if dinv.shape != (self.n,):
+            raise IncompatibleInputDimensions()
+        nx = self.n - self.m
+        K = np.empty((nx, nx))
+        _raise_for(_capi.lib().lpipm_k_tall_normal(self._h, _p(dinv), _p(K)))
+        return K
+
+    def k_tall_sym_solve(self, dinv, R1, R2):
+        """The reduced sym_solve of the tall upload at dinv for 1 or 2 right-hand sides: R1 (nrhs, n), R2 (nrhs, m)
+        -> U (nrhs, n), V (nrhs, m), info."""
+        dinv = _f64(dinv)
+        R1, R2 = np.atleast_2d(_f64(R1)), np.atleast_2d(_f64(R2))
+        nrhs = R1.shape[0]
+        if dinv.shape != (self.n,) or R1.shape != (nrhs, self.n) or R2.shape != (nrhs, self.m):
+            raise IncompatibleInputDimensions()
+        U, V = np.empty((nrhs, self.n)), np.empty((nrhs, self.m))
+        info = C.c_int32(0)
+        _raise_for(_capi.lib().lpipm_k_tall_sym_solve(self._h, _p(dinv), nrhs, _p(R1), _p(R2), _p(U), _p(V), C.byref(info)))
+        return U, V, info.value
 
     def k_potrf(self, M, repeats=1):
         L = _f64(M).copy()

@@ -1,0 +1,194 @@
+// kernels_tall.hip -- the vector stage of the tall inequality form (lpipm_upload_ub_tall) and the transpose it starts from.
+//
+// A pure-`ub` LP, min c^T x, X.x <= b, x >= 0, in slack form A = [X I] with X m x nx and m >> nx.  The normal matrix
+// A.D.A^T is m x m; the same Newton system reduces to the nx x nx SPD matrix
+//   K = X^T.diag(W_s).X + diag(E_x),   W_s[i] = z_{nx+i} / x_{nx+i},   E_x[j] = z_j / x_j,
+// built by the fp64 MFMA A.D.A^T module from the resident transpose Xt (its `A`, contraction over the m rows) with W_s as
+// its `dinv`.  sym_solve(r1, r2) (newton_equations.rs:214-225), r1 = [r1_x; r1_s], then reads
+//   t   = W_s * r2 + r1_s              k_tall_setup
+//   g   = X^T.t - r1_x                 gemv_t over X, slabs folded by k_tall_fold     (r1_x itself, never Dinv * r1)
+//   u_x = K^-1 g                       Cholesky chain + super-block solves
+//   u_s = r2 - X.u_x                   gemv_n over X (alpha = -1, addend r2)
+//   v   = W_s * u_s + r1_s             k_tall_pq_uv / k_tall_uv_corr
+//   u   = [u_x; u_s]
+// Both u and v come from the reduced solve itself: taking only v from it and u from the dense epilogue Dinv * (A^T.v - r1)
+// cancels catastrophically on the slack block.  Everything downstream (d_tau, Delta, ratio test, step,
+// residuals, indicators) is the dense path's and sees p, q, u, v where it sees them there.
+// Reductions are fixed-order (kernels_vec.hip's two stages, the same slots); a tall LP is a single LP (no member offset
+// beyond what vbatch does for the VecArgs), and the kernels of the speculatively enqueued head test the done word.
+#include "vec_kernels.hpp"
+#include "vec_device.hpp"
+
+namespace lpipm {
+
+// ---------------------------------------------------------------- resident transpose
+// Xt[j][i] = X[i][j], i < m, j < nx, through a 32 x 32 LDS tile (rows padded by one double: the transposed reads walk a
+// column of the tile).  Both sides move whole 256-byte row segments.  Xt is zeroed beforehand: nothing outside the m x nx
+// block is written.  grid (column tiles of X, row tiles of X), 32 x 8 threads.
+constexpr int TT = 32;
+__global__ __launch_bounds__(256) void k_tall_transpose(const double* __restrict__ X, long long ldx, int m, int nx,
+                                                        double* __restrict__ Xt, long long ldt) {
+    __shared__ double tile[TT][TT + 1];
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    const long long i0 = (long long)blockIdx.y * TT;
+    const int j0 = blockIdx.x * TT;
+    for (int r = ty; r < TT; r += 8) {
+        const long long i = i0 + r;
+        const int j = j0 + tx;
+        tile[r][tx] = (i < m && j < nx) ? X[i * ldx + j] : 0.0;
+    }
+    __syncthreads();
+    for (int r = ty; r < TT; r += 8) {
+        const int j = j0 + r;
+        const long long i = i0 + tx;
+        if (j < nx && i < m) Xt[(long long)j * ldt + i] = tile[tx][r];
+    }
+}
+hipError_t tall_transpose(const double* X, int64_t ldx, int m, int nx, double* Xt, int64_t ldt, hipStream_t st) {
+    if (m <= 0 || nx <= 0) return hipSuccess;
+    const dim3 grid((nx + TT - 1) / TT, (m + TT - 1) / TT);
+    if (grid.y > 65535u) return hipErrorInvalidValue;      // m <= 2^20: 32768 row tiles
+    hipLaunchKernelGGL(k_tall_transpose, grid, dim3(TT, 8), 0, st, X, (long long)ldx, m, nx, Xt, (long long)ldt);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- set-up: W_s, E_x, t
+// with_scales: W_s = z_s / x_s (i < m; the padding up to mk stays zero) and E_x = z_x / x_x (j < nx) from the iterate.
+// t of right-hand side r (r < nrhs): T[r][i] = W_s[i] * r2[i] + r1[nx + i].
+__global__ __launch_bounds__(256) void k_tall_setup(VecArgs a, TallArgs t, int with_scales, int nrhs, const double* r1a,
+                                                    const double* r2a, const double* r1b, const double* r2b) {
+    if (!vbatch(a, true)) return;
+    const int stride = gridDim.x * 256;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
+        double ws;
+        if (with_scales) { ws = a.z[t.nx + i] / a.x[t.nx + i]; t.Ws[i] = ws; }
+        else ws = t.Ws[i];
+        if (nrhs > 0) t.T[i] = ws * r2a[i] + r1a[t.nx + i];
+        if (nrhs > 1) t.T[a.mp + i] = ws * r2b[i] + r1b[t.nx + i];
+    }
+    if (with_scales)
+        for (int j = blockIdx.x * 256 + threadIdx.x; j < t.nx; j += stride) t.Ex[j] = a.z[j] / a.x[j];
+}
+void tall_setup(const VecArgs& a, const TallArgs& t, bool with_scales, int nrhs, const double* r1a, const double* r2a,
+                const double* r1b, const double* r2b, hipStream_t st) {
+    hipLaunchKernelGGL(k_tall_setup, dim3(a.nblk, 1, 1), dim3(256), 0, st, a, t, with_scales ? 1 : 0, nrhs, r1a, r2a, r1b, r2b);
+}
+
+// ---------------------------------------------------------------- right-hand side of the reduced solve
+// G[r][j] = sum_s ATpart[s][r][j] - r1[j] for j < nx, 0 for nx <= j < nxp.  A workgroup takes 64 columns; its four waves
+// take the four quarters of the row splits, each in index order, and the quarters are added as (w0 + w1) + (w2 + w3): a
+// fixed order whatever the launch.  grid (64-column groups of nxp, right-hand sides).
+__global__ __launch_bounds__(256) void k_tall_fold(VecArgs a, TallArgs t, int nrhs, const double* r1a, const double* r1b) {
+    if (!vbatch(a, true)) return;
+    __shared__ double part[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = blockIdx.x * 64 + lane, r = blockIdx.y;
+    const int per = (a.nsplit + 3) / 4;
+    const int s0 = wave * per, s1 = s0 + per < a.nsplit ? s0 + per : a.nsplit;
+    double s = 0.0;
+    if (j < t.nx)
+        for (int sp = s0; sp < s1; ++sp) s += a.ATpart[((long long)sp * nrhs + r) * t.npa + j];
+    part[wave][lane] = s;
+    __syncthreads();
+    if (wave != 0 || j >= t.nxp) return;
+    const double* r1 = r == 0 ? r1a : r1b;
+    const double sum = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+    t.G[(long long)r * t.nxp + j] = j < t.nx ? sum - r1[j] : 0.0;
+}
+void tall_fold_rhs(const VecArgs& a, const TallArgs& t, int nrhs, const double* r1a, const double* r1b, hipStream_t st) {
+    hipLaunchKernelGGL(k_tall_fold, dim3((t.nxp + 63) / 64, nrhs, 1), dim3(256), 0, st, a, t, nrhs, r1a, r1b);
+}
+
+// ---------------------------------------------------------------- epilogues
+// Predictor: (p, q) from right-hand side 0, (u, v) from right-hand side 1.  u_x = G, u_s = Us; v = W_s * u_s + r1_s goes
+// to R (q into R[0], v into R[1], as the dense solve leaves them) and q to a.q.  The four dots of delta.rs:29-32 go to
+// the reduction slots 0 .. 3 and the NaN check of newton_equations.rs:190-194 sets FLAG_NAN_PQ, as k_pq_uv.
+__global__ __launch_bounds__(256) void k_tall_pq_uv(VecArgs a, TallArgs t, const double* r1a, const double* r1b) {
+    if (!vbatch(a, true)) return;
+    const int stride = gridDim.x * 256;
+    double acc[4] = {0, 0, 0, 0};
+    int nan = 0;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < a.n; j += stride) {
+        double p, u;
+        if (j < t.nx) { p = t.G[j]; u = t.G[t.nxp + j]; }
+        else          { p = t.Us[j - t.nx]; u = t.Us[a.mp + j - t.nx]; }
+        const double cj = a.c[j];
+        a.p[j] = p;
+        a.u[j] = u;
+        acc[0] += cj * p;
+        acc[1] += cj * u;
+        nan |= (p != p);
+    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
+        const double ws = t.Ws[i], bi = a.b[i];
+        const double q = ws * t.Us[i] + r1a[t.nx + i];
+        const double v = ws * t.Us[a.mp + i] + r1b[t.nx + i];
+        a.q[i] = q;
+        a.R[i] = q;
+        a.R[a.mp + i] = v;
+        acc[2] += bi * q;
+        acc[3] += bi * v;
+        nan |= (q != q);
+    }
+    if (nan) atomicOr(a.flags, FLAG_NAN_PQ);
+    block_reduce_store<4, false>(acc, a.red, 0);
+}
+// Corrector: only (u, v) change (k_uv_corr): c.u and b.v into slots 0 and 1, v into R[0].
+__global__ __launch_bounds__(256) void k_tall_uv_corr(VecArgs a, TallArgs t, const double* r1a) {
+    if (!vbatch(a, true)) return;
+    const int stride = gridDim.x * 256;
+    double acc[2] = {0, 0};
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < a.n; j += stride) {
+        const double u = j < t.nx ? t.G[j] : t.Us[j - t.nx];
+        a.u[j] = u;
+        acc[0] += a.c[j] * u;
+    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
+        const double v = t.Ws[i] * t.Us[i] + r1a[t.nx + i];
+        a.R[i] = v;
+        acc[1] += a.b[i] * v;
+    }
+    block_reduce_store<2, false>(acc, a.red, 0);
+}
+void tall_pq_uv(const VecArgs& a, const TallArgs& t, const double* r1a, const double* r1b, hipStream_t st) {
+    hipLaunchKernelGGL(k_tall_pq_uv, dim3(a.nblk, 1, 1), dim3(256), 0, st, a, t, r1a, r1b);
+}
+void tall_uv_corr(const VecArgs& a, const TallArgs& t, const double* r1a, hipStream_t st) {
+    hipLaunchKernelGGL(k_tall_uv_corr, dim3(a.nblk, 1, 1), dim3(256), 0, st, a, t, r1a);
+}
+
+// ---------------------------------------------------------------- residuals at the current point
+// k_residuals (residual.rs:22-31, feasible_point.rs:122-123) with the row-split slabs of A^T.y only npa wide: a structural
+// column sums its slabs in index order, a slack column's A^T.y is y_i itself.  The same six partial sums in slots 0 .. 5.
+__global__ __launch_bounds__(256) void k_tall_residuals(VecArgs a, TallArgs t) {
+    if (!vbatch(a, true)) return;
+    const int stride = gridDim.x * 256;
+    const double tau = a.S[S_TAU];
+    double acc[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
+        double ax = a.Ax[i];
+        for (int ch = 1; ch < a.ax_chunks; ++ch) ax += a.Ax[(long long)ch * a.mp + i];
+        const double r = a.b[i] * tau - ax;
+        a.rP[i] = r;
+        acc[0] += r * r;
+        acc[1] += a.b[i] * a.y[i];
+    }
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < a.n; j += stride) {
+        double aty = 0.0;
+        if (j < t.nx) for (int s = 0; s < a.nsplit; ++s) aty += a.ATpart[(long long)s * t.npa + j];
+        else aty = a.y[j - t.nx];
+        const double xj = a.x[j], zj = a.z[j], cj = a.c[j];
+        const double r = cj * tau - aty - zj;
+        a.rD[j] = r;
+        acc[2] += r * r;
+        acc[3] += cj * xj;
+        acc[4] += xj * zj;
+        acc[5] += cj * (xj / tau);
+    }
+    block_reduce_store<6, false>(acc, a.red, 0);
+}
+void tall_residuals(const VecArgs& a, const TallArgs& t, hipStream_t st) {
+    hipLaunchKernelGGL(k_tall_residuals, dim3(a.nblk, 1, 1), dim3(256), 0, st, a, t);
+}
+
+}  // namespace lpipm

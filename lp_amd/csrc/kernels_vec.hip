@@ -8,70 +8,9 @@
 // Each kernel cites the reference lines whose arithmetic (and operation order) it reproduces.
 #include <cstdlib>
 #include "vec_kernels.hpp"
+#include "vec_device.hpp"
 
 namespace lpipm {
-
-// ---------------------------------------------------------------- reduction helpers
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-    return v;
-}
-// workgroup (256 threads) reduction of K values; thread 0 writes red[slot0 + k][blockIdx.x]
-template <int K, bool IS_MIN>
-__device__ __forceinline__ void block_reduce_store(double (&v)[K], double* red, int slot0) {
-    __shared__ double sm[4][K];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double w = IS_MIN ? wave_min(v[k]) : wave_sum(v[k]);
-        if (lane == 0) sm[wave][k] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const double r = IS_MIN ? fmin(fmin(sm[0][k], sm[1][k]), fmin(sm[2][k], sm[3][k]))
-                                    : (sm[0][k] + sm[1][k]) + (sm[2][k] + sm[3][k]);
-            red[(slot0 + k) * RED_STRIDE + blockIdx.x] = r;
-        }
-    }
-}
-// one wave folds the nblk partials of a slot in a fixed order; every lane gets the result
-__device__ __forceinline__ double fold_sum(const double* red, int slot, int nblk) {
-    double s = 0.0;
-    for (int b = (int)(threadIdx.x & 63); b < nblk; b += 64) s += red[slot * RED_STRIDE + b];
-    return wave_sum(s);
-}
-__device__ __forceinline__ double fold_min(const double* red, int slot, int nblk, double init) {
-    double s = init;
-    for (int b = (int)(threadIdx.x & 63); b < nblk; b += 64) s = fmin(s, red[slot * RED_STRIDE + b]);
-    return wave_min(s);
-}
-
-// LP blockIdx.z of a lockstep batch.  `check_done`: kernels of the iteration skip an LP that has finished.
-__device__ __forceinline__ bool vbatch(VecArgs& a, bool check_done) {
-    const BatchK bk{a.bstride, check_done ? a.done_chk : nullptr, 0, a.bfirst};
-    if (batch_done(bk)) return false;
-    if (blockIdx.z == 0 && a.bfirst == 0) return true;
-    a.b = batch_ptr(a.b, bk); a.c = batch_ptr(a.c, bk);
-    a.x = batch_ptr(a.x, bk); a.y = batch_ptr(a.y, bk); a.z = batch_ptr(a.z, bk);
-    a.dinv = batch_ptr(a.dinv, bk); a.xs = batch_ptr(a.xs, bk); a.r1 = batch_ptr(a.r1, bk); a.rD = batch_ptr(a.rD, bk);
-    a.p = batch_ptr(a.p, bk); a.u = batch_ptr(a.u, bk); a.dx = batch_ptr(a.dx, bk); a.dz = batch_ptr(a.dz, bk);
-    a.dxdz = batch_ptr(a.dxdz, bk);
-    a.rP = batch_ptr(a.rP, bk); a.rP2 = batch_ptr(a.rP2, bk); a.q = batch_ptr(a.q, bk); a.dy = batch_ptr(a.dy, bk);
-    a.Ax = batch_ptr(a.Ax, bk); a.W = batch_ptr(a.W, bk); a.R = batch_ptr(a.R, bk); a.ATpart = batch_ptr(a.ATpart, bk);
-    a.S = batch_ptr(a.S, bk); a.red = batch_ptr(a.red, bk); a.status = batch_ptr(a.status, bk);
-    a.potrf_info = batch_ptr(a.potrf_info, bk); a.flags = batch_ptr(a.flags, bk); a.done = batch_ptr(a.done, bk);
-    a.skip_refine = batch_ptr(a.skip_refine, bk);
-    a.done_chk = batch_ptr(a.done_chk, bk);
-    return true;
-}
 
 // n-split mode: gs[first .. first+count) <- fold of the reduction slots (sum or min), optionally the NaN
 // flag as a number in gs[flag_slot]; the host then reduces gs across ranks.
@@ -125,10 +64,7 @@ __global__ __launch_bounds__(256) void k_blind_start(VecArgs a) {
 // partial sums: |r_P|^2, b.y, |r_D|^2, c.x, x.z, c.(x/tau)   (indicators.rs:41-44)
 // A vector kernel's work is written once, for the thread `vt` of the (virtual) 256-thread block `vb` of `nvb`: the plain
 // kernels pass (blockIdx.x, threadIdx.x, gridDim.x); the fused single-workgroup kernels further down walk the same
-// virtual blocks four at a time and rebuild the same reduction tree, so their sums have the same bits.
-struct VThread { int vb, vt, nvb; };
-__device__ __forceinline__ VThread plain_thread() { return VThread{(int)blockIdx.x, (int)threadIdx.x, (int)gridDim.x}; }
-
+// virtual blocks four at a time and rebuild the same reduction tree, so their sums have the same bits (VThread, vec_device.hpp).
 __device__ __forceinline__ void body_residuals(const VecArgs& a, const VThread t, double (&acc)[6]) {
     const int stride = t.nvb * 256;
     const double tau = a.S[S_TAU];
@@ -719,6 +655,9 @@ int vec_residuals(const VecArgs& a, int is_init, int ip_next, double tol, hipStr
     if (int rc = cross(a, xr, 2, 4, 0, -1, 2, 4, st)) return rc;     // |r_D|^2, c.x, x.z, c.(x/tau)
     hipLaunchKernelGGL(k_scalar_indicators, sgrid(a), dim3(64), 0, st, a, is_init, ip_next, tol);
     return 0;
+}
+void vec_scalar_indicators(const VecArgs& a, int is_init, int ip_next, double tol, hipStream_t st) {
+    hipLaunchKernelGGL(k_scalar_indicators, sgrid(a), dim3(64), 0, st, a, is_init, ip_next, tol);
 }
 void vec_pred_setup(const VecArgs& a, hipStream_t st) { hipLaunchKernelGGL(k_pred_setup, vgrid(a), dim3(256), 0, st, a); }
 // Single GPU (a.gs == nullptr): the one-wave scalar kernels k_scalar_dtau / k_scalar_alpha are folded into their consumers

@@ -96,6 +96,12 @@ struct Problem {
     // from `ones` -- iteration 1's dinv, exact 1.0 over the np columns -- ahead of the first solve (ensure_shared_factor).
     bool shared_factor = false;
     double* ones = nullptr;
+    // The tall inequality form (lpipm_upload_ub_tall; kernels_tall.hip): a pure-`ub` LP whose Newton system is reduced to the
+    // nxp x nxp matrix K = X^T.W_s.X + E_x.  M is then K (ld nxp), `factor` its plan, `adat` the plan of the launch that builds
+    // it from Xt, and nothing in the arena is m x m.  The row-split slabs of A^T.v are npa wide (tv.npa), not np.
+    bool tall = false;
+    double* Xt = nullptr;        // nxp x mk, row-major, zero padded: X^T of the resident (scaled) X
+    TallArgs tv{};
     bool from_parts = false;     // uploaded as ub / eq blocks (lpipm_upload_ub_eq): b and c are not in the caller's slack form
     // Equilibration (lpipm_set_scaling): the exponents and the maxima slabs, in an allocation of their own that exists only
     // for a problem uploaded with scaling on.  scale_passes > 0: the resident A, b and c are the scaled ones.
@@ -469,10 +475,50 @@ static size_t first_factor_bytes(int mp, int super_w) {
     for (int r0 = 0; r0 < mp; r0 += super_w) { const size_t s = (size_t)(mp - r0 < super_w ? mp - r0 : super_w); bytes += 2 * s * s * sizeof(double); }
     return bytes;
 }
+// The arena of a tall LP (Problem::tall): the vectors of the dense layout, X and its transpose, the nxp x nxp matrix K with
+// its factor plan, and the work vectors of the reduced solve.  Nothing grows as m^2: no M, M0 or kept first factor, the slabs
+// of A^T.v are npa wide and the chunk slabs of A.x are those of the npa stored columns.
+static int layout_tall(Problem& p, FactorPlan& plan, FactorPlan& plan1, const AdatPlan& ap, Arena& ar, bool build, hipStream_t st) {
+    VecArgs& v = p.va;
+    TallArgs& t = p.tv;
+    const size_t mp = (size_t)p.mp, np = (size_t)p.np, nxp = (size_t)t.nxp;
+    p.A = ar.take<double>(mp * p.npa);
+    p.Xt = ar.take<double>(nxp * (size_t)t.mk);
+    v.b = ar.take<double>(mp); v.c = ar.take<double>(np);
+    v.x = ar.take<double>(np); v.y = ar.take<double>(mp); v.z = ar.take<double>(np);
+    v.dinv = ar.take<double>(np); v.xs = ar.take<double>(np); v.r1 = ar.take<double>(np); v.rD = ar.take<double>(np);
+    v.p = ar.take<double>(np); v.u = ar.take<double>(np); v.dx = ar.take<double>(np); v.dz = ar.take<double>(np);
+    v.dxdz = ar.take<double>(np);
+    v.rP = ar.take<double>(mp); v.rP2 = ar.take<double>(mp); v.q = ar.take<double>(mp); v.dy = ar.take<double>(mp);
+    v.Ax = ar.take<double>(mp * (size_t)gemv_dual_chunks(p.npa));
+    v.W = ar.take<double>(2 * np); v.R = ar.take<double>(2 * mp);
+    p.Y = ar.take<double>(2 * nxp);
+    p.ATpart = ar.take<double>((size_t)p.nsplit * 2 * p.npa);
+    v.ATpart = p.ATpart;
+    v.S = ar.take<double>(64); v.red = ar.take<double>((size_t)RED_SLOTS * RED_STRIDE);
+    v.status = ar.take<StatusRec>(1);
+    v.potrf_info = ar.take<int32_t>(1); v.flags = ar.take<int>(1); v.done = ar.take<int>(1);
+    v.skip_refine = ar.take<int>(1);
+    t.Ws = ar.take<double>((size_t)t.mk); t.Ex = ar.take<double>(nxp);
+    t.T = ar.take<double>(2 * mp); t.G = ar.take<double>(2 * nxp); t.Us = ar.take<double>(2 * mp);
+    p.M = ar.take<double>(nxp * nxp);
+    LP_HIP(factor_plan_create(plan, p.M, t.nxp, t.nxp, ar, build, st, super_for(t.nxp), merge_edge_for(1)));
+    p.factor = &plan;
+    p.M0 = p.R0 = p.Rho = p.symv_ws = nullptr;
+    p.tau = ar.take<double>(1);
+    p.gs = ar.take<double>(8);
+    p.xout = ar.take<double>(np);
+    adat_take(p.adat, ap, ar);
+    p.keep = false; p.shared_factor = false;
+    p.M1 = nullptr; p.factor1 = nullptr; p.info1 = nullptr; p.ones = nullptr;
+    factor_plan_destroy(plan1);
+    return LPIPM_OK;
+}
 static int layout_problem(Problem& p, FactorPlan& plan, FactorPlan& plan1, const AdatPlan& ap, int refine, bool keep, Arena& ar,
                           bool build, hipStream_t st) {
     VecArgs& v = p.va;
     const size_t mp = (size_t)p.mp, np = (size_t)p.np;
+    if (p.tall) return layout_tall(p, plan, plan1, ap, ar, build, st);
     p.A = p.shared_a ? nullptr : ar.take<double>(mp * p.npa);     // a shared A has its own allocation (upload_impl)
     v.b = ar.take<double>(mp); v.c = ar.take<double>(np);
     v.x = ar.take<double>(np); v.y = ar.take<double>(mp); v.z = ar.take<double>(np);
@@ -585,8 +631,10 @@ struct UploadParts { uint64_t m_ub; const double* A_ub; uint64_t lda_ub; const d
 // shared: A[0] is the one matrix of all `count` LPs (lpipm_upload_lockstep_shared; A holds one entry).
 static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const double* const* A, uint64_t lda,
                        const double* const* b, const double* const* cc, const double* c0, uint64_t n_slack,
-                       const UploadParts* parts = nullptr, bool shared = false, bool hint_verified = false, bool keep_ok = true) {
+                       const UploadParts* parts = nullptr, bool shared = false, bool hint_verified = false, bool keep_ok = true,
+                       bool tall = false) {
     if (!c || count < 1 || !cc) return LPIPM_ERR_BAD_ARGUMENT;
+    if (tall && (!parts || shared || count != 1 || n_slack != m)) return LPIPM_ERR_BAD_ARGUMENT;
     if (!parts && (!A || !b || lda < n)) return LPIPM_ERR_BAD_ARGUMENT;
     if (parts && (shared ? !b : count != 1)) return LPIPM_ERR_BAD_ARGUMENT;
     for (int i = 0; i < count; ++i)
@@ -601,12 +649,13 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
     destroy_views(c); // half-batch views hold copies of the geometry and of the device pointers
     c->first_valid = false;   // whatever is kept belongs to the matrix that is being replaced
     // keep_ok == false: an upload that is solved once (lpipm_solve_batch) or never through the kept factor (column split)
-    const bool keep = keep_ok && c->first_cache && c->refine <= 0;
+    const bool keep = keep_ok && c->first_cache && c->refine <= 0 && !tall;   // (tall: the first factor is not kept)
     const uint64_t nx = n - n_slack;
     const int mp = (int)round_up(m, NB), np = (int)round_up(n, BK), npa = (int)round_up(nx, BK);
     hipStream_t st = c->rs.st;
+    const int nxp = (int)round_up(nx, NB), mk = (int)round_up(m, BK);   // tall: the order of K, the contraction of its build
     if (!c->p.has_problem || mp != c->p.mp || np != c->p.np || npa != c->p.npa || count != c->p.B || shared != c->p.shared_a ||
-        keep != c->p.keep) {
+        keep != c->p.keep || tall != c->p.tall || (tall && mk != c->p.tv.mk)) {   // (mk is not a function of mp, np and npa)
         LP_HIP(hipStreamSynchronize(st));
         if (c->p.arena) { LP_HIP(hipFree(c->p.arena)); c->p.arena = nullptr; }
         if (c->p.a_shared) { LP_HIP(hipFree(c->p.a_shared)); c->p.a_shared = nullptr; c->p.a_shared_bytes = 0; }
@@ -616,11 +665,16 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
         factor_plan_destroy(c->plan1);
         c->p.has_problem = false;
         c->p.mp = mp; c->p.np = np; c->p.npa = npa; c->p.B = count;
+        c->p.tall = tall;
+        c->p.Xt = nullptr;
+        c->p.tv = TallArgs{};
+        if (tall) { c->p.tv.nx = (int)nx; c->p.tv.npa = npa; c->p.tv.nxp = nxp; c->p.tv.mk = mk; }
         c->p.nsplit = mp / GEMVT_ROWS;
         const uint64_t big = m > n ? m : n;
         c->p.nblk = (int)((big + 255) / 256);
         if (c->p.nblk > RED_STRIDE) c->p.nblk = RED_STRIDE;
-        c->ap = plan_adat(mp, npa, count, c->num_cu, c->world, c->units_env);
+        // (tall: the launch builds K from Xt -- nxp rows, a contraction over the mk padded rows of X)
+        c->ap = tall ? plan_adat(nxp, mk, 1, c->num_cu, 1, c->units_env) : plan_adat(mp, npa, count, c->num_cu, c->world, c->units_env);
         Arena measure;
         LP_TRY(layout_problem(c->p, c->plan, c->plan1, c->ap, c->refine, keep, measure, false, st));
         c->p.bstride = round_up(measure.off, 4096);
@@ -643,7 +697,7 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
             sh.base = (char*)c->p.a_shared; sh.off = a_bytes;
             if (c->p.shared_factor) LP_TRY(layout_shared_factor(c->p, c->plan, c->plan1, sh, true, st));
         }
-        LP_HIP(adat_lists_create(c->p.adat, c->ap, mp, count, st));    // (drains st)
+        LP_HIP(adat_lists_create(c->p.adat, c->ap, tall ? nxp : mp, count, st));    // (drains st)
         LP_TRY(stream_res_grow_status(c->rs, (size_t)count));
         VecArgs& v = c->p.va;
         v.np = np; v.mp = mp; v.nblk = c->p.nblk; v.nsplit = c->p.nsplit;
@@ -658,6 +712,7 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
     LP_TRY(scale_setup(c, mp, np, npa, shared ? 1 : count));
     c->p.m = m; c->p.n = n;
     c->p.ns = (int)n_slack; c->p.nx = (int)nx;
+    if (tall) c->p.tv.nx = (int)nx;            // (the padded geometry may be shared by several nx)
     c->p.from_parts = parts != nullptr;
     c->p.va.n = (int)n; c->p.va.m = (int)m;
     c->p.va.n_total = (long long)n; c->p.va.gs = nullptr; c->colsplit = false;   // lpipm_upload_nsplit overrides
@@ -703,6 +758,8 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
                                   shared ? Batch{} : members));
         LP_HIP(launch_scale_vectors(c->p.sc, (double*)c->p.va.b, (int)m, (double*)c->p.va.c, (int)n, st, members));
     }
+    // tall: the resident transpose, from the X the solves see (behind the equilibration: both copies carry its exponents)
+    if (tall) LP_HIP(tall_transpose(c->p.A, npa, (int)m, (int)nx, c->p.Xt, mk, st));
     LP_HIP(hipStreamSynchronize(st));   // the caller's arrays, c0v and onesv are free again from here
     c->p.has_problem = true;
     c->p.adat.counters_dirty = true;
@@ -730,6 +787,15 @@ extern "C" int lpipm_upload_ub_eq(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const
     return upload_impl(c, 1, m_ub + m_eq, n + m_ub, nullptr, 0, nullptr, &cc, &c0, m_ub, &parts);
 }
 
+extern "C" int lpipm_upload_ub_tall(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub,
+                                    const double* b_ub, const double* cc, double c0) {
+    if (m_ub == 0) return LPIPM_UNCONSTRAINED;                              // linear_program.rs:134-136
+    if (!c || !cc || n == 0 || !A_ub || !b_ub || lda_ub < n) return LPIPM_ERR_BAD_ARGUMENT;
+    if (c->world > 1 || c->refine > 0) return LPIPM_ERR_UNSUPPORTED;        // a column-split context; the refined solves
+    const UploadParts parts{m_ub, A_ub, lda_ub, b_ub, nullptr, 0, nullptr};
+    return upload_impl(c, 1, m_ub, n + m_ub, nullptr, 0, nullptr, &cc, &c0, m_ub, &parts, false, false, false, true);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Y = add + A.W and Upart = row-split slabs of A^T.V on the stored structural columns, plus the
 // identity block of the slack columns
@@ -743,6 +809,8 @@ static hipError_t ctx_gemv_n(lpipm_ctx* c, int nrhs, const double* W, const doub
 }
 static hipError_t ctx_gemv_t(lpipm_ctx* c, int nrhs, const double* V, const Batch& bt) {
     ++c->gemv_passes;
+    // (tall: slabs npa wide; the slack columns' part of A^T.v is v itself, and the consumers take it from there)
+    if (c->p.tall) return launch_gemv_t(c->p.A, c->p.npa, c->p.mp, c->p.npa, nrhs, V, c->p.mp, c->p.ATpart, c->rs.st, c->p.npa, bt);
     hipError_t e = launch_gemv_t(c->p.A, c->p.npa, c->p.mp, c->p.npa, nrhs, V, c->p.mp, c->p.ATpart, c->rs.st, c->p.np, bt, c->p.shared_a);
     if (e != hipSuccess) return e;
     return launch_slack_t(c->p.ns, c->p.nx, nrhs, c->p.nsplit, V, c->p.mp, c->p.ATpart, c->p.np, c->rs.st, bt);
@@ -750,6 +818,11 @@ static hipError_t ctx_gemv_t(lpipm_ctx* c, int nrhs, const double* V, const Batc
 // both in one read of A: chunk slabs of A.w into AxPart (gemv_dual_chunks(npa) of them), row-split slabs of A^T.v into ATpart
 static hipError_t ctx_gemv_dual(lpipm_ctx* c, const double* W, const double* V, double* AxPart, const Batch& bt) {
     ++c->gemv_passes;
+    if (c->p.tall) {   // slabs of A^T.v npa wide (see ctx_gemv_t); w_s into chunk slab 0 of A.w
+        hipError_t et = launch_gemv_dual(c->p.A, c->p.npa, c->p.mp, c->p.npa, W, V, AxPart, c->p.ATpart, c->p.npa, c->rs.st, bt);
+        if (et != hipSuccess) return et;
+        return launch_slack_n(c->p.ns, c->p.nx, 1, W, c->p.np, AxPart, c->p.mp, c->rs.st, bt);
+    }
     hipError_t e = launch_gemv_dual(c->p.A, c->p.npa, c->p.mp, c->p.npa, W, V, AxPart, c->p.ATpart, c->p.np, c->rs.st, bt, c->p.shared_a);
     if (e != hipSuccess) return e;
     // the slack terms of both products in one launch: w_s into chunk slab 0, v into row-split slab 0 (zeros into the others)
@@ -797,6 +870,38 @@ static hipError_t run_adat(lpipm_ctx* c, const Batch& bt) {
     return hipGetLastError();
 }
 
+// Tall form: K = X^T.diag(W_s).X + diag(E_x) into M -- the same launch with Xt as its A (nxp rows, contraction over the mk
+// padded rows of X), W_s as its dinv, the diagonal beyond nx padded with ones; E_x goes onto the diagonal the way D_s does
+// on the dense path.
+static hipError_t run_tall_normal(lpipm_ctx* c, const Batch& bt) {
+    const TallArgs& t = c->p.tv;
+    AdatLaunch a{};
+    a.A = c->p.Xt; a.lda = t.mk; a.dinv = t.Ws; a.M = c->p.M; a.ldm = t.nxp; a.M2 = nullptr;
+    a.K = t.mk; a.diag_pad_from = t.nx; a.batch = bt; a.shared_a = false;
+    hipError_t e = launch_adat(c->ap, c->p.adat, a, false, c->rs.st, nullptr);
+    if (e != hipSuccess) return e;
+    return launch_slack_diag(t.nx, 0, t.Ex, c->p.M, t.nxp, c->rs.st, bt);
+}
+// Tall form: the reduced sym_solve for nrhs right-hand sides (r1a, r2a), (r1b, r2b) whose t the set-up kernel has left in
+// T, up to u_x in G and u_s in Us; the caller's epilogue kernel forms p, q, u, v.  K's factor is in M.
+static int tall_sym_solve(lpipm_ctx* c, int nrhs, const double* r1a, const double* r2a, const double* r1b, const double* r2b,
+                          const Batch& bt) {
+    const TallArgs& t = c->p.tv;
+    const VecArgs& v = c->p.va;
+    hipStream_t st = c->rs.st;
+    LP_HIP(ctx_gemv_t(c, nrhs, t.T, bt));                                         // X^T.t
+    prof_mark(c, T_GEMV);
+    tall_fold_rhs(v, t, nrhs, r1a, r1b, st);                                      // g = X^T.t - r1_x
+    LP_HIP(hipGetLastError());
+    prof_mark(c, T_VEC);
+    LP_HIP(launch_chol_solve(c->p.M, t.nxp, *c->p.factor, nrhs, t.G, c->p.Y, st, bt));   // u_x = K^-1 g
+    prof_mark(c, T_TRSV);
+    ++c->gemv_passes;                                                             // u_s = r2 - X.u_x
+    LP_HIP(launch_gemv_n(c->p.A, c->p.npa, (int)c->p.m, c->p.npa, nrhs, t.G, t.nxp, r2a, r2b, t.Us, c->p.mp, st, -1.0, bt));
+    prof_mark(c, T_GEMV);
+    return LPIPM_OK;
+}
+
 // v = M^-1 r through the Cholesky factor (newton_equations.rs:151-169); optionally (LPIPM_REFINE, see lpipm_ctx::refine)
 // with one step of iterative refinement against the matrix itself:  v0 = L^-T L^-1 r;  rho = r - M.v0 (doubled
 // precision, one read of the lower triangle);  v = v0 + L^-T L^-1 rho.  R: nrhs x mp, in/out.
@@ -830,6 +935,13 @@ static int enqueue_residuals(lpipm_ctx* c, int is_init, int ip_next, double tol)
     prof_mark(c, T_GEMV);
     // small LPs: the launch goes on with the next iteration's Dinv / r_hat set-up (enqueue_head then skips it)
     v.status_seq = (int)(++c->rs.seq_counter & 0x7fffffffu);
+    if (c->p.tall) {                            // kernel by kernel: slabs npa wide, A^T.y of a slack column is y
+        tall_residuals(v, c->p.tv, c->rs.st);
+        vec_scalar_indicators(v, is_init, ip_next, tol, c->rs.st);
+        c->pred_done = false;
+        LP_HIP(hipGetLastError());
+        return LPIPM_OK;
+    }
     const bool with_pred = !c->colsplit && vec_fused(v);
     LP_TRY(vec_residuals(v, is_init, ip_next, tol, c->rs.st, c->colsplit ? &xr : nullptr, with_pred));
     c->pred_done = with_pred;
@@ -897,6 +1009,13 @@ static int enqueue_head(lpipm_ctx* c) {
     prof_mark(c, T_VEC);
     if (c->pred_done) c->pred_done = false;       // the residual launch in front of this head has done it (enqueue_residuals)
     else vec_pred_setup(vh, st);
+    if (c->p.tall) {     // W_s, E_x and t of the predictor's two right-hand sides (c, b), (r1, r_P); then K instead of M
+        tall_setup(vh, c->p.tv, true, 2, vh.c, vh.b, vh.r1, vh.rP, st);
+        prof_mark(c, T_VEC, true);
+        LP_HIP(run_tall_normal(c, c->p.bt_head));
+        prof_mark(c, T_ADAT, true);
+        return LPIPM_OK;
+    }
     prof_mark(c, T_VEC, true);
     if (c->skip_factor) return LPIPM_OK;          // iteration 1 on a kept factor: its M is already there, factored
     if (c->colsplit && c->world > 1 && c->p.adat.ngroups() > 0 && c->st_c) {
@@ -957,8 +1076,37 @@ struct PredictorBeside {
     }
 };
 
+// The tail of a tall LP's iteration: K's factorisation (no work beside its chain), then the reduced sym_solve twice -- both
+// right-hand sides of the predictor in one pass each, the corrector's one -- with the tall epilogues where the dense path has
+// k_pq_uv / k_uv_corr.  The vector stage runs kernel by kernel.
+static int enqueue_tail_tall(lpipm_ctx* c, int ip, const lpipm_opts* o) {
+    VecArgs& v = c->p.va;
+    const TallArgs& t = c->p.tv;
+    hipStream_t st = c->rs.st;
+    const Batch& bt = c->p.bt;
+    LP_HIP(launch_potrf(c->p.M, t.nxp, t.nxp, *c->p.factor, v.potrf_info, st, bt, lookahead(c), false, nullptr));   // :129-131
+    prof_mark(c, T_POTRF);
+    LP_TRY(tall_sym_solve(c, 2, v.c, v.b, v.r1, v.rP, bt));                    // :187-188
+    tall_pq_uv(v, t, v.c, v.r1, st);
+    LP_TRY(vec_delta(v, 0, ip, 1.0, st, nullptr));
+    vec_corr_setup(v, ip, st);
+    tall_setup(v, t, false, 1, v.r1, v.rP2, nullptr, nullptr, st);             // t of the corrector's right-hand side
+    prof_mark(c, T_VEC);
+    LP_TRY(tall_sym_solve(c, 1, v.r1, v.rP2, nullptr, nullptr, bt));
+    tall_uv_corr(v, t, v.r1, st);
+    LP_TRY(vec_delta(v, 1, ip, o->alpha0, st, nullptr));
+    vec_step(v, ip, o->alpha0, st);
+    prof_mark(c, T_VEC);
+    LP_TRY(enqueue_residuals(c, 0, 0, o->tol));
+    LP_TRY(copy_status(c));
+    prof_mark(c, T_VEC);
+    if (!c->rs.spin_status) LP_HIP(hipEventRecord(c->rs.ev_status, st));
+    return LPIPM_OK;
+}
+
 // The rest of the iteration, ending with the status record on its way to the host and ev_status behind it.
 static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
+    if (c->p.tall) return enqueue_tail_tall(c, ip, o);
     VecArgs& v = c->p.va;
     hipStream_t st = c->rs.st;
     XRank xr_{xrank_fn, c};
@@ -1133,6 +1281,7 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XO
         if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
         if (c->p.B != 1) return LPIPM_ERR_BAD_ARGUMENT;   // a lockstep batch is solved by solve_lockstep
         if (o->solver_type != LPIPM_SOLVER_CHOLESKY && c->p.mp > 16384) return LPIPM_ERR_UNSUPPORTED;  // QR solve keeps the rhs in LDS
+        if (o->solver_type != LPIPM_SOLVER_CHOLESKY && c->p.tall) return LPIPM_ERR_UNSUPPORTED;        // the reduced form: Cholesky arm only
     }
     LP_HIP(hipSetDevice(c->device));
     LP_TRY(ensure_shared_factor(c, o));                   // (a view finds it built: solve_lockstep)
@@ -1845,6 +1994,7 @@ static int timed_repeats(lpipm_ctx* c, int repeats, double* ms_out, F&& body) {
 extern "C" int lpipm_k_adat(lpipm_ctx* c, const double* dinv, double* M_out, int repeats, double* ms_out) {
     if (!c || !dinv || !M_out) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (c->p.tall) return LPIPM_ERR_UNSUPPORTED;           // a tall upload has no M (lpipm_k_tall_normal returns K)
     LP_HIP(hipSetDevice(c->device));
     LP_HIP(hipMemcpyAsync(c->p.va.dinv, dinv, c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
     LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int { LP_HIP(run_adat(c, Batch{})); return LPIPM_OK; }));
@@ -1852,6 +2002,76 @@ extern "C" int lpipm_k_adat(lpipm_ctx* c, const double* dinv, double* M_out, int
                             c->p.m * sizeof(double), c->p.m, hipMemcpyDeviceToHost, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
+}
+
+// The iterate the tall kernel entries work from: x = dinv, z = 1, so that W_s = 1 / dinv_s and E_x = 1 / dinv_x.
+static int tall_entry_iterate(lpipm_ctx* c, const double* dinv) {
+    const std::vector<double> ones((size_t)c->p.n, 1.0);
+    LP_HIP(hipMemcpyAsync(c->p.va.x, dinv, c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
+    LP_HIP(hipMemcpyAsync(c->p.va.z, ones.data(), c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));      // `ones` goes out of scope
+    return LPIPM_OK;
+}
+extern "C" int lpipm_k_tall_normal(lpipm_ctx* c, const double* dinv, double* K_out) {
+    if (!c || !dinv || !K_out) return LPIPM_ERR_BAD_ARGUMENT;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (!c->p.tall) return LPIPM_ERR_UNSUPPORTED;
+    LP_HIP(hipSetDevice(c->device));
+    vec_blind_start(c->p.va, c->rs.st);                       // clears done / flags; the iterate is overwritten next
+    LP_TRY(tall_entry_iterate(c, dinv));
+    tall_setup(c->p.va, c->p.tv, true, 0, nullptr, nullptr, nullptr, nullptr, c->rs.st);
+    LP_HIP(run_tall_normal(c, Batch{}));
+    const size_t nx = (size_t)c->p.nx;
+    LP_HIP(hipMemcpy2DAsync(K_out, nx * sizeof(double), c->p.M, (size_t)c->p.tv.nxp * sizeof(double), nx * sizeof(double), nx,
+                            hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
+    return LPIPM_OK;
+}
+extern "C" int lpipm_k_tall_sym_solve(lpipm_ctx* c, const double* dinv, int nrhs, const double* R1, const double* R2,
+                                      double* U_out, double* V_out, int32_t* info_out) {
+    if (!c || !dinv || !R1 || !R2 || !U_out || !V_out || (nrhs != 1 && nrhs != 2)) return LPIPM_ERR_BAD_ARGUMENT;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (!c->p.tall) return LPIPM_ERR_UNSUPPORTED;
+    LP_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->rs.st;
+    VecArgs& v = c->p.va;
+    const TallArgs& t = c->p.tv;
+    const size_t n = (size_t)c->p.n, m = (size_t)c->p.m, np = (size_t)c->p.np, mp = (size_t)c->p.mp;
+    // the right-hand sides on the device, rows padded as the solver's own vectors are: R1 as [nrhs][np], R2 as [nrhs][mp]
+    double* rhs = nullptr;
+    LP_HIP(hipMalloc((void**)&rhs, 2 * (np + mp) * sizeof(double)));
+    double* r1 = rhs;
+    double* r2 = rhs + 2 * np;
+    int32_t info = 0;
+    auto run = [&]() -> int {
+        LP_HIP(hipMemsetAsync(rhs, 0, 2 * (np + mp) * sizeof(double), st));
+        LP_HIP(hipMemcpy2DAsync(r1, np * sizeof(double), R1, n * sizeof(double), n * sizeof(double), (size_t)nrhs, hipMemcpyHostToDevice, st));
+        LP_HIP(hipMemcpy2DAsync(r2, mp * sizeof(double), R2, m * sizeof(double), m * sizeof(double), (size_t)nrhs, hipMemcpyHostToDevice, st));
+        vec_blind_start(v, st);
+        LP_TRY(tall_entry_iterate(c, dinv));
+        const double* r1b = nrhs == 2 ? r1 + np : nullptr;
+        const double* r2b = nrhs == 2 ? r2 + mp : nullptr;
+        tall_setup(v, t, true, nrhs, r1, r2, r1b, r2b, st);
+        LP_HIP(run_tall_normal(c, Batch{}));
+        LP_HIP(launch_potrf(c->p.M, t.nxp, t.nxp, *c->p.factor, v.potrf_info, st, Batch{}, nullptr, true, nullptr));
+        LP_TRY(tall_sym_solve(c, nrhs, r1, r2, r1b, r2b, Batch{}));
+        if (nrhs == 2) tall_pq_uv(v, t, r1, r1b, st);
+        else           tall_uv_corr(v, t, r1, st);
+        LP_HIP(hipGetLastError());
+        // nrhs == 2: (p, q) and (u, v) as the predictor leaves them; nrhs == 1: (u, v) as the corrector does
+        if (nrhs == 2) LP_HIP(hipMemcpyAsync(U_out, v.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        LP_HIP(hipMemcpyAsync(U_out + (nrhs == 2 ? n : 0), v.u, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        LP_HIP(hipMemcpy2DAsync(V_out, m * sizeof(double), v.R, mp * sizeof(double), m * sizeof(double), (size_t)nrhs, hipMemcpyDeviceToHost, st));
+        LP_HIP(hipMemcpyAsync(&info, v.potrf_info, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        LP_HIP(hipMemsetAsync(v.potrf_info, 0, sizeof(int32_t), st));     // the solver expects a clean word
+        LP_HIP(hipStreamSynchronize(st));
+        return LPIPM_OK;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(rhs);
+    if (rc == LPIPM_OK && info_out) *info_out = info;
+    return rc;
 }
 
 static int kbuf_ensure(lpipm_ctx* c, int mp) {
@@ -2046,6 +2266,12 @@ extern "C" int lpipm_k_gemv_t(lpipm_ctx* c, int nrhs, const double* V, double* U
                             nrhs, hipMemcpyHostToDevice, c->rs.st));
     LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int {
         LP_HIP(ctx_gemv_t(c, nrhs, c->p.va.R, Batch{}));
+        if (c->p.tall) {   // slabs npa wide; the slack columns' A^T.v is v
+            LP_HIP(launch_gemv_t_reduce(c->p.ATpart, c->p.nsplit, nrhs, c->p.npa, c->p.va.W, c->p.np, c->rs.st));
+            LP_HIP(hipMemcpy2DAsync(c->p.va.W + c->p.nx, (size_t)c->p.np * sizeof(double), c->p.va.R, (size_t)c->p.mp * sizeof(double),
+                                    c->p.m * sizeof(double), nrhs, hipMemcpyDeviceToDevice, c->rs.st));
+            return LPIPM_OK;
+        }
         LP_HIP(launch_gemv_t_reduce(c->p.ATpart, c->p.nsplit, nrhs, c->p.np, c->p.va.W, c->p.np, c->rs.st));
         return LPIPM_OK;
     }));
@@ -2114,12 +2340,18 @@ extern "C" int lpipm_k_gemv_dual(lpipm_ctx* c, const double* w, const double* v,
         return LPIPM_OK;
     }));
     // the consumers' folds, on the host: chunk slabs of A.w, row-block slabs of A^T.v, in index order
-    std::vector<double> ax((size_t)nch * c->p.mp), at((size_t)c->p.nsplit * c->p.np);
+    const size_t slab = c->p.tall ? (size_t)c->p.npa : (size_t)c->p.np;      // tall: slabs npa wide, A^T.v of a slack column is v
+    std::vector<double> ax((size_t)nch * c->p.mp), at((size_t)c->p.nsplit * slab);
     LP_HIP(hipMemcpyAsync(ax.data(), va.Ax, ax.size() * sizeof(double), hipMemcpyDeviceToHost, c->rs.st));
     LP_HIP(hipMemcpyAsync(at.data(), c->p.ATpart, at.size() * sizeof(double), hipMemcpyDeviceToHost, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     for (uint64_t i = 0; i < c->p.m; ++i) { double s = 0.0; for (int ch = 0; ch < nch; ++ch) s += ax[(size_t)ch * c->p.mp + i]; Aw_out[i] = s; }
-    for (uint64_t j = 0; j < c->p.n; ++j) { double s = 0.0; for (int sp = 0; sp < c->p.nsplit; ++sp) s += at[(size_t)sp * c->p.np + j]; ATv_out[j] = s; }
+    for (uint64_t j = 0; j < c->p.n; ++j) {
+        if (c->p.tall && j >= (uint64_t)c->p.nx) { ATv_out[j] = v[j - (uint64_t)c->p.nx]; continue; }
+        double s = 0.0;
+        for (int sp = 0; sp < c->p.nsplit; ++sp) s += at[(size_t)sp * slab + j];
+        ATv_out[j] = s;
+    }
     return LPIPM_OK;
 }
 

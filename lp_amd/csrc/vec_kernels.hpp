@@ -73,6 +73,8 @@ void vec_blind_start(const VecArgs& a, hipStream_t st);
 // with_pred (only where vec_fused(a) holds and xr is null): the launch also does vec_pred_setup for the next iteration
 int  vec_residuals(const VecArgs& a, int is_init, int ip_next, double tol, hipStream_t st, const XRank* xr = nullptr,
                    bool with_pred = false);
+// the scalar half of vec_residuals' kernel-by-kernel path on its own: for a residual kernel that is not k_residuals (tall form)
+void vec_scalar_indicators(const VecArgs& a, int is_init, int ip_next, double tol, hipStream_t st);
 void vec_pred_setup(const VecArgs& a, hipStream_t st);
 int  vec_pq_uv(const VecArgs& a, hipStream_t st, const XRank* xr = nullptr);
 int  vec_uv_corr(const VecArgs& a, hipStream_t st, const XRank* xr = nullptr);
@@ -102,5 +104,33 @@ template <typename T> struct ScatterSeg { T* dst = nullptr; const T* src = nullp
 template <typename T> struct ScatterRows { ScatterSeg<T> seg[SCATTER_SEGS]; };
 template <typename T> void vec_scatter_rows(const ScatterRows<T>& a, hipStream_t st, const Batch& bt);
 
+// ---------------------------------------------------------------- tall inequality form (kernels_tall.hip)
+// A pure-`ub` LP with many more rows than columns (lpipm_upload_ub_tall): A = [X I], X m x nx.  The Newton system is reduced
+// to the nx x nx SPD matrix K = X^T.diag(W_s).X + diag(E_x), W_s = z_s / x_s, E_x = z_x / x_x, and sym_solve(r1, r2)
+// (newton_equations.rs:214-225) becomes
+//   t = W_s*r2 + r1_s;  g = X^T.t - r1_x;  u_x = K^-1 g;  u_s = r2 - X.u_x;  v = W_s*u_s + r1_s;  u = [u_x; u_s]
+// What the kernels of one tall LP work in, next to its VecArgs (single LP: no member offset).
+struct TallArgs {
+    int nx, npa, nxp, mk;    // structural columns, their count padded to 16 (lda of X), to 128 (order of K), m padded to 16
+    double* Ws;              // [mk]      W_s, zeros beyond m: the `dinv` of the A.D.A^T launch that builds K
+    double* Ex;              // [nxp]     E_x, added to K's diagonal
+    double* T;               // [2][mp]   t of both right-hand sides: the V of gemv_t
+    double* G;               // [2][nxp]  g, then u_x: in/out of the Cholesky solve, the W of gemv_n
+    double* Us;              // [2][mp]   u_s, from gemv_n (alpha = -1, addend r2)
+};
+// Xt (nxp x mk, zeroed beforehand) = X^T for the m x nx block of the resident X (lda = npa)
+hipError_t tall_transpose(const double* X, int64_t ldx, int m, int nx, double* Xt, int64_t ldt, hipStream_t st);
+// W_s and E_x from the iterate (with_scales), and t for nrhs (0|1|2) right-hand sides (r1a, r2a), (r1b, r2b): r1 n-sized, r2 m-sized
+void tall_setup(const VecArgs& a, const TallArgs& t, bool with_scales, int nrhs, const double* r1a, const double* r2a,
+                const double* r1b, const double* r2b, hipStream_t st);
+// G[r][j] = sum over the row splits of ATpart[s][r][j] (slabs npa wide, in order) - r1{a,b}[j], j < nx; zeros up to nxp
+void tall_fold_rhs(const VecArgs& a, const TallArgs& t, int nrhs, const double* r1a, const double* r1b, hipStream_t st);
+// Tall counterparts of vec_pq_uv / vec_uv_corr (single GPU: d_tau is folded into k_delta): p, q, u, v -- v into R as the
+// dense path leaves it --, the same dots in the same reduction slots, FLAG_NAN_PQ.
+void tall_pq_uv(const VecArgs& a, const TallArgs& t, const double* r1a, const double* r1b, hipStream_t st);
+void tall_uv_corr(const VecArgs& a, const TallArgs& t, const double* r1a, hipStream_t st);
+// k_residuals for slabs of A^T.y that are npa wide: the slack columns' A^T.y is y itself (what slab 0 holds on the dense
+// path, next to zeros: the same bits).  Followed by vec_scalar_indicators.
+void tall_residuals(const VecArgs& a, const TallArgs& t, hipStream_t st);
 
 }  // namespace lpipm
