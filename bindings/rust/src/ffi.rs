@@ -110,6 +110,13 @@ extern "C" {
         ctx: *mut lpipm_ctx, count: u64, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, m_eq: u64, a_eq: *const f64,
         lda_eq: u64, b: *const *const f64, c: *const *const f64, c0: *const f64,
     ) -> c_int;
+    // A lockstep batch of tall inequality-form LPs over ONE A_ub (b[i]: m_ub doubles, c[i]: the n structural costs): A_ub and
+    // its transpose resident once, every member factoring its own n x n reduced system; each member bit-identical to
+    // lpipm_upload_ub_tall + lpipm_solve of that member alone.
+    pub fn lpipm_upload_lockstep_shared_ub_tall(
+        ctx: *mut lpipm_ctx, count: u64, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, b: *const *const f64,
+        c: *const *const f64, c0: *const f64,
+    ) -> c_int;
     // New b / c / c0 (each nullable: stays) for every member of the resident lockstep batch, in its upload's own form; A and
     // the kept first factor stay.  _device: packed row blocks on the device, member i at b_dev + i * ldb doubles.
     pub fn lpipm_update_lockstep_vectors(

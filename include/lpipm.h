@@ -147,9 +147,9 @@ int lpipm_upload_ub_eq(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const double* 
  * Scope.  Cholesky arm only: lpipm_solve with solver_type 1 or 2 returns LPIPM_ERR_UNSUPPORTED, and so do
  * lpipm_update_vectors (as after lpipm_upload_ub_eq), this upload on a context of a column split (lpipm_set_collective with
  * world > 1) or with the opt-in refined solves, and lpipm_k_adat (there is no M; lpipm_k_tall_normal returns K).  The first
- * iteration's factor is not kept (as for the QR arms).  `eq` rows (the reduced system is then a saddle point, not SPD) and
- * lockstep or shared-matrix batches of tall LPs are not built.  lpipm_k_iteration, lpipm_k_gemv_n, lpipm_k_gemv_t and
- * lpipm_k_gemv_dual work as on any other upload. */
+ * iteration's factor is not kept (as for the QR arms).  `eq` rows (the reduced system is then a saddle point, not SPD) are
+ * not built; many tall LPs over one A_ub are a lockstep batch (lpipm_upload_lockstep_shared_ub_tall, below).
+ * lpipm_k_iteration, lpipm_k_gemv_n, lpipm_k_gemv_t and lpipm_k_gemv_dual work as on any other upload. */
 int lpipm_upload_ub_tall(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub, const double* b_ub,
                          const double* c, double c0);
 
@@ -163,7 +163,8 @@ int lpipm_update_vectors(lpipm_ctx* ctx, const double* b, const double* c);
 
 /* New b, c and (optionally) c0 for EVERY member of the resident lockstep batch, whichever lpipm_upload_lockstep* made it, in
  * that upload's own form: b[i][m] and c[i][n] (c with its slack entries); after lpipm_upload_lockstep_shared_ub_eq
- * b[i] = [b_ub_i; b_eq_i] and c[i] = the n structural costs (the slack costs stay 0).  b or c may be NULL as a whole: those
+ * b[i] = [b_ub_i; b_eq_i] and c[i] = the n structural costs (the slack costs stay 0), after
+ * lpipm_upload_lockstep_shared_ub_tall b[i] of m_ub doubles and c[i] = the n structural costs.  b or c may be NULL as a whole: those
  * vectors stay (a right-hand-side sweep sends no costs); c0 == NULL: the constants stay.  A, the layout, the half-batch views
  * and the kept first factor(s) are not touched, and the padding beyond m and n stays zero: the next lpipm_solve_lockstep[_device]
  * is bit-identical to a fresh upload of the same members followed by a solve.  The host arrays are staged in one pinned block
@@ -314,6 +315,30 @@ int lpipm_upload_lockstep_shared_slack(lpipm_ctx* ctx, uint64_t count, uint64_t 
 int lpipm_upload_lockstep_shared_ub_eq(lpipm_ctx* ctx, uint64_t count, uint64_t n, uint64_t m_ub, const double* A_ub,
                                        uint64_t lda_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq,
                                        const double* const* b, const double* const* c, const double* c0 /* nullable */);
+/* A lockstep batch of tall inequality-form LPs (lpipm_upload_ub_tall) over ONE A_ub: L1 / L-infinity fits of many response
+ * vectors on one design matrix, quantile regression at many quantiles, scenario cuts under many right-hand sides.  Member i is
+ * (A_ub, b[i] (m_ub doubles), c[i] (the n structural costs), c0[i]); the arguments are those of
+ * lpipm_upload_lockstep_shared_ub_eq without its `eq` block.  X = A_ub and its transpose are resident ONCE for the batch
+ * (the transpose written once per upload, behind the equilibration); a member holds its vectors, its own n x n matrix K with
+ * the factor's inverses and its slabs -- nothing of a member grows as m_ub^2 and nothing of it is a copy of X.  Every pass over
+ * X and the launch that builds the members' K read the one copy for a group of members.
+ * Solve with lpipm_solve_lockstep / lpipm_solve_lockstep_device: x has n + m_ub entries, slack values last; status, fun and
+ * iterations per member.  Every member is bit-identical to lpipm_upload_ub_tall + lpipm_solve of that member alone -- x, fun,
+ * status and iteration count -- whatever the count, whichever members have finished, as one view or two half-batch views.
+ * lpipm_update_lockstep_vectors[_device] replace b[i] (m_ub doubles), c[i] (the n structural costs) and c0 in place: X and its
+ * transpose stay, and the next solve is bit-identical to a fresh upload of the same members.  lpipm_set_scaling works as for any
+ * shared-matrix batch: one set of exponents (lpipm_get_scaling with member 0), X equilibrated once, b and c of the upload and
+ * of later updates scaled with the kept exponents, x in the caller's units.  No first factor is kept
+ * (lpipm_set_first_factor_cache changes nothing here); lpipm_get_resident_bytes counts X and its transpose once.
+ * Return codes: m_ub == 0 LPIPM_UNCONSTRAINED; null pointers, count == 0 (or > 4096), lda_ub < n LPIPM_ERR_BAD_ARGUMENT; a
+ * column-split context or one with the refined solves LPIPM_ERR_UNSUPPORTED (as lpipm_upload_ub_tall); solver_type 1 or 2
+ * LPIPM_ERR_UNSUPPORTED (as every lockstep batch); lpipm_k_tall_normal, lpipm_k_tall_sym_solve, lpipm_k_iteration and
+ * lpipm_k_adat on such a batch LPIPM_ERR_UNSUPPORTED.
+ * Not built: tall batches whose members own their matrices, grouping of tall members inside lpipm_solve_batch*, `eq` rows, a
+ * kept K_1 = X^T.X + I, fused small-LP vector kernels for the tall form. */
+int lpipm_upload_lockstep_shared_ub_tall(lpipm_ctx* ctx, uint64_t count, uint64_t n, uint64_t m_ub, const double* A_ub,
+                                         uint64_t lda_ub, const double* const* b, const double* const* c,
+                                         const double* c0 /* nullable */);
 /* Device bytes the context holds for its resident problem(s) (arenas + shared matrix with the batch's one kept first factor +
  * factor workspace, and the exponent block of lpipm_set_scaling while scaling is on); 0 before any upload. */
 int lpipm_get_resident_bytes(const lpipm_ctx* ctx, uint64_t* bytes_out);
@@ -357,7 +382,7 @@ int lpipm_get_phase_times(const lpipm_ctx* ctx, lpipm_phase_times* out);
  * triangle valid (the strict upper triangle is unspecified).  `ms_out` (nullable) gets the device
  * time of the kernel launch(es) averaged over `repeats` (>= 1) back-to-back launches. */
 int lpipm_k_adat(lpipm_ctx* ctx, const double* dinv, double* M_out, int repeats, double* ms_out);   /* tall upload: LPIPM_ERR_UNSUPPORTED */
-/* On a tall upload (lpipm_upload_ub_tall), with nx its structural columns, m its rows, n = nx + m and dinv[n] = x / z:
+/* On a single tall upload (lpipm_upload_ub_tall; not a batch), with nx its structural columns, m its rows, n = nx + m and dinv[n] = x / z:
  * K_out (nx x nx row-major, LOWER triangle valid) = X^T.diag(1 / dinv_s).X + diag(1 / dinv_x).  Any other upload:
  * LPIPM_ERR_UNSUPPORTED. */
 int lpipm_k_tall_normal(lpipm_ctx* ctx, const double* dinv, double* K_out);

@@ -305,7 +305,7 @@ class Context:
         if lock is None:
             raise BackendError("no lockstep batch is resident on this context")
         K, m, n, _, _, cs = lock
-        return K, m, cs[0].shape[0]                # (after upload_lockstep_shared_ub_eq: the structural costs only)
+        return K, m, cs[0].shape[0]                # (after upload_lockstep_shared_ub_eq / _ub_tall: the structural costs only)
 
     def update_lockstep_vectors(self, bs=None, cs=None, c0s=None):
         """New b, c and c0 for every member of the resident lockstep batch (lpipm_update_lockstep_vectors), in the form of the
@@ -452,6 +452,32 @@ class Context:
                                                                   _p(A_eq) if m_eq else None, n, arr(bs), arr(cs), c0))
         self._lock = (K, m_ub + m_eq, n + m_ub, None, bs, cs)
         self.m, self.n = m_ub + m_eq, n + m_ub
+        return self
+
+    def upload_lockstep_shared_ub_tall(self, A_ub, bs, cs, c0s=None):
+        """`len(bs)` tall inequality-form LPs over ONE matrix (lpipm_upload_lockstep_shared_ub_tall): member i is
+        min cs[i]'x st A_ub x <= bs[i], x >= 0, usually with many more rows than columns.  A_ub and its transpose are resident
+        once; every member factors its own n x n reduced system.  solve_lockstep returns x with n + m_ub entries, slack values
+        last -- every member bit-identical to Context.upload(Problem...ub().build(), tall=True) + solve_raw."""
+        bs = [_f64(b) for b in bs]; cs = [_f64(c) for c in cs]
+        K = len(bs)
+        if K < 1 or len(cs) != K or (c0s is not None and len(c0s) != K) or cs[0].ndim != 1:
+            raise IncompatibleInputDimensions()
+        n = cs[0].shape[0]
+        A_ub = _f64(A_ub)
+        if A_ub.ndim != 2 or A_ub.shape[1] != n:
+            raise IncompatibleInputDimensions()
+        m_ub = A_ub.shape[0]
+        for b, c in zip(bs, cs):
+            if b.shape != (m_ub,) or c.shape != (n,):
+                raise IncompatibleInputDimensions()
+        dp = C.POINTER(C.c_double)
+        arr = lambda lst: (dp * K)(*[_p(a) for a in lst])
+        c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
+        _raise_for(_capi.lib().lpipm_upload_lockstep_shared_ub_tall(self._h, K, n, m_ub, _p(A_ub) if m_ub else None, n,
+                                                                    arr(bs), arr(cs), c0))
+        self._lock = (K, m_ub, n + m_ub, None, bs, cs)      # (the lockstep form: b[i] of m_ub, c[i] of the n structural costs)
+        self.m, self.n = m_ub, n + m_ub
         return self
 
     def resident_bytes(self) -> int:

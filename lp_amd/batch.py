@@ -133,6 +133,28 @@ def solve_shared_ub_eq(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_gr
     return out
 
 
+def solve_shared_ub_tall(A_ub, bs, cs, c0s=None, opts=None, ctx=None, max_group=32):
+    """Tall inequality-form LPs over ONE matrix (many right-hand sides or costs on one design matrix, A_ub x <= bs[i] with many
+    more rows than columns): member i = (bs[i], cs[i] = the n structural costs, c0s[i]).  Lockstep groups of at most
+    `max_group` on one context through lpipm_upload_lockstep_shared_ub_tall: A_ub and its transpose resident once, every member
+    factoring its own n x n reduced system.  Returns what solve_shared_ub_eq returns; x_slack has n + m_ub entries."""
+    import lp_amd
+    count = len(bs)
+    if len(cs) != count or (c0s is not None and len(c0s) != count):
+        raise lp_amd.IncompatibleInputDimensions()
+    if max_group < 1:
+        raise lp_amd.InvalidParameter("max_group must be >= 1")
+    ctx = ctx or lp_amd.default_context(0)
+    opts = opts or lp_amd.InteriorPoint.default().opts()
+    out = []
+    for k0 in range(0, count, max_group):
+        k1 = min(k0 + max_group, count)
+        ctx.upload_lockstep_shared_ub_tall(A_ub, bs[k0:k1], cs[k0:k1], None if c0s is None else c0s[k0:k1])
+        for st, x, fun, it in ctx.solve_lockstep(opts):
+            out.append(dict(status=st, x_slack=x, fun=fun, iterations=it))
+    return out
+
+
 def sweep_chunks(count: int, max_group: int):
     """The equal chunks of a sweep: k = ceil(count / max_group) chunks of g = ceil(count / k) members, as lists of member
     indices.  The last chunk is filled up to g with repeats of its own last member (at most k - 1 of them in all), so
@@ -180,3 +202,10 @@ def sweep_shared_ub_eq(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_gr
     """solve_shared_ub_eq as a sweep: one upload_lockstep_shared_ub_eq, then update_lockstep_vectors per later chunk (bs[i] =
     [b_ub_i; b_eq_i], cs[i] = the n structural costs).  Returns what solve_shared_ub_eq returns, bit for bit."""
     return _sweep(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_eq(A_ub, A_eq, b, c, c0), bs, cs, c0s, opts, ctx, max_group)
+
+
+def sweep_shared_ub_tall(A_ub, bs, cs, c0s=None, opts=None, ctx=None, max_group=32):
+    """solve_shared_ub_tall as a sweep: one upload_lockstep_shared_ub_tall, then update_lockstep_vectors per later chunk (bs[i]
+    of m_ub entries, cs[i] = the n structural costs); A_ub is uploaded and transposed once.  Returns what solve_shared_ub_tall
+    returns, bit for bit."""
+    return _sweep(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_tall(A_ub, b, c, c0), bs, cs, c0s, opts, ctx, max_group)

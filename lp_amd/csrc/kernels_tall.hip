@@ -14,8 +14,11 @@
 // Both u and v come from the reduced solve itself: taking only v from it and u from the dense epilogue Dinv * (A^T.v - r1)
 // cancels catastrophically on the slack block.  Everything downstream (d_tau, Delta, ratio test, step,
 // residuals, indicators) is the dense path's and sees p, q, u, v where it sees them there.
-// Reductions are fixed-order (kernels_vec.hip's two stages, the same slots); a tall LP is a single LP (no member offset
-// beyond what vbatch does for the VecArgs), and the kernels of the speculatively enqueued head test the done word.
+// Reductions are fixed-order (kernels_vec.hip's two stages, the same slots).  The vector kernels run with gridDim.z = the LPs
+// of the launch (a single tall LP, or the members of lpipm_upload_lockstep_shared_ub_tall): tbatch moves the VecArgs, the
+// TallArgs and the right-hand sides to the member and skips a finished one, as vbatch does on the dense path; a member's
+// arithmetic and reduction order are those of the single LP.  The kernels of the speculatively enqueued head test the done
+// word.
 #include "vec_kernels.hpp"
 #include "vec_device.hpp"
 
@@ -55,9 +58,9 @@ hipError_t tall_transpose(const double* X, int64_t ldx, int m, int nx, double* X
 // ---------------------------------------------------------------- set-up: W_s, E_x, t
 // with_scales: W_s = z_s / x_s (i < m; the padding up to mk stays zero) and E_x = z_x / x_x (j < nx) from the iterate.
 // t of right-hand side r (r < nrhs): T[r][i] = W_s[i] * r2[i] + r1[nx + i].
-__global__ __launch_bounds__(256) void k_tall_setup(VecArgs a, TallArgs t, int with_scales, int nrhs, const double* r1a,
-                                                    const double* r2a, const double* r1b, const double* r2b) {
-    if (!vbatch(a, true)) return;
+__global__ __launch_bounds__(256) void k_tall_setup(VecArgs a, TallArgs t, int with_scales, int nrhs, TallRhs rhs) {
+    if (!tbatch(a, t, rhs)) return;
+    const double *r1a = rhs.r1a, *r2a = rhs.r2a, *r1b = rhs.r1b, *r2b = rhs.r2b;
     const int stride = gridDim.x * 256;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
         double ws;
@@ -71,15 +74,16 @@ __global__ __launch_bounds__(256) void k_tall_setup(VecArgs a, TallArgs t, int w
 }
 void tall_setup(const VecArgs& a, const TallArgs& t, bool with_scales, int nrhs, const double* r1a, const double* r2a,
                 const double* r1b, const double* r2b, hipStream_t st) {
-    hipLaunchKernelGGL(k_tall_setup, dim3(a.nblk, 1, 1), dim3(256), 0, st, a, t, with_scales ? 1 : 0, nrhs, r1a, r2a, r1b, r2b);
+    hipLaunchKernelGGL(k_tall_setup, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, with_scales ? 1 : 0, nrhs,
+                       TallRhs{r1a, r2a, r1b, r2b});
 }
 
 // ---------------------------------------------------------------- right-hand side of the reduced solve
 // G[r][j] = sum_s ATpart[s][r][j] - r1[j] for j < nx, 0 for nx <= j < nxp.  A workgroup takes 64 columns; its four waves
 // take the four quarters of the row splits, each in index order, and the quarters are added as (w0 + w1) + (w2 + w3): a
-// fixed order whatever the launch.  grid (64-column groups of nxp, right-hand sides).
-__global__ __launch_bounds__(256) void k_tall_fold(VecArgs a, TallArgs t, int nrhs, const double* r1a, const double* r1b) {
-    if (!vbatch(a, true)) return;
+// fixed order whatever the launch.  grid (64-column groups of nxp, right-hand sides, LPs).
+__global__ __launch_bounds__(256) void k_tall_fold(VecArgs a, TallArgs t, int nrhs, TallRhs rhs) {
+    if (!tbatch(a, t, rhs)) return;
     __shared__ double part[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = blockIdx.x * 64 + lane, r = blockIdx.y;
@@ -91,20 +95,22 @@ __global__ __launch_bounds__(256) void k_tall_fold(VecArgs a, TallArgs t, int nr
     part[wave][lane] = s;
     __syncthreads();
     if (wave != 0 || j >= t.nxp) return;
-    const double* r1 = r == 0 ? r1a : r1b;
+    const double* r1 = r == 0 ? rhs.r1a : rhs.r1b;
     const double sum = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
     t.G[(long long)r * t.nxp + j] = j < t.nx ? sum - r1[j] : 0.0;
 }
 void tall_fold_rhs(const VecArgs& a, const TallArgs& t, int nrhs, const double* r1a, const double* r1b, hipStream_t st) {
-    hipLaunchKernelGGL(k_tall_fold, dim3((t.nxp + 63) / 64, nrhs, 1), dim3(256), 0, st, a, t, nrhs, r1a, r1b);
+    hipLaunchKernelGGL(k_tall_fold, dim3((t.nxp + 63) / 64, nrhs, a.bcount), dim3(256), 0, st, a, t, nrhs,
+                       TallRhs{r1a, nullptr, r1b, nullptr});
 }
 
 // ---------------------------------------------------------------- epilogues
 // Predictor: (p, q) from right-hand side 0, (u, v) from right-hand side 1.  u_x = G, u_s = Us; v = W_s * u_s + r1_s goes
 // to R (q into R[0], v into R[1], as the dense solve leaves them) and q to a.q.  The four dots of delta.rs:29-32 go to
 // the reduction slots 0 .. 3 and the NaN check of newton_equations.rs:190-194 sets FLAG_NAN_PQ, as k_pq_uv.
-__global__ __launch_bounds__(256) void k_tall_pq_uv(VecArgs a, TallArgs t, const double* r1a, const double* r1b) {
-    if (!vbatch(a, true)) return;
+__global__ __launch_bounds__(256) void k_tall_pq_uv(VecArgs a, TallArgs t, TallRhs rhs) {
+    if (!tbatch(a, t, rhs)) return;
+    const double *r1a = rhs.r1a, *r1b = rhs.r1b;
     const int stride = gridDim.x * 256;
     double acc[4] = {0, 0, 0, 0};
     int nan = 0;
@@ -134,8 +140,9 @@ __global__ __launch_bounds__(256) void k_tall_pq_uv(VecArgs a, TallArgs t, const
     block_reduce_store<4, false>(acc, a.red, 0);
 }
 // Corrector: only (u, v) change (k_uv_corr): c.u and b.v into slots 0 and 1, v into R[0].
-__global__ __launch_bounds__(256) void k_tall_uv_corr(VecArgs a, TallArgs t, const double* r1a) {
-    if (!vbatch(a, true)) return;
+__global__ __launch_bounds__(256) void k_tall_uv_corr(VecArgs a, TallArgs t, TallRhs rhs) {
+    if (!tbatch(a, t, rhs)) return;
+    const double* r1a = rhs.r1a;
     const int stride = gridDim.x * 256;
     double acc[2] = {0, 0};
     for (int j = blockIdx.x * 256 + threadIdx.x; j < a.n; j += stride) {
@@ -151,17 +158,18 @@ __global__ __launch_bounds__(256) void k_tall_uv_corr(VecArgs a, TallArgs t, con
     block_reduce_store<2, false>(acc, a.red, 0);
 }
 void tall_pq_uv(const VecArgs& a, const TallArgs& t, const double* r1a, const double* r1b, hipStream_t st) {
-    hipLaunchKernelGGL(k_tall_pq_uv, dim3(a.nblk, 1, 1), dim3(256), 0, st, a, t, r1a, r1b);
+    hipLaunchKernelGGL(k_tall_pq_uv, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, TallRhs{r1a, nullptr, r1b, nullptr});
 }
 void tall_uv_corr(const VecArgs& a, const TallArgs& t, const double* r1a, hipStream_t st) {
-    hipLaunchKernelGGL(k_tall_uv_corr, dim3(a.nblk, 1, 1), dim3(256), 0, st, a, t, r1a);
+    hipLaunchKernelGGL(k_tall_uv_corr, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, TallRhs{r1a, nullptr, nullptr, nullptr});
 }
 
 // ---------------------------------------------------------------- residuals at the current point
 // k_residuals (residual.rs:22-31, feasible_point.rs:122-123) with the row-split slabs of A^T.y only npa wide: a structural
 // column sums its slabs in index order, a slack column's A^T.y is y_i itself.  The same six partial sums in slots 0 .. 5.
 __global__ __launch_bounds__(256) void k_tall_residuals(VecArgs a, TallArgs t) {
-    if (!vbatch(a, true)) return;
+    TallRhs none;
+    if (!tbatch(a, t, none)) return;
     const int stride = gridDim.x * 256;
     const double tau = a.S[S_TAU];
     double acc[6] = {0, 0, 0, 0, 0, 0};
@@ -188,7 +196,7 @@ __global__ __launch_bounds__(256) void k_tall_residuals(VecArgs a, TallArgs t) {
     block_reduce_store<6, false>(acc, a.red, 0);
 }
 void tall_residuals(const VecArgs& a, const TallArgs& t, hipStream_t st) {
-    hipLaunchKernelGGL(k_tall_residuals, dim3(a.nblk, 1, 1), dim3(256), 0, st, a, t);
+    hipLaunchKernelGGL(k_tall_residuals, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t);
 }
 
 }  // namespace lpipm

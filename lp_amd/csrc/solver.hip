@@ -99,6 +99,8 @@ struct Problem {
     // The tall inequality form (lpipm_upload_ub_tall; kernels_tall.hip): a pure-`ub` LP whose Newton system is reduced to the
     // nxp x nxp matrix K = X^T.W_s.X + E_x.  M is then K (ld nxp), `factor` its plan, `adat` the plan of the launch that builds
     // it from Xt, and nothing in the arena is m x m.  The row-split slabs of A^T.v are npa wide (tv.npa), not np.
+    // A batch of tall LPs over ONE X (lpipm_upload_lockstep_shared_ub_tall: tall && shared_a) keeps X and Xt once, in a_shared;
+    // every member's arena then holds its vectors, W_s, E_x, T, G, U_s, its own K with its factor plan's inverses and its slabs.
     bool tall = false;
     double* Xt = nullptr;        // nxp x mk, row-major, zero padded: X^T of the resident (scaled) X
     TallArgs tv{};
@@ -477,13 +479,14 @@ static size_t first_factor_bytes(int mp, int super_w) {
 }
 // The arena of a tall LP (Problem::tall): the vectors of the dense layout, X and its transpose, the nxp x nxp matrix K with
 // its factor plan, and the work vectors of the reduced solve.  Nothing grows as m^2: no M, M0 or kept first factor, the slabs
-// of A^T.v are npa wide and the chunk slabs of A.x are those of the npa stored columns.
+// of A^T.v are npa wide and the chunk slabs of A.x are those of the npa stored columns.  A member of a shared batch
+// (p.shared_a) has the same arena without X and Xt: the batch's one copy of each is in a_shared (upload_impl).
 static int layout_tall(Problem& p, FactorPlan& plan, FactorPlan& plan1, const AdatPlan& ap, Arena& ar, bool build, hipStream_t st) {
     VecArgs& v = p.va;
     TallArgs& t = p.tv;
     const size_t mp = (size_t)p.mp, np = (size_t)p.np, nxp = (size_t)t.nxp;
-    p.A = ar.take<double>(mp * p.npa);
-    p.Xt = ar.take<double>(nxp * (size_t)t.mk);
+    p.A = p.shared_a ? nullptr : ar.take<double>(mp * p.npa);
+    p.Xt = p.shared_a ? nullptr : ar.take<double>(nxp * (size_t)t.mk);
     v.b = ar.take<double>(mp); v.c = ar.take<double>(np);
     v.x = ar.take<double>(np); v.y = ar.take<double>(mp); v.z = ar.take<double>(np);
     v.dinv = ar.take<double>(np); v.xs = ar.take<double>(np); v.r1 = ar.take<double>(np); v.rD = ar.take<double>(np);
@@ -624,6 +627,7 @@ static int scale_setup(lpipm_ctx* c, int mp, int np, int npa, int sets) {
 // hint_verified: the caller has done that check on these very matrices (batch_impl) and it is not repeated.
 // `parts` (count == 1, or shared): the rows come as two blocks of nx = n - n_slack columns -- m_ub rows of A_ub, then
 // m - m_ub rows of A_eq -- and c holds only the nx structural costs; the slack structure is then true by construction.
+// tall (parts with `ub` rows only; count == 1, or shared): the tall inequality form of the LP, or of every member over one X.
 // count == 1: b split the same way, in parts (lpipm_upload_ub_eq).  shared: the blocks are the batch's one matrix and
 // b[i] = [b_ub_i; b_eq_i] comes per member (lpipm_upload_lockstep_shared_ub_eq).
 struct UploadParts { uint64_t m_ub; const double* A_ub; uint64_t lda_ub; const double* b_ub;
@@ -634,7 +638,7 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
                        const UploadParts* parts = nullptr, bool shared = false, bool hint_verified = false, bool keep_ok = true,
                        bool tall = false) {
     if (!c || count < 1 || !cc) return LPIPM_ERR_BAD_ARGUMENT;
-    if (tall && (!parts || shared || count != 1 || n_slack != m)) return LPIPM_ERR_BAD_ARGUMENT;
+    if (tall && (!parts || (!shared && count != 1) || n_slack != m)) return LPIPM_ERR_BAD_ARGUMENT;
     if (!parts && (!A || !b || lda < n)) return LPIPM_ERR_BAD_ARGUMENT;
     if (parts && (shared ? !b : count != 1)) return LPIPM_ERR_BAD_ARGUMENT;
     for (int i = 0; i < count; ++i)
@@ -674,7 +678,13 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
         c->p.nblk = (int)((big + 255) / 256);
         if (c->p.nblk > RED_STRIDE) c->p.nblk = RED_STRIDE;
         // (tall: the launch builds K from Xt -- nxp rows, a contraction over the mk padded rows of X)
-        c->ap = tall ? plan_adat(nxp, mk, 1, c->num_cu, 1, c->units_env) : plan_adat(mp, npa, count, c->num_cu, c->world, c->units_env);
+        // A tall batch: every member's K must have the bits the single LP's has.  The units kernel gives them whatever the
+        // count; the round-2 kernel (which a single LP of a few tiles with several chunks takes) only with the single LP's
+        // own workgroup count once the contraction is longer than 4096 (round2_unit): the batch then runs that very plan.
+        if (tall) {
+            const AdatPlan single = plan_adat(nxp, mk, 1, c->num_cu, 1, c->units_env);
+            c->ap = shared && single.units ? plan_adat(nxp, mk, count, c->num_cu, 1, c->units_env) : single;
+        } else c->ap = plan_adat(mp, npa, count, c->num_cu, c->world, c->units_env);
         Arena measure;
         LP_TRY(layout_problem(c->p, c->plan, c->plan1, c->ap, c->refine, keep, measure, false, st));
         c->p.bstride = round_up(measure.off, 4096);
@@ -685,7 +695,9 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
         real.base = c->p.arena;
         LP_TRY(layout_problem(c->p, c->plan, c->plan1, c->ap, c->refine, keep, real, true, st));
         if (shared) {              // the one A of the batch: mp x npa like an arena's, zero padding; behind it the one kept factor
-            const size_t a_bytes = (size_t)mp * (size_t)npa * sizeof(double);
+            // (tall: behind X its transpose, nxp x mk, once for the batch; no factor is kept)
+            const size_t x_bytes = (size_t)mp * (size_t)npa * sizeof(double);
+            const size_t a_bytes = x_bytes + (tall ? (size_t)nxp * (size_t)mk * sizeof(double) : 0);
             Arena sh_measure;
             sh_measure.off = a_bytes;
             if (c->p.shared_factor) LP_TRY(layout_shared_factor(c->p, c->plan, c->plan1, sh_measure, false, st));
@@ -693,6 +705,7 @@ static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const do
             LP_HIP(hipMalloc((void**)&c->p.a_shared, c->p.a_shared_bytes));
             LP_HIP(hipMemsetAsync(c->p.a_shared, 0, c->p.a_shared_bytes, st));
             c->p.A = c->p.a_shared;
+            if (tall) c->p.Xt = (double*)((char*)c->p.a_shared + x_bytes);
             Arena sh;
             sh.base = (char*)c->p.a_shared; sh.off = a_bytes;
             if (c->p.shared_factor) LP_TRY(layout_shared_factor(c->p, c->plan, c->plan1, sh, true, st));
@@ -796,6 +809,17 @@ extern "C" int lpipm_upload_ub_tall(lpipm_ctx* c, uint64_t n, uint64_t m_ub, con
     return upload_impl(c, 1, m_ub, n + m_ub, nullptr, 0, nullptr, &cc, &c0, m_ub, &parts, false, false, false, true);
 }
 
+extern "C" int lpipm_upload_lockstep_shared_ub_tall(lpipm_ctx* c, uint64_t count, uint64_t n, uint64_t m_ub, const double* A_ub,
+                                                    uint64_t lda_ub, const double* const* b, const double* const* cc,
+                                                    const double* c0) {
+    if (!c || count < 1 || count > 4096 || !b || !cc) return LPIPM_ERR_BAD_ARGUMENT;
+    if (m_ub == 0) return LPIPM_UNCONSTRAINED;                              // linear_program.rs:134-136
+    if (n == 0 || !A_ub || lda_ub < n) return LPIPM_ERR_BAD_ARGUMENT;
+    if (c->world > 1 || c->refine > 0) return LPIPM_ERR_UNSUPPORTED;        // as lpipm_upload_ub_tall
+    const UploadParts parts{m_ub, A_ub, lda_ub, nullptr, nullptr, 0, nullptr};
+    return upload_impl(c, (int)count, m_ub, n + m_ub, nullptr, 0, b, cc, c0, m_ub, &parts, true, false, false, true);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Y = add + A.W and Upart = row-split slabs of A^T.V on the stored structural columns, plus the
 // identity block of the slack columns
@@ -810,7 +834,7 @@ static hipError_t ctx_gemv_n(lpipm_ctx* c, int nrhs, const double* W, const doub
 static hipError_t ctx_gemv_t(lpipm_ctx* c, int nrhs, const double* V, const Batch& bt) {
     ++c->gemv_passes;
     // (tall: slabs npa wide; the slack columns' part of A^T.v is v itself, and the consumers take it from there)
-    if (c->p.tall) return launch_gemv_t(c->p.A, c->p.npa, c->p.mp, c->p.npa, nrhs, V, c->p.mp, c->p.ATpart, c->rs.st, c->p.npa, bt);
+    if (c->p.tall) return launch_gemv_t(c->p.A, c->p.npa, c->p.mp, c->p.npa, nrhs, V, c->p.mp, c->p.ATpart, c->rs.st, c->p.npa, bt, c->p.shared_a);
     hipError_t e = launch_gemv_t(c->p.A, c->p.npa, c->p.mp, c->p.npa, nrhs, V, c->p.mp, c->p.ATpart, c->rs.st, c->p.np, bt, c->p.shared_a);
     if (e != hipSuccess) return e;
     return launch_slack_t(c->p.ns, c->p.nx, nrhs, c->p.nsplit, V, c->p.mp, c->p.ATpart, c->p.np, c->rs.st, bt);
@@ -819,7 +843,7 @@ static hipError_t ctx_gemv_t(lpipm_ctx* c, int nrhs, const double* V, const Batc
 static hipError_t ctx_gemv_dual(lpipm_ctx* c, const double* W, const double* V, double* AxPart, const Batch& bt) {
     ++c->gemv_passes;
     if (c->p.tall) {   // slabs of A^T.v npa wide (see ctx_gemv_t); w_s into chunk slab 0 of A.w
-        hipError_t et = launch_gemv_dual(c->p.A, c->p.npa, c->p.mp, c->p.npa, W, V, AxPart, c->p.ATpart, c->p.npa, c->rs.st, bt);
+        hipError_t et = launch_gemv_dual(c->p.A, c->p.npa, c->p.mp, c->p.npa, W, V, AxPart, c->p.ATpart, c->p.npa, c->rs.st, bt, c->p.shared_a);
         if (et != hipSuccess) return et;
         return launch_slack_n(c->p.ns, c->p.nx, 1, W, c->p.np, AxPart, c->p.mp, c->rs.st, bt);
     }
@@ -877,7 +901,7 @@ static hipError_t run_tall_normal(lpipm_ctx* c, const Batch& bt) {
     const TallArgs& t = c->p.tv;
     AdatLaunch a{};
     a.A = c->p.Xt; a.lda = t.mk; a.dinv = t.Ws; a.M = c->p.M; a.ldm = t.nxp; a.M2 = nullptr;
-    a.K = t.mk; a.diag_pad_from = t.nx; a.batch = bt; a.shared_a = false;
+    a.K = t.mk; a.diag_pad_from = t.nx; a.batch = bt; a.shared_a = c->p.shared_a;    // (a batch: one Xt, every member's own W_s)
     hipError_t e = launch_adat(c->ap, c->p.adat, a, false, c->rs.st, nullptr);
     if (e != hipSuccess) return e;
     return launch_slack_diag(t.nx, 0, t.Ex, c->p.M, t.nxp, c->rs.st, bt);
@@ -897,7 +921,7 @@ static int tall_sym_solve(lpipm_ctx* c, int nrhs, const double* r1a, const doubl
     LP_HIP(launch_chol_solve(c->p.M, t.nxp, *c->p.factor, nrhs, t.G, c->p.Y, st, bt));   // u_x = K^-1 g
     prof_mark(c, T_TRSV);
     ++c->gemv_passes;                                                             // u_s = r2 - X.u_x
-    LP_HIP(launch_gemv_n(c->p.A, c->p.npa, (int)c->p.m, c->p.npa, nrhs, t.G, t.nxp, r2a, r2b, t.Us, c->p.mp, st, -1.0, bt));
+    LP_HIP(launch_gemv_n(c->p.A, c->p.npa, (int)c->p.m, c->p.npa, nrhs, t.G, t.nxp, r2a, r2b, t.Us, c->p.mp, st, -1.0, bt, c->p.shared_a));
     prof_mark(c, T_GEMV);
     return LPIPM_OK;
 }
@@ -2015,7 +2039,7 @@ static int tall_entry_iterate(lpipm_ctx* c, const double* dinv) {
 extern "C" int lpipm_k_tall_normal(lpipm_ctx* c, const double* dinv, double* K_out) {
     if (!c || !dinv || !K_out) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
-    if (!c->p.tall) return LPIPM_ERR_UNSUPPORTED;
+    if (!c->p.tall || c->p.shared_a) return LPIPM_ERR_UNSUPPORTED;     // (a single tall upload, not a batch)
     LP_HIP(hipSetDevice(c->device));
     vec_blind_start(c->p.va, c->rs.st);                       // clears done / flags; the iterate is overwritten next
     LP_TRY(tall_entry_iterate(c, dinv));
@@ -2031,7 +2055,7 @@ extern "C" int lpipm_k_tall_sym_solve(lpipm_ctx* c, const double* dinv, int nrhs
                                       double* U_out, double* V_out, int32_t* info_out) {
     if (!c || !dinv || !R1 || !R2 || !U_out || !V_out || (nrhs != 1 && nrhs != 2)) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
-    if (!c->p.tall) return LPIPM_ERR_UNSUPPORTED;
+    if (!c->p.tall || c->p.shared_a) return LPIPM_ERR_UNSUPPORTED;     // (a single tall upload, not a batch)
     LP_HIP(hipSetDevice(c->device));
     hipStream_t st = c->rs.st;
     VecArgs& v = c->p.va;
@@ -2290,7 +2314,7 @@ extern "C" int lpipm_k_iteration(lpipm_ctx* c, const lpipm_opts* o, int ip, doub
                                  int32_t* info_out) {
     if (!c || !o || !x || !y || !z || !tau || !kappa || !d_x || !d_y || !d_z || !d_tk || !alpha_out) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
-    if (c->p.B != 1) return LPIPM_ERR_UNSUPPORTED;
+    if (c->p.B != 1 || (c->p.tall && c->p.shared_a)) return LPIPM_ERR_UNSUPPORTED;      // one LP, not a batch (of any count)
     // (a column-split context: x, z, d_x, d_z are this rank's slices, everything else is replicated, and every rank must
     //  call together -- enqueue_residuals / enqueue_iteration contain the cross-rank reductions)
     LP_HIP(hipSetDevice(c->device));

@@ -1,5 +1,5 @@
 // vec_device.hpp -- device helpers shared by the vector kernels (kernels_vec.hip, kernels_tall.hip): fixed-order
-// reductions, the lockstep-batch pointer shift and the (virtual) thread a kernel body is written for.
+// reductions, the lockstep-batch pointer shifts (vbatch, tbatch) and the (virtual) thread a kernel body is written for.
 #pragma once
 #include "vec_kernels.hpp"
 
@@ -64,6 +64,19 @@ __device__ __forceinline__ bool vbatch(VecArgs& a, bool check_done) {
     a.potrf_info = batch_ptr(a.potrf_info, bk); a.flags = batch_ptr(a.flags, bk); a.done = batch_ptr(a.done, bk);
     a.skip_refine = batch_ptr(a.skip_refine, bk);
     a.done_chk = batch_ptr(a.done_chk, bk);
+    return true;
+}
+
+// The same shift for a kernel of the tall form (kernels_tall.hip): besides the VecArgs, every TallArgs pointer and the raw
+// right-hand-side pointers the launch was handed (LP 0's arena addresses; null stays null) move to LP bfirst + blockIdx.z.
+// Every pointer such a kernel dereferences goes through here: one that does not reads or writes LP 0's vectors.
+__device__ __forceinline__ bool tbatch(VecArgs& a, TallArgs& t, TallRhs& r) {
+    const BatchK bk{a.bstride, nullptr, 0, a.bfirst};      // (taken before vbatch moves a's own fields)
+    if (!vbatch(a, true)) return false;
+    if (blockIdx.z == 0 && a.bfirst == 0) return true;
+    t.Ws = batch_ptr(t.Ws, bk); t.Ex = batch_ptr(t.Ex, bk); t.T = batch_ptr(t.T, bk); t.G = batch_ptr(t.G, bk);
+    t.Us = batch_ptr(t.Us, bk);
+    r.r1a = batch_ptr(r.r1a, bk); r.r2a = batch_ptr(r.r2a, bk); r.r1b = batch_ptr(r.r1b, bk); r.r2b = batch_ptr(r.r2b, bk);
     return true;
 }
 

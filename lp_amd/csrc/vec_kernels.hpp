@@ -109,7 +109,8 @@ template <typename T> void vec_scatter_rows(const ScatterRows<T>& a, hipStream_t
 // to the nx x nx SPD matrix K = X^T.diag(W_s).X + diag(E_x), W_s = z_s / x_s, E_x = z_x / x_x, and sym_solve(r1, r2)
 // (newton_equations.rs:214-225) becomes
 //   t = W_s*r2 + r1_s;  g = X^T.t - r1_x;  u_x = K^-1 g;  u_s = r2 - X.u_x;  v = W_s*u_s + r1_s;  u = [u_x; u_s]
-// What the kernels of one tall LP work in, next to its VecArgs (single LP: no member offset).
+// What the kernels of a tall LP work in, next to its VecArgs.  Every pointer is LP 0's, as in VecArgs: member z of a lockstep
+// batch has its own bstride bytes * z further (tbatch, vec_device.hpp).
 struct TallArgs {
     int nx, npa, nxp, mk;    // structural columns, their count padded to 16 (lda of X), to 128 (order of K), m padded to 16
     double* Ws;              // [mk]      W_s, zeros beyond m: the `dinv` of the A.D.A^T launch that builds K
@@ -118,6 +119,9 @@ struct TallArgs {
     double* G;               // [2][nxp]  g, then u_x: in/out of the Cholesky solve, the W of gemv_n
     double* Us;              // [2][mp]   u_s, from gemv_n (alpha = -1, addend r2)
 };
+// The right-hand sides a tall launch is handed: (r1a, r2a) and (r1b, r2b), r1 n-sized, r2 m-sized, LP 0's addresses in the
+// arena (or, for the single LP of the kernel entries, any device buffer); the unused ones are null.
+struct TallRhs { const double *r1a = nullptr, *r2a = nullptr, *r1b = nullptr, *r2b = nullptr; };
 // Xt (nxp x mk, zeroed beforehand) = X^T for the m x nx block of the resident X (lda = npa)
 hipError_t tall_transpose(const double* X, int64_t ldx, int m, int nx, double* Xt, int64_t ldt, hipStream_t st);
 // W_s and E_x from the iterate (with_scales), and t for nrhs (0|1|2) right-hand sides (r1a, r2a), (r1b, r2b): r1 n-sized, r2 m-sized
