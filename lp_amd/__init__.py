@@ -99,6 +99,11 @@ def _p(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _ptrs(arrays):
+    """The C array of pointers to the (contiguous float64) arrays."""
+    return (C.POINTER(C.c_double) * len(arrays))(*[_p(a) for a in arrays])
+
+
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
@@ -377,29 +382,31 @@ class Context:
         self.m, self.n = m, nl
         return self
 
+    def _upload_members(self, entry, head, bs, cs, c0s, m, n, nc, matrix, tail=()):
+        """What the upload_lockstep* methods share: every member's b of m and c of nc entries checked, the pointer arrays and
+        c0 made, `entry(ctx, K, *head, bs, cs, c0, *tail)` called and the resident batch (solutions of n entries) recorded."""
+        K = len(bs)
+        if K < 1 or len(cs) != K or any(b.shape != (m,) for b in bs) or any(c.shape != (nc,) for c in cs):
+            raise IncompatibleInputDimensions()
+        c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
+        _raise_for(getattr(_capi.lib(), entry)(self._h, K, *head, _ptrs(bs), _ptrs(cs), c0, *tail))
+        self._lock = (K, m, n, matrix, bs, cs)      # keep the host arrays alive only for the duration of the call chain
+        self.m, self.n = m, n
+        return self
+
     def upload_lockstep(self, As, bs, cs, c0s=None, n_slack=0):
         """`len(As)` LPs of one shape resident at once (lpipm_upload_lockstep); solve with solve_lockstep.
         n_slack > 0 (lpipm_upload_lockstep_slack): the last n_slack columns of every member are the slack block [I; 0] of its
         `ub` rows, verified and then neither stored nor multiplied -- every member bit-identical to upload_arrays(..., n_slack)
         + solve_raw of that member alone."""
         As = [_f64(A) for A in As]; bs = [_f64(b) for b in bs]; cs = [_f64(c) for c in cs]
-        K = len(As)
-        if K < 1 or len(bs) != K or len(cs) != K:
+        if len(As) < 1 or len(bs) != len(As) or len(cs) != len(As):
             raise IncompatibleInputDimensions()
         m, n = As[0].shape
-        for A, b, c in zip(As, bs, cs):
-            if A.shape != (m, n) or b.shape != (m,) or c.shape != (n,):
-                raise IncompatibleInputDimensions()
-        dp = C.POINTER(C.c_double)
-        arr = lambda lst: (dp * K)(*[_p(a) for a in lst])
-        c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
-        if n_slack:
-            _raise_for(_capi.lib().lpipm_upload_lockstep_slack(self._h, K, m, n, arr(As), arr(bs), arr(cs), c0, int(n_slack)))
-        else:
-            _raise_for(_capi.lib().lpipm_upload_lockstep(self._h, K, m, n, arr(As), arr(bs), arr(cs), c0))
-        self._lock = (K, m, n, As, bs, cs)      # keep the host arrays alive only for the duration of the call chain
-        self.m, self.n = m, n
-        return self
+        if any(A.shape != (m, n) for A in As):
+            raise IncompatibleInputDimensions()
+        entry, tail = ("lpipm_upload_lockstep_slack", (int(n_slack),)) if n_slack else ("lpipm_upload_lockstep", ())
+        return self._upload_members(entry, (m, n, _ptrs(As)), bs, cs, c0s, m, n, n, As, tail)
 
     def upload_lockstep_shared(self, A, bs, cs, c0s=None, n_slack=0):
         """`len(bs)` LPs that share ONE constraint matrix A, resident at once (lpipm_upload_lockstep_shared): member i is
@@ -408,24 +415,11 @@ class Context:
         n_slack > 0 (lpipm_upload_lockstep_shared_slack): the last n_slack columns of A are its slack block [I; 0], verified
         and then neither stored nor multiplied, as upload_arrays(..., n_slack) does for one LP."""
         A = _f64(A); bs = [_f64(b) for b in bs]; cs = [_f64(c) for c in cs]
-        K = len(bs)
-        if A.ndim != 2 or K < 1 or len(cs) != K or (c0s is not None and len(c0s) != K):
+        if A.ndim != 2 or len(bs) < 1 or len(cs) != len(bs) or (c0s is not None and len(c0s) != len(bs)):
             raise IncompatibleInputDimensions()
         m, n = A.shape
-        for b, c in zip(bs, cs):
-            if b.shape != (m,) or c.shape != (n,):
-                raise IncompatibleInputDimensions()
-        dp = C.POINTER(C.c_double)
-        arr = lambda lst: (dp * K)(*[_p(a) for a in lst])
-        c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
-        if n_slack:
-            _raise_for(_capi.lib().lpipm_upload_lockstep_shared_slack(self._h, K, m, n, _p(A), n, arr(bs), arr(cs), c0,
-                                                                      int(n_slack)))
-        else:
-            _raise_for(_capi.lib().lpipm_upload_lockstep_shared(self._h, K, m, n, _p(A), n, arr(bs), arr(cs), c0))
-        self._lock = (K, m, n, A, bs, cs)
-        self.m, self.n = m, n
-        return self
+        entry, tail = ("lpipm_upload_lockstep_shared_slack", (int(n_slack),)) if n_slack else ("lpipm_upload_lockstep_shared", ())
+        return self._upload_members(entry, (m, n, _p(A), n), bs, cs, c0s, m, n, n, A, tail)
 
     def upload_lockstep_shared_ub_eq(self, A_ub, A_eq, bs, cs, c0s=None):
         """`len(bs)` inequality-form LPs over ONE pair of blocks (lpipm_upload_lockstep_shared_ub_eq): member i is
@@ -433,8 +427,7 @@ class Context:
         the device once, as they are; the slack block is never formed.  solve_lockstep then returns x with n + m_ub entries,
         slack values last -- every member bit-identical to Context.upload(Problem...ub().eq().build()) + solve_raw."""
         bs = [_f64(b) for b in bs]; cs = [_f64(c) for c in cs]
-        K = len(bs)
-        if K < 1 or len(cs) != K or (c0s is not None and len(c0s) != K) or cs[0].ndim != 1:
+        if len(bs) < 1 or len(cs) != len(bs) or (c0s is not None and len(c0s) != len(bs)) or cs[0].ndim != 1:
             raise IncompatibleInputDimensions()
         n = cs[0].shape[0]
         A_ub = _f64(A_ub) if A_ub is not None else np.zeros((0, n))
@@ -442,17 +435,8 @@ class Context:
         if A_ub.ndim != 2 or A_eq.ndim != 2 or A_ub.shape[1] != n or A_eq.shape[1] != n:
             raise IncompatibleInputDimensions()
         m_ub, m_eq = A_ub.shape[0], A_eq.shape[0]
-        for b, c in zip(bs, cs):
-            if b.shape != (m_ub + m_eq,) or c.shape != (n,):
-                raise IncompatibleInputDimensions()
-        dp = C.POINTER(C.c_double)
-        arr = lambda lst: (dp * K)(*[_p(a) for a in lst])
-        c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
-        _raise_for(_capi.lib().lpipm_upload_lockstep_shared_ub_eq(self._h, K, n, m_ub, _p(A_ub) if m_ub else None, n, m_eq,
-                                                                  _p(A_eq) if m_eq else None, n, arr(bs), arr(cs), c0))
-        self._lock = (K, m_ub + m_eq, n + m_ub, None, bs, cs)
-        self.m, self.n = m_ub + m_eq, n + m_ub
-        return self
+        head = (n, m_ub, _p(A_ub) if m_ub else None, n, m_eq, _p(A_eq) if m_eq else None, n)
+        return self._upload_members("lpipm_upload_lockstep_shared_ub_eq", head, bs, cs, c0s, m_ub + m_eq, n + m_ub, n, None)
 
     def upload_lockstep_shared_ub_tall(self, A_ub, bs, cs, c0s=None):
         """`len(bs)` tall inequality-form LPs over ONE matrix (lpipm_upload_lockstep_shared_ub_tall): member i is
@@ -460,25 +444,15 @@ class Context:
         once; every member factors its own n x n reduced system.  solve_lockstep returns x with n + m_ub entries, slack values
         last -- every member bit-identical to Context.upload(Problem...ub().build(), tall=True) + solve_raw."""
         bs = [_f64(b) for b in bs]; cs = [_f64(c) for c in cs]
-        K = len(bs)
-        if K < 1 or len(cs) != K or (c0s is not None and len(c0s) != K) or cs[0].ndim != 1:
+        if len(bs) < 1 or len(cs) != len(bs) or (c0s is not None and len(c0s) != len(bs)) or cs[0].ndim != 1:
             raise IncompatibleInputDimensions()
         n = cs[0].shape[0]
         A_ub = _f64(A_ub)
         if A_ub.ndim != 2 or A_ub.shape[1] != n:
             raise IncompatibleInputDimensions()
-        m_ub = A_ub.shape[0]
-        for b, c in zip(bs, cs):
-            if b.shape != (m_ub,) or c.shape != (n,):
-                raise IncompatibleInputDimensions()
-        dp = C.POINTER(C.c_double)
-        arr = lambda lst: (dp * K)(*[_p(a) for a in lst])
-        c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
-        _raise_for(_capi.lib().lpipm_upload_lockstep_shared_ub_tall(self._h, K, n, m_ub, _p(A_ub) if m_ub else None, n,
-                                                                    arr(bs), arr(cs), c0))
-        self._lock = (K, m_ub, n + m_ub, None, bs, cs)      # (the lockstep form: b[i] of m_ub, c[i] of the n structural costs)
-        self.m, self.n = m_ub, n + m_ub
-        return self
+        m_ub = A_ub.shape[0]          # (the lockstep form: b[i] of m_ub, c[i] of the n structural costs)
+        head = (n, m_ub, _p(A_ub) if m_ub else None, n)
+        return self._upload_members("lpipm_upload_lockstep_shared_ub_tall", head, bs, cs, c0s, m_ub, n + m_ub, n, None)
 
     def resident_bytes(self) -> int:
         """Device bytes held for the resident problem(s): arenas + shared matrix + factor workspace."""
@@ -524,8 +498,7 @@ class Context:
         for A, b, c in zip(As, bs, cs):
             if A.ndim != 2 or b.shape != (A.shape[0],) or c.shape != (A.shape[1],):
                 raise IncompatibleInputDimensions()
-        dp = C.POINTER(C.c_double)
-        arr = lambda lst: (dp * K)(*[_p(a) for a in lst])
+        arr = _ptrs
         m = (C.c_uint64 * K)(*[A.shape[0] for A in As]); n = (C.c_uint64 * K)(*[A.shape[1] for A in As])
         c0 = (C.c_double * K)(*[float(p[3]) if len(p) > 3 else 0.0 for p in problems])
         fun = (C.c_double * K)(); its = (C.c_uint64 * K)(); st = (C.c_int32 * K)()
@@ -551,8 +524,7 @@ class Context:
         for A, b, c in zip(As, bs, cs):
             if A.ndim != 2 or b.shape != (A.shape[0],) or c.shape != (A.shape[1],):
                 raise IncompatibleInputDimensions()
-        dp = C.POINTER(C.c_double)
-        arr = lambda lst: (dp * K)(*[_p(a) for a in lst])
+        arr = _ptrs
         xs = [np.full(A.shape[1], np.nan) for A in As]
         m = (C.c_uint64 * K)(*[A.shape[0] for A in As]); n = (C.c_uint64 * K)(*[A.shape[1] for A in As])
         c0 = (C.c_double * K)(*[float(p[3]) if len(p) > 3 else 0.0 for p in problems])

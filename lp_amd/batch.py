@@ -94,21 +94,7 @@ def solve_shared_matrix(A, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, 
     once, every pass over it serving the whole group).  Returns a list of dicts {status, x_slack, fun, iterations} in member
     order, as solve_batch_sharded does.  n_slack: the last n_slack columns of A are its slack block [I; 0], kept structural
     (lpipm_upload_lockstep_shared_slack)."""
-    import lp_amd
-    count = len(bs)
-    if len(cs) != count or (c0s is not None and len(c0s) != count):
-        raise lp_amd.IncompatibleInputDimensions()
-    if max_group < 1:
-        raise lp_amd.InvalidParameter("max_group must be >= 1")
-    ctx = ctx or lp_amd.default_context(0)
-    opts = opts or lp_amd.InteriorPoint.default().opts()
-    out = []
-    for k0 in range(0, count, max_group):
-        k1 = min(k0 + max_group, count)
-        ctx.upload_lockstep_shared(A, bs[k0:k1], cs[k0:k1], None if c0s is None else c0s[k0:k1], n_slack=n_slack)
-        for st, x, fun, it in ctx.solve_lockstep(opts):
-            out.append(dict(status=st, x_slack=x, fun=fun, iterations=it))
-    return out
+    return _groups(lambda cx, b, c, c0: cx.upload_lockstep_shared(A, b, c, c0, n_slack=n_slack), bs, cs, c0s, opts, ctx, max_group)
 
 
 def solve_shared_ub_eq(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_group=32):
@@ -116,21 +102,7 @@ def solve_shared_ub_eq(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_gr
     member i = (bs[i] = [b_ub_i; b_eq_i], cs[i] = the n structural costs, c0s[i]); either block may be None.  Lockstep groups
     of at most `max_group` on one context through lpipm_upload_lockstep_shared_ub_eq: the blocks resident once, the slack
     block never formed on the host or the device.  Returns what solve_shared_matrix returns; x_slack has n + m_ub entries."""
-    import lp_amd
-    count = len(bs)
-    if len(cs) != count or (c0s is not None and len(c0s) != count):
-        raise lp_amd.IncompatibleInputDimensions()
-    if max_group < 1:
-        raise lp_amd.InvalidParameter("max_group must be >= 1")
-    ctx = ctx or lp_amd.default_context(0)
-    opts = opts or lp_amd.InteriorPoint.default().opts()
-    out = []
-    for k0 in range(0, count, max_group):
-        k1 = min(k0 + max_group, count)
-        ctx.upload_lockstep_shared_ub_eq(A_ub, A_eq, bs[k0:k1], cs[k0:k1], None if c0s is None else c0s[k0:k1])
-        for st, x, fun, it in ctx.solve_lockstep(opts):
-            out.append(dict(status=st, x_slack=x, fun=fun, iterations=it))
-    return out
+    return _groups(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_eq(A_ub, A_eq, b, c, c0), bs, cs, c0s, opts, ctx, max_group)
 
 
 def solve_shared_ub_tall(A_ub, bs, cs, c0s=None, opts=None, ctx=None, max_group=32):
@@ -138,21 +110,7 @@ def solve_shared_ub_tall(A_ub, bs, cs, c0s=None, opts=None, ctx=None, max_group=
     more rows than columns): member i = (bs[i], cs[i] = the n structural costs, c0s[i]).  Lockstep groups of at most
     `max_group` on one context through lpipm_upload_lockstep_shared_ub_tall: A_ub and its transpose resident once, every member
     factoring its own n x n reduced system.  Returns what solve_shared_ub_eq returns; x_slack has n + m_ub entries."""
-    import lp_amd
-    count = len(bs)
-    if len(cs) != count or (c0s is not None and len(c0s) != count):
-        raise lp_amd.IncompatibleInputDimensions()
-    if max_group < 1:
-        raise lp_amd.InvalidParameter("max_group must be >= 1")
-    ctx = ctx or lp_amd.default_context(0)
-    opts = opts or lp_amd.InteriorPoint.default().opts()
-    out = []
-    for k0 in range(0, count, max_group):
-        k1 = min(k0 + max_group, count)
-        ctx.upload_lockstep_shared_ub_tall(A_ub, bs[k0:k1], cs[k0:k1], None if c0s is None else c0s[k0:k1])
-        for st, x, fun, it in ctx.solve_lockstep(opts):
-            out.append(dict(status=st, x_slack=x, fun=fun, iterations=it))
-    return out
+    return _groups(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_tall(A_ub, b, c, c0), bs, cs, c0s, opts, ctx, max_group)
 
 
 def sweep_chunks(count: int, max_group: int):
@@ -169,7 +127,9 @@ def sweep_chunks(count: int, max_group: int):
     return g, chunks
 
 
-def _sweep(upload, bs, cs, c0s, opts, ctx, max_group):
+def _drive(chunks, upload, resident, bs, cs, c0s, opts, ctx, max_group):
+    """Member groups through lockstep batches on one context: `chunks(count, max_group)` gives the member indices of each group;
+    group 0 is uploaded, a later one replaces the vectors of the resident batch (resident) or is uploaded in its turn."""
     import lp_amd
     count = len(bs)
     if len(cs) != count or (c0s is not None and len(c0s) != count):
@@ -179,16 +139,27 @@ def _sweep(upload, bs, cs, c0s, opts, ctx, max_group):
     ctx = ctx or lp_amd.default_context(0)
     opts = opts or lp_amd.InteriorPoint.default().opts()
     out = []
-    for q, idx in enumerate(sweep_chunks(count, max_group)[1]):
+    for q, idx in enumerate(chunks(count, max_group)):
         pick = lambda seq: None if seq is None else [seq[i] for i in idx]
-        if q == 0:
+        if q == 0 or not resident:
             upload(ctx, pick(bs), pick(cs), pick(c0s))
         else:
             ctx.update_lockstep_vectors(pick(bs), pick(cs), pick(c0s))
         res = ctx.solve_lockstep(opts)
-        for st, x, fun, it in res[:count - len(out)]:          # (the padding's results are dropped)
+        for st, x, fun, it in res[:count - len(out)]:          # (a sweep's padding: its results are dropped)
             out.append(dict(status=st, x_slack=x, fun=fun, iterations=it))
     return out
+
+
+def _groups(upload, bs, cs, c0s, opts, ctx, max_group):
+    """Groups of at most max_group members in order, each uploaded."""
+    return _drive(lambda count, g: [range(k, min(k + g, count)) for k in range(0, count, g)], upload, False,
+                  bs, cs, c0s, opts, ctx, max_group)
+
+
+def _sweep(upload, bs, cs, c0s, opts, ctx, max_group):
+    """The equal chunks of sweep_chunks: one upload, then new vectors for the resident batch."""
+    return _drive(lambda count, g: sweep_chunks(count, g)[1], upload, True, bs, cs, c0s, opts, ctx, max_group)
 
 
 def sweep_shared_matrix(A, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, n_slack=0):

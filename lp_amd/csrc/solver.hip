@@ -18,6 +18,7 @@
 #include <cmath>
 #include <vector>
 #include <string>
+#include <optional>
 #include <thread>
 #include <atomic>
 #include <chrono>
@@ -62,12 +63,21 @@ struct StreamRes {
     bool spin_status = false;          // this solve waits for an iteration by watching the records' sequence words (wait_status)
 };
 
+// The padded geometry of a resident problem: what the two allocations and their layouts are a function of.  Two uploads
+// with equal geometries share them.  nxp, mk: tall only (zero otherwise); nsplit and nblk follow from the others.
+struct Geometry {
+    int mp = 0, np = 0, npa = 0, nxp = 0, mk = 0, B = 0, nsplit = 0, nblk = 0;
+    bool shared = false, keep = false, tall = false;
+    bool operator==(const Geometry&) const = default;
+};
+
 // The resident problem: geometry, device pointers and launch arguments.  Every pointer points into an allocation of the
 // context that uploaded it (arena, a_shared, the factor plan; the tile and unit lists belong to `adat`, made by
 // adat_lists_create and freed by adat_lists_destroy), so a plain copy of this struct shares the device state and owns
 // nothing: that is what a half-batch view holds (make_view).
 struct Problem {
     bool has_problem = false;
+    Geometry geo;                // what the fields below and the allocations were laid out for (set_geometry)
     uint64_t m = 0, n = 0;
     int mp = 0, np = 0, nblk = 1, nsplit = 1;
     int ns = 0, nx = 0, npa = 0;   // slack columns (not stored), structural columns, their padded count = lda of A
@@ -92,7 +102,7 @@ struct Problem {
     double* M1 = nullptr;
     const FactorPlan* factor1 = nullptr; // lpipm_ctx::plan1 of the uploading context
     int32_t* info1 = nullptr;
-    // A shared-matrix batch keeps ONE such set for all its members, behind A in a_shared (layout_shared_factor), built once
+    // A shared-matrix batch keeps ONE such set for all its members, behind A in a_shared (layout_shared), built once
     // from `ones` -- iteration 1's dinv, exact 1.0 over the np columns -- ahead of the first solve (ensure_shared_factor).
     bool shared_factor = false;
     double* ones = nullptr;
@@ -463,136 +473,58 @@ static int merge_edge_for(int) {
     return 32;
 }
 
-// Per-LP device state: one pass over a measuring arena sizes it, a second pass over the real one places it.
-// Every LP of a lockstep batch gets the same layout, `bstride` bytes after the previous LP's.
-static void bind_status_pinned(lpipm_ctx* c, bool allow);
-// In: p's geometry (mp, np, npa, nsplit, B, shared_a), the A.D.A^T plan, whether the context refines its solves and whether
-// the first iteration's factor is kept (`keep`).  Out: p's device pointers and `plan` (and `plan1`), the factor plans they
-// refer to.
-// The kept factor is the last block of an LP's arena, on 4096-byte bounds: mp x mp doubles of M, two s x s inverses per
-// diagonal super-block of width s, and one page for the pivot-failure word -- first_factor_bytes(mp) in all, a function of mp
-// alone.  Its plan works in the first plan's merge workspace and gemv_t slabs: the two are never in use at the same time.
-static size_t first_factor_bytes(int mp, int super_w) {
-    size_t bytes = (size_t)mp * mp * sizeof(double) + 4096;
-    for (int r0 = 0; r0 < mp; r0 += super_w) { const size_t s = (size_t)(mp - r0 < super_w ? mp - r0 : super_w); bytes += 2 * s * s * sizeof(double); }
-    return bytes;
-}
-// The arena of a tall LP (Problem::tall): the vectors of the dense layout, X and its transpose, the nxp x nxp matrix K with
-// its factor plan, and the work vectors of the reduced solve.  Nothing grows as m^2: no M, M0 or kept first factor, the slabs
-// of A^T.v are npa wide and the chunk slabs of A.x are those of the npa stored columns.  A member of a shared batch
-// (p.shared_a) has the same arena without X and Xt: the batch's one copy of each is in a_shared (upload_impl).
-static int layout_tall(Problem& p, FactorPlan& plan, FactorPlan& plan1, const AdatPlan& ap, Arena& ar, bool build, hipStream_t st) {
-    VecArgs& v = p.va;
-    TallArgs& t = p.tv;
-    const size_t mp = (size_t)p.mp, np = (size_t)p.np, nxp = (size_t)t.nxp;
-    p.A = p.shared_a ? nullptr : ar.take<double>(mp * p.npa);
-    p.Xt = p.shared_a ? nullptr : ar.take<double>(nxp * (size_t)t.mk);
-    v.b = ar.take<double>(mp); v.c = ar.take<double>(np);
-    v.x = ar.take<double>(np); v.y = ar.take<double>(mp); v.z = ar.take<double>(np);
-    v.dinv = ar.take<double>(np); v.xs = ar.take<double>(np); v.r1 = ar.take<double>(np); v.rD = ar.take<double>(np);
-    v.p = ar.take<double>(np); v.u = ar.take<double>(np); v.dx = ar.take<double>(np); v.dz = ar.take<double>(np);
-    v.dxdz = ar.take<double>(np);
-    v.rP = ar.take<double>(mp); v.rP2 = ar.take<double>(mp); v.q = ar.take<double>(mp); v.dy = ar.take<double>(mp);
-    v.Ax = ar.take<double>(mp * (size_t)gemv_dual_chunks(p.npa));
-    v.W = ar.take<double>(2 * np); v.R = ar.take<double>(2 * mp);
-    p.Y = ar.take<double>(2 * nxp);
-    p.ATpart = ar.take<double>((size_t)p.nsplit * 2 * p.npa);
-    v.ATpart = p.ATpart;
-    v.S = ar.take<double>(64); v.red = ar.take<double>((size_t)RED_SLOTS * RED_STRIDE);
-    v.status = ar.take<StatusRec>(1);
-    v.potrf_info = ar.take<int32_t>(1); v.flags = ar.take<int>(1); v.done = ar.take<int>(1);
-    v.skip_refine = ar.take<int>(1);
-    t.Ws = ar.take<double>((size_t)t.mk); t.Ex = ar.take<double>(nxp);
-    t.T = ar.take<double>(2 * mp); t.G = ar.take<double>(2 * nxp); t.Us = ar.take<double>(2 * mp);
-    p.M = ar.take<double>(nxp * nxp);
-    LP_HIP(factor_plan_create(plan, p.M, t.nxp, t.nxp, ar, build, st, super_for(t.nxp), merge_edge_for(1)));
-    p.factor = &plan;
-    p.M0 = p.R0 = p.Rho = p.symv_ws = nullptr;
-    p.tau = ar.take<double>(1);
-    p.gs = ar.take<double>(8);
-    p.xout = ar.take<double>(np);
-    adat_take(p.adat, ap, ar);
-    p.keep = false; p.shared_factor = false;
-    p.M1 = nullptr; p.factor1 = nullptr; p.info1 = nullptr; p.ones = nullptr;
-    factor_plan_destroy(plan1);
-    return LPIPM_OK;
-}
-static int layout_problem(Problem& p, FactorPlan& plan, FactorPlan& plan1, const AdatPlan& ap, int refine, bool keep, Arena& ar,
-                          bool build, hipStream_t st) {
-    VecArgs& v = p.va;
-    const size_t mp = (size_t)p.mp, np = (size_t)p.np;
-    if (p.tall) return layout_tall(p, plan, plan1, ap, ar, build, st);
-    p.A = p.shared_a ? nullptr : ar.take<double>(mp * p.npa);     // a shared A has its own allocation (upload_impl)
-    v.b = ar.take<double>(mp); v.c = ar.take<double>(np);
-    v.x = ar.take<double>(np); v.y = ar.take<double>(mp); v.z = ar.take<double>(np);
-    v.dinv = ar.take<double>(np); v.xs = ar.take<double>(np); v.r1 = ar.take<double>(np); v.rD = ar.take<double>(np);
-    v.p = ar.take<double>(np); v.u = ar.take<double>(np); v.dx = ar.take<double>(np); v.dz = ar.take<double>(np);
-    v.dxdz = ar.take<double>(np);
-    v.rP = ar.take<double>(mp); v.rP2 = ar.take<double>(mp); v.q = ar.take<double>(mp); v.dy = ar.take<double>(mp);
-    // chunk slabs of A.x: sized by the count the launches use (the STORED columns npa -- gemv_dual_chunks is not monotone:
-    // 256-column chunks below 4096 columns, 1024-column chunks from there on, so np's count can be the smaller one)
-    {
-        const int ch_a = gemv_dual_chunks(p.npa), ch_n = gemv_dual_chunks((int)np);
-        v.Ax = ar.take<double>(mp * (size_t)(ch_a > ch_n ? ch_a : ch_n));
+// Making a problem resident: request -> geometry -> the two allocations and their layouts -> copy-in.
+// What the caller asks to be resident: `count` LPs of one shape (count == 1: the ordinary upload); b, c, c0 one entry per LP.
+// The matrix comes one per member (A[i], lda), as the batch's one matrix (shared: A[0]), or as two blocks of
+// nx = n - n_slack columns (parts: m_ub rows of A_ub, then m - m_ub rows of A_eq; n_slack == m_ub, true by construction, and c
+// holds only the nx structural costs).  Parts of a single LP carry its b, split the same way (b is null); parts of a shared
+// batch are its one matrix and b[i] = [b_ub_i; b_eq_i] comes per member.
+struct UploadParts { uint64_t m_ub = 0; const double* A_ub = nullptr; uint64_t lda_ub = 0; const double* b_ub = nullptr;
+                     const double* A_eq = nullptr; uint64_t lda_eq = 0; const double* b_eq = nullptr; };
+struct Upload {
+    uint64_t count = 1, m = 0, n = 0;
+    uint64_t n_slack = 0;                // the structural hint of lpipm_upload_slack, for every member alike (verified by upload_impl)
+    const double* const* A = nullptr;
+    uint64_t lda = 0;
+    std::optional<UploadParts> parts;
+    const double *const *b = nullptr, *const *c = nullptr;
+    const double* c0 = nullptr;          // nullable: all zero
+    bool shared = false;                 // one matrix for all `count` LPs
+    bool tall = false;                   // parts with `ub` rows only: the tall inequality form, of the LP or of every member over one X
+    bool hint_verified = false;          // the caller has checked the hint on these very matrices (batch_impl): it is not repeated
+    bool keep_ok = true;                 // false: solved once (lpipm_solve_batch) or never through the kept factor (column split)
+};
+// Which requests are legal, and what the others get.  Every argument of a dense request is looked at before its shape; of a
+// request in parts the shape comes first (m == 0 is Unconstrained whatever the blocks are, linear_program.rs:134-136), ahead
+// of everything but a batch's count and vector arrays, and a batch's members are looked at last.
+static int check_upload(const lpipm_ctx* c, const Upload& u) {
+    const bool count_ok = u.count >= 1 && u.count <= 4096;
+    if (!u.parts) {
+        if (!c || !count_ok || !u.A || !u.b || !u.c || u.lda < u.n) return LPIPM_ERR_BAD_ARGUMENT;
+        for (uint64_t i = 0; i < u.count; ++i)
+            if (!u.c[i] || !u.b[i] || (!u.shared && !u.A[i])) return LPIPM_ERR_BAD_ARGUMENT;
+        if (u.shared && !u.A[0]) return LPIPM_ERR_BAD_ARGUMENT;
+        if (u.m == 0) return LPIPM_UNCONSTRAINED;  // linear_program.rs:134-136
+        if (u.n == 0 || u.n_slack > u.n || u.n_slack > u.m) return LPIPM_ERR_BAD_ARGUMENT;
+    } else {
+        const UploadParts& q = *u.parts;
+        const uint64_t nx = u.n - u.n_slack, m_eq = u.m - q.m_ub;
+        if (u.shared && (!count_ok || !u.b || !u.c)) return LPIPM_ERR_BAD_ARGUMENT;
+        if (u.m == 0) return LPIPM_UNCONSTRAINED;  // linear_program.rs:134-136
+        if ((!u.shared && !u.c[0]) || nx == 0) return LPIPM_ERR_BAD_ARGUMENT;
+        if (q.m_ub && (!q.A_ub || q.lda_ub < nx || (!u.shared && !q.b_ub))) return LPIPM_ERR_BAD_ARGUMENT;
+        if (m_eq && (!q.A_eq || q.lda_eq < nx || (!u.shared && !q.b_eq))) return LPIPM_ERR_BAD_ARGUMENT;
+        if (!c) return LPIPM_ERR_BAD_ARGUMENT;
+        if (u.tall && (c->world > 1 || c->refine > 0)) return LPIPM_ERR_UNSUPPORTED;   // a column-split context; the refined solves
+        for (uint64_t i = 0; i < u.count; ++i)
+            if (!u.c[i] || (u.b && !u.b[i])) return LPIPM_ERR_BAD_ARGUMENT;
     }
-    v.W = ar.take<double>(2 * np); v.R = ar.take<double>(2 * mp);
-    p.Y = ar.take<double>(2 * mp);
-    p.ATpart = ar.take<double>((size_t)p.nsplit * 2 * np);
-    v.ATpart = p.ATpart;
-    v.S = ar.take<double>(64); v.red = ar.take<double>((size_t)RED_SLOTS * RED_STRIDE);
-    v.status = ar.take<StatusRec>(1);
-    v.potrf_info = ar.take<int32_t>(1); v.flags = ar.take<int>(1); v.done = ar.take<int>(1);
-    v.skip_refine = ar.take<int>(1);
-    p.M = ar.take<double>(mp * mp);
-    LP_HIP(factor_plan_create(plan, p.M, p.mp, p.mp, ar, build, st, super_for(p.mp), merge_edge_for(p.B)));
-    p.factor = &plan;
-    p.M0 = p.R0 = p.Rho = p.symv_ws = nullptr;
-    if (refine > 0) {     // only the refined solves read the matrix itself
-        p.M0 = ar.take<double>(mp * mp);
-        p.R0 = ar.take<double>(2 * mp); p.Rho = ar.take<double>(2 * mp);
-        p.symv_ws = ar.take<double>(symv_slab_doubles(p.mp));
-    }
-    p.tau = ar.take<double>(mp);
-    p.gs = ar.take<double>(8);
-    p.xout = ar.take<double>(np);
-    adat_take(p.adat, ap, ar);
-    p.keep = keep;
-    p.shared_factor = keep && p.shared_a;      // one set for the batch, outside the arenas (layout_shared_factor)
-    p.M1 = nullptr; p.factor1 = nullptr; p.info1 = nullptr; p.ones = nullptr;
-    if (p.shared_factor) {}
-    else if (keep) {
-        ar.off = (size_t)round_up(ar.off, 4096);
-        const size_t begin = ar.off;
-        p.M1 = ar.take<double>(mp * mp);
-        LP_HIP(factor_plan_create(plan1, p.M1, p.mp, p.mp, ar, build, st, super_for(p.mp), merge_edge_for(p.B), &plan));
-        p.factor1 = &plan1;
-        p.info1 = ar.take<int32_t>(1);
-        ar.off = (size_t)round_up(ar.off, 4096);
-        if (ar.off - begin != first_factor_bytes(p.mp, super_for(p.mp))) return LPIPM_ERR_BAD_ARGUMENT;   // (the documented size)
-    } else factor_plan_destroy(plan1);
-    return LPIPM_OK;
+    return u.m > (1u << 20) || u.n > (1u << 24) ? LPIPM_ERR_BAD_ARGUMENT : LPIPM_OK;
 }
-// The one kept first factor of a shared-matrix batch (p.shared_factor), from `sh`: the batch's shared allocation behind A.
-// The same block as an arena's -- first_factor_bytes(mp) on 4096-byte bounds -- then the vector of ones, np doubles rounded
-// up to 4096 bytes.  The plan's inverses are the batch's; its merge workspace and gemv_t slabs stay the first plan's, per member.
-static int layout_shared_factor(Problem& p, const FactorPlan& plan, FactorPlan& plan1, Arena& sh, bool build, hipStream_t st) {
-    sh.off = (size_t)round_up(sh.off, 4096);
-    const size_t begin = sh.off;
-    p.M1 = sh.take<double>((size_t)p.mp * p.mp);
-    LP_HIP(factor_plan_create(plan1, p.M1, p.mp, p.mp, sh, build, st, super_for(p.mp), merge_edge_for(p.B), &plan));
-    p.factor1 = &plan1;
-    p.info1 = sh.take<int32_t>(1);
-    sh.off = (size_t)round_up(sh.off, 4096);
-    if (sh.off - begin != first_factor_bytes(p.mp, super_for(p.mp))) return LPIPM_ERR_BAD_ARGUMENT;   // (the documented size)
-    p.ones = sh.take<double>((size_t)p.np);
-    sh.off = (size_t)round_up(sh.off, 4096);
-    return LPIPM_OK;
-}
-
 // Whether the last n_slack columns of every one of the `count` m x n matrices are [I; 0] (n_slack == n: not a hint).
-static bool slack_hint_holds(int count, uint64_t m, uint64_t n, const double* const* A, uint64_t lda, uint64_t n_slack) {
+static bool slack_hint_holds(uint64_t count, uint64_t m, uint64_t n, const double* const* A, uint64_t lda, uint64_t n_slack) {
     if (n_slack == 0 || n_slack == n) return false;
-    for (int k = 0; k < count; ++k)
+    for (uint64_t k = 0; k < count; ++k)
         for (uint64_t i = 0; i < m; ++i) {
             const double* row = A[k] + i * lda + (n - n_slack);
             for (uint64_t j = 0; j < n_slack; ++j)
@@ -601,6 +533,162 @@ static bool slack_hint_holds(int count, uint64_t m, uint64_t n, const double* co
     return true;
 }
 
+// The geometry of a request whose hint `n_slack` holds, on a context with these settings: a value, no device needed.
+static Geometry geometry_of(const Upload& u, uint64_t n_slack, bool first_cache, int refine) {
+    Geometry g;
+    g.mp = (int)round_up(u.m, NB); g.np = (int)round_up(u.n, BK); g.npa = (int)round_up(u.n - n_slack, BK);
+    if (u.tall) { g.nxp = (int)round_up(g.npa, NB); g.mk = (int)round_up(u.m, BK); }   // the order of K, the contraction of its build
+    g.B = (int)u.count; g.nsplit = g.mp / GEMVT_ROWS;
+    g.nblk = ((g.mp > g.np ? g.mp : g.np) + 255) / 256;      // (of the larger of m and n: 256 is a multiple of both paddings)
+    if (g.nblk > RED_STRIDE) g.nblk = RED_STRIDE;
+    g.shared = u.shared; g.tall = u.tall;
+    g.keep = u.keep_ok && first_cache && refine <= 0 && !u.tall;   // (tall: the first factor is not kept)
+    return g;
+}
+// The geometry into the structs the layouts and the launches read.
+static void set_geometry(Problem& p, const Geometry& g) {
+    p.geo = g;
+    p.mp = g.mp; p.np = g.np; p.npa = g.npa; p.B = g.B; p.nsplit = g.nsplit; p.nblk = g.nblk; p.shared_a = g.shared; p.tall = g.tall;
+    p.tv = TallArgs{};
+    if (g.tall) { p.tv.npa = g.npa; p.tv.nxp = g.nxp; p.tv.mk = g.mk; }     // (tv.nx: the padded geometry may be shared by several nx)
+    VecArgs& v = p.va;
+    v.np = g.np; v.mp = g.mp; v.nblk = g.nblk; v.nsplit = g.nsplit; v.bcount = g.B; v.bfirst = 0; v.refine_below = refine_below();
+}
+// The plan of the launch that builds the normal matrix: A.D.A^T, or, tall, K from Xt -- nxp rows, a contraction over the mk
+// padded rows of X.  A tall batch: every member's K must have the bits the single LP's has.  The units kernel gives them
+// whatever the count; the round-2 kernel (which a single LP of a few tiles with several chunks takes) only with the single
+// LP's own workgroup count once the contraction is longer than 4096 (round2_unit): the batch then runs that very plan.
+static AdatPlan adat_plan_of(const Geometry& g, int num_cu, int world, int units_env) {
+    if (!g.tall) return plan_adat(g.mp, g.npa, g.B, num_cu, world, units_env);
+    const AdatPlan single = plan_adat(g.nxp, g.mk, 1, num_cu, 1, units_env);
+    return g.shared && single.units ? plan_adat(g.nxp, g.mk, g.B, num_cu, 1, units_env) : single;
+}
+
+// Device state is laid out by functions that take p's geometry and an Arena: one pass over a measuring arena sizes an
+// allocation, a second pass over the real one places it.  Out: p's device pointers and the factor plans they refer to.
+static void bind_status_pinned(lpipm_ctx* c, bool allow);
+// The vectors and status words of one LP, dense or tall.
+static void layout_vectors(Problem& p, Arena& ar) {
+    VecArgs& v = p.va;
+    const size_t mp = (size_t)p.mp, np = (size_t)p.np;
+    v.b = ar.take<double>(mp); v.c = ar.take<double>(np);
+    v.x = ar.take<double>(np); v.y = ar.take<double>(mp); v.z = ar.take<double>(np);
+    v.dinv = ar.take<double>(np); v.xs = ar.take<double>(np); v.r1 = ar.take<double>(np); v.rD = ar.take<double>(np);
+    v.p = ar.take<double>(np); v.u = ar.take<double>(np); v.dx = ar.take<double>(np); v.dz = ar.take<double>(np);
+    v.dxdz = ar.take<double>(np);
+    v.rP = ar.take<double>(mp); v.rP2 = ar.take<double>(mp); v.q = ar.take<double>(mp); v.dy = ar.take<double>(mp);
+    // chunk slabs of A.x: sized by the count the launches use (the STORED columns npa -- gemv_dual_chunks is not monotone:
+    // 256-column chunks below 4096 columns, 1024-column chunks from there on, so np's count can be the smaller one)
+    // (tall: those of the npa stored columns)
+    const int ch_a = gemv_dual_chunks(p.npa), ch_n = gemv_dual_chunks((int)np);
+    v.Ax = ar.take<double>(mp * (size_t)(p.tall || ch_a > ch_n ? ch_a : ch_n));
+    v.W = ar.take<double>(2 * np); v.R = ar.take<double>(2 * mp);
+    p.Y = ar.take<double>(2 * (p.tall ? (size_t)p.tv.nxp : mp));
+    p.ATpart = ar.take<double>((size_t)p.nsplit * 2 * (p.tall ? (size_t)p.npa : np));   // (tall: the slabs of A^T.v are npa wide)
+    v.ATpart = p.ATpart;
+    v.S = ar.take<double>(64); v.red = ar.take<double>((size_t)RED_SLOTS * RED_STRIDE);
+    v.status = ar.take<StatusRec>(1); v.potrf_info = ar.take<int32_t>(1);
+    v.flags = ar.take<int>(1); v.done = ar.take<int>(1); v.skip_refine = ar.take<int>(1);
+}
+// The kept first factor, on 4096-byte bounds: mp x mp doubles of M, two s x s inverses per diagonal super-block of width s,
+// and one page for the pivot-failure word -- first_factor_bytes(mp) in all, a function of mp alone.  Its plan works in the
+// first plan's merge workspace and gemv_t slabs: the two are never in use at the same time.  The last block of an LP's arena,
+// or, once for a shared-matrix batch, of the shared allocation (the plan's inverses are then the batch's; workspace and
+// slabs stay the first plan's, per member).
+static size_t first_factor_bytes(int mp, int super_w) {
+    size_t bytes = (size_t)mp * mp * sizeof(double) + 4096;
+    for (int r0 = 0; r0 < mp; r0 += super_w) { const size_t s = (size_t)(mp - r0 < super_w ? mp - r0 : super_w); bytes += 2 * s * s * sizeof(double); }
+    return bytes;
+}
+static int layout_first_factor(Problem& p, const FactorPlan& plan, FactorPlan& plan1, Arena& ar, bool build, hipStream_t st) {
+    ar.off = (size_t)round_up(ar.off, 4096);
+    const size_t begin = ar.off;
+    p.M1 = ar.take<double>((size_t)p.mp * p.mp);
+    LP_HIP(factor_plan_create(plan1, p.M1, p.mp, p.mp, ar, build, st, super_for(p.mp), merge_edge_for(p.B), &plan));
+    p.factor1 = &plan1; p.info1 = ar.take<int32_t>(1);
+    ar.off = (size_t)round_up(ar.off, 4096);
+    if (ar.off - begin != first_factor_bytes(p.mp, super_for(p.mp))) return LPIPM_ERR_BAD_ARGUMENT;   // (the documented size)
+    return LPIPM_OK;
+}
+// The arena of one LP; every LP of a lockstep batch gets the same layout, `bstride` bytes after the previous LP's.
+// refine: whether the context refines its solves.  Tall (Problem::tall): the vectors of the dense layout, X and its transpose, the nxp x nxp matrix K with its factor plan, and
+// the work vectors of the reduced solve.  Nothing grows as m^2: no M, M0 or kept first factor.
+// A member of a shared batch (p.shared_a) has the same arena without A (tall: X and Xt): layout_shared.
+static int layout_problem(Problem& p, FactorPlan& plan, FactorPlan& plan1, const AdatPlan& ap, int refine, Arena& ar,
+                          bool build, hipStream_t st) {
+    TallArgs& t = p.tv;
+    const size_t mp = (size_t)p.mp, np = (size_t)p.np, nxp = (size_t)t.nxp;
+    p.A = p.shared_a ? nullptr : ar.take<double>(mp * p.npa);
+    p.Xt = p.shared_a || !p.tall ? nullptr : ar.take<double>(nxp * (size_t)t.mk);
+    layout_vectors(p, ar);
+    if (p.tall) {
+        t.Ws = ar.take<double>((size_t)t.mk); t.Ex = ar.take<double>(nxp);
+        t.T = ar.take<double>(2 * mp); t.G = ar.take<double>(2 * nxp); t.Us = ar.take<double>(2 * mp);
+        p.M = ar.take<double>(nxp * nxp);
+        LP_HIP(factor_plan_create(plan, p.M, t.nxp, t.nxp, ar, build, st, super_for(t.nxp), merge_edge_for(1)));
+    } else {
+        p.M = ar.take<double>(mp * mp);
+        LP_HIP(factor_plan_create(plan, p.M, p.mp, p.mp, ar, build, st, super_for(p.mp), merge_edge_for(p.B)));
+    }
+    p.factor = &plan;
+    p.M0 = p.R0 = p.Rho = p.symv_ws = nullptr;
+    if (refine > 0 && !p.tall) {     // only the refined solves read the matrix itself
+        p.M0 = ar.take<double>(mp * mp); p.R0 = ar.take<double>(2 * mp); p.Rho = ar.take<double>(2 * mp);
+        p.symv_ws = ar.take<double>(symv_slab_doubles(p.mp));
+    }
+    p.tau = ar.take<double>(p.tall ? 1 : mp); p.gs = ar.take<double>(8); p.xout = ar.take<double>(np);
+    adat_take(p.adat, ap, ar);
+    p.keep = p.geo.keep;
+    p.shared_factor = p.keep && p.shared_a;      // one set for the batch, outside the arenas (layout_shared)
+    p.M1 = nullptr; p.factor1 = nullptr; p.info1 = nullptr; p.ones = nullptr;
+    if (!p.keep) factor_plan_destroy(plan1);
+    else if (!p.shared_factor) LP_TRY(layout_first_factor(p, plan, plan1, ar, build, st));
+    return LPIPM_OK;
+}
+// The shared allocation of a shared-matrix batch: the one A, mp x npa like an arena's, zero padding (tall: behind X its transpose,
+// nxp x mk), then the one kept first factor (p.shared_factor) and the vector of ones, np doubles rounded up to 4096 bytes.
+static int layout_shared(Problem& p, const FactorPlan& plan, FactorPlan& plan1, Arena& sh, bool build, hipStream_t st) {
+    p.A = sh.take<double>((size_t)p.mp * p.npa);
+    if (p.tall) p.Xt = sh.take<double>((size_t)p.tv.nxp * p.tv.mk);
+    if (!p.shared_factor) return LPIPM_OK;
+    LP_TRY(layout_first_factor(p, plan, plan1, sh, build, st));
+    p.ones = sh.take<double>((size_t)p.np);
+    sh.off = (size_t)round_up(sh.off, 4096);
+    return LPIPM_OK;
+}
+// Both allocations of the context, made anew for geometry g.
+static int relayout(lpipm_ctx* c, const Geometry& g) {
+    Problem& p = c->p;
+    hipStream_t st = c->rs.st;
+    LP_HIP(hipStreamSynchronize(st));
+    if (p.arena) { LP_HIP(hipFree(p.arena)); p.arena = nullptr; }
+    if (p.a_shared) { LP_HIP(hipFree(p.a_shared)); p.a_shared = nullptr; p.a_shared_bytes = 0; }
+    adat_lists_destroy(p.adat);
+    factor_plan_destroy(c->plan); factor_plan_destroy(c->plan1);
+    p.has_problem = false;
+    set_geometry(p, g);
+    c->ap = adat_plan_of(g, c->num_cu, c->world, c->units_env);
+    Arena measure;
+    LP_TRY(layout_problem(p, c->plan, c->plan1, c->ap, c->refine, measure, false, st));
+    p.bstride = round_up(measure.off, 4096);
+    p.arena_bytes = p.bstride * (size_t)g.B; p.va.bstride = (long long)p.bstride;
+    LP_HIP(hipMalloc((void**)&p.arena, p.arena_bytes));
+    LP_HIP(hipMemsetAsync(p.arena, 0, p.arena_bytes, st));
+    Arena real{p.arena};
+    LP_TRY(layout_problem(p, c->plan, c->plan1, c->ap, c->refine, real, true, st));
+    if (g.shared) {
+        Arena sh_measure;
+        LP_TRY(layout_shared(p, c->plan, c->plan1, sh_measure, false, st));
+        p.a_shared_bytes = sh_measure.off;
+        LP_HIP(hipMalloc((void**)&p.a_shared, p.a_shared_bytes));
+        LP_HIP(hipMemsetAsync(p.a_shared, 0, p.a_shared_bytes, st));
+        Arena sh{(char*)p.a_shared};
+        LP_TRY(layout_shared(p, c->plan, c->plan1, sh, true, st));
+    }
+    LP_HIP(adat_lists_create(p.adat, c->ap, g.tall ? g.nxp : g.mp, g.B, st));    // (drains st)
+    LP_TRY(stream_res_grow_status(c->rs, (size_t)g.B));
+    return LPIPM_OK;
+}
 // The exponent block of the upload being made: `sets` exponent sets for the padded geometry when the context scales, none
 // otherwise (what a previous upload left is freed).  Exponents start at zero.
 static int scale_setup(lpipm_ctx* c, int mp, int np, int npa, int sets) {
@@ -620,162 +708,90 @@ static int scale_setup(lpipm_ctx* c, int mp, int np, int npa, int sets) {
     p.sc = scale_buf_place(p.scale_mem, mp, np, npa, sets);
     return LPIPM_OK;
 }
-
-// count LPs of one geometry (count == 1: the ordinary upload).  A/b/cc/c0: one entry per LP.
-// n_slack: the structural hint of lpipm_upload_slack, for every member alike.  It is verified on every member (on the one
-// matrix of a shared batch); if any member's last n_slack columns are not [I; 0] the whole upload is dense.
-// hint_verified: the caller has done that check on these very matrices (batch_impl) and it is not repeated.
-// `parts` (count == 1, or shared): the rows come as two blocks of nx = n - n_slack columns -- m_ub rows of A_ub, then
-// m - m_ub rows of A_eq -- and c holds only the nx structural costs; the slack structure is then true by construction.
-// tall (parts with `ub` rows only; count == 1, or shared): the tall inequality form of the LP, or of every member over one X.
-// count == 1: b split the same way, in parts (lpipm_upload_ub_eq).  shared: the blocks are the batch's one matrix and
-// b[i] = [b_ub_i; b_eq_i] comes per member (lpipm_upload_lockstep_shared_ub_eq).
-struct UploadParts { uint64_t m_ub; const double* A_ub; uint64_t lda_ub; const double* b_ub;
-                     const double* A_eq; uint64_t lda_eq; const double* b_eq; };
-// shared: A[0] is the one matrix of all `count` LPs (lpipm_upload_lockstep_shared; A holds one entry).
-static int upload_impl(lpipm_ctx* c, int count, uint64_t m, uint64_t n, const double* const* A, uint64_t lda,
-                       const double* const* b, const double* const* cc, const double* c0, uint64_t n_slack,
-                       const UploadParts* parts = nullptr, bool shared = false, bool hint_verified = false, bool keep_ok = true,
-                       bool tall = false) {
-    if (!c || count < 1 || !cc) return LPIPM_ERR_BAD_ARGUMENT;
-    if (tall && (!parts || (!shared && count != 1) || n_slack != m)) return LPIPM_ERR_BAD_ARGUMENT;
-    if (!parts && (!A || !b || lda < n)) return LPIPM_ERR_BAD_ARGUMENT;
-    if (parts && (shared ? !b : count != 1)) return LPIPM_ERR_BAD_ARGUMENT;
-    for (int i = 0; i < count; ++i)
-        if (!cc[i] || (!parts && !shared && !A[i]) || (b && !b[i])) return LPIPM_ERR_BAD_ARGUMENT;
-    if (shared && !parts && !A[0]) return LPIPM_ERR_BAD_ARGUMENT;
-    if (m == 0) return LPIPM_UNCONSTRAINED;  // linear_program.rs:134-136
-    if (n == 0 || m > (1u << 20) || n > (1u << 24) || n_slack > n || n_slack > m) return LPIPM_ERR_BAD_ARGUMENT;
-    // The hint is only used if the last n_slack columns really are [I; 0] (ProblemBuilder::build
-    // guarantees it, linear_program.rs:147-156); anything else is treated as a dense matrix.
-    if (!parts && !hint_verified && !slack_hint_holds(shared ? 1 : count, m, n, A, lda, n_slack)) n_slack = 0;
+// The caller's arrays onto the stream, into the zeroed allocations.  c0v: c0 per member, made by the caller of this function
+// as its own arrays are: everything read here must outlive the asynchronous copies.
+static int copy_in(lpipm_ctx* c, const Upload& u, const double* c0v) {
+    Problem& p = c->p;
+    hipStream_t st = c->rs.st;
+    const uint64_t nx = (uint64_t)p.nx;
+    const size_t D = sizeof(double);
+    auto rows = [&](double* dst, const double* src, uint64_t ld, uint64_t nrows) {     // nx columns of each, into A's npa
+        return hipMemcpy2DAsync(dst, (size_t)p.npa * D, src, (size_t)ld * D, (size_t)nx * D, (size_t)nrows, hipMemcpyHostToDevice, st);
+    };
+    auto vec = [&](const void* dst, const double* src, uint64_t count) { return hipMemcpyAsync((void*)dst, src, count * D, hipMemcpyHostToDevice, st); };
+    // A: as parts -- rows of A_ub, then rows of A_eq, into the single LP's arena or the batch's one matrix -- or shared, here;
+    //    per member, with the member's vectors below.
+    // b: per member below, or in parts of a single LP, each part behind its rows.
+    if (u.parts) {
+        const UploadParts& q = *u.parts;
+        const uint64_t m_ub = q.m_ub, m_eq = u.m - m_ub;
+        if (m_ub) {
+            LP_HIP(rows(p.A, q.A_ub, q.lda_ub, m_ub));
+            if (!u.shared) LP_HIP(vec(p.va.b, q.b_ub, m_ub));
+        }
+        if (m_eq) {
+            LP_HIP(rows(p.A + (size_t)m_ub * p.npa, q.A_eq, q.lda_eq, m_eq));
+            if (!u.shared) LP_HIP(vec(p.va.b + m_ub, q.b_eq, m_eq));
+        }
+    } else if (u.shared) LP_HIP(rows(p.A, u.A[0], u.lda, u.m));
+    // c: n entries, or, in parts, the nx structural costs: c = [c; 0], and the arena is zero
+    const uint64_t nc = u.parts ? nx : u.n;
+    for (uint64_t i = 0; i < u.count; ++i) {
+        const size_t off = (size_t)i * p.bstride;
+        if (!u.shared && !u.parts) LP_HIP(rows((double*)((char*)p.A + off), u.A[i], u.lda, u.m));
+        if (u.b) LP_HIP(vec((const char*)p.va.b + off, u.b[i], u.m));
+        LP_HIP(vec((const char*)p.va.c + off, u.c[i], nc));
+        LP_HIP(vec((const char*)(p.va.S + S_C0) + off, &c0v[i], 1));
+    }
+    return LPIPM_OK;
+}
+static int upload_impl(lpipm_ctx* c, const Upload& u) {
+    LP_TRY(check_upload(c, u));
+    // The hint is only used if the last n_slack columns of every member (of a shared batch's one matrix) really are [I; 0]
+    // (ProblemBuilder::build guarantees it, linear_program.rs:147-156; parts have it by construction): else the upload is dense.
+    const bool hint = u.parts.has_value() || u.hint_verified || slack_hint_holds(u.shared ? 1 : u.count, u.m, u.n, u.A, u.lda, u.n_slack);
+    const uint64_t n_slack = hint ? u.n_slack : 0, nx = u.n - n_slack;
     LP_HIP(hipSetDevice(c->device));
     destroy_views(c); // half-batch views hold copies of the geometry and of the device pointers
     c->first_valid = false;   // whatever is kept belongs to the matrix that is being replaced
-    // keep_ok == false: an upload that is solved once (lpipm_solve_batch) or never through the kept factor (column split)
-    const bool keep = keep_ok && c->first_cache && c->refine <= 0 && !tall;   // (tall: the first factor is not kept)
-    const uint64_t nx = n - n_slack;
-    const int mp = (int)round_up(m, NB), np = (int)round_up(n, BK), npa = (int)round_up(nx, BK);
+    Problem& p = c->p;
     hipStream_t st = c->rs.st;
-    const int nxp = (int)round_up(nx, NB), mk = (int)round_up(m, BK);   // tall: the order of K, the contraction of its build
-    if (!c->p.has_problem || mp != c->p.mp || np != c->p.np || npa != c->p.npa || count != c->p.B || shared != c->p.shared_a ||
-        keep != c->p.keep || tall != c->p.tall || (tall && mk != c->p.tv.mk)) {   // (mk is not a function of mp, np and npa)
-        LP_HIP(hipStreamSynchronize(st));
-        if (c->p.arena) { LP_HIP(hipFree(c->p.arena)); c->p.arena = nullptr; }
-        if (c->p.a_shared) { LP_HIP(hipFree(c->p.a_shared)); c->p.a_shared = nullptr; c->p.a_shared_bytes = 0; }
-        c->p.shared_a = shared;
-        adat_lists_destroy(c->p.adat);
-        factor_plan_destroy(c->plan);
-        factor_plan_destroy(c->plan1);
-        c->p.has_problem = false;
-        c->p.mp = mp; c->p.np = np; c->p.npa = npa; c->p.B = count;
-        c->p.tall = tall;
-        c->p.Xt = nullptr;
-        c->p.tv = TallArgs{};
-        if (tall) { c->p.tv.nx = (int)nx; c->p.tv.npa = npa; c->p.tv.nxp = nxp; c->p.tv.mk = mk; }
-        c->p.nsplit = mp / GEMVT_ROWS;
-        const uint64_t big = m > n ? m : n;
-        c->p.nblk = (int)((big + 255) / 256);
-        if (c->p.nblk > RED_STRIDE) c->p.nblk = RED_STRIDE;
-        // (tall: the launch builds K from Xt -- nxp rows, a contraction over the mk padded rows of X)
-        // A tall batch: every member's K must have the bits the single LP's has.  The units kernel gives them whatever the
-        // count; the round-2 kernel (which a single LP of a few tiles with several chunks takes) only with the single LP's
-        // own workgroup count once the contraction is longer than 4096 (round2_unit): the batch then runs that very plan.
-        if (tall) {
-            const AdatPlan single = plan_adat(nxp, mk, 1, c->num_cu, 1, c->units_env);
-            c->ap = shared && single.units ? plan_adat(nxp, mk, count, c->num_cu, 1, c->units_env) : single;
-        } else c->ap = plan_adat(mp, npa, count, c->num_cu, c->world, c->units_env);
-        Arena measure;
-        LP_TRY(layout_problem(c->p, c->plan, c->plan1, c->ap, c->refine, keep, measure, false, st));
-        c->p.bstride = round_up(measure.off, 4096);
-        c->p.arena_bytes = c->p.bstride * (size_t)count;
-        LP_HIP(hipMalloc((void**)&c->p.arena, c->p.arena_bytes));
-        LP_HIP(hipMemsetAsync(c->p.arena, 0, c->p.arena_bytes, st));
-        Arena real;
-        real.base = c->p.arena;
-        LP_TRY(layout_problem(c->p, c->plan, c->plan1, c->ap, c->refine, keep, real, true, st));
-        if (shared) {              // the one A of the batch: mp x npa like an arena's, zero padding; behind it the one kept factor
-            // (tall: behind X its transpose, nxp x mk, once for the batch; no factor is kept)
-            const size_t x_bytes = (size_t)mp * (size_t)npa * sizeof(double);
-            const size_t a_bytes = x_bytes + (tall ? (size_t)nxp * (size_t)mk * sizeof(double) : 0);
-            Arena sh_measure;
-            sh_measure.off = a_bytes;
-            if (c->p.shared_factor) LP_TRY(layout_shared_factor(c->p, c->plan, c->plan1, sh_measure, false, st));
-            c->p.a_shared_bytes = sh_measure.off;
-            LP_HIP(hipMalloc((void**)&c->p.a_shared, c->p.a_shared_bytes));
-            LP_HIP(hipMemsetAsync(c->p.a_shared, 0, c->p.a_shared_bytes, st));
-            c->p.A = c->p.a_shared;
-            if (tall) c->p.Xt = (double*)((char*)c->p.a_shared + x_bytes);
-            Arena sh;
-            sh.base = (char*)c->p.a_shared; sh.off = a_bytes;
-            if (c->p.shared_factor) LP_TRY(layout_shared_factor(c->p, c->plan, c->plan1, sh, true, st));
-        }
-        LP_HIP(adat_lists_create(c->p.adat, c->ap, tall ? nxp : mp, count, st));    // (drains st)
-        LP_TRY(stream_res_grow_status(c->rs, (size_t)count));
-        VecArgs& v = c->p.va;
-        v.np = np; v.mp = mp; v.nblk = c->p.nblk; v.nsplit = c->p.nsplit;
-        v.bcount = count; v.bstride = (long long)c->p.bstride; v.bfirst = 0; v.refine_below = refine_below();
-    } else {
+    const Geometry g = geometry_of(u, n_slack, c->first_cache, c->refine);
+    if (!p.has_problem || !(g == p.geo)) LP_TRY(relayout(c, g));
+    else {
         // same padded geometry: clear the whole state, so no stale (possibly non-finite) value of a
         // previous problem can sit in a padding lane
-        LP_HIP(hipMemsetAsync(c->p.arena, 0, c->p.arena_bytes, st));
-        if (c->p.a_shared) LP_HIP(hipMemsetAsync(c->p.a_shared, 0, c->p.a_shared_bytes, st));   // (a smaller m or n than before)
+        LP_HIP(hipMemsetAsync(p.arena, 0, p.arena_bytes, st));
+        if (p.a_shared) LP_HIP(hipMemsetAsync(p.a_shared, 0, p.a_shared_bytes, st));   // (a smaller m or n than before)
     }
-    c->p.has_problem = false;     // until this upload is complete
-    LP_TRY(scale_setup(c, mp, np, npa, shared ? 1 : count));
-    c->p.m = m; c->p.n = n;
-    c->p.ns = (int)n_slack; c->p.nx = (int)nx;
-    if (tall) c->p.tv.nx = (int)nx;            // (the padded geometry may be shared by several nx)
-    c->p.from_parts = parts != nullptr;
-    c->p.va.n = (int)n; c->p.va.m = (int)m;
-    c->p.va.n_total = (long long)n; c->p.va.gs = nullptr; c->colsplit = false;   // lpipm_upload_nsplit overrides
+    p.has_problem = false;     // until this upload is complete
+    const int count = g.B;
+    LP_TRY(scale_setup(c, g.mp, g.np, g.npa, u.shared ? 1 : count));
+    p.m = u.m; p.n = u.n; p.ns = (int)n_slack; p.nx = (int)nx;
+    if (u.tall) p.tv.nx = (int)nx;            // (the padded geometry may be shared by several nx)
+    p.from_parts = u.parts.has_value();
+    p.va.n = (int)u.n; p.va.m = (int)u.m; p.va.n_total = (long long)u.n; p.va.gs = nullptr; c->colsplit = false;   // lpipm_upload_nsplit overrides
     // A single LP's loop ends on the host, so its kernels need not test the done word (one dependent load
     // less at the start of ~100 short kernels) -- except the head of an iteration, which is enqueued before
     // the host has seen the previous status.  In a batch every kernel tests it.
-    c->p.bt = Batch{count, (long long)c->p.bstride, count > 1 ? c->p.va.done : nullptr};
-    c->p.bt_head = Batch{count, (long long)c->p.bstride, c->p.va.done};
-    c->p.va.done_chk = c->p.bt.done;
+    p.bt = Batch{count, (long long)p.bstride, count > 1 ? p.va.done : nullptr};
+    p.bt_head = Batch{count, (long long)p.bstride, p.va.done};
+    p.va.done_chk = p.bt.done;
     std::vector<double> c0v((size_t)count, 0.0);          // must outlive the asynchronous copies below
-    for (int i = 0; i < count; ++i) c0v[i] = c0 ? c0[i] : 0.0;
-    const std::vector<double> onesv(c->p.shared_factor ? (size_t)np : 0, 1.0);
-    if (c->p.shared_factor) LP_HIP(hipMemcpyAsync(c->p.ones, onesv.data(), onesv.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    if (parts) {   // rows of A_ub, then rows of A_eq (into the single LP's arena or the batch's one matrix); a single LP's b likewise
-        const uint64_t m_ub = parts->m_ub, m_eq = m - m_ub;
-        if (m_ub) {
-            LP_HIP(hipMemcpy2DAsync(c->p.A, (size_t)npa * sizeof(double), parts->A_ub, (size_t)parts->lda_ub * sizeof(double),
-                                    (size_t)nx * sizeof(double), (size_t)m_ub, hipMemcpyHostToDevice, st));
-            if (!shared) LP_HIP(hipMemcpyAsync((void*)c->p.va.b, parts->b_ub, m_ub * sizeof(double), hipMemcpyHostToDevice, st));
-        }
-        if (m_eq) {
-            LP_HIP(hipMemcpy2DAsync(c->p.A + (size_t)m_ub * npa, (size_t)npa * sizeof(double), parts->A_eq,
-                                    (size_t)parts->lda_eq * sizeof(double), (size_t)nx * sizeof(double), (size_t)m_eq,
-                                    hipMemcpyHostToDevice, st));
-            if (!shared) LP_HIP(hipMemcpyAsync((void*)(c->p.va.b + m_ub), parts->b_eq, m_eq * sizeof(double), hipMemcpyHostToDevice, st));
-        }
-    } else if (shared)
-        LP_HIP(hipMemcpy2DAsync(c->p.A, (size_t)npa * sizeof(double), A[0], (size_t)lda * sizeof(double),
-                                (size_t)nx * sizeof(double), (size_t)m, hipMemcpyHostToDevice, st));
-    const uint64_t nc = parts ? nx : n;        // parts: c = [c; 0], and the arena is zero
-    for (int i = 0; i < count; ++i) {
-        const size_t off = (size_t)i * c->p.bstride;
-        if (!shared && !parts)
-            LP_HIP(hipMemcpy2DAsync((char*)c->p.A + off, (size_t)npa * sizeof(double), A[i], (size_t)lda * sizeof(double),
-                                    (size_t)nx * sizeof(double), (size_t)m, hipMemcpyHostToDevice, st));
-        if (b) LP_HIP(hipMemcpyAsync((char*)c->p.va.b + off, b[i], m * sizeof(double), hipMemcpyHostToDevice, st));
-        LP_HIP(hipMemcpyAsync((char*)c->p.va.c + off, cc[i], nc * sizeof(double), hipMemcpyHostToDevice, st));
-        LP_HIP(hipMemcpyAsync((char*)(c->p.va.S + S_C0) + off, &c0v[i], sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    if (c->p.scale_passes > 0) {   // equilibrate what was just copied: the solves see the scaled problem only
-        const Batch members{count, (long long)c->p.bstride, nullptr, 0};
-        LP_HIP(launch_equilibrate(c->p.sc, c->p.A, (int)m, mp, (int)nx, npa, (int)n_slack, c->p.scale_passes, st,
-                                  shared ? Batch{} : members));
-        LP_HIP(launch_scale_vectors(c->p.sc, (double*)c->p.va.b, (int)m, (double*)c->p.va.c, (int)n, st, members));
+    for (int i = 0; i < count; ++i) c0v[i] = u.c0 ? u.c0[i] : 0.0;
+    const std::vector<double> onesv(p.shared_factor ? (size_t)g.np : 0, 1.0);     // likewise
+    if (p.shared_factor) LP_HIP(hipMemcpyAsync(p.ones, onesv.data(), onesv.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    LP_TRY(copy_in(c, u, c0v.data()));
+    if (p.scale_passes > 0) {   // equilibrate what was just copied: the solves see the scaled problem only
+        const Batch members{count, (long long)p.bstride, nullptr, 0};
+        LP_HIP(launch_equilibrate(p.sc, p.A, (int)u.m, g.mp, (int)nx, g.npa, (int)n_slack, p.scale_passes, st,
+                                  u.shared ? Batch{} : members));
+        LP_HIP(launch_scale_vectors(p.sc, (double*)p.va.b, (int)u.m, (double*)p.va.c, (int)u.n, st, members));
     }
     // tall: the resident transpose, from the X the solves see (behind the equilibration: both copies carry its exponents)
-    if (tall) LP_HIP(tall_transpose(c->p.A, npa, (int)m, (int)nx, c->p.Xt, mk, st));
+    if (u.tall) LP_HIP(tall_transpose(p.A, g.npa, (int)u.m, (int)nx, p.Xt, g.mk, st));
     LP_HIP(hipStreamSynchronize(st));   // the caller's arrays, c0v and onesv are free again from here
-    c->p.has_problem = true;
-    c->p.adat.counters_dirty = true;
+    p.has_problem = p.adat.counters_dirty = true;
     bind_status_pinned(c, true);
     return LPIPM_OK;
 }
@@ -784,40 +800,51 @@ extern "C" int lpipm_upload(lpipm_ctx* c, uint64_t m, uint64_t n, const double* 
                             const double* b, const double* cc, double c0) {
     return lpipm_upload_slack(c, m, n, A, lda, b, cc, c0, 0);
 }
-
 extern "C" int lpipm_upload_slack(lpipm_ctx* c, uint64_t m, uint64_t n, const double* A, uint64_t lda,
                                   const double* b, const double* cc, double c0, uint64_t n_slack) {
-    return upload_impl(c, 1, m, n, &A, lda, &b, &cc, &c0, n_slack);
+    return upload_impl(c, Upload{.m = m, .n = n, .n_slack = n_slack, .A = &A, .lda = lda, .b = &b, .c = &cc, .c0 = &c0});
 }
-
 extern "C" int lpipm_upload_ub_eq(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub,
                                   const double* b_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq,
                                   const double* b_eq, const double* cc, double c0) {
-    if (m_ub + m_eq == 0) return LPIPM_UNCONSTRAINED;                       // linear_program.rs:134-136
-    if (!cc || n == 0 || (m_ub && (!A_ub || !b_ub || lda_ub < n)) || (m_eq && (!A_eq || !b_eq || lda_eq < n)))
-        return LPIPM_ERR_BAD_ARGUMENT;
-    const UploadParts parts{m_ub, A_ub, lda_ub, b_ub, A_eq, lda_eq, b_eq};
-    return upload_impl(c, 1, m_ub + m_eq, n + m_ub, nullptr, 0, nullptr, &cc, &c0, m_ub, &parts);
+    return upload_impl(c, Upload{.m = m_ub + m_eq, .n = n + m_ub, .n_slack = m_ub,
+                                 .parts = UploadParts{m_ub, A_ub, lda_ub, b_ub, A_eq, lda_eq, b_eq}, .c = &cc, .c0 = &c0});
 }
-
 extern "C" int lpipm_upload_ub_tall(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub,
                                     const double* b_ub, const double* cc, double c0) {
-    if (m_ub == 0) return LPIPM_UNCONSTRAINED;                              // linear_program.rs:134-136
-    if (!c || !cc || n == 0 || !A_ub || !b_ub || lda_ub < n) return LPIPM_ERR_BAD_ARGUMENT;
-    if (c->world > 1 || c->refine > 0) return LPIPM_ERR_UNSUPPORTED;        // a column-split context; the refined solves
-    const UploadParts parts{m_ub, A_ub, lda_ub, b_ub, nullptr, 0, nullptr};
-    return upload_impl(c, 1, m_ub, n + m_ub, nullptr, 0, nullptr, &cc, &c0, m_ub, &parts, false, false, false, true);
+    return upload_impl(c, Upload{.m = m_ub, .n = n + m_ub, .n_slack = m_ub,
+                                 .parts = UploadParts{.m_ub = m_ub, .A_ub = A_ub, .lda_ub = lda_ub, .b_ub = b_ub}, .c = &cc, .c0 = &c0, .tall = true, .keep_ok = false});
 }
-
+extern "C" int lpipm_upload_lockstep(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* const* A,
+                                     const double* const* b, const double* const* cc, const double* c0) {
+    return lpipm_upload_lockstep_slack(c, count, m, n, A, b, cc, c0, 0);
+}
+extern "C" int lpipm_upload_lockstep_slack(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* const* A,
+                                           const double* const* b, const double* const* cc, const double* c0, uint64_t n_slack) {
+    return upload_impl(c, Upload{.count = count, .m = m, .n = n, .n_slack = n_slack, .A = A, .lda = n, .b = b, .c = cc, .c0 = c0});
+}
+extern "C" int lpipm_upload_lockstep_shared(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* A, uint64_t lda,
+                                            const double* const* b, const double* const* cc, const double* c0) {
+    return lpipm_upload_lockstep_shared_slack(c, count, m, n, A, lda, b, cc, c0, 0);
+}
+extern "C" int lpipm_upload_lockstep_shared_slack(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* A, uint64_t lda,
+                                                  const double* const* b, const double* const* cc, const double* c0, uint64_t n_slack) {
+    return upload_impl(c, Upload{.count = count, .m = m, .n = n, .n_slack = n_slack, .A = &A, .lda = lda, .b = b, .c = cc, .c0 = c0,
+                                 .shared = true});
+}
+extern "C" int lpipm_upload_lockstep_shared_ub_eq(lpipm_ctx* c, uint64_t count, uint64_t n, uint64_t m_ub, const double* A_ub,
+                                                  uint64_t lda_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq,
+                                                  const double* const* b, const double* const* cc, const double* c0) {
+    return upload_impl(c, Upload{.count = count, .m = m_ub + m_eq, .n = n + m_ub, .n_slack = m_ub,
+                                 .parts = UploadParts{.m_ub = m_ub, .A_ub = A_ub, .lda_ub = lda_ub, .A_eq = A_eq, .lda_eq = lda_eq}, .b = b, .c = cc, .c0 = c0, .shared = true});
+}
 extern "C" int lpipm_upload_lockstep_shared_ub_tall(lpipm_ctx* c, uint64_t count, uint64_t n, uint64_t m_ub, const double* A_ub,
                                                     uint64_t lda_ub, const double* const* b, const double* const* cc,
                                                     const double* c0) {
-    if (!c || count < 1 || count > 4096 || !b || !cc) return LPIPM_ERR_BAD_ARGUMENT;
-    if (m_ub == 0) return LPIPM_UNCONSTRAINED;                              // linear_program.rs:134-136
-    if (n == 0 || !A_ub || lda_ub < n) return LPIPM_ERR_BAD_ARGUMENT;
-    if (c->world > 1 || c->refine > 0) return LPIPM_ERR_UNSUPPORTED;        // as lpipm_upload_ub_tall
-    const UploadParts parts{m_ub, A_ub, lda_ub, nullptr, nullptr, 0, nullptr};
-    return upload_impl(c, (int)count, m_ub, n + m_ub, nullptr, 0, b, cc, c0, m_ub, &parts, true, false, false, true);
+    if (!c) return LPIPM_ERR_BAD_ARGUMENT;       // (this entry alone refuses a null context before it looks at the shape)
+    return upload_impl(c, Upload{.count = count, .m = m_ub, .n = n + m_ub, .n_slack = m_ub,
+                                 .parts = UploadParts{.m_ub = m_ub, .A_ub = A_ub, .lda_ub = lda_ub}, .b = b, .c = cc, .c0 = c0, .shared = true,
+                                 .tall = true, .keep_ok = false});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1568,35 +1595,6 @@ static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const XOut& xo, con
     return rc[0] != LPIPM_OK ? rc[0] : rc[1];
 }
 
-extern "C" int lpipm_upload_lockstep(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* const* A,
-                                     const double* const* b, const double* const* cc, const double* c0) {
-    return lpipm_upload_lockstep_slack(c, count, m, n, A, b, cc, c0, 0);
-}
-extern "C" int lpipm_upload_lockstep_slack(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* const* A,
-                                           const double* const* b, const double* const* cc, const double* c0, uint64_t n_slack) {
-    if (count < 1 || count > 4096) return LPIPM_ERR_BAD_ARGUMENT;
-    return upload_impl(c, (int)count, m, n, A, n, b, cc, c0, n_slack);
-}
-extern "C" int lpipm_upload_lockstep_shared(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* A, uint64_t lda,
-                                            const double* const* b, const double* const* cc, const double* c0) {
-    return lpipm_upload_lockstep_shared_slack(c, count, m, n, A, lda, b, cc, c0, 0);
-}
-extern "C" int lpipm_upload_lockstep_shared_slack(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* A, uint64_t lda,
-                                                  const double* const* b, const double* const* cc, const double* c0,
-                                                  uint64_t n_slack) {
-    if (count < 1 || count > 4096 || !A) return LPIPM_ERR_BAD_ARGUMENT;
-    return upload_impl(c, (int)count, m, n, &A, lda, b, cc, c0, n_slack, nullptr, true);
-}
-extern "C" int lpipm_upload_lockstep_shared_ub_eq(lpipm_ctx* c, uint64_t count, uint64_t n, uint64_t m_ub, const double* A_ub,
-                                                  uint64_t lda_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq,
-                                                  const double* const* b, const double* const* cc, const double* c0) {
-    if (count < 1 || count > 4096) return LPIPM_ERR_BAD_ARGUMENT;
-    if (!b || !cc) return LPIPM_ERR_BAD_ARGUMENT;
-    if (m_ub + m_eq == 0) return LPIPM_UNCONSTRAINED;                       // linear_program.rs:134-136
-    if (n == 0 || (m_ub && (!A_ub || lda_ub < n)) || (m_eq && (!A_eq || lda_eq < n))) return LPIPM_ERR_BAD_ARGUMENT;
-    const UploadParts parts{m_ub, A_ub, lda_ub, nullptr, A_eq, lda_eq, nullptr};
-    return upload_impl(c, (int)count, m_ub + m_eq, n + m_ub, nullptr, 0, b, cc, c0, m_ub, &parts, true);
-}
 extern "C" int lpipm_get_resident_bytes(const lpipm_ctx* c, uint64_t* bytes_out) {
     if (!c || !bytes_out) return LPIPM_ERR_BAD_ARGUMENT;
     *bytes_out = c->p.has_problem ? (uint64_t)(c->p.arena_bytes + c->p.a_shared_bytes + c->p.adat.list_bytes + c->p.scale_bytes) : 0;
@@ -1614,18 +1612,17 @@ extern "C" int lpipm_solve_lockstep_device(lpipm_ctx* c, const lpipm_opts* o, vo
     return solve_lockstep(c, o, xo, nullptr, fun_out, iterations_out, status_out);
 }
 
-// Bytes one member of a lockstep batch of this shape occupies: the real layout (plan_adat and a measuring pass of
-// layout_problem over the bare geometry), not a formula that drifts from it.
+// Bytes one member of a lockstep batch of 32 of this shape occupies: the real layout (a measuring pass of layout_problem over
+// its geometry), not a formula that drifts from it.  No kept first factor: a chunk is uploaded, solved once and replaced.
 // n_slack: the member's (verified) structural hint -- its slack columns are not resident.
-static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, uint64_t m, uint64_t n, uint64_t n_slack, bool keep) {
+static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, uint64_t m, uint64_t n, uint64_t n_slack) {
+    const Geometry g = geometry_of(Upload{.count = 32, .m = m, .n = n, .keep_ok = false}, n_slack, c->first_cache, c->refine);
     Problem t;
-    t.B = 32;
-    t.mp = (int)round_up(m, NB); t.np = (int)round_up(n, BK); t.npa = (int)round_up(n - n_slack, BK);
-    t.nsplit = t.mp / GEMVT_ROWS;
-    const AdatPlan ap = plan_adat(t.mp, t.npa, t.B, c->num_cu, c->world, c->units_env);
+    set_geometry(t, g);
     FactorPlan fp, fp1;
     Arena measure;
-    if (layout_problem(t, fp, fp1, ap, c->refine, keep && c->first_cache && c->refine <= 0, measure, false, nullptr) != LPIPM_OK) return (size_t)-1;
+    if (layout_problem(t, fp, fp1, adat_plan_of(g, c->num_cu, c->world, c->units_env), c->refine, measure, false, nullptr) != LPIPM_OK)
+        return (size_t)-1;
     return (size_t)round_up(measure.off, 4096);
 }
 
@@ -1673,8 +1670,7 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             size_t free_b = 0, total_b = 0;
             LP_HIP(hipMemGetInfo(&free_b, &total_b));
             free_b += c->p.arena_bytes;                // the current arena is released before the next one is made
-            // the real arena layout of one member (no kept first factor: a chunk is uploaded, solved once and replaced)
-            const double per_lp = (double)lockstep_bytes_per_lp(c, m[i], n[i], ns[i], false);
+            const double per_lp = (double)lockstep_bytes_per_lp(c, m[i], n[i], ns[i]);
             size_t chunk;
             if (c->lockstep_max > 0) chunk = (size_t)c->lockstep_max;
             else if (grp.size() > 32) chunk = 32;
@@ -1714,8 +1710,8 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             auto upload_chunk = [&](lpipm_ctx* w, const Chunk& ch) -> int {
                 (void)hipSetDevice(w->device);
                 w->scaling = c->scaling;
-                return upload_impl(w, (int)ch.g, m[i], n[i], ch.A.data(), n[i], ch.b.data(), ch.c.data(), ch.c0.data(), ns[i],
-                                   nullptr, false, true, false);
+                return upload_impl(w, Upload{.count = ch.g, .m = m[i], .n = n[i], .n_slack = ns[i], .A = ch.A.data(), .lda = n[i], .b = ch.b.data(),
+                                             .c = ch.c.data(), .c0 = ch.c0.data(), .hint_verified = true, .keep_ok = false});
             };
             int rc_up = chunks.empty() ? LPIPM_OK : upload_chunk(pipe[0], chunks[0]);
             for (size_t q = 0; q < chunks.size(); ++q) {
@@ -1776,7 +1772,8 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             if (k >= rest.size() || fatal.load() != LPIPM_OK) break;
             const uint64_t i = rest[k];
             const double c0i = c0 ? c0[i] : 0.0;
-            int rc = upload_impl(w, 1, m[i], n[i], &A[i], n[i], &b[i], &cc[i], &c0i, ns[i], nullptr, false, true, false);
+            int rc = upload_impl(w, Upload{.m = m[i], .n = n[i], .n_slack = ns[i], .A = &A[i], .lda = n[i], .b = &b[i], .c = &cc[i],
+                                           .c0 = &c0i, .hint_verified = true, .keep_ok = false});
             double fun = NAN;
             uint64_t it = 0;
             if (rc == LPIPM_OK)
@@ -1856,7 +1853,8 @@ extern "C" int lpipm_upload_nsplit(lpipm_ctx* c, uint64_t m, uint64_t n_total, u
                                    uint64_t lda, const double* b, const double* c_local, double c0) {
     if (!c || n_local == 0 || n_local > n_total) return LPIPM_ERR_BAD_ARGUMENT;
     if (c->scaling > 0) return LPIPM_ERR_UNSUPPORTED;      // row maxima of a column split would need the collective
-    const int rc = upload_impl(c, 1, m, n_local, &A_local, lda, &b, &c_local, &c0, 0, nullptr, false, false, false);
+    const int rc = upload_impl(c, Upload{.m = m, .n = n_local, .A = &A_local, .lda = lda, .b = &b, .c = &c_local, .c0 = &c0,
+                                         .keep_ok = false});
     if (rc != LPIPM_OK) return rc;
     if (c->world > 1) {
         const size_t need = (size_t)c->p.mp * ((size_t)c->p.mp + 128) / 2;

@@ -178,6 +178,72 @@ def test_shared_context_reuse(built):
     reused.close()
 
 
+def _ub_members(seed, m_ub, nx, count, m_eq=0):
+    """`count` planted LPs min c'x st X x <= b_ub, E x == b_eq, x >= 0 over one X (m_ub x nx) and one E (m_eq x nx): an optimal
+    vertex with nx // 2 positive entries and as many active rows.  -> X, E, [b = [b_ub; b_eq]], [c]"""
+    rng = np.random.default_rng(seed)
+    X, E = rng.standard_normal((m_ub, nx)), rng.standard_normal((m_eq, nx))
+    bs, cs = [], []
+    for _ in range(count):
+        k = nx // 2
+        xs = np.zeros(nx); xs[:k] = rng.uniform(1, 2, k)
+        act = rng.permutation(m_ub)[:k]
+        s = rng.uniform(1, 2, m_ub); s[act] = 0.0
+        lam = np.zeros(m_ub); lam[act] = rng.uniform(1, 2, k)
+        mu = np.zeros(nx); mu[k:] = rng.uniform(1, 2, nx - k)
+        bs.append(np.concatenate([X @ xs + s, E @ xs]))
+        cs.append(-X.T @ lam + mu + E.T @ rng.standard_normal(m_eq))
+    return X, E, bs, cs
+
+
+def test_one_context_through_every_form(built):
+    """single dense -> single with hint -> ub_eq -> tall -> lockstep -> lockstep with hint -> shared -> shared with hint -> shared
+    ub_eq -> shared tall -> single dense on ONE context, three members to a batch: every step's statuses, iteration counts, fun
+    and x bit-identical to the same step on a fresh context."""
+    import lp_amd
+    from lp_amd import synth
+    o = lp_amd.InteriorPoint.default().opts()
+    A, bs, cs, _ = synth.planted_scenarios(7, 96, 200, 3)
+    X, _, hb, hc = _ub_members(8, 60, 40, 3)                              # the hint: [X I], n_slack = m
+    H, hc = np.hstack([X, np.eye(60)]), [np.concatenate([c, np.zeros(60)]) for c in hc]
+    Xu, Eu, ub, uc = _ub_members(9, 60, 40, 3, m_eq=30)
+    Xt, _, tb, tc = _ub_members(10, 300, 20, 3)
+    prob_ue = lp_amd.Problem.target(uc[1]).ub(Xu, ub[1][:60]).eq(Eu, ub[1][60:]).build()
+    prob_t = lp_amd.Problem.target(tc[1]).ub(Xt, tb[1]).build()
+
+    def single(c, upload):
+        upload(c)
+        rc, x, fun, it, _ = c.solve_raw(o)
+        return [(rc, x, fun, it)]
+
+    def batch(c, upload):
+        upload(c)
+        return c.solve_lockstep(o)
+
+    steps = [
+        ("single", single, lambda c: c.upload_arrays(A, bs[0], cs[0])),
+        ("single hint", single, lambda c: c.upload_arrays(H, hb[0], hc[0], n_slack=60)),
+        ("ub_eq", single, lambda c: c.upload(prob_ue)),
+        ("tall", single, lambda c: c.upload(prob_t, tall=True)),
+        ("lockstep", batch, lambda c: c.upload_lockstep([A] * 3, bs, cs)),
+        ("lockstep hint", batch, lambda c: c.upload_lockstep([H] * 3, hb, hc, n_slack=60)),
+        ("shared", batch, lambda c: c.upload_lockstep_shared(A, bs, cs)),
+        ("shared hint", batch, lambda c: c.upload_lockstep_shared(H, hb, hc, n_slack=60)),
+        ("shared ub_eq", batch, lambda c: c.upload_lockstep_shared_ub_eq(Xu, Eu, ub, uc)),
+        ("shared tall", batch, lambda c: c.upload_lockstep_shared_ub_tall(Xt, tb, tc)),
+        ("single again", single, lambda c: c.upload_arrays(A, bs[2], cs[2])),
+    ]
+    reused = lp_amd.Context(0)
+    for name, run, upload in steps:
+        got = run(reused, upload)
+        fresh = lp_amd.Context(0)
+        want = run(fresh, upload)
+        fresh.close()
+        assert all(r[0] == 0 for r in want), (name, [r[0] for r in want])
+        _same(got, want)
+    reused.close()
+
+
 def test_shared_upload_errors(ctx):
     import lp_amd
     from lp_amd import _capi
