@@ -117,6 +117,11 @@ extern "C" {
         ctx: *mut lpipm_ctx, count: u64, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, b: *const *const f64,
         c: *const *const f64, c0: *const f64,
     ) -> c_int;
+    // The same with one matrix per member (a_ub[i]: m_ub x n, lda_ub): every member keeps its own X, transpose and K.
+    pub fn lpipm_upload_lockstep_ub_tall(
+        ctx: *mut lpipm_ctx, count: u64, n: u64, m_ub: u64, a_ub: *const *const f64, lda_ub: u64, b: *const *const f64,
+        c: *const *const f64, c0: *const f64,
+    ) -> c_int;
     // New b / c / c0 (each nullable: stays) for every member of the resident lockstep batch, in its upload's own form; A and
     // the kept first factor stay.  _device: packed row blocks on the device, member i at b_dev + i * ldb doubles.
     pub fn lpipm_update_lockstep_vectors(
@@ -129,6 +134,14 @@ extern "C" {
     pub fn lpipm_solve_batch_slack(
         ctx: *mut lpipm_ctx, count: u64, m: *const u64, n: *const u64, n_slack: *const u64, a: *const *const f64,
         b: *const *const f64, c: *const *const f64, c0: *const f64, opts: *const lpipm_opts,
+        x_slack_out: *const *mut f64, x_dev_out: *mut c_void, row_stride: u64, fun_out: *mut f64,
+        iterations_out: *mut u64, status_out: *mut i32,
+    ) -> c_int;
+    // A shard of tall inequality-form LPs (a_ub[i]: m_ub[i] x n[i], lda = n[i]; x: n[i] + m_ub[i] entries, slack values last):
+    // members of equal shape as lockstep chunks of lpipm_upload_lockstep_ub_tall, the others through lpipm_upload_ub_tall.
+    pub fn lpipm_solve_batch_ub_tall(
+        ctx: *mut lpipm_ctx, count: u64, m_ub: *const u64, n: *const u64, a_ub: *const *const f64,
+        b_ub: *const *const f64, c: *const *const f64, c0: *const f64, opts: *const lpipm_opts,
         x_slack_out: *const *mut f64, x_dev_out: *mut c_void, row_stride: u64, fun_out: *mut f64,
         iterations_out: *mut u64, status_out: *mut i32,
     ) -> c_int;

@@ -164,7 +164,7 @@ int lpipm_update_vectors(lpipm_ctx* ctx, const double* b, const double* c);
 /* New b, c and (optionally) c0 for EVERY member of the resident lockstep batch, whichever lpipm_upload_lockstep* made it, in
  * that upload's own form: b[i][m] and c[i][n] (c with its slack entries); after lpipm_upload_lockstep_shared_ub_eq
  * b[i] = [b_ub_i; b_eq_i] and c[i] = the n structural costs (the slack costs stay 0), after
- * lpipm_upload_lockstep_shared_ub_tall b[i] of m_ub doubles and c[i] = the n structural costs.  b or c may be NULL as a whole: those
+ * lpipm_upload_lockstep_shared_ub_tall and lpipm_upload_lockstep_ub_tall b[i] of m_ub doubles and c[i] = the n structural costs.  b or c may be NULL as a whole: those
  * vectors stay (a right-hand-side sweep sends no costs); c0 == NULL: the constants stay.  A, the layout, the half-batch views
  * and the kept first factor(s) are not touched, and the padding beyond m and n stays zero: the next lpipm_solve_lockstep[_device]
  * is bit-identical to a fresh upload of the same members followed by a solve.  The host arrays are staged in one pinned block
@@ -334,11 +334,27 @@ int lpipm_upload_lockstep_shared_ub_eq(lpipm_ctx* ctx, uint64_t count, uint64_t 
  * column-split context or one with the refined solves LPIPM_ERR_UNSUPPORTED (as lpipm_upload_ub_tall); solver_type 1 or 2
  * LPIPM_ERR_UNSUPPORTED (as every lockstep batch); lpipm_k_tall_normal, lpipm_k_tall_sym_solve, lpipm_k_iteration and
  * lpipm_k_adat on such a batch LPIPM_ERR_UNSUPPORTED.
- * Not built: tall batches whose members own their matrices, grouping of tall members inside lpipm_solve_batch*, `eq` rows, a
- * kept K_1 = X^T.X + I, fused small-LP vector kernels for the tall form. */
+ * Tall LPs of one shape that each have their own matrix: lpipm_upload_lockstep_ub_tall, below.
+ * Not built: `eq` rows, a kept K_1 = X^T.X + I, fused small-LP vector kernels for the tall form, tall members inside
+ * lpipm_solve_batch / lpipm_solve_batch_slack (lpipm_solve_batch_ub_tall is their entry). */
 int lpipm_upload_lockstep_shared_ub_tall(lpipm_ctx* ctx, uint64_t count, uint64_t n, uint64_t m_ub, const double* A_ub,
                                          uint64_t lda_ub, const double* const* b, const double* const* c,
                                          const double* c0 /* nullable */);
+/* A lockstep batch of `count` independent tall inequality-form LPs of one shape, each with its OWN matrix: one L-infinity fit or
+ * cover model per customer or time window, per-scenario cut sets.  Member i is (A_ub[i] (m_ub x n row-major, lda_ub), b[i] (m_ub
+ * doubles), c[i] (the n structural costs), c0[i]): the arguments of lpipm_upload_lockstep_shared_ub_tall with one matrix per
+ * member.  Member i's arena holds its own X_i, its own transpose (made for all members by one launch, behind the per-member
+ * equilibration) and its own K beside its tall vectors; nothing of a member grows as m_ub^2 and nothing is shared.
+ * Solve with lpipm_solve_lockstep / lpipm_solve_lockstep_device: x has n + m_ub entries, slack values last.  Every member is
+ * bit-identical to lpipm_upload_ub_tall + lpipm_solve of that member alone -- x, fun, status and iteration count -- whatever the
+ * count, wherever the member sits, whichever members have finished, as one view or two half-batch views.
+ * lpipm_update_lockstep_vectors[_device] replace b[i] (m_ub doubles), c[i] (the n structural costs) and c0 in place, the next
+ * solve bit-identical to a fresh upload of the same members.  lpipm_set_scaling keeps one set of exponents per member
+ * (lpipm_get_scaling with the member's index), as for any batch whose members own their matrices.  No first factor is kept.
+ * Return codes and refusals are those of lpipm_upload_lockstep_shared_ub_tall, A_ub[i] counting among the pointers. */
+int lpipm_upload_lockstep_ub_tall(lpipm_ctx* ctx, uint64_t count, uint64_t n, uint64_t m_ub, const double* const* A_ub,
+                                  uint64_t lda_ub, const double* const* b, const double* const* c,
+                                  const double* c0 /* nullable */);
 /* Device bytes the context holds for its resident problem(s) (arenas + shared matrix with the batch's one kept first factor +
  * factor workspace, and the exponent block of lpipm_set_scaling while scaling is on); 0 before any upload. */
 int lpipm_get_resident_bytes(const lpipm_ctx* ctx, uint64_t* bytes_out);
@@ -359,6 +375,19 @@ int lpipm_solve_batch_slack(lpipm_ctx* ctx, uint64_t count, const uint64_t* m, c
                             const double* c0 /* nullable */, const lpipm_opts* opts, double* const* x_slack_out,
                             void* x_dev_out, uint64_t row_stride, double* fun_out, uint64_t* iterations_out,
                             int32_t* status_out);
+/* A shard of independent tall inequality-form LPs (pure `ub`): member i is A_ub[i] (m_ub[i] x n[i] row-major, lda = n[i]),
+ * b_ub[i] (m_ub[i] doubles), c[i] (the n[i] structural costs), c0[i].  Output conventions of lpipm_solve_batch_slack: exactly
+ * one of x_slack_out and x_dev_out (+ row_stride) is non-null, member i's x has n[i] + m_ub[i] entries, slack values last, and
+ * row_stride is at least the largest of those lengths.  Members of equal (m_ub, n) are solved as lockstep chunks of
+ * lpipm_upload_lockstep_ub_tall, the others one at a time through lpipm_upload_ub_tall on the worker contexts; chunk sizes, the
+ * two-context upload pipeline, lpipm_set_batch_lockstep, lpipm_set_batch_concurrency and the treatment of a member's bad
+ * arguments, of m_ub[i] == 0 (LPIPM_UNCONSTRAINED in status_out[i]) and of runtime codes are those of lpipm_solve_batch.  Each
+ * member bit-identical to lpipm_upload_ub_tall + lpipm_solve, at every max_group. */
+int lpipm_solve_batch_ub_tall(lpipm_ctx* ctx, uint64_t count, const uint64_t* m_ub, const uint64_t* n,
+                              const double* const* A_ub, const double* const* b_ub, const double* const* c,
+                              const double* c0 /* nullable */, const lpipm_opts* opts, double* const* x_slack_out,
+                              void* x_dev_out, uint64_t row_stride, double* fun_out, uint64_t* iterations_out,
+                              int32_t* status_out);
 /* lpipm_solve_batch groups members of equal shape into lockstep batches: max_group -1 = auto (default: chunks
  * of up to 32 within the memory budget, the upload of one chunk overlapping the solve of the previous one), 0 = never, > 0 = largest group. */
 int lpipm_set_batch_lockstep(lpipm_ctx* ctx, int max_group);

@@ -234,6 +234,22 @@ def _batch_hints(problems):
 
 
 # ------------------------------------------------------------------------------ device context
+def _tall_members(problems):
+    """(A_ubs, b_ubs, cs, c0s) of Problems built from `ub` rows only -- the members of solve_batch(..., tall=True); anything
+    else is a ValueError, raised before a context is touched."""
+    members = []
+    for p in problems:
+        parts = getattr(p, "_parts", None)
+        if parts is None or parts[2].shape[0] != 0:
+            raise ValueError("tall=True needs Problems built from `ub` rows only")
+        A_ub, b_ub, _, _, c = parts
+        A_ub, b_ub, c = _f64(A_ub), _f64(b_ub), _f64(c)
+        if A_ub.ndim != 2 or b_ub.shape != (A_ub.shape[0],) or c.shape != (A_ub.shape[1],):
+            raise IncompatibleInputDimensions()
+        members.append((A_ub, b_ub, c, float(p.c0())))
+    return tuple(list(col) for col in zip(*members)) if members else ([], [], [], [])
+
+
 class Context:
     """One lpipm_ctx: device buffers + stream of one (thread, device).  `InteriorPoint.solve` keeps one
     per device; bench/tests use it directly to separate the one-time upload from the timed solve."""
@@ -454,6 +470,45 @@ class Context:
         head = (n, m_ub, _p(A_ub) if m_ub else None, n)
         return self._upload_members("lpipm_upload_lockstep_shared_ub_tall", head, bs, cs, c0s, m_ub, n + m_ub, n, None)
 
+    def upload_lockstep_ub_tall(self, A_ubs, bs, cs, c0s=None):
+        """`len(A_ubs)` independent tall inequality-form LPs of one shape, each with its own matrix
+        (lpipm_upload_lockstep_ub_tall): member i is min cs[i]'x st A_ubs[i] x <= bs[i], x >= 0.  Every member keeps its own
+        matrix, transpose and n x n reduced system on the device.  solve_lockstep returns x with n + m_ub entries, slack
+        values last -- every member bit-identical to Context.upload(Problem...ub().build(), tall=True) + solve_raw."""
+        A_ubs = [_f64(A) for A in A_ubs]; bs = [_f64(b) for b in bs]; cs = [_f64(c) for c in cs]
+        if (len(A_ubs) < 1 or len(bs) != len(A_ubs) or len(cs) != len(A_ubs) or (c0s is not None and len(c0s) != len(A_ubs))
+                or A_ubs[0].ndim != 2 or any(A.shape != A_ubs[0].shape for A in A_ubs)):
+            raise IncompatibleInputDimensions()
+        m_ub, n = A_ubs[0].shape
+        head = (n, m_ub, _ptrs(A_ubs), n)
+        return self._upload_members("lpipm_upload_lockstep_ub_tall", head, bs, cs, c0s, m_ub, n + m_ub, n, A_ubs)
+
+    def _solve_batch_tall(self, problems, opts, x_dev_ptr=None, row_stride=0):
+        """lpipm_solve_batch_ub_tall over pure-`ub` Problems: host rows (x_dev_ptr None) or the device block."""
+        As, bs, cs, c0s = _tall_members(problems)        # (ValueError before the context is touched)
+        K = len(As)
+        if K == 0:
+            return []
+        xs = [np.full(A.shape[0] + A.shape[1], np.nan) for A in As] if x_dev_ptr is None else None
+        m = (C.c_uint64 * K)(*[A.shape[0] for A in As]); n = (C.c_uint64 * K)(*[A.shape[1] for A in As])
+        c0 = (C.c_double * K)(*c0s)
+        fun = (C.c_double * K)(); its = (C.c_uint64 * K)(); st = (C.c_int32 * K)()
+        # (a member without rows has an empty matrix: any non-null pointer serves, its status is Unconstrained)
+        rc = _capi.lib().lpipm_solve_batch_ub_tall(self._h, K, m, n, _ptrs(As), _ptrs(bs), _ptrs(cs), c0, C.byref(opts),
+                                                   _ptrs(xs) if xs is not None else None,
+                                                   C.c_void_p(int(x_dev_ptr)) if x_dev_ptr is not None else None, int(row_stride),
+                                                   fun, its, st)
+        if rc != _capi.OK:
+            _raise_for(rc)
+        out = []
+        for i in range(K):
+            has_x = st[i] in (_capi.OK, _capi.ITERATION_LIMIT)
+            if xs is not None:
+                out.append((int(st[i]), xs[i] if has_x else None, fun[i] if has_x else None, int(its[i])))
+            else:
+                out.append((int(st[i]), fun[i] if has_x else None, int(its[i])))
+        return out
+
     def resident_bytes(self) -> int:
         """Device bytes held for the resident problem(s): arenas + shared matrix + factor workspace."""
         out = C.c_uint64(0)
@@ -487,10 +542,14 @@ class Context:
             _raise_for(rc)
         return [(int(st[i]), fun[i] if st[i] in (_capi.OK, _capi.ITERATION_LIMIT) else None, int(its[i])) for i in range(K)]
 
-    def solve_batch_device(self, problems, opts: "_capi.Opts", x_dev_ptr: int, row_stride: int):
+    def solve_batch_device(self, problems, opts: "_capi.Opts", x_dev_ptr: int, row_stride: int, tall: bool = False):
         """lpipm_solve_batch_device over [(A, b, c, c0), ...]: member i's x / tau goes to the device row
         x_dev_ptr + i * row_stride doubles.  A fifth tuple element is the member's n_slack hint (lpipm_solve_batch_slack).
+        tall=True: `problems` are Problems built from `ub` rows only (else ValueError), solved in the tall inequality form
+        (lpipm_solve_batch_ub_tall); member i's row has n + m_ub entries, slack values last.
         -> list of (status, fun | None, iterations)"""
+        if tall:
+            return Context._solve_batch_tall(self, problems, opts, x_dev_ptr, row_stride)
         K = len(problems)
         if K == 0:
             return []
@@ -513,10 +572,15 @@ class Context:
             _raise_for(rc)
         return [(int(st[i]), fun[i] if st[i] in (_capi.OK, _capi.ITERATION_LIMIT) else None, int(its[i])) for i in range(K)]
 
-    def solve_batch(self, problems, opts: "_capi.Opts"):
+    def solve_batch(self, problems, opts: "_capi.Opts", tall: bool = False):
         """lpipm_solve_batch over [(A, b, c, c0), ...] (any mix of shapes; equal shapes run as lockstep batches).
         A fifth tuple element is the member's n_slack hint (lpipm_solve_batch_slack): its slack block stays structural.
+        tall=True: `problems` are Problems built from `ub` rows only (else ValueError), solved in the tall inequality form
+        (lpipm_solve_batch_ub_tall: equal shapes as lockstep batches whose members own their matrices); x_slack has
+        n + m_ub entries, slack values last.
         -> list of (status, x_slack | None, fun | None, iterations)"""
+        if tall:
+            return Context._solve_batch_tall(self, problems, opts)
         K = len(problems)
         if K == 0:
             return []

@@ -64,6 +64,9 @@ SYMBOLS = {
     "lpipm_upload_lockstep_shared_slack": (C.c_int, [_vp, _u64, _u64, _u64, _dp, _u64, _dpp, _dpp, _dp, _u64]),
     "lpipm_upload_lockstep_shared_ub_eq": (C.c_int, [_vp, _u64, _u64, _u64, _dp, _u64, _u64, _dp, _u64, _dpp, _dpp, _dp]),
     "lpipm_upload_lockstep_shared_ub_tall": (C.c_int, [_vp, _u64, _u64, _u64, _dp, _u64, _dpp, _dpp, _dp]),
+    "lpipm_upload_lockstep_ub_tall": (C.c_int, [_vp, _u64, _u64, _u64, _dpp, _u64, _dpp, _dpp, _dp]),
+    "lpipm_solve_batch_ub_tall": (C.c_int, [_vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _dpp, _dpp, _dpp, _dp,
+                                            C.POINTER(Opts), _dpp, _vp, _u64, _dp, C.POINTER(_u64), C.POINTER(C.c_int32)]),
     "lpipm_solve_batch_slack": (C.c_int, [_vp, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), _dpp, _dpp, _dpp, _dp,
                                           C.POINTER(Opts), _dpp, _vp, _u64, _dp, C.POINTER(_u64), C.POINTER(C.c_int32)]),
     "lpipm_get_resident_bytes": (C.c_int, [_vp, C.POINTER(_u64)]),

@@ -27,13 +27,24 @@ def shard_range(count: int, world: int, rank: int) -> range:
 
 
 
-def solve_batch_sharded(problems, opts=None, ctx=None, group=None, device=None, solve_fn=None):
+def solve_batch_sharded(problems, opts=None, ctx=None, group=None, device=None, solve_fn=None, tall=False):
     """problems: sequence of (A, b, c, c0) or (A, b, c, c0, n_slack) -- every rank passes the same list (or at least its shard
     at the right indices).  Returns, on EVERY rank, a list of dicts {status, x_slack, fun, iterations}
     in problem order.  `solve_fn(A, b, c, c0, None) -> (status, x | None, fun, iterations)` replaces the
-    library call in the CPU-rank tests."""
+    library call in the CPU-rank tests.
+    tall=True: problems are lp_amd.Problems built from `ub` rows only (else ValueError, before any device or rank is
+    touched); each shard goes through Context.solve_batch_device(..., tall=True) and x_slack has n + m_ub entries."""
     import torch
     import torch.distributed as dist
+
+    if tall:
+        import lp_amd
+        if solve_fn is not None:
+            raise ValueError("tall=True runs the library call: it takes no solve_fn")
+        A_ubs = lp_amd._tall_members(problems)[0]
+        tall_problems = problems
+        # the rest of this function only reads a member's length of x, from its c: n + m_ub entries in the tall form
+        problems = [(None, None, np.broadcast_to(0.0, (A.shape[0] + A.shape[1],)), 0.0) for A in A_ubs]
 
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -51,7 +62,10 @@ def solve_batch_sharded(problems, opts=None, ctx=None, group=None, device=None, 
         device = device or torch.device("cuda", ctx.device)
         packed = torch.zeros((rows, n_max + 3), dtype=torch.float64, device=device)
         torch.cuda.synchronize(device)                # the zero fill runs on torch's stream, the solver on its own
-        res = ctx.solve_batch_device([problems[i] for i in mine], opts, packed.data_ptr(), n_max + 3)
+        if tall:
+            res = ctx.solve_batch_device([tall_problems[i] for i in mine], opts, packed.data_ptr(), n_max + 3, tall=True)
+        else:
+            res = ctx.solve_batch_device([problems[i] for i in mine], opts, packed.data_ptr(), n_max + 3)
         for slot, (rc, fun, it) in enumerate(res):
             meta[slot] = (fun if fun is not None else float("nan"), float(it), float(rc))
         packed[:, n_max:] = torch.from_numpy(meta).to(device)       # 3 scalars per LP; x rows never left the device

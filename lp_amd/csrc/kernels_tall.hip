@@ -15,7 +15,7 @@
 // cancels catastrophically on the slack block.  Everything downstream (d_tau, Delta, ratio test, step,
 // residuals, indicators) is the dense path's and sees p, q, u, v where it sees them there.
 // Reductions are fixed-order (kernels_vec.hip's two stages, the same slots).  The vector kernels run with gridDim.z = the LPs
-// of the launch (a single tall LP, or the members of lpipm_upload_lockstep_shared_ub_tall): tbatch moves the VecArgs, the
+// of the launch (a single tall LP, or the members of lpipm_upload_lockstep_shared_ub_tall / lpipm_upload_lockstep_ub_tall): tbatch moves the VecArgs, the
 // TallArgs and the right-hand sides to the member and skips a finished one, as vbatch does on the dense path; a member's
 // arithmetic and reduction order are those of the single LP.  The kernels of the speculatively enqueued head test the done
 // word.
@@ -27,11 +27,14 @@ namespace lpipm {
 // ---------------------------------------------------------------- resident transpose
 // Xt[j][i] = X[i][j], i < m, j < nx, through a 32 x 32 LDS tile (rows padded by one double: the transposed reads walk a
 // column of the tile).  Both sides move whole 256-byte row segments.  Xt is zeroed beforehand: nothing outside the m x nx
-// block is written.  grid (column tiles of X, row tiles of X), 32 x 8 threads.
+// block is written.  grid (column tiles of X, row tiles of X, members), 32 x 8 threads: member z of a batch whose members
+// own their matrices has its X and its Xt `stride` bytes * z further, as everything else in its arena.
 constexpr int TT = 32;
 __global__ __launch_bounds__(256) void k_tall_transpose(const double* __restrict__ X, long long ldx, int m, int nx,
-                                                        double* __restrict__ Xt, long long ldt) {
+                                                        double* __restrict__ Xt, long long ldt, long long stride) {
     __shared__ double tile[TT][TT + 1];
+    X = (const double*)((const char*)X + (long long)blockIdx.z * stride);
+    Xt = (double*)((char*)Xt + (long long)blockIdx.z * stride);
     const int tx = threadIdx.x, ty = threadIdx.y;
     const long long i0 = (long long)blockIdx.y * TT;
     const int j0 = blockIdx.x * TT;
@@ -47,11 +50,12 @@ __global__ __launch_bounds__(256) void k_tall_transpose(const double* __restrict
         if (j < nx && i < m) Xt[(long long)j * ldt + i] = tile[tx][r];
     }
 }
-hipError_t tall_transpose(const double* X, int64_t ldx, int m, int nx, double* Xt, int64_t ldt, hipStream_t st) {
-    if (m <= 0 || nx <= 0) return hipSuccess;
-    const dim3 grid((nx + TT - 1) / TT, (m + TT - 1) / TT);
-    if (grid.y > 65535u) return hipErrorInvalidValue;      // m <= 2^20: 32768 row tiles
-    hipLaunchKernelGGL(k_tall_transpose, grid, dim3(TT, 8), 0, st, X, (long long)ldx, m, nx, Xt, (long long)ldt);
+hipError_t tall_transpose(const double* X, int64_t ldx, int m, int nx, double* Xt, int64_t ldt, hipStream_t st, const Batch& bt) {
+    if (m <= 0 || nx <= 0 || bt.count <= 0) return hipSuccess;
+    const dim3 grid((nx + TT - 1) / TT, (m + TT - 1) / TT, bt.count);
+    if (grid.y > 65535u || grid.z > 65535u) return hipErrorInvalidValue;      // m <= 2^20: 32768 row tiles; at most 4096 members
+    hipLaunchKernelGGL(k_tall_transpose, grid, dim3(TT, 8), 0, st, X, (long long)ldx, m, nx, Xt, (long long)ldt,
+                       bt.count > 1 ? bt.stride : 0LL);
     return hipGetLastError();
 }
 

@@ -111,10 +111,13 @@ struct Problem {
     // it from Xt, and nothing in the arena is m x m.  The row-split slabs of A^T.v are npa wide (tv.npa), not np.
     // A batch of tall LPs over ONE X (lpipm_upload_lockstep_shared_ub_tall: tall && shared_a) keeps X and Xt once, in a_shared;
     // every member's arena then holds its vectors, W_s, E_x, T, G, U_s, its own K with its factor plan's inverses and its slabs.
+    // A batch whose members own their matrices (lpipm_upload_lockstep_ub_tall: tall && !shared_a, B arenas) has the single
+    // tall LP's arena per member, X_i and Xt_i included.
     bool tall = false;
     double* Xt = nullptr;        // nxp x mk, row-major, zero padded: X^T of the resident (scaled) X
     TallArgs tv{};
     bool from_parts = false;     // uploaded as ub / eq blocks (lpipm_upload_ub_eq): b and c are not in the caller's slack form
+    bool owned_tall = false;     // lpipm_upload_lockstep_ub_tall: a tall batch (of any count) whose members own X_i, Xt_i and K
     // Equilibration (lpipm_set_scaling): the exponents and the maxima slabs, in an allocation of their own that exists only
     // for a problem uploaded with scaling on.  scale_passes > 0: the resident A, b and c are the scaled ones.
     int scale_passes = 0;
@@ -478,7 +481,8 @@ static int merge_edge_for(int) {
 // The matrix comes one per member (A[i], lda), as the batch's one matrix (shared: A[0]), or as two blocks of
 // nx = n - n_slack columns (parts: m_ub rows of A_ub, then m - m_ub rows of A_eq; n_slack == m_ub, true by construction, and c
 // holds only the nx structural costs).  Parts of a single LP carry its b, split the same way (b is null); parts of a shared
-// batch are its one matrix and b[i] = [b_ub_i; b_eq_i] comes per member.
+// batch are its one matrix and b[i] = [b_ub_i; b_eq_i] comes per member.  A tall batch whose members own their matrices
+// (owned) is in parts too -- no slack column is stored, c holds the structural costs -- with member i's rows in A[i].
 struct UploadParts { uint64_t m_ub = 0; const double* A_ub = nullptr; uint64_t lda_ub = 0; const double* b_ub = nullptr;
                      const double* A_eq = nullptr; uint64_t lda_eq = 0; const double* b_eq = nullptr; };
 struct Upload {
@@ -491,6 +495,7 @@ struct Upload {
     const double* c0 = nullptr;          // nullable: all zero
     bool shared = false;                 // one matrix for all `count` LPs
     bool tall = false;                   // parts with `ub` rows only: the tall inequality form, of the LP or of every member over one X
+    bool owned = false;                  // tall, a batch whose members own their matrices: X_i = A[i] (lda), b[i] per member; parts holds m_ub only
     bool hint_verified = false;          // the caller has checked the hint on these very matrices (batch_impl): it is not repeated
     bool keep_ok = true;                 // false: solved once (lpipm_solve_batch) or never through the kept factor (column split)
 };
@@ -509,15 +514,17 @@ static int check_upload(const lpipm_ctx* c, const Upload& u) {
     } else {
         const UploadParts& q = *u.parts;
         const uint64_t nx = u.n - u.n_slack, m_eq = u.m - q.m_ub;
-        if (u.shared && (!count_ok || !u.b || !u.c)) return LPIPM_ERR_BAD_ARGUMENT;
+        const bool batch = u.shared || u.owned;
+        if (batch && (!count_ok || !u.b || !u.c || (u.owned && !u.A))) return LPIPM_ERR_BAD_ARGUMENT;
         if (u.m == 0) return LPIPM_UNCONSTRAINED;  // linear_program.rs:134-136
-        if ((!u.shared && !u.c[0]) || nx == 0) return LPIPM_ERR_BAD_ARGUMENT;
-        if (q.m_ub && (!q.A_ub || q.lda_ub < nx || (!u.shared && !q.b_ub))) return LPIPM_ERR_BAD_ARGUMENT;
+        if ((!batch && !u.c[0]) || nx == 0) return LPIPM_ERR_BAD_ARGUMENT;
+        if (u.owned) { if (u.lda < nx) return LPIPM_ERR_BAD_ARGUMENT; }
+        else if (q.m_ub && (!q.A_ub || q.lda_ub < nx || (!u.shared && !q.b_ub))) return LPIPM_ERR_BAD_ARGUMENT;
         if (m_eq && (!q.A_eq || q.lda_eq < nx || (!u.shared && !q.b_eq))) return LPIPM_ERR_BAD_ARGUMENT;
         if (!c) return LPIPM_ERR_BAD_ARGUMENT;
         if (u.tall && (c->world > 1 || c->refine > 0)) return LPIPM_ERR_UNSUPPORTED;   // a column-split context; the refined solves
         for (uint64_t i = 0; i < u.count; ++i)
-            if (!u.c[i] || (u.b && !u.b[i])) return LPIPM_ERR_BAD_ARGUMENT;
+            if (!u.c[i] || (u.b && !u.b[i]) || (u.owned && !u.A[i])) return LPIPM_ERR_BAD_ARGUMENT;
     }
     return u.m > (1u << 20) || u.n > (1u << 24) ? LPIPM_ERR_BAD_ARGUMENT : LPIPM_OK;
 }
@@ -558,10 +565,11 @@ static void set_geometry(Problem& p, const Geometry& g) {
 // padded rows of X.  A tall batch: every member's K must have the bits the single LP's has.  The units kernel gives them
 // whatever the count; the round-2 kernel (which a single LP of a few tiles with several chunks takes) only with the single
 // LP's own workgroup count once the contraction is longer than 4096 (round2_unit): the batch then runs that very plan.
+// One rule for both tall batches, over one X or with a matrix per member.
 static AdatPlan adat_plan_of(const Geometry& g, int num_cu, int world, int units_env) {
     if (!g.tall) return plan_adat(g.mp, g.npa, g.B, num_cu, world, units_env);
     const AdatPlan single = plan_adat(g.nxp, g.mk, 1, num_cu, 1, units_env);
-    return g.shared && single.units ? plan_adat(g.nxp, g.mk, g.B, num_cu, 1, units_env) : single;
+    return single.units ? plan_adat(g.nxp, g.mk, g.B, num_cu, 1, units_env) : single;     // (B == 1: `single` either way)
 }
 
 // Device state is laid out by functions that take p's geometry and an Arena: one pass over a measuring arena sizes an
@@ -613,7 +621,8 @@ static int layout_first_factor(Problem& p, const FactorPlan& plan, FactorPlan& p
 // The arena of one LP; every LP of a lockstep batch gets the same layout, `bstride` bytes after the previous LP's.
 // refine: whether the context refines its solves.  Tall (Problem::tall): the vectors of the dense layout, X and its transpose, the nxp x nxp matrix K with its factor plan, and
 // the work vectors of the reduced solve.  Nothing grows as m^2: no M, M0 or kept first factor.
-// A member of a shared batch (p.shared_a) has the same arena without A (tall: X and Xt): layout_shared.
+// A member of a shared batch (p.shared_a) has the same arena without A (tall: X and Xt): layout_shared.  A member of a tall
+// batch that owns its matrix has the single tall LP's arena.
 static int layout_problem(Problem& p, FactorPlan& plan, FactorPlan& plan1, const AdatPlan& ap, int refine, Arena& ar,
                           bool build, hipStream_t st) {
     TallArgs& t = p.tv;
@@ -720,9 +729,9 @@ static int copy_in(lpipm_ctx* c, const Upload& u, const double* c0v) {
     };
     auto vec = [&](const void* dst, const double* src, uint64_t count) { return hipMemcpyAsync((void*)dst, src, count * D, hipMemcpyHostToDevice, st); };
     // A: as parts -- rows of A_ub, then rows of A_eq, into the single LP's arena or the batch's one matrix -- or shared, here;
-    //    per member, with the member's vectors below.
+    //    per member (dense, or the owned tall batch's X_i), with the member's vectors below.
     // b: per member below, or in parts of a single LP, each part behind its rows.
-    if (u.parts) {
+    if (u.parts && !u.owned) {
         const UploadParts& q = *u.parts;
         const uint64_t m_ub = q.m_ub, m_eq = u.m - m_ub;
         if (m_ub) {
@@ -738,7 +747,7 @@ static int copy_in(lpipm_ctx* c, const Upload& u, const double* c0v) {
     const uint64_t nc = u.parts ? nx : u.n;
     for (uint64_t i = 0; i < u.count; ++i) {
         const size_t off = (size_t)i * p.bstride;
-        if (!u.shared && !u.parts) LP_HIP(rows((double*)((char*)p.A + off), u.A[i], u.lda, u.m));
+        if (!u.shared && (!u.parts || u.owned)) LP_HIP(rows((double*)((char*)p.A + off), u.A[i], u.lda, u.m));
         if (u.b) LP_HIP(vec((const char*)p.va.b + off, u.b[i], u.m));
         LP_HIP(vec((const char*)p.va.c + off, u.c[i], nc));
         LP_HIP(vec((const char*)(p.va.S + S_C0) + off, &c0v[i], 1));
@@ -769,7 +778,7 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
     LP_TRY(scale_setup(c, g.mp, g.np, g.npa, u.shared ? 1 : count));
     p.m = u.m; p.n = u.n; p.ns = (int)n_slack; p.nx = (int)nx;
     if (u.tall) p.tv.nx = (int)nx;            // (the padded geometry may be shared by several nx)
-    p.from_parts = u.parts.has_value();
+    p.from_parts = u.parts.has_value(); p.owned_tall = u.owned;
     p.va.n = (int)u.n; p.va.m = (int)u.m; p.va.n_total = (long long)u.n; p.va.gs = nullptr; c->colsplit = false;   // lpipm_upload_nsplit overrides
     // A single LP's loop ends on the host, so its kernels need not test the done word (one dependent load
     // less at the start of ~100 short kernels) -- except the head of an iteration, which is enqueued before
@@ -789,7 +798,8 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
         LP_HIP(launch_scale_vectors(p.sc, (double*)p.va.b, (int)u.m, (double*)p.va.c, (int)u.n, st, members));
     }
     // tall: the resident transpose, from the X the solves see (behind the equilibration: both copies carry its exponents)
-    if (u.tall) LP_HIP(tall_transpose(p.A, g.npa, (int)u.m, (int)nx, p.Xt, g.mk, st));
+    //       (every member's own, in one launch, when the members own their matrices)
+    if (u.tall) LP_HIP(tall_transpose(p.A, g.npa, (int)u.m, (int)nx, p.Xt, g.mk, st, u.shared ? Batch{} : Batch{count, (long long)p.bstride, nullptr, 0}));
     LP_HIP(hipStreamSynchronize(st));   // the caller's arrays, c0v and onesv are free again from here
     p.has_problem = p.adat.counters_dirty = true;
     bind_status_pinned(c, true);
@@ -845,6 +855,17 @@ extern "C" int lpipm_upload_lockstep_shared_ub_tall(lpipm_ctx* c, uint64_t count
     return upload_impl(c, Upload{.count = count, .m = m_ub, .n = n + m_ub, .n_slack = m_ub,
                                  .parts = UploadParts{.m_ub = m_ub, .A_ub = A_ub, .lda_ub = lda_ub}, .b = b, .c = cc, .c0 = c0, .shared = true,
                                  .tall = true, .keep_ok = false});
+}
+// The request of a tall batch whose members own their matrices (A_ub[i]: m_ub x n, lda_ub).
+static Upload owned_tall_request(uint64_t count, uint64_t n, uint64_t m_ub, const double* const* A_ub, uint64_t lda_ub,
+                                 const double* const* b, const double* const* cc, const double* c0) {
+    return Upload{.count = count, .m = m_ub, .n = n + m_ub, .n_slack = m_ub, .A = A_ub, .lda = lda_ub,
+                  .parts = UploadParts{.m_ub = m_ub}, .b = b, .c = cc, .c0 = c0, .tall = true, .owned = true, .keep_ok = false};
+}
+extern "C" int lpipm_upload_lockstep_ub_tall(lpipm_ctx* c, uint64_t count, uint64_t n, uint64_t m_ub, const double* const* A_ub,
+                                             uint64_t lda_ub, const double* const* b, const double* const* cc, const double* c0) {
+    if (!c) return LPIPM_ERR_BAD_ARGUMENT;       // (as the shared tall batch: a null context before the shape)
+    return upload_impl(c, owned_tall_request(count, n, m_ub, A_ub, lda_ub, b, cc, c0));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -928,7 +949,7 @@ static hipError_t run_tall_normal(lpipm_ctx* c, const Batch& bt) {
     const TallArgs& t = c->p.tv;
     AdatLaunch a{};
     a.A = c->p.Xt; a.lda = t.mk; a.dinv = t.Ws; a.M = c->p.M; a.ldm = t.nxp; a.M2 = nullptr;
-    a.K = t.mk; a.diag_pad_from = t.nx; a.batch = bt; a.shared_a = c->p.shared_a;    // (a batch: one Xt, every member's own W_s)
+    a.K = t.mk; a.diag_pad_from = t.nx; a.batch = bt; a.shared_a = c->p.shared_a;    // (a batch: the one Xt or every member's own, and every member's own W_s)
     hipError_t e = launch_adat(c->ap, c->p.adat, a, false, c->rs.st, nullptr);
     if (e != hipSuccess) return e;
     return launch_slack_diag(t.nx, 0, t.Ex, c->p.M, t.nxp, c->rs.st, bt);
@@ -1614,9 +1635,11 @@ extern "C" int lpipm_solve_lockstep_device(lpipm_ctx* c, const lpipm_opts* o, vo
 
 // Bytes one member of a lockstep batch of 32 of this shape occupies: the real layout (a measuring pass of layout_problem over
 // its geometry), not a formula that drifts from it.  No kept first factor: a chunk is uploaded, solved once and replaced.
-// n_slack: the member's (verified) structural hint -- its slack columns are not resident.
-static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, uint64_t m, uint64_t n, uint64_t n_slack) {
-    const Geometry g = geometry_of(Upload{.count = 32, .m = m, .n = n, .keep_ok = false}, n_slack, c->first_cache, c->refine);
+// n_slack: the member's (verified) structural hint -- its slack columns are not resident.  tall: the member is m x n in the
+// tall inequality form (n structural columns, every slack column implied).
+static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, uint64_t m, uint64_t n, uint64_t n_slack, bool tall) {
+    const Geometry g = tall ? geometry_of(Upload{.count = 32, .m = m, .n = n + m, .tall = true, .keep_ok = false}, m, c->first_cache, c->refine)
+                            : geometry_of(Upload{.count = 32, .m = m, .n = n, .keep_ok = false}, n_slack, c->first_cache, c->refine);
     Problem t;
     set_geometry(t, g);
     FactorPlan fp, fp1;
@@ -1636,7 +1659,10 @@ static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, uint64_t m, uint64_t n, 
 // Every member's result depends only on its own inputs.
 // n_slack (nullable = all 0): member i's structural hint (lpipm_upload_slack).  Each is verified here first; members are
 // grouped by the hint that holds as well as by shape, and both upload paths pass it on.
-static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uint64_t* n, const uint64_t* n_slack,
+// tall (lpipm_solve_batch_ub_tall): the members are pure-`ub` LPs in the tall inequality form -- A[i] is m[i] x n[i] with
+// lda = n[i], b[i] has m[i] entries, c[i] the n[i] structural costs, x n[i] + m[i] entries, and there is no hint.  A group is
+// then a tall batch whose members own their matrices, a single member a tall upload; everything else is the same body.
+static int batch_impl(lpipm_ctx* c, bool tall, uint64_t count, const uint64_t* m, const uint64_t* n, const uint64_t* n_slack,
                       const double* const* A, const double* const* b, const double* const* cc,
                       const double* c0, const lpipm_opts* o, const XOut& xo,
                       double* fun_out, uint64_t* iterations_out, int32_t* status_out) {
@@ -1670,7 +1696,7 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             size_t free_b = 0, total_b = 0;
             LP_HIP(hipMemGetInfo(&free_b, &total_b));
             free_b += c->p.arena_bytes;                // the current arena is released before the next one is made
-            const double per_lp = (double)lockstep_bytes_per_lp(c, m[i], n[i], ns[i]);
+            const double per_lp = (double)lockstep_bytes_per_lp(c, m[i], n[i], ns[i], tall);
             size_t chunk;
             if (c->lockstep_max > 0) chunk = (size_t)c->lockstep_max;
             else if (grp.size() > 32) chunk = 32;
@@ -1710,6 +1736,7 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             auto upload_chunk = [&](lpipm_ctx* w, const Chunk& ch) -> int {
                 (void)hipSetDevice(w->device);
                 w->scaling = c->scaling;
+                if (tall) return upload_impl(w, owned_tall_request(ch.g, n[i], m[i], ch.A.data(), n[i], ch.b.data(), ch.c.data(), ch.c0.data()));
                 return upload_impl(w, Upload{.count = ch.g, .m = m[i], .n = n[i], .n_slack = ns[i], .A = ch.A.data(), .lda = n[i], .b = ch.b.data(),
                                              .c = ch.c.data(), .c0 = ch.c0.data(), .hint_verified = true, .keep_ok = false});
             };
@@ -1772,8 +1799,9 @@ static int batch_impl(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uin
             if (k >= rest.size() || fatal.load() != LPIPM_OK) break;
             const uint64_t i = rest[k];
             const double c0i = c0 ? c0[i] : 0.0;
-            int rc = upload_impl(w, Upload{.m = m[i], .n = n[i], .n_slack = ns[i], .A = &A[i], .lda = n[i], .b = &b[i], .c = &cc[i],
-                                           .c0 = &c0i, .hint_verified = true, .keep_ok = false});
+            int rc = tall ? lpipm_upload_ub_tall(w, n[i], m[i], A[i], n[i], b[i], cc[i], c0i)
+                          : upload_impl(w, Upload{.m = m[i], .n = n[i], .n_slack = ns[i], .A = &A[i], .lda = n[i], .b = &b[i], .c = &cc[i],
+                                                  .c0 = &c0i, .hint_verified = true, .keep_ok = false});
             double fun = NAN;
             uint64_t it = 0;
             if (rc == LPIPM_OK)
@@ -1797,7 +1825,7 @@ extern "C" int lpipm_solve_batch(lpipm_ctx* c, uint64_t count, const uint64_t* m
                                  const double* c0, const lpipm_opts* o, double* const* x_slack_out,
                                  double* fun_out, uint64_t* iterations_out, int32_t* status_out) {
     XOut xo; xo.host = x_slack_out;
-    return batch_impl(c, count, m, n, nullptr, A, b, cc, c0, o, xo, fun_out, iterations_out, status_out);
+    return batch_impl(c, false, count, m, n, nullptr, A, b, cc, c0, o, xo, fun_out, iterations_out, status_out);
 }
 extern "C" int lpipm_solve_batch_device(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uint64_t* n,
                                         const double* const* A, const double* const* b, const double* const* cc,
@@ -1807,7 +1835,7 @@ extern "C" int lpipm_solve_batch_device(lpipm_ctx* c, uint64_t count, const uint
     for (uint64_t i = 0; i < count && n; ++i)
         if (n[i] > row_stride) return LPIPM_ERR_BAD_ARGUMENT;
     XOut xo; xo.dev = (char*)x_dev_out; xo.stride_bytes = row_stride * sizeof(double);
-    return batch_impl(c, count, m, n, nullptr, A, b, cc, c0, o, xo, fun_out, iterations_out, status_out);
+    return batch_impl(c, false, count, m, n, nullptr, A, b, cc, c0, o, xo, fun_out, iterations_out, status_out);
 }
 
 extern "C" int lpipm_solve_batch_slack(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uint64_t* n, const uint64_t* n_slack,
@@ -1822,7 +1850,22 @@ extern "C" int lpipm_solve_batch_slack(lpipm_ctx* c, uint64_t count, const uint6
             if (n[i] > row_stride) return LPIPM_ERR_BAD_ARGUMENT;
         xo.dev = (char*)x_dev_out; xo.stride_bytes = row_stride * sizeof(double);
     }
-    return batch_impl(c, count, m, n, n_slack, A, b, cc, c0, o, xo, fun_out, iterations_out, status_out);
+    return batch_impl(c, false, count, m, n, n_slack, A, b, cc, c0, o, xo, fun_out, iterations_out, status_out);
+}
+
+extern "C" int lpipm_solve_batch_ub_tall(lpipm_ctx* c, uint64_t count, const uint64_t* m_ub, const uint64_t* n,
+                                         const double* const* A_ub, const double* const* b_ub, const double* const* cc,
+                                         const double* c0, const lpipm_opts* o, double* const* x_slack_out, void* x_dev_out,
+                                         uint64_t row_stride, double* fun_out, uint64_t* iterations_out, int32_t* status_out) {
+    if ((x_slack_out != nullptr) == (x_dev_out != nullptr)) return LPIPM_ERR_BAD_ARGUMENT;
+    XOut xo;
+    if (x_slack_out) xo.host = x_slack_out;
+    else {
+        for (uint64_t i = 0; i < count && n && m_ub; ++i)
+            if (n[i] + m_ub[i] > row_stride) return LPIPM_ERR_BAD_ARGUMENT;
+        xo.dev = (char*)x_dev_out; xo.stride_bytes = row_stride * sizeof(double);
+    }
+    return batch_impl(c, true, count, m_ub, n, nullptr, A_ub, b_ub, cc, c0, o, xo, fun_out, iterations_out, status_out);
 }
 
 extern "C" int lpipm_set_batch_lockstep(lpipm_ctx* c, int max_group) {
@@ -1940,7 +1983,7 @@ static int update_lockstep_impl(lpipm_ctx* c, uint64_t count, const double* cons
                                 const double* b_dev, uint64_t ldb, const double* c_dev, uint64_t ldc, const double* c0) {
     if (!c) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
-    if (c->colsplit || (c->p.from_parts && !c->p.shared_a)) return LPIPM_ERR_UNSUPPORTED;
+    if (c->colsplit || (c->p.from_parts && !c->p.shared_a && !c->p.owned_tall)) return LPIPM_ERR_UNSUPPORTED;
     const bool has_b = host ? b != nullptr : b_dev != nullptr, has_c = host ? cc != nullptr : c_dev != nullptr;
     if ((!has_b && !has_c) || count != (uint64_t)c->p.B) return LPIPM_ERR_BAD_ARGUMENT;
     const size_t B = (size_t)c->p.B, m = (size_t)c->p.m;
@@ -2037,7 +2080,7 @@ static int tall_entry_iterate(lpipm_ctx* c, const double* dinv) {
 extern "C" int lpipm_k_tall_normal(lpipm_ctx* c, const double* dinv, double* K_out) {
     if (!c || !dinv || !K_out) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
-    if (!c->p.tall || c->p.shared_a) return LPIPM_ERR_UNSUPPORTED;     // (a single tall upload, not a batch)
+    if (!c->p.tall || c->p.shared_a || c->p.owned_tall) return LPIPM_ERR_UNSUPPORTED;     // (a single tall upload, not a batch)
     LP_HIP(hipSetDevice(c->device));
     vec_blind_start(c->p.va, c->rs.st);                       // clears done / flags; the iterate is overwritten next
     LP_TRY(tall_entry_iterate(c, dinv));
@@ -2053,7 +2096,7 @@ extern "C" int lpipm_k_tall_sym_solve(lpipm_ctx* c, const double* dinv, int nrhs
                                       double* U_out, double* V_out, int32_t* info_out) {
     if (!c || !dinv || !R1 || !R2 || !U_out || !V_out || (nrhs != 1 && nrhs != 2)) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
-    if (!c->p.tall || c->p.shared_a) return LPIPM_ERR_UNSUPPORTED;     // (a single tall upload, not a batch)
+    if (!c->p.tall || c->p.shared_a || c->p.owned_tall) return LPIPM_ERR_UNSUPPORTED;     // (a single tall upload, not a batch)
     LP_HIP(hipSetDevice(c->device));
     hipStream_t st = c->rs.st;
     VecArgs& v = c->p.va;
@@ -2312,7 +2355,7 @@ extern "C" int lpipm_k_iteration(lpipm_ctx* c, const lpipm_opts* o, int ip, doub
                                  int32_t* info_out) {
     if (!c || !o || !x || !y || !z || !tau || !kappa || !d_x || !d_y || !d_z || !d_tk || !alpha_out) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
-    if (c->p.B != 1 || (c->p.tall && c->p.shared_a)) return LPIPM_ERR_UNSUPPORTED;      // one LP, not a batch (of any count)
+    if (c->p.B != 1 || (c->p.tall && (c->p.shared_a || c->p.owned_tall))) return LPIPM_ERR_UNSUPPORTED;      // one LP, not a batch (of any count)
     // (a column-split context: x, z, d_x, d_z are this rank's slices, everything else is replicated, and every rank must
     //  call together -- enqueue_residuals / enqueue_iteration contain the cross-rank reductions)
     LP_HIP(hipSetDevice(c->device));

@@ -122,8 +122,10 @@ struct TallArgs {
 // The right-hand sides a tall launch is handed: (r1a, r2a) and (r1b, r2b), r1 n-sized, r2 m-sized, LP 0's addresses in the
 // arena (or, for the single LP of the kernel entries, any device buffer); the unused ones are null.
 struct TallRhs { const double *r1a = nullptr, *r2a = nullptr, *r1b = nullptr, *r2b = nullptr; };
-// Xt (nxp x mk, zeroed beforehand) = X^T for the m x nx block of the resident X (lda = npa)
-hipError_t tall_transpose(const double* X, int64_t ldx, int m, int nx, double* Xt, int64_t ldt, hipStream_t st);
+// Xt (nxp x mk, zeroed beforehand) = X^T for the m x nx block of the resident X (lda = npa); bt: the members of a batch
+// that own their matrices (X and Xt are member 0's, the others bt.stride bytes apart), one launch for all
+hipError_t tall_transpose(const double* X, int64_t ldx, int m, int nx, double* Xt, int64_t ldt, hipStream_t st,
+                          const Batch& bt = Batch{});
 // W_s and E_x from the iterate (with_scales), and t for nrhs (0|1|2) right-hand sides (r1a, r2a), (r1b, r2b): r1 n-sized, r2 m-sized
 void tall_setup(const VecArgs& a, const TallArgs& t, bool with_scales, int nrhs, const double* r1a, const double* r2a,
                 const double* r1b, const double* r2b, hipStream_t st);
