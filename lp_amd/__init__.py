@@ -250,6 +250,62 @@ def _tall_members(problems):
     return tuple(list(col) for col in zip(*members)) if members else ([], [], [], [])
 
 
+def has_x(code) -> bool:
+    """Whether a solve that ended with this status has a solution: x, and with it fun (mod.rs:231, :237-239)."""
+    return code in (_capi.OK, _capi.ITERATION_LIMIT)
+
+
+def _members_out(K, xs=None):
+    """-> ((fun, iterations, status) C arrays of K members, unpack).  unpack(rc) raises for a failed call and else gives per
+    member (status, x_slack | None, fun | None, iterations) -- x from the host rows xs -- or, without host rows,
+    (status, fun | None, iterations)."""
+    fun, its, st = (C.c_double * K)(), (C.c_uint64 * K)(), (C.c_int32 * K)()
+
+    def unpack(rc):
+        if rc != _capi.OK:
+            _raise_for(rc)
+        rows = zip(st, fun, its, [has_x(s) for s in st])              # (one pass over each C array: this sits in timed loops)
+        if xs is None:
+            return [(s, f if ok else None, t) for s, f, t, ok in rows]
+        return [(s, x if ok else None, f if ok else None, t) for (s, f, t, ok), x in zip(rows, xs)]
+    return (fun, its, st), unpack
+
+
+def _solve_batch(ctx, problems, opts, tall, x_dev_ptr=None, row_stride=0):
+    """One call of lpipm_solve_batch / _device / _slack / _ub_tall: host rows (x_dev_ptr None) or the device block.  The members
+    are validated before the context is touched."""
+    if tall:
+        As, bs, cs, c0s = _tall_members(problems)
+        ns = None
+    else:
+        As = [_f64(p[0]) for p in problems]; bs = [_f64(p[1]) for p in problems]; cs = [_f64(p[2]) for p in problems]
+        for A, b, c in zip(As, bs, cs):
+            if A.ndim != 2 or b.shape != (A.shape[0],) or c.shape != (A.shape[1],):
+                raise IncompatibleInputDimensions()
+        c0s = [float(p[3]) if len(p) > 3 else 0.0 for p in problems]
+        ns = _batch_hints(problems)
+    K = len(As)
+    if K == 0:
+        return []
+    # a tall member's x has its m_ub slack values behind the n structural ones
+    xs = [np.full(A.shape[1] + (A.shape[0] if tall else 0), np.nan) for A in As] if x_dev_ptr is None else None
+    x_host, x_dev = (_ptrs(xs), None) if xs is not None else (None, C.c_void_p(int(x_dev_ptr)))
+    m = (C.c_uint64 * K)(*[A.shape[0] for A in As]); n = (C.c_uint64 * K)(*[A.shape[1] for A in As])
+    # (a member without rows has an empty matrix: any non-null pointer serves, its status is Unconstrained)
+    members = (_ptrs(As), _ptrs(bs), _ptrs(cs), (C.c_double * K)(*c0s), C.byref(opts))
+    out, unpack = _members_out(K, xs)
+    L = _capi.lib()
+    if tall:
+        rc = L.lpipm_solve_batch_ub_tall(ctx._h, K, m, n, *members, x_host, x_dev, int(row_stride), *out)
+    elif ns is not None:
+        rc = L.lpipm_solve_batch_slack(ctx._h, K, m, n, ns, *members, x_host, x_dev, int(row_stride), *out)
+    elif xs is not None:
+        rc = L.lpipm_solve_batch(ctx._h, K, m, n, *members, x_host, *out)
+    else:
+        rc = L.lpipm_solve_batch_device(ctx._h, K, m, n, *members, x_dev, int(row_stride), *out)
+    return unpack(rc)
+
+
 class Context:
     """One lpipm_ctx: device buffers + stream of one (thread, device).  `InteriorPoint.solve` keeps one
     per device; bench/tests use it directly to separate the one-time upload from the timed solve."""
@@ -483,32 +539,6 @@ class Context:
         head = (n, m_ub, _ptrs(A_ubs), n)
         return self._upload_members("lpipm_upload_lockstep_ub_tall", head, bs, cs, c0s, m_ub, n + m_ub, n, A_ubs)
 
-    def _solve_batch_tall(self, problems, opts, x_dev_ptr=None, row_stride=0):
-        """lpipm_solve_batch_ub_tall over pure-`ub` Problems: host rows (x_dev_ptr None) or the device block."""
-        As, bs, cs, c0s = _tall_members(problems)        # (ValueError before the context is touched)
-        K = len(As)
-        if K == 0:
-            return []
-        xs = [np.full(A.shape[0] + A.shape[1], np.nan) for A in As] if x_dev_ptr is None else None
-        m = (C.c_uint64 * K)(*[A.shape[0] for A in As]); n = (C.c_uint64 * K)(*[A.shape[1] for A in As])
-        c0 = (C.c_double * K)(*c0s)
-        fun = (C.c_double * K)(); its = (C.c_uint64 * K)(); st = (C.c_int32 * K)()
-        # (a member without rows has an empty matrix: any non-null pointer serves, its status is Unconstrained)
-        rc = _capi.lib().lpipm_solve_batch_ub_tall(self._h, K, m, n, _ptrs(As), _ptrs(bs), _ptrs(cs), c0, C.byref(opts),
-                                                   _ptrs(xs) if xs is not None else None,
-                                                   C.c_void_p(int(x_dev_ptr)) if x_dev_ptr is not None else None, int(row_stride),
-                                                   fun, its, st)
-        if rc != _capi.OK:
-            _raise_for(rc)
-        out = []
-        for i in range(K):
-            has_x = st[i] in (_capi.OK, _capi.ITERATION_LIMIT)
-            if xs is not None:
-                out.append((int(st[i]), xs[i] if has_x else None, fun[i] if has_x else None, int(its[i])))
-            else:
-                out.append((int(st[i]), fun[i] if has_x else None, int(its[i])))
-        return out
-
     def resident_bytes(self) -> int:
         """Device bytes held for the resident problem(s): arenas + shared matrix + factor workspace."""
         out = C.c_uint64(0)
@@ -518,29 +548,15 @@ class Context:
     def solve_lockstep(self, opts: "_capi.Opts"):
         """-> list of (status, x_slack | None, fun, iterations), one per LP of the last upload_lockstep"""
         K, m, n = self._lock[:3]
-        dp = C.POINTER(C.c_double)
         xs = [np.full(n, np.nan) for _ in range(K)]
-        xp = (dp * K)(*[_p(x) for x in xs])
-        fun = (C.c_double * K)(); its = (C.c_uint64 * K)(); st = (C.c_int32 * K)()
-        rc = _capi.lib().lpipm_solve_lockstep(self._h, C.byref(opts), xp, fun, its, st)
-        if rc != _capi.OK:
-            _raise_for(rc)
-        out = []
-        for i in range(K):
-            has_x = st[i] in (_capi.OK, _capi.ITERATION_LIMIT)
-            out.append((int(st[i]), xs[i] if has_x else None, fun[i] if has_x else None, int(its[i])))
-        return out
+        out, unpack = _members_out(K, xs)
+        return unpack(_capi.lib().lpipm_solve_lockstep(self._h, C.byref(opts), _ptrs(xs), *out))
 
     def solve_lockstep_device(self, opts: "_capi.Opts", x_dev_ptr: int, row_stride: int):
         """Like solve_lockstep, the solutions left in HBM: x / tau of LP i goes to the device row
         x_dev_ptr + i * row_stride doubles (lpipm_solve_lockstep_device).  -> list of (status, fun | None, iterations)"""
-        K = self._lock[0]
-        fun = (C.c_double * K)(); its = (C.c_uint64 * K)(); st = (C.c_int32 * K)()
-        rc = _capi.lib().lpipm_solve_lockstep_device(self._h, C.byref(opts), C.c_void_p(int(x_dev_ptr)), int(row_stride),
-                                                     fun, its, st)
-        if rc != _capi.OK:
-            _raise_for(rc)
-        return [(int(st[i]), fun[i] if st[i] in (_capi.OK, _capi.ITERATION_LIMIT) else None, int(its[i])) for i in range(K)]
+        out, unpack = _members_out(self._lock[0])
+        return unpack(_capi.lib().lpipm_solve_lockstep_device(self._h, C.byref(opts), C.c_void_p(int(x_dev_ptr)), int(row_stride), *out))
 
     def solve_batch_device(self, problems, opts: "_capi.Opts", x_dev_ptr: int, row_stride: int, tall: bool = False):
         """lpipm_solve_batch_device over [(A, b, c, c0), ...]: member i's x / tau goes to the device row
@@ -548,29 +564,7 @@ class Context:
         tall=True: `problems` are Problems built from `ub` rows only (else ValueError), solved in the tall inequality form
         (lpipm_solve_batch_ub_tall); member i's row has n + m_ub entries, slack values last.
         -> list of (status, fun | None, iterations)"""
-        if tall:
-            return Context._solve_batch_tall(self, problems, opts, x_dev_ptr, row_stride)
-        K = len(problems)
-        if K == 0:
-            return []
-        As = [_f64(p[0]) for p in problems]; bs = [_f64(p[1]) for p in problems]; cs = [_f64(p[2]) for p in problems]
-        for A, b, c in zip(As, bs, cs):
-            if A.ndim != 2 or b.shape != (A.shape[0],) or c.shape != (A.shape[1],):
-                raise IncompatibleInputDimensions()
-        arr = _ptrs
-        m = (C.c_uint64 * K)(*[A.shape[0] for A in As]); n = (C.c_uint64 * K)(*[A.shape[1] for A in As])
-        c0 = (C.c_double * K)(*[float(p[3]) if len(p) > 3 else 0.0 for p in problems])
-        fun = (C.c_double * K)(); its = (C.c_uint64 * K)(); st = (C.c_int32 * K)()
-        ns = _batch_hints(problems)
-        if ns is not None:
-            rc = _capi.lib().lpipm_solve_batch_slack(self._h, K, m, n, ns, arr(As), arr(bs), arr(cs), c0, C.byref(opts), None,
-                                                     C.c_void_p(int(x_dev_ptr)), int(row_stride), fun, its, st)
-        else:
-            rc = _capi.lib().lpipm_solve_batch_device(self._h, K, m, n, arr(As), arr(bs), arr(cs), c0, C.byref(opts),
-                                                      C.c_void_p(int(x_dev_ptr)), int(row_stride), fun, its, st)
-        if rc != _capi.OK:
-            _raise_for(rc)
-        return [(int(st[i]), fun[i] if st[i] in (_capi.OK, _capi.ITERATION_LIMIT) else None, int(its[i])) for i in range(K)]
+        return _solve_batch(self, problems, opts, tall, x_dev_ptr, row_stride)
 
     def solve_batch(self, problems, opts: "_capi.Opts", tall: bool = False):
         """lpipm_solve_batch over [(A, b, c, c0), ...] (any mix of shapes; equal shapes run as lockstep batches).
@@ -579,33 +573,7 @@ class Context:
         (lpipm_solve_batch_ub_tall: equal shapes as lockstep batches whose members own their matrices); x_slack has
         n + m_ub entries, slack values last.
         -> list of (status, x_slack | None, fun | None, iterations)"""
-        if tall:
-            return Context._solve_batch_tall(self, problems, opts)
-        K = len(problems)
-        if K == 0:
-            return []
-        As = [_f64(p[0]) for p in problems]; bs = [_f64(p[1]) for p in problems]; cs = [_f64(p[2]) for p in problems]
-        for A, b, c in zip(As, bs, cs):
-            if A.ndim != 2 or b.shape != (A.shape[0],) or c.shape != (A.shape[1],):
-                raise IncompatibleInputDimensions()
-        arr = _ptrs
-        xs = [np.full(A.shape[1], np.nan) for A in As]
-        m = (C.c_uint64 * K)(*[A.shape[0] for A in As]); n = (C.c_uint64 * K)(*[A.shape[1] for A in As])
-        c0 = (C.c_double * K)(*[float(p[3]) if len(p) > 3 else 0.0 for p in problems])
-        fun = (C.c_double * K)(); its = (C.c_uint64 * K)(); st = (C.c_int32 * K)()
-        ns = _batch_hints(problems)
-        if ns is not None:
-            rc = _capi.lib().lpipm_solve_batch_slack(self._h, K, m, n, ns, arr(As), arr(bs), arr(cs), c0, C.byref(opts), arr(xs),
-                                                     None, 0, fun, its, st)
-        else:
-            rc = _capi.lib().lpipm_solve_batch(self._h, K, m, n, arr(As), arr(bs), arr(cs), c0, C.byref(opts), arr(xs), fun, its, st)
-        if rc != _capi.OK:
-            _raise_for(rc)
-        out = []
-        for i in range(K):
-            has_x = st[i] in (_capi.OK, _capi.ITERATION_LIMIT)
-            out.append((int(st[i]), xs[i] if has_x else None, fun[i] if has_x else None, int(its[i])))
-        return out
+        return _solve_batch(self, problems, opts, tall)
 
     def solve_raw(self, opts: "_capi.Opts", want_log: bool = False, x_dev_ptr: int | None = None):
         """-> (status, x_slack | None, fun, iterations, log rows)"""
@@ -644,8 +612,7 @@ class Context:
         rc = _capi.lib().lpipm_solve_f32(self._h, m, n, fp(A), n, fp(b), fp(c), C.c_float(c0), C.byref(opts), fp(x), C.byref(fun),
                                          C.byref(it), C.cast(log, C.c_void_p) if want_log else None)
         rows = [tuple(float(log[7 * i + k]) for k in range(7)) for i in range(min(int(it.value), nlog))] if want_log else []
-        has_x = rc in (_capi.OK, _capi.ITERATION_LIMIT)
-        return rc, (x if has_x else None), float(fun.value), int(it.value), rows
+        return rc, (x if has_x(rc) else None), float(fun.value), int(it.value), rows
 
     def k_generic_solve_f64(self, A, b, c, c0: float = 0.0, opts: "_capi.Opts | None" = None, want_log: bool = False):
         """Test hook: the generic (scalar-type-templated) kernels of the f32 instantiation, instantiated for double."""

@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _capi
+from . import has_x
 
 
 def shard_range(count: int, world: int, rank: int) -> range:
@@ -78,8 +78,7 @@ def solve_batch_sharded(problems, opts=None, ctx=None, group=None, device=None, 
             rc, x, fun, it = solve_fn(A, b, c, c0, None)
             if x is not None:
                 host[slot, :n] = np.asarray(x, dtype=np.float64)
-            ok = rc in (_capi.OK, _capi.ITERATION_LIMIT)
-            meta[slot] = (fun if ok and fun is not None else float("nan"), float(it), float(rc))
+            meta[slot] = (fun if has_x(rc) and fun is not None else float("nan"), float(it), float(rc))
         host[:, n_max:] = meta
         packed = torch.from_numpy(host).to(device)
     if world > 1:
@@ -96,9 +95,8 @@ def solve_batch_sharded(problems, opts=None, ctx=None, group=None, device=None, 
         row = g[r, slot]
         n = np.asarray(problems[i][2]).shape[0]
         status = int(row[n_max + 2])
-        has_x = status in (_capi.OK, _capi.ITERATION_LIMIT)
-        out.append(dict(status=status, x_slack=row[:n].copy() if has_x else None,
-                        fun=float(row[n_max]) if has_x else None, iterations=int(row[n_max + 1])))
+        out.append(dict(status=status, x_slack=row[:n].copy() if has_x(status) else None,
+                        fun=float(row[n_max]) if has_x(status) else None, iterations=int(row[n_max + 1])))
     return out
 
 

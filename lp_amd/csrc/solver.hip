@@ -23,6 +23,7 @@
 #include <atomic>
 #include <chrono>
 #include "vec_kernels.hpp"
+#include "batch_plan.hpp"
 
 using namespace lpipm;
 
@@ -150,8 +151,6 @@ struct lpipm_ctx {
     bool first_valid = false;    // M1 / plan1 / info1 hold iteration 1 of this upload (every member's); dropped by any upload.  A
                                  //   half-batch view holds the parent's value for the length of one solve
     bool first_done = false;     // the last solve of this context (or view) got through its iteration 1
-    bool on_first = false;       // the iteration being enqueued works in M1 / plan1 ...
-    bool skip_factor = false;    //   ... which already hold its factor: no A.D.A^T, no factorisation
     // what building a shared-matrix batch's one factor took, until the solve it preceded reports it (lpipm_phase_times)
     double build_adat_ms = 0.0, build_potrf_ms = 0.0;
     uint64_t build_launches = 0;
@@ -175,7 +174,6 @@ struct lpipm_ctx {
                                  //   members -- each variant has its own one or two, always among the members whose last
                                  //   d_tau is ill-determined in fp64 (tests/golden/make_c4_members.py, margin()): the oracle
                                  //   does the same under a permutation of its columns.  Refinement costs 7-20 % and is off.
-    bool refine_now = false;     // the iteration being enqueued refines its solves (host mirror of the LPs' skip_refine words)
     // stand-alone potrf/solve buffers
     double *kM = nullptr, *kM0 = nullptr, *kR = nullptr, *kY = nullptr;
     int32_t* kinfo = nullptr;
@@ -528,18 +526,6 @@ static int check_upload(const lpipm_ctx* c, const Upload& u) {
     }
     return u.m > (1u << 20) || u.n > (1u << 24) ? LPIPM_ERR_BAD_ARGUMENT : LPIPM_OK;
 }
-// Whether the last n_slack columns of every one of the `count` m x n matrices are [I; 0] (n_slack == n: not a hint).
-static bool slack_hint_holds(uint64_t count, uint64_t m, uint64_t n, const double* const* A, uint64_t lda, uint64_t n_slack) {
-    if (n_slack == 0 || n_slack == n) return false;
-    for (uint64_t k = 0; k < count; ++k)
-        for (uint64_t i = 0; i < m; ++i) {
-            const double* row = A[k] + i * lda + (n - n_slack);
-            for (uint64_t j = 0; j < n_slack; ++j)
-                if (row[j] != ((i == j) ? 1.0 : 0.0)) return false;
-        }
-    return true;
-}
-
 // The geometry of a request whose hint `n_slack` holds, on a context with these settings: a value, no device needed.
 static Geometry geometry_of(const Upload& u, uint64_t n_slack, bool first_cache, int refine) {
     Geometry g;
@@ -820,10 +806,15 @@ extern "C" int lpipm_upload_ub_eq(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const
     return upload_impl(c, Upload{.m = m_ub + m_eq, .n = n + m_ub, .n_slack = m_ub,
                                  .parts = UploadParts{m_ub, A_ub, lda_ub, b_ub, A_eq, lda_eq, b_eq}, .c = &cc, .c0 = &c0});
 }
+// The request of one tall LP (cc, c0: one entry each).
+static Upload tall_request(uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub, const double* b_ub, const double* const* cc,
+                           const double* c0) {
+    return Upload{.m = m_ub, .n = n + m_ub, .n_slack = m_ub, .parts = UploadParts{.m_ub = m_ub, .A_ub = A_ub, .lda_ub = lda_ub, .b_ub = b_ub},
+                  .c = cc, .c0 = c0, .tall = true, .keep_ok = false};
+}
 extern "C" int lpipm_upload_ub_tall(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub,
                                     const double* b_ub, const double* cc, double c0) {
-    return upload_impl(c, Upload{.m = m_ub, .n = n + m_ub, .n_slack = m_ub,
-                                 .parts = UploadParts{.m_ub = m_ub, .A_ub = A_ub, .lda_ub = lda_ub, .b_ub = b_ub}, .c = &cc, .c0 = &c0, .tall = true, .keep_ok = false});
+    return upload_impl(c, tall_request(n, m_ub, A_ub, lda_ub, b_ub, &cc, &c0));
 }
 extern "C" int lpipm_upload_lockstep(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* const* A,
                                      const double* const* b, const double* const* cc, const double* c0) {
@@ -903,11 +894,16 @@ static hipError_t ctx_gemv_dual(lpipm_ctx* c, const double* W, const double* V, 
 
 // M = A . diag(dinv) . A^T, lower tiles (newton_equations.rs:54-57); a second copy of it goes to M0 (the matrix the
 // refined Cholesky solves take their residuals against: M itself is factorised in place)
-// The matrix and the factor plan of the iteration being enqueued: the kept first factor's in iteration 1 of a solve that
-// uses it (lpipm_ctx::on_first), the working ones otherwise.
-static double* cur_M(const lpipm_ctx* c) { return c->on_first ? c->p.M1 : c->p.M; }
-static const FactorPlan& cur_factor(const lpipm_ctx* c) { return c->on_first ? *c->p.factor1 : *c->p.factor; }
-static bool cur_shared(const lpipm_ctx* c) { return c->on_first && c->p.shared_factor; }   // one factor for the whole batch
+// The switches of the ONE iteration being enqueued: made by whoever enqueues it, handed down by reference, kept nowhere.
+struct Iter {
+    bool on_first = false;       // it works in M1 / plan1 (iteration 1 of a solve that uses the kept first factor) ...
+    bool skip_factor = false;    //   ... which already hold its factor: no A.D.A^T, no factorisation
+    bool refine_now = false;     // it refines its solves (host mirror of the LPs' skip_refine words)
+};
+// The matrix and the factor plan of that iteration: the kept first factor's or the working ones.
+static double* cur_M(const lpipm_ctx* c, const Iter& it) { return it.on_first ? c->p.M1 : c->p.M; }
+static const FactorPlan& cur_factor(const lpipm_ctx* c, const Iter& it) { return it.on_first ? *c->p.factor1 : *c->p.factor; }
+static bool cur_shared(const lpipm_ctx* c, const Iter& it) { return it.on_first && c->p.shared_factor; }   // one factor for the whole batch
 // The pivot-failure words of the LPs this context covers, between the solver's word and its kept copy (device to device).
 // A shared-matrix batch's one kept word goes to every LP (the other direction does not exist: the build wrote it).
 static hipError_t copy_info(lpipm_ctx* c, int32_t* dst, const int32_t* src) {
@@ -923,18 +919,18 @@ static hipError_t copy_info(lpipm_ctx* c, int32_t* dst, const int32_t* src) {
     return c->p.B == 1 ? hipMemcpyAsync(d, s, sizeof(int32_t), hipMemcpyDeviceToDevice, c->rs.st)
                        : hipMemcpy2DAsync(d, c->p.bstride, s, c->p.bstride, sizeof(int32_t), (size_t)c->p.B, hipMemcpyDeviceToDevice, c->rs.st);
 }
-static AdatLaunch adat_launch(lpipm_ctx* c, const Batch& bt) {
+static AdatLaunch adat_launch(lpipm_ctx* c, const Iter& it, const Batch& bt) {
     AdatLaunch a{};
-    a.A = c->p.A; a.lda = c->p.npa; a.dinv = c->p.va.dinv; a.M = cur_M(c); a.ldm = c->p.mp;
+    a.A = c->p.A; a.lda = c->p.npa; a.dinv = c->p.va.dinv; a.M = cur_M(c, it); a.ldm = c->p.mp;
     a.M2 = c->refine > 0 ? c->p.M0 : nullptr;                                // only the refined solves need M itself
     a.K = c->p.npa; a.diag_pad_from = (int)c->p.m; a.batch = bt; a.shared_a = c->p.shared_a;
     return a;
 }
-static hipError_t run_adat(lpipm_ctx* c, const Batch& bt) {
+static hipError_t run_adat(lpipm_ctx* c, const Iter& it, const Batch& bt) {
     bool second_copy = false;
-    hipError_t e = launch_adat(c->ap, c->p.adat, adat_launch(c, bt), false, c->rs.st, &second_copy);
+    hipError_t e = launch_adat(c->ap, c->p.adat, adat_launch(c, it, bt), false, c->rs.st, &second_copy);
     if (e != hipSuccess) return e;
-    e = launch_slack_diag(c->p.ns, c->p.nx, c->p.va.dinv, cur_M(c), c->p.mp, c->rs.st, bt);   // + diag(D_slack)
+    e = launch_slack_diag(c->p.ns, c->p.nx, c->p.va.dinv, cur_M(c, it), c->p.mp, c->rs.st, bt);   // + diag(D_slack)
     if (e != hipSuccess) return e;
     if (c->refine <= 0) return hipSuccess;
     if (second_copy) return launch_slack_diag(c->p.ns, c->p.nx, c->p.va.dinv, c->p.M0, c->p.mp, c->rs.st, bt);
@@ -977,9 +973,9 @@ static int tall_sym_solve(lpipm_ctx* c, int nrhs, const double* r1a, const doubl
 // v = M^-1 r through the Cholesky factor (newton_equations.rs:151-169); optionally (LPIPM_REFINE, see lpipm_ctx::refine)
 // with one step of iterative refinement against the matrix itself:  v0 = L^-T L^-1 r;  rho = r - M.v0 (doubled
 // precision, one read of the lower triangle);  v = v0 + L^-T L^-1 rho.  R: nrhs x mp, in/out.
-static int chol_solve_refined(lpipm_ctx* c, int nrhs, double* R, const Batch& bt) {
+static int chol_solve_refined(lpipm_ctx* c, const Iter& it, int nrhs, double* R, const Batch& bt) {
     hipStream_t st = c->rs.st;
-    if (!c->refine_now) { LP_HIP(launch_chol_solve(cur_M(c), c->p.mp, cur_factor(c), nrhs, R, c->p.Y, st, bt, SolveSteps{}, cur_shared(c))); return LPIPM_OK; }
+    if (!it.refine_now) { LP_HIP(launch_chol_solve(cur_M(c, it), c->p.mp, cur_factor(c, it), nrhs, R, c->p.Y, st, bt, SolveSteps{}, cur_shared(c, it))); return LPIPM_OK; }
     // the refinement's launches skip an LP whose own word says so (a finished one, or one that does not need it yet)
     const Batch br = c->refine == 2 ? bt : Batch{bt.count, bt.stride, c->p.va.skip_refine, bt.first};
     vec_rows_copy(c->p.mp, nrhs, c->p.R0, R, st, br);
@@ -1074,7 +1070,7 @@ static int copy_status(lpipm_ctx* c) {
 // the status of the previous iteration: the GPU goes straight from one iteration into the big kernel of the
 // next instead of idling through the read-back, and if the LP turns out to be finished the two kernels return
 // at once.
-static int enqueue_head(lpipm_ctx* c) {
+static int enqueue_head(lpipm_ctx* c, const Iter& it) {
     hipStream_t st = c->rs.st;
     VecArgs vh = c->p.va;
     vh.done_chk = c->p.bt_head.done;
@@ -1089,7 +1085,7 @@ static int enqueue_head(lpipm_ctx* c) {
         return LPIPM_OK;
     }
     prof_mark(c, T_VEC, true);
-    if (c->skip_factor) return LPIPM_OK;          // iteration 1 on a kept factor: its M is already there, factored
+    if (it.skip_factor) return LPIPM_OK;          // iteration 1 on a kept factor: its M is already there, factored
     if (c->colsplit && c->world > 1 && c->p.adat.ngroups() > 0 && c->st_c) {
         // n-split, M = sum_g A_g D_g A_g^T, PIPELINED: one A.D.A^T launch in column-group-major order on the solver's stream;
         // the workgroup that completes a group's last tile bumps the group's word; on the communication stream a one-wave
@@ -1102,7 +1098,7 @@ static int enqueue_head(lpipm_ctx* c) {
         hipStream_t sc = c->st_c;
         const Batch& bt = c->p.bt_head;
         // (the launch arms ev_c0 once the group words are zero, in front of its kernel)
-        LP_HIP(launch_adat(c->ap, c->p.adat, adat_launch(c, bt), true, st, nullptr, c->ev_c0));
+        LP_HIP(launch_adat(c->ap, c->p.adat, adat_launch(c, it, bt), true, st, nullptr, c->ev_c0));
         LP_HIP(hipStreamWaitEvent(sc, c->ev_c0, 0));
         for (int g = 0; g < c->p.adat.ngroups(); ++g) {
             const AdatGroup grp = adat_group(c->p.adat, g);
@@ -1118,7 +1114,7 @@ static int enqueue_head(lpipm_ctx* c) {
         prof_mark(c, T_ADAT, true);
         return LPIPM_OK;
     }
-    LP_HIP(run_adat(c, c->p.bt_head));                                       // newton_equations.rs:55-57
+    LP_HIP(run_adat(c, it, c->p.bt_head));                                       // newton_equations.rs:55-57
     if (c->colsplit && c->world > 1) {                                     // n-split: M = sum_g A_g D_g A_g^T
         vec_pack_lower(c->p.M, c->p.mp, c->p.mp, c->mpack, 0, st);
         LP_TRY(ctx_allreduce(c, c->mpack, c->mpack_count, 0));
@@ -1137,6 +1133,7 @@ static const PotrfLookahead* lookahead(lpipm_ctx* c) { return c->la.side ? &c->l
 // columns of L that are final by then.  R, Y and tpart belong to the solves alone; nothing of the factorisation touches them.
 struct PredictorBeside {
     lpipm_ctx* c;
+    const Iter& it;
     int fwd_done = 0;            // forward steps [0, fwd_done) of the predictor's solve are enqueued
     static hipError_t at(void* self, int sb, hipStream_t side) {
         PredictorBeside* b = (PredictorBeside*)self;
@@ -1144,7 +1141,7 @@ struct PredictorBeside {
         VecArgs& v = c->p.va;
         if (sb < 0) return ctx_gemv_n(c, 2, v.W, v.b, v.rP, v.R, c->p.bt, side);     // :220
         b->fwd_done = sb + 1;
-        return launch_chol_solve(cur_M(c), c->p.mp, cur_factor(c), 2, v.R, c->p.Y, side, c->p.bt, SolveSteps{sb, sb + 1, false}, cur_shared(c));
+        return launch_chol_solve(cur_M(c, b->it), c->p.mp, cur_factor(c, b->it), 2, v.R, c->p.Y, side, c->p.bt, SolveSteps{sb, sb + 1, false}, cur_shared(c, b->it));
     }
 };
 
@@ -1177,8 +1174,8 @@ static int enqueue_tail_tall(lpipm_ctx* c, int ip, const lpipm_opts* o) {
 }
 
 // The rest of the iteration, ending with the status record on its way to the host and ev_status behind it.
-static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
-    if (c->p.tall) return enqueue_tail_tall(c, ip, o);
+static int enqueue_tail(lpipm_ctx* c, const Iter& it, int ip, const lpipm_opts* o) {
+    if (c->p.tall) return enqueue_tail_tall(c, ip, o);          // (no kept factor, no refinement: nothing of `it` applies)
     VecArgs& v = c->p.va;
     hipStream_t st = c->rs.st;
     XRank xr_{xrank_fn, c};
@@ -1188,15 +1185,15 @@ static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
     // (no clearing of the pivot-failure word: k_blind_start and every k_scalar_indicators leave it zero)
     // a single LP whose factorisation runs with the look-ahead: the predictor's pass and the first forward steps of its
     // solve go beside the chain (launch_potrf decides whether the look-ahead applies; the serial order otherwise)
-    PredictorBeside pb{c};
+    PredictorBeside pb{c, it};
     PotrfBeside beside{PredictorBeside::at, &pb};
     const bool may_beside = chol && !c->colsplit && bt.count == 1 && c->refine <= 0;
-    if (c->skip_factor) LP_HIP(copy_info(c, v.potrf_info, c->p.info1));   // the kept factor's pivot failure, if it had one
+    if (it.skip_factor) LP_HIP(copy_info(c, v.potrf_info, c->p.info1));   // the kept factor's pivot failure, if it had one
     else {
-        if (chol) LP_HIP(launch_potrf(cur_M(c), c->p.mp, c->p.mp, cur_factor(c), v.potrf_info, st, bt, lookahead(c), false,
+        if (chol) LP_HIP(launch_potrf(cur_M(c, it), c->p.mp, c->p.mp, cur_factor(c, it), v.potrf_info, st, bt, lookahead(c), false,
                                       may_beside ? &beside : nullptr));   // :129-131
         else      LP_HIP(launch_qr_factor(c->p.M, c->p.mp, c->p.mp, c->p.tau, v.potrf_info, st));        // :133-149
-        if (c->on_first) LP_HIP(copy_info(c, c->p.info1, v.potrf_info));  // kept with the factor it belongs to
+        if (it.on_first) LP_HIP(copy_info(c, c->p.info1, v.potrf_info));  // kept with the factor it belongs to
         prof_mark(c, T_POTRF);
     }
     // predictor: both sym_solve calls of solve_newton_equations (:187-188) in one pass each
@@ -1209,8 +1206,8 @@ static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
         vec_add_rows((int)c->p.m, 2, v.R, c->p.mp, v.b, v.rP, st);
     }
     prof_mark(c, T_GEMV);
-    if (beside.calls > 0) LP_HIP(launch_chol_solve(cur_M(c), c->p.mp, cur_factor(c), 2, v.R, c->p.Y, st, bt, SolveSteps{pb.fwd_done, -1, true}, cur_shared(c)));
-    else if (chol) LP_TRY(chol_solve_refined(c, 2, v.R, bt));                               // :221, :154
+    if (beside.calls > 0) LP_HIP(launch_chol_solve(cur_M(c, it), c->p.mp, cur_factor(c, it), 2, v.R, c->p.Y, st, bt, SolveSteps{pb.fwd_done, -1, true}, cur_shared(c, it)));
+    else if (chol) LP_TRY(chol_solve_refined(c, it, 2, v.R, bt));                               // :221, :154
     else      LP_HIP(launch_qr_solve(c->p.M, c->p.mp, c->p.mp, c->p.tau, 2, v.R, v.potrf_info, st));   // :155-166
     prof_mark(c, T_TRSV);
     LP_HIP(ctx_gemv_t(c, 2, v.R, bt));              // :223
@@ -1231,7 +1228,7 @@ static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
         vec_add_rows((int)c->p.m, 1, v.R, c->p.mp, v.rP2, nullptr, st);
     }
     prof_mark(c, T_GEMV);
-    if (chol) LP_TRY(chol_solve_refined(c, 1, v.R, bt));
+    if (chol) LP_TRY(chol_solve_refined(c, it, 1, v.R, bt));
     else      LP_HIP(launch_qr_solve(c->p.M, c->p.mp, c->p.mp, c->p.tau, 1, v.R, v.potrf_info, st));
     prof_mark(c, T_TRSV);
     LP_HIP(ctx_gemv_t(c, 1, v.R, bt));
@@ -1250,9 +1247,9 @@ static int enqueue_tail(lpipm_ctx* c, int ip, const lpipm_opts* o) {
     return LPIPM_OK;
 }
 
-static int enqueue_iteration(lpipm_ctx* c, int ip, const lpipm_opts* o) {
-    LP_TRY(enqueue_head(c));
-    return enqueue_tail(c, ip, o);
+static int enqueue_iteration(lpipm_ctx* c, const Iter& it, int ip, const lpipm_opts* o) {
+    LP_TRY(enqueue_head(c, it));
+    return enqueue_tail(c, it, ip, o);
 }
 
 // The one kept first factor of a shared-matrix batch (Problem::shared_factor): M1 = A.A^T (+ I on the structural slack rows)
@@ -1269,6 +1266,7 @@ static int ensure_shared_factor(lpipm_ctx* c, const lpipm_opts* o) {
     LP_HIP(hipSetDevice(c->device));
     hipStream_t st = c->rs.st;
     const Batch one{1, (long long)c->p.bstride, nullptr, 0};
+    const Iter first{.on_first = true};
     const bool timed = c->profiling != 0;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     auto drop_events = [&]() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
@@ -1279,13 +1277,12 @@ static int ensure_shared_factor(lpipm_ctx* c, const lpipm_opts* o) {
         if (timed) LP_HIP(hipEventRecord(ev[0], st));
         AdatRes res = c->p.adat;
         res.counters_dirty = true;
-        AdatLaunch a{};
-        a.A = c->p.A; a.lda = c->p.npa; a.dinv = c->p.ones; a.M = c->p.M1; a.ldm = c->p.mp; a.M2 = nullptr;
-        a.K = c->p.npa; a.diag_pad_from = (int)c->p.m; a.batch = one; a.shared_a = true;
+        AdatLaunch a = adat_launch(c, first, one);          // into M1 (the shared A; no second copy: nothing refines here)
+        a.dinv = c->p.ones;
         LP_HIP(launch_adat(c->ap, res, a, false, st, nullptr));
-        LP_HIP(launch_slack_diag(c->p.ns, c->p.nx, c->p.ones, c->p.M1, c->p.mp, st, one));   // + I on the slack rows
+        LP_HIP(launch_slack_diag(c->p.ns, c->p.nx, c->p.ones, cur_M(c, first), c->p.mp, st, one));   // + I on the slack rows
         if (timed) LP_HIP(hipEventRecord(ev[1], st));
-        LP_HIP(launch_potrf(c->p.M1, c->p.mp, c->p.mp, *c->p.factor1, c->p.info1, st, one, nullptr, true, nullptr));
+        LP_HIP(launch_potrf(cur_M(c, first), c->p.mp, c->p.mp, cur_factor(c, first), c->p.info1, st, one, nullptr, true, nullptr));
         if (timed) LP_HIP(hipEventRecord(ev[2], st));
         LP_HIP(hipStreamSynchronize(st));
         return LPIPM_OK;
@@ -1309,12 +1306,18 @@ static void print_row(double alpha, const StatusRec& s) {  // mod.rs:228 + indic
 }
 
 // Where the solutions go: per-member host pointers, or rows of one device buffer.
-struct XOut {
-    double* const* host = nullptr;
-    char* dev = nullptr;
-    size_t stride_bytes = 0;
-    bool valid() const { return host || dev; }
-};
+struct XOut { double* const* host = nullptr; char* dev = nullptr; size_t stride_bytes = 0; };
+// What an entry was given for them, and the one place that checks it: exactly one of host rows and device block is there,
+// and a row of the block holds the row_len(i) doubles of each of the `count` members.
+struct XArgs { double* const* host_rows = nullptr; void* dev = nullptr; uint64_t row_stride = 0; };
+template <typename RowLen = uint64_t (*)(uint64_t)>
+static int xout_of(const XArgs& a, XOut& xo, uint64_t count = 0, RowLen row_len = nullptr) {
+    if ((a.host_rows != nullptr) == (a.dev != nullptr)) return LPIPM_ERR_BAD_ARGUMENT;
+    for (uint64_t i = 0; i < count && a.dev; ++i)
+        if (row_len(i) > a.row_stride) return LPIPM_ERR_BAD_ARGUMENT;
+    xo = XOut{a.host_rows, (char*)a.dev, a.row_stride * sizeof(double)};
+    return LPIPM_OK;
+}
 
 // The return code a status record stands for, -1 while the LP goes on iterating.
 static int status_code(const StatusRec& s) {
@@ -1328,23 +1331,105 @@ static int status_code(const StatusRec& s) {
 }
 static bool has_x(int code) { return code == LPIPM_OK || code == LPIPM_ITERATION_LIMIT; }
 
+// The members' return codes, objectives and iteration counts (fun, its nullable); set() is the only code that writes them.
+// A member that was refused, or whose chunk failed as a whole, has no objective and no iterations: the defaults.
+struct Results {
+    double* fun = nullptr; uint64_t* its = nullptr; int32_t* status = nullptr;
+    void set(uint64_t i, int code, double fun_i = NAN, uint64_t its_i = 0) const { status[i] = code; if (fun) fun[i] = fun_i; if (its) its[i] = its_i; }
+};
+// Everything a solve hands back, indexed by the member's place k in the resident batch (a half-batch view's member i is
+// k = bt.first + i): its results go to res[k], its solution to row rows[k] of x (row k when rows is null); log: the one LP's.
+struct SolveOut { XOut x; const uint64_t* rows = nullptr; Results res; lpipm_iter_row* log = nullptr; };
+
+// What differs between the one LP of lpipm_solve[_device] (any solver arm, column split, `disp` table, iteration log) and a
+// lockstep batch: made once at the top of solve_members.
+enum class Members { One, Lockstep };
+struct SolveMode {
+    bool batch;        // the checks of a batch apply, and the closing x launch covers every member whatever its outcome
+    bool wait_start;   // the host waits for the starting point before it enqueues iteration 1
+    bool spin;         // it waits for an iteration by watching the pinned records (wait_status), not on the status event
+    bool rows;         // the starting point's record is fetched, and the `disp` table and the iteration log are written from the records
+    bool bounce_x;     // x reaches a host row through the pinned bounce buffer: truly asynchronous, one synchronisation for x and status
+};
+
+// x / tau (mod.rs:231/238, :165) of the members that have a solution (ret[i]), each to its destination: a row of the device
+// block, a host row, or -- the one LP -- the pinned bounce buffer, *bounced then being the host row that buffer is copied to
+// once the stream has drained.  In front: one launch that forms x for every LP of a batch (none for a single LP without a
+// solution) and, for a scaled problem, the one that takes it back to the caller's units.
+static int copy_out_x(lpipm_ctx* c, const SolveMode& md, const std::vector<int>& ret, const SolveOut& out, double** bounced) {
+    *bounced = nullptr;
+    if (!md.batch && !has_x(ret[0])) return LPIPM_OK;
+    StreamRes& rs = c->rs;
+    hipStream_t st = rs.st;
+    const XOut& xo = out.x;
+    XRank xrf{xrank_fn, c};
+    LP_TRY(vec_final_x(c->p.va, c->p.xout, st, c->colsplit ? &xrf : nullptr));
+    LP_HIP(hipGetLastError());
+    if (c->p.scale_passes > 0)          // (fun is the scaled vectors' product: the same number)
+        LP_HIP(launch_unscale_x(c->p.sc, c->p.xout, (int)c->p.n, st, Batch{c->p.B, (long long)c->p.bstride, nullptr, c->p.bt.first}));
+    const size_t xbytes = c->p.n * sizeof(double);
+    for (int i = 0; i < c->p.B; ++i) {
+        if (!has_x(ret[(size_t)i])) continue;
+        const uint64_t k = (uint64_t)(c->p.bt.first + i), row = out.rows ? out.rows[k] : k;
+        const char* src = (const char*)c->p.xout + (size_t)k * c->p.bstride;
+        if (xo.dev) LP_HIP(hipMemcpyAsync(xo.dev + row * xo.stride_bytes, src, xbytes, hipMemcpyDeviceToDevice, st));
+        else if (!xo.host[row]) continue;
+        else if (!md.bounce_x) LP_HIP(hipMemcpyAsync(xo.host[row], src, xbytes, hipMemcpyDeviceToHost, st));
+        else {
+            if (rs.x_pinned_cap < c->p.n) {
+                if (rs.x_pinned) (void)hipHostFree(rs.x_pinned);
+                rs.x_pinned = nullptr; rs.x_pinned_cap = 0;
+                LP_HIP(hipHostMalloc((void**)&rs.x_pinned, xbytes));
+                rs.x_pinned_cap = c->p.n;
+            }
+            LP_HIP(hipMemcpyAsync(rs.x_pinned, src, xbytes, hipMemcpyDeviceToHost, st));
+            *bounced = xo.host[row];
+        }
+    }
+    return copy_status(c);
+}
+
+// lpipm_phase_times of the solve that has just drained (a phase's time is that of the launch, which covers all members), with
+// what building the shared first factor ahead of it took, if it was built.  replay: iteration 1 started from a kept factor.
+static void report_times(lpipm_ctx* c, uint64_t loop_iterations, bool replay) {
+    if (c->profiling) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->rs.ev_begin, c->rs.ev_end);
+        c->times.total_ms = ms;
+        c->times.adat_ms = c->tag_ms[T_ADAT] + c->build_adat_ms; c->times.potrf_ms = c->tag_ms[T_POTRF] + c->build_potrf_ms;
+        c->times.trsv_ms = c->tag_ms[T_TRSV]; c->times.gemv_ms = c->tag_ms[T_GEMV]; c->times.vec_ms = c->tag_ms[T_VEC];
+        // launches of the kernel (each covers all B members): iteration 1 on a kept factor made none
+        c->times.adat_launches = loop_iterations - (replay && loop_iterations > 0 ? 1 : 0) + c->build_launches;
+        c->times.iterations = loop_iterations;         // iterations of the loop (= the slowest member's count)
+        // the speculatively enqueued head of the iteration after the last holds no GEMV pass: every counted pass ran
+        c->times.gemv_passes = c->gemv_passes;
+    }
+    c->build_adat_ms = c->build_potrf_ms = 0.0; c->build_launches = 0;    // reported (or not asked for)
+}
+
 // The interior-point loop (solve_normal_form, mod.rs:199-240) for the B >= 1 LPs that c -- a context or a half-batch view --
-// covers; member i's return code, objective (NAN without a solution) and iteration count go to status_out[i], fun_out[i]
-// and its_out[i], its solution to row rows[i] of xo (row i when rows is null).
-// batch == false: the one LP of lpipm_solve / lpipm_solve_device (any solver arm, column split, `disp` table, iteration log).
-// batch == true, a lockstep batch: B LPs of one shape resident at once (upload_impl with count = B), every launch of the
-// iteration covering all of them (gridDim.z = B).  The ~100 dependent launches per iteration -- the
-// latency floor of a small LP -- are then paid once per B LPs.  LPs finish at different iterations:
-// k_scalar_indicators sets an LP's `done` word on the conditions that end the reference's loop
-// (mod.rs:215, :231-233) and every later kernel skips it, so its iterate stays what it was; the host
+// covers; member i's return code, objective (NAN without a solution) and iteration count go to out.res, its solution to its
+// row of out.x.  One loop for both kinds of members; SolveMode has what differs.
+// Members::Lockstep: B LPs of one shape resident at once (upload_impl with count = B), every launch of the iteration covering
+// all of them (gridDim.z = B).  The ~100 dependent launches per iteration -- the latency floor of a small LP -- are then paid
+// once per B LPs.  LPs finish at different iterations: k_scalar_indicators sets an LP's `done` word on the conditions that end
+// the reference's loop (mod.rs:215, :231-233) and every later kernel skips it, so its iterate stays what it was; the host
 // mirrors the same decisions from the status records to count iterations and pick the return codes.
-static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XOut& xo, const uint64_t* rows, double* fun_out,
-                         uint64_t* its_out, int32_t* status_out, lpipm_iter_row* log) {
+static int solve_members(lpipm_ctx* c, const lpipm_opts* o, Members members, const SolveOut& out) {
     if (!c || !o) return LPIPM_ERR_BAD_ARGUMENT;
-    // InteriorPointBuilder::build, mod.rs:118-128
-    if (!(o->alpha0 > 0.0) || !(o->alpha0 < 1.0)) return LPIPM_INVALID_PARAMETER;
-    if (!(o->tol > 0.0)) return LPIPM_INVALID_PARAMETER;
-    if (batch) {
+    const bool batch = members == Members::Lockstep;
+    // wait_start.  A single LP: the host needs the starting point's indicators only for the `disp` table, for the selective
+    // refinement's first decision and for the phase marks: otherwise the first iteration is enqueued without a round trip to
+    // the host (~25 us per solve; profiling 2 brackets A.D.A^T only: no mark yet).  A batch: nothing of the starting point is
+    // read by the host; it waits there whenever it profiles.
+    // spin.  Only a loop that speculates on records the kernels write themselves can.  A single LP with every phase bracketed
+    // -- profiling 1 -- : the last mark of an iteration is recorded BEHIND the indicators kernel and has to have completed when it
+    // is read: the event wait stays; profiling 2's two marks sit in front of it.  A batch keeps it in both profiling modes.
+    const SolveMode md{.batch = batch, .wait_start = batch ? c->profiling != 0 : (o->disp || c->refine == 1 || c->profiling == 1),
+                       .spin = !c->colsplit && c->p.va.status_pinned != nullptr && (batch ? !c->profiling : c->profiling != 1),
+                       .rows = !batch, .bounce_x = !batch};
+    if (!(o->alpha0 > 0.0) || !(o->alpha0 < 1.0) || !(o->tol > 0.0)) return LPIPM_INVALID_PARAMETER;   // InteriorPointBuilder::build, mod.rs:118-128
+    if (md.batch) {
         if (o->solver_type != LPIPM_SOLVER_CHOLESKY) return LPIPM_ERR_UNSUPPORTED;      // the QR arms are single-LP
         if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
         if (c->colsplit) return LPIPM_ERR_UNSUPPORTED;
@@ -1361,41 +1446,30 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XO
     VecArgs& v = c->p.va;
     StreamRes& rs = c->rs;
     hipStream_t st = rs.st;
-    // profiling (lpipm_set_profiling): a phase's time is that of the launch, which covers all B members
-    for (int t = 0; t < T_NTAGS; ++t) c->tag_ms[t] = 0.0;
-    c->times = lpipm_phase_times{};
-    rs.nmarks = 0;
-    c->gemv_passes = 0;
+    for (int t = 0; t < T_NTAGS; ++t) c->tag_ms[t] = 0.0;   // profiling (lpipm_set_profiling)
+    c->times = lpipm_phase_times{}; rs.nmarks = 0; c->gemv_passes = 0;
     uint64_t loop_iterations = 0;
     if (c->profiling) LP_HIP(hipEventRecord(rs.ev_begin, st));
 
     vec_blind_start(v, st);                               // feasible_point.rs:24-31
     prof_mark(c, T_VEC);
     LP_TRY(enqueue_residuals(c, 1, o->ip ? 1 : 0, o->tol));  // feasible_point.rs:32, mod.rs:206
-    if (!batch) LP_TRY(copy_status(c));                   // (only a single LP's starting record is ever read, below)
+    if (md.rows) LP_TRY(copy_status(c));
     prof_mark(c, T_VEC);
-    // A single LP: the host needs the starting point's indicators only for the `disp` table, for the selective refinement's
-    // first decision and for the phase marks: otherwise the first iteration is enqueued without a round trip to the host
-    // (~25 us per solve; profiling 2 brackets A.D.A^T only: no mark yet).  A batch: nothing of the starting point is read by
-    // the host; it waits here whenever it profiles.
-    const bool wait_start = batch ? c->profiling != 0 : (o->disp || c->refine == 1 || c->profiling == 1);
-    if (wait_start) {
+    if (md.wait_start) {
         LP_HIP(hipStreamSynchronize(st));
         prof_collect(c);
     }
-    if (!batch && o->disp) {                              // mod.rs:208-211
+    if (md.rows && o->disp) {                             // mod.rs:208-211
         printf("alpha     \trho_p     \trho_d     \trho_g     \trho_mu    \tobj       \n");
         print_row(1.0, *rs.status_host);
     }
     // (selective mode: at the starting point mu / mu_0 = 1, so no member of a batch refines its first iteration)
-    c->refine_now = c->refine == 2 || (!batch && c->refine == 1 && rs.status_host->rho_mu <= refine_below());
+    bool refine_now = c->refine == 2 || (md.rows && c->refine == 1 && rs.status_host->rho_mu <= refine_below());
     // the head of iteration k+1 goes out before the status of iteration k is read (see enqueue_head); not when the
     // iteration contains host-side collectives
     const bool speculate = !c->colsplit;
-    // (a single LP with every phase bracketed -- profiling 1 -- : the last mark of an iteration is recorded BEHIND the indicators
-    //  kernel and has to have completed when it is read: the event wait stays; profiling 2's two marks sit in front of it.  A
-    //  batch keeps the event wait in both profiling modes.)
-    rs.spin_status = speculate && v.status_pinned != nullptr && (batch ? !c->profiling : c->profiling != 1);
+    rs.spin_status = md.spin;
     std::vector<int> ret((size_t)B, -1), act((size_t)B);        // -1: still iterating; act[0 .. running): those members, ascending
     std::vector<uint64_t> its((size_t)B, 0);
     for (int i = 0; i < B; ++i) act[(size_t)i] = i;
@@ -1411,21 +1485,20 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XO
     if (use_first && c->p.shared_factor && !replay) { g_err_detail = "the shared first factor is not built"; return LPIPM_ERR_HIP; }
     c->first_done = false;
     if (use_first && !c->p.shared_factor) c->first_valid = false;
+    const Iter ahead{};          // the head that is enqueued ahead of its iteration: never iteration 1's, and a head refines nothing
     for (uint64_t iteration = 1; iteration <= o->max_iter && running > 0; ++iteration) {   // mod.rs:213
-        c->on_first = use_first && iteration == 1;
-        c->skip_factor = c->on_first && replay;
+        const bool on_first = use_first && iteration == 1;
+        const Iter it{.on_first = on_first, .skip_factor = on_first && replay, .refine_now = refine_now};
         if (!speculate) {
-            LP_TRY(enqueue_iteration(c, ip, o));
-            c->on_first = c->skip_factor = false;
+            LP_TRY(enqueue_iteration(c, it, ip, o));
             LP_HIP(hipStreamSynchronize(st));
             prof_collect(c);
         } else {
-            if (!head_out) LP_TRY(enqueue_head(c));
-            LP_TRY(enqueue_tail(c, ip, o));
-            c->on_first = c->skip_factor = false;
+            if (!head_out) LP_TRY(enqueue_head(c, it));
+            LP_TRY(enqueue_tail(c, it, ip, o));
             const size_t marks = rs.nmarks;
             head_out = iteration < o->max_iter;
-            if (head_out) LP_TRY(enqueue_head(c));       // next iteration's A.D.A^T, before this one's status is read
+            if (head_out) LP_TRY(enqueue_head(c, ahead));  // next iteration's A.D.A^T, before this one's status is read
             // the members that were still running when this iteration was enqueued write a record; the others are skipped
             LP_TRY(wait_status(c, act.data(), running));
             prof_collect(c, marks);
@@ -1446,10 +1519,10 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XO
             const int i = act[(size_t)k];
             const StatusRec s = rs.status_host[i];
             const int code = status_code(s);
-            if (!batch && code != LPIPM_NUMERICAL_PROBLEM) {       // (get_delta fails before the row of its iteration exists)
+            if (md.rows && code != LPIPM_NUMERICAL_PROBLEM) {      // (get_delta fails before the row of its iteration exists)
                 if (o->disp) print_row(s.alpha, s);
-                if (log) {
-                    lpipm_iter_row& r = log[iteration - 1];
+                if (out.log) {
+                    lpipm_iter_row& r = out.log[iteration - 1];
                     r.alpha = s.alpha; r.rho_p = s.rho_p; r.rho_d = s.rho_d; r.rho_A = s.rho_A;
                     r.rho_g = s.rho_g; r.rho_mu = s.rho_mu; r.obj = s.obj;
                 }
@@ -1459,86 +1532,41 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, bool batch, const XO
             any_refines = any_refines || (c->refine == 1 && s.rho_mu <= refine_below());
         }
         running = still;
-        c->refine_now = c->refine == 2 || any_refines;
+        refine_now = c->refine == 2 || any_refines;
     }
     for (int i = 0; i < B; ++i)
         if (ret[(size_t)i] < 0) { ret[(size_t)i] = LPIPM_ITERATION_LIMIT; its[(size_t)i] = o->max_iter; }   // mod.rs:237-239
-    // x (mod.rs:231/238, :165): one launch for every LP of a batch; none for a single LP that has no solution
     double* bounced = nullptr;
-    if (batch || has_x(ret[0])) {
-        XRank xrf{xrank_fn, c};
-        LP_TRY(vec_final_x(v, c->p.xout, st, c->colsplit ? &xrf : nullptr));
-        LP_HIP(hipGetLastError());
-        // a scaled problem's x back in the caller's units (fun is the scaled vectors' product: the same number)
-        if (c->p.scale_passes > 0)
-            LP_HIP(launch_unscale_x(c->p.sc, c->p.xout, (int)c->p.n, st, Batch{B, (long long)c->p.bstride, nullptr, c->p.bt.first}));
-        const size_t xbytes = c->p.n * sizeof(double);
-        for (int i = 0; i < B; ++i) {
-            if (!has_x(ret[(size_t)i])) continue;
-            const uint64_t row = rows ? rows[i] : (uint64_t)i;
-            const char* src = (const char*)c->p.xout + (size_t)(c->p.bt.first + i) * c->p.bstride;
-            if (xo.dev) LP_HIP(hipMemcpyAsync(xo.dev + row * xo.stride_bytes, src, xbytes, hipMemcpyDeviceToDevice, st));
-            else if (!xo.host[row]) continue;
-            else if (batch) LP_HIP(hipMemcpyAsync(xo.host[row], src, xbytes, hipMemcpyDeviceToHost, st));
-            else {   // a single LP: through a pinned buffer -- truly asynchronous, one synchronisation for x and the status record
-                if (rs.x_pinned_cap < c->p.n) {
-                    if (rs.x_pinned) (void)hipHostFree(rs.x_pinned);
-                    rs.x_pinned = nullptr; rs.x_pinned_cap = 0;
-                    LP_HIP(hipHostMalloc((void**)&rs.x_pinned, xbytes));
-                    rs.x_pinned_cap = c->p.n;
-                }
-                LP_HIP(hipMemcpyAsync(rs.x_pinned, src, xbytes, hipMemcpyDeviceToHost, st));
-                bounced = xo.host[row];
-            }
-        }
-        LP_TRY(copy_status(c));
-    }
+    LP_TRY(copy_out_x(c, md, ret, out, &bounced));
     if (c->profiling) LP_HIP(hipEventRecord(rs.ev_end, st));
     LP_HIP(hipStreamSynchronize(st));
     if (bounced) std::memcpy(bounced, rs.x_pinned, c->p.n * sizeof(double));
-    if (c->profiling) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, rs.ev_begin, rs.ev_end);
-        c->times.total_ms = ms;
-        // (with what building the shared first factor ahead of this solve took, if it was built)
-        c->times.adat_ms = c->tag_ms[T_ADAT] + c->build_adat_ms; c->times.potrf_ms = c->tag_ms[T_POTRF] + c->build_potrf_ms;
-        c->times.trsv_ms = c->tag_ms[T_TRSV]; c->times.gemv_ms = c->tag_ms[T_GEMV];
-        c->times.vec_ms = c->tag_ms[T_VEC];
-        // launches of the kernel (each covers all B members): iteration 1 on a kept factor made none
-        c->times.adat_launches = loop_iterations - (replay && loop_iterations > 0 ? 1 : 0) + c->build_launches;
-        c->times.iterations = loop_iterations;         // iterations of the loop (= the slowest member's count)
-        // the speculatively enqueued head of the iteration after the last holds no GEMV pass: every counted pass ran
-        c->times.gemv_passes = c->gemv_passes;
-    }
-    c->build_adat_ms = c->build_potrf_ms = 0.0; c->build_launches = 0;    // reported (or not asked for)
-    for (int i = 0; i < B; ++i) {
-        status_out[i] = ret[(size_t)i];
-        if (fun_out) fun_out[i] = has_x(ret[(size_t)i]) ? rs.status_host[i].obj : NAN;
-        if (its_out) its_out[i] = its[(size_t)i];
-    }
+    report_times(c, loop_iterations, replay);
+    for (int i = 0; i < B; ++i)
+        out.res.set((uint64_t)(c->p.bt.first + i), ret[(size_t)i], has_x(ret[(size_t)i]) ? rs.status_host[i].obj : NAN, its[(size_t)i]);
     return LPIPM_OK;
 }
 
-// One LP: the return code is the LP's own, and fun_out stays untouched when it has no solution.
-static int solve_single(lpipm_ctx* c, const lpipm_opts* o, double* x_host, void* x_dev, double* fun_out,
-                        uint64_t* iters_out, lpipm_iter_row* log) {
-    XOut xo; xo.host = &x_host; xo.dev = (char*)x_dev;
+// One LP: the return code is the LP's own, and *fun stays untouched when it has no solution.
+struct SingleOut { double* x_host = nullptr; void* x_dev = nullptr; double* fun = nullptr; uint64_t* its = nullptr; lpipm_iter_row* log = nullptr; };
+static int solve_single(lpipm_ctx* c, const lpipm_opts* o, const SingleOut& s) {
     double fun = NAN;
     uint64_t its = 0;
     int32_t code = LPIPM_OK;
-    LP_TRY(solve_members(c, o, false, xo, nullptr, &fun, &its, &code, log));
-    if (fun_out && has_x(code)) *fun_out = fun;
-    if (iters_out) *iters_out = its;
+    LP_TRY(solve_members(c, o, Members::One, SolveOut{.x = XOut{.host = &s.x_host, .dev = (char*)s.x_dev},
+                                                      .res = Results{&fun, &its, &code}, .log = s.log}));
+    if (s.fun && has_x(code)) *s.fun = fun;
+    if (s.its) *s.its = its;
     return code;
 }
 extern "C" int lpipm_solve(lpipm_ctx* c, const lpipm_opts* o, double* x_slack_out, double* fun_out,
                            uint64_t* iterations_out, lpipm_iter_row* log) {
     if (!x_slack_out) return LPIPM_ERR_BAD_ARGUMENT;
-    return solve_single(c, o, x_slack_out, nullptr, fun_out, iterations_out, log);
+    return solve_single(c, o, {.x_host = x_slack_out, .fun = fun_out, .its = iterations_out, .log = log});
 }
 extern "C" int lpipm_solve_device(lpipm_ctx* c, const lpipm_opts* o, void* x_dev_out, double* fun_out,
                                   uint64_t* iterations_out, lpipm_iter_row* log) {
-    return solve_single(c, o, nullptr, x_dev_out, fun_out, iterations_out, log);
+    return solve_single(c, o, {.x_dev = x_dev_out, .fun = fun_out, .its = iterations_out, .log = log});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1575,11 +1603,10 @@ static lpipm_ctx* make_view(const lpipm_ctx* c, int first, int count) {
 // and arguments of the one-stream path: the results are bit-identical (tests/test_gpu_c4_members.py).  Measured on the C4
 // shard (32 x 1024x2048): +3 .. +6.5 % (profiles/r03_rejected_experiments.txt has the variants).  Not while profiling (the
 // phase marks are per stream) and not for the views themselves.
-static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const XOut& xo, const uint64_t* rows, double* fun_out,
-                          uint64_t* its_out, int32_t* status_out) {
-    if (!c || !o || !xo.valid() || !status_out) return LPIPM_ERR_BAD_ARGUMENT;
+static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const SolveOut& out) {
+    if (!c || !o || !out.res.status) return LPIPM_ERR_BAD_ARGUMENT;      // (out.x is xout_of's: one destination is there)
     if (c->is_view || !c->halves_env || c->profiling || c->p.B < 16 || !c->p.has_problem || c->colsplit)
-        return solve_members(c, o, true, xo, rows, fun_out, its_out, status_out, nullptr);
+        return solve_members(c, o, Members::Lockstep, out);
     LP_HIP(hipSetDevice(c->device));
     if (c->halves.empty()) {
         const int h = c->p.B / 2;
@@ -1587,7 +1614,7 @@ static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const XOut& xo, con
         lpipm_ctx* b = a ? make_view(c, h, c->p.B - h) : nullptr;
         if (!a || !b) {
             if (a) { c->halves.push_back(a); destroy_views(c); }
-            return solve_members(c, o, true, xo, rows, fun_out, its_out, status_out, nullptr);
+            return solve_members(c, o, Members::Lockstep, out);
         }
         c->halves.push_back(a); c->halves.push_back(b);
     }
@@ -1600,15 +1627,7 @@ static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const XOut& xo, con
     for (lpipm_ctx* v : c->halves) { v->first_cache = c->first_cache; v->first_valid = c->first_valid; }
     if (use_first) c->first_valid = false;
     int rc[2] = {LPIPM_OK, LPIPM_OK};
-    // a view numbers its members from 0: member i of half k is member first + i of the batch
-    std::vector<uint64_t> ident;
-    if (!rows) { ident.resize((size_t)c->p.B); for (int i = 0; i < c->p.B; ++i) ident[(size_t)i] = (uint64_t)i; rows = ident.data(); }
-    auto run = [&](int k) {
-        lpipm_ctx* v = c->halves[(size_t)k];
-        const int f = v->p.bt.first;
-        rc[k] = solve_members(v, o, true, xo, rows + f, fun_out ? fun_out + f : nullptr, its_out ? its_out + f : nullptr,
-                              status_out + f, nullptr);
-    };
+    auto run = [&](int k) { rc[k] = solve_members(c->halves[(size_t)k], o, Members::Lockstep, out); };
     std::thread other(run, 1);
     run(0);
     other.join();
@@ -1623,23 +1642,42 @@ extern "C" int lpipm_get_resident_bytes(const lpipm_ctx* c, uint64_t* bytes_out)
 }
 extern "C" int lpipm_solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, double* const* x_slack_out, double* fun_out,
                                     uint64_t* iterations_out, int32_t* status_out) {
-    XOut xo; xo.host = x_slack_out;
-    return solve_lockstep(c, o, xo, nullptr, fun_out, iterations_out, status_out);
+    XOut xo;
+    LP_TRY(xout_of({.host_rows = x_slack_out}, xo));
+    return solve_lockstep(c, o, SolveOut{.x = xo, .res = Results{fun_out, iterations_out, status_out}});
 }
 extern "C" int lpipm_solve_lockstep_device(lpipm_ctx* c, const lpipm_opts* o, void* x_dev_out, uint64_t row_stride,
                                            double* fun_out, uint64_t* iterations_out, int32_t* status_out) {
-    if (!c || !x_dev_out || row_stride < c->p.n) return LPIPM_ERR_BAD_ARGUMENT;
-    XOut xo; xo.dev = (char*)x_dev_out; xo.stride_bytes = row_stride * sizeof(double);
-    return solve_lockstep(c, o, xo, nullptr, fun_out, iterations_out, status_out);
+    // (a row's length is the resident problem's: this entry looks at its context before its destination, the others after)
+    if (!c) return LPIPM_ERR_BAD_ARGUMENT;
+    XOut xo;
+    LP_TRY(xout_of({.dev = x_dev_out, .row_stride = row_stride}, xo, 1, [&](uint64_t) { return c->p.n; }));
+    return solve_lockstep(c, o, SolveOut{.x = xo, .res = Results{fun_out, iterations_out, status_out}});
 }
 
-// Bytes one member of a lockstep batch of 32 of this shape occupies: the real layout (a measuring pass of layout_problem over
-// its geometry), not a formula that drifts from it.  No kept first factor: a chunk is uploaded, solved once and replaced.
-// n_slack: the member's (verified) structural hint -- its slack columns are not resident.  tall: the member is m x n in the
-// tall inequality form (n structural columns, every slack column implied).
-static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, uint64_t m, uint64_t n, uint64_t n_slack, bool tall) {
-    const Geometry g = tall ? geometry_of(Upload{.count = 32, .m = m, .n = n + m, .tall = true, .keep_ok = false}, m, c->first_cache, c->refine)
-                            : geometry_of(Upload{.count = 32, .m = m, .n = n, .keep_ok = false}, n_slack, c->first_cache, c->refine);
+// A shard of independent LPs on one device: what the four lpipm_solve_batch* entries ask of batch_impl.  Dense members: A[i] is
+// m[i] x n[i] in slack form (lda = n[i]), with member i's structural hint n_slack[i] (lpipm_upload_slack; nullable = all 0).
+// Tall members (lpipm_solve_batch_ub_tall): pure-`ub` LPs in the tall inequality form -- A[i] is m[i] x n[i] with lda = n[i],
+// b[i] has m[i] entries, c[i] the n[i] structural costs, x n[i] + m[i] entries; no hint.
+struct BatchRequest {
+    bool tall = false;                   // the members' form
+    uint64_t count = 0;
+    const uint64_t *m = nullptr, *n = nullptr, *n_slack = nullptr;
+    const double *const *A = nullptr, *const *b = nullptr, *const *c = nullptr;
+    const double* c0 = nullptr;          // nullable: all zero
+    // _slack and _ub_tall, which take either destination of x, refuse a call without one before anything else; the other two
+    // entries let a call of no members and no destination through to batch_impl's own checks (nothing to do: Ok)
+    bool x_always = false;
+    bool has_lens() const { return n && (!tall || m); }
+    uint64_t row_len(uint64_t i) const { return n[i] + (tall ? m[i] : 0); }     // doubles of member i's x
+};
+
+// Bytes member i of a batch request would occupy in a lockstep batch of 32 of its shape: the real layout (a measuring pass
+// of layout_problem over its geometry), not a formula that drifts from it.  No kept first factor: a chunk is uploaded, solved
+// once and replaced.  n_slack: the member's verified hint -- its slack columns are not resident (a tall member's never are).
+static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, const BatchRequest& q, uint64_t i, uint64_t n_slack) {
+    const uint64_t m = q.m[i], n = q.row_len(i);
+    const Geometry g = geometry_of(Upload{.count = 32, .m = m, .n = n, .tall = q.tall, .keep_ok = false}, q.tall ? m : n_slack, c->first_cache, c->refine);
     Problem t;
     set_geometry(t, g);
     FactorPlan fp, fp1;
@@ -1649,144 +1687,92 @@ static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, uint64_t m, uint64_t n, 
     return (size_t)round_up(measure.off, 4096);
 }
 
-// A shard of independent LPs on one device.
-//  1. Members of one shape (>= 2 of them, Cholesky arm) are solved as lockstep batches, in chunks that fit
-//     the memory budget: one launch per kernel for the whole chunk.
-//  2. The rest (odd shapes, QR arms) are latency-bound one by one (the factorisation's diagonal chain
-//     keeps 1 of 256 CUs busy), so `batch_concurrency` contexts -- each with its own stream and buffers,
-//     each driven by its own host thread -- solve different members at the same time; independent
-//     streams need no cross-stream synchronisation.  Members are handed out through an atomic counter.
-// Every member's result depends only on its own inputs.
-// n_slack (nullable = all 0): member i's structural hint (lpipm_upload_slack).  Each is verified here first; members are
-// grouped by the hint that holds as well as by shape, and both upload paths pass it on.
-// tall (lpipm_solve_batch_ub_tall): the members are pure-`ub` LPs in the tall inequality form -- A[i] is m[i] x n[i] with
-// lda = n[i], b[i] has m[i] entries, c[i] the n[i] structural costs, x n[i] + m[i] entries, and there is no hint.  A group is
-// then a tall batch whose members own their matrices, a single member a tall upload; everything else is the same body.
-static int batch_impl(lpipm_ctx* c, bool tall, uint64_t count, const uint64_t* m, const uint64_t* n, const uint64_t* n_slack,
-                      const double* const* A, const double* const* b, const double* const* cc,
-                      const double* c0, const lpipm_opts* o, const XOut& xo,
-                      double* fun_out, uint64_t* iterations_out, int32_t* status_out) {
-    if (!c || !o || (count && (!m || !n || !A || !b || !cc || !xo.valid() || !status_out)))
-        return LPIPM_ERR_BAD_ARGUMENT;
-    // the hint that holds, per member: verified here, once (the uploads below are told so).  A hint larger than the member's
-    // n or m is that member's error, as it is lpipm_upload_slack's: the member is refused here and takes no further part.
-    std::vector<uint64_t> ns(count, 0);
-    std::vector<char> taken(count, 0);              // in a lockstep group, or refused
-    for (uint64_t i = 0; i < count && n_slack; ++i) {
-        if (m[i] == 0 || n_slack[i] == 0 || !A[i]) continue;          // (Unconstrained / a null A: the upload's answer)
-        if (n_slack[i] > n[i] || n_slack[i] > m[i]) {
-            taken[i] = 1;
-            status_out[i] = LPIPM_ERR_BAD_ARGUMENT;
-            if (fun_out) fun_out[i] = NAN;
-            if (iterations_out) iterations_out[i] = 0;
-        } else if (slack_hint_holds(1, m[i], n[i], &A[i], n[i], n_slack[i])) ns[i] = n_slack[i];
+// The upload of the members idx[k0 .. k0 + g) -- one shape, one verified hint ns -- with the arrays its request points into:
+// a lockstep chunk, or (g == 1) a member solved alone.  Tall: a chunk is a batch whose members own their matrices, a member
+// alone the tall LP of lpipm_upload_ub_tall itself (a batch of one would not be the same resident problem).
+struct MemberUpload {
+    std::vector<const double*> A, b, c;
+    std::vector<double> c0;
+    Upload u;
+    MemberUpload() = default;
+    MemberUpload(MemberUpload&&) = default;      // u points into the vectors' storage, which moves with them: moved, never copied
+};
+static MemberUpload member_upload(const BatchRequest& q, const std::vector<uint64_t>& idx, size_t k0, size_t g, uint64_t ns) {
+    MemberUpload r;
+    r.A.resize(g); r.b.resize(g); r.c.resize(g); r.c0.assign(g, 0.0);
+    for (size_t k = 0; k < g; ++k) {
+        const uint64_t j = idx[k0 + k];
+        r.A[k] = q.A[j]; r.b[k] = q.b[j]; r.c[k] = q.c[j];
+        if (q.c0) r.c0[k] = q.c0[j];
     }
-    std::vector<uint64_t> rest;                      // members left to the one-by-one path
-    if (c->lockstep_max != 0 && o->solver_type == LPIPM_SOLVER_CHOLESKY) {
-        LP_HIP(hipSetDevice(c->device));
-        for (uint64_t i = 0; i < count; ++i) {
-            if (taken[i]) continue;
-            std::vector<uint64_t> grp;
-            for (uint64_t j = i; j < count; ++j)
-                if (!taken[j] && m[j] == m[i] && n[j] == n[i] && ns[j] == ns[i]) grp.push_back(j);
-            if (grp.size() < 2) continue;
-            for (uint64_t j : grp) taken[j] = 1;
-            // chunk size: the configured maximum, and what fits in ~60 % of the free memory (two chunks are
-            // resident: one being solved, the next one being uploaded)
-            size_t free_b = 0, total_b = 0;
-            LP_HIP(hipMemGetInfo(&free_b, &total_b));
-            free_b += c->p.arena_bytes;                // the current arena is released before the next one is made
-            const double per_lp = (double)lockstep_bytes_per_lp(c, m[i], n[i], ns[i], tall);
-            size_t chunk;
-            if (c->lockstep_max > 0) chunk = (size_t)c->lockstep_max;
-            else if (grp.size() > 32) chunk = 32;
-            else if (grp.size() >= 16) chunk = (grp.size() + 1) / 2;   // two chunks: the second upload hides behind the first solve
-            else chunk = grp.size();
-            const size_t fit = (size_t)(0.3 * (double)free_b / per_lp);
-            if (chunk > fit) chunk = fit;
-            if (chunk < 2) { for (uint64_t j : grp) rest.push_back(j); continue; }
-            // chunks of the group; a last chunk of one member goes to the one-by-one path
-            struct Chunk { size_t k0, g; std::vector<const double*> A, b, c; std::vector<double> c0; };
-            std::vector<Chunk> chunks;
-            for (size_t k0 = 0; k0 < grp.size(); k0 += chunk) {
-                const size_t g = (k0 + chunk < grp.size() ? k0 + chunk : grp.size()) - k0;
-                if (g < 2) { rest.push_back(grp[k0]); continue; }
-                Chunk ch{k0, g, std::vector<const double*>(g), std::vector<const double*>(g), std::vector<const double*>(g),
-                         std::vector<double>(g, 0.0)};
-                for (size_t k = 0; k < g; ++k) {
-                    const uint64_t j = grp[k0 + k];
-                    ch.A[k] = A[j]; ch.b[k] = b[j]; ch.c[k] = cc[j];
-                    if (c0) ch.c0[k] = c0[j];
-                }
-                chunks.push_back(std::move(ch));
-            }
-            // Pipeline over two contexts: while chunk q is being solved on one, a helper thread uploads
-            // chunk q+1 into the other (host staging + copy engine vs. compute: the PCIe time of a large
-            // batch hides behind the solves).
-            lpipm_ctx* pipe[2] = {c, nullptr};
-            if (chunks.size() > 1) {
-                if (c->workers.empty()) {
-                    lpipm_ctx* w = nullptr;
-                    const int rcw = lpipm_create(c->device, &w);
-                    if (rcw != LPIPM_OK) return rcw;
-                    c->workers.push_back(w);
-                }
-                pipe[1] = c->workers[0];
-            }
-            auto upload_chunk = [&](lpipm_ctx* w, const Chunk& ch) -> int {
-                (void)hipSetDevice(w->device);
-                w->scaling = c->scaling;
-                if (tall) return upload_impl(w, owned_tall_request(ch.g, n[i], m[i], ch.A.data(), n[i], ch.b.data(), ch.c.data(), ch.c0.data()));
-                return upload_impl(w, Upload{.count = ch.g, .m = m[i], .n = n[i], .n_slack = ns[i], .A = ch.A.data(), .lda = n[i], .b = ch.b.data(),
-                                             .c = ch.c.data(), .c0 = ch.c0.data(), .hint_verified = true, .keep_ok = false});
-            };
-            int rc_up = chunks.empty() ? LPIPM_OK : upload_chunk(pipe[0], chunks[0]);
-            for (size_t q = 0; q < chunks.size(); ++q) {
-                const Chunk& ch = chunks[q];
-                lpipm_ctx* w = pipe[q & 1];
-                int rc_next = LPIPM_OK;
-                std::thread up;
-                if (q + 1 < chunks.size()) up = std::thread([&, q] { rc_next = upload_chunk(pipe[(q + 1) & 1], chunks[q + 1]); });
-                const size_t g = ch.g;
-                std::vector<double> gfun(g, NAN);
-                std::vector<uint64_t> gits(g, 0), grow(g);
-                std::vector<int32_t> gst(g, 0);
-                for (size_t k = 0; k < g; ++k) grow[k] = grp[ch.k0 + k];
-                int rc = rc_up;
-                if (rc == LPIPM_OK) rc = solve_lockstep(w, o, xo, grow.data(), gfun.data(), gits.data(), gst.data());
-                if (up.joinable()) up.join();
-                if (rc >= 100) return rc;            // runtime failure: nothing sensible to continue with
-                for (size_t k = 0; k < g; ++k) {
-                    const uint64_t j = grp[ch.k0 + k];
-                    status_out[j] = rc == LPIPM_OK ? gst[k] : rc;     // e.g. Unconstrained / InvalidParameter for all
-                    if (fun_out) fun_out[j] = rc == LPIPM_OK ? gfun[k] : NAN;
-                    if (iterations_out) iterations_out[j] = rc == LPIPM_OK ? gits[k] : 0;
-                }
-                rc_up = rc_next;
-            }
-        }
-        for (uint64_t i = 0; i < count; ++i)
-            if (!taken[i]) rest.push_back(i);
-    } else {
-        for (uint64_t i = 0; i < count; ++i)
-            if (!taken[i]) rest.push_back(i);
+    const uint64_t m = q.m[idx[k0]], n = q.n[idx[k0]];
+    if (!q.tall) r.u = Upload{.count = g, .m = m, .n = n, .n_slack = ns, .A = r.A.data(), .lda = n, .b = r.b.data(), .c = r.c.data(),
+                                .c0 = r.c0.data(), .hint_verified = true, .keep_ok = false};
+    else if (g > 1) r.u = owned_tall_request(g, n, m, r.A.data(), n, r.b.data(), r.c.data(), r.c0.data());
+    else            r.u = tall_request(n, m, r.A[0], n, r.b[0], r.c.data(), r.c0.data());
+    return r;
+}
+
+// At least `count` worker contexts beside c: each with its own stream and buffers, kept until lpipm_destroy.
+static int ensure_workers(lpipm_ctx* c, size_t count) {
+    while (c->workers.size() < count) {
+        lpipm_ctx* w = nullptr;
+        LP_TRY(lpipm_create(c->device, &w));
+        c->workers.push_back(w);
     }
+    return LPIPM_OK;
+}
+// One group's chunks (split_chunks) as lockstep batches, through a pipeline over two contexts: while chunk k is being solved on
+// one, a helper thread uploads chunk k+1 into the other (host staging + copy engine vs. compute: the PCIe time of a large batch
+// hides behind the solves).  A chunk refused as a whole (Unconstrained, ...) gives every member that code; a runtime failure ends the call.
+static int solve_chunks(lpipm_ctx* c, const BatchRequest& q, const std::vector<uint64_t>& grp, uint64_t ns, const std::vector<Span>& spans,
+                        const lpipm_opts* o, const XOut& xo, const Results& res) {
+    std::vector<MemberUpload> ups;
+    ups.reserve(spans.size());
+    for (const Span& s : spans) ups.push_back(member_upload(q, grp, s.k0, s.g, ns));
+    if (spans.size() > 1) LP_TRY(ensure_workers(c, 1));
+    lpipm_ctx* pipe[2] = {c, spans.size() > 1 ? c->workers[0] : nullptr};
+    auto upload = [&](size_t k) -> int {
+        lpipm_ctx* w = pipe[k & 1];
+        (void)hipSetDevice(w->device);
+        w->scaling = c->scaling;
+        return upload_impl(w, ups[k].u);
+    };
+    int rc_up = spans.empty() ? LPIPM_OK : upload(0);
+    for (size_t k = 0; k < spans.size(); ++k) {
+        const Span& s = spans[k];
+        int rc_next = LPIPM_OK;
+        std::thread up;
+        if (k + 1 < spans.size()) up = std::thread([&, k] { rc_next = upload(k + 1); });
+        std::vector<double> gfun(s.g, NAN);
+        std::vector<uint64_t> gits(s.g, 0);
+        std::vector<int32_t> gst(s.g, 0);
+        int rc = rc_up;
+        if (rc == LPIPM_OK)      // (member i of the chunk is member grp[k0 + i] of the call: that row of x)
+            rc = solve_lockstep(pipe[k & 1], o, SolveOut{.x = xo, .rows = grp.data() + s.k0, .res = Results{gfun.data(), gits.data(), gst.data()}});
+        if (up.joinable()) up.join();
+        if (rc >= 100) return rc;
+        for (size_t i = 0; i < s.g; ++i)
+            rc == LPIPM_OK ? res.set(grp[s.k0 + i], gst[i], gfun[i], gits[i]) : res.set(grp[s.k0 + i], rc);
+        rc_up = rc_next;
+    }
+    return LPIPM_OK;
+}
+
+// The members left over, one by one.  They are latency-bound (the factorisation's diagonal chain keeps 1 of 256 CUs busy), so
+// `batch_concurrency` contexts -- each with its own stream and buffers, each driven by its own host thread -- solve different
+// members at the same time, handed out through an atomic counter.  -> the first runtime failure (which ends the handing out) or Ok.
+static int solve_rest(lpipm_ctx* c, const BatchRequest& q, const std::vector<uint64_t>& ns, const std::vector<uint64_t>& rest,
+                      const lpipm_opts* o, const XOut& xo, const Results& res) {
     if (rest.empty()) return LPIPM_OK;
     int nworkers = c->batch_concurrency;
-    if (nworkers == 0) {   // auto: latency-bound sizes gain ~3x from 4-8 members in flight (measured at
-                           // 1024x2048: 165 -> 513 LP/s); sizes that fill the chip by themselves do not
+    if (nworkers == 0) {   // auto: latency-bound sizes gain ~3x from 4-8 members in flight (1024x2048: 165 -> 513 LP/s); others do not
         uint64_t mmax = 0;
-        for (uint64_t i : rest) mmax = m[i] > mmax ? m[i] : mmax;
+        for (uint64_t i : rest) mmax = q.m[i] > mmax ? q.m[i] : mmax;
         nworkers = mmax <= 2048 ? 8 : 2;
     }
     if ((size_t)nworkers > rest.size()) nworkers = (int)rest.size();
-    if (nworkers < 1) nworkers = 1;
-    while ((int)c->workers.size() < nworkers - 1) {
-        lpipm_ctx* w = nullptr;
-        const int rc = lpipm_create(c->device, &w);
-        if (rc != LPIPM_OK) return rc;
-        c->workers.push_back(w);
-    }
+    LP_TRY(ensure_workers(c, (size_t)nworkers - 1));
     std::atomic<uint64_t> next{0};
     std::atomic<int> fatal{LPIPM_OK};
     auto run = [&](lpipm_ctx* w) {
@@ -1798,18 +1784,15 @@ static int batch_impl(lpipm_ctx* c, bool tall, uint64_t count, const uint64_t* m
             const uint64_t k = next.fetch_add(1);
             if (k >= rest.size() || fatal.load() != LPIPM_OK) break;
             const uint64_t i = rest[k];
-            const double c0i = c0 ? c0[i] : 0.0;
-            int rc = tall ? lpipm_upload_ub_tall(w, n[i], m[i], A[i], n[i], b[i], cc[i], c0i)
-                          : upload_impl(w, Upload{.m = m[i], .n = n[i], .n_slack = ns[i], .A = &A[i], .lda = n[i], .b = &b[i], .c = &cc[i],
-                                                  .c0 = &c0i, .hint_verified = true, .keep_ok = false});
+            const MemberUpload up = member_upload(q, rest, k, 1, ns[i]);
+            int rc = upload_impl(w, up.u);
             double fun = NAN;
             uint64_t it = 0;
+            if (rc == LPIPM_OK && !xo.dev && !xo.host[i]) rc = LPIPM_ERR_BAD_ARGUMENT;      // as lpipm_solve: a host row is not optional
             if (rc == LPIPM_OK)
-                rc = xo.dev ? solve_single(w, &opts, nullptr, xo.dev + i * xo.stride_bytes, &fun, &it, nullptr)
-                            : lpipm_solve(w, &opts, xo.host[i], &fun, &it, nullptr);
-            status_out[i] = rc;
-            if (fun_out) fun_out[i] = fun;
-            if (iterations_out) iterations_out[i] = it;
+                rc = solve_single(w, &opts, {.x_host = xo.dev ? nullptr : xo.host[i],
+                                             .x_dev = xo.dev ? xo.dev + i * xo.stride_bytes : nullptr, .fun = &fun, .its = &it});
+            res.set(i, rc, fun, it);
             if (rc >= 100) { int expected = LPIPM_OK; fatal.compare_exchange_strong(expected, rc); }
         }
     };
@@ -1820,52 +1803,67 @@ static int batch_impl(lpipm_ctx* c, bool tall, uint64_t count, const uint64_t* m
     return fatal.load();
 }
 
+//  1. Every member's hint is verified (verify_hints); a member whose hint is out of range is refused and takes no further part.
+//  2. Members of one shape and one hint that holds (>= 2 of them, Cholesky arm) are solved as lockstep batches, in chunks that
+//     fit the memory budget: one launch per kernel for the whole chunk (group_members, chunk_size, split_chunks, solve_chunks).
+//  3. The rest (odd shapes, a chunk's odd member, QR arms) go one by one through the worker pool (solve_rest).
+// Every member's result depends only on its own inputs.  The planning of 1 and 2 touches no device (batch_plan.hpp).
+static int batch_impl(lpipm_ctx* c, const BatchRequest& q, const lpipm_opts* o, const XArgs& xa, const Results& res) {
+    XOut xo;
+    if (q.x_always || q.count || xa.host_rows || xa.dev)
+        LP_TRY(xout_of(xa, xo, q.has_lens() ? q.count : 0, [&](uint64_t i) { return q.row_len(i); }));
+    if (!c || !o || (q.count && (!q.m || !q.n || !q.A || !q.b || !q.c || !res.status))) return LPIPM_ERR_BAD_ARGUMENT;
+    std::vector<char> taken(q.count, 0);             // refused, or in a lockstep group
+    const std::vector<uint64_t> ns = verify_hints(q.count, q.m, q.n, q.n_slack, q.A, taken);
+    for (uint64_t i = 0; i < q.count; ++i)
+        if (taken[i]) res.set(i, LPIPM_ERR_BAD_ARGUMENT);
+    std::vector<uint64_t> rest;                      // members left to the one-by-one path
+    if (c->lockstep_max != 0 && o->solver_type == LPIPM_SOLVER_CHOLESKY) {
+        LP_HIP(hipSetDevice(c->device));
+        for (const std::vector<uint64_t>& grp : group_members(q.count, q.m, q.n, ns, taken)) {
+            const uint64_t first = grp[0];
+            // what fits in ~60 % of the free memory: two chunks are resident, one being solved, the next one being uploaded
+            size_t free_b = 0, total_b = 0;
+            LP_HIP(hipMemGetInfo(&free_b, &total_b));
+            free_b += c->p.arena_bytes;                // the current arena is released before the next one is made
+            const size_t fit = (size_t)(0.3 * (double)free_b / (double)lockstep_bytes_per_lp(c, q, first, ns[first]));
+            const std::vector<Span> spans = split_chunks(grp, chunk_size(grp.size(), c->lockstep_max, fit), rest);
+            LP_TRY(solve_chunks(c, q, grp, ns[first], spans, o, xo, res));
+        }
+    }
+    for (uint64_t i = 0; i < q.count; ++i)
+        if (!taken[i]) rest.push_back(i);
+    return solve_rest(c, q, ns, rest, o, xo, res);
+}
+
 extern "C" int lpipm_solve_batch(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uint64_t* n,
                                  const double* const* A, const double* const* b, const double* const* cc,
                                  const double* c0, const lpipm_opts* o, double* const* x_slack_out,
                                  double* fun_out, uint64_t* iterations_out, int32_t* status_out) {
-    XOut xo; xo.host = x_slack_out;
-    return batch_impl(c, false, count, m, n, nullptr, A, b, cc, c0, o, xo, fun_out, iterations_out, status_out);
+    return batch_impl(c, BatchRequest{.count = count, .m = m, .n = n, .A = A, .b = b, .c = cc, .c0 = c0}, o,
+                      XArgs{.host_rows = x_slack_out}, Results{fun_out, iterations_out, status_out});
 }
 extern "C" int lpipm_solve_batch_device(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uint64_t* n,
                                         const double* const* A, const double* const* b, const double* const* cc,
                                         const double* c0, const lpipm_opts* o, void* x_dev_out, uint64_t row_stride,
                                         double* fun_out, uint64_t* iterations_out, int32_t* status_out) {
-    if (count && !x_dev_out) return LPIPM_ERR_BAD_ARGUMENT;
-    for (uint64_t i = 0; i < count && n; ++i)
-        if (n[i] > row_stride) return LPIPM_ERR_BAD_ARGUMENT;
-    XOut xo; xo.dev = (char*)x_dev_out; xo.stride_bytes = row_stride * sizeof(double);
-    return batch_impl(c, false, count, m, n, nullptr, A, b, cc, c0, o, xo, fun_out, iterations_out, status_out);
+    return batch_impl(c, BatchRequest{.count = count, .m = m, .n = n, .A = A, .b = b, .c = cc, .c0 = c0}, o,
+                      XArgs{.dev = x_dev_out, .row_stride = row_stride}, Results{fun_out, iterations_out, status_out});
 }
-
 extern "C" int lpipm_solve_batch_slack(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uint64_t* n, const uint64_t* n_slack,
                                        const double* const* A, const double* const* b, const double* const* cc,
                                        const double* c0, const lpipm_opts* o, double* const* x_slack_out, void* x_dev_out,
                                        uint64_t row_stride, double* fun_out, uint64_t* iterations_out, int32_t* status_out) {
-    if ((x_slack_out != nullptr) == (x_dev_out != nullptr)) return LPIPM_ERR_BAD_ARGUMENT;
-    XOut xo;
-    if (x_slack_out) xo.host = x_slack_out;
-    else {
-        for (uint64_t i = 0; i < count && n; ++i)
-            if (n[i] > row_stride) return LPIPM_ERR_BAD_ARGUMENT;
-        xo.dev = (char*)x_dev_out; xo.stride_bytes = row_stride * sizeof(double);
-    }
-    return batch_impl(c, false, count, m, n, n_slack, A, b, cc, c0, o, xo, fun_out, iterations_out, status_out);
+    return batch_impl(c, BatchRequest{.count = count, .m = m, .n = n, .n_slack = n_slack, .A = A, .b = b, .c = cc, .c0 = c0, .x_always = true}, o,
+                      XArgs{.host_rows = x_slack_out, .dev = x_dev_out, .row_stride = row_stride}, Results{fun_out, iterations_out, status_out});
 }
-
 extern "C" int lpipm_solve_batch_ub_tall(lpipm_ctx* c, uint64_t count, const uint64_t* m_ub, const uint64_t* n,
                                          const double* const* A_ub, const double* const* b_ub, const double* const* cc,
                                          const double* c0, const lpipm_opts* o, double* const* x_slack_out, void* x_dev_out,
                                          uint64_t row_stride, double* fun_out, uint64_t* iterations_out, int32_t* status_out) {
-    if ((x_slack_out != nullptr) == (x_dev_out != nullptr)) return LPIPM_ERR_BAD_ARGUMENT;
-    XOut xo;
-    if (x_slack_out) xo.host = x_slack_out;
-    else {
-        for (uint64_t i = 0; i < count && n && m_ub; ++i)
-            if (n[i] + m_ub[i] > row_stride) return LPIPM_ERR_BAD_ARGUMENT;
-        xo.dev = (char*)x_dev_out; xo.stride_bytes = row_stride * sizeof(double);
-    }
-    return batch_impl(c, true, count, m_ub, n, nullptr, A_ub, b_ub, cc, c0, o, xo, fun_out, iterations_out, status_out);
+    return batch_impl(c, BatchRequest{.tall = true, .count = count, .m = m_ub, .n = n, .A = A_ub, .b = b_ub, .c = cc, .c0 = c0,
+                                      .x_always = true}, o,
+                      XArgs{.host_rows = x_slack_out, .dev = x_dev_out, .row_stride = row_stride}, Results{fun_out, iterations_out, status_out});
 }
 
 extern "C" int lpipm_set_batch_lockstep(lpipm_ctx* c, int max_group) {
@@ -2062,7 +2060,7 @@ extern "C" int lpipm_k_adat(lpipm_ctx* c, const double* dinv, double* M_out, int
     if (c->p.tall) return LPIPM_ERR_UNSUPPORTED;           // a tall upload has no M (lpipm_k_tall_normal returns K)
     LP_HIP(hipSetDevice(c->device));
     LP_HIP(hipMemcpyAsync(c->p.va.dinv, dinv, c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
-    LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int { LP_HIP(run_adat(c, Batch{})); return LPIPM_OK; }));
+    LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int { LP_HIP(run_adat(c, Iter{}, Batch{})); return LPIPM_OK; }));
     LP_HIP(hipMemcpy2DAsync(M_out, c->p.m * sizeof(double), c->p.M, (size_t)c->p.mp * sizeof(double),
                             c->p.m * sizeof(double), c->p.m, hipMemcpyDeviceToHost, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
@@ -2361,7 +2359,7 @@ extern "C" int lpipm_k_iteration(lpipm_ctx* c, const lpipm_opts* o, int ip, doub
     LP_HIP(hipSetDevice(c->device));
     VecArgs& v = c->p.va;
     hipStream_t st = c->rs.st;
-    c->refine_now = c->refine == 2;
+    const Iter it{.refine_now = c->refine == 2};
     vec_blind_start(v, st);                                   // clears done / flags; the iterate is overwritten next
     LP_HIP(hipMemcpyAsync(v.x, x, c->p.n * sizeof(double), hipMemcpyHostToDevice, st));
     LP_HIP(hipMemcpyAsync(v.y, y, c->p.m * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2370,7 +2368,7 @@ extern "C" int lpipm_k_iteration(lpipm_ctx* c, const lpipm_opts* o, int ip, doub
     LP_HIP(hipMemcpyAsync(v.S + S_TAU, &tk[0], sizeof(double), hipMemcpyHostToDevice, st));
     LP_HIP(hipMemcpyAsync(v.S + S_KAPPA, &tk[1], sizeof(double), hipMemcpyHostToDevice, st));
     LP_TRY(enqueue_residuals(c, 1, ip ? 1 : 0, o->tol));      // r_P, r_D, r_G, mu at the point
-    LP_TRY(enqueue_iteration(c, ip ? 1 : 0, o));
+    LP_TRY(enqueue_iteration(c, it, ip ? 1 : 0, o));
     double sc[S_COUNT];
     LP_HIP(hipMemcpyAsync(sc, v.S, sizeof(sc), hipMemcpyDeviceToHost, st));
     LP_HIP(hipMemcpyAsync(x, v.x, c->p.n * sizeof(double), hipMemcpyDeviceToHost, st));
