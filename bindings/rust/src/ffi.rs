@@ -34,6 +34,51 @@ pub struct lpipm_iter_row {
     pub obj: f64,
 }
 
+/// include/lpipm.h `lpipm_dev_matrix`: a strided matrix in device memory (strides in elements of the source type)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct lpipm_dev_matrix {
+    pub ptr: *const c_void,
+    pub row_stride: i64,
+    pub col_stride: i64,
+    pub member_stride: i64,
+}
+
+/// include/lpipm.h `lpipm_dev_vector`
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct lpipm_dev_vector {
+    pub ptr: *const c_void,
+    pub stride: i64,
+    pub member_stride: i64,
+}
+
+/// include/lpipm.h `lpipm_device_problem`: what lpipm_upload_device makes resident (struct_size = size_of::<Self>())
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct lpipm_device_problem {
+    pub struct_size: u32,
+    pub form: u32,
+    pub src_type: u32,
+    pub shared: u32,
+    pub count: u64,
+    pub m: u64,
+    pub m_eq: u64,
+    pub n: u64,
+    pub n_slack: u64,
+    pub a: lpipm_dev_matrix,
+    pub a_eq: lpipm_dev_matrix,
+    pub b: lpipm_dev_vector,
+    pub c: lpipm_dev_vector,
+    pub c0: *const f64,
+}
+
+pub const LPIPM_FORM_SLACK: u32 = 0;
+pub const LPIPM_FORM_UB_EQ: u32 = 1;
+pub const LPIPM_FORM_UB_TALL: u32 = 2;
+pub const LPIPM_SRC_F64: u32 = 0;
+pub const LPIPM_SRC_F32: u32 = 1;
+
 pub const LPIPM_OK: c_int = 0;
 pub const LPIPM_UNCONSTRAINED: c_int = 1;
 pub const LPIPM_NUMERICAL_PROBLEM: c_int = 2;
@@ -129,6 +174,19 @@ extern "C" {
     ) -> c_int;
     pub fn lpipm_update_lockstep_vectors_device(
         ctx: *mut lpipm_ctx, count: u64, b_dev: *const c_void, ldb: u64, c_dev: *const c_void, ldc: u64, c0: *const f64,
+    ) -> c_int;
+    // Any of the uploads above from DEVICE memory, strided, double or float: (form, shared, count) select the host entry the
+    // call is equivalent to; every source pointer is checked against its allocation before anything is launched.
+    pub fn lpipm_upload_device(ctx: *mut lpipm_ctx, d: *const lpipm_device_problem) -> c_int;
+    // lpipm_update_vectors with b[m], c[n] (doubles, contiguous) in device memory.
+    pub fn lpipm_update_vectors_device(ctx: *mut lpipm_ctx, b_dev: *const c_void, c_dev: *const c_void) -> c_int;
+    // Test hook: the top-left rows x cols of member's padded resident image (mp x npa) to the host.
+    pub fn lpipm_k_resident_matrix(
+        ctx: *mut lpipm_ctx, member: u64, rows: u64, cols: u64, out: *mut f64, ld: u64, mp_out: *mut u64, npa_out: *mut u64,
+    ) -> c_int;
+    // Measuring hook: the launch that packs A, `repeats` times between two events, beside the runtime's copy of as many bytes.
+    pub fn lpipm_k_pack_matrix(
+        ctx: *mut lpipm_ctx, d: *const lpipm_device_problem, repeats: c_int, pack_ms_out: *mut f64, copy_ms_out: *mut f64,
     ) -> c_int;
     // lpipm_solve_batch with a per-member hint (n_slack nullable); exactly one of x_slack_out and x_dev_out is non-null.
     pub fn lpipm_solve_batch_slack(

@@ -355,6 +355,65 @@ int lpipm_upload_lockstep_shared_ub_tall(lpipm_ctx* ctx, uint64_t count, uint64_
 int lpipm_upload_lockstep_ub_tall(lpipm_ctx* ctx, uint64_t count, uint64_t n, uint64_t m_ub, const double* const* A_ub,
                                   uint64_t lda_ub, const double* const* b, const double* const* c,
                                   const double* c0 /* nullable */);
+/* ---- problems that are already in device memory ----------------------------------------------------------
+ * Every upload above reads the caller's HOST arrays.  lpipm_upload_device makes the same problems resident from DEVICE memory
+ * -- a torch model's cut sets, a design matrix a kernel built, members sliced out of one big tensor -- with no host copy of A,
+ * b or c: one descriptor covers every form the host entries cover.
+ *   form, shared, count select the host entry the call is equivalent to:
+ *     SLACK    shared 0  count 1    lpipm_upload_slack                    UB_TALL  shared 0  count 1    lpipm_upload_ub_tall
+ *     SLACK    shared 0  count > 1  lpipm_upload_lockstep_slack           UB_TALL  shared 0  count > 1  lpipm_upload_lockstep_ub_tall
+ *     SLACK    shared 1  any        lpipm_upload_lockstep_shared_slack    UB_TALL  shared 1  any        lpipm_upload_lockstep_shared_ub_tall
+ *     UB_EQ    shared 0  count 1    lpipm_upload_ub_eq                    UB_EQ    shared 1  any        lpipm_upload_lockstep_shared_ub_eq
+ *   (UB_EQ members with their own matrices have no host entry: LPIPM_ERR_UNSUPPORTED).  After a successful call the context is
+ *   in exactly the state that entry leaves for the same numbers -- geometry, lpipm_get_resident_bytes, scaling exponents, the
+ *   kept first factor -- and every later call (solves, lpipm_update_vectors, lpipm_update_lockstep_vectors[_device],
+ *   lpipm_get_scaling, the lpipm_k_* entries) gives the same bits and the same return codes: an upload is a copy.
+ * Source layout.  Element (i, j) of member k of a matrix is at ptr + k * member_stride + i * row_stride + j * col_stride
+ *   ELEMENTS (of src_type: LPIPM_SRC_F32 is widened to double, which is exact); element i of member k of a vector at
+ *   ptr + k * member_stride + i * stride.  Every stride that is read must be >= 1; member_stride is not read for a shared
+ *   matrix or count == 1.  A row-major block with a leading dimension, a column-major one and a slice of a larger tensor all go
+ *   in as they are; ptr needs no alignment beyond its element type's.  b of member k: m entries (UB_EQ: [b_ub; b_eq],
+ *   m + m_eq); c: n entries (UB_EQ / UB_TALL: the n structural costs).  c0 is a HOST array of count doubles (NULL: zeros).
+ *   A with unit col_stride is moved as whole row segments (16 bytes per lane when base and pitches allow, else 8), one with
+ *   unit row_stride through an LDS tile; any other pair of strides is gathered element by element -- correct, not fast.
+ * Stream contract (as lpipm_update_lockstep_vectors_device): the sources must be complete when the call is made; they are read on
+ *   the context's stream; the call returns when they are free again.
+ * The slack hint (SLACK, 0 < n_slack < n) is verified ON THE DEVICE over the last n_slack columns of every member (of the one
+ *   matrix when shared), with lpipm_upload_slack's comparison (a NaN fails it); one 4-byte word is read back before the
+ *   geometry is chosen.  A hint that fails gives a dense upload and still returns Ok.  The word lives in an allocation of the
+ *   context that lpipm_get_resident_bytes does not count.
+ * Nothing reaches a kernel that could make it read outside the caller's allocations: before any launch every source pointer
+ *   is looked up with the runtime, must be device memory of the context's device, and the farthest element its strides and
+ *   extents address must lie inside that allocation; otherwise LPIPM_ERR_BAD_ARGUMENT, with nothing enqueued and the resident
+ *   problem untouched.
+ * Return codes: a null context or descriptor, struct_size other than sizeof(lpipm_device_problem), an unknown form or
+ *   src_type, shared > 1, count 0 or > 4096, a stride < 1 LPIPM_ERR_BAD_ARGUMENT; then what the equivalent host entry returns
+ *   for null pointers, m == 0 (LPIPM_UNCONSTRAINED), n == 0, n_slack > n or > m, m > 2^20, n > 2^24 and a tall form on a
+ *   context with the refined solves; a column-split context (lpipm_set_collective, world > 1) LPIPM_ERR_UNSUPPORTED
+ *   (lpipm_upload_nsplit stays host-only). */
+enum { LPIPM_FORM_SLACK = 0, LPIPM_FORM_UB_EQ = 1, LPIPM_FORM_UB_TALL = 2 };
+enum { LPIPM_SRC_F64 = 0, LPIPM_SRC_F32 = 1 };          /* element type of A, A_eq, b, c on the device */
+typedef struct { const void* ptr; int64_t row_stride, col_stride, member_stride; } lpipm_dev_matrix; /* strides in ELEMENTS */
+typedef struct { const void* ptr; int64_t stride, member_stride; } lpipm_dev_vector;
+typedef struct {
+    uint32_t struct_size;   /* sizeof(lpipm_device_problem): anything else is LPIPM_ERR_BAD_ARGUMENT */
+    uint32_t form, src_type, shared;   /* shared = 1: ONE matrix (A, A_eq) for all `count` members */
+    uint64_t count;         /* 1..4096 */
+    uint64_t m;             /* rows of A: SLACK all rows; UB_EQ / UB_TALL the `ub` rows */
+    uint64_t m_eq;          /* rows of A_eq (UB_EQ only, else 0) */
+    uint64_t n;             /* columns of A (SLACK: slack columns included) */
+    uint64_t n_slack;       /* SLACK only: the hint of lpipm_upload_slack, verified ON THE DEVICE */
+    lpipm_dev_matrix A, A_eq;
+    lpipm_dev_vector b;     /* per member: SLACK m; UB_EQ [b_ub; b_eq] of m + m_eq; UB_TALL m */
+    lpipm_dev_vector c;     /* per member: SLACK n; UB_EQ / UB_TALL the n structural costs */
+    const double* c0;       /* HOST array of `count`, nullable: zeros (as lpipm_update_lockstep_vectors_device) */
+} lpipm_device_problem;
+int lpipm_upload_device(lpipm_ctx* ctx, const lpipm_device_problem* d);
+/* lpipm_update_vectors with b[m] and c[n] read from DEVICE memory (doubles, contiguous), on the context's stream and under the
+ * stream contract above; the pointers are looked up as lpipm_upload_device's are.  Same refusals; the next solve is
+ * bit-identical to one after lpipm_update_vectors with the same values. */
+int lpipm_update_vectors_device(lpipm_ctx* ctx, const void* b_dev, const void* c_dev);
+
 /* Device bytes the context holds for its resident problem(s) (arenas + shared matrix with the batch's one kept first factor +
  * factor workspace, and the exponent block of lpipm_set_scaling while scaling is on); 0 before any upload. */
 int lpipm_get_resident_bytes(const lpipm_ctx* ctx, uint64_t* bytes_out);
@@ -411,6 +470,21 @@ int lpipm_get_phase_times(const lpipm_ctx* ctx, lpipm_phase_times* out);
  * triangle valid (the strict upper triangle is unspecified).  `ms_out` (nullable) gets the device
  * time of the kernel launch(es) averaged over `repeats` (>= 1) back-to-back launches. */
 int lpipm_k_adat(lpipm_ctx* ctx, const double* dinv, double* M_out, int repeats, double* ms_out);   /* tall upload: LPIPM_ERR_UNSUPPORTED */
+/* The resident image of the stored structural block of member `member` (0 for a single LP and for a shared-matrix batch), as
+ * the solves read it: mp x npa doubles (rows padded to 128, stored columns to 16, zeros beyond m and the stored columns), after
+ * any equilibration.  Copies its top-left rows x cols to out (leading dimension ld >= cols) and reports the padded shape in
+ * mp_out / npa_out (nullable).  rows > mp, cols > npa, ld < cols or a member that does not exist: LPIPM_ERR_BAD_ARGUMENT;
+ * LPIPM_ERR_NO_PROBLEM without an upload. */
+int lpipm_k_resident_matrix(lpipm_ctx* ctx, uint64_t member, uint64_t rows, uint64_t cols, double* out, uint64_t ld,
+                            uint64_t* mp_out, uint64_t* npa_out);
+/* The launch of lpipm_upload_device that moves A (both blocks of the UB_EQ form) into the resident image, alone and timed:
+ * `repeats` (>= 1) back-to-back launches between two HIP events, the mean per launch in pack_ms_out; then, the same way, as
+ * many hipMemcpyDtoDAsync calls over as many bytes as one launch reads and writes together (half of them each way) between two
+ * scratch allocations, in copy_ms_out: the runtime's copy is the yardstick of the kernel (profiles/device_upload.md).  The
+ * resident problem must be the one lpipm_upload_device made from this very descriptor -- the image is rewritten with the
+ * values it holds; another shape is LPIPM_ERR_BAD_ARGUMENT, a scaled upload or a column-split context
+ * LPIPM_ERR_UNSUPPORTED.  The descriptor is checked as lpipm_upload_device checks it. */
+int lpipm_k_pack_matrix(lpipm_ctx* ctx, const lpipm_device_problem* d, int repeats, double* pack_ms_out, double* copy_ms_out);
 /* On a single tall upload (lpipm_upload_ub_tall; not a batch), with nx its structural columns, m its rows, n = nx + m and dinv[n] = x / z:
  * K_out (nx x nx row-major, LOWER triangle valid) = X^T.diag(1 / dinv_s).X + diag(1 / dinv_x).  Any other upload:
  * LPIPM_ERR_UNSUPPORTED. */

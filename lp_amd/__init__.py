@@ -306,6 +306,63 @@ def _solve_batch(ctx, problems, opts, tall, x_dev_ptr=None, row_stride=0):
     return unpack(rc)
 
 
+_DEVICE_FORMS = {"slack": _capi.FORM_SLACK, "ub_eq": _capi.FORM_UB_EQ, "ub_tall": _capi.FORM_UB_TALL}
+
+
+def _device_request(A, b, c, c0s=None, form="slack", A_eq=None, n_slack=0):
+    """The lpipm_device_problem of torch CUDA tensors (Context.upload_device), checked without a context: shapes, one dtype
+    (float64 or float32), one CUDA device.  -> (descriptor, what must stay alive while it is used, K, len(b[i]), len(x),
+    device index, whether the request is a lockstep batch).  Tensors with a stride < 1 are made contiguous; nothing else is
+    copied."""
+    import torch
+    if form not in _DEVICE_FORMS:
+        raise ValueError(f"form must be one of {sorted(_DEVICE_FORMS)}")
+    tensors = [A, b, c] + ([A_eq] if A_eq is not None else [])
+    if not all(isinstance(t, torch.Tensor) for t in tensors):
+        raise ValueError("upload_device takes torch tensors")
+    if not all(t.is_cuda for t in tensors):
+        raise ValueError("upload_device takes CUDA tensors: host arrays go through the upload* methods")
+    if A.dtype not in (torch.float64, torch.float32) or any(t.dtype != A.dtype for t in tensors):
+        raise ValueError("A, b, c (and A_eq) must all be float64 or all be float32")
+    if any(t.device != A.device for t in tensors):
+        raise ValueError("A, b, c (and A_eq) must be on one device")
+    if (A_eq is not None and form != "ub_eq") or (n_slack and form != "slack") or int(n_slack) < 0:
+        raise ValueError("A_eq belongs to form='ub_eq', n_slack to form='slack'")
+    if A.ndim == 2 and b.ndim == 1:
+        K, shared, batch = 1, 0, False
+    elif A.ndim == 2 and b.ndim == 2:
+        K, shared, batch = b.shape[0], 1, True
+    elif A.ndim == 3 and b.ndim == 2:
+        K, shared, batch = A.shape[0], 0, True
+    else:
+        raise IncompatibleInputDimensions()
+    m, n = A.shape[-2:]
+    m_eq = 0
+    if A_eq is not None:
+        if A_eq.ndim != 2 or A_eq.shape[1] != n:
+            raise IncompatibleInputDimensions()
+        m_eq = A_eq.shape[0]
+    nb = m + m_eq
+    if K < 1 or b.shape != ((K, nb) if batch else (nb,)) or c.shape != ((K, n) if batch else (n,)):
+        raise IncompatibleInputDimensions()
+    if c0s is not None and len(c0s) != K:
+        raise IncompatibleInputDimensions()
+    fix = lambda t: t if all(s >= 1 for s in t.stride()) else t.contiguous()
+    A, b, c = fix(A), fix(b), fix(c)
+    A_eq = fix(A_eq) if A_eq is not None else None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+    mat = lambda t: _capi.DevMatrix(ptr(t), t.stride(-2), t.stride(-1), t.stride(0) if t.ndim == 3 else 0)
+    vec = lambda t: _capi.DevVector(ptr(t), t.stride(-1), t.stride(0) if t.ndim == 2 else 0)
+    c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
+    d = _capi.DeviceProblem(
+        struct_size=C.sizeof(_capi.DeviceProblem), form=_DEVICE_FORMS[form], shared=shared, count=K, m=m, m_eq=m_eq, n=n,
+        src_type=_capi.SRC_F32 if A.dtype == torch.float32 else _capi.SRC_F64, n_slack=int(n_slack), A=mat(A),
+        A_eq=mat(A_eq) if A_eq is not None else _capi.DevMatrix(None, 1, 1, 0), b=vec(b), c=vec(c),
+        c0=C.cast(c0, C.POINTER(C.c_double)) if c0 is not None else None)
+    n_out = n if form == "slack" else n + m
+    return d, (A, b, c, A_eq, c0), K, nb, n_out, A.device.index if A.device.index is not None else torch.cuda.current_device(), batch
+
+
 class Context:
     """One lpipm_ctx: device buffers + stream of one (thread, device).  `InteriorPoint.solve` keeps one
     per device; bench/tests use it directly to separate the one-time upload from the timed solve."""
@@ -375,6 +432,61 @@ class Context:
             raise IncompatibleInputDimensions()
         _raise_for(_capi.lib().lpipm_update_vectors(self._h, _p(b), _p(c)))
         return self
+
+    def upload_device(self, A, b, c, c0s=None, *, form="slack", A_eq=None, n_slack=0):
+        """A problem or a lockstep batch straight from torch CUDA tensors (lpipm_upload_device): float64 or float32 (all of one
+        dtype), any strides, on this context's device; no host copy of A, b or c is made.  The shapes pick the request:
+        A [m, n] with b [m]: a single LP; A [m, n] with b [K, .]: K members over ONE matrix; A [K, m, n]: K members that own
+        their matrices.  form: "slack" (A with its slack columns, n_slack the hint of upload_arrays, verified on the device),
+        "ub_eq" (A the `ub` rows, A_eq the `eq` rows, b = [b_ub; b_eq], c the structural costs) or "ub_tall" (`ub` rows
+        only, the tall inequality form).  The context is then exactly where the equivalent host upload leaves it: solve_raw,
+        solve_lockstep[_device], update_lockstep_vectors[_device] and scaling work unchanged, bit for bit.  Torch's current
+        stream on the device is synchronised first; the tensors are free again when the call returns."""
+        import torch
+        d, keep, K, nb, n_out, dev, batch = _device_request(A, b, c, c0s, form, A_eq, n_slack)
+        if dev != self.device:
+            raise ValueError(f"the tensors are on device {dev}, the context on device {self.device}")
+        torch.cuda.current_stream(dev).synchronize()         # the sources are complete when the library reads them
+        _raise_for(_capi.lib().lpipm_upload_device(self._h, C.byref(d)))
+        del keep
+        if batch:
+            self._lock = (K, nb, n_out, None, None, [np.empty(d.n)])     # (_lockstep_form reads the length of a c[i] from it)
+        self.m, self.n = nb, n_out
+        return self
+
+    def update_vectors_device(self, b, c):
+        """update_vectors with b [m] and c [n] taken from float64 torch CUDA tensors on this context's device
+        (lpipm_update_vectors_device); non-contiguous ones are made contiguous on the device first."""
+        import torch
+        for t in (b, c):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64:
+                raise ValueError("update_vectors_device takes float64 CUDA tensors")
+        if b.shape != (self.m,) or c.shape != (self.n,):
+            raise IncompatibleInputDimensions()
+        if b.device.index != self.device or c.device.index != self.device:
+            raise ValueError("the tensors are not on the context's device")
+        b, c = b.contiguous(), c.contiguous()
+        torch.cuda.current_stream(self.device).synchronize()
+        _raise_for(_capi.lib().lpipm_update_vectors_device(self._h, C.c_void_p(b.data_ptr()), C.c_void_p(c.data_ptr())))
+        return self
+
+    def k_resident_matrix(self, member: int = 0):
+        """-> the whole padded resident image (mp x npa) of the stored structural block of `member`, as the solves read it
+        (lpipm_k_resident_matrix)."""
+        mp, npa = C.c_uint64(0), C.c_uint64(0)
+        _raise_for(_capi.lib().lpipm_k_resident_matrix(self._h, int(member), 0, 0, None, 0, C.byref(mp), C.byref(npa)))
+        out = np.full((mp.value, npa.value), np.nan)
+        _raise_for(_capi.lib().lpipm_k_resident_matrix(self._h, int(member), mp.value, npa.value, _p(out), npa.value, None, None))
+        return out
+
+    def k_pack_matrix(self, A, b, c, repeats=20, **kw):
+        """-> (pack_ms, copy_ms): the launch that moved A of the resident upload_device(A, b, c, **kw), `repeats` times back to
+        back between two events, and the runtime's device-to-device copy of as many bytes the same way (lpipm_k_pack_matrix)."""
+        d, keep = _device_request(A, b, c, **kw)[:2]
+        pack, copy = C.c_double(0.0), C.c_double(0.0)
+        _raise_for(_capi.lib().lpipm_k_pack_matrix(self._h, C.byref(d), int(repeats), C.byref(pack), C.byref(copy)))
+        del keep
+        return pack.value, copy.value
 
     def _lockstep_form(self):
         """(members, len(b[i]), len(c[i])) of the resident lockstep batch, in its upload's own form."""

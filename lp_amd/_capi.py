@@ -30,6 +30,24 @@ class PhaseTimes(C.Structure):  # lpipm_phase_times
                 ("gemv_passes", C.c_uint64)]
 
 
+FORM_SLACK, FORM_UB_EQ, FORM_UB_TALL = range(3)     # lpipm_device_problem.form
+SRC_F64, SRC_F32 = range(2)                           # lpipm_device_problem.src_type
+
+
+class DevMatrix(C.Structure):  # lpipm_dev_matrix (strides in elements)
+    _fields_ = [("ptr", C.c_void_p), ("row_stride", C.c_int64), ("col_stride", C.c_int64), ("member_stride", C.c_int64)]
+
+
+class DevVector(C.Structure):  # lpipm_dev_vector
+    _fields_ = [("ptr", C.c_void_p), ("stride", C.c_int64), ("member_stride", C.c_int64)]
+
+
+class DeviceProblem(C.Structure):  # lpipm_device_problem
+    _fields_ = [("struct_size", C.c_uint32), ("form", C.c_uint32), ("src_type", C.c_uint32), ("shared", C.c_uint32),
+                ("count", C.c_uint64), ("m", C.c_uint64), ("m_eq", C.c_uint64), ("n", C.c_uint64), ("n_slack", C.c_uint64),
+                ("A", DevMatrix), ("A_eq", DevMatrix), ("b", DevVector), ("c", DevVector), ("c0", C.POINTER(C.c_double))]
+
+
 # every symbol include/lpipm.h declares: name -> (restype, argtypes)
 _dp, _u64, _vp = C.POINTER(C.c_double), C.c_uint64, C.c_void_p
 _dpp = C.POINTER(_dp)
@@ -48,6 +66,10 @@ SYMBOLS = {
     "lpipm_update_vectors": (C.c_int, [_vp, _dp, _dp]),
     "lpipm_update_lockstep_vectors": (C.c_int, [_vp, _u64, _dpp, _dpp, _dp]),
     "lpipm_update_lockstep_vectors_device": (C.c_int, [_vp, _u64, _vp, _u64, _vp, _u64, _dp]),
+    "lpipm_upload_device": (C.c_int, [_vp, C.POINTER(DeviceProblem)]),
+    "lpipm_update_vectors_device": (C.c_int, [_vp, _vp, _vp]),
+    "lpipm_k_resident_matrix": (C.c_int, [_vp, _u64, _u64, _u64, _dp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "lpipm_k_pack_matrix": (C.c_int, [_vp, C.POINTER(DeviceProblem), C.c_int, _dp, _dp]),
     "lpipm_set_first_factor_cache": (C.c_int, [_vp, C.c_int]),
     "lpipm_set_scaling": (C.c_int, [_vp, C.c_int]),
     "lpipm_get_scaling": (C.c_int, [_vp, _u64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -139,6 +139,46 @@ def sweep_chunks(count: int, max_group: int):
     return g, chunks
 
 
+def solve_device(A, b, c, c0s=None, *, form="slack", A_eq=None, n_slack=0, opts=None, ctx=None, max_group=32):
+    """A batch that is already on the GPU, end to end without a host copy of A, b, c or x: torch CUDA tensors as
+    Context.upload_device takes them -- A [m, n] with b [K, .] (one matrix for all members) or A [K, m, n] (members that own
+    their matrices), float64 or float32, any strides.  The members go through lockstep chunks of sweep_chunks's size (at most
+    `max_group`), each uploaded from a slice of the tensors (lpipm_upload_device) and solved straight into its rows of the
+    result (solve_lockstep_device).  A shared A is uploaded once per chunk size: a later chunk of the resident size only
+    replaces the vectors (update_lockstep_vectors_device).
+    -> (x, status, fun, iterations): x a float64 CUDA tensor [K, len(x)], NaN in the rows of members without a solution;
+    status (int32), fun (float64, NaN without a solution) and iterations (int64) numpy arrays of K entries."""
+    import torch
+    import lp_amd
+    _, _, K, nb, n_out, dev, batch = lp_amd._device_request(A, b, c, c0s, form, A_eq, n_slack)
+    if not batch:
+        raise lp_amd.IncompatibleInputDimensions()
+    if max_group < 1:
+        raise lp_amd.InvalidParameter("max_group must be >= 1")
+    ctx = ctx or lp_amd.default_context(dev)
+    opts = opts or lp_amd.InteriorPoint.default().opts()
+    shared = A.ndim == 2
+    x = torch.full((K, n_out), float("nan"), dtype=torch.float64, device=A.device)
+    status, fun, its = np.zeros(K, dtype=np.int32), np.full(K, np.nan), np.zeros(K, dtype=np.int64)
+    g = sweep_chunks(K, max_group)[0]
+    resident = 0                                          # members of the shared-matrix batch that is resident
+    for k0 in range(0, K, g):
+        k1 = min(k0 + g, K)
+        c0 = None if c0s is None else [float(v) for v in c0s[k0:k1]]
+        if shared and resident == k1 - k0:
+            rows = lambda t: t[k0:k1] if t.dtype == torch.float64 and t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t[k0:k1].double().contiguous()
+            bq, cq = rows(b), rows(c)
+            torch.cuda.current_stream(dev).synchronize()
+            ctx.update_lockstep_vectors_device(bq.data_ptr(), bq.stride(0), cq.data_ptr(), cq.stride(0), c0)
+        else:
+            ctx.upload_device(A if shared else A[k0:k1], b[k0:k1], c[k0:k1], c0, form=form, A_eq=A_eq, n_slack=n_slack)
+            resident = k1 - k0 if shared else 0
+        for i, (st, f, it) in enumerate(ctx.solve_lockstep_device(opts, x[k0].data_ptr(), n_out)):
+            status[k0 + i], its[k0 + i] = st, it
+            fun[k0 + i] = np.nan if f is None else f
+    return x, status, fun, its
+
+
 def _drive(chunks, upload, resident, bs, cs, c0s, opts, ctx, max_group):
     """Member groups through lockstep batches on one context: `chunks(count, max_group)` gives the member indices of each group;
     group 0 is uploaded, a later one replaces the vectors of the resident batch (resident) or is uploaded in its turn."""

@@ -24,6 +24,7 @@
 #include <chrono>
 #include "vec_kernels.hpp"
 #include "batch_plan.hpp"
+#include "device_source.hpp"
 
 using namespace lpipm;
 
@@ -159,6 +160,7 @@ struct lpipm_ctx {
     double* stage_host = nullptr;
     double* stage_dev = nullptr;
     size_t stage_cap = 0;        // doubles, each side
+    int* hint_dev = nullptr;     // lpipm_upload_device: the word k_slack_hint writes.  Made on first use, freed by lpipm_destroy
     int units_env = 1;                   // LPIPM_ADAT_UNITS=0: the round-2 kernel (data-parallel tiles + fix-up launch) everywhere
     PotrfLookahead la;                   // trailing updates of one factorisation beside the next panel's chain (launch_potrf)
     // a lockstep batch as two half-batches driven by two host threads on two streams (solve_lockstep): views of this
@@ -438,6 +440,7 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     if (c->p.scale_mem) (void)hipFree(c->p.scale_mem);
     if (c->stage_dev) (void)hipFree(c->stage_dev);
     if (c->stage_host) (void)hipHostFree(c->stage_host);
+    if (c->hint_dev) (void)hipFree(c->hint_dev);
     adat_lists_destroy(c->p.adat);
     free_list(c->kallocs);
     if (c->mpack) (void)hipFree(c->mpack);
@@ -496,6 +499,9 @@ struct Upload {
     bool owned = false;                  // tall, a batch whose members own their matrices: X_i = A[i] (lda), b[i] per member; parts holds m_ub only
     bool hint_verified = false;          // the caller has checked the hint on these very matrices (batch_impl): it is not repeated
     bool keep_ok = true;                 // false: solved once (lpipm_solve_batch) or never through the kept factor (column split)
+    // lpipm_upload_device: A, b and c are in DEVICE memory, laid out as this descriptor says.  The request is otherwise the
+    // equivalent host entry's; its pointers above stand for "given" / "null" only (check_upload) and are never read through.
+    const lpipm_device_problem* dev = nullptr;
 };
 // Which requests are legal, and what the others get.  Every argument of a dense request is looked at before its shape; of a
 // request in parts the shape comes first (m == 0 is Unconstrained whatever the blocks are, linear_program.rs:134-136), ahead
@@ -740,11 +746,108 @@ static int copy_in(lpipm_ctx* c, const Upload& u, const double* c0v) {
     }
     return LPIPM_OK;
 }
+// ---- a request whose sources are in device memory (Upload::dev) ----
+// One source: the farthest element its extents and strides address lies inside the device allocation of the context's
+// device that holds its base.  A source of no elements is not looked at.
+static int source_inside(const lpipm_ctx* c, const void* ptr, const Dim* dims, int ndims, size_t elem) {
+    uint64_t bytes = 0;
+    if (!span_bytes(dims, ndims, elem, &bytes)) return LPIPM_ERR_BAD_ARGUMENT;
+    if (bytes == 0) return LPIPM_OK;
+    if (!ptr) return LPIPM_ERR_BAD_ARGUMENT;
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); return LPIPM_ERR_BAD_ARGUMENT; }   // (pageable host memory)
+    if (at.type != hipMemoryTypeDevice || at.device != c->device) return LPIPM_ERR_BAD_ARGUMENT;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ptr) != hipSuccess) { (void)hipGetLastError(); return LPIPM_ERR_BAD_ARGUMENT; }
+    return inside((uintptr_t)ptr, bytes, (uintptr_t)base, (uint64_t)size) ? LPIPM_OK : LPIPM_ERR_BAD_ARGUMENT;
+}
+// Every source of the descriptor, over everything a kernel of this upload may read: all n columns of a SLACK matrix (the
+// hint test reads the slack block), the members as far as their strides go.
+static int sources_inside(const lpipm_ctx* c, const Upload& u) {
+    const lpipm_device_problem& d = *u.dev;
+    const size_t el = src_elem_bytes(d.src_type);
+    const uint64_t mats = member_strided(&d) ? d.count : 1;
+    const uint64_t nb = u.m, nc = u.parts ? u.n - u.n_slack : u.n;
+    const Dim a[3] = {{mats, d.A.member_stride}, {d.m, d.A.row_stride}, {d.n, d.A.col_stride}};
+    const Dim e[2] = {{d.m_eq, d.A_eq.row_stride}, {d.n, d.A_eq.col_stride}};
+    const Dim b[2] = {{d.count, d.b.member_stride}, {nb, d.b.stride}}, cc[2] = {{d.count, d.c.member_stride}, {nc, d.c.stride}};
+    LP_TRY(source_inside(c, d.A.ptr, mats > 1 ? a : a + 1, mats > 1 ? 3 : 2, el));
+    if (d.form == LPIPM_FORM_UB_EQ) LP_TRY(source_inside(c, d.A_eq.ptr, e, 2, el));
+    LP_TRY(source_inside(c, d.b.ptr, d.count > 1 ? b : b + 1, d.count > 1 ? 2 : 1, el));
+    LP_TRY(source_inside(c, d.c.ptr, d.count > 1 ? cc : cc + 1, d.count > 1 ? 2 : 1, el));
+    return LPIPM_OK;
+}
+// slack_hint_holds on the device: one launch over the hinted columns of every matrix, one word back.
+static int device_hint_holds(lpipm_ctx* c, const Upload& u, bool* holds) {
+    const lpipm_device_problem& d = *u.dev;
+    *holds = false;
+    if (u.n_slack == 0 || u.n_slack == u.n) return LPIPM_OK;
+    hipStream_t st = c->rs.st;
+    if (!c->hint_dev) LP_HIP(hipMalloc((void**)&c->hint_dev, sizeof(int)));
+    static const int one = 1;
+    LP_HIP(hipMemcpyAsync(c->hint_dev, &one, sizeof(int), hipMemcpyHostToDevice, st));
+    const bool own = member_strided(&d);
+    const SlackHint h{d.A.ptr, d.A.row_stride, d.A.col_stride, own ? d.A.member_stride : 0, (long long)(u.n - u.n_slack),
+                      (int)u.m, (int)u.n_slack, c->hint_dev};
+    LP_HIP(launch_slack_hint(h, d.src_type == LPIPM_SRC_F32, own ? (int)d.count : 1, st));
+    int word = 0;
+    LP_HIP(hipMemcpyAsync(&word, c->hint_dev, sizeof(int), hipMemcpyDeviceToHost, st));
+    LP_HIP(hipStreamSynchronize(st));
+    *holds = word != 0;
+    return LPIPM_OK;
+}
+// The launch that moves the descriptor's A into p's image(s): the `ub` and `eq` blocks of a request in parts are its two
+// blocks of rows, each with the copy mode its own strides and alignment allow.
+static PackMatrix pack_matrix_of(const Problem& p, const lpipm_device_problem& d) {
+    const bool own = member_strided(&d);
+    const size_t el = src_elem_bytes(d.src_type);
+    auto block = [&](const lpipm_dev_matrix& M, uint64_t rows, uint64_t row0) {
+        PackSeg s;
+        if (rows == 0) return s;
+        s.src = M.ptr; s.rs = M.row_stride; s.cs = M.col_stride; s.ms = own ? M.member_stride : 0;
+        s.rows = (int)rows; s.row0 = (int)row0;
+        s.mode = (int)pack_mode((uintptr_t)M.ptr, el, M.row_stride, M.col_stride, M.member_stride, own);
+        return s;
+    };
+    PackMatrix pm;
+    pm.seg[0] = block(d.A, d.m, 0);
+    if (d.form == LPIPM_FORM_UB_EQ) pm.seg[1] = block(d.A_eq, d.m_eq, d.m);
+    pm.dst = p.A; pm.ldd = p.npa; pm.dstride = own ? (long long)p.bstride : 0; pm.nx = p.nx;
+    return pm;
+}
+// copy_in for device sources: one launch for A, one for b, c and c0 of every member; c0 goes through the staging block, as in
+// update_lockstep_impl.
+static int stage_grow(lpipm_ctx* c, size_t count);
+static int copy_in_device(lpipm_ctx* c, const Upload& u, const double* c0v) {
+    const lpipm_device_problem& d = *u.dev;
+    Problem& p = c->p;
+    hipStream_t st = c->rs.st;
+    const bool f32 = d.src_type == LPIPM_SRC_F32;
+    LP_HIP(launch_pack_matrix(pack_matrix_of(p, d), f32, member_strided(&d) ? (int)u.count : 1, st));
+    const size_t count = (size_t)u.count;
+    LP_TRY(stage_grow(c, count));
+    std::memcpy(c->stage_host, c0v, count * sizeof(double));
+    LP_HIP(hipMemcpyAsync(c->stage_dev, c->stage_host, count * sizeof(double), hipMemcpyHostToDevice, st));
+    const bool many = u.count > 1;
+    PackVectors pv;
+    pv.seg[0] = PackVecSeg{d.b.ptr, d.b.stride, many ? d.b.member_stride : 0, (double*)p.va.b, (int)u.m};
+    pv.seg[1] = PackVecSeg{d.c.ptr, d.c.stride, many ? d.c.member_stride : 0, (double*)p.va.c, (int)(u.parts ? (uint64_t)p.nx : u.n)};
+    pv.c0_src = c->stage_dev; pv.c0_dst = p.va.S + S_C0; pv.dstride = (long long)p.bstride;
+    LP_HIP(launch_pack_vectors(pv, f32, (int)u.count, st));
+    return LPIPM_OK;
+}
 static int upload_impl(lpipm_ctx* c, const Upload& u) {
     LP_TRY(check_upload(c, u));
     // The hint is only used if the last n_slack columns of every member (of a shared batch's one matrix) really are [I; 0]
     // (ProblemBuilder::build guarantees it, linear_program.rs:147-156; parts have it by construction): else the upload is dense.
-    const bool hint = u.parts.has_value() || u.hint_verified || slack_hint_holds(u.shared ? 1 : u.count, u.m, u.n, u.A, u.lda, u.n_slack);
+    bool hint = u.parts.has_value() || u.hint_verified;
+    if (u.dev) {      // nothing is enqueued, and nothing of the resident problem touched, before the sources are known to be readable
+        if (c->world > 1) return LPIPM_ERR_UNSUPPORTED;
+        LP_HIP(hipSetDevice(c->device));
+        LP_TRY(sources_inside(c, u));
+        if (!hint) LP_TRY(device_hint_holds(c, u, &hint));
+    } else if (!hint) hint = slack_hint_holds(u.shared ? 1 : u.count, u.m, u.n, u.A, u.lda, u.n_slack);
     const uint64_t n_slack = hint ? u.n_slack : 0, nx = u.n - n_slack;
     LP_HIP(hipSetDevice(c->device));
     destroy_views(c); // half-batch views hold copies of the geometry and of the device pointers
@@ -776,7 +879,7 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
     for (int i = 0; i < count; ++i) c0v[i] = u.c0 ? u.c0[i] : 0.0;
     const std::vector<double> onesv(p.shared_factor ? (size_t)g.np : 0, 1.0);     // likewise
     if (p.shared_factor) LP_HIP(hipMemcpyAsync(p.ones, onesv.data(), onesv.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    LP_TRY(copy_in(c, u, c0v.data()));
+    LP_TRY(u.dev ? copy_in_device(c, u, c0v.data()) : copy_in(c, u, c0v.data()));
     if (p.scale_passes > 0) {   // equilibrate what was just copied: the solves see the scaled problem only
         const Batch members{count, (long long)p.bstride, nullptr, 0};
         LP_HIP(launch_equilibrate(p.sc, p.A, (int)u.m, g.mp, (int)nx, g.npa, (int)n_slack, p.scale_passes, st,
@@ -857,6 +960,53 @@ extern "C" int lpipm_upload_lockstep_ub_tall(lpipm_ctx* c, uint64_t count, uint6
                                              uint64_t lda_ub, const double* const* b, const double* const* cc, const double* c0) {
     if (!c) return LPIPM_ERR_BAD_ARGUMENT;       // (as the shared tall batch: a null context before the shape)
     return upload_impl(c, owned_tall_request(count, n, m_ub, A_ub, lda_ub, b, cc, c0));
+}
+// The request of the host entry the descriptor stands for, with the descriptor as its source.  The pointer arrays hold the
+// descriptor's base pointers, member after member alike: check_upload asks only whether they are null.
+struct DeviceRequest { std::vector<const double*> Av, bv, cv; Upload u; };
+static int device_request(const lpipm_device_problem* d, DeviceRequest& q) {
+    if (!d) return LPIPM_ERR_BAD_ARGUMENT;
+    HostEntry entry;
+    if (const int rc = entry_of(d, &entry); rc != LPIPM_OK) return rc;
+    if (!strides_ok(d)) return LPIPM_ERR_BAD_ARGUMENT;
+    if ((d->form != LPIPM_FORM_UB_EQ && d->m_eq != 0) || (d->form != LPIPM_FORM_SLACK && d->n_slack != 0)) return LPIPM_ERR_BAD_ARGUMENT;
+    const uint64_t K = d->count, m = d->m, n = d->n;
+    const double *A = (const double*)d->A.ptr, *A_eq = (const double*)d->A_eq.ptr, *b = (const double*)d->b.ptr, *cc = (const double*)d->c.ptr;
+    q.Av.assign((size_t)K, A); q.bv.assign((size_t)K, b); q.cv.assign((size_t)K, cc);
+    const std::vector<const double*>&Av = q.Av, &bv = q.bv, &cv = q.cv;
+    Upload& u = q.u;
+    switch (entry) {
+    case HostEntry::Slack: case HostEntry::LockstepSlack:
+        u = Upload{.count = K, .m = m, .n = n, .n_slack = d->n_slack, .A = Av.data(), .lda = n, .b = bv.data(), .c = cv.data(), .c0 = d->c0};
+        break;
+    case HostEntry::SharedSlack:
+        u = Upload{.count = K, .m = m, .n = n, .n_slack = d->n_slack, .A = Av.data(), .lda = n, .b = bv.data(), .c = cv.data(), .c0 = d->c0,
+                   .shared = true};
+        break;
+    case HostEntry::UbEq:
+        u = Upload{.m = m + d->m_eq, .n = n + m, .n_slack = m, .parts = UploadParts{m, A, n, b, A_eq, n, b}, .c = cv.data(), .c0 = d->c0};
+        break;
+    case HostEntry::SharedUbEq:
+        u = Upload{.count = K, .m = m + d->m_eq, .n = n + m, .n_slack = m,
+                   .parts = UploadParts{.m_ub = m, .A_ub = A, .lda_ub = n, .A_eq = A_eq, .lda_eq = n}, .b = bv.data(), .c = cv.data(), .c0 = d->c0,
+                   .shared = true};
+        break;
+    case HostEntry::UbTall: u = tall_request(n, m, A, n, b, cv.data(), d->c0); break;
+    case HostEntry::SharedUbTall:
+        u = Upload{.count = K, .m = m, .n = n + m, .n_slack = m, .parts = UploadParts{.m_ub = m, .A_ub = A, .lda_ub = n}, .b = bv.data(),
+                   .c = cv.data(), .c0 = d->c0, .shared = true, .tall = true, .keep_ok = false};
+        break;
+    case HostEntry::LockstepUbTall: u = owned_tall_request(K, n, m, Av.data(), n, bv.data(), cv.data(), d->c0); break;
+    default: return LPIPM_ERR_BAD_ARGUMENT;
+    }
+    u.dev = d;
+    return LPIPM_OK;
+}
+extern "C" int lpipm_upload_device(lpipm_ctx* c, const lpipm_device_problem* d) {
+    if (!c) return LPIPM_ERR_BAD_ARGUMENT;
+    DeviceRequest q;
+    LP_TRY(device_request(d, q));
+    return upload_impl(c, q.u);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1962,6 +2112,22 @@ extern "C" int lpipm_update_vectors(lpipm_ctx* c, const double* b, const double*
     return LPIPM_OK;
 }
 
+extern "C" int lpipm_update_vectors_device(lpipm_ctx* c, const void* b_dev, const void* c_dev) {
+    if (!c || !b_dev || !c_dev) return LPIPM_ERR_BAD_ARGUMENT;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (c->p.B != 1 || c->colsplit || c->p.from_parts) return LPIPM_ERR_UNSUPPORTED;
+    LP_HIP(hipSetDevice(c->device));
+    const Dim db{c->p.m, 1}, dc{c->p.n, 1};
+    LP_TRY(source_inside(c, b_dev, &db, 1, sizeof(double)));
+    LP_TRY(source_inside(c, c_dev, &dc, 1, sizeof(double)));
+    LP_HIP(hipMemcpyAsync((void*)c->p.va.b, b_dev, c->p.m * sizeof(double), hipMemcpyDeviceToDevice, c->rs.st));
+    LP_HIP(hipMemcpyAsync((void*)c->p.va.c, c_dev, c->p.n * sizeof(double), hipMemcpyDeviceToDevice, c->rs.st));
+    if (c->p.scale_passes > 0)
+        LP_HIP(launch_scale_vectors(c->p.sc, (double*)c->p.va.b, (int)c->p.m, (double*)c->p.va.c, (int)c->p.n, c->rs.st, Batch{}));
+    LP_HIP(hipStreamSynchronize(c->rs.st));   // the caller's blocks are free again from here
+    return LPIPM_OK;
+}
+
 // At least `count` doubles in the context's pinned staging block and in its device image.
 static int stage_grow(lpipm_ctx* c, size_t count) {
     if (count <= c->stage_cap) return LPIPM_OK;
@@ -2052,6 +2218,69 @@ static int timed_repeats(lpipm_ctx* c, int repeats, double* ms_out, F&& body) {
     }
     if (ms_out) *ms_out = total / repeats;
     return LPIPM_OK;
+}
+
+extern "C" int lpipm_k_resident_matrix(lpipm_ctx* c, uint64_t member, uint64_t rows, uint64_t cols, double* out, uint64_t ld,
+                                       uint64_t* mp_out, uint64_t* npa_out) {
+    if (!c || (rows && cols && !out)) return LPIPM_ERR_BAD_ARGUMENT;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+    const Problem& p = c->p;
+    if (member >= (uint64_t)(p.shared_a ? 1 : p.B) || rows > (uint64_t)p.mp || cols > (uint64_t)p.npa || ld < cols) return LPIPM_ERR_BAD_ARGUMENT;
+    if (mp_out) *mp_out = (uint64_t)p.mp;
+    if (npa_out) *npa_out = (uint64_t)p.npa;
+    if (rows == 0 || cols == 0) return LPIPM_OK;
+    LP_HIP(hipSetDevice(c->device));
+    const char* img = (const char*)p.A + (p.shared_a ? 0 : (size_t)member * p.bstride);
+    LP_HIP(hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), img, (size_t)p.npa * sizeof(double), (size_t)cols * sizeof(double), (size_t)rows,
+                            hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
+    return LPIPM_OK;
+}
+
+extern "C" int lpipm_k_pack_matrix(lpipm_ctx* c, const lpipm_device_problem* d, int repeats, double* pack_ms_out, double* copy_ms_out) {
+    if (!c) return LPIPM_ERR_BAD_ARGUMENT;
+    DeviceRequest q;
+    LP_TRY(device_request(d, q));
+    LP_TRY(check_upload(c, q.u));
+    Problem& p = c->p;
+    if (!p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (c->world > 1 || p.scale_passes > 0) return LPIPM_ERR_UNSUPPORTED;      // (the launch would put the unscaled matrix back)
+    LP_HIP(hipSetDevice(c->device));
+    LP_TRY(sources_inside(c, q.u));
+    // the resident problem must be this descriptor's: the launch writes its m x nx block into the resident image
+    if (q.u.m != p.m || q.u.n != p.n || q.u.count != (uint64_t)p.B || q.u.shared != p.shared_a || q.u.tall != p.tall ||
+        q.u.parts.has_value() != p.from_parts || (q.u.parts && q.u.n_slack != (uint64_t)p.ns))     // (parts: the same `ub` rows, so the same columns)
+        return LPIPM_ERR_BAD_ARGUMENT;
+    if (repeats < 1) repeats = 1;
+    hipStream_t st = c->rs.st;
+    const PackMatrix pm = pack_matrix_of(p, *d);
+    const bool f32 = d->src_type == LPIPM_SRC_F32;
+    const int members = member_strided(d) ? p.B : 1;
+    auto timed = [&](double* ms_out, auto&& body) -> int {
+        LP_HIP(hipEventRecord(c->rs.ev_begin, st));
+        for (int r = 0; r < repeats; ++r) LP_HIP(body());
+        LP_HIP(hipEventRecord(c->rs.ev_end, st));
+        LP_HIP(hipStreamSynchronize(st));
+        float ms = 0.f;
+        LP_HIP(hipEventElapsedTime(&ms, c->rs.ev_begin, c->rs.ev_end));
+        if (ms_out) *ms_out = (double)ms / repeats;
+        return LPIPM_OK;
+    };
+    LP_TRY(timed(pack_ms_out, [&] { return launch_pack_matrix(pm, f32, members, st); }));
+    // the runtime's copy of as many bytes: the launch reads elements of the source type and writes doubles
+    const size_t elems = (size_t)members * (size_t)p.m * (size_t)p.nx;
+    const size_t bytes = elems * (src_elem_bytes(d->src_type) + sizeof(double)) / 2;
+    void *from = nullptr, *to = nullptr;
+    if (hipMalloc(&from, bytes) != hipSuccess || hipMalloc(&to, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        if (from) (void)hipFree(from);
+        return LPIPM_ERR_HIP;
+    }
+    int rc = hipMemsetAsync(from, 0, bytes, st) == hipSuccess ? LPIPM_OK : LPIPM_ERR_HIP;
+    if (rc == LPIPM_OK) rc = timed(copy_ms_out, [&] { return hipMemcpyDtoDAsync((hipDeviceptr_t)to, (hipDeviceptr_t)from, bytes, st); });
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(from); (void)hipFree(to);
+    return rc;
 }
 
 extern "C" int lpipm_k_adat(lpipm_ctx* c, const double* dinv, double* M_out, int repeats, double* ms_out) {

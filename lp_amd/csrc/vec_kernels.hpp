@@ -139,4 +139,24 @@ void tall_uv_corr(const VecArgs& a, const TallArgs& t, const double* r1a, hipStr
 // path, next to zeros: the same bits).  Followed by vec_scalar_indicators.
 void tall_residuals(const VecArgs& a, const TallArgs& t, hipStream_t st);
 
+// ---------------------------------------------------------------- device sources (kernels_pack.hip)
+// lpipm_upload_device: the caller's strided device arrays (double or float) into the zeroed resident image.  Strides are in
+// ELEMENTS of the source type; `ms` is the member stride of the source (0: one source for the launch), dstride the BYTES
+// between the members' arenas (0: one image).  The callers have checked that every address these launches form lies inside
+// the caller's allocations (solver.hip, sources_inside).
+// A: up to two blocks of rows (the `ub` and `eq` blocks of lpipm_upload_ub_eq; a block of 0 rows is skipped), block s's row i
+// going to row row0 + i of the image (ldd doubles per row), columns [0, nx).  mode: a PackMode (device_source.hpp).
+struct PackSeg { const void* src = nullptr; long long rs = 0, cs = 0, ms = 0; int rows = 0, row0 = 0, mode = 0; };
+struct PackMatrix { PackSeg seg[2]; double* dst = nullptr; long long ldd = 0, dstride = 0; int nx = 0; };
+hipError_t launch_pack_matrix(const PackMatrix& a, bool f32, int members, hipStream_t st);
+// b and c of every member (segment s: len elements, `stride` apart, into dst of member z's arena), and c0 from a packed
+// device array of doubles (c0_src[z] -> c0_dst of member z; null: not written), in one launch.
+struct PackVecSeg { const void* src = nullptr; long long stride = 0, ms = 0; double* dst = nullptr; int len = 0; };
+struct PackVectors { PackVecSeg seg[2]; const double* c0_src = nullptr; double* c0_dst = nullptr; long long dstride = 0; };
+hipError_t launch_pack_vectors(const PackVectors& a, bool f32, int members, hipStream_t st);
+// Whether columns [col0, col0 + ns) of every member's m rows are [I; 0]: a thread that finds an element != (i == j ? 1 : 0)
+// (a NaN is one) stores 0 into *word, which the caller set to 1 on the same stream.
+struct SlackHint { const void* src = nullptr; long long rs = 0, cs = 0, ms = 0, col0 = 0; int m = 0, ns = 0; int* word = nullptr; };
+hipError_t launch_slack_hint(const SlackHint& a, bool f32, int members, hipStream_t st);
+
 }  // namespace lpipm
