@@ -107,6 +107,12 @@ extern "C" {
     pub fn lpipm_upload_ub_tall(
         ctx: *mut lpipm_ctx, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, b_ub: *const f64, c: *const f64, c0: f64,
     ) -> c_int;
+    /// The tall form with equality rows: K on the `ub` rows as lpipm_upload_ub_tall, the m_eq `eq` rows through the Schur
+    /// complement S = A_eq K^-1 A_eq^T on K's factor (arguments of lpipm_upload_ub_eq; m_eq == 0: lpipm_upload_ub_tall itself).
+    pub fn lpipm_upload_ub_eq_tall(
+        ctx: *mut lpipm_ctx, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, b_ub: *const f64, m_eq: u64,
+        a_eq: *const f64, lda_eq: u64, b_eq: *const f64, c: *const f64, c0: f64,
+    ) -> c_int;
     pub fn lpipm_solve(
         ctx: *mut lpipm_ctx, opts: *const lpipm_opts, x_slack_out: *mut f64, fun_out: *mut f64,
         iterations_out: *mut u64, log: *mut lpipm_iter_row,

@@ -147,11 +147,38 @@ int lpipm_upload_ub_eq(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const double* 
  * Scope.  Cholesky arm only: lpipm_solve with solver_type 1 or 2 returns LPIPM_ERR_UNSUPPORTED, and so do
  * lpipm_update_vectors (as after lpipm_upload_ub_eq), this upload on a context of a column split (lpipm_set_collective with
  * world > 1) or with the opt-in refined solves, and lpipm_k_adat (there is no M; lpipm_k_tall_normal returns K).  The first
- * iteration's factor is not kept (as for the QR arms).  `eq` rows (the reduced system is then a saddle point, not SPD) are
- * not built; many tall LPs over one A_ub are a lockstep batch (lpipm_upload_lockstep_shared_ub_tall, below).
+ * iteration's factor is not kept (as for the QR arms).  `eq` rows go through lpipm_upload_ub_eq_tall (below: a Schur
+ * complement on K's factor); many tall LPs over one A_ub are a lockstep batch (lpipm_upload_lockstep_shared_ub_tall, below).
  * lpipm_k_iteration, lpipm_k_gemv_n, lpipm_k_gemv_t and lpipm_k_gemv_dual work as on any other upload. */
 int lpipm_upload_ub_tall(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub, const double* b_ub,
                          const double* c, double c0);
+
+/* The tall form with equality rows: min c^T x, A_ub.x <= b_ub, A_eq.x = b_eq, x >= 0, m_ub >> n and a few `eq` rows (a budget
+ * or normalisation row, an interpolation constraint, a conservation row).  The arguments of lpipm_upload_ub_eq.  K stays the
+ * n x n SPD matrix of lpipm_upload_ub_tall, built from the `ub` rows alone; the m_eq equality rows go through a Schur complement
+ * on its factor.  Once per iteration, after K = L.L^T:
+ *   Zt = A_eq.L^-T  (m_eq x n),   S = Zt.Zt^T = A_eq.K^-1.A_eq^T  (m_eq x m_eq, SPD),   S = L_S.L_S^T
+ * and sym_solve(r1, r2), r2 = [r2_u; r2_e], reads
+ *   t = W_s*r2_u + r1_s;  g = X^T.t - r1_x;  w = L^-1.g;  h = r2_e - Zt.w;  v_e = S^-1.h;  w += Zt^T.v_e;  u_x = L^-T.w;
+ *   u_s = r2_u - X.u_x;  v_u = W_s*u_s + r1_s;  u = [u_x; u_s];  v = [v_u; v_e]
+ * Afterwards lpipm_solve / lpipm_solve_device run that.  x_slack_out has n + m_ub entries, slack values last; return codes, fun,
+ * the iteration log and the `disp` table are as after lpipm_upload_ub_eq, and the contract against it on the same LP is the
+ * same status and iteration count and x to rounding (no bit-identity).  A failed pivot of K or of S is
+ * LPIPM_NUMERICAL_PROBLEM: linearly dependent equality rows, and m_eq > n, end there.  Phase times: adat_ms and adat_launches
+ * count the build of K only; potrf_ms holds the factorisation of K, then Zt, then S and its factorisation; trsv_ms all
+ * triangular solves, the two on S included.  The resident image is lpipm_upload_ub_eq's (rows of A_ub, then rows of A_eq),
+ * the transpose is of the `ub` rows only; Zt, S with its inverses and the work vectors of the Schur solve are counted by
+ * lpipm_get_resident_bytes, and nothing grows as m_ub^2.  lpipm_set_scaling works as on any upload (the image with its `eq`
+ * rows is equilibrated before the transpose is written, Zt comes from the scaled image, x comes back in the caller's units).
+ * m_eq == 0: exactly lpipm_upload_ub_tall on the same arguments -- the same request, the same bits.
+ * Refusals.  m_ub == 0 and m_eq == 0: LPIPM_UNCONSTRAINED.  Null pointers or lda < n: LPIPM_ERR_BAD_ARGUMENT.  m_ub == 0 < m_eq
+ * (not a tall LP: lpipm_upload_ub_eq is its entry), a column-split context or one with the refined solves, solver_type 1 or
+ * 2, lpipm_update_vectors[_device] and lpipm_k_adat: LPIPM_ERR_UNSUPPORTED, as on every tall upload.
+ * Out of scope: batches of such LPs; lpipm_upload_device (its form value 3 stays LPIPM_ERR_BAD_ARGUMENT); a kept K_1; the QR
+ * arms.  No first factor is kept. */
+int lpipm_upload_ub_eq_tall(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub,
+                            const double* b_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq, const double* b_eq,
+                            const double* c, double c0);
 
 /* New b and c for the resident problem of lpipm_upload / lpipm_upload_slack: b[m] and c[n] in that upload's own form (c with
  * its slack entries).  A stays where it is, so a sweep over right-hand sides or costs, or a sequence of LPs over one
@@ -335,7 +362,7 @@ int lpipm_upload_lockstep_shared_ub_eq(lpipm_ctx* ctx, uint64_t count, uint64_t 
  * LPIPM_ERR_UNSUPPORTED (as every lockstep batch); lpipm_k_tall_normal, lpipm_k_tall_sym_solve, lpipm_k_iteration and
  * lpipm_k_adat on such a batch LPIPM_ERR_UNSUPPORTED.
  * Tall LPs of one shape that each have their own matrix: lpipm_upload_lockstep_ub_tall, below.
- * Not built: `eq` rows, a kept K_1 = X^T.X + I, fused small-LP vector kernels for the tall form, tall members inside
+ * Not built: `eq` rows in a batch (one such LP: lpipm_upload_ub_eq_tall), a kept K_1 = X^T.X + I, fused small-LP vector kernels for the tall form, tall members inside
  * lpipm_solve_batch / lpipm_solve_batch_slack (lpipm_solve_batch_ub_tall is their entry). */
 int lpipm_upload_lockstep_shared_ub_tall(lpipm_ctx* ctx, uint64_t count, uint64_t n, uint64_t m_ub, const double* A_ub,
                                          uint64_t lda_ub, const double* const* b, const double* const* c,
@@ -485,15 +512,22 @@ int lpipm_k_resident_matrix(lpipm_ctx* ctx, uint64_t member, uint64_t rows, uint
  * values it holds; another shape is LPIPM_ERR_BAD_ARGUMENT, a scaled upload or a column-split context
  * LPIPM_ERR_UNSUPPORTED.  The descriptor is checked as lpipm_upload_device checks it. */
 int lpipm_k_pack_matrix(lpipm_ctx* ctx, const lpipm_device_problem* d, int repeats, double* pack_ms_out, double* copy_ms_out);
-/* On a single tall upload (lpipm_upload_ub_tall; not a batch), with nx its structural columns, m its rows, n = nx + m and dinv[n] = x / z:
- * K_out (nx x nx row-major, LOWER triangle valid) = X^T.diag(1 / dinv_s).X + diag(1 / dinv_x).  Any other upload:
- * LPIPM_ERR_UNSUPPORTED. */
+/* On a single tall upload (lpipm_upload_ub_tall or lpipm_upload_ub_eq_tall; not a batch), with nx its structural columns, m_ub
+ * its `ub` rows, n = nx + m_ub and dinv[n] = x / z:
+ * K_out (nx x nx row-major, LOWER triangle valid) = X^T.diag(1 / dinv_s).X + diag(1 / dinv_x), from the `ub` rows.  Any other
+ * upload: LPIPM_ERR_UNSUPPORTED. */
 int lpipm_k_tall_normal(lpipm_ctx* ctx, const double* dinv, double* K_out);
 /* The reduced sym_solve (newton_equations.rs:214-225) on a tall upload at the given dinv[n], for nrhs (1|2) right-hand sides:
  * R1 nrhs x n, R2 nrhs x m -> U_out nrhs x n, V_out nrhs x m, with M.V = R2 + A.(dinv * R1), U = dinv * (A^T.V - R1) in exact
- * arithmetic.  info_out (nullable): pivot failure of K as lpipm_k_potrf.  The iterate of the context is overwritten. */
+ * arithmetic.  info_out (nullable): pivot failure of K as lpipm_k_potrf.  The iterate of the context is overwritten.
+ * After lpipm_upload_ub_eq_tall m = m_ub + m_eq: R2 and V_out carry the `eq` entries behind the `ub` ones, and info_out also
+ * reports a failed pivot of S. */
 int lpipm_k_tall_sym_solve(lpipm_ctx* ctx, const double* dinv, int nrhs, const double* R1, const double* R2, double* U_out,
                            double* V_out, int32_t* info_out);
+/* After lpipm_upload_ub_eq_tall with m_eq > 0: builds K at dinv[n], factors it and returns the Schur complement
+ * S_out (m_eq x m_eq row-major, LOWER triangle valid) = A_eq.K^-1.A_eq^T, as built (before its own factorisation).  Any other
+ * upload: LPIPM_ERR_UNSUPPORTED.  The iterate of the context is overwritten. */
+int lpipm_k_tall_schur(lpipm_ctx* ctx, const double* dinv, double* S_out);
 /* newton_equations.rs:129-131: in-place lower Cholesky of the m x m row-major matrix M (lower
  * triangle read, lower triangle written).  info_out: 0, or k+1 for the first non-positive pivot. */
 int lpipm_k_potrf(lpipm_ctx* ctx, uint64_t m, double* M_inout, int32_t* info_out, int repeats,

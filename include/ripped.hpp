@@ -204,6 +204,10 @@ public:
     // (lpipm_upload_ub_tall) -- the solve factors the n x n reduced system instead of the m_ub x m_ub normal matrix.  For LPs
     // with many more rows than columns; Cholesky arm only.  Problems with `eq` rows are solved as before.
     InteriorPoint& tall_form(bool on = true) { tall_ = on; return *this; }
+    // A separate opt-in: a problem with `ub` rows and any `eq` rows goes through lpipm_upload_ub_eq_tall -- the n x n reduced
+    // system of the `ub` rows, the `eq` rows through a Schur complement on its factor.  For many more `ub` rows than columns and
+    // a few `eq` rows; Cholesky arm only.  tall_form() alone keeps solving problems with `eq` rows as before.
+    InteriorPoint& tall_eq_form(bool on = true) { tall_eq_ = on; return *this; }
 
     // mod.rs:161-168.  One context (stream + device buffers) per call keeps `solve(&self)` stateless
     // and re-entrant like the reference; callers that solve many problems can hold an lpipm_ctx.
@@ -212,7 +216,13 @@ public:
         raise_for(lpipm_create(device_, &ctx));
         struct Guard { lpipm_ctx* c; ~Guard() { lpipm_destroy(c); } } guard{ctx};
         const Matrix& A = problem.A();
-        if (tall_ && problem.n_slack() == A.rows && problem.n_slack() < A.cols)
+        if (tall_eq_ && problem.n_slack() > 0 && problem.n_slack() <= A.rows && problem.n_slack() < A.cols) {
+            // A = [[X I], [A_eq 0]]: the `ub` block is the first n_slack rows, the `eq` block the rest, both with lda = cols
+            const std::size_t m_ub = problem.n_slack(), m_eq = A.rows - m_ub;
+            raise_for(lpipm_upload_ub_eq_tall(ctx, A.cols - m_ub, m_ub, A.data.data(), A.cols, problem.b().data(), m_eq,
+                                              m_eq ? A.data.data() + m_ub * A.cols : nullptr, A.cols,
+                                              m_eq ? problem.b().data() + m_ub : nullptr, problem.c().data(), problem.c0()));
+        } else if (tall_ && problem.n_slack() == A.rows && problem.n_slack() < A.cols)
             // `ub` rows only: A = [X I], X = the first cols - n_slack columns (lda = cols); the slack costs are zero
             raise_for(lpipm_upload_ub_tall(ctx, A.cols - problem.n_slack(), A.rows, A.data.data(), A.cols, problem.b().data(),
                                            problem.c().data(), problem.c0()));
@@ -248,7 +258,7 @@ public:
 private:
     lpipm_opts o_;
     int device_;
-    bool tall_ = false;
+    bool tall_ = false, tall_eq_ = false;
 };
 
 inline InteriorPoint InteriorPointBuilder::build() const {

@@ -375,6 +375,7 @@ class Context:
                                f"{_capi.last_error_detail()} -- a HIP device is required, there is no CPU path")
         self.device = int(device)
         self.n = self.m = 0
+        self._m_eq = 0               # `eq` rows of the resident upload_tall_eq problem; every upload that succeeds sets it with m and n
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -389,7 +390,8 @@ class Context:
 
     def upload(self, problem: Problem, use_slack_structure: bool = True, tall: bool = False):
         """tall=True: the tall inequality form (lpipm_upload_ub_tall) -- a Problem with `ub` rows only, usually many more of
-        them than columns; the solves then factor the n x n reduced system instead of the m x m normal matrix."""
+        them than columns; the solves then factor the n x n reduced system instead of the m x m normal matrix.  (A Problem
+        that has `eq` rows as well: upload_tall_eq.)"""
         if tall:
             parts = getattr(problem, "_parts", None)
             if parts is None or parts[0].shape[0] == 0 or parts[2].shape[0] != 0:
@@ -398,7 +400,7 @@ class Context:
             A_ub, b_ub, c = _f64(A_ub), _f64(b_ub), _f64(c)
             m_ub, n = A_ub.shape[0], c.shape[0]
             _raise_for(_capi.lib().lpipm_upload_ub_tall(self._h, n, m_ub, _p(A_ub), n, _p(b_ub), _p(c), float(problem.c0())))
-            self.m, self.n = m_ub, n + m_ub
+            self.m, self.n, self._m_eq = m_ub, n + m_ub, 0
             return self
         if use_slack_structure and getattr(problem, "_parts", None) is not None:
             # device-side assembly: the ub / eq blocks as given, no host slack matrix (lpipm_upload_ub_eq)
@@ -408,10 +410,26 @@ class Context:
                                                 m_eq, _p(A_eq) if m_eq else None, n, _p(b_eq) if m_eq else None,
                                                 _p(c), float(problem.c0()))
             _raise_for(rc)
-            self.m, self.n = m_ub + m_eq, n + m_ub
+            self.m, self.n, self._m_eq = m_ub + m_eq, n + m_ub, 0
             return self
         A, b, c = _f64(problem.A()), _f64(problem.b()), _f64(problem.c())
         return self.upload_arrays(A, b, c, problem.c0(), problem.n_slack() if use_slack_structure else 0)
+
+    def upload_tall_eq(self, problem: Problem):
+        """The tall form with equality rows (lpipm_upload_ub_eq_tall): a Problem with `ub` rows -- usually many more of them
+        than columns -- and any `eq` rows.  The solves factor the n x n reduced system of the `ub` rows and take the `eq` rows
+        through a Schur complement on its factor; x_slack has n + m_ub entries, slack values last.  Without `eq` rows this is
+        upload(problem, tall=True).  A Problem without `ub` rows is a ValueError (upload() is its entry)."""
+        parts = getattr(problem, "_parts", None)
+        if parts is None or parts[0].shape[0] == 0:
+            raise ValueError("upload_tall_eq needs a Problem built from `ub` rows (and any `eq` rows)")
+        A_ub, b_ub, A_eq, b_eq, c = (_f64(a) for a in parts)
+        m_ub, m_eq, n = A_ub.shape[0], A_eq.shape[0], c.shape[0]
+        rc = _capi.lib().lpipm_upload_ub_eq_tall(self._h, n, m_ub, _p(A_ub), n, _p(b_ub), m_eq, _p(A_eq) if m_eq else None, n,
+                                                 _p(b_eq) if m_eq else None, _p(c), float(problem.c0()))
+        _raise_for(rc)
+        self.m, self.n, self._m_eq = m_ub + m_eq, n + m_ub, m_eq
+        return self
 
     def upload_arrays(self, A, b, c, c0=0.0, n_slack=0):
         A, b, c = _f64(A), _f64(b), _f64(c)
@@ -420,7 +438,7 @@ class Context:
         m, n = A.shape
         rc = _capi.lib().lpipm_upload_slack(self._h, m, n, _p(A), n, _p(b), _p(c), float(c0), int(n_slack))
         _raise_for(rc)
-        self.m, self.n = m, n
+        self.m, self.n, self._m_eq = m, n, 0
         return self
 
     def update_vectors(self, b, c):
@@ -451,7 +469,7 @@ class Context:
         del keep
         if batch:
             self._lock = (K, nb, n_out, None, None, [np.empty(d.n)])     # (_lockstep_form reads the length of a c[i] from it)
-        self.m, self.n = nb, n_out
+        self.m, self.n, self._m_eq = nb, n_out, 0
         return self
 
     def update_vectors_device(self, b, c):
@@ -563,7 +581,7 @@ class Context:
             raise IncompatibleInputDimensions()
         m, nl = A.shape
         _raise_for(_capi.lib().lpipm_upload_nsplit(self._h, m, int(n_total), nl, _p(A), nl, _p(b), _p(c), float(c0)))
-        self.m, self.n = m, nl
+        self.m, self.n, self._m_eq = m, nl, 0
         return self
 
     def _upload_members(self, entry, head, bs, cs, c0s, m, n, nc, matrix, tail=()):
@@ -575,7 +593,7 @@ class Context:
         c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
         _raise_for(getattr(_capi.lib(), entry)(self._h, K, *head, _ptrs(bs), _ptrs(cs), c0, *tail))
         self._lock = (K, m, n, matrix, bs, cs)      # keep the host arrays alive only for the duration of the call chain
-        self.m, self.n = m, n
+        self.m, self.n, self._m_eq = m, n, 0
         return self
 
     def upload_lockstep(self, As, bs, cs, c0s=None, n_slack=0):
@@ -762,10 +780,20 @@ class Context:
         dinv = _f64(dinv)
         if dinv.shape != (self.n,):
             raise IncompatibleInputDimensions()
-        nx = self.n - self.m
+        nx = self.n - (self.m - self._m_eq)
         K = np.empty((nx, nx))
         _raise_for(_capi.lib().lpipm_k_tall_normal(self._h, _p(dinv), _p(K)))
         return K
+
+    def k_tall_schur(self, dinv):
+        """S = A_eq K^-1 A_eq^T of the upload_tall_eq problem at dinv (m_eq x m_eq, lower triangle valid), as built from
+        Zt = A_eq L^-T behind K's factorisation."""
+        dinv = _f64(dinv)
+        if dinv.shape != (self.n,):
+            raise IncompatibleInputDimensions()
+        S = np.empty((self._m_eq, self._m_eq))
+        _raise_for(_capi.lib().lpipm_k_tall_schur(self._h, _p(dinv), _p(S)))
+        return S
 
     def k_tall_sym_solve(self, dinv, R1, R2):
         """The reduced sym_solve of the tall upload at dinv for 1 or 2 right-hand sides: R1 (nrhs, n), R2 (nrhs, m)

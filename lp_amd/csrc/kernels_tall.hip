@@ -19,6 +19,13 @@
 // TallArgs and the right-hand sides to the member and skips a finished one, as vbatch does on the dense path; a member's
 // arithmetic and reduction order are those of the single LP.  The kernels of the speculatively enqueued head test the done
 // word.
+// Equality rows (lpipm_upload_ub_eq_tall, t.me > 0): the image is [X; A_eq], K is built from the ms `ub` rows alone, and between
+// the two halves of the solve on K = L.L^T the `eq` rows come in through Zt = A_eq.L^-T and S = Zt.Zt^T (kernels_trsm.hip,
+// solver.hip: tall_eq_schur, tall_eq_reduced_solve):
+//   w = L^-1 g;  h = r2_e - Zt.w;  v_e = S^-1 h;  w += Zt^T.v_e (k_tall_eq_add_w);  u_x = L^-T w;  v = [W_s * u_s + r1_s; v_e]
+// The eq-aware siblings below (k_tall_eq_setup, _pq_uv, _uv_corr) loop slack quantities over ms and row quantities over
+// ms + me; k_tall_fold and k_tall_residuals depend on neither count and serve both.  The kernels of every other tall upload are
+// untouched: their bits stay.
 #include "vec_kernels.hpp"
 #include "vec_device.hpp"
 
@@ -76,8 +83,29 @@ __global__ __launch_bounds__(256) void k_tall_setup(VecArgs a, TallArgs t, int w
     if (with_scales)
         for (int j = blockIdx.x * 256 + threadIdx.x; j < t.nx; j += stride) t.Ex[j] = a.z[j] / a.x[j];
 }
+// Equality rows (t.me > 0): the same over the ms `ub` rows alone -- only they carry a slack column, K is built from them, and
+// t stays zero on the `eq` rows (nothing ever writes it there), so the pass X^T.t over the whole image sees the `ub` rows only.
+__global__ __launch_bounds__(256) void k_tall_eq_setup(VecArgs a, TallArgs t, int with_scales, int nrhs, TallRhs rhs) {
+    if (!tbatch(a, t, rhs)) return;
+    const double *r1a = rhs.r1a, *r2a = rhs.r2a, *r1b = rhs.r1b, *r2b = rhs.r2b;
+    const int stride = gridDim.x * 256;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < t.ms; i += stride) {
+        double ws;
+        if (with_scales) { ws = a.z[t.nx + i] / a.x[t.nx + i]; t.Ws[i] = ws; }
+        else ws = t.Ws[i];
+        if (nrhs > 0) t.T[i] = ws * r2a[i] + r1a[t.nx + i];
+        if (nrhs > 1) t.T[a.mp + i] = ws * r2b[i] + r1b[t.nx + i];
+    }
+    if (with_scales)
+        for (int j = blockIdx.x * 256 + threadIdx.x; j < t.nx; j += stride) t.Ex[j] = a.z[j] / a.x[j];
+}
 void tall_setup(const VecArgs& a, const TallArgs& t, bool with_scales, int nrhs, const double* r1a, const double* r2a,
                 const double* r1b, const double* r2b, hipStream_t st) {
+    if (t.me > 0) {
+        hipLaunchKernelGGL(k_tall_eq_setup, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, with_scales ? 1 : 0, nrhs,
+                           TallRhs{r1a, r2a, r1b, r2b});
+        return;
+    }
     hipLaunchKernelGGL(k_tall_setup, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, with_scales ? 1 : 0, nrhs,
                        TallRhs{r1a, r2a, r1b, r2b});
 }
@@ -161,10 +189,97 @@ __global__ __launch_bounds__(256) void k_tall_uv_corr(VecArgs a, TallArgs t, Tal
     }
     block_reduce_store<2, false>(acc, a.red, 0);
 }
+// Equality rows: n = nx + ms columns as above; of the ms + me rows the first ms are v_u = W_s * u_s + r1_s, the others v_e,
+// which the Schur solve has left in Ve.  The same dots in the same slots, reduced in the same order.
+__global__ __launch_bounds__(256) void k_tall_eq_pq_uv(VecArgs a, TallArgs t, TallRhs rhs) {
+    if (!tbatch(a, t, rhs)) return;
+    const double *r1a = rhs.r1a, *r1b = rhs.r1b;
+    const int stride = gridDim.x * 256;
+    double acc[4] = {0, 0, 0, 0};
+    int nan = 0;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < a.n; j += stride) {
+        double p, u;
+        if (j < t.nx) { p = t.G[j]; u = t.G[t.nxp + j]; }
+        else          { p = t.Us[j - t.nx]; u = t.Us[a.mp + j - t.nx]; }
+        const double cj = a.c[j];
+        a.p[j] = p;
+        a.u[j] = u;
+        acc[0] += cj * p;
+        acc[1] += cj * u;
+        nan |= (p != p);
+    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
+        const double bi = a.b[i];
+        double q, v;
+        if (i < t.ms) {
+            const double ws = t.Ws[i];
+            q = ws * t.Us[i] + r1a[t.nx + i];
+            v = ws * t.Us[a.mp + i] + r1b[t.nx + i];
+        } else { q = t.Ve[i - t.ms]; v = t.Ve[t.mep + i - t.ms]; }
+        a.q[i] = q;
+        a.R[i] = q;
+        a.R[a.mp + i] = v;
+        acc[2] += bi * q;
+        acc[3] += bi * v;
+        nan |= (q != q);
+    }
+    if (nan) atomicOr(a.flags, FLAG_NAN_PQ);
+    block_reduce_store<4, false>(acc, a.red, 0);
+}
+__global__ __launch_bounds__(256) void k_tall_eq_uv_corr(VecArgs a, TallArgs t, TallRhs rhs) {
+    if (!tbatch(a, t, rhs)) return;
+    const double* r1a = rhs.r1a;
+    const int stride = gridDim.x * 256;
+    double acc[2] = {0, 0};
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < a.n; j += stride) {
+        const double u = j < t.nx ? t.G[j] : t.Us[j - t.nx];
+        a.u[j] = u;
+        acc[0] += a.c[j] * u;
+    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
+        const double v = i < t.ms ? t.Ws[i] * t.Us[i] + r1a[t.nx + i] : t.Ve[i - t.ms];
+        a.R[i] = v;
+        acc[1] += a.b[i] * v;
+    }
+    block_reduce_store<2, false>(acc, a.red, 0);
+}
+// W[r][j] += sum_s ZtPart[s][r][j], j < nxp, slabs in index order.  grid (256-column groups of nxp, right-hand sides, LPs).
+__global__ __launch_bounds__(256) void k_tall_eq_add_w(VecArgs a, TallArgs t, int nrhs, double* W, const double* ZtPart) {
+    TallRhs ptrs{W, ZtPart, nullptr, nullptr};       // (moved to the member with everything else)
+    if (!tbatch(a, t, ptrs)) return;
+    const int j = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
+    if (j >= t.nxp) return;
+    double s = 0.0;
+    for (int sp = 0; sp < t.mep / GEMVT_ROWS; ++sp) s += ptrs.r2a[((long long)sp * nrhs + r) * t.nxp + j];
+    double* w = const_cast<double*>(ptrs.r1a);
+    w[(long long)r * t.nxp + j] += s;
+}
+// More equality rows than columns: S = Zt.Zt^T has rank <= nx < me, so its pivot nx is zero in exact arithmetic whatever the
+// data; rounding may leave it a tiny positive number.  The pivot-failure word gets what exact arithmetic gives (the first
+// failure recorded wins, as in the factorisation).
+__global__ void k_tall_eq_singular(VecArgs a, TallArgs t) {
+    TallRhs none;
+    if (!tbatch(a, t, none)) return;
+    if (threadIdx.x == 0) atomicCAS((int*)a.potrf_info, 0, t.nx + 1);
+}
+void tall_eq_singular(const VecArgs& a, const TallArgs& t, hipStream_t st) {
+    hipLaunchKernelGGL(k_tall_eq_singular, dim3(1, 1, a.bcount), dim3(64), 0, st, a, t);
+}
+void tall_eq_add_w(const VecArgs& a, const TallArgs& t, int nrhs, double* W, const double* ZtPart, hipStream_t st) {
+    hipLaunchKernelGGL(k_tall_eq_add_w, dim3((t.nxp + 255) / 256, nrhs, a.bcount), dim3(256), 0, st, a, t, nrhs, W, ZtPart);
+}
 void tall_pq_uv(const VecArgs& a, const TallArgs& t, const double* r1a, const double* r1b, hipStream_t st) {
+    if (t.me > 0) {
+        hipLaunchKernelGGL(k_tall_eq_pq_uv, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, TallRhs{r1a, nullptr, r1b, nullptr});
+        return;
+    }
     hipLaunchKernelGGL(k_tall_pq_uv, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, TallRhs{r1a, nullptr, r1b, nullptr});
 }
 void tall_uv_corr(const VecArgs& a, const TallArgs& t, const double* r1a, hipStream_t st) {
+    if (t.me > 0) {
+        hipLaunchKernelGGL(k_tall_eq_uv_corr, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, TallRhs{r1a, nullptr, nullptr, nullptr});
+        return;
+    }
     hipLaunchKernelGGL(k_tall_uv_corr, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, TallRhs{r1a, nullptr, nullptr, nullptr});
 }
 

@@ -271,6 +271,13 @@ hipError_t launch_chol_solve(const double* L, int64_t ld, const FactorPlan& plan
                              double* Yscratch, hipStream_t st, const Batch& bt = Batch{}, const SolveSteps& steps = SolveSteps{},
                              bool shared_factor = false);
 
+// ---------------------------------------------------------------- many right-hand sides (kernels_trsm.hip)
+// Z = B . L^-T for the factor L (ld ldl) of `plan`, order n = plan.mp: row r of Z solves L.z = B[r,:]^T.  B: rows x cols
+// (cols <= n, zeros assumed beyond), row-major.  Z: round_up(rows, 16) x n, ld ldz (a multiple of 4), written whole -- rows
+// past `rows` as zeros.  One launch, one workgroup per 16 rows, fixed-order sums.
+hipError_t launch_trsm_lt(const double* B, int64_t ldb, int rows, int cols, const double* L, int64_t ldl, const FactorPlan& plan,
+                          double* Z, int64_t ldz, hipStream_t st);
+
 // ---------------------------------------------------------------- QR arms (kernels_qr.hip)
 // EquationSolverType::{Inverse, LeastSquares}: Householder QR of the full mp x mp matrix whose LOWER
 // triangle is in M (the upper one is filled in first); reflectors below the diagonal, R on and above,

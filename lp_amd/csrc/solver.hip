@@ -69,7 +69,8 @@ struct StreamRes {
 // with equal geometries share them.  nxp, mk: tall only (zero otherwise); nsplit and nblk follow from the others.
 struct Geometry {
     int mp = 0, np = 0, npa = 0, nxp = 0, mk = 0, B = 0, nsplit = 0, nblk = 0;
-    bool shared = false, keep = false, tall = false;
+    int mep = 0;                 // tall_eq only: the `eq` rows padded to 128, the order of S (mk is then that of the `ub` rows alone)
+    bool shared = false, keep = false, tall = false, tall_eq = false;
     bool operator==(const Geometry&) const = default;
 };
 
@@ -118,6 +119,16 @@ struct Problem {
     bool tall = false;
     double* Xt = nullptr;        // nxp x mk, row-major, zero padded: X^T of the resident (scaled) X
     TallArgs tv{};
+    // A tall LP with `me` equality rows (lpipm_upload_ub_eq_tall; tall is set as well): the image is lpipm_upload_ub_eq's, rows
+    // of X then rows of A_eq; Xt and K are those of the `ub` rows alone.  Once per iteration, behind K's factorisation,
+    // Zt = A_eq.L^-T (mep x nxp, padding rows zero) and S = Zt.Zt^T (mep x mep, diagonal padded with ones from me) with its
+    // own factor plan and A.D.A^T plan (`ones_k`: its dinv).  H, tv.Ve: the work vectors of the solve on S; ZtPart: the
+    // row-split slabs of Zt^T.v_e.
+    bool tall_eq = false;
+    int me = 0;
+    double *Zt = nullptr, *S = nullptr, *H = nullptr, *ZtPart = nullptr, *ones_k = nullptr;
+    const FactorPlan* factor_s = nullptr;  // lpipm_ctx::plan_s of the uploading context
+    AdatRes adat_s;
     bool from_parts = false;     // uploaded as ub / eq blocks (lpipm_upload_ub_eq): b and c are not in the caller's slack form
     bool owned_tall = false;     // lpipm_upload_lockstep_ub_tall: a tall batch (of any count) whose members own X_i, Xt_i and K
     // Equilibration (lpipm_set_scaling): the exponents and the maxima slabs, in an allocation of their own that exists only
@@ -139,6 +150,8 @@ struct lpipm_ctx {
     StreamRes rs;
     Problem p;
     AdatPlan ap;
+    AdatPlan ap_s;               // tall_eq: the plan of the launch that builds S from Zt
+    FactorPlan plan_s;           //          and the factor plan of S
     std::vector<void*> kallocs;  // buffers of the stand-alone kernel entry points
     FactorPlan plan, kplan;
     double* ktau = nullptr;
@@ -442,6 +455,7 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     if (c->stage_host) (void)hipHostFree(c->stage_host);
     if (c->hint_dev) (void)hipFree(c->hint_dev);
     adat_lists_destroy(c->p.adat);
+    adat_lists_destroy(c->p.adat_s);
     free_list(c->kallocs);
     if (c->mpack) (void)hipFree(c->mpack);
     if (c->st_c) { (void)hipStreamSynchronize(c->st_c); (void)hipStreamDestroy(c->st_c); }
@@ -449,6 +463,7 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     if (c->ev_c1) (void)hipEventDestroy(c->ev_c1);
     factor_plan_destroy(c->plan);
     factor_plan_destroy(c->plan1);
+    factor_plan_destroy(c->plan_s);
     factor_plan_destroy(c->kplan);
     if (c->la.side) { (void)hipStreamSynchronize(c->la.side); (void)hipStreamDestroy(c->la.side); }
     for (hipEvent_t e : c->la.ev_chain) (void)hipEventDestroy(e);
@@ -496,6 +511,8 @@ struct Upload {
     const double* c0 = nullptr;          // nullable: all zero
     bool shared = false;                 // one matrix for all `count` LPs
     bool tall = false;                   // parts with `ub` rows only: the tall inequality form, of the LP or of every member over one X
+    bool tall_eq = false;                // tall, one LP, with `eq` rows as well: the Schur complement on K's factor
+    uint64_t me = 0;                     //   its `eq` rows (m - parts.m_ub > 0)
     bool owned = false;                  // tall, a batch whose members own their matrices: X_i = A[i] (lda), b[i] per member; parts holds m_ub only
     bool hint_verified = false;          // the caller has checked the hint on these very matrices (batch_impl): it is not repeated
     bool keep_ok = true;                 // false: solved once (lpipm_solve_batch) or never through the kept factor (column split)
@@ -526,6 +543,7 @@ static int check_upload(const lpipm_ctx* c, const Upload& u) {
         else if (q.m_ub && (!q.A_ub || q.lda_ub < nx || (!u.shared && !q.b_ub))) return LPIPM_ERR_BAD_ARGUMENT;
         if (m_eq && (!q.A_eq || q.lda_eq < nx || (!u.shared && !q.b_eq))) return LPIPM_ERR_BAD_ARGUMENT;
         if (!c) return LPIPM_ERR_BAD_ARGUMENT;
+        if (u.tall_eq && q.m_ub == 0) return LPIPM_ERR_UNSUPPORTED;     // no `ub` row: not a tall LP (lpipm_upload_ub_eq is its entry)
         if (u.tall && (c->world > 1 || c->refine > 0)) return LPIPM_ERR_UNSUPPORTED;   // a column-split context; the refined solves
         for (uint64_t i = 0; i < u.count; ++i)
             if (!u.c[i] || (u.b && !u.b[i]) || (u.owned && !u.A[i])) return LPIPM_ERR_BAD_ARGUMENT;
@@ -537,6 +555,7 @@ static Geometry geometry_of(const Upload& u, uint64_t n_slack, bool first_cache,
     Geometry g;
     g.mp = (int)round_up(u.m, NB); g.np = (int)round_up(u.n, BK); g.npa = (int)round_up(u.n - n_slack, BK);
     if (u.tall) { g.nxp = (int)round_up(g.npa, NB); g.mk = (int)round_up(u.m, BK); }   // the order of K, the contraction of its build
+    if (u.tall_eq) { g.tall_eq = true; g.mk = (int)round_up(u.parts->m_ub, BK); g.mep = (int)round_up(u.me, NB); }
     g.B = (int)u.count; g.nsplit = g.mp / GEMVT_ROWS;
     g.nblk = ((g.mp > g.np ? g.mp : g.np) + 255) / 256;      // (of the larger of m and n: 256 is a multiple of both paddings)
     if (g.nblk > RED_STRIDE) g.nblk = RED_STRIDE;
@@ -550,6 +569,7 @@ static void set_geometry(Problem& p, const Geometry& g) {
     p.mp = g.mp; p.np = g.np; p.npa = g.npa; p.B = g.B; p.nsplit = g.nsplit; p.nblk = g.nblk; p.shared_a = g.shared; p.tall = g.tall;
     p.tv = TallArgs{};
     if (g.tall) { p.tv.npa = g.npa; p.tv.nxp = g.nxp; p.tv.mk = g.mk; }     // (tv.nx: the padded geometry may be shared by several nx)
+    p.tall_eq = g.tall_eq; p.tv.mep = g.mep;                                 // (tv.ms, tv.me: likewise)
     VecArgs& v = p.va;
     v.np = g.np; v.mp = g.mp; v.nblk = g.nblk; v.nsplit = g.nsplit; v.bcount = g.B; v.bfirst = 0; v.refine_below = refine_below();
 }
@@ -615,8 +635,10 @@ static int layout_first_factor(Problem& p, const FactorPlan& plan, FactorPlan& p
 // the work vectors of the reduced solve.  Nothing grows as m^2: no M, M0 or kept first factor.
 // A member of a shared batch (p.shared_a) has the same arena without A (tall: X and Xt): layout_shared.  A member of a tall
 // batch that owns its matrix has the single tall LP's arena.
-static int layout_problem(Problem& p, FactorPlan& plan, FactorPlan& plan1, const AdatPlan& ap, int refine, Arena& ar,
-                          bool build, hipStream_t st) {
+// tall_eq: behind K and its plan, Zt, S with its plan (plan_s), the work vectors of the Schur solve, the slabs of Zt^T.v_e, the
+// vector of ones and the words and slabs of the launch that builds S (ap_s).
+static int layout_problem(Problem& p, FactorPlan& plan, FactorPlan& plan1, FactorPlan& plan_s, const AdatPlan& ap,
+                          const AdatPlan& ap_s, int refine, Arena& ar, bool build, hipStream_t st) {
     TallArgs& t = p.tv;
     const size_t mp = (size_t)p.mp, np = (size_t)p.np, nxp = (size_t)t.nxp;
     p.A = p.shared_a ? nullptr : ar.take<double>(mp * p.npa);
@@ -627,7 +649,18 @@ static int layout_problem(Problem& p, FactorPlan& plan, FactorPlan& plan1, const
         t.T = ar.take<double>(2 * mp); t.G = ar.take<double>(2 * nxp); t.Us = ar.take<double>(2 * mp);
         p.M = ar.take<double>(nxp * nxp);
         LP_HIP(factor_plan_create(plan, p.M, t.nxp, t.nxp, ar, build, st, super_for(t.nxp), merge_edge_for(1)));
+        p.Zt = p.S = p.H = p.ZtPart = p.ones_k = nullptr; t.Ve = nullptr; p.factor_s = nullptr;
+        if (p.tall_eq) {
+            const size_t mep = (size_t)t.mep;
+            p.Zt = ar.take<double>(mep * nxp); p.S = ar.take<double>(mep * mep);
+            LP_HIP(factor_plan_create(plan_s, p.S, t.mep, t.mep, ar, build, st, super_for(t.mep), merge_edge_for(1)));
+            p.factor_s = &plan_s;
+            t.Ve = ar.take<double>(2 * mep); p.H = ar.take<double>(2 * mep);
+            p.ZtPart = ar.take<double>(mep / GEMVT_ROWS * 2 * nxp); p.ones_k = ar.take<double>(nxp);
+            adat_take(p.adat_s, ap_s, ar);
+        } else factor_plan_destroy(plan_s);
     } else {
+        factor_plan_destroy(plan_s);
         p.M = ar.take<double>(mp * mp);
         LP_HIP(factor_plan_create(plan, p.M, p.mp, p.mp, ar, build, st, super_for(p.mp), merge_edge_for(p.B)));
     }
@@ -664,19 +697,20 @@ static int relayout(lpipm_ctx* c, const Geometry& g) {
     LP_HIP(hipStreamSynchronize(st));
     if (p.arena) { LP_HIP(hipFree(p.arena)); p.arena = nullptr; }
     if (p.a_shared) { LP_HIP(hipFree(p.a_shared)); p.a_shared = nullptr; p.a_shared_bytes = 0; }
-    adat_lists_destroy(p.adat);
-    factor_plan_destroy(c->plan); factor_plan_destroy(c->plan1);
+    adat_lists_destroy(p.adat); adat_lists_destroy(p.adat_s);
+    factor_plan_destroy(c->plan); factor_plan_destroy(c->plan1); factor_plan_destroy(c->plan_s);
     p.has_problem = false;
     set_geometry(p, g);
     c->ap = adat_plan_of(g, c->num_cu, c->world, c->units_env);
+    c->ap_s = g.tall_eq ? plan_adat(g.mep, g.nxp, 1, c->num_cu, 1, c->units_env) : AdatPlan{};     // S = Zt.Zt^T: mep rows, contraction nxp
     Arena measure;
-    LP_TRY(layout_problem(p, c->plan, c->plan1, c->ap, c->refine, measure, false, st));
+    LP_TRY(layout_problem(p, c->plan, c->plan1, c->plan_s, c->ap, c->ap_s, c->refine, measure, false, st));
     p.bstride = round_up(measure.off, 4096);
     p.arena_bytes = p.bstride * (size_t)g.B; p.va.bstride = (long long)p.bstride;
     LP_HIP(hipMalloc((void**)&p.arena, p.arena_bytes));
     LP_HIP(hipMemsetAsync(p.arena, 0, p.arena_bytes, st));
     Arena real{p.arena};
-    LP_TRY(layout_problem(p, c->plan, c->plan1, c->ap, c->refine, real, true, st));
+    LP_TRY(layout_problem(p, c->plan, c->plan1, c->plan_s, c->ap, c->ap_s, c->refine, real, true, st));
     if (g.shared) {
         Arena sh_measure;
         LP_TRY(layout_shared(p, c->plan, c->plan1, sh_measure, false, st));
@@ -687,6 +721,7 @@ static int relayout(lpipm_ctx* c, const Geometry& g) {
         LP_TRY(layout_shared(p, c->plan, c->plan1, sh, true, st));
     }
     LP_HIP(adat_lists_create(p.adat, c->ap, g.tall ? g.nxp : g.mp, g.B, st));    // (drains st)
+    if (g.tall_eq) LP_HIP(adat_lists_create(p.adat_s, c->ap_s, g.mep, 1, st));
     LP_TRY(stream_res_grow_status(c->rs, (size_t)g.B));
     return LPIPM_OK;
 }
@@ -867,6 +902,9 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
     LP_TRY(scale_setup(c, g.mp, g.np, g.npa, u.shared ? 1 : count));
     p.m = u.m; p.n = u.n; p.ns = (int)n_slack; p.nx = (int)nx;
     if (u.tall) p.tv.nx = (int)nx;            // (the padded geometry may be shared by several nx)
+    const uint64_t m_ub = u.parts ? u.parts->m_ub : 0;
+    p.me = u.tall_eq ? (int)u.me : 0;
+    if (u.tall) { p.tv.ms = (int)m_ub; p.tv.me = p.me; }
     p.from_parts = u.parts.has_value(); p.owned_tall = u.owned;
     p.va.n = (int)u.n; p.va.m = (int)u.m; p.va.n_total = (long long)u.n; p.va.gs = nullptr; c->colsplit = false;   // lpipm_upload_nsplit overrides
     // A single LP's loop ends on the host, so its kernels need not test the done word (one dependent load
@@ -879,6 +917,8 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
     for (int i = 0; i < count; ++i) c0v[i] = u.c0 ? u.c0[i] : 0.0;
     const std::vector<double> onesv(p.shared_factor ? (size_t)g.np : 0, 1.0);     // likewise
     if (p.shared_factor) LP_HIP(hipMemcpyAsync(p.ones, onesv.data(), onesv.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    const std::vector<double> ones_k(u.tall_eq ? (size_t)g.nxp : 0, 1.0);         // likewise: the dinv of S = Zt.Zt^T
+    if (u.tall_eq) LP_HIP(hipMemcpyAsync(p.ones_k, ones_k.data(), ones_k.size() * sizeof(double), hipMemcpyHostToDevice, st));
     LP_TRY(u.dev ? copy_in_device(c, u, c0v.data()) : copy_in(c, u, c0v.data()));
     if (p.scale_passes > 0) {   // equilibrate what was just copied: the solves see the scaled problem only
         const Batch members{count, (long long)p.bstride, nullptr, 0};
@@ -888,9 +928,10 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
     }
     // tall: the resident transpose, from the X the solves see (behind the equilibration: both copies carry its exponents)
     //       (every member's own, in one launch, when the members own their matrices)
-    if (u.tall) LP_HIP(tall_transpose(p.A, g.npa, (int)u.m, (int)nx, p.Xt, g.mk, st, u.shared ? Batch{} : Batch{count, (long long)p.bstride, nullptr, 0}));
+    //       (of the `ub` rows alone when there are `eq` rows: K is built from them)
+    if (u.tall) LP_HIP(tall_transpose(p.A, g.npa, (int)(u.tall_eq ? m_ub : u.m), (int)nx, p.Xt, g.mk, st, u.shared ? Batch{} : Batch{count, (long long)p.bstride, nullptr, 0}));
     LP_HIP(hipStreamSynchronize(st));   // the caller's arrays, c0v and onesv are free again from here
-    p.has_problem = p.adat.counters_dirty = true;
+    p.has_problem = p.adat.counters_dirty = p.adat_s.counters_dirty = true;
     bind_status_pinned(c, true);
     return LPIPM_OK;
 }
@@ -918,6 +959,15 @@ static Upload tall_request(uint64_t n, uint64_t m_ub, const double* A_ub, uint64
 extern "C" int lpipm_upload_ub_tall(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub,
                                     const double* b_ub, const double* cc, double c0) {
     return upload_impl(c, tall_request(n, m_ub, A_ub, lda_ub, b_ub, &cc, &c0));
+}
+// A tall LP with equality rows.  Without any it is lpipm_upload_ub_tall's request itself.
+extern "C" int lpipm_upload_ub_eq_tall(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub,
+                                       const double* b_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq,
+                                       const double* b_eq, const double* cc, double c0) {
+    if (m_eq == 0) return upload_impl(c, tall_request(n, m_ub, A_ub, lda_ub, b_ub, &cc, &c0));
+    return upload_impl(c, Upload{.m = m_ub + m_eq, .n = n + m_ub, .n_slack = m_ub,
+                                 .parts = UploadParts{m_ub, A_ub, lda_ub, b_ub, A_eq, lda_eq, b_eq}, .c = &cc, .c0 = &c0,
+                                 .tall = true, .tall_eq = true, .me = m_eq, .keep_ok = false});
 }
 extern "C" int lpipm_upload_lockstep(lpipm_ctx* c, uint64_t count, uint64_t m, uint64_t n, const double* const* A,
                                      const double* const* b, const double* const* cc, const double* c0) {
@@ -1100,6 +1150,49 @@ static hipError_t run_tall_normal(lpipm_ctx* c, const Batch& bt) {
     if (e != hipSuccess) return e;
     return launch_slack_diag(t.nx, 0, t.Ex, c->p.M, t.nxp, c->rs.st, bt);
 }
+// Tall form with equality rows, once per iteration behind K = L.L^T: Zt = A_eq.L^-T from the `eq` rows of the (scaled) image,
+// S = Zt.Zt^T = A_eq.K^-1.A_eq^T by the A.D.A^T module (A = Zt, dinv = ones, diagonal padded with ones from me), S = L_S.L_S^T.
+// A failed pivot of S lands in the word K's does: dependent equality rows, or more of them than columns, are NumericalProblem.
+// factor == false (lpipm_k_tall_schur): S is left as built.
+static int tall_eq_schur(lpipm_ctx* c, bool factor = true) {
+    const TallArgs& t = c->p.tv;
+    hipStream_t st = c->rs.st;
+    LP_HIP(launch_trsm_lt(c->p.A + (size_t)t.ms * c->p.npa, c->p.npa, t.me, c->p.npa, c->p.M, t.nxp, *c->p.factor, c->p.Zt, t.nxp, st));
+    AdatLaunch a{};
+    a.A = c->p.Zt; a.lda = t.nxp; a.dinv = c->p.ones_k; a.M = c->p.S; a.ldm = t.mep; a.M2 = nullptr;
+    a.K = t.nxp; a.diag_pad_from = t.me; a.batch = Batch{}; a.shared_a = false;
+    LP_HIP(launch_adat(c->ap_s, c->p.adat_s, a, false, st, nullptr));
+    if (!factor) return LPIPM_OK;
+    LP_HIP(launch_potrf(c->p.S, t.mep, t.mep, *c->p.factor_s, c->p.va.potrf_info, st, Batch{}, nullptr, false, nullptr));
+    if (t.me > t.nx) {       // rank(S) <= nx < me: the zero pivot of exact arithmetic, which rounding may have left positive
+        tall_eq_singular(c->p.va, t, st);
+        LP_HIP(hipGetLastError());
+    }
+    return LPIPM_OK;
+}
+// ... and per sym_solve, in place of u_x = K^-1.g (g in G, the `eq` part of r2 behind its ms `ub` entries):
+//   w = L^-1.g;  h = r2_e - Zt.w;  v_e = S^-1.h;  w += Zt^T.v_e;  u_x = L^-T.w
+// The forward half leaves w in Y, the backward half takes it from there and leaves u_x in G; v_e stays in Ve for the epilogue.
+// (The shorter form that keeps the solve on K whole -- y0 = K^-1.g, u_x = y0 + K^-1.A_eq^T.v_e -- was emulated up to 68 x worse
+// in x and is not to be built: DESIGN.md 3.10.)
+static int tall_eq_reduced_solve(lpipm_ctx* c, int nrhs, const double* r2a, const double* r2b) {
+    const TallArgs& t = c->p.tv;
+    hipStream_t st = c->rs.st;
+    const FactorPlan& fk = *c->p.factor;
+    LP_HIP(launch_chol_solve(c->p.M, t.nxp, fk, nrhs, t.G, c->p.Y, st, Batch{}, SolveSteps{0, -1, false}));
+    prof_mark(c, T_TRSV);
+    LP_HIP(launch_gemv_n(c->p.Zt, t.nxp, t.me, t.nxp, nrhs, c->p.Y, t.nxp, r2a + t.ms, r2b ? r2b + t.ms : nullptr, t.Ve, t.mep, st, -1.0));
+    prof_mark(c, T_GEMV);
+    LP_HIP(launch_chol_solve(c->p.S, t.mep, *c->p.factor_s, nrhs, t.Ve, c->p.H, st));
+    prof_mark(c, T_TRSV);
+    LP_HIP(launch_gemv_t(c->p.Zt, t.nxp, t.mep, t.nxp, nrhs, t.Ve, t.mep, c->p.ZtPart, st, t.nxp));
+    prof_mark(c, T_GEMV);
+    tall_eq_add_w(c->p.va, t, nrhs, c->p.Y, c->p.ZtPart, st);
+    LP_HIP(hipGetLastError());
+    prof_mark(c, T_VEC);
+    LP_HIP(launch_chol_solve(c->p.M, t.nxp, fk, nrhs, t.G, c->p.Y, st, Batch{}, SolveSteps{(int)fk.sbs.size(), -1, true}));
+    return LPIPM_OK;
+}
 // Tall form: the reduced sym_solve for nrhs right-hand sides (r1a, r2a), (r1b, r2b) whose t the set-up kernel has left in
 // T, up to u_x in G and u_s in Us; the caller's epilogue kernel forms p, q, u, v.  K's factor is in M.
 static int tall_sym_solve(lpipm_ctx* c, int nrhs, const double* r1a, const double* r2a, const double* r1b, const double* r2b,
@@ -1112,10 +1205,11 @@ static int tall_sym_solve(lpipm_ctx* c, int nrhs, const double* r1a, const doubl
     tall_fold_rhs(v, t, nrhs, r1a, r1b, st);                                      // g = X^T.t - r1_x
     LP_HIP(hipGetLastError());
     prof_mark(c, T_VEC);
-    LP_HIP(launch_chol_solve(c->p.M, t.nxp, *c->p.factor, nrhs, t.G, c->p.Y, st, bt));   // u_x = K^-1 g
+    if (c->p.tall_eq) LP_TRY(tall_eq_reduced_solve(c, nrhs, r2a, r2b));          // u_x through the Schur complement, v_e
+    else LP_HIP(launch_chol_solve(c->p.M, t.nxp, *c->p.factor, nrhs, t.G, c->p.Y, st, bt));   // u_x = K^-1 g
     prof_mark(c, T_TRSV);
-    ++c->gemv_passes;                                                             // u_s = r2 - X.u_x
-    LP_HIP(launch_gemv_n(c->p.A, c->p.npa, (int)c->p.m, c->p.npa, nrhs, t.G, t.nxp, r2a, r2b, t.Us, c->p.mp, st, -1.0, bt, c->p.shared_a));
+    ++c->gemv_passes;                                                             // u_s = r2 - X.u_x   (tall_eq: over the `ub` rows)
+    LP_HIP(launch_gemv_n(c->p.A, c->p.npa, c->p.tall_eq ? t.ms : (int)c->p.m, c->p.npa, nrhs, t.G, t.nxp, r2a, r2b, t.Us, c->p.mp, st, -1.0, bt, c->p.shared_a));
     prof_mark(c, T_GEMV);
     return LPIPM_OK;
 }
@@ -1304,6 +1398,7 @@ static int enqueue_tail_tall(lpipm_ctx* c, int ip, const lpipm_opts* o) {
     hipStream_t st = c->rs.st;
     const Batch& bt = c->p.bt;
     LP_HIP(launch_potrf(c->p.M, t.nxp, t.nxp, *c->p.factor, v.potrf_info, st, bt, lookahead(c), false, nullptr));   // :129-131
+    if (c->p.tall_eq) LP_TRY(tall_eq_schur(c));                                // Zt, S and its factor
     prof_mark(c, T_POTRF);
     LP_TRY(tall_sym_solve(c, 2, v.c, v.b, v.r1, v.rP, bt));                    // :187-188
     tall_pq_uv(v, t, v.c, v.r1, st);
@@ -1787,7 +1882,7 @@ static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const SolveOut& out
 
 extern "C" int lpipm_get_resident_bytes(const lpipm_ctx* c, uint64_t* bytes_out) {
     if (!c || !bytes_out) return LPIPM_ERR_BAD_ARGUMENT;
-    *bytes_out = c->p.has_problem ? (uint64_t)(c->p.arena_bytes + c->p.a_shared_bytes + c->p.adat.list_bytes + c->p.scale_bytes) : 0;
+    *bytes_out = c->p.has_problem ? (uint64_t)(c->p.arena_bytes + c->p.a_shared_bytes + c->p.adat.list_bytes + c->p.adat_s.list_bytes + c->p.scale_bytes) : 0;
     return LPIPM_OK;
 }
 extern "C" int lpipm_solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, double* const* x_slack_out, double* fun_out,
@@ -1830,9 +1925,9 @@ static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, const BatchRequest& q, u
     const Geometry g = geometry_of(Upload{.count = 32, .m = m, .n = n, .tall = q.tall, .keep_ok = false}, q.tall ? m : n_slack, c->first_cache, c->refine);
     Problem t;
     set_geometry(t, g);
-    FactorPlan fp, fp1;
+    FactorPlan fp, fp1, fps;
     Arena measure;
-    if (layout_problem(t, fp, fp1, adat_plan_of(g, c->num_cu, c->world, c->units_env), c->refine, measure, false, nullptr) != LPIPM_OK)
+    if (layout_problem(t, fp, fp1, fps, adat_plan_of(g, c->num_cu, c->world, c->units_env), AdatPlan{}, c->refine, measure, false, nullptr) != LPIPM_OK)
         return (size_t)-1;
     return (size_t)round_up(measure.off, 4096);
 }
@@ -2319,6 +2414,26 @@ extern "C" int lpipm_k_tall_normal(lpipm_ctx* c, const double* dinv, double* K_o
     LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
 }
+extern "C" int lpipm_k_tall_schur(lpipm_ctx* c, const double* dinv, double* S_out) {
+    if (!c || !dinv || !S_out) return LPIPM_ERR_BAD_ARGUMENT;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (!c->p.tall_eq) return LPIPM_ERR_UNSUPPORTED;          // (the upload of lpipm_upload_ub_eq_tall with m_eq > 0, nothing else)
+    LP_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->rs.st;
+    const TallArgs& t = c->p.tv;
+    vec_blind_start(c->p.va, st);
+    LP_TRY(tall_entry_iterate(c, dinv));
+    tall_setup(c->p.va, t, true, 0, nullptr, nullptr, nullptr, nullptr, st);
+    LP_HIP(run_tall_normal(c, Batch{}));
+    LP_HIP(launch_potrf(c->p.M, t.nxp, t.nxp, *c->p.factor, c->p.va.potrf_info, st, Batch{}, nullptr, true, nullptr));
+    LP_TRY(tall_eq_schur(c, false));
+    const size_t me = (size_t)t.me;
+    LP_HIP(hipMemcpy2DAsync(S_out, me * sizeof(double), c->p.S, (size_t)t.mep * sizeof(double), me * sizeof(double), me,
+                            hipMemcpyDeviceToHost, st));
+    LP_HIP(hipMemsetAsync(c->p.va.potrf_info, 0, sizeof(int32_t), st));      // the solver expects a clean word
+    LP_HIP(hipStreamSynchronize(st));
+    return LPIPM_OK;
+}
 extern "C" int lpipm_k_tall_sym_solve(lpipm_ctx* c, const double* dinv, int nrhs, const double* R1, const double* R2,
                                       double* U_out, double* V_out, int32_t* info_out) {
     if (!c || !dinv || !R1 || !R2 || !U_out || !V_out || (nrhs != 1 && nrhs != 2)) return LPIPM_ERR_BAD_ARGUMENT;
@@ -2346,6 +2461,7 @@ extern "C" int lpipm_k_tall_sym_solve(lpipm_ctx* c, const double* dinv, int nrhs
         tall_setup(v, t, true, nrhs, r1, r2, r1b, r2b, st);
         LP_HIP(run_tall_normal(c, Batch{}));
         LP_HIP(launch_potrf(c->p.M, t.nxp, t.nxp, *c->p.factor, v.potrf_info, st, Batch{}, nullptr, true, nullptr));
+        if (c->p.tall_eq) LP_TRY(tall_eq_schur(c));
         LP_TRY(tall_sym_solve(c, nrhs, r1, r2, r1b, r2b, Batch{}));
         if (nrhs == 2) tall_pq_uv(v, t, r1, r1b, st);
         else           tall_uv_corr(v, t, r1, st);

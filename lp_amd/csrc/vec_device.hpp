@@ -75,7 +75,7 @@ __device__ __forceinline__ bool tbatch(VecArgs& a, TallArgs& t, TallRhs& r) {
     if (!vbatch(a, true)) return false;
     if (blockIdx.z == 0 && a.bfirst == 0) return true;
     t.Ws = batch_ptr(t.Ws, bk); t.Ex = batch_ptr(t.Ex, bk); t.T = batch_ptr(t.T, bk); t.G = batch_ptr(t.G, bk);
-    t.Us = batch_ptr(t.Us, bk);
+    t.Us = batch_ptr(t.Us, bk); t.Ve = batch_ptr(t.Ve, bk);
     r.r1a = batch_ptr(r.r1a, bk); r.r2a = batch_ptr(r.r2a, bk); r.r1b = batch_ptr(r.r1b, bk); r.r2b = batch_ptr(r.r2b, bk);
     return true;
 }

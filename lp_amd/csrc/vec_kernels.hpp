@@ -118,6 +118,10 @@ struct TallArgs {
     double* T;               // [2][mp]   t of both right-hand sides: the V of gemv_t
     double* G;               // [2][nxp]  g, then u_x: in/out of the Cholesky solve, the W of gemv_n
     double* Us;              // [2][mp]   u_s, from gemv_n (alpha = -1, addend r2)
+    // Equality rows (lpipm_upload_ub_eq_tall; me == 0 on every other tall upload, whose kernels read none of these): the image
+    // is [X; A_eq], a.m = ms + me rows of which the first ms carry a slack column; K is built from the ms `ub` rows alone.
+    int ms, me, mep;         // `ub` rows (= slack columns), `eq` rows, their count padded to 128 (order of S)
+    double* Ve;              // [2][mep]  v_e = S^-1.h of both right-hand sides, zeros beyond me
 };
 // The right-hand sides a tall launch is handed: (r1a, r2a) and (r1b, r2b), r1 n-sized, r2 m-sized, LP 0's addresses in the
 // arena (or, for the single LP of the kernel entries, any device buffer); the unused ones are null.
@@ -135,6 +139,13 @@ void tall_fold_rhs(const VecArgs& a, const TallArgs& t, int nrhs, const double* 
 // dense path leaves it --, the same dots in the same reduction slots, FLAG_NAN_PQ.
 void tall_pq_uv(const VecArgs& a, const TallArgs& t, const double* r1a, const double* r1b, hipStream_t st);
 void tall_uv_corr(const VecArgs& a, const TallArgs& t, const double* r1a, hipStream_t st);
+// (tall_setup, tall_pq_uv and tall_uv_corr launch their eq-aware siblings when t.me > 0: slack quantities over ms, row
+// quantities over ms + me with v_e from Ve.)
+// Equality rows: W[r][j] += sum over the row splits of ZtPart[s][r][j] (slabs nxp wide, in order), j < nxp: the correction
+// Zt^T.v_e of the half-solved right-hand side w = L^-1.g
+void tall_eq_add_w(const VecArgs& a, const TallArgs& t, int nrhs, double* W, const double* ZtPart, hipStream_t st);
+// me > nx: S is singular by construction (rank <= nx); records the failed pivot nx of exact arithmetic in potrf_info
+void tall_eq_singular(const VecArgs& a, const TallArgs& t, hipStream_t st);
 // k_residuals for slabs of A^T.y that are npa wide: the slack columns' A^T.y is y itself (what slab 0 holds on the dense
 // path, next to zeros: the same bits).  Followed by vec_scalar_indicators.
 void tall_residuals(const VecArgs& a, const TallArgs& t, hipStream_t st);
