@@ -532,6 +532,13 @@ int lpipm_k_tall_schur(lpipm_ctx* ctx, const double* dinv, double* S_out);
  * triangle read, lower triangle written).  info_out: 0, or k+1 for the first non-positive pivot. */
 int lpipm_k_potrf(lpipm_ctx* ctx, uint64_t m, double* M_inout, int32_t* info_out, int repeats,
                   double* ms_out);
+/* After lpipm_k_potrf at size m on this ctx: the explicit inverses of the factor's diagonal super-blocks as the solves read
+ * them.  inv_out, invT_out: mp x mp row-major (mp = m rounded up to 128), zero but for the diagonal super-blocks, which
+ * hold inv(L_ss) and inv(L_ss)^T.  super_w_out (nullable): the super-block width. */
+int lpipm_k_factor_inverses(lpipm_ctx* ctx, uint64_t m, double* inv_out, double* invT_out, int32_t* super_w_out);
+/* lpipm_k_potrf of `count` (1..64) m x m matrices (Ms_inout: count x m x m) as ONE lockstep batch: the launches of a lockstep
+ * solve's factorisation, every member in its own arena.  infos_out[count]. */
+int lpipm_k_potrf_lockstep(lpipm_ctx* ctx, uint64_t m, int count, double* Ms_inout, int32_t* infos_out);
 /* newton_equations.rs:151-169: V[r] = L^-T L^-1 R[r] for nrhs (1 or 2) right-hand sides, with
  * L = the factor of a preceding lpipm_k_potrf on this ctx (kept on device).  R, V: nrhs x m. */
 int lpipm_k_chol_solve(lpipm_ctx* ctx, uint64_t m, int nrhs, const double* R, double* V,

@@ -814,6 +814,23 @@ class Context:
         _raise_for(_capi.lib().lpipm_k_potrf(self._h, L.shape[0], _p(L), C.byref(info), repeats, C.byref(ms)))
         return L, info.value, ms.value
 
+    def k_factor_inverses(self, m):
+        """After k_potrf at size m: (inv, invT, super-block width).  inv / invT are mp x mp (mp = m rounded up to 128), zero but
+        for the diagonal super-blocks, which hold inv(L_ss) and inv(L_ss)^T as the solves read them."""
+        mp = -(-int(m) // 128) * 128
+        inv, invT = np.empty((mp, mp)), np.empty((mp, mp))
+        w = C.c_int32(0)
+        _raise_for(_capi.lib().lpipm_k_factor_inverses(self._h, m, _p(inv), _p(invT), C.byref(w)))
+        return inv, invT, w.value
+
+    def k_potrf_lockstep(self, Ms):
+        """The factors and info words of `count` m x m matrices factored as ONE lockstep batch."""
+        L = np.ascontiguousarray(_f64(Ms)).copy()
+        count, m = L.shape[0], L.shape[1]
+        infos = np.zeros(count, dtype=np.int32)
+        _raise_for(_capi.lib().lpipm_k_potrf_lockstep(self._h, m, count, _p(L), infos.ctypes.data_as(C.POINTER(C.c_int32))))
+        return L, infos
+
     def k_chol_solve(self, m, R, repeats=1):
         R = np.atleast_2d(_f64(R))
         V = np.empty_like(R)

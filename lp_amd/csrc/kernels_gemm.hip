@@ -18,7 +18,7 @@ struct GemmK {
     double* C; long long ldc;
     int KT;
     double alpha, beta;
-    int tiles_lower, ntj;
+    int tiles_lower, ntj, skip_upper;
     BatchK bk;
 };
 // LP blockIdx.z of a lockstep batch: per-LP pointers shifted
@@ -38,6 +38,10 @@ __device__ __forceinline__ void tile_coords(const GemmK& p, int t, int& ti, int&
     } else {
         ti = t / p.ntj; tj = t - ti * p.ntj;
     }
+}
+// A tile of a rectangular band whose rows all lie above its columns: nothing reads it (GemmArgs::skip_upper).
+__device__ __forceinline__ bool tile_unread(const GemmK& p, int ti, int tj, int TM, int TN) {
+    return p.skip_upper && ti * TM + TM <= tj * TN;
 }
 
 // acc(128x128 tile, 64 doubles per lane) += sum over k-tiles [kb, ke) of P-panel . (s o Q-panel)^T
@@ -127,6 +131,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_tile_kernel(const GemmK p0) {
     TILE_THREAD_IDS
     int ti, tj;
     tile_coords(p, blockIdx.x, ti, tj);
+    if (tile_unread(p, ti, tj, TM, TN)) return;
     d4 acc[MTM][MTN];
     acc_clear(acc);
     tile_mainloop<false, MTM, MTN>(ldsA, ldsB, p.P + (long long)(ti * TM + srow) * p.ldp + scol, p.ldp,
@@ -150,6 +155,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_tile_k128_kernel(const GemmK p
     TILE_THREAD_IDS
     int ti, tj;
     tile_coords(p, blockIdx.x, ti, tj);
+    if (tile_unread(p, ti, tj, TM, TN)) return;
     const double* Pp = p.P + (long long)(ti * TM + srow) * p.ldp + scol;
     const double* Qp = p.Q + (long long)(tj * TN + srow) * p.ldq + scol;
     d2 pa[KT8][MTM], pb[KT8][MTN];
@@ -195,20 +201,27 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_tile_k128_kernel(const GemmK p
 // The in-place panel solve of the factorisation (L21 = A21 . inv(L_kk)^T): a workgroup must own whole rows, so its tile is
 // 32 rows x all 128 columns; on 8 waves (2 x 4 waves of 16 x 32) a wave runs 64 MFMAs instead of the 128 of the 4-wave
 // <1, 4> tile -- the launch is one round of tiles on a chain, its length is the per-wave MFMA count plus one round trip
-// (factorisation at m = 4096: 1909 -> 1896 us).
+// (factorisation at m = 4096: 1909 -> 1896 us).  Q MUST be lower triangular with exact zeros above its diagonal (the
+// 128-block inverse): the kernel neither loads nor multiplies what lies above it.
 __global__ __launch_bounds__(512, 1) void gemm_nt_rows32_k128_kernel(const GemmK p0) {
     if (batch_done(p0.bk)) return;
     const GemmK p = batch_shift(p0);
     constexpr int TM = 32, TN = 128, KT8 = 8;
     __shared__ __attribute__((aligned(16))) double ldsA[2][TM][LDS_STRIDE];
     __shared__ __attribute__((aligned(16))) double ldsB[2][TN][LDS_STRIDE];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: the triangle's tests below go scalar
     const int wr = wave >> 2, wc = wave & 3;
     const int fr = lane & 15, fq = lane >> 4;
     const int srow = tid >> 3, scol = (tid & 7) * 2;          // staging: 64 rows per pass, 8 lanes per 128-B row segment
     int ti, tj;
     tile_coords(p, blockIdx.x, ti, tj);
+    // Q = inv(L_kk) is lower triangular: Q[c][k] = 0 for k > c, so k-tile kt meets only the rows c >= 16 kt of Q and the
+    // 16-column blocks >= kt of the product.  Only those rows are requested (72 of Q's 128 KB) and only those products run
+    // (36 of 64), each in the k order it always had.  Wave column wc takes the column blocks wc and 7 - wc: 9 products on
+    // every wave.  (qb, the 16-row block of a staging row, is the same for the 8 rows a wave stages: the tests are scalar.)
     const bool stage_a = srow < TM;
+    const int qb = wave >> 1;                                  // == srow >> 4; staging rows srow, srow + 64: blocks qb, qb + 4
     const double* Pp = p.P + (long long)(ti * TM + (stage_a ? srow : 0)) * p.ldp + scol;
     const double* Qp = p.Q + (long long)(tj * TN + srow) * p.ldq + scol;
     d2 pa[KT8], pb[KT8][2];
@@ -216,8 +229,12 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_rows32_k128_kernel(const GemmK
     for (int kt = 0; kt < KT8; ++kt) {
         pa[kt] = *(const d2*)(Pp + kt * BK);
 #pragma unroll
-        for (int r = 0; r < 2; ++r) pb[kt][r] = *(const d2*)(Qp + (long long)(64 * r) * p.ldq + kt * BK);
+        for (int r = 0; r < 2; ++r) {
+            pb[kt][r] = (d2){0.0, 0.0};
+            if (kt <= qb + 4 * r) pb[kt][r] = *(const d2*)(Qp + (long long)(64 * r) * p.ldq + kt * BK);
+        }
     }
+    const int cblk[2] = {wc, 7 - wc};
     d4 acc[1][2];
     acc_clear(acc);
 #pragma unroll
@@ -225,23 +242,30 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_rows32_k128_kernel(const GemmK
         const int buf = kt & 1;
         if (stage_a) *(d2*)&ldsA[buf][srow][lds_wcol(srow, scol)] = pa[kt];
 #pragma unroll
-        for (int r = 0; r < 2; ++r) *(d2*)&ldsB[buf][srow + 64 * r][lds_wcol(srow, scol)] = pb[kt][r];
+        for (int r = 0; r < 2; ++r)
+            if (kt <= qb + 4 * r) *(d2*)&ldsB[buf][srow + 64 * r][lds_wcol(srow, scol)] = pb[kt][r];
         __syncthreads();   // buffer `buf` was last read two k-tiles ago: that read finished before the previous barrier
+        if (kt <= cblk[1]) {                                   // wave-uniform; cblk[0] <= cblk[1]
 #pragma unroll
-        for (int round = 0; round < 2; ++round) {
-            const d2 a = *(const d2*)&ldsA[buf][wr * 16 + fr][round * 8 + lds_rq(fr, fq)];
-            d2 b[2];
+            for (int round = 0; round < 2; ++round) {
+                const d2 a = *(const d2*)&ldsA[buf][wr * 16 + fr][round * 8 + lds_rq(fr, fq)];
 #pragma unroll
-            for (int nj = 0; nj < 2; ++nj) b[nj] = *(const d2*)&ldsB[buf][wc * 32 + nj * 16 + fr][round * 8 + lds_rq(fr, fq)];
+                for (int nj = 0; nj < 2; ++nj) {
+                    if (kt > cblk[nj]) continue;
+                    const d2 b = *(const d2*)&ldsB[buf][cblk[nj] * 16 + fr][round * 8 + lds_rq(fr, fq)];
 #pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int nj = 0; nj < 2; ++nj)
-                    acc[0][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t], b[nj][t], acc[0][nj], 0, 0, 0);
+                    for (int t = 0; t < 2; ++t)
+                        acc[0][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t], b[t], acc[0][nj], 0, 0, 0);
+                }
+            }
         }
     }
-    double* cb = p.C + (long long)(ti * TM + wr * 16 + fq) * p.ldc + (tj * TN + wc * 32 + fr);
-    tile_store<1, 2>(cb, p.ldc, acc, p.alpha, p.beta, false, 0, -1, fr, fq);
+#pragma unroll
+    for (int nj = 0; nj < 2; ++nj) {
+        const d4 one[1][1] = {{acc[0][nj]}};
+        double* cb = p.C + (long long)(ti * TM + wr * 16 + fq) * p.ldc + (tj * TN + cblk[nj] * 16 + fr);
+        tile_store<1, 1>(cb, p.ldc, one, p.alpha, p.beta, false, 0, -1, fr, fq);
+    }
 }
 
 // Grouped GEMM: every workgroup takes its own descriptor (operands, k-range, alpha): the doubling
@@ -273,7 +297,7 @@ hipError_t launch_gemm_nt(const GemmArgs& a, hipStream_t st) {
     GemmK k;
     k.P = a.P; k.ldp = a.ldp; k.Q = a.Q; k.ldq = a.ldq;
     k.C = a.C; k.ldc = a.ldc; k.KT = a.K / BK; k.alpha = a.alpha; k.beta = a.beta;
-    k.tiles_lower = a.tiles_lower; k.ntj = a.ntj; k.bk = batch_k(a.batch);
+    k.tiles_lower = a.tiles_lower; k.ntj = a.ntj; k.skip_upper = a.skip_upper; k.bk = batch_k(a.batch);
     if (a.ntiles <= 0 || k.KT <= 0) return hipSuccess;
     const dim3 grid(a.ntiles, 1, a.batch.count);
     const TileShape shape = a.tile_shape;

@@ -339,12 +339,19 @@ __global__ __launch_bounds__(DT) void potrf_diag_kernel(double* __restrict__ Mbl
 
     // The image: 8 pairs per thread, all requested before anything else -- a loop of load / mask / LDS store paid one global
     // round trip per pair (6700 cycles of prologue, 9000 with the role set-up behind it) -- and stored once the roles below
-    // have been worked out in their shadow (lds_barrier does not wait for vmcnt): 5000.
+    // have been worked out in their shadow (lds_barrier does not wait for vmcnt): 5000.  Pairs wholly above the diagonal are
+    // not requested (they are zeros in the image whatever the block holds): 72 of the 128 KB go through this CU.  Branch-free:
+    // a buffer load whose offset lies past the block's last byte returns zeros without touching memory (a branch around each
+    // load cost 459 spilled registers in the elimination).
+    const __amdgpu_buffer_rsrc_t blk =
+        __builtin_amdgcn_make_buffer_rsrc((void*)Mblk, 0, (int)(((long long)(NB - 1) * ld + NB) * 8), 0x00027000);
     d2 img[NB * NB / (2 * DT)];
 #pragma unroll
     for (int i = 0; i < NB * NB / (2 * DT); ++i) {
         const int e = tid * 2 + i * 2 * DT;
-        img[i] = *(const d2*)(Mblk + (long long)(e >> 7) * ld + (e & 127));
+        const int r = e >> 7, c = e & 127;
+        const unsigned off = c <= r ? (unsigned)(((long long)r * ld + c) * 8) : 0x7ffffff0u;
+        img[i] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(blk, off, 0, 0));
     }
     if (tid < SB * SB) eye[tid >> 4][tid & 15] = ((tid >> 4) == (tid & 15)) ? 1.0 : 0.0;
     if (lane == 0) wsimd[wave] = my_simd;
@@ -659,14 +666,14 @@ static hipError_t potrf_panel_chain(double* M, int64_t ld, int mp, const FactorP
         const int ncols = J1 - j - 1;            // column blocks of the outer panel right of j
         if (ncols > 0) {
             // rows j+1..nb x columns j+1..J1-1 -= L[rows, j] . L[cols, j]^T  (rectangular grid of tiles; the few tiles
-            // above the diagonal are computed too and never read)
+            // wholly above the diagonal return at once: nothing reads them)
             GemmArgs c{};
             c.P = panel; c.ldp = ld; c.Q = panel; c.ldq = ld;
             c.C = M + (o + NB) * ld + (o + NB); c.ldc = ld; c.K = NB; c.alpha = -1.0; c.beta = 1.0;
             // 32x32 tiles: 16x as many workgroups as 128x128 ones, 32 MFMAs per wave; the launch is one round of tiles on the
-            // chain (factorisation at m = 4096: 1998 us with 64x64 tiles, 1942 with 32x64, 1903 with 32x32)
+            // chain (factorisation at m = 4096: 1998 us with 64x64 tiles on 4 waves, 1942 with 32x64, 1903 with 32x32)
             c.tile_shape = TileShape::T32x32; c.tiles_lower = 0; c.ntj = 4 * ncols; c.ntiles = (4 * rem) * (4 * ncols);
-            c.batch = bt;
+            c.skip_upper = 1; c.batch = bt;
             e = launch_gemm_nt(c, st);
             if (e != hipSuccess) return e;
         }
@@ -687,9 +694,10 @@ static hipError_t trailing_update_columns(double* M, int64_t ld, int nb, hipStre
     u.ldp = ld; u.ldq = ld; u.ldc = ld; u.K = (J1 - J0) * NB; u.alpha = -1.0; u.beta = 1.0; u.batch = bt;
     u.P = M + oC0 * ld + oJ0; u.Q = u.P; u.C = M + oC0 * ld + oC0;
     if (C1 < nb) {
-        // a band of columns: rectangular grid of 32x32 tiles, rows C0..nb x columns C0..C1 (the few tiles above the diagonal
-        // are computed too and never read); it sits on the chain, and a 32x32 tile is the shortest MFMA chain there is
+        // a band of columns: rectangular grid of tiles, rows C0..nb x columns C0..C1 (the few tiles wholly above the diagonal
+        // return at once); it sits on the chain, and 16x16 per wave is the shortest MFMA chain there is
         u.tile_shape = TileShape::T32x32; u.tiles_lower = 0; u.ntj = 4 * (C1 - C0); u.ntiles = (4 * remT) * (4 * (C1 - C0));
+        u.skip_upper = 1;
     } else {
         u.tiles_lower = 1; u.ntj = 0;
         // up to 16 trailing blocks (at most one round of 64x64 tiles) 32x32 tiles: the launch lasts as long as the busiest CU's

@@ -95,6 +95,7 @@ struct Arena {
 //   trailing update    (P = Q = L21, alpha=-1, beta=1, lower tiles)         Cholesky, :129-131
 //   TRSM as GEMM       (P = A21, Q = inv(L11), rectangular tiles)
 // output tile of a launch (rows x columns); tile indices count in these units
+// T32x128 at K = 128 is the panel solve: its Q must be lower triangular with exact zeros above the diagonal (a 128-block inverse).
 enum class TileShape { T128x128, T64x64, T32x128, T32x32 };
 struct GemmArgs {
     const double* P; int64_t ldp;
@@ -105,6 +106,7 @@ struct GemmArgs {
     int           ntiles;       // == workgroups per LP
     int           tiles_lower;  // 1: tile index -> lower triangle (row-major), 0: rectangular
     int           ntj;          // rectangular: number of tile columns
+    int           skip_upper;   // rectangular, C's origin on the diagonal: tiles whose rows all lie above their columns are not run
     TileShape     tile_shape;   // (a value-initialised GemmArgs has 128x128)
     Batch         batch;        // lockstep batch (every pointer above is per LP)
 };

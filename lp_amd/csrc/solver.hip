@@ -2563,6 +2563,69 @@ extern "C" int lpipm_k_potrf(lpipm_ctx* c, uint64_t m, double* M_inout, int32_t*
     return LPIPM_OK;
 }
 
+extern "C" int lpipm_k_factor_inverses(lpipm_ctx* c, uint64_t m, double* inv_out, double* invT_out, int32_t* super_w_out) {
+    if (!c || !inv_out || !invT_out) return LPIPM_ERR_BAD_ARGUMENT;
+    const int mp = (int)round_up(m, NB);
+    if (c->kmp != mp || !c->kchol_valid) return LPIPM_ERR_NO_PROBLEM;  // needs a preceding lpipm_k_potrf of this size
+    LP_HIP(hipSetDevice(c->device));
+    std::fill(inv_out, inv_out + (size_t)mp * mp, 0.0);
+    std::fill(invT_out, invT_out + (size_t)mp * mp, 0.0);
+    for (const SuperBlock& s : c->kplan.sbs) {
+        const size_t row = (size_t)s.size * sizeof(double), at = (size_t)s.row0 * mp + s.row0;
+        LP_HIP(hipMemcpy2DAsync(inv_out + at, (size_t)mp * sizeof(double), s.inv, row, row, s.size, hipMemcpyDeviceToHost, c->rs.st));
+        LP_HIP(hipMemcpy2DAsync(invT_out + at, (size_t)mp * sizeof(double), s.invT, row, row, s.size, hipMemcpyDeviceToHost, c->rs.st));
+    }
+    LP_HIP(hipStreamSynchronize(c->rs.st));
+    if (super_w_out) *super_w_out = c->kplan.super_w;
+    return LPIPM_OK;
+}
+
+extern "C" int lpipm_k_potrf_lockstep(lpipm_ctx* c, uint64_t m, int count, double* Ms_inout, int32_t* infos_out) {
+    if (!c || !Ms_inout || !infos_out || m == 0 || m > 16384 || count < 1 || count > 64) return LPIPM_ERR_BAD_ARGUMENT;
+    LP_HIP(hipSetDevice(c->device));
+    const int mp = (int)round_up(m, NB);
+    hipStream_t st = c->rs.st;
+    // one member's arena: the padded matrix, the info word, the inverse storage of its plan; identical layouts `stride` apart
+    FactorPlan plan;
+    auto layout = [&](Arena& ar, bool build, double** M, int32_t** info) -> hipError_t {
+        *M = ar.take<double>((size_t)mp * mp);
+        *info = ar.take<int32_t>(1);
+        return factor_plan_create(plan, *M, mp, mp, ar, build, st, super_for(mp), merge_edge_for(count));
+    };
+    double* M0 = nullptr; int32_t* info0 = nullptr;
+    Arena measure;
+    LP_HIP(layout(measure, false, &M0, &info0));
+    const size_t stride = round_up(measure.off + 256, 4096);
+    char* base = nullptr;
+    LP_HIP(hipMalloc((void**)&base, stride * (size_t)count));
+    // every failure leaves through the one exit below, which frees the plan and the buffer
+    hipError_t e = hipMemsetAsync(base, 0, stride * (size_t)count, st);
+    Arena real;
+    real.base = base;
+    if (e == hipSuccess) e = layout(real, true, &M0, &info0);
+    const std::vector<double> pad((size_t)(mp - m), 1.0);
+    for (int q = 0; q < count && e == hipSuccess; ++q) {          // padded copies: [[M, 0], [0, I]]
+        double* Mq = (double*)((char*)M0 + (size_t)q * stride);
+        e = hipMemcpy2DAsync(Mq, (size_t)mp * sizeof(double), Ms_inout + (size_t)q * m * m, m * sizeof(double), m * sizeof(double),
+                             m, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && mp > (int)m)
+            e = hipMemcpy2DAsync(Mq + m * mp + m, (size_t)(mp + 1) * sizeof(double), pad.data(), sizeof(double), sizeof(double),
+                                 mp - m, hipMemcpyHostToDevice, st);
+    }
+    if (e == hipSuccess) e = launch_potrf(M0, mp, mp, plan, info0, st, Batch{count, (long long)stride, nullptr, 0});
+    for (int q = 0; q < count && e == hipSuccess; ++q) {
+        e = hipMemcpy2DAsync(Ms_inout + (size_t)q * m * m, m * sizeof(double), (char*)M0 + (size_t)q * stride, (size_t)mp * sizeof(double),
+                             m * sizeof(double), m, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(infos_out + q, (char*)info0 + (size_t)q * stride, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    }
+    const hipError_t es = hipStreamSynchronize(st);               // also on failure: nothing may still use the buffer freed next
+    if (e == hipSuccess) e = es;
+    factor_plan_destroy(plan);
+    (void)hipFree(base);
+    LP_HIP(e);
+    return LPIPM_OK;
+}
+
 extern "C" int lpipm_k_chol_solve(lpipm_ctx* c, uint64_t m, int nrhs, const double* R, double* V, int repeats,
                                   double* ms_out) {
     if (!c || !R || !V || (nrhs != 1 && nrhs != 2)) return LPIPM_ERR_BAD_ARGUMENT;
