@@ -221,7 +221,11 @@ int lpipm_update_lockstep_vectors_device(lpipm_ctx* ctx, uint64_t count, const v
  * Cost per resident LP -- once per shared-matrix batch, which adds a vector of ones over the padded columns (8 np bytes
  * rounded up to 4096, np = n rounded up to 16) --, with mp = m rounded up to 128 and s_k the widths of the diagonal
  * super-blocks (512 each up to mp = 2048, 1024 beyond; the last one what is left of mp):  8 mp^2 + 16 sum_k s_k^2 + 4096
- * bytes (lpipm_get_resident_bytes counts them).  on = 0 gives that memory back: the kept factor is no longer used from the
+ * bytes (lpipm_get_resident_bytes counts them).  A single LP with mp >= 4096 -- not a batch, not a column split -- solves
+ * through the coupled backward sweep, and its kept factor has blocks of its own for that: the products H_k (s_k x s_k+1, one
+ * per super-block but the last) and the transposed copy of every block column k of the factor below super-block k + 1
+ * (s_k x (mp - r_k+2), r_j the first row of super-block j): 8 (sum_k s_k s_k+1 + sum_k s_k (mp - r_k+2)) bytes more, 48 MiB
+ * at mp = 4096.  on = 0 gives that memory back: the kept factor is no longer used from the
  * next solve on, and the buffers go (or, with on = 1 again, come back) with the next upload; a shared-matrix batch uploaded
  * with on = 0 has no shared set, and every member forms and factors its own iteration 1.  Default: on. */
 int lpipm_set_first_factor_cache(lpipm_ctx* ctx, int on);
@@ -543,6 +547,22 @@ int lpipm_k_potrf_lockstep(lpipm_ctx* ctx, uint64_t m, int count, double* Ms_ino
  * L = the factor of a preceding lpipm_k_potrf on this ctx (kept on device).  R, V: nrhs x m. */
 int lpipm_k_chol_solve(lpipm_ctx* ctx, uint64_t m, int nrhs, const double* R, double* V,
                        int repeats, double* ms_out);
+/* The same solve as two calls of the sweep: the forward steps [0, split) of the super-blocks, then the rest of the forward
+ * sweep and the backward one (how the solver runs the predictor's first steps beside the factorisation).  Same bits as
+ * lpipm_k_chol_solve whatever the split. */
+int lpipm_k_chol_solve_split(lpipm_ctx* ctx, uint64_t m, int nrhs, const double* R, double* V, int split);
+/* The launches of the triangular sweep for an m x m factor with super-blocks of width super_w (a multiple of 128), as numbers;
+ * needs no device.  coupled: 0 the plain sweep, 1 both sweeps coupled, 2 the backward one alone (the solver's choice for a
+ * single LP from m = 4096; the forward sweep is then the plain recurrence, listed as two launches per step), 3 the forward
+ * one alone (the plain backward sweep is not listed).
+ * out (cap int32): nsb, coupled (0 when the shape has one super-block), the number of launches; then per
+ * launch {0 forward | 1 backward, super-block of the step, pieces, workgroups} and per piece {rows, columns of the first term,
+ * columns of the second term (0: none), first vector's offset, whether it is in the scratch, second vector's offset (-1:
+ * none), in the scratch, addend's offset (-1: none), in the scratch, output's offset, in the scratch, first workgroup}; then per
+ * super-block {first row of its transposed block column (-1: none), that copy's row length, has H, has G}.  An uncoupled plan
+ * has no launches listed.  count_out: numbers written.  coupling_bytes_out (nullable): bytes of the coupling blocks. */
+int lpipm_k_sweep_plan(uint64_t m, int super_w, int coupled, int32_t* out, int cap, int32_t* count_out,
+                       uint64_t* coupling_bytes_out);
 /* The residual of the refinement step of the Cholesky solve (solver.hip chol_solve_refined): Rho[q] = R0[q] - M.V[q],
  * q < nrhs (1|2), for a symmetric m x m row-major M of which only the LOWER triangle is read.  V, R0, Rho: nrhs x m. */
 int lpipm_k_symv_residual(lpipm_ctx* ctx, uint64_t m, const double* M, int nrhs, const double* V, const double* R0, double* Rho);

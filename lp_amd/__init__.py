@@ -838,6 +838,13 @@ class Context:
         _raise_for(_capi.lib().lpipm_k_chol_solve(self._h, m, R.shape[0], _p(R), _p(V), repeats, C.byref(ms)))
         return V, ms.value
 
+    def k_chol_solve_split(self, m, R, split):
+        """k_chol_solve as two calls of the sweep: forward steps [0, split), then the rest."""
+        R = np.atleast_2d(_f64(R))
+        V = np.empty_like(R)
+        _raise_for(_capi.lib().lpipm_k_chol_solve_split(self._h, m, R.shape[0], _p(R), _p(V), split))
+        return V
+
     def k_symv_residual(self, M, V, R0):
         M = _f64(M); V = np.atleast_2d(_f64(V)); R0 = np.atleast_2d(_f64(R0))
         Rho = np.empty_like(V)

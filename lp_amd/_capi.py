@@ -109,6 +109,8 @@ SYMBOLS = {
     "lpipm_k_factor_inverses": (C.c_int, [_vp, _u64, _dp, _dp, C.POINTER(C.c_int32)]),
     "lpipm_k_potrf_lockstep": (C.c_int, [_vp, _u64, C.c_int, _dp, C.POINTER(C.c_int32)]),
     "lpipm_k_chol_solve": (C.c_int, [_vp, _u64, C.c_int, _dp, _dp, C.c_int, _dp]),
+    "lpipm_k_chol_solve_split": (C.c_int, [_vp, _u64, C.c_int, _dp, _dp, C.c_int]),
+    "lpipm_k_sweep_plan": (C.c_int, [_u64, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(_u64)]),
     "lpipm_k_symv_residual": (C.c_int, [_vp, _u64, _dp, C.c_int, _dp, _dp, _dp]),
     "lpipm_k_qr_solve": (C.c_int, [_vp, _u64, _dp, C.c_int, _dp, _dp, C.POINTER(C.c_int32), _dp]),
     "lpipm_k_gemv_n": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp]),

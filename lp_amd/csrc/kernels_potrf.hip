@@ -752,13 +752,24 @@ hipError_t launch_potrf(double* M, int64_t ld, int mp, const FactorPlan& plan, i
             if ((e2 = launch_gemm_grouped(plan.descs_dev + g.first, g.count, la->side, bt, plan.merge_edge)) != hipSuccess) return e2;
             issued[g.stage] += (size_t)g.count;
         }
-        if (!beside || !beside->at) return hipSuccess;
-        if (beside->calls == 0) { ++beside->calls; if ((e2 = beside->at(beside->self, -1, la->side)) != hipSuccess) return e2; }
+        const bool has_at = beside && beside->at;
+        if (has_at && beside->calls == 0) { ++beside->calls; if ((e2 = beside->at(beside->self, -1, la->side)) != hipSuccess) return e2; }
         for (; sb_next < (int)plan.sbs.size(); ++sb_next) {
             const SuperBlock& s = plan.sbs[sb_next];
             if (((s.row0 + s.size) / NB - 1) / OUTER > pnl) break;
+            // the coupling blocks of a coupled plan (kernels_trsv.hip), ahead of the caller's forward step that reads them
+            if ((e2 = launch_couple_step(M, ld, plan, sb_next, la->side)) != hipSuccess) return e2;
+            if (!has_at) continue;
             ++beside->calls;
             if ((e2 = beside->at(beside->self, sb_next, la->side)) != hipSuccess) return e2;
+        }
+        return hipSuccess;
+    };
+    // the coupling blocks of the super-blocks the side stream did not get, in line behind the inverses
+    auto couple_rest = [&]() -> hipError_t {
+        for (; sb_next < (int)plan.sbs.size(); ++sb_next) {
+            const hipError_t e2 = launch_couple_step(M, ld, plan, sb_next, st);
+            if (e2 != hipSuccess) return e2;
         }
         return hipSuccess;
     };
@@ -784,7 +795,10 @@ hipError_t launch_potrf(double* M, int64_t ld, int mp, const FactorPlan& plan, i
         }
     }
     if (pending >= 0 && (e = hipStreamWaitEvent(st, la->ev_rest[pending], 0)) != hipSuccess) return e;
-    if (last_side < 0) return potrf_superblock_inverses(plan, st, bt);
+    if (last_side < 0) {
+        if ((e = potrf_superblock_inverses(plan, st, bt)) != hipSuccess) return e;
+        return couple_rest();
+    }
     // one join behind the last thing the side stream got, then what is left of every stage (its tail: panels ascend inside a
     // stage), in the order of the serial schedule
     if ((e = hipEventRecord(la->ev_join, la->side)) != hipSuccess) return e;
@@ -795,7 +809,7 @@ hipError_t launch_potrf(double* M, int64_t ld, int mp, const FactorPlan& plan, i
         e = launch_gemm_grouped(plan.descs_dev + plan.stages[i].first + issued[i], left, st, bt, plan.merge_edge);
         if (e != hipSuccess) return e;
     }
-    return hipSuccess;
+    return couple_rest();
 }
 
 }  // namespace lpipm

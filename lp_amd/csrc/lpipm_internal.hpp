@@ -207,6 +207,32 @@ struct SuperBlock {
 // A stage's descriptors whose inputs become final with one outer panel of the factorisation: the 128-block inverses the
 // merge of blocks [lo, hi) reads and L[mid..hi, lo..mid] are final once chain step hi - 1 has run.
 struct MergeGroup { int first, count, stage, panel; };
+// The coupled sweep (FactorPlan::coupled): the coupling between NEIGHBOURING super-blocks is multiplied out once per
+// factorisation,
+//   H_k = Inv_k^T . L[k+1,k]^T  (s_k x s_k+1, k < nsb - 1)        G_k = Inv_k . L[k,k-1]  (s_k x s_k-1, 1 <= k <= nsb - 2),
+// and the block columns of L below the near block are kept transposed as well, so that every step of a sweep is ONE launch of
+// row-split mat-vec pieces (the last forward step keeps two: G of the last super-block would wait for the last inverse):
+//   F_k: y_k = Inv_k.t_k - G_k.y_k-1        ||  t_j -= L[j,k-1].y_k-1 for every j > k
+//   B_k: v_k = Inv_k^T.s_k - H_k.v_k+1      ||  s_i -= L[k+1,i]^T.v_k+1 for every i < k
+// The pieces behind || read only vectors finished one launch earlier.  t lives in R, y and s in Y, v goes to R.
+// Either sweep can be coupled alone (COUPLE_H / COUPLE_G): without G the forward sweep is the plain recurrence as pieces of
+// the same kernel (two launches per step), without H the backward sweep is launch_chol_solve's transposed mat-vec and fold.
+// One piece: out[i] = (add >= 0 ? add[i] : 0) + a0 * A0[i,:].w0 (+ a1 * A1[i,:].w1), i < rows; the vectors are element offsets
+// into R (.. _y == 0) or the scratch Y (== 1) of the solve, each sum in the lane order and butterfly of gemv_n.
+struct SweepPiece {
+    const double* A0; const double* A1;     // row-major; A1 == nullptr: one term
+    int lda0, lda1, np0, np1;
+    int rows, blk0;                          // blk0: the piece's first workgroup in its launch (4 rows per workgroup)
+    int w0, w1, add, out;
+    unsigned char w0_y, w1_y, add_y, out_y;
+    unsigned char tri0;                      // A0 is a triangular inverse, zeros elsewhere: 1 lower, 2 upper (0: full rows)
+    double a0, a1;
+};
+constexpr int COUPLE_H = 1, COUPLE_G = 2;   // the backward sweep through H, the forward sweep through G
+struct SweepLaunch { int first, count, blocks; };          // pieces [first, first + count), workgroups
+// What is enqueued once the inverse of super-block k is and block column k of L is final: the transposed copy of
+// L[rows >= lt_row0, column k] (lt: s_k x lt_ld, null: none) and one grouped GEMM for H_k and G_k.
+struct CoupleStep { double* lt; int lt_row0, lt_ld; int first, count; };
 struct FactorPlan {
     int mp = 0;
     int merge_edge = 128;    // output tile edge of the merge GEMMs (32 / 64: latency-bound, 128: flop-bound)
@@ -219,6 +245,15 @@ struct FactorPlan {
     std::vector<MergeGroup> groups;              // the stages cut by outer panel (stage by stage, panels ascending inside one)
     double* tpart = nullptr;                     // gemv_t slabs of the backward sweep
     double* tws = nullptr;                       // workspace of the merges (T^T of every merge)
+    // the coupled sweep (kernels_trsv.hip): storage from the arena, descriptors behind the merges' in descs_dev
+    int coupled = 0;                             // COUPLE_H | COUPLE_G: which sweeps are coupled
+    int couple_edge = 32;                        // output tile edge of the coupling GEMMs
+    std::vector<double*> H, G;                   // per super-block (null where there is none)
+    std::vector<CoupleStep> couple;              // per super-block
+    std::vector<SweepPiece> pieces;              // host copy of pieces_dev
+    SweepPiece* pieces_dev = nullptr;
+    std::vector<std::vector<SweepLaunch>> fwd;   // launches of forward step k
+    std::vector<SweepLaunch> bwd;                // launches of the backward sweep, in order
     // 128-block k of the factorisation -> where its inverse / transposed inverse go, and their ld
     double* blk_inv(int k) const;
     double* blk_invT(int k) const;
@@ -229,9 +264,16 @@ struct FactorPlan {
 // merge descriptors.  build == false: sizing pass over a measuring arena, nothing is allocated.
 // scratch_of (nullable): a plan of the same mp, widths and arena that is never in use at the same time as this one; the new
 // plan then takes only the inverse storage from the arena and works in that plan's merge workspace and gemv_t slabs.
+// coupled (COUPLE_H | COUPLE_G): lay out and describe the coupled backward / forward sweep as well (ignored with a single
+// super-block).  couple_edge: output tile edge of the coupling GEMMs (32, 64 or 128).
 hipError_t factor_plan_create(FactorPlan& plan, const double* L, int64_t ld, int mp, Arena& arena, bool build, hipStream_t st,
-                              int super_w = SUPER, int merge_edge = 128, const FactorPlan* scratch_of = nullptr);
+                              int super_w = SUPER, int merge_edge = 128, const FactorPlan* scratch_of = nullptr,
+                              int coupled = 0, int couple_edge = 32);
 void factor_plan_destroy(FactorPlan& plan);
+// Bytes of the coupling blocks and transposed block columns a coupled plan of this shape takes from its arena.
+size_t factor_coupling_bytes(int mp, int super_w, int coupled);
+// The coupling work of super-block k (CoupleStep), on `st`.
+hipError_t launch_couple_step(const double* L, int64_t ld, const FactorPlan& plan, int k, hipStream_t st);
 
 // ---------------------------------------------------------------- Cholesky (kernels_potrf.hip)
 // In-place blocked lower Cholesky of the mp x mp row-major matrix M (mp multiple of NB), followed by

@@ -71,6 +71,7 @@ struct Geometry {
     int mp = 0, np = 0, npa = 0, nxp = 0, mk = 0, B = 0, nsplit = 0, nblk = 0;
     int mep = 0;                 // tall_eq only: the `eq` rows padded to 128, the order of S (mk is then that of the `ub` rows alone)
     bool shared = false, keep = false, tall = false, tall_eq = false;
+    int coupled = 0;             // the factor plans lay out the coupled sweep (coupled_for)
     bool operator==(const Geometry&) const = default;
 };
 
@@ -485,6 +486,28 @@ static int super_for(int mp) {
     if (const char* e = lp_knob("LPIPM_SUPER")) { const int w = atoi(e); if (w >= NB && w % NB == 0 && w <= 4096) return w; }
     return mp <= 2048 ? 512 : SUPER;
 }
+// Which sweeps of the triangular solves run coupled (kernels_trsv.hip): a function of the shape alone, never of the
+// schedule.  One LP that owns its factor -- no batch, no shared matrix, no column split, not the tall form -- from m = 4096
+// (two super-blocks at least; factor_plan_create drops it for one): the backward sweep.  The coupled forward sweep is built
+// and tested but off: its blocks G_k cost the chain more beside it than the two launches they save in the corrector's solve
+// (profiles/solve_coupled.md).  LPIPM_SOLVE_COUPLED=1 turns both on at any m, =2 the backward and =3 the forward sweep
+// alone, =0 both off (measurement knob; tests/test_gpu_coupled_sweep.py).
+static int coupled_for(int mp, bool single) {
+    if (!single) return 0;
+    if (const char* e = lp_knob("LPIPM_SOLVE_COUPLED")) {    // 2 / 3: the backward / the forward sweep alone (the A/B of the parts)
+        if (e[0] == '1') return COUPLE_H | COUPLE_G;
+        if (e[0] == '0') return 0;
+        if (e[0] == '2') return COUPLE_H;
+        if (e[0] == '3') return COUPLE_G;
+    }
+    return mp >= 4096 ? COUPLE_H : 0;
+}
+static int couple_edge_for() {
+    // 32x32 tiles, like the merges: the products run beside the chain, which every side-stream workgroup slows, so the
+    // shortest launch wins (C3, it/s: parent 264.96, 128-edge 259.5, 64-edge 264.1, 32-edge 265.96; profiles/solve_coupled.md)
+    if (const char* e = lp_knob("LPIPM_COUPLE_EDGE")) { const int v = atoi(e); return (v == 128 || v == 64) ? v : 32; }
+    return 32;
+}
 static int merge_edge_for(int) {
     // 32x32 merge tiles: a stage is one round of tiles on the chain (factorisation m = 512: 194 -> 177 us, 1024: 364 -> 346,
     // 4096: 1865 -> 1854; the lockstep C4 batch is indifferent: 1745 LP/s either way)
@@ -516,6 +539,7 @@ struct Upload {
     bool owned = false;                  // tall, a batch whose members own their matrices: X_i = A[i] (lda), b[i] per member; parts holds m_ub only
     bool hint_verified = false;          // the caller has checked the hint on these very matrices (batch_impl): it is not repeated
     bool keep_ok = true;                 // false: solved once (lpipm_solve_batch) or never through the kept factor (column split)
+    bool colsplit = false;               // lpipm_upload_nsplit: this rank's columns of a column-split LP
     // lpipm_upload_device: A, b and c are in DEVICE memory, laid out as this descriptor says.  The request is otherwise the
     // equivalent host entry's; its pointers above stand for "given" / "null" only (check_upload) and are never read through.
     const lpipm_device_problem* dev = nullptr;
@@ -561,6 +585,7 @@ static Geometry geometry_of(const Upload& u, uint64_t n_slack, bool first_cache,
     if (g.nblk > RED_STRIDE) g.nblk = RED_STRIDE;
     g.shared = u.shared; g.tall = u.tall;
     g.keep = u.keep_ok && first_cache && refine <= 0 && !u.tall;   // (tall: the first factor is not kept)
+    g.coupled = coupled_for(g.mp, u.count == 1 && !u.shared && !u.tall && !u.colsplit);
     return g;
 }
 // The geometry into the structs the layouts and the launches read.
@@ -615,8 +640,9 @@ static void layout_vectors(Problem& p, Arena& ar) {
 // first plan's merge workspace and gemv_t slabs: the two are never in use at the same time.  The last block of an LP's arena,
 // or, once for a shared-matrix batch, of the shared allocation (the plan's inverses are then the batch's; workspace and
 // slabs stay the first plan's, per member).
-static size_t first_factor_bytes(int mp, int super_w) {
+static size_t first_factor_bytes(int mp, int super_w, int coupled) {
     size_t bytes = (size_t)mp * mp * sizeof(double) + 4096;
+    bytes += factor_coupling_bytes(mp, super_w, coupled);   // its own coupling blocks
     for (int r0 = 0; r0 < mp; r0 += super_w) { const size_t s = (size_t)(mp - r0 < super_w ? mp - r0 : super_w); bytes += 2 * s * s * sizeof(double); }
     return bytes;
 }
@@ -624,10 +650,10 @@ static int layout_first_factor(Problem& p, const FactorPlan& plan, FactorPlan& p
     ar.off = (size_t)round_up(ar.off, 4096);
     const size_t begin = ar.off;
     p.M1 = ar.take<double>((size_t)p.mp * p.mp);
-    LP_HIP(factor_plan_create(plan1, p.M1, p.mp, p.mp, ar, build, st, super_for(p.mp), merge_edge_for(p.B), &plan));
+    LP_HIP(factor_plan_create(plan1, p.M1, p.mp, p.mp, ar, build, st, super_for(p.mp), merge_edge_for(p.B), &plan, p.geo.coupled, couple_edge_for()));
     p.factor1 = &plan1; p.info1 = ar.take<int32_t>(1);
     ar.off = (size_t)round_up(ar.off, 4096);
-    if (ar.off - begin != first_factor_bytes(p.mp, super_for(p.mp))) return LPIPM_ERR_BAD_ARGUMENT;   // (the documented size)
+    if (ar.off - begin != first_factor_bytes(p.mp, super_for(p.mp), p.geo.coupled)) return LPIPM_ERR_BAD_ARGUMENT;   // (the documented size)
     return LPIPM_OK;
 }
 // The arena of one LP; every LP of a lockstep batch gets the same layout, `bstride` bytes after the previous LP's.
@@ -662,7 +688,7 @@ static int layout_problem(Problem& p, FactorPlan& plan, FactorPlan& plan1, Facto
     } else {
         factor_plan_destroy(plan_s);
         p.M = ar.take<double>(mp * mp);
-        LP_HIP(factor_plan_create(plan, p.M, p.mp, p.mp, ar, build, st, super_for(p.mp), merge_edge_for(p.B)));
+        LP_HIP(factor_plan_create(plan, p.M, p.mp, p.mp, ar, build, st, super_for(p.mp), merge_edge_for(p.B), nullptr, p.geo.coupled, couple_edge_for()));
     }
     p.factor = &plan;
     p.M0 = p.R0 = p.Rho = p.symv_ws = nullptr;
@@ -2140,7 +2166,7 @@ extern "C" int lpipm_upload_nsplit(lpipm_ctx* c, uint64_t m, uint64_t n_total, u
     if (!c || n_local == 0 || n_local > n_total) return LPIPM_ERR_BAD_ARGUMENT;
     if (c->scaling > 0) return LPIPM_ERR_UNSUPPORTED;      // row maxima of a column split would need the collective
     const int rc = upload_impl(c, Upload{.m = m, .n = n_local, .A = &A_local, .lda = lda, .b = &b, .c = &c_local, .c0 = &c0,
-                                         .keep_ok = false});
+                                         .keep_ok = false, .colsplit = true});
     if (rc != LPIPM_OK) return rc;
     if (c->world > 1) {
         const size_t need = (size_t)c->p.mp * ((size_t)c->p.mp + 128) / 2;
@@ -2495,12 +2521,12 @@ static int kbuf_ensure(lpipm_ctx* c, int mp) {
     LP_TRY(dalloc(c->kallocs, nullptr, &c->kinfo, 1, c->rs.st));
     LP_TRY(dalloc(c->kallocs, nullptr, &c->ktau, (size_t)mp, c->rs.st));
     Arena measure;
-    LP_HIP(factor_plan_create(c->kplan, c->kM, mp, mp, measure, false, c->rs.st, super_for(mp), merge_edge_for(1)));
+    LP_HIP(factor_plan_create(c->kplan, c->kM, mp, mp, measure, false, c->rs.st, super_for(mp), merge_edge_for(1), nullptr, coupled_for(mp, true), couple_edge_for()));
     char* kar = nullptr;
     LP_TRY(dalloc(c->kallocs, nullptr, &kar, measure.off + 256, c->rs.st));   // zeroed
     Arena real;
     real.base = kar;
-    LP_HIP(factor_plan_create(c->kplan, c->kM, mp, mp, real, true, c->rs.st, super_for(mp), merge_edge_for(1)));
+    LP_HIP(factor_plan_create(c->kplan, c->kM, mp, mp, real, true, c->rs.st, super_for(mp), merge_edge_for(1), nullptr, coupled_for(mp, true), couple_edge_for()));
     c->kmp = mp;
     return LPIPM_OK;
 }
@@ -2626,8 +2652,8 @@ extern "C" int lpipm_k_potrf_lockstep(lpipm_ctx* c, uint64_t m, int count, doubl
     return LPIPM_OK;
 }
 
-extern "C" int lpipm_k_chol_solve(lpipm_ctx* c, uint64_t m, int nrhs, const double* R, double* V, int repeats,
-                                  double* ms_out) {
+// split >= 0: the forward steps [0, split) in a call of their own, the rest of the sweep in a second one (SolveSteps)
+static int k_chol_solve_impl(lpipm_ctx* c, uint64_t m, int nrhs, const double* R, double* V, int repeats, double* ms_out, int split) {
     if (!c || !R || !V || (nrhs != 1 && nrhs != 2)) return LPIPM_ERR_BAD_ARGUMENT;
     const int mp = (int)round_up(m, NB);
     if (c->kmp != mp || !c->kchol_valid) return LPIPM_ERR_NO_PROBLEM;  // needs a preceding lpipm_k_potrf of this size
@@ -2639,7 +2665,12 @@ extern "C" int lpipm_k_chol_solve(lpipm_ctx* c, uint64_t m, int nrhs, const doub
         LP_HIP(hipMemcpy2DAsync(c->kR, (size_t)mp * sizeof(double), R, m * sizeof(double), m * sizeof(double), nrhs,
                                 hipMemcpyHostToDevice, c->rs.st));
         LP_HIP(hipEventRecord(c->rs.ev_begin, c->rs.st));
-        LP_HIP(launch_chol_solve(c->kM, mp, c->kplan, nrhs, c->kR, c->kY, c->rs.st));
+        if (split < 0) LP_HIP(launch_chol_solve(c->kM, mp, c->kplan, nrhs, c->kR, c->kY, c->rs.st));
+        else {
+            const int k = split < (int)c->kplan.sbs.size() ? split : (int)c->kplan.sbs.size();
+            LP_HIP(launch_chol_solve(c->kM, mp, c->kplan, nrhs, c->kR, c->kY, c->rs.st, Batch{}, SolveSteps{0, k, false}));
+            LP_HIP(launch_chol_solve(c->kM, mp, c->kplan, nrhs, c->kR, c->kY, c->rs.st, Batch{}, SolveSteps{k, -1, true}));
+        }
         LP_HIP(hipEventRecord(c->rs.ev_end, c->rs.st));
         LP_HIP(hipStreamSynchronize(c->rs.st));
         float ms = 0.f;
@@ -2650,6 +2681,51 @@ extern "C" int lpipm_k_chol_solve(lpipm_ctx* c, uint64_t m, int nrhs, const doub
     LP_HIP(hipMemcpy2DAsync(V, m * sizeof(double), c->kR, (size_t)mp * sizeof(double), m * sizeof(double), nrhs,
                             hipMemcpyDeviceToHost, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
+    return LPIPM_OK;
+}
+
+extern "C" int lpipm_k_chol_solve(lpipm_ctx* c, uint64_t m, int nrhs, const double* R, double* V, int repeats,
+                                  double* ms_out) {
+    return k_chol_solve_impl(c, m, nrhs, R, V, repeats, ms_out, -1);
+}
+extern "C" int lpipm_k_chol_solve_split(lpipm_ctx* c, uint64_t m, int nrhs, const double* R, double* V, int split) {
+    if (split < 0) return LPIPM_ERR_BAD_ARGUMENT;
+    return k_chol_solve_impl(c, m, nrhs, R, V, 1, nullptr, split);
+}
+
+// The sweep plan of an mp x mp factor as numbers (no device): see include/lpipm.h.
+extern "C" int lpipm_k_sweep_plan(uint64_t m, int super_w, int coupled, int32_t* out, int cap, int32_t* count_out,
+                                  uint64_t* coupling_bytes_out) {
+    if (m == 0 || m > (1u << 20) || super_w < NB || super_w % NB != 0 || !out || !count_out || cap < 3) return LPIPM_ERR_BAD_ARGUMENT;
+    const int mp = (int)round_up(m, NB);
+    FactorPlan plan;
+    Arena measure;
+    LP_HIP(factor_plan_create(plan, nullptr, mp, mp, measure, false, nullptr, super_w, 32, nullptr,
+                              coupled == 1 ? COUPLE_H | COUPLE_G : coupled == 2 ? COUPLE_H : coupled == 3 ? COUPLE_G : 0));
+    std::vector<int32_t> v;
+    const int nsb = (int)plan.sbs.size();
+    v.push_back(nsb); v.push_back(plan.coupled ? 1 : 0); v.push_back(0);
+    auto put = [&](int kind, int k, const SweepLaunch& l) {
+        ++v[2];
+        v.insert(v.end(), {kind, k, l.count, l.blocks});
+        for (int i = l.first; i < l.first + l.count; ++i) {
+            const SweepPiece& q = plan.pieces[(size_t)i];
+            v.insert(v.end(), {q.rows, q.np0, q.A1 ? q.np1 : 0, q.w0, q.w0_y, q.A1 ? q.w1 : -1, q.w1_y, q.add, q.add_y, q.out, q.out_y, q.blk0});
+        }
+    };
+    if (plan.coupled) {
+        for (int k = 0; k < nsb && !plan.fwd.empty(); ++k) for (const SweepLaunch& l : plan.fwd[(size_t)k]) put(0, k, l);
+        for (int i = 0; i < (int)plan.bwd.size(); ++i) put(1, nsb - 1 - i, plan.bwd[(size_t)i]);
+        for (int k = 0; k < nsb; ++k) {
+            const CoupleStep& cs = plan.couple[(size_t)k];
+            v.insert(v.end(), {cs.lt ? cs.lt_row0 : -1, cs.lt ? cs.lt_ld : 0, plan.H[(size_t)k] ? 1 : 0, plan.G[(size_t)k] ? 1 : 0});
+        }
+    }
+    if (coupling_bytes_out) *coupling_bytes_out = factor_coupling_bytes(mp, super_w, plan.coupled);
+    factor_plan_destroy(plan);
+    if ((int)v.size() > cap) return LPIPM_ERR_BAD_ARGUMENT;
+    std::copy(v.begin(), v.end(), out);
+    *count_out = (int32_t)v.size();
     return LPIPM_OK;
 }
 
