@@ -168,6 +168,12 @@ extern "C" {
         ctx: *mut lpipm_ctx, count: u64, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, b: *const *const f64,
         c: *const *const f64, c0: *const f64,
     ) -> c_int;
+    // The same batch with `eq` rows in the one image (b[i] = [b_ub_i; b_eq_i]): every member a tall LP with equality rows, its
+    // own K and its own Schur complement; each member bit-identical to lpipm_upload_ub_eq_tall + lpipm_solve of that member alone.
+    pub fn lpipm_upload_lockstep_shared_ub_eq_tall(
+        ctx: *mut lpipm_ctx, count: u64, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, m_eq: u64, a_eq: *const f64,
+        lda_eq: u64, b: *const *const f64, c: *const *const f64, c0: *const f64,
+    ) -> c_int;
     // The same with one matrix per member (a_ub[i]: m_ub x n, lda_ub): every member keeps its own X, transpose and K.
     pub fn lpipm_upload_lockstep_ub_tall(
         ctx: *mut lpipm_ctx, count: u64, n: u64, m_ub: u64, a_ub: *const *const f64, lda_ub: u64, b: *const *const f64,

@@ -174,8 +174,9 @@ int lpipm_upload_ub_tall(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const double
  * Refusals.  m_ub == 0 and m_eq == 0: LPIPM_UNCONSTRAINED.  Null pointers or lda < n: LPIPM_ERR_BAD_ARGUMENT.  m_ub == 0 < m_eq
  * (not a tall LP: lpipm_upload_ub_eq is its entry), a column-split context or one with the refined solves, solver_type 1 or
  * 2, lpipm_update_vectors[_device] and lpipm_k_adat: LPIPM_ERR_UNSUPPORTED, as on every tall upload.
- * Out of scope: batches of such LPs; lpipm_upload_device (its form value 3 stays LPIPM_ERR_BAD_ARGUMENT); a kept K_1; the QR
- * arms.  No first factor is kept. */
+ * Many such LPs over one [A_ub; A_eq] are a lockstep batch: lpipm_upload_lockstep_shared_ub_eq_tall, below.
+ * Out of scope: such LPs with their own matrices as a batch; lpipm_upload_device (its form value 3 stays
+ * LPIPM_ERR_BAD_ARGUMENT); a kept K_1; the QR arms.  No first factor is kept. */
 int lpipm_upload_ub_eq_tall(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub,
                             const double* b_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq, const double* b_eq,
                             const double* c, double c0);
@@ -191,7 +192,8 @@ int lpipm_update_vectors(lpipm_ctx* ctx, const double* b, const double* c);
 /* New b, c and (optionally) c0 for EVERY member of the resident lockstep batch, whichever lpipm_upload_lockstep* made it, in
  * that upload's own form: b[i][m] and c[i][n] (c with its slack entries); after lpipm_upload_lockstep_shared_ub_eq
  * b[i] = [b_ub_i; b_eq_i] and c[i] = the n structural costs (the slack costs stay 0), after
- * lpipm_upload_lockstep_shared_ub_tall and lpipm_upload_lockstep_ub_tall b[i] of m_ub doubles and c[i] = the n structural costs.  b or c may be NULL as a whole: those
+ * lpipm_upload_lockstep_shared_ub_tall and lpipm_upload_lockstep_ub_tall b[i] of m_ub doubles and c[i] = the n structural costs,
+ * after lpipm_upload_lockstep_shared_ub_eq_tall b[i] = [b_ub_i; b_eq_i] and c[i] = the n structural costs.  b or c may be NULL as a whole: those
  * vectors stay (a right-hand-side sweep sends no costs); c0 == NULL: the constants stay.  A, the layout, the half-batch views
  * and the kept first factor(s) are not touched, and the padding beyond m and n stays zero: the next lpipm_solve_lockstep[_device]
  * is bit-identical to a fresh upload of the same members followed by a solve.  The host arrays are staged in one pinned block
@@ -366,11 +368,40 @@ int lpipm_upload_lockstep_shared_ub_eq(lpipm_ctx* ctx, uint64_t count, uint64_t 
  * LPIPM_ERR_UNSUPPORTED (as every lockstep batch); lpipm_k_tall_normal, lpipm_k_tall_sym_solve, lpipm_k_iteration and
  * lpipm_k_adat on such a batch LPIPM_ERR_UNSUPPORTED.
  * Tall LPs of one shape that each have their own matrix: lpipm_upload_lockstep_ub_tall, below.
- * Not built: `eq` rows in a batch (one such LP: lpipm_upload_ub_eq_tall), a kept K_1 = X^T.X + I, fused small-LP vector kernels for the tall form, tall members inside
+ * The same batch with `eq` rows in the one image: lpipm_upload_lockstep_shared_ub_eq_tall, below.
+ * Not built: a kept K_1 = X^T.X + I, fused small-LP vector kernels for the tall form, tall members inside
  * lpipm_solve_batch / lpipm_solve_batch_slack (lpipm_solve_batch_ub_tall is their entry). */
 int lpipm_upload_lockstep_shared_ub_tall(lpipm_ctx* ctx, uint64_t count, uint64_t n, uint64_t m_ub, const double* A_ub,
                                          uint64_t lda_ub, const double* const* b, const double* const* c,
                                          const double* c0 /* nullable */);
+/* A lockstep batch of tall LPs with equality rows (lpipm_upload_ub_eq_tall) over ONE pair (A_ub, A_eq): the batches of
+ * lpipm_upload_lockstep_shared_ub_tall whose members also carry a sum-to-one, budget, interpolation or conservation row.  The
+ * arguments are those of lpipm_upload_lockstep_shared_ub_eq: member i is (A_ub, A_eq, b[i] = [b_ub_i; b_eq_i] (m_ub + m_eq
+ * doubles), c[i] (the n structural costs), c0[i]).  Resident once: the image [A_ub; A_eq] and the transpose of its `ub` rows.
+ * In each member's arena, beside its K, tall vectors and slabs: Zt = A_eq.L^-T, S with its factor's inverses and the words
+ * and slabs of the launch that builds it, the work vectors of the Schur solve and the n ones that launch scales by.  Nothing
+ * of a member is a copy of A_ub or A_eq, nothing of it grows as m_ub^2.  Once per iteration one launch forms every running
+ * member's Zt from the one block of `eq` rows and the member's own factor of K; S, its factorisation and the solves follow
+ * as lockstep launches.  A failed pivot of K or of S (dependent equality rows, m_eq > n) is that member's
+ * LPIPM_NUMERICAL_PROBLEM; the others go on.
+ * Solve with lpipm_solve_lockstep / lpipm_solve_lockstep_device: x has n + m_ub entries, slack values last.  Every member is
+ * bit-identical to lpipm_upload_ub_eq_tall + lpipm_solve of that member alone -- x, fun, status and iteration count --
+ * whatever the count, whichever members have finished, as one view or two half-batch views.
+ * lpipm_update_lockstep_vectors[_device] replace b[i] (m_ub + m_eq doubles), c[i] (the n structural costs) and c0 in place,
+ * the next solve bit-identical to a fresh upload of the same members.  lpipm_set_scaling works as for any shared-matrix
+ * batch: one set of exponents (lpipm_get_scaling with member 0), the image with its `eq` rows equilibrated once, before the
+ * transpose is written, Zt formed from the scaled image, updates scaled with the kept exponents, x in the caller's units.
+ * No first factor is kept.
+ * m_eq == 0: exactly lpipm_upload_lockstep_shared_ub_tall on the same arguments -- the same request, the same bits.
+ * Refusals.  m_ub == 0 and m_eq == 0: LPIPM_UNCONSTRAINED.  m_ub == 0 < m_eq: LPIPM_ERR_UNSUPPORTED.  Null pointers, count == 0
+ * (or > 4096), lda_ub < n or lda_eq < n: LPIPM_ERR_BAD_ARGUMENT.  A column-split context or one with the refined solves,
+ * solver_type 1 or 2 at solve time, and lpipm_k_tall_normal, lpipm_k_tall_schur, lpipm_k_tall_sym_solve, lpipm_k_iteration and
+ * lpipm_k_adat on such a batch: LPIPM_ERR_UNSUPPORTED.  A refused call leaves the resident problem as it was.
+ * Out of scope: members with their own A_ub and A_eq, tall members with `eq` rows inside lpipm_solve_batch*, a kept first
+ * factor, lpipm_upload_device (its form value 3 stays LPIPM_ERR_BAD_ARGUMENT). */
+int lpipm_upload_lockstep_shared_ub_eq_tall(lpipm_ctx* ctx, uint64_t count, uint64_t n, uint64_t m_ub, const double* A_ub,
+                                            uint64_t lda_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq,
+                                            const double* const* b, const double* const* c, const double* c0 /* nullable */);
 /* A lockstep batch of `count` independent tall inequality-form LPs of one shape, each with its OWN matrix: one L-infinity fit or
  * cover model per customer or time window, per-scenario cut sets.  Member i is (A_ub[i] (m_ub x n row-major, lda_ub), b[i] (m_ub
  * doubles), c[i] (the n structural costs), c0[i]): the arguments of lpipm_upload_lockstep_shared_ub_tall with one matrix per
@@ -530,7 +561,7 @@ int lpipm_k_tall_sym_solve(lpipm_ctx* ctx, const double* dinv, int nrhs, const d
                            double* V_out, int32_t* info_out);
 /* After lpipm_upload_ub_eq_tall with m_eq > 0: builds K at dinv[n], factors it and returns the Schur complement
  * S_out (m_eq x m_eq row-major, LOWER triangle valid) = A_eq.K^-1.A_eq^T, as built (before its own factorisation).  Any other
- * upload: LPIPM_ERR_UNSUPPORTED.  The iterate of the context is overwritten. */
+ * upload, a batch of such LPs included: LPIPM_ERR_UNSUPPORTED.  The iterate of the context is overwritten. */
 int lpipm_k_tall_schur(lpipm_ctx* ctx, const double* dinv, double* S_out);
 /* newton_equations.rs:129-131: in-place lower Cholesky of the m x m row-major matrix M (lower
  * triangle read, lower triangle written).  info_out: 0, or k+1 for the first non-positive pivot. */
@@ -543,6 +574,17 @@ int lpipm_k_factor_inverses(lpipm_ctx* ctx, uint64_t m, double* inv_out, double*
 /* lpipm_k_potrf of `count` (1..64) m x m matrices (Ms_inout: count x m x m) as ONE lockstep batch: the launches of a lockstep
  * solve's factorisation, every member in its own arena.  infos_out[count]. */
 int lpipm_k_potrf_lockstep(lpipm_ctx* ctx, uint64_t m, int count, double* Ms_inout, int32_t* infos_out);
+/* Z = B . L^-T with a member dimension, as a lockstep batch of tall LPs with equality rows forms its members' Zt: factors the
+ * `count` (1..64) n x n SPD matrices Ms (count x n x n) as lpipm_k_potrf_lockstep does, then runs ONE substitution launch over
+ * the members.  B: one rows x cols block (row-major, ld ldb, cols <= n) for all members when shared_b, else `count` of them
+ * rows * ldb doubles apart.  Z_inout: count blocks of round_up(rows, 16) x round_up(n, 128) doubles (row r of block q solves
+ * L_q.z = B_q[r, :]^T; columns beyond n and rows beyond `rows` come back zero).  What a block holds on entry is what that
+ * member's Z holds before the launch.  done_mask (nullable): one int per member, non-zero marks it finished -- its block comes
+ * back as it went in.  Member q's Z is bit-identical to a call with count == 1 on Ms[q], whatever the count and the mask.
+ * infos_out[count]: the factorisations' pivot words. */
+int lpipm_k_trsm_lt_lockstep(lpipm_ctx* ctx, uint64_t n, int count, int rows, int cols, int shared_b, const double* Ms,
+                             const double* B, uint64_t ldb, double* Z_inout, int32_t* infos_out,
+                             const int32_t* done_mask /* nullable */);
 /* newton_equations.rs:151-169: V[r] = L^-T L^-1 R[r] for nrhs (1 or 2) right-hand sides, with
  * L = the factor of a preceding lpipm_k_potrf on this ctx (kept on device).  R, V: nrhs x m. */
 int lpipm_k_chol_solve(lpipm_ctx* ctx, uint64_t m, int nrhs, const double* R, double* V,

@@ -656,6 +656,25 @@ class Context:
         head = (n, m_ub, _p(A_ub) if m_ub else None, n)
         return self._upload_members("lpipm_upload_lockstep_shared_ub_tall", head, bs, cs, c0s, m_ub, n + m_ub, n, None)
 
+    def upload_lockstep_shared_ub_eq_tall(self, A_ub, A_eq, bs, cs, c0s=None):
+        """`len(bs)` tall LPs with equality rows over ONE pair of blocks (lpipm_upload_lockstep_shared_ub_eq_tall): member i is
+        min cs[i]'x st A_ub x <= bs[i][:m_ub], A_eq x == bs[i][m_ub:], x >= 0, with many more `ub` rows than columns and a few
+        `eq` rows.  The image [A_ub; A_eq] and the transpose of A_ub are resident once; every member factors its own n x n
+        reduced system and its own m_eq x m_eq Schur complement.  A_eq None (or without rows): upload_lockstep_shared_ub_tall
+        itself.  solve_lockstep returns x with n + m_ub entries, slack values last -- every member bit-identical to
+        Context.upload_tall_eq(Problem...ub().eq().build()) + solve_raw."""
+        bs = [_f64(b) for b in bs]; cs = [_f64(c) for c in cs]
+        if len(bs) < 1 or len(cs) != len(bs) or (c0s is not None and len(c0s) != len(bs)) or cs[0].ndim != 1:
+            raise IncompatibleInputDimensions()
+        n = cs[0].shape[0]
+        A_ub = _f64(A_ub) if A_ub is not None else np.zeros((0, n))
+        A_eq = _f64(A_eq) if A_eq is not None else np.zeros((0, n))
+        if A_ub.ndim != 2 or A_eq.ndim != 2 or A_ub.shape[1] != n or A_eq.shape[1] != n:
+            raise IncompatibleInputDimensions()
+        m_ub, m_eq = A_ub.shape[0], A_eq.shape[0]
+        head = (n, m_ub, _p(A_ub) if m_ub else None, n, m_eq, _p(A_eq) if m_eq else None, n)
+        return self._upload_members("lpipm_upload_lockstep_shared_ub_eq_tall", head, bs, cs, c0s, m_ub + m_eq, n + m_ub, n, None)
+
     def upload_lockstep_ub_tall(self, A_ubs, bs, cs, c0s=None):
         """`len(A_ubs)` independent tall inequality-form LPs of one shape, each with its own matrix
         (lpipm_upload_lockstep_ub_tall): member i is min cs[i]'x st A_ubs[i] x <= bs[i], x >= 0.  Every member keeps its own
@@ -830,6 +849,31 @@ class Context:
         infos = np.zeros(count, dtype=np.int32)
         _raise_for(_capi.lib().lpipm_k_potrf_lockstep(self._h, m, count, _p(L), infos.ctypes.data_as(C.POINTER(C.c_int32))))
         return L, infos
+
+    def k_trsm_lt_lockstep(self, Ms, B, done_mask=None, fill=0.0):
+        """Z = B L^-T for every member of a lockstep batch (lpipm_k_trsm_lt_lockstep): Ms (count, n, n) SPD, factored as one
+        batch; B (rows, cols) is one block for all members, B (count, rows, cols) one per member.  -> (Z, infos) with Z
+        (count, round_up(rows, 16), round_up(n, 128)).  Every Z starts as `fill`; a member whose done_mask entry is non-zero is
+        skipped and keeps it."""
+        Ms = np.ascontiguousarray(_f64(Ms)); B = np.ascontiguousarray(_f64(B))
+        if Ms.ndim != 3 or Ms.shape[1] != Ms.shape[2] or B.ndim not in (2, 3):
+            raise IncompatibleInputDimensions()
+        count, n = Ms.shape[0], Ms.shape[1]
+        shared = B.ndim == 2
+        rows, cols = B.shape[-2:]
+        if (not shared and B.shape[0] != count) or cols > n or rows < 1 or cols < 1:
+            raise IncompatibleInputDimensions()
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        mask = None
+        if done_mask is not None:
+            mask = np.ascontiguousarray(done_mask, dtype=np.int32)
+            if mask.shape != (count,):
+                raise IncompatibleInputDimensions()
+        Z = np.full((count, -(-rows // 16) * 16, -(-n // 128) * 128), float(fill))
+        infos = np.zeros(count, dtype=np.int32)
+        _raise_for(_capi.lib().lpipm_k_trsm_lt_lockstep(self._h, n, count, rows, cols, int(shared), _p(Ms), _p(B), cols, _p(Z), ip(infos),
+                                                        ip(mask) if mask is not None else None))
+        return Z, infos
 
     def k_chol_solve(self, m, R, repeats=1):
         R = np.atleast_2d(_f64(R))

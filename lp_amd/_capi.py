@@ -87,6 +87,7 @@ SYMBOLS = {
     "lpipm_upload_lockstep_shared_slack": (C.c_int, [_vp, _u64, _u64, _u64, _dp, _u64, _dpp, _dpp, _dp, _u64]),
     "lpipm_upload_lockstep_shared_ub_eq": (C.c_int, [_vp, _u64, _u64, _u64, _dp, _u64, _u64, _dp, _u64, _dpp, _dpp, _dp]),
     "lpipm_upload_lockstep_shared_ub_tall": (C.c_int, [_vp, _u64, _u64, _u64, _dp, _u64, _dpp, _dpp, _dp]),
+    "lpipm_upload_lockstep_shared_ub_eq_tall": (C.c_int, [_vp, _u64, _u64, _u64, _dp, _u64, _u64, _dp, _u64, _dpp, _dpp, _dp]),
     "lpipm_upload_lockstep_ub_tall": (C.c_int, [_vp, _u64, _u64, _u64, _dpp, _u64, _dpp, _dpp, _dp]),
     "lpipm_solve_batch_ub_tall": (C.c_int, [_vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _dpp, _dpp, _dpp, _dp,
                                             C.POINTER(Opts), _dpp, _vp, _u64, _dp, C.POINTER(_u64), C.POINTER(C.c_int32)]),
@@ -108,6 +109,8 @@ SYMBOLS = {
     "lpipm_k_potrf": (C.c_int, [_vp, _u64, _dp, C.POINTER(C.c_int32), C.c_int, _dp]),
     "lpipm_k_factor_inverses": (C.c_int, [_vp, _u64, _dp, _dp, C.POINTER(C.c_int32)]),
     "lpipm_k_potrf_lockstep": (C.c_int, [_vp, _u64, C.c_int, _dp, C.POINTER(C.c_int32)]),
+    "lpipm_k_trsm_lt_lockstep": (C.c_int, [_vp, _u64, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _u64, _dp, C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32)]),
     "lpipm_k_chol_solve": (C.c_int, [_vp, _u64, C.c_int, _dp, _dp, C.c_int, _dp]),
     "lpipm_k_chol_solve_split": (C.c_int, [_vp, _u64, C.c_int, _dp, _dp, C.c_int]),
     "lpipm_k_sweep_plan": (C.c_int, [_u64, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(_u64)]),

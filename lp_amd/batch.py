@@ -125,6 +125,15 @@ def solve_shared_ub_tall(A_ub, bs, cs, c0s=None, opts=None, ctx=None, max_group=
     return _groups(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_tall(A_ub, b, c, c0), bs, cs, c0s, opts, ctx, max_group)
 
 
+def solve_shared_ub_eq_tall(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_group=32):
+    """Tall LPs with equality rows over ONE pair of blocks (solve_shared_ub_tall's users with a sum-to-one, budget or
+    interpolation row): member i = (bs[i] = [b_ub_i; b_eq_i], cs[i] = the n structural costs, c0s[i]).  Lockstep groups of at
+    most `max_group` on one context through lpipm_upload_lockstep_shared_ub_eq_tall: the image and the transpose of A_ub resident
+    once, every member factoring its own n x n reduced system and its own m_eq x m_eq Schur complement.  Returns what
+    solve_shared_ub_eq returns; x_slack has n + m_ub entries."""
+    return _groups(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_eq_tall(A_ub, A_eq, b, c, c0), bs, cs, c0s, opts, ctx, max_group)
+
+
 def sweep_chunks(count: int, max_group: int):
     """The equal chunks of a sweep: k = ceil(count / max_group) chunks of g = ceil(count / k) members, as lists of member
     indices.  The last chunk is filled up to g with repeats of its own last member (at most k - 1 of them in all), so
@@ -232,3 +241,10 @@ def sweep_shared_ub_tall(A_ub, bs, cs, c0s=None, opts=None, ctx=None, max_group=
     of m_ub entries, cs[i] = the n structural costs); A_ub is uploaded and transposed once.  Returns what solve_shared_ub_tall
     returns, bit for bit."""
     return _sweep(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_tall(A_ub, b, c, c0), bs, cs, c0s, opts, ctx, max_group)
+
+
+def sweep_shared_ub_eq_tall(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_group=32):
+    """solve_shared_ub_eq_tall as a sweep: one upload_lockstep_shared_ub_eq_tall, then update_lockstep_vectors per later chunk
+    (bs[i] = [b_ub_i; b_eq_i], cs[i] = the n structural costs); the image is uploaded and A_ub transposed once.  Returns what
+    solve_shared_ub_eq_tall returns, bit for bit."""
+    return _sweep(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_eq_tall(A_ub, A_eq, b, c, c0), bs, cs, c0s, opts, ctx, max_group)

@@ -319,8 +319,12 @@ hipError_t launch_chol_solve(const double* L, int64_t ld, const FactorPlan& plan
 // Z = B . L^-T for the factor L (ld ldl) of `plan`, order n = plan.mp: row r of Z solves L.z = B[r,:]^T.  B: rows x cols
 // (cols <= n, zeros assumed beyond), row-major.  Z: round_up(rows, 16) x n, ld ldz (a multiple of 4), written whole -- rows
 // past `rows` as zeros.  One launch, one workgroup per 16 rows, fixed-order sums.
+// bt: the members of a lockstep batch, each with its own L, inverses (the plan's are member 0's) and Z, and its own B unless
+// shared_b says that B is one block for all of them (it is then not offset).  Finished members' Z stays untouched; member z's
+// Z has the bits of a single launch on that member's L.  Without a member dimension (count 1, first 0, no done words) the
+// launch is the single kernel's.
 hipError_t launch_trsm_lt(const double* B, int64_t ldb, int rows, int cols, const double* L, int64_t ldl, const FactorPlan& plan,
-                          double* Z, int64_t ldz, hipStream_t st);
+                          double* Z, int64_t ldz, hipStream_t st, const Batch& bt = Batch{}, bool shared_b = false);
 
 // ---------------------------------------------------------------- QR arms (kernels_qr.hip)
 // EquationSolverType::{Inverse, LeastSquares}: Householder QR of the full mp x mp matrix whose LOWER

@@ -125,6 +125,9 @@ struct Problem {
     // Zt = A_eq.L^-T (mep x nxp, padding rows zero) and S = Zt.Zt^T (mep x mep, diagonal padded with ones from me) with its
     // own factor plan and A.D.A^T plan (`ones_k`: its dinv).  H, tv.Ve: the work vectors of the solve on S; ZtPart: the
     // row-split slabs of Zt^T.v_e.
+    // A batch of such LPs over ONE image (lpipm_upload_lockstep_shared_ub_eq_tall: tall_eq && shared_a): [X; A_eq] and Xt are
+    // resident once, in a_shared; every member's arena holds, behind its K, its own Zt, S with its plan's inverses, H, Ve, ZtPart,
+    // the words and slabs of the launch that builds S, and its own ones_k (launch_adat moves dinv with the member).
     bool tall_eq = false;
     int me = 0;
     double *Zt = nullptr, *S = nullptr, *H = nullptr, *ZtPart = nullptr, *ones_k = nullptr;
@@ -534,7 +537,7 @@ struct Upload {
     const double* c0 = nullptr;          // nullable: all zero
     bool shared = false;                 // one matrix for all `count` LPs
     bool tall = false;                   // parts with `ub` rows only: the tall inequality form, of the LP or of every member over one X
-    bool tall_eq = false;                // tall, one LP, with `eq` rows as well: the Schur complement on K's factor
+    bool tall_eq = false;                // tall with `eq` rows as well (one LP, or a batch over one image): the Schur complement on K's factor
     uint64_t me = 0;                     //   its `eq` rows (m - parts.m_ub > 0)
     bool owned = false;                  // tall, a batch whose members own their matrices: X_i = A[i] (lda), b[i] per member; parts holds m_ub only
     bool hint_verified = false;          // the caller has checked the hint on these very matrices (batch_impl): it is not repeated
@@ -608,6 +611,13 @@ static AdatPlan adat_plan_of(const Geometry& g, int num_cu, int world, int units
     const AdatPlan single = plan_adat(g.nxp, g.mk, 1, num_cu, 1, units_env);
     return single.units ? plan_adat(g.nxp, g.mk, g.B, num_cu, 1, units_env) : single;     // (B == 1: `single` either way)
 }
+// tall_eq: the plan of the launch that builds S = Zt.Zt^T -- mep rows, a contraction over nxp -- by the same rule: every member's
+// S must have the bits the single upload's has.
+static AdatPlan adat_s_plan_of(const Geometry& g, int num_cu, int units_env) {
+    if (!g.tall_eq) return AdatPlan{};
+    const AdatPlan single = plan_adat(g.mep, g.nxp, 1, num_cu, 1, units_env);
+    return single.units ? plan_adat(g.mep, g.nxp, g.B, num_cu, 1, units_env) : single;
+}
 
 // Device state is laid out by functions that take p's geometry and an Arena: one pass over a measuring arena sizes an
 // allocation, a second pass over the real one places it.  Out: p's device pointers and the factor plans they refer to.
@@ -662,7 +672,7 @@ static int layout_first_factor(Problem& p, const FactorPlan& plan, FactorPlan& p
 // A member of a shared batch (p.shared_a) has the same arena without A (tall: X and Xt): layout_shared.  A member of a tall
 // batch that owns its matrix has the single tall LP's arena.
 // tall_eq: behind K and its plan, Zt, S with its plan (plan_s), the work vectors of the Schur solve, the slabs of Zt^T.v_e, the
-// vector of ones and the words and slabs of the launch that builds S (ap_s).
+// vector of ones and the words and slabs of the launch that builds S (ap_s) -- in every member's arena of a batch as well.
 static int layout_problem(Problem& p, FactorPlan& plan, FactorPlan& plan1, FactorPlan& plan_s, const AdatPlan& ap,
                           const AdatPlan& ap_s, int refine, Arena& ar, bool build, hipStream_t st) {
     TallArgs& t = p.tv;
@@ -728,7 +738,7 @@ static int relayout(lpipm_ctx* c, const Geometry& g) {
     p.has_problem = false;
     set_geometry(p, g);
     c->ap = adat_plan_of(g, c->num_cu, c->world, c->units_env);
-    c->ap_s = g.tall_eq ? plan_adat(g.mep, g.nxp, 1, c->num_cu, 1, c->units_env) : AdatPlan{};     // S = Zt.Zt^T: mep rows, contraction nxp
+    c->ap_s = adat_s_plan_of(g, c->num_cu, c->units_env);
     Arena measure;
     LP_TRY(layout_problem(p, c->plan, c->plan1, c->plan_s, c->ap, c->ap_s, c->refine, measure, false, st));
     p.bstride = round_up(measure.off, 4096);
@@ -747,7 +757,7 @@ static int relayout(lpipm_ctx* c, const Geometry& g) {
         LP_TRY(layout_shared(p, c->plan, c->plan1, sh, true, st));
     }
     LP_HIP(adat_lists_create(p.adat, c->ap, g.tall ? g.nxp : g.mp, g.B, st));    // (drains st)
-    if (g.tall_eq) LP_HIP(adat_lists_create(p.adat_s, c->ap_s, g.mep, 1, st));
+    if (g.tall_eq) LP_HIP(adat_lists_create(p.adat_s, c->ap_s, g.mep, g.B, st));
     LP_TRY(stream_res_grow_status(c->rs, (size_t)g.B));
     return LPIPM_OK;
 }
@@ -944,7 +954,8 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
     const std::vector<double> onesv(p.shared_factor ? (size_t)g.np : 0, 1.0);     // likewise
     if (p.shared_factor) LP_HIP(hipMemcpyAsync(p.ones, onesv.data(), onesv.size() * sizeof(double), hipMemcpyHostToDevice, st));
     const std::vector<double> ones_k(u.tall_eq ? (size_t)g.nxp : 0, 1.0);         // likewise: the dinv of S = Zt.Zt^T
-    if (u.tall_eq) LP_HIP(hipMemcpyAsync(p.ones_k, ones_k.data(), ones_k.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    for (int i = 0; i < count && u.tall_eq; ++i)                                   // (every member's own: launch_adat moves dinv with the member)
+        LP_HIP(hipMemcpyAsync((char*)p.ones_k + (size_t)i * p.bstride, ones_k.data(), ones_k.size() * sizeof(double), hipMemcpyHostToDevice, st));
     LP_TRY(u.dev ? copy_in_device(c, u, c0v.data()) : copy_in(c, u, c0v.data()));
     if (p.scale_passes > 0) {   // equilibrate what was just copied: the solves see the scaled problem only
         const Batch members{count, (long long)p.bstride, nullptr, 0};
@@ -1025,6 +1036,16 @@ extern "C" int lpipm_upload_lockstep_shared_ub_tall(lpipm_ctx* c, uint64_t count
     return upload_impl(c, Upload{.count = count, .m = m_ub, .n = n + m_ub, .n_slack = m_ub,
                                  .parts = UploadParts{.m_ub = m_ub, .A_ub = A_ub, .lda_ub = lda_ub}, .b = b, .c = cc, .c0 = c0, .shared = true,
                                  .tall = true, .keep_ok = false});
+}
+// The same batch with `eq` rows in the one image: every member a tall LP with equality rows.  Without any it is
+// lpipm_upload_lockstep_shared_ub_tall's request itself.
+extern "C" int lpipm_upload_lockstep_shared_ub_eq_tall(lpipm_ctx* c, uint64_t count, uint64_t n, uint64_t m_ub, const double* A_ub,
+                                                       uint64_t lda_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq,
+                                                       const double* const* b, const double* const* cc, const double* c0) {
+    if (m_eq == 0) return lpipm_upload_lockstep_shared_ub_tall(c, count, n, m_ub, A_ub, lda_ub, b, cc, c0);
+    return upload_impl(c, Upload{.count = count, .m = m_ub + m_eq, .n = n + m_ub, .n_slack = m_ub,
+                                 .parts = UploadParts{.m_ub = m_ub, .A_ub = A_ub, .lda_ub = lda_ub, .A_eq = A_eq, .lda_eq = lda_eq}, .b = b, .c = cc,
+                                 .c0 = c0, .shared = true, .tall = true, .tall_eq = true, .me = m_eq, .keep_ok = false});
 }
 // The request of a tall batch whose members own their matrices (A_ub[i]: m_ub x n, lda_ub).
 static Upload owned_tall_request(uint64_t count, uint64_t n, uint64_t m_ub, const double* const* A_ub, uint64_t lda_ub,
@@ -1180,16 +1201,21 @@ static hipError_t run_tall_normal(lpipm_ctx* c, const Batch& bt) {
 // S = Zt.Zt^T = A_eq.K^-1.A_eq^T by the A.D.A^T module (A = Zt, dinv = ones, diagonal padded with ones from me), S = L_S.L_S^T.
 // A failed pivot of S lands in the word K's does: dependent equality rows, or more of them than columns, are NumericalProblem.
 // factor == false (lpipm_k_tall_schur): S is left as built.
+// A batch over one image (lpipm_upload_lockstep_shared_ub_eq_tall): every launch covers the members of bt.  The `eq` rows are
+// the one image's (shared_b); Zt, S, their plans' inverses and the pivot word are each member's own, so a failed pivot of K or
+// of S ends that member alone.
 static int tall_eq_schur(lpipm_ctx* c, bool factor = true) {
     const TallArgs& t = c->p.tv;
     hipStream_t st = c->rs.st;
-    LP_HIP(launch_trsm_lt(c->p.A + (size_t)t.ms * c->p.npa, c->p.npa, t.me, c->p.npa, c->p.M, t.nxp, *c->p.factor, c->p.Zt, t.nxp, st));
+    const Batch& bt = c->p.bt;
+    LP_HIP(launch_trsm_lt(c->p.A + (size_t)t.ms * c->p.npa, c->p.npa, t.me, c->p.npa, c->p.M, t.nxp, *c->p.factor, c->p.Zt, t.nxp, st,
+                          bt, c->p.shared_a));
     AdatLaunch a{};
     a.A = c->p.Zt; a.lda = t.nxp; a.dinv = c->p.ones_k; a.M = c->p.S; a.ldm = t.mep; a.M2 = nullptr;
-    a.K = t.nxp; a.diag_pad_from = t.me; a.batch = Batch{}; a.shared_a = false;
+    a.K = t.nxp; a.diag_pad_from = t.me; a.batch = bt; a.shared_a = false;          // (every member's own Zt and ones)
     LP_HIP(launch_adat(c->ap_s, c->p.adat_s, a, false, st, nullptr));
     if (!factor) return LPIPM_OK;
-    LP_HIP(launch_potrf(c->p.S, t.mep, t.mep, *c->p.factor_s, c->p.va.potrf_info, st, Batch{}, nullptr, false, nullptr));
+    LP_HIP(launch_potrf(c->p.S, t.mep, t.mep, *c->p.factor_s, c->p.va.potrf_info, st, bt, nullptr, false, nullptr));
     if (t.me > t.nx) {       // rank(S) <= nx < me: the zero pivot of exact arithmetic, which rounding may have left positive
         tall_eq_singular(c->p.va, t, st);
         LP_HIP(hipGetLastError());
@@ -1205,18 +1231,31 @@ static int tall_eq_reduced_solve(lpipm_ctx* c, int nrhs, const double* r2a, cons
     const TallArgs& t = c->p.tv;
     hipStream_t st = c->rs.st;
     const FactorPlan& fk = *c->p.factor;
-    LP_HIP(launch_chol_solve(c->p.M, t.nxp, fk, nrhs, t.G, c->p.Y, st, Batch{}, SolveSteps{0, -1, false}));
+    const Batch& bt = c->p.bt;
+    LP_HIP(launch_chol_solve(c->p.M, t.nxp, fk, nrhs, t.G, c->p.Y, st, bt, SolveSteps{0, -1, false}));
     prof_mark(c, T_TRSV);
-    LP_HIP(launch_gemv_n(c->p.Zt, t.nxp, t.me, t.nxp, nrhs, c->p.Y, t.nxp, r2a + t.ms, r2b ? r2b + t.ms : nullptr, t.Ve, t.mep, st, -1.0));
+    LP_HIP(launch_gemv_n(c->p.Zt, t.nxp, t.me, t.nxp, nrhs, c->p.Y, t.nxp, r2a + t.ms, r2b ? r2b + t.ms : nullptr, t.Ve, t.mep, st, -1.0, bt));
     prof_mark(c, T_GEMV);
-    LP_HIP(launch_chol_solve(c->p.S, t.mep, *c->p.factor_s, nrhs, t.Ve, c->p.H, st));
+    LP_HIP(launch_chol_solve(c->p.S, t.mep, *c->p.factor_s, nrhs, t.Ve, c->p.H, st, bt));
     prof_mark(c, T_TRSV);
-    LP_HIP(launch_gemv_t(c->p.Zt, t.nxp, t.mep, t.nxp, nrhs, t.Ve, t.mep, c->p.ZtPart, st, t.nxp));
+    LP_HIP(launch_gemv_t(c->p.Zt, t.nxp, t.mep, t.nxp, nrhs, t.Ve, t.mep, c->p.ZtPart, st, t.nxp, bt));
     prof_mark(c, T_GEMV);
     tall_eq_add_w(c->p.va, t, nrhs, c->p.Y, c->p.ZtPart, st);
     LP_HIP(hipGetLastError());
     prof_mark(c, T_VEC);
-    LP_HIP(launch_chol_solve(c->p.M, t.nxp, fk, nrhs, t.G, c->p.Y, st, Batch{}, SolveSteps{(int)fk.sbs.size(), -1, true}));
+    LP_HIP(launch_chol_solve(c->p.M, t.nxp, fk, nrhs, t.G, c->p.Y, st, bt, SolveSteps{(int)fk.sbs.size(), -1, true}));
+    return LPIPM_OK;
+}
+// What a member's earlier solve may have left behind in a batch over one image.  v_e is solved in place over all mep entries
+// of Ve, of which the pass over Zt writes the first me only: a member whose K or S lost a pivot leaves NaN in the padding, and the
+// next solve on the same upload -- of the same member, or of the one lpipm_update_lockstep_vectors puts in its place -- would
+// multiply it into Zt^T.v_e (0 * NaN) and end in NumericalProblem at its first iteration.  Ve of every member this context covers
+// goes back to zero ahead of a solve.  (A single tall-eq upload takes no new vectors and keeps its launch sequence.)
+static int tall_eq_reset(lpipm_ctx* c) {
+    if (!c->p.tall_eq || !c->p.shared_a) return LPIPM_OK;
+    char* ve = (char*)c->p.tv.Ve + (size_t)c->p.bt.first * c->p.bstride;
+    const size_t bytes = 2 * (size_t)c->p.tv.mep * sizeof(double);
+    LP_HIP(c->p.B == 1 ? hipMemsetAsync(ve, 0, bytes, c->rs.st) : hipMemset2DAsync(ve, c->p.bstride, 0, bytes, (size_t)c->p.B, c->rs.st));
     return LPIPM_OK;
 }
 // Tall form: the reduced sym_solve for nrhs right-hand sides (r1a, r2a), (r1b, r2b) whose t the set-up kernel has left in
@@ -1723,6 +1762,7 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, Members members, con
     if (c->profiling) LP_HIP(hipEventRecord(rs.ev_begin, st));
 
     vec_blind_start(v, st);                               // feasible_point.rs:24-31
+    LP_TRY(tall_eq_reset(c));
     prof_mark(c, T_VEC);
     LP_TRY(enqueue_residuals(c, 1, o->ip ? 1 : 0, o->tol));  // feasible_point.rs:32, mod.rs:206
     if (md.rows) LP_TRY(copy_status(c));
@@ -1857,9 +1897,9 @@ static lpipm_ctx* make_view(const lpipm_ctx* c, int first, int count) {
     if (stream_res_create(v->rs, (size_t)count) != LPIPM_OK) { delete v; return nullptr; }
     v->is_view = true;
     v->device = c->device; v->num_cu = c->num_cu; v->refine = c->refine;
-    v->ap = c->ap;
+    v->ap = c->ap; v->ap_s = c->ap_s;
     v->p = c->p;
-    v->p.adat.counters_dirty = true;     // whatever the parent's state: this view's stream has not launched yet
+    v->p.adat.counters_dirty = v->p.adat_s.counters_dirty = true;     // whatever the parent's state: this view's stream has not launched yet
     v->p.B = count;
     v->p.bt = Batch{count, (long long)c->p.bstride, c->p.va.done, first};
     v->p.bt_head = v->p.bt;
@@ -2443,7 +2483,7 @@ extern "C" int lpipm_k_tall_normal(lpipm_ctx* c, const double* dinv, double* K_o
 extern "C" int lpipm_k_tall_schur(lpipm_ctx* c, const double* dinv, double* S_out) {
     if (!c || !dinv || !S_out) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
-    if (!c->p.tall_eq) return LPIPM_ERR_UNSUPPORTED;          // (the upload of lpipm_upload_ub_eq_tall with m_eq > 0, nothing else)
+    if (!c->p.tall_eq || c->p.shared_a) return LPIPM_ERR_UNSUPPORTED;   // (the upload of lpipm_upload_ub_eq_tall with m_eq > 0, nothing else)
     LP_HIP(hipSetDevice(c->device));
     hipStream_t st = c->rs.st;
     const TallArgs& t = c->p.tv;
@@ -2643,6 +2683,71 @@ extern "C" int lpipm_k_potrf_lockstep(lpipm_ctx* c, uint64_t m, int count, doubl
         e = hipMemcpy2DAsync(Ms_inout + (size_t)q * m * m, m * sizeof(double), (char*)M0 + (size_t)q * stride, (size_t)mp * sizeof(double),
                              m * sizeof(double), m, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(infos_out + q, (char*)info0 + (size_t)q * stride, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    }
+    const hipError_t es = hipStreamSynchronize(st);               // also on failure: nothing may still use the buffer freed next
+    if (e == hipSuccess) e = es;
+    factor_plan_destroy(plan);
+    (void)hipFree(base);
+    LP_HIP(e);
+    return LPIPM_OK;
+}
+
+// Z = B . L^-T for every member of a lockstep batch: `count` n x n SPD matrices factored as lpipm_k_potrf_lockstep factors
+// them, then ONE launch_trsm_lt over the members.  B: one rows x cols block (ld ldb) when shared_b, else `count` of them, rows * ldb
+// doubles apart.  Z_inout: count blocks of round_up(rows, 16) x round_up(n, 128) doubles; what they hold on entry is what the
+// members' Z hold before the launch, so a member the launch skips hands it back.  done_mask (nullable): one int per member,
+// non-zero = finished.  With count == 1 and no mask the launch has no member dimension: it is the single kernel's.
+extern "C" int lpipm_k_trsm_lt_lockstep(lpipm_ctx* c, uint64_t n, int count, int rows, int cols, int shared_b, const double* Ms,
+                                        const double* B, uint64_t ldb, double* Z_inout, int32_t* infos_out, const int32_t* done_mask) {
+    if (!c || !Ms || !B || !Z_inout || !infos_out || n == 0 || n > 16384 || count < 1 || count > 64 || rows < 1 || rows > 4096 ||
+        cols < 1 || (uint64_t)cols > n || ldb < (uint64_t)cols)
+        return LPIPM_ERR_BAD_ARGUMENT;
+    LP_HIP(hipSetDevice(c->device));
+    const int mp = (int)round_up(n, NB), rp = (int)round_up((uint64_t)rows, 16);
+    hipStream_t st = c->rs.st;
+    const size_t D = sizeof(double);
+    // one member's arena: the padded matrix, the info and done words, its block of B, its Z, the inverse storage of its plan
+    FactorPlan plan;
+    struct Place { double *M, *Bm, *Z; int32_t* info; int* done; } at{};
+    auto layout = [&](Arena& ar, bool build) -> hipError_t {
+        at.M = ar.take<double>((size_t)mp * mp);
+        at.info = ar.take<int32_t>(1); at.done = ar.take<int>(1);
+        at.Bm = ar.take<double>((size_t)rows * cols); at.Z = ar.take<double>((size_t)rp * mp);
+        return factor_plan_create(plan, at.M, mp, mp, ar, build, st, super_for(mp), merge_edge_for(count));
+    };
+    Arena measure;
+    LP_HIP(layout(measure, false));
+    const size_t stride = round_up(measure.off + 256, 4096);
+    char* base = nullptr;
+    LP_HIP(hipMalloc((void**)&base, stride * (size_t)count));
+    // every failure leaves through the one exit below, which frees the plan and the buffer
+    hipError_t e = hipMemsetAsync(base, 0, stride * (size_t)count, st);
+    Arena real;
+    real.base = base;
+    if (e == hipSuccess) e = layout(real, true);
+    const std::vector<double> pad((size_t)(mp - n), 1.0);
+    std::vector<int> done((size_t)count, 0);
+    for (int q = 0; q < count && done_mask; ++q) done[(size_t)q] = done_mask[q] != 0;
+    for (int q = 0; q < count && e == hipSuccess; ++q) {          // padded copies: [[M, 0], [0, I]]
+        const size_t off = (size_t)q * stride;
+        double* Mq = (double*)((char*)at.M + off);
+        e = hipMemcpy2DAsync(Mq, (size_t)mp * D, Ms + (size_t)q * n * n, n * D, n * D, n, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && mp > (int)n)
+            e = hipMemcpy2DAsync(Mq + n * mp + n, (size_t)(mp + 1) * D, pad.data(), D, D, mp - n, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && (q == 0 || !shared_b))
+            e = hipMemcpy2DAsync((char*)at.Bm + off, (size_t)cols * D, B + (size_t)q * rows * ldb, ldb * D, (size_t)cols * D, (size_t)rows,
+                                 hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)at.Z + off, Z_inout + (size_t)q * rp * mp, (size_t)rp * mp * D, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)at.done + off, &done[(size_t)q], sizeof(int), hipMemcpyHostToDevice, st);
+    }
+    if (e == hipSuccess) e = launch_potrf(at.M, mp, mp, plan, at.info, st, Batch{count, (long long)stride, nullptr, 0});
+    if (e == hipSuccess)
+        e = launch_trsm_lt(at.Bm, cols, rows, cols, at.M, mp, plan, at.Z, mp, st,
+                           Batch{count, (long long)stride, done_mask ? at.done : nullptr, 0}, shared_b != 0);
+    for (int q = 0; q < count && e == hipSuccess; ++q) {
+        const size_t off = (size_t)q * stride;
+        e = hipMemcpyAsync(Z_inout + (size_t)q * rp * mp, (char*)at.Z + off, (size_t)rp * mp * D, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(infos_out + q, (char*)at.info + off, sizeof(int32_t), hipMemcpyDeviceToHost, st);
     }
     const hipError_t es = hipStreamSynchronize(st);               // also on failure: nothing may still use the buffer freed next
     if (e == hipSuccess) e = es;
