@@ -43,11 +43,15 @@ __global__ __launch_bounds__(256) void k_pack_lower(double* __restrict__ M, long
 
 // ---------------------------------------------------------------- FeasiblePoint::blind_start
 // feasible_point.rs:24-31: x = 1, y = 0, z = 1, tau = kappa = 1
+// ... and the one padding an earlier solve on the same upload can have written: the solves run in place over all
+// mp entries of both rows of R, of which the pass A.W writes the first m only, so a factor that holds NaNs -- a lost pivot, a
+// NaN in the iterate -- leaves NaN in R[m .. mp), and the next solve would multiply it into every entry (0 * NaN).  Back to zero.
 __global__ __launch_bounds__(256) void k_blind_start(VecArgs a) {
     if (!vbatch(a, false)) return;
     const int stride = gridDim.x * 256;
     for (int j = blockIdx.x * 256 + threadIdx.x; j < a.n; j += stride) { a.x[j] = 1.0; a.z[j] = 1.0; }
     for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) a.y[i] = 0.0;
+    for (int i = a.m + blockIdx.x * 256 + threadIdx.x; i < a.mp; i += stride) { a.R[i] = 0.0; a.R[a.mp + i] = 0.0; }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         a.S[S_TAU] = 1.0;
         a.S[S_KAPPA] = 1.0;

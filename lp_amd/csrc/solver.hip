@@ -1246,13 +1246,13 @@ static int tall_eq_reduced_solve(lpipm_ctx* c, int nrhs, const double* r2a, cons
     LP_HIP(launch_chol_solve(c->p.M, t.nxp, fk, nrhs, t.G, c->p.Y, st, bt, SolveSteps{(int)fk.sbs.size(), -1, true}));
     return LPIPM_OK;
 }
-// What a member's earlier solve may have left behind in a batch over one image.  v_e is solved in place over all mep entries
-// of Ve, of which the pass over Zt writes the first me only: a member whose K or S lost a pivot leaves NaN in the padding, and the
-// next solve on the same upload -- of the same member, or of the one lpipm_update_lockstep_vectors puts in its place -- would
-// multiply it into Zt^T.v_e (0 * NaN) and end in NumericalProblem at its first iteration.  Ve of every member this context covers
-// goes back to zero ahead of a solve.  (A single tall-eq upload takes no new vectors and keeps its launch sequence.)
+// What an earlier solve on the same upload may have left behind.  v_e is solved in place over all mep entries of Ve,
+// of which the pass over Zt writes the first me only: a solve whose K or S lost a pivot, or whose iterate held a NaN, leaves NaN
+// in the padding, and the next solve on the same upload -- of the same LP, or of the one new vectors put in its place -- would
+// multiply it into Zt^T.v_e (0 * NaN) and end in NumericalProblem at its first iteration.  Ve of every LP this context covers
+// goes back to zero ahead of a solve, and ahead of the kernel entries that run the reduced solve.
 static int tall_eq_reset(lpipm_ctx* c) {
-    if (!c->p.tall_eq || !c->p.shared_a) return LPIPM_OK;
+    if (!c->p.tall_eq) return LPIPM_OK;
     char* ve = (char*)c->p.tv.Ve + (size_t)c->p.bt.first * c->p.bstride;
     const size_t bytes = 2 * (size_t)c->p.tv.mep * sizeof(double);
     LP_HIP(c->p.B == 1 ? hipMemsetAsync(ve, 0, bytes, c->rs.st) : hipMemset2DAsync(ve, c->p.bstride, 0, bytes, (size_t)c->p.B, c->rs.st));
@@ -2521,6 +2521,7 @@ extern "C" int lpipm_k_tall_sym_solve(lpipm_ctx* c, const double* dinv, int nrhs
         LP_HIP(hipMemcpy2DAsync(r1, np * sizeof(double), R1, n * sizeof(double), n * sizeof(double), (size_t)nrhs, hipMemcpyHostToDevice, st));
         LP_HIP(hipMemcpy2DAsync(r2, mp * sizeof(double), R2, m * sizeof(double), m * sizeof(double), (size_t)nrhs, hipMemcpyHostToDevice, st));
         vec_blind_start(v, st);
+        LP_TRY(tall_eq_reset(c));
         LP_TRY(tall_entry_iterate(c, dinv));
         const double* r1b = nrhs == 2 ? r1 + np : nullptr;
         const double* r2b = nrhs == 2 ? r2 + mp : nullptr;
@@ -2950,6 +2951,7 @@ extern "C" int lpipm_k_iteration(lpipm_ctx* c, const lpipm_opts* o, int ip, doub
     hipStream_t st = c->rs.st;
     const Iter it{.refine_now = c->refine == 2};
     vec_blind_start(v, st);                                   // clears done / flags; the iterate is overwritten next
+    LP_TRY(tall_eq_reset(c));
     LP_HIP(hipMemcpyAsync(v.x, x, c->p.n * sizeof(double), hipMemcpyHostToDevice, st));
     LP_HIP(hipMemcpyAsync(v.y, y, c->p.m * sizeof(double), hipMemcpyHostToDevice, st));
     LP_HIP(hipMemcpyAsync(v.z, z, c->p.n * sizeof(double), hipMemcpyHostToDevice, st));
