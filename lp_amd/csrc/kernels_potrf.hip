@@ -720,8 +720,9 @@ static hipError_t potrf_superblock_inverses(const FactorPlan& plan, hipStream_t 
     return hipSuccess;
 }
 
-hipError_t launch_potrf(double* M, int64_t ld, int mp, const FactorPlan& plan, int32_t* info, hipStream_t st,
+hipError_t launch_potrf(const FactorPlan& plan, int32_t* info, hipStream_t st,
                         const Batch& bt, const PotrfLookahead* la, bool clear_info, PotrfBeside* beside) {
+    double* M = plan.L; const int64_t ld = plan.ld; const int mp = plan.mp;
     hipError_t e = clear_info ? potrf_clear_info(info, st, bt) : hipSuccess;   // (the solver's iteration keeps the word clean itself)
     if (e != hipSuccess) return e;
     const int nb = mp / NB;
@@ -758,7 +759,7 @@ hipError_t launch_potrf(double* M, int64_t ld, int mp, const FactorPlan& plan, i
             const SuperBlock& s = plan.sbs[sb_next];
             if (((s.row0 + s.size) / NB - 1) / OUTER > pnl) break;
             // the coupling blocks of a coupled plan (kernels_trsv.hip), ahead of the caller's forward step that reads them
-            if ((e2 = launch_couple_step(M, ld, plan, sb_next, la->side)) != hipSuccess) return e2;
+            if ((e2 = launch_couple_step(plan, sb_next, la->side)) != hipSuccess) return e2;
             if (!has_at) continue;
             ++beside->calls;
             if ((e2 = beside->at(beside->self, sb_next, la->side)) != hipSuccess) return e2;
@@ -768,7 +769,7 @@ hipError_t launch_potrf(double* M, int64_t ld, int mp, const FactorPlan& plan, i
     // the coupling blocks of the super-blocks the side stream did not get, in line behind the inverses
     auto couple_rest = [&]() -> hipError_t {
         for (; sb_next < (int)plan.sbs.size(); ++sb_next) {
-            const hipError_t e2 = launch_couple_step(M, ld, plan, sb_next, st);
+            const hipError_t e2 = launch_couple_step(plan, sb_next, st);
             if (e2 != hipSuccess) return e2;
         }
         return hipSuccess;

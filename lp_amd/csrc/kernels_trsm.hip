@@ -151,9 +151,10 @@ __global__ __launch_bounds__(256) void trsm_lt_batch_kernel(const double* B, lon
     }
 }
 
-hipError_t launch_trsm_lt(const double* B, int64_t ldb, int rows, int cols, const double* L, int64_t ldl, const FactorPlan& plan,
-                          double* Z, int64_t ldz, hipStream_t st, const Batch& bt, bool shared_b) {
+hipError_t launch_trsm_lt(const double* B, int64_t ldb, int rows, int cols, const FactorPlan& plan, double* Z, int64_t ldz,
+                          hipStream_t st, const Batch& bt, bool shared_b) {
     if (rows <= 0 || bt.count <= 0) return hipSuccess;
+    const double* L = plan.L; const int64_t ldl = plan.ld;
     const int n = plan.mp;
     if (n <= 0 || n % NB != 0 || cols > n || ldz < n || ldl < n || (ldz & 3) != 0 || (ldl & 3) != 0 || plan.super_w % NB != 0 ||
         (int)plan.sbs.size() > TRSM_MAX_SB)

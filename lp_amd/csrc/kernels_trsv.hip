@@ -151,11 +151,11 @@ size_t factor_coupling_bytes(int mp, int super_w, int coupled) {
     return doubles * sizeof(double);
 }
 
-hipError_t factor_plan_create(FactorPlan& plan, const double* L, int64_t ld, int mp, Arena& arena, bool build,
+hipError_t factor_plan_create(FactorPlan& plan, double* L, int64_t ld, int mp, Arena& arena, bool build,
                               hipStream_t st, int super_w, int merge_edge, const FactorPlan* scratch_of, int coupled,
                               int couple_edge) {
     factor_plan_destroy(plan);
-    plan.mp = mp;
+    plan.L = L; plan.ld = ld; plan.mp = mp;
     plan.super_w = super_w;
     plan.merge_edge = (merge_edge == 64 || merge_edge == 32) ? merge_edge : 128;
     const int E = plan.merge_edge, SUB = NB / E, EK = E / BK;   // sub-tiles per 128-block edge, k-tiles per sub-tile edge
@@ -340,7 +340,7 @@ void factor_plan_destroy(FactorPlan& plan) {
     plan.descs_dev = nullptr;
     plan.tpart = nullptr;
     plan.tws = nullptr;
-    plan.mp = 0;
+    plan.L = nullptr; plan.ld = 0; plan.mp = 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -384,8 +384,9 @@ __global__ __launch_bounds__(256) void transpose_block_kernel(const double* __re
     for (int i = 0; i < 4; ++i) T[(c0 + ty + 8 * i) * ldt + r0 + tx] = tile[tx][ty + 8 * i];
 }
 
-hipError_t launch_couple_step(const double* L, int64_t ld, const FactorPlan& plan, int k, hipStream_t st) {
+hipError_t launch_couple_step(const FactorPlan& plan, int k, hipStream_t st) {
     if (!plan.coupled) return hipSuccess;
+    const double* L = plan.L; const int64_t ld = plan.ld;
     const CoupleStep& c = plan.couple[(size_t)k];
     const SuperBlock& s = plan.sbs[(size_t)k];
     if (c.lt) {
@@ -472,14 +473,14 @@ static hipError_t launch_sweep(const FactorPlan& plan, const SweepLaunch& l, int
     return hipGetLastError();
 }
 
-hipError_t launch_chol_solve(const double* L, int64_t ld, const FactorPlan& plan, int nrhs, double* R,
-                             double* Y, hipStream_t st, const Batch& bt, const SolveSteps& steps, bool shared_factor) {
+hipError_t launch_chol_solve(const FactorPlan& plan, int nrhs, double* R, double* Y, hipStream_t st, const Batch& bt, const SolveSteps& steps, bool shared_factor) {
     // a coupled plan: one LP that owns its factor (the rule of the callers: a function of the shape alone).  Either sweep may
     // be the coupled one; both leave y in Y and take v to R, and the steps keep their meaning.
     if (plan.coupled && (bt.count != 1 || bt.first != 0 || shared_factor)) return hipErrorInvalidValue;
     // shared_factor: L, inv and invT are ONE factor for the whole batch and get no member offset; every mat-vec of the sweep
     // then runs as the shared-matrix group template (a block of the factor is read once per group of members).  R, Y and
     // the slabs stay per member, and a member's sums are those of the group of one.
+    const double* L = plan.L; const int64_t ld = plan.ld;
     const int mp = plan.mp;
     hipError_t e;
     const int nsb = (int)plan.sbs.size();

@@ -234,6 +234,8 @@ struct SweepLaunch { int first, count, blocks; };          // pieces [first, fir
 // L[rows >= lt_row0, column k] (lt: s_k x lt_ld, null: none) and one grouped GEMM for H_k and G_k.
 struct CoupleStep { double* lt; int lt_row0, lt_ld; int first, count; };
 struct FactorPlan {
+    double* L = nullptr;     // the matrix the plan was created for: factored in place by launch_potrf, read by the solves (LP 0's
+    int64_t ld = 0;          //   in a batch; null: a plan made only to be measured or inspected, never launched)
     int mp = 0;
     int merge_edge = 128;    // output tile edge of the merge GEMMs (32 / 64: latency-bound, 128: flop-bound)
     int super_w = SUPER;     // width of the diagonal super-blocks whose inverses are formed: wider = fewer, fully
@@ -259,25 +261,25 @@ struct FactorPlan {
     double* blk_invT(int k) const;
     int blk_ld(int k) const;
 };
-// Takes the inverse storage for an mp x mp factor living at (L, ld) from the arena (which must be zeroed:
-// the never-written halves of the triangular inverses are read as zeros) and, when `build`, uploads the
-// merge descriptors.  build == false: sizing pass over a measuring arena, nothing is allocated.
+// Takes the inverse storage for an mp x mp factor living at (L, ld) -- recorded in the plan: every launcher below takes the
+// plan alone and works on that matrix -- from the arena (which must be zeroed: the never-written halves of the triangular
+// inverses are read as zeros) and, when `build`, uploads the merge descriptors.  build == false: sizing pass, nothing is allocated.
 // scratch_of (nullable): a plan of the same mp, widths and arena that is never in use at the same time as this one; the new
 // plan then takes only the inverse storage from the arena and works in that plan's merge workspace and gemv_t slabs.
 // coupled (COUPLE_H | COUPLE_G): lay out and describe the coupled backward / forward sweep as well (ignored with a single
 // super-block).  couple_edge: output tile edge of the coupling GEMMs (32, 64 or 128).
-hipError_t factor_plan_create(FactorPlan& plan, const double* L, int64_t ld, int mp, Arena& arena, bool build, hipStream_t st,
+hipError_t factor_plan_create(FactorPlan& plan, double* L, int64_t ld, int mp, Arena& arena, bool build, hipStream_t st,
                               int super_w = SUPER, int merge_edge = 128, const FactorPlan* scratch_of = nullptr,
                               int coupled = 0, int couple_edge = 32);
 void factor_plan_destroy(FactorPlan& plan);
 // Bytes of the coupling blocks and transposed block columns a coupled plan of this shape takes from its arena.
 size_t factor_coupling_bytes(int mp, int super_w, int coupled);
 // The coupling work of super-block k (CoupleStep), on `st`.
-hipError_t launch_couple_step(const double* L, int64_t ld, const FactorPlan& plan, int k, hipStream_t st);
+hipError_t launch_couple_step(const FactorPlan& plan, int k, hipStream_t st);
 
 // ---------------------------------------------------------------- Cholesky (kernels_potrf.hip)
-// In-place blocked lower Cholesky of the mp x mp row-major matrix M (mp multiple of NB), followed by
-// the inverses of the diagonal super-blocks (plan).  info (device int32): 0, or 1 + index of the
+// In-place blocked lower Cholesky of the plan's mp x mp row-major matrix (mp multiple of NB), followed by
+// the inverses of its diagonal super-blocks.  info (device int32): 0, or 1 + index of the
 // first non-positive pivot.
 // Look-ahead for the trailing updates of a single factorisation: `side` is a second stream (CU-masked, so that the chain
 // always finds free CUs), ev_chain / ev_rest one event per outer panel.  nullptr: everything on `st`.
@@ -298,33 +300,30 @@ struct PotrfBeside {
     void* self = nullptr;
     int calls = 0;
 };
-hipError_t launch_potrf(double* M, int64_t ld, int mp, const FactorPlan& plan, int32_t* info, hipStream_t st,
-                        const Batch& bt = Batch{}, const PotrfLookahead* la = nullptr, bool clear_info = true,
-                        PotrfBeside* beside = nullptr);
+hipError_t launch_potrf(const FactorPlan& plan, int32_t* info, hipStream_t st, const Batch& bt = Batch{},
+                        const PotrfLookahead* la = nullptr, bool clear_info = true, PotrfBeside* beside = nullptr);
 
 constexpr int POTRF_OUTER = 4;   // 128-blocks per outer panel (also the width of the column groups of A.D.A^T, kernels_adat.hip)
 
 // ---------------------------------------------------------------- triangular solves (kernels_trsv.hip)
-// R[r] <- L^-T L^-1 R[r], r < nrhs (1|2); R is nrhs x mp (row stride mp); Yscratch: nrhs x mp.
+// R[r] <- L^-T L^-1 R[r] for the plan's factor, r < nrhs (1|2); R is nrhs x mp (row stride mp); Yscratch: nrhs x mp.
 // steps: the forward steps [fwd_begin, fwd_end) (fwd_end < 0: to the last one; the steps before fwd_begin have been run by
 // an earlier call on the same R and Yscratch), then the backward sweep unless `backward` is false.
 struct SolveSteps { int fwd_begin = 0, fwd_end = -1; bool backward = true; };
 // shared_factor: the factor and the plan's inverses belong to the whole batch (a shared-matrix batch's kept first factor):
 // they are not offset by the member, and each step runs as the shared group template of launch_gemv_n / launch_gemv_t.
-hipError_t launch_chol_solve(const double* L, int64_t ld, const FactorPlan& plan, int nrhs, double* R,
-                             double* Yscratch, hipStream_t st, const Batch& bt = Batch{}, const SolveSteps& steps = SolveSteps{},
-                             bool shared_factor = false);
+hipError_t launch_chol_solve(const FactorPlan& plan, int nrhs, double* R, double* Yscratch, hipStream_t st,
+                             const Batch& bt = Batch{}, const SolveSteps& steps = SolveSteps{}, bool shared_factor = false);
 
 // ---------------------------------------------------------------- many right-hand sides (kernels_trsm.hip)
-// Z = B . L^-T for the factor L (ld ldl) of `plan`, order n = plan.mp: row r of Z solves L.z = B[r,:]^T.  B: rows x cols
+// Z = B . L^-T for the factor L of `plan`, order n = plan.mp: row r of Z solves L.z = B[r,:]^T.  B: rows x cols
 // (cols <= n, zeros assumed beyond), row-major.  Z: round_up(rows, 16) x n, ld ldz (a multiple of 4), written whole -- rows
 // past `rows` as zeros.  One launch, one workgroup per 16 rows, fixed-order sums.
 // bt: the members of a lockstep batch, each with its own L, inverses (the plan's are member 0's) and Z, and its own B unless
 // shared_b says that B is one block for all of them (it is then not offset).  Finished members' Z stays untouched; member z's
 // Z has the bits of a single launch on that member's L.  Without a member dimension (count 1, first 0, no done words) the
 // launch is the single kernel's.
-hipError_t launch_trsm_lt(const double* B, int64_t ldb, int rows, int cols, const double* L, int64_t ldl, const FactorPlan& plan,
-                          double* Z, int64_t ldz, hipStream_t st, const Batch& bt = Batch{}, bool shared_b = false);
+hipError_t launch_trsm_lt(const double* B, int64_t ldb, int rows, int cols, const FactorPlan& plan, double* Z, int64_t ldz, hipStream_t st, const Batch& bt = Batch{}, bool shared_b = false);
 
 // ---------------------------------------------------------------- QR arms (kernels_qr.hip)
 // EquationSolverType::{Inverse, LeastSquares}: Householder QR of the full mp x mp matrix whose LOWER

@@ -75,8 +75,25 @@ struct Geometry {
     bool operator==(const Geometry&) const = default;
 };
 
+// One symmetric system of the iteration, complete: the matrix, the plan that factors it in place and solves with it, its
+// pivot-failure word, and the one A.D.A^T launch that builds it (plan, device resources, operand) with what follows it on the
+// diagonal.  Laid out by layout_system, its operand bound by bind_systems, built by build_system.  The uploading context owns
+// the FactorPlan (lpipm_ctx::plans) and the allocations: a plain copy shares everything and owns nothing.
+struct NormalSystem {
+    double* M = nullptr;                 // n x n (ld), lower triangle; null: this problem has no such system
+    int n = 0; int64_t ld = 0;
+    const FactorPlan* factor = nullptr;  // created for (M, ld): the launchers take it alone
+    int32_t* info = nullptr;             // where its failed pivot is kept
+    AdatPlan ap; AdatRes res;            // of the launch that builds it (kernels_adat.hip)
+    bool twin = false;                   // the kept first system: built by the working system's launch (its A, ap and res) into this M
+    // the build's operand: M = A.diag(dinv).A^T over K columns, diagonal entries from diag_pad_from on written as 1
+    const double* A = nullptr; int64_t lda = 0; const double* dinv = nullptr; int K = 0, diag_pad_from = 0; bool shared_a = false;
+    int ns = 0, nx = 0; const double* d = nullptr;     // ... and its diagonal add-on: M[i][i] += d[nx + i], i < ns (d null: none)
+};
+enum { SYS_WORK = 0, SYS_FIRST, SYS_SCHUR, SYS_COUNT };
+
 // The resident problem: geometry, device pointers and launch arguments.  Every pointer points into an allocation of the
-// context that uploaded it (arena, a_shared, the factor plan; the tile and unit lists belong to `adat`, made by
+// context that uploaded it (arena, a_shared, the factor plans; the tile and unit lists belong to each system's `res`, made by
 // adat_lists_create and freed by adat_lists_destroy), so a plain copy of this struct shares the device state and owns
 // nothing: that is what a half-batch view holds (make_view).
 struct Problem {
@@ -96,23 +113,22 @@ struct Problem {
     size_t a_shared_bytes = 0;
     Batch bt;                    // what the solve path hands to every launcher (count, stride, done flags)
     Batch bt_head;               // same with the done test always on: the speculatively enqueued head of an iteration
-    const FactorPlan* factor = nullptr;  // lpipm_ctx::plan of the uploading context
+    // SYS_WORK: M = A.D.A^T, or, tall, K (res.ngroups() > 0: one LP split by columns over ranks, M is reduced column group by
+    // column group behind the running launch).  SYS_FIRST: the kept first-iteration twin M1 (keep).  SYS_SCHUR: S (tall_eq).
+    NormalSystem sys[SYS_COUNT];
     double* tau = nullptr;               // Householder scalars of the QR arms
-    double *A = nullptr, *M = nullptr, *Y = nullptr, *ATpart = nullptr, *xout = nullptr;
+    double *A = nullptr, *Y = nullptr, *ATpart = nullptr, *xout = nullptr;
     double *M0 = nullptr, *R0 = nullptr, *Rho = nullptr, *symv_ws = nullptr;   // refinement of the Cholesky solve
     // The first iteration's factor (see lpipm_ctx::first_valid): a second M with a second factor plan's inverses and a copy
-    // of the pivot-failure word, at the end of every LP's arena.  keep: this layout has them.
+    // of the pivot-failure word, at the end of every LP's arena (sys[SYS_FIRST]).  keep: this layout has them.
     bool keep = false;
-    double* M1 = nullptr;
-    const FactorPlan* factor1 = nullptr; // lpipm_ctx::plan1 of the uploading context
-    int32_t* info1 = nullptr;
     // A shared-matrix batch keeps ONE such set for all its members, behind A in a_shared (layout_shared), built once
     // from `ones` -- iteration 1's dinv, exact 1.0 over the np columns -- ahead of the first solve (ensure_shared_factor).
     bool shared_factor = false;
     double* ones = nullptr;
     // The tall inequality form (lpipm_upload_ub_tall; kernels_tall.hip): a pure-`ub` LP whose Newton system is reduced to the
-    // nxp x nxp matrix K = X^T.W_s.X + E_x.  M is then K (ld nxp), `factor` its plan, `adat` the plan of the launch that builds
-    // it from Xt, and nothing in the arena is m x m.  The row-split slabs of A^T.v are npa wide (tv.npa), not np.
+    // nxp x nxp matrix K = X^T.W_s.X + E_x.  The working system is then K (ld nxp), built from Xt, and nothing in the arena is
+    // m x m.  The row-split slabs of A^T.v are npa wide (tv.npa), not np.
     // A batch of tall LPs over ONE X (lpipm_upload_lockstep_shared_ub_tall: tall && shared_a) keeps X and Xt once, in a_shared;
     // every member's arena then holds its vectors, W_s, E_x, T, G, U_s, its own K with its factor plan's inverses and its slabs.
     // A batch whose members own their matrices (lpipm_upload_lockstep_ub_tall: tall && !shared_a, B arenas) has the single
@@ -130,9 +146,7 @@ struct Problem {
     // the words and slabs of the launch that builds S, and its own ones_k (launch_adat moves dinv with the member).
     bool tall_eq = false;
     int me = 0;
-    double *Zt = nullptr, *S = nullptr, *H = nullptr, *ZtPart = nullptr, *ones_k = nullptr;
-    const FactorPlan* factor_s = nullptr;  // lpipm_ctx::plan_s of the uploading context
-    AdatRes adat_s;
+    double *Zt = nullptr, *H = nullptr, *ZtPart = nullptr, *ones_k = nullptr;
     bool from_parts = false;     // uploaded as ub / eq blocks (lpipm_upload_ub_eq): b and c are not in the caller's slack form
     bool owned_tall = false;     // lpipm_upload_lockstep_ub_tall: a tall batch (of any count) whose members own X_i, Xt_i and K
     // Equilibration (lpipm_set_scaling): the exponents and the maxima slabs, in an allocation of their own that exists only
@@ -141,8 +155,6 @@ struct Problem {
     void* scale_mem = nullptr;
     size_t scale_bytes = 0;
     ScaleBuf sc;
-    AdatRes adat;                // what the A.D.A^T launches use on the device (kernels_adat.hip); adat.ngroups() > 0: one LP split by
-                                 //   columns over ranks, M is reduced column group by column group behind the running launch
     double* gs = nullptr;        // 8 doubles: sums / minima that must be reduced across ranks (n-split mode)
     VecArgs va{};
 };
@@ -153,20 +165,23 @@ struct lpipm_ctx {
     int num_cu = 256;
     StreamRes rs;
     Problem p;
-    AdatPlan ap;
-    AdatPlan ap_s;               // tall_eq: the plan of the launch that builds S from Zt
-    FactorPlan plan_s;           //          and the factor plan of S
-    std::vector<void*> kallocs;  // buffers of the stand-alone kernel entry points
-    FactorPlan plan, kplan;
-    double* ktau = nullptr;
+    FactorPlan plans[SYS_COUNT]; // of p.sys[i] (NormalSystem::factor): they own descriptor and piece lists, so they stay here
+    // Buffers of the stand-alone potrf / solve entries (lpipm_k_potrf and the like): the padded matrix plan.L with its plan,
+    // a pristine copy, right-hand sides, scratch, pivot word, Householder scalars.  kbuf_ensure alone makes them, for an order mp.
+    struct KernelScratch {
+        std::vector<void*> allocs;
+        FactorPlan plan;
+        double *M0 = nullptr, *R = nullptr, *Y = nullptr, *tau = nullptr;
+        int32_t* info = nullptr; int mp = 0;
+        bool chol_valid = false;     // plan.L holds a Cholesky factor (lpipm_k_potrf ran last)
+    } k;
     // Iteration 1 of every solve starts from x = z = 1 (k_blind_start), so its dinv is exactly 1 and its normal matrix is
     // A.A^T (+ I on the slack rows): that matrix, its factor, the inverses and the pivot-failure word depend on A alone.  The
-    // Cholesky arm of a resident problem therefore factors iteration 1 into a second set of buffers (Problem::M1, plan1, info1)
-    // and every later solve on the same upload starts from them instead of running A.D.A^T and the factorisation again.
-    FactorPlan plan1;
+    // Cholesky arm of a resident problem therefore factors iteration 1 into a second system (Problem::sys[SYS_FIRST])
+    // and every later solve on the same upload starts from it instead of running A.D.A^T and the factorisation again.
     bool first_cache = true;     // lpipm_set_first_factor_cache
     int scaling = 0;             // lpipm_set_scaling: equilibration passes of every later upload (0: none)
-    bool first_valid = false;    // M1 / plan1 / info1 hold iteration 1 of this upload (every member's); dropped by any upload.  A
+    bool first_valid = false;    // sys[SYS_FIRST] holds iteration 1 of this upload (every member's); dropped by any upload.  A
                                  //   half-batch view holds the parent's value for the length of one solve
     bool first_done = false;     // the last solve of this context (or view) got through its iteration 1
     // what building a shared-matrix batch's one factor took, until the solve it preceded reports it (lpipm_phase_times)
@@ -193,11 +208,6 @@ struct lpipm_ctx {
                                  //   members -- each variant has its own one or two, always among the members whose last
                                  //   d_tau is ill-determined in fp64 (tests/golden/make_c4_members.py, margin()): the oracle
                                  //   does the same under a permutation of its columns.  Refinement costs 7-20 % and is off.
-    // stand-alone potrf/solve buffers
-    double *kM = nullptr, *kM0 = nullptr, *kR = nullptr, *kY = nullptr;
-    int32_t* kinfo = nullptr;
-    int kmp = 0;
-    bool kchol_valid = false;
     // profiling
     int profiling = 0;           // 0 off, 1 every phase, 2 only the A.D.A^T launches (2 events per iteration)
     double tag_ms[T_NTAGS] = {0, 0, 0, 0, 0};
@@ -458,17 +468,14 @@ extern "C" void lpipm_destroy(lpipm_ctx* c) {
     if (c->stage_dev) (void)hipFree(c->stage_dev);
     if (c->stage_host) (void)hipHostFree(c->stage_host);
     if (c->hint_dev) (void)hipFree(c->hint_dev);
-    adat_lists_destroy(c->p.adat);
-    adat_lists_destroy(c->p.adat_s);
-    free_list(c->kallocs);
+    for (NormalSystem& s : c->p.sys) adat_lists_destroy(s.res);
+    free_list(c->k.allocs);
     if (c->mpack) (void)hipFree(c->mpack);
     if (c->st_c) { (void)hipStreamSynchronize(c->st_c); (void)hipStreamDestroy(c->st_c); }
     if (c->ev_c0) (void)hipEventDestroy(c->ev_c0);
     if (c->ev_c1) (void)hipEventDestroy(c->ev_c1);
-    factor_plan_destroy(c->plan);
-    factor_plan_destroy(c->plan1);
-    factor_plan_destroy(c->plan_s);
-    factor_plan_destroy(c->kplan);
+    for (FactorPlan& f : c->plans) factor_plan_destroy(f);
+    factor_plan_destroy(c->k.plan);
     if (c->la.side) { (void)hipStreamSynchronize(c->la.side); (void)hipStreamDestroy(c->la.side); }
     for (hipEvent_t e : c->la.ev_chain) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->la.ev_rest) (void)hipEventDestroy(e);
@@ -601,22 +608,15 @@ static void set_geometry(Problem& p, const Geometry& g) {
     VecArgs& v = p.va;
     v.np = g.np; v.mp = g.mp; v.nblk = g.nblk; v.nsplit = g.nsplit; v.bcount = g.B; v.bfirst = 0; v.refine_below = refine_below();
 }
-// The plan of the launch that builds the normal matrix: A.D.A^T, or, tall, K from Xt -- nxp rows, a contraction over the mk
-// padded rows of X.  A tall batch: every member's K must have the bits the single LP's has.  The units kernel gives them
-// whatever the count; the round-2 kernel (which a single LP of a few tiles with several chunks takes) only with the single
+// The plan of the launch that builds a system of `order` rows by a contraction over `contraction` columns, for each of B
+// members.  The dense M = A.D.A^T: the batch's plan.  single_bits -- a tall system, K from Xt (nxp rows over the mk padded rows
+// of X) or S from Zt (mep rows over nxp): every member's matrix must have the bits the single LP's has.  The units kernel gives
+// them whatever the count; the round-2 kernel (which a single LP of a few tiles with several chunks takes) only with the single
 // LP's own workgroup count once the contraction is longer than 4096 (round2_unit): the batch then runs that very plan.
-// One rule for both tall batches, over one X or with a matrix per member.
-static AdatPlan adat_plan_of(const Geometry& g, int num_cu, int world, int units_env) {
-    if (!g.tall) return plan_adat(g.mp, g.npa, g.B, num_cu, world, units_env);
-    const AdatPlan single = plan_adat(g.nxp, g.mk, 1, num_cu, 1, units_env);
-    return single.units ? plan_adat(g.nxp, g.mk, g.B, num_cu, 1, units_env) : single;     // (B == 1: `single` either way)
-}
-// tall_eq: the plan of the launch that builds S = Zt.Zt^T -- mep rows, a contraction over nxp -- by the same rule: every member's
-// S must have the bits the single upload's has.
-static AdatPlan adat_s_plan_of(const Geometry& g, int num_cu, int units_env) {
-    if (!g.tall_eq) return AdatPlan{};
-    const AdatPlan single = plan_adat(g.mep, g.nxp, 1, num_cu, 1, units_env);
-    return single.units ? plan_adat(g.mep, g.nxp, g.B, num_cu, 1, units_env) : single;
+static AdatPlan adat_plan_of(int order, int contraction, int B, bool single_bits, int num_cu, int world, int units_env) {
+    if (!single_bits) return plan_adat(order, contraction, B, num_cu, world, units_env);
+    const AdatPlan single = plan_adat(order, contraction, 1, num_cu, 1, units_env);
+    return single.units ? plan_adat(order, contraction, B, num_cu, 1, units_env) : single;     // (B == 1: `single` either way)
 }
 
 // Device state is laid out by functions that take p's geometry and an Arena: one pass over a measuring arena sizes an
@@ -656,72 +656,80 @@ static size_t first_factor_bytes(int mp, int super_w, int coupled) {
     for (int r0 = 0; r0 < mp; r0 += super_w) { const size_t s = (size_t)(mp - r0 < super_w ? mp - r0 : super_w); bytes += 2 * s * s * sizeof(double); }
     return bytes;
 }
-static int layout_first_factor(Problem& p, const FactorPlan& plan, FactorPlan& plan1, Arena& ar, bool build, hipStream_t st) {
+// The plans of the launches that build the systems of p's geometry on context c (what layout_problem sizes their slabs by).
+static void plan_builds(Problem& p, const lpipm_ctx* c) {
+    const Geometry& g = p.geo;
+    p.sys[SYS_WORK].ap = g.tall ? adat_plan_of(g.nxp, g.mk, g.B, true, c->num_cu, 1, c->units_env)
+                                : adat_plan_of(g.mp, g.npa, g.B, false, c->num_cu, c->world, c->units_env);
+    p.sys[SYS_SCHUR].ap = g.tall_eq ? adat_plan_of(g.mep, g.nxp, g.B, true, c->num_cu, 1, c->units_env) : AdatPlan{};
+}
+// One system of order n into an arena: its matrix, then the storage of its factor plan, which is created for that matrix.
+// merge_for: the member count the merge tiles are chosen for; scratch_of: see factor_plan_create.
+static int layout_system(NormalSystem& s, FactorPlan& plan, int n, Arena& ar, bool build, hipStream_t st, int merge_for, int coupled, const FactorPlan* scratch_of = nullptr) {
+    s.n = n; s.ld = n; s.M = ar.take<double>((size_t)n * n);
+    LP_HIP(factor_plan_create(plan, s.M, n, n, ar, build, st, super_for(n), merge_edge_for(merge_for), scratch_of, coupled, couple_edge_for()));
+    s.factor = &plan;
+    return LPIPM_OK;
+}
+static int layout_first_factor(Problem& p, FactorPlan* plans, Arena& ar, bool build, hipStream_t st) {
+    NormalSystem& s = p.sys[SYS_FIRST];
     ar.off = (size_t)round_up(ar.off, 4096);
     const size_t begin = ar.off;
-    p.M1 = ar.take<double>((size_t)p.mp * p.mp);
-    LP_HIP(factor_plan_create(plan1, p.M1, p.mp, p.mp, ar, build, st, super_for(p.mp), merge_edge_for(p.B), &plan, p.geo.coupled, couple_edge_for()));
-    p.factor1 = &plan1; p.info1 = ar.take<int32_t>(1);
+    LP_TRY(layout_system(s, plans[SYS_FIRST], p.mp, ar, build, st, p.B, p.geo.coupled, &plans[SYS_WORK]));
+    s.info = ar.take<int32_t>(1); s.twin = true;
     ar.off = (size_t)round_up(ar.off, 4096);
-    if (ar.off - begin != first_factor_bytes(p.mp, super_for(p.mp), p.geo.coupled)) return LPIPM_ERR_BAD_ARGUMENT;   // (the documented size)
-    return LPIPM_OK;
+    return ar.off - begin == first_factor_bytes(p.mp, super_for(p.mp), p.geo.coupled) ? LPIPM_OK : LPIPM_ERR_BAD_ARGUMENT;   // (the documented size)
 }
 // The arena of one LP; every LP of a lockstep batch gets the same layout, `bstride` bytes after the previous LP's.
 // refine: whether the context refines its solves.  Tall (Problem::tall): the vectors of the dense layout, X and its transpose, the nxp x nxp matrix K with its factor plan, and
 // the work vectors of the reduced solve.  Nothing grows as m^2: no M, M0 or kept first factor.
 // A member of a shared batch (p.shared_a) has the same arena without A (tall: X and Xt): layout_shared.  A member of a tall
 // batch that owns its matrix has the single tall LP's arena.
-// tall_eq: behind K and its plan, Zt, S with its plan (plan_s), the work vectors of the Schur solve, the slabs of Zt^T.v_e, the
-// vector of ones and the words and slabs of the launch that builds S (ap_s) -- in every member's arena of a batch as well.
-static int layout_problem(Problem& p, FactorPlan& plan, FactorPlan& plan1, FactorPlan& plan_s, const AdatPlan& ap,
-                          const AdatPlan& ap_s, int refine, Arena& ar, bool build, hipStream_t st) {
+// tall_eq: behind K and its plan, Zt, S with its plan, the work vectors of the Schur solve, the slabs of Zt^T.v_e, the
+// vector of ones and the words and slabs of the launch that builds S -- in every member's arena of a batch as well.
+// The systems' A.D.A^T plans are set (relayout); plans: lpipm_ctx::plans.
+static int layout_problem(Problem& p, FactorPlan* plans, int refine, Arena& ar, bool build, hipStream_t st) {
     TallArgs& t = p.tv;
+    NormalSystem &work = p.sys[SYS_WORK], &schur = p.sys[SYS_SCHUR];
     const size_t mp = (size_t)p.mp, np = (size_t)p.np, nxp = (size_t)t.nxp;
     p.A = p.shared_a ? nullptr : ar.take<double>(mp * p.npa);
     p.Xt = p.shared_a || !p.tall ? nullptr : ar.take<double>(nxp * (size_t)t.mk);
     layout_vectors(p, ar);
+    p.Zt = p.H = p.ZtPart = p.ones_k = nullptr; t.Ve = nullptr;
     if (p.tall) {
         t.Ws = ar.take<double>((size_t)t.mk); t.Ex = ar.take<double>(nxp);
         t.T = ar.take<double>(2 * mp); t.G = ar.take<double>(2 * nxp); t.Us = ar.take<double>(2 * mp);
-        p.M = ar.take<double>(nxp * nxp);
-        LP_HIP(factor_plan_create(plan, p.M, t.nxp, t.nxp, ar, build, st, super_for(t.nxp), merge_edge_for(1)));
-        p.Zt = p.S = p.H = p.ZtPart = p.ones_k = nullptr; t.Ve = nullptr; p.factor_s = nullptr;
+        LP_TRY(layout_system(work, plans[SYS_WORK], t.nxp, ar, build, st, 1, 0));
         if (p.tall_eq) {
             const size_t mep = (size_t)t.mep;
-            p.Zt = ar.take<double>(mep * nxp); p.S = ar.take<double>(mep * mep);
-            LP_HIP(factor_plan_create(plan_s, p.S, t.mep, t.mep, ar, build, st, super_for(t.mep), merge_edge_for(1)));
-            p.factor_s = &plan_s;
+            p.Zt = ar.take<double>(mep * nxp);
+            LP_TRY(layout_system(schur, plans[SYS_SCHUR], t.mep, ar, build, st, 1, 0));
             t.Ve = ar.take<double>(2 * mep); p.H = ar.take<double>(2 * mep);
             p.ZtPart = ar.take<double>(mep / GEMVT_ROWS * 2 * nxp); p.ones_k = ar.take<double>(nxp);
-            adat_take(p.adat_s, ap_s, ar);
-        } else factor_plan_destroy(plan_s);
-    } else {
-        factor_plan_destroy(plan_s);
-        p.M = ar.take<double>(mp * mp);
-        LP_HIP(factor_plan_create(plan, p.M, p.mp, p.mp, ar, build, st, super_for(p.mp), merge_edge_for(p.B), nullptr, p.geo.coupled, couple_edge_for()));
-    }
-    p.factor = &plan;
+            adat_take(schur.res, schur.ap, ar);
+        }
+    } else LP_TRY(layout_system(work, plans[SYS_WORK], p.mp, ar, build, st, p.B, p.geo.coupled));
+    work.info = schur.info = p.va.potrf_info;    // (a failed pivot of S lands in the word K's does)
     p.M0 = p.R0 = p.Rho = p.symv_ws = nullptr;
     if (refine > 0 && !p.tall) {     // only the refined solves read the matrix itself
         p.M0 = ar.take<double>(mp * mp); p.R0 = ar.take<double>(2 * mp); p.Rho = ar.take<double>(2 * mp);
         p.symv_ws = ar.take<double>(symv_slab_doubles(p.mp));
     }
     p.tau = ar.take<double>(p.tall ? 1 : mp); p.gs = ar.take<double>(8); p.xout = ar.take<double>(np);
-    adat_take(p.adat, ap, ar);
+    adat_take(work.res, work.ap, ar);
     p.keep = p.geo.keep;
     p.shared_factor = p.keep && p.shared_a;      // one set for the batch, outside the arenas (layout_shared)
-    p.M1 = nullptr; p.factor1 = nullptr; p.info1 = nullptr; p.ones = nullptr;
-    if (!p.keep) factor_plan_destroy(plan1);
-    else if (!p.shared_factor) LP_TRY(layout_first_factor(p, plan, plan1, ar, build, st));
+    p.ones = nullptr;
+    if (p.keep && !p.shared_factor) LP_TRY(layout_first_factor(p, plans, ar, build, st));
     return LPIPM_OK;
 }
 // The shared allocation of a shared-matrix batch: the one A, mp x npa like an arena's, zero padding (tall: behind X its transpose,
 // nxp x mk), then the one kept first factor (p.shared_factor) and the vector of ones, np doubles rounded up to 4096 bytes.
-static int layout_shared(Problem& p, const FactorPlan& plan, FactorPlan& plan1, Arena& sh, bool build, hipStream_t st) {
+static int layout_shared(Problem& p, FactorPlan* plans, Arena& sh, bool build, hipStream_t st) {
     p.A = sh.take<double>((size_t)p.mp * p.npa);
     if (p.tall) p.Xt = sh.take<double>((size_t)p.tv.nxp * p.tv.mk);
     if (!p.shared_factor) return LPIPM_OK;
-    LP_TRY(layout_first_factor(p, plan, plan1, sh, build, st));
+    LP_TRY(layout_first_factor(p, plans, sh, build, st));
     p.ones = sh.take<double>((size_t)p.np);
     sh.off = (size_t)round_up(sh.off, 4096);
     return LPIPM_OK;
@@ -733,33 +741,44 @@ static int relayout(lpipm_ctx* c, const Geometry& g) {
     LP_HIP(hipStreamSynchronize(st));
     if (p.arena) { LP_HIP(hipFree(p.arena)); p.arena = nullptr; }
     if (p.a_shared) { LP_HIP(hipFree(p.a_shared)); p.a_shared = nullptr; p.a_shared_bytes = 0; }
-    adat_lists_destroy(p.adat); adat_lists_destroy(p.adat_s);
-    factor_plan_destroy(c->plan); factor_plan_destroy(c->plan1); factor_plan_destroy(c->plan_s);
+    for (int i = 0; i < SYS_COUNT; ++i) { adat_lists_destroy(p.sys[i].res); factor_plan_destroy(c->plans[i]); p.sys[i] = NormalSystem{}; }
     p.has_problem = false;
     set_geometry(p, g);
-    c->ap = adat_plan_of(g, c->num_cu, c->world, c->units_env);
-    c->ap_s = adat_s_plan_of(g, c->num_cu, c->units_env);
+    plan_builds(p, c);
     Arena measure;
-    LP_TRY(layout_problem(p, c->plan, c->plan1, c->plan_s, c->ap, c->ap_s, c->refine, measure, false, st));
+    LP_TRY(layout_problem(p, c->plans, c->refine, measure, false, st));
     p.bstride = round_up(measure.off, 4096);
     p.arena_bytes = p.bstride * (size_t)g.B; p.va.bstride = (long long)p.bstride;
     LP_HIP(hipMalloc((void**)&p.arena, p.arena_bytes));
     LP_HIP(hipMemsetAsync(p.arena, 0, p.arena_bytes, st));
     Arena real{p.arena};
-    LP_TRY(layout_problem(p, c->plan, c->plan1, c->plan_s, c->ap, c->ap_s, c->refine, real, true, st));
+    LP_TRY(layout_problem(p, c->plans, c->refine, real, true, st));
     if (g.shared) {
         Arena sh_measure;
-        LP_TRY(layout_shared(p, c->plan, c->plan1, sh_measure, false, st));
+        LP_TRY(layout_shared(p, c->plans, sh_measure, false, st));
         p.a_shared_bytes = sh_measure.off;
         LP_HIP(hipMalloc((void**)&p.a_shared, p.a_shared_bytes));
         LP_HIP(hipMemsetAsync(p.a_shared, 0, p.a_shared_bytes, st));
         Arena sh{(char*)p.a_shared};
-        LP_TRY(layout_shared(p, c->plan, c->plan1, sh, true, st));
+        LP_TRY(layout_shared(p, c->plans, sh, true, st));
     }
-    LP_HIP(adat_lists_create(p.adat, c->ap, g.tall ? g.nxp : g.mp, g.B, st));    // (drains st)
-    if (g.tall_eq) LP_HIP(adat_lists_create(p.adat_s, c->ap_s, g.mep, g.B, st));
+    for (NormalSystem& s : p.sys) if (s.M && !s.twin) LP_HIP(adat_lists_create(s.res, s.ap, s.n, g.B, st));    // (drains st)
     LP_TRY(stream_res_grow_status(c->rs, (size_t)g.B));
     return LPIPM_OK;
+}
+// What each system's launch reads, bound once the upload's own sizes are known (a padded geometry serves several m, nx, me);
+// the kept first system is the working one's twin.
+static void bind_systems(Problem& p) {
+    const TallArgs& t = p.tv;
+    auto bind = [](NormalSystem& s, const double* A, int lda, const double* dinv, int pad_from, bool shared_a, int ns, int nx, const double* d) {
+        s.A = A; s.lda = s.K = lda; s.dinv = dinv; s.diag_pad_from = pad_from; s.shared_a = shared_a; s.ns = ns; s.nx = nx; s.d = d;
+    };
+    // M = A.D.A^T + diag(D_slack) (newton_equations.rs:54-57).  Tall: K = X^T.diag(W_s).X + diag(E_x), Xt as its A, a contraction
+    // over the mk padded rows of X (a batch: the one Xt or every member's own, and every member's own W_s), ones beyond nx
+    if (p.tall) bind(p.sys[SYS_WORK], p.Xt, t.mk, t.Ws, t.nx, p.shared_a, t.nx, 0, t.Ex);
+    else bind(p.sys[SYS_WORK], p.A, p.npa, p.va.dinv, (int)p.m, p.shared_a, p.ns, p.nx, p.va.dinv);
+    // S = Zt.Zt^T: A = Zt, dinv = ones (every member's own of both), the diagonal padded with ones from me, nothing added
+    if (p.tall_eq) bind(p.sys[SYS_SCHUR], p.Zt, t.nxp, p.ones_k, t.me, false, 0, 0, nullptr);
 }
 // The exponent block of the upload being made: `sets` exponent sets for the padded geometry when the context scales, none
 // otherwise (what a previous upload left is freed).  Exponents start at zero.
@@ -942,6 +961,7 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
     p.me = u.tall_eq ? (int)u.me : 0;
     if (u.tall) { p.tv.ms = (int)m_ub; p.tv.me = p.me; }
     p.from_parts = u.parts.has_value(); p.owned_tall = u.owned;
+    bind_systems(p);
     p.va.n = (int)u.n; p.va.m = (int)u.m; p.va.n_total = (long long)u.n; p.va.gs = nullptr; c->colsplit = false;   // lpipm_upload_nsplit overrides
     // A single LP's loop ends on the host, so its kernels need not test the done word (one dependent load
     // less at the start of ~100 short kernels) -- except the head of an iteration, which is enqueued before
@@ -951,11 +971,10 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
     p.va.done_chk = p.bt.done;
     std::vector<double> c0v((size_t)count, 0.0);          // must outlive the asynchronous copies below
     for (int i = 0; i < count; ++i) c0v[i] = u.c0 ? u.c0[i] : 0.0;
-    const std::vector<double> onesv(p.shared_factor ? (size_t)g.np : 0, 1.0);     // likewise
+    const std::vector<double> onesv(p.shared_factor ? (size_t)g.np : u.tall_eq ? (size_t)g.nxp : 0, 1.0);     // likewise
     if (p.shared_factor) LP_HIP(hipMemcpyAsync(p.ones, onesv.data(), onesv.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    const std::vector<double> ones_k(u.tall_eq ? (size_t)g.nxp : 0, 1.0);         // likewise: the dinv of S = Zt.Zt^T
-    for (int i = 0; i < count && u.tall_eq; ++i)                                   // (every member's own: launch_adat moves dinv with the member)
-        LP_HIP(hipMemcpyAsync((char*)p.ones_k + (size_t)i * p.bstride, ones_k.data(), ones_k.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    for (int i = 0; i < count && u.tall_eq; ++i)     // the dinv of S = Zt.Zt^T (every member's own: launch_adat moves dinv with the member)
+        LP_HIP(hipMemcpyAsync((char*)p.ones_k + (size_t)i * p.bstride, onesv.data(), onesv.size() * sizeof(double), hipMemcpyHostToDevice, st));
     LP_TRY(u.dev ? copy_in_device(c, u, c0v.data()) : copy_in(c, u, c0v.data()));
     if (p.scale_passes > 0) {   // equilibrate what was just copied: the solves see the scaled problem only
         const Batch members{count, (long long)p.bstride, nullptr, 0};
@@ -968,7 +987,8 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
     //       (of the `ub` rows alone when there are `eq` rows: K is built from them)
     if (u.tall) LP_HIP(tall_transpose(p.A, g.npa, (int)(u.tall_eq ? m_ub : u.m), (int)nx, p.Xt, g.mk, st, u.shared ? Batch{} : Batch{count, (long long)p.bstride, nullptr, 0}));
     LP_HIP(hipStreamSynchronize(st));   // the caller's arrays, c0v and onesv are free again from here
-    p.has_problem = p.adat.counters_dirty = p.adat_s.counters_dirty = true;
+    p.has_problem = true;
+    for (NormalSystem& sy : p.sys) sy.res.counters_dirty = true;
     bind_status_pinned(c, true);
     return LPIPM_OK;
 }
@@ -1139,22 +1159,19 @@ static hipError_t ctx_gemv_dual(lpipm_ctx* c, const double* W, const double* V, 
     return launch_slack_dual(c->p.ns, c->p.nx, c->p.nsplit, W, V, AxPart, c->p.ATpart, c->p.np, c->rs.st, bt);
 }
 
-// M = A . diag(dinv) . A^T, lower tiles (newton_equations.rs:54-57); a second copy of it goes to M0 (the matrix the
-// refined Cholesky solves take their residuals against: M itself is factorised in place)
 // The switches of the ONE iteration being enqueued: made by whoever enqueues it, handed down by reference, kept nowhere.
 struct Iter {
-    bool on_first = false;       // it works in M1 / plan1 (iteration 1 of a solve that uses the kept first factor) ...
+    bool on_first = false;       // it works in the kept first system (iteration 1 of a solve that uses the kept first factor) ...
     bool skip_factor = false;    //   ... which already hold its factor: no A.D.A^T, no factorisation
     bool refine_now = false;     // it refines its solves (host mirror of the LPs' skip_refine words)
 };
-// The matrix and the factor plan of that iteration: the kept first factor's or the working ones.
-static double* cur_M(const lpipm_ctx* c, const Iter& it) { return it.on_first ? c->p.M1 : c->p.M; }
-static const FactorPlan& cur_factor(const lpipm_ctx* c, const Iter& it) { return it.on_first ? *c->p.factor1 : *c->p.factor; }
-static bool cur_shared(const lpipm_ctx* c, const Iter& it) { return it.on_first && c->p.shared_factor; }   // one factor for the whole batch
+// The system of that iteration, and whether it is the ONE kept factor of a whole shared-matrix batch.
+static NormalSystem& cur_sys(lpipm_ctx* c, const Iter& it) { return c->p.sys[it.on_first ? SYS_FIRST : SYS_WORK]; }
+static bool shared_first(const lpipm_ctx* c, const Iter& it) { return it.on_first && c->p.shared_factor; }
 // The pivot-failure words of the LPs this context covers, between the solver's word and its kept copy (device to device).
 // A shared-matrix batch's one kept word goes to every LP (the other direction does not exist: the build wrote it).
 static hipError_t copy_info(lpipm_ctx* c, int32_t* dst, const int32_t* src) {
-    if (c->p.shared_factor && src == c->p.info1) {
+    if (c->p.shared_factor && src == c->p.sys[SYS_FIRST].info) {
         ScatterRows<int32_t> w;
         w.seg[0].dst = dst; w.seg[0].src = src; w.seg[0].ld = 0; w.seg[0].len = 1;
         vec_scatter_rows(w, c->rs.st, c->p.bt);
@@ -1166,39 +1183,32 @@ static hipError_t copy_info(lpipm_ctx* c, int32_t* dst, const int32_t* src) {
     return c->p.B == 1 ? hipMemcpyAsync(d, s, sizeof(int32_t), hipMemcpyDeviceToDevice, c->rs.st)
                        : hipMemcpy2DAsync(d, c->p.bstride, s, c->p.bstride, sizeof(int32_t), (size_t)c->p.B, hipMemcpyDeviceToDevice, c->rs.st);
 }
-static AdatLaunch adat_launch(lpipm_ctx* c, const Iter& it, const Batch& bt) {
+// Builds system s for the members of bt: its one A.D.A^T launch, then its diagonal add-on.  Nothing else fills an AdatLaunch.
+struct BuildOpts {
+    const double* dinv = nullptr;    // instead of the system's own (and of its add-on's vector, where that is the same one)
+    double* M2 = nullptr;            // a second copy of M, which is factored in place: a refining context's M0 (null otherwise)
+    bool signal_groups = false;      // the column-split pipeline (launch_adat, armed with ev_c0): the caller reduces M group by group
+                                     //   behind the launch and makes the copy itself; no structural slack there, nothing is added
+};
+static hipError_t build_system(lpipm_ctx* c, NormalSystem& s, const Batch& bt, const BuildOpts& o = BuildOpts{}) {
+    NormalSystem& src = s.twin ? c->p.sys[SYS_WORK] : s;
+    hipStream_t st = c->rs.st;
     AdatLaunch a{};
-    a.A = c->p.A; a.lda = c->p.npa; a.dinv = c->p.va.dinv; a.M = cur_M(c, it); a.ldm = c->p.mp;
-    a.M2 = c->refine > 0 ? c->p.M0 : nullptr;                                // only the refined solves need M itself
-    a.K = c->p.npa; a.diag_pad_from = (int)c->p.m; a.batch = bt; a.shared_a = c->p.shared_a;
-    return a;
-}
-static hipError_t run_adat(lpipm_ctx* c, const Iter& it, const Batch& bt) {
+    a.A = src.A; a.lda = src.lda; a.dinv = o.dinv ? o.dinv : src.dinv; a.M = s.M; a.ldm = s.ld; a.M2 = o.M2;
+    a.K = src.K; a.diag_pad_from = src.diag_pad_from; a.batch = bt; a.shared_a = src.shared_a;
     bool second_copy = false;
-    hipError_t e = launch_adat(c->ap, c->p.adat, adat_launch(c, it, bt), false, c->rs.st, &second_copy);
-    if (e != hipSuccess) return e;
-    e = launch_slack_diag(c->p.ns, c->p.nx, c->p.va.dinv, cur_M(c, it), c->p.mp, c->rs.st, bt);   // + diag(D_slack)
-    if (e != hipSuccess) return e;
-    if (c->refine <= 0) return hipSuccess;
-    if (second_copy) return launch_slack_diag(c->p.ns, c->p.nx, c->p.va.dinv, c->p.M0, c->p.mp, c->rs.st, bt);
-    vec_copy_lower(c->p.M, c->p.M0, c->p.mp, c->p.mp, c->rs.st, bt);     // the launch could not write it: copied afterwards
+    hipError_t e = launch_adat(src.ap, src.res, a, o.signal_groups, st, &second_copy, o.signal_groups ? c->ev_c0 : nullptr);
+    if (e != hipSuccess || o.signal_groups || !src.d) return e;
+    const double* d = o.dinv && src.d == src.dinv ? o.dinv : src.d;
+    e = launch_slack_diag(src.ns, src.nx, d, s.M, s.ld, st, bt);
+    if (e != hipSuccess || !o.M2) return e;
+    if (second_copy) return launch_slack_diag(src.ns, src.nx, d, o.M2, s.ld, st, bt);
+    vec_copy_lower(s.M, o.M2, s.n, s.n, st, bt);          // the launch could not write it: copied afterwards
     return hipGetLastError();
 }
 
-// Tall form: K = X^T.diag(W_s).X + diag(E_x) into M -- the same launch with Xt as its A (nxp rows, contraction over the mk
-// padded rows of X), W_s as its dinv, the diagonal beyond nx padded with ones; E_x goes onto the diagonal the way D_s does
-// on the dense path.
-static hipError_t run_tall_normal(lpipm_ctx* c, const Batch& bt) {
-    const TallArgs& t = c->p.tv;
-    AdatLaunch a{};
-    a.A = c->p.Xt; a.lda = t.mk; a.dinv = t.Ws; a.M = c->p.M; a.ldm = t.nxp; a.M2 = nullptr;
-    a.K = t.mk; a.diag_pad_from = t.nx; a.batch = bt; a.shared_a = c->p.shared_a;    // (a batch: the one Xt or every member's own, and every member's own W_s)
-    hipError_t e = launch_adat(c->ap, c->p.adat, a, false, c->rs.st, nullptr);
-    if (e != hipSuccess) return e;
-    return launch_slack_diag(t.nx, 0, t.Ex, c->p.M, t.nxp, c->rs.st, bt);
-}
 // Tall form with equality rows, once per iteration behind K = L.L^T: Zt = A_eq.L^-T from the `eq` rows of the (scaled) image,
-// S = Zt.Zt^T = A_eq.K^-1.A_eq^T by the A.D.A^T module (A = Zt, dinv = ones, diagonal padded with ones from me), S = L_S.L_S^T.
+// S = Zt.Zt^T = A_eq.K^-1.A_eq^T by the A.D.A^T module, S = L_S.L_S^T.
 // A failed pivot of S lands in the word K's does: dependent equality rows, or more of them than columns, are NumericalProblem.
 // factor == false (lpipm_k_tall_schur): S is left as built.
 // A batch over one image (lpipm_upload_lockstep_shared_ub_eq_tall): every launch covers the members of bt.  The `eq` rows are
@@ -1208,14 +1218,11 @@ static int tall_eq_schur(lpipm_ctx* c, bool factor = true) {
     const TallArgs& t = c->p.tv;
     hipStream_t st = c->rs.st;
     const Batch& bt = c->p.bt;
-    LP_HIP(launch_trsm_lt(c->p.A + (size_t)t.ms * c->p.npa, c->p.npa, t.me, c->p.npa, c->p.M, t.nxp, *c->p.factor, c->p.Zt, t.nxp, st,
-                          bt, c->p.shared_a));
-    AdatLaunch a{};
-    a.A = c->p.Zt; a.lda = t.nxp; a.dinv = c->p.ones_k; a.M = c->p.S; a.ldm = t.mep; a.M2 = nullptr;
-    a.K = t.nxp; a.diag_pad_from = t.me; a.batch = bt; a.shared_a = false;          // (every member's own Zt and ones)
-    LP_HIP(launch_adat(c->ap_s, c->p.adat_s, a, false, st, nullptr));
+    NormalSystem& S = c->p.sys[SYS_SCHUR];
+    LP_HIP(launch_trsm_lt(c->p.A + (size_t)t.ms * c->p.npa, c->p.npa, t.me, c->p.npa, *c->p.sys[SYS_WORK].factor, c->p.Zt, t.nxp, st, bt, c->p.shared_a));
+    LP_HIP(build_system(c, S, bt));
     if (!factor) return LPIPM_OK;
-    LP_HIP(launch_potrf(c->p.S, t.mep, t.mep, *c->p.factor_s, c->p.va.potrf_info, st, bt, nullptr, false, nullptr));
+    LP_HIP(launch_potrf(*S.factor, S.info, st, bt, nullptr, false, nullptr));
     if (t.me > t.nx) {       // rank(S) <= nx < me: the zero pivot of exact arithmetic, which rounding may have left positive
         tall_eq_singular(c->p.va, t, st);
         LP_HIP(hipGetLastError());
@@ -1230,20 +1237,20 @@ static int tall_eq_schur(lpipm_ctx* c, bool factor = true) {
 static int tall_eq_reduced_solve(lpipm_ctx* c, int nrhs, const double* r2a, const double* r2b) {
     const TallArgs& t = c->p.tv;
     hipStream_t st = c->rs.st;
-    const FactorPlan& fk = *c->p.factor;
+    const FactorPlan& fk = *c->p.sys[SYS_WORK].factor;
     const Batch& bt = c->p.bt;
-    LP_HIP(launch_chol_solve(c->p.M, t.nxp, fk, nrhs, t.G, c->p.Y, st, bt, SolveSteps{0, -1, false}));
+    LP_HIP(launch_chol_solve(fk, nrhs, t.G, c->p.Y, st, bt, SolveSteps{0, -1, false}));
     prof_mark(c, T_TRSV);
     LP_HIP(launch_gemv_n(c->p.Zt, t.nxp, t.me, t.nxp, nrhs, c->p.Y, t.nxp, r2a + t.ms, r2b ? r2b + t.ms : nullptr, t.Ve, t.mep, st, -1.0, bt));
     prof_mark(c, T_GEMV);
-    LP_HIP(launch_chol_solve(c->p.S, t.mep, *c->p.factor_s, nrhs, t.Ve, c->p.H, st, bt));
+    LP_HIP(launch_chol_solve(*c->p.sys[SYS_SCHUR].factor, nrhs, t.Ve, c->p.H, st, bt));
     prof_mark(c, T_TRSV);
     LP_HIP(launch_gemv_t(c->p.Zt, t.nxp, t.mep, t.nxp, nrhs, t.Ve, t.mep, c->p.ZtPart, st, t.nxp, bt));
     prof_mark(c, T_GEMV);
     tall_eq_add_w(c->p.va, t, nrhs, c->p.Y, c->p.ZtPart, st);
     LP_HIP(hipGetLastError());
     prof_mark(c, T_VEC);
-    LP_HIP(launch_chol_solve(c->p.M, t.nxp, fk, nrhs, t.G, c->p.Y, st, bt, SolveSteps{(int)fk.sbs.size(), -1, true}));
+    LP_HIP(launch_chol_solve(fk, nrhs, t.G, c->p.Y, st, bt, SolveSteps{(int)fk.sbs.size(), -1, true}));
     return LPIPM_OK;
 }
 // What an earlier solve on the same upload may have left behind.  v_e is solved in place over all mep entries of Ve,
@@ -1259,7 +1266,7 @@ static int tall_eq_reset(lpipm_ctx* c) {
     return LPIPM_OK;
 }
 // Tall form: the reduced sym_solve for nrhs right-hand sides (r1a, r2a), (r1b, r2b) whose t the set-up kernel has left in
-// T, up to u_x in G and u_s in Us; the caller's epilogue kernel forms p, q, u, v.  K's factor is in M.
+// T, up to u_x in G and u_s in Us; the caller's epilogue kernel forms p, q, u, v.  K is factored.
 static int tall_sym_solve(lpipm_ctx* c, int nrhs, const double* r1a, const double* r2a, const double* r1b, const double* r2b,
                           const Batch& bt) {
     const TallArgs& t = c->p.tv;
@@ -1271,7 +1278,7 @@ static int tall_sym_solve(lpipm_ctx* c, int nrhs, const double* r1a, const doubl
     LP_HIP(hipGetLastError());
     prof_mark(c, T_VEC);
     if (c->p.tall_eq) LP_TRY(tall_eq_reduced_solve(c, nrhs, r2a, r2b));          // u_x through the Schur complement, v_e
-    else LP_HIP(launch_chol_solve(c->p.M, t.nxp, *c->p.factor, nrhs, t.G, c->p.Y, st, bt));   // u_x = K^-1 g
+    else LP_HIP(launch_chol_solve(*c->p.sys[SYS_WORK].factor, nrhs, t.G, c->p.Y, st, bt));   // u_x = K^-1 g
     prof_mark(c, T_TRSV);
     ++c->gemv_passes;                                                             // u_s = r2 - X.u_x   (tall_eq: over the `ub` rows)
     LP_HIP(launch_gemv_n(c->p.A, c->p.npa, c->p.tall_eq ? t.ms : (int)c->p.m, c->p.npa, nrhs, t.G, t.nxp, r2a, r2b, t.Us, c->p.mp, st, -1.0, bt, c->p.shared_a));
@@ -1284,13 +1291,14 @@ static int tall_sym_solve(lpipm_ctx* c, int nrhs, const double* r1a, const doubl
 // precision, one read of the lower triangle);  v = v0 + L^-T L^-1 rho.  R: nrhs x mp, in/out.
 static int chol_solve_refined(lpipm_ctx* c, const Iter& it, int nrhs, double* R, const Batch& bt) {
     hipStream_t st = c->rs.st;
-    if (!it.refine_now) { LP_HIP(launch_chol_solve(cur_M(c, it), c->p.mp, cur_factor(c, it), nrhs, R, c->p.Y, st, bt, SolveSteps{}, cur_shared(c, it))); return LPIPM_OK; }
+    const FactorPlan& f = *cur_sys(c, it).factor;    // (a refining context keeps no first factor: the working system's)
+    if (!it.refine_now) { LP_HIP(launch_chol_solve(f, nrhs, R, c->p.Y, st, bt, SolveSteps{}, shared_first(c, it))); return LPIPM_OK; }
     // the refinement's launches skip an LP whose own word says so (a finished one, or one that does not need it yet)
     const Batch br = c->refine == 2 ? bt : Batch{bt.count, bt.stride, c->p.va.skip_refine, bt.first};
     vec_rows_copy(c->p.mp, nrhs, c->p.R0, R, st, br);
-    LP_HIP(launch_chol_solve(c->p.M, c->p.mp, *c->p.factor, nrhs, R, c->p.Y, st, bt));
+    LP_HIP(launch_chol_solve(f, nrhs, R, c->p.Y, st, bt));
     LP_HIP(launch_symv_residual(c->p.M0, c->p.mp, c->p.mp, nrhs, R, c->p.mp, c->p.R0, c->p.mp, c->p.Rho, c->p.mp, c->p.symv_ws, st, br));
-    LP_HIP(launch_chol_solve(c->p.M, c->p.mp, *c->p.factor, nrhs, c->p.Rho, c->p.Y, st, br));
+    LP_HIP(launch_chol_solve(f, nrhs, c->p.Rho, c->p.Y, st, br));
     vec_rows_add(c->p.mp, nrhs, R, c->p.Rho, st, br);
     LP_HIP(hipGetLastError());
     return LPIPM_OK;
@@ -1367,8 +1375,8 @@ static int copy_status(lpipm_ctx* c) {
     else if (c->p.B == 1) LP_HIP(hipMemcpyAsync(c->rs.status_host, (const char*)c->p.va.status + (size_t)c->p.bt.first * c->p.bstride, sizeof(StatusRec), hipMemcpyDeviceToHost, c->rs.st));
     else LP_HIP(hipMemcpy2DAsync(c->rs.status_host, sizeof(StatusRec), (const char*)c->p.va.status + (size_t)c->p.bt.first * c->p.bstride, c->p.bstride,
                                  sizeof(StatusRec), (size_t)c->p.B, hipMemcpyDeviceToHost, c->rs.st));
-    if (c->colsplit && c->p.adat.ngroups() > 0)   // a wait kernel that gave up (its producer never ran) says so here
-        LP_HIP(hipMemcpyAsync(c->rs.timeout_host, c->p.adat.wait_timeout, sizeof(unsigned int), hipMemcpyDeviceToHost, c->rs.st));
+    if (c->colsplit && c->p.sys[SYS_WORK].res.ngroups() > 0)   // a wait kernel that gave up (its producer never ran) says so here
+        LP_HIP(hipMemcpyAsync(c->rs.timeout_host, c->p.sys[SYS_WORK].res.wait_timeout, sizeof(unsigned int), hipMemcpyDeviceToHost, c->rs.st));
     return LPIPM_OK;
 }
 
@@ -1381,6 +1389,7 @@ static int copy_status(lpipm_ctx* c) {
 // at once.
 static int enqueue_head(lpipm_ctx* c, const Iter& it) {
     hipStream_t st = c->rs.st;
+    NormalSystem& work = c->p.sys[SYS_WORK];
     VecArgs vh = c->p.va;
     vh.done_chk = c->p.bt_head.done;
     prof_mark(c, T_VEC);
@@ -1389,13 +1398,13 @@ static int enqueue_head(lpipm_ctx* c, const Iter& it) {
     if (c->p.tall) {     // W_s, E_x and t of the predictor's two right-hand sides (c, b), (r1, r_P); then K instead of M
         tall_setup(vh, c->p.tv, true, 2, vh.c, vh.b, vh.r1, vh.rP, st);
         prof_mark(c, T_VEC, true);
-        LP_HIP(run_tall_normal(c, c->p.bt_head));
+        LP_HIP(build_system(c, work, c->p.bt_head));
         prof_mark(c, T_ADAT, true);
         return LPIPM_OK;
     }
     prof_mark(c, T_VEC, true);
     if (it.skip_factor) return LPIPM_OK;          // iteration 1 on a kept factor: its M is already there, factored
-    if (c->colsplit && c->world > 1 && c->p.adat.ngroups() > 0 && c->st_c) {
+    if (c->colsplit && c->world > 1 && work.res.ngroups() > 0 && c->st_c) {
         // n-split, M = sum_g A_g D_g A_g^T, PIPELINED: one A.D.A^T launch in column-group-major order on the solver's stream;
         // the workgroup that completes a group's last tile bumps the group's word; on the communication stream a one-wave
         // kernel waits for that word, the group's tiles are packed, summed over the ranks (the caller's all-reduce) and
@@ -1407,28 +1416,28 @@ static int enqueue_head(lpipm_ctx* c, const Iter& it) {
         hipStream_t sc = c->st_c;
         const Batch& bt = c->p.bt_head;
         // (the launch arms ev_c0 once the group words are zero, in front of its kernel)
-        LP_HIP(launch_adat(c->ap, c->p.adat, adat_launch(c, it, bt), true, st, nullptr, c->ev_c0));
+        LP_HIP(build_system(c, cur_sys(c, it), bt, BuildOpts{.M2 = c->p.M0, .signal_groups = true}));
         LP_HIP(hipStreamWaitEvent(sc, c->ev_c0, 0));
-        for (int g = 0; g < c->p.adat.ngroups(); ++g) {
-            const AdatGroup grp = adat_group(c->p.adat, g);
+        for (int g = 0; g < work.res.ngroups(); ++g) {
+            const AdatGroup grp = adat_group(work.res, g);
             double* slice = c->mpack + (size_t)grp.first * TILE * TILE;
-            LP_HIP(launch_wait_count(grp.word, (unsigned)grp.ntiles, bt.done, c->p.adat.wait_timeout, sc));
-            vec_pack_tiles(c->p.M, c->p.mp, grp.tiles, grp.ntiles, slice, 0, sc);
+            LP_HIP(launch_wait_count(grp.word, (unsigned)grp.ntiles, bt.done, work.res.wait_timeout, sc));
+            vec_pack_tiles(work.M, work.n, grp.tiles, grp.ntiles, slice, 0, sc);
             LP_TRY(ctx_allreduce(c, slice, (uint64_t)grp.ntiles * TILE * TILE, 0, sc));
-            vec_pack_tiles(c->p.M, c->p.mp, grp.tiles, grp.ntiles, slice, 1, sc);
+            vec_pack_tiles(work.M, work.n, grp.tiles, grp.ntiles, slice, 1, sc);
         }
         LP_HIP(hipEventRecord(c->ev_c1, sc));
         LP_HIP(hipStreamWaitEvent(st, c->ev_c1, 0));
-        if (c->refine > 0) vec_copy_lower(c->p.M, c->p.M0, c->p.mp, c->p.mp, st, c->p.bt_head);   // the summed matrix, for the refined solves
+        if (c->refine > 0) vec_copy_lower(work.M, c->p.M0, work.n, work.n, st, c->p.bt_head);   // the summed matrix, for the refined solves
         prof_mark(c, T_ADAT, true);
         return LPIPM_OK;
     }
-    LP_HIP(run_adat(c, it, c->p.bt_head));                                       // newton_equations.rs:55-57
+    LP_HIP(build_system(c, cur_sys(c, it), c->p.bt_head, BuildOpts{.M2 = c->p.M0}));   // newton_equations.rs:55-57
     if (c->colsplit && c->world > 1) {                                     // n-split: M = sum_g A_g D_g A_g^T
-        vec_pack_lower(c->p.M, c->p.mp, c->p.mp, c->mpack, 0, st);
+        vec_pack_lower(work.M, work.n, work.n, c->mpack, 0, st);
         LP_TRY(ctx_allreduce(c, c->mpack, c->mpack_count, 0));
-        vec_pack_lower(c->p.M, c->p.mp, c->p.mp, c->mpack, 1, st);
-        if (c->refine > 0) vec_copy_lower(c->p.M, c->p.M0, c->p.mp, c->p.mp, st, c->p.bt_head);   // the summed matrix, for the refined solves
+        vec_pack_lower(work.M, work.n, work.n, c->mpack, 1, st);
+        if (c->refine > 0) vec_copy_lower(work.M, c->p.M0, work.n, work.n, st, c->p.bt_head);   // the summed matrix, for the refined solves
     }
     prof_mark(c, T_ADAT, true);
     return LPIPM_OK;
@@ -1450,7 +1459,7 @@ struct PredictorBeside {
         VecArgs& v = c->p.va;
         if (sb < 0) return ctx_gemv_n(c, 2, v.W, v.b, v.rP, v.R, c->p.bt, side);     // :220
         b->fwd_done = sb + 1;
-        return launch_chol_solve(cur_M(c, b->it), c->p.mp, cur_factor(c, b->it), 2, v.R, c->p.Y, side, c->p.bt, SolveSteps{sb, sb + 1, false}, cur_shared(c, b->it));
+        return launch_chol_solve(*cur_sys(c, b->it).factor, 2, v.R, c->p.Y, side, c->p.bt, SolveSteps{sb, sb + 1, false}, shared_first(c, b->it));
     }
 };
 
@@ -1462,7 +1471,7 @@ static int enqueue_tail_tall(lpipm_ctx* c, int ip, const lpipm_opts* o) {
     const TallArgs& t = c->p.tv;
     hipStream_t st = c->rs.st;
     const Batch& bt = c->p.bt;
-    LP_HIP(launch_potrf(c->p.M, t.nxp, t.nxp, *c->p.factor, v.potrf_info, st, bt, lookahead(c), false, nullptr));   // :129-131
+    LP_HIP(launch_potrf(*c->p.sys[SYS_WORK].factor, v.potrf_info, st, bt, lookahead(c), false, nullptr));   // :129-131
     if (c->p.tall_eq) LP_TRY(tall_eq_schur(c));                                // Zt, S and its factor
     prof_mark(c, T_POTRF);
     LP_TRY(tall_sym_solve(c, 2, v.c, v.b, v.r1, v.rP, bt));                    // :187-188
@@ -1492,18 +1501,18 @@ static int enqueue_tail(lpipm_ctx* c, const Iter& it, int ip, const lpipm_opts* 
     const XRank* xr = c->colsplit ? &xr_ : nullptr;
     const Batch& bt = c->p.bt;
     const bool chol = o->solver_type == LPIPM_SOLVER_CHOLESKY;
+    const NormalSystem& sys = cur_sys(c, it);     // (the QR arms keep no first factor: the working system)
     // (no clearing of the pivot-failure word: k_blind_start and every k_scalar_indicators leave it zero)
     // a single LP whose factorisation runs with the look-ahead: the predictor's pass and the first forward steps of its
     // solve go beside the chain (launch_potrf decides whether the look-ahead applies; the serial order otherwise)
     PredictorBeside pb{c, it};
     PotrfBeside beside{PredictorBeside::at, &pb};
     const bool may_beside = chol && !c->colsplit && bt.count == 1 && c->refine <= 0;
-    if (it.skip_factor) LP_HIP(copy_info(c, v.potrf_info, c->p.info1));   // the kept factor's pivot failure, if it had one
+    if (it.skip_factor) LP_HIP(copy_info(c, v.potrf_info, c->p.sys[SYS_FIRST].info));   // the kept factor's pivot failure, if it had one
     else {
-        if (chol) LP_HIP(launch_potrf(cur_M(c, it), c->p.mp, c->p.mp, cur_factor(c, it), v.potrf_info, st, bt, lookahead(c), false,
-                                      may_beside ? &beside : nullptr));   // :129-131
-        else      LP_HIP(launch_qr_factor(c->p.M, c->p.mp, c->p.mp, c->p.tau, v.potrf_info, st));        // :133-149
-        if (it.on_first) LP_HIP(copy_info(c, c->p.info1, v.potrf_info));  // kept with the factor it belongs to
+        if (chol) LP_HIP(launch_potrf(*sys.factor, v.potrf_info, st, bt, lookahead(c), false, may_beside ? &beside : nullptr));   // :129-131
+        else      LP_HIP(launch_qr_factor(sys.M, sys.n, sys.n, c->p.tau, v.potrf_info, st));        // :133-149
+        if (it.on_first) LP_HIP(copy_info(c, c->p.sys[SYS_FIRST].info, v.potrf_info));  // kept with the factor it belongs to
         prof_mark(c, T_POTRF);
     }
     // predictor: both sym_solve calls of solve_newton_equations (:187-188) in one pass each
@@ -1516,9 +1525,9 @@ static int enqueue_tail(lpipm_ctx* c, const Iter& it, int ip, const lpipm_opts* 
         vec_add_rows((int)c->p.m, 2, v.R, c->p.mp, v.b, v.rP, st);
     }
     prof_mark(c, T_GEMV);
-    if (beside.calls > 0) LP_HIP(launch_chol_solve(cur_M(c, it), c->p.mp, cur_factor(c, it), 2, v.R, c->p.Y, st, bt, SolveSteps{pb.fwd_done, -1, true}, cur_shared(c, it)));
+    if (beside.calls > 0) LP_HIP(launch_chol_solve(*sys.factor, 2, v.R, c->p.Y, st, bt, SolveSteps{pb.fwd_done, -1, true}, shared_first(c, it)));
     else if (chol) LP_TRY(chol_solve_refined(c, it, 2, v.R, bt));                               // :221, :154
-    else      LP_HIP(launch_qr_solve(c->p.M, c->p.mp, c->p.mp, c->p.tau, 2, v.R, v.potrf_info, st));   // :155-166
+    else      LP_HIP(launch_qr_solve(sys.M, sys.n, sys.n, c->p.tau, 2, v.R, v.potrf_info, st));   // :155-166
     prof_mark(c, T_TRSV);
     LP_HIP(ctx_gemv_t(c, 2, v.R, bt));              // :223
     prof_mark(c, T_GEMV);
@@ -1539,7 +1548,7 @@ static int enqueue_tail(lpipm_ctx* c, const Iter& it, int ip, const lpipm_opts* 
     }
     prof_mark(c, T_GEMV);
     if (chol) LP_TRY(chol_solve_refined(c, it, 1, v.R, bt));
-    else      LP_HIP(launch_qr_solve(c->p.M, c->p.mp, c->p.mp, c->p.tau, 1, v.R, v.potrf_info, st));
+    else      LP_HIP(launch_qr_solve(sys.M, sys.n, sys.n, c->p.tau, 1, v.R, v.potrf_info, st));
     prof_mark(c, T_TRSV);
     LP_HIP(ctx_gemv_t(c, 1, v.R, bt));
     prof_mark(c, T_GEMV);
@@ -1576,7 +1585,7 @@ static int ensure_shared_factor(lpipm_ctx* c, const lpipm_opts* o) {
     LP_HIP(hipSetDevice(c->device));
     hipStream_t st = c->rs.st;
     const Batch one{1, (long long)c->p.bstride, nullptr, 0};
-    const Iter first{.on_first = true};
+    const NormalSystem& first = c->p.sys[SYS_FIRST];
     const bool timed = c->profiling != 0;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     auto drop_events = [&]() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
@@ -1585,14 +1594,11 @@ static int ensure_shared_factor(lpipm_ctx* c, const lpipm_opts* o) {
             if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); drop_events(); g_err_detail = "failed to create events"; return LPIPM_ERR_HIP; }
     auto enqueue = [&]() -> int {
         if (timed) LP_HIP(hipEventRecord(ev[0], st));
-        AdatRes res = c->p.adat;
-        res.counters_dirty = true;
-        AdatLaunch a = adat_launch(c, first, one);          // into M1 (the shared A; no second copy: nothing refines here)
-        a.dinv = c->p.ones;
-        LP_HIP(launch_adat(c->ap, res, a, false, st, nullptr));
-        LP_HIP(launch_slack_diag(c->p.ns, c->p.nx, c->p.ones, cur_M(c, first), c->p.mp, st, one));   // + I on the slack rows
+        NormalSystem build = c->p.sys[SYS_WORK];            // the working system's launch with a private dirty mark, into M1
+        build.M = first.M; build.res.counters_dirty = true;
+        LP_HIP(build_system(c, build, one, BuildOpts{.dinv = c->p.ones}));   // (+ I on the slack rows; nothing refines here)
         if (timed) LP_HIP(hipEventRecord(ev[1], st));
-        LP_HIP(launch_potrf(cur_M(c, first), c->p.mp, c->p.mp, cur_factor(c, first), c->p.info1, st, one, nullptr, true, nullptr));
+        LP_HIP(launch_potrf(*first.factor, first.info, st, one, nullptr, true, nullptr));
         if (timed) LP_HIP(hipEventRecord(ev[2], st));
         LP_HIP(hipStreamSynchronize(st));
         return LPIPM_OK;
@@ -1816,7 +1822,7 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, Members members, con
         }
         ++loop_iterations;
         if (iteration == 1) { c->first_done = true; if (use_first) c->first_valid = true; }
-        if (c->colsplit && c->p.adat.ngroups() > 0 && *rs.timeout_host != 0) {
+        if (c->colsplit && c->p.sys[SYS_WORK].res.ngroups() > 0 && *rs.timeout_host != 0) {
             g_err_detail = "a column group of A.D.A^T did not complete within the wait kernel's bound";
             LP_HIP(hipStreamSynchronize(st));
             return LPIPM_ERR_HIP;
@@ -1891,15 +1897,14 @@ static void destroy_views(lpipm_ctx* c) {
     c->halves.clear();
 }
 // A view of the LPs [first, first + count) of c's resident batch: a copy of the problem (the same device state: every pointer
-// stays LP 0's) and of the A.D.A^T plan, and its own stream, events and pinned status records.
+// stays LP 0's; its systems carry their plans), and its own stream, events and pinned status records.
 static lpipm_ctx* make_view(const lpipm_ctx* c, int first, int count) {
     lpipm_ctx* v = new lpipm_ctx();
     if (stream_res_create(v->rs, (size_t)count) != LPIPM_OK) { delete v; return nullptr; }
     v->is_view = true;
     v->device = c->device; v->num_cu = c->num_cu; v->refine = c->refine;
-    v->ap = c->ap; v->ap_s = c->ap_s;
     v->p = c->p;
-    v->p.adat.counters_dirty = v->p.adat_s.counters_dirty = true;     // whatever the parent's state: this view's stream has not launched yet
+    for (NormalSystem& s : v->p.sys) s.res.counters_dirty = true;     // whatever the parent's state: this view's stream has not launched yet
     v->p.B = count;
     v->p.bt = Batch{count, (long long)c->p.bstride, c->p.va.done, first};
     v->p.bt_head = v->p.bt;
@@ -1948,7 +1953,9 @@ static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const SolveOut& out
 
 extern "C" int lpipm_get_resident_bytes(const lpipm_ctx* c, uint64_t* bytes_out) {
     if (!c || !bytes_out) return LPIPM_ERR_BAD_ARGUMENT;
-    *bytes_out = c->p.has_problem ? (uint64_t)(c->p.arena_bytes + c->p.a_shared_bytes + c->p.adat.list_bytes + c->p.adat_s.list_bytes + c->p.scale_bytes) : 0;
+    size_t lists = 0;
+    for (const NormalSystem& s : c->p.sys) lists += s.res.list_bytes;
+    *bytes_out = c->p.has_problem ? (uint64_t)(c->p.arena_bytes + c->p.a_shared_bytes + lists + c->p.scale_bytes) : 0;
     return LPIPM_OK;
 }
 extern "C" int lpipm_solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, double* const* x_slack_out, double* fun_out,
@@ -1991,10 +1998,10 @@ static size_t lockstep_bytes_per_lp(const lpipm_ctx* c, const BatchRequest& q, u
     const Geometry g = geometry_of(Upload{.count = 32, .m = m, .n = n, .tall = q.tall, .keep_ok = false}, q.tall ? m : n_slack, c->first_cache, c->refine);
     Problem t;
     set_geometry(t, g);
-    FactorPlan fp, fp1, fps;
+    plan_builds(t, c);
+    FactorPlan plans[SYS_COUNT];
     Arena measure;
-    if (layout_problem(t, fp, fp1, fps, adat_plan_of(g, c->num_cu, c->world, c->units_env), AdatPlan{}, c->refine, measure, false, nullptr) != LPIPM_OK)
-        return (size_t)-1;
+    if (layout_problem(t, plans, c->refine, measure, false, nullptr) != LPIPM_OK) return (size_t)-1;
     return (size_t)round_up(measure.off, 4096);
 }
 
@@ -2450,19 +2457,28 @@ extern "C" int lpipm_k_adat(lpipm_ctx* c, const double* dinv, double* M_out, int
     if (c->p.tall) return LPIPM_ERR_UNSUPPORTED;           // a tall upload has no M (lpipm_k_tall_normal returns K)
     LP_HIP(hipSetDevice(c->device));
     LP_HIP(hipMemcpyAsync(c->p.va.dinv, dinv, c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
-    LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int { LP_HIP(run_adat(c, Iter{}, Batch{})); return LPIPM_OK; }));
-    LP_HIP(hipMemcpy2DAsync(M_out, c->p.m * sizeof(double), c->p.M, (size_t)c->p.mp * sizeof(double),
+    LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int { LP_HIP(build_system(c, c->p.sys[SYS_WORK], Batch{}, BuildOpts{.M2 = c->p.M0})); return LPIPM_OK; }));
+    LP_HIP(hipMemcpy2DAsync(M_out, c->p.m * sizeof(double), c->p.sys[SYS_WORK].M, (size_t)c->p.mp * sizeof(double),
                             c->p.m * sizeof(double), c->p.m, hipMemcpyDeviceToHost, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
 }
 
-// The iterate the tall kernel entries work from: x = dinv, z = 1, so that W_s = 1 / dinv_s and E_x = 1 / dinv_x.
-static int tall_entry_iterate(lpipm_ctx* c, const double* dinv) {
+// What the tall kernel entries start from: the iterate x = dinv, z = 1 (so that W_s = 1 / dinv_s and E_x = 1 / dinv_x), W_s, E_x
+// and t of the nrhs given right-hand sides, K built and, `factor`, factored.  Ahead of a reduced solve (nrhs > 0): tall_eq_reset.
+static int tall_entry_system(lpipm_ctx* c, const double* dinv, bool factor, int nrhs = 0, const double* r1 = nullptr,
+                             const double* r2 = nullptr, const double* r1b = nullptr, const double* r2b = nullptr) {
+    hipStream_t st = c->rs.st;
+    NormalSystem& K = c->p.sys[SYS_WORK];
     const std::vector<double> ones((size_t)c->p.n, 1.0);
-    LP_HIP(hipMemcpyAsync(c->p.va.x, dinv, c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
-    LP_HIP(hipMemcpyAsync(c->p.va.z, ones.data(), c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
-    LP_HIP(hipStreamSynchronize(c->rs.st));      // `ones` goes out of scope
+    vec_blind_start(c->p.va, st);                  // clears done / flags; the iterate is overwritten next
+    if (nrhs > 0) LP_TRY(tall_eq_reset(c));
+    LP_HIP(hipMemcpyAsync(c->p.va.x, dinv, c->p.n * sizeof(double), hipMemcpyHostToDevice, st));
+    LP_HIP(hipMemcpyAsync(c->p.va.z, ones.data(), c->p.n * sizeof(double), hipMemcpyHostToDevice, st));
+    LP_HIP(hipStreamSynchronize(st));              // `ones` goes out of scope
+    tall_setup(c->p.va, c->p.tv, true, nrhs, r1, r2, r1b, r2b, st);
+    LP_HIP(build_system(c, K, Batch{}));
+    if (factor) LP_HIP(launch_potrf(*K.factor, K.info, st, Batch{}, nullptr, true, nullptr));
     return LPIPM_OK;
 }
 extern "C" int lpipm_k_tall_normal(lpipm_ctx* c, const double* dinv, double* K_out) {
@@ -2470,12 +2486,9 @@ extern "C" int lpipm_k_tall_normal(lpipm_ctx* c, const double* dinv, double* K_o
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
     if (!c->p.tall || c->p.shared_a || c->p.owned_tall) return LPIPM_ERR_UNSUPPORTED;     // (a single tall upload, not a batch)
     LP_HIP(hipSetDevice(c->device));
-    vec_blind_start(c->p.va, c->rs.st);                       // clears done / flags; the iterate is overwritten next
-    LP_TRY(tall_entry_iterate(c, dinv));
-    tall_setup(c->p.va, c->p.tv, true, 0, nullptr, nullptr, nullptr, nullptr, c->rs.st);
-    LP_HIP(run_tall_normal(c, Batch{}));
+    LP_TRY(tall_entry_system(c, dinv, false));
     const size_t nx = (size_t)c->p.nx;
-    LP_HIP(hipMemcpy2DAsync(K_out, nx * sizeof(double), c->p.M, (size_t)c->p.tv.nxp * sizeof(double), nx * sizeof(double), nx,
+    LP_HIP(hipMemcpy2DAsync(K_out, nx * sizeof(double), c->p.sys[SYS_WORK].M, (size_t)c->p.tv.nxp * sizeof(double), nx * sizeof(double), nx,
                             hipMemcpyDeviceToHost, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
@@ -2487,14 +2500,10 @@ extern "C" int lpipm_k_tall_schur(lpipm_ctx* c, const double* dinv, double* S_ou
     LP_HIP(hipSetDevice(c->device));
     hipStream_t st = c->rs.st;
     const TallArgs& t = c->p.tv;
-    vec_blind_start(c->p.va, st);
-    LP_TRY(tall_entry_iterate(c, dinv));
-    tall_setup(c->p.va, t, true, 0, nullptr, nullptr, nullptr, nullptr, st);
-    LP_HIP(run_tall_normal(c, Batch{}));
-    LP_HIP(launch_potrf(c->p.M, t.nxp, t.nxp, *c->p.factor, c->p.va.potrf_info, st, Batch{}, nullptr, true, nullptr));
+    LP_TRY(tall_entry_system(c, dinv, true));
     LP_TRY(tall_eq_schur(c, false));
     const size_t me = (size_t)t.me;
-    LP_HIP(hipMemcpy2DAsync(S_out, me * sizeof(double), c->p.S, (size_t)t.mep * sizeof(double), me * sizeof(double), me,
+    LP_HIP(hipMemcpy2DAsync(S_out, me * sizeof(double), c->p.sys[SYS_SCHUR].M, (size_t)t.mep * sizeof(double), me * sizeof(double), me,
                             hipMemcpyDeviceToHost, st));
     LP_HIP(hipMemsetAsync(c->p.va.potrf_info, 0, sizeof(int32_t), st));      // the solver expects a clean word
     LP_HIP(hipStreamSynchronize(st));
@@ -2520,14 +2529,9 @@ extern "C" int lpipm_k_tall_sym_solve(lpipm_ctx* c, const double* dinv, int nrhs
         LP_HIP(hipMemsetAsync(rhs, 0, 2 * (np + mp) * sizeof(double), st));
         LP_HIP(hipMemcpy2DAsync(r1, np * sizeof(double), R1, n * sizeof(double), n * sizeof(double), (size_t)nrhs, hipMemcpyHostToDevice, st));
         LP_HIP(hipMemcpy2DAsync(r2, mp * sizeof(double), R2, m * sizeof(double), m * sizeof(double), (size_t)nrhs, hipMemcpyHostToDevice, st));
-        vec_blind_start(v, st);
-        LP_TRY(tall_eq_reset(c));
-        LP_TRY(tall_entry_iterate(c, dinv));
         const double* r1b = nrhs == 2 ? r1 + np : nullptr;
         const double* r2b = nrhs == 2 ? r2 + mp : nullptr;
-        tall_setup(v, t, true, nrhs, r1, r2, r1b, r2b, st);
-        LP_HIP(run_tall_normal(c, Batch{}));
-        LP_HIP(launch_potrf(c->p.M, t.nxp, t.nxp, *c->p.factor, v.potrf_info, st, Batch{}, nullptr, true, nullptr));
+        LP_TRY(tall_entry_system(c, dinv, true, nrhs, r1, r2, r1b, r2b));
         if (c->p.tall_eq) LP_TRY(tall_eq_schur(c));
         LP_TRY(tall_sym_solve(c, nrhs, r1, r2, r1b, r2b, Batch{}));
         if (nrhs == 2) tall_pq_uv(v, t, r1, r1b, st);
@@ -2549,26 +2553,35 @@ extern "C" int lpipm_k_tall_sym_solve(lpipm_ctx* c, const double* dinv, int nrhs
     return rc;
 }
 
+// dst (mp x mp, zeroed) <- [[M, 0], [0, I]] from the host's m x m M; pad: mp - m ones, which must outlive the copies
+static hipError_t copy_padded(double* dst, int mp, const double* M, size_t m, const std::vector<double>& pad, hipStream_t st) {
+    const size_t D = sizeof(double);
+    const hipError_t e = hipMemcpy2DAsync(dst, (size_t)mp * D, M, m * D, m * D, m, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess || (size_t)mp == m) return e;
+    return hipMemcpy2DAsync(dst + m * mp + m, (size_t)(mp + 1) * D, pad.data(), D, D, mp - m, hipMemcpyHostToDevice, st);
+}
 static int kbuf_ensure(lpipm_ctx* c, int mp) {
-    if (c->kmp == mp) return LPIPM_OK;
-    LP_HIP(hipStreamSynchronize(c->rs.st));
-    free_list(c->kallocs);
-    factor_plan_destroy(c->kplan);
-    c->kmp = 0;
-    LP_TRY(dalloc(c->kallocs, nullptr, &c->kM, (size_t)mp * mp, c->rs.st));
-    LP_TRY(dalloc(c->kallocs, nullptr, &c->kM0, (size_t)mp * mp, c->rs.st));
-    LP_TRY(dalloc(c->kallocs, nullptr, &c->kR, (size_t)2 * mp, c->rs.st));
-    LP_TRY(dalloc(c->kallocs, nullptr, &c->kY, (size_t)2 * mp, c->rs.st));
-    LP_TRY(dalloc(c->kallocs, nullptr, &c->kinfo, 1, c->rs.st));
-    LP_TRY(dalloc(c->kallocs, nullptr, &c->ktau, (size_t)mp, c->rs.st));
+    lpipm_ctx::KernelScratch& k = c->k;
+    if (k.mp == mp) return LPIPM_OK;
+    hipStream_t st = c->rs.st;
+    LP_HIP(hipStreamSynchronize(st));
+    free_list(k.allocs);
+    factor_plan_destroy(k.plan);
+    k.mp = 0; k.chol_valid = false;
+    double* M = nullptr;
+    LP_TRY(dalloc(k.allocs, nullptr, &M, (size_t)mp * mp, st));
+    LP_TRY(dalloc(k.allocs, nullptr, &k.M0, (size_t)mp * mp, st));
+    LP_TRY(dalloc(k.allocs, nullptr, &k.R, (size_t)2 * mp, st));
+    LP_TRY(dalloc(k.allocs, nullptr, &k.Y, (size_t)2 * mp, st));
+    LP_TRY(dalloc(k.allocs, nullptr, &k.info, 1, st));
+    LP_TRY(dalloc(k.allocs, nullptr, &k.tau, (size_t)mp, st));
     Arena measure;
-    LP_HIP(factor_plan_create(c->kplan, c->kM, mp, mp, measure, false, c->rs.st, super_for(mp), merge_edge_for(1), nullptr, coupled_for(mp, true), couple_edge_for()));
+    LP_HIP(factor_plan_create(k.plan, M, mp, mp, measure, false, st, super_for(mp), merge_edge_for(1), nullptr, coupled_for(mp, true), couple_edge_for()));
     char* kar = nullptr;
-    LP_TRY(dalloc(c->kallocs, nullptr, &kar, measure.off + 256, c->rs.st));   // zeroed
-    Arena real;
-    real.base = kar;
-    LP_HIP(factor_plan_create(c->kplan, c->kM, mp, mp, real, true, c->rs.st, super_for(mp), merge_edge_for(1), nullptr, coupled_for(mp, true), couple_edge_for()));
-    c->kmp = mp;
+    LP_TRY(dalloc(k.allocs, nullptr, &kar, measure.off + 256, st));   // zeroed
+    Arena real{kar};
+    LP_HIP(factor_plan_create(k.plan, M, mp, mp, real, true, st, super_for(mp), merge_edge_for(1), nullptr, coupled_for(mp, true), couple_edge_for()));
+    k.mp = mp;
     return LPIPM_OK;
 }
 
@@ -2580,19 +2593,15 @@ extern "C" int lpipm_k_potrf(lpipm_ctx* c, uint64_t m, double* M_inout, int32_t*
     LP_TRY(kbuf_ensure(c, mp));
     // padded pristine copy: [[M, 0], [0, I]]
     std::vector<double> pad((size_t)(mp - m), 1.0);
-    LP_HIP(hipMemsetAsync(c->kM0, 0, (size_t)mp * mp * sizeof(double), c->rs.st));
-    LP_HIP(hipMemcpy2DAsync(c->kM0, (size_t)mp * sizeof(double), M_inout, m * sizeof(double), m * sizeof(double),
-                            m, hipMemcpyHostToDevice, c->rs.st));
-    if (mp > (int)m)
-        LP_HIP(hipMemcpy2DAsync(c->kM0 + m * mp + m, (size_t)(mp + 1) * sizeof(double), pad.data(), sizeof(double),
-                                sizeof(double), mp - m, hipMemcpyHostToDevice, c->rs.st));
+    LP_HIP(hipMemsetAsync(c->k.M0, 0, (size_t)mp * mp * sizeof(double), c->rs.st));
+    LP_HIP(copy_padded(c->k.M0, mp, M_inout, m, pad, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     if (repeats < 1) repeats = 1;
     float total = 0.f;
     for (int r = 0; r < repeats; ++r) {
-        LP_HIP(hipMemcpyAsync(c->kM, c->kM0, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToDevice, c->rs.st));
+        LP_HIP(hipMemcpyAsync(c->k.plan.L, c->k.M0, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToDevice, c->rs.st));
         LP_HIP(hipEventRecord(c->rs.ev_begin, c->rs.st));
-        LP_HIP(launch_potrf(c->kM, mp, mp, c->kplan, c->kinfo, c->rs.st, Batch{}, lookahead(c)));
+        LP_HIP(launch_potrf(c->k.plan, c->k.info, c->rs.st, Batch{}, lookahead(c)));
         LP_HIP(hipEventRecord(c->rs.ev_end, c->rs.st));
         LP_HIP(hipStreamSynchronize(c->rs.st));
         float ms = 0.f;
@@ -2605,8 +2614,8 @@ extern "C" int lpipm_k_potrf(lpipm_ctx* c, uint64_t m, double* M_inout, int32_t*
         if (hipMalloc((void**)&d, sizeof(h)) == hipSuccess) {
             g_diag_stamps = d;
             (void)hipMemset(d, 0, sizeof(h));
-            (void)hipMemcpyAsync(c->kM, c->kM0, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToDevice, c->rs.st);
-            (void)launch_potrf(c->kM, mp, mp, c->kplan, c->kinfo, c->rs.st);
+            (void)hipMemcpyAsync(c->k.plan.L, c->k.M0, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToDevice, c->rs.st);
+            (void)launch_potrf(c->k.plan, c->k.info, c->rs.st);
             (void)hipStreamSynchronize(c->rs.st);
             g_diag_stamps = nullptr;
             (void)hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
@@ -2621,29 +2630,29 @@ extern "C" int lpipm_k_potrf(lpipm_ctx* c, uint64_t m, double* M_inout, int32_t*
         }
     }
     int32_t info = 0;
-    LP_HIP(hipMemcpyAsync(&info, c->kinfo, sizeof(int32_t), hipMemcpyDeviceToHost, c->rs.st));
-    LP_HIP(hipMemcpy2DAsync(M_inout, m * sizeof(double), c->kM, (size_t)mp * sizeof(double), m * sizeof(double), m,
+    LP_HIP(hipMemcpyAsync(&info, c->k.info, sizeof(int32_t), hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(hipMemcpy2DAsync(M_inout, m * sizeof(double), c->k.plan.L, (size_t)mp * sizeof(double), m * sizeof(double), m,
                             hipMemcpyDeviceToHost, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     if (info_out) *info_out = info;
-    c->kchol_valid = true;
+    c->k.chol_valid = true;
     return LPIPM_OK;
 }
 
 extern "C" int lpipm_k_factor_inverses(lpipm_ctx* c, uint64_t m, double* inv_out, double* invT_out, int32_t* super_w_out) {
     if (!c || !inv_out || !invT_out) return LPIPM_ERR_BAD_ARGUMENT;
     const int mp = (int)round_up(m, NB);
-    if (c->kmp != mp || !c->kchol_valid) return LPIPM_ERR_NO_PROBLEM;  // needs a preceding lpipm_k_potrf of this size
+    if (c->k.mp != mp || !c->k.chol_valid) return LPIPM_ERR_NO_PROBLEM;  // needs a preceding lpipm_k_potrf of this size
     LP_HIP(hipSetDevice(c->device));
     std::fill(inv_out, inv_out + (size_t)mp * mp, 0.0);
     std::fill(invT_out, invT_out + (size_t)mp * mp, 0.0);
-    for (const SuperBlock& s : c->kplan.sbs) {
+    for (const SuperBlock& s : c->k.plan.sbs) {
         const size_t row = (size_t)s.size * sizeof(double), at = (size_t)s.row0 * mp + s.row0;
         LP_HIP(hipMemcpy2DAsync(inv_out + at, (size_t)mp * sizeof(double), s.inv, row, row, s.size, hipMemcpyDeviceToHost, c->rs.st));
         LP_HIP(hipMemcpy2DAsync(invT_out + at, (size_t)mp * sizeof(double), s.invT, row, row, s.size, hipMemcpyDeviceToHost, c->rs.st));
     }
     LP_HIP(hipStreamSynchronize(c->rs.st));
-    if (super_w_out) *super_w_out = c->kplan.super_w;
+    if (super_w_out) *super_w_out = c->k.plan.super_w;
     return LPIPM_OK;
 }
 
@@ -2667,19 +2676,14 @@ extern "C" int lpipm_k_potrf_lockstep(lpipm_ctx* c, uint64_t m, int count, doubl
     LP_HIP(hipMalloc((void**)&base, stride * (size_t)count));
     // every failure leaves through the one exit below, which frees the plan and the buffer
     hipError_t e = hipMemsetAsync(base, 0, stride * (size_t)count, st);
-    Arena real;
-    real.base = base;
+    Arena real{base};
     if (e == hipSuccess) e = layout(real, true, &M0, &info0);
     const std::vector<double> pad((size_t)(mp - m), 1.0);
     for (int q = 0; q < count && e == hipSuccess; ++q) {          // padded copies: [[M, 0], [0, I]]
         double* Mq = (double*)((char*)M0 + (size_t)q * stride);
-        e = hipMemcpy2DAsync(Mq, (size_t)mp * sizeof(double), Ms_inout + (size_t)q * m * m, m * sizeof(double), m * sizeof(double),
-                             m, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && mp > (int)m)
-            e = hipMemcpy2DAsync(Mq + m * mp + m, (size_t)(mp + 1) * sizeof(double), pad.data(), sizeof(double), sizeof(double),
-                                 mp - m, hipMemcpyHostToDevice, st);
+        e = copy_padded(Mq, mp, Ms_inout + (size_t)q * m * m, m, pad, st);
     }
-    if (e == hipSuccess) e = launch_potrf(M0, mp, mp, plan, info0, st, Batch{count, (long long)stride, nullptr, 0});
+    if (e == hipSuccess) e = launch_potrf(plan, info0, st, Batch{count, (long long)stride, nullptr, 0});
     for (int q = 0; q < count && e == hipSuccess; ++q) {
         e = hipMemcpy2DAsync(Ms_inout + (size_t)q * m * m, m * sizeof(double), (char*)M0 + (size_t)q * stride, (size_t)mp * sizeof(double),
                              m * sizeof(double), m, hipMemcpyDeviceToHost, st);
@@ -2723,8 +2727,7 @@ extern "C" int lpipm_k_trsm_lt_lockstep(lpipm_ctx* c, uint64_t n, int count, int
     LP_HIP(hipMalloc((void**)&base, stride * (size_t)count));
     // every failure leaves through the one exit below, which frees the plan and the buffer
     hipError_t e = hipMemsetAsync(base, 0, stride * (size_t)count, st);
-    Arena real;
-    real.base = base;
+    Arena real{base};
     if (e == hipSuccess) e = layout(real, true);
     const std::vector<double> pad((size_t)(mp - n), 1.0);
     std::vector<int> done((size_t)count, 0);
@@ -2732,18 +2735,16 @@ extern "C" int lpipm_k_trsm_lt_lockstep(lpipm_ctx* c, uint64_t n, int count, int
     for (int q = 0; q < count && e == hipSuccess; ++q) {          // padded copies: [[M, 0], [0, I]]
         const size_t off = (size_t)q * stride;
         double* Mq = (double*)((char*)at.M + off);
-        e = hipMemcpy2DAsync(Mq, (size_t)mp * D, Ms + (size_t)q * n * n, n * D, n * D, n, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && mp > (int)n)
-            e = hipMemcpy2DAsync(Mq + n * mp + n, (size_t)(mp + 1) * D, pad.data(), D, D, mp - n, hipMemcpyHostToDevice, st);
+        e = copy_padded(Mq, mp, Ms + (size_t)q * n * n, n, pad, st);
         if (e == hipSuccess && (q == 0 || !shared_b))
             e = hipMemcpy2DAsync((char*)at.Bm + off, (size_t)cols * D, B + (size_t)q * rows * ldb, ldb * D, (size_t)cols * D, (size_t)rows,
                                  hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync((char*)at.Z + off, Z_inout + (size_t)q * rp * mp, (size_t)rp * mp * D, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync((char*)at.done + off, &done[(size_t)q], sizeof(int), hipMemcpyHostToDevice, st);
     }
-    if (e == hipSuccess) e = launch_potrf(at.M, mp, mp, plan, at.info, st, Batch{count, (long long)stride, nullptr, 0});
+    if (e == hipSuccess) e = launch_potrf(plan, at.info, st, Batch{count, (long long)stride, nullptr, 0});
     if (e == hipSuccess)
-        e = launch_trsm_lt(at.Bm, cols, rows, cols, at.M, mp, plan, at.Z, mp, st,
+        e = launch_trsm_lt(at.Bm, cols, rows, cols, plan, at.Z, mp, st,
                            Batch{count, (long long)stride, done_mask ? at.done : nullptr, 0}, shared_b != 0);
     for (int q = 0; q < count && e == hipSuccess; ++q) {
         const size_t off = (size_t)q * stride;
@@ -2762,20 +2763,20 @@ extern "C" int lpipm_k_trsm_lt_lockstep(lpipm_ctx* c, uint64_t n, int count, int
 static int k_chol_solve_impl(lpipm_ctx* c, uint64_t m, int nrhs, const double* R, double* V, int repeats, double* ms_out, int split) {
     if (!c || !R || !V || (nrhs != 1 && nrhs != 2)) return LPIPM_ERR_BAD_ARGUMENT;
     const int mp = (int)round_up(m, NB);
-    if (c->kmp != mp || !c->kchol_valid) return LPIPM_ERR_NO_PROBLEM;  // needs a preceding lpipm_k_potrf of this size
+    if (c->k.mp != mp || !c->k.chol_valid) return LPIPM_ERR_NO_PROBLEM;  // needs a preceding lpipm_k_potrf of this size
     LP_HIP(hipSetDevice(c->device));
     if (repeats < 1) repeats = 1;
     float total = 0.f;
     for (int r = 0; r < repeats; ++r) {
-        LP_HIP(hipMemsetAsync(c->kR, 0, (size_t)2 * mp * sizeof(double), c->rs.st));
-        LP_HIP(hipMemcpy2DAsync(c->kR, (size_t)mp * sizeof(double), R, m * sizeof(double), m * sizeof(double), nrhs,
+        LP_HIP(hipMemsetAsync(c->k.R, 0, (size_t)2 * mp * sizeof(double), c->rs.st));
+        LP_HIP(hipMemcpy2DAsync(c->k.R, (size_t)mp * sizeof(double), R, m * sizeof(double), m * sizeof(double), nrhs,
                                 hipMemcpyHostToDevice, c->rs.st));
         LP_HIP(hipEventRecord(c->rs.ev_begin, c->rs.st));
-        if (split < 0) LP_HIP(launch_chol_solve(c->kM, mp, c->kplan, nrhs, c->kR, c->kY, c->rs.st));
+        if (split < 0) LP_HIP(launch_chol_solve(c->k.plan, nrhs, c->k.R, c->k.Y, c->rs.st));
         else {
-            const int k = split < (int)c->kplan.sbs.size() ? split : (int)c->kplan.sbs.size();
-            LP_HIP(launch_chol_solve(c->kM, mp, c->kplan, nrhs, c->kR, c->kY, c->rs.st, Batch{}, SolveSteps{0, k, false}));
-            LP_HIP(launch_chol_solve(c->kM, mp, c->kplan, nrhs, c->kR, c->kY, c->rs.st, Batch{}, SolveSteps{k, -1, true}));
+            const int k = split < (int)c->k.plan.sbs.size() ? split : (int)c->k.plan.sbs.size();
+            LP_HIP(launch_chol_solve(c->k.plan, nrhs, c->k.R, c->k.Y, c->rs.st, Batch{}, SolveSteps{0, k, false}));
+            LP_HIP(launch_chol_solve(c->k.plan, nrhs, c->k.R, c->k.Y, c->rs.st, Batch{}, SolveSteps{k, -1, true}));
         }
         LP_HIP(hipEventRecord(c->rs.ev_end, c->rs.st));
         LP_HIP(hipStreamSynchronize(c->rs.st));
@@ -2784,7 +2785,7 @@ static int k_chol_solve_impl(lpipm_ctx* c, uint64_t m, int nrhs, const double* R
         total += ms;
     }
     if (ms_out) *ms_out = total / repeats;
-    LP_HIP(hipMemcpy2DAsync(V, m * sizeof(double), c->kR, (size_t)mp * sizeof(double), m * sizeof(double), nrhs,
+    LP_HIP(hipMemcpy2DAsync(V, m * sizeof(double), c->k.R, (size_t)mp * sizeof(double), m * sizeof(double), nrhs,
                             hipMemcpyDeviceToHost, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
@@ -2846,11 +2847,11 @@ extern "C" int lpipm_k_symv_residual(lpipm_ctx* c, uint64_t m, const double* M, 
     hipError_t e = hipMalloc((void**)&ws, symv_slab_doubles(mp) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&vbuf, (size_t)6 * mp * sizeof(double));
     if (e == hipSuccess) e = hipMemsetAsync(vbuf, 0, (size_t)6 * mp * sizeof(double), c->rs.st);
-    if (e == hipSuccess) e = hipMemsetAsync(c->kM0, 0, (size_t)mp * mp * sizeof(double), c->rs.st);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(c->kM0, (size_t)mp * sizeof(double), M, m * sizeof(double), m * sizeof(double), m, hipMemcpyHostToDevice, c->rs.st);
+    if (e == hipSuccess) e = hipMemsetAsync(c->k.M0, 0, (size_t)mp * mp * sizeof(double), c->rs.st);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(c->k.M0, (size_t)mp * sizeof(double), M, m * sizeof(double), m * sizeof(double), m, hipMemcpyHostToDevice, c->rs.st);
     if (e == hipSuccess) e = hipMemcpy2DAsync(vbuf, (size_t)mp * sizeof(double), V, m * sizeof(double), m * sizeof(double), nrhs, hipMemcpyHostToDevice, c->rs.st);
     if (e == hipSuccess) e = hipMemcpy2DAsync(vbuf + 2 * mp, (size_t)mp * sizeof(double), R0, m * sizeof(double), m * sizeof(double), nrhs, hipMemcpyHostToDevice, c->rs.st);
-    if (e == hipSuccess) e = launch_symv_residual(c->kM0, mp, mp, nrhs, vbuf, mp, vbuf + 2 * mp, mp, vbuf + 4 * mp, mp, ws, c->rs.st);
+    if (e == hipSuccess) e = launch_symv_residual(c->k.M0, mp, mp, nrhs, vbuf, mp, vbuf + 2 * mp, mp, vbuf + 4 * mp, mp, ws, c->rs.st);
     if (e == hipSuccess)
         e = hipMemcpy2DAsync(Rho, m * sizeof(double), vbuf + 4 * mp, (size_t)mp * sizeof(double), m * sizeof(double), nrhs, hipMemcpyDeviceToHost, c->rs.st);
     const hipError_t es = hipStreamSynchronize(c->rs.st);      // also on failure: nothing may still use the buffers freed next
@@ -2868,29 +2869,25 @@ extern "C" int lpipm_k_qr_solve(lpipm_ctx* c, uint64_t m, const double* M, int n
     const int mp = (int)round_up(m, NB);
     LP_TRY(kbuf_ensure(c, mp));
     std::vector<double> pad((size_t)(mp - m), 1.0);
-    LP_HIP(hipMemsetAsync(c->kM, 0, (size_t)mp * mp * sizeof(double), c->rs.st));
-    LP_HIP(hipMemcpy2DAsync(c->kM, (size_t)mp * sizeof(double), M, m * sizeof(double), m * sizeof(double), m,
-                            hipMemcpyHostToDevice, c->rs.st));
-    if (mp > (int)m)
-        LP_HIP(hipMemcpy2DAsync(c->kM + m * mp + m, (size_t)(mp + 1) * sizeof(double), pad.data(), sizeof(double),
-                                sizeof(double), mp - m, hipMemcpyHostToDevice, c->rs.st));
-    LP_HIP(hipMemsetAsync(c->kR, 0, (size_t)2 * mp * sizeof(double), c->rs.st));
-    LP_HIP(hipMemcpy2DAsync(c->kR, (size_t)mp * sizeof(double), R, m * sizeof(double), m * sizeof(double), nrhs,
+    LP_HIP(hipMemsetAsync(c->k.plan.L, 0, (size_t)mp * mp * sizeof(double), c->rs.st));
+    LP_HIP(copy_padded(c->k.plan.L, mp, M, m, pad, c->rs.st));
+    LP_HIP(hipMemsetAsync(c->k.R, 0, (size_t)2 * mp * sizeof(double), c->rs.st));
+    LP_HIP(hipMemcpy2DAsync(c->k.R, (size_t)mp * sizeof(double), R, m * sizeof(double), m * sizeof(double), nrhs,
                             hipMemcpyHostToDevice, c->rs.st));
     LP_HIP(hipEventRecord(c->rs.ev_begin, c->rs.st));
-    LP_HIP(launch_qr_factor(c->kM, mp, mp, c->ktau, c->kinfo, c->rs.st));
-    LP_HIP(launch_qr_solve(c->kM, mp, mp, c->ktau, nrhs, c->kR, c->kinfo, c->rs.st));
+    LP_HIP(launch_qr_factor(c->k.plan.L, mp, mp, c->k.tau, c->k.info, c->rs.st));
+    LP_HIP(launch_qr_solve(c->k.plan.L, mp, mp, c->k.tau, nrhs, c->k.R, c->k.info, c->rs.st));
     LP_HIP(hipEventRecord(c->rs.ev_end, c->rs.st));
     int32_t info = 0;
-    LP_HIP(hipMemcpyAsync(&info, c->kinfo, sizeof(int32_t), hipMemcpyDeviceToHost, c->rs.st));
-    LP_HIP(hipMemcpy2DAsync(V, m * sizeof(double), c->kR, (size_t)mp * sizeof(double), m * sizeof(double), nrhs,
+    LP_HIP(hipMemcpyAsync(&info, c->k.info, sizeof(int32_t), hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(hipMemcpy2DAsync(V, m * sizeof(double), c->k.R, (size_t)mp * sizeof(double), m * sizeof(double), nrhs,
                             hipMemcpyDeviceToHost, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     float ms = 0.f;
     LP_HIP(hipEventElapsedTime(&ms, c->rs.ev_begin, c->rs.ev_end));
     if (ms_out) *ms_out = ms;
     if (info_out) *info_out = info;
-    c->kchol_valid = false;   // kM no longer holds a Cholesky factor: lpipm_k_chol_solve needs a new lpipm_k_potrf
+    c->k.chol_valid = false;   // plan.L no longer holds a Cholesky factor: lpipm_k_chol_solve needs a new lpipm_k_potrf
     return LPIPM_OK;
 }
 
@@ -2969,7 +2966,7 @@ extern "C" int lpipm_k_iteration(lpipm_ctx* c, const lpipm_opts* o, int ip, doub
     LP_HIP(hipMemcpyAsync(d_y, v.dy, c->p.m * sizeof(double), hipMemcpyDeviceToHost, st));
     LP_HIP(hipMemcpyAsync(d_z, v.dz, c->p.n * sizeof(double), hipMemcpyDeviceToHost, st));
     LP_HIP(hipStreamSynchronize(st));
-    if (c->colsplit && c->p.adat.ngroups() > 0 && *c->rs.timeout_host != 0) {   // as solve_members: a group wait that gave up is an error
+    if (c->colsplit && c->p.sys[SYS_WORK].res.ngroups() > 0 && *c->rs.timeout_host != 0) {   // as solve_members: a group wait that gave up is an error
         g_err_detail = "a column group of A.D.A^T did not complete within the wait kernel's bound";
         return LPIPM_ERR_HIP;
     }
