@@ -23,9 +23,10 @@
 // the two halves of the solve on K = L.L^T the `eq` rows come in through Zt = A_eq.L^-T and S = Zt.Zt^T (kernels_trsm.hip,
 // solver.hip: tall_eq_schur, tall_eq_reduced_solve):
 //   w = L^-1 g;  h = r2_e - Zt.w;  v_e = S^-1 h;  w += Zt^T.v_e (k_tall_eq_add_w);  u_x = L^-T w;  v = [W_s * u_s + r1_s; v_e]
-// The eq-aware siblings below (k_tall_eq_setup, _pq_uv, _uv_corr) loop slack quantities over ms and row quantities over
-// ms + me; k_tall_fold and k_tall_residuals depend on neither count and serve both.  The kernels of every other tall upload are
-// untouched: their bits stay.
+// k_tall_setup, k_tall_pq_uv and k_tall_uv_corr are one body each with two instantiations (template <bool EQ>, picked by the host
+// wrapper from t.me > 0): under EQ slack quantities loop over ms and row quantities over ms + me, taking v_e from Ve; without it
+// ms == m and me == 0, the loops run to m and no line that reads Ve is compiled, so the kernels of every other tall upload do what
+// they did before there were equality rows: their bits stay.  k_tall_fold and k_tall_residuals depend on neither count.
 #include "vec_kernels.hpp"
 #include "vec_device.hpp"
 
@@ -69,27 +70,14 @@ hipError_t tall_transpose(const double* X, int64_t ldx, int m, int nx, double* X
 // ---------------------------------------------------------------- set-up: W_s, E_x, t
 // with_scales: W_s = z_s / x_s (i < m; the padding up to mk stays zero) and E_x = z_x / x_x (j < nx) from the iterate.
 // t of right-hand side r (r < nrhs): T[r][i] = W_s[i] * r2[i] + r1[nx + i].
+// EQ: the same over the ms `ub` rows alone -- only they carry a slack column, K is built from them, and t stays zero on the `eq`
+// rows (nothing ever writes it there), so the pass X^T.t over the whole image sees the `ub` rows only.
+template <bool EQ>
 __global__ __launch_bounds__(256) void k_tall_setup(VecArgs a, TallArgs t, int with_scales, int nrhs, TallRhs rhs) {
     if (!tbatch(a, t, rhs)) return;
     const double *r1a = rhs.r1a, *r2a = rhs.r2a, *r1b = rhs.r1b, *r2b = rhs.r2b;
     const int stride = gridDim.x * 256;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
-        double ws;
-        if (with_scales) { ws = a.z[t.nx + i] / a.x[t.nx + i]; t.Ws[i] = ws; }
-        else ws = t.Ws[i];
-        if (nrhs > 0) t.T[i] = ws * r2a[i] + r1a[t.nx + i];
-        if (nrhs > 1) t.T[a.mp + i] = ws * r2b[i] + r1b[t.nx + i];
-    }
-    if (with_scales)
-        for (int j = blockIdx.x * 256 + threadIdx.x; j < t.nx; j += stride) t.Ex[j] = a.z[j] / a.x[j];
-}
-// Equality rows (t.me > 0): the same over the ms `ub` rows alone -- only they carry a slack column, K is built from them, and
-// t stays zero on the `eq` rows (nothing ever writes it there), so the pass X^T.t over the whole image sees the `ub` rows only.
-__global__ __launch_bounds__(256) void k_tall_eq_setup(VecArgs a, TallArgs t, int with_scales, int nrhs, TallRhs rhs) {
-    if (!tbatch(a, t, rhs)) return;
-    const double *r1a = rhs.r1a, *r2a = rhs.r2a, *r1b = rhs.r1b, *r2b = rhs.r2b;
-    const int stride = gridDim.x * 256;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < t.ms; i += stride) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < (EQ ? t.ms : a.m); i += stride) {
         double ws;
         if (with_scales) { ws = a.z[t.nx + i] / a.x[t.nx + i]; t.Ws[i] = ws; }
         else ws = t.Ws[i];
@@ -101,13 +89,8 @@ __global__ __launch_bounds__(256) void k_tall_eq_setup(VecArgs a, TallArgs t, in
 }
 void tall_setup(const VecArgs& a, const TallArgs& t, bool with_scales, int nrhs, const double* r1a, const double* r2a,
                 const double* r1b, const double* r2b, hipStream_t st) {
-    if (t.me > 0) {
-        hipLaunchKernelGGL(k_tall_eq_setup, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, with_scales ? 1 : 0, nrhs,
-                           TallRhs{r1a, r2a, r1b, r2b});
-        return;
-    }
-    hipLaunchKernelGGL(k_tall_setup, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, with_scales ? 1 : 0, nrhs,
-                       TallRhs{r1a, r2a, r1b, r2b});
+    hipLaunchKernelGGL(t.me > 0 ? k_tall_setup<true> : k_tall_setup<false>, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t,
+                       with_scales ? 1 : 0, nrhs, TallRhs{r1a, r2a, r1b, r2b});
 }
 
 // ---------------------------------------------------------------- right-hand side of the reduced solve
@@ -140,6 +123,9 @@ void tall_fold_rhs(const VecArgs& a, const TallArgs& t, int nrhs, const double* 
 // Predictor: (p, q) from right-hand side 0, (u, v) from right-hand side 1.  u_x = G, u_s = Us; v = W_s * u_s + r1_s goes
 // to R (q into R[0], v into R[1], as the dense solve leaves them) and q to a.q.  The four dots of delta.rs:29-32 go to
 // the reduction slots 0 .. 3 and the NaN check of newton_equations.rs:190-194 sets FLAG_NAN_PQ, as k_pq_uv.
+// EQ: n = nx + ms columns as above; of the ms + me rows the first ms are v_u = W_s * u_s + r1_s, the others v_e, which the Schur
+// solve has left in Ve.  The same dots in the same slots, reduced in the same order.
+template <bool EQ>
 __global__ __launch_bounds__(256) void k_tall_pq_uv(VecArgs a, TallArgs t, TallRhs rhs) {
     if (!tbatch(a, t, rhs)) return;
     const double *r1a = rhs.r1a, *r1b = rhs.r1b;
@@ -158,9 +144,10 @@ __global__ __launch_bounds__(256) void k_tall_pq_uv(VecArgs a, TallArgs t, TallR
         nan |= (p != p);
     }
     for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
-        const double ws = t.Ws[i], bi = a.b[i];
-        const double q = ws * t.Us[i] + r1a[t.nx + i];
-        const double v = ws * t.Us[a.mp + i] + r1b[t.nx + i];
+        const bool ub = !EQ || i < t.ms;
+        const double ws = ub ? t.Ws[i] : 0.0, bi = a.b[i];
+        const double q = ub ? ws * t.Us[i] + r1a[t.nx + i] : t.Ve[i - t.ms];
+        const double v = ub ? ws * t.Us[a.mp + i] + r1b[t.nx + i] : t.Ve[t.mep + i - t.ms];
         a.q[i] = q;
         a.R[i] = q;
         a.R[a.mp + i] = v;
@@ -172,6 +159,7 @@ __global__ __launch_bounds__(256) void k_tall_pq_uv(VecArgs a, TallArgs t, TallR
     block_reduce_store<4, false>(acc, a.red, 0);
 }
 // Corrector: only (u, v) change (k_uv_corr): c.u and b.v into slots 0 and 1, v into R[0].
+template <bool EQ>
 __global__ __launch_bounds__(256) void k_tall_uv_corr(VecArgs a, TallArgs t, TallRhs rhs) {
     if (!tbatch(a, t, rhs)) return;
     const double* r1a = rhs.r1a;
@@ -183,61 +171,7 @@ __global__ __launch_bounds__(256) void k_tall_uv_corr(VecArgs a, TallArgs t, Tal
         acc[0] += a.c[j] * u;
     }
     for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
-        const double v = t.Ws[i] * t.Us[i] + r1a[t.nx + i];
-        a.R[i] = v;
-        acc[1] += a.b[i] * v;
-    }
-    block_reduce_store<2, false>(acc, a.red, 0);
-}
-// Equality rows: n = nx + ms columns as above; of the ms + me rows the first ms are v_u = W_s * u_s + r1_s, the others v_e,
-// which the Schur solve has left in Ve.  The same dots in the same slots, reduced in the same order.
-__global__ __launch_bounds__(256) void k_tall_eq_pq_uv(VecArgs a, TallArgs t, TallRhs rhs) {
-    if (!tbatch(a, t, rhs)) return;
-    const double *r1a = rhs.r1a, *r1b = rhs.r1b;
-    const int stride = gridDim.x * 256;
-    double acc[4] = {0, 0, 0, 0};
-    int nan = 0;
-    for (int j = blockIdx.x * 256 + threadIdx.x; j < a.n; j += stride) {
-        double p, u;
-        if (j < t.nx) { p = t.G[j]; u = t.G[t.nxp + j]; }
-        else          { p = t.Us[j - t.nx]; u = t.Us[a.mp + j - t.nx]; }
-        const double cj = a.c[j];
-        a.p[j] = p;
-        a.u[j] = u;
-        acc[0] += cj * p;
-        acc[1] += cj * u;
-        nan |= (p != p);
-    }
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
-        const double bi = a.b[i];
-        double q, v;
-        if (i < t.ms) {
-            const double ws = t.Ws[i];
-            q = ws * t.Us[i] + r1a[t.nx + i];
-            v = ws * t.Us[a.mp + i] + r1b[t.nx + i];
-        } else { q = t.Ve[i - t.ms]; v = t.Ve[t.mep + i - t.ms]; }
-        a.q[i] = q;
-        a.R[i] = q;
-        a.R[a.mp + i] = v;
-        acc[2] += bi * q;
-        acc[3] += bi * v;
-        nan |= (q != q);
-    }
-    if (nan) atomicOr(a.flags, FLAG_NAN_PQ);
-    block_reduce_store<4, false>(acc, a.red, 0);
-}
-__global__ __launch_bounds__(256) void k_tall_eq_uv_corr(VecArgs a, TallArgs t, TallRhs rhs) {
-    if (!tbatch(a, t, rhs)) return;
-    const double* r1a = rhs.r1a;
-    const int stride = gridDim.x * 256;
-    double acc[2] = {0, 0};
-    for (int j = blockIdx.x * 256 + threadIdx.x; j < a.n; j += stride) {
-        const double u = j < t.nx ? t.G[j] : t.Us[j - t.nx];
-        a.u[j] = u;
-        acc[0] += a.c[j] * u;
-    }
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
-        const double v = i < t.ms ? t.Ws[i] * t.Us[i] + r1a[t.nx + i] : t.Ve[i - t.ms];
+        const double v = (!EQ || i < t.ms) ? t.Ws[i] * t.Us[i] + r1a[t.nx + i] : t.Ve[i - t.ms];
         a.R[i] = v;
         acc[1] += a.b[i] * v;
     }
@@ -269,18 +203,12 @@ void tall_eq_add_w(const VecArgs& a, const TallArgs& t, int nrhs, double* W, con
     hipLaunchKernelGGL(k_tall_eq_add_w, dim3((t.nxp + 255) / 256, nrhs, a.bcount), dim3(256), 0, st, a, t, nrhs, W, ZtPart);
 }
 void tall_pq_uv(const VecArgs& a, const TallArgs& t, const double* r1a, const double* r1b, hipStream_t st) {
-    if (t.me > 0) {
-        hipLaunchKernelGGL(k_tall_eq_pq_uv, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, TallRhs{r1a, nullptr, r1b, nullptr});
-        return;
-    }
-    hipLaunchKernelGGL(k_tall_pq_uv, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, TallRhs{r1a, nullptr, r1b, nullptr});
+    hipLaunchKernelGGL(t.me > 0 ? k_tall_pq_uv<true> : k_tall_pq_uv<false>, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t,
+                       TallRhs{r1a, nullptr, r1b, nullptr});
 }
 void tall_uv_corr(const VecArgs& a, const TallArgs& t, const double* r1a, hipStream_t st) {
-    if (t.me > 0) {
-        hipLaunchKernelGGL(k_tall_eq_uv_corr, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, TallRhs{r1a, nullptr, nullptr, nullptr});
-        return;
-    }
-    hipLaunchKernelGGL(k_tall_uv_corr, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t, TallRhs{r1a, nullptr, nullptr, nullptr});
+    hipLaunchKernelGGL(t.me > 0 ? k_tall_uv_corr<true> : k_tall_uv_corr<false>, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, t,
+                       TallRhs{r1a, nullptr, nullptr, nullptr});
 }
 
 // ---------------------------------------------------------------- residuals at the current point

@@ -1168,6 +1168,18 @@ struct Iter {
 // The system of that iteration, and whether it is the ONE kept factor of a whole shared-matrix batch.
 static NormalSystem& cur_sys(lpipm_ctx* c, const Iter& it) { return c->p.sys[it.on_first ? SYS_FIRST : SYS_WORK]; }
 static bool shared_first(const lpipm_ctx* c, const Iter& it) { return it.on_first && c->p.shared_factor; }
+// The same `bytes` of every member the context covers, on its stream: copied device to device from src to dst (both in the
+// members' arenas, bstride apart, from member bt.first on), device to host into dst (packed, `bytes` apart, from its start), or
+// zeroed (src null).  One member: the runtime's plain call, several: its 2-D one -- which of the runtime's kernels runs, and
+// shows in a trace, follows from that choice.
+static hipError_t member_bytes(lpipm_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind = hipMemcpyDeviceToDevice) {
+    const size_t off = (size_t)c->p.bt.first * c->p.bstride, pitch = c->p.bstride, B = (size_t)c->p.B;
+    const bool to_host = kind == hipMemcpyDeviceToHost;
+    char* d = (char*)dst + (to_host ? 0 : off);
+    const char* s = src ? (const char*)src + off : nullptr;
+    if (B == 1) return s ? hipMemcpyAsync(d, s, bytes, kind, c->rs.st) : hipMemsetAsync(d, 0, bytes, c->rs.st);
+    return s ? hipMemcpy2DAsync(d, to_host ? bytes : pitch, s, pitch, bytes, B, kind, c->rs.st) : hipMemset2DAsync(d, pitch, 0, bytes, B, c->rs.st);
+}
 // The pivot-failure words of the LPs this context covers, between the solver's word and its kept copy (device to device).
 // A shared-matrix batch's one kept word goes to every LP (the other direction does not exist: the build wrote it).
 static hipError_t copy_info(lpipm_ctx* c, int32_t* dst, const int32_t* src) {
@@ -1177,11 +1189,7 @@ static hipError_t copy_info(lpipm_ctx* c, int32_t* dst, const int32_t* src) {
         vec_scatter_rows(w, c->rs.st, c->p.bt);
         return hipGetLastError();
     }
-    const size_t off = (size_t)c->p.bt.first * c->p.bstride;
-    char* d = (char*)dst + off;
-    const char* s = (const char*)src + off;
-    return c->p.B == 1 ? hipMemcpyAsync(d, s, sizeof(int32_t), hipMemcpyDeviceToDevice, c->rs.st)
-                       : hipMemcpy2DAsync(d, c->p.bstride, s, c->p.bstride, sizeof(int32_t), (size_t)c->p.B, hipMemcpyDeviceToDevice, c->rs.st);
+    return member_bytes(c, dst, src, sizeof(int32_t));
 }
 // Builds system s for the members of bt: its one A.D.A^T launch, then its diagonal add-on.  Nothing else fills an AdatLaunch.
 struct BuildOpts {
@@ -1260,39 +1268,26 @@ static int tall_eq_reduced_solve(lpipm_ctx* c, int nrhs, const double* r2a, cons
 // goes back to zero ahead of a solve, and ahead of the kernel entries that run the reduced solve.
 static int tall_eq_reset(lpipm_ctx* c) {
     if (!c->p.tall_eq) return LPIPM_OK;
-    char* ve = (char*)c->p.tv.Ve + (size_t)c->p.bt.first * c->p.bstride;
-    const size_t bytes = 2 * (size_t)c->p.tv.mep * sizeof(double);
-    LP_HIP(c->p.B == 1 ? hipMemsetAsync(ve, 0, bytes, c->rs.st) : hipMemset2DAsync(ve, c->p.bstride, 0, bytes, (size_t)c->p.B, c->rs.st));
-    return LPIPM_OK;
-}
-// Tall form: the reduced sym_solve for nrhs right-hand sides (r1a, r2a), (r1b, r2b) whose t the set-up kernel has left in
-// T, up to u_x in G and u_s in Us; the caller's epilogue kernel forms p, q, u, v.  K is factored.
-static int tall_sym_solve(lpipm_ctx* c, int nrhs, const double* r1a, const double* r2a, const double* r1b, const double* r2b,
-                          const Batch& bt) {
-    const TallArgs& t = c->p.tv;
-    const VecArgs& v = c->p.va;
-    hipStream_t st = c->rs.st;
-    LP_HIP(ctx_gemv_t(c, nrhs, t.T, bt));                                         // X^T.t
-    prof_mark(c, T_GEMV);
-    tall_fold_rhs(v, t, nrhs, r1a, r1b, st);                                      // g = X^T.t - r1_x
-    LP_HIP(hipGetLastError());
-    prof_mark(c, T_VEC);
-    if (c->p.tall_eq) LP_TRY(tall_eq_reduced_solve(c, nrhs, r2a, r2b));          // u_x through the Schur complement, v_e
-    else LP_HIP(launch_chol_solve(*c->p.sys[SYS_WORK].factor, nrhs, t.G, c->p.Y, st, bt));   // u_x = K^-1 g
-    prof_mark(c, T_TRSV);
-    ++c->gemv_passes;                                                             // u_s = r2 - X.u_x   (tall_eq: over the `ub` rows)
-    LP_HIP(launch_gemv_n(c->p.A, c->p.npa, c->p.tall_eq ? t.ms : (int)c->p.m, c->p.npa, nrhs, t.G, t.nxp, r2a, r2b, t.Us, c->p.mp, st, -1.0, bt, c->p.shared_a));
-    prof_mark(c, T_GEMV);
+    LP_HIP(member_bytes(c, c->p.tv.Ve, nullptr, 2 * (size_t)c->p.tv.mep * sizeof(double)));
     return LPIPM_OK;
 }
 
-// v = M^-1 r through the Cholesky factor (newton_equations.rs:151-169); optionally (LPIPM_REFINE, see lpipm_ctx::refine)
-// with one step of iterative refinement against the matrix itself:  v0 = L^-T L^-1 r;  rho = r - M.v0 (doubled
-// precision, one read of the lower triangle);  v = v0 + L^-T L^-1 rho.  R: nrhs x mp, in/out.
-static int chol_solve_refined(lpipm_ctx* c, const Iter& it, int nrhs, double* R, const Batch& bt) {
-    hipStream_t st = c->rs.st;
-    const FactorPlan& f = *cur_sys(c, it).factor;    // (a refining context keeps no first factor: the working system's)
-    if (!it.refine_now) { LP_HIP(launch_chol_solve(f, nrhs, R, c->p.Y, st, bt, SolveSteps{}, shared_first(c, it))); return LPIPM_OK; }
+// R = A.W + r2 for the nrhs right-hand sides whose r2 are add0, add1 (newton_equations.rs:220), on the solver's stream or `on`.
+// Column split: the addends enter once, after the cross-rank sum of the ranks' products.
+static int pass_aw(lpipm_ctx* c, int nrhs, const double* add0, const double* add1, hipStream_t on = nullptr) {
+    VecArgs& v = c->p.va;
+    if (!c->colsplit) { LP_HIP(ctx_gemv_n(c, nrhs, v.W, add0, add1, v.R, c->p.bt, on)); return LPIPM_OK; }
+    LP_HIP(ctx_gemv_n(c, nrhs, v.W, nullptr, nullptr, v.R, c->p.bt, on));
+    LP_TRY(ctx_allreduce(c, v.R, (uint64_t)nrhs * c->p.mp, 0, on));
+    vec_add_rows((int)c->p.m, nrhs, v.R, c->p.mp, add0, add1, on ? on : c->rs.st);
+    return LPIPM_OK;
+}
+
+// v = M^-1 r through the Cholesky factor f with one step of iterative refinement against the matrix itself (LPIPM_REFINE, see
+// lpipm_ctx::refine):  v0 = L^-T L^-1 r;  rho = r - M.v0 (doubled precision, one read of the lower triangle);  v = v0 + L^-T L^-1 rho.
+// R: nrhs x mp, in/out.
+static int chol_solve_refined(lpipm_ctx* c, const FactorPlan& f, int nrhs, double* R, hipStream_t st) {
+    const Batch& bt = c->p.bt;
     // the refinement's launches skip an LP whose own word says so (a finished one, or one that does not need it yet)
     const Batch br = c->refine == 2 ? bt : Batch{bt.count, bt.stride, c->p.va.skip_refine, bt.first};
     vec_rows_copy(c->p.mp, nrhs, c->p.R0, R, st, br);
@@ -1301,6 +1296,18 @@ static int chol_solve_refined(lpipm_ctx* c, const Iter& it, int nrhs, double* R,
     LP_HIP(launch_chol_solve(f, nrhs, c->p.Rho, c->p.Y, st, br));
     vec_rows_add(c->p.mp, nrhs, R, c->p.Rho, st, br);
     LP_HIP(hipGetLastError());
+    return LPIPM_OK;
+}
+// R <- M^-1.R (nrhs x mp, in place) with the dense system of this iteration (newton_equations.rs:151-169), on the solver's stream
+// or `on`; the arm is chosen here and nowhere else: QR, the refined Cholesky solve, or the steps given of the Cholesky sweep (all of
+// them, unless the first ran beside the chain).
+static int normal_solve(lpipm_ctx* c, const Iter& it, const lpipm_opts* o, int nrhs, const SolveSteps& steps = SolveSteps{}, hipStream_t on = nullptr) {
+    hipStream_t st = on ? on : c->rs.st;
+    double* R = c->p.va.R;
+    const NormalSystem& sys = cur_sys(c, it);        // (the QR arms and a refining context keep no first factor: the working system)
+    if (o->solver_type != LPIPM_SOLVER_CHOLESKY) LP_HIP(launch_qr_solve(sys.M, sys.n, sys.n, c->p.tau, nrhs, R, c->p.va.potrf_info, st));   // :155-166
+    else if (it.refine_now) LP_TRY(chol_solve_refined(c, *sys.factor, nrhs, R, st));
+    else LP_HIP(launch_chol_solve(*sys.factor, nrhs, R, c->p.Y, st, c->p.bt, steps, shared_first(c, it)));   // :154
     return LPIPM_OK;
 }
 
@@ -1371,10 +1378,8 @@ static int wait_status(lpipm_ctx* c, const int* idx, int count) {
     return LPIPM_ERR_HIP;
 }
 static int copy_status(lpipm_ctx* c) {
-    if (c->p.va.status_pinned) {}          // written by the kernels themselves
-    else if (c->p.B == 1) LP_HIP(hipMemcpyAsync(c->rs.status_host, (const char*)c->p.va.status + (size_t)c->p.bt.first * c->p.bstride, sizeof(StatusRec), hipMemcpyDeviceToHost, c->rs.st));
-    else LP_HIP(hipMemcpy2DAsync(c->rs.status_host, sizeof(StatusRec), (const char*)c->p.va.status + (size_t)c->p.bt.first * c->p.bstride, c->p.bstride,
-                                 sizeof(StatusRec), (size_t)c->p.B, hipMemcpyDeviceToHost, c->rs.st));
+    if (!c->p.va.status_pinned)            // (else written by the kernels themselves)
+        LP_HIP(member_bytes(c, c->rs.status_host, c->p.va.status, sizeof(StatusRec), hipMemcpyDeviceToHost));
     if (c->colsplit && c->p.sys[SYS_WORK].res.ngroups() > 0)   // a wait kernel that gave up (its producer never ran) says so here
         LP_HIP(hipMemcpyAsync(c->rs.timeout_host, c->p.sys[SYS_WORK].res.wait_timeout, sizeof(unsigned int), hipMemcpyDeviceToHost, c->rs.st));
     return LPIPM_OK;
@@ -1387,6 +1392,41 @@ static int copy_status(lpipm_ctx* c) {
 // the status of the previous iteration: the GPU goes straight from one iteration into the big kernel of the
 // next instead of idling through the read-back, and if the LP turns out to be finished the two kernels return
 // at once.
+// n-split: M = sum over the ranks of A_g D_g A_g^T, behind the launch that built this rank's term; a refining context's M0 is
+// then the summed matrix.
+// grouped (the launch went in column-group-major order, armed with ev_c0): PIPELINED.  The workgroup that completes a
+// group's last tile bumps the group's word; on the communication stream a one-wave kernel waits for that word, the
+// group's tiles are packed, summed over the ranks (the caller's all-reduce) and unpacked -- while the launch goes on with the
+// next groups.  After the last tile only the last group's sum is left (C5: 1/32 .. 1/8 of the 1.08 GB that round 2 reduced in
+// one block after the launch).  Element-wise sums: the same values as one reduction of the whole triangle -- bit for bit with two
+// ranks; with three or more only if the caller's all-reduce sums an element's terms in an order that does not depend on where
+// the element sits in the buffer (a ring all-reduce such as gloo's does not: last-bit differences between the two ways).
+// Otherwise: the packed lower triangle in one block on the solver's stream.
+static int reduce_system(lpipm_ctx* c, bool grouped) {
+    hipStream_t st = c->rs.st;
+    NormalSystem& work = c->p.sys[SYS_WORK];
+    const Batch& bt = c->p.bt_head;
+    if (grouped) {
+        hipStream_t sc = c->st_c;
+        LP_HIP(hipStreamWaitEvent(sc, c->ev_c0, 0));
+        for (int g = 0; g < work.res.ngroups(); ++g) {
+            const AdatGroup grp = adat_group(work.res, g);
+            double* slice = c->mpack + (size_t)grp.first * TILE * TILE;
+            LP_HIP(launch_wait_count(grp.word, (unsigned)grp.ntiles, bt.done, work.res.wait_timeout, sc));
+            vec_pack_tiles(work.M, work.n, grp.tiles, grp.ntiles, slice, 0, sc);
+            LP_TRY(ctx_allreduce(c, slice, (uint64_t)grp.ntiles * TILE * TILE, 0, sc));
+            vec_pack_tiles(work.M, work.n, grp.tiles, grp.ntiles, slice, 1, sc);
+        }
+        LP_HIP(hipEventRecord(c->ev_c1, sc));
+        LP_HIP(hipStreamWaitEvent(st, c->ev_c1, 0));
+    } else {
+        vec_pack_lower(work.M, work.n, work.n, c->mpack, 0, st);
+        LP_TRY(ctx_allreduce(c, c->mpack, c->mpack_count, 0));
+        vec_pack_lower(work.M, work.n, work.n, c->mpack, 1, st);
+    }
+    if (c->refine > 0) vec_copy_lower(work.M, c->p.M0, work.n, work.n, st, bt);   // the summed matrix, for the refined solves
+    return LPIPM_OK;
+}
 static int enqueue_head(lpipm_ctx* c, const Iter& it) {
     hipStream_t st = c->rs.st;
     NormalSystem& work = c->p.sys[SYS_WORK];
@@ -1404,41 +1444,10 @@ static int enqueue_head(lpipm_ctx* c, const Iter& it) {
     }
     prof_mark(c, T_VEC, true);
     if (it.skip_factor) return LPIPM_OK;          // iteration 1 on a kept factor: its M is already there, factored
-    if (c->colsplit && c->world > 1 && work.res.ngroups() > 0 && c->st_c) {
-        // n-split, M = sum_g A_g D_g A_g^T, PIPELINED: one A.D.A^T launch in column-group-major order on the solver's stream;
-        // the workgroup that completes a group's last tile bumps the group's word; on the communication stream a one-wave
-        // kernel waits for that word, the group's tiles are packed, summed over the ranks (the caller's all-reduce) and
-        // unpacked -- while the launch goes on with the next groups.  After the last tile only the last group's sum is
-        // left (C5: 1/32 .. 1/8 of the 1.08 GB that round 2 reduced in one block after the launch).  Element-wise sums:
-        // the same values as one reduction of the whole triangle -- bit for bit with two ranks; with three or more only if
-        // the caller's all-reduce sums an element's terms in an order that does not depend on where the element sits in
-        // the buffer (a ring all-reduce such as gloo's does not: last-bit differences between the two ways).
-        hipStream_t sc = c->st_c;
-        const Batch& bt = c->p.bt_head;
-        // (the launch arms ev_c0 once the group words are zero, in front of its kernel)
-        LP_HIP(build_system(c, cur_sys(c, it), bt, BuildOpts{.M2 = c->p.M0, .signal_groups = true}));
-        LP_HIP(hipStreamWaitEvent(sc, c->ev_c0, 0));
-        for (int g = 0; g < work.res.ngroups(); ++g) {
-            const AdatGroup grp = adat_group(work.res, g);
-            double* slice = c->mpack + (size_t)grp.first * TILE * TILE;
-            LP_HIP(launch_wait_count(grp.word, (unsigned)grp.ntiles, bt.done, work.res.wait_timeout, sc));
-            vec_pack_tiles(work.M, work.n, grp.tiles, grp.ntiles, slice, 0, sc);
-            LP_TRY(ctx_allreduce(c, slice, (uint64_t)grp.ntiles * TILE * TILE, 0, sc));
-            vec_pack_tiles(work.M, work.n, grp.tiles, grp.ntiles, slice, 1, sc);
-        }
-        LP_HIP(hipEventRecord(c->ev_c1, sc));
-        LP_HIP(hipStreamWaitEvent(st, c->ev_c1, 0));
-        if (c->refine > 0) vec_copy_lower(work.M, c->p.M0, work.n, work.n, st, c->p.bt_head);   // the summed matrix, for the refined solves
-        prof_mark(c, T_ADAT, true);
-        return LPIPM_OK;
-    }
-    LP_HIP(build_system(c, cur_sys(c, it), c->p.bt_head, BuildOpts{.M2 = c->p.M0}));   // newton_equations.rs:55-57
-    if (c->colsplit && c->world > 1) {                                     // n-split: M = sum_g A_g D_g A_g^T
-        vec_pack_lower(work.M, work.n, work.n, c->mpack, 0, st);
-        LP_TRY(ctx_allreduce(c, c->mpack, c->mpack_count, 0));
-        vec_pack_lower(work.M, work.n, work.n, c->mpack, 1, st);
-        if (c->refine > 0) vec_copy_lower(work.M, c->p.M0, work.n, work.n, st, c->p.bt_head);   // the summed matrix, for the refined solves
-    }
+    const bool split = c->colsplit && c->world > 1;
+    const bool grouped = split && work.res.ngroups() > 0 && c->st_c;    // (the launch then arms ev_c0 once the group words are zero)
+    LP_HIP(build_system(c, cur_sys(c, it), c->p.bt_head, BuildOpts{.M2 = c->p.M0, .signal_groups = grouped}));   // newton_equations.rs:55-57
+    if (split) LP_TRY(reduce_system(c, grouped));
     prof_mark(c, T_ADAT, true);
     return LPIPM_OK;
 }
@@ -1452,118 +1461,127 @@ static const PotrfLookahead* lookahead(lpipm_ctx* c) { return c->la.side ? &c->l
 struct PredictorBeside {
     lpipm_ctx* c;
     const Iter& it;
-    int fwd_done = 0;            // forward steps [0, fwd_done) of the predictor's solve are enqueued
+    const lpipm_opts* o;
+    int fwd_done = -1;           // the pass is enqueued (>= 0), and the forward steps [0, fwd_done) of the predictor's solve
+    int rc = LPIPM_OK;           // what the pass or a step returned (at() itself answers the factorisation in its terms)
     static hipError_t at(void* self, int sb, hipStream_t side) {
         PredictorBeside* b = (PredictorBeside*)self;
         lpipm_ctx* c = b->c;
-        VecArgs& v = c->p.va;
-        if (sb < 0) return ctx_gemv_n(c, 2, v.W, v.b, v.rP, v.R, c->p.bt, side);     // :220
         b->fwd_done = sb + 1;
-        return launch_chol_solve(*cur_sys(c, b->it).factor, 2, v.R, c->p.Y, side, c->p.bt, SolveSteps{sb, sb + 1, false}, shared_first(c, b->it));
+        b->rc = sb < 0 ? pass_aw(c, 2, c->p.va.b, c->p.va.rP, side)     // :220
+                       : normal_solve(c, b->it, b->o, 2, SolveSteps{sb, sb + 1, false}, side);
+        return b->rc == LPIPM_OK ? hipSuccess : hipErrorUnknown;
     }
 };
 
-// The tail of a tall LP's iteration: K's factorisation (no work beside its chain), then the reduced sym_solve twice -- both
-// right-hand sides of the predictor in one pass each, the corrector's one -- with the tall epilogues where the dense path has
-// k_pq_uv / k_uv_corr.  The vector stage runs kernel by kernel.
-static int enqueue_tail_tall(lpipm_ctx* c, int ip, const lpipm_opts* o) {
+// The factor of this iteration's system.  Dense: the kept first factor as it is (its pivot failure, if it had one, to the solver's
+// word); else M's Cholesky factor (:129-131; a single LP: `pb` beside its chain if launch_potrf finds that the look-ahead applies)
+// or its QR factorisation (:133-149), the pivot word of a first system kept with the factor it belongs to.  Tall: K's Cholesky
+// factor, then with equality rows Zt, S and S's factor; a tall LP has no kept factor, no refinement and no QR arm, so nothing of
+// `it` or of the solver type applies to it, here or in sym_solve.
+static int factor_system(lpipm_ctx* c, const Iter& it, const lpipm_opts* o, PredictorBeside& pb) {
     VecArgs& v = c->p.va;
-    const TallArgs& t = c->p.tv;
     hipStream_t st = c->rs.st;
     const Batch& bt = c->p.bt;
-    LP_HIP(launch_potrf(*c->p.sys[SYS_WORK].factor, v.potrf_info, st, bt, lookahead(c), false, nullptr));   // :129-131
-    if (c->p.tall_eq) LP_TRY(tall_eq_schur(c));                                // Zt, S and its factor
+    // (no clearing of the pivot-failure word: k_blind_start and every k_scalar_indicators leave it zero)
+    if (c->p.tall) {
+        LP_HIP(launch_potrf(*c->p.sys[SYS_WORK].factor, v.potrf_info, st, bt, lookahead(c), false, nullptr));
+        if (c->p.tall_eq) LP_TRY(tall_eq_schur(c));
+    } else if (it.skip_factor) {
+        LP_HIP(copy_info(c, v.potrf_info, c->p.sys[SYS_FIRST].info));
+        return LPIPM_OK;
+    } else {
+        const NormalSystem& sys = cur_sys(c, it);     // (the QR arms keep no first factor: the working system)
+        if (o->solver_type == LPIPM_SOLVER_CHOLESKY) {
+            PotrfBeside beside{PredictorBeside::at, &pb};
+            const bool may_beside = !c->colsplit && bt.count == 1 && c->refine <= 0;
+            const hipError_t e = launch_potrf(*sys.factor, v.potrf_info, st, bt, lookahead(c), false, may_beside ? &beside : nullptr);
+            LP_TRY(pb.rc);
+            LP_HIP(e);
+        } else LP_HIP(launch_qr_factor(sys.M, sys.n, sys.n, c->p.tau, v.potrf_info, st));
+        if (it.on_first) LP_HIP(copy_info(c, c->p.sys[SYS_FIRST].info, v.potrf_info));
+    }
     prof_mark(c, T_POTRF);
-    LP_TRY(tall_sym_solve(c, 2, v.c, v.b, v.r1, v.rP, bt));                    // :187-188
-    tall_pq_uv(v, t, v.c, v.r1, st);
-    LP_TRY(vec_delta(v, 0, ip, 1.0, st, nullptr));
-    vec_corr_setup(v, ip, st);
-    tall_setup(v, t, false, 1, v.r1, v.rP2, nullptr, nullptr, st);             // t of the corrector's right-hand side
-    prof_mark(c, T_VEC);
-    LP_TRY(tall_sym_solve(c, 1, v.r1, v.rP2, nullptr, nullptr, bt));
-    tall_uv_corr(v, t, v.r1, st);
-    LP_TRY(vec_delta(v, 1, ip, o->alpha0, st, nullptr));
-    vec_step(v, ip, o->alpha0, st);
-    prof_mark(c, T_VEC);
-    LP_TRY(enqueue_residuals(c, 0, 0, o->tol));
-    LP_TRY(copy_status(c));
-    prof_mark(c, T_VEC);
-    if (!c->rs.spin_status) LP_HIP(hipEventRecord(c->rs.ev_status, st));
     return LPIPM_OK;
 }
 
-// The rest of the iteration, ending with the status record on its way to the host and ev_status behind it.
-static int enqueue_tail(lpipm_ctx* c, const Iter& it, int ip, const lpipm_opts* o) {
-    if (c->p.tall) return enqueue_tail_tall(c, ip, o);          // (no kept factor, no refinement: nothing of `it` applies)
-    VecArgs& v = c->p.va;
+// sym_solve (newton_equations.rs:214-225) for `count` right-hand sides (r1a, r2a), (r1b, r2b) with the factor of factor_system, up
+// to where the epilogue forms p, q, u, v.  Dense: R = A.W + r2 (W is set up, so only r2 is read), R <- M^-1.R, the slabs of A^T.R;
+// beside_done >= 0: the pass and the forward steps [0, beside_done) of the solve ran beside the factorisation (PredictorBeside).
+// Tall: the reduced solve, whose t the set-up kernel has left in T, up to u_x in G, u_s in Us and v_e in Ve.
+struct SymRhs { int count; const double *r1a, *r2a, *r1b = nullptr, *r2b = nullptr; };
+static int sym_solve(lpipm_ctx* c, const Iter& it, const lpipm_opts* o, const SymRhs& rhs, int beside_done = -1) {
+    const VecArgs& v = c->p.va;
     hipStream_t st = c->rs.st;
+    const Batch& bt = c->p.bt;
+    const int nrhs = rhs.count;
+    if (c->p.tall) {
+        const TallArgs& t = c->p.tv;
+        LP_HIP(ctx_gemv_t(c, nrhs, t.T, bt));                                         // X^T.t
+        prof_mark(c, T_GEMV);
+        tall_fold_rhs(v, t, nrhs, rhs.r1a, rhs.r1b, st);                              // g = X^T.t - r1_x
+        LP_HIP(hipGetLastError());
+        prof_mark(c, T_VEC);
+        if (c->p.tall_eq) LP_TRY(tall_eq_reduced_solve(c, nrhs, rhs.r2a, rhs.r2b));  // u_x through the Schur complement, v_e
+        else LP_HIP(launch_chol_solve(*c->p.sys[SYS_WORK].factor, nrhs, t.G, c->p.Y, st, bt));   // u_x = K^-1 g
+        prof_mark(c, T_TRSV);
+        ++c->gemv_passes;                                                             // u_s = r2 - X.u_x   (tall_eq: over the `ub` rows)
+        LP_HIP(launch_gemv_n(c->p.A, c->p.npa, c->p.tall_eq ? t.ms : (int)c->p.m, c->p.npa, nrhs, t.G, t.nxp, rhs.r2a, rhs.r2b, t.Us, c->p.mp, st, -1.0, bt, c->p.shared_a));
+        prof_mark(c, T_GEMV);
+        return LPIPM_OK;
+    }
+    if (beside_done < 0) LP_TRY(pass_aw(c, nrhs, rhs.r2a, rhs.r2b));                  // :220
+    prof_mark(c, T_GEMV);
+    LP_TRY(normal_solve(c, it, o, nrhs, SolveSteps{beside_done < 0 ? 0 : beside_done, -1, true}));   // :221
+    prof_mark(c, T_TRSV);
+    LP_HIP(ctx_gemv_t(c, nrhs, v.R, bt));                                             // :223
+    prof_mark(c, T_GEMV);
+    return LPIPM_OK;
+}
+
+// The vector stage behind a sym_solve.  Predictor: (p, q), (u, v) and their dots (:223, delta.rs:29-32,38), Delta (delta.rs:33-37,
+// feasible_point.rs:134-136) and the corrector's right-hand side (rhat.rs:37-75; tall: with its t).  Corrector: (u, v), Delta and
+// the step length (mod.rs:216-221), the step (feasible_point.rs:76-106).  Small n on one rank: each in one fused launch.
+enum class Phase { Predictor, Corrector };
+static int epilogue(lpipm_ctx* c, Phase phase, int ip, double alpha0) {
+    VecArgs& v = c->p.va;
+    const TallArgs& t = c->p.tv;
+    hipStream_t st = c->rs.st;
+    const bool corr = phase == Phase::Corrector;
     XRank xr_{xrank_fn, c};
     const XRank* xr = c->colsplit ? &xr_ : nullptr;
-    const Batch& bt = c->p.bt;
-    const bool chol = o->solver_type == LPIPM_SOLVER_CHOLESKY;
-    const NormalSystem& sys = cur_sys(c, it);     // (the QR arms keep no first factor: the working system)
-    // (no clearing of the pivot-failure word: k_blind_start and every k_scalar_indicators leave it zero)
-    // a single LP whose factorisation runs with the look-ahead: the predictor's pass and the first forward steps of its
-    // solve go beside the chain (launch_potrf decides whether the look-ahead applies; the serial order otherwise)
-    PredictorBeside pb{c, it};
-    PotrfBeside beside{PredictorBeside::at, &pb};
-    const bool may_beside = chol && !c->colsplit && bt.count == 1 && c->refine <= 0;
-    if (it.skip_factor) LP_HIP(copy_info(c, v.potrf_info, c->p.sys[SYS_FIRST].info));   // the kept factor's pivot failure, if it had one
-    else {
-        if (chol) LP_HIP(launch_potrf(*sys.factor, v.potrf_info, st, bt, lookahead(c), false, may_beside ? &beside : nullptr));   // :129-131
-        else      LP_HIP(launch_qr_factor(sys.M, sys.n, sys.n, c->p.tau, v.potrf_info, st));        // :133-149
-        if (it.on_first) LP_HIP(copy_info(c, c->p.sys[SYS_FIRST].info, v.potrf_info));  // kept with the factor it belongs to
-        prof_mark(c, T_POTRF);
-    }
-    // predictor: both sym_solve calls of solve_newton_equations (:187-188) in one pass each
-    if (beside.calls > 0) {}                                // the pass ran beside the factorisation
-    else if (!c->colsplit) {
-        LP_HIP(ctx_gemv_n(c, 2, v.W, v.b, v.rP, v.R, bt));  // :220
-    } else {   // the addend r2 enters once, after the cross-rank sum of the column-split products
-        LP_HIP(ctx_gemv_n(c, 2, v.W, nullptr, nullptr, v.R, bt));
-        LP_TRY(ctx_allreduce(c, v.R, (uint64_t)2 * c->p.mp, 0));
-        vec_add_rows((int)c->p.m, 2, v.R, c->p.mp, v.b, v.rP, st);
-    }
-    prof_mark(c, T_GEMV);
-    if (beside.calls > 0) LP_HIP(launch_chol_solve(*sys.factor, 2, v.R, c->p.Y, st, bt, SolveSteps{pb.fwd_done, -1, true}, shared_first(c, it)));
-    else if (chol) LP_TRY(chol_solve_refined(c, it, 2, v.R, bt));                               // :221, :154
-    else      LP_HIP(launch_qr_solve(sys.M, sys.n, sys.n, c->p.tau, 2, v.R, v.potrf_info, st));   // :155-166
-    prof_mark(c, T_TRSV);
-    LP_HIP(ctx_gemv_t(c, 2, v.R, bt));              // :223
-    prof_mark(c, T_GEMV);
-    if (!xr && vec_fused(v)) vec_fused_predictor(v, ip, st);   // the three below in one launch (small n)
-    else {
-    LP_TRY(vec_pq_uv(v, st, xr));                       // :223, delta.rs:29-32,38
-    LP_TRY(vec_delta(v, 0, ip, 1.0, st, xr));           // delta.rs:33-37, feasible_point.rs:134-136
-    vec_corr_setup(v, ip, st);              // rhat.rs:37-75
-    }
-    prof_mark(c, T_VEC);
-    // corrector: only the second sym_solve changes
-    if (!c->colsplit) {
-        LP_HIP(ctx_gemv_n(c, 1, v.W, v.rP2, nullptr, v.R, bt));
+    if (!c->p.tall && !xr && vec_fused(v)) {
+        if (corr) vec_fused_corrector(v, ip, alpha0, st); else vec_fused_predictor(v, ip, st);
     } else {
-        LP_HIP(ctx_gemv_n(c, 1, v.W, nullptr, nullptr, v.R, bt));
-        LP_TRY(ctx_allreduce(c, v.R, c->p.mp, 0));
-        vec_add_rows((int)c->p.m, 1, v.R, c->p.mp, v.rP2, nullptr, st);
-    }
-    prof_mark(c, T_GEMV);
-    if (chol) LP_TRY(chol_solve_refined(c, it, 1, v.R, bt));
-    else      LP_HIP(launch_qr_solve(sys.M, sys.n, sys.n, c->p.tau, 1, v.R, v.potrf_info, st));
-    prof_mark(c, T_TRSV);
-    LP_HIP(ctx_gemv_t(c, 1, v.R, bt));
-    prof_mark(c, T_GEMV);
-    if (!xr && vec_fused(v)) vec_fused_corrector(v, ip, o->alpha0, st);
-    else {
-    LP_TRY(vec_uv_corr(v, st, xr));
-    LP_TRY(vec_delta(v, 1, ip, o->alpha0, st, xr));     // mod.rs:216-221
-    vec_step(v, ip, o->alpha0, st);         // feasible_point.rs:76-106 (+ the step length, mod.rs:216-221, when folded)
+        if (c->p.tall) { if (corr) tall_uv_corr(v, t, v.r1, st); else tall_pq_uv(v, t, v.c, v.r1, st); }
+        else LP_TRY(corr ? vec_uv_corr(v, st, xr) : vec_pq_uv(v, st, xr));
+        LP_TRY(vec_delta(v, corr ? 1 : 0, ip, corr ? alpha0 : 1.0, st, xr));
+        if (corr) vec_step(v, ip, alpha0, st); else vec_corr_setup(v, ip, st);
+        if (c->p.tall && !corr) tall_setup(v, t, false, 1, v.r1, v.rP2, nullptr, nullptr, st);
     }
     prof_mark(c, T_VEC);
-    LP_TRY(enqueue_residuals(c, 0, 0, o->tol));   // mod.rs:225
+    return LPIPM_OK;
+}
+
+// The residuals and indicators at the new point (mod.rs:225), the status record on its way to the host, ev_status behind it.
+static int finish_iteration(lpipm_ctx* c, double tol) {
+    LP_TRY(enqueue_residuals(c, 0, 0, tol));
     LP_TRY(copy_status(c));
     prof_mark(c, T_VEC);
-    if (!c->rs.spin_status) LP_HIP(hipEventRecord(c->rs.ev_status, st));
+    if (!c->rs.spin_status) LP_HIP(hipEventRecord(c->rs.ev_status, c->rs.st));
     return LPIPM_OK;
+}
+
+// The rest of the iteration, one sequence for every form, ending with the status record on its way to the host.
+static int enqueue_tail(lpipm_ctx* c, const Iter& it, int ip, const lpipm_opts* o) {
+    const VecArgs& v = c->p.va;
+    PredictorBeside pb{c, it, o};
+    LP_TRY(factor_system(c, it, o, pb));
+    LP_TRY(sym_solve(c, it, o, SymRhs{2, v.c, v.b, v.r1, v.rP}, pb.fwd_done));   // both calls of solve_newton_equations (:187-188)
+    LP_TRY(epilogue(c, Phase::Predictor, ip, o->alpha0));
+    LP_TRY(sym_solve(c, it, o, SymRhs{1, v.r1, v.rP2}));                         // corrector: only the second call changes
+    LP_TRY(epilogue(c, Phase::Corrector, ip, o->alpha0));
+    return finish_iteration(c, o->tol);
 }
 
 static int enqueue_iteration(lpipm_ctx* c, const Iter& it, int ip, const lpipm_opts* o) {
@@ -2525,6 +2543,8 @@ extern "C" int lpipm_k_tall_sym_solve(lpipm_ctx* c, const double* dinv, int nrhs
     double* r1 = rhs;
     double* r2 = rhs + 2 * np;
     int32_t info = 0;
+    lpipm_opts o;
+    lpipm_default_opts(&o);
     auto run = [&]() -> int {
         LP_HIP(hipMemsetAsync(rhs, 0, 2 * (np + mp) * sizeof(double), st));
         LP_HIP(hipMemcpy2DAsync(r1, np * sizeof(double), R1, n * sizeof(double), n * sizeof(double), (size_t)nrhs, hipMemcpyHostToDevice, st));
@@ -2533,7 +2553,7 @@ extern "C" int lpipm_k_tall_sym_solve(lpipm_ctx* c, const double* dinv, int nrhs
         const double* r2b = nrhs == 2 ? r2 + mp : nullptr;
         LP_TRY(tall_entry_system(c, dinv, true, nrhs, r1, r2, r1b, r2b));
         if (c->p.tall_eq) LP_TRY(tall_eq_schur(c));
-        LP_TRY(tall_sym_solve(c, nrhs, r1, r2, r1b, r2b, Batch{}));
+        LP_TRY(sym_solve(c, Iter{}, &o, SymRhs{nrhs, r1, r2, r1b, r2b}));
         if (nrhs == 2) tall_pq_uv(v, t, r1, r1b, st);
         else           tall_uv_corr(v, t, r1, st);
         LP_HIP(hipGetLastError());

@@ -139,7 +139,7 @@ void tall_fold_rhs(const VecArgs& a, const TallArgs& t, int nrhs, const double* 
 // dense path leaves it --, the same dots in the same reduction slots, FLAG_NAN_PQ.
 void tall_pq_uv(const VecArgs& a, const TallArgs& t, const double* r1a, const double* r1b, hipStream_t st);
 void tall_uv_corr(const VecArgs& a, const TallArgs& t, const double* r1a, hipStream_t st);
-// (tall_setup, tall_pq_uv and tall_uv_corr launch their eq-aware siblings when t.me > 0: slack quantities over ms, row
+// (tall_setup, tall_pq_uv and tall_uv_corr launch their kernel's EQ instantiation when t.me > 0: slack quantities over ms, row
 // quantities over ms + me with v_e from Ve.)
 // Equality rows: W[r][j] += sum over the row splits of ZtPart[s][r][j] (slabs nxp wide, in order), j < nxp: the correction
 // Zt^T.v_e of the half-solved right-hand side w = L^-1.g
