@@ -21,6 +21,17 @@ pub struct lpipm_opts {
     pub disp: i32,
 }
 
+/// include/lpipm.h `lpipm_dual_info` (32 bytes): dual_fun = b.(y / tau) + c0, the iterate's tau and kappa, the member's status
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct lpipm_dual_info {
+    pub dual_fun: f64,
+    pub tau: f64,
+    pub kappa: f64,
+    pub status: i32,
+    pub reserved: i32,
+}
+
 /// include/lpipm.h `lpipm_iter_row` (indicators.rs:8-23 + alpha)
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -217,6 +228,16 @@ extern "C" {
     ) -> c_int;
     // Device bytes held for the resident problem(s): arenas + shared matrix + factor workspace.
     pub fn lpipm_get_resident_bytes(ctx: *const lpipm_ctx, bytes_out: *mut u64) -> c_int;
+    // Dual values and reduced costs of the LAST solve on the context, in the caller's units: y_out[m] (rows of the upload, `ub`
+    // first), z_out[n] (as long as x_slack_out), each nullable; A^T.y + z = c, z >= 0, d fun / d b_i = y_i.  A member without
+    // a solution: its own status is returned and nothing is written.  _device: every resident member at once, member i's y at
+    // y_dev + i * ldy doubles, its z at z_dev + i * ldz; info_out a host array of one record per member.
+    pub fn lpipm_get_duals(
+        ctx: *mut lpipm_ctx, member: u64, y_out: *mut f64, z_out: *mut f64, info_out: *mut lpipm_dual_info,
+    ) -> c_int;
+    pub fn lpipm_get_duals_device(
+        ctx: *mut lpipm_ctx, y_dev: *mut c_void, ldy: u64, z_dev: *mut c_void, ldz: u64, info_out: *mut lpipm_dual_info,
+    ) -> c_int;
     // Power-of-two row / column equilibration of every later upload (passes 1..64; 0 = off, the default), and the int32
     // exponents in use for a resident member: row_exp_out[m], col_exp_out[n].  x comes back in the caller's units.
     pub fn lpipm_set_scaling(ctx: *mut lpipm_ctx, passes: c_int) -> c_int;

@@ -41,15 +41,9 @@ fn to_error(status: i32, x: Option<Array1<f64>>) -> LinearProgramError<f64> {
     }
 }
 
-impl Solver<f64> for InteriorPoint<f64> {
-    /// Same contract as interior_point/mod.rs:161-168: stateless, re-entrant, never panics on a
-    /// numerical failure.  One lpipm_ctx per call (stream + device buffers); A is uploaded once.
-    fn solve(&self, problem: &Problem<f64>) -> Result<OptimizeResult<f64>, LinearProgramError<f64>> {
-        let a = problem.A().as_standard_layout(); // row-major, as ProblemBuilder::build leaves it (linear_program.rs:145-156)
-        let (m, n) = a.dim();
-        let b = problem.b().as_standard_layout();
-        let c = problem.c().as_standard_layout();
-        let opts = lpipm_opts {
+impl InteriorPoint<f64> {
+    fn hip_opts(&self) -> lpipm_opts {
+        lpipm_opts {
             tol: self.tol,
             alpha0: self.alpha0,
             max_iter: self.max_iter as u64,
@@ -60,7 +54,17 @@ impl Solver<f64> for InteriorPoint<f64> {
                 EquationSolverType::LeastSquares => 2,
             },
             disp: self.disp as i32,
-        };
+        }
+    }
+
+    /// What `solve` and `solve_with_duals` share: one lpipm_ctx per call (stream + device buffers), A uploaded once, one
+    /// `lpipm_solve`.  -> the context (still holding the solve's last iterate), x / tau in slack form, fun, the iteration.
+    fn upload_and_solve(&self, problem: &Problem<f64>) -> Result<(Ctx, Array1<f64>, f64, u64), LinearProgramError<f64>> {
+        let a = problem.A().as_standard_layout(); // row-major, as ProblemBuilder::build leaves it (linear_program.rs:145-156)
+        let (m, n) = a.dim();
+        let b = problem.b().as_standard_layout();
+        let c = problem.c().as_standard_layout();
+        let opts = self.hip_opts();
         let mut raw: *mut lpipm_ctx = std::ptr::null_mut();
         let rc = unsafe { lpipm_create(0, &mut raw) };
         if rc != LPIPM_OK {
@@ -82,15 +86,53 @@ impl Solver<f64> for InteriorPoint<f64> {
             lpipm_solve(ctx.0, &opts, x_slack.as_mut_ptr(), &mut fun, &mut iteration, std::ptr::null_mut())
         };
         match rc {
-            LPIPM_OK => {
-                // mod.rs:165-167: fun = c.x + c0 (computed on device from the same x), drop the slack tail
-                let x = problem.denormalize_x_into(x_slack);
-                Ok(OptimizeResult::new(x, fun, iteration as usize))
-            }
+            LPIPM_OK => Ok((ctx, x_slack, fun, iteration)),
             LPIPM_ITERATION_LIMIT => Err(to_error(rc, Some(x_slack))), // mod.rs:237-239
             _ => Err(to_error(rc, None)),
         }
     }
+
+    /// `solve` followed by `lpipm_get_duals` on the same context.  A problem without a solution is the same error `solve` gives.
+    pub fn solve_with_duals(&self, problem: &Problem<f64>) -> Result<DualResult, LinearProgramError<f64>> {
+        let (ctx, x_slack, fun, iteration) = self.upload_and_solve(problem)?;
+        let (m, n) = problem.A().dim();
+        let n_slack = problem.n_slack();
+        let (mut y, mut z) = (Array1::<f64>::zeros(m), Array1::<f64>::zeros(n));
+        let mut info = lpipm_dual_info::default();
+        let rc = unsafe { lpipm_get_duals(ctx.0, 0, y.as_mut_ptr(), z.as_mut_ptr(), &mut info) };
+        if rc != LPIPM_OK {
+            return Err(to_error(rc, None));
+        }
+        // the `ub` rows come first, one slack column each behind the structural ones (linear_program.rs:145-161)
+        Ok(DualResult {
+            result: OptimizeResult::new(problem.denormalize_x_into(x_slack), fun, iteration as usize),
+            y_ub: y.slice(ndarray::s![..n_slack]).to_owned(),
+            y_eq: y.slice(ndarray::s![n_slack..]).to_owned(),
+            reduced_costs: z.slice(ndarray::s![..n - n_slack]).to_owned(),
+            dual_fun: info.dual_fun,
+        })
+    }
+}
+
+impl Solver<f64> for InteriorPoint<f64> {
+    /// Same contract as interior_point/mod.rs:161-168: stateless, re-entrant, never panics on a
+    /// numerical failure.  One lpipm_ctx per call (stream + device buffers); A is uploaded once.
+    fn solve(&self, problem: &Problem<f64>) -> Result<OptimizeResult<f64>, LinearProgramError<f64>> {
+        let (_ctx, x_slack, fun, iteration) = self.upload_and_solve(problem)?;
+        // mod.rs:165-167: fun = c.x + c0 (computed on device from the same x), drop the slack tail
+        Ok(OptimizeResult::new(problem.denormalize_x_into(x_slack), fun, iteration as usize))
+    }
+}
+
+/// What `InteriorPoint::<f64>::solve_with_duals` returns: the `OptimizeResult` of `solve` and the duals of its last iterate,
+/// split as `ProblemBuilder::build` stacks the rows (linear_program.rs:145-158): `y_ub` / `y_eq` the multipliers of the `ub`
+/// and `eq` rows (d fun / d b), `reduced_costs` those of the structural columns, `dual_fun` = b.y + c0.
+pub struct DualResult {
+    pub result: OptimizeResult<f64>,
+    pub y_ub: Array1<f64>,
+    pub y_eq: Array1<f64>,
+    pub reduced_costs: Array1<f64>,
+    pub dual_fun: f64,
 }
 
 fn to_error_f32(status: i32, x: Option<Array1<f32>>) -> LinearProgramError<f32> {

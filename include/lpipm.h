@@ -476,6 +476,46 @@ int lpipm_upload_device(lpipm_ctx* ctx, const lpipm_device_problem* d);
  * bit-identical to one after lpipm_update_vectors with the same values. */
 int lpipm_update_vectors_device(lpipm_ctx* ctx, const void* b_dev, const void* c_dev);
 
+/* ---- dual values and reduced costs of the LAST solve ------------------------------------------------------------------
+ * Every solve above hands back x / tau, fun and the iteration count; the multipliers y of the rows and the reduced costs z of
+ * the columns of the same iterate stay in the context and are fetched here, after the solve: a Benders or scenario cut is y,
+ * the sensitivity of fun to b_i is y_i, column pricing is z.  No solve entry, no arena layout and no bit of any solve changes.
+ * Definition.  (x, y, z, tau, kappa) is the iterate at which the member's status was decided -- the one x_slack_out was
+ *   formed from, for LPIPM_OK and for LPIPM_ITERATION_LIMIT alike.  In the resident (possibly scaled) problem yh = y / tau,
+ *   zh = z / tau; with kr, kc the kept exponents of lpipm_get_scaling the values returned are y_i = ldexp(yh_i, kr[i]) and
+ *   z_j = ldexp(zh_j, -kc[j]) (the slack column of `ub` row i carries kc = -kr[i]: its z gets +kr[i]) -- the division first, the
+ *   power of two second, as for x: exact unless a value under- or overflows.  dual_fun = b.yh + c0 from the resident vectors,
+ *   as fun is; tau and kappa are the iterate's.  Convention (residual.rs:23-29, r_D = c.tau - A^T.y - z): A^T.y + z = c,
+ *   z >= 0, d fun / d b_i = y_i; the multiplier of a `ub` row is <= 0 and equals minus its slack's reduced cost up to the
+ *   dual residual.
+ * Lengths and order.  y: the m rows of the upload (*_ub_eq and *_ub_eq_tall: m_ub + m_eq, `ub` first); z: exactly as long as
+ *   x_slack_out of that upload (structural entries, then the slack entries where the form has them).
+ * lpipm_get_duals: resident member `member` (0 for a single LP), to host arrays (each nullable).  A member whose last status
+ *   has no solution: that status (LPIPM_INFEASIBLE, ...) is returned and nothing is written.
+ * lpipm_get_duals_device: all members at once, left in HBM on the context's stream (complete on return): member i's y at
+ *   y_dev + i * ldy doubles, its z at z_dev + i * ldz (ldy >= the length of y, ldz >= that of z; either pointer may be NULL).
+ *   Returns LPIPM_OK; the rows of a member without a solution stay untouched and its info is {NaN, NaN, NaN, status}.
+ *   info_out: a host array of one record per resident member (nullable).  The destinations are looked up with the runtime
+ *   and checked against their allocation before any launch, as lpipm_upload_device checks its sources.
+ * The context keeps the per-member return codes of its last solve, whichever entry ran it (both half-batch views of a large
+ *   lockstep batch record into it), and every member comes out bit-identical -- y, z, dual_fun, tau, kappa -- to the single
+ *   upload + lpipm_solve + lpipm_get_duals of that member alone, by either entry.
+ * Validity.  LPIPM_ERR_BAD_ARGUMENT: a null context, member >= the resident count, ldy or ldz too small, a destination that
+ *   is not device memory of the context's device or does not hold every row.  LPIPM_ERR_UNSUPPORTED: a column-split context.
+ *   LPIPM_ERR_NO_PROBLEM: nothing resident, or no solve has completed since the last event that changes what the iterate
+ *   means: any upload, lpipm_update_vectors[_device], lpipm_update_lockstep_vectors[_device] (b and c are new, the iterate is
+ *   old), an lpipm_k_* entry that writes the iterate (lpipm_k_iteration, lpipm_k_tall_normal, lpipm_k_tall_schur,
+ *   lpipm_k_tall_sym_solve), a solve that returned a runtime code (>= 100), lpipm_solve_batch* (which replace the resident
+ *   problem with whichever chunk or member the context solved last: that is nobody's to ask about).  All three solver arms qualify.  Not served: lpipm_solve_batch*, lpipm_solve_f32, column-split contexts.
+ * Cost: one vector launch and one scalar launch over the batch (gridDim.z = the resident count; the grid over a member
+ *   depends on m and n alone), reduction slot 0, and for host destinations a staging block of the context that
+ *   lpipm_get_resident_bytes does not count (the block of lpipm_update_lockstep_vectors).  The iterate is only read. */
+typedef struct { double dual_fun, tau, kappa; int32_t status; int32_t reserved; } lpipm_dual_info;   /* 32 bytes */
+int lpipm_get_duals(lpipm_ctx* ctx, uint64_t member, double* y_out /* nullable */, double* z_out /* nullable */,
+                    lpipm_dual_info* info_out /* nullable */);
+int lpipm_get_duals_device(lpipm_ctx* ctx, void* y_dev /* nullable */, uint64_t ldy, void* z_dev /* nullable */, uint64_t ldz,
+                           lpipm_dual_info* info_out /* host array, one per resident member, nullable */);
+
 /* Device bytes the context holds for its resident problem(s) (arenas + shared matrix with the batch's one kept first factor +
  * factor workspace, and the exponent block of lpipm_set_scaling while scaling is on); 0 before any upload. */
 int lpipm_get_resident_bytes(const lpipm_ctx* ctx, uint64_t* bytes_out);

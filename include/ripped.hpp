@@ -215,28 +215,37 @@ public:
         lpipm_ctx* ctx = nullptr;
         raise_for(lpipm_create(device_, &ctx));
         struct Guard { lpipm_ctx* c; ~Guard() { lpipm_destroy(c); } } guard{ctx};
-        const Matrix& A = problem.A();
-        if (tall_eq_ && problem.n_slack() > 0 && problem.n_slack() <= A.rows && problem.n_slack() < A.cols) {
-            // A = [[X I], [A_eq 0]]: the `ub` block is the first n_slack rows, the `eq` block the rest, both with lda = cols
-            const std::size_t m_ub = problem.n_slack(), m_eq = A.rows - m_ub;
-            raise_for(lpipm_upload_ub_eq_tall(ctx, A.cols - m_ub, m_ub, A.data.data(), A.cols, problem.b().data(), m_eq,
-                                              m_eq ? A.data.data() + m_ub * A.cols : nullptr, A.cols,
-                                              m_eq ? problem.b().data() + m_ub : nullptr, problem.c().data(), problem.c0()));
-        } else if (tall_ && problem.n_slack() == A.rows && problem.n_slack() < A.cols)
-            // `ub` rows only: A = [X I], X = the first cols - n_slack columns (lda = cols); the slack costs are zero
-            raise_for(lpipm_upload_ub_tall(ctx, A.cols - problem.n_slack(), A.rows, A.data.data(), A.cols, problem.b().data(),
-                                           problem.c().data(), problem.c0()));
-        else
-        // n_slack tells the backend that the last columns are the [I; 0] slack block (linear_program.rs:147-161)
-        raise_for(lpipm_upload_slack(ctx, A.rows, A.cols, A.data.data(), A.cols, problem.b().data(),
-                                     problem.c().data(), problem.c0(), problem.n_slack()));
-        std::vector<double> x(A.cols);
+        std::vector<double> x;
         double fun = 0.0;
         uint64_t it = 0;
-        const int rc = lpipm_solve(ctx, &o_, x.data(), &fun, &it, nullptr);
-        if (rc == LPIPM_ITERATION_LIMIT) raise_for(rc, x);          // payload: x / tau, mod.rs:237-239
-        raise_for(rc);
+        upload_and_solve(ctx, problem, x, fun, it);
         return OptimizeResult(problem.denormalize_x_into(std::move(x)), fun, it);  // mod.rs:165-167
+    }
+    // solve() with the duals of its last iterate (lpipm_get_duals on the same context; tall_form() / tall_eq_form() are
+    // honoured): y_ub, y_eq the multipliers of the `ub` and `eq` rows as ProblemBuilder::build stacks them
+    // (linear_program.rs:145-158; d fun / d b), reduced_costs those of the structural columns, dual_fun = b.y + c0.
+    // A^T y + z = c with z >= 0; the multiplier of a `ub` row is <= 0.  Not in the reference.
+    struct DualResult {
+        OptimizeResult result;
+        std::vector<double> y_ub, y_eq, reduced_costs;
+        double dual_fun;
+    };
+    DualResult solve_with_duals(const Problem& problem) const {
+        lpipm_ctx* ctx = nullptr;
+        raise_for(lpipm_create(device_, &ctx));
+        struct Guard { lpipm_ctx* c; ~Guard() { lpipm_destroy(c); } } guard{ctx};
+        std::vector<double> x;
+        double fun = 0.0;
+        uint64_t it = 0;
+        upload_and_solve(ctx, problem, x, fun, it);
+        const Matrix& A = problem.A();
+        std::vector<double> y(A.rows), z(A.cols);
+        lpipm_dual_info info{};
+        raise_for(lpipm_get_duals(ctx, 0, y.data(), z.data(), &info));
+        const std::size_t ns = problem.n_slack();
+        return DualResult{OptimizeResult(problem.denormalize_x_into(std::move(x)), fun, it),
+                          std::vector<double>(y.begin(), y.begin() + ns), std::vector<double>(y.begin() + ns, y.end()),
+                          std::vector<double>(z.begin(), z.end() - ns), info.dual_fun};
     }
     // The f32 instantiation of the same `solve` (src/float.rs:42-43): every operation in f32, lpipm_solve_f32.  With the
     // default tol = 1e-8 an f32 solve cannot satisfy the optimality test (the reference's behaviour): pass 1e-4 .. 1e-5.
@@ -256,6 +265,28 @@ public:
     }
 
 private:
+    // What solve() and solve_with_duals() share: the upload of `problem` in the form the opt-ins select, and lpipm_solve.
+    void upload_and_solve(lpipm_ctx* ctx, const Problem& problem, std::vector<double>& x, double& fun, uint64_t& it) const {
+        const Matrix& A = problem.A();
+        if (tall_eq_ && problem.n_slack() > 0 && problem.n_slack() <= A.rows && problem.n_slack() < A.cols) {
+            // A = [[X I], [A_eq 0]]: the `ub` block is the first n_slack rows, the `eq` block the rest, both with lda = cols
+            const std::size_t m_ub = problem.n_slack(), m_eq = A.rows - m_ub;
+            raise_for(lpipm_upload_ub_eq_tall(ctx, A.cols - m_ub, m_ub, A.data.data(), A.cols, problem.b().data(), m_eq,
+                                              m_eq ? A.data.data() + m_ub * A.cols : nullptr, A.cols,
+                                              m_eq ? problem.b().data() + m_ub : nullptr, problem.c().data(), problem.c0()));
+        } else if (tall_ && problem.n_slack() == A.rows && problem.n_slack() < A.cols)
+            // `ub` rows only: A = [X I], X = the first cols - n_slack columns (lda = cols); the slack costs are zero
+            raise_for(lpipm_upload_ub_tall(ctx, A.cols - problem.n_slack(), A.rows, A.data.data(), A.cols, problem.b().data(),
+                                           problem.c().data(), problem.c0()));
+        else
+        // n_slack tells the backend that the last columns are the [I; 0] slack block (linear_program.rs:147-161)
+        raise_for(lpipm_upload_slack(ctx, A.rows, A.cols, A.data.data(), A.cols, problem.b().data(),
+                                     problem.c().data(), problem.c0(), problem.n_slack()));
+        x.assign(A.cols, 0.0);
+        const int rc = lpipm_solve(ctx, &o_, x.data(), &fun, &it, nullptr);
+        if (rc == LPIPM_ITERATION_LIMIT) raise_for(rc, x);          // payload: x / tau, mod.rs:237-239
+        raise_for(rc);
+    }
     lpipm_opts o_;
     int device_;
     bool tall_ = false, tall_eq_ = false;

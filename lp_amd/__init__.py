@@ -152,6 +152,14 @@ class Problem:
     def denormalize_x_into(self, x_slack: np.ndarray) -> np.ndarray:   # :65-69
         return np.array(x_slack[: x_slack.shape[0] - self._n_slack])
 
+    def denormalize_duals(self, y: np.ndarray, z: np.ndarray):
+        """The counterpart of denormalize_x_into for the duals of the slack form (Context.duals): the rows split as
+        ProblemBuilder::build stacks them (linear_program.rs:145-158: the `ub` rows first, one slack column each, then the
+        `eq` rows), z cut to the structural columns.  -> (y_ub, y_eq, reduced_costs)"""
+        y, z = np.asarray(y), np.asarray(z)
+        ns = self._n_slack
+        return np.array(y[:ns]), np.array(y[ns:]), np.array(z[: z.shape[0] - ns])
+
 
 class ProblemBuilder:
     """linear_program.rs:72-170."""
@@ -295,6 +303,9 @@ def _solve_batch(ctx, problems, opts, tall, x_dev_ptr=None, row_stride=0):
     members = (_ptrs(As), _ptrs(bs), _ptrs(cs), (C.c_double * K)(*c0s), C.byref(opts))
     out, unpack = _members_out(K, xs)
     L = _capi.lib()
+    # the call replaces the context's resident problem with whatever it solved last: nothing the context recorded describes it
+    ctx.m = ctx.n = ctx._m_eq = ctx._members = 0
+    ctx._lock = None
     if tall:
         rc = L.lpipm_solve_batch_ub_tall(ctx._h, K, m, n, *members, x_host, x_dev, int(row_stride), *out)
     elif ns is not None:
@@ -375,6 +386,7 @@ class Context:
                                f"{_capi.last_error_detail()} -- a HIP device is required, there is no CPU path")
         self.device = int(device)
         self.n = self.m = 0
+        self._members = 1            # resident members: 1 after a single upload, the count of a lockstep batch
         self._m_eq = 0               # `eq` rows of the resident upload_tall_eq problem; every upload that succeeds sets it with m and n
 
     def close(self):
@@ -400,7 +412,7 @@ class Context:
             A_ub, b_ub, c = _f64(A_ub), _f64(b_ub), _f64(c)
             m_ub, n = A_ub.shape[0], c.shape[0]
             _raise_for(_capi.lib().lpipm_upload_ub_tall(self._h, n, m_ub, _p(A_ub), n, _p(b_ub), _p(c), float(problem.c0())))
-            self.m, self.n, self._m_eq = m_ub, n + m_ub, 0
+            self.m, self.n, self._m_eq, self._members = m_ub, n + m_ub, 0, 1
             return self
         if use_slack_structure and getattr(problem, "_parts", None) is not None:
             # device-side assembly: the ub / eq blocks as given, no host slack matrix (lpipm_upload_ub_eq)
@@ -410,7 +422,7 @@ class Context:
                                                 m_eq, _p(A_eq) if m_eq else None, n, _p(b_eq) if m_eq else None,
                                                 _p(c), float(problem.c0()))
             _raise_for(rc)
-            self.m, self.n, self._m_eq = m_ub + m_eq, n + m_ub, 0
+            self.m, self.n, self._m_eq, self._members = m_ub + m_eq, n + m_ub, 0, 1
             return self
         A, b, c = _f64(problem.A()), _f64(problem.b()), _f64(problem.c())
         return self.upload_arrays(A, b, c, problem.c0(), problem.n_slack() if use_slack_structure else 0)
@@ -428,7 +440,7 @@ class Context:
         rc = _capi.lib().lpipm_upload_ub_eq_tall(self._h, n, m_ub, _p(A_ub), n, _p(b_ub), m_eq, _p(A_eq) if m_eq else None, n,
                                                  _p(b_eq) if m_eq else None, _p(c), float(problem.c0()))
         _raise_for(rc)
-        self.m, self.n, self._m_eq = m_ub + m_eq, n + m_ub, m_eq
+        self.m, self.n, self._m_eq, self._members = m_ub + m_eq, n + m_ub, m_eq, 1
         return self
 
     def upload_arrays(self, A, b, c, c0=0.0, n_slack=0):
@@ -438,7 +450,7 @@ class Context:
         m, n = A.shape
         rc = _capi.lib().lpipm_upload_slack(self._h, m, n, _p(A), n, _p(b), _p(c), float(c0), int(n_slack))
         _raise_for(rc)
-        self.m, self.n, self._m_eq = m, n, 0
+        self.m, self.n, self._m_eq, self._members = m, n, 0, 1
         return self
 
     def update_vectors(self, b, c):
@@ -469,7 +481,7 @@ class Context:
         del keep
         if batch:
             self._lock = (K, nb, n_out, None, None, [np.empty(d.n)])     # (_lockstep_form reads the length of a c[i] from it)
-        self.m, self.n, self._m_eq = nb, n_out, 0
+        self.m, self.n, self._m_eq, self._members = nb, n_out, 0, K
         return self
 
     def update_vectors_device(self, b, c):
@@ -581,7 +593,7 @@ class Context:
             raise IncompatibleInputDimensions()
         m, nl = A.shape
         _raise_for(_capi.lib().lpipm_upload_nsplit(self._h, m, int(n_total), nl, _p(A), nl, _p(b), _p(c), float(c0)))
-        self.m, self.n, self._m_eq = m, nl, 0
+        self.m, self.n, self._m_eq, self._members = m, nl, 0, 1
         return self
 
     def _upload_members(self, entry, head, bs, cs, c0s, m, n, nc, matrix, tail=()):
@@ -593,7 +605,7 @@ class Context:
         c0 = (C.c_double * K)(*[float(v) for v in c0s]) if c0s is not None else None
         _raise_for(getattr(_capi.lib(), entry)(self._h, K, *head, _ptrs(bs), _ptrs(cs), c0, *tail))
         self._lock = (K, m, n, matrix, bs, cs)      # keep the host arrays alive only for the duration of the call chain
-        self.m, self.n, self._m_eq = m, n, 0
+        self.m, self.n, self._m_eq, self._members = m, n, 0, K
         return self
 
     def upload_lockstep(self, As, bs, cs, c0s=None, n_slack=0):
@@ -743,6 +755,52 @@ class Context:
                 r = log[i]
                 rows.append((r.alpha, r.rho_p, r.rho_d, r.rho_A, r.rho_g, r.rho_mu, r.obj))
         return rc, x, fun.value, int(it.value), rows
+
+    def _duals_lengths(self):
+        """(members, len(y), len(z)) of what is resident, as the uploads recorded them; BackendError when nothing is (before an
+        upload, after solve_batch*): the getter's buffers are never sized for another problem than the one C holds."""
+        if self._members < 1 or self.m < 1 or self.n < 1:
+            raise BackendError("no resident problem on this context: upload and solve before asking for duals")
+        return self._members, self.m, self.n
+
+    def duals(self, member: int = 0) -> dict:
+        """The duals of resident member `member` (0 for a single LP) at the iterate of the LAST solve on this context
+        (lpipm_get_duals): dict(y, z, dual_fun, tau, kappa) -- y the multipliers of the upload's rows, z the reduced costs, as
+        long as x_slack, both in the caller's units; A'y + z = c, z >= 0, d fun / d b_i = y_i.  A member without a solution
+        raises its LinearProgramError subclass; a context without a completed solve raises BackendError."""
+        _, m, n = self._duals_lengths()
+        y, z = np.full(m, np.nan), np.full(n, np.nan)
+        info = _capi.DualInfo()
+        _raise_for(_capi.lib().lpipm_get_duals(self._h, int(member), _p(y), _p(z), C.byref(info)))
+        return dict(y=y, z=z, dual_fun=info.dual_fun, tau=info.tau, kappa=info.kappa)
+
+    def _get_duals_device(self, y_ptr, ldy, z_ptr, ldz):
+        """lpipm_get_duals_device -> the lpipm_dual_info records, one per resident member."""
+        info = (_capi.DualInfo * self._duals_lengths()[0])()
+        _raise_for(_capi.lib().lpipm_get_duals_device(self._h, C.c_void_p(int(y_ptr)) if y_ptr else None, int(ldy),
+                                                      C.c_void_p(int(z_ptr)) if z_ptr else None, int(ldz), info))
+        return info
+
+    def duals_lockstep(self, members: int | None = None) -> list:
+        """Context.duals of the first `members` (default: all) members of the resident lockstep batch after its
+        solve_lockstep[_device]: a list of that dict, None for a member without a solution.  One lpipm_get_duals_device into
+        one device block and one copy of that block to the host, whatever the count: the same bits as one lpipm_get_duals per
+        member."""
+        import torch
+        K, m, n = self._duals_lengths()
+        block = torch.empty((K, m + n), dtype=torch.float64, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(self.device).synchronize()      # (the block may be recycled memory torch still works on)
+        info = self._get_duals_device(block.data_ptr(), m + n, block.data_ptr() + 8 * m, m + n)
+        keep = K if members is None else min(int(members), K)
+        rows = block[:keep].cpu().numpy()
+        return [dict(y=rows[k, :m].copy(), z=rows[k, m:].copy(), dual_fun=info[k].dual_fun, tau=info[k].tau, kappa=info[k].kappa)
+                if has_x(info[k].status) else None for k in range(keep)]
+
+    def duals_device(self, y_ptr, ldy: int, z_ptr, ldz: int) -> list:
+        """The duals of every resident member left in HBM (lpipm_get_duals_device): member i's y to the device row
+        y_ptr + i * ldy doubles, its z to z_ptr + i * ldz; a null (0 / None) pointer skips those vectors, the rows of a member
+        without a solution stay untouched.  Complete on return.  -> list of (status, dual_fun | None)"""
+        return [(r.status, r.dual_fun if has_x(r.status) else None) for r in self._get_duals_device(y_ptr, ldy, z_ptr, ldz)]
 
     def solve_f32(self, A, b, c, c0: float = 0.0, opts: "_capi.Opts | None" = None, want_log: bool = False):
         """InteriorPoint<f32>::solve on a slack-form problem (src/float.rs:42-43; lpipm_solve_f32): every operation in f32.
@@ -1031,7 +1089,9 @@ class InteriorPoint(Solver):
         ctx.upload(problem)
         return self.solve_uploaded(ctx, problem)
 
-    def solve_uploaded(self, ctx: Context, problem: Problem, want_log=False):
+    def solve_uploaded(self, ctx: Context, problem: Problem, want_log=False, want_duals=False):
+        """want_duals: the result also carries y_ub, y_eq, reduced_costs (Problem.denormalize_duals of Context.duals) and
+        dual_fun of the solve's last iterate."""
         rc, x_slack, fun, it, rows = ctx.solve_raw(self.opts(), want_log=want_log)
         if rc == _capi.ITERATION_LIMIT:
             raise IterationLimitExceeded(x_slack)            # mod.rs:237-239 (payload: x / tau, slack form)
@@ -1040,4 +1100,18 @@ class InteriorPoint(Solver):
         if want_log:
             res.log = rows
             res.x_slack = x_slack
+        if want_duals:
+            d = ctx.duals()
+            res.y_ub, res.y_eq, res.reduced_costs = problem.denormalize_duals(d["y"], d["z"])
+            res.dual_fun = d["dual_fun"]
         return res
+
+    def solve_with_duals(self, problem: Problem) -> OptimizeResult:
+        """solve(problem) with the duals of its last iterate: the OptimizeResult plus y_ub, y_eq (the multipliers of the `ub`
+        and `eq` rows, d fun / d b), reduced_costs (of the structural columns) and dual_fun.  (A Problem<f32> has none:
+        lpipm_solve_f32 releases its problem inside the call.)"""
+        if problem.dtype == np.float32:
+            raise ValueError("solve_with_duals needs a float64 Problem")
+        ctx = default_context(self.device)
+        ctx.upload(problem)
+        return self.solve_uploaded(ctx, problem, want_duals=True)

@@ -30,6 +30,11 @@ class PhaseTimes(C.Structure):  # lpipm_phase_times
                 ("gemv_passes", C.c_uint64)]
 
 
+class DualInfo(C.Structure):  # lpipm_dual_info (32 bytes)
+    _fields_ = [("dual_fun", C.c_double), ("tau", C.c_double), ("kappa", C.c_double), ("status", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 FORM_SLACK, FORM_UB_EQ, FORM_UB_TALL = range(3)     # lpipm_device_problem.form
 SRC_F64, SRC_F32 = range(2)                           # lpipm_device_problem.src_type
 
@@ -93,6 +98,8 @@ SYMBOLS = {
                                             C.POINTER(Opts), _dpp, _vp, _u64, _dp, C.POINTER(_u64), C.POINTER(C.c_int32)]),
     "lpipm_solve_batch_slack": (C.c_int, [_vp, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), _dpp, _dpp, _dpp, _dp,
                                           C.POINTER(Opts), _dpp, _vp, _u64, _dp, C.POINTER(_u64), C.POINTER(C.c_int32)]),
+    "lpipm_get_duals": (C.c_int, [_vp, _u64, _dp, _dp, C.POINTER(DualInfo)]),
+    "lpipm_get_duals_device": (C.c_int, [_vp, _vp, _u64, _vp, _u64, C.POINTER(DualInfo)]),
     "lpipm_get_resident_bytes": (C.c_int, [_vp, C.POINTER(_u64)]),
     "lpipm_solve_lockstep": (C.c_int, [_vp, C.POINTER(Opts), _dpp, _dp, C.POINTER(_u64), C.POINTER(C.c_int32)]),
     "lpipm_solve_lockstep_device": (C.c_int, [_vp, C.POINTER(Opts), _vp, _u64, _dp, C.POINTER(_u64), C.POINTER(C.c_int32)]),

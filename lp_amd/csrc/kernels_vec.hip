@@ -629,6 +629,41 @@ __global__ void k_scalar_fun(VecArgs a) {
     }
 }
 
+// y / tau and z / tau of the final iterate in the caller's units (the division first, then the power of two: as k_final_x +
+// k_unscale_x do for x), and the partials of dual_fun = b.(y / tau) from the resident vectors (DualsOut, vec_kernels.hpp)
+__global__ __launch_bounds__(256) void k_final_duals(VecArgs a, DualsOut d) {
+    const long long lp = (long long)a.bfirst + blockIdx.z;
+    if (!d.mask[lp]) return;
+    if (!vbatch(a, false)) return;
+    const int32_t* kr = d.kr ? d.kr + lp * d.estride : nullptr;
+    const int32_t* kc = d.kr ? d.kc + lp * d.estride : nullptr;
+    double* yo = d.y ? d.y + (lp - d.row0) * d.ldy : nullptr;
+    double* zo = d.z ? d.z + (lp - d.row0) * d.ldz : nullptr;
+    const int stride = gridDim.x * 256;
+    const double tau = a.S[S_TAU];
+    double acc[1] = {0};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
+        const double v = a.y[i] / tau;
+        acc[0] += a.b[i] * v;
+        if (yo) yo[i] = kr ? ldexp(v, kr[i]) : v;
+    }
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < a.n && zo; j += stride) {
+        const double v = a.z[j] / tau;
+        zo[j] = kc ? ldexp(v, -kc[j]) : v;
+    }
+    block_reduce_store<1, false>(acc, a.red, 0);
+}
+__global__ void k_scalar_duals(VecArgs a, DualsOut d) {
+    const long long lp = (long long)a.bfirst + blockIdx.z;
+    if (!d.mask[lp]) return;
+    if (!vbatch(a, false)) return;
+    const double s = fold_sum(a.red, 0, a.nblk);
+    if (threadIdx.x == 0) {
+        double* o = d.info + 3 * (lp - d.row0);
+        o[0] = s + a.S[S_C0]; o[1] = a.S[S_TAU]; o[2] = a.S[S_KAPPA];
+    }
+}
+
 // ---------------------------------------------------------------- launchers
 static inline dim3 vgrid(const VecArgs& a) { return dim3(a.nblk, 1, a.bcount); }
 static inline dim3 sgrid(const VecArgs& a) { return dim3(1, 1, a.bcount); }
@@ -712,6 +747,10 @@ int vec_final_x(const VecArgs& a, double* xout, hipStream_t st, const XRank* xr)
     if (int rc = cross(a, xr, 0, 1, 0, -1, 0, 1, st)) return rc;     // c.(x/tau)
     hipLaunchKernelGGL(k_scalar_fun, sgrid(a), dim3(64), 0, st, a);
     return 0;
+}
+void vec_final_duals(const VecArgs& a, const DualsOut& d, hipStream_t st) {
+    hipLaunchKernelGGL(k_final_duals, vgrid(a), dim3(256), 0, st, a, d);
+    hipLaunchKernelGGL(k_scalar_duals, sgrid(a), dim3(64), 0, st, a, d);
 }
 // One column group of M (its tiles, in the grouped tile list's order) <-> a contiguous block, for the group-by-group
 // cross-rank sum of the column-split mode.  One workgroup per tile.

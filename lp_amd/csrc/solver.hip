@@ -184,6 +184,12 @@ struct lpipm_ctx {
     bool first_valid = false;    // sys[SYS_FIRST] holds iteration 1 of this upload (every member's); dropped by any upload.  A
                                  //   half-batch view holds the parent's value for the length of one solve
     bool first_done = false;     // the last solve of this context (or view) got through its iteration 1
+    // lpipm_get_duals[_device]: the arena holds the final iterate of the last solve, and last_ret every member's return code of
+    // it.  Up from a solve that returned Ok until anything changes what the iterate means (invalidate_duals).  A half-batch
+    // view writes its members' codes into its parent's record.
+    bool duals_valid = false;
+    std::vector<int32_t> last_ret;
+    lpipm_ctx* parent = nullptr; // of a half-batch view: the context whose batch it covers
     // what building a shared-matrix batch's one factor took, until the solve it preceded reports it (lpipm_phase_times)
     double build_adat_ms = 0.0, build_potrf_ms = 0.0;
     uint64_t build_launches = 0;
@@ -230,6 +236,8 @@ struct lpipm_ctx {
 };
 
 static void destroy_views(lpipm_ctx* c);      // half-batch views of a lockstep batch (solve_lockstep)
+// The iterate in the arena no longer belongs to a completed solve of the resident b and c (lpipm_get_duals: LPIPM_ERR_NO_PROBLEM).
+static void invalidate_duals(lpipm_ctx* c) { c->duals_valid = false; }
 namespace lpipm { lpipm_ctx_device lpipm_ctx_device_of(lpipm_ctx* c) { return lpipm_ctx_device{c->device, c->rs.st}; } }
 
 // Cross-rank reduction of `count` doubles at a device pointer, ordered after everything enqueued on the ctx's stream
@@ -942,6 +950,7 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
     LP_HIP(hipSetDevice(c->device));
     destroy_views(c); // half-batch views hold copies of the geometry and of the device pointers
     c->first_valid = false;   // whatever is kept belongs to the matrix that is being replaced
+    invalidate_duals(c);
     Problem& p = c->p;
     hipStream_t st = c->rs.st;
     const Geometry g = geometry_of(u, n_slack, c->first_cache, c->refine);
@@ -1751,6 +1760,7 @@ static void report_times(lpipm_ctx* c, uint64_t loop_iterations, bool replay) {
 // mirrors the same decisions from the status records to count iterations and pick the return codes.
 static int solve_members(lpipm_ctx* c, const lpipm_opts* o, Members members, const SolveOut& out) {
     if (!c || !o) return LPIPM_ERR_BAD_ARGUMENT;
+    if (!c->is_view) invalidate_duals(c);                 // up again when this solve returns Ok (a view's parent: solve_lockstep)
     const bool batch = members == Members::Lockstep;
     // wait_start.  A single LP: the host needs the starting point's indicators only for the `disp` table, for the selective
     // refinement's first decision and for the phase marks: otherwise the first iteration is enqueued without a round trip to
@@ -1877,6 +1887,9 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, Members members, con
     LP_HIP(hipStreamSynchronize(st));
     if (bounced) std::memcpy(bounced, rs.x_pinned, c->p.n * sizeof(double));
     report_times(c, loop_iterations, replay);
+    lpipm_ctx* rec = c->is_view ? c->parent : c;          // the return codes lpipm_get_duals goes by
+    if (!c->is_view) { c->last_ret.assign((size_t)B, LPIPM_ERR_NO_PROBLEM); c->duals_valid = true; }
+    for (int i = 0; i < B && rec; ++i) rec->last_ret[(size_t)(c->p.bt.first + i)] = ret[(size_t)i];
     for (int i = 0; i < B; ++i)
         out.res.set((uint64_t)(c->p.bt.first + i), ret[(size_t)i], has_x(ret[(size_t)i]) ? rs.status_host[i].obj : NAN, its[(size_t)i]);
     return LPIPM_OK;
@@ -1939,6 +1952,7 @@ static lpipm_ctx* make_view(const lpipm_ctx* c, int first, int count) {
 // phase marks are per stream) and not for the views themselves.
 static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const SolveOut& out) {
     if (!c || !o || !out.res.status) return LPIPM_ERR_BAD_ARGUMENT;      // (out.x is xout_of's: one destination is there)
+    if (!c->is_view) invalidate_duals(c);
     if (c->is_view || !c->halves_env || c->profiling || c->p.B < 16 || !c->p.has_problem || c->colsplit)
         return solve_members(c, o, Members::Lockstep, out);
     LP_HIP(hipSetDevice(c->device));
@@ -1950,8 +1964,10 @@ static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const SolveOut& out
             if (a) { c->halves.push_back(a); destroy_views(c); }
             return solve_members(c, o, Members::Lockstep, out);
         }
+        a->parent = b->parent = c;
         c->halves.push_back(a); c->halves.push_back(b);
     }
+    c->last_ret.assign((size_t)c->p.B, LPIPM_ERR_NO_PROBLEM);
     LP_TRY(ensure_shared_factor(c, o));             // one factor for the batch: built here, once, before both halves
     c->build_adat_ms = c->build_potrf_ms = 0.0; c->build_launches = 0;   // (nothing is profiled on this path)
     LP_HIP(hipStreamSynchronize(c->rs.st));         // the upload (or whatever else the caller enqueued) precedes both halves
@@ -1966,6 +1982,7 @@ static int solve_lockstep(lpipm_ctx* c, const lpipm_opts* o, const SolveOut& out
     run(0);
     other.join();
     if (use_first && rc[0] == LPIPM_OK && rc[1] == LPIPM_OK && c->halves[0]->first_done && c->halves[1]->first_done) c->first_valid = true;
+    c->duals_valid = rc[0] == LPIPM_OK && rc[1] == LPIPM_OK;
     return rc[0] != LPIPM_OK ? rc[0] : rc[1];
 }
 
@@ -2144,7 +2161,7 @@ static int solve_rest(lpipm_ctx* c, const BatchRequest& q, const std::vector<uin
 //     fit the memory budget: one launch per kernel for the whole chunk (group_members, chunk_size, split_chunks, solve_chunks).
 //  3. The rest (odd shapes, a chunk's odd member, QR arms) go one by one through the worker pool (solve_rest).
 // Every member's result depends only on its own inputs.  The planning of 1 and 2 touches no device (batch_plan.hpp).
-static int batch_impl(lpipm_ctx* c, const BatchRequest& q, const lpipm_opts* o, const XArgs& xa, const Results& res) {
+static int batch_members(lpipm_ctx* c, const BatchRequest& q, const lpipm_opts* o, const XArgs& xa, const Results& res) {
     XOut xo;
     if (q.x_always || q.count || xa.host_rows || xa.dev)
         LP_TRY(xout_of(xa, xo, q.has_lens() ? q.count : 0, [&](uint64_t i) { return q.row_len(i); }));
@@ -2170,6 +2187,15 @@ static int batch_impl(lpipm_ctx* c, const BatchRequest& q, const lpipm_opts* o, 
     for (uint64_t i = 0; i < q.count; ++i)
         if (!taken[i]) rest.push_back(i);
     return solve_rest(c, q, ns, rest, o, xo, res);
+}
+// The chunks and the members solved one at a time are uploaded and solved on c itself (and on its workers), and each of those
+// solves leaves its own duals behind: whichever member c happened to solve last.  None of that is the caller's resident
+// problem, so on every way out of the batch the getter finds nothing (lpipm_get_duals: LPIPM_ERR_NO_PROBLEM).
+static int batch_impl(lpipm_ctx* c, const BatchRequest& q, const lpipm_opts* o, const XArgs& xa, const Results& res) {
+    if (c) invalidate_duals(c);
+    const int rc = batch_members(c, q, o, xa, res);
+    if (c) invalidate_duals(c);
+    return rc;
 }
 
 extern "C" int lpipm_solve_batch(lpipm_ctx* c, uint64_t count, const uint64_t* m, const uint64_t* n,
@@ -2289,6 +2315,7 @@ extern "C" int lpipm_update_vectors(lpipm_ctx* c, const double* b, const double*
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
     if (c->p.B != 1 || c->colsplit || c->p.from_parts) return LPIPM_ERR_UNSUPPORTED;
     LP_HIP(hipSetDevice(c->device));
+    invalidate_duals(c);                      // b and c are new, the iterate is old
     // (the padding beyond m and n stays zero; A, and with it the kept first factor, is not touched)
     LP_HIP(hipMemcpyAsync((void*)c->p.va.b, b, c->p.m * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
     LP_HIP(hipMemcpyAsync((void*)c->p.va.c, cc, c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
@@ -2303,6 +2330,7 @@ extern "C" int lpipm_update_vectors_device(lpipm_ctx* c, const void* b_dev, cons
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
     if (c->p.B != 1 || c->colsplit || c->p.from_parts) return LPIPM_ERR_UNSUPPORTED;
     LP_HIP(hipSetDevice(c->device));
+    invalidate_duals(c);                      // b and c are new, the iterate is old
     const Dim db{c->p.m, 1}, dc{c->p.n, 1};
     LP_TRY(source_inside(c, b_dev, &db, 1, sizeof(double)));
     LP_TRY(source_inside(c, c_dev, &dc, 1, sizeof(double)));
@@ -2343,6 +2371,7 @@ static int update_lockstep_impl(lpipm_ctx* c, uint64_t count, const double* cons
             if ((has_b && !b[i]) || (has_c && !cc[i])) return LPIPM_ERR_BAD_ARGUMENT;
     } else if ((has_b && ldb < m) || (has_c && ldc < nc)) return LPIPM_ERR_BAD_ARGUMENT;
     LP_HIP(hipSetDevice(c->device));
+    invalidate_duals(c);                      // b and c are new, the iterate is old
     hipStream_t st = c->rs.st;
     // the staged block: [b rows | c rows | c0], each part only if it is sent from the host
     const size_t nb_st = host && has_b ? B * m : 0, nc_st = host && has_c ? B * nc : 0, n0_st = c0 ? B : 0;
@@ -2374,6 +2403,84 @@ extern "C" int lpipm_update_lockstep_vectors(lpipm_ctx* c, uint64_t count, const
 extern "C" int lpipm_update_lockstep_vectors_device(lpipm_ctx* c, uint64_t count, const void* b_dev, uint64_t ldb,
                                                     const void* c_dev, uint64_t ldc, const double* c0) {
     return update_lockstep_impl(c, count, nullptr, nullptr, false, (const double*)b_dev, ldb, (const double*)c_dev, ldc, c0);
+}
+
+// ---- duals of the last solve (lpipm_get_duals, lpipm_get_duals_device) ---------------------------------------------------
+// What both entries check first, in this order: the context, a resident problem, no column split, a completed solve whose
+// iterate still means something (lpipm_ctx::duals_valid).
+static int duals_ready(const lpipm_ctx* c) {
+    if (!c) return LPIPM_ERR_BAD_ARGUMENT;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (c->colsplit) return LPIPM_ERR_UNSUPPORTED;
+    if (!c->duals_valid || c->last_ret.size() != (size_t)c->p.B) return LPIPM_ERR_NO_PROBLEM;
+    return LPIPM_OK;
+}
+// One launch of k_final_duals + its scalar kernel over the whole resident batch, delivering the members [row0, row0 + rows)
+// whose last status has a solution.  Device destinations (y_dev, z_dev; member k's rows at k - row0) are written directly;
+// host ones (want_y / want_z with null device pointers) go through the context's staging block, which also carries the mask
+// in and the {dual_fun, tau, kappa} triples out.  On return *ys / *zs / *infos point at the staged rows (m, n and 3 doubles each).
+struct DualsRun { const double *ys = nullptr, *zs = nullptr, *infos = nullptr; };
+static int run_duals(lpipm_ctx* c, size_t row0, size_t rows, bool want_y, bool want_z, double* y_dev, uint64_t ldy, double* z_dev,
+                     uint64_t ldz, DualsRun& out) {
+    const Problem& p = c->p;
+    const size_t B = (size_t)p.B, m = (size_t)p.m, n = (size_t)p.n;
+    const bool stage_y = want_y && !y_dev, stage_z = want_z && !z_dev;
+    const size_t nmask = (B + 1) / 2, ninfo = 3 * rows, ny = stage_y ? rows * m : 0, nz = stage_z ? rows * n : 0;
+    LP_TRY(stage_grow(c, nmask + ninfo + ny + nz));
+    hipStream_t st = c->rs.st;
+    int32_t* mask = (int32_t*)c->stage_host;
+    bool any = false;
+    for (size_t k = 0; k < B; ++k) {
+        mask[k] = k >= row0 && k < row0 + rows && has_x(c->last_ret[k]) ? 1 : 0;
+        any = any || mask[k] != 0;
+    }
+    out.infos = c->stage_host + nmask; out.ys = out.infos + ninfo; out.zs = out.ys + ny;
+    if (!any) return LPIPM_OK;
+    LP_HIP(hipMemcpyAsync(c->stage_dev, c->stage_host, nmask * sizeof(double), hipMemcpyHostToDevice, st));
+    double* dev = c->stage_dev + nmask;
+    DualsOut d{};
+    d.info = dev; d.row0 = (long long)row0; d.mask = (const int32_t*)c->stage_dev;
+    d.y = stage_y ? dev + ninfo : y_dev; d.ldy = (long long)(stage_y ? m : ldy);
+    d.z = stage_z ? dev + ninfo + ny : z_dev; d.ldz = (long long)(stage_z ? n : ldz);
+    if (p.scale_passes > 0) { d.kr = p.sc.kr; d.kc = p.sc.kc; d.estride = p.sc.estride; }
+    vec_final_duals(p.va, d, st);
+    LP_HIP(hipGetLastError());
+    LP_HIP(hipMemcpyAsync(c->stage_host + nmask, dev, (ninfo + ny + nz) * sizeof(double), hipMemcpyDeviceToHost, st));
+    LP_HIP(hipStreamSynchronize(st));
+    return LPIPM_OK;
+}
+static lpipm_dual_info dual_info_of(const double* triple, int32_t status) {
+    return triple ? lpipm_dual_info{triple[0], triple[1], triple[2], status, 0} : lpipm_dual_info{NAN, NAN, NAN, status, 0};
+}
+extern "C" int lpipm_get_duals(lpipm_ctx* c, uint64_t member, double* y_out, double* z_out, lpipm_dual_info* info_out) {
+    LP_TRY(duals_ready(c));
+    if (member >= (uint64_t)c->p.B) return LPIPM_ERR_BAD_ARGUMENT;
+    const int32_t code = c->last_ret[(size_t)member];
+    if (!has_x(code)) return code;                   // the member's own outcome; nothing is written
+    LP_HIP(hipSetDevice(c->device));
+    DualsRun r;
+    LP_TRY(run_duals(c, (size_t)member, 1, y_out != nullptr, z_out != nullptr, nullptr, 0, nullptr, 0, r));
+    if (y_out) std::memcpy(y_out, r.ys, c->p.m * sizeof(double));
+    if (z_out) std::memcpy(z_out, r.zs, c->p.n * sizeof(double));
+    if (info_out) *info_out = dual_info_of(r.infos, code);
+    return LPIPM_OK;
+}
+extern "C" int lpipm_get_duals_device(lpipm_ctx* c, void* y_dev, uint64_t ldy, void* z_dev, uint64_t ldz, lpipm_dual_info* info_out) {
+    LP_TRY(duals_ready(c));
+    const uint64_t B = (uint64_t)c->p.B;
+    if ((y_dev && ldy < c->p.m) || (z_dev && ldz < c->p.n)) return LPIPM_ERR_BAD_ARGUMENT;
+    LP_HIP(hipSetDevice(c->device));
+    // nothing is launched before both destinations are known to be device memory that holds every member's row
+    const Dim dy[2] = {{B, (int64_t)ldy}, {c->p.m, 1}}, dz[2] = {{B, (int64_t)ldz}, {c->p.n, 1}};
+    if (y_dev) LP_TRY(source_inside(c, y_dev, dy, 2, sizeof(double)));
+    if (z_dev) LP_TRY(source_inside(c, z_dev, dz, 2, sizeof(double)));
+    DualsRun r;
+    LP_TRY(run_duals(c, 0, (size_t)B, false, false, (double*)y_dev, ldy, (double*)z_dev, ldz, r));
+    for (uint64_t k = 0; k < B && info_out; ++k) {
+        const int32_t code = c->last_ret[(size_t)k];
+        info_out[k] = dual_info_of(has_x(code) ? r.infos + 3 * k : nullptr, code);
+    }
+    return LPIPM_OK;
 }
 
 extern "C" int lpipm_set_profiling(lpipm_ctx* c, int on) {
@@ -2489,6 +2596,7 @@ static int tall_entry_system(lpipm_ctx* c, const double* dinv, bool factor, int 
     hipStream_t st = c->rs.st;
     NormalSystem& K = c->p.sys[SYS_WORK];
     const std::vector<double> ones((size_t)c->p.n, 1.0);
+    invalidate_duals(c);
     vec_blind_start(c->p.va, st);                  // clears done / flags; the iterate is overwritten next
     if (nrhs > 0) LP_TRY(tall_eq_reset(c));
     LP_HIP(hipMemcpyAsync(c->p.va.x, dinv, c->p.n * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2967,6 +3075,7 @@ extern "C" int lpipm_k_iteration(lpipm_ctx* c, const lpipm_opts* o, int ip, doub
     VecArgs& v = c->p.va;
     hipStream_t st = c->rs.st;
     const Iter it{.refine_now = c->refine == 2};
+    invalidate_duals(c);
     vec_blind_start(v, st);                                   // clears done / flags; the iterate is overwritten next
     LP_TRY(tall_eq_reset(c));
     LP_HIP(hipMemcpyAsync(v.x, x, c->p.n * sizeof(double), hipMemcpyHostToDevice, st));

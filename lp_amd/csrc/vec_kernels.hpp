@@ -86,6 +86,21 @@ bool vec_fused(const VecArgs& a);
 void vec_fused_predictor(const VecArgs& a, int ip, hipStream_t st);                  // vec_pq_uv + vec_delta(0) + vec_corr_setup
 void vec_fused_corrector(const VecArgs& a, int ip, double alpha0, hipStream_t st);   // vec_uv_corr + vec_delta(1) + vec_step
 int  vec_final_x(const VecArgs& a, double* xout, hipStream_t st, const XRank* xr = nullptr);
+// The duals of the iterate the arena holds (lpipm_get_duals[_device]): for every member k of the launch whose mask word is
+// set, y / tau (m entries) and z / tau (n entries) of the resident problem taken to the caller's units -- y_i by kr[i], z_j by
+// -kc[j] (ScaleBuf's exponents, set k's estride * k further; kr null: unscaled) -- into row k - row0 of y (ldy doubles per
+// row) and of z (ldz), either of which may be null, and {b.(y / tau) + c0, tau, kappa} into the 3 doubles of row k - row0 of
+// info.  a is the resident batch's (bfirst 0, bcount = its count): the grid over a member is a.nblk workgroups whatever the
+// count, so the sum has the same bits from a single LP and from any batch.  Reduction slot 0 is used; the iterate is only read.
+struct DualsOut {
+    double* y; long long ldy;
+    double* z; long long ldz;
+    double* info;
+    long long row0;
+    const int32_t* mask;
+    const int32_t *kr, *kc; long long estride;
+};
+void vec_final_duals(const VecArgs& a, const DualsOut& d, hipStream_t st);
 // Y[q][i] += add_q[i] (i < m): the addend of a column-split A.w after its cross-rank sum
 // packed has mp*(mp+128)/2 doubles; dir 0 = M -> packed, 1 = packed -> M (mp a multiple of 128, ld even)
 void vec_pack_lower(double* M, long long ld, int mp, double* packed, int dir, hipStream_t st);
