@@ -566,11 +566,18 @@ int lpipm_get_phase_times(const lpipm_ctx* ctx, lpipm_phase_times* out);
 /* ---- kernel-granularity entry points ---------------------------------------------------------
  * Each runs ONE stage of the hot path on the uploaded problem / the given operands so that the
  * parity tests can compare it with the oracle's restatement of the cited reference lines.
- * Host pointers in, host pointers out (copies are outside any timing the library reports). */
+ * Host pointers in, host pointers out (copies are outside any timing the library reports).
+ * An `ms_out` (nullable) is device time between two HIP events on the context's stream, taken in one of two ways:
+ *   per repeat    what the entry launches is bracketed and the stream drained `repeats` (>= 1) times over, one after the other;
+ *                 the mean of the brackets.  lpipm_k_adat, lpipm_k_potrf, lpipm_k_chol_solve, lpipm_k_gemv_n, lpipm_k_gemv_t,
+ *                 lpipm_k_gemv_dual, lpipm_k_mfma_f64_probe (three repeats) and lpipm_k_qr_solve (one).  What a repeat needs put
+ *                 back first (the matrix lpipm_k_potrf factors in place, the right-hand sides lpipm_k_chol_solve overwrites) is
+ *                 enqueued ahead of its bracket.
+ *   back to back  one bracket around `repeats` launches enqueued without a drain between them, divided by `repeats`.
+ *                 lpipm_k_pack_matrix only. */
 
 /* newton_equations.rs:54-57:  M = A . diag(dinv) . A^T.  dinv[n]; M_out m x m row-major, LOWER
- * triangle valid (the strict upper triangle is unspecified).  `ms_out` (nullable) gets the device
- * time of the kernel launch(es) averaged over `repeats` (>= 1) back-to-back launches. */
+ * triangle valid (the strict upper triangle is unspecified).  ms_out: the launches of one build, per repeat. */
 int lpipm_k_adat(lpipm_ctx* ctx, const double* dinv, double* M_out, int repeats, double* ms_out);   /* tall upload: LPIPM_ERR_UNSUPPORTED */
 /* The resident image of the stored structural block of member `member` (0 for a single LP and for a shared-matrix batch), as
  * the solves read it: mp x npa doubles (rows padded to 128, stored columns to 16, zeros beyond m and the stored columns), after
@@ -604,7 +611,8 @@ int lpipm_k_tall_sym_solve(lpipm_ctx* ctx, const double* dinv, int nrhs, const d
  * upload, a batch of such LPs included: LPIPM_ERR_UNSUPPORTED.  The iterate of the context is overwritten. */
 int lpipm_k_tall_schur(lpipm_ctx* ctx, const double* dinv, double* S_out);
 /* newton_equations.rs:129-131: in-place lower Cholesky of the m x m row-major matrix M (lower
- * triangle read, lower triangle written).  info_out: 0, or k+1 for the first non-positive pivot. */
+ * triangle read, lower triangle written).  info_out: 0, or k+1 for the first non-positive pivot.
+ * ms_out: the factorisation's launches, per repeat. */
 int lpipm_k_potrf(lpipm_ctx* ctx, uint64_t m, double* M_inout, int32_t* info_out, int repeats,
                   double* ms_out);
 /* After lpipm_k_potrf at size m on this ctx: the explicit inverses of the factor's diagonal super-blocks as the solves read
@@ -626,7 +634,8 @@ int lpipm_k_trsm_lt_lockstep(lpipm_ctx* ctx, uint64_t n, int count, int rows, in
                              const double* B, uint64_t ldb, double* Z_inout, int32_t* infos_out,
                              const int32_t* done_mask /* nullable */);
 /* newton_equations.rs:151-169: V[r] = L^-T L^-1 R[r] for nrhs (1 or 2) right-hand sides, with
- * L = the factor of a preceding lpipm_k_potrf on this ctx (kept on device).  R, V: nrhs x m. */
+ * L = the factor of a preceding lpipm_k_potrf on this ctx (kept on device).  R, V: nrhs x m.
+ * ms_out: the sweep's launches, per repeat. */
 int lpipm_k_chol_solve(lpipm_ctx* ctx, uint64_t m, int nrhs, const double* R, double* V,
                        int repeats, double* ms_out);
 /* The same solve as two calls of the sweep: the forward steps [0, split) of the super-blocks, then the rest of the forward
@@ -651,11 +660,11 @@ int lpipm_k_symv_residual(lpipm_ctx* ctx, uint64_t m, const double* M, int nrhs,
 /* newton_equations.rs:133-149, :155-166 (the Inverse / LeastSquares arms): V[r] = R^-1 Q^T R[r] with
  * M = QR a Householder factorisation of the symmetric m x m matrix M (row-major; only the lower
  * triangle is read), nrhs 1|2, m <= 16384.  info_out: 0, or k+1 for a zero column / zero R[k][k].
- * ms_out: device time of factorisation + solves. */
+ * ms_out: factorisation and solves in one bracket (one repeat). */
 int lpipm_k_qr_solve(lpipm_ctx* ctx, uint64_t m, const double* M, int nrhs, const double* R, double* V,
                      int32_t* info_out, double* ms_out);
 /* A.w (feasible_point.rs:122, newton_equations.rs:220, residual.rs:23): nrhs (1|2) vectors,
- * W nrhs x n -> Y nrhs x m. */
+ * W nrhs x n -> Y nrhs x m.  ms_out (also of lpipm_k_gemv_t and lpipm_k_gemv_dual): one pass, per repeat. */
 int lpipm_k_gemv_n(lpipm_ctx* ctx, int nrhs, const double* W, double* Y, int repeats, double* ms_out);
 /* A^T.v (feasible_point.rs:123, newton_equations.rs:223, residual.rs:25): V nrhs x m -> U nrhs x n */
 int lpipm_k_gemv_t(lpipm_ctx* ctx, int nrhs, const double* V, double* U, int repeats, double* ms_out);
@@ -694,7 +703,8 @@ int lpipm_k_generic_solve_f64(lpipm_ctx* ctx, uint64_t m, uint64_t n, const doub
                               uint64_t* iterations_out, lpipm_iter_row* log);
 
 /* fp64 MFMA issue-rate probe (v_mfma_f64_16x16x4_f64 back to back, operands in registers):
- * tflops_out = achieved TFLOP/s over the whole chip; used to confirm the roofline denominator. */
+ * tflops_out = achieved TFLOP/s over the whole chip; used to confirm the roofline denominator.  ms_out: one launch, per
+ * repeat, three repeats. */
 int lpipm_k_mfma_f64_probe(lpipm_ctx* ctx, int iters, double* tflops_out, double* ms_out);
 
 /* ---- synthetic inputs (SURVEY.md 8d / BASELINE.md 3) -----------------------------------------

@@ -108,6 +108,29 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _rows(a, length):
+    """`a` as the 1 or 2 contiguous float64 rows of `length` entries a kernel entry reads (a vector is one row); any other shape
+    is IncompatibleInputDimensions."""
+    a = np.atleast_2d(_f64(a))
+    if a.ndim != 2 or a.shape[0] not in (1, 2) or a.shape[1] != length:
+        raise IncompatibleInputDimensions()
+    return a
+
+
+def _vec(a, length):
+    a = _f64(a)
+    if a.shape != (length,):
+        raise IncompatibleInputDimensions()
+    return a
+
+
+def _square(M):
+    M = _f64(M)
+    if M.ndim != 2 or M.shape[0] != M.shape[1]:
+        raise IncompatibleInputDimensions()
+    return M
+
+
 # ------------------------------------------------------------------------------ linear_program.rs
 class Problem:
     """A linear program in slack form (linear_program.rs:24-30): min c'x st A x == b, x >= 0."""
@@ -844,9 +867,16 @@ class Context:
         _capi.lib().lpipm_get_phase_times(self._h, C.byref(t))
         return {k: getattr(t, k) for k, _ in _capi.PhaseTimes._fields_}
 
-    # ---- kernel-granularity entry points (parity tests / micro-benchmarks)
+    # ---- kernel-granularity entry points (parity tests / micro-benchmarks).  The C entries read what the resident shape or
+    # the given m says, so every array is checked against that first: a wrong shape is IncompatibleInputDimensions, and no
+    # entry is handed a buffer shorter than it reads.
+    def _need_problem(self):
+        """Raises what every entry raises without a resident problem (self.m and self.n mean nothing then)."""
+        _raise_for(_capi.lib().lpipm_k_resident_matrix(self._h, 0, 0, 0, None, 0, None, None))
+
     def k_adat(self, dinv, repeats=1):
-        dinv = _f64(dinv)
+        self._need_problem()
+        dinv = _vec(dinv, self.n)
         M = np.empty((self.m, self.m))
         ms = C.c_double(0)
         _raise_for(_capi.lib().lpipm_k_adat(self._h, _p(dinv), _p(M), repeats, C.byref(ms)))
@@ -886,7 +916,7 @@ class Context:
         return U, V, info.value
 
     def k_potrf(self, M, repeats=1):
-        L = _f64(M).copy()
+        L = _square(M).copy()
         info, ms = C.c_int32(0), C.c_double(0)
         _raise_for(_capi.lib().lpipm_k_potrf(self._h, L.shape[0], _p(L), C.byref(info), repeats, C.byref(ms)))
         return L, info.value, ms.value
@@ -902,7 +932,9 @@ class Context:
 
     def k_potrf_lockstep(self, Ms):
         """The factors and info words of `count` m x m matrices factored as ONE lockstep batch."""
-        L = np.ascontiguousarray(_f64(Ms)).copy()
+        L = _f64(Ms).copy()
+        if L.ndim != 3 or L.shape[1] != L.shape[2]:
+            raise IncompatibleInputDimensions()
         count, m = L.shape[0], L.shape[1]
         infos = np.zeros(count, dtype=np.int32)
         _raise_for(_capi.lib().lpipm_k_potrf_lockstep(self._h, m, count, _p(L), infos.ctypes.data_as(C.POINTER(C.c_int32))))
@@ -934,7 +966,7 @@ class Context:
         return Z, infos
 
     def k_chol_solve(self, m, R, repeats=1):
-        R = np.atleast_2d(_f64(R))
+        R = _rows(R, int(m))
         V = np.empty_like(R)
         ms = C.c_double(0)
         _raise_for(_capi.lib().lpipm_k_chol_solve(self._h, m, R.shape[0], _p(R), _p(V), repeats, C.byref(ms)))
@@ -942,20 +974,22 @@ class Context:
 
     def k_chol_solve_split(self, m, R, split):
         """k_chol_solve as two calls of the sweep: forward steps [0, split), then the rest."""
-        R = np.atleast_2d(_f64(R))
+        R = _rows(R, int(m))
         V = np.empty_like(R)
         _raise_for(_capi.lib().lpipm_k_chol_solve_split(self._h, m, R.shape[0], _p(R), _p(V), split))
         return V
 
     def k_symv_residual(self, M, V, R0):
-        M = _f64(M); V = np.atleast_2d(_f64(V)); R0 = np.atleast_2d(_f64(R0))
+        M = _square(M); V = _rows(V, M.shape[0]); R0 = _rows(R0, M.shape[0])
+        if R0.shape != V.shape:
+            raise IncompatibleInputDimensions()
         Rho = np.empty_like(V)
         _raise_for(_capi.lib().lpipm_k_symv_residual(self._h, M.shape[0], _p(M), V.shape[0], _p(V), _p(R0), _p(Rho)))
         return Rho
 
     def k_qr_solve(self, M, R):
-        M = _f64(M)
-        R = np.atleast_2d(_f64(R))
+        M = _square(M)
+        R = _rows(R, M.shape[0])
         V = np.empty_like(R)
         info, ms = C.c_int32(0), C.c_double(0)
         _raise_for(_capi.lib().lpipm_k_qr_solve(self._h, M.shape[0], _p(M), R.shape[0], _p(R), _p(V), C.byref(info),
@@ -963,14 +997,16 @@ class Context:
         return V, info.value, ms.value
 
     def k_gemv_n(self, W, repeats=1):
-        W = np.atleast_2d(_f64(W))
+        self._need_problem()
+        W = _rows(W, self.n)
         Y = np.empty((W.shape[0], self.m))
         ms = C.c_double(0)
         _raise_for(_capi.lib().lpipm_k_gemv_n(self._h, W.shape[0], _p(W), _p(Y), repeats, C.byref(ms)))
         return Y, ms.value
 
     def k_gemv_t(self, V, repeats=1):
-        V = np.atleast_2d(_f64(V))
+        self._need_problem()
+        V = _rows(V, self.m)
         U = np.empty((V.shape[0], self.n))
         ms = C.c_double(0)
         _raise_for(_capi.lib().lpipm_k_gemv_t(self._h, V.shape[0], _p(V), _p(U), repeats, C.byref(ms)))
@@ -979,7 +1015,8 @@ class Context:
     def k_iteration(self, opts, x, y, z, tau, kappa, ip=False):
         """One loop body of solve_normal_form from the given iterate (lpipm_k_iteration).
         -> dict(x, y, z, tau, kappa, d_x, d_y, d_z, d_tau, d_kappa, alpha, info)"""
-        x, y, z = _f64(x).copy(), _f64(y).copy(), _f64(z).copy()
+        self._need_problem()
+        x, y, z = _vec(x, self.n).copy(), _vec(y, self.m).copy(), _vec(z, self.n).copy()
         tk = np.array([float(tau), float(kappa)])
         dx, dy, dz, dtk, al = np.empty(self.n), np.empty(self.m), np.empty(self.n), np.empty(2), np.empty(1)
         info = C.c_int32(0)
@@ -989,7 +1026,8 @@ class Context:
                     d_kappa=float(dtk[1]), alpha=float(al[0]), info=info.value)
 
     def k_gemv_dual(self, w, v, repeats=1):
-        w, v = _f64(w), _f64(v)
+        self._need_problem()
+        w, v = _vec(w, self.n), _vec(v, self.m)
         Aw, ATv = np.empty(self.m), np.empty(self.n)
         ms = C.c_double(0)
         _raise_for(_capi.lib().lpipm_k_gemv_dual(self._h, _p(w), _p(v), _p(Aw), _p(ATv), repeats, C.byref(ms)))

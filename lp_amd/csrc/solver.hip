@@ -2496,11 +2496,18 @@ extern "C" int lpipm_get_phase_times(const lpipm_ctx* c, lpipm_phase_times* out)
 
 // ------------------------------------------------------------------------------------------------
 // kernel-granularity entry points (parity tests / micro-benchmarks)
-template <typename F>
-static int timed_repeats(lpipm_ctx* c, int repeats, double* ms_out, F&& body) {
+// The two timers.  Every ms_out of the entries comes from one of them; nothing else records ev_begin / ev_end.
+// 1. A bracket per repeat: `prepare` (untimed: what a repeat needs put back first), ev_begin, `body`, ev_end, a drain of the
+//    stream; *ms_out is the mean over the repeats.  lpipm_k_adat, lpipm_k_gemv_*, lpipm_k_mfma_f64_probe (no prepare),
+//    lpipm_k_potrf (prepare restores the matrix the factorisation overwrote), lpipm_k_chol_solve (prepare reloads the
+//    right-hand sides the solve overwrote) and lpipm_k_qr_solve (one repeat): each launch sequence alone on an idle device.
+static int no_prepare() { return LPIPM_OK; }
+template <typename F, typename P = int (*)()>
+static int timed_repeats(lpipm_ctx* c, int repeats, double* ms_out, F&& body, P prepare = no_prepare) {
     if (repeats < 1) repeats = 1;
     float total = 0.f;
     for (int r = 0; r < repeats; ++r) {
+        LP_TRY(prepare());
         LP_HIP(hipEventRecord(c->rs.ev_begin, c->rs.st));
         LP_TRY(body());
         LP_HIP(hipEventRecord(c->rs.ev_end, c->rs.st));
@@ -2512,6 +2519,53 @@ static int timed_repeats(lpipm_ctx* c, int repeats, double* ms_out, F&& body) {
     if (ms_out) *ms_out = total / repeats;
     return LPIPM_OK;
 }
+// 2. One bracket around `repeats` launches back to back; *ms_out is the bracket over the repeats.  lpipm_k_pack_matrix, for its
+//    launch and for the runtime's copy beside it: a copy's rate is that of a queue kept full (profiles/device_upload.md).
+template <typename F>
+static int timed_back_to_back(lpipm_ctx* c, int repeats, double* ms_out, F&& launch) {
+    if (repeats < 1) repeats = 1;
+    LP_HIP(hipEventRecord(c->rs.ev_begin, c->rs.st));
+    for (int r = 0; r < repeats; ++r) LP_HIP(launch());
+    LP_HIP(hipEventRecord(c->rs.ev_end, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
+    float ms = 0.f;
+    LP_HIP(hipEventElapsedTime(&ms, c->rs.ev_begin, c->rs.ev_end));
+    if (ms_out) *ms_out = (double)ms / repeats;
+    return LPIPM_OK;
+}
+
+// `rows` rows of `width` doubles from a block of row length ld_src to one of row length ld_dst: every size in doubles.  Every
+// strided copy of the entries is one of these.
+static hipError_t copy_rows(double* dst, size_t ld_dst, const double* src, size_t ld_src, size_t width, size_t rows, hipMemcpyKind kind,
+                            hipStream_t st) {
+    const size_t D = sizeof(double);
+    return hipMemcpy2DAsync(dst, ld_dst * D, src, ld_src * D, width * D, rows, kind, st);
+}
+static hipError_t rows_to_device(double* dst, size_t ld_dev, const double* src, size_t ld_host, size_t width, size_t rows, hipStream_t st) {
+    return copy_rows(dst, ld_dev, src, ld_host, width, rows, hipMemcpyHostToDevice, st);
+}
+static hipError_t rows_to_host(double* dst, size_t ld_host, const double* src, size_t ld_dev, size_t width, size_t rows, hipStream_t st) {
+    return copy_rows(dst, ld_host, src, ld_dev, width, rows, hipMemcpyDeviceToHost, st);
+}
+
+// Device memory for the length of one entry.  Whichever way the entry is left, the destructor drains the stream the memory was
+// used on and only then frees it: nothing enqueued may outlive what it reads or writes.
+struct DeviceTemp {
+    hipStream_t st;
+    std::vector<void*> taken;
+    explicit DeviceTemp(hipStream_t s) : st(s) {}
+    DeviceTemp(const DeviceTemp&) = delete;
+    ~DeviceTemp() { (void)hipStreamSynchronize(st); free_list(taken); }
+    template <typename T>
+    int take(T** out, size_t count, bool zero) {
+        void* p = nullptr;
+        LP_HIP(hipMalloc(&p, count * sizeof(T)));
+        taken.push_back(p);
+        if (zero) LP_HIP(hipMemsetAsync(p, 0, count * sizeof(T), st));
+        *out = (T*)p;
+        return LPIPM_OK;
+    }
+};
 
 extern "C" int lpipm_k_resident_matrix(lpipm_ctx* c, uint64_t member, uint64_t rows, uint64_t cols, double* out, uint64_t ld,
                                        uint64_t* mp_out, uint64_t* npa_out) {
@@ -2524,8 +2578,7 @@ extern "C" int lpipm_k_resident_matrix(lpipm_ctx* c, uint64_t member, uint64_t r
     if (rows == 0 || cols == 0) return LPIPM_OK;
     LP_HIP(hipSetDevice(c->device));
     const char* img = (const char*)p.A + (p.shared_a ? 0 : (size_t)member * p.bstride);
-    LP_HIP(hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), img, (size_t)p.npa * sizeof(double), (size_t)cols * sizeof(double), (size_t)rows,
-                            hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(rows_to_host(out, ld, (const double*)img, (size_t)p.npa, cols, rows, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
 }
@@ -2544,36 +2597,19 @@ extern "C" int lpipm_k_pack_matrix(lpipm_ctx* c, const lpipm_device_problem* d, 
     if (q.u.m != p.m || q.u.n != p.n || q.u.count != (uint64_t)p.B || q.u.shared != p.shared_a || q.u.tall != p.tall ||
         q.u.parts.has_value() != p.from_parts || (q.u.parts && q.u.n_slack != (uint64_t)p.ns))     // (parts: the same `ub` rows, so the same columns)
         return LPIPM_ERR_BAD_ARGUMENT;
-    if (repeats < 1) repeats = 1;
     hipStream_t st = c->rs.st;
     const PackMatrix pm = pack_matrix_of(p, *d);
     const bool f32 = d->src_type == LPIPM_SRC_F32;
     const int members = member_strided(d) ? p.B : 1;
-    auto timed = [&](double* ms_out, auto&& body) -> int {
-        LP_HIP(hipEventRecord(c->rs.ev_begin, st));
-        for (int r = 0; r < repeats; ++r) LP_HIP(body());
-        LP_HIP(hipEventRecord(c->rs.ev_end, st));
-        LP_HIP(hipStreamSynchronize(st));
-        float ms = 0.f;
-        LP_HIP(hipEventElapsedTime(&ms, c->rs.ev_begin, c->rs.ev_end));
-        if (ms_out) *ms_out = (double)ms / repeats;
-        return LPIPM_OK;
-    };
-    LP_TRY(timed(pack_ms_out, [&] { return launch_pack_matrix(pm, f32, members, st); }));
+    LP_TRY(timed_back_to_back(c, repeats, pack_ms_out, [&] { return launch_pack_matrix(pm, f32, members, st); }));
     // the runtime's copy of as many bytes: the launch reads elements of the source type and writes doubles
     const size_t elems = (size_t)members * (size_t)p.m * (size_t)p.nx;
     const size_t bytes = elems * (src_elem_bytes(d->src_type) + sizeof(double)) / 2;
-    void *from = nullptr, *to = nullptr;
-    if (hipMalloc(&from, bytes) != hipSuccess || hipMalloc(&to, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        if (from) (void)hipFree(from);
-        return LPIPM_ERR_HIP;
-    }
-    int rc = hipMemsetAsync(from, 0, bytes, st) == hipSuccess ? LPIPM_OK : LPIPM_ERR_HIP;
-    if (rc == LPIPM_OK) rc = timed(copy_ms_out, [&] { return hipMemcpyDtoDAsync((hipDeviceptr_t)to, (hipDeviceptr_t)from, bytes, st); });
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(from); (void)hipFree(to);
-    return rc;
+    DeviceTemp tmp{st};
+    char *from = nullptr, *to = nullptr;
+    LP_TRY(tmp.take(&from, bytes, true));
+    LP_TRY(tmp.take(&to, bytes, false));
+    return timed_back_to_back(c, repeats, copy_ms_out, [&] { return hipMemcpyDtoDAsync((hipDeviceptr_t)to, (hipDeviceptr_t)from, bytes, st); });
 }
 
 extern "C" int lpipm_k_adat(lpipm_ctx* c, const double* dinv, double* M_out, int repeats, double* ms_out) {
@@ -2583,8 +2619,7 @@ extern "C" int lpipm_k_adat(lpipm_ctx* c, const double* dinv, double* M_out, int
     LP_HIP(hipSetDevice(c->device));
     LP_HIP(hipMemcpyAsync(c->p.va.dinv, dinv, c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
     LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int { LP_HIP(build_system(c, c->p.sys[SYS_WORK], Batch{}, BuildOpts{.M2 = c->p.M0})); return LPIPM_OK; }));
-    LP_HIP(hipMemcpy2DAsync(M_out, c->p.m * sizeof(double), c->p.sys[SYS_WORK].M, (size_t)c->p.mp * sizeof(double),
-                            c->p.m * sizeof(double), c->p.m, hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(rows_to_host(M_out, c->p.m, c->p.sys[SYS_WORK].M, (size_t)c->p.mp, c->p.m, c->p.m, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
 }
@@ -2614,8 +2649,7 @@ extern "C" int lpipm_k_tall_normal(lpipm_ctx* c, const double* dinv, double* K_o
     LP_HIP(hipSetDevice(c->device));
     LP_TRY(tall_entry_system(c, dinv, false));
     const size_t nx = (size_t)c->p.nx;
-    LP_HIP(hipMemcpy2DAsync(K_out, nx * sizeof(double), c->p.sys[SYS_WORK].M, (size_t)c->p.tv.nxp * sizeof(double), nx * sizeof(double), nx,
-                            hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(rows_to_host(K_out, nx, c->p.sys[SYS_WORK].M, (size_t)c->p.tv.nxp, nx, nx, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
 }
@@ -2629,8 +2663,7 @@ extern "C" int lpipm_k_tall_schur(lpipm_ctx* c, const double* dinv, double* S_ou
     LP_TRY(tall_entry_system(c, dinv, true));
     LP_TRY(tall_eq_schur(c, false));
     const size_t me = (size_t)t.me;
-    LP_HIP(hipMemcpy2DAsync(S_out, me * sizeof(double), c->p.sys[SYS_SCHUR].M, (size_t)t.mep * sizeof(double), me * sizeof(double), me,
-                            hipMemcpyDeviceToHost, st));
+    LP_HIP(rows_to_host(S_out, me, c->p.sys[SYS_SCHUR].M, (size_t)t.mep, me, me, st));
     LP_HIP(hipMemsetAsync(c->p.va.potrf_info, 0, sizeof(int32_t), st));      // the solver expects a clean word
     LP_HIP(hipStreamSynchronize(st));
     return LPIPM_OK;
@@ -2646,47 +2679,41 @@ extern "C" int lpipm_k_tall_sym_solve(lpipm_ctx* c, const double* dinv, int nrhs
     const TallArgs& t = c->p.tv;
     const size_t n = (size_t)c->p.n, m = (size_t)c->p.m, np = (size_t)c->p.np, mp = (size_t)c->p.mp;
     // the right-hand sides on the device, rows padded as the solver's own vectors are: R1 as [nrhs][np], R2 as [nrhs][mp]
+    DeviceTemp tmp{st};
     double* rhs = nullptr;
-    LP_HIP(hipMalloc((void**)&rhs, 2 * (np + mp) * sizeof(double)));
+    LP_TRY(tmp.take(&rhs, 2 * (np + mp), true));
     double* r1 = rhs;
     double* r2 = rhs + 2 * np;
     int32_t info = 0;
     lpipm_opts o;
     lpipm_default_opts(&o);
-    auto run = [&]() -> int {
-        LP_HIP(hipMemsetAsync(rhs, 0, 2 * (np + mp) * sizeof(double), st));
-        LP_HIP(hipMemcpy2DAsync(r1, np * sizeof(double), R1, n * sizeof(double), n * sizeof(double), (size_t)nrhs, hipMemcpyHostToDevice, st));
-        LP_HIP(hipMemcpy2DAsync(r2, mp * sizeof(double), R2, m * sizeof(double), m * sizeof(double), (size_t)nrhs, hipMemcpyHostToDevice, st));
-        const double* r1b = nrhs == 2 ? r1 + np : nullptr;
-        const double* r2b = nrhs == 2 ? r2 + mp : nullptr;
-        LP_TRY(tall_entry_system(c, dinv, true, nrhs, r1, r2, r1b, r2b));
-        if (c->p.tall_eq) LP_TRY(tall_eq_schur(c));
-        LP_TRY(sym_solve(c, Iter{}, &o, SymRhs{nrhs, r1, r2, r1b, r2b}));
-        if (nrhs == 2) tall_pq_uv(v, t, r1, r1b, st);
-        else           tall_uv_corr(v, t, r1, st);
-        LP_HIP(hipGetLastError());
-        // nrhs == 2: (p, q) and (u, v) as the predictor leaves them; nrhs == 1: (u, v) as the corrector does
-        if (nrhs == 2) LP_HIP(hipMemcpyAsync(U_out, v.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
-        LP_HIP(hipMemcpyAsync(U_out + (nrhs == 2 ? n : 0), v.u, n * sizeof(double), hipMemcpyDeviceToHost, st));
-        LP_HIP(hipMemcpy2DAsync(V_out, m * sizeof(double), v.R, mp * sizeof(double), m * sizeof(double), (size_t)nrhs, hipMemcpyDeviceToHost, st));
-        LP_HIP(hipMemcpyAsync(&info, v.potrf_info, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        LP_HIP(hipMemsetAsync(v.potrf_info, 0, sizeof(int32_t), st));     // the solver expects a clean word
-        LP_HIP(hipStreamSynchronize(st));
-        return LPIPM_OK;
-    };
-    const int rc = run();
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(rhs);
-    if (rc == LPIPM_OK && info_out) *info_out = info;
-    return rc;
+    LP_HIP(rows_to_device(r1, np, R1, n, n, (size_t)nrhs, st));
+    LP_HIP(rows_to_device(r2, mp, R2, m, m, (size_t)nrhs, st));
+    const double* r1b = nrhs == 2 ? r1 + np : nullptr;
+    const double* r2b = nrhs == 2 ? r2 + mp : nullptr;
+    LP_TRY(tall_entry_system(c, dinv, true, nrhs, r1, r2, r1b, r2b));
+    if (c->p.tall_eq) LP_TRY(tall_eq_schur(c));
+    LP_TRY(sym_solve(c, Iter{}, &o, SymRhs{nrhs, r1, r2, r1b, r2b}));
+    if (nrhs == 2) tall_pq_uv(v, t, r1, r1b, st);
+    else           tall_uv_corr(v, t, r1, st);
+    LP_HIP(hipGetLastError());
+    // nrhs == 2: (p, q) and (u, v) as the predictor leaves them; nrhs == 1: (u, v) as the corrector does
+    if (nrhs == 2) LP_HIP(hipMemcpyAsync(U_out, v.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    LP_HIP(hipMemcpyAsync(U_out + (nrhs == 2 ? n : 0), v.u, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    LP_HIP(rows_to_host(V_out, m, v.R, mp, m, (size_t)nrhs, st));
+    LP_HIP(hipMemcpyAsync(&info, v.potrf_info, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    LP_HIP(hipMemsetAsync(v.potrf_info, 0, sizeof(int32_t), st));     // the solver expects a clean word
+    LP_HIP(hipStreamSynchronize(st));
+    if (info_out) *info_out = info;
+    return LPIPM_OK;
 }
 
-// dst (mp x mp, zeroed) <- [[M, 0], [0, I]] from the host's m x m M; pad: mp - m ones, which must outlive the copies
-static hipError_t copy_padded(double* dst, int mp, const double* M, size_t m, const std::vector<double>& pad, hipStream_t st) {
-    const size_t D = sizeof(double);
-    const hipError_t e = hipMemcpy2DAsync(dst, (size_t)mp * D, M, m * D, m * D, m, hipMemcpyHostToDevice, st);
+// dst (mp x mp, zeroed) <- [[M, 0], [0, I]] from the host's m x m M (mp - m < NB; the ones outlive every copy)
+static hipError_t copy_padded(double* dst, int mp, const double* M, size_t m, hipStream_t st) {
+    static const std::vector<double> ones((size_t)NB, 1.0);
+    const hipError_t e = rows_to_device(dst, (size_t)mp, M, m, m, m, st);
     if (e != hipSuccess || (size_t)mp == m) return e;
-    return hipMemcpy2DAsync(dst + m * mp + m, (size_t)(mp + 1) * D, pad.data(), D, D, mp - m, hipMemcpyHostToDevice, st);
+    return rows_to_device(dst + m * mp + m, (size_t)mp + 1, ones.data(), 1, 1, mp - m, st);      // (the diagonal: one double per "row")
 }
 static int kbuf_ensure(lpipm_ctx* c, int mp) {
     lpipm_ctx::KernelScratch& k = c->k;
@@ -2713,6 +2740,27 @@ static int kbuf_ensure(lpipm_ctx* c, int mp) {
     return LPIPM_OK;
 }
 
+// Debug aid (LPIPM_DIAG_STAMPS): one more factorisation of the pristine copy with the cycle stamps of its first diagonal-block
+// kernel collected, printed to stderr.  Best effort: a failure prints nothing.
+static void dump_diag_stamps(lpipm_ctx* c, int mp) {
+    DeviceTemp tmp{c->rs.st};
+    long long* d = nullptr; long long h[64] = {0};
+    if (tmp.take(&d, 64, true) != LPIPM_OK) return;
+    g_diag_stamps = d;
+    (void)hipMemcpyAsync(c->k.plan.L, c->k.M0, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToDevice, c->rs.st);
+    (void)launch_potrf(c->k.plan, c->k.info, c->rs.st);
+    (void)hipStreamSynchronize(c->rs.st);
+    g_diag_stamps = nullptr;
+    (void)hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
+    fprintf(stderr, "diag stamps (cycles): E(0) %lld, P tile + wait for all eight on wave 0 %lld, barrier to barrier (k = 1) %lld, "
+            "all block columns %lld, last stores %lld\n  k = 1, cycles after the barrier, per wave: P tile done",
+            h[1]-h[0], h[2]-h[1], h[3]-h[1], h[6]-h[0], h[7]-h[6]);
+    for (int w = 0; w < 16; ++w) fprintf(stderr, " %lld", h[32 + w] - h[1]);
+    fprintf(stderr, "\n  at the next barrier");
+    for (int w = 0; w < 16; ++w) fprintf(stderr, " %lld", h[16 + w] - h[1]);
+    fprintf(stderr, "\n");
+}
+
 extern "C" int lpipm_k_potrf(lpipm_ctx* c, uint64_t m, double* M_inout, int32_t* info_out, int repeats,
                              double* ms_out) {
     if (!c || !M_inout || m == 0 || m > (1u << 20)) return LPIPM_ERR_BAD_ARGUMENT;
@@ -2720,47 +2768,18 @@ extern "C" int lpipm_k_potrf(lpipm_ctx* c, uint64_t m, double* M_inout, int32_t*
     const int mp = (int)round_up(m, NB);
     LP_TRY(kbuf_ensure(c, mp));
     // padded pristine copy: [[M, 0], [0, I]]
-    std::vector<double> pad((size_t)(mp - m), 1.0);
     LP_HIP(hipMemsetAsync(c->k.M0, 0, (size_t)mp * mp * sizeof(double), c->rs.st));
-    LP_HIP(copy_padded(c->k.M0, mp, M_inout, m, pad, c->rs.st));
+    LP_HIP(copy_padded(c->k.M0, mp, M_inout, m, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
-    if (repeats < 1) repeats = 1;
-    float total = 0.f;
-    for (int r = 0; r < repeats; ++r) {
+    auto restore = [&]() -> int {      // the factorisation is in place: every repeat starts from the pristine copy
         LP_HIP(hipMemcpyAsync(c->k.plan.L, c->k.M0, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToDevice, c->rs.st));
-        LP_HIP(hipEventRecord(c->rs.ev_begin, c->rs.st));
-        LP_HIP(launch_potrf(c->k.plan, c->k.info, c->rs.st, Batch{}, lookahead(c)));
-        LP_HIP(hipEventRecord(c->rs.ev_end, c->rs.st));
-        LP_HIP(hipStreamSynchronize(c->rs.st));
-        float ms = 0.f;
-        LP_HIP(hipEventElapsedTime(&ms, c->rs.ev_begin, c->rs.ev_end));
-        total += ms;
-    }
-    if (ms_out) *ms_out = total / repeats;
-    if (lp_knob("LPIPM_DIAG_STAMPS")) {  // debug aid: cycle stamps of the first diagonal-block kernel
-        long long* d = nullptr; long long h[64] = {0};
-        if (hipMalloc((void**)&d, sizeof(h)) == hipSuccess) {
-            g_diag_stamps = d;
-            (void)hipMemset(d, 0, sizeof(h));
-            (void)hipMemcpyAsync(c->k.plan.L, c->k.M0, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToDevice, c->rs.st);
-            (void)launch_potrf(c->k.plan, c->k.info, c->rs.st);
-            (void)hipStreamSynchronize(c->rs.st);
-            g_diag_stamps = nullptr;
-            (void)hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-            (void)hipFree(d);
-            fprintf(stderr, "diag stamps (cycles): E(0) %lld, P tile + wait for all eight on wave 0 %lld, barrier to barrier (k = 1) %lld, "
-                    "all block columns %lld, last stores %lld\n  k = 1, cycles after the barrier, per wave: P tile done",
-                    h[1]-h[0], h[2]-h[1], h[3]-h[1], h[6]-h[0], h[7]-h[6]);
-            for (int w = 0; w < 16; ++w) fprintf(stderr, " %lld", h[32 + w] - h[1]);
-            fprintf(stderr, "\n  at the next barrier");
-            for (int w = 0; w < 16; ++w) fprintf(stderr, " %lld", h[16 + w] - h[1]);
-            fprintf(stderr, "\n");
-        }
-    }
+        return LPIPM_OK;
+    };
+    LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int { LP_HIP(launch_potrf(c->k.plan, c->k.info, c->rs.st, Batch{}, lookahead(c))); return LPIPM_OK; }, restore));
+    if (lp_knob("LPIPM_DIAG_STAMPS")) dump_diag_stamps(c, mp);
     int32_t info = 0;
     LP_HIP(hipMemcpyAsync(&info, c->k.info, sizeof(int32_t), hipMemcpyDeviceToHost, c->rs.st));
-    LP_HIP(hipMemcpy2DAsync(M_inout, m * sizeof(double), c->k.plan.L, (size_t)mp * sizeof(double), m * sizeof(double), m,
-                            hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(rows_to_host(M_inout, m, c->k.plan.L, (size_t)mp, m, m, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     if (info_out) *info_out = info;
     c->k.chol_valid = true;
@@ -2775,53 +2794,68 @@ extern "C" int lpipm_k_factor_inverses(lpipm_ctx* c, uint64_t m, double* inv_out
     std::fill(inv_out, inv_out + (size_t)mp * mp, 0.0);
     std::fill(invT_out, invT_out + (size_t)mp * mp, 0.0);
     for (const SuperBlock& s : c->k.plan.sbs) {
-        const size_t row = (size_t)s.size * sizeof(double), at = (size_t)s.row0 * mp + s.row0;
-        LP_HIP(hipMemcpy2DAsync(inv_out + at, (size_t)mp * sizeof(double), s.inv, row, row, s.size, hipMemcpyDeviceToHost, c->rs.st));
-        LP_HIP(hipMemcpy2DAsync(invT_out + at, (size_t)mp * sizeof(double), s.invT, row, row, s.size, hipMemcpyDeviceToHost, c->rs.st));
+        const size_t w = (size_t)s.size, at = (size_t)s.row0 * mp + s.row0;
+        LP_HIP(rows_to_host(inv_out + at, (size_t)mp, s.inv, w, w, w, c->rs.st));
+        LP_HIP(rows_to_host(invT_out + at, (size_t)mp, s.invT, w, w, w, c->rs.st));
     }
     LP_HIP(hipStreamSynchronize(c->rs.st));
     if (super_w_out) *super_w_out = c->k.plan.super_w;
     return LPIPM_OK;
 }
 
+// The members of a lockstep factorisation, each in an arena of its own with identical layouts `stride` bytes apart: the padded
+// matrix, the info word, whatever `extra` takes, the inverse storage of the plan.  factor() measures one arena, takes `count`
+// of them zeroed, lays the plan out over member 0's, loads the padded matrices [[M, 0], [0, I]] from the host's `count` m x m
+// ones and enqueues ONE launch_potrf over the members.  The order of the takes, the stride, super_for and merge_edge_for are
+// those of a lockstep solve: the bits of the factors depend on them.
+struct LockstepFactor {
+    hipStream_t st;
+    FactorPlan plan;
+    double* M = nullptr; int32_t* info = nullptr;       // member 0's; member() gives member q's
+    int mp = 0, count = 0;
+    size_t stride = 0;
+    DeviceTemp tmp;
+    explicit LockstepFactor(hipStream_t s) : st(s), tmp(s) {}
+    ~LockstepFactor() {                                 // the plan goes as the memory does: after a drain (tmp frees after this)
+        (void)hipStreamSynchronize(st);
+        factor_plan_destroy(plan);
+    }
+    template <typename T>
+    T* member(T* of_first, int q) const { return (T*)((char*)of_first + (size_t)q * stride); }
+    Batch batch(const int* done = nullptr) const { return Batch{count, (long long)stride, done, 0}; }
+    template <typename Extra>
+    int factor(int mp_, int count_, const double* Ms, size_t m, Extra&& extra) {
+        mp = mp_; count = count_;
+        auto layout = [&](Arena& ar, bool build) -> hipError_t {
+            M = ar.take<double>((size_t)mp * mp);
+            info = ar.take<int32_t>(1);
+            extra(ar);
+            return factor_plan_create(plan, M, mp, mp, ar, build, st, super_for(mp), merge_edge_for(count));
+        };
+        Arena measure;
+        LP_HIP(layout(measure, false));
+        stride = round_up(measure.off + 256, 4096);
+        char* base = nullptr;
+        LP_TRY(tmp.take(&base, stride * (size_t)count, true));
+        Arena real{base};
+        LP_HIP(layout(real, true));
+        for (int q = 0; q < count; ++q) LP_HIP(copy_padded(member(M, q), mp, Ms + (size_t)q * m * m, m, st));
+        LP_HIP(launch_potrf(plan, info, st, batch()));
+        return LPIPM_OK;
+    }
+};
+
 extern "C" int lpipm_k_potrf_lockstep(lpipm_ctx* c, uint64_t m, int count, double* Ms_inout, int32_t* infos_out) {
     if (!c || !Ms_inout || !infos_out || m == 0 || m > 16384 || count < 1 || count > 64) return LPIPM_ERR_BAD_ARGUMENT;
     LP_HIP(hipSetDevice(c->device));
-    const int mp = (int)round_up(m, NB);
     hipStream_t st = c->rs.st;
-    // one member's arena: the padded matrix, the info word, the inverse storage of its plan; identical layouts `stride` apart
-    FactorPlan plan;
-    auto layout = [&](Arena& ar, bool build, double** M, int32_t** info) -> hipError_t {
-        *M = ar.take<double>((size_t)mp * mp);
-        *info = ar.take<int32_t>(1);
-        return factor_plan_create(plan, *M, mp, mp, ar, build, st, super_for(mp), merge_edge_for(count));
-    };
-    double* M0 = nullptr; int32_t* info0 = nullptr;
-    Arena measure;
-    LP_HIP(layout(measure, false, &M0, &info0));
-    const size_t stride = round_up(measure.off + 256, 4096);
-    char* base = nullptr;
-    LP_HIP(hipMalloc((void**)&base, stride * (size_t)count));
-    // every failure leaves through the one exit below, which frees the plan and the buffer
-    hipError_t e = hipMemsetAsync(base, 0, stride * (size_t)count, st);
-    Arena real{base};
-    if (e == hipSuccess) e = layout(real, true, &M0, &info0);
-    const std::vector<double> pad((size_t)(mp - m), 1.0);
-    for (int q = 0; q < count && e == hipSuccess; ++q) {          // padded copies: [[M, 0], [0, I]]
-        double* Mq = (double*)((char*)M0 + (size_t)q * stride);
-        e = copy_padded(Mq, mp, Ms_inout + (size_t)q * m * m, m, pad, st);
+    LockstepFactor f{st};
+    LP_TRY(f.factor((int)round_up(m, NB), count, Ms_inout, m, [](Arena&) {}));
+    for (int q = 0; q < count; ++q) {
+        LP_HIP(rows_to_host(Ms_inout + (size_t)q * m * m, m, f.member(f.M, q), (size_t)f.mp, m, m, st));
+        LP_HIP(hipMemcpyAsync(infos_out + q, f.member(f.info, q), sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
-    if (e == hipSuccess) e = launch_potrf(plan, info0, st, Batch{count, (long long)stride, nullptr, 0});
-    for (int q = 0; q < count && e == hipSuccess; ++q) {
-        e = hipMemcpy2DAsync(Ms_inout + (size_t)q * m * m, m * sizeof(double), (char*)M0 + (size_t)q * stride, (size_t)mp * sizeof(double),
-                             m * sizeof(double), m, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(infos_out + q, (char*)info0 + (size_t)q * stride, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    }
-    const hipError_t es = hipStreamSynchronize(st);               // also on failure: nothing may still use the buffer freed next
-    if (e == hipSuccess) e = es;
-    factor_plan_destroy(plan);
-    (void)hipFree(base);
-    LP_HIP(e);
+    LP_HIP(hipStreamSynchronize(st));
     return LPIPM_OK;
 }
 
@@ -2838,52 +2872,28 @@ extern "C" int lpipm_k_trsm_lt_lockstep(lpipm_ctx* c, uint64_t n, int count, int
     LP_HIP(hipSetDevice(c->device));
     const int mp = (int)round_up(n, NB), rp = (int)round_up((uint64_t)rows, 16);
     hipStream_t st = c->rs.st;
-    const size_t D = sizeof(double);
-    // one member's arena: the padded matrix, the info and done words, its block of B, its Z, the inverse storage of its plan
-    FactorPlan plan;
-    struct Place { double *M, *Bm, *Z; int32_t* info; int* done; } at{};
-    auto layout = [&](Arena& ar, bool build) -> hipError_t {
-        at.M = ar.take<double>((size_t)mp * mp);
-        at.info = ar.take<int32_t>(1); at.done = ar.take<int>(1);
-        at.Bm = ar.take<double>((size_t)rows * cols); at.Z = ar.take<double>((size_t)rp * mp);
-        return factor_plan_create(plan, at.M, mp, mp, ar, build, st, super_for(mp), merge_edge_for(count));
-    };
-    Arena measure;
-    LP_HIP(layout(measure, false));
-    const size_t stride = round_up(measure.off + 256, 4096);
-    char* base = nullptr;
-    LP_HIP(hipMalloc((void**)&base, stride * (size_t)count));
-    // every failure leaves through the one exit below, which frees the plan and the buffer
-    hipError_t e = hipMemsetAsync(base, 0, stride * (size_t)count, st);
-    Arena real{base};
-    if (e == hipSuccess) e = layout(real, true);
-    const std::vector<double> pad((size_t)(mp - n), 1.0);
-    std::vector<int> done((size_t)count, 0);
+    const size_t zsize = (size_t)rp * mp;
+    std::vector<int> done((size_t)count, 0);                      // (declared ahead of `f`: alive until its drain)
     for (int q = 0; q < count && done_mask; ++q) done[(size_t)q] = done_mask[q] != 0;
-    for (int q = 0; q < count && e == hipSuccess; ++q) {          // padded copies: [[M, 0], [0, I]]
-        const size_t off = (size_t)q * stride;
-        double* Mq = (double*)((char*)at.M + off);
-        e = copy_padded(Mq, mp, Ms + (size_t)q * n * n, n, pad, st);
-        if (e == hipSuccess && (q == 0 || !shared_b))
-            e = hipMemcpy2DAsync((char*)at.Bm + off, (size_t)cols * D, B + (size_t)q * rows * ldb, ldb * D, (size_t)cols * D, (size_t)rows,
-                                 hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync((char*)at.Z + off, Z_inout + (size_t)q * rp * mp, (size_t)rp * mp * D, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync((char*)at.done + off, &done[(size_t)q], sizeof(int), hipMemcpyHostToDevice, st);
+    // a member's arena also holds its done word, its block of B and its Z
+    LockstepFactor f{st};
+    int* done0 = nullptr; double *B0 = nullptr, *Z0 = nullptr;
+    LP_TRY(f.factor(mp, count, Ms, n, [&](Arena& ar) {
+        done0 = ar.take<int>(1);
+        B0 = ar.take<double>((size_t)rows * cols);
+        Z0 = ar.take<double>(zsize);
+    }));
+    for (int q = 0; q < count; ++q) {
+        if (q == 0 || !shared_b) LP_HIP(rows_to_device(f.member(B0, q), (size_t)cols, B + (size_t)q * rows * ldb, ldb, (size_t)cols, (size_t)rows, st));
+        LP_HIP(hipMemcpyAsync(f.member(Z0, q), Z_inout + (size_t)q * zsize, zsize * sizeof(double), hipMemcpyHostToDevice, st));
+        LP_HIP(hipMemcpyAsync(f.member(done0, q), &done[(size_t)q], sizeof(int), hipMemcpyHostToDevice, st));
     }
-    if (e == hipSuccess) e = launch_potrf(plan, at.info, st, Batch{count, (long long)stride, nullptr, 0});
-    if (e == hipSuccess)
-        e = launch_trsm_lt(at.Bm, cols, rows, cols, plan, at.Z, mp, st,
-                           Batch{count, (long long)stride, done_mask ? at.done : nullptr, 0}, shared_b != 0);
-    for (int q = 0; q < count && e == hipSuccess; ++q) {
-        const size_t off = (size_t)q * stride;
-        e = hipMemcpyAsync(Z_inout + (size_t)q * rp * mp, (char*)at.Z + off, (size_t)rp * mp * D, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(infos_out + q, (char*)at.info + off, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    LP_HIP(launch_trsm_lt(B0, cols, rows, cols, f.plan, Z0, mp, st, f.batch(done_mask ? done0 : nullptr), shared_b != 0));
+    for (int q = 0; q < count; ++q) {
+        LP_HIP(hipMemcpyAsync(Z_inout + (size_t)q * zsize, f.member(Z0, q), zsize * sizeof(double), hipMemcpyDeviceToHost, st));
+        LP_HIP(hipMemcpyAsync(infos_out + q, f.member(f.info, q), sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
-    const hipError_t es = hipStreamSynchronize(st);               // also on failure: nothing may still use the buffer freed next
-    if (e == hipSuccess) e = es;
-    factor_plan_destroy(plan);
-    (void)hipFree(base);
-    LP_HIP(e);
+    LP_HIP(hipStreamSynchronize(st));
     return LPIPM_OK;
 }
 
@@ -2893,28 +2903,21 @@ static int k_chol_solve_impl(lpipm_ctx* c, uint64_t m, int nrhs, const double* R
     const int mp = (int)round_up(m, NB);
     if (c->k.mp != mp || !c->k.chol_valid) return LPIPM_ERR_NO_PROBLEM;  // needs a preceding lpipm_k_potrf of this size
     LP_HIP(hipSetDevice(c->device));
-    if (repeats < 1) repeats = 1;
-    float total = 0.f;
-    for (int r = 0; r < repeats; ++r) {
+    auto reload = [&]() -> int {       // the solve is in place: every repeat starts from the given right-hand sides
         LP_HIP(hipMemsetAsync(c->k.R, 0, (size_t)2 * mp * sizeof(double), c->rs.st));
-        LP_HIP(hipMemcpy2DAsync(c->k.R, (size_t)mp * sizeof(double), R, m * sizeof(double), m * sizeof(double), nrhs,
-                                hipMemcpyHostToDevice, c->rs.st));
-        LP_HIP(hipEventRecord(c->rs.ev_begin, c->rs.st));
+        LP_HIP(rows_to_device(c->k.R, (size_t)mp, R, m, m, (size_t)nrhs, c->rs.st));
+        return LPIPM_OK;
+    };
+    LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int {
         if (split < 0) LP_HIP(launch_chol_solve(c->k.plan, nrhs, c->k.R, c->k.Y, c->rs.st));
         else {
             const int k = split < (int)c->k.plan.sbs.size() ? split : (int)c->k.plan.sbs.size();
             LP_HIP(launch_chol_solve(c->k.plan, nrhs, c->k.R, c->k.Y, c->rs.st, Batch{}, SolveSteps{0, k, false}));
             LP_HIP(launch_chol_solve(c->k.plan, nrhs, c->k.R, c->k.Y, c->rs.st, Batch{}, SolveSteps{k, -1, true}));
         }
-        LP_HIP(hipEventRecord(c->rs.ev_end, c->rs.st));
-        LP_HIP(hipStreamSynchronize(c->rs.st));
-        float ms = 0.f;
-        LP_HIP(hipEventElapsedTime(&ms, c->rs.ev_begin, c->rs.ev_end));
-        total += ms;
-    }
-    if (ms_out) *ms_out = total / repeats;
-    LP_HIP(hipMemcpy2DAsync(V, m * sizeof(double), c->k.R, (size_t)mp * sizeof(double), m * sizeof(double), nrhs,
-                            hipMemcpyDeviceToHost, c->rs.st));
+        return LPIPM_OK;
+    }, reload));
+    LP_HIP(rows_to_host(V, m, c->k.R, (size_t)mp, m, (size_t)nrhs, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
 }
@@ -2970,23 +2973,19 @@ extern "C" int lpipm_k_symv_residual(lpipm_ctx* c, uint64_t m, const double* M, 
     LP_HIP(hipSetDevice(c->device));
     const int mp = (int)round_up(m, NB);
     LP_TRY(kbuf_ensure(c, mp));
-    double *ws = nullptr, *vbuf = nullptr;
-    // every failure leaves through the one exit below, which frees both buffers
-    hipError_t e = hipMalloc((void**)&ws, symv_slab_doubles(mp) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&vbuf, (size_t)6 * mp * sizeof(double));
-    if (e == hipSuccess) e = hipMemsetAsync(vbuf, 0, (size_t)6 * mp * sizeof(double), c->rs.st);
-    if (e == hipSuccess) e = hipMemsetAsync(c->k.M0, 0, (size_t)mp * mp * sizeof(double), c->rs.st);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(c->k.M0, (size_t)mp * sizeof(double), M, m * sizeof(double), m * sizeof(double), m, hipMemcpyHostToDevice, c->rs.st);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(vbuf, (size_t)mp * sizeof(double), V, m * sizeof(double), m * sizeof(double), nrhs, hipMemcpyHostToDevice, c->rs.st);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(vbuf + 2 * mp, (size_t)mp * sizeof(double), R0, m * sizeof(double), m * sizeof(double), nrhs, hipMemcpyHostToDevice, c->rs.st);
-    if (e == hipSuccess) e = launch_symv_residual(c->k.M0, mp, mp, nrhs, vbuf, mp, vbuf + 2 * mp, mp, vbuf + 4 * mp, mp, ws, c->rs.st);
-    if (e == hipSuccess)
-        e = hipMemcpy2DAsync(Rho, m * sizeof(double), vbuf + 4 * mp, (size_t)mp * sizeof(double), m * sizeof(double), nrhs, hipMemcpyDeviceToHost, c->rs.st);
-    const hipError_t es = hipStreamSynchronize(c->rs.st);      // also on failure: nothing may still use the buffers freed next
-    if (e == hipSuccess) e = es;
-    if (ws) (void)hipFree(ws);
-    if (vbuf) (void)hipFree(vbuf);
-    LP_HIP(e);
+    hipStream_t st = c->rs.st;
+    DeviceTemp tmp{st};
+    double *ws = nullptr, *vbuf = nullptr;             // vbuf: V, R0 and Rho, two padded rows each
+    LP_TRY(tmp.take(&ws, symv_slab_doubles(mp), false));
+    LP_TRY(tmp.take(&vbuf, (size_t)6 * mp, true));
+    double *Vd = vbuf, *R0d = vbuf + 2 * mp, *Rhod = vbuf + 4 * mp;
+    LP_HIP(hipMemsetAsync(c->k.M0, 0, (size_t)mp * mp * sizeof(double), st));
+    LP_HIP(rows_to_device(c->k.M0, (size_t)mp, M, m, m, m, st));
+    LP_HIP(rows_to_device(Vd, (size_t)mp, V, m, m, (size_t)nrhs, st));
+    LP_HIP(rows_to_device(R0d, (size_t)mp, R0, m, m, (size_t)nrhs, st));
+    LP_HIP(launch_symv_residual(c->k.M0, mp, mp, nrhs, Vd, mp, R0d, mp, Rhod, mp, ws, st));
+    LP_HIP(rows_to_host(Rho, m, Rhod, (size_t)mp, m, (size_t)nrhs, st));
+    LP_HIP(hipStreamSynchronize(st));
     return LPIPM_OK;
 }
 
@@ -2996,24 +2995,19 @@ extern "C" int lpipm_k_qr_solve(lpipm_ctx* c, uint64_t m, const double* M, int n
     LP_HIP(hipSetDevice(c->device));
     const int mp = (int)round_up(m, NB);
     LP_TRY(kbuf_ensure(c, mp));
-    std::vector<double> pad((size_t)(mp - m), 1.0);
     LP_HIP(hipMemsetAsync(c->k.plan.L, 0, (size_t)mp * mp * sizeof(double), c->rs.st));
-    LP_HIP(copy_padded(c->k.plan.L, mp, M, m, pad, c->rs.st));
+    LP_HIP(copy_padded(c->k.plan.L, mp, M, m, c->rs.st));
     LP_HIP(hipMemsetAsync(c->k.R, 0, (size_t)2 * mp * sizeof(double), c->rs.st));
-    LP_HIP(hipMemcpy2DAsync(c->k.R, (size_t)mp * sizeof(double), R, m * sizeof(double), m * sizeof(double), nrhs,
-                            hipMemcpyHostToDevice, c->rs.st));
-    LP_HIP(hipEventRecord(c->rs.ev_begin, c->rs.st));
-    LP_HIP(launch_qr_factor(c->k.plan.L, mp, mp, c->k.tau, c->k.info, c->rs.st));
-    LP_HIP(launch_qr_solve(c->k.plan.L, mp, mp, c->k.tau, nrhs, c->k.R, c->k.info, c->rs.st));
-    LP_HIP(hipEventRecord(c->rs.ev_end, c->rs.st));
+    LP_HIP(rows_to_device(c->k.R, (size_t)mp, R, m, m, (size_t)nrhs, c->rs.st));
+    LP_TRY(timed_repeats(c, 1, ms_out, [&]() -> int {           // both are in place: one repeat
+        LP_HIP(launch_qr_factor(c->k.plan.L, mp, mp, c->k.tau, c->k.info, c->rs.st));
+        LP_HIP(launch_qr_solve(c->k.plan.L, mp, mp, c->k.tau, nrhs, c->k.R, c->k.info, c->rs.st));
+        return LPIPM_OK;
+    }));
     int32_t info = 0;
     LP_HIP(hipMemcpyAsync(&info, c->k.info, sizeof(int32_t), hipMemcpyDeviceToHost, c->rs.st));
-    LP_HIP(hipMemcpy2DAsync(V, m * sizeof(double), c->k.R, (size_t)mp * sizeof(double), m * sizeof(double), nrhs,
-                            hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(rows_to_host(V, m, c->k.R, (size_t)mp, m, (size_t)nrhs, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
-    float ms = 0.f;
-    LP_HIP(hipEventElapsedTime(&ms, c->rs.ev_begin, c->rs.ev_end));
-    if (ms_out) *ms_out = ms;
     if (info_out) *info_out = info;
     c->k.chol_valid = false;   // plan.L no longer holds a Cholesky factor: lpipm_k_chol_solve needs a new lpipm_k_potrf
     return LPIPM_OK;
@@ -3023,14 +3017,12 @@ extern "C" int lpipm_k_gemv_n(lpipm_ctx* c, int nrhs, const double* W, double* Y
     if (!c || !W || !Y || (nrhs != 1 && nrhs != 2)) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
     LP_HIP(hipSetDevice(c->device));
-    LP_HIP(hipMemcpy2DAsync(c->p.va.W, (size_t)c->p.np * sizeof(double), W, c->p.n * sizeof(double), c->p.n * sizeof(double),
-                            nrhs, hipMemcpyHostToDevice, c->rs.st));
+    LP_HIP(rows_to_device(c->p.va.W, (size_t)c->p.np, W, c->p.n, c->p.n, (size_t)nrhs, c->rs.st));
     LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int {
         LP_HIP(ctx_gemv_n(c, nrhs, c->p.va.W, nullptr, nullptr, c->p.va.R, Batch{}));
         return LPIPM_OK;
     }));
-    LP_HIP(hipMemcpy2DAsync(Y, c->p.m * sizeof(double), c->p.va.R, (size_t)c->p.mp * sizeof(double), c->p.m * sizeof(double),
-                            nrhs, hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(rows_to_host(Y, c->p.m, c->p.va.R, (size_t)c->p.mp, c->p.m, (size_t)nrhs, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
 }
@@ -3040,21 +3032,18 @@ extern "C" int lpipm_k_gemv_t(lpipm_ctx* c, int nrhs, const double* V, double* U
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
     LP_HIP(hipSetDevice(c->device));
     LP_HIP(hipMemsetAsync(c->p.va.R, 0, (size_t)2 * c->p.mp * sizeof(double), c->rs.st));
-    LP_HIP(hipMemcpy2DAsync(c->p.va.R, (size_t)c->p.mp * sizeof(double), V, c->p.m * sizeof(double), c->p.m * sizeof(double),
-                            nrhs, hipMemcpyHostToDevice, c->rs.st));
+    LP_HIP(rows_to_device(c->p.va.R, (size_t)c->p.mp, V, c->p.m, c->p.m, (size_t)nrhs, c->rs.st));
     LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int {
         LP_HIP(ctx_gemv_t(c, nrhs, c->p.va.R, Batch{}));
         if (c->p.tall) {   // slabs npa wide; the slack columns' A^T.v is v
             LP_HIP(launch_gemv_t_reduce(c->p.ATpart, c->p.nsplit, nrhs, c->p.npa, c->p.va.W, c->p.np, c->rs.st));
-            LP_HIP(hipMemcpy2DAsync(c->p.va.W + c->p.nx, (size_t)c->p.np * sizeof(double), c->p.va.R, (size_t)c->p.mp * sizeof(double),
-                                    c->p.m * sizeof(double), nrhs, hipMemcpyDeviceToDevice, c->rs.st));
+            LP_HIP(copy_rows(c->p.va.W + c->p.nx, (size_t)c->p.np, c->p.va.R, (size_t)c->p.mp, c->p.m, (size_t)nrhs, hipMemcpyDeviceToDevice, c->rs.st));
             return LPIPM_OK;
         }
         LP_HIP(launch_gemv_t_reduce(c->p.ATpart, c->p.nsplit, nrhs, c->p.np, c->p.va.W, c->p.np, c->rs.st));
         return LPIPM_OK;
     }));
-    LP_HIP(hipMemcpy2DAsync(U, c->p.n * sizeof(double), c->p.va.W, (size_t)c->p.np * sizeof(double), c->p.n * sizeof(double),
-                            nrhs, hipMemcpyDeviceToHost, c->rs.st));
+    LP_HIP(rows_to_host(U, c->p.n, c->p.va.W, (size_t)c->p.np, c->p.n, (size_t)nrhs, c->rs.st));
     LP_HIP(hipStreamSynchronize(c->rs.st));
     return LPIPM_OK;
 }
@@ -3139,12 +3128,11 @@ extern "C" int lpipm_k_mfma_f64_probe(lpipm_ctx* c, int iters, double* tflops_ou
     if (!c || iters < 1) return LPIPM_ERR_BAD_ARGUMENT;
     LP_HIP(hipSetDevice(c->device));
     const int blocks = c->num_cu * 2;
+    DeviceTemp tmp{c->rs.st};
     double* sink = nullptr;
-    LP_HIP(hipMalloc((void**)&sink, (size_t)blocks * 256 * sizeof(double)));
+    LP_TRY(tmp.take(&sink, (size_t)blocks * 256, false));
     double ms = 0.0;
-    int rc = timed_repeats(c, 3, &ms, [&]() -> int { LP_HIP(launch_mfma_probe(iters, sink, blocks, c->rs.st)); return LPIPM_OK; });
-    (void)hipFree(sink);
-    if (rc != LPIPM_OK) return rc;
+    LP_TRY(timed_repeats(c, 3, &ms, [&]() -> int { LP_HIP(launch_mfma_probe(iters, sink, blocks, c->rs.st)); return LPIPM_OK; }));
     // per wave and loop trip: 16 independent accumulators x one 16x16x4 MFMA = 16 * 2048 flop
     const double flop = (double)blocks * 4.0 * (double)iters * 16.0 * 2048.0;
     if (ms_out) *ms_out = ms;
