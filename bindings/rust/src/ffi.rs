@@ -32,6 +32,22 @@ pub struct lpipm_dual_info {
     pub reserved: i32,
 }
 
+/// include/lpipm.h `lpipm_cert_info` (40 bytes): scale = b.y or -c.x, the ray's residual in the caller's units, the iterate's
+/// tau and kappa, kind (LPIPM_CERT_*), the member's status
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct lpipm_cert_info {
+    pub scale: f64,
+    pub residual: f64,
+    pub tau: f64,
+    pub kappa: f64,
+    pub kind: i32,
+    pub status: i32,
+}
+pub const LPIPM_CERT_NONE: i32 = 0;
+pub const LPIPM_CERT_FARKAS: i32 = 1;
+pub const LPIPM_CERT_RAY: i32 = 2;
+
 /// include/lpipm.h `lpipm_iter_row` (indicators.rs:8-23 + alpha)
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -237,6 +253,16 @@ extern "C" {
     ) -> c_int;
     pub fn lpipm_get_duals_device(
         ctx: *mut lpipm_ctx, y_dev: *mut c_void, ldy: u64, z_dev: *mut c_void, ldz: u64, info_out: *mut lpipm_dual_info,
+    ) -> c_int;
+    // The certificate of the LAST solve on the context for a member that ended Infeasible (kind FARKAS: y_out[m] = y / b.y,
+    // col_out[n] = z / b.y; A^T.y + z ~ 0, z >= 0, b.y = 1) or Unbounded (kind RAY: col_out[n] = x / (-c.x); A.x ~ 0, x >= 0,
+    // c.x = -1), in the caller's units; kind NONE (any other status, or c.x >= 0): nothing is written.  info_out is required.
+    // _device: every resident member at once, member i's y at y_dev + i * ldy doubles, its z or x at col_dev + i * ldc.
+    pub fn lpipm_get_certificate(
+        ctx: *mut lpipm_ctx, member: u64, y_out: *mut f64, col_out: *mut f64, info_out: *mut lpipm_cert_info,
+    ) -> c_int;
+    pub fn lpipm_get_certificate_device(
+        ctx: *mut lpipm_ctx, y_dev: *mut c_void, ldy: u64, col_dev: *mut c_void, ldc: u64, info_out: *mut lpipm_cert_info,
     ) -> c_int;
     // Power-of-two row / column equilibration of every later upload (passes 1..64; 0 = off, the default), and the int32
     // exponents in use for a resident member: row_exp_out[m], col_exp_out[n].  x comes back in the caller's units.

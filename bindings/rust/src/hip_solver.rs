@@ -57,9 +57,19 @@ impl InteriorPoint<f64> {
         }
     }
 
-    /// What `solve` and `solve_with_duals` share: one lpipm_ctx per call (stream + device buffers), A uploaded once, one
-    /// `lpipm_solve`.  -> the context (still holding the solve's last iterate), x / tau in slack form, fun, the iteration.
+    /// What `solve` and `solve_with_duals` share: `upload_and_solve_raw`, with every status but Ok turned into its error.
     fn upload_and_solve(&self, problem: &Problem<f64>) -> Result<(Ctx, Array1<f64>, f64, u64), LinearProgramError<f64>> {
+        let (ctx, rc, x_slack, fun, iteration) = self.upload_and_solve_raw(problem)?;
+        match rc {
+            LPIPM_OK => Ok((ctx, x_slack, fun, iteration)),
+            LPIPM_ITERATION_LIMIT => Err(to_error(rc, Some(x_slack))), // mod.rs:237-239
+            _ => Err(to_error(rc, None)),
+        }
+    }
+
+    /// One lpipm_ctx per call (stream + device buffers), A uploaded once, one `lpipm_solve`.  -> the context (still holding the
+    /// solve's last iterate), the solve's status, x / tau in slack form, fun, the iteration.
+    fn upload_and_solve_raw(&self, problem: &Problem<f64>) -> Result<(Ctx, i32, Array1<f64>, f64, u64), LinearProgramError<f64>> {
         let a = problem.A().as_standard_layout(); // row-major, as ProblemBuilder::build leaves it (linear_program.rs:145-156)
         let (m, n) = a.dim();
         let b = problem.b().as_standard_layout();
@@ -85,11 +95,38 @@ impl InteriorPoint<f64> {
         let rc = unsafe {
             lpipm_solve(ctx.0, &opts, x_slack.as_mut_ptr(), &mut fun, &mut iteration, std::ptr::null_mut())
         };
+        Ok((ctx, rc, x_slack, fun, iteration))
+    }
+
+    /// `solve`, but an Infeasible or Unbounded problem comes back with its certificate (`lpipm_get_certificate` on the same
+    /// context) next to the error `solve` gives; every other outcome is `solve`'s.
+    pub fn solve_with_certificate(&self, problem: &Problem<f64>) -> Result<OptimizeResult<f64>, (LinearProgramError<f64>, Option<Certificate>)> {
+        let (ctx, rc, x_slack, fun, iteration) = self.upload_and_solve_raw(problem).map_err(|e| (e, None))?;
         match rc {
-            LPIPM_OK => Ok((ctx, x_slack, fun, iteration)),
-            LPIPM_ITERATION_LIMIT => Err(to_error(rc, Some(x_slack))), // mod.rs:237-239
-            _ => Err(to_error(rc, None)),
+            LPIPM_OK => return Ok(OptimizeResult::new(problem.denormalize_x_into(x_slack), fun, iteration as usize)),
+            LPIPM_INFEASIBLE | LPIPM_UNBOUNDED => {}
+            LPIPM_ITERATION_LIMIT => return Err((to_error(rc, Some(x_slack)), None)),
+            _ => return Err((to_error(rc, None), None)),
         }
+        let (m, n) = problem.A().dim();
+        let n_slack = problem.n_slack();
+        let (mut y, mut col) = (Array1::<f64>::zeros(m), Array1::<f64>::zeros(n));
+        let mut info = lpipm_cert_info::default();
+        let got = unsafe { lpipm_get_certificate(ctx.0, 0, y.as_mut_ptr(), col.as_mut_ptr(), &mut info) };
+        if got != LPIPM_OK || info.kind == LPIPM_CERT_NONE {
+            return Err((to_error(rc, None), None));
+        }
+        let farkas = info.kind == LPIPM_CERT_FARKAS;
+        let cut = col.slice(ndarray::s![..n - n_slack]).to_owned();
+        Err((to_error(rc, None), Some(Certificate {
+            kind: info.kind,
+            y_ub: if farkas { Some(y.slice(ndarray::s![..n_slack]).to_owned()) } else { None },
+            y_eq: if farkas { Some(y.slice(ndarray::s![n_slack..]).to_owned()) } else { None },
+            z: if farkas { Some(cut.clone()) } else { None },
+            x: if farkas { None } else { Some(cut) },
+            scale: info.scale,
+            residual: info.residual,
+        })))
     }
 
     /// `solve` followed by `lpipm_get_duals` on the same context.  A problem without a solution is the same error `solve` gives.
@@ -133,6 +170,20 @@ pub struct DualResult {
     pub y_eq: Array1<f64>,
     pub reduced_costs: Array1<f64>,
     pub dual_fun: f64,
+}
+
+/// What `InteriorPoint::<f64>::solve_with_certificate` hands back with an Infeasible or Unbounded error, split as
+/// `ProblemBuilder::build` stacks the rows.  kind LPIPM_CERT_FARKAS: `y_ub` (<= 0), `y_eq`, `z` (>= 0, structural columns) with
+/// A_ub^T y_ub + A_eq^T y_eq + z ~ 0 and b.y = 1 -- a feasibility cut; kind LPIPM_CERT_RAY: `x` (>= 0, structural columns) with
+/// A_ub x <= 0, A_eq x ~ 0, c.x = -1.  `residual`: max |A^T y + z|, respectively max |A x|, of the slack form.
+pub struct Certificate {
+    pub kind: i32,
+    pub y_ub: Option<Array1<f64>>,
+    pub y_eq: Option<Array1<f64>>,
+    pub z: Option<Array1<f64>>,
+    pub x: Option<Array1<f64>>,
+    pub scale: f64,
+    pub residual: f64,
 }
 
 fn to_error_f32(status: i32, x: Option<Array1<f32>>) -> LinearProgramError<f32> {

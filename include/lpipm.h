@@ -516,6 +516,52 @@ int lpipm_get_duals(lpipm_ctx* ctx, uint64_t member, double* y_out /* nullable *
 int lpipm_get_duals_device(lpipm_ctx* ctx, void* y_dev /* nullable */, uint64_t ldy, void* z_dev /* nullable */, uint64_t ldz,
                            lpipm_dual_info* info_out /* host array, one per resident member, nullable */);
 
+/* ---- infeasibility and unboundedness certificates of the LAST solve ------------------------------------------------------
+ * A member that ends LPIPM_INFEASIBLE or LPIPM_UNBOUNDED has no x and no duals; what a Benders or scenario loop needs from it is
+ * the ray: the Farkas multipliers for a feasibility cut, or the improving direction.  Both are the homogeneous iterate
+ * (x, y, z, tau, kappa) at which indicators.rs:66-76 decided the status, which stays in the context, normalised here after the
+ * solve.  No solve entry, no arena layout, no lpipm_get_resident_bytes value and no bit of any solve changes.
+ * Definition, in the resident (possibly scaled) problem:
+ *   LPIPM_INFEASIBLE: kind = LPIPM_CERT_FARKAS, s = b.y (> tol by indicators.rs:72), yh = y / s, zh = z / s; y_out gets yh,
+ *     col_out gets zh.  A^T.yh + zh ~ 0, zh >= 0, b.yh = 1: A x = b, x >= 0 has no solution.  The multiplier of a `ub` row is
+ *     <= 0 and equals minus its slack's zh up to the residual.
+ *   LPIPM_UNBOUNDED: s = -c.x.  s > 0: kind = LPIPM_CERT_RAY, xh = x / s, col_out gets xh, y_out is untouched.  A.xh ~ 0,
+ *     xh >= 0, c.xh = -1: the dual is infeasible, the primal unbounded wherever it is feasible.  s <= 0 (the reference says
+ *     Unbounded whenever b.y <= tol, so nothing is proved): kind = LPIPM_CERT_NONE, nothing is written.
+ *   Any other status (Ok, iteration limit, numerical problem): kind = LPIPM_CERT_NONE, nothing is written, scale and residual
+ *     are NaN.
+ *   info: status is the member's last return code, tau and kappa the iterate's, scale = s.
+ * Caller's units: the mapping of lpipm_get_duals, the division first and the power of two second: yh_i -> ldexp(., kr[i]),
+ *   zh_j -> ldexp(., -kc[j]), xh_j -> ldexp(., kc[j]) (as x).  b.y and c.x are invariant under the equilibration: s needs no
+ *   correction.  Lengths and order are those of lpipm_get_duals: y_out the m rows of the upload (`ub` first), col_out as long
+ *   as x_slack_out, slack entries included.
+ * residual, in the caller's units, computed on the device by one pass over the resident image (the residual pair's pass):
+ *   Farkas max_j |ldexp((A^T.yh + zh)_j, -kc[j])| over all n columns (a slack column contributes yh_i + zh_s,i), ray
+ *   max_i |ldexp((A.xh)_i, -kr[i])| over the m rows.
+ * lpipm_get_certificate: resident member `member` (0 for a single LP) to host arrays (each nullable; info_out required).
+ * lpipm_get_certificate_device: all members at once, member i's yh at y_dev + i * ldy doubles, its zh or xh at
+ *   col_dev + i * ldc (ldy >= m, ldc >= n; either pointer may be NULL), complete on return; the rows of a kind NONE member stay
+ *   untouched.  info_out: a host array of one record per resident member (required).
+ * Every member comes out bit-identical -- y, col and the whole record -- to the single upload + lpipm_solve +
+ *   lpipm_get_certificate of that member alone, by either entry.
+ * Return codes.  First lpipm_get_duals's checks in its order: a null context LPIPM_ERR_BAD_ARGUMENT, nothing resident
+ *   LPIPM_ERR_NO_PROBLEM, a column-split context LPIPM_ERR_UNSUPPORTED, no completed solve since the last event that changes
+ *   what the iterate means (the list above) LPIPM_ERR_NO_PROBLEM.  Then LPIPM_ERR_BAD_ARGUMENT: member >= the resident count, a
+ *   null info_out, ldy < m, ldc < n, a device destination that is not device memory of the context's device or does not hold
+ *   every row (checked before anything is enqueued).  Otherwise LPIPM_OK, and info.kind says what was written.
+ * Served: every resident form and solver arm lpipm_get_duals serves.  Not served: lpipm_solve_batch*, lpipm_solve_f32,
+ *   column-split contexts.
+ * Cost: five short launches and one pass over the resident image (shared images: one read per group of members).  In the
+ *   arenas it writes reduction slots 0-3, the slabs of the pass and three work vectors below m and n, all of which every
+ *   iteration rewrites before it reads them; the iterate, b, c and every padding are only read: lpipm_get_duals and the next
+ *   solve find what they would have found. */
+enum { LPIPM_CERT_NONE = 0, LPIPM_CERT_FARKAS = 1, LPIPM_CERT_RAY = 2 };
+typedef struct { double scale, residual, tau, kappa; int32_t kind, status; } lpipm_cert_info;   /* 40 bytes */
+int lpipm_get_certificate(lpipm_ctx* ctx, uint64_t member, double* y_out /* m, nullable */, double* col_out /* n, nullable */,
+                          lpipm_cert_info* info_out /* required */);
+int lpipm_get_certificate_device(lpipm_ctx* ctx, void* y_dev /* nullable */, uint64_t ldy, void* col_dev /* nullable */,
+                                 uint64_t ldc, lpipm_cert_info* info_out /* host, one per resident member, required */);
+
 /* Device bytes the context holds for its resident problem(s) (arenas + shared matrix with the batch's one kept first factor +
  * factor workspace, and the exponent block of lpipm_set_scaling while scaling is on); 0 before any upload. */
 int lpipm_get_resident_bytes(const lpipm_ctx* ctx, uint64_t* bytes_out);

@@ -54,6 +54,25 @@ private:
     std::vector<double> x_;
 };
 
+// What InteriorPoint::solve_with_certificate hands back with an Infeasible or Unbounded error (lpipm_get_certificate), split as
+// ProblemBuilder::build stacks the rows.  kind LPIPM_CERT_FARKAS: y_ub (<= 0), y_eq and z (>= 0, the structural columns) with
+// A_ub^T y_ub + A_eq^T y_eq + z ~ 0 and b_ub.y_ub + b_eq.y_eq = 1 -- a feasibility cut.  kind LPIPM_CERT_RAY: x (>= 0, the
+// structural columns) with A_ub x <= 0, A_eq x ~ 0, c.x = -1.  kind LPIPM_CERT_NONE: an Unbounded call that proves nothing.
+// residual: max |A^T y + z|, respectively max |A x|, over the slack form.  The vectors a kind does not have are empty.
+struct Certificate {
+    int kind = LPIPM_CERT_NONE;
+    std::vector<double> y_ub, y_eq, z, x;
+    double scale = 0.0, residual = 0.0;
+};
+class CertifiedError : public LinearProgramError {
+public:
+    CertifiedError(ErrorKind k, const std::string& msg, Certificate c) : LinearProgramError(k, msg), cert_(std::move(c)) {}
+    const Certificate& certificate() const { return cert_; }
+
+private:
+    Certificate cert_;
+};
+
 inline void raise_for(int status, std::vector<double> x = {}) {
     if (status == LPIPM_OK) return;
     std::string msg = lpipm_strerror(status);
@@ -247,6 +266,36 @@ public:
                           std::vector<double>(y.begin(), y.begin() + ns), std::vector<double>(y.begin() + ns, y.end()),
                           std::vector<double>(z.begin(), z.end() - ns), info.dual_fun};
     }
+    // solve(), but an Infeasible or Unbounded problem throws a CertifiedError (a LinearProgramError of the same kind) that
+    // carries the certificate of the solve's last iterate (lpipm_get_certificate on the same context; tall_form() /
+    // tall_eq_form() are honoured).  Every other outcome is solve()'s.  Not in the reference.
+    OptimizeResult solve_with_certificate(const Problem& problem) const {
+        lpipm_ctx* ctx = nullptr;
+        raise_for(lpipm_create(device_, &ctx));
+        struct Guard { lpipm_ctx* c; ~Guard() { lpipm_destroy(c); } } guard{ctx};
+        std::vector<double> x;
+        double fun = 0.0;
+        uint64_t it = 0;
+        const int rc = upload_and_solve_rc(ctx, problem, x, fun, it);
+        if (rc == LPIPM_INFEASIBLE || rc == LPIPM_UNBOUNDED) {
+            const Matrix& A = problem.A();
+            std::vector<double> y(A.rows), col(A.cols);
+            lpipm_cert_info info{};
+            raise_for(lpipm_get_certificate(ctx, 0, y.data(), col.data(), &info));
+            const std::size_t ns = problem.n_slack();
+            Certificate cert;
+            cert.kind = info.kind; cert.scale = info.scale; cert.residual = info.residual;
+            if (info.kind == LPIPM_CERT_FARKAS) {
+                cert.y_ub.assign(y.begin(), y.begin() + ns); cert.y_eq.assign(y.begin() + ns, y.end());
+                cert.z.assign(col.begin(), col.end() - ns);
+            } else if (info.kind == LPIPM_CERT_RAY)
+                cert.x.assign(col.begin(), col.end() - ns);
+            throw CertifiedError(static_cast<ErrorKind>(rc), lpipm_strerror(rc), std::move(cert));
+        }
+        if (rc == LPIPM_ITERATION_LIMIT) raise_for(rc, x);          // payload: x / tau, mod.rs:237-239
+        raise_for(rc);
+        return OptimizeResult(problem.denormalize_x_into(std::move(x)), fun, it);
+    }
     // The f32 instantiation of the same `solve` (src/float.rs:42-43): every operation in f32, lpipm_solve_f32.  With the
     // default tol = 1e-8 an f32 solve cannot satisfy the optimality test (the reference's behaviour): pass 1e-4 .. 1e-5.
     OptimizeResultF32 solve(const ProblemF32& problem) const {
@@ -265,8 +314,14 @@ public:
     }
 
 private:
-    // What solve() and solve_with_duals() share: the upload of `problem` in the form the opt-ins select, and lpipm_solve.
+    // What solve() and solve_with_duals() share: upload_and_solve_rc, every status but Ok thrown.
     void upload_and_solve(lpipm_ctx* ctx, const Problem& problem, std::vector<double>& x, double& fun, uint64_t& it) const {
+        const int rc = upload_and_solve_rc(ctx, problem, x, fun, it);
+        if (rc == LPIPM_ITERATION_LIMIT) raise_for(rc, x);          // payload: x / tau, mod.rs:237-239
+        raise_for(rc);
+    }
+    // The upload of `problem` in the form the opt-ins select, and lpipm_solve.  -> the solve's status
+    int upload_and_solve_rc(lpipm_ctx* ctx, const Problem& problem, std::vector<double>& x, double& fun, uint64_t& it) const {
         const Matrix& A = problem.A();
         if (tall_eq_ && problem.n_slack() > 0 && problem.n_slack() <= A.rows && problem.n_slack() < A.cols) {
             // A = [[X I], [A_eq 0]]: the `ub` block is the first n_slack rows, the `eq` block the rest, both with lda = cols
@@ -283,9 +338,7 @@ private:
         raise_for(lpipm_upload_slack(ctx, A.rows, A.cols, A.data.data(), A.cols, problem.b().data(),
                                      problem.c().data(), problem.c0(), problem.n_slack()));
         x.assign(A.cols, 0.0);
-        const int rc = lpipm_solve(ctx, &o_, x.data(), &fun, &it, nullptr);
-        if (rc == LPIPM_ITERATION_LIMIT) raise_for(rc, x);          // payload: x / tau, mod.rs:237-239
-        raise_for(rc);
+        return lpipm_solve(ctx, &o_, x.data(), &fun, &it, nullptr);
     }
     lpipm_opts o_;
     int device_;

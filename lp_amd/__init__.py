@@ -183,6 +183,22 @@ class Problem:
         ns = self._n_slack
         return np.array(y[:ns]), np.array(y[ns:]), np.array(z[: z.shape[0] - ns])
 
+    def denormalize_certificate(self, y, col, kind: int):
+        """The counterpart of denormalize_duals for a certificate of the slack form (Context.certificate): the rows split as
+        ProblemBuilder::build stacks them (the `ub` rows first, then the `eq` rows), col cut to the structural columns.
+        Farkas (kind 1): -> (y_ub, y_eq, z) with A_ub^T y_ub + A_eq^T y_eq + z ~ 0, y_ub <= 0, z >= 0,
+        b_ub.y_ub + b_eq.y_eq = 1.  Ray (kind 2; y is None): -> (None, None, x) with A_ub x <= 0, A_eq x ~ 0, x >= 0,
+        c.x = -1.  No certificate (kind 0): -> (None, None, None)."""
+        ns = self._n_slack
+        if kind == _capi.CERT_NONE:
+            return None, None, None
+        col = np.asarray(col)
+        cut = np.array(col[: col.shape[0] - ns])
+        if kind == _capi.CERT_RAY:
+            return None, None, cut
+        y = np.asarray(y)
+        return np.array(y[:ns]), np.array(y[ns:]), cut
+
 
 class ProblemBuilder:
     """linear_program.rs:72-170."""
@@ -825,6 +841,54 @@ class Context:
         without a solution stay untouched.  Complete on return.  -> list of (status, dual_fun | None)"""
         return [(r.status, r.dual_fun if has_x(r.status) else None) for r in self._get_duals_device(y_ptr, ldy, z_ptr, ldz)]
 
+    @staticmethod
+    def _certificate_dict(info, y, col):
+        kind = int(info.kind)
+        return dict(kind=kind, status=int(info.status), y=y if kind == _capi.CERT_FARKAS else None,
+                    col=col if kind != _capi.CERT_NONE else None, scale=info.scale, residual=info.residual, tau=info.tau,
+                    kappa=info.kappa)
+
+    def certificate(self, member: int = 0) -> dict:
+        """The certificate of resident member `member` (0 for a single LP) at the iterate of the LAST solve on this context
+        (lpipm_get_certificate): dict(kind, status, y, col, scale, residual, tau, kappa).  kind 1 (status Infeasible): the
+        Farkas ray y, col = z with A'y + z ~ 0, z >= 0, b.y = 1; kind 2 (status Unbounded, c.x < 0): col = x with A x ~ 0,
+        x >= 0, c.x = -1, y None; kind 0 (any other status, or an Unbounded call that proves nothing): y and col None.  In the
+        caller's units; residual is max|A'y + z|, respectively max|A x|.  A context without a completed solve raises
+        BackendError."""
+        _, m, n = self._duals_lengths()
+        y, col = np.full(m, np.nan), np.full(n, np.nan)
+        info = _capi.CertInfo()
+        _raise_for(_capi.lib().lpipm_get_certificate(self._h, int(member), _p(y), _p(col), C.byref(info)))
+        return self._certificate_dict(info, y, col)
+
+    def _get_certificates_device(self, y_ptr, ldy, col_ptr, ldc):
+        """lpipm_get_certificate_device -> the lpipm_cert_info records, one per resident member."""
+        info = (_capi.CertInfo * self._duals_lengths()[0])()
+        _raise_for(_capi.lib().lpipm_get_certificate_device(self._h, C.c_void_p(int(y_ptr)) if y_ptr else None, int(ldy),
+                                                            C.c_void_p(int(col_ptr)) if col_ptr else None, int(ldc), info))
+        return info
+
+    def certificates_lockstep(self, members: int | None = None) -> list:
+        """Context.certificate of the first `members` (default: all) members of the resident lockstep batch after its
+        solve_lockstep[_device]: a list of that dict.  One lpipm_get_certificate_device into one device block and one copy
+        of that block to the host, whatever the count: the same bits as one lpipm_get_certificate per member."""
+        import torch
+        K, m, n = self._duals_lengths()
+        block = torch.empty((K, m + n), dtype=torch.float64, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(self.device).synchronize()      # (the block may be recycled memory torch still works on)
+        info = self._get_certificates_device(block.data_ptr(), m + n, block.data_ptr() + 8 * m, m + n)
+        keep = K if members is None else min(int(members), K)
+        rows = block[:keep].cpu().numpy()
+        return [self._certificate_dict(info[k], rows[k, :m].copy(), rows[k, m:].copy()) for k in range(keep)]
+
+    def certificates_device(self, y_ptr, ldy: int, col_ptr, ldc: int) -> list:
+        """The certificates of every resident member left in HBM (lpipm_get_certificate_device): member i's Farkas y to the
+        device row y_ptr + i * ldy doubles, its z or x to col_ptr + i * ldc; a null (0 / None) pointer skips those vectors,
+        the rows of a member without a certificate stay untouched.  Complete on return.
+        -> list of dict(kind, status, scale, residual, tau, kappa)"""
+        return [dict(kind=int(r.kind), status=int(r.status), scale=r.scale, residual=r.residual, tau=r.tau, kappa=r.kappa)
+                for r in self._get_certificates_device(y_ptr, ldy, col_ptr, ldc)]
+
     def solve_f32(self, A, b, c, c0: float = 0.0, opts: "_capi.Opts | None" = None, want_log: bool = False):
         """InteriorPoint<f32>::solve on a slack-form problem (src/float.rs:42-43; lpipm_solve_f32): every operation in f32.
         -> (status, x_slack float32 | None, fun, iterations, log rows).  The context's uploaded fp64 problem, if any, is untouched."""
@@ -1127,12 +1191,21 @@ class InteriorPoint(Solver):
         ctx.upload(problem)
         return self.solve_uploaded(ctx, problem)
 
-    def solve_uploaded(self, ctx: Context, problem: Problem, want_log=False, want_duals=False):
+    def solve_uploaded(self, ctx: Context, problem: Problem, want_log=False, want_duals=False, want_certificate=False):
         """want_duals: the result also carries y_ub, y_eq, reduced_costs (Problem.denormalize_duals of Context.duals) and
-        dual_fun of the solve's last iterate."""
+        dual_fun of the solve's last iterate.  want_certificate: a raised Infeasible / Unbounded carries .certificate
+        (solve_with_certificate)."""
         rc, x_slack, fun, it, rows = ctx.solve_raw(self.opts(), want_log=want_log)
         if rc == _capi.ITERATION_LIMIT:
             raise IterationLimitExceeded(x_slack)            # mod.rs:237-239 (payload: x / tau, slack form)
+        if want_certificate and rc in (_capi.INFEASIBLE, _capi.UNBOUNDED):
+            d = ctx.certificate()
+            err = _BY_CODE[rc]()
+            y_ub, y_eq, cut = problem.denormalize_certificate(d["y"], d["col"], d["kind"])
+            err.certificate = dict(kind=d["kind"], y_ub=y_ub, y_eq=y_eq, z=cut if d["kind"] == _capi.CERT_FARKAS else None,
+                                   x=cut if d["kind"] == _capi.CERT_RAY else None, scale=d["scale"], residual=d["residual"],
+                                   tau=d["tau"], kappa=d["kappa"])
+            raise err
         _raise_for(rc)
         res = OptimizeResult(problem.denormalize_x_into(x_slack), fun, it)   # mod.rs:165-167
         if want_log:
@@ -1153,3 +1226,15 @@ class InteriorPoint(Solver):
         ctx = default_context(self.device)
         ctx.upload(problem)
         return self.solve_uploaded(ctx, problem, want_duals=True)
+
+    def solve_with_certificate(self, problem: Problem) -> OptimizeResult:
+        """solve(problem), but a raised Infeasible or Unbounded carries .certificate: dict(kind, y_ub, y_eq, z, x, scale,
+        residual, tau, kappa) -- kind 1: the Farkas multipliers of the `ub` and `eq` rows and z of the structural columns
+        (A_ub^T y_ub + A_eq^T y_eq + z ~ 0, y_ub <= 0, z >= 0, b.y = 1: a feasibility cut); kind 2: the improving ray x of the
+        structural columns (A_ub x <= 0, A_eq x ~ 0, x >= 0, c.x = -1); kind 0: an Unbounded call that proves nothing.  The
+        fields a kind does not have are None.  (A Problem<f32> has none: lpipm_solve_f32 releases its problem inside the call.)"""
+        if problem.dtype == np.float32:
+            raise ValueError("solve_with_certificate needs a float64 Problem")
+        ctx = default_context(self.device)
+        ctx.upload(problem)
+        return self.solve_uploaded(ctx, problem, want_certificate=True)

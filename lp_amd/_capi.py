@@ -35,6 +35,13 @@ class DualInfo(C.Structure):  # lpipm_dual_info (32 bytes)
                 ("reserved", C.c_int32)]
 
 
+class CertInfo(C.Structure):  # lpipm_cert_info (40 bytes)
+    _fields_ = [("scale", C.c_double), ("residual", C.c_double), ("tau", C.c_double), ("kappa", C.c_double),
+                ("kind", C.c_int32), ("status", C.c_int32)]
+
+
+CERT_NONE, CERT_FARKAS, CERT_RAY = range(3)           # lpipm_cert_info.kind
+
 FORM_SLACK, FORM_UB_EQ, FORM_UB_TALL = range(3)     # lpipm_device_problem.form
 SRC_F64, SRC_F32 = range(2)                           # lpipm_device_problem.src_type
 
@@ -100,6 +107,8 @@ SYMBOLS = {
                                           C.POINTER(Opts), _dpp, _vp, _u64, _dp, C.POINTER(_u64), C.POINTER(C.c_int32)]),
     "lpipm_get_duals": (C.c_int, [_vp, _u64, _dp, _dp, C.POINTER(DualInfo)]),
     "lpipm_get_duals_device": (C.c_int, [_vp, _vp, _u64, _vp, _u64, C.POINTER(DualInfo)]),
+    "lpipm_get_certificate": (C.c_int, [_vp, _u64, _dp, _dp, C.POINTER(CertInfo)]),
+    "lpipm_get_certificate_device": (C.c_int, [_vp, _vp, _u64, _vp, _u64, C.POINTER(CertInfo)]),
     "lpipm_get_resident_bytes": (C.c_int, [_vp, C.POINTER(_u64)]),
     "lpipm_solve_lockstep": (C.c_int, [_vp, C.POINTER(Opts), _dpp, _dp, C.POINTER(_u64), C.POINTER(C.c_int32)]),
     "lpipm_solve_lockstep_device": (C.c_int, [_vp, C.POINTER(Opts), _vp, _u64, _dp, C.POINTER(_u64), C.POINTER(C.c_int32)]),

@@ -100,7 +100,7 @@ def solve_batch_sharded(problems, opts=None, ctx=None, group=None, device=None, 
     return out
 
 
-def solve_shared_matrix(A, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, n_slack=0, duals=False):
+def solve_shared_matrix(A, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, n_slack=0, duals=False, certificates=False):
     """LPs that share ONE constraint matrix A (scenario sweeps: only b, c and c0 vary), member i = (A, bs[i], cs[i], c0s[i]).
     The members go through lockstep groups of at most `max_group` on one context (lpipm_upload_lockstep_shared: A resident
     once, every pass over it serving the whole group).  Returns a list of dicts {status, x_slack, fun, iterations} in member
@@ -108,33 +108,36 @@ def solve_shared_matrix(A, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, 
     (lpipm_upload_lockstep_shared_slack).
     duals=True (here and in every solve_shared_* / sweep_shared_* below): each member's dict gains y, z and dual_fun
     (Context.duals: None for a member without a solution), fetched after each group's solve_lockstep -- a scenario-cut loop
-    reads its cuts from y."""
-    return _groups(lambda cx, b, c, c0: cx.upload_lockstep_shared(A, b, c, c0, n_slack=n_slack), bs, cs, c0s, opts, ctx, max_group, duals)
+    reads its cuts from y.
+    certificates=True (likewise): each member WITHOUT a solution gains cert_kind, cert_y, cert_col, cert_scale and
+    cert_residual (Context.certificate's kind, y, col, scale, residual), fetched where duals=True fetches its rows -- the
+    feasibility cut of an infeasible scenario is cert_y."""
+    return _groups(lambda cx, b, c, c0: cx.upload_lockstep_shared(A, b, c, c0, n_slack=n_slack), bs, cs, c0s, opts, ctx, max_group, duals, certificates)
 
 
-def solve_shared_ub_eq(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, duals=False):
+def solve_shared_ub_eq(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, duals=False, certificates=False):
     """Inequality-form LPs over ONE pair of blocks (right-hand-side and cost sweeps over A_ub x <= b_ub, A_eq x == b_eq):
     member i = (bs[i] = [b_ub_i; b_eq_i], cs[i] = the n structural costs, c0s[i]); either block may be None.  Lockstep groups
     of at most `max_group` on one context through lpipm_upload_lockstep_shared_ub_eq: the blocks resident once, the slack
     block never formed on the host or the device.  Returns what solve_shared_matrix returns; x_slack has n + m_ub entries."""
-    return _groups(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_eq(A_ub, A_eq, b, c, c0), bs, cs, c0s, opts, ctx, max_group, duals)
+    return _groups(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_eq(A_ub, A_eq, b, c, c0), bs, cs, c0s, opts, ctx, max_group, duals, certificates)
 
 
-def solve_shared_ub_tall(A_ub, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, duals=False):
+def solve_shared_ub_tall(A_ub, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, duals=False, certificates=False):
     """Tall inequality-form LPs over ONE matrix (many right-hand sides or costs on one design matrix, A_ub x <= bs[i] with many
     more rows than columns): member i = (bs[i], cs[i] = the n structural costs, c0s[i]).  Lockstep groups of at most
     `max_group` on one context through lpipm_upload_lockstep_shared_ub_tall: A_ub and its transpose resident once, every member
     factoring its own n x n reduced system.  Returns what solve_shared_ub_eq returns; x_slack has n + m_ub entries."""
-    return _groups(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_tall(A_ub, b, c, c0), bs, cs, c0s, opts, ctx, max_group, duals)
+    return _groups(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_tall(A_ub, b, c, c0), bs, cs, c0s, opts, ctx, max_group, duals, certificates)
 
 
-def solve_shared_ub_eq_tall(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, duals=False):
+def solve_shared_ub_eq_tall(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, duals=False, certificates=False):
     """Tall LPs with equality rows over ONE pair of blocks (solve_shared_ub_tall's users with a sum-to-one, budget or
     interpolation row): member i = (bs[i] = [b_ub_i; b_eq_i], cs[i] = the n structural costs, c0s[i]).  Lockstep groups of at
     most `max_group` on one context through lpipm_upload_lockstep_shared_ub_eq_tall: the image and the transpose of A_ub resident
     once, every member factoring its own n x n reduced system and its own m_eq x m_eq Schur complement.  Returns what
     solve_shared_ub_eq returns; x_slack has n + m_ub entries."""
-    return _groups(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_eq_tall(A_ub, A_eq, b, c, c0), bs, cs, c0s, opts, ctx, max_group, duals)
+    return _groups(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_eq_tall(A_ub, A_eq, b, c, c0), bs, cs, c0s, opts, ctx, max_group, duals, certificates)
 
 
 def sweep_chunks(count: int, max_group: int):
@@ -151,7 +154,7 @@ def sweep_chunks(count: int, max_group: int):
     return g, chunks
 
 
-def solve_device(A, b, c, c0s=None, *, form="slack", A_eq=None, n_slack=0, opts=None, ctx=None, max_group=32, duals=False):
+def solve_device(A, b, c, c0s=None, *, form="slack", A_eq=None, n_slack=0, opts=None, ctx=None, max_group=32, duals=False, certificates=False):
     """A batch that is already on the GPU, end to end without a host copy of A, b, c or x: torch CUDA tensors as
     Context.upload_device takes them -- A [m, n] with b [K, .] (one matrix for all members) or A [K, m, n] (members that own
     their matrices), float64 or float32, any strides.  The members go through lockstep chunks of sweep_chunks's size (at most
@@ -162,7 +165,11 @@ def solve_device(A, b, c, c0s=None, *, form="slack", A_eq=None, n_slack=0, opts=
     status (int32), fun (float64, NaN without a solution) and iterations (int64) numpy arrays of K entries.
     duals=True: -> (x, status, fun, iterations, y, z, dual_fun) with y [K, len(b[i])] and z [K, len(x)] float64 CUDA tensors
     written by Context.duals_device after each chunk's solve (NaN rows for members without a solution) and dual_fun a numpy
-    array (NaN likewise)."""
+    array (NaN likewise).
+    certificates=True: the tuple gains (cert_y, cert_col, cert_kind) at its end -- cert_y [K, len(b[i])] and cert_col
+    [K, len(x)] float64 CUDA tensors written by Context.certificates_device after each chunk's solve (the Farkas y and z of an
+    infeasible member, the ray x of an unbounded one in cert_col; NaN rows for every other member) and cert_kind a numpy int32
+    array (Context.certificate's kind)."""
     import torch
     import lp_amd
     _, _, K, nb, n_out, dev, batch = lp_amd._device_request(A, b, c, c0s, form, A_eq, n_slack)
@@ -180,6 +187,11 @@ def solve_device(A, b, c, c0s=None, *, form="slack", A_eq=None, n_slack=0, opts=
         z = torch.full((K, n_out), float("nan"), dtype=torch.float64, device=A.device)
         dual_fun = np.full(K, np.nan)
         torch.cuda.current_stream(dev).synchronize()      # the fills run on torch's stream, the library on its own
+    if certificates:
+        cert_y = torch.full((K, nb), float("nan"), dtype=torch.float64, device=A.device)
+        cert_col = torch.full((K, n_out), float("nan"), dtype=torch.float64, device=A.device)
+        cert_kind = np.zeros(K, dtype=np.int32)
+        torch.cuda.current_stream(dev).synchronize()
     g = sweep_chunks(K, max_group)[0]
     resident = 0                                          # members of the shared-matrix batch that is resident
     for k0 in range(0, K, g):
@@ -199,12 +211,14 @@ def solve_device(A, b, c, c0s=None, *, form="slack", A_eq=None, n_slack=0, opts=
         if duals:
             for i, (_, df) in enumerate(ctx.duals_device(y[k0].data_ptr(), nb, z[k0].data_ptr(), n_out)):
                 dual_fun[k0 + i] = np.nan if df is None else df
-    if duals:
-        return x, status, fun, its, y, z, dual_fun
-    return x, status, fun, its
+        if certificates:
+            for i, d in enumerate(ctx.certificates_device(cert_y[k0].data_ptr(), nb, cert_col[k0].data_ptr(), n_out)):
+                cert_kind[k0 + i] = d["kind"]
+    out = (x, status, fun, its) + ((y, z, dual_fun) if duals else ())
+    return out + ((cert_y, cert_col, cert_kind) if certificates else ())
 
 
-def _drive(chunks, upload, resident, bs, cs, c0s, opts, ctx, max_group, duals=False):
+def _drive(chunks, upload, resident, bs, cs, c0s, opts, ctx, max_group, duals=False, certificates=False):
     """Member groups through lockstep batches on one context: `chunks(count, max_group)` gives the member indices of each group;
     group 0 is uploaded, a later one replaces the vectors of the resident batch (resident) or is uploaded in its turn."""
     import lp_amd
@@ -229,42 +243,47 @@ def _drive(chunks, upload, resident, bs, cs, c0s, opts, ctx, max_group, duals=Fa
         if duals:                                              # of this group's solve, before the next one replaces its iterate
             for member, d in zip(out[first:], ctx.duals_lockstep(len(out) - first)):   # (not a sweep's padding)
                 member.update(y=d["y"] if d else None, z=d["z"] if d else None, dual_fun=d["dual_fun"] if d else None)
+        if certificates and any(not lp_amd.has_x(q["status"]) for q in out[first:]):
+            for member, d in zip(out[first:], ctx.certificates_lockstep(len(out) - first)):
+                if not lp_amd.has_x(member["status"]):
+                    member.update(cert_kind=d["kind"], cert_y=d["y"], cert_col=d["col"], cert_scale=d["scale"],
+                                  cert_residual=d["residual"])
     return out
 
 
-def _groups(upload, bs, cs, c0s, opts, ctx, max_group, duals=False):
+def _groups(upload, bs, cs, c0s, opts, ctx, max_group, duals=False, certificates=False):
     """Groups of at most max_group members in order, each uploaded."""
     return _drive(lambda count, g: [range(k, min(k + g, count)) for k in range(0, count, g)], upload, False,
-                  bs, cs, c0s, opts, ctx, max_group, duals)
+                  bs, cs, c0s, opts, ctx, max_group, duals, certificates)
 
 
-def _sweep(upload, bs, cs, c0s, opts, ctx, max_group, duals=False):
+def _sweep(upload, bs, cs, c0s, opts, ctx, max_group, duals=False, certificates=False):
     """The equal chunks of sweep_chunks: one upload, then new vectors for the resident batch."""
-    return _drive(lambda count, g: sweep_chunks(count, g)[1], upload, True, bs, cs, c0s, opts, ctx, max_group, duals)
+    return _drive(lambda count, g: sweep_chunks(count, g)[1], upload, True, bs, cs, c0s, opts, ctx, max_group, duals, certificates)
 
 
-def sweep_shared_matrix(A, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, n_slack=0, duals=False):
+def sweep_shared_matrix(A, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, n_slack=0, duals=False, certificates=False):
     """solve_shared_matrix for a sweep of more than one group: ONE upload_lockstep_shared (the first chunk), then
     update_lockstep_vectors for every later chunk -- A goes to the device once, and its first iteration's factor is formed
     once for the whole sweep.  The chunks are equal (sweep_chunks).  Returns what solve_shared_matrix returns, bit for bit."""
-    return _sweep(lambda cx, b, c, c0: cx.upload_lockstep_shared(A, b, c, c0, n_slack=n_slack), bs, cs, c0s, opts, ctx, max_group, duals)
+    return _sweep(lambda cx, b, c, c0: cx.upload_lockstep_shared(A, b, c, c0, n_slack=n_slack), bs, cs, c0s, opts, ctx, max_group, duals, certificates)
 
 
-def sweep_shared_ub_eq(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, duals=False):
+def sweep_shared_ub_eq(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, duals=False, certificates=False):
     """solve_shared_ub_eq as a sweep: one upload_lockstep_shared_ub_eq, then update_lockstep_vectors per later chunk (bs[i] =
     [b_ub_i; b_eq_i], cs[i] = the n structural costs).  Returns what solve_shared_ub_eq returns, bit for bit."""
-    return _sweep(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_eq(A_ub, A_eq, b, c, c0), bs, cs, c0s, opts, ctx, max_group, duals)
+    return _sweep(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_eq(A_ub, A_eq, b, c, c0), bs, cs, c0s, opts, ctx, max_group, duals, certificates)
 
 
-def sweep_shared_ub_tall(A_ub, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, duals=False):
+def sweep_shared_ub_tall(A_ub, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, duals=False, certificates=False):
     """solve_shared_ub_tall as a sweep: one upload_lockstep_shared_ub_tall, then update_lockstep_vectors per later chunk (bs[i]
     of m_ub entries, cs[i] = the n structural costs); A_ub is uploaded and transposed once.  Returns what solve_shared_ub_tall
     returns, bit for bit."""
-    return _sweep(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_tall(A_ub, b, c, c0), bs, cs, c0s, opts, ctx, max_group, duals)
+    return _sweep(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_tall(A_ub, b, c, c0), bs, cs, c0s, opts, ctx, max_group, duals, certificates)
 
 
-def sweep_shared_ub_eq_tall(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, duals=False):
+def sweep_shared_ub_eq_tall(A_ub, A_eq, bs, cs, c0s=None, opts=None, ctx=None, max_group=32, duals=False, certificates=False):
     """solve_shared_ub_eq_tall as a sweep: one upload_lockstep_shared_ub_eq_tall, then update_lockstep_vectors per later chunk
     (bs[i] = [b_ub_i; b_eq_i], cs[i] = the n structural costs); the image is uploaded and A_ub transposed once.  Returns what
     solve_shared_ub_eq_tall returns, bit for bit."""
-    return _sweep(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_eq_tall(A_ub, A_eq, b, c, c0), bs, cs, c0s, opts, ctx, max_group, duals)
+    return _sweep(lambda cx, b, c, c0: cx.upload_lockstep_shared_ub_eq_tall(A_ub, A_eq, b, c, c0), bs, cs, c0s, opts, ctx, max_group, duals, certificates)

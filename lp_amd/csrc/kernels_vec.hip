@@ -664,6 +664,99 @@ __global__ void k_scalar_duals(VecArgs a, DualsOut d) {
     }
 }
 
+// ---------------------------------------------------------------- certificates of the last solve (CertOut, vec_kernels.hpp)
+// The homogeneous iterate at which indicators.rs:66-76 called the member Infeasible or Unbounded, normalised into a Farkas
+// ray (y, z) / b.y or an improving ray x / (-c.x).  Reduction slots: 0 = b.y, 1 = c.x, 2 = {s, kind}, 3 = the residual's maxima.
+__device__ __forceinline__ int cert_mask(const VecArgs& a, const CertOut& d) { return d.mask[(long long)a.bfirst + blockIdx.z]; }
+__global__ __launch_bounds__(256) void k_cert_dots(VecArgs a, CertOut d) {
+    if (cert_mask(a, d) < CERT_ASK_INFEASIBLE) return;
+    if (!vbatch(a, false)) return;
+    const int stride = gridDim.x * 256;
+    double acc[2] = {0, 0};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) acc[0] += a.b[i] * a.y[i];
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < a.n; j += stride) acc[1] += a.c[j] * a.x[j];
+    block_reduce_store<2, false>(acc, a.red, 0);
+}
+// s = b.y (Infeasible: > tol by indicators.rs:72) or -c.x (Unbounded: the reference says so whenever b.y <= tol, so s may be
+// <= 0 and then nothing is proved); kind from the status and the sign of s
+__global__ void k_cert_decide(VecArgs a, CertOut d) {
+    const int ask = cert_mask(a, d);
+    if (ask < CERT_ASK_INFEASIBLE) return;
+    if (!vbatch(a, false)) return;
+    const double by = fold_sum(a.red, 0, a.nblk), cx = fold_sum(a.red, 1, a.nblk);
+    if (threadIdx.x != 0) return;
+    const double s = ask == CERT_ASK_INFEASIBLE ? by : -cx;
+    a.red[2 * RED_STRIDE] = s;
+    a.red[2 * RED_STRIDE + 1] = s > 0.0 ? (ask == CERT_ASK_INFEASIBLE ? 1.0 : 2.0) : 0.0;
+}
+// The normalised ray into work vectors -- y^ into dy, z^ into dz, x^ into row 0 of W, zeros for the ray the member does not
+// have: the pass over A that follows reads both of every member -- and, in the caller's units, to the destinations.
+__global__ __launch_bounds__(256) void k_cert_write(VecArgs a, CertOut d) {
+    const long long lp = (long long)a.bfirst + blockIdx.z;
+    if (d.mask[lp] < CERT_ASK_INFEASIBLE) return;
+    if (!vbatch(a, false)) return;
+    const double s = a.red[2 * RED_STRIDE];
+    const int kind = (int)a.red[2 * RED_STRIDE + 1];
+    const int32_t* kr = d.kr ? d.kr + lp * d.estride : nullptr;
+    const int32_t* kc = d.kr ? d.kc + lp * d.estride : nullptr;
+    double* yo = d.y && kind == 1 ? d.y + (lp - d.row0) * d.ldy : nullptr;
+    double* co = d.col && kind != 0 ? d.col + (lp - d.row0) * d.ldc : nullptr;
+    const int stride = gridDim.x * 256;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
+        const double v = kind == 1 ? a.y[i] / s : 0.0;
+        a.dy[i] = v;
+        if (yo) yo[i] = kr ? ldexp(v, kr[i]) : v;
+    }
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < a.n; j += stride) {
+        const double zh = kind == 1 ? a.z[j] / s : 0.0, xh = kind == 2 ? a.x[j] / s : 0.0;
+        a.dz[j] = zh;
+        a.W[j] = xh;
+        if (co) co[j] = kind == 1 ? (kc ? ldexp(zh, -kc[j]) : zh) : (kc ? ldexp(xh, kc[j]) : xh);
+    }
+}
+// max_j |(A^T.y^ + z^)_j| by -kc[j] (slabs d.slab wide for the first d.nxs columns; behind them a tall form's slack column,
+// whose A^T.y^ is y^ itself) or max_i |(A.x^)_i| by -kr[i] (chunk slabs of mp), into slot 3
+__global__ __launch_bounds__(256) void k_cert_residual(VecArgs a, CertOut d) {
+    const long long lp = (long long)a.bfirst + blockIdx.z;
+    if (d.mask[lp] < CERT_ASK_INFEASIBLE) return;
+    if (!vbatch(a, false)) return;
+    const int kind = (int)a.red[2 * RED_STRIDE + 1];
+    if (kind == 0) return;
+    const int32_t* kr = d.kr ? d.kr + lp * d.estride : nullptr;
+    const int32_t* kc = d.kr ? d.kc + lp * d.estride : nullptr;
+    const int stride = gridDim.x * 256;
+    double acc = 0.0;
+    if (kind == 1) {
+        for (int j = blockIdx.x * 256 + threadIdx.x; j < a.n; j += stride) {
+            double aty = 0.0;
+            if (j < d.nxs) for (int s = 0; s < a.nsplit; ++s) aty += a.ATpart[(long long)s * d.slab + j];
+            else aty = a.dy[j - d.nxs];
+            const double r = aty + a.dz[j];
+            acc = max_nan(acc, fabs(kc ? ldexp(r, -kc[j]) : r));
+        }
+    } else {
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
+            double ax = a.Ax[i];
+            for (int ch = 1; ch < a.ax_chunks; ++ch) ax += a.Ax[(long long)ch * a.mp + i];
+            acc = max_nan(acc, fabs(kr ? ldexp(ax, -kr[i]) : ax));
+        }
+    }
+    block_max_store(acc, a.red, 3);
+}
+__global__ void k_cert_info(VecArgs a, CertOut d) {
+    const long long lp = (long long)a.bfirst + blockIdx.z;
+    const int ask = d.mask[lp];
+    if (ask == CERT_ASK_NOT) return;
+    if (!vbatch(a, false)) return;
+    const bool cert = ask >= CERT_ASK_INFEASIBLE;
+    const double kind = cert ? a.red[2 * RED_STRIDE + 1] : 0.0;
+    const double res = kind != 0.0 ? fold_max(a.red, 3, a.nblk, 0.0) : NAN;
+    if (threadIdx.x == 0) {
+        double* o = d.info + CERT_INFO_DOUBLES * (lp - d.row0);
+        o[0] = cert ? a.red[2 * RED_STRIDE] : NAN; o[1] = res; o[2] = a.S[S_TAU]; o[3] = a.S[S_KAPPA]; o[4] = kind;
+    }
+}
+
 // ---------------------------------------------------------------- launchers
 static inline dim3 vgrid(const VecArgs& a) { return dim3(a.nblk, 1, a.bcount); }
 static inline dim3 sgrid(const VecArgs& a) { return dim3(1, 1, a.bcount); }
@@ -751,6 +844,15 @@ int vec_final_x(const VecArgs& a, double* xout, hipStream_t st, const XRank* xr)
 void vec_final_duals(const VecArgs& a, const DualsOut& d, hipStream_t st) {
     hipLaunchKernelGGL(k_final_duals, vgrid(a), dim3(256), 0, st, a, d);
     hipLaunchKernelGGL(k_scalar_duals, sgrid(a), dim3(64), 0, st, a, d);
+}
+void vec_cert_rays(const VecArgs& a, const CertOut& d, hipStream_t st) {
+    hipLaunchKernelGGL(k_cert_dots, vgrid(a), dim3(256), 0, st, a, d);
+    hipLaunchKernelGGL(k_cert_decide, sgrid(a), dim3(64), 0, st, a, d);
+    hipLaunchKernelGGL(k_cert_write, vgrid(a), dim3(256), 0, st, a, d);
+}
+void vec_cert_residual(const VecArgs& a, const CertOut& d, hipStream_t st) {
+    hipLaunchKernelGGL(k_cert_residual, vgrid(a), dim3(256), 0, st, a, d);
+    hipLaunchKernelGGL(k_cert_info, sgrid(a), dim3(64), 0, st, a, d);
 }
 // One column group of M (its tiles, in the grouped tile list's order) <-> a contiguous block, for the group-by-group
 // cross-rank sum of the column-split mode.  One workgroup per tile.

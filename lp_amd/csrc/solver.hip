@@ -2483,6 +2483,84 @@ extern "C" int lpipm_get_duals_device(lpipm_ctx* c, void* y_dev, uint64_t ldy, v
     return LPIPM_OK;
 }
 
+// ---- certificates of the last solve (lpipm_get_certificate, lpipm_get_certificate_device) -------------------------------
+// The launches of vec_cert_rays, one pass over the resident image and vec_cert_residual over the whole resident batch,
+// delivering the members [row0, row0 + rows).  Destinations as in run_duals: device rows written directly, host ones through
+// the staging block, which carries the mask in and the info records out.  The pass is the residual pair's (ctx_gemv_dual:
+// A^T.y^ and A.x^ in one read of the image, the structural slack block, shared images, the tall forms' X and the `eq` rows),
+// with a Batch that has no done word: every member is done by now.
+struct CertRun { const double *ys = nullptr, *cols = nullptr, *infos = nullptr; };
+static int run_certificates(lpipm_ctx* c, size_t row0, size_t rows, bool want_y, bool want_col, double* y_dev, uint64_t ldy,
+                            double* col_dev, uint64_t ldc, CertRun& out) {
+    Problem& p = c->p;
+    const size_t B = (size_t)p.B, m = (size_t)p.m, n = (size_t)p.n;
+    const bool stage_y = want_y && !y_dev, stage_c = want_col && !col_dev;
+    const size_t nmask = (B + 1) / 2, ninfo = (size_t)CERT_INFO_DOUBLES * rows, ny = stage_y ? rows * m : 0, nc = stage_c ? rows * n : 0;
+    LP_TRY(stage_grow(c, nmask + ninfo + ny + nc));
+    hipStream_t st = c->rs.st;
+    int32_t* mask = (int32_t*)c->stage_host;
+    bool any = false;
+    for (size_t k = 0; k < B; ++k) {
+        const int32_t code = c->last_ret[k];
+        mask[k] = k < row0 || k >= row0 + rows ? CERT_ASK_NOT
+                : code == LPIPM_INFEASIBLE ? CERT_ASK_INFEASIBLE : code == LPIPM_UNBOUNDED ? CERT_ASK_UNBOUNDED : CERT_ASK_PLAIN;
+        any = any || mask[k] >= CERT_ASK_INFEASIBLE;
+    }
+    out.infos = c->stage_host + nmask; out.ys = out.infos + ninfo; out.cols = out.ys + ny;
+    LP_HIP(hipMemcpyAsync(c->stage_dev, c->stage_host, nmask * sizeof(double), hipMemcpyHostToDevice, st));
+    double* dev = c->stage_dev + nmask;
+    CertOut d{};
+    d.info = dev; d.row0 = (long long)row0; d.mask = (const int32_t*)c->stage_dev;
+    d.y = stage_y ? dev + ninfo : y_dev; d.ldy = (long long)(stage_y ? m : ldy);
+    d.col = stage_c ? dev + ninfo + ny : col_dev; d.ldc = (long long)(stage_c ? n : ldc);
+    if (p.scale_passes > 0) { d.kr = p.sc.kr; d.kc = p.sc.kc; d.estride = p.sc.estride; }
+    d.nxs = p.tall ? p.tv.nx : (int)n; d.slab = p.tall ? p.npa : p.np;
+    VecArgs v = p.va;                      // (a copy: the solves' own block keeps its ax_chunks)
+    if (any) {
+        vec_cert_rays(v, d, st);
+        LP_HIP(hipGetLastError());
+        v.ax_chunks = gemv_dual_chunks(p.npa);
+        const uint64_t passes = c->gemv_passes;
+        LP_HIP(ctx_gemv_dual(c, v.W, v.dy, v.Ax, Batch{p.bt.count, p.bt.stride, nullptr, p.bt.first}));
+        c->gemv_passes = passes;           // (lpipm_phase_times counts a solve's passes)
+    }
+    vec_cert_residual(v, d, st);           // (without a certificate to form: its scalar launch alone has work)
+    LP_HIP(hipGetLastError());
+    LP_HIP(hipMemcpyAsync(c->stage_host + nmask, dev, (ninfo + ny + nc) * sizeof(double), hipMemcpyDeviceToHost, st));
+    LP_HIP(hipStreamSynchronize(st));
+    return LPIPM_OK;
+}
+static lpipm_cert_info cert_info_of(const double* rec, int32_t status) {
+    return lpipm_cert_info{rec[0], rec[1], rec[2], rec[3], (int32_t)rec[4], status};
+}
+extern "C" int lpipm_get_certificate(lpipm_ctx* c, uint64_t member, double* y_out, double* col_out, lpipm_cert_info* info_out) {
+    LP_TRY(duals_ready(c));
+    if (member >= (uint64_t)c->p.B || !info_out) return LPIPM_ERR_BAD_ARGUMENT;
+    LP_HIP(hipSetDevice(c->device));
+    CertRun r;
+    LP_TRY(run_certificates(c, (size_t)member, 1, y_out != nullptr, col_out != nullptr, nullptr, 0, nullptr, 0, r));
+    const lpipm_cert_info info = cert_info_of(r.infos, c->last_ret[(size_t)member]);
+    if (y_out && info.kind == LPIPM_CERT_FARKAS) std::memcpy(y_out, r.ys, c->p.m * sizeof(double));
+    if (col_out && info.kind != LPIPM_CERT_NONE) std::memcpy(col_out, r.cols, c->p.n * sizeof(double));
+    *info_out = info;
+    return LPIPM_OK;
+}
+extern "C" int lpipm_get_certificate_device(lpipm_ctx* c, void* y_dev, uint64_t ldy, void* col_dev, uint64_t ldc,
+                                            lpipm_cert_info* info_out) {
+    LP_TRY(duals_ready(c));
+    const uint64_t B = (uint64_t)c->p.B;
+    if (!info_out || (y_dev && ldy < c->p.m) || (col_dev && ldc < c->p.n)) return LPIPM_ERR_BAD_ARGUMENT;
+    LP_HIP(hipSetDevice(c->device));
+    // nothing is launched before both destinations are known to be device memory that holds every member's row
+    const Dim dy[2] = {{B, (int64_t)ldy}, {c->p.m, 1}}, dc[2] = {{B, (int64_t)ldc}, {c->p.n, 1}};
+    if (y_dev) LP_TRY(source_inside(c, y_dev, dy, 2, sizeof(double)));
+    if (col_dev) LP_TRY(source_inside(c, col_dev, dc, 2, sizeof(double)));
+    CertRun r;
+    LP_TRY(run_certificates(c, 0, (size_t)B, false, false, (double*)y_dev, ldy, (double*)col_dev, ldc, r));
+    for (uint64_t k = 0; k < B; ++k) info_out[k] = cert_info_of(r.infos + CERT_INFO_DOUBLES * k, c->last_ret[(size_t)k]);
+    return LPIPM_OK;
+}
+
 extern "C" int lpipm_set_profiling(lpipm_ctx* c, int on) {
     if (!c) return LPIPM_ERR_BAD_ARGUMENT;
     c->profiling = on < 0 ? 0 : (on > 2 ? 1 : on);

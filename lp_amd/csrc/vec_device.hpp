@@ -16,6 +16,13 @@ __device__ __forceinline__ double wave_min(double v) {
     for (int off = 32; off >= 1; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
     return v;
 }
+// max that keeps a NaN once it has met one (a residual that is NaN must not read as small)
+__device__ __forceinline__ double max_nan(double a, double b) { return (b > a || b != b) ? b : a; }
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = max_nan(v, __shfl_xor(v, off, 64));
+    return v;
+}
 // workgroup (256 threads) reduction of K values; thread 0 writes red[slot0 + k][blockIdx.x]
 template <int K, bool IS_MIN>
 __device__ __forceinline__ void block_reduce_store(double (&v)[K], double* red, int slot0) {
@@ -46,6 +53,21 @@ __device__ __forceinline__ double fold_min(const double* red, int slot, int nblk
     double s = init;
     for (int b = (int)(threadIdx.x & 63); b < nblk; b += 64) s = fmin(s, red[slot * RED_STRIDE + b]);
     return wave_min(s);
+}
+
+// workgroup (256 threads) maximum of one value (>= 0 or NaN); thread 0 writes red[slot][blockIdx.x]
+__device__ __forceinline__ void block_max_store(double v, double* red, int slot) {
+    __shared__ double smx[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double w = wave_max(v);
+    if (lane == 0) smx[wave] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) red[slot * RED_STRIDE + blockIdx.x] = max_nan(max_nan(smx[0], smx[1]), max_nan(smx[2], smx[3]));
+}
+__device__ __forceinline__ double fold_max(const double* red, int slot, int nblk, double init) {
+    double s = init;
+    for (int b = (int)(threadIdx.x & 63); b < nblk; b += 64) s = max_nan(s, red[slot * RED_STRIDE + b]);
+    return wave_max(s);
 }
 
 // LP blockIdx.z of a lockstep batch.  `check_done`: kernels of the iteration skip an LP that has finished.

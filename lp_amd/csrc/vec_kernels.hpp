@@ -101,6 +101,29 @@ struct DualsOut {
     const int32_t *kr, *kc; long long estride;
 };
 void vec_final_duals(const VecArgs& a, const DualsOut& d, hipStream_t st);
+// The certificate of the iterate the arena holds (lpipm_get_certificate[_device]).  mask[k] says what member k of the resident
+// batch is asked for: CERT_ASK_NOT (skipped by every kernel), CERT_ASK_PLAIN (a status without a certificate: only its info
+// record is written), CERT_ASK_INFEASIBLE, CERT_ASK_UNBOUNDED.  vec_cert_rays: s = b.y, respectively -c.x (slots 0 and 1 folded
+// in fold_sum's order), kind (1 Farkas, 2 ray, 0 when s <= 0) into slot 2; y^ = y / s into dy, z^ = z / s into dz, x^ = x / s
+// into row 0 of W (zeros for the ray the member has not), and to row k - row0 of y (Farkas only) and col (z^, respectively x^) in
+// the caller's units: y^ by kr, z^ by -kc, x^ by kc.  The caller then passes over A with W and dy (a.ax_chunks set), and
+// vec_cert_residual takes max_j |A^T.y^ + z^| by -kc (the first nxs columns from row-split slabs `slab` doubles wide, the
+// columns behind them from y^: a tall form's slack block) or max_i |A.x^| by -kr into slot 3, and writes CERT_INFO_DOUBLES per
+// row of info: {s, residual, tau, kappa, kind}, s and residual NaN for CERT_ASK_PLAIN, residual NaN for kind 0.  The grid over
+// a member is a.nblk workgroups whatever the count.  Written in the arena: slots 0-3, dy, dz, W below m and n.
+enum { CERT_ASK_NOT = 0, CERT_ASK_PLAIN = 1, CERT_ASK_INFEASIBLE = 2, CERT_ASK_UNBOUNDED = 3 };
+constexpr int CERT_INFO_DOUBLES = 5;
+struct CertOut {
+    double* y; long long ldy;
+    double* col; long long ldc;
+    double* info;
+    long long row0;
+    const int32_t* mask;
+    const int32_t *kr, *kc; long long estride;
+    int nxs; long long slab;
+};
+void vec_cert_rays(const VecArgs& a, const CertOut& d, hipStream_t st);
+void vec_cert_residual(const VecArgs& a, const CertOut& d, hipStream_t st);
 // Y[q][i] += add_q[i] (i < m): the addend of a column-split A.w after its cross-rank sum
 // packed has mp*(mp+128)/2 doubles; dir 0 = M -> packed, 1 = packed -> M (mp a multiple of 128, ld even)
 void vec_pack_lower(double* M, long long ld, int mp, double* packed, int dir, hipStream_t st);
