@@ -140,6 +140,19 @@ extern "C" {
         ctx: *mut lpipm_ctx, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, b_ub: *const f64, m_eq: u64,
         a_eq: *const f64, lda_eq: u64, b_eq: *const f64, c: *const f64, c0: f64,
     ) -> c_int;
+    /// The bounded form: lpipm_upload_ub_eq's LP with upper bounds on nb of its structural columns (upper[n], +inf = none).  The
+    /// bound block is eliminated in closed form, so the normal matrix stays m x m; x_slack has n + m_ub + nb entries, the bound
+    /// slacks last, y of lpipm_get_duals m + nb (Cholesky arm only; nb == 0 is lpipm_upload_ub_eq itself; see include/lpipm.h).
+    pub fn lpipm_upload_bounded(
+        ctx: *mut lpipm_ctx, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, b_ub: *const f64, m_eq: u64,
+        a_eq: *const f64, lda_eq: u64, b_eq: *const f64, c: *const f64, c0: f64, upper: *const f64,
+    ) -> c_int;
+    /// Kernel entries of a bounded upload: M~ (m x m, lower triangle) at dinv_ext[n + nb], and its reduced sym_solve.
+    pub fn lpipm_k_bounded_normal(ctx: *mut lpipm_ctx, dinv_ext: *const f64, m_out: *mut f64) -> c_int;
+    pub fn lpipm_k_bounded_sym_solve(
+        ctx: *mut lpipm_ctx, dinv_ext: *const f64, nrhs: c_int, r1: *const f64, r2: *const f64, u_out: *mut f64,
+        v_out: *mut f64, info_out: *mut i32,
+    ) -> c_int;
     pub fn lpipm_solve(
         ctx: *mut lpipm_ctx, opts: *const lpipm_opts, x_slack_out: *mut f64, fun_out: *mut f64,
         iterations_out: *mut u64, log: *mut lpipm_iter_row,

@@ -181,6 +181,46 @@ int lpipm_upload_ub_eq_tall(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const dou
                             const double* b_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq, const double* b_eq,
                             const double* c, double c0);
 
+/* The bounded form: min c^T x, A_ub.x <= b_ub, A_eq.x = b_eq, 0 <= x, x_j <= upper[j] -- capacities, 0-1 relaxations, box
+ * constraints, trust regions.  The arguments of lpipm_upload_ub_eq, plus upper[n]: +inf means no bound; B is the ascending list
+ * of the nb columns with a finite one.  Written as `ub` rows the bounds would grow the normal matrix from m x m to
+ * (m + nb) x (m + nb), m = m_ub + m_eq.  Here the LP that is solved is that explicit one,
+ *   A_ext = [[A, 0], [E_B, I_nb]]   b_ext = [b; u_B]   c_ext = [c; 0]   x_ext = [x; w]   z_ext = [z; v]   y_ext = [y; y_b]
+ * (A the slack form of lpipm_upload_ub_eq, w the bound slacks, v their reduced costs, y_b = -v at a solution), by the unchanged
+ * algorithm on the extended vectors -- but the bound block of the Newton system is diagonal and is eliminated in closed form.
+ * With dx = x / z, dw = w / v, s = dx_j + dw_j and D~_j = 1 / (z_j / x_j + v_j / w_j) for j in B, D~_j = dx_j elsewhere,
+ * sym_solve(r1, r2) (newton_equations.rs:214-225), r1 = [r1_x; r1_w], r2 = [r2_1; r2_2], reads
+ *   M~   = A.diag(D~).A^T                    m x m: the A.D.A^T build with D~ for dinv (+ diag(D_s) on the `ub` rows, as always)
+ *   W_j  = D~_j (r1_x,j - r1_w,j) - (dx_j / s) r2_2,j        j in B;   W_j = dx_j r1_x,j otherwise
+ *   v_1  = M~^-1 (r2_1 + A.W);   t = A^T.v_1                 one pass A.w, one solve, one pass A^T.v: the dense arm's
+ *   g_j  = D~_j (t_j - r1_x,j + r1_w,j);  u_x,j = g_j + (dx_j / s) r2_2,j;  u_w,j = -g_j + (dw_j / s) r2_2,j     j in B
+ *   u_x,j = dx_j (t_j - r1_x,j) otherwise;   v_2,j = r1_w,j + u_w,j / dw_j;   u = [u_x; u_w],  v = [v_1; v_2]
+ * (u_w never as r2_2 - u_x: that cancels once a column sits at its bound.)  The bound block is never stored and never
+ * multiplied; an iteration makes as many passes over A as after lpipm_upload_ub_eq.
+ * Outputs.  x_slack_out of lpipm_solve[_device] has n + m_ub + nb entries: the structural values, the `ub` slacks, then the
+ * bound slacks w in ascending column order.  lpipm_get_duals[_device] and lpipm_get_certificate[_device] serve the upload:
+ * y has m + nb entries, the bound rows last (a bound row's multiplier is <= 0 and equals -v_j up to the dual residual); z and
+ * col are as long as x_slack_out.
+ * Contract against the explicit form -- the same LP with its bound rows appended to A_ub, through lpipm_upload_ub_eq: the same
+ * status and iteration count, x and fun to rounding (no bit-identity).  nb == 0 (upper NULL or all +inf): exactly
+ * lpipm_upload_ub_eq on the same arguments -- the same request, the same bits.
+ * Memory: nothing the context holds grows as (m + nb)^2; lpipm_get_resident_bytes counts the index lists.  Phase times are as
+ * after lpipm_upload_ub_eq.  lpipm_set_scaling works as on any upload: exponents from the stored structural block; the bound
+ * row of column j gets kr = -kc[j] and its slack column kc = kc[j] (its entries stay exactly 1, the block unstored),
+ * u_j <- ldexp(u_j, -kc[j]), x_j and w_j come back by ldexp(., kc[j]); lpipm_get_scaling returns m + nb row exponents and
+ * n + m_ub + nb column exponents.
+ * Refusals (a refused call leaves the resident problem as it was).  An upper[j] that is NaN or -inf: LPIPM_ERR_BAD_ARGUMENT (any
+ * finite value is accepted, as the explicit form accepts it).  Both blocks absent: LPIPM_UNCONSTRAINED.  solver_type 1 or 2 at
+ * solve time, a column-split context, a context with the refined solves, lpipm_update_vectors[_device] and lpipm_k_adat:
+ * LPIPM_ERR_UNSUPPORTED.  lpipm_k_iteration, lpipm_k_gemv_n, lpipm_k_gemv_t and lpipm_k_gemv_dual see A_ext with its extended
+ * lengths.  No first factor is kept.
+ * Out of scope: lockstep and shared-matrix batches of bounded LPs; lpipm_upload_device and lpipm_solve_batch*; a kept first
+ * factor (M~_1 depends on A and B alone: a follow-up); the QR arms; f32; bounds on the tall forms (there a bound is one more
+ * cheap row already); lower bounds other than 0; free columns. */
+int lpipm_upload_bounded(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub, const double* b_ub,
+                         uint64_t m_eq, const double* A_eq, uint64_t lda_eq, const double* b_eq, const double* c, double c0,
+                         const double* upper);
+
 /* New b and c for the resident problem of lpipm_upload / lpipm_upload_slack: b[m] and c[n] in that upload's own form (c with
  * its slack entries).  A stays where it is, so a sweep over right-hand sides or costs, or a sequence of LPs over one
  * constraint matrix, pays for the upload of A once -- and, with it, for the first iteration's factor (below), which depends
@@ -505,7 +545,7 @@ int lpipm_update_vectors_device(lpipm_ctx* ctx, const void* b_dev, const void* c
  *   LPIPM_ERR_NO_PROBLEM: nothing resident, or no solve has completed since the last event that changes what the iterate
  *   means: any upload, lpipm_update_vectors[_device], lpipm_update_lockstep_vectors[_device] (b and c are new, the iterate is
  *   old), an lpipm_k_* entry that writes the iterate (lpipm_k_iteration, lpipm_k_tall_normal, lpipm_k_tall_schur,
- *   lpipm_k_tall_sym_solve), a solve that returned a runtime code (>= 100), lpipm_solve_batch* (which replace the resident
+ *   lpipm_k_tall_sym_solve, lpipm_k_bounded_normal, lpipm_k_bounded_sym_solve), a solve that returned a runtime code (>= 100), lpipm_solve_batch* (which replace the resident
  *   problem with whichever chunk or member the context solved last: that is nobody's to ask about).  All three solver arms qualify.  Not served: lpipm_solve_batch*, lpipm_solve_f32, column-split contexts.
  * Cost: one vector launch and one scalar launch over the batch (gridDim.z = the resident count; the grid over a member
  *   depends on m and n alone), reduction slot 0, and for host destinations a staging block of the context that
@@ -656,6 +696,17 @@ int lpipm_k_tall_sym_solve(lpipm_ctx* ctx, const double* dinv, int nrhs, const d
  * S_out (m_eq x m_eq row-major, LOWER triangle valid) = A_eq.K^-1.A_eq^T, as built (before its own factorisation).  Any other
  * upload, a batch of such LPs included: LPIPM_ERR_UNSUPPORTED.  The iterate of the context is overwritten. */
 int lpipm_k_tall_schur(lpipm_ctx* ctx, const double* dinv, double* S_out);
+/* On a bounded upload (lpipm_upload_bounded with nb > 0), with m = m_ub + m_eq, n = nx + m_ub and dinv_ext[n + nb] = x / z of
+ * the explicit LP's columns (the bound slacks last): M_out (m x m row-major, LOWER triangle valid) = M~ = A.diag(D~).A^T,
+ * D~_j = 1 / (1 / dinv_ext[j] + 1 / dinv_ext[n + k]) on the k-th bounded column, dinv_ext[j] elsewhere.  Any other upload:
+ * LPIPM_ERR_UNSUPPORTED.  The iterate of the context is overwritten. */
+int lpipm_k_bounded_normal(lpipm_ctx* ctx, const double* dinv_ext, double* M_out);
+/* The reduced sym_solve on a bounded upload at the given dinv_ext[n + nb], for nrhs (1|2) right-hand sides of the explicit LP:
+ * R1 nrhs x (n + nb), R2 nrhs x (m + nb) -> U_out nrhs x (n + nb), V_out nrhs x (m + nb), with M_ext.V = R2 + A_ext.(dinv_ext * R1),
+ * U = dinv_ext * (A_ext^T.V - R1) in exact arithmetic.  info_out (nullable): pivot failure of M~ as lpipm_k_potrf.  The iterate
+ * of the context is overwritten. */
+int lpipm_k_bounded_sym_solve(lpipm_ctx* ctx, const double* dinv_ext, int nrhs, const double* R1, const double* R2, double* U_out,
+                              double* V_out, int32_t* info_out);
 /* newton_equations.rs:129-131: in-place lower Cholesky of the m x m row-major matrix M (lower
  * triangle read, lower triangle written).  info_out: 0, or k+1 for the first non-positive pivot.
  * ms_out: the factorisation's launches, per repeat. */

@@ -23,6 +23,7 @@
 #include <stdexcept>
 #include <string>
 #include <utility>
+#include <limits>
 #include <vector>
 
 #include "lpipm.h"
@@ -101,8 +102,12 @@ public:
     const std::vector<F>& c() const { return c_; }                   // :52-54
     F c0() const { return c0_; }                                     // :57-59
     uint64_t n_slack() const { return n_slack_; }
+    // Not in the reference: the upper bounds of the structural columns given to ProblemBuilder::upper (+inf: none; empty: no
+    // bounds at all) and how many of them are finite.  A(), b() and c() stay the slack form WITHOUT the bounds.
+    const std::vector<F>& upper() const { return upper_; }
+    uint64_t n_bounded() const { return n_bounded_; }
     std::vector<F> denormalize_x_into(std::vector<F> x_slack) const {  // :65-69
-        x_slack.resize(x_slack.size() - n_slack_);
+        x_slack.resize(x_slack.size() - n_slack_ - n_bounded_);      // (a bounded solve's x_slack ends with the bound slacks)
         return x_slack;
     }
 
@@ -112,6 +117,8 @@ private:
     std::vector<F> b_, c_;
     F c0_ = 0;
     uint64_t n_slack_ = 0;
+    std::vector<F> upper_;
+    uint64_t n_bounded_ = 0;
 };
 
 // src/linear_program.rs:72-170
@@ -120,6 +127,9 @@ public:
     explicit BasicProblemBuilder(const std::vector<F>& c) : c_(c) {}
     BasicProblemBuilder& ub(const BasicMatrix<F>& A, const std::vector<F>& b) { ub_A_ = &A; ub_b_ = &b; return *this; }  // :93-96
     BasicProblemBuilder& eq(const BasicMatrix<F>& A, const std::vector<F>& b) { eq_A_ = &A; eq_b_ = &b; return *this; }  // :102-105
+    // Not in the reference: upper bounds x_j <= u[j] on the structural columns, one entry per column, +infinity where there is
+    // none.  InteriorPoint::solve then runs the bounded form (lpipm_upload_bounded): the normal matrix keeps its order.  f64 only.
+    BasicProblemBuilder& upper(const std::vector<F>& u) { upper_ = &u; return *this; }
     BasicProblem<F> build() const {                                                                               // :125-169
         const uint64_t n = c_.size();
         const uint64_t m_ub = ub_A_ ? ub_A_->rows : 0, m_eq = eq_A_ ? eq_A_->rows : 0;
@@ -153,6 +163,14 @@ public:
             for (uint64_t j = 0; j < n; ++j) p.c_[j] = c_[j];
             p.n_slack_ = m_ub;
         }
+        if (upper_) {
+            if (upper_->size() != n) raise_for(LPIPM_INCOMPATIBLE_DIMENSIONS);
+            for (const F u : *upper_) {
+                if (u != u || u == -std::numeric_limits<F>::infinity()) raise_for(LPIPM_INVALID_PARAMETER);
+                if (u != std::numeric_limits<F>::infinity()) ++p.n_bounded_;
+            }
+            p.upper_ = *upper_;
+        }
         return p;
     }
 
@@ -162,6 +180,7 @@ private:
     const std::vector<F>* ub_b_ = nullptr;
     const BasicMatrix<F>* eq_A_ = nullptr;
     const std::vector<F>* eq_b_ = nullptr;
+    const std::vector<F>* upper_ = nullptr;
 };
 template <class F> inline BasicProblemBuilder<F> BasicProblem<F>::target(const std::vector<F>& c) { return BasicProblemBuilder<F>(c); }
 
@@ -258,13 +277,13 @@ public:
         uint64_t it = 0;
         upload_and_solve(ctx, problem, x, fun, it);
         const Matrix& A = problem.A();
-        std::vector<double> y(A.rows), z(A.cols);
+        const std::size_t ns = problem.n_slack(), nb = problem.n_bounded();     // (bounded: the bound rows and their slacks come last)
+        std::vector<double> y(A.rows + nb), z(A.cols + nb);
         lpipm_dual_info info{};
         raise_for(lpipm_get_duals(ctx, 0, y.data(), z.data(), &info));
-        const std::size_t ns = problem.n_slack();
         return DualResult{OptimizeResult(problem.denormalize_x_into(std::move(x)), fun, it),
-                          std::vector<double>(y.begin(), y.begin() + ns), std::vector<double>(y.begin() + ns, y.end()),
-                          std::vector<double>(z.begin(), z.end() - ns), info.dual_fun};
+                          std::vector<double>(y.begin(), y.begin() + ns), std::vector<double>(y.begin() + ns, y.end() - nb),
+                          std::vector<double>(z.begin(), z.end() - ns - nb), info.dual_fun};
     }
     // solve(), but an Infeasible or Unbounded problem throws a CertifiedError (a LinearProgramError of the same kind) that
     // carries the certificate of the solve's last iterate (lpipm_get_certificate on the same context; tall_form() /
@@ -279,17 +298,17 @@ public:
         const int rc = upload_and_solve_rc(ctx, problem, x, fun, it);
         if (rc == LPIPM_INFEASIBLE || rc == LPIPM_UNBOUNDED) {
             const Matrix& A = problem.A();
-            std::vector<double> y(A.rows), col(A.cols);
+            const std::size_t ns = problem.n_slack(), nb = problem.n_bounded();
+            std::vector<double> y(A.rows + nb), col(A.cols + nb);
             lpipm_cert_info info{};
             raise_for(lpipm_get_certificate(ctx, 0, y.data(), col.data(), &info));
-            const std::size_t ns = problem.n_slack();
             Certificate cert;
             cert.kind = info.kind; cert.scale = info.scale; cert.residual = info.residual;
             if (info.kind == LPIPM_CERT_FARKAS) {
-                cert.y_ub.assign(y.begin(), y.begin() + ns); cert.y_eq.assign(y.begin() + ns, y.end());
-                cert.z.assign(col.begin(), col.end() - ns);
+                cert.y_ub.assign(y.begin(), y.begin() + ns); cert.y_eq.assign(y.begin() + ns, y.end() - nb);
+                cert.z.assign(col.begin(), col.end() - ns - nb);
             } else if (info.kind == LPIPM_CERT_RAY)
-                cert.x.assign(col.begin(), col.end() - ns);
+                cert.x.assign(col.begin(), col.end() - ns - nb);
             throw CertifiedError(static_cast<ErrorKind>(rc), lpipm_strerror(rc), std::move(cert));
         }
         if (rc == LPIPM_ITERATION_LIMIT) raise_for(rc, x);          // payload: x / tau, mod.rs:237-239
@@ -302,6 +321,7 @@ public:
         lpipm_ctx* ctx = nullptr;
         raise_for(lpipm_create(device_, &ctx));
         struct Guard { lpipm_ctx* c; ~Guard() { lpipm_destroy(c); } } guard{ctx};
+        if (problem.n_bounded() > 0) raise_for(LPIPM_ERR_UNSUPPORTED);     // the bounded form has no f32 arm
         const MatrixF32& A = problem.A();
         std::vector<float> x(A.cols);
         float fun = 0.0f;
@@ -323,6 +343,17 @@ private:
     // The upload of `problem` in the form the opt-ins select, and lpipm_solve.  -> the solve's status
     int upload_and_solve_rc(lpipm_ctx* ctx, const Problem& problem, std::vector<double>& x, double& fun, uint64_t& it) const {
         const Matrix& A = problem.A();
+        if (problem.n_bounded() > 0) {
+            // the bounded form, whatever the opt-ins say (on a tall form a bound is one more `ub` row): the blocks of
+            // A = [[A_ub I], [A_eq 0]] with lda = cols, the bounds as given; x_slack ends with the nb bound slacks
+            const std::size_t m_ub = problem.n_slack(), m_eq = A.rows - m_ub;
+            raise_for(lpipm_upload_bounded(ctx, A.cols - m_ub, m_ub, m_ub ? A.data.data() : nullptr, A.cols,
+                                           m_ub ? problem.b().data() : nullptr, m_eq, m_eq ? A.data.data() + m_ub * A.cols : nullptr,
+                                           A.cols, m_eq ? problem.b().data() + m_ub : nullptr, problem.c().data(), problem.c0(),
+                                           problem.upper().data()));
+            x.assign(A.cols + problem.n_bounded(), 0.0);
+            return lpipm_solve(ctx, &o_, x.data(), &fun, &it, nullptr);
+        }
         if (tall_eq_ && problem.n_slack() > 0 && problem.n_slack() <= A.rows && problem.n_slack() < A.cols) {
             // A = [[X I], [A_eq 0]]: the `ub` block is the first n_slack rows, the `eq` block the rest, both with lda = cols
             const std::size_t m_ub = problem.n_slack(), m_eq = A.rows - m_ub;

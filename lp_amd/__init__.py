@@ -135,8 +135,12 @@ def _square(M):
 class Problem:
     """A linear program in slack form (linear_program.rs:24-30): min c'x st A x == b, x >= 0."""
 
-    def __init__(self, A, b, c, c0, n_slack, parts=None, dtype=np.float64):
+    def __init__(self, A, b, c, c0, n_slack, parts=None, dtype=np.float64, upper=None):
         self._A, self._b, self._c, self._c0, self._n_slack = A, b, c, float(c0), int(n_slack)
+        # ProblemBuilder.upper: one entry per structural column, +inf where there is no bound (None: no bounds at all).
+        # A(), b() and c() stay the slack form WITHOUT the bounds; Context.upload hands them to lpipm_upload_bounded.
+        self._upper = upper
+        self._bounded = np.flatnonzero(np.isfinite(upper)) if upper is not None else np.zeros(0, dtype=np.int64)
         # F of Problem<F> (linear_program.rs:24): float32 when every array the builder was given is float32 (the reference
         # infers F from its ndarray arguments), float64 otherwise.  A Problem<f32> is solved by InteriorPoint<f32>
         # (lpipm_solve_f32: every operation in f32, src/float.rs:42-43).
@@ -172,16 +176,35 @@ class Problem:
     def n_slack(self) -> int:
         return self._n_slack
 
+    def upper(self):
+        """The upper bounds of the structural columns (+inf: none), or None for a Problem without bounds."""
+        return self._upper
+
+    def n_bounded(self) -> int:
+        return int(self._bounded.shape[0])
+
     def denormalize_x_into(self, x_slack: np.ndarray) -> np.ndarray:   # :65-69
-        return np.array(x_slack[: x_slack.shape[0] - self._n_slack])
+        # (a bounded upload's x_slack ends with the bound slacks w, behind the `ub` slacks)
+        return np.array(x_slack[: x_slack.shape[0] - self._n_slack - self.n_bounded()])
 
     def denormalize_duals(self, y: np.ndarray, z: np.ndarray):
         """The counterpart of denormalize_x_into for the duals of the slack form (Context.duals): the rows split as
         ProblemBuilder::build stacks them (linear_program.rs:145-158: the `ub` rows first, one slack column each, then the
         `eq` rows), z cut to the structural columns.  -> (y_ub, y_eq, reduced_costs)"""
         y, z = np.asarray(y), np.asarray(z)
-        ns = self._n_slack
-        return np.array(y[:ns]), np.array(y[ns:]), np.array(z[: z.shape[0] - ns])
+        ns, nb = self._n_slack, self.n_bounded()      # (a bounded upload: the bound rows and their slack columns come last)
+        return np.array(y[:ns]), np.array(y[ns: y.shape[0] - nb]), np.array(z[: z.shape[0] - ns - nb])
+
+    def denormalize_bound_duals(self, z: np.ndarray) -> np.ndarray:
+        """The multipliers v_j >= 0 of the bounds x_j <= u_j per structural column (0 where there is no bound), from the z
+        of a bounded upload (Context.duals): the reduced costs of the bound slacks, which are its last entries.  The bound
+        row's own multiplier is y_b = -v up to the dual residual, and d fun / d u_j = -v_j."""
+        z = np.asarray(z)
+        nb = self.n_bounded()
+        v = np.zeros(z.shape[0] - self._n_slack - nb)
+        if nb:
+            v[self._bounded] = z[z.shape[0] - nb:]
+        return v
 
     def denormalize_certificate(self, y, col, kind: int):
         """The counterpart of denormalize_duals for a certificate of the slack form (Context.certificate): the rows split as
@@ -189,15 +212,27 @@ class Problem:
         Farkas (kind 1): -> (y_ub, y_eq, z) with A_ub^T y_ub + A_eq^T y_eq + z ~ 0, y_ub <= 0, z >= 0,
         b_ub.y_ub + b_eq.y_eq = 1.  Ray (kind 2; y is None): -> (None, None, x) with A_ub x <= 0, A_eq x ~ 0, x >= 0,
         c.x = -1.  No certificate (kind 0): -> (None, None, None)."""
-        ns = self._n_slack
+        ns, nb = self._n_slack, self.n_bounded()      # (a bounded upload: the bound rows and their slack columns come last)
         if kind == _capi.CERT_NONE:
             return None, None, None
         col = np.asarray(col)
-        cut = np.array(col[: col.shape[0] - ns])
+        cut = np.array(col[: col.shape[0] - ns - nb])
         if kind == _capi.CERT_RAY:
             return None, None, cut
         y = np.asarray(y)
-        return np.array(y[:ns]), np.array(y[ns:]), cut
+        return np.array(y[:ns]), np.array(y[ns: y.shape[0] - nb]), cut
+
+    def denormalize_bound_certificate(self, y, kind: int):
+        """The bound rows' part of a Farkas ray of a bounded upload, per structural column (0 where there is no bound):
+        y_upper <= 0 with A_ub^T y_ub + A_eq^T y_eq + y_upper + z ~ 0 and b_ub.y_ub + b_eq.y_eq + u.y_upper = 1 over the
+        bounded columns.  None for any other kind, and for a Problem without bounds."""
+        nb = self.n_bounded()
+        if kind != _capi.CERT_FARKAS or nb == 0:
+            return None
+        y = np.asarray(y)
+        out = np.zeros(self._upper.shape[0])
+        out[self._bounded] = y[y.shape[0] - nb:]
+        return out
 
 
 class ProblemBuilder:
@@ -207,6 +242,13 @@ class ProblemBuilder:
         self._c = c
         self._ub = None
         self._eq = None
+        self._upper = None
+
+    def upper(self, u) -> "ProblemBuilder":
+        """Upper bounds x_j <= u_j on the structural columns: one entry per column, +inf (np.inf) where there is none.
+        The solves then run the bounded form (lpipm_upload_bounded): the normal matrix keeps its order."""
+        self._upper = u
+        return self
 
     def ub(self, A, b) -> "ProblemBuilder":      # :93-96
         self._ub = (A, b)
@@ -236,6 +278,13 @@ class ProblemBuilder:
             raise IncompatibleInputDimensions()
         b = np.concatenate([b_ub, b_eq])                                     # :157-158
         cs = np.concatenate([c, np.zeros(m_ub)])                             # :159-160
+        if self._upper is not None:          # (f64 whatever the arrays' type: the bounded form has no f32 arm)
+            upper = _f64(self._upper)
+            if upper.shape != (n,):
+                raise IncompatibleInputDimensions()
+            if np.isnan(upper).any() or (upper == -np.inf).any():
+                raise InvalidParameter("upper: NaN or -inf")
+            return Problem(None, b, cs, 0.0, m_ub, parts=(A_ub, b_ub, A_eq, b_eq, c), upper=np.array(upper))
         if f32:     # Problem<f32>: the f32 values as given (exactly representable in the f64 working copies above)
             t = np.float32
             return Problem(None, b.astype(t), cs.astype(t), 0.0, m_ub,
@@ -443,6 +492,20 @@ class Context:
         """tall=True: the tall inequality form (lpipm_upload_ub_tall) -- a Problem with `ub` rows only, usually many more of
         them than columns; the solves then factor the n x n reduced system instead of the m x m normal matrix.  (A Problem
         that has `eq` rows as well: upload_tall_eq.)"""
+        bounded = getattr(problem, "_upper", None) is not None and problem.n_bounded() > 0
+        if tall and bounded:
+            raise ValueError("tall=True does not take upper bounds: on a tall form a bound is one more `ub` row")
+        if bounded:
+            # the bounded form (lpipm_upload_bounded): x_slack = [x; `ub` slacks; bound slacks], y = [y_ub; y_eq; y_bounds]
+            A_ub, b_ub, A_eq, b_eq, c = (_f64(a) for a in problem._parts)
+            upper = _f64(problem._upper)
+            m_ub, m_eq, n, nb = A_ub.shape[0], A_eq.shape[0], c.shape[0], problem.n_bounded()
+            rc = _capi.lib().lpipm_upload_bounded(self._h, n, m_ub, _p(A_ub) if m_ub else None, n, _p(b_ub) if m_ub else None,
+                                                  m_eq, _p(A_eq) if m_eq else None, n, _p(b_eq) if m_eq else None,
+                                                  _p(c), float(problem.c0()), _p(upper))
+            _raise_for(rc)
+            self.m, self.n, self._m_eq, self._members = m_ub + m_eq + nb, n + m_ub + nb, 0, 1
+            return self
         if tall:
             parts = getattr(problem, "_parts", None)
             if parts is None or parts[0].shape[0] == 0 or parts[2].shape[0] != 0:
@@ -979,6 +1042,29 @@ class Context:
         _raise_for(_capi.lib().lpipm_k_tall_sym_solve(self._h, _p(dinv), nrhs, _p(R1), _p(R2), _p(U), _p(V), C.byref(info)))
         return U, V, info.value
 
+    def k_bounded_normal(self, dinv_ext, m: int):
+        """M~ = A diag(D~) A^T (+ D~ of the `ub` slacks on their rows) of the bounded upload at dinv_ext, the x / z of all
+        n + nb columns: m x m, m the rows WITHOUT the bound rows, lower triangle valid."""
+        dinv_ext = _f64(dinv_ext)
+        if dinv_ext.shape != (self.n,):
+            raise IncompatibleInputDimensions()
+        M = np.empty((int(m), int(m)))
+        _raise_for(_capi.lib().lpipm_k_bounded_normal(self._h, _p(dinv_ext), _p(M)))
+        return M
+
+    def k_bounded_sym_solve(self, dinv_ext, R1, R2):
+        """The reduced sym_solve of the bounded upload at dinv_ext for 1 or 2 right-hand sides of the explicit LP: R1
+        (nrhs, n), R2 (nrhs, m), n and m the extended lengths -> U (nrhs, n), V (nrhs, m), info."""
+        dinv_ext = _f64(dinv_ext)
+        R1, R2 = np.atleast_2d(_f64(R1)), np.atleast_2d(_f64(R2))
+        nrhs = R1.shape[0]
+        if dinv_ext.shape != (self.n,) or R1.shape != (nrhs, self.n) or R2.shape != (nrhs, self.m):
+            raise IncompatibleInputDimensions()
+        U, V = np.empty((nrhs, self.n)), np.empty((nrhs, self.m))
+        info = C.c_int32(0)
+        _raise_for(_capi.lib().lpipm_k_bounded_sym_solve(self._h, _p(dinv_ext), nrhs, _p(R1), _p(R2), _p(U), _p(V), C.byref(info)))
+        return U, V, info.value
+
     def k_potrf(self, M, repeats=1):
         L = _square(M).copy()
         info, ms = C.c_int32(0), C.c_double(0)
@@ -1205,6 +1291,8 @@ class InteriorPoint(Solver):
             err.certificate = dict(kind=d["kind"], y_ub=y_ub, y_eq=y_eq, z=cut if d["kind"] == _capi.CERT_FARKAS else None,
                                    x=cut if d["kind"] == _capi.CERT_RAY else None, scale=d["scale"], residual=d["residual"],
                                    tau=d["tau"], kappa=d["kappa"])
+            if problem.n_bounded():
+                err.certificate["y_upper"] = problem.denormalize_bound_certificate(d["y"], d["kind"])
             raise err
         _raise_for(rc)
         res = OptimizeResult(problem.denormalize_x_into(x_slack), fun, it)   # mod.rs:165-167
@@ -1215,6 +1303,7 @@ class InteriorPoint(Solver):
             d = ctx.duals()
             res.y_ub, res.y_eq, res.reduced_costs = problem.denormalize_duals(d["y"], d["z"])
             res.dual_fun = d["dual_fun"]
+            res.upper = problem.denormalize_bound_duals(d["z"])
         return res
 
     def solve_with_duals(self, problem: Problem) -> OptimizeResult:

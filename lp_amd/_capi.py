@@ -76,6 +76,7 @@ SYMBOLS = {
     "lpipm_upload_ub_eq": (C.c_int, [_vp, _u64, _u64, _dp, _u64, _dp, _u64, _dp, _u64, _dp, _dp, C.c_double]),
     "lpipm_upload_ub_tall": (C.c_int, [_vp, _u64, _u64, _dp, _u64, _dp, _dp, C.c_double]),
     "lpipm_upload_ub_eq_tall": (C.c_int, [_vp, _u64, _u64, _dp, _u64, _dp, _u64, _dp, _u64, _dp, _dp, C.c_double]),
+    "lpipm_upload_bounded": (C.c_int, [_vp, _u64, _u64, _dp, _u64, _dp, _u64, _dp, _u64, _dp, _dp, C.c_double, _dp]),
     "lpipm_update_vectors": (C.c_int, [_vp, _dp, _dp]),
     "lpipm_update_lockstep_vectors": (C.c_int, [_vp, _u64, _dpp, _dpp, _dp]),
     "lpipm_update_lockstep_vectors_device": (C.c_int, [_vp, _u64, _vp, _u64, _vp, _u64, _dp]),
@@ -122,6 +123,8 @@ SYMBOLS = {
     "lpipm_k_tall_normal": (C.c_int, [_vp, _dp, _dp]),
     "lpipm_k_tall_schur": (C.c_int, [_vp, _dp, _dp]),
     "lpipm_k_tall_sym_solve": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
+    "lpipm_k_bounded_normal": (C.c_int, [_vp, _dp, _dp]),
+    "lpipm_k_bounded_sym_solve": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
     "lpipm_k_potrf": (C.c_int, [_vp, _u64, _dp, C.POINTER(C.c_int32), C.c_int, _dp]),
     "lpipm_k_factor_inverses": (C.c_int, [_vp, _u64, _dp, _dp, C.POINTER(C.c_int32)]),
     "lpipm_k_potrf_lockstep": (C.c_int, [_vp, _u64, C.c_int, _dp, C.POINTER(C.c_int32)]),

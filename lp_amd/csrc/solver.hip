@@ -70,6 +70,9 @@ struct StreamRes {
 struct Geometry {
     int mp = 0, np = 0, npa = 0, nxp = 0, mk = 0, B = 0, nsplit = 0, nblk = 0;
     int mep = 0;                 // tall_eq only: the `eq` rows padded to 128, the order of S (mk is then that of the `ub` rows alone)
+    int mpv = 0, npv = 0;        // the paddings of the row and column VECTORS: mp and np, but on the bounded form those of m + nb and n + nb
+    int nbp = 0;                 // bounded form only: the bounded columns padded to 256 (what the index lists and ratio vectors are sized by)
+    bool box = false;
     bool shared = false, keep = false, tall = false, tall_eq = false;
     int coupled = 0;             // the factor plans lay out the coupled sweep (coupled_for)
     bool operator==(const Geometry&) const = default;
@@ -147,6 +150,15 @@ struct Problem {
     bool tall_eq = false;
     int me = 0;
     double *Zt = nullptr, *H = nullptr, *ZtPart = nullptr, *ones_k = nullptr;
+    // The bounded form (lpipm_upload_bounded; kernels_box.hip): nb of the structural columns have an upper bound.  m and n are
+    // then those of the explicit LP, ma + nb and na + nb, and so are the lengths and paddings in `va`; the image, the passes
+    // over it and the working system stay those of the ma x na slack form (mp, np, npa, nsplit).  solW, solR: what the pass
+    // A.W reads and what the solve works in -- va.W and va.R on every other form, bx.Wb and bx.Rs here.
+    bool box = false;
+    int nb = 0;
+    uint64_t ma = 0, na = 0;     // rows and columns of the resident slack form (== m, n unless box)
+    BoxArgs bx{};
+    double *solW = nullptr, *solR = nullptr;
     bool from_parts = false;     // uploaded as ub / eq blocks (lpipm_upload_ub_eq): b and c are not in the caller's slack form
     bool owned_tall = false;     // lpipm_upload_lockstep_ub_tall: a tall batch (of any count) whose members own X_i, Xt_i and K
     // Equilibration (lpipm_set_scaling): the exponents and the maxima slabs, in an allocation of their own that exists only
@@ -558,6 +570,13 @@ struct Upload {
     bool hint_verified = false;          // the caller has checked the hint on these very matrices (batch_impl): it is not repeated
     bool keep_ok = true;                 // false: solved once (lpipm_solve_batch) or never through the kept factor (column split)
     bool colsplit = false;               // lpipm_upload_nsplit: this rank's columns of a column-split LP
+    // lpipm_upload_bounded: parts with nb > 0 bounded structural columns.  m and n stay those of the slack form without the
+    // bound rows; bidx (nb, ascending), binv (n entries) and ub (the nb finite bounds) are the caller's host arrays.
+    bool box = false;
+    uint64_t nb = 0;
+    const int *bidx = nullptr, *binv = nullptr;
+    const double* ub = nullptr;
+    bool upper_bad = false;              // an upper[j] that is NaN or -inf: refused behind the shape
     // lpipm_upload_device: A, b and c are in DEVICE memory, laid out as this descriptor says.  The request is otherwise the
     // equivalent host entry's; its pointers above stand for "given" / "null" only (check_upload) and are never read through.
     const lpipm_device_problem* dev = nullptr;
@@ -587,6 +606,8 @@ static int check_upload(const lpipm_ctx* c, const Upload& u) {
         if (!c) return LPIPM_ERR_BAD_ARGUMENT;
         if (u.tall_eq && q.m_ub == 0) return LPIPM_ERR_UNSUPPORTED;     // no `ub` row: not a tall LP (lpipm_upload_ub_eq is its entry)
         if (u.tall && (c->world > 1 || c->refine > 0)) return LPIPM_ERR_UNSUPPORTED;   // a column-split context; the refined solves
+        if (u.upper_bad) return LPIPM_ERR_BAD_ARGUMENT;
+        if (u.box && (c->world > 1 || c->refine > 0)) return LPIPM_ERR_UNSUPPORTED;    // likewise
         for (uint64_t i = 0; i < u.count; ++i)
             if (!u.c[i] || (u.b && !u.b[i]) || (u.owned && !u.A[i])) return LPIPM_ERR_BAD_ARGUMENT;
     }
@@ -599,10 +620,14 @@ static Geometry geometry_of(const Upload& u, uint64_t n_slack, bool first_cache,
     if (u.tall) { g.nxp = (int)round_up(g.npa, NB); g.mk = (int)round_up(u.m, BK); }   // the order of K, the contraction of its build
     if (u.tall_eq) { g.tall_eq = true; g.mk = (int)round_up(u.parts->m_ub, BK); g.mep = (int)round_up(u.me, NB); }
     g.B = (int)u.count; g.nsplit = g.mp / GEMVT_ROWS;
-    g.nblk = ((g.mp > g.np ? g.mp : g.np) + 255) / 256;      // (of the larger of m and n: 256 is a multiple of both paddings)
+    g.mpv = g.mp; g.npv = g.np;
+    if (u.box) {     // the system's order, R, Y and the slab count follow m; the row and column vectors follow m + nb and n + nb
+        g.box = true; g.mpv = (int)round_up(u.m + u.nb, NB); g.npv = (int)round_up(u.n + u.nb, BK); g.nbp = (int)round_up(u.nb, BK);
+    }
+    g.nblk = ((g.mpv > g.npv ? g.mpv : g.npv) + 255) / 256;  // (of the larger of m and n: 256 is a multiple of both paddings)
     if (g.nblk > RED_STRIDE) g.nblk = RED_STRIDE;
     g.shared = u.shared; g.tall = u.tall;
-    g.keep = u.keep_ok && first_cache && refine <= 0 && !u.tall;   // (tall: the first factor is not kept)
+    g.keep = u.keep_ok && first_cache && refine <= 0 && !u.tall && !u.box;   // (tall, bounded: the first factor is not kept)
     g.coupled = coupled_for(g.mp, u.count == 1 && !u.shared && !u.tall && !u.colsplit);
     return g;
 }
@@ -613,8 +638,10 @@ static void set_geometry(Problem& p, const Geometry& g) {
     p.tv = TallArgs{};
     if (g.tall) { p.tv.npa = g.npa; p.tv.nxp = g.nxp; p.tv.mk = g.mk; }     // (tv.nx: the padded geometry may be shared by several nx)
     p.tall_eq = g.tall_eq; p.tv.mep = g.mep;                                 // (tv.ms, tv.me: likewise)
+    p.box = g.box; p.bx = BoxArgs{};
+    if (g.box) { p.bx.nps = g.np; p.bx.mps = g.mp; }                         // (bx.nb, na, ma: likewise)
     VecArgs& v = p.va;
-    v.np = g.np; v.mp = g.mp; v.nblk = g.nblk; v.nsplit = g.nsplit; v.bcount = g.B; v.bfirst = 0; v.refine_below = refine_below();
+    v.np = g.npv; v.mp = g.mpv; v.nblk = g.nblk; v.nsplit = g.nsplit; v.bcount = g.B; v.bfirst = 0; v.refine_below = refine_below();
 }
 // The plan of the launch that builds a system of `order` rows by a contraction over `contraction` columns, for each of B
 // members.  The dense M = A.D.A^T: the batch's plan.  single_bits -- a tall system, K from Xt (nxp rows over the mk padded rows
@@ -633,7 +660,8 @@ static void bind_status_pinned(lpipm_ctx* c, bool allow);
 // The vectors and status words of one LP, dense or tall.
 static void layout_vectors(Problem& p, Arena& ar) {
     VecArgs& v = p.va;
-    const size_t mp = (size_t)p.mp, np = (size_t)p.np;
+    const size_t mp = (size_t)v.mp, np = (size_t)v.np;       // the vectors' paddings (bounded form: of m + nb, n + nb) ...
+    const size_t mps = (size_t)p.mp, nps = (size_t)p.np;     // ... and those of the system and the passes over the image
     v.b = ar.take<double>(mp); v.c = ar.take<double>(np);
     v.x = ar.take<double>(np); v.y = ar.take<double>(mp); v.z = ar.take<double>(np);
     v.dinv = ar.take<double>(np); v.xs = ar.take<double>(np); v.r1 = ar.take<double>(np); v.rD = ar.take<double>(np);
@@ -643,12 +671,21 @@ static void layout_vectors(Problem& p, Arena& ar) {
     // chunk slabs of A.x: sized by the count the launches use (the STORED columns npa -- gemv_dual_chunks is not monotone:
     // 256-column chunks below 4096 columns, 1024-column chunks from there on, so np's count can be the smaller one)
     // (tall: those of the npa stored columns)
-    const int ch_a = gemv_dual_chunks(p.npa), ch_n = gemv_dual_chunks((int)np);
-    v.Ax = ar.take<double>(mp * (size_t)(p.tall || ch_a > ch_n ? ch_a : ch_n));
+    const int ch_a = gemv_dual_chunks(p.npa), ch_n = gemv_dual_chunks((int)nps);
+    v.Ax = ar.take<double>(mps * (size_t)(p.tall || ch_a > ch_n ? ch_a : ch_n));
     v.W = ar.take<double>(2 * np); v.R = ar.take<double>(2 * mp);
-    p.Y = ar.take<double>(2 * (p.tall ? (size_t)p.tv.nxp : mp));
-    p.ATpart = ar.take<double>((size_t)p.nsplit * 2 * (p.tall ? (size_t)p.npa : np));   // (tall: the slabs of A^T.v are npa wide)
+    p.Y = ar.take<double>(2 * (p.tall ? (size_t)p.tv.nxp : mps));
+    p.ATpart = ar.take<double>((size_t)p.nsplit * 2 * (p.tall ? (size_t)p.npa : nps));   // (tall: the slabs of A^T.v are npa wide)
     v.ATpart = p.ATpart;
+    p.solW = v.W; p.solR = v.R;
+    if (p.box) {     // the index lists, the three kept ratio vectors, W and the solve's right-hand sides
+        BoxArgs& bx = p.bx;
+        const size_t nbp = (size_t)p.geo.nbp;
+        bx.bidx = ar.take<int>(nbp); bx.binv = ar.take<int>(nps);
+        bx.Dt = ar.take<double>(nps); bx.Rx = ar.take<double>(nbp); bx.Rw = ar.take<double>(nbp);
+        bx.Wb = ar.take<double>(2 * nps); bx.Rs = ar.take<double>(2 * mps);
+        p.solW = bx.Wb; p.solR = bx.Rs;
+    }
     v.S = ar.take<double>(64); v.red = ar.take<double>((size_t)RED_SLOTS * RED_STRIDE);
     v.status = ar.take<StatusRec>(1); v.potrf_info = ar.take<int32_t>(1);
     v.flags = ar.take<int>(1); v.done = ar.take<int>(1); v.skip_refine = ar.take<int>(1);
@@ -699,7 +736,7 @@ static int layout_first_factor(Problem& p, FactorPlan* plans, Arena& ar, bool bu
 static int layout_problem(Problem& p, FactorPlan* plans, int refine, Arena& ar, bool build, hipStream_t st) {
     TallArgs& t = p.tv;
     NormalSystem &work = p.sys[SYS_WORK], &schur = p.sys[SYS_SCHUR];
-    const size_t mp = (size_t)p.mp, np = (size_t)p.np, nxp = (size_t)t.nxp;
+    const size_t mp = (size_t)p.mp, np = (size_t)p.va.np, nxp = (size_t)t.nxp;       // (np: of xout, a column vector)
     p.A = p.shared_a ? nullptr : ar.take<double>(mp * p.npa);
     p.Xt = p.shared_a || !p.tall ? nullptr : ar.take<double>(nxp * (size_t)t.mk);
     layout_vectors(p, ar);
@@ -784,7 +821,9 @@ static void bind_systems(Problem& p) {
     // M = A.D.A^T + diag(D_slack) (newton_equations.rs:54-57).  Tall: K = X^T.diag(W_s).X + diag(E_x), Xt as its A, a contraction
     // over the mk padded rows of X (a batch: the one Xt or every member's own, and every member's own W_s), ones beyond nx
     if (p.tall) bind(p.sys[SYS_WORK], p.Xt, t.mk, t.Ws, t.nx, p.shared_a, t.nx, 0, t.Ex);
-    else bind(p.sys[SYS_WORK], p.A, p.npa, p.va.dinv, (int)p.m, p.shared_a, p.ns, p.nx, p.va.dinv);
+    // Bounded: M~ = A.diag(D~).A^T + diag(D~_slack): the dense build with D~ for dinv
+    else if (p.box) bind(p.sys[SYS_WORK], p.A, p.npa, p.bx.Dt, (int)p.ma, false, p.ns, p.nx, p.bx.Dt);
+    else bind(p.sys[SYS_WORK], p.A, p.npa, p.va.dinv, (int)p.ma, p.shared_a, p.ns, p.nx, p.va.dinv);
     // S = Zt.Zt^T: A = Zt, dinv = ones (every member's own of both), the diagonal padded with ones from me, nothing added
     if (p.tall_eq) bind(p.sys[SYS_SCHUR], p.Zt, t.nxp, p.ones_k, t.me, false, 0, 0, nullptr);
 }
@@ -841,6 +880,11 @@ static int copy_in(lpipm_ctx* c, const Upload& u, const double* c0v) {
         if (u.b) LP_HIP(vec((const char*)p.va.b + off, u.b[i], u.m));
         LP_HIP(vec((const char*)p.va.c + off, u.c[i], nc));
         LP_HIP(vec((const char*)(p.va.S + S_C0) + off, &c0v[i], 1));
+    }
+    if (u.box) {     // b_ext = [b; u_B]; c_ext = [c; 0]: the arena is zero; the index lists
+        LP_HIP(vec(p.va.b + u.m, u.ub, u.nb));
+        LP_HIP(hipMemcpyAsync((void*)p.bx.bidx, u.bidx, u.nb * sizeof(int), hipMemcpyHostToDevice, st));
+        LP_HIP(hipMemcpyAsync((void*)p.bx.binv, u.binv, u.n * sizeof(int), hipMemcpyHostToDevice, st));
     }
     return LPIPM_OK;
 }
@@ -963,15 +1007,17 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
     }
     p.has_problem = false;     // until this upload is complete
     const int count = g.B;
-    LP_TRY(scale_setup(c, g.mp, g.np, g.npa, u.shared ? 1 : count));
-    p.m = u.m; p.n = u.n; p.ns = (int)n_slack; p.nx = (int)nx;
+    LP_TRY(scale_setup(c, g.mpv, g.npv, g.npa, u.shared ? 1 : count));      // (exponents per row and column of the vectors' lengths)
+    p.ma = u.m; p.na = u.n; p.nb = (int)u.nb;
+    p.m = u.m + u.nb; p.n = u.n + u.nb; p.ns = (int)n_slack; p.nx = (int)nx;
+    if (u.box) { p.bx.nb = (int)u.nb; p.bx.na = (int)u.n; p.bx.ma = (int)u.m; }
     if (u.tall) p.tv.nx = (int)nx;            // (the padded geometry may be shared by several nx)
     const uint64_t m_ub = u.parts ? u.parts->m_ub : 0;
     p.me = u.tall_eq ? (int)u.me : 0;
     if (u.tall) { p.tv.ms = (int)m_ub; p.tv.me = p.me; }
     p.from_parts = u.parts.has_value(); p.owned_tall = u.owned;
     bind_systems(p);
-    p.va.n = (int)u.n; p.va.m = (int)u.m; p.va.n_total = (long long)u.n; p.va.gs = nullptr; c->colsplit = false;   // lpipm_upload_nsplit overrides
+    p.va.n = (int)p.n; p.va.m = (int)p.m; p.va.n_total = (long long)p.n; p.va.gs = nullptr; c->colsplit = false;   // lpipm_upload_nsplit overrides
     // A single LP's loop ends on the host, so its kernels need not test the done word (one dependent load
     // less at the start of ~100 short kernels) -- except the head of an iteration, which is enqueued before
     // the host has seen the previous status.  In a batch every kernel tests it.
@@ -989,7 +1035,9 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
         const Batch members{count, (long long)p.bstride, nullptr, 0};
         LP_HIP(launch_equilibrate(p.sc, p.A, (int)u.m, g.mp, (int)nx, g.npa, (int)n_slack, p.scale_passes, st,
                                   u.shared ? Batch{} : members));
-        LP_HIP(launch_scale_vectors(p.sc, (double*)p.va.b, (int)u.m, (double*)p.va.c, (int)u.n, st, members));
+        // bounded: the bound rows and their slack columns take their exponents from the bounded columns' (the block stays 1)
+        if (u.box) { box_exponents(p.bx, p.sc.kr, p.sc.kc, st); LP_HIP(hipGetLastError()); }
+        LP_HIP(launch_scale_vectors(p.sc, (double*)p.va.b, (int)p.m, (double*)p.va.c, (int)p.n, st, members));
     }
     // tall: the resident transpose, from the X the solves see (behind the equilibration: both copies carry its exponents)
     //       (every member's own, in one launch, when the members own their matrices)
@@ -1015,6 +1063,31 @@ extern "C" int lpipm_upload_ub_eq(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const
                                   const double* b_eq, const double* cc, double c0) {
     return upload_impl(c, Upload{.m = m_ub + m_eq, .n = n + m_ub, .n_slack = m_ub,
                                  .parts = UploadParts{m_ub, A_ub, lda_ub, b_ub, A_eq, lda_eq, b_eq}, .c = &cc, .c0 = &c0});
+}
+// lpipm_upload_ub_eq's LP with upper bounds on some of its structural columns: the bounded form (kernels_box.hip).  Without a
+// finite bound it is lpipm_upload_ub_eq's request itself.  The index lists and the packed bounds live until upload_impl returns.
+extern "C" int lpipm_upload_bounded(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub,
+                                    const double* b_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq,
+                                    const double* b_eq, const double* cc, double c0, const double* upper) {
+    std::vector<int> bidx, binv;
+    std::vector<double> ub;
+    bool bad = false;
+    if (upper && n <= (1u << 24)) {
+        binv.assign((size_t)(n + m_ub), -1);
+        for (uint64_t j = 0; j < n; ++j) {
+            const double uj = upper[j];
+            if (uj != uj || (std::isinf(uj) && uj < 0.0)) { bad = true; break; }
+            if (std::isinf(uj)) continue;
+            binv[(size_t)j] = (int)bidx.size();
+            bidx.push_back((int)j);
+            ub.push_back(uj);
+        }
+    }
+    if (!bad && bidx.empty()) return lpipm_upload_ub_eq(c, n, m_ub, A_ub, lda_ub, b_ub, m_eq, A_eq, lda_eq, b_eq, cc, c0);
+    Upload u{.m = m_ub + m_eq, .n = n + m_ub, .n_slack = m_ub,
+             .parts = UploadParts{m_ub, A_ub, lda_ub, b_ub, A_eq, lda_eq, b_eq}, .c = &cc, .c0 = &c0, .keep_ok = false};
+    u.box = !bad; u.nb = bad ? 0 : bidx.size(); u.bidx = bidx.data(); u.binv = binv.data(); u.ub = ub.data(); u.upper_bad = bad;
+    return upload_impl(c, u);
 }
 // The request of one tall LP (cc, c0: one entry each).
 static Upload tall_request(uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub, const double* b_ub, const double* const* cc,
@@ -1142,7 +1215,7 @@ static hipError_t ctx_gemv_n(lpipm_ctx* c, int nrhs, const double* W, const doub
                              const Batch& bt, hipStream_t on = nullptr) {
     hipStream_t st = on ? on : c->rs.st;
     ++c->gemv_passes;
-    hipError_t e = launch_gemv_n(c->p.A, c->p.npa, (int)c->p.m, c->p.npa, nrhs, W, c->p.np, add0, add1, Y, c->p.mp, st, 1.0, bt, c->p.shared_a);
+    hipError_t e = launch_gemv_n(c->p.A, c->p.npa, (int)c->p.ma, c->p.npa, nrhs, W, c->p.np, add0, add1, Y, c->p.mp, st, 1.0, bt, c->p.shared_a);
     if (e != hipSuccess) return e;
     return launch_slack_n(c->p.ns, c->p.nx, nrhs, W, c->p.np, Y, c->p.mp, st, bt);
 }
@@ -1281,11 +1354,19 @@ static int tall_eq_reset(lpipm_ctx* c) {
     return LPIPM_OK;
 }
 
+// Bounded form, likewise: the solves run in place over all mps entries of both rows of Rs, of which the pass A.W writes the
+// first ma only (k_blind_start clears the padding of va.R, which on this form the solves do not work in).
+static int box_reset(lpipm_ctx* c) {
+    if (!c->p.box) return LPIPM_OK;
+    LP_HIP(member_bytes(c, c->p.bx.Rs, nullptr, 2 * (size_t)c->p.bx.mps * sizeof(double)));
+    return LPIPM_OK;
+}
+
 // R = A.W + r2 for the nrhs right-hand sides whose r2 are add0, add1 (newton_equations.rs:220), on the solver's stream or `on`.
 // Column split: the addends enter once, after the cross-rank sum of the ranks' products.
 static int pass_aw(lpipm_ctx* c, int nrhs, const double* add0, const double* add1, hipStream_t on = nullptr) {
     VecArgs& v = c->p.va;
-    if (!c->colsplit) { LP_HIP(ctx_gemv_n(c, nrhs, v.W, add0, add1, v.R, c->p.bt, on)); return LPIPM_OK; }
+    if (!c->colsplit) { LP_HIP(ctx_gemv_n(c, nrhs, c->p.solW, add0, add1, c->p.solR, c->p.bt, on)); return LPIPM_OK; }
     LP_HIP(ctx_gemv_n(c, nrhs, v.W, nullptr, nullptr, v.R, c->p.bt, on));
     LP_TRY(ctx_allreduce(c, v.R, (uint64_t)nrhs * c->p.mp, 0, on));
     vec_add_rows((int)c->p.m, nrhs, v.R, c->p.mp, add0, add1, on ? on : c->rs.st);
@@ -1312,7 +1393,7 @@ static int chol_solve_refined(lpipm_ctx* c, const FactorPlan& f, int nrhs, doubl
 // them, unless the first ran beside the chain).
 static int normal_solve(lpipm_ctx* c, const Iter& it, const lpipm_opts* o, int nrhs, const SolveSteps& steps = SolveSteps{}, hipStream_t on = nullptr) {
     hipStream_t st = on ? on : c->rs.st;
-    double* R = c->p.va.R;
+    double* R = c->p.solR;
     const NormalSystem& sys = cur_sys(c, it);        // (the QR arms and a refining context keep no first factor: the working system)
     if (o->solver_type != LPIPM_SOLVER_CHOLESKY) LP_HIP(launch_qr_solve(sys.M, sys.n, sys.n, c->p.tau, nrhs, R, c->p.va.potrf_info, st));   // :155-166
     else if (it.refine_now) LP_TRY(chol_solve_refined(c, *sys.factor, nrhs, R, st));
@@ -1336,8 +1417,9 @@ static int enqueue_residuals(lpipm_ctx* c, int is_init, int ip_next, double tol)
     prof_mark(c, T_GEMV);
     // small LPs: the launch goes on with the next iteration's Dinv / r_hat set-up (enqueue_head then skips it)
     v.status_seq = (int)(++c->rs.seq_counter & 0x7fffffffu);
-    if (c->p.tall) {                            // kernel by kernel: slabs npa wide, A^T.y of a slack column is y
-        tall_residuals(v, c->p.tv, c->rs.st);
+    if (c->p.tall || c->p.box) {                // kernel by kernel: slabs npa wide, A^T.y of a slack column is y (bounded: the bound block)
+        if (c->p.box) box_residuals(v, c->p.bx, c->rs.st);
+        else tall_residuals(v, c->p.tv, c->rs.st);
         vec_scalar_indicators(v, is_init, ip_next, tol, c->rs.st);
         c->pred_done = false;
         LP_HIP(hipGetLastError());
@@ -1451,6 +1533,8 @@ static int enqueue_head(lpipm_ctx* c, const Iter& it) {
         prof_mark(c, T_ADAT, true);
         return LPIPM_OK;
     }
+    // bounded: D~ and the ratios from the x / z of k_pred_setup, W of the predictor's two right-hand sides; then M~ with D~
+    if (c->p.box) box_setup(vh, c->p.bx, true, 2, vh.c, vh.b, vh.r1, vh.rP, st);
     prof_mark(c, T_VEC, true);
     if (it.skip_factor) return LPIPM_OK;          // iteration 1 on a kept factor: its M is already there, factored
     const bool split = c->colsplit && c->world > 1;
@@ -1503,7 +1587,7 @@ static int factor_system(lpipm_ctx* c, const Iter& it, const lpipm_opts* o, Pred
         const NormalSystem& sys = cur_sys(c, it);     // (the QR arms keep no first factor: the working system)
         if (o->solver_type == LPIPM_SOLVER_CHOLESKY) {
             PotrfBeside beside{PredictorBeside::at, &pb};
-            const bool may_beside = !c->colsplit && bt.count == 1 && c->refine <= 0;
+            const bool may_beside = !c->colsplit && bt.count == 1 && c->refine <= 0 && !c->p.box;
             const hipError_t e = launch_potrf(*sys.factor, v.potrf_info, st, bt, lookahead(c), false, may_beside ? &beside : nullptr);
             LP_TRY(pb.rc);
             LP_HIP(e);
@@ -1543,7 +1627,7 @@ static int sym_solve(lpipm_ctx* c, const Iter& it, const lpipm_opts* o, const Sy
     prof_mark(c, T_GEMV);
     LP_TRY(normal_solve(c, it, o, nrhs, SolveSteps{beside_done < 0 ? 0 : beside_done, -1, true}));   // :221
     prof_mark(c, T_TRSV);
-    LP_HIP(ctx_gemv_t(c, nrhs, v.R, bt));                                             // :223
+    LP_HIP(ctx_gemv_t(c, nrhs, c->p.solR, bt));                                       // :223
     prof_mark(c, T_GEMV);
     return LPIPM_OK;
 }
@@ -1559,14 +1643,16 @@ static int epilogue(lpipm_ctx* c, Phase phase, int ip, double alpha0) {
     const bool corr = phase == Phase::Corrector;
     XRank xr_{xrank_fn, c};
     const XRank* xr = c->colsplit ? &xr_ : nullptr;
-    if (!c->p.tall && !xr && vec_fused(v)) {
+    if (!c->p.tall && !c->p.box && !xr && vec_fused(v)) {
         if (corr) vec_fused_corrector(v, ip, alpha0, st); else vec_fused_predictor(v, ip, st);
     } else {
         if (c->p.tall) { if (corr) tall_uv_corr(v, t, v.r1, st); else tall_pq_uv(v, t, v.c, v.r1, st); }
+        else if (c->p.box) { if (corr) box_uv_corr(v, c->p.bx, v.r1, v.rP2, st); else box_pq_uv(v, c->p.bx, v.c, v.b, v.r1, v.rP, st); }
         else LP_TRY(corr ? vec_uv_corr(v, st, xr) : vec_pq_uv(v, st, xr));
         LP_TRY(vec_delta(v, corr ? 1 : 0, ip, corr ? alpha0 : 1.0, st, xr));
         if (corr) vec_step(v, ip, alpha0, st); else vec_corr_setup(v, ip, st);
         if (c->p.tall && !corr) tall_setup(v, t, false, 1, v.r1, v.rP2, nullptr, nullptr, st);
+        if (c->p.box && !corr) box_setup(v, c->p.bx, false, 1, v.r1, v.rP2, nullptr, nullptr, st);
     }
     prof_mark(c, T_VEC);
     return LPIPM_OK;
@@ -1782,7 +1868,7 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, Members members, con
         if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
         if (c->p.B != 1) return LPIPM_ERR_BAD_ARGUMENT;   // a lockstep batch is solved by solve_lockstep
         if (o->solver_type != LPIPM_SOLVER_CHOLESKY && c->p.mp > 16384) return LPIPM_ERR_UNSUPPORTED;  // QR solve keeps the rhs in LDS
-        if (o->solver_type != LPIPM_SOLVER_CHOLESKY && c->p.tall) return LPIPM_ERR_UNSUPPORTED;        // the reduced form: Cholesky arm only
+        if (o->solver_type != LPIPM_SOLVER_CHOLESKY && (c->p.tall || c->p.box)) return LPIPM_ERR_UNSUPPORTED;   // the reduced forms: Cholesky arm only
     }
     LP_HIP(hipSetDevice(c->device));
     LP_TRY(ensure_shared_factor(c, o));                   // (a view finds it built: solve_lockstep)
@@ -1797,6 +1883,7 @@ static int solve_members(lpipm_ctx* c, const lpipm_opts* o, Members members, con
 
     vec_blind_start(v, st);                               // feasible_point.rs:24-31
     LP_TRY(tall_eq_reset(c));
+    LP_TRY(box_reset(c));
     prof_mark(c, T_VEC);
     LP_TRY(enqueue_residuals(c, 1, o->ip ? 1 : 0, o->tol));  // feasible_point.rs:32, mod.rs:206
     if (md.rows) LP_TRY(copy_status(c));
@@ -2523,6 +2610,12 @@ static int run_certificates(lpipm_ctx* c, size_t row0, size_t rows, bool want_y,
         const uint64_t passes = c->gemv_passes;
         LP_HIP(ctx_gemv_dual(c, v.W, v.dy, v.Ax, Batch{p.bt.count, p.bt.stride, nullptr, p.bt.first}));
         c->gemv_passes = passes;           // (lpipm_phase_times counts a solve's passes)
+        if (p.box) {     // the bound block: A_ext^T.y^ into u, A_ext.x^ into q, both whole, which the residual then reads as one slab each
+            box_products(v, p.bx, BoxProducts{v.W, v.Ax, v.ax_chunks, v.q, v.dy, p.ATpart, (long long)p.np, v.u}, st);
+            LP_HIP(hipGetLastError());
+            v.ATpart = v.u; v.nsplit = 1; d.nxs = (int)n; d.slab = v.np;
+            v.Ax = v.q; v.ax_chunks = 1;
+        }
     }
     vec_cert_residual(v, d, st);           // (without a certificate to form: its scalar launch alone has work)
     LP_HIP(hipGetLastError());
@@ -2694,6 +2787,7 @@ extern "C" int lpipm_k_adat(lpipm_ctx* c, const double* dinv, double* M_out, int
     if (!c || !dinv || !M_out) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
     if (c->p.tall) return LPIPM_ERR_UNSUPPORTED;           // a tall upload has no M (lpipm_k_tall_normal returns K)
+    if (c->p.box) return LPIPM_ERR_UNSUPPORTED;            // a bounded upload builds M~ from D~ (lpipm_k_bounded_normal returns it)
     LP_HIP(hipSetDevice(c->device));
     LP_HIP(hipMemcpyAsync(c->p.va.dinv, dinv, c->p.n * sizeof(double), hipMemcpyHostToDevice, c->rs.st));
     LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int { LP_HIP(build_system(c, c->p.sys[SYS_WORK], Batch{}, BuildOpts{.M2 = c->p.M0})); return LPIPM_OK; }));
@@ -2783,6 +2877,124 @@ extern "C" int lpipm_k_tall_sym_solve(lpipm_ctx* c, const double* dinv, int nrhs
     LP_HIP(hipMemsetAsync(v.potrf_info, 0, sizeof(int32_t), st));     // the solver expects a clean word
     LP_HIP(hipStreamSynchronize(st));
     if (info_out) *info_out = info;
+    return LPIPM_OK;
+}
+
+// What the bounded kernel entries start from: the iterate x = dinv_ext, z = 1 over all n + nb columns (so that x / z, which the
+// set-up takes from the vector k_pred_setup leaves it in, is dinv_ext), D~ and the ratios, W of the nrhs given right-hand
+// sides, M~ built and, `factor`, factored.
+static int box_entry_system(lpipm_ctx* c, const double* dinv, bool factor, int nrhs = 0, const double* r1 = nullptr,
+                            const double* r2 = nullptr, const double* r1b = nullptr, const double* r2b = nullptr) {
+    hipStream_t st = c->rs.st;
+    NormalSystem& M = c->p.sys[SYS_WORK];
+    const std::vector<double> ones((size_t)c->p.n, 1.0);
+    invalidate_duals(c);
+    vec_blind_start(c->p.va, st);                  // clears done / flags; the iterate is overwritten next
+    LP_TRY(box_reset(c));
+    LP_HIP(hipMemcpyAsync(c->p.va.x, dinv, c->p.n * sizeof(double), hipMemcpyHostToDevice, st));
+    LP_HIP(hipMemcpyAsync(c->p.va.dinv, dinv, c->p.n * sizeof(double), hipMemcpyHostToDevice, st));
+    LP_HIP(hipMemcpyAsync(c->p.va.z, ones.data(), c->p.n * sizeof(double), hipMemcpyHostToDevice, st));
+    LP_HIP(hipStreamSynchronize(st));              // `ones` goes out of scope
+    box_setup(c->p.va, c->p.bx, true, nrhs, r1, r2, r1b, r2b, st);
+    LP_HIP(build_system(c, M, Batch{}));
+    if (factor) LP_HIP(launch_potrf(*M.factor, M.info, st, Batch{}, nullptr, true, nullptr));
+    return LPIPM_OK;
+}
+extern "C" int lpipm_k_bounded_normal(lpipm_ctx* c, const double* dinv_ext, double* M_out) {
+    if (!c || !dinv_ext || !M_out) return LPIPM_ERR_BAD_ARGUMENT;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (!c->p.box) return LPIPM_ERR_UNSUPPORTED;
+    LP_HIP(hipSetDevice(c->device));
+    LP_TRY(box_entry_system(c, dinv_ext, false));
+    const size_t ma = (size_t)c->p.ma;
+    LP_HIP(rows_to_host(M_out, ma, c->p.sys[SYS_WORK].M, (size_t)c->p.mp, ma, ma, c->rs.st));
+    LP_HIP(hipStreamSynchronize(c->rs.st));
+    return LPIPM_OK;
+}
+extern "C" int lpipm_k_bounded_sym_solve(lpipm_ctx* c, const double* dinv_ext, int nrhs, const double* R1, const double* R2,
+                                         double* U_out, double* V_out, int32_t* info_out) {
+    if (!c || !dinv_ext || !R1 || !R2 || !U_out || !V_out || (nrhs != 1 && nrhs != 2)) return LPIPM_ERR_BAD_ARGUMENT;
+    if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
+    if (!c->p.box) return LPIPM_ERR_UNSUPPORTED;
+    LP_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->rs.st;
+    VecArgs& v = c->p.va;
+    const size_t n = (size_t)c->p.n, m = (size_t)c->p.m, np = (size_t)v.np, mp = (size_t)v.mp;
+    // the right-hand sides on the device, rows padded as the solver's own vectors are: R1 as [nrhs][np], R2 as [nrhs][mp]
+    DeviceTemp tmp{st};
+    double* rhs = nullptr;
+    LP_TRY(tmp.take(&rhs, 2 * (np + mp), true));
+    double* r1 = rhs;
+    double* r2 = rhs + 2 * np;
+    int32_t info = 0;
+    lpipm_opts o;
+    lpipm_default_opts(&o);
+    LP_HIP(rows_to_device(r1, np, R1, n, n, (size_t)nrhs, st));
+    LP_HIP(rows_to_device(r2, mp, R2, m, m, (size_t)nrhs, st));
+    const double* r1b = nrhs == 2 ? r1 + np : nullptr;
+    const double* r2b = nrhs == 2 ? r2 + mp : nullptr;
+    LP_TRY(box_entry_system(c, dinv_ext, true, nrhs, r1, r2, r1b, r2b));
+    LP_TRY(sym_solve(c, Iter{}, &o, SymRhs{nrhs, r1, r2, r1b, r2b}));
+    if (nrhs == 2) box_pq_uv(v, c->p.bx, r1, r2, r1b, r2b, st);
+    else           box_uv_corr(v, c->p.bx, r1, r2, st);
+    LP_HIP(hipGetLastError());
+    // nrhs == 2: (p, q) and (u, v) as the predictor leaves them; nrhs == 1: (u, v) as the corrector does
+    if (nrhs == 2) LP_HIP(hipMemcpyAsync(U_out, v.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    LP_HIP(hipMemcpyAsync(U_out + (nrhs == 2 ? n : 0), v.u, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    LP_HIP(rows_to_host(V_out, m, v.R, mp, m, (size_t)nrhs, st));
+    LP_HIP(hipMemcpyAsync(&info, v.potrf_info, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    LP_HIP(hipMemsetAsync(v.potrf_info, 0, sizeof(int32_t), st));     // the solver expects a clean word
+    LP_HIP(hipStreamSynchronize(st));
+    if (info_out) *info_out = info;
+    return LPIPM_OK;
+}
+// lpipm_k_gemv_n, lpipm_k_gemv_t and lpipm_k_gemv_dual on a bounded upload: they see A_ext at its extended lengths.  The pass
+// runs over A from the first na (ma) entries of its input, which go into the solve's own buffers (rows nps and mps apart); the
+// whole input sits in va.W / va.R, and box_products adds the bound block.  w: nrhs rows of n entries (null: no product A_ext.w),
+// v: nrhs rows of m entries (null: no A_ext^T.v); dual: both in one read of A (one right-hand side).
+static int box_k_passes(lpipm_ctx* c, int nrhs, const double* w, const double* v, bool dual, double* Aw_out, double* ATv_out,
+                        int repeats, double* ms_out) {
+    Problem& p = c->p;
+    VecArgs& va = p.va;
+    const BoxArgs& bx = p.bx;
+    hipStream_t st = c->rs.st;
+    const size_t n = (size_t)p.n, m = (size_t)p.m, na = (size_t)p.na, ma = (size_t)p.ma;
+    if (w) {
+        LP_HIP(rows_to_device(va.W, (size_t)va.np, w, n, n, (size_t)nrhs, st));
+        LP_HIP(rows_to_device(bx.Wb, (size_t)bx.nps, w, n, na, (size_t)nrhs, st));
+    }
+    if (v) {
+        LP_HIP(hipMemsetAsync(bx.Rs, 0, 2 * (size_t)bx.mps * sizeof(double), st));
+        LP_HIP(rows_to_device(va.R, (size_t)va.mp, v, m, m, (size_t)nrhs, st));
+        LP_HIP(rows_to_device(bx.Rs, (size_t)bx.mps, v, m, ma, (size_t)nrhs, st));
+    }
+    const int nch = gemv_dual_chunks(p.npa);
+    LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int {
+        if (dual) {
+            LP_HIP(ctx_gemv_dual(c, bx.Wb, bx.Rs, va.Ax, Batch{}));
+            box_products(va, bx, BoxProducts{va.W, va.Ax, nch, va.q, va.R, p.ATpart, (long long)bx.nps, va.u}, st);
+        } else if (w) {        // A.w_x into the rows of dy-sized scratch: Y, nrhs rows mps apart, then whole into rP / rP2
+            LP_HIP(ctx_gemv_n(c, nrhs, bx.Wb, nullptr, nullptr, p.Y, Batch{}));
+            for (int r = 0; r < nrhs; ++r)
+                box_products(va, bx, BoxProducts{va.W + (size_t)r * va.np, p.Y + (size_t)r * bx.mps, 1, r ? va.rP2 : va.rP}, st);
+        } else {
+            LP_HIP(ctx_gemv_t(c, nrhs, bx.Rs, Batch{}));
+            for (int r = 0; r < nrhs; ++r)
+                box_products(va, bx, BoxProducts{nullptr, nullptr, 1, nullptr, va.R + (size_t)r * va.mp, p.ATpart + (size_t)r * bx.nps,
+                                                 (long long)nrhs * bx.nps, r ? va.p : va.u}, st);
+        }
+        LP_HIP(hipGetLastError());
+        return LPIPM_OK;
+    }));
+    if (dual) {
+        LP_HIP(hipMemcpyAsync(Aw_out, va.q, m * sizeof(double), hipMemcpyDeviceToHost, st));
+        LP_HIP(hipMemcpyAsync(ATv_out, va.u, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    } else if (w) {
+        for (int r = 0; r < nrhs; ++r) LP_HIP(hipMemcpyAsync(Aw_out + (size_t)r * m, r ? va.rP2 : va.rP, m * sizeof(double), hipMemcpyDeviceToHost, st));
+    } else {
+        for (int r = 0; r < nrhs; ++r) LP_HIP(hipMemcpyAsync(ATv_out + (size_t)r * n, r ? va.p : va.u, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    LP_HIP(hipStreamSynchronize(st));
     return LPIPM_OK;
 }
 
@@ -3095,6 +3307,7 @@ extern "C" int lpipm_k_gemv_n(lpipm_ctx* c, int nrhs, const double* W, double* Y
     if (!c || !W || !Y || (nrhs != 1 && nrhs != 2)) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
     LP_HIP(hipSetDevice(c->device));
+    if (c->p.box) return box_k_passes(c, nrhs, W, nullptr, false, Y, nullptr, repeats, ms_out);
     LP_HIP(rows_to_device(c->p.va.W, (size_t)c->p.np, W, c->p.n, c->p.n, (size_t)nrhs, c->rs.st));
     LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int {
         LP_HIP(ctx_gemv_n(c, nrhs, c->p.va.W, nullptr, nullptr, c->p.va.R, Batch{}));
@@ -3109,6 +3322,7 @@ extern "C" int lpipm_k_gemv_t(lpipm_ctx* c, int nrhs, const double* V, double* U
     if (!c || !V || !U || (nrhs != 1 && nrhs != 2)) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
     LP_HIP(hipSetDevice(c->device));
+    if (c->p.box) return box_k_passes(c, nrhs, nullptr, V, false, nullptr, U, repeats, ms_out);
     LP_HIP(hipMemsetAsync(c->p.va.R, 0, (size_t)2 * c->p.mp * sizeof(double), c->rs.st));
     LP_HIP(rows_to_device(c->p.va.R, (size_t)c->p.mp, V, c->p.m, c->p.m, (size_t)nrhs, c->rs.st));
     LP_TRY(timed_repeats(c, repeats, ms_out, [&]() -> int {
@@ -3145,6 +3359,7 @@ extern "C" int lpipm_k_iteration(lpipm_ctx* c, const lpipm_opts* o, int ip, doub
     invalidate_duals(c);
     vec_blind_start(v, st);                                   // clears done / flags; the iterate is overwritten next
     LP_TRY(tall_eq_reset(c));
+    LP_TRY(box_reset(c));
     LP_HIP(hipMemcpyAsync(v.x, x, c->p.n * sizeof(double), hipMemcpyHostToDevice, st));
     LP_HIP(hipMemcpyAsync(v.y, y, c->p.m * sizeof(double), hipMemcpyHostToDevice, st));
     LP_HIP(hipMemcpyAsync(v.z, z, c->p.n * sizeof(double), hipMemcpyHostToDevice, st));
@@ -3176,6 +3391,7 @@ extern "C" int lpipm_k_gemv_dual(lpipm_ctx* c, const double* w, const double* v,
     if (!c || !w || !v || !Aw_out || !ATv_out) return LPIPM_ERR_BAD_ARGUMENT;
     if (!c->p.has_problem) return LPIPM_ERR_NO_PROBLEM;
     LP_HIP(hipSetDevice(c->device));
+    if (c->p.box) return box_k_passes(c, 1, w, v, true, Aw_out, ATv_out, repeats, ms_out);
     VecArgs& va = c->p.va;
     LP_HIP(hipMemsetAsync(va.W, 0, (size_t)c->p.np * sizeof(double), c->rs.st));
     LP_HIP(hipMemsetAsync(va.R, 0, (size_t)c->p.mp * sizeof(double), c->rs.st));

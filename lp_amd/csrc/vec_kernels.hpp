@@ -188,6 +188,50 @@ void tall_eq_singular(const VecArgs& a, const TallArgs& t, hipStream_t st);
 // path, next to zeros: the same bits).  Followed by vec_scalar_indicators.
 void tall_residuals(const VecArgs& a, const TallArgs& t, hipStream_t st);
 
+// ---------------------------------------------------------------- bounded form (kernels_box.hip)
+// An LP of lpipm_upload_ub_eq with upper bounds on nb of its structural columns (lpipm_upload_bounded).  What is solved is the
+// explicit LP A_ext = [[A, 0], [E_B, I]], x_ext = [x; w], y_ext = [y; y_b]: the VecArgs carry the extended lengths (n = na + nb,
+// m = ma + nb, np and mp their paddings), the resident image and the normal system stay those of A (ma rows, na columns with
+// its slack block).  The bound block is eliminated in closed form: M~ = A.diag(D~).A^T, D~_j = 1 / (z_j / x_j + v_j / w_j) on
+// a bounded column and x_j / z_j elsewhere, and sym_solve(r1, r2), r1 = [r1_x; r1_w], r2 = [r2_1; r2_2], reads
+//   W_j  = D~_j (r1_x,j - r1_w,j) - (dx_j / s_j) r2_2,j   (j bounded, s = dx + dw;  D~_j r1_x,j elsewhere)     k_box_setup
+//   v_1  = M~^-1 (r2_1 + A.W);   t = A^T.v_1                                                        the dense arm's passes
+//   g_j  = D~_j (t_j - r1_x,j + r1_w,j);  u_x,j = g_j + (dx_j / s_j) r2_2,j;  u_w,j = -g_j + (dw_j / s_j) r2_2,j
+//   v_2,j = r1_w,j + u_w,j / dw_j                                                            k_box_pq_uv / k_box_uv_corr
+// Every pointer is LP 0's, as in VecArgs (bbatch, kernels_box.hip, moves them to the member).
+struct BoxArgs {
+    int nb, na, ma;          // bounded columns; columns and rows of A's slack form (the VecArgs' n - nb and m - nb)
+    int nps, mps;            // na padded to 256: width of the A^T.v slabs and of a row of Wb; ma padded to 128: order of M~, row of Rs
+    const int* bidx;         // [nb]     the bounded columns, ascending
+    const int* binv;         // [na]     k where bidx[k] == j, -1 on a column without a bound
+    double* Dt;              // [nps]    D~: the `dinv` of the A.D.A^T launch that builds M~
+    double* Rx;              // [nb]     dx / s
+    double* Rw;              // [nb]     dw / s
+    double* Wb;              // [2][nps] W: the input of the pass A.W
+    double* Rs;              // [2][mps] r2_1 + A.W, then v_1: in/out of the Cholesky solve, the V of the pass A^T.v
+};
+// D~, dx / s and dw / s from the iterate (with_scales: a.dinv holds x / z over all n columns, from k_pred_setup), and W for
+// nrhs (0|1|2) right-hand sides (r1a, r2a), (r1b, r2b): r1 n-sized, r2 m-sized
+void box_setup(const VecArgs& a, const BoxArgs& bx, bool with_scales, int nrhs, const double* r1a, const double* r2a,
+               const double* r1b, const double* r2b, hipStream_t st);
+// Bounded counterparts of vec_pq_uv / vec_uv_corr (single GPU: d_tau is folded into k_delta): p, q, u, v where the dense
+// kernels leave them (q into R[0], v into R[1]; corrector: v into R[0]), the same dots in the same slots, FLAG_NAN_PQ.
+void box_pq_uv(const VecArgs& a, const BoxArgs& bx, const double* r1a, const double* r2a, const double* r1b, const double* r2b,
+               hipStream_t st);
+void box_uv_corr(const VecArgs& a, const BoxArgs& bx, const double* r1a, const double* r2a, hipStream_t st);
+// k_residuals with the bound rows and columns: A.x chunk slabs mps apart, A^T.y slabs nps wide.  Followed by vec_scalar_indicators.
+void box_residuals(const VecArgs& a, const BoxArgs& bx, hipStream_t st);
+// The structural bound block of the passes over A (the kernel entries, the certificates): Aw (m entries) = A_ext.w from the
+// ax_chunks chunk slabs of A.w_x (mps apart) and w itself (n entries); ATv (n entries) = A_ext^T.v from the row-split slabs
+// of A^T.v_1 (slab_stride doubles apart) and v itself (m entries).  A null output skips its half.  LP 0's pointers.
+struct BoxProducts {
+    const double* w = nullptr; const double* AxPart = nullptr; int ax_chunks = 1; double* Aw = nullptr;
+    const double* v = nullptr; const double* ATpart = nullptr; long long slab_stride = 0; double* ATv = nullptr;
+};
+void box_products(const VecArgs& a, const BoxArgs& bx, const BoxProducts& q, hipStream_t st);
+// kr of the bound rows and kc of the bound slack columns from kc of the bounded columns (one exponent set: a single LP)
+void box_exponents(const BoxArgs& bx, int32_t* kr, int32_t* kc, hipStream_t st);
+
 // ---------------------------------------------------------------- device sources (kernels_pack.hip)
 // lpipm_upload_device: the caller's strided device arrays (double or float) into the zeroed resident image.  Strides are in
 // ELEMENTS of the source type; `ms` is the member stride of the source (0: one source for the launch), dstride the BYTES
