@@ -21,6 +21,17 @@ __device__ __forceinline__ int lds_swz(int row) { return ((row + 4) >> 3) & 1; }
 __device__ __forceinline__ int lds_wcol(int row, int scol) { return scol ^ (lds_swz(row) << 1); }     // scol = 2 * k-block
 __device__ __forceinline__ int lds_rq(int fr, int fq) { return (fq ^ lds_swz(fr)) << 1; }
 
+// The panel solve's products of one k-tile for one 16x16 block, from the k-tile's LDS images (rows row0 .. row0 + 15 of either
+// operand): per round one fragment of each side, then two MFMAs.  An element's sum is this sequence over the k-tiles in
+// ascending order and nothing else: gemm_nt_rows32_k128_kernel and the panel workgroups of potrf_diag_kernel both run it.
+__device__ __forceinline__ d2 ktile_frag(const double (*img)[LDS_STRIDE], int row0, int round, int fr, int fq) {
+    return *(const d2*)&img[row0 + fr][round * 8 + lds_rq(fr, fq)];
+}
+__device__ __forceinline__ void ktile_mfma2(d4& acc, const d2& a, const d2& b) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t], b[t], acc, 0, 0, 0);
+}
+
 template <int MTM, int MTN>
 __device__ __forceinline__ void acc_clear(d4 (&acc)[MTM][MTN]) {
 #pragma unroll

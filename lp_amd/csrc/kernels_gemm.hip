@@ -248,14 +248,11 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_rows32_k128_kernel(const GemmK
         if (kt <= cblk[1]) {                                   // wave-uniform; cblk[0] <= cblk[1]
 #pragma unroll
             for (int round = 0; round < 2; ++round) {
-                const d2 a = *(const d2*)&ldsA[buf][wr * 16 + fr][round * 8 + lds_rq(fr, fq)];
+                const d2 a = ktile_frag(ldsA[buf], wr * 16, round, fr, fq);
 #pragma unroll
                 for (int nj = 0; nj < 2; ++nj) {
                     if (kt > cblk[nj]) continue;
-                    const d2 b = *(const d2*)&ldsB[buf][cblk[nj] * 16 + fr][round * 8 + lds_rq(fr, fq)];
-#pragma unroll
-                    for (int t = 0; t < 2; ++t)
-                        acc[0][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t], b[t], acc[0][nj], 0, 0, 0);
+                    ktile_mfma2(acc[0][nj], a, ktile_frag(ldsB[buf], cblk[nj] * 16, round, fr, fq));
                 }
             }
         }

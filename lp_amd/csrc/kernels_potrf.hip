@@ -6,12 +6,13 @@
 //     1. potrf_diag_kernel  (ONE workgroup): factor the 128x128 diagonal block in LDS and form
 //        inv(L_kk); both are needed downstream (inv(L_kk) turns the panel TRSM into a GEMM and the
 //        triangular solves into block mat-vecs).  See the comment in front of the kernel.
-//     2. L21 = A21 . inv(L_kk)^T           -> MFMA NT-GEMM, in place
+//     2. L21 = A21 . inv(L_kk)^T           -> MFMA NT-GEMM, in place; for one LP inside launch 1, column block by column
+//        block as the rows of inv(L_kk) are handed over (the pipelined chain step, in front of potrf_diag_kernel)
 //     3. A22 -= L21 . L21^T (lower tiles)  -> MFMA NT-GEMM, alpha=-1, beta=1
 // A non-positive pivot is recorded in `info` (1 + its global index, first one wins) and the
 // factorisation continues on NaNs; the host maps info != 0 to NumericalProblem exactly where the
 // reference maps a failed `cholesky()` (newton_equations.rs:59-63).
-#include "lpipm_internal.hpp"
+#include "gemm_tile.hpp"
 #include <utility>
 #include <type_traits>
 
@@ -21,10 +22,6 @@ constexpr int SB  = 16;        // sub-block edge inside the diagonal block
 constexpr int NSB = NB / SB;   // 8
 constexpr int LS  = NB + 2;    // LDS row stride in doubles (260 dwords: rows 4 banks apart)
 constexpr int DT  = 1024;      // threads of the diagonal-block kernel: 16 waves, 4 per SIMD
-
-typedef double d2 __attribute__((ext_vector_type(2)));
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 // 1/sqrt(d): hardware seed (v_rsq_f64) + two Newton steps; NaN for d <= 0 propagates to L.
 __device__ __forceinline__ double rsqrt_nr(double d) {
@@ -305,16 +302,113 @@ __device__ __forceinline__ void update_tile_rawpiv(double (*Ls)[LS], const TileA
     tile_mfma_store<false>(Ls, t, t, fr, fq, pv, g, g);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The pipelined chain step (potrf_diag_kernel<NARR, true>): the panel solve L21 = A21 . inv(L_kk)^T runs in the SAME launch as
+// the diagonal block, on workgroups 1 .. 2 rem beside workgroup 0.  Column block c of L21 needs A21 -- final before the
+// launch -- and row block c of inv(L_kk), which workgroup 0 stores with block column c (store_block_column), one block
+// column after the other: seven of the eight column blocks are computed while workgroup 0 is still eliminating, on CUs
+// that would stand idle, and only the eighth and its store stay on the chain.
+// Hand-off, the protocol of gemm_nt_units_kernel (kernels_adat.hip): workgroup 0 stores the rows of L^-1 write-through (sc1),
+// every storing wave waits vmcnt(0) and counts itself in an LDS word, the wave that completes the count adds 1 to the
+// step's flag word c (agent scope); a panel workgroup polls that word with one lane (relaxed, bounded), acquires, passes a
+// workgroup barrier and reads the strip with sc1 loads only.  Workgroup 0 never waits for a panel workgroup, so no cycle
+// of waits exists wherever the workgroups are placed; a panel workgroup that runs out of polls sets PIPE_TIMEOUT in the
+// info word -- the factorisation then reports a failure instead of hanging.
+// The eight flag words return to zero inside the launch: every panel workgroup adds 1 to word 7 once it has seen it
+// raised (its last look at any of them) and so does workgroup 0 when it raises it; whoever brings it to npanel + 1 clears
+// all eight.
+constexpr int PIPE_TIMEOUT = 1 << 30;       // info word: a panel workgroup gave up waiting for the diagonal block
+// Polls of one flag word before a panel workgroup gives up.  A poll is one L2 round trip and an s_sleep 8, 0.5 us or more;
+// the diagonal-block workgroup lasts ~26 us and raises a flag every ~2.7 us: the bound is at least 2000 of its durations.
+constexpr unsigned PIPE_POLLS = 1u << 17;
+constexpr int PIPE_AUX_SC1 = 16;            // cache-policy operand of the buffer loads and stores: sc1
+typedef unsigned int pu4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void pipe_clear_flags(unsigned int* flags) {
+#pragma unroll
+    for (int c = 0; c < NSB; ++c) __hip_atomic_store(flags + c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Panel workgroup g (0-based) of a step: rows 64 g .. 64 g + 63 of the panel, two of the 32-row tiles of
+// gemm_nt_rows32_k128_kernel, every element with that kernel's sum (k-tiles 0 .. c in order, ktile_mfma2 per round, from
+// zero).  lds: the kernel's image array, here the k-tile images of the 64 rows [8][64][LDS_STRIDE] and, double-buffered, of
+// the strip of inv(L_kk) [2][8][16][LDS_STRIDE].  Wave w sits on SIMD w & 3 and takes the 16x16 block (tile, row block)
+// = (w & 3) of the column blocks q = w >> 2 and 7 - q: the four blocks of a column block run on four SIMDs, and the last
+// column block belongs to waves that have had nothing to do since the first.
+__device__ __forceinline__ void panel_pipe_workgroup(double* lds, int* s_ok, double* rows, long long ld, const double* Linv,
+                                                     long long ldinv, unsigned int* flags, int npanel, int32_t* info) {
+    static_assert((NSB * 64 + 2 * NSB * SB) * LDS_STRIDE <= NB * LS, "the panel workgroup's images fit into the diagonal block's");
+    double (*As)[64][LDS_STRIDE] = (double (*)[64][LDS_STRIDE])lds;
+    double (*Qs)[NSB][SB][LDS_STRIDE] = (double (*)[NSB][SB][LDS_STRIDE])(lds + NSB * 64 * LDS_STRIDE);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fr = lane & 15, fq = lane >> 4;
+    const int skt = lane >> 3, scol = (lane & 7) * 2;        // staging: a wave moves one row of 128 doubles, 16 B per lane
+    // the 64 rows of A21, requested at once: wave w takes rows w, w + 16, w + 32, w + 48
+    d2 pa[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pa[i] = *(const d2*)(rows + (long long)(wave + 16 * i) * ld + 2 * lane);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *(d2*)&As[skt][wave + 16 * i][lds_wcol(wave + 16 * i, scol)] = pa[i];
+    const __amdgpu_buffer_rsrc_t qr =
+        __builtin_amdgcn_make_buffer_rsrc((void*)Linv, 0, (int)(((long long)(NB - 1) * ldinv + NB) * 8), 0x00027000);
+    const int blk = wave & 3, q = wave >> 2;
+    const bool poller = wave == DT / 64 - 1 && lane == 0;    // (a wave of the middle column blocks: nothing of the last on it)
+    for (int c = 0; c < NSB; ++c) {
+        if (poller) {
+            unsigned spins = 0;
+            while (__hip_atomic_load(flags + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u && ++spins < PIPE_POLLS)
+                __builtin_amdgcn_s_sleep(8);
+            const bool ok = spins < PIPE_POLLS;
+            if (ok) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            } else {
+                atomicOr((int*)info, PIPE_TIMEOUT);
+            }
+            // this workgroup's last look at the flag words: seen raised, or given up
+            if (!ok || c == NSB - 1) {
+                const unsigned old = __hip_atomic_fetch_add(flags + NSB - 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if ((int)old == npanel) pipe_clear_flags(flags);
+            }
+            *s_ok = ok;
+        }
+        __syncthreads();                                       // (also: the images of A21 are in place, c = 0)
+        if (!*s_ok) return;                                    // workgroup-uniform
+        // rows 16 c .. 16 c + 15 of L^-1, columns 0 .. 16 c + 15: wave w moves row w
+        if (skt <= c) {
+            const unsigned off = (unsigned)((((long long)(c * SB + wave)) * ldinv + 2 * lane) * 8);
+            const d2 v = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(qr, (int)off, 0, PIPE_AUX_SC1));
+            *(d2*)&Qs[c & 1][skt][wave][lds_wcol(wave, scol)] = v;
+        }
+        __syncthreads();
+        if (c == q || c == NSB - 1 - q) {                      // wave-uniform
+            d4 acc = (d4){0.0, 0.0, 0.0, 0.0};
+            for (int kt = 0; kt <= c; ++kt) {
+#pragma unroll
+                for (int round = 0; round < 2; ++round)
+                    ktile_mfma2(acc, ktile_frag(As[kt], blk * SB, round, fr, fq), ktile_frag(Qs[c & 1][kt], 0, round, fr, fq));
+            }
+            const d4 one[1][1] = {{acc}};
+            tile_store<1, 1>(rows + (long long)(blk * SB + fq) * ld + (c * SB + fr), ld, one, 1.0, 0.0, false, 0, -1, fr, fq);
+        }
+    }
+}
+
 // Mblk: top-left of the 128x128 diagonal block (row-major, ld).  Linv / LinvT: where inv(L_kk) and its transpose go
 // (row-major, ldinv): the diagonal 128-blocks of the super-block inverses.  The elimination of [A; I] leaves [L; L^-T]:
 // row i of L^-T lives in the strict upper triangle of the LDS image right of its own 16-block and, inside its own
 // block, in xid.  The strict upper triangle of the diagonal 16x16 sub-blocks of Mblk is written as zeros (nothing
 // reads it: this kernel itself ignores it on load).
-template <int NARR>
+// PIPE: the pipelined chain step (above).  Workgroup 0 is the diagonal-block workgroup, with the rows of L^-1 stored
+// write-through and flag word c raised behind block column c; workgroups 1 .. npanel solve the panel below the block
+// (rows NB .. of the same columns of Mblk).  flags: the step's eight words, zero between launches.  Without PIPE the grid is
+// one workgroup per LP and flags / npanel are not looked at.
+template <int NARR, bool PIPE>
 __global__ __launch_bounds__(DT) void potrf_diag_kernel(double* __restrict__ Mblk, long long ld,
                                                          double* __restrict__ Linv, double* __restrict__ LinvT,
                                                          long long ldinv, int32_t* info, int global_row0,
-                                                         long long* stamps, BatchK bk) {
+                                                         long long* stamps, BatchK bk, unsigned int* flags, int npanel) {
     if (batch_done(bk)) return;
     Mblk = batch_ptr(Mblk, bk); Linv = batch_ptr(Linv, bk); LinvT = batch_ptr(LinvT, bk); info = batch_ptr(info, bk);
 #define STAMP(i) do { if (stamps && threadIdx.x == 0) stamps[i] = clock64(); } while (0)
@@ -330,6 +424,14 @@ __global__ __launch_bounds__(DT) void potrf_diag_kernel(double* __restrict__ Mbl
     __shared__ int nrole[2];                                              // MFMA workers, store workers
     __shared__ int pdone[NSB], ready[NSB];                                // P tiles done / scales and tile table ready, per block column
     __shared__ __attribute__((aligned(16))) int ttab[NSB - 1][32][4];     // R tiles of every block column: LDS byte offsets
+    __shared__ int sdone[NSB];                                            // PIPE: storing waves whose stores of a block column have landed
+    if constexpr (PIPE) {
+        if (blockIdx.x != 0) {
+            panel_pipe_workgroup(&Ls[0][0], &sdone[0], Mblk + ((long long)NB + 64ll * (blockIdx.x - 1)) * ld, ld, Linv, ldinv,
+                                 flags, npanel, info);
+            return;
+        }
+    }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);            // wave-uniform: tile decode and branches go scalar
     const int fr = lane & 15, fq = lane >> 4;
@@ -355,7 +457,7 @@ __global__ __launch_bounds__(DT) void potrf_diag_kernel(double* __restrict__ Mbl
     }
     if (tid < SB * SB) eye[tid >> 4][tid & 15] = ((tid >> 4) == (tid & 15)) ? 1.0 : 0.0;
     if (lane == 0) wsimd[wave] = my_simd;
-    if (tid < NSB) { pdone[tid] = 0; ready[tid] = 0; }
+    if (tid < NSB) { pdone[tid] = 0; ready[tid] = 0; if constexpr (PIPE) sdone[tid] = 0; }
     lds_barrier();
     // Roles beside the elimination.  FP64 MFMA and v_fma_f64 share a SIMD's double-precision pipe and the eliminating wave
     // runs at priority 3, so the waves on its SIMD stay out of the way.  On every other SIMD the first two waves stream the
@@ -466,12 +568,31 @@ __global__ __launch_bounds__(DT) void potrf_diag_kernel(double* __restrict__ Mbl
                 const int s1 = img ? LS : XS3;
                 double* dst = Linv + (long long)(c0 + rw0) * ldinv + i;
                 const long long dstep = (long long)rwstep * ldinv;
+                // PIPE: these are the rows the panel workgroups of this launch read: write-through
                 for (int r = rw0; r < SB; r += rwstep, src += rwstep, dst += dstep) {
                     if (i <= c0 + r) {
                         const double rs1 = dinv[c0 + r];
-                        *(d2*)dst = (d2){src[0] * rs1, src[s1] * rs1};
+                        const d2 w = (d2){src[0] * rs1, src[s1] * rs1};
+                        if constexpr (PIPE) {
+                            const __amdgpu_buffer_rsrc_t lr = __builtin_amdgcn_make_buffer_rsrc(
+                                (void*)Linv, 0, (int)(((long long)(NB - 1) * ldinv + NB) * 8), 0x00027000);
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pu4, w), lr, (int)((dst - Linv) * 8), 0, PIPE_AUX_SC1);
+                        } else {
+                            *(d2*)dst = w;
+                        }
                     }
                 }
+            }
+        }
+    };
+    // PIPE: behind the stores of block column c by `nwaves` waves.  Every one of them waits for its stores and counts itself;
+    // the one that completes the count raises flag word c (and, with word 7, counts workgroup 0 among those done with them).
+    auto publish = [&](int c, int nwaves) {
+        if constexpr (PIPE) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (lane == 0 && atomicAdd(&sdone[c], 1) == nwaves - 1) {
+                const unsigned old = __hip_atomic_fetch_add(flags + c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (c == NSB - 1 && (int)old == npanel) pipe_clear_flags(flags);
             }
         }
     };
@@ -489,6 +610,7 @@ __global__ __launch_bounds__(DT) void potrf_diag_kernel(double* __restrict__ Mbl
             __builtin_amdgcn_s_setprio(2);
             store_block_column(k, (role - 16) * 64 + lane, n_sw * 64);
             __builtin_amdgcn_s_setprio(0);
+            publish(k, n_sw);
             return;
         }
         // Two-stage pipeline per worker: right behind the first MFMA of tile i come the operand loads of tile i+1 and the read
@@ -558,7 +680,7 @@ __global__ __launch_bounds__(DT) void potrf_diag_kernel(double* __restrict__ Mbl
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ea), "+v"(eb));
             tile_wait<0>(ga); tile_wait<0>(gb);
         }
-        if (n_sw == 0) store_block_column(k, role * 64 + lane, n_mw * 64);
+        if (n_sw == 0) { store_block_column(k, role * 64 + lane, n_mw * 64); publish(k, n_mw); }
     };
 
     // One workgroup barrier per block column.  Between two barriers, with X(k-1) known:
@@ -616,6 +738,7 @@ __global__ __launch_bounds__(DT) void potrf_diag_kernel(double* __restrict__ Mbl
     if (wave == 8) pivot_scales(NSB - 1);
     lds_barrier();
     store_block_column(NSB - 1, tid, DT);
+    publish(NSB - 1, NW);
     STAMP(7);
 #undef STAMP
 #undef WSTAMP
@@ -641,28 +764,48 @@ static hipError_t potrf_panel_chain(double* M, int64_t ld, int mp, const FactorP
                                     const Batch& bt, int J0, int J1) {
     hipError_t e;
     const int nb = mp / NB;
+    // One LP: the panel solve rides in the diagonal block's launch (potrf_diag_kernel<2, true>), 2 rem panel workgroups of
+    // 64 rows beside the diagonal-block one, while each of them has a CU to itself.  LPIPM_PANEL_PIPE=0: the two launches;
+    // =2: the two launches with the producer side alone in the first (write-through rows of L^-1, flags raised and, with no
+    // panel workgroup to count, cleared by workgroup 0 itself): what the hand-off costs the elimination.
+    static const int n_cus = [] {
+        int dev = 0, n = 0;
+        return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) ? n : 0;
+    }();
+    const char* knob = lp_knob("LPIPM_PANEL_PIPE");          // (read per call: the tests switch it inside one process)
+    const bool pipe_on = bt.count == 1 && plan.pipe_flags && !(knob && knob[0] == '0');
     for (int j = J0; j < J1; ++j) {
         const int64_t o = (int64_t)j * NB;
         double* diag = M + o * ld + o;
         double* linv = plan.blk_inv(j);
         const int ldinv = plan.blk_ld(j);
-        hipLaunchKernelGGL(potrf_diag_kernel<2>, dim3(1, 1, bt.count), dim3(DT), 0, st, diag, (long long)ld, linv,
-                           plan.blk_invT(j), (long long)ldinv, info, (int)o,
-                           (long long*)(j == 0 ? g_diag_stamps : nullptr), batch_k(bt));
+        const int rem = nb - j - 1;
+        const bool producer = pipe_on && rem > 0 && 1 + 2 * rem <= n_cus;
+        const bool pipe = producer && !(knob && knob[0] == '2');
+        const int npanel = pipe ? 2 * rem : 0;
+        long long* stamps = (long long*)(j == 0 ? g_diag_stamps : nullptr);
+        if (producer)
+            hipLaunchKernelGGL((potrf_diag_kernel<2, true>), dim3(1 + npanel, 1, 1), dim3(DT), 0, st, diag, (long long)ld, linv,
+                               plan.blk_invT(j), (long long)ldinv, info, (int)o, stamps, batch_k(bt),
+                               plan.pipe_flags + (size_t)j * NSB, npanel);
+        else
+            hipLaunchKernelGGL((potrf_diag_kernel<2, false>), dim3(1, 1, bt.count), dim3(DT), 0, st, diag, (long long)ld, linv,
+                               plan.blk_invT(j), (long long)ldinv, info, (int)o, stamps, batch_k(bt), (unsigned int*)nullptr, 0);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
-        const int rem = nb - j - 1;
         if (rem <= 0) break;
         double* panel = M + (o + NB) * ld + o;   // rows below block j, column block j
-        GemmArgs t{};
-        t.P = panel; t.ldp = ld; t.Q = linv; t.ldq = ldinv;
-        t.C = panel; t.ldc = ld; t.K = NB; t.alpha = 1.0; t.beta = 0.0;
-        // few tiles -> latency-bound: 32-row x 128-col tiles put 4x as many CUs on the panel, and a
-        // workgroup still owns whole rows, so the product may overwrite its own input
-        t.tile_shape = TileShape::T32x128;
-        t.ntiles = 4 * rem; t.tiles_lower = 0; t.ntj = 1; t.batch = bt;
-        e = launch_gemm_nt(t, st);
-        if (e != hipSuccess) return e;
+        if (!pipe) {
+            GemmArgs t{};
+            t.P = panel; t.ldp = ld; t.Q = linv; t.ldq = ldinv;
+            t.C = panel; t.ldc = ld; t.K = NB; t.alpha = 1.0; t.beta = 0.0;
+            // few tiles -> latency-bound: 32-row x 128-col tiles put 4x as many CUs on the panel, and a
+            // workgroup still owns whole rows, so the product may overwrite its own input
+            t.tile_shape = TileShape::T32x128;
+            t.ntiles = 4 * rem; t.tiles_lower = 0; t.ntj = 1; t.batch = bt;
+            e = launch_gemm_nt(t, st);
+            if (e != hipSuccess) return e;
+        }
         const int ncols = J1 - j - 1;            // column blocks of the outer panel right of j
         if (ncols > 0) {
             // rows j+1..nb x columns j+1..J1-1 -= L[rows, j] . L[cols, j]^T  (rectangular grid of tiles; the few tiles

@@ -320,7 +320,11 @@ hipError_t factor_plan_create(FactorPlan& plan, double* L, int64_t ld, int mp, A
         e = hipMemcpyAsync(plan.pieces_dev, plan.pieces.data(), plan.pieces.size() * sizeof(SweepPiece), hipMemcpyHostToDevice, st);
         if (e != hipSuccess) return e;
     }
-    if ((e = hipMalloc((void**)&plan.descs_dev, (descs.size() + 1) * sizeof(GemmTileDesc))) != hipSuccess) return e;
+    // (one allocation: the descriptors, then the hand-off words of the pipelined chain step -- 8 words x 4 B per 128-block)
+    const size_t desc_bytes = round_up((descs.size() + 1) * sizeof(GemmTileDesc), 16), flag_bytes = (size_t)(mp / NB) * 8 * sizeof(unsigned int);
+    if ((e = hipMalloc((void**)&plan.descs_dev, desc_bytes + flag_bytes)) != hipSuccess) return e;
+    plan.pipe_flags = (unsigned int*)((char*)plan.descs_dev + desc_bytes);
+    if ((e = hipMemsetAsync(plan.pipe_flags, 0, flag_bytes, st)) != hipSuccess) return e;
     if (!descs.empty()) {
         e = hipMemcpyAsync(plan.descs_dev, descs.data(), descs.size() * sizeof(GemmTileDesc), hipMemcpyHostToDevice, st);
         if (e != hipSuccess) return e;
@@ -338,6 +342,7 @@ void factor_plan_destroy(FactorPlan& plan) {
     plan.H.clear(); plan.G.clear(); plan.couple.clear(); plan.pieces.clear(); plan.fwd.clear(); plan.bwd.clear();
     plan.pieces_dev = nullptr;
     plan.descs_dev = nullptr;
+    plan.pipe_flags = nullptr;
     plan.tpart = nullptr;
     plan.tws = nullptr;
     plan.L = nullptr; plan.ld = 0; plan.mp = 0;

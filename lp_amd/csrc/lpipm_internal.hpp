@@ -243,6 +243,8 @@ struct FactorPlan {
                              // the chip prefers 512)
     std::vector<SuperBlock> sbs;
     GemmTileDesc* descs_dev = nullptr;           // grouped-GEMM tiles of all merge stages (own allocation, shared by a batch)
+    unsigned int* pipe_flags = nullptr;          // the pipelined chain step's hand-off words, 8 per 128-block, zero between launches
+                                                 //   (kernels_potrf.hip; behind the descriptors in descs_dev's allocation)
     std::vector<std::pair<int, int>> stages;     // (first descriptor, count) per launch, in order
     std::vector<MergeGroup> groups;              // the stages cut by outer panel (stage by stage, panels ascending inside one)
     double* tpart = nullptr;                     // gemv_t slabs of the backward sweep
