@@ -147,6 +147,14 @@ extern "C" {
         ctx: *mut lpipm_ctx, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, b_ub: *const f64, m_eq: u64,
         a_eq: *const f64, lda_eq: u64, b_eq: *const f64, c: *const f64, c0: f64, upper: *const f64,
     ) -> c_int;
+    /// General column bounds lower[n] <= x <= upper[n] (null lower: zeros, null upper: +inf; -inf / +inf = no such end): shifts,
+    /// reflections and free columns without growing the normal matrix or storing a column twice.  x_slack has n + m_ub + nb + nf
+    /// entries -- the structural values in the caller's variables, the `ub` slacks, the bound slacks, the free columns' negative
+    /// parts --, y of lpipm_get_duals m + nb.  lower_j > upper_j: LPIPM_INFEASIBLE from the upload (see include/lpipm.h).
+    pub fn lpipm_upload_bounds(
+        ctx: *mut lpipm_ctx, n: u64, m_ub: u64, a_ub: *const f64, lda_ub: u64, b_ub: *const f64, m_eq: u64,
+        a_eq: *const f64, lda_eq: u64, b_eq: *const f64, c: *const f64, c0: f64, lower: *const f64, upper: *const f64,
+    ) -> c_int;
     /// Kernel entries of a bounded upload: M~ (m x m, lower triangle) at dinv_ext[n + nb], and its reduced sym_solve.
     pub fn lpipm_k_bounded_normal(ctx: *mut lpipm_ctx, dinv_ext: *const f64, m_out: *mut f64) -> c_int;
     pub fn lpipm_k_bounded_sym_solve(

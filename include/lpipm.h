@@ -216,10 +216,47 @@ int lpipm_upload_ub_eq_tall(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const dou
  * lengths.  No first factor is kept.
  * Out of scope: lockstep and shared-matrix batches of bounded LPs; lpipm_upload_device and lpipm_solve_batch*; a kept first
  * factor (M~_1 depends on A and B alone: a follow-up); the QR arms; f32; bounds on the tall forms (there a bound is one more
- * cheap row already); lower bounds other than 0; free columns. */
+ * cheap row already); lower bounds other than 0 and free columns (lpipm_upload_bounds, next, has them). */
 int lpipm_upload_bounded(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub, const double* b_ub,
                          uint64_t m_eq, const double* A_eq, uint64_t lda_eq, const double* b_eq, const double* c, double c0,
                          const double* upper);
+
+/* General column bounds: min c.x + c0, A_ub x <= b_ub, A_eq x = b_eq, lower_j <= x_j <= upper_j, with lower_j real or -inf
+ * (NULL: all 0) and upper_j real or +inf (NULL: all +inf), one pair per structural column.  The normal matrix still has the
+ * order m = m_ub + m_eq, and no column of A is stored or read twice.  Per column:
+ *   P  lower finite, upper +inf    the shift x_j = lower_j + x'_j          (lower_j = 0: the ordinary column)
+ *   B  both finite                 the shift, then lpipm_upload_bounded's column with u'_j = upper_j - lower_j
+ *   N  lower -inf, upper finite    the reflection x_j = upper_j - x'_j     (sigma_j = -1, t_j = upper_j)
+ *   F  lower -inf, upper +inf      free: x_j = x'_j - x^-_j, both halves >= 0, ONE stored column
+ * With sigma_j = +1 outside N and t_j = 0 on F the iteration sees the primed LP A' = A.diag(sigma), b' = b - A.t, c' = sigma c,
+ * c0' = c0 + c.t, extended as lpipm_upload_bounded extends it plus one column per free column (F ascending, nf of them):
+ *   A_ext = [[A', 0, -A'_F], [E_B, I_nb, 0]]   b_ext = [b'; u'_B]   c_ext = [c'; 0; -c'_F]   x_ext = [x'; w; x^-]   z_ext = [z; v; z^-]
+ * Only sym_solve changes, on F (dm = x^- / z^-, r1 = [r1_x; r1_w; r1_m], t = A'^T.v_1):
+ *   D~_j = dx_j + dm_j;   W_j = dx_j r1_x,j - dm_j r1_m,j;   u_x,j = dx_j (t_j - r1_x,j);   u_m,j = dm_j (-t_j - r1_m,j)
+ * The free block is never stored and never multiplied: a pass over A' reads the net vector (x'_j - x^-_j on F), and the x^-
+ * column of A_ext^T.v is -(A'^T.v_1)_j.  The two halves of a free column are determined only up to a common shift: the contract
+ * is on their difference.
+ * Outputs.  x_slack_out of lpipm_solve[_device] has n + m_ub + nb + nf entries: the structural values IN THE CALLER'S VARIABLES
+ * (x_j = t_j + sigma_j x'_j; x'_j - x^-_j on F), the `ub` slacks, the bound slacks w, then the negative parts x^- in ascending
+ * column order (a diagnostic: the positive part is x_j + x^-_j).  fun = c.x + c0 in the caller's variables.
+ * lpipm_get_duals[_device]: y has m + nb entries (a column transform does not change a row's multiplier); z is as long as
+ * x_slack_out, z_j = sigma_j z'_j on the structural columns, so that A^T y + z = c holds in the caller's orientation up to the
+ * dual residual (z_j <= 0 on N, z_j ~ 0 on F), v and z^- behind them; dual_fun is that of the primed LP (b'.y + u'.y_b + c0').
+ * lpipm_get_certificate[_device]: as on the bounded form.  The improving ray comes in the caller's orientation (sigma applied,
+ * the free halves netted: A x ~ 0, c.x = -1, x_j >= 0 outside N and F, x_j <= 0 on N); the Farkas ray is normalised against the
+ * SHIFTED right-hand side, b'.y + u'.y_b = 1 with b' = b - A.t, and its z comes with sigma applied.
+ * lpipm_get_scaling returns m + nb row exponents and n + m_ub + nb + nf column exponents (an x^- column has its column's).
+ * Refusals (a refused call leaves the resident problem as it was).  NaN, lower_j = +inf or upper_j = -inf: LPIPM_ERR_BAD_ARGUMENT;
+ * lower_j > upper_j: LPIPM_INFEASIBLE, returned by the upload; lower_j == upper_j is class B with width 0 and behaves as the
+ * explicit form does.  Everything lpipm_upload_bounded refuses with LPIPM_ERR_UNSUPPORTED is refused here.  The
+ * lpipm_k_bounded_* entries, lpipm_k_iteration and lpipm_k_gemv_n/_t/_dual see A_ext at the new lengths.  No first factor is kept.
+ * Without a free column, a reflection or a non-zero shift this is lpipm_upload_bounded's request itself: the same launches,
+ * the same bits.
+ * Out of scope: lockstep and shared-matrix batches; lpipm_upload_device and lpipm_solve_batch*; the tall forms; f32; the QR
+ * arms; a kept first factor; eliminating fixed columns; ranged rows. */
+int lpipm_upload_bounds(lpipm_ctx* ctx, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub, const double* b_ub,
+                        uint64_t m_eq, const double* A_eq, uint64_t lda_eq, const double* b_eq, const double* c, double c0,
+                        const double* lower, const double* upper);
 
 /* New b and c for the resident problem of lpipm_upload / lpipm_upload_slack: b[m] and c[n] in that upload's own form (c with
  * its slack entries).  A stays where it is, so a sweep over right-hand sides or costs, or a sequence of LPs over one

@@ -106,8 +106,16 @@ public:
     // bounds at all) and how many of them are finite.  A(), b() and c() stay the slack form WITHOUT the bounds.
     const std::vector<F>& upper() const { return upper_; }
     uint64_t n_bounded() const { return n_bounded_; }
+    // Likewise the lower bounds given to ProblemBuilder::lower (-inf: none; empty: all 0), the columns with neither end, and
+    // whether any lower end is not 0: InteriorPoint then uploads through lpipm_upload_bounds.  n_bounded() counts the columns
+    // with both ends finite.
+    const std::vector<F>& lower() const { return lower_; }
+    uint64_t n_free() const { return n_free_; }
+    bool general_bounds() const { return general_; }
+    // what follows the structural columns in the upload's column vectors: `ub` slacks, bound slacks, negative parts
+    uint64_t tail() const { return n_slack_ + n_bounded_ + n_free_; }
     std::vector<F> denormalize_x_into(std::vector<F> x_slack) const {  // :65-69
-        x_slack.resize(x_slack.size() - n_slack_ - n_bounded_);      // (a bounded solve's x_slack ends with the bound slacks)
+        x_slack.resize(x_slack.size() - tail());      // (a bounded solve's x_slack ends with the bound slacks, then the x^-)
         return x_slack;
     }
 
@@ -117,8 +125,9 @@ private:
     std::vector<F> b_, c_;
     F c0_ = 0;
     uint64_t n_slack_ = 0;
-    std::vector<F> upper_;
-    uint64_t n_bounded_ = 0;
+    std::vector<F> upper_, lower_;
+    uint64_t n_bounded_ = 0, n_free_ = 0;
+    bool general_ = false;
 };
 
 // src/linear_program.rs:72-170
@@ -130,6 +139,10 @@ public:
     // Not in the reference: upper bounds x_j <= u[j] on the structural columns, one entry per column, +infinity where there is
     // none.  InteriorPoint::solve then runs the bounded form (lpipm_upload_bounded): the normal matrix keeps its order.  f64 only.
     BasicProblemBuilder& upper(const std::vector<F>& u) { upper_ = &u; return *this; }
+    // Not in the reference: lower bounds l[j] <= x_j, one entry per column, -infinity where there is none (without this call every
+    // lower bound is 0); a column with neither end is free.  InteriorPoint::solve then runs lpipm_upload_bounds and returns x,
+    // fun, the duals and the certificates in these variables.  f64 only.
+    BasicProblemBuilder& lower(const std::vector<F>& l) { lower_ = &l; return *this; }
     BasicProblem<F> build() const {                                                                               // :125-169
         const uint64_t n = c_.size();
         const uint64_t m_ub = ub_A_ ? ub_A_->rows : 0, m_eq = eq_A_ ? eq_A_->rows : 0;
@@ -163,13 +176,18 @@ public:
             for (uint64_t j = 0; j < n; ++j) p.c_[j] = c_[j];
             p.n_slack_ = m_ub;
         }
-        if (upper_) {
-            if (upper_->size() != n) raise_for(LPIPM_INCOMPATIBLE_DIMENSIONS);
-            for (const F u : *upper_) {
-                if (u != u || u == -std::numeric_limits<F>::infinity()) raise_for(LPIPM_INVALID_PARAMETER);
-                if (u != std::numeric_limits<F>::infinity()) ++p.n_bounded_;
+        if (upper_ || lower_) {
+            const F inf = std::numeric_limits<F>::infinity();
+            if ((upper_ && upper_->size() != n) || (lower_ && lower_->size() != n)) raise_for(LPIPM_INCOMPATIBLE_DIMENSIONS);
+            p.upper_ = upper_ ? *upper_ : std::vector<F>(n, inf);
+            if (lower_) p.lower_ = *lower_;
+            for (uint64_t j = 0; j < n; ++j) {
+                const F u = p.upper_[j], l = lower_ ? p.lower_[j] : F(0);
+                if (u != u || u == -inf || l != l || l == inf) raise_for(LPIPM_INVALID_PARAMETER);
+                if (u != inf && l != -inf) ++p.n_bounded_;
+                if (u == inf && l == -inf) ++p.n_free_;
+                if (l != F(0)) p.general_ = true;
             }
-            p.upper_ = *upper_;
         }
         return p;
     }
@@ -181,6 +199,7 @@ private:
     const BasicMatrix<F>* eq_A_ = nullptr;
     const std::vector<F>* eq_b_ = nullptr;
     const std::vector<F>* upper_ = nullptr;
+    const std::vector<F>* lower_ = nullptr;
 };
 template <class F> inline BasicProblemBuilder<F> BasicProblem<F>::target(const std::vector<F>& c) { return BasicProblemBuilder<F>(c); }
 
@@ -278,12 +297,13 @@ public:
         upload_and_solve(ctx, problem, x, fun, it);
         const Matrix& A = problem.A();
         const std::size_t ns = problem.n_slack(), nb = problem.n_bounded();     // (bounded: the bound rows and their slacks come last)
-        std::vector<double> y(A.rows + nb), z(A.cols + nb);
+        const std::size_t nf = problem.n_free();                                 // (general bounds: then the negative parts)
+        std::vector<double> y(A.rows + nb), z(A.cols + nb + nf);
         lpipm_dual_info info{};
         raise_for(lpipm_get_duals(ctx, 0, y.data(), z.data(), &info));
         return DualResult{OptimizeResult(problem.denormalize_x_into(std::move(x)), fun, it),
                           std::vector<double>(y.begin(), y.begin() + ns), std::vector<double>(y.begin() + ns, y.end() - nb),
-                          std::vector<double>(z.begin(), z.end() - ns - nb), info.dual_fun};
+                          std::vector<double>(z.begin(), z.end() - ns - nb - nf), info.dual_fun};
     }
     // solve(), but an Infeasible or Unbounded problem throws a CertifiedError (a LinearProgramError of the same kind) that
     // carries the certificate of the solve's last iterate (lpipm_get_certificate on the same context; tall_form() /
@@ -299,16 +319,17 @@ public:
         if (rc == LPIPM_INFEASIBLE || rc == LPIPM_UNBOUNDED) {
             const Matrix& A = problem.A();
             const std::size_t ns = problem.n_slack(), nb = problem.n_bounded();
-            std::vector<double> y(A.rows + nb), col(A.cols + nb);
+            const std::size_t nf = problem.n_free();
+            std::vector<double> y(A.rows + nb), col(A.cols + nb + nf);
             lpipm_cert_info info{};
             raise_for(lpipm_get_certificate(ctx, 0, y.data(), col.data(), &info));
             Certificate cert;
             cert.kind = info.kind; cert.scale = info.scale; cert.residual = info.residual;
             if (info.kind == LPIPM_CERT_FARKAS) {
                 cert.y_ub.assign(y.begin(), y.begin() + ns); cert.y_eq.assign(y.begin() + ns, y.end() - nb);
-                cert.z.assign(col.begin(), col.end() - ns - nb);
+                cert.z.assign(col.begin(), col.end() - ns - nb - nf);
             } else if (info.kind == LPIPM_CERT_RAY)
-                cert.x.assign(col.begin(), col.end() - ns - nb);
+                cert.x.assign(col.begin(), col.end() - ns - nb - nf);
             throw CertifiedError(static_cast<ErrorKind>(rc), lpipm_strerror(rc), std::move(cert));
         }
         if (rc == LPIPM_ITERATION_LIMIT) raise_for(rc, x);          // payload: x / tau, mod.rs:237-239
@@ -321,7 +342,7 @@ public:
         lpipm_ctx* ctx = nullptr;
         raise_for(lpipm_create(device_, &ctx));
         struct Guard { lpipm_ctx* c; ~Guard() { lpipm_destroy(c); } } guard{ctx};
-        if (problem.n_bounded() > 0) raise_for(LPIPM_ERR_UNSUPPORTED);     // the bounded form has no f32 arm
+        if (problem.n_bounded() > 0 || problem.general_bounds()) raise_for(LPIPM_ERR_UNSUPPORTED);     // the bounded forms have no f32 arm
         const MatrixF32& A = problem.A();
         std::vector<float> x(A.cols);
         float fun = 0.0f;
@@ -343,6 +364,17 @@ private:
     // The upload of `problem` in the form the opt-ins select, and lpipm_solve.  -> the solve's status
     int upload_and_solve_rc(lpipm_ctx* ctx, const Problem& problem, std::vector<double>& x, double& fun, uint64_t& it) const {
         const Matrix& A = problem.A();
+        if (problem.general_bounds()) {
+            // general column bounds, whatever the opt-ins say: the blocks of A = [[A_ub I], [A_eq 0]] with lda = cols, both
+            // bound vectors as given; x_slack comes back in the caller's variables and ends with the bound slacks and the x^-
+            const std::size_t m_ub = problem.n_slack(), m_eq = A.rows - m_ub;
+            raise_for(lpipm_upload_bounds(ctx, A.cols - m_ub, m_ub, m_ub ? A.data.data() : nullptr, A.cols,
+                                          m_ub ? problem.b().data() : nullptr, m_eq, m_eq ? A.data.data() + m_ub * A.cols : nullptr,
+                                          A.cols, m_eq ? problem.b().data() + m_ub : nullptr, problem.c().data(), problem.c0(),
+                                          problem.lower().data(), problem.upper().data()));
+            x.assign(A.cols + problem.n_bounded() + problem.n_free(), 0.0);
+            return lpipm_solve(ctx, &o_, x.data(), &fun, &it, nullptr);
+        }
         if (problem.n_bounded() > 0) {
             // the bounded form, whatever the opt-ins say (on a tall form a bound is one more `ub` row): the blocks of
             // A = [[A_ub I], [A_eq 0]] with lda = cols, the bounds as given; x_slack ends with the nb bound slacks

@@ -135,12 +135,18 @@ def _square(M):
 class Problem:
     """A linear program in slack form (linear_program.rs:24-30): min c'x st A x == b, x >= 0."""
 
-    def __init__(self, A, b, c, c0, n_slack, parts=None, dtype=np.float64, upper=None):
+    def __init__(self, A, b, c, c0, n_slack, parts=None, dtype=np.float64, upper=None, lower=None):
         self._A, self._b, self._c, self._c0, self._n_slack = A, b, c, float(c0), int(n_slack)
         # ProblemBuilder.upper: one entry per structural column, +inf where there is no bound (None: no bounds at all).
         # A(), b() and c() stay the slack form WITHOUT the bounds; Context.upload hands them to lpipm_upload_bounded.
+        # ProblemBuilder.lower: likewise, -inf where there is no lower end (None: all 0).  With any lower that is not 0
+        # Context.upload hands both to lpipm_upload_bounds; the results come back in these variables.
         self._upper = upper
-        self._bounded = np.flatnonzero(np.isfinite(upper)) if upper is not None else np.zeros(0, dtype=np.int64)
+        self._lower = lower
+        none = np.zeros(0, dtype=np.int64)
+        has_l = np.isfinite(lower) if lower is not None else True
+        self._bounded = np.flatnonzero(np.isfinite(upper) & has_l) if upper is not None else none
+        self._free = np.flatnonzero(np.isinf(upper) & np.isinf(lower)) if lower is not None else none
         # F of Problem<F> (linear_program.rs:24): float32 when every array the builder was given is float32 (the reference
         # infers F from its ndarray arguments), float64 otherwise.  A Problem<f32> is solved by InteriorPoint<f32>
         # (lpipm_solve_f32: every operation in f32, src/float.rs:42-43).
@@ -180,12 +186,25 @@ class Problem:
         """The upper bounds of the structural columns (+inf: none), or None for a Problem without bounds."""
         return self._upper
 
+    def lower(self):
+        """The lower bounds of the structural columns (-inf: none), or None for a Problem built without .lower (all 0)."""
+        return self._lower
+
     def n_bounded(self) -> int:
+        """Columns with a finite lower and a finite upper end: the bound rows of the upload."""
         return int(self._bounded.shape[0])
 
+    def n_free(self) -> int:
+        """Columns with neither end: each adds one negative part x^- at the end of the upload's x_slack."""
+        return int(self._free.shape[0])
+
+    def _tail(self) -> int:
+        # what follows the structural columns in the upload's column vectors: `ub` slacks, bound slacks w, negative parts x^-
+        return self._n_slack + self.n_bounded() + self.n_free()
+
     def denormalize_x_into(self, x_slack: np.ndarray) -> np.ndarray:   # :65-69
-        # (a bounded upload's x_slack ends with the bound slacks w, behind the `ub` slacks)
-        return np.array(x_slack[: x_slack.shape[0] - self._n_slack - self.n_bounded()])
+        # (a bounded upload's x_slack ends with the bound slacks w, behind the `ub` slacks; general bounds: then x^-)
+        return np.array(x_slack[: x_slack.shape[0] - self._tail()])
 
     def denormalize_duals(self, y: np.ndarray, z: np.ndarray):
         """The counterpart of denormalize_x_into for the duals of the slack form (Context.duals): the rows split as
@@ -193,17 +212,17 @@ class Problem:
         `eq` rows), z cut to the structural columns.  -> (y_ub, y_eq, reduced_costs)"""
         y, z = np.asarray(y), np.asarray(z)
         ns, nb = self._n_slack, self.n_bounded()      # (a bounded upload: the bound rows and their slack columns come last)
-        return np.array(y[:ns]), np.array(y[ns: y.shape[0] - nb]), np.array(z[: z.shape[0] - ns - nb])
+        return np.array(y[:ns]), np.array(y[ns: y.shape[0] - nb]), np.array(z[: z.shape[0] - self._tail()])
 
     def denormalize_bound_duals(self, z: np.ndarray) -> np.ndarray:
         """The multipliers v_j >= 0 of the bounds x_j <= u_j per structural column (0 where there is no bound), from the z
         of a bounded upload (Context.duals): the reduced costs of the bound slacks, which are its last entries.  The bound
         row's own multiplier is y_b = -v up to the dual residual, and d fun / d u_j = -v_j."""
         z = np.asarray(z)
-        nb = self.n_bounded()
-        v = np.zeros(z.shape[0] - self._n_slack - nb)
+        nb, nf = self.n_bounded(), self.n_free()      # (general bounds: the negative parts' z^- come behind v)
+        v = np.zeros(z.shape[0] - self._tail())
         if nb:
-            v[self._bounded] = z[z.shape[0] - nb:]
+            v[self._bounded] = z[z.shape[0] - nf - nb: z.shape[0] - nf]
         return v
 
     def denormalize_certificate(self, y, col, kind: int):
@@ -216,7 +235,7 @@ class Problem:
         if kind == _capi.CERT_NONE:
             return None, None, None
         col = np.asarray(col)
-        cut = np.array(col[: col.shape[0] - ns - nb])
+        cut = np.array(col[: col.shape[0] - self._tail()])
         if kind == _capi.CERT_RAY:
             return None, None, cut
         y = np.asarray(y)
@@ -243,11 +262,21 @@ class ProblemBuilder:
         self._ub = None
         self._eq = None
         self._upper = None
+        self._lower = None
 
     def upper(self, u) -> "ProblemBuilder":
         """Upper bounds x_j <= u_j on the structural columns: one entry per column, +inf (np.inf) where there is none.
-        The solves then run the bounded form (lpipm_upload_bounded): the normal matrix keeps its order."""
+        The solves then run the bounded form (lpipm_upload_bounded): the normal matrix keeps its order.  Beside .lower a
+        column may have an upper end only (lower -inf)."""
         self._upper = u
+        return self
+
+    def lower(self, l) -> "ProblemBuilder":
+        """Lower bounds l_j <= x_j on the structural columns: one entry per column, -inf (-np.inf) where there is none;
+        without this call every lower bound is 0.  A column with neither end is free.  The solves run lpipm_upload_bounds:
+        shifts, reflections and free columns are handled in the vector stage, the normal matrix keeps its order and no
+        column is stored twice; x, fun, the duals and the certificates come back in these variables."""
+        self._lower = l
         return self
 
     def ub(self, A, b) -> "ProblemBuilder":      # :93-96
@@ -278,13 +307,21 @@ class ProblemBuilder:
             raise IncompatibleInputDimensions()
         b = np.concatenate([b_ub, b_eq])                                     # :157-158
         cs = np.concatenate([c, np.zeros(m_ub)])                             # :159-160
-        if self._upper is not None:          # (f64 whatever the arrays' type: the bounded form has no f32 arm)
-            upper = _f64(self._upper)
+        if self._upper is not None or self._lower is not None:   # (f64 whatever the arrays' type: the bounded forms have no f32 arm)
+            upper = _f64(self._upper) if self._upper is not None else np.full(n, np.inf)
             if upper.shape != (n,):
                 raise IncompatibleInputDimensions()
             if np.isnan(upper).any() or (upper == -np.inf).any():
                 raise InvalidParameter("upper: NaN or -inf")
-            return Problem(None, b, cs, 0.0, m_ub, parts=(A_ub, b_ub, A_eq, b_eq, c), upper=np.array(upper))
+            lower = None
+            if self._lower is not None:
+                lower = _f64(self._lower)
+                if lower.shape != (n,):
+                    raise IncompatibleInputDimensions()
+                if np.isnan(lower).any() or (lower == np.inf).any():
+                    raise InvalidParameter("lower: NaN or +inf")
+                lower = np.array(lower)
+            return Problem(None, b, cs, 0.0, m_ub, parts=(A_ub, b_ub, A_eq, b_eq, c), upper=np.array(upper), lower=lower)
         if f32:     # Problem<f32>: the f32 values as given (exactly representable in the f64 working copies above)
             t = np.float32
             return Problem(None, b.astype(t), cs.astype(t), 0.0, m_ub,
@@ -493,8 +530,21 @@ class Context:
         them than columns; the solves then factor the n x n reduced system instead of the m x m normal matrix.  (A Problem
         that has `eq` rows as well: upload_tall_eq.)"""
         bounded = getattr(problem, "_upper", None) is not None and problem.n_bounded() > 0
-        if tall and bounded:
-            raise ValueError("tall=True does not take upper bounds: on a tall form a bound is one more `ub` row")
+        lower = getattr(problem, "_lower", None)
+        general = lower is not None and bool(np.any(lower != 0.0))       # some lower end is not 0 (-inf included)
+        if tall and (bounded or general):
+            raise ValueError("tall=True does not take column bounds: on a tall form a bound is one more `ub` row")
+        if general:
+            # general bounds (lpipm_upload_bounds): x_slack = [x in the caller's variables; `ub` slacks; bound slacks; x^-]
+            A_ub, b_ub, A_eq, b_eq, c = (_f64(a) for a in problem._parts)
+            lower, upper = _f64(lower), _f64(problem._upper)
+            m_ub, m_eq, n, nb, nf = A_ub.shape[0], A_eq.shape[0], c.shape[0], problem.n_bounded(), problem.n_free()
+            rc = _capi.lib().lpipm_upload_bounds(self._h, n, m_ub, _p(A_ub) if m_ub else None, n, _p(b_ub) if m_ub else None,
+                                                 m_eq, _p(A_eq) if m_eq else None, n, _p(b_eq) if m_eq else None,
+                                                 _p(c), float(problem.c0()), _p(lower), _p(upper))
+            _raise_for(rc)
+            self.m, self.n, self._m_eq, self._members = m_ub + m_eq + nb, n + m_ub + nb + nf, 0, 1
+            return self
         if bounded:
             # the bounded form (lpipm_upload_bounded): x_slack = [x; `ub` slacks; bound slacks], y = [y_ub; y_eq; y_bounds]
             A_ub, b_ub, A_eq, b_eq, c = (_f64(a) for a in problem._parts)

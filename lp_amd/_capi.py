@@ -77,6 +77,7 @@ SYMBOLS = {
     "lpipm_upload_ub_tall": (C.c_int, [_vp, _u64, _u64, _dp, _u64, _dp, _dp, C.c_double]),
     "lpipm_upload_ub_eq_tall": (C.c_int, [_vp, _u64, _u64, _dp, _u64, _dp, _u64, _dp, _u64, _dp, _dp, C.c_double]),
     "lpipm_upload_bounded": (C.c_int, [_vp, _u64, _u64, _dp, _u64, _dp, _u64, _dp, _u64, _dp, _dp, C.c_double, _dp]),
+    "lpipm_upload_bounds": (C.c_int, [_vp, _u64, _u64, _dp, _u64, _dp, _u64, _dp, _u64, _dp, _dp, C.c_double, _dp, _dp]),
     "lpipm_update_vectors": (C.c_int, [_vp, _dp, _dp]),
     "lpipm_update_lockstep_vectors": (C.c_int, [_vp, _u64, _dpp, _dpp, _dp]),
     "lpipm_update_lockstep_vectors_device": (C.c_int, [_vp, _u64, _vp, _u64, _vp, _u64, _dp]),

@@ -21,6 +21,14 @@
 // the LPs of the launch: bbatch moves the VecArgs, the BoxArgs and the right-hand sides to the member and skips a finished
 // one, as vbatch and tbatch do; the index lists are the upload's and are moved with the member's arena like everything else.
 // The kernels of the speculatively enqueued head test the done word.
+//
+// General column bounds (lpipm_upload_bounds) run the same kernels on the primed LP x_j = t_j + sigma_j x'_j,
+//   A_ext = [[A', 0, -A'_F], [E_B, I, 0]],   x_ext = [x'; w; x^-],   z_ext = [z; v; z^-]   (a.n = na + nb + nf),
+// with one more column x^- per free column j of F (disjoint from B).  On F, with dm = x^- / z^-,
+//   D~_j = dx_j + dm_j,  W_j = dx_j r1_x,j - dm_j r1_m,j,  u_x,j = dx_j (t_j - r1_x,j),  u_m,j = dm_j (-t_j - r1_m,j),
+// u_m from its own line.  The free block is never stored and never multiplied: a pass over A' reads the NET vector
+// (k_box_net: x'_j - x^-_j on F) and the x^- column of A_ext^T.v is -(A'^T.v_1)_j.  Shifts and reflections happen at upload
+// (k_box_reflect, the pass A.t) and on the way out (k_box_caller_units); with nf == 0 no kernel here takes an F branch.
 #include "vec_kernels.hpp"
 #include "vec_device.hpp"
 
@@ -35,6 +43,8 @@ __device__ __forceinline__ bool bbatch(VecArgs& a, BoxArgs& bx, BoxRhs& r) {
     bx.bidx = batch_ptr(bx.bidx, bk); bx.binv = batch_ptr(bx.binv, bk);
     bx.Dt = batch_ptr(bx.Dt, bk); bx.Rx = batch_ptr(bx.Rx, bk); bx.Rw = batch_ptr(bx.Rw, bk);
     bx.Wb = batch_ptr(bx.Wb, bk); bx.Rs = batch_ptr(bx.Rs, bk);
+    bx.fidx = batch_ptr(bx.fidx, bk); bx.finv = batch_ptr(bx.finv, bk); bx.Xn = batch_ptr(bx.Xn, bk);
+    bx.Sg = batch_ptr(bx.Sg, bk); bx.Tj = batch_ptr(bx.Tj, bk);
     r.r1a = batch_ptr(r.r1a, bk); r.r2a = batch_ptr(r.r2a, bk); r.r1b = batch_ptr(r.r1b, bk); r.r2b = batch_ptr(r.r2b, bk);
     return true;
 }
@@ -49,6 +59,15 @@ __global__ __launch_bounds__(256) void k_box_setup(VecArgs a, BoxArgs bx, int wi
     const int stride = gridDim.x * 256;
     for (int j = blockIdx.x * 256 + threadIdx.x; j < bx.na; j += stride) {
         const int k = bx.binv[j];
+        const int kf = bx.nf > 0 ? bx.finv[j] : -1;
+        if (kf >= 0) {       // a free column: D~ = dx + dm, W = dx r1_x - dm r1_m (a.dinv holds x / z throughout the iteration)
+            const int jm = bx.na + bx.nb + kf;
+            const double dx = a.dinv[j], dm = a.dinv[jm];
+            if (with_scales) bx.Dt[j] = dx + dm;
+            if (nrhs > 0) bx.Wb[j] = dx * r1a[j] - dm * r1a[jm];
+            if (nrhs > 1) bx.Wb[bx.nps + j] = dx * r1b[j] - dm * r1b[jm];
+            continue;
+        }
         double dt, rx = 0.0;
         if (with_scales) {
             const double dx = a.dinv[j];
@@ -125,6 +144,17 @@ __global__ __launch_bounds__(256) void k_box_pq_uv(VecArgs a, BoxArgs bx, BoxRhs
             acc[2] += bw * P.v2;
             acc[3] += bw * U.v2;
             nan |= (P.uw != P.uw) | (P.v2 != P.v2);
+        } else if (bx.nf > 0 && bx.finv[j] >= 0) {      // free: u_x = dx (t - r1_x), u_m = dm (-t - r1_m), each from its own line
+            const int jm = bx.na + bx.nb + bx.finv[j];
+            const double dx = a.dinv[j], dm = a.dinv[jm], cm = a.c[jm];
+            const double pm = dm * (-atq - r1a[jm]), um = dm * (-atv - r1b[jm]);
+            p = dx * (atq - r1a[j]);
+            u = dx * (atv - r1b[j]);
+            a.p[jm] = pm;
+            a.u[jm] = um;
+            acc[0] += cm * pm;
+            acc[1] += cm * um;
+            nan |= (pm != pm);      // (the check is on p and q, as everywhere: newton_equations.rs:190-194)
         } else {
             p = dt * (atq - r1a[j]);
             u = dt * (atv - r1b[j]);
@@ -167,6 +197,12 @@ __global__ __launch_bounds__(256) void k_box_uv_corr(VecArgs a, BoxArgs bx, BoxR
             a.R[iw] = U.v2;
             acc[0] += a.c[jw] * U.uw;
             acc[1] += a.b[iw] * U.v2;
+        } else if (bx.nf > 0 && bx.finv[j] >= 0) {
+            const int jm = bx.na + bx.nb + bx.finv[j];
+            const double um = a.dinv[jm] * (-atv - r1a[jm]);
+            u = a.dinv[j] * (atv - r1a[j]);
+            a.u[jm] = um;
+            acc[0] += a.c[jm] * um;
         } else u = dt * (atv - r1a[j]);
         a.u[j] = u;
         acc[0] += a.c[j] * u;
@@ -216,7 +252,12 @@ __global__ __launch_bounds__(256) void k_box_residuals(VecArgs a, BoxArgs bx) {
             for (int s = 0; s < a.nsplit; ++s) aty += a.ATpart[(long long)s * bx.nps + j];
             const int k = bx.binv[j];
             if (k >= 0) aty += a.y[bx.ma + k];
-        } else aty = a.y[bx.ma + j - bx.na];
+        } else if (j < bx.na + bx.nb) aty = a.y[bx.ma + j - bx.na];
+        else {               // the x^- column of free column f: A_ext's column is -a'_f (c[j] holds -c'_f)
+            const int f = bx.fidx[j - bx.na - bx.nb];
+            for (int s = 0; s < a.nsplit; ++s) aty += a.ATpart[(long long)s * bx.nps + f];
+            aty = -aty;
+        }
         const double xj = a.x[j], zj = a.z[j], cj = a.c[j];
         const double r = cj * tau - aty - zj;
         a.rD[j] = r;
@@ -240,7 +281,7 @@ __global__ __launch_bounds__(256) void k_box_products(VecArgs a, BoxArgs bx, Box
     const BatchK bk{a.bstride, nullptr, 0, a.bfirst};
     q.w = batch_ptr(q.w, bk); q.AxPart = batch_ptr(q.AxPart, bk); q.Aw = batch_ptr(q.Aw, bk);
     q.v = batch_ptr(q.v, bk); q.ATpart = batch_ptr(q.ATpart, bk); q.ATv = batch_ptr(q.ATv, bk);
-    bx.bidx = batch_ptr(bx.bidx, bk); bx.binv = batch_ptr(bx.binv, bk);
+    bx.bidx = batch_ptr(bx.bidx, bk); bx.binv = batch_ptr(bx.binv, bk); bx.fidx = batch_ptr(bx.fidx, bk);
     const int stride = gridDim.x * 256;
     if (q.Aw)
         for (int i = blockIdx.x * 256 + threadIdx.x; i < a.m; i += stride) {
@@ -261,7 +302,12 @@ __global__ __launch_bounds__(256) void k_box_products(VecArgs a, BoxArgs bx, Box
                 for (int sp = 0; sp < a.nsplit; ++sp) s += q.ATpart[(long long)sp * q.slab_stride + j];
                 const int k = bx.binv[j];
                 if (k >= 0) s += q.v[bx.ma + k];
-            } else s = q.v[bx.ma + j - bx.na];
+            } else if (j < bx.na + bx.nb) s = q.v[bx.ma + j - bx.na];
+            else {
+                const int f = bx.fidx[j - bx.na - bx.nb];
+                for (int sp = 0; sp < a.nsplit; ++sp) s += q.ATpart[(long long)sp * q.slab_stride + f];
+                s = -s;
+            }
             q.ATv[j] = s;
         }
 }
@@ -273,13 +319,74 @@ void box_products(const VecArgs& a, const BoxArgs& bx, const BoxProducts& q, hip
 // exactly 1 (and unstored); u_j <- ldexp(u_j, -kc[j]) then follows from the scaling of b_ext by kr.
 __global__ __launch_bounds__(256) void k_box_exponents(BoxArgs bx, int32_t* __restrict__ kr, int32_t* __restrict__ kc) {
     const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= bx.nb) return;
-    const int e = kc[bx.bidx[k]];
-    kr[bx.ma + k] = -e;
-    kc[bx.na + k] = e;
+    if (k < bx.nb) {
+        const int e = kc[bx.bidx[k]];
+        kr[bx.ma + k] = -e;
+        kc[bx.na + k] = e;
+    }
+    if (k < bx.nf) kc[bx.na + bx.nb + k] = kc[bx.fidx[k]];     // the x^- column is its column's negative: the same exponent
 }
 void box_exponents(const BoxArgs& bx, int32_t* kr, int32_t* kc, hipStream_t st) {
-    if (bx.nb > 0) hipLaunchKernelGGL(k_box_exponents, dim3((bx.nb + 255) / 256), dim3(256), 0, st, bx, kr, kc);
+    const int most = bx.nb > bx.nf ? bx.nb : bx.nf;
+    if (most > 0) hipLaunchKernelGGL(k_box_exponents, dim3((most + 255) / 256), dim3(256), 0, st, bx, kr, kc);
+}
+
+// ---------------------------------------------------------------- general bounds: net vectors, reflection, caller's variables
+// The net vector of `rows` extended rows: what a pass over A reads where the explicit form would read [x'; x^-] against
+// [A', -A'_F].  check_done: the launch belongs to an iteration (the residual pair's).
+__global__ __launch_bounds__(256) void k_box_net(VecArgs a, BoxArgs bx, const double* src, long long lds, double* dst, long long ldd,
+                                                 int rows, int check_done) {
+    const BatchK bk{a.bstride, check_done ? a.done_chk : nullptr, 0, a.bfirst};
+    if (batch_done(bk)) return;
+    src = batch_ptr(src, bk); dst = batch_ptr(dst, bk); bx.finv = batch_ptr(bx.finv, bk);
+    const int stride = gridDim.x * 256;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < bx.na; j += stride) {
+        const int kf = bx.finv[j];
+        for (int r = 0; r < rows; ++r) {
+            const double* s = src + r * lds;
+            dst[r * ldd + j] = kf >= 0 ? s[j] - s[bx.na + bx.nb + kf] : s[j];
+        }
+    }
+}
+void box_net(const VecArgs& a, const BoxArgs& bx, const double* src, long long lds, double* dst, long long ldd, int rows,
+             bool check_done, hipStream_t st) {
+    hipLaunchKernelGGL(k_box_net, dim3(a.nblk, 1, a.bcount), dim3(256), 0, st, a, bx, src, lds, dst, ldd, rows, check_done ? 1 : 0);
+}
+
+// A' = A.diag(sigma): the stored structural columns of N negated in the resident image (exact), ahead of the equilibration.
+__global__ __launch_bounds__(256) void k_box_reflect(BoxArgs bx, double* __restrict__ A, long long lda, int nx) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= nx || !(bx.Sg[j] < 0.0)) return;
+    for (int i = blockIdx.y; i < bx.ma; i += gridDim.y) A[(long long)i * lda + j] = -A[(long long)i * lda + j];
+}
+void box_reflect(const BoxArgs& bx, double* A, long long lda, int nx, hipStream_t st) {
+    const int gy = bx.ma < 1024 ? bx.ma : 1024;
+    hipLaunchKernelGGL(k_box_reflect, dim3((nx + 255) / 256, gy), dim3(256), 0, st, bx, A, lda, nx);
+}
+
+// One output row of a.n extended entries into the caller's variables, in place (see BOX_OUT_*), one LP.  Only the structural
+// entries change: sigma is +1 and t is 0 on every `ub` slack column, and w, x^- keep their places.
+__global__ __launch_bounds__(256) void k_box_caller_units(VecArgs a, BoxArgs bx, double* row, int mode) {
+    const BatchK bk{a.bstride, nullptr, 0, a.bfirst};
+    bx.finv = batch_ptr(bx.finv, bk); bx.Sg = batch_ptr(bx.Sg, bk); bx.Tj = batch_ptr(bx.Tj, bk);
+    if (mode == BOX_OUT_CERT) {
+        const int kind = (int)batch_ptr(a.red, bk)[2 * RED_STRIDE + 1];
+        if (kind == 0) return;
+        mode = kind == 1 ? BOX_OUT_Z : BOX_OUT_RAY;
+    }
+    const int stride = gridDim.x * 256;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < bx.na; j += stride) {
+        const double sg = bx.Sg[j], v = row[j];
+        const int kf = bx.nf > 0 ? bx.finv[j] : -1;
+        if (mode == BOX_OUT_Z) row[j] = sg * v;
+        else {
+            const double net = kf >= 0 ? v - row[bx.na + bx.nb + kf] : sg * v;
+            row[j] = mode == BOX_OUT_X ? bx.Tj[j] + net : net;
+        }
+    }
+}
+void box_caller_units(const VecArgs& a, const BoxArgs& bx, double* row, int mode, hipStream_t st) {
+    hipLaunchKernelGGL(k_box_caller_units, dim3(a.nblk, 1, 1), dim3(256), 0, st, a, bx, row, mode);
 }
 
 }  // namespace lpipm

@@ -73,6 +73,8 @@ struct Geometry {
     int mpv = 0, npv = 0;        // the paddings of the row and column VECTORS: mp and np, but on the bounded form those of m + nb and n + nb
     int nbp = 0;                 // bounded form only: the bounded columns padded to 256 (what the index lists and ratio vectors are sized by)
     bool box = false;
+    int nfp = 0;                 // general bounds only: the free columns padded to 256 (their index list)
+    bool gen = false;            // general bounds (lpipm_upload_bounds): the arena holds sigma, t and the free columns' lists and net vector
     bool shared = false, keep = false, tall = false, tall_eq = false;
     int coupled = 0;             // the factor plans lay out the coupled sweep (coupled_for)
     bool operator==(const Geometry&) const = default;
@@ -577,6 +579,15 @@ struct Upload {
     const int *bidx = nullptr, *binv = nullptr;
     const double* ub = nullptr;
     bool upper_bad = false;              // an upper[j] that is NaN or -inf: refused behind the shape
+    // lpipm_upload_bounds: the bounded request in the primed variables x_j = t_j + sigma_j x'_j (ub = upper - lower, c = sigma c,
+    // c0 = c0 + c.t are the caller's host arrays already), with nf free columns fidx (ascending; finv: n entries) that are not in
+    // bidx, sigma and tshift (n entries each: +1 and 0 on the slack columns) and cminus (-c'_j of the free columns, nf entries).
+    bool gen = false;
+    uint64_t nf = 0;
+    const int *fidx = nullptr, *finv = nullptr;
+    const double *sigma = nullptr, *tshift = nullptr, *cminus = nullptr;
+    bool reflects = false, shifts = false;   // some sigma_j is -1; some t_j is not zero
+    int bounds_code = LPIPM_OK;          // what the bounds themselves are refused with, behind the shape
     // lpipm_upload_device: A, b and c are in DEVICE memory, laid out as this descriptor says.  The request is otherwise the
     // equivalent host entry's; its pointers above stand for "given" / "null" only (check_upload) and are never read through.
     const lpipm_device_problem* dev = nullptr;
@@ -607,6 +618,7 @@ static int check_upload(const lpipm_ctx* c, const Upload& u) {
         if (u.tall_eq && q.m_ub == 0) return LPIPM_ERR_UNSUPPORTED;     // no `ub` row: not a tall LP (lpipm_upload_ub_eq is its entry)
         if (u.tall && (c->world > 1 || c->refine > 0)) return LPIPM_ERR_UNSUPPORTED;   // a column-split context; the refined solves
         if (u.upper_bad) return LPIPM_ERR_BAD_ARGUMENT;
+        if (u.bounds_code != LPIPM_OK) return u.bounds_code;
         if (u.box && (c->world > 1 || c->refine > 0)) return LPIPM_ERR_UNSUPPORTED;    // likewise
         for (uint64_t i = 0; i < u.count; ++i)
             if (!u.c[i] || (u.b && !u.b[i]) || (u.owned && !u.A[i])) return LPIPM_ERR_BAD_ARGUMENT;
@@ -622,7 +634,8 @@ static Geometry geometry_of(const Upload& u, uint64_t n_slack, bool first_cache,
     g.B = (int)u.count; g.nsplit = g.mp / GEMVT_ROWS;
     g.mpv = g.mp; g.npv = g.np;
     if (u.box) {     // the system's order, R, Y and the slab count follow m; the row and column vectors follow m + nb and n + nb
-        g.box = true; g.mpv = (int)round_up(u.m + u.nb, NB); g.npv = (int)round_up(u.n + u.nb, BK); g.nbp = (int)round_up(u.nb, BK);
+        g.box = true; g.mpv = (int)round_up(u.m + u.nb, NB); g.npv = (int)round_up(u.n + u.nb + u.nf, BK); g.nbp = (int)round_up(u.nb, BK);
+        g.gen = u.gen; g.nfp = (int)round_up(u.nf, BK);      // (general bounds: the x^- columns lengthen the column vectors only)
     }
     g.nblk = ((g.mpv > g.npv ? g.mpv : g.npv) + 255) / 256;  // (of the larger of m and n: 256 is a multiple of both paddings)
     if (g.nblk > RED_STRIDE) g.nblk = RED_STRIDE;
@@ -685,6 +698,10 @@ static void layout_vectors(Problem& p, Arena& ar) {
         bx.Dt = ar.take<double>(nps); bx.Rx = ar.take<double>(nbp); bx.Rw = ar.take<double>(nbp);
         bx.Wb = ar.take<double>(2 * nps); bx.Rs = ar.take<double>(2 * mps);
         p.solW = bx.Wb; p.solR = bx.Rs;
+        if (p.geo.gen) {     // general bounds: sigma and t, and with free columns their lists and the net vector -- O(n + nf)
+            bx.Sg = ar.take<double>(nps); bx.Tj = ar.take<double>(nps);
+            if (p.geo.nfp > 0) { bx.fidx = ar.take<int>((size_t)p.geo.nfp); bx.finv = ar.take<int>(nps); bx.Xn = ar.take<double>(nps); }
+        }
     }
     v.S = ar.take<double>(64); v.red = ar.take<double>((size_t)RED_SLOTS * RED_STRIDE);
     v.status = ar.take<StatusRec>(1); v.potrf_info = ar.take<int32_t>(1);
@@ -886,6 +903,15 @@ static int copy_in(lpipm_ctx* c, const Upload& u, const double* c0v) {
         LP_HIP(hipMemcpyAsync((void*)p.bx.bidx, u.bidx, u.nb * sizeof(int), hipMemcpyHostToDevice, st));
         LP_HIP(hipMemcpyAsync((void*)p.bx.binv, u.binv, u.n * sizeof(int), hipMemcpyHostToDevice, st));
     }
+    if (u.gen) {     // sigma and t (caller's units); c_ext = [c'; 0; -c'_F] and the free columns' lists
+        LP_HIP(vec(p.bx.Sg, u.sigma, u.n));
+        LP_HIP(vec(p.bx.Tj, u.tshift, u.n));
+        if (u.nf) {
+            LP_HIP(vec(p.va.c + u.n + u.nb, u.cminus, u.nf));
+            LP_HIP(hipMemcpyAsync((void*)p.bx.fidx, u.fidx, u.nf * sizeof(int), hipMemcpyHostToDevice, st));
+            LP_HIP(hipMemcpyAsync((void*)p.bx.finv, u.finv, u.n * sizeof(int), hipMemcpyHostToDevice, st));
+        }
+    }
     return LPIPM_OK;
 }
 // ---- a request whose sources are in device memory (Upload::dev) ----
@@ -1009,8 +1035,8 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
     const int count = g.B;
     LP_TRY(scale_setup(c, g.mpv, g.npv, g.npa, u.shared ? 1 : count));      // (exponents per row and column of the vectors' lengths)
     p.ma = u.m; p.na = u.n; p.nb = (int)u.nb;
-    p.m = u.m + u.nb; p.n = u.n + u.nb; p.ns = (int)n_slack; p.nx = (int)nx;
-    if (u.box) { p.bx.nb = (int)u.nb; p.bx.na = (int)u.n; p.bx.ma = (int)u.m; }
+    p.m = u.m + u.nb; p.n = u.n + u.nb + u.nf; p.ns = (int)n_slack; p.nx = (int)nx;
+    if (u.box) { p.bx.nb = (int)u.nb; p.bx.na = (int)u.n; p.bx.ma = (int)u.m; p.bx.nf = (int)u.nf; p.bx.gen = u.gen ? 1 : 0; }
     if (u.tall) p.tv.nx = (int)nx;            // (the padded geometry may be shared by several nx)
     const uint64_t m_ub = u.parts ? u.parts->m_ub : 0;
     p.me = u.tall_eq ? (int)u.me : 0;
@@ -1031,6 +1057,13 @@ static int upload_impl(lpipm_ctx* c, const Upload& u) {
     for (int i = 0; i < count && u.tall_eq; ++i)     // the dinv of S = Zt.Zt^T (every member's own: launch_adat moves dinv with the member)
         LP_HIP(hipMemcpyAsync((char*)p.ones_k + (size_t)i * p.bstride, onesv.data(), onesv.size() * sizeof(double), hipMemcpyHostToDevice, st));
     LP_TRY(u.dev ? copy_in_device(c, u, c0v.data()) : copy_in(c, u, c0v.data()));
+    // general bounds, on the unscaled image: b' = b - A.t by the pass over A (t is zero on the slack columns, so their block adds
+    // nothing), then A' = A.diag(sigma).  Both ahead of the equilibration: the exponents are those of A'.
+    if (u.gen && u.shifts) {
+        LP_HIP(launch_gemv_n(p.A, p.npa, (int)u.m, p.npa, 1, p.bx.Tj, p.np, p.va.b, nullptr, p.Y, p.mp, st, -1.0, Batch{}, false));
+        LP_HIP(hipMemcpyAsync((void*)p.va.b, p.Y, u.m * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    if (u.gen && u.reflects) { box_reflect(p.bx, p.A, p.npa, (int)nx, st); LP_HIP(hipGetLastError()); }
     if (p.scale_passes > 0) {   // equilibrate what was just copied: the solves see the scaled problem only
         const Batch members{count, (long long)p.bstride, nullptr, 0};
         LP_HIP(launch_equilibrate(p.sc, p.A, (int)u.m, g.mp, (int)nx, g.npa, (int)n_slack, p.scale_passes, st,
@@ -1087,6 +1120,55 @@ extern "C" int lpipm_upload_bounded(lpipm_ctx* c, uint64_t n, uint64_t m_ub, con
     Upload u{.m = m_ub + m_eq, .n = n + m_ub, .n_slack = m_ub,
              .parts = UploadParts{m_ub, A_ub, lda_ub, b_ub, A_eq, lda_eq, b_eq}, .c = &cc, .c0 = &c0, .keep_ok = false};
     u.box = !bad; u.nb = bad ? 0 : bidx.size(); u.bidx = bidx.data(); u.binv = binv.data(); u.ub = ub.data(); u.upper_bad = bad;
+    return upload_impl(c, u);
+}
+// lpipm_upload_ub_eq's LP with lower_j <= x_j <= upper_j on its structural columns.  Per column: a finite lower
+// end is a shift t_j = lower_j (with a finite upper end: the bounded form's column, u'_j = upper_j - lower_j); only an upper end
+// is the reflection x_j = upper_j - x'_j; neither is a free column, x_j = x'_j - x^-_j, which keeps ONE stored column.  What
+// goes resident is the primed LP (c' = sigma c and c0' = c0 + c.t from here; b' = b - A.t and A' = A.diag(sigma) by upload_impl
+// on the device).  With no free column, no reflection and no shift this is lpipm_upload_bounded's request itself.
+extern "C" int lpipm_upload_bounds(lpipm_ctx* c, uint64_t n, uint64_t m_ub, const double* A_ub, uint64_t lda_ub,
+                                   const double* b_ub, uint64_t m_eq, const double* A_eq, uint64_t lda_eq,
+                                   const double* b_eq, const double* cc, double c0, const double* lower, const double* upper) {
+    std::vector<int> bidx, binv, fidx, finv;
+    std::vector<double> ub, sigma, tshift, cprime, cminus;
+    int code = LPIPM_OK;
+    double c0p = c0;                                              // c0' = c0 + c.t
+    bool reflects = false, shifts = false;
+    // (else check_upload refuses the request, by its shape or its null c, before anything is sized or read)
+    const bool sized = n <= (1u << 24) && m_ub <= (1u << 20) && cc != nullptr;
+    if (sized) {
+        const size_t na = (size_t)(n + m_ub);
+        binv.assign(na, -1); finv.assign(na, -1); sigma.assign(na, 1.0); tshift.assign(na, 0.0); cprime.assign((size_t)n, 0.0);
+        bool crossed = false;
+        for (uint64_t j = 0; j < n && code == LPIPM_OK; ++j) {
+            const double lj = lower ? lower[j] : 0.0, uj = upper ? upper[j] : INFINITY;
+            if (lj != lj || uj != uj || (std::isinf(lj) && lj > 0.0) || (std::isinf(uj) && uj < 0.0)) { code = LPIPM_ERR_BAD_ARGUMENT; break; }
+            if (lj > uj) crossed = true;
+            const bool has_l = !std::isinf(lj), has_u = !std::isinf(uj);
+            if (has_l) {
+                tshift[(size_t)j] = lj;
+                if (has_u) { binv[(size_t)j] = (int)bidx.size(); bidx.push_back((int)j); ub.push_back(uj - lj); }
+            } else if (has_u) { sigma[(size_t)j] = -1.0; tshift[(size_t)j] = uj; reflects = true; }
+            else { finv[(size_t)j] = (int)fidx.size(); fidx.push_back((int)j); }
+            shifts = shifts || tshift[(size_t)j] != 0.0;
+            cprime[(size_t)j] = sigma[(size_t)j] * cc[j];
+            c0p += cc[j] * tshift[(size_t)j];
+        }
+        if (code == LPIPM_OK && crossed) code = LPIPM_INFEASIBLE;     // lower_j > upper_j: no point satisfies the bounds
+        if (code == LPIPM_OK && fidx.empty() && !reflects && !shifts)
+            return lpipm_upload_bounded(c, n, m_ub, A_ub, lda_ub, b_ub, m_eq, A_eq, lda_eq, b_eq, cc, c0, upper);
+        for (int j : fidx) cminus.push_back(-cprime[(size_t)j]);
+    }
+    const double* cp = sized && code == LPIPM_OK ? cprime.data() : cc;
+    Upload u{.m = m_ub + m_eq, .n = n + m_ub, .n_slack = m_ub,
+             .parts = UploadParts{m_ub, A_ub, lda_ub, b_ub, A_eq, lda_eq, b_eq}, .c = &cp, .c0 = &c0p, .keep_ok = false};
+    u.bounds_code = code;
+    if (sized && code == LPIPM_OK) {
+        u.box = u.gen = true; u.nb = bidx.size(); u.bidx = bidx.data(); u.binv = binv.data(); u.ub = ub.data();
+        u.nf = fidx.size(); u.fidx = fidx.data(); u.finv = finv.data();
+        u.sigma = sigma.data(); u.tshift = tshift.data(); u.cminus = cminus.data(); u.reflects = reflects; u.shifts = shifts;
+    }
     return upload_impl(c, u);
 }
 // The request of one tall LP (cc, c0: one entry each).
@@ -1407,7 +1489,12 @@ static int enqueue_residuals(lpipm_ctx* c, int is_init, int ip_next, double tol)
     XRank xr{xrank_fn, c};
     if (!(c->colsplit && c->world > 1)) {       // both products in one read of A
         v.ax_chunks = gemv_dual_chunks(c->p.npa);
-        LP_HIP(ctx_gemv_dual(c, v.x, v.y, v.Ax, c->p.bt));
+        const double* x_in = v.x;
+        if (c->p.box && c->p.bx.nf > 0) {       // free columns: the pass reads the net vector x' - x^- (the only change to its input)
+            box_net(v, c->p.bx, v.x, 0, c->p.bx.Xn, 0, 1, true, c->rs.st);
+            x_in = c->p.bx.Xn;
+        }
+        LP_HIP(ctx_gemv_dual(c, x_in, v.y, v.Ax, c->p.bt));
     } else {
         v.ax_chunks = 1;
         LP_HIP(ctx_gemv_n(c, 1, v.x, nullptr, nullptr, v.Ax, c->p.bt));
@@ -1796,6 +1883,10 @@ static int copy_out_x(lpipm_ctx* c, const SolveMode& md, const std::vector<int>&
     LP_HIP(hipGetLastError());
     if (c->p.scale_passes > 0)          // (fun is the scaled vectors' product: the same number)
         LP_HIP(launch_unscale_x(c->p.sc, c->p.xout, (int)c->p.n, st, Batch{c->p.B, (long long)c->p.bstride, nullptr, c->p.bt.first}));
+    if (c->p.box && c->p.bx.gen) {      // general bounds: the structural values in the caller's variables (fun already is: c0 holds c.t)
+        box_caller_units(c->p.va, c->p.bx, c->p.xout, BOX_OUT_X, st);
+        LP_HIP(hipGetLastError());
+    }
     const size_t xbytes = c->p.n * sizeof(double);
     for (int i = 0; i < c->p.B; ++i) {
         if (!has_x(ret[(size_t)i])) continue;
@@ -2531,6 +2622,7 @@ static int run_duals(lpipm_ctx* c, size_t row0, size_t rows, bool want_y, bool w
     d.z = stage_z ? dev + ninfo + ny : z_dev; d.ldz = (long long)(stage_z ? n : ldz);
     if (p.scale_passes > 0) { d.kr = p.sc.kr; d.kc = p.sc.kc; d.estride = p.sc.estride; }
     vec_final_duals(p.va, d, st);
+    if (p.box && p.bx.gen && d.z) box_caller_units(p.va, p.bx, d.z, BOX_OUT_Z, st);     // z_j = sigma_j z'_j (one LP: row 0)
     LP_HIP(hipGetLastError());
     LP_HIP(hipMemcpyAsync(c->stage_host + nmask, dev, (ninfo + ny + nz) * sizeof(double), hipMemcpyDeviceToHost, st));
     LP_HIP(hipStreamSynchronize(st));
@@ -2608,7 +2700,12 @@ static int run_certificates(lpipm_ctx* c, size_t row0, size_t rows, bool want_y,
         LP_HIP(hipGetLastError());
         v.ax_chunks = gemv_dual_chunks(p.npa);
         const uint64_t passes = c->gemv_passes;
-        LP_HIP(ctx_gemv_dual(c, v.W, v.dy, v.Ax, Batch{p.bt.count, p.bt.stride, nullptr, p.bt.first}));
+        const double* x_in = v.W;
+        if (p.box && p.bx.nf > 0) {        // free columns: the pass reads the net ray
+            box_net(v, p.bx, v.W, 0, p.bx.Xn, 0, 1, false, st);
+            x_in = p.bx.Xn;
+        }
+        LP_HIP(ctx_gemv_dual(c, x_in, v.dy, v.Ax, Batch{p.bt.count, p.bt.stride, nullptr, p.bt.first}));
         c->gemv_passes = passes;           // (lpipm_phase_times counts a solve's passes)
         if (p.box) {     // the bound block: A_ext^T.y^ into u, A_ext.x^ into q, both whole, which the residual then reads as one slab each
             box_products(v, p.bx, BoxProducts{v.W, v.Ax, v.ax_chunks, v.q, v.dy, p.ATpart, (long long)p.np, v.u}, st);
@@ -2618,6 +2715,8 @@ static int run_certificates(lpipm_ctx* c, size_t row0, size_t rows, bool want_y,
         }
     }
     vec_cert_residual(v, d, st);           // (without a certificate to form: its scalar launch alone has work)
+    // general bounds: z^ or the improving ray in the caller's orientation (sigma applied, the free halves netted; one LP: row 0)
+    if (any && p.box && p.bx.gen && d.col) box_caller_units(v, p.bx, d.col, BOX_OUT_CERT, st);
     LP_HIP(hipGetLastError());
     LP_HIP(hipMemcpyAsync(c->stage_host + nmask, dev, (ninfo + ny + nc) * sizeof(double), hipMemcpyDeviceToHost, st));
     LP_HIP(hipStreamSynchronize(st));
@@ -2961,7 +3060,8 @@ static int box_k_passes(lpipm_ctx* c, int nrhs, const double* w, const double* v
     const size_t n = (size_t)p.n, m = (size_t)p.m, na = (size_t)p.na, ma = (size_t)p.ma;
     if (w) {
         LP_HIP(rows_to_device(va.W, (size_t)va.np, w, n, n, (size_t)nrhs, st));
-        LP_HIP(rows_to_device(bx.Wb, (size_t)bx.nps, w, n, na, (size_t)nrhs, st));
+        if (bx.nf > 0) box_net(va, bx, va.W, va.np, bx.Wb, bx.nps, nrhs, false, st);      // free columns: the pass reads the net rows
+        else LP_HIP(rows_to_device(bx.Wb, (size_t)bx.nps, w, n, na, (size_t)nrhs, st));
     }
     if (v) {
         LP_HIP(hipMemsetAsync(bx.Rs, 0, 2 * (size_t)bx.mps * sizeof(double), st));

@@ -209,6 +209,18 @@ struct BoxArgs {
     double* Rw;              // [nb]     dw / s
     double* Wb;              // [2][nps] W: the input of the pass A.W
     double* Rs;              // [2][mps] r2_1 + A.W, then v_1: in/out of the Cholesky solve, the V of the pass A^T.v
+    // General column bounds (lpipm_upload_bounds): the iteration sees the primed LP x_j = t_j + sigma_j x'_j, with one more
+    // column x^-_j (A_ext column -a'_j, cost -c'_j) per free column j of F: x_ext = [x'; w; x^-], n = na + nb + nf.  On F
+    //   D~_j = dx_j + dm_j,  W_j = dx_j r1_x,j - dm_j r1_m,j,  u_x,j = dx_j (t_j - r1_x,j),  u_m,j = dm_j (-t_j - r1_m,j)
+    // (dm = x^- / z^-), the passes over A read the NET vector (x_j - x^-_j on F), and the x^- column of A_ext^T.v is
+    // -(A^T.v_1)_j.  All zero / null on the bounded form itself.
+    int nf;                  // free columns
+    int gen;                 // a general upload: Sg and Tj are there (a reflection or a shift), and Xn when nf > 0
+    const int* fidx;         // [nf]     the free columns, ascending
+    const int* finv;         // [na]     k where fidx[k] == j, -1 on every other column
+    double* Xn;              // [nps]    the net vector the residual pair's pass over A reads
+    const double* Sg;        // [nps]    sigma_j: -1 on a reflected column, +1 elsewhere (0 in the padding)
+    const double* Tj;        // [nps]    t_j in the caller's units: lower_j, or upper_j on a reflected column; 0 on F and the slacks
 };
 // D~, dx / s and dw / s from the iterate (with_scales: a.dinv holds x / z over all n columns, from k_pred_setup), and W for
 // nrhs (0|1|2) right-hand sides (r1a, r2a), (r1b, r2b): r1 n-sized, r2 m-sized
@@ -229,8 +241,20 @@ struct BoxProducts {
     const double* v = nullptr; const double* ATpart = nullptr; long long slab_stride = 0; double* ATv = nullptr;
 };
 void box_products(const VecArgs& a, const BoxArgs& bx, const BoxProducts& q, hipStream_t st);
-// kr of the bound rows and kc of the bound slack columns from kc of the bounded columns (one exponent set: a single LP)
+// kr of the bound rows and kc of the bound slack columns from kc of the bounded columns (one exponent set: a single LP);
+// the x^- column of a free column takes its column's kc
 void box_exponents(const BoxArgs& bx, int32_t* kr, int32_t* kc, hipStream_t st);
+// General bounds.  box_net: dst[j] = src[j] - src[na + nb + finv[j]] on F, src[j] elsewhere, j < na, for each of `rows` rows
+// (lds, ldd doubles apart): what a pass over A is handed in place of an extended vector.  check_done: the solve's own launch.
+void box_net(const VecArgs& a, const BoxArgs& bx, const double* src, long long lds, double* dst, long long ldd, int rows,
+             bool check_done, hipStream_t st);
+// Upload time, on the unscaled image (lda doubles a row, nx structural columns, ma rows): the columns of N negated.
+void box_reflect(const BoxArgs& bx, double* A, long long lda, int nx, hipStream_t st);
+// An output row of n extended entries into the caller's variables, in place, behind the column unscaling:
+//   BOX_OUT_X: x_j = t_j + sigma_j x'_j (x'_j - x^-_j on F);  BOX_OUT_RAY: the same without t;  BOX_OUT_Z: z_j = sigma_j z'_j;
+//   BOX_OUT_CERT: RAY or Z as the certificate's kind in the reduction block says (nothing without a certificate).
+enum { BOX_OUT_X = 0, BOX_OUT_RAY, BOX_OUT_Z, BOX_OUT_CERT };
+void box_caller_units(const VecArgs& a, const BoxArgs& bx, double* row, int mode, hipStream_t st);
 
 // ---------------------------------------------------------------- device sources (kernels_pack.hip)
 // lpipm_upload_device: the caller's strided device arrays (double or float) into the zeroed resident image.  Strides are in
